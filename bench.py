@@ -6,7 +6,13 @@ over one batch of synthetic 150 bp reads that is already resident in HBM.  Workl
 (SURVEY.md §8d): balanced 1024-leaf SBT over 50 kbp random genomes, k=21, nbits=71 887 936, 10 hashes, fixed
 seeds; reads 50 % positive (uniform leaf / offset / strand, error-free) and 50 % uniform random, theta = 1.0.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+      --dump-outputs DIR: after the timed steps, rank 0 writes what they computed as float64 .npy files —
+      DIR/leaf_counts_last_step.npy (per-genome hits of the last timed step alone) and DIR/leaf_counts.npy (per-genome
+      hits of all K timed steps, what the timed region hands back), both indexed by genome and reduced over the ranks.
+      The inputs are fixed by the arguments (seeded generators), so two builds can be compared output for output.
+      The snapshot of the counters before the last step is one device copy of 8 B per leaf inside the timed region, so
+      a dump run's ms_per_step includes it (microseconds against a step of milliseconds).
       N > 1 without a launcher: this process starts the N ranks itself (torch.distributed.run, one process per GPU,
       before anything touches a GPU) and exits with their status.  Under a launcher (WORLD_SIZE set) it is one rank.
       Every rank holds a replica of the tree and classifies its own shard of the reads (weak scaling, no data-path
@@ -57,7 +63,12 @@ def parse_args():
     ap.add_argument("--hashes", type=int, default=NUM_HASHES, help="scenario runs only: hashes per k-mer")
     ap.add_argument("--subtree-depth", type=int, default=0, help="config 5: shards = nodes of this depth, one per rank (2^D == N)")
     ap.add_argument("--subtree-index", type=int, default=-1, help="N = 1 only: run this one shard of the depth-D frontier")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-genome counts of the last timed step and of all timed steps to DIR/*.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -215,6 +226,9 @@ def main() -> None:
     torch.cuda.synchronize()
     tree.reset_counts()
     counts = torch.zeros(max(n_local, 1), dtype=torch.int64, device=dev)
+    # --dump-outputs: the counters as they stand before the last timed step (8 B per leaf, copied on the launch stream),
+    # so that the last step's own counts are the difference
+    before_last = torch.zeros_like(counts) if args.dump_outputs else None
 
     def barrier() -> None:
         if use_pg:
@@ -229,6 +243,8 @@ def main() -> None:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if before_last is not None and i == args.steps - 1:
+            tree.export_counts(before_last.data_ptr(), stream)
         step(args.warmup + i)
     tree.export_counts(counts.data_ptr(), stream)
     torch.cuda.synchronize()
@@ -252,6 +268,11 @@ def main() -> None:
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         per_rank_s = [float(g.item()) for g in gathered]
+    last_step_counts = None
+    if before_last is not None:  # the last step's own counts, reduced over the ranks like the timed region's
+        # (from local_counts: with read sharding `counts` was all-reduced in place and holds every rank's counts by now)
+        last_local = local_counts - before_last[:n_local]
+        last_step_counts = pad_and_reduce(last_local, first_leaf, n_g) if subtree else all_reduce_counts(last_local)
 
     prof = tree.profile_end()
     st = tree.last_stats()
@@ -409,6 +430,10 @@ def main() -> None:
     bad = torch.tensor([len(problems)], dtype=torch.int64, device=dev)
     if use_pg:
         dist.all_reduce(bad, op=dist.ReduceOp.SUM)
+    if rank == 0 and last_step_counts is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("leaf_counts_last_step", last_step_counts), ("leaf_counts", total_counts)):
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), t[:n_g].cpu().numpy().astype(np.float64))
     if problems:
         print(f"[rank {rank}] bench.py: WRONG RESULTS, no bench line: " + "; ".join(problems), file=sys.stderr, flush=True)
     if rank == 0 and int(bad.item()) == 0:

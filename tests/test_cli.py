@@ -187,7 +187,7 @@ def test_cli_errors_exit_like_a_panic(cli_db, tmp_path):
 
 
 @pytest.mark.gpu
-def test_cli_build_and_add_match_oracle(tmp_path):
+def test_cli_build_and_add_match_oracle(gpu, tmp_path):
     """`phage_filter build` / `add` (main.rs:148-247): same database as the oracle's greedy insertion, record by
     record in input order (directory files from the back of the sorted list), then queryable."""
     import numpy as np
@@ -233,7 +233,7 @@ def test_cli_build_and_add_match_oracle(tmp_path):
 
 
 @pytest.mark.gpu
-def test_cli_accepts_benchmark_harness_invocations(tmp_path):
+def test_cli_accepts_benchmark_harness_invocations(gpu, tmp_path):
     """the exact command lines of benchmarking/bench/tools/phage_filter.py:79-86 (build) and :105-116
     (query), and the two output files its parse_output reads (:41-66) in the way it reads them — including the
     harness's habit of opening POS_FILTERING.fa, which exists only for FASTA reads."""
@@ -377,7 +377,7 @@ def test_cli_block_size_zero_processes_nothing(cli_db, tmp_path):
 # BASELINE config 1 end to end through the CLI's own greedy `build`
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-def test_config1_greedy_build_then_query_examples(tmp_path):
+def test_config1_greedy_build_then_query_examples(gpu, tmp_path):
     """`phage_filter build` on the example genomes with the README's defaults (k = 20, fpr 0.001, largest genome 10^6;
     main.rs:148-200: one leaf per FASTA record, greedy placement) and `phage_filter query` on the example reads: the
     database equals the oracle's restatement of BloomTree::insert record by record, CLASSIFICATION.csv and the POS/NEG
