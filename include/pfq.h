@@ -77,6 +77,12 @@ int pfq_tree_open(const char *db_dir, int device, pfq_tree **out);
  * guard columns, so results equal the reference's whole-tree traversal. */
 int pfq_tree_open_subtree(const char *db_dir, int device, uint64_t depth, uint64_t index, pfq_tree **out);
 
+/* Number of subtree shards of <db_dir> at depth `depth`: the size of the depth-`depth` frontier that
+ * pfq_tree_open_subtree indexes (nodes at that depth, plus leaves above it).  Reads tree.bin only; no .bf file is
+ * read and no device is used.  PFQ_ERR_IO: tree.bin missing or unreadable; PFQ_ERR_FORMAT: it does not parse;
+ * PFQ_ERR_STATE: the tree is empty. */
+int pfq_db_shard_count(const char *db_dir, uint64_t depth, uint64_t *n_shards);
+
 /* The reference's `build` / `add` (main.rs:148-247) on the device.
  * pfq_tree_create = BloomTree::new (bloom_tree.rs:100-118): an empty tree; filter geometry from
  *   (false_pos_rate, largest_expected_genome) exactly like with_rate (bloom_filter.rs:229-240,:342-357, f32 arithmetic);

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("PFQ_LIBPFQ") or os.path.join(_HERE, "libpfq.so")
 
 # every symbol include/pfq.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "pfq_tree_open", "pfq_tree_open_subtree", "pfq_tree_create", "pfq_tree_insert", "pfq_tree_build_balanced", "pfq_tree_build_balanced_device",
+    "pfq_tree_open", "pfq_tree_open_subtree", "pfq_db_shard_count", "pfq_tree_create", "pfq_tree_insert", "pfq_tree_build_balanced", "pfq_tree_build_balanced_device",
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_leaf_counts",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
@@ -70,6 +70,7 @@ def lib() -> C.CDLL:
     L.pfq_version.restype = C.c_char_p
     L.pfq_tree_open.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     L.pfq_tree_open_subtree.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.pfq_db_shard_count.argtypes = [C.c_char_p, C.c_uint64, u64p]
     L.pfq_tree_build_balanced.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint64,
                                           C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, C.c_int,
                                           C.POINTER(vp)]

@@ -660,9 +660,11 @@ struct ReadQueue {
         s->last = true;
         return s;
     }
+    // segments the pool takes back (filtering: batches in flight hold their segments)
+    size_t pool_cap() const { return lookahead + 4 + (keep ? 48 : 0); }
     void recycle(Segment *s) {
         std::lock_guard<std::mutex> lk(mu);
-        if (pool.size() < lookahead + 4 + (keep ? 48 : 0)) pool.push_back(s);  // (filtering: batches in flight hold their segments)
+        if (pool.size() < pool_cap()) pool.push_back(s);
         else delete s;
     }
     // one holder less; the last one hands the segment back (a segment that ends in malformed input is not reused)
@@ -935,7 +937,7 @@ int cmd_query(int argc, char **argv) {
     std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
                              {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
-                             {"devices", 0, true}};
+                             {"devices", 0, true}, {"shard-depth", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -968,14 +970,34 @@ int cmd_query(int argc, char **argv) {
         if (devices.empty()) devices.push_back(device_from_env());
     }
     const size_t n_dev = devices.size();
-    std::vector<pfq_tree *> trees(n_dev, nullptr);
-    {   // BloomTree::load per replica, side by side
-        std::vector<std::string> errs(n_dev);
+    // --shard-depth D: the database is split into the subtree shards of its depth-E frontier (pfq_tree_open_subtree), E = D,
+    // or the search depth when that is smaller (a shard cut below the pruning depth would put one pruned leaf into several
+    // shards).  Shard i lives on devices[i % N] and classifies EVERY read; the shards' leaf ranges are disjoint and follow
+    // the whole tree's leaf order, so their hits and counts are concatenated in shard order.  Each shard has its own host
+    // thread.  Checked before any device is touched; at least one shard per device (no replication of shards).
+    const bool sharded = a.val.count("shard-depth") != 0;
+    uint64_t shard_depth = 0;
+    size_t n_trees = n_dev;
+    if (sharded) {
+        shard_depth = to_u64(a.val.at("shard-depth"), "shard-depth");
+        if (a.val.count("search-depth")) shard_depth = std::min(shard_depth, to_u64(a.val.at("search-depth"), "search-depth"));
+        uint64_t n_shards = 0;
+        check(pfq_db_shard_count(db.c_str(), shard_depth, &n_shards));
+        if (n_shards < n_dev)
+            die("--shard-depth: the database has " + std::to_string(n_shards) + " subtree shards at depth " + std::to_string(shard_depth) +
+                ", fewer than the " + std::to_string(n_dev) + " devices listed (every device needs a shard of its own)");
+        n_trees = (size_t)n_shards;
+    }
+    std::vector<pfq_tree *> trees(n_trees, nullptr);
+    {   // BloomTree::load per replica (or shard), side by side
+        std::vector<std::string> errs(n_trees);
         std::vector<std::thread> th;
         auto open_one = [&](size_t i) {
-            if (pfq_tree_open(db.c_str(), devices[i], &trees[i]) != PFQ_OK) errs[i] = std::string("libpfq: ") + pfq_last_error();
+            const int rc = sharded ? pfq_tree_open_subtree(db.c_str(), devices[i % n_dev], shard_depth, i, &trees[i])
+                                   : pfq_tree_open(db.c_str(), devices[i], &trees[i]);
+            if (rc != PFQ_OK) errs[i] = std::string("libpfq: ") + pfq_last_error();
         };
-        for (size_t i = 1; i < n_dev; ++i) th.emplace_back(open_one, i);
+        for (size_t i = 1; i < n_trees; ++i) th.emplace_back(open_one, i);
         open_one(0);
         for (auto &t : th) t.join();
         for (auto &e : errs)
@@ -1020,11 +1042,20 @@ int cmd_query(int argc, char **argv) {
         }
     };
 
-    const char *const *tax = nullptr;
-    const uint64_t *cnt = nullptr;
-    uint64_t n_leaves = 0;
-    check(pfq_leaf_counts(tree, &tax, &cnt, &n_leaves));
-    std::vector<std::string> leaf_names(tax, tax + n_leaves);
+    // leaf names in the whole tree's order; shard i's leaves are [leaf_base[i], leaf_base[i + 1]) of it (after pruning)
+    std::vector<std::string> leaf_names;
+    std::vector<uint64_t> leaf_base(1, 0);
+    for (size_t i = 0; i < (sharded ? n_trees : 1); ++i) {
+        const char *const *tax = nullptr;
+        uint64_t n_leaves = 0;
+        check(pfq_leaf_counts(trees[i], &tax, nullptr, &n_leaves));
+        leaf_names.insert(leaf_names.end(), tax, tax + n_leaves);
+        leaf_base.push_back(leaf_base.back() + n_leaves);
+    }
+    if (sharded)
+        for (size_t i = 0; i < n_trees; ++i)
+            fprintf(stderr, "shard %zu/%zu: leaves [%llu, %llu) of %llu on device %d\n", i, n_trees, (unsigned long long)leaf_base[i],
+                    (unsigned long long)leaf_base[i + 1], (unsigned long long)leaf_base.back(), devices[i % n_dev]);
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
@@ -1038,6 +1069,76 @@ int cmd_query(int argc, char **argv) {
     };
     if (block == 0) {
         // nothing to do: see above
+    } else if (!filtering && sharded) {
+        // Counts only, shards: every parsed segment goes to every shard's thread; segment k sits in ring[k % W] until the
+        // last shard is done with it, then goes back to the reader.  W is what the reader's pool takes back, so at most W
+        // segments are in flight and a shard at most W segments ahead of the slowest one.  One thread at a time takes the
+        // next segment from the reader (outside the lock: the others go on with the segments already taken) and pads it
+        // once, before any shard reads it.
+        const size_t W = rq.pool_cap();
+        std::vector<Segment *> ring(W, nullptr);
+        std::vector<size_t> shards_left(W, 0);
+        std::mutex qm;
+        std::condition_variable qcv;
+        uint64_t fetched = 0;      // segments taken from the reader
+        bool fetching = false;
+        long long n_seg = -1;      // number of segments, once the end of the input (or malformed input) is reached
+        auto shard_loop = [&](size_t i) {
+            for (uint64_t k = 0;; ++k) {
+                const size_t slot = (size_t)(k % W);
+                Segment *sg = nullptr;
+                {
+                    std::unique_lock<std::mutex> lk(qm);
+                    qcv.wait(lk, [&] {
+                        return k < fetched || (n_seg >= 0 && (long long)k >= n_seg) || (k == fetched && !fetching && !ring[slot]);
+                    });
+                    if (n_seg >= 0 && (long long)k >= n_seg) return;
+                    if (k == fetched) {
+                        fetching = true;
+                        lk.unlock();
+                        sg = rq.next_segment();
+                        if (sg && sg->b.n()) sg->b.seq.resize(sg->b.seq.size() + 16);
+                        lk.lock();
+                        fetching = false;
+                        if (!sg) n_seg = (long long)k;
+                        else {
+                            if (!sg->err.empty()) {  // malformed input: the reads before it are still classified, nothing after it
+                                rq.pending_error = sg->err;
+                                n_seg = (long long)k + 1;
+                            }
+                            ring[slot] = sg;
+                            shards_left[slot] = n_trees;
+                            ++fetched;
+                        }
+                        qcv.notify_all();
+                        if (!sg) return;
+                    }
+                    sg = ring[slot];
+                }
+                const uint64_t n = sg->b.n();
+                if (n) {
+                    const uint64_t tq0 = ReadQueue::now_ns();
+                    if (pfq_query_batch(trees[i], sg->b.seq.data(), sg->b.off.data(), n, threshold, 0, nullptr) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    ns_gpu += ReadQueue::now_ns() - tq0;
+                    if (i == 0) n_total += n;
+                }
+                bool last;
+                {
+                    std::lock_guard<std::mutex> lk(qm);
+                    last = --shards_left[slot] == 0;
+                    if (last) ring[slot] = nullptr;
+                }
+                if (!last) continue;
+                if (!sg->err.empty()) delete sg;
+                else rq.recycle(sg);
+                qcv.notify_all();
+            }
+        };
+        std::vector<std::thread> th;
+        for (size_t i = 1; i < n_trees; ++i) th.emplace_back(shard_loop, i);
+        shard_loop(0);
+        for (auto &t : th) t.join();
     } else if (!filtering) {
         // Counts only: the result does not depend on how the reads are cut into device calls (mapped_reads just
         // accumulates, query.rs:143), so every parsed segment goes to a GPU as it is — no host-side copy.  Segments are
@@ -1094,6 +1195,10 @@ int cmd_query(int argc, char **argv) {
         std::vector<std::vector<uint32_t>> hit_leaves(NB);
         std::vector<int> ready(NB, 0);          // 0 = free for the assembler, 1 = filled, 2 = classified
         std::vector<uint64_t> batch_seq(NB, 0);  // which batch a slot holds
+        // shards: every shard's hits of the batch in a slot, and how many shards have yet to classify it
+        std::vector<std::vector<std::vector<uint64_t>>> shard_off(sharded ? NB : 0, std::vector<std::vector<uint64_t>>(n_trees));
+        std::vector<std::vector<std::vector<uint32_t>>> shard_leaves(sharded ? NB : 0, std::vector<std::vector<uint32_t>>(n_trees));
+        std::vector<size_t> shards_left(NB, 0);
         std::mutex mu;
         std::condition_variable cv;
         long long last_seq = -1;                 // sequence number of the last batch, once the assembler knows it
@@ -1110,8 +1215,11 @@ int cmd_query(int argc, char **argv) {
                 rq.release_held(batches[slot]);  // (written: its segments go back to the parsers)
                 batches[slot].clear();
                 more = rq.fill(batches[slot], batch_reads, 3ull << 30, true);
+                // shards: padded here, once — every shard's thread reads the batch at the same time
+                if (sharded && batches[slot].n()) batches[slot].seq.resize(batches[slot].seq.size() + 16);
                 {
                     std::lock_guard<std::mutex> lk(mu);
+                    shards_left[slot] = n_trees;
                     ready[slot] = 1;
                     batch_seq[slot] = k;
                     if (!more) last_seq = (long long)k;
@@ -1145,6 +1253,61 @@ int cmd_query(int argc, char **argv) {
                     hit_leaves[slot].assign(hits.leaves, hits.leaves + hits.offsets[n]);
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     n_total += n;
+                }
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    ready[slot] = 2;
+                }
+                cv.notify_all();
+            }
+        };
+        // Shards: thread i runs EVERY batch through shard i.  The last shard to finish a batch merges the shards' hits: per
+        // read, the shards' ascending lists in shard order, each offset by the shard's first leaf — the whole tree's CSR.
+        auto shard_loop = [&](size_t i) {
+            for (uint64_t k = 0;; ++k) {
+                const size_t slot = (size_t)(k % NB);
+                {
+                    std::unique_lock<std::mutex> lk(mu);
+                    cv.wait(lk, [&] { return (ready[slot] == 1 && batch_seq[slot] == k) || (last_seq >= 0 && (long long)k > last_seq); });
+                    if (last_seq >= 0 && (long long)k > last_seq) return;
+                }
+                const Batch &b = batches[slot];
+                const uint64_t n = b.n();
+                std::vector<uint64_t> &s_off = shard_off[slot][i];
+                std::vector<uint32_t> &s_leaves = shard_leaves[slot][i];
+                s_off.assign(n + 1, 0);
+                s_leaves.clear();
+                if (n) {
+                    pfq_hits hits{};
+                    const uint64_t tq0 = ReadQueue::now_ns();
+                    if (pfq_query_batch(trees[i], b.seq.data(), b.off.data(), n, threshold, PFQ_WANT_HITS, &hits) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    memcpy(s_off.data(), hits.offsets, (n + 1) * sizeof(uint64_t));
+                    s_leaves.assign(hits.leaves, hits.leaves + hits.offsets[n]);
+                    ns_gpu += ReadQueue::now_ns() - tq0;
+                    if (i == 0) n_total += n;
+                }
+                bool last;
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    last = --shards_left[slot] == 0;
+                }
+                if (!last) continue;
+                std::vector<uint64_t> &h_off = hit_off[slot];
+                std::vector<uint32_t> &h_leaves = hit_leaves[slot];
+                uint64_t total = 0;
+                for (size_t s = 0; s < n_trees; ++s) total += shard_off[slot][s][n];
+                h_off.assign(n + 1, 0);
+                h_leaves.resize(total);
+                uint64_t at = 0;
+                for (uint64_t r = 0; r < n; ++r) {
+                    for (size_t s = 0; s < n_trees; ++s) {
+                        const uint64_t *o = shard_off[slot][s].data();
+                        const uint32_t *l = shard_leaves[slot][s].data();
+                        const uint32_t base = (uint32_t)leaf_base[s];
+                        for (uint64_t j = o[r]; j < o[r + 1]; ++j) h_leaves[at++] = l[j] + base;
+                    }
+                    h_off[r + 1] = at;
                 }
                 {
                     std::lock_guard<std::mutex> lk(mu);
@@ -1414,8 +1577,13 @@ int cmd_query(int argc, char **argv) {
             }
         });
         std::vector<std::thread> th;
-        for (size_t d = 1; d < n_dev; ++d) th.emplace_back(device_loop, d);
-        device_loop(0);
+        if (sharded) {
+            for (size_t i = 1; i < n_trees; ++i) th.emplace_back(shard_loop, i);
+            shard_loop(0);
+        } else {
+            for (size_t d = 1; d < n_dev; ++d) th.emplace_back(device_loop, d);
+            device_loop(0);
+        }
         for (auto &t : th) t.join();
         parser.join();
         output.join();
@@ -1443,9 +1611,26 @@ int cmd_query(int argc, char **argv) {
     if (pos_fd >= 0) close(pos_fd);
     if (neg_fd >= 0) close(neg_fd);
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
-    // per-genome counts of all replicas: one RCCL all-reduce (every replica then holds the totals); replica 0 writes the file
-    if (n_dev > 1) check(pfq_trees_allreduce_counts(trees.data(), (uint32_t)n_dev));
-    check(pfq_save_leaf_counts(tree, (out + "/CLASSIFICATION.csv").c_str()));
+    if (sharded) {
+        // the shards' counts one after the other, in pfq_save_leaf_counts' format: the leaf ranges are disjoint, so every
+        // leaf (and every count stored in tree.bin) appears once — nothing to reduce
+        const std::string csv = out + "/CLASSIFICATION.csv";
+        FILE *f = fopen(csv.c_str(), "wb");
+        if (!f) die("cannot create " + csv + ": " + strerror(errno));
+        for (pfq_tree *t : trees) {
+            const char *const *tax = nullptr;
+            const uint64_t *cnt = nullptr;
+            uint64_t n_leaves = 0;
+            check(pfq_leaf_counts(t, &tax, &cnt, &n_leaves));
+            for (uint64_t j = 0; j < n_leaves; ++j)
+                if (cnt[j] > 0) fprintf(f, "%s,%llu\n", tax[j], (unsigned long long)cnt[j]);  // query.rs:177-182
+        }
+        if (fclose(f) != 0) die("short write to " + csv);
+    } else {
+        // per-genome counts of all replicas: one RCCL all-reduce (every replica then holds the totals); replica 0 writes the file
+        if (n_dev > 1) check(pfq_trees_allreduce_counts(trees.data(), (uint32_t)n_dev));
+        check(pfq_save_leaf_counts(tree, (out + "/CLASSIFICATION.csv").c_str()));
+    }
     for (pfq_tree *t : trees) pfq_tree_close(t);
     printf("Finished.\n");
     return 0;
@@ -1624,7 +1809,10 @@ void usage() {
             "  build-balanced  Builds a balanced synthetic BloomTree on the GPU (benchmark databases)\n"
             "  ingest-check    Parses reads like `query` and prints what was read (no GPU)\n\n"
             "query takes the reference's options, plus --devices <0,1,..|all>: one replica of the database per GPU, reads\n"
-            "dealt over them, per-genome counts combined by one RCCL all-reduce (default: device $PFQ_DEVICE or 0)\n");
+            "dealt over them, per-genome counts combined by one RCCL all-reduce (default: device $PFQ_DEVICE or 0), and\n"
+            "--shard-depth <D>: the database split into the subtree shards of its depth-D frontier (depth min(D, --search-depth)),\n"
+            "shard i on device i mod N of the N listed; every shard sees every read and loads only its own .bf files, so a\n"
+            "database larger than one GPU's memory can be queried.  Needs at least N shards.  Same outputs as the whole tree\n");
 }
 
 }  // namespace

@@ -1602,13 +1602,12 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
     return q.run();
 }
 
-// Reduce a whole tree to subtree shard `index` of the depth-`depth` frontier (pfq_tree_open_subtree): the shard's node,
-// everything below it and the chain of its ancestors, each reduced to the child on the path.  `reachable` marks the nodes
-// that stay; `chain` lists the ancestors, root first.  Needs parent / depth of every node (relink).
-int apply_shard(pfq_tree &t, uint64_t depth, uint64_t index, std::vector<uint8_t> &reachable, std::vector<int32_t> &chain) {
-    if (t.root < 0) return fail(PFQ_ERR_STATE, "subtree shard of an empty tree");
-    // frontier at depth `depth`, left to right: nodes at that depth and leaves above it
-    std::vector<int32_t> frontier, st{t.root};
+// The subtree shards of a tree: its depth-`depth` frontier, left to right — nodes at that depth and leaves above it
+// (pfq_tree_open_subtree, pfq_db_shard_count).  Needs depth of every node.
+std::vector<int32_t> shard_frontier(const pfq_tree &t, uint64_t depth) {
+    std::vector<int32_t> frontier;
+    if (t.root < 0) return frontier;
+    std::vector<int32_t> st{t.root};
     while (!st.empty()) {
         int32_t v = st.back();
         st.pop_back();
@@ -1617,6 +1616,15 @@ int apply_shard(pfq_tree &t, uint64_t depth, uint64_t index, std::vector<uint8_t
         if (nd.right >= 0) st.push_back(nd.right);
         if (nd.left >= 0) st.push_back(nd.left);
     }
+    return frontier;
+}
+
+// Reduce a whole tree to subtree shard `index` of the depth-`depth` frontier (pfq_tree_open_subtree): the shard's node,
+// everything below it and the chain of its ancestors, each reduced to the child on the path.  `reachable` marks the nodes
+// that stay; `chain` lists the ancestors, root first.  Needs parent / depth of every node (relink).
+int apply_shard(pfq_tree &t, uint64_t depth, uint64_t index, std::vector<uint8_t> &reachable, std::vector<int32_t> &chain) {
+    if (t.root < 0) return fail(PFQ_ERR_STATE, "subtree shard of an empty tree");
+    const std::vector<int32_t> frontier = shard_frontier(t, depth);
     if (index >= frontier.size())
         return fail(PFQ_ERR_ARG, "subtree index " + std::to_string(index) + " out of range: the depth-" +
                                      std::to_string(depth) + " frontier has " + std::to_string(frontier.size()) + " nodes");
@@ -1823,6 +1831,25 @@ int pfq_host_free(void *p) {
 const char *pfq_last_error(void) { return g_err.c_str(); }
 const char *pfq_version(void) { return "libpfq 0.1 (gfx950)"; }
 
+// <dir>/tree.bin (BloomTree::load, bloom_tree.rs:364-386) into the model of `t`: topology, names, counts, parameters.
+// Reads no .bf file and uses no device.
+static int read_tree_bin(const std::string &dir, pfq_tree &t) {
+    std::vector<uint8_t> buf;
+    if (!read_file(dir + "/tree.bin", buf))
+        return fail(PFQ_ERR_IO, "cannot read " + dir + "/tree.bin (reference: panic at bloom_tree.rs:375)");
+    Cur c{buf.data(), buf.size()};
+    uint8_t tag = c.u8();
+    if (!c.ok || tag > 1) return fail(PFQ_ERR_FORMAT, "tree.bin: bad Option tag for root");
+    if (tag == 1) PFQ_TRY(parse_node(c, t, -1, 0, t.root));
+    t.false_pos_rate = c.f32();
+    t.largest_expected_genome = c.u32();
+    t.kmer_size = c.u64();
+    t.seed1 = c.u64();
+    t.seed2 = c.u64();
+    if (!c.ok || c.p != c.n) return fail(PFQ_ERR_FORMAT, "tree.bin: truncated or trailing bytes");
+    return PFQ_OK;
+}
+
 static int open_impl(const char *db_dir, int device, bool shard, uint64_t shard_depth, uint64_t shard_index, pfq_tree **out) {
     if (!db_dir || !out) return fail(PFQ_ERR_ARG, "null argument");
     *out = nullptr;
@@ -1830,19 +1857,7 @@ static int open_impl(const char *db_dir, int device, bool shard, uint64_t shard_
     std::unique_ptr<pfq_tree> t(new pfq_tree());
     t->device = device;
     std::string dir(db_dir);
-    std::vector<uint8_t> buf;
-    if (!read_file(dir + "/tree.bin", buf))
-        return fail(PFQ_ERR_IO, "cannot read " + dir + "/tree.bin (reference: panic at bloom_tree.rs:375)");
-    Cur c{buf.data(), buf.size()};
-    uint8_t tag = c.u8();
-    if (!c.ok || tag > 1) return fail(PFQ_ERR_FORMAT, "tree.bin: bad Option tag for root");
-    if (tag == 1) PFQ_TRY(parse_node(c, *t, -1, 0, t->root));
-    t->false_pos_rate = c.f32();
-    t->largest_expected_genome = c.u32();
-    t->kmer_size = c.u64();
-    t->seed1 = c.u64();
-    t->seed2 = c.u64();
-    if (!c.ok || c.p != c.n) return fail(PFQ_ERR_FORMAT, "tree.bin: truncated or trailing bytes");
+    PFQ_TRY(read_tree_bin(dir, *t));
     t->tree_leaves = leaves_dfs(*t).size();
     std::vector<uint8_t> reachable(t->nodes.size(), 1);
     std::vector<int32_t> chain;
@@ -1960,6 +1975,16 @@ int pfq_tree_open(const char *db_dir, int device, pfq_tree **out) { return open_
 
 int pfq_tree_open_subtree(const char *db_dir, int device, uint64_t depth, uint64_t index, pfq_tree **out) {
     return open_impl(db_dir, device, true, depth, index, out);
+}
+
+int pfq_db_shard_count(const char *db_dir, uint64_t depth, uint64_t *n_shards) {
+    if (!db_dir || !n_shards) return fail(PFQ_ERR_ARG, "null argument");
+    *n_shards = 0;
+    pfq_tree t;  // the model only: no filter is read, no device is touched
+    PFQ_TRY(read_tree_bin(db_dir, t));
+    if (t.root < 0) return fail(PFQ_ERR_STATE, "subtree shards of an empty tree");
+    *n_shards = shard_frontier(t, depth).size();
+    return PFQ_OK;
 }
 
 // BloomTree::new (bloom_tree.rs:100-118) with explicit hash seeds: an empty tree whose filters are sized like

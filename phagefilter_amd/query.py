@@ -63,6 +63,14 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_tree_open_subtree(directory.encode(), device, depth, index, C.byref(h)))
         return cls(h, device)
 
+    @staticmethod
+    def shard_count(directory: str, depth: int) -> int:
+        """Number of subtree shards at depth `depth` (pfq_db_shard_count): the indices load_subtree accepts are
+        0 .. shard_count - 1.  Reads tree.bin only; needs no device."""
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_db_shard_count(directory.encode(), depth, C.byref(n)))
+        return n.value
+
     @classmethod
     def new(cls, kmer_size: int, false_pos_rate: float, largest_expected_genome: int, seed1: int, seed2: int,
             expected_genomes: int = 0, device: int = 0) -> "BloomTree":

@@ -1,0 +1,274 @@
+"""`phage_filter query --shard-depth D`: the database split into the subtree shards of its depth-D frontier, shard i on
+device i mod N, every read classified by every shard, hits and counts concatenated in shard order.  Every output file
+(and stdout) must equal the whole-tree run of the same CLI byte for byte; CLASSIFICATION.csv also equals the oracle's.
+The CLI runs one after the other."""
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pfq_format as fmt
+from oracle import pfq_oracle as orc
+from phagefilter_amd import BloomTree, PfqError
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EX = os.path.join(ROOT, "tests", "golden", "examples")
+CLI = os.path.join(ROOT, "phagefilter_amd", "phage_filter")
+TIMEOUT = 300
+PFQ_ERR_ARG = -1
+# small batches and segments: many of both from the examples' 1500 reads
+ENV = dict(os.environ, PFQ_CLI_BATCH_READS="128", PFQ_INGEST_CHUNK_BYTES="20000")
+SHARD_LINE = re.compile(r"^shard (\d+)/(\d+): leaves \[(\d+), (\d+)\) of (\d+) on device (\d+)$")
+
+
+def query(db, reads, out, *extra, env=ENV):
+    """One CLI run: (exit status, stdout, stderr, {file: bytes} of the output directory)."""
+    p = subprocess.run([CLI, "query", "--reads", reads, "--out", out, "--db-path", db, "--block-size-reads", "64",
+                        "--threads", "4", *extra], capture_output=True, text=True, env=env, timeout=TIMEOUT)
+    files = {f: open(os.path.join(out, f), "rb").read() for f in sorted(os.listdir(out))} if os.path.isdir(out) else {}
+    return p.returncode, p.stdout, p.stderr, files
+
+
+def shard_lines(stderr):
+    return [tuple(int(x) for x in m.groups()) for m in (SHARD_LINE.match(l) for l in stderr.splitlines()) if m]
+
+
+def check_shard_lines(stderr, n_shards, n_dev):
+    """One line per shard, in order; the leaf ranges partition [0, n_leaves); shard i on device list entry i mod N (all 0 here)."""
+    lines = shard_lines(stderr)
+    assert [l[0] for l in lines] == list(range(n_shards)) and all(l[1] == n_shards for l in lines), stderr
+    assert lines[0][2] == 0 and lines[-1][3] == lines[-1][4], stderr
+    for a, b in zip(lines, lines[1:]):
+        assert a[3] == b[2] and a[4] == b[4], stderr
+    assert all(l[2] < l[3] for l in lines), stderr
+    assert all(l[5] == 0 for l in lines), stderr
+    return lines
+
+
+def assert_same_run(whole, sharded, n_shards, n_dev):
+    rc, out, err, files = sharded
+    assert rc == whole[0], err
+    assert out == whole[1]
+    assert files == whole[3]
+    check_shard_lines(err, n_shards, n_dev)
+
+
+@pytest.fixture(scope="module")
+def ex_db(gpu, tmp_path_factory):
+    db = str(tmp_path_factory.mktemp("shard_cli") / "db")
+    p = subprocess.run([CLI, "build-balanced", "--genomes", os.path.join(EX, "genomes"), "--db-path", db],
+                       capture_output=True, text=True, timeout=TIMEOUT)
+    assert p.returncode == 0, p.stderr
+    return db
+
+
+@pytest.fixture(scope="module")
+def ex_whole(ex_db, tmp_path_factory):
+    """Whole-tree runs of the examples: (threshold, filtering) -> query()."""
+    base = tmp_path_factory.mktemp("whole")
+    runs = {}
+    for thr in ("1.0", "0.7"):
+        for filtering in (False, True):
+            out = str(base / f"{thr}_{int(filtering)}")
+            r = query(ex_db, os.path.join(EX, "reads"), out, "--filter-threshold", thr,
+                      *(["--pos-filter", "--neg-filter"] if filtering else []))
+            assert r[0] == 0 and not shard_lines(r[2]), r[2]
+            runs[thr, filtering] = r
+    return runs
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+def test_examples_shards_equal_whole_tree(ex_db, ex_whole, tmp_path, depth):
+    gold = json.load(open(os.path.join(EX, "expected.json")))
+    n_shards = BloomTree.shard_count(ex_db, depth)
+    assert n_shards == 2 ** depth                    # 12 leaves, balanced: every node above depth 3 is internal
+    for devs in ("0", "0,0", "0,0,0,0"):
+        n_dev = devs.count(",") + 1
+        if n_shards < n_dev:
+            continue
+        for thr in ("1.0", "0.7"):
+            for filtering in (False, True):
+                whole = ex_whole[thr, filtering]
+                assert whole[3]["CLASSIFICATION.csv"].decode() == gold["expected"][thr]["classification_csv"]
+                out = str(tmp_path / f"{devs}_{thr}_{int(filtering)}")
+                r = query(ex_db, os.path.join(EX, "reads"), out, "--filter-threshold", thr, "--shard-depth", str(depth),
+                          "--devices", devs, *(["--pos-filter", "--neg-filter"] if filtering else []))
+                assert_same_run(whole, r, n_shards, n_dev)
+                assert len(r[3]) == (3 if filtering else 1)
+
+
+def test_shard_count_matches_load_subtree(ex_db):
+    for depth in range(4):
+        n = BloomTree.shard_count(ex_db, depth)
+        leaves = []
+        for i in range(n):
+            t = BloomTree.load_subtree(ex_db, depth, i)
+            info = t.info()
+            assert info.shard_first_leaf == len(leaves)
+            leaves += [name for name, _ in t.get_leaf_counts()]
+            t.close()
+        with pytest.raises(PfqError) as e:
+            BloomTree.load_subtree(ex_db, depth, n)
+        assert e.value.code == PFQ_ERR_ARG
+        whole = BloomTree.load(ex_db)
+        assert leaves == [name for name, _ in whole.get_leaf_counts()]
+        whole.close()
+
+
+def test_too_few_shards_for_the_devices(ex_db, tmp_path):
+    r = query(ex_db, os.path.join(EX, "reads"), str(tmp_path / "o"), "--shard-depth", "1", "--devices", "0,0,0")
+    assert r[0] == 101 and "2 subtree shards" in r[2] and "3 devices" in r[2], r[2]
+
+
+def test_search_depth_below_and_above_the_shard_depth(ex_db, tmp_path):
+    """E = min(D, S): with S < D the shards are cut at S (a pruned leaf in one shard only); with S >= D at D."""
+    for d, s in ((3, 1), (1, 3)):
+        args = ("--filter-threshold", "0.7", "--search-depth", str(s), "--pos-filter", "--neg-filter")
+        whole = query(ex_db, os.path.join(EX, "reads"), str(tmp_path / f"w{d}{s}"), *args)
+        assert whole[0] == 0, whole[2]
+        r = query(ex_db, os.path.join(EX, "reads"), str(tmp_path / f"s{d}{s}"), *args, "--shard-depth", str(d))
+        assert_same_run(whole, r, 2 ** min(d, s), 1)
+        assert f"Search depth settings: {s}" in r[1]
+
+
+def _dna(rng, n):
+    return bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n).astype(np.uint8))
+
+
+def _reads_of(rng, genomes, n_pos, n_neg, length):
+    out = []
+    for _ in range(n_pos):
+        g = genomes[int(rng.integers(0, len(genomes)))]
+        o = int(rng.integers(0, len(g) - length + 1))
+        r = bytearray(g[o:o + length])
+        if rng.random() < 0.3:                       # a substitution: below threshold 1.0, often above 0.7
+            r[int(rng.integers(0, length))] = ord("ACGT"[int(rng.integers(0, 4))])
+        out.append(bytes(r))
+    return out + [_dna(rng, length) for _ in range(n_neg)]
+
+
+def _write_fastq(path, reads):
+    with open(path, "wb") as f:
+        for i, r in enumerate(reads):
+            f.write(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)))
+
+
+def test_greedy_database_with_leaves_above_the_cut(gpu, tmp_path):
+    """`phage_filter build` (greedy placement) of one base genome, an unrelated one and variants of the base: the unrelated
+    genome is a leaf at depth 1, above the depth-2 cut, and is a shard of its own."""
+    rng = np.random.default_rng(11)
+    base = _dna(rng, 900)
+
+    def mut(g, m):
+        g = bytearray(g)
+        for _ in range(m):
+            g[int(rng.integers(0, len(g)))] = ord("ACGT"[int(rng.integers(0, 4))])
+        return bytes(g)
+
+    genomes = [base, _dna(rng, 2000)] + [mut(base, 2 * i) for i in range(1, 10)]
+    ids = [f"g{i}" for i in range(len(genomes))]
+    (tmp_path / "genomes.fa").write_bytes(b"".join(b">%s\n%s\n" % (i.encode(), g) for i, g in zip(ids, genomes)))
+    db = str(tmp_path / "db")
+    p = subprocess.run([CLI, "build", "-g", str(tmp_path / "genomes.fa"), "-d", db, "-k", "15", "-f", "0.01", "-l", "2000",
+                        "--seed1", "5", "--seed2", "10"], capture_output=True, text=True, timeout=TIMEOUT)
+    assert p.returncode == 0, p.stderr
+    ot = fmt.read_db(db)
+    depth_of, st = {}, [(ot.root, 0)]
+    while st:
+        v, d = st.pop()
+        depth_of[v] = d
+        st += [(c, d + 1) for c in (ot.left[v], ot.right[v]) if c >= 0]
+    assert min(depth_of[v] for v in ot.leaves_dfs()) < 2 < max(depth_of[v] for v in ot.leaves_dfs())
+    reads = _reads_of(rng, genomes, 600, 200, 80)
+    rfile = str(tmp_path / "reads.fq")
+    _write_fastq(rfile, reads)
+    n_shards = BloomTree.shard_count(db, 2)
+    for thr in ("1.0", "0.7"):
+        for filtering in (False, True):
+            extra = ("--filter-threshold", thr) + (("--pos-filter", "--neg-filter") if filtering else ())
+            whole = query(db, rfile, str(tmp_path / f"w{thr}{filtering}"), *extra)
+            assert whole[0] == 0, whole[2]
+            r = query(db, rfile, str(tmp_path / f"s{thr}{filtering}"), *extra, "--shard-depth", "2")
+            assert_same_run(whole, r, n_shards, 1)
+            for v in range(ot.n_nodes):
+                ot.mapped_reads[v] = 0
+            orc.query_batch(ot, reads, float(thr), threads=4, want_hits=False)
+            assert r[3]["CLASSIFICATION.csv"].decode() == ot.classification_csv()
+            assert sum(ot.mapped_reads[v] for v in ot.leaves_dfs()) > 0
+
+
+def test_colliding_internal_names_guard_columns(gpu, tmp_path):
+    """Internal nodes that alias one .bf (reference-built trees): parent ⊇ child fails on some edges, so the
+    shards carry guard columns for their ancestor chains."""
+    rng = np.random.default_rng(5)
+    k, nbits, h = 21, 100003, 5
+    genomes = [_dna(rng, int(rng.integers(300, 500))) for _ in range(40)]
+    genomes[11] = genomes[10]
+    ids = [f"G{i:05d}" for i in range(len(genomes))]
+    ot = orc.build_balanced_tree(genomes, ids, k, nbits, h, 5, 10)
+    internal = [v for v in range(ot.n_nodes) if not ot.is_leaf(v)]
+    picks = rng.choice(len(internal), size=8, replace=False)
+    for a, b in zip(picks[:4], picks[4:]):
+        a, b = internal[int(a)], internal[int(b)]
+        ot.bf_path[a] = ot.bf_path[b]
+        ot.filter_of[a] = ot.filter_of[b]
+    db = str(tmp_path / "db")
+    fmt.write_db(ot, db)
+    reads = _reads_of(rng, genomes, 800, 200, 150)
+    rfile = str(tmp_path / "reads.fq")
+    _write_fastq(rfile, reads)
+    for thr in ("1.0", "0.3"):
+        extra = ("--filter-threshold", thr, "--pos-filter", "--neg-filter")
+        whole = query(db, rfile, str(tmp_path / f"w{thr}"), *extra)
+        assert whole[0] == 0, whole[2]
+        for depth in (2, 3):
+            r = query(db, rfile, str(tmp_path / f"s{thr}_{depth}"), *extra, "--shard-depth", str(depth))
+            assert_same_run(whole, r, BloomTree.shard_count(db, depth), 1)
+        for v in range(ot.n_nodes):
+            ot.mapped_reads[v] = 0
+        orc.query_batch(ot, reads, float(thr), threads=4, want_hits=False)
+        assert whole[3]["CLASSIFICATION.csv"].decode() == ot.classification_csv()
+
+
+def test_stored_counts_are_reported_once(ex_db, tmp_path):
+    from phagefilter_amd import pack_reads
+    db = str(tmp_path / "db_counted")
+    shutil.copytree(ex_db, db)
+    t = BloomTree.load(db)
+    reads = []
+    for f in sorted(os.listdir(os.path.join(EX, "reads"))):
+        lines = open(os.path.join(EX, "reads", f)).read().split("\n")
+        reads += [lines[4 * i + 1].encode() for i in range(len(lines) // 4)]
+    seq, off = pack_reads(reads[:300])
+    t.query_packed(seq, off, 0.7)
+    assert sum(c for _, c in t.get_leaf_counts()) > 0
+    t.save(db)
+    t.close()
+    whole = query(db, os.path.join(EX, "reads"), str(tmp_path / "w"), "--filter-threshold", "0.7")
+    assert whole[0] == 0, whole[2]
+    gold = json.load(open(os.path.join(EX, "expected.json")))
+    assert whole[3]["CLASSIFICATION.csv"].decode() != gold["expected"]["0.7"]["classification_csv"]
+    for depth in (1, 3):
+        r = query(db, os.path.join(EX, "reads"), str(tmp_path / f"s{depth}"), "--filter-threshold", "0.7", "--shard-depth", str(depth))
+        assert_same_run(whole, r, 2 ** depth, 1)
+
+
+def test_malformed_fastq_tail(ex_db, tmp_path):
+    """The reads before the bad record are classified by every shard, the outputs are written, then exit 101."""
+    src = sorted(os.listdir(os.path.join(EX, "reads")))[0]
+    bad = tmp_path / "bad.fq"
+    bad.write_bytes(open(os.path.join(EX, "reads", src), "rb").read() + b"@cut\nACGTACGT\n+\n")
+    for filtering in (False, True):
+        extra = ("--filter-threshold", "0.7") + (("--pos-filter", "--neg-filter") if filtering else ())
+        whole = query(ex_db, str(bad), str(tmp_path / f"w{filtering}"), *extra)
+        assert whole[0] == 101 and "Incomplete record" in whole[2], whole[2]
+        r = query(ex_db, str(bad), str(tmp_path / f"s{filtering}"), *extra, "--shard-depth", "2")
+        assert_same_run(whole, r, 4, 1)
+        if filtering:
+            assert len(r[3]["POS_FILTERING.fq"]) > 0

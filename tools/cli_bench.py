@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--block", default="100000", help="-b of every query run")
     ap.add_argument("--only", default="", help="'posneg': only the run with both outputs (environment variables reach the CLI)")
     ap.add_argument("--devices", default="", help="comma-separated device lists to run as well, ';'-separated (e.g. '0,0' = two replicas on GPU 0)")
+    ap.add_argument("--shard-depth", default="", help="the --devices runs split the database into the subtree shards of this depth "
+                    "(query --shard-depth) instead of replicating it")
     a = ap.parse_args()
     import torch
     from phagefilter_amd import BloomTree, _ffi
@@ -118,8 +120,10 @@ def main():
         run("fastq counts-only", fq, a.reads, t)
     run("fastq pos+neg output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter"))
     for devs in [d for d in a.devices.split(";") if d]:
-        run(f"fastq counts-only --devices {devs}", fq, a.reads, tmax, ("--devices", devs))
-        run(f"fastq pos+neg output --devices {devs}", fq, a.reads, tmax, ("--devices", devs, "--pos-filter", "--neg-filter"))
+        sh = ("--shard-depth", a.shard_depth) if a.shard_depth else ()
+        label = f"--devices {devs}" + (f" --shard-depth {a.shard_depth}" if a.shard_depth else "")
+        run(f"fastq counts-only {label}", fq, a.reads, tmax, ("--devices", devs, *sh))
+        run(f"fastq pos+neg output {label}", fq, a.reads, tmax, ("--devices", devs, *sh, "--pos-filter", "--neg-filter"))
     # gzip: a directory of 8 parts (streams inflate side by side), 1/4 of the reads
     gzdir = os.path.join(a.workdir, "gz")
     os.makedirs(gzdir)
