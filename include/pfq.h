@@ -59,6 +59,7 @@ typedef struct pfq_hits {
 } pfq_hits;
 
 #define PFQ_WANT_HITS 1u /* fill pfq_hits (needed for POS/NEG filtering, main.rs:345-361) */
+#define PFQ_WANT_SCORES 2u /* also score every hit (pfq_last_hit_scores); only together with PFQ_WANT_HITS, alone: PFQ_ERR_ARG */
 
 /* ---- database ---- */
 
@@ -153,6 +154,14 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
  * for that one.  This is the entry the benchmark times. */
 int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_reads,
                            uint64_t total_bytes, float threshold, uint32_t flags, void *stream, pfq_hits *hits);
+
+/* Scores of the hits of the last pfq_query_batch[_device] call on `tree`, which must have set PFQ_WANT_SCORES (else
+ * PFQ_ERR_ARG): scores[j] belongs to hits.leaves[j] of that call, n_hits = hits.offsets[n_reads].  The score of (read r,
+ * hit leaf l) is num_matches of query_passes (query.rs:38-49) on l's filter: how many of get_kmers(r) (canonical k-mers,
+ * duplicates counted, file_parser.rs:114-148) have all num_hashes probed bits set (bloom_filter.rs:312-332), between
+ * ceil(threshold * n_kmers) and n_kmers = max(len - k + 1, 0).  The hits themselves are those of the same call without
+ * PFQ_WANT_SCORES.  Library-owned; valid until the next query call on the tree. */
+int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits);
 
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);

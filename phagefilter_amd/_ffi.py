@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PFQ_LIBPFQ") or os.path.join(_HERE, "libpfq.so")
 SYMBOLS = [
     "pfq_tree_open", "pfq_tree_open_subtree", "pfq_db_shard_count", "pfq_tree_create", "pfq_tree_insert", "pfq_tree_build_balanced", "pfq_tree_build_balanced_device",
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
-    "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_leaf_counts",
+    "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_synth_genomes_device",
@@ -54,6 +54,7 @@ class Profile(C.Structure):
 
 
 WANT_HITS = 1
+WANT_SCORES = 2
 _lib = None
 
 
@@ -94,6 +95,7 @@ def lib() -> C.CDLL:
     L.pfq_tree_close.restype = None
     L.pfq_query_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_query_batch_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, vp, C.POINTER(Hits)]
+    L.pfq_last_hit_scores.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), u64p]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

@@ -937,7 +937,7 @@ int cmd_query(int argc, char **argv) {
     std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
                              {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
-                             {"devices", 0, true}, {"shard-depth", 0, true}};
+                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -946,6 +946,9 @@ int cmd_query(int argc, char **argv) {
     const float threshold = to_f32(opt(a, "filter-threshold", "1.0"), "filter-threshold");
     const bool pos = a.flags.count("pos-filter") != 0, neg = a.flags.count("neg-filter") != 0;
     const bool filtering = pos || neg;
+    // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
+    const bool scores = a.flags.count("scores") != 0;
+    const bool per_read = filtering || scores;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
 
     // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
@@ -1018,7 +1021,7 @@ int cmd_query(int argc, char **argv) {
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    if (block != 0) rq.start(filtering, threads);
+    if (block != 0) rq.start(per_read, threads);
 
     // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
     struct stat st;
@@ -1031,6 +1034,15 @@ int cmd_query(int argc, char **argv) {
         die("cannot create POS_FILTERING in " + out);
     if (neg && (neg_fd = open((out + "/NEG_FILTERING." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
         die("cannot create NEG_FILTERING in " + out);
+    FILE *scores_f = nullptr;
+    uint64_t kmer_size = 0;
+    if (scores) {
+        if (!(scores_f = fopen((out + "/READ_SCORES.tsv").c_str(), "wb"))) die("cannot create READ_SCORES.tsv in " + out);
+        fputs("#read_id\tkmers\tgenome\tmatched_kmers\n", scores_f);
+        pfq_info info{};
+        check(pfq_tree_info(tree, &info));
+        kmer_size = info.kmer_size;
+    }
     auto write_at = [](int fd, const char *buf, size_t len, uint64_t at) {
         for (size_t done = 0; done < len;) {
             ssize_t n = pwrite(fd, buf + done, len - done, (off_t)(at + done));
@@ -1069,7 +1081,7 @@ int cmd_query(int argc, char **argv) {
     };
     if (block == 0) {
         // nothing to do: see above
-    } else if (!filtering && sharded) {
+    } else if (!per_read && sharded) {
         // Counts only, shards: every parsed segment goes to every shard's thread; segment k sits in ring[k % W] until the
         // last shard is done with it, then goes back to the reader.  W is what the reader's pool takes back, so at most W
         // segments are in flight and a shard at most W segments ahead of the slowest one.  One thread at a time takes the
@@ -1139,7 +1151,7 @@ int cmd_query(int argc, char **argv) {
         for (size_t i = 1; i < n_trees; ++i) th.emplace_back(shard_loop, i);
         shard_loop(0);
         for (auto &t : th) t.join();
-    } else if (!filtering) {
+    } else if (!per_read) {
         // Counts only: the result does not depend on how the reads are cut into device calls (mapped_reads just
         // accumulates, query.rs:143), so every parsed segment goes to a GPU as it is — no host-side copy.  Segments are
         // handed out in input order to whichever replica's thread asks next.
@@ -1193,11 +1205,14 @@ int cmd_query(int argc, char **argv) {
         std::vector<Batch> batches(NB);
         std::vector<std::vector<uint64_t>> hit_off(NB);
         std::vector<std::vector<uint32_t>> hit_leaves(NB);
+        std::vector<std::vector<uint32_t>> hit_scores(scores ? NB : 0);  // --scores: aligned with hit_leaves
+        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u);
         std::vector<int> ready(NB, 0);          // 0 = free for the assembler, 1 = filled, 2 = classified
         std::vector<uint64_t> batch_seq(NB, 0);  // which batch a slot holds
         // shards: every shard's hits of the batch in a slot, and how many shards have yet to classify it
         std::vector<std::vector<std::vector<uint64_t>>> shard_off(sharded ? NB : 0, std::vector<std::vector<uint64_t>>(n_trees));
         std::vector<std::vector<std::vector<uint32_t>>> shard_leaves(sharded ? NB : 0, std::vector<std::vector<uint32_t>>(n_trees));
+        std::vector<std::vector<std::vector<uint32_t>>> shard_scores(sharded && scores ? NB : 0, std::vector<std::vector<uint32_t>>(n_trees));
         std::vector<size_t> shards_left(NB, 0);
         std::mutex mu;
         std::condition_variable cv;
@@ -1246,11 +1261,17 @@ int cmd_query(int argc, char **argv) {
                     b.seq.resize(b.seq.size() + 16);
                     pfq_hits hits{};
                     const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[d], b.seq.data(), b.off.data(), n, threshold, PFQ_WANT_HITS, &hits) != PFQ_OK)
+                    if (pfq_query_batch(trees[d], b.seq.data(), b.off.data(), n, threshold, query_flags, &hits) != PFQ_OK)
                         fail_from_thread(pfq_last_error());
                     // (library-owned until the next call on this replica: the output thread works on copies)
                     memcpy(hit_off[slot].data(), hits.offsets, (n + 1) * sizeof(uint64_t));
                     hit_leaves[slot].assign(hits.leaves, hits.leaves + hits.offsets[n]);
+                    if (scores) {
+                        const uint32_t *sc = nullptr;
+                        uint64_t n_sc = 0;
+                        if (pfq_last_hit_scores(trees[d], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
+                        hit_scores[slot].assign(sc, sc + n_sc);
+                    }
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     n_total += n;
                 }
@@ -1280,10 +1301,16 @@ int cmd_query(int argc, char **argv) {
                 if (n) {
                     pfq_hits hits{};
                     const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[i], b.seq.data(), b.off.data(), n, threshold, PFQ_WANT_HITS, &hits) != PFQ_OK)
+                    if (pfq_query_batch(trees[i], b.seq.data(), b.off.data(), n, threshold, query_flags, &hits) != PFQ_OK)
                         fail_from_thread(pfq_last_error());
                     memcpy(s_off.data(), hits.offsets, (n + 1) * sizeof(uint64_t));
                     s_leaves.assign(hits.leaves, hits.leaves + hits.offsets[n]);
+                    if (scores) {
+                        const uint32_t *sc = nullptr;
+                        uint64_t n_sc = 0;
+                        if (pfq_last_hit_scores(trees[i], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
+                        shard_scores[slot][i].assign(sc, sc + n_sc);
+                    }
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     if (i == 0) n_total += n;
                 }
@@ -1299,12 +1326,14 @@ int cmd_query(int argc, char **argv) {
                 for (size_t s = 0; s < n_trees; ++s) total += shard_off[slot][s][n];
                 h_off.assign(n + 1, 0);
                 h_leaves.resize(total);
+                if (scores) hit_scores[slot].resize(total);
                 uint64_t at = 0;
                 for (uint64_t r = 0; r < n; ++r) {
                     for (size_t s = 0; s < n_trees; ++s) {
                         const uint64_t *o = shard_off[slot][s].data();
                         const uint32_t *l = shard_leaves[slot][s].data();
                         const uint32_t base = (uint32_t)leaf_base[s];
+                        if (scores) std::copy(shard_scores[slot][s].begin() + o[r], shard_scores[slot][s].begin() + o[r + 1], hit_scores[slot].begin() + at);
                         for (uint64_t j = o[r]; j < o[r + 1]; ++j) h_leaves[at++] = l[j] + base;
                     }
                     h_off[r + 1] = at;
@@ -1554,6 +1583,33 @@ int cmd_query(int argc, char **argv) {
                     }
                 });
                 for (unsigned w = nw; w < fmt_workers; ++w) pos_buf[w].n = neg_buf[w].n = 0;
+                if (scores) {
+                    // READ_SCORES.tsv: per record with hits, its genomes by matched k-mers (descending; ties in leaf order)
+                    std::vector<std::string> parts(nw);
+                    const uint32_t *h_sc = hit_scores[slot].data();
+                    run_workers(nw, [&](unsigned w) {
+                        std::string &o = parts[w];
+                        std::vector<uint64_t> order;
+                        char kmers[32], num[32];
+                        for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r) {
+                            if (h_off[r] == h_off[r + 1]) continue;
+                            order.clear();
+                            for (uint64_t j = h_off[r]; j < h_off[r + 1]; ++j) order.push_back(j);
+                            std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return h_sc[x] > h_sc[y]; });
+                            const uint64_t len = b.off[r + 1] - b.off[r];
+                            const int nk = snprintf(kmers, sizeof kmers, "\t%llu\t", (unsigned long long)(len >= kmer_size ? len - kmer_size + 1 : 0));
+                            const std::string_view id = b.id(r);
+                            for (uint64_t j : order) {
+                                o.append(id.data(), id.size());
+                                o.append(kmers, (size_t)nk);
+                                o.append(leaf_names[h_leaves[j]]);
+                                o.append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", h_sc[j]));
+                            }
+                        }
+                    });
+                    for (const std::string &p : parts)
+                        if (!p.empty() && fwrite(p.data(), 1, p.size(), scores_f) != p.size()) fail_from_thread("short write to READ_SCORES.tsv");
+                }
                 const uint64_t t1 = ReadQueue::now_ns();
                 ns_fmt += t1 - t0;
                 // the bytes: batches come in input order, so a part's place is the sum of what lies before it
@@ -1610,6 +1666,7 @@ int cmd_query(int argc, char **argv) {
     }
     if (pos_fd >= 0) close(pos_fd);
     if (neg_fd >= 0) close(neg_fd);
+    if (scores_f && fclose(scores_f) != 0) die("short write to READ_SCORES.tsv");
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
     if (sharded) {
         // the shards' counts one after the other, in pfq_save_leaf_counts' format: the leaf ranges are disjoint, so every
@@ -1812,7 +1869,9 @@ void usage() {
             "dealt over them, per-genome counts combined by one RCCL all-reduce (default: device $PFQ_DEVICE or 0), and\n"
             "--shard-depth <D>: the database split into the subtree shards of its depth-D frontier (depth min(D, --search-depth)),\n"
             "shard i on device i mod N of the N listed; every shard sees every read and loads only its own .bf files, so a\n"
-            "database larger than one GPU's memory can be queried.  Needs at least N shards.  Same outputs as the whole tree\n");
+            "database larger than one GPU's memory can be queried.  Needs at least N shards.  Same outputs as the whole tree\n"
+            "--scores: also write READ_SCORES.tsv into --out: per read record and genome it hits, how many of the read's k-mers\n"
+            "the genome's filter contains (\"#read_id<TAB>kmers<TAB>genome<TAB>matched_kmers\", best genome first)\n");
 }
 
 }  // namespace

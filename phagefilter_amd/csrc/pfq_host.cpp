@@ -254,6 +254,12 @@ struct pfq_tree {
     uint64_t *h_hit_off = nullptr;
     uint32_t *h_hit_leaves = nullptr;
     size_t h_hit_off_cap = 0, h_hit_leaves_cap = 0;
+    // PFQ_WANT_SCORES: one score per entry of h_hit_leaves (pfq_last_hit_scores); valid only after a call that asked for them
+    DevBuf<uint32_t> d_hit_scores;
+    uint32_t *h_hit_scores = nullptr;
+    size_t h_hit_scores_cap = 0;
+    bool scores_valid = false;
+    uint64_t scores_n = 0;
 };
 
 namespace {
@@ -850,7 +856,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
@@ -874,6 +880,7 @@ struct QueryRun {
         if (t.root < 0) return fail(PFQ_ERR_STATE, "query on an empty tree");
         PFQ_TRY(build_layout(t));
         want_hits = (flags & PFQ_WANT_HITS) != 0;
+        want_scores = (flags & PFQ_WANT_SCORES) != 0;
         if (want_hits && !hits) return fail(PFQ_ERR_ARG, "PFQ_WANT_HITS set but hits == NULL");
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
@@ -1567,9 +1574,22 @@ struct QueryRun {
                     pfq::launch_hits_fill(t.d_hit_pairs.p, cursors[0], t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipMemcpyAsync(t.h_hit_leaves, t.d_hit_leaves.p, total * 4, hipMemcpyDeviceToHost, st));
+                    if (want_scores) {  // the hit set is final: score every (read, hit leaf) pair of the CSR
+                        HIP_TRY(t.d_hit_scores.ensure(total));
+                        PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
+                        pfq::launch_hit_scores(t.hp, d_seq, d_off, n_reads, threshold, t.d_hit_off.p, t.d_hit_leaves.p, t.d_col_row.p,
+                                               t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
+                    }
                     HIP_TRY(hipStreamSynchronize(st));
                 }
             } else PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, 4));
+            if (want_scores) {
+                PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
+                t.scores_valid = true;
+                t.scores_n = total;
+            }
             hits->n_reads = n_reads;
             hits->offsets = t.h_hit_off;
             hits->leaves = t.h_hit_leaves;
@@ -1597,6 +1617,7 @@ struct QueryRun {
 
 int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, uint64_t total_bytes,
                  float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
+    t.scores_valid = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
     PFQ_TRY(q.plan());
     return q.run();
@@ -2355,15 +2376,24 @@ void pfq_tree_close(pfq_tree *tree) {
         if (h) (void)hipHostFree(h);
     if (tree->h_hit_off) (void)hipHostFree(tree->h_hit_off);
     if (tree->h_hit_leaves) (void)hipHostFree(tree->h_hit_leaves);
+    if (tree->h_hit_scores) (void)hipHostFree(tree->h_hit_scores);
 
     if (tree->h_pair_cursor) (void)hipHostFree(tree->h_pair_cursor);
     if (tree->hint_ev) (void)hipEventDestroy(tree->hint_ev);
     delete tree;
 }
 
+// Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
+static int check_flags(pfq_tree &t, uint32_t flags) {
+    t.scores_valid = false;
+    if ((flags & PFQ_WANT_SCORES) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SCORES needs PFQ_WANT_HITS");
+    return PFQ_OK;
+}
+
 int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_reads,
                            uint64_t total_bytes, float threshold, uint32_t flags, void *stream, pfq_hits *hits) {
     if (!tree || (n_reads && (!d_seq || !d_offsets))) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(check_flags(*tree, flags));
     PFQ_TRY(use_device(tree->device));
     return query_device(*tree, d_seq, d_offsets, n_reads, total_bytes, threshold, flags, (hipStream_t)stream, hits);
 }
@@ -2371,6 +2401,7 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
 int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets, uint64_t n_reads, float threshold,
                     uint32_t flags, pfq_hits *hits) {
     if (!tree || (n_reads && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(check_flags(*tree, flags));
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
     uint64_t total = n_reads ? offsets[n_reads] : 0;
@@ -2394,6 +2425,14 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
     HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
     t.in_used[slot] = true;
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
+    return PFQ_OK;
+}
+
+int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits) {
+    if (!tree || !scores || !n_hits) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->scores_valid) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for scores (PFQ_WANT_SCORES)");
+    *scores = tree->h_hit_scores;
+    *n_hits = tree->scores_n;
     return PFQ_OK;
 }
 

@@ -340,6 +340,11 @@ void launch_hits_csr(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_al
                      uint32_t *d_cnt, unsigned long long *d_sums, unsigned long long *d_off, hipStream_t st);
 void launch_hits_fill(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_allhit, uint64_t n_reads, const unsigned long long *d_off,
                       uint32_t *d_cnt, uint32_t *d_leaves, hipStream_t st);
+// PFQ_WANT_SCORES: d_scores[j] = the number of k-mers of read r contained in the filter of hit leaf d_hit_leaves[j],
+// d_hit_off[r] <= j < d_hit_off[r + 1] (the CSR of launch_hits_fill); column c's filter is row d_col_row[c] of d_bits.
+void launch_hit_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, float threshold,
+                       const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
+                       uint64_t n_words, uint32_t *d_scores, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -3263,6 +3263,73 @@ void launch_hits_fill(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_a
     hipLaunchKernelGGL(k_hit_sort, dim3(4096), dim3(256), 0, st, d_off, d_leaves, d_allhit, n_reads);
 }
 
+// PFQ_WANT_SCORES: score[j] = num_matches of query_passes (query.rs:38-49) on the filter of hit leaf j — the read's canonical
+// k-mers, duplicates counted, whose num_hashes probed bits are all set (bloom_filter.rs:312-332).  One wave per read with hits.
+// A read whose need is at least its k-mer count (threshold 1, reads without k-mers) contains every k-mer in each leaf it hits:
+// the score is n_kmers and nothing is probed.  Otherwise the wave takes the read's hits 64 at a time (lane j accumulates hit j
+// of the chunk, so every score is written once) and, window by window, every lane probes its k-mer's bits in the hit leaf's
+// node-major filter, eight probes in flight, until one is 0.
+__global__ void __launch_bounds__(256) k_hit_scores(HashParams hp, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ off, uint64_t n_reads,
+                                                    float threshold, const unsigned long long *__restrict__ hit_off,
+                                                    const uint32_t *__restrict__ hit_leaves, const uint32_t *__restrict__ col_row,
+                                                    const uint64_t *__restrict__ bits, uint64_t n_words, uint32_t *__restrict__ scores) {
+    __shared__ BlockLds lds;
+    fill_complement(lds.comp);
+    __syncthreads();
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, H = hp.num_hashes;
+    for (uint64_t r = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; r < n_reads; r += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const uint64_t h0 = hit_off[r], h1 = hit_off[r + 1];
+        if (h0 == h1) continue;
+        const uint64_t o = off[r], len = off[r + 1] - o;
+        const uint64_t n = len >= hp.k ? len - hp.k + 1 : 0;
+        if (need_kmers(threshold, n) >= n) {
+            for (uint64_t j = h0 + lane; j < h1; j += 64) scores[j] = (uint32_t)n;
+            continue;
+        }
+        for (uint64_t c0 = h0; c0 < h1; c0 += 64) {
+            const uint32_t nh = (uint32_t)min<uint64_t>(h1 - c0, 64);
+            const uint32_t my_row = lane < nh ? col_row[hit_leaves[c0 + lane]] : 0u;
+            uint32_t acc = 0;
+            for (uint64_t base = 0; base < n; base += WIN_KMERS) {
+                const uint32_t cnt = (uint32_t)min<uint64_t>(n - base, WIN_KMERS);
+                stage_window(lds, wave, seq + o, base, cnt, hp.k);
+                const bool valid = lane < cnt;
+                uint64_t kh1, kh2;
+                kmer_hashes(lds, wave, lane, cnt, valid, hp, kh1, kh2);
+                for (uint32_t j = 0; j < nh; ++j) {
+                    const uint64_t *f = bits + (uint64_t)bcast_u32(my_row, j) * n_words;
+                    ProbeIter it;
+                    it.init(kh1, kh2, hp);
+                    bool in = valid;
+                    for (uint32_t i = 0; i < H && ballot64(in) != 0; i += 8) {  // (i is wave-uniform)
+                        uint32_t idx[8];
+                        uint64_t w[8];
+#pragma unroll
+                        for (uint32_t b = 0; b < 8; ++b) {
+                            const uint32_t p = i + b;
+                            idx[b] = p == 0 ? it.i0 : p == 1 ? it.g : p == 2 ? it.x : (p < H ? it.step(hp) : 0u);
+                            w[b] = (in && p < H) ? f[idx[b] >> 6] : ~0ull;
+                        }
+#pragma unroll
+                        for (uint32_t b = 0; b < 8; ++b) in = in && ((w[b] >> (idx[b] & 63u)) & 1ull);
+                    }
+                    const uint32_t c = (uint32_t)__popcll(ballot64(in));
+                    acc += lane == j ? c : 0u;
+                }
+            }
+            if (lane < nh) scores[c0 + lane] = acc;
+        }
+    }
+}
+void launch_hit_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, float threshold,
+                       const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
+                       uint64_t n_words, uint32_t *d_scores, hipStream_t st) {
+    if (!n_reads) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_reads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192);
+    hipLaunchKernelGGL(k_hit_scores, dim3(blocks), dim3(256), 0, st, hp, d_seq, d_off, n_reads, threshold, d_hit_off, d_hit_leaves,
+                       d_col_row, d_bits, n_words, d_scores);
+}
+
 // ---- test / bench helpers ----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_debug_indices(HashParams hp, const uint8_t *seq, uint64_t len, uint64_t *out) {
     __shared__ BlockLds lds;

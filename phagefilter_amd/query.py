@@ -204,20 +204,32 @@ class BloomTree:
         return out
 
     # ---- query
-    def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False):
-        """One block of reads from host memory.  Returns None or (offsets, leaves) CSR."""
+    def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
+                     want_scores: bool = False):
+        """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
+        (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores)."""
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         hits = _ffi.Hits()
-        _ffi.check(_ffi.lib().pfq_query_batch(self._h, seq.ctypes.data, off.ctypes.data, n, threshold,
-                                              _ffi.WANT_HITS if want_hits else 0, C.byref(hits)))
+        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0)
+        _ffi.check(_ffi.lib().pfq_query_batch(self._h, seq.ctypes.data, off.ctypes.data, n, threshold, flags, C.byref(hits)))
         if not want_hits:
             return None
         offs = np.ctypeslib.as_array(hits.offsets, shape=(n + 1,)).copy() if n else np.zeros(1, dtype=np.uint64)
         total = int(offs[-1])
         leaves = np.ctypeslib.as_array(hits.leaves, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
-        return offs, leaves
+        if not want_scores:
+            return offs, leaves
+        return offs, leaves, self.last_hit_scores().copy()
+
+    def last_hit_scores(self) -> np.ndarray:
+        """Scores of the hits of the last query call, which must have asked for them (view of the library's buffer, valid
+        until the next query call on this tree)."""
+        p = C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_last_hit_scores(self._h, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value,)) if n.value else np.zeros(0, dtype=np.uint32)
 
     def query_device(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float,
                      stream: int = 0) -> None:
@@ -225,16 +237,20 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, 0,
                                                      stream, None))
 
-    def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0):
-        """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) as views of the library's buffers
-        (valid until the next call on this tree)."""
+    def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
+                          want_scores: bool = False):
+        """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
+        (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree)."""
         hits = _ffi.Hits()
-        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, _ffi.WANT_HITS,
+        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0)
+        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         offs = np.ctypeslib.as_array(hits.offsets, shape=(n_reads + 1,)) if n_reads else np.zeros(1, dtype=np.uint64)
         total = int(offs[-1])
         leaves = np.ctypeslib.as_array(hits.leaves, shape=(total,)) if total else np.zeros(0, dtype=np.uint32)
-        return offs, leaves
+        if not want_scores:
+            return offs, leaves
+        return offs, leaves, self.last_hit_scores()
 
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
