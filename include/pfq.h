@@ -60,6 +60,15 @@ typedef struct pfq_hits {
 
 #define PFQ_WANT_HITS 1u /* fill pfq_hits (needed for POS/NEG filtering, main.rs:345-361) */
 #define PFQ_WANT_SCORES 2u /* also score every hit (pfq_last_hit_scores); only together with PFQ_WANT_HITS, alone: PFQ_ERR_ARG */
+/* Paired-end reads: reads 2i and 2i + 1 are the two mates of fragment i (an odd n_reads is PFQ_ERR_ARG).  Each mate is
+ * classified on its own, exactly like an unpaired read (its own n_kmers and need); the fragment's hit set is the union of the
+ * mates' sets, or with PFQ_PAIR_BOTH their intersection (a mate shorter than k passes every leaf: `either` gives every leaf,
+ * `both` the other mate's set).  The leaf counters count fragments, one per leaf of the fragment's set; pfq_hits has one row
+ * per fragment (n_reads / 2); pfq_last_hit_scores gives per (fragment, listed leaf) the matched k-mers of both mates summed,
+ * each counted on that leaf's own filter.  Without PFQ_WANT_HITS the call returns once the mates' hit lists are checked and
+ * the fragment kernels are queued. */
+#define PFQ_PAIRED 4u
+#define PFQ_PAIR_BOTH 8u /* only together with PFQ_PAIRED, alone: PFQ_ERR_ARG */
 
 /* ---- database ---- */
 

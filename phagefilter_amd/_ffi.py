@@ -55,6 +55,8 @@ class Profile(C.Structure):
 
 WANT_HITS = 1
 WANT_SCORES = 2
+PAIRED = 4
+PAIR_BOTH = 8
 _lib = None
 
 

@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <random>
 #include <set>
@@ -814,6 +815,63 @@ struct ReadQueue {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// paired-end input: two streams whose records are mates by index (--reads2), or one stream of adjacent mates
+// (--interleaved).  Fragments come out as batches of records 2i (R1) and 2i + 1 (R2), what PFQ_PAIRED takes.
+// ---------------------------------------------------------------------------------------------------------------
+struct PairSource {
+    ReadQueue &q1;
+    ReadQueue *q2;        // nullptr: interleaved (mates are records 2i, 2i + 1 of q1)
+    Batch b1, b2;
+    uint64_t n_pairs = 0;  // fragments handed out so far
+    std::string err;       // fatal, once the fragments before it have been processed
+    bool done = false;
+
+    // the mate id without its trailing "/1" (R1) or "/2" (R2)
+    static std::string_view base_id(std::string_view id, char mate) {
+        if (id.size() >= 2 && id[id.size() - 2] == '/' && id[id.size() - 1] == mate) id.remove_suffix(2);
+        return id;
+    }
+    // Appends up to max_frags fragments (ids and qualities kept) to `out`; false: no fragment follows (end of the input, or
+    // err: malformed input, streams of different lengths, mate ids that differ — the fragments before it are in `out`).
+    bool next(Batch &out, uint64_t max_frags) {
+        if (done) return false;
+        b1.clear();
+        b2.clear();
+        bool more1 = q1.fill(b1, q2 ? max_frags : 2 * max_frags, ~0ull), more2 = more1;
+        if (q2) more2 = q2->fill(b2, max_frags, ~0ull);
+        const Batch &m1 = b1, &m2 = q2 ? b2 : b1;
+        const uint64_t n1 = q2 ? b1.n() : b1.n() / 2, n2 = q2 ? b2.n() : b1.n() / 2;
+        uint64_t n = std::min(n1, n2);
+        if (!q1.pending_error.empty()) err = q1.pending_error;
+        else if (q2 && !q2->pending_error.empty()) err = q2->pending_error;
+        else if (q2 && n1 != n2)
+            err = "paired input: " + std::string(n1 < n2 ? "--reads" : "--reads2") + " ends after " + std::to_string(n_pairs + n) +
+                  " records, its mate stream has more";
+        else if (!q2 && (b1.n() & 1))
+            err = "paired input: --interleaved has an odd number of records (" + std::to_string(2 * (n_pairs + n) + 1) + ")";
+        for (uint64_t i = 0; i < n; ++i) {  // Record::id() of the mates, "/1" and "/2" stripped, must be equal
+            const std::string_view a = m1.id(q2 ? i : 2 * i), b = m2.id(q2 ? i : 2 * i + 1);
+            if (base_id(a, '1') != base_id(b, '2')) {
+                err = "paired input: the ids of mates " + std::to_string(n_pairs + i + 1) + " differ: '" + std::string(a) + "' and '" +
+                      std::string(b) + "'";
+                n = i;
+                break;
+            }
+        }
+        if (q2)
+            for (uint64_t i = 0; i < n; ++i) {
+                out.append(b1, i, i + 1, true);
+                out.append(b2, i, i + 1, true);
+            }
+        else if (n)
+            out.append(b1, 0, 2 * n, true);
+        n_pairs += n;
+        done = !err.empty() || (!more1 && !more2);
+        return !done;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // argument parsing (clap surface of main.rs:44-136)
 // ---------------------------------------------------------------------------------------------------------------
 struct Args {
@@ -937,7 +995,8 @@ int cmd_query(int argc, char **argv) {
     std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
                              {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
-                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}};
+                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
+                             {"interleaved", 0, false}, {"pair-mode", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -950,6 +1009,15 @@ int cmd_query(int argc, char **argv) {
     const bool scores = a.flags.count("scores") != 0;
     const bool per_read = filtering || scores;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
+    // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
+    // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
+    const bool interleaved = a.flags.count("interleaved") != 0, has_reads2 = a.val.count("reads2") != 0;
+    if (interleaved && has_reads2) die("error: the argument '--reads2 <READS2>' cannot be used with '--interleaved'");
+    const bool paired = interleaved || has_reads2;
+    const std::string pair_mode = opt(a, "pair-mode", "either");
+    if (pair_mode != "either" && pair_mode != "both")
+        die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
+    if (a.val.count("pair-mode") && !paired) die("error: '--pair-mode' needs '--reads2' or '--interleaved'");
 
     // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
     // the per-genome counts are combined by one RCCL all-reduce at the end.  The reference has one rayon pool instead
@@ -1016,12 +1084,15 @@ int cmd_query(int argc, char **argv) {
         for (pfq_tree *t : trees) check(pfq_tree_prune(t, depth));
     }
     ReadQueue rq(reads, ov);
+    std::unique_ptr<ReadQueue> rq2;
+    if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
     // Page-locking costs ~1.7 s per GB here (hipHostMalloc), the pageable copy ~0.1 s per GB: pinned buffers only
     // pay off once every pooled buffer has been reused a few dozen times (inputs of >~ 10^9 reads).  Opt-in.
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    if (block != 0) rq.start(per_read, threads);
+    if (block != 0) rq.start(per_read || paired, threads);  // (paired: the mates' ids are compared)
+    if (block != 0 && rq2) rq2->start(true, threads);
 
     // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
     struct stat st;
@@ -1030,10 +1101,18 @@ int cmd_query(int argc, char **argv) {
     const char *ext = rq.peek_format() == Fmt::Fastq ? "fq" : "fa";
     int pos_fd = -1, neg_fd = -1;
     uint64_t pos_size = 0, neg_size = 0;  // bytes written so far (formatters write their parts at computed offsets)
-    if (pos && (pos_fd = open((out + "/POS_FILTERING." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+    // --reads2: the mates of R2 go to POS_FILTERING_2 / NEG_FILTERING_2, those of R1 to the files named _1
+    const std::string mate1 = has_reads2 ? "_1." : ".";
+    int pos2_fd = -1, neg2_fd = -1;
+    uint64_t pos2_size = 0, neg2_size = 0;
+    if (pos && (pos_fd = open((out + "/POS_FILTERING" + mate1 + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
         die("cannot create POS_FILTERING in " + out);
-    if (neg && (neg_fd = open((out + "/NEG_FILTERING." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+    if (neg && (neg_fd = open((out + "/NEG_FILTERING" + mate1 + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
         die("cannot create NEG_FILTERING in " + out);
+    if (has_reads2 && pos && (pos2_fd = open((out + "/POS_FILTERING_2." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+        die("cannot create POS_FILTERING_2 in " + out);
+    if (has_reads2 && neg && (neg2_fd = open((out + "/NEG_FILTERING_2." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+        die("cannot create NEG_FILTERING_2 in " + out);
     FILE *scores_f = nullptr;
     uint64_t kmer_size = 0;
     if (scores) {
@@ -1081,6 +1160,155 @@ int cmd_query(int argc, char **argv) {
     };
     if (block == 0) {
         // nothing to do: see above
+    } else if (paired) {
+        // Fragments, batch by batch: the parsers fill a batch of whole fragments (mates adjacent, -b counts fragments); every
+        // replica classifies a contiguous share of its fragments (every shard: all of them) with PFQ_PAIRED on its own
+        // thread, so no batch, device share or shard slot splits a pair; then the batch is written.  Without filtering or
+        // scores the calls want counts only.
+        uint64_t batch_frags = 1u << 19;
+        if (const char *e = getenv("PFQ_CLI_BATCH_READS")) batch_frags = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: several batches)
+        batch_frags = std::max<uint64_t>(block, batch_frags) / block * block;
+        const uint32_t flags = PFQ_PAIRED | (pair_mode == "both" ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) |
+                               (scores ? PFQ_WANT_SCORES : 0u);
+        PairSource src{rq, rq2.get(), {}, {}, 0, {}, false};
+        Batch b;
+        std::vector<std::vector<uint64_t>> t_off(n_trees), sub_off(n_trees);
+        std::vector<std::vector<uint32_t>> t_leaves(n_trees), t_scores(n_trees);
+        std::vector<uint64_t> f_off;
+        std::vector<uint32_t> f_leaves, f_scores;
+        std::string pos_out, neg_out, pos2_out, neg2_out, sc_out;
+        bool more = true;
+        while (more) {
+            b.clear();
+            more = src.next(b, batch_frags);
+            const uint64_t n = b.n(), nf = n / 2;
+            if (!nf) continue;
+            b.seq.resize(b.seq.size() + 16);
+            const uint64_t tq0 = ReadQueue::now_ns();
+            auto share = [&](size_t i, uint64_t &f0, uint64_t &f1) {
+                f0 = sharded ? 0 : nf * i / n_trees;
+                f1 = sharded ? nf : nf * (i + 1) / n_trees;
+            };
+            auto run = [&](size_t i) {
+                uint64_t f0, f1;
+                share(i, f0, f1);
+                const uint64_t r0 = 2 * f0, r1 = 2 * f1;
+                std::vector<uint64_t> &so = sub_off[i];
+                so.resize(r1 - r0 + 1);
+                for (uint64_t r = r0; r <= r1; ++r) so[r - r0] = b.off[r] - b.off[r0];
+                t_off[i].assign(f1 - f0 + 1, 0);
+                t_leaves[i].clear();
+                t_scores[i].clear();
+                if (r1 == r0) return;
+                pfq_hits hits{};
+                if (pfq_query_batch(trees[i], b.seq.data() + b.off[r0], so.data(), r1 - r0, threshold, flags, per_read ? &hits : nullptr) != PFQ_OK)
+                    fail_from_thread(pfq_last_error());
+                if (!per_read) return;
+                memcpy(t_off[i].data(), hits.offsets, (f1 - f0 + 1) * sizeof(uint64_t));
+                t_leaves[i].assign(hits.leaves, hits.leaves + hits.offsets[f1 - f0]);
+                if (scores) {
+                    const uint32_t *sc = nullptr;
+                    uint64_t n_sc = 0;
+                    if (pfq_last_hit_scores(trees[i], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    t_scores[i].assign(sc, sc + n_sc);
+                }
+            };
+            {
+                std::vector<std::thread> th;
+                for (size_t i = 1; i < n_trees; ++i) th.emplace_back(run, i);
+                run(0);
+                for (auto &t : th) t.join();
+            }
+            ns_gpu += ReadQueue::now_ns() - tq0;
+            n_total += n;
+            if (!per_read) continue;
+            // the fragments' lists in the whole tree's leaf order: replicas' shares one after the other; shards' lists per
+            // fragment in shard order, each offset by the shard's first leaf
+            f_off.assign(nf + 1, 0);
+            f_leaves.clear();
+            f_scores.clear();
+            for (uint64_t f = 0; f < nf; ++f) {
+                for (size_t i = 0; i < n_trees; ++i) {
+                    uint64_t f0, f1;
+                    share(i, f0, f1);
+                    if (f < f0 || f >= f1) continue;
+                    const uint64_t j0 = t_off[i][f - f0], j1 = t_off[i][f - f0 + 1];
+                    const uint32_t base = sharded ? (uint32_t)leaf_base[i] : 0u;
+                    for (uint64_t j = j0; j < j1; ++j) f_leaves.push_back(t_leaves[i][j] + base);
+                    if (scores) f_scores.insert(f_scores.end(), t_scores[i].begin() + j0, t_scores[i].begin() + j1);
+                }
+                f_off[f + 1] = f_leaves.size();
+            }
+            // every mate with its own id and its fragment's genomes; a fragment with genomes goes to POS, both mates alike
+            pos_out.clear();
+            neg_out.clear();
+            pos2_out.clear();
+            neg2_out.clear();
+            sc_out.clear();
+            for (uint64_t f = 0; f < nf; ++f) {
+                const bool mapped = f_off[f] != f_off[f + 1];
+                if (mapped ? !pos : !neg) continue;
+                for (uint64_t r = 2 * f; r < 2 * f + 2; ++r) {
+                    std::string &o = (r & 1) && has_reads2 ? (mapped ? pos2_out : neg2_out) : (mapped ? pos_out : neg_out);
+                    const bool fq = b.has_qual[r] != 0;
+                    const std::string_view id = b.id(r);
+                    o.push_back(fq ? '@' : '>');
+                    o.append(id.data(), id.size());
+                    if (mapped) {  // get_ext_id: "{id} |{g1,g2}", genomes in leaf order
+                        o.append(" |");
+                        for (uint64_t j = f_off[f]; j < f_off[f + 1]; ++j) {
+                            if (j != f_off[f]) o.push_back(',');
+                            o.append(leaf_names[f_leaves[j]]);
+                        }
+                    }
+                    o.push_back('\n');
+                    const uint64_t len = b.off[r + 1] - b.off[r], at = o.size();
+                    o.resize(at + len);
+                    copy_upper(&o[at], b.seq.data() + b.off[r], len);
+                    o.push_back('\n');
+                    if (fq) {
+                        const std::string_view q = b.quality(r);
+                        o.append("+\n");
+                        o.append(q.data(), q.size());
+                        o.push_back('\n');
+                    }
+                }
+            }
+            if (scores) {
+                // READ_SCORES.tsv: per fragment with hits (R1's id), both mates' k-mers and matched k-mers per genome, best first
+                std::vector<uint64_t> order;
+                char num[64];
+                for (uint64_t f = 0; f < nf; ++f) {
+                    if (f_off[f] == f_off[f + 1]) continue;
+                    order.clear();
+                    for (uint64_t j = f_off[f]; j < f_off[f + 1]; ++j) order.push_back(j);
+                    std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return f_scores[x] > f_scores[y]; });
+                    uint64_t nk = 0;
+                    for (uint64_t r = 2 * f; r < 2 * f + 2; ++r) {
+                        const uint64_t len = b.off[r + 1] - b.off[r];
+                        nk += len >= kmer_size ? len - kmer_size + 1 : 0;
+                    }
+                    const std::string_view id = b.id(2 * f);
+                    for (uint64_t j : order) {
+                        sc_out.append(id.data(), id.size());
+                        sc_out.append(num, (size_t)snprintf(num, sizeof num, "\t%llu\t", (unsigned long long)nk));
+                        sc_out.append(leaf_names[f_leaves[j]]);
+                        sc_out.append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", f_scores[j]));
+                    }
+                }
+                if (!sc_out.empty() && fwrite(sc_out.data(), 1, sc_out.size(), scores_f) != sc_out.size()) die("short write to READ_SCORES.tsv");
+            }
+            auto put = [&](int fd, const std::string &o, uint64_t &size) {
+                if (fd < 0 || o.empty()) return;
+                write_at(fd, o.data(), o.size(), size);
+                size += o.size();
+            };
+            put(pos_fd, pos_out, pos_size);
+            put(neg_fd, neg_out, neg_size);
+            put(pos2_fd, pos2_out, pos2_size);
+            put(neg2_fd, neg2_out, neg2_size);
+        }
+        if (!src.err.empty()) rq.pending_error = src.err;  // fatal below, after the outputs of the fragments before it
     } else if (!per_read && sharded) {
         // Counts only, shards: every parsed segment goes to every shard's thread; segment k sits in ring[k % W] until the
         // last shard is done with it, then goes back to the reader.  W is what the reader's pool takes back, so at most W
@@ -1666,6 +1894,8 @@ int cmd_query(int argc, char **argv) {
     }
     if (pos_fd >= 0) close(pos_fd);
     if (neg_fd >= 0) close(neg_fd);
+    if (pos2_fd >= 0) close(pos2_fd);
+    if (neg2_fd >= 0) close(neg2_fd);
     if (scores_f && fclose(scores_f) != 0) die("short write to READ_SCORES.tsv");
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
     if (sharded) {
@@ -1812,11 +2042,22 @@ int cmd_add(int argc, char **argv) {
 // ---------------------------------------------------------------------------------------------------------------
 int cmd_ingest_check(int argc, char **argv) {
     std::vector<Opt> opts = {{"reads", 'r', true}, {"threads", 't', true}, {"format", 'F', true}, {"dump", 0, false},
-                             {"count", 0, false}, {"block-size-reads", 'b', true}};
+                             {"count", 0, false}, {"block-size-reads", 'b', true}, {"reads2", 0, true}, {"interleaved", 0, false}};
     Args a = parse(argc, argv, 2, opts);
-    ReadQueue rq(req(a, "reads"), to_fmt(opt(a, "format", "auto")));
+    // --reads2 / --interleaved: the fragments exactly as `query` pairs them, mates adjacent (-b counts fragments)
+    const bool interleaved = a.flags.count("interleaved") != 0, has_reads2 = a.val.count("reads2") != 0;
+    if (interleaved && has_reads2) die("error: the argument '--reads2 <READS2>' cannot be used with '--interleaved'");
+    const bool paired = interleaved || has_reads2;
+    const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
+    ReadQueue rq(req(a, "reads"), ov);
+    std::unique_ptr<ReadQueue> rq2;
+    if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
     const bool count_only = a.flags.count("count") != 0;  // what `query` without filtering keeps: bases and offsets only
-    rq.start(!count_only, (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256));
+    if (count_only && paired) die("error: '--count' cannot be used with '--reads2' or '--interleaved' (mates keep their ids)");
+    const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);
+    rq.start(!count_only, threads);
+    if (rq2) rq2->start(true, threads);
+    PairSource src{rq, rq2.get(), {}, {}, 0, {}, false};
     const uint64_t block = std::max<uint64_t>(1, to_u64(opt(a, "block-size-reads", "1000000"), "block-size-reads"));
     const bool dump = a.flags.count("dump") != 0;
     uint64_t n = 0, bytes = 0, h = 0xcbf29ce484222325ull;
@@ -1829,7 +2070,7 @@ int cmd_ingest_check(int argc, char **argv) {
     bool more = true;
     while (more) {
         b.clear();
-        more = rq.fill(b, block, ~0ull);
+        more = paired ? src.next(b, block) : rq.fill(b, block, ~0ull);
         if (count_only) {
             n += b.n();
             bytes += b.seq.size();
@@ -1852,6 +2093,7 @@ int cmd_ingest_check(int argc, char **argv) {
     }
     printf("reads=%llu bases=%llu fnv=%016llx\n", (unsigned long long)n, (unsigned long long)bytes, (unsigned long long)h);
     rq.report_timing();
+    if (!src.err.empty()) die(src.err);
     if (!rq.pending_error.empty()) die(rq.pending_error);
     return 0;
 }
@@ -1871,7 +2113,16 @@ void usage() {
             "shard i on device i mod N of the N listed; every shard sees every read and loads only its own .bf files, so a\n"
             "database larger than one GPU's memory can be queried.  Needs at least N shards.  Same outputs as the whole tree\n"
             "--scores: also write READ_SCORES.tsv into --out: per read record and genome it hits, how many of the read's k-mers\n"
-            "the genome's filter contains (\"#read_id<TAB>kmers<TAB>genome<TAB>matched_kmers\", best genome first)\n");
+            "the genome's filter contains (\"#read_id<TAB>kmers<TAB>genome<TAB>matched_kmers\", best genome first)\n"
+            "--reads2 <R2>: paired-end reads, R1 from -r and R2 from here (files or directories; mates by record index), or\n"
+            "--interleaved: the mates are adjacent records of -r.  Mate ids must agree once a trailing /1 (R1) and /2 (R2) are\n"
+            "stripped; a mismatch or one stream ending first is fatal after the fragments before it.  Every mate is judged on\n"
+            "its own; the fragment's genomes are the union of its mates' (--pair-mode either, the default) or their\n"
+            "intersection (--pair-mode both).  CLASSIFICATION.csv counts fragments; -b counts fragments.  A fragment with\n"
+            "genomes goes to POS, both mates alike, each under its own id with the fragment's \" |g1,g2\":\n"
+            "POS_FILTERING_1/_2 and NEG_FILTERING_1/_2 (--interleaved: POS_FILTERING / NEG_FILTERING, mates adjacent).\n"
+            "With --scores: one line per fragment and genome, R1's id, both mates' k-mers and matched k-mers summed.\n"
+            "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
 }
 
 }  // namespace

@@ -260,6 +260,11 @@ struct pfq_tree {
     size_t h_hit_scores_cap = 0;
     bool scores_valid = false;
     uint64_t scores_n = 0;
+    // PFQ_PAIRED: the mates' increments land in d_pair_sink (never read); the fragment CSR is built into d_frag_off /
+    // d_frag_leaves and its histogram goes into d_counts.  d_pair_long: fragments queued for a wave; d_pair_misc: [0] queued,
+    // [1] all-leaf fragments left unlisted
+    DevBuf<unsigned long long> d_pair_sink, d_frag_off, d_pair_misc;
+    DevBuf<uint32_t> d_frag_leaves, d_pair_long;
 };
 
 namespace {
@@ -856,7 +861,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
@@ -879,9 +884,12 @@ struct QueryRun {
     int plan() {
         if (t.root < 0) return fail(PFQ_ERR_STATE, "query on an empty tree");
         PFQ_TRY(build_layout(t));
-        want_hits = (flags & PFQ_WANT_HITS) != 0;
+        user_hits = (flags & PFQ_WANT_HITS) != 0;
         want_scores = (flags & PFQ_WANT_SCORES) != 0;
-        if (want_hits && !hits) return fail(PFQ_ERR_ARG, "PFQ_WANT_HITS set but hits == NULL");
+        paired = (flags & PFQ_PAIRED) != 0;
+        pair_both = (flags & PFQ_PAIR_BOTH) != 0;
+        if (user_hits && !hits) return fail(PFQ_ERR_ARG, "PFQ_WANT_HITS set but hits == NULL");
+        want_hits = user_hits || paired;  // (fragments are combined from the mates' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
         if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipStreamSynchronize(t.last_stream));
@@ -890,6 +898,7 @@ struct QueryRun {
         t.last_n_reads = n_reads;
         PFQ_TRY(ensure_scratch(t, n_reads, want_hits));
         nl = t.leaves.size();
+        if (paired) HIP_TRY(t.d_pair_sink.ensure(nl + 1));
         nc = t.n_cols;  // leaf + guard columns = buckets of the bucketed path (block mode: blocks of 8 leaf columns)
         with_guards = !t.guard_col.empty();
         // bucketed path: threshold 1 (any certificate kernel), or 0 < threshold < 1 with probe records (per-pair k-mer miss bits)
@@ -1125,7 +1134,7 @@ struct QueryRun {
             a.n_cols = t.n_cols;
             a.guard_off = t.d_guard_off.p;
             a.guard_col = t.d_guard_col.p;
-            a.counts = t.d_counts.p;
+            a.counts = count_dst();
             a.hit_pairs = want_hits ? t.d_hit_pairs.p : nullptr;
             a.hit_cap = hit_cap;
             a.hit_cursor = t.d_cursors.p;
@@ -1169,6 +1178,9 @@ struct QueryRun {
         }
         return PFQ_OK;
     }
+
+    // where the classify / finalize kernels count: the tree's counters, or with PFQ_PAIRED a sink (fragments count afterwards)
+    unsigned long long *count_dst() const { return paired ? t.d_pair_sink.p : t.d_counts.p; }
 
     // deferred-pair buffer, bucket histograms, probe records, miss words; block tables on first use
     int setup_pairs() {
@@ -1463,7 +1475,7 @@ struct QueryRun {
         f.bucket_off = off;
         f.sub_log2 = sub_log2;
         f.threshold = threshold;
-        f.counts = t.d_counts.p;
+        f.counts = count_dst();
         f.hit_pairs = a.hit_pairs;
         f.hit_cap = hit_cap;
         f.hit_cursor = t.d_cursors.p;
@@ -1502,7 +1514,7 @@ struct QueryRun {
         f.miss_words = v.miss_words;
         f.miss_pos = v.miss_pos;
         f.threshold = threshold;
-        f.counts = t.d_counts.p;
+        f.counts = count_dst();
         f.hit_pairs = a.hit_pairs;
         f.hit_cap = hit_cap;
         f.hit_cursor = t.d_cursors.p;
@@ -1539,6 +1551,7 @@ struct QueryRun {
         unsigned long long cursors[2] = {0, 0};
         HIP_TRY(hipMemcpy(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost));
         if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)cursors[0] / (double)n_reads);
+        if (cursors[0] <= hit_cap && paired) return pair_hits(cursors[0]);
         if (cursors[0] <= hit_cap) {
             // CSR read -> leaves (ascending; reads that pass every node list every leaf), built on the device from the
             // unordered hit pairs and copied into page-locked host buffers
@@ -1603,10 +1616,85 @@ struct QueryRun {
         return PFQ_OK;
     }
 
+    // PFQ_PAIRED, after the mates' hit pairs are complete: the mate CSR (all-hit mates as flags only), the fragment CSR
+    // (union / intersection per fragment), its histogram into the tree's counters and — PFQ_WANT_HITS — the lists and
+    // scores copied out.  Without PFQ_WANT_HITS nothing more is waited for: every all-leaf fragment is a count, the lists
+    // hold at most the mates' n_pairs entries.
+    int pair_hits(uint64_t n_pairs) {
+        const uint64_t n_frag = n_reads / 2;
+        auto host_room = [&](void **p, size_t &cap, size_t want) -> int {
+            if (want <= cap) return PFQ_OK;
+            if (*p) (void)hipHostFree(*p);
+            *p = nullptr;
+            cap = 0;
+            const size_t grown = want + want / 4 + 4096;
+            HIP_TRY(hipHostMalloc(p, grown, hipHostMallocDefault));
+            cap = grown;
+            return PFQ_OK;
+        };
+        uint64_t total = 0;
+        if (n_frag && nl) {
+            HIP_TRY(t.d_hit_cnt.ensure(n_reads + 1));
+            HIP_TRY(t.d_hit_off.ensure(n_reads + 2));
+            HIP_TRY(t.d_hit_sums.ensure((n_reads + 4095) / 4096 + 2));
+            HIP_TRY(t.d_hit_leaves.ensure(n_pairs + 1));
+            HIP_TRY(t.d_frag_off.ensure(n_frag + 2));
+            HIP_TRY(t.d_pair_long.ensure(n_frag + 1));
+            HIP_TRY(t.d_pair_misc.ensure(2));
+            HIP_TRY(hipMemsetAsync(t.d_hit_cnt.p, 0, (n_reads + 1) * 4, st));
+            HIP_TRY(hipMemsetAsync(t.d_pair_misc.p, 0, 16, st));
+            pfq::launch_hits_csr(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, (uint32_t)nl, false, t.d_hit_cnt.p, t.d_hit_sums.p, t.d_hit_off.p, st);
+            pfq::launch_hits_fill(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
+            // (the scatter leaves d_hit_cnt zero: it holds the fragments' counts next)
+            pfq::launch_pair_combine(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, user_hits, t.d_hit_cnt.p,
+                                     t.d_pair_long.p, t.d_pair_misc.p, t.d_hit_sums.p, t.d_frag_off.p, st);
+            HIP_TRY(hipGetLastError());
+            uint64_t room = n_pairs;  // a union holds at most both mates' entries
+            if (user_hits) {
+                PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, (n_frag + 1) * 8));
+                HIP_TRY(hipMemcpyAsync(t.h_hit_off, t.d_frag_off.p, (n_frag + 1) * 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                total = room = t.h_hit_off[n_frag];
+            }
+            HIP_TRY(t.d_frag_leaves.ensure(room + 1));
+            pfq::launch_pair_fill(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, t.d_pair_long.p, t.d_pair_misc.p,
+                                  t.d_frag_off.p, t.d_frag_leaves.p, st);
+            pfq::launch_pair_leaf_counts(t.d_frag_leaves.p, t.d_frag_off.p + n_frag, t.d_pair_misc.p, (uint32_t)nl, room, t.d_counts.p, st);
+            HIP_TRY(hipGetLastError());
+            if (user_hits && total) {
+                PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, (size_t)total * 4 + 4));
+                HIP_TRY(hipMemcpyAsync(t.h_hit_leaves, t.d_frag_leaves.p, total * 4, hipMemcpyDeviceToHost, st));
+                if (want_scores) {
+                    HIP_TRY(t.d_hit_scores.ensure(total));
+                    PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
+                    pfq::launch_pair_scores(t.hp, d_seq, d_off, n_frag, threshold, pair_both, t.d_frag_off.p, t.d_frag_leaves.p, t.d_col_row.p,
+                                            t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
+                    HIP_TRY(hipGetLastError());
+                    HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
+                }
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+        } else if (user_hits) {  // no fragments, or no leaves: empty lists
+            PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, (n_frag + 1) * 8));
+            for (uint64_t i = 0; i <= n_frag; ++i) t.h_hit_off[i] = 0;
+        }
+        if (!user_hits) return PFQ_OK;
+        PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, (size_t)total * 4 + 4));
+        if (want_scores) {
+            PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
+            t.scores_valid = true;
+            t.scores_n = total;
+        }
+        hits->n_reads = n_frag;
+        hits->offsets = t.h_hit_off;
+        hits->leaves = t.h_hit_leaves;
+        return PFQ_OK;
+    }
+
     int run() {
         for (int attempt_no = 0; attempt_no < 2; ++attempt_no) {
             PFQ_TRY(attempt(attempt_no));
-            if (!want_hits) return PFQ_OK;
+            if (!want_hits) return PFQ_OK;  // (PFQ_PAIRED always builds the mates' hit lists)
             bool done = false;
             PFQ_TRY(read_hits(done));
             if (done) return PFQ_OK;
@@ -2384,16 +2472,18 @@ void pfq_tree_close(pfq_tree *tree) {
 }
 
 // Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
-static int check_flags(pfq_tree &t, uint32_t flags) {
+static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     t.scores_valid = false;
     if ((flags & PFQ_WANT_SCORES) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SCORES needs PFQ_WANT_HITS");
+    if ((flags & PFQ_PAIRED) && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
+    if ((flags & PFQ_PAIR_BOTH) && !(flags & PFQ_PAIRED)) return fail(PFQ_ERR_ARG, "PFQ_PAIR_BOTH needs PFQ_PAIRED");
     return PFQ_OK;
 }
 
 int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_reads,
                            uint64_t total_bytes, float threshold, uint32_t flags, void *stream, pfq_hits *hits) {
     if (!tree || (n_reads && (!d_seq || !d_offsets))) return fail(PFQ_ERR_ARG, "null argument");
-    PFQ_TRY(check_flags(*tree, flags));
+    PFQ_TRY(check_flags(*tree, flags, n_reads));
     PFQ_TRY(use_device(tree->device));
     return query_device(*tree, d_seq, d_offsets, n_reads, total_bytes, threshold, flags, (hipStream_t)stream, hits);
 }
@@ -2401,7 +2491,7 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
 int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets, uint64_t n_reads, float threshold,
                     uint32_t flags, pfq_hits *hits) {
     if (!tree || (n_reads && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
-    PFQ_TRY(check_flags(*tree, flags));
+    PFQ_TRY(check_flags(*tree, flags, n_reads));
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
     uint64_t total = n_reads ? offsets[n_reads] : 0;

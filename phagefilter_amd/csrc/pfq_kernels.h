@@ -345,6 +345,25 @@ void launch_hits_fill(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_a
 void launch_hit_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, float threshold,
                        const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
                        uint64_t n_words, uint32_t *d_scores, hipStream_t st);
+// PFQ_PAIRED: reads 2f and 2f + 1 are the mates of fragment f; its hit set is the union (both = false) or the intersection of
+// theirs.  Input: the mate CSR of launch_hits_csr / launch_hits_fill with any_allhit = false (all-hit mates: d_allhit only).
+// launch_pair_combine: the fragment CSR's offsets d_frag_off[n_frag + 1] (count, then the scan of launch_hits_csr; d_cnt
+// [n_frag], d_sums as there, d_long [n_frag] a queue for waves, d_misc [2] zeroed by the caller: queued fragments, all-leaf
+// fragments left unlisted).  list_all: an all-leaf fragment lists every leaf (else it only counts, in d_misc[1]).
+// launch_pair_fill: the lists, ascending.  launch_pair_leaf_counts: adds the fragments' leaf counts to d_counts (d_total =
+// d_frag_off + n_frag; max_entries: a bound on it, sizes the grid).  launch_pair_scores: per listed (fragment, leaf), the
+// k-mers of both mates the leaf's filter contains.
+void launch_pair_combine(const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint8_t *d_allhit, uint64_t n_frag, bool both,
+                         uint32_t n_leaves, bool list_all, uint32_t *d_cnt, uint32_t *d_long, unsigned long long *d_misc, unsigned long long *d_sums,
+                         unsigned long long *d_frag_off, hipStream_t st);
+void launch_pair_fill(const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint8_t *d_allhit, uint64_t n_frag, bool both,
+                      uint32_t n_leaves, const uint32_t *d_long, const unsigned long long *d_misc, const unsigned long long *d_frag_off,
+                      uint32_t *d_frag_leaves, hipStream_t st);
+void launch_pair_leaf_counts(const uint32_t *d_frag_leaves, const unsigned long long *d_total, const unsigned long long *d_misc, uint32_t n_leaves,
+                             uint64_t max_entries, unsigned long long *d_counts, hipStream_t st);
+void launch_pair_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_frag, float threshold, bool both,
+                        const unsigned long long *d_frag_off, const uint32_t *d_frag_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
+                        uint64_t n_words, uint32_t *d_scores, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

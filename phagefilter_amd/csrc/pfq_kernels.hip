@@ -3263,12 +3263,48 @@ void launch_hits_fill(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_a
     hipLaunchKernelGGL(k_hit_sort, dim3(4096), dim3(256), 0, st, d_off, d_leaves, d_allhit, n_reads);
 }
 
+// The k-mers of one read (n of them, from `read`) contained in the filters of up to 64 leaves, the filter of lane j's leaf being
+// row my_row of `bits` (lanes j >= nh: none): lane j returns the count of leaf j.  Window by window, every lane probes its
+// k-mer's bits in each leaf's node-major filter, eight probes in flight, until one is 0.
+__device__ __forceinline__ uint32_t score_chunk(BlockLds &lds, uint32_t wave, uint32_t lane, const HashParams &hp, const uint8_t *read, uint64_t n,
+                                                uint32_t my_row, uint32_t nh, const uint64_t *__restrict__ bits, uint64_t n_words) {
+    const uint32_t H = hp.num_hashes;
+    uint32_t acc = 0;
+    for (uint64_t base = 0; base < n; base += WIN_KMERS) {
+        const uint32_t cnt = (uint32_t)min<uint64_t>(n - base, WIN_KMERS);
+        stage_window(lds, wave, read, base, cnt, hp.k);
+        const bool valid = lane < cnt;
+        uint64_t kh1, kh2;
+        kmer_hashes(lds, wave, lane, cnt, valid, hp, kh1, kh2);
+        for (uint32_t j = 0; j < nh; ++j) {
+            const uint64_t *f = bits + (uint64_t)bcast_u32(my_row, j) * n_words;
+            ProbeIter it;
+            it.init(kh1, kh2, hp);
+            bool in = valid;
+            for (uint32_t i = 0; i < H && ballot64(in) != 0; i += 8) {  // (i is wave-uniform)
+                uint32_t idx[8];
+                uint64_t w[8];
+#pragma unroll
+                for (uint32_t b = 0; b < 8; ++b) {
+                    const uint32_t p = i + b;
+                    idx[b] = p == 0 ? it.i0 : p == 1 ? it.g : p == 2 ? it.x : (p < H ? it.step(hp) : 0u);
+                    w[b] = (in && p < H) ? f[idx[b] >> 6] : ~0ull;
+                }
+#pragma unroll
+                for (uint32_t b = 0; b < 8; ++b) in = in && ((w[b] >> (idx[b] & 63u)) & 1ull);
+            }
+            const uint32_t c = (uint32_t)__popcll(ballot64(in));
+            acc += lane == j ? c : 0u;
+        }
+    }
+    return acc;
+}
+
 // PFQ_WANT_SCORES: score[j] = num_matches of query_passes (query.rs:38-49) on the filter of hit leaf j — the read's canonical
 // k-mers, duplicates counted, whose num_hashes probed bits are all set (bloom_filter.rs:312-332).  One wave per read with hits.
 // A read whose need is at least its k-mer count (threshold 1, reads without k-mers) contains every k-mer in each leaf it hits:
 // the score is n_kmers and nothing is probed.  Otherwise the wave takes the read's hits 64 at a time (lane j accumulates hit j
-// of the chunk, so every score is written once) and, window by window, every lane probes its k-mer's bits in the hit leaf's
-// node-major filter, eight probes in flight, until one is 0.
+// of the chunk, so every score is written once) through score_chunk.
 __global__ void __launch_bounds__(256) k_hit_scores(HashParams hp, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ off, uint64_t n_reads,
                                                     float threshold, const unsigned long long *__restrict__ hit_off,
                                                     const uint32_t *__restrict__ hit_leaves, const uint32_t *__restrict__ col_row,
@@ -3276,7 +3312,7 @@ __global__ void __launch_bounds__(256) k_hit_scores(HashParams hp, const uint8_t
     __shared__ BlockLds lds;
     fill_complement(lds.comp);
     __syncthreads();
-    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, H = hp.num_hashes;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (uint64_t r = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; r < n_reads; r += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
         const uint64_t h0 = hit_off[r], h1 = hit_off[r + 1];
         if (h0 == h1) continue;
@@ -3289,34 +3325,7 @@ __global__ void __launch_bounds__(256) k_hit_scores(HashParams hp, const uint8_t
         for (uint64_t c0 = h0; c0 < h1; c0 += 64) {
             const uint32_t nh = (uint32_t)min<uint64_t>(h1 - c0, 64);
             const uint32_t my_row = lane < nh ? col_row[hit_leaves[c0 + lane]] : 0u;
-            uint32_t acc = 0;
-            for (uint64_t base = 0; base < n; base += WIN_KMERS) {
-                const uint32_t cnt = (uint32_t)min<uint64_t>(n - base, WIN_KMERS);
-                stage_window(lds, wave, seq + o, base, cnt, hp.k);
-                const bool valid = lane < cnt;
-                uint64_t kh1, kh2;
-                kmer_hashes(lds, wave, lane, cnt, valid, hp, kh1, kh2);
-                for (uint32_t j = 0; j < nh; ++j) {
-                    const uint64_t *f = bits + (uint64_t)bcast_u32(my_row, j) * n_words;
-                    ProbeIter it;
-                    it.init(kh1, kh2, hp);
-                    bool in = valid;
-                    for (uint32_t i = 0; i < H && ballot64(in) != 0; i += 8) {  // (i is wave-uniform)
-                        uint32_t idx[8];
-                        uint64_t w[8];
-#pragma unroll
-                        for (uint32_t b = 0; b < 8; ++b) {
-                            const uint32_t p = i + b;
-                            idx[b] = p == 0 ? it.i0 : p == 1 ? it.g : p == 2 ? it.x : (p < H ? it.step(hp) : 0u);
-                            w[b] = (in && p < H) ? f[idx[b] >> 6] : ~0ull;
-                        }
-#pragma unroll
-                        for (uint32_t b = 0; b < 8; ++b) in = in && ((w[b] >> (idx[b] & 63u)) & 1ull);
-                    }
-                    const uint32_t c = (uint32_t)__popcll(ballot64(in));
-                    acc += lane == j ? c : 0u;
-                }
-            }
+            const uint32_t acc = score_chunk(lds, wave, lane, hp, seq + o, n, my_row, nh, bits, n_words);
             if (lane < nh) scores[c0 + lane] = acc;
         }
     }
@@ -3327,6 +3336,242 @@ void launch_hit_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_
     if (!n_reads) return;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_reads + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192);
     hipLaunchKernelGGL(k_hit_scores, dim3(blocks), dim3(256), 0, st, hp, d_seq, d_off, n_reads, threshold, d_hit_off, d_hit_leaves,
+                       d_col_row, d_bits, n_words, d_scores);
+}
+
+// ---- paired-end fragments (PFQ_PAIRED) ----------------------------------------------------------------------------------
+// Reads 2f and 2f + 1 are the mates of fragment f.  Each mate is classified on its own, with its own n_kmers and need; the
+// fragment's hit set is the union (`either`) or the intersection (`both`) of the mates' sets.  The input is the mate-level CSR
+// of launch_hits_csr / launch_hits_fill built without listing all-hit mates (need == 0: every leaf); those are d_allhit flags.
+// A fragment whose set is every leaf is listed only when the caller wants the lists; otherwise it is one count in misc[1] that
+// the histogram adds to every leaf.  Work per thread is bounded: a fragment with a mate list longer than PAIR_SHORT (or an
+// all-leaf fragment to list) is queued for a wave, whose 64 lanes each merge 1/64 of it from their own merge-path split.
+constexpr uint32_t PAIR_SHORT = 64;
+constexpr uint32_t PAIR_HIST_LDS = 8192;  // trees of up to this many leaves: a block counts in LDS (u32) and flushes once
+
+struct PairView {
+    const uint32_t *A, *B;  // ascending leaf lists of the two mates (empty for an all-hit mate)
+    uint32_t na, nb;
+    int both;               // 1: intersection, 0: union
+    bool all;               // the fragment's set is every leaf
+};
+__device__ __forceinline__ PairView pair_view(uint64_t f, const unsigned long long *__restrict__ hit_off, const uint32_t *__restrict__ hit_leaves,
+                                              const uint8_t *__restrict__ allhit, int both) {
+    PairView v;
+    const unsigned long long a0 = hit_off[2 * f], a1 = hit_off[2 * f + 1], b1 = hit_off[2 * f + 2];
+    v.A = hit_leaves + a0;
+    v.na = (uint32_t)(a1 - a0);
+    v.B = hit_leaves + a1;
+    v.nb = (uint32_t)(b1 - a1);
+    const bool fa = allhit[2 * f] != 0, fb = allhit[2 * f + 1] != 0;
+    v.both = both;
+    v.all = both ? (fa && fb) : (fa || fb);
+    if (both && fa != fb) {  // every leaf intersected with the other mate's set: that set (its union with an empty list)
+        if (fa) {
+            v.A = v.B;
+            v.na = v.nb;
+        }
+        v.nb = 0;
+        v.both = 0;
+    }
+    return v;
+}
+__device__ __forceinline__ bool pair_is_long(const PairView &v) { return v.na > PAIR_SHORT || v.nb > PAIR_SHORT; }
+
+// Steps [d0, d1) of the merge of A and B (an A element goes before an equal B element).  A B element is in both lists iff it
+// equals the A element taken just before it.  Union keeps every A element and the B elements not in A, intersection the B
+// elements in A.  The kept elements go to out, ascending (nullptr: count only); returns how many were kept.
+__device__ uint32_t merge_span(const PairView &v, uint32_t d0, uint32_t d1, uint32_t *out) {
+    uint32_t lo = d0 > v.nb ? d0 - v.nb : 0u, hi = min(d0, v.na);  // merge path: A elements among the first d0 steps
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (v.A[mid] <= v.B[d0 - mid - 1]) lo = mid + 1;
+        else hi = mid;
+    }
+    uint32_t i = lo, j = d0 - lo, c = 0;
+    for (uint32_t d = d0; d < d1; ++d) {
+        if (j >= v.nb || (i < v.na && v.A[i] <= v.B[j])) {
+            if (!v.both) {
+                if (out) out[c] = v.A[i];
+                ++c;
+            }
+            ++i;
+        } else {
+            const bool in_a = i > 0 && v.A[i - 1] == v.B[j];
+            if (in_a == (v.both != 0)) {
+                if (out) out[c] = v.B[j];
+                ++c;
+            }
+            ++j;
+        }
+    }
+    return c;
+}
+
+// cnt[f] = size of fragment f's list; long fragments are queued (misc[0]) and counted by k_pair_long<false>
+__global__ void __launch_bounds__(256) k_pair_count(const unsigned long long *__restrict__ hit_off, const uint32_t *__restrict__ hit_leaves,
+                                                    const uint8_t *__restrict__ allhit, uint64_t n_frag, int both, uint32_t n_leaves, int list_all,
+                                                    uint32_t *__restrict__ cnt, uint32_t *__restrict__ long_list, unsigned long long *misc) {
+    const uint32_t lane = lane_id();
+    for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n_frag; f += (uint64_t)gridDim.x * blockDim.x) {
+        const PairView v = pair_view(f, hit_off, hit_leaves, allhit, both);
+        bool to_wave = false, all_count = false;
+        uint32_t c = 0;
+        if (v.all) {
+            c = list_all ? n_leaves : 0u;
+            to_wave = list_all != 0;
+            all_count = !list_all;
+        } else if (pair_is_long(v)) to_wave = true;
+        else c = merge_span(v, 0, v.na + v.nb, nullptr);
+        cnt[f] = c;
+        const uint64_t act = ballot64(true), m_all = ballot64(all_count);
+        if (m_all && lane == (uint32_t)__builtin_ctzll(act)) atomicAdd(&misc[1], (unsigned long long)__popcll(m_all));
+        if (to_wave) long_list[atomicAdd(&misc[0], 1ull)] = (uint32_t)f;
+    }
+}
+// One wave per queued fragment: lane l merges steps [l * per, (l + 1) * per) of the na + nb; FILL: writes them at the lane's
+// exclusive prefix of the wave's counts (else: the wave's total into cnt[f]).
+template <bool FILL>
+__global__ void __launch_bounds__(256) k_pair_long(const unsigned long long *__restrict__ hit_off, const uint32_t *__restrict__ hit_leaves,
+                                                   const uint8_t *__restrict__ allhit, int both, uint32_t n_leaves, const uint32_t *__restrict__ long_list,
+                                                   const unsigned long long *__restrict__ misc, uint32_t *__restrict__ cnt,
+                                                   const unsigned long long *__restrict__ frag_off, uint32_t *__restrict__ frag_leaves) {
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint64_t n_long = misc[0];
+    for (uint64_t q = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; q < n_long; q += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const uint64_t f = long_list[q];
+        const PairView v = pair_view(f, hit_off, hit_leaves, allhit, both);
+        if (v.all) {  // (queued only when the lists are wanted)
+            if (FILL)
+                for (uint32_t l = lane; l < n_leaves; l += 64) frag_leaves[frag_off[f] + l] = l;
+            else if (lane == 0) cnt[f] = n_leaves;
+            continue;
+        }
+        const uint32_t total = v.na + v.nb, per = (total + 63u) >> 6;
+        const uint32_t d0 = min(lane * per, total), d1 = min(d0 + per, total);
+        const uint32_t c = merge_span(v, d0, d1, nullptr);
+        if (!FILL) {
+            uint32_t s = c;
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d);
+            if (lane == 0) cnt[f] = s;
+            continue;
+        }
+        uint32_t incl = c;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += o;
+        }
+        merge_span(v, d0, d1, frag_leaves + frag_off[f] + (incl - c));
+    }
+}
+__global__ void __launch_bounds__(256) k_pair_fill(const unsigned long long *__restrict__ hit_off, const uint32_t *__restrict__ hit_leaves,
+                                                   const uint8_t *__restrict__ allhit, uint64_t n_frag, int both,
+                                                   const unsigned long long *__restrict__ frag_off, uint32_t *__restrict__ frag_leaves) {
+    for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < n_frag; f += (uint64_t)gridDim.x * blockDim.x) {
+        const PairView v = pair_view(f, hit_off, hit_leaves, allhit, both);
+        if (v.all || pair_is_long(v)) continue;
+        merge_span(v, 0, v.na + v.nb, frag_leaves + frag_off[f]);
+    }
+}
+// The fragments' leaf counts: a histogram of the fragment lists (*total entries), plus misc[1] (all-leaf fragments not listed)
+// on every leaf, added to the tree's u64 counters.  LDS: u32 counters per block (a block's count of one leaf is at most the
+// number of fragments), flushed once.
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_pair_hist(const uint32_t *__restrict__ frag_leaves, const unsigned long long *__restrict__ total_ptr,
+                                                   const unsigned long long *__restrict__ misc, uint32_t n_leaves, unsigned long long *counts) {
+    __shared__ uint32_t h[LDS ? PAIR_HIST_LDS : 1];
+    if (LDS) {
+        for (uint32_t c = threadIdx.x; c < n_leaves; c += blockDim.x) h[c] = 0;
+        __syncthreads();
+    }
+    const uint64_t total = *total_ptr;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t l = frag_leaves[i];
+        if (LDS) atomicAdd(&h[l], 1u);
+        else atomicAdd(&counts[l], 1ull);
+    }
+    const unsigned long long n_all = blockIdx.x == 0 ? misc[1] : 0ull;
+    if (LDS) {
+        __syncthreads();
+        for (uint32_t c = threadIdx.x; c < n_leaves; c += blockDim.x) {
+            const unsigned long long v = (unsigned long long)h[c] + n_all;
+            if (v) atomicAdd(&counts[c], v);
+        }
+    } else if (n_all) {
+        for (uint32_t c = threadIdx.x; c < n_leaves; c += blockDim.x) atomicAdd(&counts[c], n_all);
+    }
+}
+// Pair scores: per (fragment, listed leaf), the k-mers of both mates contained in that leaf's filter, summed.  A mate is tested
+// against every leaf of the list, passed or not, so the k_hit_scores shortcut (need >= n: the score is n) only holds in `both`
+// mode, where every mate that is not all-hit passed every listed leaf (and an all-hit mate with need >= n has no k-mers).
+__global__ void __launch_bounds__(256) k_pair_scores(HashParams hp, const uint8_t *__restrict__ seq, const uint64_t *__restrict__ off, uint64_t n_frag,
+                                                     float threshold, int both, const unsigned long long *__restrict__ frag_off,
+                                                     const uint32_t *__restrict__ frag_leaves, const uint32_t *__restrict__ col_row,
+                                                     const uint64_t *__restrict__ bits, uint64_t n_words, uint32_t *__restrict__ scores) {
+    __shared__ BlockLds lds;
+    fill_complement(lds.comp);
+    __syncthreads();
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    for (uint64_t f = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; f < n_frag; f += (uint64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const uint64_t h0 = frag_off[f], h1 = frag_off[f + 1];
+        if (h0 == h1) continue;
+        for (uint64_t c0 = h0; c0 < h1; c0 += 64) {
+            const uint32_t nh = (uint32_t)min<uint64_t>(h1 - c0, 64);
+            const uint32_t my_row = lane < nh ? col_row[frag_leaves[c0 + lane]] : 0u;
+            uint32_t acc = 0;
+            for (uint64_t r = 2 * f; r < 2 * f + 2; ++r) {
+                const uint64_t o = off[r], len = off[r + 1] - o;
+                const uint64_t n = len >= hp.k ? len - hp.k + 1 : 0;
+                if (both && need_kmers(threshold, n) >= n) acc += (uint32_t)n;
+                else acc += score_chunk(lds, wave, lane, hp, seq + o, n, my_row, nh, bits, n_words);
+            }
+            if (lane < nh) scores[c0 + lane] = acc;
+        }
+    }
+}
+void launch_pair_combine(const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint8_t *d_allhit, uint64_t n_frag, bool both,
+                         uint32_t n_leaves, bool list_all, uint32_t *d_cnt, uint32_t *d_long, unsigned long long *d_misc, unsigned long long *d_sums,
+                         unsigned long long *d_frag_off, hipStream_t st) {
+    if (!n_frag) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_frag + 255) / 256, 4096);
+    const uint32_t wblocks = (uint32_t)std::min<uint64_t>((n_frag + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 1024);
+    hipLaunchKernelGGL(k_pair_count, dim3(blocks), dim3(256), 0, st, d_hit_off, d_hit_leaves, d_allhit, n_frag, both ? 1 : 0, n_leaves,
+                       list_all ? 1 : 0, d_cnt, d_long, d_misc);
+    hipLaunchKernelGGL(k_pair_long<false>, dim3(wblocks), dim3(256), 0, st, d_hit_off, d_hit_leaves, d_allhit, both ? 1 : 0, n_leaves, d_long,
+                       d_misc, d_cnt, nullptr, nullptr);
+    const uint32_t n_blocks = (uint32_t)((n_frag + SCAN_ITEMS - 1) / SCAN_ITEMS);
+    hipLaunchKernelGGL(k_scan_sums, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n_frag, d_sums);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_sums, n_blocks);
+    hipLaunchKernelGGL(k_scan_apply, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n_frag, d_sums, d_frag_off);
+}
+void launch_pair_fill(const unsigned long long *d_hit_off, const uint32_t *d_hit_leaves, const uint8_t *d_allhit, uint64_t n_frag, bool both,
+                      uint32_t n_leaves, const uint32_t *d_long, const unsigned long long *d_misc, const unsigned long long *d_frag_off,
+                      uint32_t *d_frag_leaves, hipStream_t st) {
+    if (!n_frag) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_frag + 255) / 256, 4096);
+    const uint32_t wblocks = (uint32_t)std::min<uint64_t>((n_frag + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 1024);
+    hipLaunchKernelGGL(k_pair_fill, dim3(blocks), dim3(256), 0, st, d_hit_off, d_hit_leaves, d_allhit, n_frag, both ? 1 : 0, d_frag_off, d_frag_leaves);
+    hipLaunchKernelGGL(k_pair_long<true>, dim3(wblocks), dim3(256), 0, st, d_hit_off, d_hit_leaves, d_allhit, both ? 1 : 0, n_leaves, d_long,
+                       d_misc, nullptr, d_frag_off, d_frag_leaves);
+}
+void launch_pair_leaf_counts(const uint32_t *d_frag_leaves, const unsigned long long *d_total, const unsigned long long *d_misc, uint32_t n_leaves,
+                             uint64_t max_entries, unsigned long long *d_counts, hipStream_t st) {
+    if (!n_leaves) return;
+    // LDS: a block flushes up to n_leaves atomics, so it takes at least 8 entries per leaf (the flush stays <= 1/8 of the
+    // entries); global atomics: 4096 entries per block
+    const uint64_t per_block = n_leaves <= PAIR_HIST_LDS ? std::max<uint64_t>(4096, 8ull * n_leaves) : 4096;
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((max_entries + per_block - 1) / per_block, 1024));
+    if (n_leaves <= PAIR_HIST_LDS)
+        hipLaunchKernelGGL(k_pair_hist<true>, dim3(blocks), dim3(256), 0, st, d_frag_leaves, d_total, d_misc, n_leaves, d_counts);
+    else
+        hipLaunchKernelGGL(k_pair_hist<false>, dim3(blocks), dim3(256), 0, st, d_frag_leaves, d_total, d_misc, n_leaves, d_counts);
+}
+void launch_pair_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_frag, float threshold, bool both,
+                        const unsigned long long *d_frag_off, const uint32_t *d_frag_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
+                        uint64_t n_words, uint32_t *d_scores, hipStream_t st) {
+    if (!n_frag) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_frag + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 8192);
+    hipLaunchKernelGGL(k_pair_scores, dim3(blocks), dim3(256), 0, st, hp, d_seq, d_off, n_frag, threshold, both ? 1 : 0, d_frag_off, d_frag_leaves,
                        d_col_row, d_bits, n_words, d_scores);
 }
 

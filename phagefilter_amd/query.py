@@ -205,17 +205,20 @@ class BloomTree:
 
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
-                     want_scores: bool = False):
+                     want_scores: bool = False, paired: bool = False, pair_mode: str = "either"):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
-        (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores)."""
+        (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
+        `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
+        (pair_mode "either") or the intersection ("both") of the mates' sets."""
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         hits = _ffi.Hits()
-        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0)
+        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode)
         _ffi.check(_ffi.lib().pfq_query_batch(self._h, seq.ctypes.data, off.ctypes.data, n, threshold, flags, C.byref(hits)))
         if not want_hits:
             return None
+        n = int(hits.n_reads)
         offs = np.ctypeslib.as_array(hits.offsets, shape=(n + 1,)).copy() if n else np.zeros(1, dtype=np.uint64)
         total = int(offs[-1])
         leaves = np.ctypeslib.as_array(hits.leaves, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
@@ -232,25 +235,37 @@ class BloomTree:
         return np.ctypeslib.as_array(p, shape=(n.value,)) if n.value else np.zeros(0, dtype=np.uint32)
 
     def query_device(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float,
-                     stream: int = 0) -> None:
+                     stream: int = 0, paired: bool = False, pair_mode: str = "either") -> None:
         """One block already resident in HBM (raw device pointers), asynchronous on `stream`."""
-        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, 0,
-                                                     stream, None))
+        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold,
+                                                     _pair_flags(paired, pair_mode), stream, None))
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
-                          want_scores: bool = False):
+                          want_scores: bool = False, paired: bool = False, pair_mode: str = "either"):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
-        (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree)."""
+        (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
+        `paired`: one row per fragment (reads 2i, 2i + 1), as in query_packed."""
         hits = _ffi.Hits()
-        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0)
+        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode)
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
+        n_reads = int(hits.n_reads)
         offs = np.ctypeslib.as_array(hits.offsets, shape=(n_reads + 1,)) if n_reads else np.zeros(1, dtype=np.uint64)
         total = int(offs[-1])
         leaves = np.ctypeslib.as_array(hits.leaves, shape=(total,)) if total else np.zeros(0, dtype=np.uint32)
         if not want_scores:
             return offs, leaves
         return offs, leaves, self.last_hit_scores()
+
+    def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
+                    mode: str = "either") -> List[List[int]]:
+        """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
+        (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments."""
+        if len(r1) != len(r2):
+            raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
+        seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
+        offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, paired=True, pair_mode=mode)
+        return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
 
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
@@ -265,6 +280,14 @@ class BloomTree:
     def import_counts_delta(self, d_src: int, stream: int = 0) -> None:
         """counters = base + d_src (the sum of the ranks' deltas); that becomes the new base."""
         _ffi.check(_ffi.lib().pfq_leaf_counts_import_delta(self._h, d_src, stream))
+
+
+def _pair_flags(paired: bool, pair_mode: str) -> int:
+    if pair_mode not in ("either", "both"):
+        raise ValueError(f"pair_mode must be 'either' or 'both', not {pair_mode!r}")
+    if not paired:
+        return 0
+    return _ffi.PAIRED | (_ffi.PAIR_BOTH if pair_mode == "both" else 0)
 
 
 def query_batch(bloom_tree: BloomTree, read_set: Sequence[bytes], threshold: float,
