@@ -232,7 +232,8 @@ typedef struct pfq_stats {
     uint32_t leaf_groups;       /* groups of leaf columns of the sliced matrix (1 for trees of up to 2048 columns) */
     uint32_t coarse_cols;       /* columns (internal nodes) of the coarse level this call used; 0: flat frontier */
     uint32_t coarse_probes;     /* probes per k-mer its screens looked at */
-    uint32_t pad_;
+    uint32_t tile_bin_build;    /* build of k_tile_bin the LDS-tile passes of this call ran: waves << 16 | bin capacity
+                                 * (e.g. 16 << 16 | 512, 8 << 16 | 128); 0: no pass ran */
     uint64_t group_reads;       /* (read, leaf group) combinations the coarse level let through to the leaf level */
 } pfq_stats;
 int pfq_last_stats(pfq_tree *tree, pfq_stats *out);

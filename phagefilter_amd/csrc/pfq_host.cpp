@@ -219,6 +219,7 @@ struct pfq_tree {
     uint32_t last_block_mode = 0;
     DevBuf<uint32_t> d_round_k0, d_n_rounds, d_pair_kpos;  // thresholds < 1: LDS-tile passes with k-mer entries
     uint32_t last_tile_mode = 0, last_passes = 1;
+    uint32_t last_tile_bin = 0;        // build of k_tile_bin the last call launched (waves << 16 | bin capacity); 0: no pass
     DevBuf<uint2> d_hit_pairs, d_pairs, d_sorted;
     DevBuf<uint32_t> d_bucket, d_fail;  // bucket: cnt[n], off[n+1], cur[n]
     DevBuf<unsigned int> d_queue;
@@ -966,6 +967,7 @@ struct QueryRun {
             }
         }
         t.last_path = bucketed ? 1 : 0;
+        if (!bucketed) t.last_tile_mode = t.last_tile_bin = 0;  // (the direct path runs no tile pass)
         hit_cap = t.d_hit_pairs.n;
         return PFQ_OK;
     }
@@ -1317,6 +1319,7 @@ struct QueryRun {
         uint64_t tile_budget = std::min<uint64_t>(64ull << 30, (uint64_t)((double)(mem_free + t.d_entries.bytes()) * 0.8));
         if (kn.tile_gb >= 0) tile_budget = (uint64_t)kn.tile_gb << 30;
         t.last_tile_mode = 0;
+        t.last_tile_bin = 0;
         if (tile_mode) {
             // every read may survive with one candidate: (bases - (k-1) per read) * hashes * 1.125 + slack per bucket
             const uint64_t max_chunks = nc + ((t.leaf_cap + t.guard_cap) >> chunk_log2) + 2;
@@ -1404,7 +1407,7 @@ struct QueryRun {
                 for (uint64_t p = 0; p < n_passes; ++p) {
                     ta.pass = (uint32_t)p;
                     ta.bin_queue = t.d_binq.p + p;
-                    pfq::launch_tile_bin(ta, bin_blocks, st);
+                    t.last_tile_bin = pfq::launch_tile_bin(ta, bin_blocks, st);
                     if (p == 0 && ev) HIP_TRY(hipEventRecord(ev[3], st));
                     pfq::launch_tile_test(ta, test_blocks, st);
                 }
@@ -2793,6 +2796,7 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
     out->path = t.last_path;
     out->n_slices = t.last_slices;
     out->tile_mode = t.last_tile_mode;
+    out->tile_bin_build = t.last_tile_bin;
     if (t.d_cursors.p) {
         unsigned long long c[4];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));

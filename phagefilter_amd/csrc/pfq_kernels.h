@@ -263,7 +263,8 @@ struct TileArgs {
     uint32_t *pair_kpos;         // [sorted pair] position of the pair's first k-mer in its chunk
 };
 void launch_tile_plan(const TileArgs &a, hipStream_t st);
-void launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st);
+// returns the build it launched: BIN_WAVES << 16 | BIN_CAP of k_tile_bin (chosen from n_tiles by its LDS need, and bin_shape)
+uint32_t launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st);
 void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st);
 
 // launches (all asynchronous on `st`)

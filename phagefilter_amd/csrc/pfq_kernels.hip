@@ -2162,23 +2162,30 @@ static void launch_tile_bin_shape(const TileArgs &a, int blocks, size_t lds, hip
     else if (a.blocks) hipLaunchKernelGGL((k_tile_bin<W, CAP, 2>), dim3(blocks), dim3(W * 64), lds, st, a);
     else hipLaunchKernelGGL((k_tile_bin<W, CAP, 0>), dim3(blocks), dim3(W * 64), lds, st, a);
 }
-void launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st) {
+uint32_t launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st) {
     const size_t nt = (a.n_tiles + 63u) & ~63u;
     auto lds_of = [&](size_t cap) { return (2 * nt + 64 + (size_t)a.n_tiles * (cap + 4)) * 4; };
     if (a.bin_shape == 3 && lds_of(256) <= 74 * 1024) {  // experiment: two 8-wave blocks per CU
         launch_tile_bin_shape<8, 256>(a, blocks, lds_of(256), st);
+        return 8u << 16 | 256u;
     } else if (lds_of(2048) <= 148 * 1024 && a.bin_shape == 0) {  // few tiles (small filters): deeper bins, longer rounds
         launch_tile_bin_shape<16, 2048>(a, (blocks + 1) / 2, lds_of(2048), st);
+        return 16u << 16 | 2048u;
     } else if (lds_of(1024) <= 148 * 1024 && a.bin_shape == 0) {
         launch_tile_bin_shape<16, 1024>(a, (blocks + 1) / 2, lds_of(1024), st);
+        return 16u << 16 | 1024u;
     } else if (lds_of(512) <= 148 * 1024 && a.bin_shape == 0) {
         launch_tile_bin_shape<16, 512>(a, (blocks + 1) / 2, lds_of(512), st);
+        return 16u << 16 | 512u;
     } else if (lds_of(256) <= 148 * 1024 && a.bin_shape != 1) {
         launch_tile_bin_shape<16, 256>(a, (blocks + 1) / 2, lds_of(256), st);
+        return 16u << 16 | 256u;
     } else if (lds_of(128) <= 148 * 1024) {
         launch_tile_bin_shape<8, 128>(a, blocks, lds_of(128), st);
+        return 8u << 16 | 128u;
     } else {  // several hundred tiles (block mode of large filters): shallow bins
         launch_tile_bin_shape<16, 60>(a, (blocks + 1) / 2, lds_of(60), st);
+        return 16u << 16 | 60u;
     }
 }
 
