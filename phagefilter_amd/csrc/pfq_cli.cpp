@@ -57,6 +57,15 @@ inline void copy_upper(char *dst, const uint8_t *src, size_t n) {
     }
 }
 
+// fn(0), .., fn(n - 1) side by side: fn(0) on the calling thread, the others on threads of their own
+template <class F>
+void fan_out(size_t n, const F &fn) {
+    std::vector<std::thread> th;
+    for (size_t i = 1; i < n; ++i) th.emplace_back(std::cref(fn), i);
+    fn(0);
+    for (auto &t : th) t.join();
+}
+
 [[noreturn]] void die(const std::string &msg) {  // the reference panics: message on stderr, exit code 101
     fprintf(stderr, "phage_filter: %s\n", msg.c_str());
     exit(101);
@@ -349,10 +358,7 @@ struct Batch {
             }
         };
         const size_t T = cnt >= 16384 ? 4 : 1;
-        std::vector<std::thread> ts;
-        for (size_t t = 1; t < T; ++t) ts.emplace_back(part, cnt * t / T, cnt * (t + 1) / T);
-        part(0, cnt / T);
-        for (auto &t : ts) t.join();
+        fan_out(T, [&](size_t t) { part(cnt * t / T, cnt * (t + 1) / T); });
     }
 };
 
@@ -663,16 +669,19 @@ struct ReadQueue {
     }
     // segments the pool takes back (filtering: batches in flight hold their segments)
     size_t pool_cap() const { return lookahead + 4 + (keep ? 48 : 0); }
+    // a consumed segment back to the pool (one that ends in malformed input is not reused)
     void recycle(Segment *s) {
+        if (!s->err.empty()) {
+            delete s;
+            return;
+        }
         std::lock_guard<std::mutex> lk(mu);
         if (pool.size() < pool_cap()) pool.push_back(s);
         else delete s;
     }
-    // one holder less; the last one hands the segment back (a segment that ends in malformed input is not reused)
+    // one holder less; the last one hands the segment back
     void release(Segment *s) {
-        if (--s->refs > 0) return;
-        if (!s->err.empty()) delete s;
-        else recycle(s);
+        if (--s->refs == 0) recycle(s);
     }
     void release_held(Batch &b) {
         for (Segment *s : b.held) release(s);
@@ -991,192 +1000,313 @@ int device_from_env() {
 // ---------------------------------------------------------------------------------------------------------------
 // query (main.rs:249-376)
 // ---------------------------------------------------------------------------------------------------------------
-int cmd_query(int argc, char **argv) {
-    std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
-                             {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
-                             {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
-                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
-                             {"interleaved", 0, false}, {"pair-mode", 0, true}};
-    Args a = parse(argc, argv, 2, opts);
-    const std::string reads = req(a, "reads"), out = req(a, "out"), db = req(a, "db-path");
-    const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
-    (void)to_u64(opt(a, "cache-size", "10"), "cache-size");  // LRU of .bf files: the whole tree is resident in HBM
-    const uint64_t block = to_u64(opt(a, "block-size-reads", "100"), "block-size-reads");
-    const float threshold = to_f32(opt(a, "filter-threshold", "1.0"), "filter-threshold");
-    const bool pos = a.flags.count("pos-filter") != 0, neg = a.flags.count("neg-filter") != 0;
-    const bool filtering = pos || neg;
-    // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
-    const bool scores = a.flags.count("scores") != 0;
-    const bool per_read = filtering || scores;  // the per-read hit lists are needed
-    const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
-    // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
-    // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
-    const bool interleaved = a.flags.count("interleaved") != 0, has_reads2 = a.val.count("reads2") != 0;
-    if (interleaved && has_reads2) die("error: the argument '--reads2 <READS2>' cannot be used with '--interleaved'");
-    const bool paired = interleaved || has_reads2;
-    const std::string pair_mode = opt(a, "pair-mode", "either");
-    if (pair_mode != "either" && pair_mode != "both")
-        die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
-    if (a.val.count("pair-mode") && !paired) die("error: '--pair-mode' needs '--reads2' or '--interleaved'");
-
-    // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
-    // the per-genome counts are combined by one RCCL all-reduce at the end.  The reference has one rayon pool instead
-    // (main.rs:269-272); results do not depend on how the reads are dealt.
-    std::vector<int> devices;
-    {
-        std::string spec = opt(a, "devices", getenv("PFQ_DEVICES") ? getenv("PFQ_DEVICES") : "");
-        if (spec == "all") {
-            int n = 0;
-            check(pfq_device_count(&n));
-            for (int i = 0; i < n; ++i) devices.push_back(i);
-        } else if (!spec.empty()) {
-            size_t p0 = 0;
-            while (p0 <= spec.size()) {
-                size_t p1 = spec.find(',', p0);
-                if (p1 == std::string::npos) p1 = spec.size();
-                devices.push_back((int)to_u64(spec.substr(p0, p1 - p0), "devices"));
-                p0 = p1 + 1;
-            }
+// An error on a worker thread ends the process at once, WITHOUT exit(): exit() would run the atexit handlers and static
+// destructors (the HIP runtime's among them) while the other replicas' threads, the parser and the formatters are still
+// inside HIP calls or writing.  Same message and status as die() (the reference panics: status 101).
+[[noreturn]] void fail_from_thread(const char *what) {
+    fprintf(stderr, "phage_filter: libpfq: %s\n", what);
+    fflush(stderr);
+    _exit(101);
+}
+void write_at(int fd, const char *buf, size_t len, uint64_t at) {
+    for (size_t done = 0; done < len;) {
+        ssize_t n = pwrite(fd, buf + done, len - done, (off_t)(at + done));
+        if (n < 0) {
+            fprintf(stderr, "phage_filter: write error: %s\n", strerror(errno));
+            _exit(101);  // (called from writer threads: see fail_from_thread)
         }
-        if (devices.empty()) devices.push_back(device_from_env());
+        done += (size_t)n;
     }
-    const size_t n_dev = devices.size();
-    // --shard-depth D: the database is split into the subtree shards of its depth-E frontier (pfq_tree_open_subtree), E = D,
-    // or the search depth when that is smaller (a shard cut below the pruning depth would put one pruned leaf into several
-    // shards).  Shard i lives on devices[i % N] and classifies EVERY read; the shards' leaf ranges are disjoint and follow
-    // the whole tree's leaf order, so their hits and counts are concatenated in shard order.  Each shard has its own host
-    // thread.  Checked before any device is touched; at least one shard per device (no replication of shards).
-    const bool sharded = a.val.count("shard-depth") != 0;
-    uint64_t shard_depth = 0;
-    size_t n_trees = n_dev;
-    if (sharded) {
-        shard_depth = to_u64(a.val.at("shard-depth"), "shard-depth");
-        if (a.val.count("search-depth")) shard_depth = std::min(shard_depth, to_u64(a.val.at("search-depth"), "search-depth"));
-        uint64_t n_shards = 0;
-        check(pfq_db_shard_count(db.c_str(), shard_depth, &n_shards));
-        if (n_shards < n_dev)
-            die("--shard-depth: the database has " + std::to_string(n_shards) + " subtree shards at depth " + std::to_string(shard_depth) +
-                ", fewer than the " + std::to_string(n_dev) + " devices listed (every device needs a shard of its own)");
-        n_trees = (size_t)n_shards;
-    }
-    std::vector<pfq_tree *> trees(n_trees, nullptr);
-    {   // BloomTree::load per replica (or shard), side by side
-        std::vector<std::string> errs(n_trees);
-        std::vector<std::thread> th;
-        auto open_one = [&](size_t i) {
-            const int rc = sharded ? pfq_tree_open_subtree(db.c_str(), devices[i % n_dev], shard_depth, i, &trees[i])
-                                   : pfq_tree_open(db.c_str(), devices[i], &trees[i]);
+}
+
+// The database as a query serves it: one replica per listed device, or (--shard-depth) the subtree shards of its depth-E
+// frontier, shard i on devices[i % N].  Shard i's leaves are [leaf_base[i], leaf_base[i + 1]) of the whole tree's
+// leaf_names (after pruning); the shards' leaf ranges are disjoint and follow the whole tree's leaf order.
+struct ServedDb {
+    std::vector<int> devices;
+    bool sharded;
+    std::vector<pfq_tree *> trees;
+    std::vector<std::string> leaf_names;
+    std::vector<uint64_t> leaf_base{0};
+
+    // BloomTree::load per replica (or shard), side by side.  At least one shard per device (no replication of shards),
+    // checked before any device is touched.
+    ServedDb(const std::string &path, const std::vector<int> &devs, bool shards, uint64_t shard_depth) : devices(devs), sharded(shards) {
+        size_t n = devices.size();
+        if (sharded) {
+            uint64_t n_shards = 0;
+            check(pfq_db_shard_count(path.c_str(), shard_depth, &n_shards));
+            if (n_shards < devices.size())
+                die("--shard-depth: the database has " + std::to_string(n_shards) + " subtree shards at depth " + std::to_string(shard_depth) +
+                    ", fewer than the " + std::to_string(devices.size()) + " devices listed (every device needs a shard of its own)");
+            n = (size_t)n_shards;
+        }
+        trees.assign(n, nullptr);
+        std::vector<std::string> errs(n);
+        fan_out(n, [&](size_t i) {
+            const int rc = sharded ? pfq_tree_open_subtree(path.c_str(), devices[i % devices.size()], shard_depth, i, &trees[i])
+                                   : pfq_tree_open(path.c_str(), devices[i], &trees[i]);
             if (rc != PFQ_OK) errs[i] = std::string("libpfq: ") + pfq_last_error();
-        };
-        for (size_t i = 1; i < n_trees; ++i) th.emplace_back(open_one, i);
-        open_one(0);
-        for (auto &t : th) t.join();
+        });
         for (auto &e : errs)
             if (!e.empty()) die(e);
     }
-    pfq_tree *tree = trees[0];
-    printf("Querying reads...\n");
-    printf("Filtering settings: positive=%s; negative=%s\n", pos ? "true" : "false", neg ? "true" : "false");
-    if (a.val.count("search-depth")) {
-        uint64_t depth = to_u64(a.val.at("search-depth"), "search-depth");
-        if (!filtering) printf("If using a search depth, use a filtering flag (--pos-filter or --neg-filter, or both!)\n");
-        printf("Search depth settings: %llu\n", (unsigned long long)depth);
+    void prune(uint64_t depth) {
         for (pfq_tree *t : trees) check(pfq_tree_prune(t, depth));
     }
-    ReadQueue rq(reads, ov);
-    std::unique_ptr<ReadQueue> rq2;
-    if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
-    // Page-locking costs ~1.7 s per GB here (hipHostMalloc), the pageable copy ~0.1 s per GB: pinned buffers only
-    // pay off once every pooled buffer has been reused a few dozen times (inputs of >~ 10^9 reads).  Opt-in.
-    g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
-    // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
-    // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    if (block != 0) rq.start(per_read || paired, threads);  // (paired: the mates' ids are compared)
-    if (block != 0 && rq2) rq2->start(true, threads);
-
-    // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
-    struct stat st;
-    if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
-    mkdir(out.c_str(), 0777);
-    const char *ext = rq.peek_format() == Fmt::Fastq ? "fq" : "fa";
-    int pos_fd = -1, neg_fd = -1;
-    uint64_t pos_size = 0, neg_size = 0;  // bytes written so far (formatters write their parts at computed offsets)
-    // --reads2: the mates of R2 go to POS_FILTERING_2 / NEG_FILTERING_2, those of R1 to the files named _1
-    const std::string mate1 = has_reads2 ? "_1." : ".";
-    int pos2_fd = -1, neg2_fd = -1;
-    uint64_t pos2_size = 0, neg2_size = 0;
-    if (pos && (pos_fd = open((out + "/POS_FILTERING" + mate1 + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
-        die("cannot create POS_FILTERING in " + out);
-    if (neg && (neg_fd = open((out + "/NEG_FILTERING" + mate1 + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
-        die("cannot create NEG_FILTERING in " + out);
-    if (has_reads2 && pos && (pos2_fd = open((out + "/POS_FILTERING_2." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
-        die("cannot create POS_FILTERING_2 in " + out);
-    if (has_reads2 && neg && (neg2_fd = open((out + "/NEG_FILTERING_2." + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
-        die("cannot create NEG_FILTERING_2 in " + out);
-    FILE *scores_f = nullptr;
-    uint64_t kmer_size = 0;
-    if (scores) {
-        if (!(scores_f = fopen((out + "/READ_SCORES.tsv").c_str(), "wb"))) die("cannot create READ_SCORES.tsv in " + out);
-        fputs("#read_id\tkmers\tgenome\tmatched_kmers\n", scores_f);
-        pfq_info info{};
-        check(pfq_tree_info(tree, &info));
-        kmer_size = info.kmer_size;
-    }
-    auto write_at = [](int fd, const char *buf, size_t len, uint64_t at) {
-        for (size_t done = 0; done < len;) {
-            ssize_t n = pwrite(fd, buf + done, len - done, (off_t)(at + done));
-            if (n < 0) {
-                fprintf(stderr, "phage_filter: write error: %s\n", strerror(errno));
-                _exit(101);  // (called from writer threads: see fail_from_thread)
-            }
-            done += (size_t)n;
+    void load_leaf_names() {
+        for (size_t i = 0; i < (sharded ? trees.size() : 1); ++i) {
+            const char *const *tax = nullptr;
+            uint64_t n_leaves = 0;
+            check(pfq_leaf_counts(trees[i], &tax, nullptr, &n_leaves));
+            leaf_names.insert(leaf_names.end(), tax, tax + n_leaves);
+            leaf_base.push_back(leaf_base.back() + n_leaves);
         }
-    };
-
-    // leaf names in the whole tree's order; shard i's leaves are [leaf_base[i], leaf_base[i + 1]) of it (after pruning)
-    std::vector<std::string> leaf_names;
-    std::vector<uint64_t> leaf_base(1, 0);
-    for (size_t i = 0; i < (sharded ? n_trees : 1); ++i) {
-        const char *const *tax = nullptr;
-        uint64_t n_leaves = 0;
-        check(pfq_leaf_counts(trees[i], &tax, nullptr, &n_leaves));
-        leaf_names.insert(leaf_names.end(), tax, tax + n_leaves);
-        leaf_base.push_back(leaf_base.back() + n_leaves);
+        if (sharded)
+            for (size_t i = 0; i < trees.size(); ++i)
+                fprintf(stderr, "shard %zu/%zu: leaves [%llu, %llu) of %llu on device %d\n", i, trees.size(), (unsigned long long)leaf_base[i],
+                        (unsigned long long)leaf_base[i + 1], (unsigned long long)leaf_base.back(), devices[i % devices.size()]);
     }
-    if (sharded)
-        for (size_t i = 0; i < n_trees; ++i)
-            fprintf(stderr, "shard %zu/%zu: leaves [%llu, %llu) of %llu on device %d\n", i, n_trees, (unsigned long long)leaf_base[i],
-                    (unsigned long long)leaf_base[i + 1], (unsigned long long)leaf_base.back(), devices[i % n_dev]);
+    void save_counts(const std::string &csv) {
+        if (!sharded) {
+            // per-genome counts of all replicas: one RCCL all-reduce (every replica then holds the totals); replica 0 writes the file
+            if (trees.size() > 1) check(pfq_trees_allreduce_counts(trees.data(), (uint32_t)trees.size()));
+            check(pfq_save_leaf_counts(trees[0], csv.c_str()));
+            return;
+        }
+        // the shards' counts one after the other, in pfq_save_leaf_counts' format: the leaf ranges are disjoint, so every
+        // leaf (and every count stored in tree.bin) appears once — nothing to reduce
+        FILE *f = fopen(csv.c_str(), "wb");
+        if (!f) die("cannot create " + csv + ": " + strerror(errno));
+        for (pfq_tree *t : trees) {
+            const char *const *tax = nullptr;
+            const uint64_t *cnt = nullptr;
+            uint64_t n_leaves = 0;
+            check(pfq_leaf_counts(t, &tax, &cnt, &n_leaves));
+            for (uint64_t j = 0; j < n_leaves; ++j)
+                if (cnt[j] > 0) fprintf(f, "%s,%llu\n", tax[j], (unsigned long long)cnt[j]);  // query.rs:177-182
+        }
+        if (fclose(f) != 0) die("short write to " + csv);
+    }
+    void close() {
+        for (pfq_tree *t : trees) pfq_tree_close(t);
+    }
+};
 
-    const uint64_t t_loop0 = ReadQueue::now_ns();
+// A POS/NEG file and the bytes written to it so far (the formatters' parts are written at computed offsets)
+struct OutFile {
+    int fd = -1;
+    uint64_t size = 0;
+    void append(const char *p, size_t len) {
+        if (fd < 0 || !len) return;
+        write_at(fd, p, len, size);
+        size += len;
+    }
+};
+struct Outputs {
+    OutFile pos, neg, pos2, neg2;  // --reads2: the mates of R2 go to POS_FILTERING_2 / NEG_FILTERING_2, those of R1 to _1
+    FILE *scores = nullptr;        // --scores: READ_SCORES.tsv
+    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores) {
+        auto create = [&](OutFile &f, const std::string &name, const char *suffix) {
+            if ((f.fd = open((dir + "/" + name + suffix + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+                die("cannot create " + name + " in " + dir);
+        };
+        const char *mate1 = has_reads2 ? "_1." : ".";
+        if (want_pos) create(pos, "POS_FILTERING", mate1);
+        if (want_neg) create(neg, "NEG_FILTERING", mate1);
+        if (has_reads2 && want_pos) create(pos2, "POS_FILTERING_2", ".");
+        if (has_reads2 && want_neg) create(neg2, "NEG_FILTERING_2", ".");
+        if (want_scores) {
+            if (!(scores = fopen((dir + "/READ_SCORES.tsv").c_str(), "wb"))) die("cannot create READ_SCORES.tsv in " + dir);
+            fputs("#read_id\tkmers\tgenome\tmatched_kmers\n", scores);
+        }
+    }
+    void close() {
+        for (OutFile *f : {&pos, &neg, &pos2, &neg2})
+            if (f->fd >= 0) ::close(f->fd);
+        if (scores && fclose(scores) != 0) die("short write to READ_SCORES.tsv");
+    }
+};
+
+// Hit lists: unit u (a read, or with PFQ_PAIRED a fragment) hits leaves[off[u], off[u + 1]), ascending; --scores: the
+// matched k-mers, aligned with leaves
+struct Hits {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> leaves, scores;
+    std::vector<uint64_t> call_off;  // the call's read offsets, when its range does not start at the batch's first read
+};
+// Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
+// scores) are copied out of the library's buffers, which the next call on the tree reuses, into h.
+void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h) {
+    const bool want = (flags & PFQ_WANT_HITS) != 0;
+    const uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
+    if (want) {
+        h.off.assign(units + 1, 0);
+        h.leaves.clear();
+        h.scores.clear();
+    }
+    if (r1 == r0) return;
+    const uint64_t *off = b.off.data();
+    if (r0) {
+        h.call_off.resize(r1 - r0 + 1);
+        for (uint64_t r = r0; r <= r1; ++r) h.call_off[r - r0] = b.off[r] - b.off[r0];
+        off = h.call_off.data();
+    }
+    pfq_hits hits{};
+    if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, threshold, flags, want ? &hits : nullptr) != PFQ_OK)
+        fail_from_thread(pfq_last_error());
+    if (!want) return;
+    memcpy(h.off.data(), hits.offsets, (units + 1) * sizeof(uint64_t));
+    h.leaves.assign(hits.leaves, hits.leaves + hits.offsets[units]);
+    if (flags & PFQ_WANT_SCORES) {
+        const uint32_t *sc = nullptr;
+        uint64_t n_sc = 0;
+        if (pfq_last_hit_scores(tree, &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
+        h.scores.assign(sc, sc + n_sc);
+    }
+}
+// The trees' hit lists of n units in the whole tree's leaf order.  Part i covers units [n i / P, n (i + 1) / P) for a
+// replica (the shares follow one another) and all of them for a shard (per unit, the shards' lists in shard order, each
+// offset by the shard's first leaf).  A single part is swapped into `out`.
+void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &out) {
+    const size_t P = parts.size();
+    if (P == 1) {
+        std::swap(out, parts[0]);
+        return;
+    }
+    uint64_t total = 0;
+    bool with_scores = false;
+    for (const Hits &h : parts) {
+        total += h.leaves.size();
+        with_scores |= !h.scores.empty();
+    }
+    out.off.assign(n + 1, 0);
+    out.leaves.resize(total);
+    out.scores.resize(with_scores ? total : 0);
+    uint64_t at = 0;
+    for (uint64_t u = 0; u < n; ++u) {
+        for (size_t i = 0; i < P; ++i) {
+            const uint64_t u0 = db.sharded ? 0 : n * i / P, u1 = db.sharded ? n : n * (i + 1) / P;
+            if (u < u0 || u >= u1) continue;
+            const Hits &h = parts[i];
+            const uint64_t j0 = h.off[u - u0], j1 = h.off[u - u0 + 1];
+            const uint32_t base = db.sharded ? (uint32_t)db.leaf_base[i] : 0u;
+            if (with_scores) std::copy(h.scores.begin() + j0, h.scores.begin() + j1, out.scores.begin() + at);
+            for (uint64_t j = j0; j < j1; ++j) out.leaves[at++] = h.leaves[j] + base;
+        }
+        out.off[u + 1] = at;
+    }
+}
+
+// Output buffers of the formatters: grown with realloc (no zero fill), kept from batch to batch.
+struct OutBuf {
+    char *p = nullptr;
+    size_t n = 0, cap = 0;
+    ~OutBuf() { free(p); }
+    char *room(size_t want) {
+        if (n + want > cap) {
+            cap = std::max(n + want, cap + cap / 2 + (1u << 20));
+            p = (char *)realloc(p, cap);
+            if (!p) die("out of memory (output buffer)");
+        }
+        return p + n;
+    }
+    void put(const char *src, size_t len) {
+        memcpy(room(len), src, len);
+        n += len;
+    }
+    void put(char c) {
+        *room(1) = c;
+        ++n;
+    }
+};
+// write_record (main.rs:394-404) of read r: '@' / '>' + id; for a mapped read get_ext_id's " |g1,g2" with the genomes
+// [l0, l1) (set order unspecified in the reference; leaf order here); the sequence, upper-cased (main.rs:347-349); FASTQ:
+// '+' and the quality.  No allocation per record.
+void put_record(OutBuf &o, const Batch &b, uint64_t r, const uint32_t *l0, const uint32_t *l1, const std::vector<std::string> &names) {
+    const std::string_view id = b.id(r);
+    const uint64_t len = b.off[r + 1] - b.off[r];
+    const bool fq = b.has_qual[r] != 0;
+    {
+        char *dst = o.room(id.size() + 3);
+        dst[0] = fq ? '@' : '>';
+        memcpy(dst + 1, id.data(), id.size());
+        o.n += id.size() + 1;
+    }
+    if (l0 != l1) {
+        o.put(" |", 2);
+        for (const uint32_t *l = l0; l < l1; ++l) {
+            if (l != l0) o.put(',');
+            o.put(names[*l].data(), names[*l].size());
+        }
+    }
+    const std::string_view q = fq ? b.quality(r) : std::string_view();
+    char *dst = o.room(len + q.size() + 5);
+    *dst++ = '\n';
+    copy_upper(dst, b.seq.data() + b.off[r], len);
+    dst += len;
+    *dst++ = '\n';
+    size_t wrote = len + 2;
+    if (fq) {
+        dst[0] = '+';
+        dst[1] = '\n';
+        memcpy(dst + 2, q.data(), q.size());
+        dst[2 + q.size()] = '\n';
+        wrote += q.size() + 3;
+    }
+    o.n += wrote;
+}
+uint64_t n_kmers(uint64_t len, uint64_t k) { return len >= k ? len - k + 1 : 0; }
+// READ_SCORES.tsv lines of a record (or fragment) with hits, "id\tkmers\tgenome\tmatched": its n genomes by matched
+// k-mers, descending (ties in leaf order)
+void put_scores(std::string &o, std::string_view id, uint64_t kmers, const uint32_t *leaves, const uint32_t *sc, uint64_t n,
+                const std::vector<std::string> &names, std::vector<uint64_t> &order) {
+    order.resize(n);
+    for (uint64_t j = 0; j < n; ++j) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return sc[x] > sc[y]; });
+    char ks[32], num[32];
+    const int nk = snprintf(ks, sizeof ks, "\t%llu\t", (unsigned long long)kmers);
+    for (uint64_t j : order) {
+        o.append(id.data(), id.size());
+        o.append(ks, (size_t)nk);
+        o.append(names[leaves[j]]);
+        o.append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", sc[j]));
+    }
+}
+
+// The three query loops over an open database, the reader and the outputs.
+struct QueryLoop {
+    ServedDb &db;
+    ReadQueue &rq;
+    Outputs &out;
+    const float threshold;
+    const uint64_t block;
+    const bool pos, neg, scores;
+    const unsigned threads;
+    const uint64_t kmer_size;
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
-    // An error on a worker thread ends the process at once, WITHOUT exit(): exit() would run the atexit handlers and static
-    // destructors (the HIP runtime's among them) while the other replicas' threads, the parser and the formatters are still
-    // inside HIP calls or writing.  Same message and status as die() (the reference panics: status 101).
-    auto fail_from_thread = [](const char *what) {
-        fprintf(stderr, "phage_filter: libpfq: %s\n", what);
-        fflush(stderr);
-        _exit(101);
-    };
-    if (block == 0) {
-        // nothing to do: see above
-    } else if (paired) {
-        // Fragments, batch by batch: the parsers fill a batch of whole fragments (mates adjacent, -b counts fragments); every
-        // replica classifies a contiguous share of its fragments (every shard: all of them) with PFQ_PAIRED on its own
-        // thread, so no batch, device share or shard slot splits a pair; then the batch is written.  Without filtering or
-        // scores the calls want counts only.
-        uint64_t batch_frags = 1u << 19;
-        if (const char *e = getenv("PFQ_CLI_BATCH_READS")) batch_frags = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: several batches)
-        batch_frags = std::max<uint64_t>(block, batch_frags) / block * block;
-        const uint32_t flags = PFQ_PAIRED | (pair_mode == "both" ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) |
-                               (scores ? PFQ_WANT_SCORES : 0u);
-        PairSource src{rq, rq2.get(), {}, {}, 0, {}, false};
+
+    size_t n_trees() const { return db.trees.size(); }
+    uint64_t batch_size(uint64_t target) const {  // a whole number of reference blocks
+        if (const char *e = getenv("PFQ_CLI_BATCH_READS")) target = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: several batches)
+        return std::max<uint64_t>(block, target) / block * block;
+    }
+
+    // Fragments, batch by batch: the parsers fill a batch of whole fragments (mates adjacent, -b counts fragments); every
+    // replica classifies a contiguous share of its fragments (every shard: all of them) with PFQ_PAIRED on its own thread,
+    // so no batch, device share or shard slot splits a pair; then the batch is written.  Without filtering or scores the
+    // calls want counts only.
+    void paired(ReadQueue *rq2, bool both) {
+        const uint64_t batch_frags = batch_size(1u << 19);
+        const bool per_read = pos || neg || scores;
+        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u);
+        PairSource src{rq, rq2, {}, {}, 0, {}, false};
         Batch b;
-        std::vector<std::vector<uint64_t>> t_off(n_trees), sub_off(n_trees);
-        std::vector<std::vector<uint32_t>> t_leaves(n_trees), t_scores(n_trees);
-        std::vector<uint64_t> f_off;
-        std::vector<uint32_t> f_leaves, f_scores;
-        std::string pos_out, neg_out, pos2_out, neg2_out, sc_out;
+        std::vector<Hits> parts(n_trees());
+        Hits f;  // the fragments' lists in the whole tree's leaf order
+        OutBuf pos_out, neg_out, pos2_out, neg2_out;
+        std::string sc_out;
+        std::vector<uint64_t> order;
         bool more = true;
         while (more) {
             b.clear();
@@ -1185,145 +1315,96 @@ int cmd_query(int argc, char **argv) {
             if (!nf) continue;
             b.seq.resize(b.seq.size() + 16);
             const uint64_t tq0 = ReadQueue::now_ns();
-            auto share = [&](size_t i, uint64_t &f0, uint64_t &f1) {
-                f0 = sharded ? 0 : nf * i / n_trees;
-                f1 = sharded ? nf : nf * (i + 1) / n_trees;
-            };
-            auto run = [&](size_t i) {
-                uint64_t f0, f1;
-                share(i, f0, f1);
-                const uint64_t r0 = 2 * f0, r1 = 2 * f1;
-                std::vector<uint64_t> &so = sub_off[i];
-                so.resize(r1 - r0 + 1);
-                for (uint64_t r = r0; r <= r1; ++r) so[r - r0] = b.off[r] - b.off[r0];
-                t_off[i].assign(f1 - f0 + 1, 0);
-                t_leaves[i].clear();
-                t_scores[i].clear();
-                if (r1 == r0) return;
-                pfq_hits hits{};
-                if (pfq_query_batch(trees[i], b.seq.data() + b.off[r0], so.data(), r1 - r0, threshold, flags, per_read ? &hits : nullptr) != PFQ_OK)
-                    fail_from_thread(pfq_last_error());
-                if (!per_read) return;
-                memcpy(t_off[i].data(), hits.offsets, (f1 - f0 + 1) * sizeof(uint64_t));
-                t_leaves[i].assign(hits.leaves, hits.leaves + hits.offsets[f1 - f0]);
-                if (scores) {
-                    const uint32_t *sc = nullptr;
-                    uint64_t n_sc = 0;
-                    if (pfq_last_hit_scores(trees[i], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
-                    t_scores[i].assign(sc, sc + n_sc);
-                }
-            };
-            {
-                std::vector<std::thread> th;
-                for (size_t i = 1; i < n_trees; ++i) th.emplace_back(run, i);
-                run(0);
-                for (auto &t : th) t.join();
-            }
+            fan_out(n_trees(), [&](size_t i) {
+                const size_t P = n_trees();
+                const uint64_t f0 = db.sharded ? 0 : nf * i / P, f1 = db.sharded ? nf : nf * (i + 1) / P;
+                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i]);
+            });
             ns_gpu += ReadQueue::now_ns() - tq0;
             n_total += n;
             if (!per_read) continue;
-            // the fragments' lists in the whole tree's leaf order: replicas' shares one after the other; shards' lists per
-            // fragment in shard order, each offset by the shard's first leaf
-            f_off.assign(nf + 1, 0);
-            f_leaves.clear();
-            f_scores.clear();
-            for (uint64_t f = 0; f < nf; ++f) {
-                for (size_t i = 0; i < n_trees; ++i) {
-                    uint64_t f0, f1;
-                    share(i, f0, f1);
-                    if (f < f0 || f >= f1) continue;
-                    const uint64_t j0 = t_off[i][f - f0], j1 = t_off[i][f - f0 + 1];
-                    const uint32_t base = sharded ? (uint32_t)leaf_base[i] : 0u;
-                    for (uint64_t j = j0; j < j1; ++j) f_leaves.push_back(t_leaves[i][j] + base);
-                    if (scores) f_scores.insert(f_scores.end(), t_scores[i].begin() + j0, t_scores[i].begin() + j1);
-                }
-                f_off[f + 1] = f_leaves.size();
-            }
+            merge_hits(parts, nf, db, f);
             // every mate with its own id and its fragment's genomes; a fragment with genomes goes to POS, both mates alike
-            pos_out.clear();
-            neg_out.clear();
-            pos2_out.clear();
-            neg2_out.clear();
+            pos_out.n = neg_out.n = pos2_out.n = neg2_out.n = 0;
             sc_out.clear();
-            for (uint64_t f = 0; f < nf; ++f) {
-                const bool mapped = f_off[f] != f_off[f + 1];
+            for (uint64_t fr = 0; fr < nf; ++fr) {
+                const uint32_t *l0 = f.leaves.data() + f.off[fr], *l1 = f.leaves.data() + f.off[fr + 1];
+                const bool mapped = l0 != l1;
                 if (mapped ? !pos : !neg) continue;
-                for (uint64_t r = 2 * f; r < 2 * f + 2; ++r) {
-                    std::string &o = (r & 1) && has_reads2 ? (mapped ? pos2_out : neg2_out) : (mapped ? pos_out : neg_out);
-                    const bool fq = b.has_qual[r] != 0;
-                    const std::string_view id = b.id(r);
-                    o.push_back(fq ? '@' : '>');
-                    o.append(id.data(), id.size());
-                    if (mapped) {  // get_ext_id: "{id} |{g1,g2}", genomes in leaf order
-                        o.append(" |");
-                        for (uint64_t j = f_off[f]; j < f_off[f + 1]; ++j) {
-                            if (j != f_off[f]) o.push_back(',');
-                            o.append(leaf_names[f_leaves[j]]);
-                        }
-                    }
-                    o.push_back('\n');
-                    const uint64_t len = b.off[r + 1] - b.off[r], at = o.size();
-                    o.resize(at + len);
-                    copy_upper(&o[at], b.seq.data() + b.off[r], len);
-                    o.push_back('\n');
-                    if (fq) {
-                        const std::string_view q = b.quality(r);
-                        o.append("+\n");
-                        o.append(q.data(), q.size());
-                        o.push_back('\n');
-                    }
-                }
+                for (uint64_t r = 2 * fr; r < 2 * fr + 2; ++r)
+                    put_record((r & 1) && rq2 ? (mapped ? pos2_out : neg2_out) : (mapped ? pos_out : neg_out), b, r, l0, l1, db.leaf_names);
             }
             if (scores) {
-                // READ_SCORES.tsv: per fragment with hits (R1's id), both mates' k-mers and matched k-mers per genome, best first
-                std::vector<uint64_t> order;
-                char num[64];
-                for (uint64_t f = 0; f < nf; ++f) {
-                    if (f_off[f] == f_off[f + 1]) continue;
-                    order.clear();
-                    for (uint64_t j = f_off[f]; j < f_off[f + 1]; ++j) order.push_back(j);
-                    std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return f_scores[x] > f_scores[y]; });
-                    uint64_t nk = 0;
-                    for (uint64_t r = 2 * f; r < 2 * f + 2; ++r) {
-                        const uint64_t len = b.off[r + 1] - b.off[r];
-                        nk += len >= kmer_size ? len - kmer_size + 1 : 0;
-                    }
-                    const std::string_view id = b.id(2 * f);
-                    for (uint64_t j : order) {
-                        sc_out.append(id.data(), id.size());
-                        sc_out.append(num, (size_t)snprintf(num, sizeof num, "\t%llu\t", (unsigned long long)nk));
-                        sc_out.append(leaf_names[f_leaves[j]]);
-                        sc_out.append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", f_scores[j]));
-                    }
+                // READ_SCORES.tsv: per fragment with hits (R1's id), both mates' k-mers and matched k-mers per genome
+                for (uint64_t fr = 0; fr < nf; ++fr) {
+                    if (f.off[fr] == f.off[fr + 1]) continue;
+                    const uint64_t nk = n_kmers(b.off[2 * fr + 1] - b.off[2 * fr], kmer_size) + n_kmers(b.off[2 * fr + 2] - b.off[2 * fr + 1], kmer_size);
+                    put_scores(sc_out, b.id(2 * fr), nk, f.leaves.data() + f.off[fr], f.scores.data() + f.off[fr], f.off[fr + 1] - f.off[fr],
+                               db.leaf_names, order);
                 }
-                if (!sc_out.empty() && fwrite(sc_out.data(), 1, sc_out.size(), scores_f) != sc_out.size()) die("short write to READ_SCORES.tsv");
+                if (!sc_out.empty() && fwrite(sc_out.data(), 1, sc_out.size(), out.scores) != sc_out.size()) die("short write to READ_SCORES.tsv");
             }
-            auto put = [&](int fd, const std::string &o, uint64_t &size) {
-                if (fd < 0 || o.empty()) return;
-                write_at(fd, o.data(), o.size(), size);
-                size += o.size();
-            };
-            put(pos_fd, pos_out, pos_size);
-            put(neg_fd, neg_out, neg_size);
-            put(pos2_fd, pos2_out, pos2_size);
-            put(neg2_fd, neg2_out, neg2_size);
+            out.pos.append(pos_out.p, pos_out.n);
+            out.neg.append(neg_out.p, neg_out.n);
+            out.pos2.append(pos2_out.p, pos2_out.n);
+            out.neg2.append(neg2_out.p, neg2_out.n);
         }
-        if (!src.err.empty()) rq.pending_error = src.err;  // fatal below, after the outputs of the fragments before it
-    } else if (!per_read && sharded) {
-        // Counts only, shards: every parsed segment goes to every shard's thread; segment k sits in ring[k % W] until the
-        // last shard is done with it, then goes back to the reader.  W is what the reader's pool takes back, so at most W
-        // segments are in flight and a shard at most W segments ahead of the slowest one.  One thread at a time takes the
-        // next segment from the reader (outside the lock: the others go on with the segments already taken) and pads it
-        // once, before any shard reads it.
+        if (!src.err.empty()) rq.pending_error = src.err;  // fatal later, after the outputs of the fragments before it
+    }
+
+    // Counts only: the next parsed segment in input order, padded for the device, or nullptr at the end of the input.
+    // `end`: nothing follows it — malformed input ends the input (the reads before it are still classified).
+    Segment *fetch_segment(bool &end) {
+        Segment *sg = rq.next_segment();
+        end = !sg || !sg->err.empty();
+        if (!sg) return nullptr;
+        if (!sg->err.empty()) rq.pending_error = sg->err;
+        if (sg->b.n()) sg->b.seq.resize(sg->b.seq.size() + 16);
+        return sg;
+    }
+    void count_segment(size_t i, const Segment &sg, Hits &unused) {
+        const uint64_t n = sg.b.n();
+        if (!n) return;
+        const uint64_t tq0 = ReadQueue::now_ns();
+        classify(db.trees[i], sg.b, 0, n, threshold, 0, unused);
+        ns_gpu += ReadQueue::now_ns() - tq0;
+        if (!db.sharded || i == 0) n_total += n;
+    }
+    // Counts only: the result does not depend on how the reads are cut into device calls (mapped_reads just accumulates,
+    // query.rs:143), so every parsed segment goes to a GPU as it is — no host-side copy.
+    //   replicas: segments are handed out in input order to whichever replica's thread asks next;
+    //   shards: every segment goes to every shard's thread; segment k sits in ring[k % W] until the last shard is done with
+    //   it, then goes back to the reader.  W is what the reader's pool takes back, so at most W segments are in flight and
+    //   a shard at most W segments ahead of the slowest one.  One thread at a time takes the next segment from the reader
+    //   (outside the lock: the others go on with the segments already taken).
+    void counts_only() {
+        std::mutex qm;
+        if (!db.sharded) {
+            bool done = false;
+            fan_out(n_trees(), [&](size_t d) {
+                Hits unused;
+                while (true) {
+                    Segment *sg;
+                    {
+                        std::lock_guard<std::mutex> lk(qm);
+                        if (done) return;
+                        if (!(sg = fetch_segment(done))) return;
+                    }
+                    count_segment(d, *sg, unused);
+                    rq.recycle(sg);
+                }
+            });
+            return;
+        }
         const size_t W = rq.pool_cap();
         std::vector<Segment *> ring(W, nullptr);
         std::vector<size_t> shards_left(W, 0);
-        std::mutex qm;
         std::condition_variable qcv;
         uint64_t fetched = 0;      // segments taken from the reader
         bool fetching = false;
         long long n_seg = -1;      // number of segments, once the end of the input (or malformed input) is reached
-        auto shard_loop = [&](size_t i) {
+        fan_out(n_trees(), [&](size_t i) {
+            Hits unused;
             for (uint64_t k = 0;; ++k) {
                 const size_t slot = (size_t)(k % W);
                 Segment *sg = nullptr;
@@ -1336,18 +1417,14 @@ int cmd_query(int argc, char **argv) {
                     if (k == fetched) {
                         fetching = true;
                         lk.unlock();
-                        sg = rq.next_segment();
-                        if (sg && sg->b.n()) sg->b.seq.resize(sg->b.seq.size() + 16);
+                        bool end;
+                        sg = fetch_segment(end);
                         lk.lock();
                         fetching = false;
-                        if (!sg) n_seg = (long long)k;
-                        else {
-                            if (!sg->err.empty()) {  // malformed input: the reads before it are still classified, nothing after it
-                                rq.pending_error = sg->err;
-                                n_seg = (long long)k + 1;
-                            }
+                        if (end) n_seg = (long long)k + (sg ? 1 : 0);
+                        if (sg) {
                             ring[slot] = sg;
-                            shards_left[slot] = n_trees;
+                            shards_left[slot] = n_trees();
                             ++fetched;
                         }
                         qcv.notify_all();
@@ -1355,14 +1432,7 @@ int cmd_query(int argc, char **argv) {
                     }
                     sg = ring[slot];
                 }
-                const uint64_t n = sg->b.n();
-                if (n) {
-                    const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[i], sg->b.seq.data(), sg->b.off.data(), n, threshold, 0, nullptr) != PFQ_OK)
-                        fail_from_thread(pfq_last_error());
-                    ns_gpu += ReadQueue::now_ns() - tq0;
-                    if (i == 0) n_total += n;
-                }
+                count_segment(i, *sg, unused);
                 bool last;
                 {
                     std::lock_guard<std::mutex> lk(qm);
@@ -1370,229 +1440,92 @@ int cmd_query(int argc, char **argv) {
                     if (last) ring[slot] = nullptr;
                 }
                 if (!last) continue;
-                if (!sg->err.empty()) delete sg;
-                else rq.recycle(sg);
+                rq.recycle(sg);
                 qcv.notify_all();
             }
+        });
+    }
+
+    // Per read, with POS/NEG and/or READ_SCORES.  The device processes big batches; ResultMap semantics (ids merged per
+    // reference block, cleared per block, main.rs:334-368) are applied per `block` consecutive reads so the outputs do not
+    // depend on the batch size.  Three stages, each on its own thread(s), batches in flight between them: (1) the
+    // assembler (above all the copy of the parsed records into batches of whole reference blocks), (2) one thread per
+    // tree: pfq_query_batch with hits, which are copied out of the library's buffers, (3) ONE output thread that takes the
+    // classified batches in input order, formats them with `threads` workers and writes every worker's part at its offset
+    // (pwrite, side by side) — while batch k is formatted and written, batch k + 1 is on the GPU and batch k + 2 is being
+    // assembled.
+    void per_read() {
+        const uint64_t batch_reads = batch_size(1u << 20);
+        struct Slot {
+            Batch b;
+            int ready = 0;            // 0 = free for the assembler, 1 = filled, 2 = classified
+            uint64_t seq = 0;         // which batch the slot holds
+            size_t trees_left = 0;    // trees that have yet to classify it
+            std::vector<Hits> parts;  // per tree (a replica: one)
+            Hits hits;                // the whole tree's
         };
-        std::vector<std::thread> th;
-        for (size_t i = 1; i < n_trees; ++i) th.emplace_back(shard_loop, i);
-        shard_loop(0);
-        for (auto &t : th) t.join();
-    } else if (!per_read) {
-        // Counts only: the result does not depend on how the reads are cut into device calls (mapped_reads just
-        // accumulates, query.rs:143), so every parsed segment goes to a GPU as it is — no host-side copy.  Segments are
-        // handed out in input order to whichever replica's thread asks next.
-        std::mutex qm;
-        bool done = false;
-        auto device_loop = [&](size_t d) {
-            while (true) {
-                Segment *sg = nullptr;
-                {
-                    std::lock_guard<std::mutex> lk(qm);
-                    if (done) return;
-                    sg = rq.next_segment();
-                    if (!sg) {
-                        done = true;
-                        return;
-                    }
-                    if (!sg->err.empty()) {  // malformed input: the reads before it are still classified, nothing after it
-                        rq.pending_error = sg->err;
-                        done = true;
-                    }
-                }
-                const uint64_t n = sg->b.n();
-                if (n) {
-                    sg->b.seq.resize(sg->b.seq.size() + 16);
-                    const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[d], sg->b.seq.data(), sg->b.off.data(), n, threshold, 0, nullptr) != PFQ_OK)
-                        fail_from_thread(pfq_last_error());
-                    ns_gpu += ReadQueue::now_ns() - tq0;
-                    n_total += n;
-                }
-                if (!sg->err.empty()) delete sg;
-                else rq.recycle(sg);
-            }
-        };
-        std::vector<std::thread> th;
-        for (size_t d = 1; d < n_dev; ++d) th.emplace_back(device_loop, d);
-        device_loop(0);
-        for (auto &t : th) t.join();
-    } else {
-        // The device processes big batches; ResultMap semantics (ids merged per reference block, cleared per block,
-        // main.rs:334-368) are applied per `block` consecutive reads so the outputs do not depend on the batch size.
-        uint64_t batch_target = 1u << 20;
-        if (const char *e = getenv("PFQ_CLI_BATCH_READS")) batch_target = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: several batches from a small input)
-        const uint64_t batch_reads = std::max<uint64_t>(block, batch_target) / block * block;
-        // Three stages, each on its own thread(s), batches in flight between them: (1) the assembler (above all the copy of
-        // the parsed records into batches of whole reference blocks), (2) one thread per replica: pfq_query_batch with hits,
-        // which are copied out of the library's buffers, (3) ONE output thread that takes the classified batches in input
-        // order, formats them with `threads` workers and writes every worker's part at its offset (pwrite, side by side) —
-        // while batch k is formatted and written, batch k + 1 is on the GPU and batch k + 2 is being assembled.
-        const size_t NB = n_dev + 3;
-        std::vector<Batch> batches(NB);
-        std::vector<std::vector<uint64_t>> hit_off(NB);
-        std::vector<std::vector<uint32_t>> hit_leaves(NB);
-        std::vector<std::vector<uint32_t>> hit_scores(scores ? NB : 0);  // --scores: aligned with hit_leaves
+        std::vector<Slot> slots(db.devices.size() + 3);
+        const size_t NB = slots.size();
+        for (Slot &s : slots) s.parts.resize(db.sharded ? n_trees() : 1);
         const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u);
-        std::vector<int> ready(NB, 0);          // 0 = free for the assembler, 1 = filled, 2 = classified
-        std::vector<uint64_t> batch_seq(NB, 0);  // which batch a slot holds
-        // shards: every shard's hits of the batch in a slot, and how many shards have yet to classify it
-        std::vector<std::vector<std::vector<uint64_t>>> shard_off(sharded ? NB : 0, std::vector<std::vector<uint64_t>>(n_trees));
-        std::vector<std::vector<std::vector<uint32_t>>> shard_leaves(sharded ? NB : 0, std::vector<std::vector<uint32_t>>(n_trees));
-        std::vector<std::vector<std::vector<uint32_t>>> shard_scores(sharded && scores ? NB : 0, std::vector<std::vector<uint32_t>>(n_trees));
-        std::vector<size_t> shards_left(NB, 0);
         std::mutex mu;
         std::condition_variable cv;
         long long last_seq = -1;                 // sequence number of the last batch, once the assembler knows it
+        auto past_end = [&](uint64_t k) { return last_seq >= 0 && (long long)k > last_seq; };
         uint64_t next_take = 0;
         std::atomic<uint64_t> ns_fmt{0}, ns_write{0};
         std::thread parser([&] {
             bool more = true;
             for (uint64_t k = 0; more; ++k) {
-                const size_t slot = (size_t)(k % NB);
+                Slot &s = slots[k % NB];
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return ready[slot] == 0; });
+                    cv.wait(lk, [&] { return s.ready == 0; });
                 }
-                rq.release_held(batches[slot]);  // (written: its segments go back to the parsers)
-                batches[slot].clear();
-                more = rq.fill(batches[slot], batch_reads, 3ull << 30, true);
-                // shards: padded here, once — every shard's thread reads the batch at the same time
-                if (sharded && batches[slot].n()) batches[slot].seq.resize(batches[slot].seq.size() + 16);
+                rq.release_held(s.b);  // (written: its segments go back to the parsers)
+                s.b.clear();
+                more = rq.fill(s.b, batch_reads, 3ull << 30, true);
+                // padded here, once: every shard's thread reads the batch at the same time
+                if (s.b.n()) s.b.seq.resize(s.b.seq.size() + 16);
                 {
                     std::lock_guard<std::mutex> lk(mu);
-                    shards_left[slot] = n_trees;
-                    ready[slot] = 1;
-                    batch_seq[slot] = k;
+                    s.trees_left = db.sharded ? n_trees() : 1;
+                    s.ready = 1;
+                    s.seq = k;
                     if (!more) last_seq = (long long)k;
                 }
                 cv.notify_all();
             }
         });
-        auto device_loop = [&](size_t d) {
-            while (true) {
+        // A replica's thread takes the next batch nobody has taken; a shard's thread takes every batch.  The thread that
+        // classifies a batch last merges the trees' hits (shards: see merge_hits) and hands it to the output thread.
+        auto classify_loop = [&](size_t i) {
+            for (uint64_t mine = 0;;) {
                 uint64_t k;
-                size_t slot;
+                Slot *s;
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    k = next_take++;
-                    slot = (size_t)(k % NB);
-                    cv.wait(lk, [&] { return (ready[slot] == 1 && batch_seq[slot] == k) || (last_seq >= 0 && (long long)k > last_seq); });
-                    if (last_seq >= 0 && (long long)k > last_seq) return;
+                    k = db.sharded ? mine++ : next_take++;
+                    s = &slots[k % NB];
+                    cv.wait(lk, [&] { return (s->ready == 1 && s->seq == k) || past_end(k); });
+                    if (past_end(k)) return;
                 }
-                Batch &b = batches[slot];
-                const uint64_t n = b.n();
-                hit_off[slot].assign(n + 1, 0);
-                hit_leaves[slot].clear();
+                const uint64_t n = s->b.n(), tq0 = ReadQueue::now_ns();
+                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0]);
                 if (n) {
-                    b.seq.resize(b.seq.size() + 16);
-                    pfq_hits hits{};
-                    const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[d], b.seq.data(), b.off.data(), n, threshold, query_flags, &hits) != PFQ_OK)
-                        fail_from_thread(pfq_last_error());
-                    // (library-owned until the next call on this replica: the output thread works on copies)
-                    memcpy(hit_off[slot].data(), hits.offsets, (n + 1) * sizeof(uint64_t));
-                    hit_leaves[slot].assign(hits.leaves, hits.leaves + hits.offsets[n]);
-                    if (scores) {
-                        const uint32_t *sc = nullptr;
-                        uint64_t n_sc = 0;
-                        if (pfq_last_hit_scores(trees[d], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
-                        hit_scores[slot].assign(sc, sc + n_sc);
-                    }
                     ns_gpu += ReadQueue::now_ns() - tq0;
-                    n_total += n;
+                    if (!db.sharded || i == 0) n_total += n;
                 }
                 {
                     std::lock_guard<std::mutex> lk(mu);
-                    ready[slot] = 2;
+                    if (--s->trees_left != 0) continue;
+                }
+                merge_hits(s->parts, n, db, s->hits);
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    s->ready = 2;
                 }
                 cv.notify_all();
-            }
-        };
-        // Shards: thread i runs EVERY batch through shard i.  The last shard to finish a batch merges the shards' hits: per
-        // read, the shards' ascending lists in shard order, each offset by the shard's first leaf — the whole tree's CSR.
-        auto shard_loop = [&](size_t i) {
-            for (uint64_t k = 0;; ++k) {
-                const size_t slot = (size_t)(k % NB);
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return (ready[slot] == 1 && batch_seq[slot] == k) || (last_seq >= 0 && (long long)k > last_seq); });
-                    if (last_seq >= 0 && (long long)k > last_seq) return;
-                }
-                const Batch &b = batches[slot];
-                const uint64_t n = b.n();
-                std::vector<uint64_t> &s_off = shard_off[slot][i];
-                std::vector<uint32_t> &s_leaves = shard_leaves[slot][i];
-                s_off.assign(n + 1, 0);
-                s_leaves.clear();
-                if (n) {
-                    pfq_hits hits{};
-                    const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_query_batch(trees[i], b.seq.data(), b.off.data(), n, threshold, query_flags, &hits) != PFQ_OK)
-                        fail_from_thread(pfq_last_error());
-                    memcpy(s_off.data(), hits.offsets, (n + 1) * sizeof(uint64_t));
-                    s_leaves.assign(hits.leaves, hits.leaves + hits.offsets[n]);
-                    if (scores) {
-                        const uint32_t *sc = nullptr;
-                        uint64_t n_sc = 0;
-                        if (pfq_last_hit_scores(trees[i], &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
-                        shard_scores[slot][i].assign(sc, sc + n_sc);
-                    }
-                    ns_gpu += ReadQueue::now_ns() - tq0;
-                    if (i == 0) n_total += n;
-                }
-                bool last;
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    last = --shards_left[slot] == 0;
-                }
-                if (!last) continue;
-                std::vector<uint64_t> &h_off = hit_off[slot];
-                std::vector<uint32_t> &h_leaves = hit_leaves[slot];
-                uint64_t total = 0;
-                for (size_t s = 0; s < n_trees; ++s) total += shard_off[slot][s][n];
-                h_off.assign(n + 1, 0);
-                h_leaves.resize(total);
-                if (scores) hit_scores[slot].resize(total);
-                uint64_t at = 0;
-                for (uint64_t r = 0; r < n; ++r) {
-                    for (size_t s = 0; s < n_trees; ++s) {
-                        const uint64_t *o = shard_off[slot][s].data();
-                        const uint32_t *l = shard_leaves[slot][s].data();
-                        const uint32_t base = (uint32_t)leaf_base[s];
-                        if (scores) std::copy(shard_scores[slot][s].begin() + o[r], shard_scores[slot][s].begin() + o[r + 1], hit_scores[slot].begin() + at);
-                        for (uint64_t j = o[r]; j < o[r + 1]; ++j) h_leaves[at++] = l[j] + base;
-                    }
-                    h_off[r + 1] = at;
-                }
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready[slot] = 2;
-                }
-                cv.notify_all();
-            }
-        };
-        // Output buffers of the formatters: grown with realloc (no zero fill), kept from batch to batch.
-        struct OutBuf {
-            char *p = nullptr;
-            size_t n = 0, cap = 0;
-            ~OutBuf() { free(p); }
-            char *room(size_t want) {
-                if (n + want > cap) {
-                    cap = std::max(n + want, cap + cap / 2 + (1u << 20));
-                    p = (char *)realloc(p, cap);
-                    if (!p) die("out of memory (output buffer)");
-                }
-                return p + n;
-            }
-            void put(const char *src, size_t len) {
-                memcpy(room(len), src, len);
-                n += len;
-            }
-            void put(char c) {
-                *room(1) = c;
-                ++n;
             }
         };
         // (formatters and writers share the cores with the parser workers and the assembler; measured on 16 cores with
@@ -1621,17 +1554,13 @@ int cmd_query(int argc, char **argv) {
                 }
                 const uint64_t t1 = ReadQueue::now_ns();
                 std::vector<OutBuf> &pb = pos_sets[j & 1], &nb = neg_sets[j & 1];
-                std::vector<std::thread> ts;
                 const unsigned n_wr = std::min(job.nw, max_writers);
-                auto write_parts = [&](unsigned x) {  // writer x takes parts x, x + n_wr, ...
-                    for (unsigned w = x; w < job.nw; w += n_wr) {
-                        if (pos_fd >= 0) write_at(pos_fd, pb[w].p, pb[w].n, job.pos_at[w]);
-                        if (neg_fd >= 0) write_at(neg_fd, nb[w].p, nb[w].n, job.neg_at[w]);
+                fan_out(n_wr, [&](size_t x) {  // writer x takes parts x, x + n_wr, ...
+                    for (size_t w = x; w < job.nw; w += n_wr) {
+                        if (out.pos.fd >= 0) write_at(out.pos.fd, pb[w].p, pb[w].n, job.pos_at[w]);
+                        if (out.neg.fd >= 0) write_at(out.neg.fd, nb[w].p, nb[w].n, job.neg_at[w]);
                     }
-                };
-                for (unsigned x = 1; x < n_wr; ++x) ts.emplace_back(write_parts, x);
-                write_parts(0);
-                for (auto &t : ts) t.join();
+                });
                 ns_write += ReadQueue::now_ns() - t1;
                 {
                     std::lock_guard<std::mutex> lk(mu);
@@ -1670,23 +1599,17 @@ int cmd_query(int argc, char **argv) {
                 h = (h ^ x) * 0xc4ceb9fe1a85ec53ull;
                 return h ^ (h >> 29);
             };
-            auto run_workers = [&](unsigned nw, const std::function<void(unsigned)> &fn) {
-                std::vector<std::thread> ts;
-                for (unsigned w = 1; w < nw; ++w) ts.emplace_back(fn, w);
-                fn(0);
-                for (auto &t : ts) t.join();
-            };
             for (uint64_t k = 0;; ++k) {
-                const size_t slot = (size_t)(k % NB);
+                Slot &s = slots[k % NB];
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return (ready[slot] == 2 && batch_seq[slot] == k) || (last_seq >= 0 && (long long)k > last_seq); });
-                    if (last_seq >= 0 && (long long)k > last_seq) return;
+                    cv.wait(lk, [&] { return (s.ready == 2 && s.seq == k) || past_end(k); });
+                    if (past_end(k)) return;
                 }
-                const Batch &b = batches[slot];
+                const Batch &b = s.b;
                 const uint64_t n = b.n();
-                const uint64_t *h_off = hit_off[slot].data();
-                const uint32_t *h_leaves = hit_leaves[slot].data();
+                const uint64_t *h_off = s.hits.off.data();
+                const uint32_t *h_leaves = s.hits.leaves.data();
                 {   // the buffer set of this batch must have been written
                     std::unique_lock<std::mutex> lk(mu);
                     cv.wait(lk, [&] { return jobs[k & 1].state == 0; });
@@ -1714,7 +1637,7 @@ int cmd_query(int argc, char **argv) {
                 if (grp_of.size() < n) grp_of.resize(n);
                 merged_of.resize(std::max<size_t>(merged_of.size(), n_blocks));
                 const unsigned nw1 = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(fmt_workers, n_blocks));
-                run_workers(nw1, [&](unsigned w) {
+                fan_out(nw1, [&](size_t w) {
                     for (uint64_t blk = n_blocks * w / nw1; blk < n_blocks * (w + 1) / nw1; ++blk) {
                         const uint64_t b0 = blk * block, b1 = std::min(n, b0 + block);
                         Group *grp = groups.data() + grp0[blk];
@@ -1759,28 +1682,17 @@ int cmd_query(int argc, char **argv) {
                 });
                 // ---- phase 2: the records
                 const unsigned nw = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(fmt_workers, (n + 4095) / 4096));
-                run_workers(nw, [&](unsigned w) {
+                fan_out(nw, [&](size_t w) {
                     OutBuf &pb = pos_buf[w], &nb = neg_buf[w];
                     pb.n = nb.n = 0;
                     for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r) {
                         const int32_t g = grp_of[r];
                         const bool mapped = g >= 0;
                         if (mapped ? !pos : !neg) continue;
-                        OutBuf &line = mapped ? pb : nb;
-                        const std::string_view id = b.id(r);
-                        const uint64_t len = b.off[r + 1] - b.off[r];
-                        const bool fq = b.has_qual[r] != 0;
-                        {   // write_record (main.rs:394-404): '@' / '>' + id
-                            char *dst = line.room(id.size() + 3);
-                            dst[0] = fq ? '@' : '>';
-                            memcpy(dst + 1, id.data(), id.size());
-                            line.n += id.size() + 1;
-                        }
-                        if (mapped) {                              // get_ext_id: "{id} |{g1,g2}" (set order unspecified in the reference)
-                            line.put(" |", 2);
+                        const uint32_t *l0 = nullptr, *l1 = nullptr;
+                        if (mapped) {
                             const uint64_t blk = r / block;
                             const Group &gr = groups[grp0[blk] + (uint64_t)g];
-                            const uint32_t *l0, *l1;
                             if (gr.merged >= 0) {
                                 l0 = merged_of[blk][gr.merged].data();
                                 l1 = l0 + merged_of[blk][gr.merged].size();
@@ -1788,70 +1700,39 @@ int cmd_query(int argc, char **argv) {
                                 l0 = h_leaves + h_off[gr.first_read];   // (ascending within a read, no duplicates)
                                 l1 = h_leaves + h_off[gr.first_read + 1];
                             }
-                            for (const uint32_t *l = l0; l < l1; ++l) {
-                                if (l != l0) line.put(',');
-                                line.put(leaf_names[*l].data(), leaf_names[*l].size());
-                            }
                         }
-                        const std::string_view q = fq ? b.quality(r) : std::string_view();
-                        char *dst = line.room(len + q.size() + 5);
-                        *dst++ = '\n';
-                        copy_upper(dst, b.seq.data() + b.off[r], len);   // the sequence, upper-cased (main.rs:347-349)
-                        dst += len;
-                        *dst++ = '\n';
-                        size_t wrote = len + 2;
-                        if (fq) {
-                            dst[0] = '+';
-                            dst[1] = '\n';
-                            memcpy(dst + 2, q.data(), q.size());
-                            dst[2 + q.size()] = '\n';
-                            wrote += q.size() + 3;
-                        }
-                        line.n += wrote;
+                        put_record(mapped ? pb : nb, b, r, l0, l1, db.leaf_names);
                     }
                 });
                 for (unsigned w = nw; w < fmt_workers; ++w) pos_buf[w].n = neg_buf[w].n = 0;
                 if (scores) {
-                    // READ_SCORES.tsv: per record with hits, its genomes by matched k-mers (descending; ties in leaf order)
+                    // READ_SCORES.tsv: per record with hits, its genomes by matched k-mers
                     std::vector<std::string> parts(nw);
-                    const uint32_t *h_sc = hit_scores[slot].data();
-                    run_workers(nw, [&](unsigned w) {
-                        std::string &o = parts[w];
+                    const uint32_t *h_sc = s.hits.scores.data();
+                    fan_out(nw, [&](size_t w) {
                         std::vector<uint64_t> order;
-                        char kmers[32], num[32];
-                        for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r) {
-                            if (h_off[r] == h_off[r + 1]) continue;
-                            order.clear();
-                            for (uint64_t j = h_off[r]; j < h_off[r + 1]; ++j) order.push_back(j);
-                            std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return h_sc[x] > h_sc[y]; });
-                            const uint64_t len = b.off[r + 1] - b.off[r];
-                            const int nk = snprintf(kmers, sizeof kmers, "\t%llu\t", (unsigned long long)(len >= kmer_size ? len - kmer_size + 1 : 0));
-                            const std::string_view id = b.id(r);
-                            for (uint64_t j : order) {
-                                o.append(id.data(), id.size());
-                                o.append(kmers, (size_t)nk);
-                                o.append(leaf_names[h_leaves[j]]);
-                                o.append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", h_sc[j]));
-                            }
-                        }
+                        for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r)
+                            if (h_off[r] != h_off[r + 1])
+                                put_scores(parts[w], b.id(r), n_kmers(b.off[r + 1] - b.off[r], kmer_size), h_leaves + h_off[r], h_sc + h_off[r],
+                                           h_off[r + 1] - h_off[r], db.leaf_names, order);
                     });
                     for (const std::string &p : parts)
-                        if (!p.empty() && fwrite(p.data(), 1, p.size(), scores_f) != p.size()) fail_from_thread("short write to READ_SCORES.tsv");
+                        if (!p.empty() && fwrite(p.data(), 1, p.size(), out.scores) != p.size()) fail_from_thread("short write to READ_SCORES.tsv");
                 }
                 const uint64_t t1 = ReadQueue::now_ns();
                 ns_fmt += t1 - t0;
                 // the bytes: batches come in input order, so a part's place is the sum of what lies before it
-                std::vector<uint64_t> pos_at(nw + 1, pos_size), neg_at(nw + 1, neg_size);
+                std::vector<uint64_t> pos_at(nw + 1, out.pos.size), neg_at(nw + 1, out.neg.size);
                 for (unsigned x = 0; x < nw; ++x) {
                     pos_at[x + 1] = pos_at[x] + pos_buf[x].n;
                     neg_at[x + 1] = neg_at[x] + neg_buf[x].n;
                 }
-                pos_size = pos_at[nw];
-                neg_size = neg_at[nw];
+                out.pos.size = pos_at[nw];
+                out.neg.size = neg_at[nw];
                 ns_out += ReadQueue::now_ns() - t0;
                 {   // the batch is free again (everything it holds is in the buffers); the writer takes over
                     std::lock_guard<std::mutex> lk(mu);
-                    ready[slot] = 0;
+                    s.ready = 0;
                     jobs[k & 1].nw = nw;
                     jobs[k & 1].pos_at = pos_at;
                     jobs[k & 1].neg_at = neg_at;
@@ -1860,15 +1741,7 @@ int cmd_query(int argc, char **argv) {
                 cv.notify_all();
             }
         });
-        std::vector<std::thread> th;
-        if (sharded) {
-            for (size_t i = 1; i < n_trees; ++i) th.emplace_back(shard_loop, i);
-            shard_loop(0);
-        } else {
-            for (size_t d = 1; d < n_dev; ++d) th.emplace_back(device_loop, d);
-            device_loop(0);
-        }
-        for (auto &t : th) t.join();
+        fan_out(n_trees(), classify_loop);
         parser.join();
         output.join();
         {
@@ -1877,48 +1750,131 @@ int cmd_query(int argc, char **argv) {
         }
         cv.notify_all();
         writer.join();
-        for (Batch &bb : batches) rq.release_held(bb);
+        for (Slot &s : slots) rq.release_held(s.b);
         if (getenv("PFQ_INGEST_TIMING"))
             fprintf(stderr, "output: format %.3f s, write %.3f s (%u workers; wall times of the formatter and the writer thread, which overlap)\n",
                     ns_fmt.load() * 1e-9, ns_write.load() * 1e-9, fmt_workers);
     }
+};
+
+int cmd_query(int argc, char **argv) {
+    std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
+                             {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
+                             {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
+                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
+                             {"interleaved", 0, false}, {"pair-mode", 0, true}};
+    Args a = parse(argc, argv, 2, opts);
+    const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
+    const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
+    (void)to_u64(opt(a, "cache-size", "10"), "cache-size");  // LRU of .bf files: the whole tree is resident in HBM
+    const uint64_t block = to_u64(opt(a, "block-size-reads", "100"), "block-size-reads");
+    const float threshold = to_f32(opt(a, "filter-threshold", "1.0"), "filter-threshold");
+    const bool pos = a.flags.count("pos-filter") != 0, neg = a.flags.count("neg-filter") != 0;
+    const bool filtering = pos || neg;
+    // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
+    const bool scores = a.flags.count("scores") != 0;
+    const bool per_read = filtering || scores;  // the per-read hit lists are needed
+    const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
+    // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
+    // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
+    const bool interleaved = a.flags.count("interleaved") != 0, has_reads2 = a.val.count("reads2") != 0;
+    if (interleaved && has_reads2) die("error: the argument '--reads2 <READS2>' cannot be used with '--interleaved'");
+    const bool paired = interleaved || has_reads2;
+    const std::string pair_mode = opt(a, "pair-mode", "either");
+    if (pair_mode != "either" && pair_mode != "both")
+        die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
+    if (a.val.count("pair-mode") && !paired) die("error: '--pair-mode' needs '--reads2' or '--interleaved'");
+
+    // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
+    // the per-genome counts are combined by one RCCL all-reduce at the end.  The reference has one rayon pool instead
+    // (main.rs:269-272); results do not depend on how the reads are dealt.
+    std::vector<int> devices;
+    {
+        std::string spec = opt(a, "devices", getenv("PFQ_DEVICES") ? getenv("PFQ_DEVICES") : "");
+        if (spec == "all") {
+            int n = 0;
+            check(pfq_device_count(&n));
+            for (int i = 0; i < n; ++i) devices.push_back(i);
+        } else if (!spec.empty()) {
+            size_t p0 = 0;
+            while (p0 <= spec.size()) {
+                size_t p1 = spec.find(',', p0);
+                if (p1 == std::string::npos) p1 = spec.size();
+                devices.push_back((int)to_u64(spec.substr(p0, p1 - p0), "devices"));
+                p0 = p1 + 1;
+            }
+        }
+        if (devices.empty()) devices.push_back(device_from_env());
+    }
+    // --shard-depth D: the database is split into the subtree shards of its depth-E frontier (pfq_tree_open_subtree), E = D,
+    // or the search depth when that is smaller (a shard cut below the pruning depth would put one pruned leaf into several
+    // shards).  Shard i classifies EVERY read, on its own host thread; the shards' hits and counts are concatenated in
+    // shard order.
+    const bool sharded = a.val.count("shard-depth") != 0;
+    uint64_t shard_depth = 0;
+    if (sharded) {
+        shard_depth = to_u64(a.val.at("shard-depth"), "shard-depth");
+        if (a.val.count("search-depth")) shard_depth = std::min(shard_depth, to_u64(a.val.at("search-depth"), "search-depth"));
+    }
+    ServedDb db(db_path, devices, sharded, shard_depth);
+    printf("Querying reads...\n");
+    printf("Filtering settings: positive=%s; negative=%s\n", pos ? "true" : "false", neg ? "true" : "false");
+    if (a.val.count("search-depth")) {
+        uint64_t depth = to_u64(a.val.at("search-depth"), "search-depth");
+        if (!filtering) printf("If using a search depth, use a filtering flag (--pos-filter or --neg-filter, or both!)\n");
+        printf("Search depth settings: %llu\n", (unsigned long long)depth);
+        db.prune(depth);
+    }
+    ReadQueue rq(reads, ov);
+    std::unique_ptr<ReadQueue> rq2;
+    if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
+    // Page-locking costs ~1.7 s per GB here (hipHostMalloc), the pageable copy ~0.1 s per GB: pinned buffers only
+    // pay off once every pooled buffer has been reused a few dozen times (inputs of >~ 10^9 reads).  Opt-in.
+    g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
+    // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
+    // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
+    if (block != 0) rq.start(per_read || paired, threads);  // (paired: the mates' ids are compared)
+    if (block != 0 && rq2) rq2->start(true, threads);
+
+    // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
+    struct stat st;
+    if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
+    mkdir(out.c_str(), 0777);
+    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores);
+    uint64_t kmer_size = 0;
+    if (scores) {
+        pfq_info info{};
+        check(pfq_tree_info(db.trees[0], &info));
+        kmer_size = info.kmer_size;
+    }
+    db.load_leaf_names();
+
+    const uint64_t t_loop0 = ReadQueue::now_ns();
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size};
+    if (block == 0) {
+        // nothing to do: see above
+    } else if (paired) {
+        q.paired(rq2.get(), pair_mode == "both");
+    } else if (!per_read) {
+        q.counts_only();
+    } else {
+        q.per_read();
+    }
     if (getenv("PFQ_INGEST_TIMING")) {
         const double wall = (ReadQueue::now_ns() - t_loop0) * 1e-9;
         fprintf(stderr, "query loop: %llu reads in %.3f s = %.2f M reads/s on %zu device(s) (pfq_query_batch %.3f s, output %.3f s)\n",
-                (unsigned long long)n_total.load(), wall, n_total.load() / wall * 1e-6, n_dev, ns_gpu.load() * 1e-9, ns_out.load() * 1e-9);
+                (unsigned long long)q.n_total.load(), wall, q.n_total.load() / wall * 1e-6, devices.size(), q.ns_gpu.load() * 1e-9,
+                q.ns_out.load() * 1e-9);
         rq.report_timing();
         struct rusage ru;
         if (getrusage(RUSAGE_SELF, &ru) == 0)
             fprintf(stderr, "cpu: user %.2f s + system %.2f s so far (all threads) for %.2f s of query loop\n",
                     ru.ru_utime.tv_sec + ru.ru_utime.tv_usec * 1e-6, ru.ru_stime.tv_sec + ru.ru_stime.tv_usec * 1e-6, wall);
     }
-    if (pos_fd >= 0) close(pos_fd);
-    if (neg_fd >= 0) close(neg_fd);
-    if (pos2_fd >= 0) close(pos2_fd);
-    if (neg2_fd >= 0) close(neg2_fd);
-    if (scores_f && fclose(scores_f) != 0) die("short write to READ_SCORES.tsv");
+    outs.close();
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
-    if (sharded) {
-        // the shards' counts one after the other, in pfq_save_leaf_counts' format: the leaf ranges are disjoint, so every
-        // leaf (and every count stored in tree.bin) appears once — nothing to reduce
-        const std::string csv = out + "/CLASSIFICATION.csv";
-        FILE *f = fopen(csv.c_str(), "wb");
-        if (!f) die("cannot create " + csv + ": " + strerror(errno));
-        for (pfq_tree *t : trees) {
-            const char *const *tax = nullptr;
-            const uint64_t *cnt = nullptr;
-            uint64_t n_leaves = 0;
-            check(pfq_leaf_counts(t, &tax, &cnt, &n_leaves));
-            for (uint64_t j = 0; j < n_leaves; ++j)
-                if (cnt[j] > 0) fprintf(f, "%s,%llu\n", tax[j], (unsigned long long)cnt[j]);  // query.rs:177-182
-        }
-        if (fclose(f) != 0) die("short write to " + csv);
-    } else {
-        // per-genome counts of all replicas: one RCCL all-reduce (every replica then holds the totals); replica 0 writes the file
-        if (n_dev > 1) check(pfq_trees_allreduce_counts(trees.data(), (uint32_t)n_dev));
-        check(pfq_save_leaf_counts(tree, (out + "/CLASSIFICATION.csv").c_str()));
-    }
-    for (pfq_tree *t : trees) pfq_tree_close(t);
+    db.save_counts(out + "/CLASSIFICATION.csv");
+    db.close();
     printf("Finished.\n");
     return 0;
 }

@@ -145,8 +145,7 @@ def test_paired_devices_and_shards_agree(db, pairs, tmp_path, mode):
         got = run(db, str(tmp_path / f"v{i}"), ["-r", r1, "--reads2", r2], "0.5", *flags, *extra)
         assert sorted(got) == sorted(base)
         assert open(got["CLASSIFICATION.csv"], "rb").read() == open(base["CLASSIFICATION.csv"], "rb").read(), extra
-        for f in base:
-            if f != "CLASSIFICATION.csv":
-                assert collections.Counter(open(got[f]).read().splitlines()) == collections.Counter(open(base[f]).read().splitlines()), (extra, f)
+        for f in base:   # (fragments are written in input order whatever classified them)
+            assert open(got[f], "rb").read() == open(base[f], "rb").read(), (extra, f)
     counts_only = run(db, str(tmp_path / "counts"), ["-r", r1, "--reads2", r2], "0.5", "--pair-mode", mode, "--devices", "0,0")
     assert open(counts_only["CLASSIFICATION.csv"], "rb").read() == open(base["CLASSIFICATION.csv"], "rb").read()

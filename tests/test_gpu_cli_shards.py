@@ -260,7 +260,8 @@ def test_stored_counts_are_reported_once(ex_db, tmp_path):
 
 
 def test_malformed_fastq_tail(ex_db, tmp_path):
-    """The reads before the bad record are classified by every shard, the outputs are written, then exit 101."""
+    """The reads before the bad record are classified by every shard (and by the replicas), the outputs are written, then
+    exit 101."""
     src = sorted(os.listdir(os.path.join(EX, "reads")))[0]
     bad = tmp_path / "bad.fq"
     bad.write_bytes(open(os.path.join(EX, "reads", src), "rb").read() + b"@cut\nACGTACGT\n+\n")
@@ -270,5 +271,8 @@ def test_malformed_fastq_tail(ex_db, tmp_path):
         assert whole[0] == 101 and "Incomplete record" in whole[2], whole[2]
         r = query(ex_db, str(bad), str(tmp_path / f"s{filtering}"), *extra, "--shard-depth", "2")
         assert_same_run(whole, r, 4, 1)
+        rep = query(ex_db, str(bad), str(tmp_path / f"r{filtering}"), *extra, "--devices", "0,0")
+        assert rep[0] == 101 and rep[1] == whole[1] and rep[3] == whole[3], rep[2]
+        assert [l for l in rep[2].splitlines() if l.startswith("phage_filter:")] == [l for l in whole[2].splitlines() if l.startswith("phage_filter:")]
         if filtering:
             assert len(r[3]["POS_FILTERING.fq"]) > 0
