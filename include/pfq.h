@@ -103,7 +103,12 @@ int pfq_db_shard_count(const char *db_dir, uint64_t depth, uint64_t *n_shards);
  *   continues into the child at smaller Hamming distance (right only if strictly smaller, :201); the leaf reached is
  *   replaced by a new internal node (left = old leaf, right = new leaf, filter = union, :226-245).  internal_name
  *   names that node (tax_id, "<name>.bf"); NULL = "Internal_Node_<n>" with a running n unique in the tree (the
- *   reference draws a random u16, :231-233).  Works on trees from pfq_tree_open as well (`add`). */
+ *   reference draws a random u16, :231-233).  Works on trees from pfq_tree_open as well (`add`).
+ *   An insertion that fails (a node with one child on the walk: PFQ_ERR_FORMAT, the reference panics at :209; the
+ *   device walk's barrier timing out: PFQ_ERR_DEVICE) may be reported by this call or, since the walk runs
+ *   asynchronously, by the next call that needs the topology.  From then on the error persists until pfq_tree_close:
+ *   pfq_tree_insert, pfq_tree_save, pfq_tree_prune, both query calls and every leaf-count call return the same code
+ *   and message, and nothing is written.  pfq_tree_info and pfq_tree_close keep working. */
 int pfq_tree_create(uint64_t kmer_size, float false_pos_rate, uint32_t largest_expected_genome, uint64_t seed1,
                     uint64_t seed2, uint64_t expected_genomes, int device, pfq_tree **out);
 int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char *tax_id, const char *internal_name);

@@ -372,15 +372,35 @@ def renumber_preorder(t: OracleTree) -> None:
     t.root = 0 if order else -1
 
 
+def reserve_rows(t: OracleTree, rows: int) -> None:
+    """Room for `rows` filter rows without copying: t.bits becomes a view of the first rows of a zeroed buffer of at
+    least that many (greedy_insert grows it by half each time it is full, so n insertions copy O(n) rows in all)."""
+    n = 0 if t.bits is None else t.bits.shape[0]
+    buf = getattr(t, "_bits_buf", None)
+    if buf is not None and t.bits is not None and t.bits.base is buf and buf.shape[0] >= rows:
+        return
+    cap = max(rows, n)
+    buf = np.zeros((cap, t.n_words), dtype=np.uint64)
+    if n:
+        buf[:n] = t.bits
+    t._bits_buf = buf
+    t.bits = buf[:n]
+
+
 def greedy_insert(t: OracleTree, genome: bytes, tax_id: str, internal_name: Optional[str] = None) -> None:
     """BloomTree::insert (bloom_tree.rs:128-143): init_leaf_node (:154-168), add_to_tree (:187-214) and
     init_internal_node (:226-245).  Filter rows are appended to t.bits; nodes are appended (call renumber_preorder
     when done).  internal_name replaces the reference's random "Internal_Node_<u16>" (:231-233); default
     "Internal_Node_<n>" with n counting the internal nodes made so far, skipping names already in the tree."""
     def new_row() -> int:
-        t.bits = np.zeros((1, t.n_words), dtype=np.uint64) if t.bits is None or t.n_nodes == 0 else \
-            np.vstack([t.bits, np.zeros((1, t.n_words), dtype=np.uint64)])
-        return t.bits.shape[0] - 1
+        if t.n_nodes == 0 and t.bits is not None and t.bits.shape[0]:
+            t.bits = None                            # (an empty tree starts its rows afresh)
+        n = 0 if t.bits is None else t.bits.shape[0]
+        buf = getattr(t, "_bits_buf", None)
+        if buf is None or t.bits is None or t.bits.base is not buf or buf.shape[0] <= n:
+            reserve_rows(t, n + n // 2 + 2)
+        t.bits = t._bits_buf[:n + 1]
+        return n
 
     r = new_row()
     nv = t.add_node(tax_id, f"{tax_id}.bf", r)

@@ -178,6 +178,10 @@ struct pfq_tree {
     uint32_t gseq_next = 0;
     int greedy_blocks = 0;
     uint32_t walk_seq = 0;             // launches of the device walk since d_walk was written (parity: where the root is read / left)
+    // the first insertion that failed (a one-child node on the walk, the device walk's barrier): every call that needs the
+    // topology returns it from then on — the ancestors have absorbed the leaf, the shape on the device is half made
+    int insert_err = PFQ_OK;
+    std::string insert_err_msg;
 
     pfq::HashParams hp{};
     // ---- device: node-major filters
@@ -477,18 +481,32 @@ uint32_t optimal_num_hashes_f32(uint64_t bits, uint32_t items) {  // bloom_filte
     return std::min<uint32_t>(std::max<uint32_t>(h, 2), 200);
 }
 
+// A failed insertion is sticky (include/pfq.h): the first one is recorded, and it is what every later call that needs the
+// topology returns.
+const char *const ONE_CHILD_MSG = "Node with only one child encountered - should not happen. (bloom_tree.rs:209)";
+int insertion_failed(pfq_tree &t, int code, const std::string &msg) {
+    if (t.insert_err == PFQ_OK) {
+        t.insert_err = code;
+        t.insert_err_msg = msg;
+    }
+    return fail(t.insert_err, t.insert_err_msg);
+}
+int insertion_error(const pfq_tree &t) { return t.insert_err == PFQ_OK ? PFQ_OK : fail(t.insert_err, t.insert_err_msg); }
+
 // Nodes in pre-order again (root = 0) after pfq_tree_insert appended some; parents, depths and the ⊇ flags follow.
 // The shape the insertions on the device left (k_greedy_insert): children of every node, the root.
 int sync_topology(pfq_tree &t) {
+    PFQ_TRY(insertion_error(t));
     if (!t.topo_pending) return PFQ_OK;
     HIP_TRY(hipDeviceSynchronize());
     std::vector<pfq::TopoNode> h(t.nodes.size());
     int st[2] = {-1, 0};
     HIP_TRY(hipMemcpy(h.data(), t.d_topo.p, h.size() * sizeof(pfq::TopoNode), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(st, t.d_walk.p, sizeof st, hipMemcpyDeviceToHost));
+    // (topo_pending stays set on failure: the shape on the device is never taken over)
+    if (st[1] == 1) return insertion_failed(t, PFQ_ERR_FORMAT, ONE_CHILD_MSG);
+    if (st[1] != 0) return insertion_failed(t, PFQ_ERR_DEVICE, "the insertion kernel's grid barrier timed out");
     t.topo_pending = false;
-    if (st[1] == 1) return fail(PFQ_ERR_FORMAT, "Node with only one child encountered - should not happen. (bloom_tree.rs:209)");
-    if (st[1] != 0) return fail(PFQ_ERR_DEVICE, "the insertion kernel's grid barrier timed out");
     for (size_t v = 0; v < h.size(); ++v) {
         t.nodes[v].left = h[v].left;
         t.nodes[v].right = h[v].right;
@@ -682,6 +700,7 @@ int build_coarse(pfq_tree &t, const CoarsePlan &plan) {
 }
 
 int build_layout(pfq_tree &t) {
+    PFQ_TRY(insertion_error(t));
     if (t.layout_valid) return PFQ_OK;
     PFQ_TRY(finish_topology(t));
     t.leaves = leaves_dfs(t);
@@ -2130,6 +2149,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     if (!tree || !tax_id || (len && !seq)) return fail(PFQ_ERR_ARG, "null argument");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
+    PFQ_TRY(insertion_error(t));
     if (t.is_shard) return fail(PFQ_ERR_STATE, "a subtree shard cannot be extended");
     if (t.n_words == 0) return fail(PFQ_ERR_STATE, "tree has no filter geometry");
     // One .bf per node here.  (The reference keys filters by file name: a second node called <tax_id> gets a fresh empty
@@ -2158,8 +2178,13 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     }
     // the device's copy of the shape (all of it once; afterwards the kernel keeps it current)
     const size_t n_after = t.nodes.size() + 2;
-    if (t.knobs.greedy_host > 0) HIP_TRY(t.d_dist.ensure(2 * (size_t)pfq::INSERT_STEP_BLOCKS));
-    else if (!t.topo_on_device || t.d_topo.n < n_after) {
+    if (t.knobs.greedy_host > 0) {
+        // the host walk takes the shape over from the device walk's insertions (before the new leaf is appended: the
+        // device's copy has no entry for it yet)
+        PFQ_TRY(sync_topology(t));
+        t.topo_on_device = false;
+        HIP_TRY(t.d_dist.ensure(2 * (size_t)pfq::INSERT_STEP_BLOCKS));
+    } else if (!t.topo_on_device || t.d_topo.n < n_after) {
         PFQ_TRY(sync_topology(t));
         HIP_TRY(hipDeviceSynchronize());
         const size_t cap = std::max<size_t>(n_after, 2 * t.d_topo.n + 1024);
@@ -2223,8 +2248,6 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     // PFQ_GREEDY_HOST=1: the descent level by level from the host (one launch and one read-back per level; no kernel with a
     // grid barrier) — for devices that are shared with other work, where not every block of such a kernel stays resident
     if (t.knobs.greedy_host > 0) {
-        PFQ_TRY(sync_topology(t));
-        t.topo_on_device = false;
         if (t.root < 0 || nv == 0) {
             t.root = nv;
             --t.n_rows;  // (no internal node: its row is not used)
@@ -2275,7 +2298,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
                 else (went_right ? t.nodes[parent].right : t.nodes[parent].left) = ni_h;
                 break;
             } else {
-                return fail(PFQ_ERR_FORMAT, "Node with only one child encountered - should not happen. (bloom_tree.rs:209)");
+                return insertion_failed(t, PFQ_ERR_FORMAT, ONE_CHILD_MSG);
             }
         }
         HIP_TRY(hipDeviceSynchronize());
@@ -2413,9 +2436,11 @@ int pfq_tree_save(const pfq_tree *tree, const char *db_dir) {
 
 int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
     if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
-    if (tree->topology_dirty) {
+    if (tree->topology_dirty && tree->insert_err == PFQ_OK) {
         PFQ_TRY(use_device(tree->device));
-        PFQ_TRY(finish_topology(*const_cast<pfq_tree *>(tree)));
+        // (an insertion that failed is learnt here without failing the call: the parameters stay readable)
+        const int rc = finish_topology(*const_cast<pfq_tree *>(tree));
+        if (rc != PFQ_OK && tree->insert_err == PFQ_OK) return rc;
     }
     const pfq_tree &t = *tree;
     out->kmer_size = t.kmer_size;

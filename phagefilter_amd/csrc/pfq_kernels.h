@@ -307,8 +307,9 @@ void launch_insert_one(const HashParams &hp, const uint8_t *d_genome, uint64_t l
 // The greedy placement of one new leaf (BloomTree::insert, bloom_tree.rs:187-245) walked on the device in one launch; the tree's
 // shape is mirrored in device memory: a TopoNode per node, state[0] = the root's index (-1: empty; state[2 + (seq & 1)] is
 // where launch number seq reads it, state[2 + (~seq & 1)] where it leaves it), state[1] = error word
-// (1: a node with one child was met; 2: the grid's barrier timed out), sync = GREEDY_SYNC_LINES lines of GREEDY_SYNC_STRIDE
-// bytes, zeroed once (the barrier's counters, generation words and distance accumulators, a line each: see grid_turn).
+// (1: a node with one child was met; 2: the grid's barrier timed out; a launch that finds it set returns at once),
+// sync = GREEDY_SYNC_LINES lines of GREEDY_SYNC_STRIDE bytes, zeroed once (the barrier's counters, generation words and
+// distance accumulators, a line each: see grid_turn).
 // `blocks` must not exceed the number of CUs (every block has to be resident).
 struct TopoNode {
     int32_t left, right;   // node indices, -1: none

@@ -2931,11 +2931,17 @@ __global__ void __launch_bounds__(1024) k_greedy_insert(uint64_t *bits, uint64_t
                                                         uint32_t seq) {
     __shared__ unsigned long long s_l[16], s_r[16];
     __shared__ unsigned int s_gen;
+    __shared__ int s_err;
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, G = gridDim.x;
     // (the generation the block's copy holds when this launch starts; nobody changes it before all have read it: the first
     //  change needs every block's arrival)
-    if (threadIdx.x == 0) s_gen = atomicAdd(sync_word(sync, 17u + (blockIdx.x & 15u)), 0u) >> 1;
+    if (threadIdx.x == 0) {
+        s_gen = atomicAdd(sync_word(sync, 17u + (blockIdx.x & 15u)), 0u) >> 1;
+        s_err = __hip_atomic_load(&state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     __syncthreads();
+    // an insertion before this one failed (the host refuses the tree from then on): the shape it left is not walked
+    if (s_err != 0) return;
     unsigned int my_gen = s_gen;
     const uint64_t *nw = bits + (uint64_t)new_row * n_words;
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)G * blockDim.x;

@@ -36,6 +36,18 @@ def _oracle_copy(gt, ids):
     return ot
 
 
+def _check_filters_against_oracle(ot, genomes, ids):
+    """The device's filters are not only what the queries are checked over: two leaves, whose parent is the internal node of
+    two leaves that comes last in pre-order, equal the oracle's insertion of their genomes, and that parent equals their OR."""
+    v = max(u for u in range(ot.n_nodes) if not ot.is_leaf(u) and ot.is_leaf(ot.left[u]) and ot.is_leaf(ot.right[u]))
+    ref = orc.OracleTree(K, NBITS, H, SEEDS[0], SEEDS[1], 0.001, 5000000)
+    ref.bits = np.zeros((2, ot.n_words), dtype=np.uint64)
+    for row, leaf in enumerate((ot.left[v], ot.right[v])):
+        orc.insert_sequence(ref, row, genomes[ids.index(ot.tax_id[leaf])].tobytes())
+        assert np.array_equal(ot.bits[ot.filter_of[leaf]], ref.bits[row]), ot.tax_id[leaf]
+    assert np.array_equal(ot.bits[ot.filter_of[v]], ref.bits[0] | ref.bits[1])
+
+
 def _reads(genomes, rng, n, err):
     """n reads of RLEN: even indices from the genomes (uniform leaf / offset / strand, `err` substitutions per base), odd
     ones uniform random.  Returns (seq, off) packed."""
@@ -104,6 +116,7 @@ def test_config3_geometry_thresholds_below_one_vs_oracle(gpu):
     genomes = d_gen.to_numpy().reshape(N_LEAVES, GLEN)
     d_gen.free()
     ot = _oracle_copy(gt, ids)
+    _check_filters_against_oracle(ot, genomes, ids)
     rng = np.random.default_rng(20261005)
     seq, off = _reads(genomes, rng, N_READS, 0.01)
     for thr in (0.3, 0.7, 1.0):
