@@ -218,6 +218,15 @@ uint32_t pfq_last_allreduce_ranks(void);
  * to the built-in choice.  Results never depend on a knob. */
 int pfq_set_option(pfq_tree *tree, const char *name, const char *value);
 
+/* Scratch capacities of the last pfq_query_batch[_device] and how far its kernels got into them (waits for the stream
+ * of that call).  Writes min(n, PFQ_CAPACITY_N) values: [0] deferred-pair cursor, [1] its cap, [2] guard-pair cursor,
+ * [3] its cap, [4] k-mer miss-word cursor, [5] its cap, [6] tile-mode miss bytes handed out (saturates at the cap),
+ * [7] its cap, [8] hit cursor of the first attempt, [9] its hit cap, [10] attempts (2: the hit buffer overflowed and the
+ * block ran again), [11] pairs sorted into the buckets.  A cursor above its cap: that buffer overflowed, the rest was
+ * certified inline.  Pair values are 0 on the direct path; hit values are 0 without PFQ_WANT_HITS / PFQ_PAIRED. */
+#define PFQ_CAPACITY_N 12
+int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n);
+
 
 /* Per-call statistics of the last pfq_query_batch[_device] (valid after the stream is synchronised). */
 typedef struct pfq_stats {

@@ -16,7 +16,8 @@ SYMBOLS = [
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
-    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_synth_genomes_device",
+    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
+    "pfq_synth_genomes_device",
     "pfq_synth_reads_device", "pfq_host_alloc", "pfq_host_free", "pfq_last_error", "pfq_version",
 ]
 
@@ -111,6 +112,7 @@ def lib() -> C.CDLL:
     L.pfq_profile_end.argtypes = [vp, C.POINTER(Profile)]
     L.pfq_debug_kmer_indices.argtypes = [vp, vp, C.c_uint64, vp, u64p]
     L.pfq_debug_node_filter.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
+    L.pfq_debug_last_capacity.argtypes = [vp, vp, C.c_uint64]
     L.pfq_synth_genomes_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]
     L.pfq_synth_reads_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64,
                                          C.c_uint64, vp]

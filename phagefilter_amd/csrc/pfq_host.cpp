@@ -84,6 +84,7 @@ struct Knobs {
     long long verify_blocks = -1, verify_chunk = -1, verify_sub = -1, verify_threads = -1, bin_blocks = -1, test_blocks = -1;
     long long tile = -1, tile_counts = -1, no_tail_batch = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1;
     long long coarse = -1, coarse_cols = -1, coarse_probes = -1, group_log2 = -1, screen_recs = -1, coarse_min_leaves = -1, greedy_host = -1;
+    long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
 };
 struct KnobName {
     const char *name;
@@ -106,6 +107,9 @@ const KnobName KNOBS[] = {
     {"PFQ_COARSE_PROBES", &Knobs::coarse_probes}, {"PFQ_GROUP_LOG2", &Knobs::group_log2},
     {"PFQ_SCREEN_RECS", &Knobs::screen_recs},   {"PFQ_COARSE_MIN_LEAVES", &Knobs::coarse_min_leaves},
     {"PFQ_GREEDY_HOST", &Knobs::greedy_host},
+    {"PFQ_PAIR_SLOTS", &Knobs::pair_slots},     {"PFQ_GUARD_SLOTS", &Knobs::guard_slots},
+    {"PFQ_MISS_WORDS", &Knobs::miss_words},     {"PFQ_KMISS_BYTES", &Knobs::kmiss_bytes},
+    {"PFQ_HIT_SLOTS", &Knobs::hit_slots},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -240,8 +244,11 @@ struct pfq_tree {
     DevBuf<uint4> d_meta;  // resolved per-pair metadata for the record-driven verify
     DevBuf<uint64_t> d_off;
     DevBuf<unsigned long long> d_counts_snapshot;
+    // the stream of the last query call, for comparison only: the caller may destroy it once it is synchronised, so what
+    // waits for that call is last_done, recorded on it after the call's work
     hipStream_t last_stream = nullptr;
     bool have_last_stream = false;
+    hipEvent_t last_done = nullptr;
     int force_path = -1;
     // ---- profiling (HIP events on the launch stream)
     std::vector<hipEvent_t> prof_ev;  // PROF_EV events per recorded call
@@ -249,6 +256,10 @@ struct pfq_tree {
     std::vector<uint8_t> prof_bucketed;
     uint32_t last_path = 0, last_slices = 1;
     uint64_t last_n_reads = 0;
+    // pfq_debug_last_capacity: the caps the last call gave the kernels, its first attempt's hit cursor, its attempts
+    uint64_t last_pair_cap = 0, last_guard_cap = 0, last_miss_cap = 0, last_kmiss_cap = 0, last_hit_cap0 = 0, last_hit_cursor0 = 0;
+    uint64_t last_nb = 0;  // buckets of the last bucketed call (0: direct path): d_bucket[2 * last_nb] = pairs sorted
+    uint32_t last_attempts = 0;
     // ---- outputs (library-owned)
     std::vector<std::string> out_tax;
     std::vector<const char *> out_tax_ptr;
@@ -912,7 +923,8 @@ struct QueryRun {
         want_hits = user_hits || paired;  // (fragments are combined from the mates' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
-        if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipStreamSynchronize(t.last_stream));
+        if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
+        if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipEventSynchronize(t.last_done));
         t.last_stream = st;
         t.have_last_stream = true;
         t.last_n_reads = n_reads;
@@ -985,9 +997,15 @@ struct QueryRun {
                     bucketed = false;
             }
         }
+        if (bucketed && kn.miss_words >= 0) miss_cap = std::min<uint64_t>(miss_cap, (uint64_t)kn.miss_words);
         t.last_path = bucketed ? 1 : 0;
         if (!bucketed) t.last_tile_mode = t.last_tile_bin = 0;  // (the direct path runs no tile pass)
         hit_cap = t.d_hit_pairs.n;
+        if (kn.hit_slots >= 0) hit_cap = std::min<uint64_t>(hit_cap, (uint64_t)kn.hit_slots);  // (first attempt only, see read_hits)
+        t.last_pair_cap = t.last_guard_cap = t.last_kmiss_cap = t.last_hit_cursor0 = t.last_attempts = 0;
+        t.last_miss_cap = miss_cap;
+        t.last_hit_cap0 = want_hits ? hit_cap : 0;
+        t.last_nb = bucketed ? nb : 0;
         return PFQ_OK;
     }
 
@@ -1132,6 +1150,7 @@ struct QueryRun {
     }
 
     int attempt(int attempt_no) {
+        t.last_attempts = (uint32_t)attempt_no + 1;
         HIP_TRY(hipMemsetAsync(t.d_stats.p, 0, pfq::ST_N * 8, st));
         HIP_TRY(hipMemsetAsync(t.d_cursors.p, 0, 128, st));
         if (want_hits) {
@@ -1211,6 +1230,8 @@ struct QueryRun {
         cur = off + nb + 1;
         a.pairs = t.d_pairs.p;
         a.pair_cap = t.leaf_cap;  // whole reservations only (PAIR_CHUNK = 32)
+        if (kn.pair_slots >= 0) a.pair_cap = std::min<uint64_t>(a.pair_cap, (uint64_t)kn.pair_slots & ~(uint64_t)(pfq::PAIR_RESERVE - 1));
+        t.last_pair_cap = a.pair_cap;
         a.pair_cursor = t.d_cursors.p + 1;
         a.bucket_cnt = cnt;
         a.sub_log2 = sub_log2;
@@ -1262,6 +1283,8 @@ struct QueryRun {
         if (with_guards && !block_mode) {  // every guard of a deferred pair's leaf becomes a pair of its own (second region of the buffer)
             ga.pairs = t.d_pairs.p + t.leaf_cap;
             ga.cap = t.guard_cap;
+            if (kn.guard_slots >= 0) ga.cap = std::min<uint64_t>(ga.cap, (uint64_t)kn.guard_slots);
+            t.last_guard_cap = ga.cap;
             ga.cursor = t.d_cursors.p + 8;
             ga.slot0 = (uint32_t)t.leaf_cap;
             ga.owner = t.d_owner.p;
@@ -1349,8 +1372,9 @@ struct QueryRun {
             // thresholds < 1: one miss byte per k-mer of every pair the recent calls make expect (chunks that find no room
             // take the fallback), the rounds' positions, the pairs' positions
             // (block mode: 8 bytes per k-mer, one per leaf of the block; chunk offsets are in 16-byte units)
-            const uint64_t kmiss_cap = counts_mode ? std::min<uint64_t>(((uint64_t)((double)total_bytes * std::max(1.0, 1.3 * t.pairs_per_read)) + 16 * max_chunks + 64) * (block_mode ? 8u : 1u),
-                                                                            block_mode ? (48ull << 30) : 0xfffffff0ull) & ~15ull : 0;
+            uint64_t kmiss_cap = counts_mode ? std::min<uint64_t>(((uint64_t)((double)total_bytes * std::max(1.0, 1.3 * t.pairs_per_read)) + 16 * max_chunks + 64) * (block_mode ? 8u : 1u),
+                                                                      block_mode ? (48ull << 30) : 0xfffffff0ull) & ~15ull : 0;
+            if (counts_mode && kn.kmiss_bytes >= 0) kmiss_cap = std::min<uint64_t>(kmiss_cap, (uint64_t)kn.kmiss_bytes & ~15ull);
             bool ok = soft_ensure(t.d_entries, want) && soft_ensure(t.d_pair_chunk, t.d_pairs.n) && soft_ensure(t.d_flag_list, t.d_pairs.n) &&
                       soft_ensure(t.d_leaf_chunk0, nc + 1) && soft_ensure(t.d_chunks, max_chunks) && soft_ensure(t.d_gfill, max_chunks * n_tiles) && soft_ensure(t.d_binq, 256);
             if (ok && counts_mode)
@@ -1401,6 +1425,7 @@ struct QueryRun {
                     ta.threshold = threshold;
                     ta.kmiss = t.d_kmiss.p;
                     ta.kmiss_cap = kmiss_cap;
+                    t.last_kmiss_cap = kmiss_cap;
                     ta.kmiss_used = t.d_cursors.p + 9;
                     ta.round_k0 = t.d_round_k0.p;
                     ta.n_rounds = t.d_n_rounds.p;
@@ -1573,6 +1598,7 @@ struct QueryRun {
         unsigned long long cursors[2] = {0, 0};
         HIP_TRY(hipMemcpy(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost));
         if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)cursors[0] / (double)n_reads);
+        if (t.last_attempts == 1) t.last_hit_cursor0 = cursors[0];
         if (cursors[0] <= hit_cap && paired) return pair_hits(cursors[0]);
         if (cursors[0] <= hit_cap) {
             // CSR read -> leaves (ascending; reads that pass every node list every leaf), built on the device from the
@@ -1630,7 +1656,7 @@ struct QueryRun {
             hits->leaves = t.h_hit_leaves;
             return PFQ_OK;
         }
-        // hit buffer too small: restore the counters and run the block again with room for every hit
+        // hit buffer too small: restore the counters and run the block again with room for every hit (whatever PFQ_HIT_SLOTS says)
         if (nl) HIP_TRY(hipMemcpy(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice));
         HIP_TRY(t.d_hit_pairs.ensure(cursors[0] + 1024));
         hit_cap = t.d_hit_pairs.n;
@@ -1729,8 +1755,15 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
                  float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
     t.scores_valid = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
-    PFQ_TRY(q.plan());
-    return q.run();
+    int rc = q.plan();
+    if (rc == PFQ_OK) rc = q.run();
+    if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
+    return rc;
+}
+// Waits for the last query call's work (its stream may since have been destroyed by the caller).
+int wait_last_call(pfq_tree &t) {
+    if (t.last_done) HIP_TRY(hipEventSynchronize(t.last_done));
+    return PFQ_OK;
 }
 
 // The subtree shards of a tree: its depth-`depth` frontier, left to right — nodes at that depth and leaves above it
@@ -2496,6 +2529,7 @@ void pfq_tree_close(pfq_tree *tree) {
 
     if (tree->h_pair_cursor) (void)hipHostFree(tree->h_pair_cursor);
     if (tree->hint_ev) (void)hipEventDestroy(tree->hint_ev);
+    if (tree->last_done) (void)hipEventDestroy(tree->last_done);
     delete tree;
 }
 
@@ -2810,7 +2844,7 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
     pfq_tree &t = *tree;
     memset(out, 0, sizeof *out);
     if (!t.d_stats.p) return PFQ_OK;
-    HIP_TRY(hipStreamSynchronize(t.last_stream));
+    PFQ_TRY(wait_last_call(t));
     unsigned long long h[pfq::ST_N];
     HIP_TRY(hipMemcpy(h, t.d_stats.p, sizeof h, hipMemcpyDeviceToHost));
     out->n_reads = t.last_n_reads;
@@ -2858,7 +2892,7 @@ int pfq_profile_end(pfq_tree *tree, pfq_profile *out) {
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
     memset(out, 0, sizeof *out);
-    HIP_TRY(hipStreamSynchronize(t.last_stream));
+    PFQ_TRY(wait_last_call(t));
     for (size_t c = 0; c < t.prof_used; ++c) {
         hipEvent_t *ev = &t.prof_ev[PROF_EV * c];
         float ms = 0;
@@ -2897,6 +2931,26 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
 int pfq_set_path(pfq_tree *tree, int path) {
     if (!tree || path < -1 || path > 1) return fail(PFQ_ERR_ARG, "bad argument");
     tree->force_path = path;
+    return PFQ_OK;
+}
+
+int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n) {
+    if (!tree || (n && !out)) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    uint64_t v[PFQ_CAPACITY_N] = {};
+    if (t.d_cursors.p) {
+        PFQ_TRY(wait_last_call(t));
+        unsigned long long c[10];
+        HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
+        uint32_t sorted = 0;
+        if (t.last_nb && t.d_bucket.n > 2 * t.last_nb) HIP_TRY(hipMemcpy(&sorted, t.d_bucket.p + 2 * t.last_nb, 4, hipMemcpyDeviceToHost));
+        const uint64_t w[PFQ_CAPACITY_N] = {c[1], t.last_pair_cap, c[8], t.last_guard_cap, c[5], t.last_miss_cap, c[9], t.last_kmiss_cap,
+                                            t.last_hit_cursor0, t.last_hit_cap0, t.last_attempts, sorted};
+        if (t.last_path) memcpy(v, w, sizeof v);
+        else v[8] = w[8], v[9] = w[9], v[10] = w[10];  // (the direct path has no pair buffers)
+    }
+    for (uint64_t i = 0; i < n && i < PFQ_CAPACITY_N; ++i) out[i] = v[i];
     return PFQ_OK;
 }
 

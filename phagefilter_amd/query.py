@@ -180,6 +180,17 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_last_stats(self._h, C.byref(s)))
         return s
 
+    CAPACITY_FIELDS = ("pair_cursor", "pair_cap", "guard_cursor", "guard_cap", "miss_cursor", "miss_cap", "kmiss_used",
+                       "kmiss_cap", "hit_cursor", "hit_cap", "attempts", "pairs_sorted")
+
+    def last_capacity(self) -> dict:
+        """Scratch capacities of the last query call and how far its kernels got into them (pfq_debug_last_capacity):
+        a cursor above its cap means that buffer overflowed and the rest was certified inline; `hit_cursor` / `hit_cap`
+        are the first attempt's, `attempts` is 2 when the hit buffer overflowed and the block ran again."""
+        out = np.zeros(len(self.CAPACITY_FIELDS), dtype=np.uint64)
+        _ffi.check(_ffi.lib().pfq_debug_last_capacity(self._h, out.ctypes.data, out.size))
+        return {k: int(v) for k, v in zip(self.CAPACITY_FIELDS, out)}
+
     def profile_begin(self, max_calls: int) -> None:
         _ffi.check(_ffi.lib().pfq_profile_begin(self._h, max_calls))
 

@@ -14,6 +14,9 @@ def hip():
         _hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
         _hip.hipFree.argtypes = [C.c_void_p]
         _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+        _hip.hipStreamDestroy.argtypes = [C.c_void_p]
     return _hip
 
 
@@ -24,6 +27,24 @@ def _check(rc, what):
 
 def synchronize():
     _check(hip().hipDeviceSynchronize(), "hipDeviceSynchronize")
+
+
+HIP_STREAM_NON_BLOCKING = 1
+
+
+def stream_create(non_blocking: bool = True) -> int:
+    """A new stream (raw handle); non-blocking: not ordered with the null stream."""
+    s = C.c_void_p()
+    _check(hip().hipStreamCreateWithFlags(C.byref(s), HIP_STREAM_NON_BLOCKING if non_blocking else 0), "hipStreamCreateWithFlags")
+    return s.value
+
+
+def stream_synchronize(stream: int) -> None:
+    _check(hip().hipStreamSynchronize(stream), "hipStreamSynchronize")
+
+
+def stream_destroy(stream: int) -> None:
+    _check(hip().hipStreamDestroy(stream), "hipStreamDestroy")
 
 
 class DeviceBuffer:
