@@ -6,7 +6,12 @@ over one batch of synthetic 150 bp reads that is already resident in HBM.  Workl
 (SURVEY.md §8d): balanced 1024-leaf SBT over 50 kbp random genomes, k=21, nbits=71 887 936, 10 hashes, fixed
 seeds; reads 50 % positive (uniform leaf / offset / strand, error-free) and 50 % uniform random, theta = 1.0.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+      A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes the outputs
+      if asked and prints the line.  It checks nothing; --dump-outputs gives what to compare.
+      --full: after the timed steps, also measure and check what the headline figure does not need (see below: the
+      host-buffer and hit-list rates, the CPU baseline within --cpu-seconds, the oracle parity on a sample and the
+      checks of everything timed).  The timed steps and the line's headline fields are the same in both modes.
       --dump-outputs DIR: after the timed steps, rank 0 writes what they computed as float64 .npy files —
       DIR/leaf_counts_last_step.npy (per-genome hits of the last timed step alone) and DIR/leaf_counts.npy (per-genome
       hits of all K timed steps, what the timed region hands back), both indexed by genome and reduced over the ranks.
@@ -23,10 +28,12 @@ seeds; reads 50 % positive (uniform leaf / offset / strand, error-free) and 50 %
       (N = 1 with --subtree-index i: one shard alone, i.e. one rank's work of the sharded job.)
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (contract figure of SURVEY §8d over the
-kernel time measured live with HIP events on the launch stream, plus the measured-traffic view `hbm_utilisation`) and
-`cpu_baseline` (the CPU oracle in reference-faithful mode on the host cores, rank 0, N = 1 only; a reported baseline,
-not the target).  The GPU result is checked before the line is printed — against the oracle on a sample and against the
-workload's ground truth on everything timed; a mismatch exits non-zero without a line.
+kernel time measured live with HIP events on the launch stream, plus the measured-traffic view `hbm_utilisation`).
+With --full the line also carries `host_buffers_reads_per_s` and `want_hits_reads_per_s` (N = 1), `cpu_baseline` (the
+CPU oracle in reference-faithful mode on the host cores, rank 0, N = 1 only, --cpu-seconds > 0; a reported baseline,
+not the target) and `parity`: the GPU result is checked before the line is printed — the reduced counts against the
+ranks' counters, against the oracle on a sample and against the workload's ground truth on everything timed; a mismatch
+exits non-zero without a line.
 """
 import argparse
 import json
@@ -57,7 +64,11 @@ def parse_args():
     ap.add_argument("--read-len", type=int, default=150)
     ap.add_argument("--threshold", type=float, default=1.0)
     ap.add_argument("--path", type=int, default=-1, help="-1 auto, 0 direct kernel, 1 bucketed")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget; 0 disables the timing (not the parity check)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the host-buffer and hit-list rates and the CPU baseline, and "
+                         "check the result against the oracle and the workload's ground truth")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: CPU-baseline budget; 0 disables the timing (not the parity check)")
     ap.add_argument("--k", type=int, default=K, help="scenario runs only: k-mer size (the metric's workload is the default)")
     ap.add_argument("--nbits", type=int, default=NBITS, help="scenario runs only: filter bits")
     ap.add_argument("--hashes", type=int, default=NUM_HASHES, help="scenario runs only: hashes per k-mer")
@@ -281,29 +292,30 @@ def main() -> None:
     total_reads = args.steps * B if subtree else world * args.steps * B
     total_hits = int(total_counts.sum().item())
 
-    # ---- checks on everything that was timed (all ranks): the reduction is the sum of the ranks' counters, every positive
-    # read hit its source leaf, and what else was hit stays within the Bloom false-positive rate
-    local_sum = torch.tensor([int(local_counts.sum().item())], dtype=torch.int64, device=dev)
-    if use_pg:
-        dist.all_reduce(local_sum, op=dist.ReduceOp.SUM)
+    # ---- --full: checks on everything that was timed (all ranks): the reduction is the sum of the ranks' counters, every
+    # positive read hit its source leaf, and what else was hit stays within the Bloom false-positive rate
     problems = []
-    if int(local_sum.item()) != total_hits:
-        problems.append(f"reduced counts sum to {total_hits}, the ranks' own counters to {int(local_sum.item())}")
-    if not experiment and args.threshold == 1.0 and rl >= K:
-        expect = np.zeros(n_g, dtype=np.int64)
-        for i in range(args.steps):
-            for r in (range(1) if subtree else range(world)):
-                b = (args.warmup + i) % n_batches
-                f = b * B if subtree else (b * world + r) * B
-                pos, leaf = read_plan(np, READ_SEED, f, B, n_g)
-                expect += np.bincount(leaf[pos], minlength=n_g)
-        got = total_counts.cpu().numpy()[:n_g]
-        if subtree and world == 1:   # one shard alone: only its own leaves are held
-            expect, got = expect[first_leaf:first_leaf + n_local], got[first_leaf:first_leaf + n_local]
-        if not (got >= expect).all():
-            problems.append("a positive read did not hit its source leaf")
-        elif int(got.sum() - expect.sum()) > max(64, total_reads // 50000):
-            problems.append(f"{int(got.sum() - expect.sum())} hits beyond the positives' source leaves (Bloom false positives should be rare)")
+    if args.full:
+        local_sum = torch.tensor([int(local_counts.sum().item())], dtype=torch.int64, device=dev)
+        if use_pg:
+            dist.all_reduce(local_sum, op=dist.ReduceOp.SUM)
+        if int(local_sum.item()) != total_hits:
+            problems.append(f"reduced counts sum to {total_hits}, the ranks' own counters to {int(local_sum.item())}")
+        if not experiment and args.threshold == 1.0 and rl >= K:
+            expect = np.zeros(n_g, dtype=np.int64)
+            for i in range(args.steps):
+                for r in (range(1) if subtree else range(world)):
+                    b = (args.warmup + i) % n_batches
+                    f = b * B if subtree else (b * world + r) * B
+                    pos, leaf = read_plan(np, READ_SEED, f, B, n_g)
+                    expect += np.bincount(leaf[pos], minlength=n_g)
+            got = total_counts.cpu().numpy()[:n_g]
+            if subtree and world == 1:   # one shard alone: only its own leaves are held
+                expect, got = expect[first_leaf:first_leaf + n_local], got[first_leaf:first_leaf + n_local]
+            if not (got >= expect).all():
+                problems.append("a positive read did not hit its source leaf")
+            elif int(got.sum() - expect.sum()) > max(64, total_reads // 50000):
+                problems.append(f"{int(got.sum() - expect.sum())} hits beyond the positives' source leaves (Bloom false positives should be rare)")
 
     result = None
     if rank == 0:
@@ -394,8 +406,8 @@ def main() -> None:
             "setup_seconds": setup_s,
         }
 
-    # ---- PCIe-inclusive rate: the same block handed over as HOST buffers (pfq_query_batch); never `value`
-    if rank == 0 and world == 1:
+    # ---- --full: PCIe-inclusive rate: the same block handed over as HOST buffers (pfq_query_batch); never `value`
+    if args.full and rank == 0 and world == 1:
         h_seq = np.concatenate([reads[:B * rl].cpu().numpy(), np.zeros(16, dtype=np.uint8)])
         h_off = np.arange(B + 1, dtype=np.uint64) * rl
         best = None
@@ -417,8 +429,8 @@ def main() -> None:
         result["want_hits_reads_per_s"] = B / best
         result["want_hits_pairs"] = int(offs[-1])
 
-    # ---- parity vs the oracle on a sample (rank 0, always) + the CPU baseline timing (N = 1, --cpu-seconds > 0)
-    if rank == 0:
+    # ---- --full: parity vs the oracle on a sample (rank 0) + the CPU baseline timing (N = 1, --cpu-seconds > 0)
+    if args.full and rank == 0:
         check = oracle_check_and_baseline(tree, reads, n_g, ids, B, rl, args, np, torch, subtree, shard_index,
                                           time_it=(world == 1 and args.cpu_seconds > 0))
         if check.get("gpu_parity_on_sample") not in ("ok", "skipped"):

@@ -1,6 +1,7 @@
 """bench.py --dump-outputs: the per-genome counts of the last timed step and of all timed steps, as float64 .npy.
 The GPU runs use a small tree and few reads.  The two-rank run puts both ranks on device 0 with gloo (bench.py's
-PFQ_BENCH_SAME_GPU rehearsal), so the reduction of the counts over the ranks is exercised on a one-GPU box."""
+PFQ_BENCH_SAME_GPU rehearsal), so the reduction of the counts over the ranks is exercised on a one-GPU box.  A --full
+run must compute what a plain run computes and add its extra rates and checks."""
 import json
 import os
 import signal
@@ -68,3 +69,37 @@ def test_dump_outputs(gpu, tmp_path, world):
     assert (last >= expect).all()
     assert last.sum() - expect.sum() <= 64
     assert (total >= last).all() and total.sum() > last.sum()
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"])
+    assert bench.parse_args().full is True
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world", [1, 2])
+def test_full_run_checks_and_matches_plain(gpu, tmp_path, world):
+    """--full adds the extra rates, the CPU baseline and the checks; the timed steps compute the same as a plain run's."""
+    env = {k: v for k, v in os.environ.items() if k not in bench.EXPERIMENT_VARS}
+    if world > 1:
+        env["PFQ_BENCH_SAME_GPU"] = "1"
+    common = ["--gpus", str(world), "--steps", str(STEPS), "--warmup", str(WARMUP), "--leaves", str(LEAVES),
+              "--reads-per-step", str(READS), "--cpu-seconds", "1"]
+    lines = {}
+    for mode in ("plain", "full"):
+        rc, out, err = _bench(common + ["--dump-outputs", str(tmp_path / mode)] + (["--full"] if mode == "full" else []), env)
+        assert rc == 0, err[-3000:]
+        lines[mode] = json.loads(out.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    extras = ("parity", "cpu_baseline", "host_buffers_reads_per_s", "want_hits_reads_per_s")
+    assert not any(k in plain for k in extras)
+    assert full["parity"]["oracle_sample"] == "ok" and full["parity"]["timed_region_ground_truth"] == "ok"
+    if world == 1:
+        assert full["cpu_baseline"]["value"] > 0
+        assert full["host_buffers_reads_per_s"] > 0 and full["want_hits_reads_per_s"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "hits_total"):
+        assert plain[k] == full[k], k
+    for name in ("leaf_counts_last_step", "leaf_counts"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy"))

@@ -12,7 +12,7 @@ tools/gpu_profile.sh r03_bench > $o/r03_bench_profile.log 2>&1 || { tail -5 $o/r
 python3 tools/pmc_traffic.py $o/r03_bench_tcc 8388608 1024 1.0 $o/r03_pmc_traffic.json > $o/r03_pmc_traffic.log 2>&1 || { tail -3 $o/r03_pmc_traffic.log; }
 rm -rf $o/r03_bench_tcc
 cp $o/r03_pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $o/r03_bench.json 2> $o/r03_bench.err || { tail -5 $o/r03_bench.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > $o/r03_bench.json 2> $o/r03_bench.err || { tail -5 $o/r03_bench.err; exit 1; }
 fi
 step "harness geometry: kernel trace + PMC (theta 0.3, theta 1)"
 H="--leaves 10010 --nbits 11981322 --hashes 17 --k 20 --read-len 100"
@@ -27,7 +27,7 @@ rm -rf $o/r03_theta03_errors_tcc
 tools/gpu_scen.sh r03s t1 t1e t03 t03e t07e fam4 fam8 fam8t03 fam8t03e fam8t07e fam4t03 l64 l2048 l4096 long1k harness harness03 > $o/r03_scenarios.txt 2>&1 || { tail -5 $o/r03_scenarios.txt; exit 1; }
 cat $o/r03_scenarios.txt; }
 step "config 5: one shard"
-timeout -k 10 280 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --subtree-depth 3 --subtree-index 5 --leaves 16384 > $o/r03_config5_one_shard.json 2> $o/r03_config5_one_shard.err || { tail -3 $o/r03_config5_one_shard.err; exit 1; }
+timeout -k 10 280 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --full --subtree-depth 3 --subtree-index 5 --leaves 16384 > $o/r03_config5_one_shard.json 2> $o/r03_config5_one_shard.err || { tail -3 $o/r03_config5_one_shard.err; exit 1; }
 step "build"
 python tools/build_bench.py --genomes 1024 > $o/r03_build_1024.json 2>/dev/null; tail -1 $o/r03_build_1024.json | cut -c1-300
 step "CLI"

@@ -6,7 +6,7 @@ o=gpurun_out; mkdir -p $o
 run() {  # name, env..., -- args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 280 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 "$@" > $o/${tag}_$name.json 2> $o/${tag}_$name.err || { echo "$name FAILED"; tail -3 $o/${tag}_$name.err; return 1; }
+  env "${envs[@]}" timeout -k 10 280 python bench.py --steps 5 --warmup 2 --cpu-seconds 0 --full "$@" > $o/${tag}_$name.json 2> $o/${tag}_$name.err || { echo "$name FAILED"; tail -3 $o/${tag}_$name.err; return 1; }
   python - <<PY
 import json
 d=json.loads([l for l in open("$o/${tag}_$name.json") if l.startswith("{")][-1])

@@ -35,7 +35,7 @@ def main() -> None:
         for r in csv.DictReader(open(f)):
             rows[(int(r["Dispatch_Id"]), r["Kernel_Name"])][r["Counter_Name"]] = float(r["Counter_Value"])
     # the dispatches of the LAST bucketed step: from the last k_classify<true, ...> (the deferring build) launch group up to
-    # the next k_classify of any kind (bench.py ends with a small parity query on the direct kernel)
+    # the next k_classify of any kind (a --full run of bench.py ends with a small parity query on the direct kernel)
     disp = sorted(rows.items())
     is_cls = ["k_classify" in k for (_, k), _ in disp]
     last_start = max(i for i, ((_, k), _) in enumerate(disp) if "k_classify<true" in k and (i == 0 or not is_cls[i - 1]))
