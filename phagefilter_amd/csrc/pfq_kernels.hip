@@ -1967,8 +1967,11 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
             r.qb = (((unsigned long long)m.y << 32) | m.x) + (lane == 0 ? koff : 0ull) - (unsigned long long)(incl - n_l);
             return r;
         };
+        // Unconditional, clamped into the chunk (compose reads only the candidates' lanes): behind a branch hipcc consumed
+        // the value inside the branch and waited vmcnt(0) there, for the round's record loads and the last flush's stores too.
         auto load_meta = [&](uint32_t p) {
-            return (lane < ROUND_PAIRS && p + lane < dsc.n) ? a.meta[dsc.first + p + lane] : make_uint4(0, 0, 0, 0);
+            const uint32_t i = p + lane % ROUND_PAIRS;
+            return a.meta[dsc.first + (i < dsc.n ? i : dsc.n - 1u)];
         };
         // the records of a round's windows of this wave: WPI windows of 64 flattened k-mers, window u = wave + u * BIN_WAVES
         auto load_recs = [&](const Round &r, uint4 (&rec)[WPI], uint32_t (&local)[WPI], bool (&valid)[WPI]) {
@@ -1990,9 +1993,22 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
                         qb = qn;
                     }
                 }
-                rec[u] = valid[u] ? a.recs[qb + f] : make_uint4(0, 0, 0, 0);  // (no k-mer: every index 0, see `put`)
+                // (unconditional, like load_meta: a lane without a k-mer loads the record at lane 0's qb — the round's first
+                // k-mer, or the first of the chunk's last pair — and `settle` zeroes it)
+                rec[u] = a.recs[valid[u] ? qb + f : bcast_u64(r.qb, 0)];
                 local[u] = (COUNTS ? f : r.p + j) << TL;
             }
+        };
+        // Takes loaded records and metadata over: the asm makes the values live HERE (a plain copy is only a renaming, and the
+        // wait would sink to the first use, behind younger bucket stores); a lane without a k-mer gets the zero record
+        // (every index 0, see `put`).
+        auto settle = [&](uint4 (&rec)[WPI], const bool (&valid)[WPI], uint4 &m) {
+#pragma unroll
+            for (uint32_t u = 0; u < WPI; ++u) {
+                asm volatile("" : "+v"(rec[u].x), "+v"(rec[u].y), "+v"(rec[u].z), "+v"(rec[u].w));
+                if (!valid[u]) rec[u] = make_uint4(0, 0, 0, 0);
+            }
+            asm volatile("" : "+v"(m.x), "+v"(m.y), "+v"(m.z));
         };
         // Software pipeline over the rounds: while round r is binned, the records of round r + 1 and the pair metadata of
         // round r + 2 are in flight (all waves of the block move in step, so a load issued where it is needed would expose
@@ -2007,6 +2023,7 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
             const uint32_t p1 = cur.partial ? cur.p : cur.p + cur.P;
             m_nxt = load_meta(p1);
         }
+        settle(rec, valid, m_nxt);  // (nothing may enter the round loop pending: its first use would wait there every round)
         uint32_t rho = 0, k0 = 0;  // COUNTS: number of this round; chunk position of its first k-mer
         while (cur.p < dsc.n) {
             if (COUNTS) {
@@ -2072,10 +2089,12 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
                 }
             }
             lds_barrier();  // every probe of the round is in its bin
-            // (the next round's records are taken over BEFORE the bucket stores are issued: waiting for them afterwards would
-            // also wait for every store, which are younger in the same counter)
+            // (the next round's records and the metadata of the round after it are taken over BEFORE the bucket stores are
+            // issued: waiting for them afterwards would also wait for every store, which are younger in the same counter —
+            // this way the stores drain while the next round bins)
             const uint32_t flush_p = cur.p, flush_P = cur.P, flush_K = cur.K;
             cur = nxt;
+            settle(rec_n, valid_n, m_nxt);
 #pragma unroll
             for (uint32_t u = 0; u < WPI; ++u) {
                 rec[u] = rec_n[u];
