@@ -249,6 +249,11 @@ typedef struct pfq_stats {
     uint32_t tile_bin_build;    /* build of k_tile_bin the LDS-tile passes of this call ran: waves << 16 | bin capacity
                                  * (e.g. 16 << 16 | 512, 8 << 16 | 128); 0: no pass ran */
     uint64_t group_reads;       /* (read, leaf group) combinations the coarse level let through to the leaf level */
+    uint32_t pair_stage;        /* bucketed path, between classify and the certificates.  Bits 0-1: how the pairs were sorted by leaf —
+                                 * 1: slices of slots counted in an LDS histogram, one global atomic per bucket and slice;
+                                 * 2: one global atomic per pair (more buckets than LDS holds).  Bits 4-6: the shapes of
+                                 * last-window pass that served at least one pair — 0x10: sixteen reads x 4 k-mers,
+                                 * 0x20: four x 16, 0x40: two x 32 (none: no last window was left to the batched kernel) */
 } pfq_stats;
 int pfq_last_stats(pfq_tree *tree, pfq_stats *out);
 /* Force a query path: -1 auto, 0 direct, 1 bucketed. */

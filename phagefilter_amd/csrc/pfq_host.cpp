@@ -214,7 +214,7 @@ struct pfq_tree {
     // reduced: the reductions over replicas / ranks add up counters - base, so that stored counts are not added once per replica
     DevBuf<unsigned long long> d_counts_base, d_counts_delta;
     // ---- query scratch
-    DevBuf<unsigned long long> d_stats, d_cursors;  // cursors: [0] hit, [1] pair, [2] tile entries, [3] lo: chunks, hi: flagged pairs, [4] long reads, [5] miss words, [6] dirty pairs, [7] lo: open pairs after the tile passes (thresholds < 1), [8] guard pairs, [9] k-mer miss bytes handed out
+    DevBuf<unsigned long long> d_stats, d_cursors;  // cursors: [0] hit, [1] pair, [2] tile entries, [3] lo: chunks, hi: flagged pairs, [4] long reads, [5] miss words, [6] dirty pairs, [7] lo: open pairs after the tile passes (thresholds < 1), [8] guard pairs, [9] k-mer miss bytes handed out, [10] tail shapes that served a pair (pfq::TAIL_SHAPE_*)
     DevBuf<uint32_t> d_entries, d_pair_chunk, d_leaf_chunk0, d_flag_list;  // LDS-tile certificates
     DevBuf<pfq::ChunkDesc> d_chunks;
     DevBuf<unsigned int> d_gfill, d_binq;
@@ -227,6 +227,7 @@ struct pfq_tree {
     uint32_t last_block_mode = 0;
     DevBuf<uint32_t> d_round_k0, d_n_rounds, d_pair_kpos;  // thresholds < 1: LDS-tile passes with k-mer entries
     uint32_t last_tile_mode = 0, last_passes = 1;
+    uint32_t last_sort = 0;            // kernel the last call sorted its pairs with (pfq::SORT_SLICED / SORT_PER_PAIR); 0: direct path
     uint32_t last_tile_bin = 0;        // build of k_tile_bin the last call launched (waves << 16 | bin capacity); 0: no pass
     DevBuf<uint2> d_hit_pairs, d_pairs, d_sorted;
     DevBuf<uint32_t> d_bucket, d_fail;  // bucket: cnt[n], off[n+1], cur[n]
@@ -999,6 +1000,7 @@ struct QueryRun {
         }
         if (bucketed && kn.miss_words >= 0) miss_cap = std::min<uint64_t>(miss_cap, (uint64_t)kn.miss_words);
         t.last_path = bucketed ? 1 : 0;
+        t.last_sort = 0;
         if (!bucketed) t.last_tile_mode = t.last_tile_bin = 0;  // (the direct path runs no tile pass)
         hit_cap = t.d_hit_pairs.n;
         if (kn.hit_slots >= 0) hit_cap = std::min<uint64_t>(hit_cap, (uint64_t)kn.hit_slots);  // (first attempt only, see read_hits)
@@ -1291,7 +1293,7 @@ struct QueryRun {
             ga.gfail = t.d_gfail.p;
             pfq::launch_expand_guards(a, ga, 2048, st);
         }
-        if (a.batch_tails) pfq::launch_tail_records(a, 2048, st);
+        if (a.batch_tails) pfq::launch_tail_records(a, reinterpret_cast<unsigned int *>(t.d_cursors.p + 10), 2048, st);
         if (ev) HIP_TRY(hipEventRecord(ev[1], st));
         return PFQ_OK;
     }
@@ -1299,17 +1301,17 @@ struct QueryRun {
     int bucket_sort() {
         pfq::launch_bucket_scan(cnt, off, cur, (uint32_t)nb, st);
         if (counts_mode && !block_mode) pfq::launch_bucket_scan(cntw, offw, curw, (uint32_t)nb, st);
-        pfq::launch_bucket_scatter(t.d_pairs.p, t.d_cursors.p + 1, a.pair_cap, off, cur, sub_log2, t.d_sorted.p,
-                                   recs ? t.d_meta.p : nullptr, d_off, block_mode ? nullptr : t.d_col_row.p, offw, curw,
-                                   (counts_mode && !block_mode) ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
-                                   (with_guards && !block_mode) ? t.d_owner.p : nullptr,
-                                   (with_guards && !block_mode) ? t.d_owner_sorted.p : nullptr,
-                                   block_mode ? 2u : 0u, 1024, st);
-        if (with_guards && !block_mode)
-            pfq::launch_bucket_scatter(ga.pairs, ga.cursor, ga.cap, off, cur, sub_log2, t.d_sorted.p,
+        t.last_sort = pfq::launch_bucket_scatter(t.d_pairs.p, t.d_cursors.p + 1, a.pair_cap, off, cur, (uint32_t)nb, sub_log2, t.d_sorted.p,
+                                                 recs ? t.d_meta.p : nullptr, d_off, block_mode ? nullptr : t.d_col_row.p, offw, curw,
+                                                 (counts_mode && !block_mode) ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
+                                                 (with_guards && !block_mode) ? t.d_owner.p : nullptr,
+                                                 (with_guards && !block_mode) ? t.d_owner_sorted.p : nullptr,
+                                                 block_mode ? 2u : 0u, st);
+        if (with_guards && !block_mode)  // (the guard pairs reserve on the same cursors)
+            pfq::launch_bucket_scatter(ga.pairs, ga.cursor, ga.cap, off, cur, (uint32_t)nb, sub_log2, t.d_sorted.p,
                                        recs ? t.d_meta.p : nullptr, d_off, t.d_col_row.p, offw, curw,
                                        counts_mode ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
-                                       t.d_owner.p + t.leaf_cap, t.d_owner_sorted.p, 0u, 256, st);
+                                       t.d_owner.p + t.leaf_cap, t.d_owner_sorted.p, 0u, st);
         if (ev) HIP_TRY(hipEventRecord(ev[2], st));
         return PFQ_OK;
     }
@@ -2857,8 +2859,9 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
     out->tile_mode = t.last_tile_mode;
     out->tile_bin_build = t.last_tile_bin;
     if (t.d_cursors.p) {
-        unsigned long long c[4];
+        unsigned long long c[11];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
+        out->pair_stage = t.last_sort | (t.last_path ? (uint32_t)c[10] << 4 : 0u);
         out->n_chunks = (uint32_t)c[3];
         out->n_fallback_pairs = (uint32_t)(c[3] >> 32);
         out->tile_entries = c[2];

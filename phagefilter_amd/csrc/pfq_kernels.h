@@ -269,16 +269,21 @@ void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st);
 
 // launches (all asynchronous on `st`)
 void launch_classify(const QueryArgs &a, bool defer, bool counts_mode, int blocks, hipStream_t st);
-void launch_tail_records(const QueryArgs &a, int blocks, hipStream_t st);  // after launch_classify when a.batch_tails
+// after launch_classify when a.batch_tails; ORs into *shapes which passes served a pair: TAIL_SHAPE_4 / _16 / _32
+constexpr uint32_t TAIL_SHAPE_4 = 1, TAIL_SHAPE_16 = 2, TAIL_SHAPE_32 = 4;
+void launch_tail_records(const QueryArgs &a, unsigned int *shapes, int blocks, hipStream_t st);
 void launch_bucket_scan(const uint32_t *bucket_cnt, uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t n, hipStream_t st);
 // words_off / words_cur / miss_pos: thresholds < 1 (miss words of a bucket start at words_off[bucket]); else nullptr
 // key_mode 0: the bucket of a pair is its column; 1 (block mode): the block = low 24 bits of its second word, which goes to
 // meta.w whole; 2 (block mode with k-mer entries): (block << 8) | candidate mask
-void launch_bucket_scatter(const uint2 *pairs, const unsigned long long *n_pairs_ptr, uint64_t pair_cap,
-                           const uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t sub_log2, uint2 *sorted, uint4 *meta,
-                           const uint64_t *read_off, const uint32_t *col_row, const uint32_t *words_off, uint32_t *words_cur,
-                           uint32_t *miss_pos, uint32_t kmer_size, const uint32_t *owner, uint32_t *owner_sorted, uint32_t key_mode,
-                           int blocks, hipStream_t st);
+// Returns the kernel the bucket count selected: SORT_SLICED (an LDS histogram per slice of slots, one global atomic per
+// bucket and slice) or SORT_PER_PAIR (more buckets than LDS holds: one global atomic per pair).
+constexpr uint32_t SORT_SLICED = 1, SORT_PER_PAIR = 2;
+uint32_t launch_bucket_scatter(const uint2 *pairs, const unsigned long long *n_pairs_ptr, uint64_t pair_cap,
+                               const uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t n_buckets, uint32_t sub_log2, uint2 *sorted,
+                               uint4 *meta, const uint64_t *read_off, const uint32_t *col_row, const uint32_t *words_off,
+                               uint32_t *words_cur, uint32_t *miss_pos, uint32_t kmer_size, const uint32_t *owner,
+                               uint32_t *owner_sorted, uint32_t key_mode, hipStream_t st);
 // block tables: T[b][i] = byte whose bit j is bit i of the filter of leaf column 8b + j (zero for columns past the last leaf)
 void launch_block_tables(const uint64_t *bits, uint64_t n_words, const uint32_t *d_col_row, uint32_t n_leaves, uint8_t *T, hipStream_t st);
 // block mode: flagged pairs (fail bit 1) certified leaf by leaf against the sliced matrix; then the counts / hits of all pairs

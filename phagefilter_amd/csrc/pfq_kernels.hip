@@ -663,8 +663,9 @@ __device__ __forceinline__ void dense_counts(uint32_t *fw, uint32_t *rw_, const 
     }
 }
 
-// A read's last window of records is made by k_tail_records when it holds at most tail_max k-mers (16: four reads per pass;
-// 32: two — the host asks for 32 when the reads' length makes such tails, e.g. 100 bp reads at k = 20: 81 = 64 + 17 k-mers).
+// A read's last window of records is made by k_tail_records when it holds at most tail_max k-mers (up to 4: sixteen reads per
+// pass, up to 16: four, up to 32: two — the host asks for 32 when the reads' length makes such tails, e.g. 100 bp reads at
+// k = 20: 81 = 64 + 17 k-mers).
 __device__ __forceinline__ bool has_batched_tail(uint64_t n, uint32_t tail_max) {
     const uint32_t tl = (uint32_t)(n & (WIN_KMERS - 1u));
     return n > WIN_KMERS && n < (1ull << 32) && tl != 0 && tl <= tail_max;
@@ -818,7 +819,7 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
                     if (a.recs && !prepared) {  // hash the read once; every slice of the verify reuses the records
                         prepared = true;
                         // 150 bp reads at k = 20..23 have 128 + (1..3) k-mers: a third hashing pass for two or three
-                        // k-mers.  Such last windows are left to k_tail_records (four reads per pass).
+                        // k-mers.  Such last windows are left to k_tail_records (several reads per pass).
                         const bool split_tail = a.batch_tails && has_batched_tail(rc.n, a.batch_tails);
                         for (uint64_t base = n_done; base < rc.n; base += WIN_KMERS) {
                             uint32_t cnt = (uint32_t)((rc.n - base) < WIN_KMERS ? (rc.n - base) : WIN_KMERS);
@@ -1300,27 +1301,78 @@ void launch_expand_guards(const QueryArgs &a, const GuardArgs &ga, int blocks, h
     hipLaunchKernelGGL(k_expand_guards, dim3(blocks), dim3(256), 0, st, a, ga);
 }
 
-// Records of the last windows k_classify<DEFER> left out (has_batched_tail): one pass serves 64 / TAIL deferred pairs,
-// lane = (pair j, k-mer t of up to TAIL); the TAIL = 32 build takes the tails of 17 .. 32 k-mers, the TAIL = 16 build the
-// shorter ones.  Walks the deferred-pair buffer; a read deferred for two leaves gets its tail records written twice (same
-// values).
+constexpr uint32_t TAIL_LDS_BYTES = DENSE_READS * MINI_BYTES + 2u * WIN_PAD;  // per wave and direction: sixteen mini windows
+// Records of the last windows k_classify<DEFER> left out (has_batched_tail).  One hashing pass serves 64 / TAIL pairs, lane =
+// (pair j, k-mer t of up to TAIL): sixteen pairs with tails of up to 4 k-mers (150 bp reads at k = 20 .. 23 have 1 .. 3: the
+// shape of dense_screen's mini windows), four with up to 16, two with up to 32.  `have`, o0 (the read's byte offset) and n
+// (its k-mers) are those of the lane's pair.
 template <uint32_t TAIL>
-__global__ void __launch_bounds__(256) k_tail_records(QueryArgs a) {
-    constexpr uint32_t PAIRS = 64u / TAIL, STRIDE = 384u / PAIRS, LOADS = (TAIL + KMAX - 1u + TAIL - 1u) / TAIL;  // bytes per pair in LDS; byte loads per lane
+__device__ __forceinline__ void tail_pass(const QueryArgs &a, uint32_t *tfw, uint32_t *trc, const uint8_t *s_comp, bool have,
+                                          uint64_t o0, uint32_t n) {
+    // bytes per pair in LDS; byte loads per lane and batch (TAIL = 4: batches of six, as many as k asks for)
+    constexpr uint32_t STRIDE = TAIL == 4u ? MINI_BYTES : 6u * TAIL, BATCH = TAIL == 4u ? 6u : (TAIL + KMAX - 1u + TAIL - 1u) / TAIL;
     static_assert(WIN_PAD + TAIL + KMAX - 1u + WIN_PAD <= STRIDE + WIN_PAD, "a tail's bytes fit its share of the LDS");
-    __shared__ uint32_t s_fw[WAVES_PER_BLOCK][4 * 96 / 4 + 4], s_rc[WAVES_PER_BLOCK][4 * 96 / 4 + 4];
-    __shared__ uint8_t s_comp[256];
+    static_assert((64u / TAIL) * STRIDE + 2u * WIN_PAD <= TAIL_LDS_BYTES, "the passes' pairs fit the wave's LDS");
+    const uint32_t lane = lane_id(), k = a.hp.k, j = lane / TAIL, t = lane % TAIL;
+    uint8_t *tfwd = reinterpret_cast<uint8_t *>(tfw), *trcb = reinterpret_cast<uint8_t *>(trc);
+    const uint32_t tl = n & (WIN_KMERS - 1u);
+    const uint64_t base = n - tl;
+    const uint32_t W = have ? tl + k - 1u : 0u;  // <= TAIL + KMAX - 1 bytes
+    const uint32_t mb = j * STRIDE + WIN_PAD;
+    const uint8_t *src = a.seq + (have ? o0 + base : 0ull);
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t i0 = 0; i0 < TAIL + k - 1u; i0 += BATCH * TAIL) {  // loads before uses
+        uint8_t b[BATCH];
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; ++u) {
+            const uint32_t idx = i0 + TAIL * u + t;
+            b[u] = src[idx < W ? idx : 0u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < BATCH; ++u) {
+            const uint32_t idx = i0 + TAIL * u + t;
+            if (idx < W) {
+                tfwd[mb + idx] = b[u];
+                trcb[mb + (W - 1u - idx)] = s_comp[b[u]];
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const bool valid = have && t < tl;
+    uint64_t h1, h2;
+    kmer_hashes_at(tfw, trc, mb + t, mb + (W - t - k), valid, a.hp, h1, h2);
+    const uint4 rec = make_probe_record(h1, h2, a.hp);
+    if (valid) a.recs[o0 + base + t] = rec;
+}
+// The pairs of one shape among a wave's 64 slots, 64 / TAIL per pass: list[0 .. cnt) names their lanes, which hold o0 and n.
+template <uint32_t TAIL>
+__device__ __forceinline__ void tail_passes(const QueryArgs &a, uint32_t *tfw, uint32_t *trc, const uint8_t *s_comp,
+                                            const uint8_t *list, uint32_t cnt, uint64_t o0, uint32_t n) {
+    const uint32_t j = lane_id() / TAIL;
+    for (uint32_t p0 = 0; p0 < cnt; p0 += 64u / TAIL) {
+        const bool have = p0 + j < cnt;
+        const int from = have ? (int)list[p0 + j] : 0;
+        const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)o0, from), hi = (uint32_t)__shfl((int)(uint32_t)(o0 >> 32), from);
+        const uint32_t nn = (uint32_t)__shfl((int)n, from);
+        tail_pass<TAIL>(a, tfw, trc, s_comp, have, ((uint64_t)hi << 32) | lo, nn);
+    }
+}
+// Walks the deferred-pair buffer, a wave 64 slots at a time (lane = slot), and sorts the slots' tails by shape, so that a file
+// of trimmed reads keeps every tail length batched and a pass is full whatever the mix.  A read deferred for two leaves gets
+// its tail records written twice (same values).  shapes: bits 0 / 1 / 2 are set when a pass of 4 / 16 / 32 k-mers served a pair.
+__global__ void __launch_bounds__(256) k_tail_records(QueryArgs a, unsigned int *shapes) {
+    __shared__ uint32_t s_fw[WAVES_PER_BLOCK][TAIL_LDS_BYTES / 4], s_rc[WAVES_PER_BLOCK][TAIL_LDS_BYTES / 4];
+    __shared__ uint8_t s_comp[256], s_list[WAVES_PER_BLOCK][3][64];
     fill_complement(s_comp);
     __syncthreads();
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, k = a.hp.k;
-    const uint32_t j = lane / TAIL, t = lane % TAIL;
     unsigned long long n_slots = *a.pair_cursor;
     if (n_slots > a.pair_cap) n_slots = a.pair_cap;
     uint32_t *tfw = s_fw[wave], *trc = s_rc[wave];
-    uint8_t *tfwd = reinterpret_cast<uint8_t *>(tfw), *trcb = reinterpret_cast<uint8_t *>(trc);
     const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave, nw = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
-    for (uint64_t s0 = gw * PAIRS; s0 < n_slots; s0 += nw * PAIRS) {
-        const uint64_t slot = s0 + j;
+    uint32_t used = 0;
+    for (uint64_t s0 = gw * 64u; s0 < n_slots; s0 += nw * 64u) {
+        const uint64_t slot = s0 + lane;
         uint32_t r = 0xffffffffu;
         if (slot < n_slots) r = a.pairs[slot].x;
         uint64_t o0 = 0, n = 0;
@@ -1330,39 +1382,24 @@ __global__ void __launch_bounds__(256) k_tail_records(QueryArgs a) {
             n = (L >= k) ? (L - k + 1) : 0;
         }
         const uint32_t tl = (uint32_t)(n & (WIN_KMERS - 1u));
-        // (tails of up to 16 k-mers belong to the TAIL = 16 build, longer ones to the TAIL = 32 build)
-        const bool have = r != 0xffffffffu && has_batched_tail(n, a.batch_tails) && (TAIL == 16 ? tl <= 16u : tl > 16u) && o0 + n <= a.rec_cap;
-        if (ballot64(have) == 0) continue;
-        const uint64_t base = n - tl;
-        const uint32_t W = have ? tl + k - 1u : 0u;  // <= TAIL + KMAX - 1 bytes
-        const uint32_t mb = j * STRIDE + WIN_PAD;
-        const uint8_t *src = a.seq + (have ? o0 + base : 0ull);
+        const bool have = r != 0xffffffffu && has_batched_tail(n, a.batch_tails) && o0 + n <= a.rec_cap;
+        const uint32_t shape = tl <= 4u ? 0u : (tl <= 16u ? 1u : 2u);
+        const uint64_t m0 = ballot64(have && shape == 0u), m1 = ballot64(have && shape == 1u), m2 = ballot64(have && shape == 2u);
+        if ((m0 | m1 | m2) == 0) continue;
+        const uint64_t mine = shape == 0u ? m0 : (shape == 1u ? m1 : m2);
         __builtin_amdgcn_wave_barrier();
-        uint8_t b[LOADS];
-#pragma unroll
-        for (uint32_t u = 0; u < LOADS; ++u) {
-            const uint32_t idx = TAIL * u + t;
-            b[u] = src[idx < W ? idx : 0u];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < LOADS; ++u) {
-            const uint32_t idx = TAIL * u + t;
-            if (idx < W) {
-                tfwd[mb + idx] = b[u];
-                trcb[mb + (W - 1u - idx)] = s_comp[b[u]];
-            }
-        }
+        if (have) s_list[wave][shape][__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u))] = (uint8_t)lane;
         __builtin_amdgcn_wave_barrier();
-        const bool valid = have && t < tl;
-        uint64_t h1, h2;
-        kmer_hashes_at(tfw, trc, mb + t, mb + (W - t - k), valid, a.hp, h1, h2);
-        const uint4 rec = make_probe_record(h1, h2, a.hp);
-        if (valid) a.recs[o0 + base + t] = rec;
+        tail_passes<4>(a, tfw, trc, s_comp, s_list[wave][0], (uint32_t)__popcll(m0), o0, (uint32_t)n);
+        tail_passes<16>(a, tfw, trc, s_comp, s_list[wave][1], (uint32_t)__popcll(m1), o0, (uint32_t)n);
+        tail_passes<32>(a, tfw, trc, s_comp, s_list[wave][2], (uint32_t)__popcll(m2), o0, (uint32_t)n);
+        used |= (m0 ? 1u : 0u) | (m1 ? 2u : 0u) | (m2 ? 4u : 0u);
     }
+    // (most waves find the bits set already: no wave-count of atomics on one word)
+    if (used && lane == 0 && (*(volatile unsigned int *)shapes & used) != used) atomicOr(shapes, used);
 }
-void launch_tail_records(const QueryArgs &a, int blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_tail_records<16>, dim3(blocks), dim3(256), 0, st, a);
-    if (a.batch_tails > 16u) hipLaunchKernelGGL(k_tail_records<32>, dim3(blocks), dim3(256), 0, st, a);
+void launch_tail_records(const QueryArgs &a, unsigned int *shapes, int blocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_tail_records, dim3(blocks), dim3(256), 0, st, a, shapes);
 }
 
 // ---- bucketing of deferred (read, leaf) pairs by leaf --------------------------------------------------------------
@@ -1391,40 +1428,118 @@ void launch_bucket_scan(const uint32_t *bucket_cnt, uint32_t *bucket_off, uint32
 
 // Scatter into leaf order; `meta` gets everything the record-driven verify needs about a pair in one 16-byte
 // entry (read byte offset, read length, filter row) so that kernel has no dependent metadata loads.
-__global__ void __launch_bounds__(256) k_bucket_scatter(const uint2 *pairs, const unsigned long long *n_pairs_ptr,
-                                                        uint64_t pair_cap, const uint32_t *off, uint32_t *cur, uint32_t sub_log2,
-                                                        uint2 *sorted, uint4 *meta, const uint64_t *read_off,
-                                                        const uint32_t *col_row, const uint32_t *words_off,
-                                                        uint32_t *words_cur, uint32_t *miss_pos, uint32_t kmer_size,
-                                                        const uint32_t *owner, uint32_t *owner_sorted, uint32_t key_mode) {
-    uint64_t n = *n_pairs_ptr;
-    if (n > pair_cap) n = pair_cap;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint2 p = pairs[i];
-        if (p.y == 0xffffffffu) continue;  // voided slot of a partially used reservation
-        // (block mode: p.y = block | mask << 24; keyed by the block, or — k-mer entries — by (block, mask))
-        const uint32_t key = key_mode == 0 ? p.y : (key_mode == 2 ? (((p.y & 0xffffffu) << 8) | (p.y >> 24)) : (p.y & 0xffffffu));
-        const uint32_t bkt = (key << sub_log2) | (p.x & ((1u << sub_log2) - 1u));
-        uint32_t pos = off[bkt] + atomicAdd(&cur[bkt], 1u);
-        sorted[pos] = p;
-        if (owner) owner_sorted[pos] = owner[i];
-        if (meta) {
-            uint64_t o0 = read_off[p.x], L = read_off[p.x + 1] - o0;
-            meta[pos] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)L, key_mode == 0 ? col_row[p.y] : p.y);
-            if (miss_pos) {  // thresholds < 1: the pair's miss words, ceil(n/64) of them, inside its bucket's range
-                const uint32_t words = (uint32_t)((L - kmer_size + 1 + 63) >> 6);
-                miss_pos[pos] = words_off[bkt] + atomicAdd(&words_cur[bkt], words);
+// (block mode: p.y = block | mask << 24; keyed by the block, or — k-mer entries — by (block, mask))
+__device__ __forceinline__ uint32_t pair_bucket(uint2 p, uint32_t key_mode, uint32_t sub_log2) {
+    const uint32_t key = key_mode == 0 ? p.y : (key_mode == 2 ? (((p.y & 0xffffffu) << 8) | (p.y >> 24)) : (p.y & 0xffffffu));
+    return (key << sub_log2) | (p.x & ((1u << sub_log2) - 1u));
+}
+struct ScatterArgs {
+    const uint2 *pairs;
+    const unsigned long long *n_pairs_ptr;
+    uint64_t pair_cap;
+    const uint32_t *off;
+    uint32_t *cur;
+    uint32_t nb, sub_log2, key_mode, kmer_size;
+    uint2 *sorted;
+    uint4 *meta;
+    const uint64_t *read_off;
+    const uint32_t *col_row, *words_off;
+    uint32_t *words_cur, *miss_pos;
+    const uint32_t *owner;
+    uint32_t *owner_sorted;
+};
+__device__ __forceinline__ void place_pair(const ScatterArgs &s, uint2 p, uint64_t i, uint32_t pos) {
+    s.sorted[pos] = p;
+    if (s.owner) s.owner_sorted[pos] = s.owner[i];
+    if (s.meta) {
+        const uint64_t o0 = s.read_off[p.x], L = s.read_off[p.x + 1] - o0;
+        s.meta[pos] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)L, s.key_mode == 0 ? s.col_row[p.y] : p.y);
+    }
+}
+// Up to SORT_LDS_BUCKETS buckets: a block takes slices of SORT_SLICE consecutive slots, counts their keys in LDS, reserves
+// each non-empty bucket's range with ONE global atomic per slice (a returning device-scope atomic per pair on 4 KiB of counters
+// was this kernel's whole time: a line of counters takes ~ 100 of them per microsecond) and places the pairs with LDS
+// atomics on the reserved bases; a slice's pairs of one bucket land next to each other.  The miss words of thresholds < 1
+// are reserved the same way.  The order of pairs inside a bucket is arbitrary, as it always was.
+constexpr uint32_t SORT_THREADS = 512, SORT_PER_THREAD = 16, SORT_SLICE = SORT_THREADS * SORT_PER_THREAD, SORT_LDS_BUCKETS = 4096;
+__global__ void __launch_bounds__(SORT_THREADS) k_bucket_scatter(ScatterArgs s) {
+    __shared__ uint32_t s_pos[SORT_LDS_BUCKETS], s_wpos[SORT_LDS_BUCKETS];
+    uint64_t n = *s.n_pairs_ptr;
+    if (n > s.pair_cap) n = s.pair_cap;
+    const bool miss = s.meta && s.miss_pos;  // thresholds < 1: the pair's miss words, ceil(n/64) of them, inside its bucket's range
+    for (uint64_t s0 = (uint64_t)blockIdx.x * SORT_SLICE; s0 < n; s0 += (uint64_t)gridDim.x * SORT_SLICE) {
+        for (uint32_t b = threadIdx.x; b < s.nb; b += SORT_THREADS) s_pos[b] = s_wpos[b] = 0;
+        __syncthreads();
+        uint2 p[SORT_PER_THREAD];
+        uint32_t words[SORT_PER_THREAD];
+#pragma unroll
+        for (uint32_t u = 0; u < SORT_PER_THREAD; ++u) {
+            const uint64_t i = s0 + u * SORT_THREADS + threadIdx.x;
+            p[u] = i < n ? s.pairs[i] : make_uint2(0xffffffffu, 0xffffffffu);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < SORT_PER_THREAD; ++u) {
+            words[u] = 0;
+            if (p[u].y == 0xffffffffu) continue;  // voided slot of a partially used reservation
+            const uint32_t bkt = pair_bucket(p[u], s.key_mode, s.sub_log2);
+            if (bkt >= s.nb) { p[u].y = 0xffffffffu; continue; }  // (never: k_classify counted the same key)
+            atomicAdd(&s_pos[bkt], 1u);
+            if (miss) {
+                const uint64_t L = s.read_off[p[u].x + 1] - s.read_off[p[u].x];
+                words[u] = (uint32_t)((L - s.kmer_size + 1 + 63) >> 6);
+                atomicAdd(&s_wpos[bkt], words[u]);
             }
+        }
+        __syncthreads();
+        for (uint32_t b = threadIdx.x; b < s.nb; b += SORT_THREADS) {
+            const uint32_t c = s_pos[b];
+            if (c == 0) continue;
+            s_pos[b] = s.off[b] + atomicAdd(&s.cur[b], c);
+            if (miss) s_wpos[b] = s.words_off[b] + atomicAdd(&s.words_cur[b], s_wpos[b]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t u = 0; u < SORT_PER_THREAD; ++u) {
+            if (p[u].y == 0xffffffffu) continue;
+            const uint32_t bkt = pair_bucket(p[u], s.key_mode, s.sub_log2);
+            const uint32_t pos = atomicAdd(&s_pos[bkt], 1u);
+            place_pair(s, p[u], s0 + u * SORT_THREADS + threadIdx.x, pos);
+            if (miss) s.miss_pos[pos] = atomicAdd(&s_wpos[bkt], words[u]);
+        }
+        __syncthreads();
+    }
+}
+// More buckets than an LDS histogram holds (block mode: blocks x 256 masks; trees of more than SORT_LDS_BUCKETS columns): one
+// global atomic per pair; the counters are many lines then.
+__global__ void __launch_bounds__(256) k_bucket_scatter_wide(ScatterArgs s) {
+    uint64_t n = *s.n_pairs_ptr;
+    if (n > s.pair_cap) n = s.pair_cap;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint2 p = s.pairs[i];
+        if (p.y == 0xffffffffu) continue;  // voided slot of a partially used reservation
+        const uint32_t bkt = pair_bucket(p, s.key_mode, s.sub_log2);
+        const uint32_t pos = s.off[bkt] + atomicAdd(&s.cur[bkt], 1u);
+        place_pair(s, p, i, pos);
+        if (s.meta && s.miss_pos) {
+            const uint64_t L = s.read_off[p.x + 1] - s.read_off[p.x];
+            s.miss_pos[pos] = s.words_off[bkt] + atomicAdd(&s.words_cur[bkt], (uint32_t)((L - s.kmer_size + 1 + 63) >> 6));
         }
     }
 }
-void launch_bucket_scatter(const uint2 *pairs, const unsigned long long *n_pairs_ptr, uint64_t pair_cap,
-                           const uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t sub_log2, uint2 *sorted, uint4 *meta,
-                           const uint64_t *read_off, const uint32_t *col_row, const uint32_t *words_off, uint32_t *words_cur,
-                           uint32_t *miss_pos, uint32_t kmer_size, const uint32_t *owner, uint32_t *owner_sorted, uint32_t key_mode,
-                           int blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_bucket_scatter, dim3(blocks), dim3(256), 0, st, pairs, n_pairs_ptr, pair_cap, bucket_off, bucket_cur,
-                       sub_log2, sorted, meta, read_off, col_row, words_off, words_cur, miss_pos, kmer_size, owner, owner_sorted, key_mode);
+uint32_t launch_bucket_scatter(const uint2 *pairs, const unsigned long long *n_pairs_ptr, uint64_t pair_cap,
+                               const uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t n_buckets, uint32_t sub_log2, uint2 *sorted,
+                               uint4 *meta, const uint64_t *read_off, const uint32_t *col_row, const uint32_t *words_off,
+                               uint32_t *words_cur, uint32_t *miss_pos, uint32_t kmer_size, const uint32_t *owner,
+                               uint32_t *owner_sorted, uint32_t key_mode, hipStream_t st) {
+    ScatterArgs s{pairs, n_pairs_ptr, pair_cap, bucket_off, bucket_cur, n_buckets, sub_log2, key_mode, kmer_size, sorted, meta,
+                  read_off, col_row, words_off, words_cur, miss_pos, owner, owner_sorted};
+    if (n_buckets <= SORT_LDS_BUCKETS) {
+        const uint64_t slices = (pair_cap + SORT_SLICE - 1) / SORT_SLICE;
+        hipLaunchKernelGGL(k_bucket_scatter, dim3((uint32_t)std::min<uint64_t>(std::max<uint64_t>(slices, 1), 4096)), dim3(SORT_THREADS), 0, st, s);
+        return SORT_SLICED;
+    }
+    hipLaunchKernelGGL(k_bucket_scatter_wide, dim3((uint32_t)std::min<uint64_t>((pair_cap + 4095) / 4096 + 1, 1024)), dim3(256), 0, st, s);
+    return SORT_PER_PAIR;
 }
 
 // ---- K2 for bucketed survivors: L2-resident filter slices ------------------------------------------------------------

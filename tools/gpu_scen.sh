@@ -1,5 +1,5 @@
 #!/bin/bash
-# Scenario lines of bench.py (kernel times per step).  Usage: tools/gpu_scen.sh <tag> <scenario>...   scenarios: t1 t1e t03 t03e t07e fam4 fam8 fam8t03 harness harness03
+# Scenario lines of bench.py (kernel times per step).  Usage: tools/gpu_scen.sh <tag> <scenario>...   scenarios: t1 t1e t03 t03e t07e fam4 fam8 fam8t03 harness harness03 rl153 rl165
 set -o pipefail
 tag=$1; shift
 o=gpurun_out; mkdir -p $o
@@ -32,6 +32,8 @@ fam4t03) run fam4t03 PFQ_BENCH_FAMILY=4 -- --threshold 0.3 ;;
 l64) run l64 X=1 -- --leaves 64 ;;
 l2048) run l2048 X=1 -- --leaves 2048 ;;
 l4096) run l4096 X=1 -- --leaves 4096 ;;
+rl153) run rl153 X=1 -- --read-len 153 ;;  # last windows of 5 k-mers at k = 21 (the 4 x 16 shape), rl165: of 17 (2 x 32)
+rl165) run rl165 X=1 -- --read-len 165 ;;
 long1k) run long1k X=1 -- --read-len 1000 --reads-per-step 1048576 --threshold 0.5 ;;
 harness) run harness X=1 -- --leaves 10010 --nbits 11981322 --hashes 17 --k 20 --read-len 100 ;;
 harness03) run harness03 PFQ_BENCH_PARITY_READS=500 -- --leaves 10010 --nbits 11981322 --hashes 17 --k 20 --read-len 100 --threshold 0.3 ;;
