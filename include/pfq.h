@@ -69,6 +69,16 @@ typedef struct pfq_hits {
  * the fragment kernels are queued. */
 #define PFQ_PAIRED 4u
 #define PFQ_PAIR_BOTH 8u /* only together with PFQ_PAIRED, alone: PFQ_ERR_ARG */
+/* Lowest common ancestor: every unit of the call (a read; with PFQ_PAIRED a fragment) is also assigned to the deepest clade
+ * that is an ancestor-or-self of every leaf of its hit set — exactly the row pfq_hits gives for it (pfq_last_lca), and that
+ * clade's counter grows by one (pfq_clade_counts).  Combines with every other flag and changes none of their results.  Without
+ * PFQ_WANT_HITS the call returns once the hit list is checked and the LCA kernels are queued.  Subtree shards:
+ * PFQ_ERR_UNSUPPORTED (a shard does not hold the other shards' topology). */
+#define PFQ_WANT_LCA 16u
+/* The LCA is taken over the hits whose score (pfq_last_hit_scores) is the unit's highest; ties stay ambiguous.  Only together
+ * with PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES, else PFQ_ERR_ARG. */
+#define PFQ_LCA_BEST 32u
+#define PFQ_NO_CLADE 0xffffffffu /* pfq_last_lca: the unit hit nothing */
 
 /* ---- database ---- */
 
@@ -177,6 +187,30 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
  * PFQ_WANT_SCORES.  Library-owned; valid until the next query call on the tree. */
 int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits);
 
+/* ---- clades (PFQ_WANT_LCA) ----
+ * The clades of a tree are the nodes reachable from its root as the tree currently is (after pfq_tree_prune, after
+ * pfq_tree_insert), numbered in pre-order: node, left subtree, right subtree; the root is clade 0.  The index is the identity
+ * of a clade; names may collide (the reference names internal nodes "Internal_Node_<random u16>"). */
+typedef struct pfq_clade {
+    uint32_t parent;     /* clade index; PFQ_NO_CLADE for the root */
+    uint32_t depth;      /* edges from the root */
+    uint32_t first_leaf; /* the clade's leaves are columns [first_leaf, first_leaf + n_leaves) of pfq_leaf_counts */
+    uint32_t n_leaves;
+    const char *name;    /* the node's tax_id; without one, its .bf file name without the suffix */
+} pfq_clade;
+/* The clade table: library-owned, valid until the topology next changes (pfq_tree_insert, pfq_tree_prune). */
+int pfq_tree_clades(pfq_tree *tree, const pfq_clade **clades, uint64_t *n);
+/* Per clade, here[c] = units whose LCA is c, accumulated over the PFQ_WANT_LCA calls like the leaf counters, and below[c] =
+ * the sum of here over c's subtree (below[0] = units that hit anything).  They start at zero when a tree is opened or
+ * created, are not stored by pfq_tree_save, and are zeroed by pfq_leaf_counts_reset, pfq_tree_prune and pfq_tree_insert.  A
+ * block whose hit buffer overflowed and ran again counts once.  Waits for the device like pfq_leaf_counts.  Library-owned. */
+int pfq_clade_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **below, uint64_t *n);
+/* One clade index (or PFQ_NO_CLADE) per unit of the last query call on `tree`, which must have set PFQ_WANT_LCA (else
+ * PFQ_ERR_ARG); n_units = n_reads, with PFQ_PAIRED n_reads / 2.  Waits for that call.  A unit that hits every leaf (no k-mers,
+ * threshold <= 0, all-leaf fragments) gets the LCA of all leaves: the root, or below a root with one child the deepest node
+ * of that chain.  Library-owned; valid until the next query call on the tree. */
+int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units);
+
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);
 /* save_leaf_counts (query.rs:173-183): "<tax_id>,<count>\n" for count > 0, no header. */
@@ -223,7 +257,8 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value);
  * [3] its cap, [4] k-mer miss-word cursor, [5] its cap, [6] tile-mode miss bytes handed out (saturates at the cap),
  * [7] its cap, [8] hit cursor of the first attempt, [9] its hit cap, [10] attempts (2: the hit buffer overflowed and the
  * block ran again), [11] pairs sorted into the buckets.  A cursor above its cap: that buffer overflowed, the rest was
- * certified inline.  Pair values are 0 on the direct path; hit values are 0 without PFQ_WANT_HITS / PFQ_PAIRED. */
+ * certified inline.  Pair values are 0 on the direct path; hit values are 0 without PFQ_WANT_HITS / PFQ_PAIRED /
+ * PFQ_WANT_LCA. */
 #define PFQ_CAPACITY_N 12
 int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n);
 

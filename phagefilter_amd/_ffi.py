@@ -14,6 +14,7 @@ SYMBOLS = [
     "pfq_tree_open", "pfq_tree_open_subtree", "pfq_db_shard_count", "pfq_tree_create", "pfq_tree_insert", "pfq_tree_build_balanced", "pfq_tree_build_balanced_device",
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
+    "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
@@ -55,10 +56,18 @@ class Profile(C.Structure):
                 ("test_ms", C.c_double), ("verify_ms", C.c_double), ("finalize_ms", C.c_double)]
 
 
+class Clade(C.Structure):
+    _fields_ = [("parent", C.c_uint32), ("depth", C.c_uint32), ("first_leaf", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("name", C.c_char_p)]
+
+
 WANT_HITS = 1
 WANT_SCORES = 2
 PAIRED = 4
 PAIR_BOTH = 8
+WANT_LCA = 16
+LCA_BEST = 32
+NO_CLADE = 0xFFFFFFFF
 _lib = None
 
 
@@ -100,6 +109,9 @@ def lib() -> C.CDLL:
     L.pfq_query_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_query_batch_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, vp, C.POINTER(Hits)]
     L.pfq_last_hit_scores.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), u64p]
+    L.pfq_tree_clades.argtypes = [vp, C.POINTER(C.POINTER(Clade)), u64p]
+    L.pfq_clade_counts.argtypes = [vp, C.POINTER(u64p), C.POINTER(u64p), u64p]
+    L.pfq_last_lca.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), u64p]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

@@ -1088,6 +1088,41 @@ struct ServedDb {
         }
         if (fclose(f) != 0) die("short write to " + csv);
     }
+    // --lca: the clade names (READ_LCA.tsv), from replica 0: the replicas hold one tree
+    std::vector<std::string> clade_names;
+    void load_clade_names() {
+        const pfq_clade *cl = nullptr;
+        uint64_t n = 0;
+        check(pfq_tree_clades(trees[0], &cl, &n));
+        for (uint64_t c = 0; c < n; ++c) clade_names.push_back(cl[c].name);
+    }
+    // --lca: CLADE_COUNTS.tsv.  Every replica counted its own reads: their `here` are summed on the host (a few KB) and
+    // `below` is the sum over each clade's subtree (pre-order: children come after their parent).
+    void save_clade_counts(const std::string &tsv) {
+        const pfq_clade *cl = nullptr;
+        uint64_t n = 0;
+        check(pfq_tree_clades(trees[0], &cl, &n));
+        std::vector<uint64_t> here(n, 0);
+        for (pfq_tree *t : trees) {
+            const uint64_t *h = nullptr;
+            uint64_t nh = 0;
+            check(pfq_clade_counts(t, &h, nullptr, &nh));
+            if (nh != n) die("--lca: the replicas' clade tables differ");
+            for (uint64_t c = 0; c < n; ++c) here[c] += h[c];
+        }
+        std::vector<uint64_t> below(here);
+        for (uint64_t c = n; c-- > 1;) below[cl[c].parent] += below[c];
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+        fputs("#clade\tparent\tdepth\tgenomes\tname\treads_here\treads_below\n", f);
+        for (uint64_t c = 0; c < n; ++c) {
+            if (!below[c]) continue;
+            const std::string parent = cl[c].parent == PFQ_NO_CLADE ? "-" : std::to_string(cl[c].parent);
+            fprintf(f, "%llu\t%s\t%u\t%u\t%s\t%llu\t%llu\n", (unsigned long long)c, parent.c_str(), cl[c].depth, cl[c].n_leaves, cl[c].name,
+                    (unsigned long long)here[c], (unsigned long long)below[c]);
+        }
+        if (fclose(f) != 0) die("short write to " + tsv);
+    }
     void close() {
         for (pfq_tree *t : trees) pfq_tree_close(t);
     }
@@ -1106,7 +1141,8 @@ struct OutFile {
 struct Outputs {
     OutFile pos, neg, pos2, neg2;  // --reads2: the mates of R2 go to POS_FILTERING_2 / NEG_FILTERING_2, those of R1 to _1
     FILE *scores = nullptr;        // --scores: READ_SCORES.tsv
-    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores) {
+    FILE *lca = nullptr;           // --lca-reads: READ_LCA.tsv
+    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores, bool want_lca_reads) {
         auto create = [&](OutFile &f, const std::string &name, const char *suffix) {
             if ((f.fd = open((dir + "/" + name + suffix + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
                 die("cannot create " + name + " in " + dir);
@@ -1120,11 +1156,16 @@ struct Outputs {
             if (!(scores = fopen((dir + "/READ_SCORES.tsv").c_str(), "wb"))) die("cannot create READ_SCORES.tsv in " + dir);
             fputs("#read_id\tkmers\tgenome\tmatched_kmers\n", scores);
         }
+        if (want_lca_reads) {
+            if (!(lca = fopen((dir + "/READ_LCA.tsv").c_str(), "wb"))) die("cannot create READ_LCA.tsv in " + dir);
+            fputs("#read_id\thits\tclade\tname\n", lca);
+        }
     }
     void close() {
         for (OutFile *f : {&pos, &neg, &pos2, &neg2})
             if (f->fd >= 0) ::close(f->fd);
         if (scores && fclose(scores) != 0) die("short write to READ_SCORES.tsv");
+        if (lca && fclose(lca) != 0) die("short write to READ_LCA.tsv");
     }
 };
 
@@ -1133,17 +1174,20 @@ struct Outputs {
 struct Hits {
     std::vector<uint64_t> off;
     std::vector<uint32_t> leaves, scores;
+    std::vector<uint32_t> lca;       // --lca-reads: the unit's clade (PFQ_NO_CLADE: no hit)
     std::vector<uint64_t> call_off;  // the call's read offsets, when its range does not start at the batch's first read
 };
 // Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
-// scores) are copied out of the library's buffers, which the next call on the tree reuses, into h.
-void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h) {
+// scores; keep_lca: the units' LCAs of a PFQ_WANT_LCA call) are copied out of the library's buffers, which the next call on
+// the tree reuses, into h.
+void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h, bool keep_lca = false) {
     const bool want = (flags & PFQ_WANT_HITS) != 0;
     const uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
     if (want) {
         h.off.assign(units + 1, 0);
         h.leaves.clear();
         h.scores.clear();
+        h.lca.clear();
     }
     if (r1 == r0) return;
     const uint64_t *off = b.off.data();
@@ -1164,6 +1208,12 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         if (pfq_last_hit_scores(tree, &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
         h.scores.assign(sc, sc + n_sc);
     }
+    if (keep_lca) {
+        const uint32_t *lca = nullptr;
+        uint64_t n_lca = 0;
+        if (pfq_last_lca(tree, &lca, &n_lca) != PFQ_OK) fail_from_thread(pfq_last_error());
+        h.lca.assign(lca, lca + n_lca);
+    }
 }
 // The trees' hit lists of n units in the whole tree's leaf order.  Part i covers units [n i / P, n (i + 1) / P) for a
 // replica (the shares follow one another) and all of them for a shard (per unit, the shards' lists in shard order, each
@@ -1175,11 +1225,13 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
         return;
     }
     uint64_t total = 0;
-    bool with_scores = false;
+    bool with_scores = false, with_lca = false;
     for (const Hits &h : parts) {
         total += h.leaves.size();
         with_scores |= !h.scores.empty();
+        with_lca |= !h.lca.empty();
     }
+    out.lca.assign(with_lca ? n : 0, PFQ_NO_CLADE);  // (replicas only: --lca does not serve shards)
     out.off.assign(n + 1, 0);
     out.leaves.resize(total);
     out.scores.resize(with_scores ? total : 0);
@@ -1192,6 +1244,7 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
             const uint64_t j0 = h.off[u - u0], j1 = h.off[u - u0 + 1];
             const uint32_t base = db.sharded ? (uint32_t)db.leaf_base[i] : 0u;
             if (with_scores) std::copy(h.scores.begin() + j0, h.scores.begin() + j1, out.scores.begin() + at);
+            if (with_lca) out.lca[u] = h.lca[u - u0];
             for (uint64_t j = j0; j < j1; ++j) out.leaves[at++] = h.leaves[j] + base;
         }
         out.off[u + 1] = at;
@@ -1274,6 +1327,15 @@ void put_scores(std::string &o, std::string_view id, uint64_t kmers, const uint3
     }
 }
 
+// READ_LCA.tsv line of a record (or fragment) with hits: "id\thits\tclade\tname"
+void put_lca(std::string &o, std::string_view id, uint64_t n_hits, uint32_t clade, const std::vector<std::string> &clade_names) {
+    char num[64];
+    o.append(id.data(), id.size());
+    o.append(num, (size_t)snprintf(num, sizeof num, "\t%llu\t%u\t", (unsigned long long)n_hits, clade));
+    o.append(clade_names[clade]);
+    o.push_back('\n');
+}
+
 // The three query loops over an open database, the reader and the outputs.
 struct QueryLoop {
     ServedDb &db;
@@ -1284,6 +1346,9 @@ struct QueryLoop {
     const bool pos, neg, scores;
     const unsigned threads;
     const uint64_t kmer_size;
+    const int lca = 0;             // --lca: 0 none, 1 all, 2 best (the library is asked for hits and scores)
+    const bool lca_reads = false;  // --lca-reads: READ_LCA.tsv
+    uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
 
     size_t n_trees() const { return db.trees.size(); }
@@ -1298,14 +1363,14 @@ struct QueryLoop {
     // calls want counts only.
     void paired(ReadQueue *rq2, bool both) {
         const uint64_t batch_frags = batch_size(1u << 19);
-        const bool per_read = pos || neg || scores;
-        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u);
+        const bool per_read = pos || neg || scores || lca_reads;
+        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags();
         PairSource src{rq, rq2, {}, {}, 0, {}, false};
         Batch b;
         std::vector<Hits> parts(n_trees());
         Hits f;  // the fragments' lists in the whole tree's leaf order
         OutBuf pos_out, neg_out, pos2_out, neg2_out;
-        std::string sc_out;
+        std::string sc_out, lca_out;
         std::vector<uint64_t> order;
         bool more = true;
         while (more) {
@@ -1318,7 +1383,7 @@ struct QueryLoop {
             fan_out(n_trees(), [&](size_t i) {
                 const size_t P = n_trees();
                 const uint64_t f0 = db.sharded ? 0 : nf * i / P, f1 = db.sharded ? nf : nf * (i + 1) / P;
-                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i]);
+                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads);
             });
             ns_gpu += ReadQueue::now_ns() - tq0;
             n_total += n;
@@ -1344,6 +1409,12 @@ struct QueryLoop {
                 }
                 if (!sc_out.empty() && fwrite(sc_out.data(), 1, sc_out.size(), out.scores) != sc_out.size()) die("short write to READ_SCORES.tsv");
             }
+            if (lca_reads) {
+                lca_out.clear();
+                for (uint64_t fr = 0; fr < nf; ++fr)
+                    if (f.off[fr] != f.off[fr + 1]) put_lca(lca_out, b.id(2 * fr), f.off[fr + 1] - f.off[fr], f.lca[fr], db.clade_names);
+                if (!lca_out.empty() && fwrite(lca_out.data(), 1, lca_out.size(), out.lca) != lca_out.size()) die("short write to READ_LCA.tsv");
+            }
             out.pos.append(pos_out.p, pos_out.n);
             out.neg.append(neg_out.p, neg_out.n);
             out.pos2.append(pos2_out.p, pos2_out.n);
@@ -1366,7 +1437,7 @@ struct QueryLoop {
         const uint64_t n = sg.b.n();
         if (!n) return;
         const uint64_t tq0 = ReadQueue::now_ns();
-        classify(db.trees[i], sg.b, 0, n, threshold, 0, unused);
+        classify(db.trees[i], sg.b, 0, n, threshold, lca_flags(), unused);
         ns_gpu += ReadQueue::now_ns() - tq0;
         if (!db.sharded || i == 0) n_total += n;
     }
@@ -1467,7 +1538,7 @@ struct QueryLoop {
         std::vector<Slot> slots(db.devices.size() + 3);
         const size_t NB = slots.size();
         for (Slot &s : slots) s.parts.resize(db.sharded ? n_trees() : 1);
-        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u);
+        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags();
         std::mutex mu;
         std::condition_variable cv;
         long long last_seq = -1;                 // sequence number of the last batch, once the assembler knows it
@@ -1511,7 +1582,7 @@ struct QueryLoop {
                     if (past_end(k)) return;
                 }
                 const uint64_t n = s->b.n(), tq0 = ReadQueue::now_ns();
-                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0]);
+                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads);
                 if (n) {
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     if (!db.sharded || i == 0) n_total += n;
@@ -1719,6 +1790,17 @@ struct QueryLoop {
                     for (const std::string &p : parts)
                         if (!p.empty() && fwrite(p.data(), 1, p.size(), out.scores) != p.size()) fail_from_thread("short write to READ_SCORES.tsv");
                 }
+                if (lca_reads) {
+                    // READ_LCA.tsv: per record with hits, the size of its hit set and its clade
+                    std::vector<std::string> parts(nw);
+                    const uint32_t *h_lca = s.hits.lca.data();
+                    fan_out(nw, [&](size_t w) {
+                        for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r)
+                            if (h_off[r] != h_off[r + 1]) put_lca(parts[w], b.id(r), h_off[r + 1] - h_off[r], h_lca[r], db.clade_names);
+                    });
+                    for (const std::string &p : parts)
+                        if (!p.empty() && fwrite(p.data(), 1, p.size(), out.lca) != p.size()) fail_from_thread("short write to READ_LCA.tsv");
+                }
                 const uint64_t t1 = ReadQueue::now_ns();
                 ns_fmt += t1 - t0;
                 // the bytes: batches come in input order, so a part's place is the sum of what lies before it
@@ -1762,7 +1844,7 @@ int cmd_query(int argc, char **argv) {
                              {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
-                             {"interleaved", 0, false}, {"pair-mode", 0, true}};
+                             {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -1773,7 +1855,18 @@ int cmd_query(int argc, char **argv) {
     const bool filtering = pos || neg;
     // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
     const bool scores = a.flags.count("scores") != 0;
-    const bool per_read = filtering || scores;  // the per-read hit lists are needed
+    // --lca all|best: every read (fragment) is also assigned to the lowest common ancestor of its hit genomes (best: of the
+    // genomes with its highest score): CLADE_COUNTS.tsv; --lca-reads: READ_LCA.tsv, one line per record with hits
+    const std::string lca_arg = opt(a, "lca", "");
+    if (a.val.count("lca") && lca_arg != "all" && lca_arg != "best")
+        die("error: invalid value '" + lca_arg + "' for '--lca' [possible values: all, best]");
+    const int lca = lca_arg == "all" ? 1 : lca_arg == "best" ? 2 : 0;
+    const bool lca_reads = a.flags.count("lca-reads") != 0;
+    if (lca_reads && !lca) die("error: '--lca-reads' needs '--lca <all|best>'");
+    if (lca && a.val.count("shard-depth"))
+        die("error: '--lca' cannot be used with '--shard-depth': a subtree shard holds only its own part of the tree, and combining "
+            "the shards' lowest common ancestors needs the whole tree's clades (not implemented)");
+    const bool per_read = filtering || scores || lca == 2 || lca_reads;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
@@ -1840,7 +1933,7 @@ int cmd_query(int argc, char **argv) {
     struct stat st;
     if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
     mkdir(out.c_str(), 0777);
-    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores);
+    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads);
     uint64_t kmer_size = 0;
     if (scores) {
         pfq_info info{};
@@ -1848,9 +1941,10 @@ int cmd_query(int argc, char **argv) {
         kmer_size = info.kmer_size;
     }
     db.load_leaf_names();
+    if (lca_reads) db.load_clade_names();
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads};
     if (block == 0) {
         // nothing to do: see above
     } else if (paired) {
@@ -1874,6 +1968,7 @@ int cmd_query(int argc, char **argv) {
     outs.close();
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
     db.save_counts(out + "/CLASSIFICATION.csv");
+    if (lca) db.save_clade_counts(out + "/CLADE_COUNTS.tsv");
     db.close();
     printf("Finished.\n");
     return 0;
@@ -2078,6 +2173,15 @@ void usage() {
             "genomes goes to POS, both mates alike, each under its own id with the fragment's \" |g1,g2\":\n"
             "POS_FILTERING_1/_2 and NEG_FILTERING_1/_2 (--interleaved: POS_FILTERING / NEG_FILTERING, mates adjacent).\n"
             "With --scores: one line per fragment and genome, R1's id, both mates' k-mers and matched k-mers summed.\n"
+            "--lca <all|best>: also assign every read to the lowest common ancestor (LCA) of the genomes it hits in the tree,\n"
+            "the smallest group of genomes the read cannot tell apart, and write CLADE_COUNTS.tsv into --out: one row per node\n"
+            "with reads at or below it, nodes numbered in pre-order (\"#clade<TAB>parent<TAB>depth<TAB>genomes<TAB>name<TAB>\n"
+            "reads_here<TAB>reads_below\"; parent is - for the root; paired input: fragments).  The other outputs stay as they are.\n"
+            "--lca best: the LCA of the genomes with the read's highest --scores value only (ties stay ambiguous); it asks the\n"
+            "library for hits and scores, READ_SCORES.tsv is still written with --scores only.  Not with --shard-depth: a\n"
+            "shard holds only its own part of the tree.  With --devices the replicas' counts are summed.\n"
+            "--lca-reads (needs --lca): also write READ_LCA.tsv, one line per record with hits in input order (per fragment:\n"
+            "R1's id): \"#read_id<TAB>hits<TAB>clade<TAB>name\", hits = the number of genomes hit (also with --lca best)\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
 }
 

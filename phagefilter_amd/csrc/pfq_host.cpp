@@ -282,6 +282,19 @@ struct pfq_tree {
     // [1] all-leaf fragments left unlisted
     DevBuf<unsigned long long> d_pair_sink, d_frag_off, d_pair_misc;
     DevBuf<uint32_t> d_frag_leaves, d_pair_long;
+    // PFQ_WANT_LCA: the clades (nodes reachable from the root, pre-order) and the device tables over the current leaf set are
+    // built on first use and again after the layout changed (ensure_lca); the counters d_clade_here live as long as the tables
+    bool lca_valid = false;
+    std::vector<pfq_clade> clades;
+    std::vector<std::string> clade_names;
+    uint32_t top_clade = 0;                // LCA of all leaves
+    DevBuf<uint32_t> d_leaf_clade, d_gap_min, d_lca, d_lca_long;
+    DevBuf<unsigned long long> d_clade_here, d_lca_misc;
+    DevBuf<uint2> d_lca_span;
+    std::vector<uint64_t> out_here, out_below;
+    std::vector<uint32_t> out_lca;
+    bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
+    uint64_t lca_units = 0;
 };
 
 namespace {
@@ -817,6 +830,88 @@ int build_layout(pfq_tree &t) {
     return PFQ_OK;
 }
 
+// PFQ_WANT_LCA: the clade table of the tree as it is and the device tables over its leaf columns (pfq_kernels.h), built on
+// first use and again after pfq_tree_insert / pfq_tree_prune; the clade counters start at zero with them.
+int ensure_lca(pfq_tree &t) {
+    if (t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_LCA on a subtree shard: a shard holds only its own subtree and ancestor chain, not the "
+                                         "other shards' topology, so its clades are not the whole tree's");
+    PFQ_TRY(build_layout(t));
+    if (t.lca_valid) return PFQ_OK;
+    t.clades.clear();
+    t.clade_names.clear();
+    const size_t nl = t.leaves.size();
+    std::vector<uint32_t> leaf_clade(nl, 0), gap(nl ? nl - 1 : 0, 0);
+    if (t.root >= 0) {
+        // pre-order, left before right; a two-child node is the LCA of the last leaf of its left subtree and the first leaf
+        // of its right one, which are adjacent columns: it owns the gap before its right child's first leaf
+        struct Frame { int32_t node; uint32_t clade; int stage; };
+        std::vector<Frame> st;
+        uint32_t next_leaf = 0;
+        auto enter = [&](int32_t v, uint32_t parent, uint32_t depth) {
+            const uint32_t c = (uint32_t)t.clades.size();
+            t.clades.push_back(pfq_clade{parent, depth, next_leaf, 0, nullptr});
+            const Node &nd = t.nodes[v];
+            std::string name = nd.tax_id;
+            if (!nd.has_tax) {
+                const size_t slash = nd.bf_path.find_last_of('/');
+                name = slash == std::string::npos ? nd.bf_path : nd.bf_path.substr(slash + 1);
+                if (name.size() > 3 && name.compare(name.size() - 3, 3, ".bf") == 0) name.resize(name.size() - 3);
+            }
+            t.clade_names.push_back(std::move(name));
+            if (nd.is_leaf()) leaf_clade[next_leaf++] = c;
+            st.push_back(Frame{v, c, 0});
+        };
+        enter(t.root, PFQ_NO_CLADE, 0);
+        while (!st.empty()) {
+            Frame &f = st.back();
+            const Node &nd = t.nodes[f.node];
+            const uint32_t c = f.clade, depth = t.clades[c].depth;
+            if (f.stage == 0) {
+                f.stage = 1;
+                if (nd.left >= 0) {
+                    enter(nd.left, c, depth + 1);
+                    continue;
+                }
+            }
+            if (f.stage == 1) {
+                f.stage = 2;
+                if (nd.right >= 0) {
+                    if (nd.left >= 0) gap[next_leaf - 1] = c;
+                    enter(nd.right, c, depth + 1);
+                    continue;
+                }
+            }
+            t.clades[c].n_leaves = next_leaf - t.clades[c].first_leaf;
+            st.pop_back();
+        }
+    }
+    for (size_t c = 0; c < t.clades.size(); ++c) t.clades[c].name = t.clade_names[c].c_str();
+    const size_t nc = t.clades.size();
+    t.top_clade = 0;
+    while (t.top_clade + 1 < nc && t.clades[t.top_clade + 1].n_leaves == nl) ++t.top_clade;  // (a chain of one-child nodes from the root)
+    if (nl) {
+        uint32_t levels = 1;
+        while ((2ull << (levels - 1)) <= gap.size()) ++levels;
+        std::vector<uint32_t> tab((size_t)levels * nl, PFQ_NO_CLADE);
+        std::copy(gap.begin(), gap.end(), tab.begin());
+        for (uint32_t j = 1; j < levels; ++j) {
+            const size_t half = (size_t)1 << (j - 1);
+            const uint32_t *prev = tab.data() + (size_t)(j - 1) * nl;
+            uint32_t *cur = tab.data() + (size_t)j * nl;
+            for (size_t i = 0; i + 2 * half <= gap.size(); ++i) cur[i] = std::min(prev[i], prev[i + half]);
+        }
+        HIP_TRY(t.d_leaf_clade.ensure(nl));
+        HIP_TRY(t.d_gap_min.ensure(tab.size()));
+        HIP_TRY(t.d_clade_here.ensure(nc));
+        HIP_TRY(hipMemcpy(t.d_leaf_clade.p, leaf_clade.data(), nl * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t.d_gap_min.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(t.d_clade_here.p, 0, nc * 8));
+    }
+    t.lca_valid = true;
+    return PFQ_OK;
+}
+
 int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
     HIP_TRY(t.d_stats.ensure(pfq::ST_N));
     HIP_TRY(t.d_cursors.ensure(16));
@@ -893,7 +988,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
@@ -921,7 +1016,10 @@ struct QueryRun {
         paired = (flags & PFQ_PAIRED) != 0;
         pair_both = (flags & PFQ_PAIR_BOTH) != 0;
         if (user_hits && !hits) return fail(PFQ_ERR_ARG, "PFQ_WANT_HITS set but hits == NULL");
-        want_hits = user_hits || paired;  // (fragments are combined from the mates' hit lists)
+        want_lca = (flags & PFQ_WANT_LCA) != 0;
+        lca_best = (flags & PFQ_LCA_BEST) != 0;
+        if (want_lca) PFQ_TRY(ensure_lca(t));
+        want_hits = user_hits || paired || want_lca;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
         if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
@@ -1602,6 +1700,15 @@ struct QueryRun {
         if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)cursors[0] / (double)n_reads);
         if (t.last_attempts == 1) t.last_hit_cursor0 = cursors[0];
         if (cursors[0] <= hit_cap && paired) return pair_hits(cursors[0]);
+        if (cursors[0] <= hit_cap && !user_hits) {  // PFQ_WANT_LCA alone: the reads' spans straight from the hit pairs, nothing waited for
+            if (n_reads && nl) {
+                HIP_TRY(t.d_lca_span.ensure(n_reads));
+                HIP_TRY(hipMemsetAsync(t.d_lca_span.p, 0xff, n_reads * sizeof(uint2), st));
+                pfq::launch_lca_pairs(t.d_hit_pairs.p, cursors[0], t.d_allhit.p, n_reads, t.d_lca_span.p, lca_tables(), t.d_lca.p, st);
+                HIP_TRY(hipGetLastError());
+            }
+            return PFQ_OK;
+        }
         if (cursors[0] <= hit_cap) {
             // CSR read -> leaves (ascending; reads that pass every node list every leaf), built on the device from the
             // unordered hit pairs and copied into page-locked host buffers
@@ -1645,8 +1752,9 @@ struct QueryRun {
                         HIP_TRY(hipGetLastError());
                         HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
                     }
+                    if (want_lca) PFQ_TRY(lca_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, 0));  // (runs beside the copies)
                     HIP_TRY(hipStreamSynchronize(st));
-                }
+                } else if (want_lca) PFQ_TRY(lca_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, 0));  // (every row is empty)
             } else PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, 4));
             if (want_scores) {
                 PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
@@ -1722,8 +1830,9 @@ struct QueryRun {
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
                 }
+                if (want_lca) PFQ_TRY(lca_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, pair_both ? 2 : 1));
                 HIP_TRY(hipStreamSynchronize(st));
-            }
+            } else if (want_lca) PFQ_TRY(lca_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, pair_both ? 2 : 1));
         } else if (user_hits) {  // no fragments, or no leaves: empty lists
             PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, (n_frag + 1) * 8));
             for (uint64_t i = 0; i <= n_frag; ++i) t.h_hit_off[i] = 0;
@@ -1741,7 +1850,29 @@ struct QueryRun {
         return PFQ_OK;
     }
 
+    pfq::LcaTables lca_tables() const {
+        return pfq::LcaTables{(uint32_t)nl, (uint32_t)t.clades.size(), t.top_clade, t.d_leaf_clade.p, t.d_gap_min.p, t.d_clade_here.p};
+    }
+    // PFQ_WANT_LCA over the rows of the CSR the call has built (reads, or fragments: pair_mode 1 either / 2 both, whose all-leaf
+    // fragments may be unlisted); PFQ_LCA_BEST: over the entries with the row's highest score (the scores are queued before)
+    int lca_rows(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units, int pair_mode) {
+        if (lca_best) {
+            HIP_TRY(t.d_lca_span.ensure(n_units));
+            HIP_TRY(t.d_lca_long.ensure(n_units));
+            HIP_TRY(t.d_lca_misc.ensure(1));
+            HIP_TRY(hipMemsetAsync(t.d_lca_misc.p, 0, 8, st));
+            pfq::launch_lca_best(off, leaves, t.d_hit_scores.p, n_units, t.d_lca_span.p, t.d_lca_long.p, t.d_lca_misc.p, lca_tables(), t.d_lca.p, st);
+        } else pfq::launch_lca_rows(off, leaves, n_units, t.d_allhit.p, pair_mode, lca_tables(), t.d_lca.p, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
+    }
+
     int run() {
+        if (want_lca) {
+            t.lca_units = paired ? n_reads / 2 : n_reads;
+            HIP_TRY(t.d_lca.ensure(t.lca_units + 1));
+            HIP_TRY(hipMemsetAsync(t.d_lca.p, 0xff, t.lca_units * 4, st));  // (an empty tree or call: no unit has a clade)
+        }
         for (int attempt_no = 0; attempt_no < 2; ++attempt_no) {
             PFQ_TRY(attempt(attempt_no));
             if (!want_hits) return PFQ_OK;  // (PFQ_PAIRED always builds the mates' hit lists)
@@ -1756,9 +1887,11 @@ struct QueryRun {
 int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, uint64_t total_bytes,
                  float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
     t.scores_valid = false;
+    t.lca_last = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
     int rc = q.plan();
     if (rc == PFQ_OK) rc = q.run();
+    t.lca_last = rc == PFQ_OK && (flags & PFQ_WANT_LCA);
     if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
     return rc;
 }
@@ -2201,6 +2334,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
         return fail(PFQ_ERR_ARG, std::string("a node named ") + internal_name + " exists already: two nodes would share " + internal_name + ".bf");
     PFQ_TRY(sync_counts_to_nodes(t));
     t.layout_valid = false;
+    t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     PFQ_TRY(reserve_rows(t, t.n_rows + 2));
     if (!t.greedy_blocks) {
         hipDeviceProp_t prop;
@@ -2508,6 +2642,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
         if (nd.depth >= search_depth) nd.left = nd.right = -1;  // bloom_tree.rs:322-325
     // nodes below the cut are unreachable now; they keep their slots (and filters) but never appear as leaves
     t.layout_valid = false;
+    t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     return PFQ_OK;
 }
 
@@ -2538,6 +2673,12 @@ void pfq_tree_close(pfq_tree *tree) {
 // Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
 static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     t.scores_valid = false;
+    t.lca_last = false;
+    if ((flags & PFQ_LCA_BEST) && (~flags & (PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES)))
+        return fail(PFQ_ERR_ARG, "PFQ_LCA_BEST needs PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES");
+    if ((flags & PFQ_WANT_LCA) && t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_LCA on a subtree shard: a shard holds only its own subtree and ancestor chain, not the "
+                                         "other shards' topology, so its clades are not the whole tree's");
     if ((flags & PFQ_WANT_SCORES) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SCORES needs PFQ_WANT_HITS");
     if ((flags & PFQ_PAIRED) && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
     if ((flags & PFQ_PAIR_BOTH) && !(flags & PFQ_PAIRED)) return fail(PFQ_ERR_ARG, "PFQ_PAIR_BOTH needs PFQ_PAIRED");
@@ -2587,6 +2728,47 @@ int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hit
     if (!tree->scores_valid) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for scores (PFQ_WANT_SCORES)");
     *scores = tree->h_hit_scores;
     *n_hits = tree->scores_n;
+    return PFQ_OK;
+}
+
+int pfq_tree_clades(pfq_tree *tree, const pfq_clade **clades, uint64_t *n) {
+    if (!tree || !clades || !n) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    PFQ_TRY(ensure_lca(*tree));
+    *clades = tree->clades.data();
+    *n = tree->clades.size();
+    return PFQ_OK;
+}
+
+int pfq_clade_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **below, uint64_t *n) {
+    if (!tree || !n) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(ensure_lca(t));
+    const size_t nc = t.clades.size();
+    t.out_here.assign(nc, 0);
+    if (nc && !t.leaves.empty()) {
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(t.out_here.data(), t.d_clade_here.p, nc * 8, hipMemcpyDeviceToHost));
+    }
+    t.out_below = t.out_here;
+    for (size_t c = nc; c-- > 1;) t.out_below[t.clades[c].parent] += t.out_below[c];  // (pre-order: children after their parent)
+    if (here) *here = t.out_here.data();
+    if (below) *below = t.out_below.data();
+    *n = nc;
+    return PFQ_OK;
+}
+
+int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units) {
+    if (!tree || !lca || !n_units) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->lca_last) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for the LCAs (PFQ_WANT_LCA)");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(wait_last_call(t));
+    t.out_lca.resize(t.lca_units + 1);
+    if (t.lca_units) HIP_TRY(hipMemcpy(t.out_lca.data(), t.d_lca.p, t.lca_units * 4, hipMemcpyDeviceToHost));
+    *lca = t.out_lca.data();
+    *n_units = t.lca_units;
     return PFQ_OK;
 }
 
@@ -2835,6 +3017,7 @@ int pfq_leaf_counts_reset(pfq_tree *tree) {
     if (!tree->leaves.empty()) {
         HIP_TRY(hipMemset(tree->d_counts.p, 0, tree->leaves.size() * 8));
         HIP_TRY(hipMemset(tree->d_counts_base.p, 0, tree->leaves.size() * 8));
+        if (tree->lca_valid) HIP_TRY(hipMemset(tree->d_clade_here.p, 0, tree->clades.size() * 8));
     }
     for (auto &nd : tree->nodes) nd.mapped_reads = nd.base_reads = 0;
     return PFQ_OK;

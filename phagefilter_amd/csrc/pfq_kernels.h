@@ -371,6 +371,28 @@ void launch_pair_leaf_counts(const uint32_t *d_frag_leaves, const unsigned long 
 void launch_pair_scores(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_frag, float threshold, bool both,
                         const unsigned long long *d_frag_off, const uint32_t *d_frag_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
                         uint64_t n_words, uint32_t *d_scores, hipStream_t st);
+// PFQ_WANT_LCA (pfq_lca.hip): d_lca[u] = clade of the lowest common ancestor of unit u's hit leaves (LCA_NO_CLADE: no hit) and
+// here[that clade] += 1.  The tables describe the current leaf set: leaf_clade [n_leaves]; gap_min [levels][n_leaves], level j
+// entry i = the smallest clade index among the LCAs of adjacent leaves (i, i + 1) .. (i + 2^j - 1, i + 2^j) — clades are in
+// pre-order, so that is their shallowest; top_clade = the LCA of all leaves.
+//   launch_lca_pairs: units = reads, from the unordered (read, leaf) hit pairs and the all-hit flags; d_span [n_reads], filled
+//     with 0xff by the caller.
+//   launch_lca_rows: units = rows of an ascending CSR; pair_mode 1 (either) / 2 (both): rows are fragments, d_allhit holds the
+//     mates' flags and an empty row of an all-leaf fragment stands for every leaf; 0: d_allhit is not read.
+//   launch_lca_best: rows reduced to the entries with the row's highest score first; d_span [n_units], d_long [n_units],
+//     d_n_long zeroed by the caller.
+constexpr uint32_t LCA_NO_CLADE = 0xffffffffu;
+struct LcaTables {
+    uint32_t n_leaves, n_clades, top_clade;
+    const uint32_t *leaf_clade, *gap_min;
+    unsigned long long *here;
+};
+void launch_lca_pairs(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_allhit, uint64_t n_reads, uint2 *d_span, const LcaTables &tb,
+                      uint32_t *d_lca, hipStream_t st);
+void launch_lca_rows(const unsigned long long *d_off, const uint32_t *d_leaves, uint64_t n_units, const uint8_t *d_allhit, int pair_mode,
+                     const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
+void launch_lca_best(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint2 *d_span,
+                     uint32_t *d_long, unsigned long long *d_n_long, const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

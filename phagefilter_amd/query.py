@@ -216,16 +216,21 @@ class BloomTree:
 
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
-                     want_scores: bool = False, paired: bool = False, pair_mode: str = "either"):
+                     want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
+                     lca: Optional[str] = None):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
-        (pair_mode "either") or the intersection ("both") of the mates' sets."""
+        (pair_mode "either") or the intersection ("both") of the mates' sets.
+        `lca`: "all" also assigns every read / fragment to the lowest common ancestor of its hit leaves (last_lca(),
+        clade_counts()), "best" to that of its best-scoring hits (needs want_hits and want_scores); the return value and
+        every other result stay what they are without it."""
+        lca_flags = _lca_flags(lca, want_hits, want_scores)
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         hits = _ffi.Hits()
-        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode)
+        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
         _ffi.check(_ffi.lib().pfq_query_batch(self._h, seq.ctypes.data, off.ctypes.data, n, threshold, flags, C.byref(hits)))
         if not want_hits:
             return None
@@ -246,18 +251,20 @@ class BloomTree:
         return np.ctypeslib.as_array(p, shape=(n.value,)) if n.value else np.zeros(0, dtype=np.uint32)
 
     def query_device(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float,
-                     stream: int = 0, paired: bool = False, pair_mode: str = "either") -> None:
-        """One block already resident in HBM (raw device pointers), asynchronous on `stream`."""
-        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold,
-                                                     _pair_flags(paired, pair_mode), stream, None))
+                     stream: int = 0, paired: bool = False, pair_mode: str = "either", lca: Optional[str] = None) -> None:
+        """One block already resident in HBM (raw device pointers), asynchronous on `stream`.  `lca`: None or "all"
+        (as in query_packed; "best" needs the hits: query_device_hits)."""
+        flags = _pair_flags(paired, pair_mode) | _lca_flags(lca, False, False)
+        _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags, stream, None))
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
-                          want_scores: bool = False, paired: bool = False, pair_mode: str = "either"):
+                          want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
+                          lca: Optional[str] = None):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", as in query_packed."""
         hits = _ffi.Hits()
-        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode)
+        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | _lca_flags(lca, True, want_scores)
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -269,14 +276,45 @@ class BloomTree:
         return offs, leaves, self.last_hit_scores()
 
     def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
-                    mode: str = "either") -> List[List[int]]:
+                    mode: str = "either", lca: Optional[str] = None) -> List[List[int]]:
         """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
-        (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments."""
+        (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments.
+        `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca()."""
+        if lca not in (None, "all", "best"):
+            raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
         if len(r1) != len(r2):
             raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
         seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
-        offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, paired=True, pair_mode=mode)
+        offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best", paired=True,
+                                         pair_mode=mode, lca=lca)[:2]
         return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
+
+    # ---- clades (lowest common ancestors)
+    def clades(self) -> List[Tuple[int, int, int, int, str]]:
+        """The clades of the tree as it is: (parent, depth, first_leaf, n_leaves, name) per node reachable from the root, in
+        pre-order (the root is clade 0, its parent -1); a clade's leaves are get_leaf_counts()[first_leaf : first_leaf +
+        n_leaves]."""
+        p = C.POINTER(_ffi.Clade)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_tree_clades(self._h, C.byref(p), C.byref(n)))
+        return [(-1 if p[i].parent == _ffi.NO_CLADE else int(p[i].parent), int(p[i].depth), int(p[i].first_leaf),
+                 int(p[i].n_leaves), p[i].name.decode()) for i in range(n.value)]
+
+    def clade_counts(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(here, below): per clade the reads / fragments whose LCA it is, and the sum of that over its subtree."""
+        here, below = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_clade_counts(self._h, C.byref(here), C.byref(below), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+        return (np.ctypeslib.as_array(here, shape=(n.value,)).copy(), np.ctypeslib.as_array(below, shape=(n.value,)).copy())
+
+    def last_lca(self) -> np.ndarray:
+        """Clade index per read / fragment of the last query call, which must have asked for it (_ffi.NO_CLADE: no hit)."""
+        p = C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_last_lca(self._h, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
 
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
@@ -291,6 +329,18 @@ class BloomTree:
     def import_counts_delta(self, d_src: int, stream: int = 0) -> None:
         """counters = base + d_src (the sum of the ranks' deltas); that becomes the new base."""
         _ffi.check(_ffi.lib().pfq_leaf_counts_import_delta(self._h, d_src, stream))
+
+
+def _lca_flags(lca: Optional[str], want_hits: bool, want_scores: bool) -> int:
+    if lca is None:
+        return 0
+    if lca not in ("all", "best"):
+        raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
+    if lca == "all":
+        return _ffi.WANT_LCA
+    if not (want_hits and want_scores):
+        raise ValueError("lca='best' needs the hits and their scores (want_hits=True, want_scores=True)")
+    return _ffi.WANT_LCA | _ffi.LCA_BEST
 
 
 def _pair_flags(paired: bool, pair_mode: str) -> int:
