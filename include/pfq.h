@@ -286,7 +286,9 @@ typedef struct pfq_stats {
     uint64_t group_reads;       /* (read, leaf group) combinations the coarse level let through to the leaf level */
     uint32_t pair_stage;        /* bucketed path, between classify and the certificates.  Bits 0-1: how the pairs were sorted by leaf —
                                  * 1: slices of slots counted in an LDS histogram, one global atomic per bucket and slice;
-                                 * 2: one global atomic per pair (more buckets than LDS holds).  Bits 4-6: the shapes of
+                                 * 2: one global atomic per pair (more buckets than LDS holds).  Bit 2 (0x4): k_classify only deferred
+                                 * its survivors and k_tail_records made all their probe records, 64 k-mers a pass
+                                 * (theta = 1 with records unless PFQ_SPLIT_RECORDS=0).  Bits 4-6: the shapes of
                                  * last-window pass that served at least one pair — 0x10: sixteen reads x 4 k-mers,
                                  * 0x20: four x 16, 0x40: two x 32 (none: no last window was left to the batched kernel) */
 } pfq_stats;
@@ -298,7 +300,8 @@ int pfq_set_path(pfq_tree *tree, int path);
  * launched on.  begin: record around the kernels of the next (up to max_calls) query calls; end: synchronise and sum. */
 typedef struct pfq_profile {
     uint64_t calls;
-    double classify_ms; /* k_classify (pre-screen, frontier, probe records or inline certificates) */
+    double classify_ms; /* k_classify (pre-screen, frontier, inline certificates) + k_expand_guards + k_tail_records (the probe
+                         * records of the deferred reads at theta = 1; only their last windows with PFQ_SPLIT_RECORDS=0) */
     double bucket_ms;   /* bucket scan + scatter */
     double bin_ms;      /* k_tile_plan + k_tile_bin (probes binned by leaf chunk and filter tile) */
     double test_ms;     /* k_tile_test (tiles tested out of LDS) */

@@ -274,7 +274,9 @@ __device__ __forceinline__ void for_each_probe(ProbeIter &it, const HashParams &
 // Probe record of one k-mer: everything the bucketed verify needs to regenerate the num_hashes indices with
 // 32-bit arithmetic only: x = h1 % d, y = h2 % d, z = ((h1+2)*h2 mod 2^64) % d, w = wrap-carry bits of the
 // 64-bit walk (bit i-3 set iff (h1+i)*h2 wrapped relative to (h1+i-1)*h2, i = 3..num_hashes-1).
-// Valid for d < 2^30 and num_hashes <= 35.
+// Valid for d < 2^30 and num_hashes <= 35.  STEPS: num_hashes - 3 where the caller knows it at compile time (the walk is then
+// straight-line code, three instructions a step), -1: taken from hp (a rolled loop, seven a step).
+template <int STEPS = -1>
 __device__ __forceinline__ uint4 make_probe_record(uint64_t h1, uint64_t h2, const HashParams &hp) {
     uint4 rec;
     rec.x = mod_nbits30(h1, hp);
@@ -285,12 +287,19 @@ __device__ __forceinline__ uint4 make_probe_record(uint64_t h1, uint64_t h2, con
     // instructions a step; compare-and-select code was seven); the first step ends up in the highest of the n bits
     uint32_t rl = (uint32_t)r, rh = (uint32_t)(r >> 32), cm = 0;
     const uint32_t hl = (uint32_t)h2, hh = (uint32_t)(h2 >> 32);
-    const uint32_t n = hp.num_hashes > 3 ? hp.num_hashes - 3 : 0;
-    for (uint32_t i = 0; i < n; ++i)
+    const uint32_t n = STEPS >= 0 ? (uint32_t)STEPS : (hp.num_hashes > 3 ? hp.num_hashes - 3 : 0);
+    auto walk_step = [&]() {
         asm("v_add_co_u32 %0, vcc, %0, %3\n\tv_addc_co_u32 %1, vcc, %1, %4, vcc\n\tv_addc_co_u32 %2, vcc, %2, %2, vcc"
             : "+v"(rl), "+v"(rh), "+v"(cm)
             : "v"(hl), "v"(hh)
             : "vcc");
+    };
+    if constexpr (STEPS >= 0) {
+#pragma unroll
+        for (int i = 0; i < STEPS; ++i) walk_step();
+    } else {
+        for (uint32_t i = 0; i < n; ++i) walk_step();
+    }
     rec.w = n ? __brev(cm) >> (32u - n) : 0u;
     return rec;
 }

@@ -82,7 +82,7 @@ struct DevBuf {
 struct Knobs {
     long long record_gb = -1, tile_gb = -1, tile_entries = -1, slice_kb = -1;
     long long verify_blocks = -1, verify_chunk = -1, verify_sub = -1, verify_threads = -1, bin_blocks = -1, test_blocks = -1;
-    long long tile = -1, tile_counts = -1, no_tail_batch = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1;
+    long long tile = -1, tile_counts = -1, no_tail_batch = -1, split_records = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1;
     long long coarse = -1, coarse_cols = -1, coarse_probes = -1, group_log2 = -1, screen_recs = -1, coarse_min_leaves = -1, greedy_host = -1;
     long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
 };
@@ -98,7 +98,7 @@ const KnobName KNOBS[] = {
     {"PFQ_BIN_BLOCKS", &Knobs::bin_blocks},     {"PFQ_TEST_BLOCKS", &Knobs::test_blocks},
     {"PFQ_TILE", &Knobs::tile},                 {"PFQ_TILE_COUNTS", &Knobs::tile_counts},
     {"PFQ_NO_TAIL_BATCH", &Knobs::no_tail_batch}, {"PFQ_BIN_NARROW", &Knobs::bin_narrow},
-    {"PFQ_BIN_WIDE", &Knobs::bin_wide},
+    {"PFQ_BIN_WIDE", &Knobs::bin_wide},         {"PFQ_SPLIT_RECORDS", &Knobs::split_records},
 #ifdef PFQ_EXPERIMENTS  // (timing experiments with wrong results: not in the library as shipped)
     {"PFQ_BIN_DEBUG", &Knobs::bin_debug},
 #endif
@@ -214,7 +214,7 @@ struct pfq_tree {
     // reduced: the reductions over replicas / ranks add up counters - base, so that stored counts are not added once per replica
     DevBuf<unsigned long long> d_counts_base, d_counts_delta;
     // ---- query scratch
-    DevBuf<unsigned long long> d_stats, d_cursors;  // cursors: [0] hit, [1] pair, [2] tile entries, [3] lo: chunks, hi: flagged pairs, [4] long reads, [5] miss words, [6] dirty pairs, [7] lo: open pairs after the tile passes (thresholds < 1), [8] guard pairs, [9] k-mer miss bytes handed out, [10] tail shapes that served a pair (pfq::TAIL_SHAPE_*)
+    DevBuf<unsigned long long> d_stats, d_cursors;  // cursors: [0] hit, [1] pair, [2] tile entries, [3] lo: chunks, hi: flagged pairs, [4] long reads, [5] miss words, [6] dirty pairs, [7] lo: open pairs after the tile passes (thresholds < 1), [8] guard pairs, [9] k-mer miss bytes handed out, [10] tail shapes that served a pair (pfq::TAIL_SHAPE_*), [11] lo: k_tail_records' work counter
     DevBuf<uint32_t> d_entries, d_pair_chunk, d_leaf_chunk0, d_flag_list;  // LDS-tile certificates
     DevBuf<pfq::ChunkDesc> d_chunks;
     DevBuf<unsigned int> d_gfill, d_binq;
@@ -1366,6 +1366,9 @@ struct QueryRun {
             const uint64_t tl = avg_len >= t.kmer_size ? ((avg_len - t.kmer_size + 1) & 63u) : 0;
             a.batch_tails = (tl > 16 && tl <= 32) ? 32u : 16u;
         }
+        // theta = 1: k_classify only defers its survivors; k_tail_records, leaner and with no frontier to walk, hashes them
+        // (PFQ_SPLIT_RECORDS=0: k_classify hashes every window it does not leave to the batched tails)
+        a.split_recs = (recs && !counts_mode && kn.split_records != 0) ? 1u : 0u;
         a.block_pairs = block_mode ? 1u : 0u;
         a.screen_recs = kn.screen_recs >= 0 ? (uint32_t)(kn.screen_recs != 0) : 1u;
         if (block_mode) {
@@ -1377,7 +1380,7 @@ struct QueryRun {
         }
         return PFQ_OK;
     }
-    // guard columns of the deferred pairs (pairs of their own), the records of the last windows
+    // guard columns of the deferred pairs (pairs of their own), the probe records of the deferred reads
     int guards_and_tails() {
         ga = pfq::GuardArgs{};
         if (with_guards && !block_mode) {  // every guard of a deferred pair's leaf becomes a pair of its own (second region of the buffer)
@@ -1391,7 +1394,7 @@ struct QueryRun {
             ga.gfail = t.d_gfail.p;
             pfq::launch_expand_guards(a, ga, 2048, st);
         }
-        if (a.batch_tails) pfq::launch_tail_records(a, reinterpret_cast<unsigned int *>(t.d_cursors.p + 10), 2048, st);
+        if (a.batch_tails || a.split_recs) pfq::launch_tail_records(a, reinterpret_cast<unsigned int *>(t.d_cursors.p + 10), 2048, st);
         if (ev) HIP_TRY(hipEventRecord(ev[1], st));
         return PFQ_OK;
     }
@@ -3044,7 +3047,8 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
     if (t.d_cursors.p) {
         unsigned long long c[11];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
-        out->pair_stage = t.last_sort | (t.last_path ? (uint32_t)c[10] << 4 : 0u);
+        const uint32_t shapes = t.last_path ? (uint32_t)c[10] : 0u;  // pfq::TAIL_SHAPE_*
+        out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u);
         out->n_chunks = (uint32_t)c[3];
         out->n_fallback_pairs = (uint32_t)(c[3] >> 32);
         out->tile_entries = c[2];

@@ -73,6 +73,7 @@ struct QueryArgs {
     uint32_t *long_list;         // thresholds < 1: reads of >= 256 k-mers, classified by a second launch (wider counters)
     unsigned int *n_long;
     uint32_t batch_tails;        // theta == 1 with records: last windows of <= batch_tails k-mers (0: none, 16 or 32) are left to k_tail_records
+    uint32_t split_recs;         // 1 (theta == 1 with records): k_classify only defers; k_tail_records makes every record of a deferred read
     uint32_t block_pairs;        // 1 (DEFER, theta == 1, no guard columns): defer (read, block of 8 leaves | candidate mask << 24)
     uint32_t screen_recs;        // thresholds < 1: the dense counting screen writes the probe records of the k-mers it hashes
     uint32_t screen_only;        // (launches without deferral) count the frontier's candidate leaves, certify nothing, count no read
@@ -269,8 +270,10 @@ void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st);
 
 // launches (all asynchronous on `st`)
 void launch_classify(const QueryArgs &a, bool defer, bool counts_mode, int blocks, hipStream_t st);
-// after launch_classify when a.batch_tails; ORs into *shapes which passes served a pair: TAIL_SHAPE_4 / _16 / _32
-constexpr uint32_t TAIL_SHAPE_4 = 1, TAIL_SHAPE_16 = 2, TAIL_SHAPE_32 = 4;
+// after launch_classify when a.batch_tails or a.split_recs; ORs into *shapes which passes served a pair: TAIL_SHAPE_4 / _16 /
+// _32 (last windows, a.batch_tails) and TAIL_SHAPE_FULL (a.split_recs: the 64-k-mer pass made a read's other windows);
+// shapes[2] is the kernel's work counter and must be zero (the host clears both with the call's cursors)
+constexpr uint32_t TAIL_SHAPE_4 = 1, TAIL_SHAPE_16 = 2, TAIL_SHAPE_32 = 4, TAIL_SHAPE_FULL = 8;
 void launch_tail_records(const QueryArgs &a, unsigned int *shapes, int blocks, hipStream_t st);
 void launch_bucket_scan(const uint32_t *bucket_cnt, uint32_t *bucket_off, uint32_t *bucket_cur, uint32_t n, hipStream_t st);
 // words_off / words_cur / miss_pos: thresholds < 1 (miss words of a bucket start at words_off[bucket]); else nullptr

@@ -816,7 +816,9 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
                     miss_left -= miss_need;
                     ++pair_used;
                     ++st_def;
-                    if (a.recs && !prepared) {  // hash the read once; every slice of the verify reuses the records
+                    // (a.split_recs: the pair is all this kernel leaves behind — k_tail_records hashes the read, 7 waves per SIMD
+                    // there against 4 here and no frontier between two windows)
+                    if (a.recs && !prepared && !(!COUNTS && a.split_recs)) {  // hash the read once; every slice of the verify reuses the records
                         prepared = true;
                         // 150 bp reads at k = 20..23 have 128 + (1..3) k-mers: a third hashing pass for two or three
                         // k-mers.  Such last windows are left to k_tail_records (several reads per pass).
@@ -1306,7 +1308,7 @@ constexpr uint32_t TAIL_LDS_BYTES = DENSE_READS * MINI_BYTES + 2u * WIN_PAD;  //
 // (pair j, k-mer t of up to TAIL): sixteen pairs with tails of up to 4 k-mers (150 bp reads at k = 20 .. 23 have 1 .. 3: the
 // shape of dense_screen's mini windows), four with up to 16, two with up to 32.  `have`, o0 (the read's byte offset) and n
 // (its k-mers) are those of the lane's pair.
-template <uint32_t TAIL>
+template <uint32_t TAIL, int STEPS>
 __device__ __forceinline__ void tail_pass(const QueryArgs &a, uint32_t *tfw, uint32_t *trc, const uint8_t *s_comp, bool have,
                                           uint64_t o0, uint32_t n) {
     // bytes per pair in LDS; byte loads per lane and batch (TAIL = 4: batches of six, as many as k asks for)
@@ -1341,11 +1343,11 @@ __device__ __forceinline__ void tail_pass(const QueryArgs &a, uint32_t *tfw, uin
     const bool valid = have && t < tl;
     uint64_t h1, h2;
     kmer_hashes_at(tfw, trc, mb + t, mb + (W - t - k), valid, a.hp, h1, h2);
-    const uint4 rec = make_probe_record(h1, h2, a.hp);
+    const uint4 rec = make_probe_record<STEPS>(h1, h2, a.hp);
     if (valid) a.recs[o0 + base + t] = rec;
 }
 // The pairs of one shape among a wave's 64 slots, 64 / TAIL per pass: list[0 .. cnt) names their lanes, which hold o0 and n.
-template <uint32_t TAIL>
+template <uint32_t TAIL, int STEPS>
 __device__ __forceinline__ void tail_passes(const QueryArgs &a, uint32_t *tfw, uint32_t *trc, const uint8_t *s_comp,
                                             const uint8_t *list, uint32_t cnt, uint64_t o0, uint32_t n) {
     const uint32_t j = lane_id() / TAIL;
@@ -1354,15 +1356,87 @@ __device__ __forceinline__ void tail_passes(const QueryArgs &a, uint32_t *tfw, u
         const int from = have ? (int)list[p0 + j] : 0;
         const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)o0, from), hi = (uint32_t)__shfl((int)(uint32_t)(o0 >> 32), from);
         const uint32_t nn = (uint32_t)__shfl((int)n, from);
-        tail_pass<TAIL>(a, tfw, trc, s_comp, have, ((uint64_t)hi << 32) | lo, nn);
+        tail_pass<TAIL, STEPS>(a, tfw, trc, s_comp, have, ((uint64_t)hi << 32) | lo, nn);
     }
 }
-// Walks the deferred-pair buffer, a wave 64 slots at a time (lane = slot), and sorts the slots' tails by shape, so that a file
-// of trimmed reads keeps every tail length batched and a pass is full whatever the mix.  A read deferred for two leaves gets
-// its tail records written twice (same values).  shapes: bits 0 / 1 / 2 are set when a pass of 4 / 16 / 32 k-mers served a pair.
-__global__ void __launch_bounds__(256) k_tail_records(QueryArgs a, unsigned int *shapes) {
+// Every window the shape passes do not take, of the reads whose bit is set in m (lane = slot; o0 and lim of a read live on its
+// lane: byte offset, and the k-mers to make records for from the first on).  One window of up to 64 k-mers per pass, lane =
+// k-mer, the reads' windows one after the other.  The bytes of the next window — of this read or of the next — are loaded
+// before the current one is hashed and go to the other of two LDS buffers afterwards: the lanes of a wave move in step, so a
+// load issued where its bytes are needed would expose its whole latency once per window.
+template <int STEPS>
+__device__ __forceinline__ void full_windows(const QueryArgs &a, uint32_t *tfw, uint32_t *trc, const uint8_t *s_comp, uint64_t m,
+                                             uint64_t o0, uint64_t lim) {
+    const uint32_t lane = lane_id(), k = a.hp.k;
+    uint64_t nx_o0 = 0, nx_lim = 0, nx_base = 0;  // the window after the one being hashed (wave-uniform)
+    auto advance = [&]() -> bool {
+        nx_base += WIN_KMERS;
+        if (nx_base < nx_lim) return true;
+        if (!m) return false;
+        const int src = __ffsll((unsigned long long)m) - 1;
+        m &= m - 1;
+        nx_o0 = bcast_u64(o0, src);
+        nx_lim = bcast_u64(lim, src);
+        nx_base = 0;
+        return true;
+    };
+    uint8_t b0 = 0, b1 = 0;
+    uint32_t nx_cnt = 0;
+    auto load = [&]() {  // W = cnt + k - 1 <= 127 bytes: two per lane, both issued before either is used
+        nx_cnt = (uint32_t)(nx_lim - nx_base < WIN_KMERS ? nx_lim - nx_base : WIN_KMERS);
+        const uint32_t W = nx_cnt + k - 1u;
+        const uint8_t *src = a.seq + nx_o0 + nx_base;
+        if (lane < W) b0 = src[lane];
+        if (lane + 64u < W) b1 = src[lane + 64u];
+    };
+    auto stash = [&](uint32_t p) {
+        uint8_t *fwd = reinterpret_cast<uint8_t *>(tfw + p * WIN_DWORDS), *rc = reinterpret_cast<uint8_t *>(trc + p * WIN_DWORDS);
+        const uint32_t W = nx_cnt + k - 1u;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < W) {
+            fwd[WIN_PAD + lane] = b0;
+            rc[WIN_PAD + (W - 1u - lane)] = s_comp[b0];
+        }
+        if (lane + 64u < W) {
+            fwd[WIN_PAD + lane + 64u] = b1;
+            rc[WIN_PAD + (W - 1u - lane - 64u)] = s_comp[b1];
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    bool more = advance();
+    if (more) {
+        load();
+        stash(0u);
+    }
+    for (uint32_t p = 0; more; p ^= 1u) {
+        const uint64_t dst = nx_o0 + nx_base;
+        const uint32_t cnt = nx_cnt, W = cnt + k - 1u;
+        more = advance();
+        if (more) load();
+        uint64_t h1, h2;
+        kmer_hashes_at(tfw + p * WIN_DWORDS, trc + p * WIN_DWORDS, WIN_PAD + lane, WIN_PAD + (W - lane - k), lane < cnt, a.hp, h1, h2);
+        const uint4 rec = make_probe_record<STEPS>(h1, h2, a.hp);
+        if (lane < cnt) a.recs[dst + lane] = rec;
+        if (more) stash(p ^ 1u);
+    }
+}
+// The probe records k_classify<DEFER> left out.  Walks the first region of the deferred-pair buffer (the guard pairs of the
+// second belong to reads that have a pair here), a wave 64 slots at a time (lane = slot).
+//   a.batch_tails: last windows of few k-mers (has_batched_tail) are sorted by shape, so that a file of trimmed reads keeps
+//     every tail length batched and a pass is full whatever the mix.
+//   a.split_recs: k_classify hashed no deferred read; every other window is made here too (full_windows), once per read and
+//     not once per pair.  A wave of k_classify emits the pairs of a read into consecutive slots, so a slot whose predecessor
+//     names the same read is not the read's first and is passed over.  The pairs of a read that straddle two reservations
+//     are apart: that read is hashed twice, with equal values, as is a read listed for several leaf groups.
+//   Without a.split_recs a read deferred for two leaves gets its tail records written twice (same values).
+// shapes[0]: bits 0 / 1 / 2 are set when a pass of 4 / 16 / 32 k-mers served a pair, bit 3 when full_windows served a read.
+// STEPS: num_hashes - 3, or -1 (make_probe_record).  70 VGPRs (72 with the rolled walk): 7 waves per SIMD; 11 904 B of LDS a block.
+constexpr uint32_t TAIL_WAVES_PER_SIMD = 7;
+template <int STEPS>
+__global__ void __launch_bounds__(256, TAIL_WAVES_PER_SIMD) k_tail_records(QueryArgs a, unsigned int *shapes) {
     __shared__ uint32_t s_fw[WAVES_PER_BLOCK][TAIL_LDS_BYTES / 4], s_rc[WAVES_PER_BLOCK][TAIL_LDS_BYTES / 4];
     __shared__ uint8_t s_comp[256], s_list[WAVES_PER_BLOCK][3][64];
+    static_assert(2u * WIN_BYTES <= TAIL_LDS_BYTES, "the two window buffers of full_windows fit the wave's LDS");
     fill_complement(s_comp);
     __syncthreads();
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6, k = a.hp.k;
@@ -1371,35 +1445,71 @@ __global__ void __launch_bounds__(256) k_tail_records(QueryArgs a, unsigned int 
     uint32_t *tfw = s_fw[wave], *trc = s_rc[wave];
     const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave, nw = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
     uint32_t used = 0;
-    for (uint64_t s0 = gw * 64u; s0 < n_slots; s0 += nw * 64u) {
+    // A wave's first 64 slots follow from its number, the others are handed out by a counter (shapes[2], zero before the
+    // launch): the slots' work is uneven — voided reservations, reads of many windows — and a wave that ends early would
+    // leave its SIMD with fewer waves to hide the others' latencies.  (One atomic per ~100 hashing passes; none at the start.)
+    unsigned int *const next_step = shapes + 2;
+    for (uint64_t step = gw;; ) {
+        const uint64_t s0 = step * 64u;
+        if (s0 >= n_slots) break;
+        uint32_t got = 0;
+        if (lane == 0) got = atomicAdd(next_step, 1u);
+        step = nw + bcast_u32(got, 0);
         const uint64_t slot = s0 + lane;
         uint32_t r = 0xffffffffu;
         if (slot < n_slots) r = a.pairs[slot].x;
+        bool first = true;  // of the slots of its read
+        if (a.split_recs) {
+            uint32_t before = 0xffffffffu;
+            if (lane == 0 && s0 != 0) before = a.pairs[s0 - 1].x;
+            const uint32_t up = (uint32_t)__shfl_up((int)r, 1);
+            first = r != (lane == 0 ? before : up);
+        }
         uint64_t o0 = 0, n = 0;
-        if (r != 0xffffffffu) {
+        if (r != 0xffffffffu && first) {
             o0 = a.off[r];
             const uint64_t L = a.off[r + 1] - o0;
             n = (L >= k) ? (L - k + 1) : 0;
         }
         const uint32_t tl = (uint32_t)(n & (WIN_KMERS - 1u));
-        const bool have = r != 0xffffffffu && has_batched_tail(n, a.batch_tails) && o0 + n <= a.rec_cap;
+        const bool ok = r != 0xffffffffu && first && o0 + n <= a.rec_cap;
+        const bool have = ok && has_batched_tail(n, a.batch_tails);
+        const uint64_t lim = (a.split_recs && ok) ? (have ? n - tl : n) : 0ull;  // k-mers of the windows before the batched tail
         const uint32_t shape = tl <= 4u ? 0u : (tl <= 16u ? 1u : 2u);
         const uint64_t m0 = ballot64(have && shape == 0u), m1 = ballot64(have && shape == 1u), m2 = ballot64(have && shape == 2u);
-        if ((m0 | m1 | m2) == 0) continue;
-        const uint64_t mine = shape == 0u ? m0 : (shape == 1u ? m1 : m2);
-        __builtin_amdgcn_wave_barrier();
-        if (have) s_list[wave][shape][__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u))] = (uint8_t)lane;
-        __builtin_amdgcn_wave_barrier();
-        tail_passes<4>(a, tfw, trc, s_comp, s_list[wave][0], (uint32_t)__popcll(m0), o0, (uint32_t)n);
-        tail_passes<16>(a, tfw, trc, s_comp, s_list[wave][1], (uint32_t)__popcll(m1), o0, (uint32_t)n);
-        tail_passes<32>(a, tfw, trc, s_comp, s_list[wave][2], (uint32_t)__popcll(m2), o0, (uint32_t)n);
-        used |= (m0 ? 1u : 0u) | (m1 ? 2u : 0u) | (m2 ? 4u : 0u);
+        const uint64_t mf = ballot64(lim != 0);
+        if ((m0 | m1 | m2 | mf) == 0) continue;
+        if (m0 | m1 | m2) {
+            const uint64_t mine = shape == 0u ? m0 : (shape == 1u ? m1 : m2);
+            __builtin_amdgcn_wave_barrier();
+            if (have) s_list[wave][shape][__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u))] = (uint8_t)lane;
+            __builtin_amdgcn_wave_barrier();
+            tail_passes<4, STEPS>(a, tfw, trc, s_comp, s_list[wave][0], (uint32_t)__popcll(m0), o0, (uint32_t)n);
+            tail_passes<16, STEPS>(a, tfw, trc, s_comp, s_list[wave][1], (uint32_t)__popcll(m1), o0, (uint32_t)n);
+            tail_passes<32, STEPS>(a, tfw, trc, s_comp, s_list[wave][2], (uint32_t)__popcll(m2), o0, (uint32_t)n);
+        }
+        if (mf) full_windows<STEPS>(a, tfw, trc, s_comp, mf, o0, lim);
+        used |= (m0 ? TAIL_SHAPE_4 : 0u) | (m1 ? TAIL_SHAPE_16 : 0u) | (m2 ? TAIL_SHAPE_32 : 0u) | (mf ? TAIL_SHAPE_FULL : 0u);
     }
     // (most waves find the bits set already: no wave-count of atomics on one word)
     if (used && lane == 0 && (*(volatile unsigned int *)shapes & used) != used) atomicOr(shapes, used);
 }
+// the carry walk of the records as straight-line code for 4 .. 12 hashes (what filters of 5 .. 17 bits a k-mer ask for)
+template <int STEPS>
+static void launch_tail_records_n(const QueryArgs &a, unsigned int *shapes, int blocks, hipStream_t st) {
+    if constexpr (STEPS > 9) hipLaunchKernelGGL(k_tail_records<-1>, dim3(blocks), dim3(256), 0, st, a, shapes);
+    else if (a.hp.num_hashes == (uint32_t)STEPS + 3u) hipLaunchKernelGGL(k_tail_records<STEPS>, dim3(blocks), dim3(256), 0, st, a, shapes);
+    else launch_tail_records_n<STEPS + 1>(a, shapes, blocks, st);
+}
 void launch_tail_records(const QueryArgs &a, unsigned int *shapes, int blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_tail_records, dim3(blocks), dim3(256), 0, st, a, shapes);
+    // One resident round: four SIMDs x TAIL_WAVES_PER_SIMD waves = that many blocks of four waves a CU.  With full windows a wave
+    // has ~1000 hashing passes to make; the 2048 blocks of the other launches left 256 of them to a second round at one
+    // wave per SIMD, where nothing hides a pass's latencies: 4.15 ms instead of the 3 ms of the grid that fits.
+    int dev = 0, cus = 0;
+    if (a.split_recs && hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+        blocks = cus * (int)TAIL_WAVES_PER_SIMD;
+    launch_tail_records_n<1>(a, shapes, blocks, st);
 }
 
 // ---- bucketing of deferred (read, leaf) pairs by leaf --------------------------------------------------------------
