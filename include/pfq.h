@@ -79,6 +79,14 @@ typedef struct pfq_hits {
  * with PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES, else PFQ_ERR_ARG. */
 #define PFQ_LCA_BEST 32u
 #define PFQ_NO_CLADE 0xffffffffu /* pfq_last_lca: the unit hit nothing */
+/* Abundance: every unit of the call (a read; with PFQ_PAIRED a fragment) is also logged on the device for pfq_abundance_estimate
+ * — exactly the row pfq_hits gives for it.  Only together with PFQ_WANT_HITS (alone: PFQ_ERR_ARG); combines with every other
+ * flag and changes none of their results.  A block whose hit buffer overflowed and ran again is logged once.  Subtree shards:
+ * PFQ_ERR_UNSUPPORTED (a shard sees only its own leaves, so its rows would be partial).  A call whose rows do not fit the log
+ * (PFQ_ABUND_SLOTS, device memory, more than 2^32 - 1 units in all) returns PFQ_ERR_UNSUPPORTED with a message that names the
+ * log: its other results (counts, hits, scores, LCAs) stand, the log keeps what it held and is incomplete until it is reset. */
+#define PFQ_WANT_ABUNDANCE 64u
+#define PFQ_ABUND_Q 16 /* pfq_abundance.mass counts units in steps of 2^-16 */
 
 /* ---- database ---- */
 
@@ -210,6 +218,39 @@ int pfq_clade_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **bel
  * threshold <= 0, all-leaf fragments) gets the LCA of all leaves: the root, or below a root with one child the deepest node
  * of that chain.  Library-owned; valid until the next query call on the tree. */
 int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units);
+
+/* ---- abundance (PFQ_WANT_ABUNDANCE) ----
+ * The log holds, per unit of every PFQ_WANT_ABUNDANCE call since it was last cleared, the unit's row, by class (L = n_leaves):
+ * empty: n_unhit; one leaf l: unique[l]; L > 1 and all L leaves (units without k-mers, threshold <= 0, all-leaf fragments — the
+ * row says nothing about proportions): n_all_leaves; anything else: ambiguous, the row itself is kept in device memory.
+ * pfq_abundance_estimate waits for the queued work and runs an integer EM from a uniform start, every time (the log is not
+ * consumed; more queries may follow): a[l] = 1 << 16; one iteration: new[l] = unique[l] << 16, and every ambiguous row R with
+ * D = sum of a over R > 0 adds (a[l] << 16) / D (unsigned, floor) to new[l] for each l in R (D = 0, possible only for rows of
+ * 65 536 leaves or more, adds nothing); last_delta = max |new[l] - a[l]|; a = new.  It stops after an iteration with
+ * last_delta <= tol (converged = 1), else after max_iters iterations (converged = 0).  The result is a pure function of the
+ * multiset of logged rows: it does not depend on the order of the calls, how the units were split over them, or any knob.
+ * The floor drops less than |R| * 2^-16 units per row and iteration, so the masses sum to slightly less than
+ * (n_unique + n_ambiguous) << 16.  With no unit logged there is nothing to iterate: all masses are 0, iterations = 1,
+ * converged = 1, last_delta = 0.  max_iters == 0: PFQ_ERR_ARG; an incomplete log (see PFQ_WANT_ABUNDANCE): PFQ_ERR_STATE.
+ * mass and unique are library-owned and valid until the next estimate, reset or topology change on the tree.
+ * The log and its counters are cleared by pfq_abundance_reset, pfq_leaf_counts_reset, pfq_tree_prune and pfq_tree_insert (the
+ * leaf columns change meaning); they are not stored by pfq_tree_save.  The leaf counters are untouched by all of this. */
+typedef struct pfq_abundance {
+    uint64_t n_leaves;
+    const uint64_t *mass;    /* [n_leaves] estimated units << 16, leaf order of pfq_leaf_counts; library-owned */
+    const uint64_t *unique;  /* [n_leaves] units whose row is this leaf alone; library-owned */
+    uint64_t n_units, n_unhit, n_unique, n_ambiguous, n_all_leaves;
+    uint64_t n_entries;      /* leaf entries of the ambiguous rows held */
+    uint64_t last_delta;
+    uint32_t iterations, converged;
+} pfq_abundance;
+int pfq_abundance_estimate(pfq_tree *tree, uint32_t max_iters, uint64_t tol, pfq_abundance *out);
+int pfq_abundance_reset(pfq_tree *tree);
+/* Moves src's log (counters, unique, ambiguous rows) into dst's and clears src.  The trees must be replicas: the same
+ * n_leaves, neither a subtree shard, dst != src (else PFQ_ERR_ARG); they may sit on different devices (the rows are staged
+ * through host memory: this runs once per job).  An incomplete log on either side: PFQ_ERR_STATE.  If dst's log cannot take
+ * the rows (as for a query call): PFQ_ERR_UNSUPPORTED, and both logs stay as they were. */
+int pfq_abundance_absorb(pfq_tree *dst, pfq_tree *src);
 
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);

@@ -15,6 +15,7 @@ SYMBOLS = [
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
+    "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
@@ -61,12 +62,21 @@ class Clade(C.Structure):
                 ("name", C.c_char_p)]
 
 
+class Abundance(C.Structure):
+    _fields_ = [("n_leaves", C.c_uint64), ("mass", C.POINTER(C.c_uint64)), ("unique", C.POINTER(C.c_uint64)),
+                ("n_units", C.c_uint64), ("n_unhit", C.c_uint64), ("n_unique", C.c_uint64), ("n_ambiguous", C.c_uint64),
+                ("n_all_leaves", C.c_uint64), ("n_entries", C.c_uint64), ("last_delta", C.c_uint64),
+                ("iterations", C.c_uint32), ("converged", C.c_uint32)]
+
+
 WANT_HITS = 1
 WANT_SCORES = 2
 PAIRED = 4
 PAIR_BOTH = 8
 WANT_LCA = 16
 LCA_BEST = 32
+WANT_ABUNDANCE = 64
+ABUND_Q = 16
 NO_CLADE = 0xFFFFFFFF
 _lib = None
 
@@ -112,6 +122,9 @@ def lib() -> C.CDLL:
     L.pfq_tree_clades.argtypes = [vp, C.POINTER(C.POINTER(Clade)), u64p]
     L.pfq_clade_counts.argtypes = [vp, C.POINTER(u64p), C.POINTER(u64p), u64p]
     L.pfq_last_lca.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), u64p]
+    L.pfq_abundance_estimate.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(Abundance)]
+    L.pfq_abundance_reset.argtypes = [vp]
+    L.pfq_abundance_absorb.argtypes = [vp, vp]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

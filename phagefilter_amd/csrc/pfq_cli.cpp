@@ -1123,6 +1123,28 @@ struct ServedDb {
         }
         if (fclose(f) != 0) die("short write to " + tsv);
     }
+    // --abundance: ABUNDANCE.tsv.  Every replica logged its own units' rows: they are moved into replica 0's log, which is
+    // then estimated once (tol 65: below 0.001 unit).  estimated = mass / 2^16 rounded to three decimals.
+    void save_abundance(const std::string &tsv, uint32_t max_iters) {
+        for (size_t i = 1; i < trees.size(); ++i) check(pfq_abundance_absorb(trees[0], trees[i]));
+        pfq_abundance ab{};
+        check(pfq_abundance_estimate(trees[0], max_iters, 65, &ab));
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+        fputs("#genome\tunique\testimated\tfraction\n", f);
+        fprintf(f, "#units=%llu unhit=%llu unique=%llu ambiguous=%llu all_leaves=%llu iterations=%u converged=%u\n", (unsigned long long)ab.n_units,
+                (unsigned long long)ab.n_unhit, (unsigned long long)ab.n_unique, (unsigned long long)ab.n_ambiguous,
+                (unsigned long long)ab.n_all_leaves, ab.iterations, ab.converged);
+        long double sum = 0;
+        for (uint64_t l = 0; l < ab.n_leaves; ++l) sum += (long double)ab.mass[l];
+        for (uint64_t l = 0; l < ab.n_leaves; ++l) {
+            if (!ab.mass[l]) continue;
+            const unsigned __int128 milli = ((unsigned __int128)ab.mass[l] * 1000 + 32768) >> 16;
+            fprintf(f, "%s\t%llu\t%llu.%03llu\t%.6f\n", leaf_names[l].c_str(), (unsigned long long)ab.unique[l], (unsigned long long)(milli / 1000),
+                    (unsigned long long)(milli % 1000), (double)((long double)ab.mass[l] / sum));
+        }
+        if (fclose(f) != 0) die("short write to " + tsv);
+    }
     void close() {
         for (pfq_tree *t : trees) pfq_tree_close(t);
     }
@@ -1348,6 +1370,8 @@ struct QueryLoop {
     const uint64_t kmer_size;
     const int lca = 0;             // --lca: 0 none, 1 all, 2 best (the library is asked for hits and scores)
     const bool lca_reads = false;  // --lca-reads: READ_LCA.tsv
+    const bool abundance = false;  // --abundance: every call asks for the hits and logs their rows
+    uint32_t abundance_flags() const { return abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u; }
     uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
 
@@ -1364,7 +1388,8 @@ struct QueryLoop {
     void paired(ReadQueue *rq2, bool both) {
         const uint64_t batch_frags = batch_size(1u << 19);
         const bool per_read = pos || neg || scores || lca_reads;
-        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags();
+        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags() |
+                               abundance_flags();
         PairSource src{rq, rq2, {}, {}, 0, {}, false};
         Batch b;
         std::vector<Hits> parts(n_trees());
@@ -1538,7 +1563,7 @@ struct QueryLoop {
         std::vector<Slot> slots(db.devices.size() + 3);
         const size_t NB = slots.size();
         for (Slot &s : slots) s.parts.resize(db.sharded ? n_trees() : 1);
-        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags();
+        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags() | abundance_flags();
         std::mutex mu;
         std::condition_variable cv;
         long long last_seq = -1;                 // sequence number of the last batch, once the assembler knows it
@@ -1844,7 +1869,8 @@ int cmd_query(int argc, char **argv) {
                              {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
-                             {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false}};
+                             {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
+                             {"abundance", 0, false}, {"abundance-iters", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -1866,7 +1892,17 @@ int cmd_query(int argc, char **argv) {
     if (lca && a.val.count("shard-depth"))
         die("error: '--lca' cannot be used with '--shard-depth': a subtree shard holds only its own part of the tree, and combining "
             "the shards' lowest common ancestors needs the whole tree's clades (not implemented)");
-    const bool per_read = filtering || scores || lca == 2 || lca_reads;  // the per-read hit lists are needed
+    // --abundance: every query call also logs its units' hit rows on the device (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE); at the end
+    // an EM over the log estimates how many units every genome produced: ABUNDANCE.tsv
+    const bool abundance = a.flags.count("abundance") != 0;
+    if (a.val.count("abundance-iters") && !abundance) die("error: '--abundance-iters' needs '--abundance'");
+    const uint64_t abundance_iters = to_u64(opt(a, "abundance-iters", "200"), "abundance-iters");
+    if (abundance && (abundance_iters == 0 || abundance_iters > 0xffffffffull))
+        die("error: invalid value '" + opt(a, "abundance-iters", "") + "' for '--abundance-iters': at least 1 iteration");
+    if (abundance && a.val.count("shard-depth"))
+        die("error: '--abundance' cannot be used with '--shard-depth': a subtree shard sees only its own genomes, so the hit rows it "
+            "would log are partial (not implemented)");
+    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
@@ -1944,7 +1980,7 @@ int cmd_query(int argc, char **argv) {
     if (lca_reads) db.load_clade_names();
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance};
     if (block == 0) {
         // nothing to do: see above
     } else if (paired) {
@@ -1969,6 +2005,7 @@ int cmd_query(int argc, char **argv) {
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
     db.save_counts(out + "/CLASSIFICATION.csv");
     if (lca) db.save_clade_counts(out + "/CLADE_COUNTS.tsv");
+    if (abundance) db.save_abundance(out + "/ABUNDANCE.tsv", (uint32_t)abundance_iters);
     db.close();
     printf("Finished.\n");
     return 0;
@@ -2182,6 +2219,15 @@ void usage() {
             "shard holds only its own part of the tree.  With --devices the replicas' counts are summed.\n"
             "--lca-reads (needs --lca): also write READ_LCA.tsv, one line per record with hits in input order (per fragment:\n"
             "R1's id): \"#read_id<TAB>hits<TAB>clade<TAB>name\", hits = the number of genomes hit (also with --lca best)\n"
+            "--abundance: also estimate how many reads (paired input: fragments) every genome produced, and write ABUNDANCE.tsv\n"
+            "into --out.  A read that hits several related genomes counts once for each of them in CLASSIFICATION.csv; here an\n"
+            "EM over all reads' hit lists shares it among them in proportion to the genomes' estimated abundances, so a relative\n"
+            "of a genome that is present keeps little more than the reads only it explains.  \"#genome<TAB>unique<TAB>estimated\n"
+            "<TAB>fraction\", a second # line with the run's totals, then one row per genome with estimated > 0 (unique: reads that\n"
+            "hit this genome alone).  Reads that hit every genome or none are left out.  Every query call then asks the library\n"
+            "for the hit lists, the counts-only mode (no filter, no --scores) too, which so runs at the hit-list rate.  The other\n"
+            "outputs stay as they are.  Not with --shard-depth: a shard sees only its own genomes.  With --devices the replicas'\n"
+            "logs are merged before the estimate.  --abundance-iters <N> (needs --abundance): at most N EM iterations (default 200)\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
 }
 

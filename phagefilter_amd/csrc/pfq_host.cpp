@@ -85,6 +85,7 @@ struct Knobs {
     long long tile = -1, tile_counts = -1, no_tail_batch = -1, split_records = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1;
     long long coarse = -1, coarse_cols = -1, coarse_probes = -1, group_log2 = -1, screen_recs = -1, coarse_min_leaves = -1, greedy_host = -1;
     long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
+    long long abund_slots = -1, abund_blocks = -1, abund_lds = -1;  // PFQ_WANT_ABUNDANCE: cap on the log's leaf entries; grid and LDS use of the EM step
 };
 struct KnobName {
     const char *name;
@@ -110,6 +111,8 @@ const KnobName KNOBS[] = {
     {"PFQ_PAIR_SLOTS", &Knobs::pair_slots},     {"PFQ_GUARD_SLOTS", &Knobs::guard_slots},
     {"PFQ_MISS_WORDS", &Knobs::miss_words},     {"PFQ_KMISS_BYTES", &Knobs::kmiss_bytes},
     {"PFQ_HIT_SLOTS", &Knobs::hit_slots},
+    {"PFQ_ABUND_SLOTS", &Knobs::abund_slots},   {"PFQ_ABUND_BLOCKS", &Knobs::abund_blocks},
+    {"PFQ_ABUND_LDS", &Knobs::abund_lds},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -292,6 +295,16 @@ struct pfq_tree {
     DevBuf<unsigned long long> d_clade_here, d_lca_misc;
     DevBuf<uint2> d_lca_span;
     std::vector<uint64_t> out_here, out_below;
+    // PFQ_WANT_ABUNDANCE: the log of the calls' rows.  Ambiguous rows live in device memory (row r = d_ab_entries[d_ab_start[r]
+    // .. + d_ab_len[r])), rows of one leaf in d_ab_unique; the class counters and the numbers of rows and entries in use are
+    // kept on the host: k_abund_count says what a call adds (d_ab_cur[2..]: five words read back per call) before anything is
+    // appended, so the host makes exactly that much room or refuses the call (d_ab_cur[0..1] hands ab_rows / ab_entries to the
+    // append kernel).  The buffers grow geometrically, with a copy (DevBuf::ensure drops the contents).
+    DevBuf<unsigned long long> d_ab_start, d_ab_unique, d_ab_cur, d_ab_a, d_ab_b, d_ab_delta;
+    DevBuf<uint32_t> d_ab_len, d_ab_entries;
+    uint64_t ab_rows = 0, ab_entries = 0, ab_units = 0, ab_unhit = 0, ab_unique = 0, ab_all = 0;
+    bool ab_incomplete = false;            // a call's rows did not fit: no estimate until the log is reset
+    std::vector<uint64_t> out_mass, out_unique;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -912,6 +925,75 @@ int ensure_lca(pfq_tree &t) {
     return PFQ_OK;
 }
 
+// ---- PFQ_WANT_ABUNDANCE: the log of the calls' rows (pfq_tree::d_ab_*) ----
+static_assert(pfq::ABUND_Q == PFQ_ABUND_Q, "pfq.h and pfq_kernels.h disagree about the mass unit");
+constexpr uint64_t ABUND_MAX_UNITS = 0xffffffffull;  // a[l] < 2^48, so a[l] << 16 fits 64 bits
+constexpr size_t ABUND_LOG_MIN = 1024;               // first allocation of a log buffer (elements); then it at least doubles
+
+// Empties the log and gives its memory back (hipFree waits for the device).
+void abund_clear(pfq_tree &t) {
+    t.d_ab_start.release();
+    t.d_ab_len.release();
+    t.d_ab_entries.release();
+    t.d_ab_unique.release();
+    t.ab_rows = t.ab_entries = t.ab_units = t.ab_unhit = t.ab_unique = t.ab_all = 0;
+    t.ab_incomplete = false;
+}
+// Room for `want` elements with the first `used` kept: max(want, twice the size, ABUND_LOG_MIN), or just `want` where
+// that much memory is not to be had.  On failure the buffer is what it was.  The device is idle (the caller has waited).
+template <typename T>
+hipError_t grow_copy(DevBuf<T> &b, size_t used, size_t want) {
+    if (want <= b.n) return hipSuccess;
+    size_t cap = std::max(std::max(want, 2 * b.n), ABUND_LOG_MIN);
+    T *p = nullptr;
+    hipError_t e = hipMalloc(&p, cap * sizeof(T));
+    if (e != hipSuccess && cap > want) {
+        (void)hipGetLastError();
+        cap = want;
+        e = hipMalloc(&p, cap * sizeof(T));
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e;
+    }
+    if (used) e = hipMemcpy(p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return e;
+    }
+    if (b.p) (void)hipFree(b.p);
+    b.p = p;
+    b.n = cap;
+    return hipSuccess;
+}
+// Why `units` more units with `entries` more leaf entries in ambiguous rows cannot be logged ("" = they can), before anything
+// is changed: the 2^32 - 1 unit bound, the PFQ_ABUND_SLOTS cap.
+std::string abund_refusal(const pfq_tree &t, uint64_t units, uint64_t entries) {
+    if (t.ab_incomplete) return "an earlier call's rows did not fit, the log is incomplete";
+    if (units > ABUND_MAX_UNITS - t.ab_units)
+        return "more than 2^32 - 1 units (" + std::to_string(t.ab_units) + " logged, " + std::to_string(units) + " more)";
+    if (t.knobs.abund_slots >= 0 && t.ab_entries + entries > (uint64_t)t.knobs.abund_slots)
+        return std::to_string(t.ab_entries) + " leaf entries held and " + std::to_string(entries) + " more exceed PFQ_ABUND_SLOTS = " +
+               std::to_string(t.knobs.abund_slots);
+    return "";
+}
+// Device room for `rows` more ambiguous rows with `entries` more entries, and the unique counters.  false: out of memory.
+int abund_room(pfq_tree &t, uint64_t rows, uint64_t entries, bool &ok) {
+    ok = grow_copy(t.d_ab_start, t.ab_rows, t.ab_rows + rows) == hipSuccess && grow_copy(t.d_ab_len, t.ab_rows, t.ab_rows + rows) == hipSuccess &&
+         grow_copy(t.d_ab_entries, t.ab_entries, t.ab_entries + entries) == hipSuccess;
+    if (!ok) return PFQ_OK;
+    if (!t.d_ab_unique.p && !t.leaves.empty()) {
+        HIP_TRY(t.d_ab_unique.ensure(t.leaves.size()));
+        HIP_TRY(hipMemset(t.d_ab_unique.p, 0, t.leaves.size() * 8));
+    }
+    HIP_TRY(t.d_ab_cur.ensure(2 + pfq::ABUND_CNT_N));
+    return PFQ_OK;
+}
+int abund_shard_refused() {
+    return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_ABUNDANCE on a subtree shard: a shard sees only its own leaves, so the rows it would log "
+                                     "are partial");
+}
+
 int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
     HIP_TRY(t.d_stats.ensure(pfq::ST_N));
     HIP_TRY(t.d_cursors.ensure(16));
@@ -988,7 +1070,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
@@ -1018,6 +1100,7 @@ struct QueryRun {
         if (user_hits && !hits) return fail(PFQ_ERR_ARG, "PFQ_WANT_HITS set but hits == NULL");
         want_lca = (flags & PFQ_WANT_LCA) != 0;
         lca_best = (flags & PFQ_LCA_BEST) != 0;
+        want_abund = (flags & PFQ_WANT_ABUNDANCE) != 0;
         if (want_lca) PFQ_TRY(ensure_lca(t));
         want_hits = user_hits || paired || want_lca;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
@@ -1767,6 +1850,7 @@ struct QueryRun {
             hits->n_reads = n_reads;
             hits->offsets = t.h_hit_off;
             hits->leaves = t.h_hit_leaves;
+            if (want_abund) return abund_append(t.d_hit_off.p, t.d_hit_leaves.p, n_reads);
             return PFQ_OK;
         }
         // hit buffer too small: restore the counters and run the block again with room for every hit (whatever PFQ_HIT_SLOTS says)
@@ -1850,6 +1934,48 @@ struct QueryRun {
         hits->n_reads = n_frag;
         hits->offsets = t.h_hit_off;
         hits->leaves = t.h_hit_leaves;
+        if (want_abund) return abund_append(t.d_frag_off.p, t.d_frag_leaves.p, n_frag);
+        return PFQ_OK;
+    }
+
+    // PFQ_WANT_ABUNDANCE: the rows of the call's final CSR (off / leaves, in device memory) go into the log, device to device.
+    // k_abund_count first says what they add; the host reads those five words (the one wait the flag costs), makes exactly
+    // that much room and appends.  The stream is otherwise idle here: PFQ_WANT_HITS has waited for the copies.  Rows that do
+    // not fit: PFQ_ERR_UNSUPPORTED, the call's other results stand (they are complete by now) and the log keeps what it held.
+    int abund_append(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units) {
+        if (!n_units) return PFQ_OK;
+        HIP_TRY(t.d_ab_cur.ensure(2 + pfq::ABUND_CNT_N));
+        unsigned long long *d_cnt = t.d_ab_cur.p + 2, c[pfq::ABUND_CNT_N];
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof c, st));
+        pfq::launch_abund_count(off, n_units, (uint32_t)nl, d_cnt, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c, d_cnt, sizeof c, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint64_t unhit = c[pfq::ABUND_CNT_UNHIT], uniq = c[pfq::ABUND_CNT_UNIQUE], all = c[pfq::ABUND_CNT_ALL], rows = c[pfq::ABUND_CNT_ROWS],
+                       entries = c[pfq::ABUND_CNT_ENTRIES];
+        std::string why = abund_refusal(t, n_units, entries);
+        bool ok = true;
+        if (why.empty()) {
+            PFQ_TRY(abund_room(t, rows, entries, ok));
+            if (!ok) why = "no device memory for " + std::to_string(rows) + " more rows with " + std::to_string(entries) + " leaf entries";
+        }
+        if (!why.empty()) {
+            t.ab_incomplete = true;
+            results_stand = true;
+            return fail(PFQ_ERR_UNSUPPORTED, "abundance log: " + why + ": this call's units were not logged (its other results stand); "
+                                             "pfq_abundance_reset starts a new log");
+        }
+        const unsigned long long cur[2] = {t.ab_rows, t.ab_entries};
+        HIP_TRY(hipMemcpy(t.d_ab_cur.p, cur, sizeof cur, hipMemcpyHostToDevice));
+        pfq::AbundLog g{t.d_ab_start.p, t.d_ab_len.p, t.d_ab_entries.p, t.d_ab_cur.p, t.d_ab_unique.p, t.ab_rows + rows, t.ab_entries + entries};
+        pfq::launch_abund_append(off, leaves, n_units, (uint32_t)nl, g, st);
+        HIP_TRY(hipGetLastError());
+        t.ab_rows += rows;
+        t.ab_entries += entries;
+        t.ab_units += n_units;
+        t.ab_unhit += unhit;
+        t.ab_unique += uniq;
+        t.ab_all += all;
         return PFQ_OK;
     }
 
@@ -1894,7 +2020,7 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
     int rc = q.plan();
     if (rc == PFQ_OK) rc = q.run();
-    t.lca_last = rc == PFQ_OK && (flags & PFQ_WANT_LCA);
+    t.lca_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_LCA);
     if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
     return rc;
 }
@@ -2338,6 +2464,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     PFQ_TRY(sync_counts_to_nodes(t));
     t.layout_valid = false;
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
+    abund_clear(t);       // (the leaf columns change meaning)
     PFQ_TRY(reserve_rows(t, t.n_rows + 2));
     if (!t.greedy_blocks) {
         hipDeviceProp_t prop;
@@ -2629,7 +2756,8 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
     out->shard_first_leaf = t.shard_first_leaf;
     out->tree_leaves = t.is_shard ? t.tree_leaves : out->n_leaves;
     out->device_bytes = t.d_bits.bytes() + t.d_S.bytes() + t.d_pairs.bytes() + t.d_sorted.bytes() + t.d_fail.bytes() +
-                        t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes();
+                        t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes() +
+                        t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes();  // (the abundance log)
     return PFQ_OK;
 }
 
@@ -2646,6 +2774,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
     // nodes below the cut are unreachable now; they keep their slots (and filters) but never appear as leaves
     t.layout_valid = false;
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
+    abund_clear(t);       // (the leaf columns change meaning)
     return PFQ_OK;
 }
 
@@ -2683,6 +2812,8 @@ static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
         return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_LCA on a subtree shard: a shard holds only its own subtree and ancestor chain, not the "
                                          "other shards' topology, so its clades are not the whole tree's");
     if ((flags & PFQ_WANT_SCORES) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SCORES needs PFQ_WANT_HITS");
+    if ((flags & PFQ_WANT_ABUNDANCE) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_ABUNDANCE needs PFQ_WANT_HITS");
+    if ((flags & PFQ_WANT_ABUNDANCE) && t.is_shard) return abund_shard_refused();
     if ((flags & PFQ_PAIRED) && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
     if ((flags & PFQ_PAIR_BOTH) && !(flags & PFQ_PAIRED)) return fail(PFQ_ERR_ARG, "PFQ_PAIR_BOTH needs PFQ_PAIRED");
     return PFQ_OK;
@@ -2772,6 +2903,127 @@ int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units) {
     if (t.lca_units) HIP_TRY(hipMemcpy(t.out_lca.data(), t.d_lca.p, t.lca_units * 4, hipMemcpyDeviceToHost));
     *lca = t.out_lca.data();
     *n_units = t.lca_units;
+    return PFQ_OK;
+}
+
+int pfq_abundance_reset(pfq_tree *tree) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    HIP_TRY(hipDeviceSynchronize());
+    abund_clear(*tree);
+    return PFQ_OK;
+}
+
+int pfq_abundance_estimate(pfq_tree *tree, uint32_t max_iters, uint64_t tol, pfq_abundance *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (!max_iters) return fail(PFQ_ERR_ARG, "pfq_abundance_estimate: max_iters must be at least 1");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    HIP_TRY(hipDeviceSynchronize());  // the queued appends
+    if (t.ab_incomplete)
+        return fail(PFQ_ERR_STATE, "the abundance log is incomplete: a query call's rows did not fit (it returned PFQ_ERR_UNSUPPORTED); "
+                                   "pfq_abundance_reset starts a new log");
+    const size_t nl = t.leaves.size();
+    memset(out, 0, sizeof *out);
+    t.out_mass.assign(nl + 1, 0);
+    t.out_unique.assign(nl + 1, 0);
+    out->n_leaves = nl;
+    out->mass = t.out_mass.data();
+    out->unique = t.out_unique.data();
+    out->n_units = t.ab_units;
+    out->n_unhit = t.ab_unhit;
+    out->n_unique = t.ab_unique;
+    out->n_ambiguous = t.ab_rows;
+    out->n_all_leaves = t.ab_all;
+    out->n_entries = t.ab_entries;
+    out->iterations = 1;
+    out->converged = 1;
+    if (!t.ab_units || !nl) return PFQ_OK;  // nothing logged: nothing to iterate
+    bool ok = true;
+    PFQ_TRY(abund_room(t, 0, 0, ok));  // (the unique counters, should no call have made them)
+    HIP_TRY(t.d_ab_a.ensure(nl));
+    HIP_TRY(t.d_ab_b.ensure(nl));
+    HIP_TRY(t.d_ab_delta.ensure(1));
+    unsigned long long *a = t.d_ab_a.p, *nxt = t.d_ab_b.p;
+    const uint32_t blocks = t.knobs.abund_blocks > 0 ? (uint32_t)std::min<long long>(t.knobs.abund_blocks, 65535) : 0;
+    const bool lds = t.knobs.abund_lds != 0;
+    pfq::launch_abund_start(a, nxt, t.d_ab_unique.p, (uint32_t)nl, nullptr);
+    unsigned long long delta = 0;
+    uint32_t it = 0;
+    bool converged = false;
+    while (it < max_iters && !converged) {
+        HIP_TRY(hipMemsetAsync(t.d_ab_delta.p, 0, 8, nullptr));
+        pfq::AbundStep s{t.d_ab_start.p, t.d_ab_len.p, t.d_ab_entries.p, t.ab_rows, (uint32_t)nl, a, nxt};
+        pfq::launch_abund_step(s, blocks, lds, nullptr);
+        pfq::launch_abund_delta(a, nxt, t.d_ab_unique.p, (uint32_t)nl, t.d_ab_delta.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&delta, t.d_ab_delta.p, 8, hipMemcpyDeviceToHost));  // (the one wait per iteration)
+        std::swap(a, nxt);  // a: this iteration's result; nxt: unique << 16, the next one's start
+        ++it;
+        converged = delta <= tol;
+    }
+    HIP_TRY(hipMemcpy(t.out_mass.data(), a, nl * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.out_unique.data(), t.d_ab_unique.p, nl * 8, hipMemcpyDeviceToHost));
+    out->last_delta = delta;
+    out->iterations = it;
+    out->converged = converged ? 1 : 0;
+    return PFQ_OK;
+}
+
+int pfq_abundance_absorb(pfq_tree *dst, pfq_tree *src) {
+    if (!dst || !src) return fail(PFQ_ERR_ARG, "null argument");
+    if (dst == src) return fail(PFQ_ERR_ARG, "pfq_abundance_absorb: dst and src are one tree");
+    pfq_tree &d = *dst, &s = *src;
+    if (d.is_shard || s.is_shard) return fail(PFQ_ERR_ARG, "pfq_abundance_absorb: a subtree shard has no abundance log");
+    PFQ_TRY(use_device(s.device));
+    PFQ_TRY(build_layout(s));
+    HIP_TRY(hipDeviceSynchronize());
+    PFQ_TRY(use_device(d.device));
+    PFQ_TRY(build_layout(d));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t nl = d.leaves.size();
+    if (s.leaves.size() != nl)
+        return fail(PFQ_ERR_ARG, "pfq_abundance_absorb: the trees are not replicas (" + std::to_string(nl) + " and " + std::to_string(s.leaves.size()) +
+                                 " leaves)");
+    if (d.ab_incomplete || s.ab_incomplete) return fail(PFQ_ERR_STATE, "pfq_abundance_absorb: an abundance log is incomplete; pfq_abundance_reset starts a new one");
+    if (!s.ab_units) return PFQ_OK;
+    std::string why = abund_refusal(d, s.ab_units, s.ab_entries);
+    bool ok = true;
+    if (why.empty()) {
+        PFQ_TRY(abund_room(d, s.ab_rows, s.ab_entries, ok));
+        if (!ok) why = "no device memory for " + std::to_string(s.ab_rows) + " more rows with " + std::to_string(s.ab_entries) + " leaf entries";
+    }
+    if (!why.empty()) return fail(PFQ_ERR_UNSUPPORTED, "abundance log: " + why + ": nothing was absorbed");
+    // staged through host memory: the replicas may sit on different devices, and this runs once per job
+    std::vector<unsigned long long> start(s.ab_rows), uq(nl), uq_d(nl);
+    std::vector<uint32_t> len(s.ab_rows), ent(s.ab_entries);
+    PFQ_TRY(use_device(s.device));
+    if (s.ab_rows) {
+        HIP_TRY(hipMemcpy(start.data(), s.d_ab_start.p, s.ab_rows * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(len.data(), s.d_ab_len.p, s.ab_rows * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ent.data(), s.d_ab_entries.p, s.ab_entries * 4, hipMemcpyDeviceToHost));
+    }
+    if (s.d_ab_unique.p) HIP_TRY(hipMemcpy(uq.data(), s.d_ab_unique.p, nl * 8, hipMemcpyDeviceToHost));
+    for (auto &v : start) v += d.ab_entries;  // src's entries follow dst's
+    PFQ_TRY(use_device(d.device));
+    if (s.ab_rows) {
+        HIP_TRY(hipMemcpy(d.d_ab_start.p + d.ab_rows, start.data(), s.ab_rows * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.d_ab_len.p + d.ab_rows, len.data(), s.ab_rows * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.d_ab_entries.p + d.ab_entries, ent.data(), s.ab_entries * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(uq_d.data(), d.d_ab_unique.p, nl * 8, hipMemcpyDeviceToHost));
+    for (size_t l = 0; l < nl; ++l) uq_d[l] += uq[l];
+    HIP_TRY(hipMemcpy(d.d_ab_unique.p, uq_d.data(), nl * 8, hipMemcpyHostToDevice));
+    d.ab_rows += s.ab_rows;
+    d.ab_entries += s.ab_entries;
+    d.ab_units += s.ab_units;
+    d.ab_unhit += s.ab_unhit;
+    d.ab_unique += s.ab_unique;
+    d.ab_all += s.ab_all;
+    PFQ_TRY(use_device(s.device));
+    abund_clear(s);
+    PFQ_TRY(use_device(d.device));
     return PFQ_OK;
 }
 
@@ -3023,6 +3275,7 @@ int pfq_leaf_counts_reset(pfq_tree *tree) {
         if (tree->lca_valid) HIP_TRY(hipMemset(tree->d_clade_here.p, 0, tree->clades.size() * 8));
     }
     for (auto &nd : tree->nodes) nd.mapped_reads = nd.base_reads = 0;
+    abund_clear(*tree);
     return PFQ_OK;
 }
 

@@ -396,6 +396,43 @@ void launch_lca_rows(const unsigned long long *d_off, const uint32_t *d_leaves, 
                      const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
 void launch_lca_best(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint2 *d_span,
                      uint32_t *d_long, unsigned long long *d_n_long, const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
+// PFQ_WANT_ABUNDANCE (pfq_abund.hip): the device log of the calls' ambiguous rows and the EM over it.
+//   launch_abund_count: d_cnt[ABUND_CNT_*] += what the CSR d_off [n_units] would add to the log, per class (a row's class
+//     follows from its length: 0 unhit, 1 unique, n_leaves > 1 all leaves, else ambiguous) and the ambiguous rows' entries.
+//   launch_abund_append: rows of the ascending CSR d_off / d_leaves [n_units].  A row of one leaf l: unique[l] += 1; a row of two
+//     or more leaves that does not list all n_leaves: appended — cursors[0] rows and cursors[1] entries are in use, and the
+//     caller has made room for what this CSR adds (row_cap, entry_cap: nothing is written beyond them).  Other rows: nothing.
+//   launch_abund_start: a = 1 << ABUND_Q, nxt = unique << ABUND_Q.  launch_abund_step: nxt[l] += (a[l] << ABUND_Q) / D over the
+//     rows (D = the row's sum of a; rows with D = 0 add nothing); blocks = 0: the built-in grid; lds = false: global atomics
+//     only.  launch_abund_delta: *d_delta = max(*d_delta, max |nxt - a|), then a = unique << ABUND_Q (the next iteration's nxt).
+constexpr uint32_t ABUND_Q = 16;
+constexpr uint32_t ABUND_HIST_LDS = 8192;  // step: per-block u64 histogram in LDS up to this many leaves (64 KiB, two blocks per CU)
+constexpr uint32_t ABUND_A_LDS = 4096;     // ... and a[] beside it up to this many
+enum { ABUND_CNT_UNHIT = 0, ABUND_CNT_UNIQUE, ABUND_CNT_ALL, ABUND_CNT_ROWS, ABUND_CNT_ENTRIES, ABUND_CNT_N };
+struct AbundLog {
+    unsigned long long *row_start;  // [row_cap] first entry of the row
+    uint32_t *row_len;              // [row_cap]
+    uint32_t *entries;              // [entry_cap] leaf columns
+    unsigned long long *cursors;    // [2] rows, entries in use
+    unsigned long long *unique;     // [n_leaves]
+    unsigned long long row_cap, entry_cap;
+};
+struct AbundStep {
+    const unsigned long long *row_start;
+    const uint32_t *row_len;
+    const uint32_t *entries;
+    uint64_t n_rows;
+    uint32_t n_leaves;
+    const unsigned long long *a;
+    unsigned long long *nxt;
+};
+void launch_abund_count(const unsigned long long *d_off, uint64_t n_units, uint32_t n_leaves, unsigned long long *d_cnt, hipStream_t st);
+void launch_abund_append(const unsigned long long *d_off, const uint32_t *d_leaves, uint64_t n_units, uint32_t n_leaves, const AbundLog &g,
+                         hipStream_t st);
+void launch_abund_start(unsigned long long *d_a, unsigned long long *d_nxt, const unsigned long long *d_unique, uint32_t n_leaves, hipStream_t st);
+void launch_abund_step(const AbundStep &s, uint32_t blocks, bool lds, hipStream_t st);
+void launch_abund_delta(unsigned long long *d_a, const unsigned long long *d_nxt, const unsigned long long *d_unique, uint32_t n_leaves,
+                        unsigned long long *d_delta, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

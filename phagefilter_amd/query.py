@@ -217,15 +217,16 @@ class BloomTree:
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
                      want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                     lca: Optional[str] = None):
+                     lca: Optional[str] = None, abundance: bool = False):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
         (pair_mode "either") or the intersection ("both") of the mates' sets.
         `lca`: "all" also assigns every read / fragment to the lowest common ancestor of its hit leaves (last_lca(),
         clade_counts()), "best" to that of its best-scoring hits (needs want_hits and want_scores); the return value and
-        every other result stay what they are without it."""
-        lca_flags = _lca_flags(lca, want_hits, want_scores)
+        every other result stay what they are without it.
+        `abundance`: the call's rows are also logged on the device for abundance() (needs want_hits)."""
+        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits)
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -259,12 +260,13 @@ class BloomTree:
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
                           want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                          lca: Optional[str] = None):
+                          lca: Optional[str] = None, abundance: bool = False):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, as in query_packed."""
         hits = _ffi.Hits()
-        flags = _ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | _lca_flags(lca, True, want_scores)
+        flags = (_ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) |
+                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True))
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -276,17 +278,18 @@ class BloomTree:
         return offs, leaves, self.last_hit_scores()
 
     def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
-                    mode: str = "either", lca: Optional[str] = None) -> List[List[int]]:
+                    mode: str = "either", lca: Optional[str] = None, abundance: bool = False) -> List[List[int]]:
         """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
         (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments.
-        `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca()."""
+        `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca().
+        `abundance`: the fragments' rows are also logged for abundance()."""
         if lca not in (None, "all", "best"):
             raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
         if len(r1) != len(r2):
             raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
         seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
         offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best", paired=True,
-                                         pair_mode=mode, lca=lca)[:2]
+                                         pair_mode=mode, lca=lca, abundance=abundance)[:2]
         return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
 
     # ---- clades (lowest common ancestors)
@@ -316,6 +319,30 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_last_lca(self._h, C.byref(p), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
 
+    # ---- abundance (PFQ_WANT_ABUNDANCE)
+    def abundance(self, max_iters: int = 200, tol: int = 65) -> dict:
+        """Per-genome abundance from the rows the `abundance=True` calls have logged (pfq_abundance_estimate): an integer
+        EM from a uniform start that gives every genome its share of the ambiguous rows.  `mass` (numpy uint64, leaf order of
+        get_leaf_counts) is in units of 2**-16 reads / fragments, `tol` likewise (65: below 0.001).  Also `unique`, the class
+        counters n_units, n_unhit, n_unique, n_ambiguous, n_all_leaves, n_entries, and iterations, converged, last_delta.
+        The log is not consumed: more queries and another estimate may follow."""
+        a = _ffi.Abundance()
+        _ffi.check(_ffi.lib().pfq_abundance_estimate(self._h, max_iters, tol, C.byref(a)))
+        n = int(a.n_leaves)
+        out = {"mass": np.ctypeslib.as_array(a.mass, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint64),
+               "unique": np.ctypeslib.as_array(a.unique, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint64)}
+        for k in ("n_units", "n_unhit", "n_unique", "n_ambiguous", "n_all_leaves", "n_entries", "iterations", "converged", "last_delta"):
+            out[k] = int(getattr(a, k))
+        return out
+
+    def abundance_reset(self) -> None:
+        """Empties the abundance log (reset_counts, prune_tree and insert do so as well)."""
+        _ffi.check(_ffi.lib().pfq_abundance_reset(self._h))
+
+    def abundance_absorb(self, other: "BloomTree") -> None:
+        """Moves the abundance log of `other`, a replica of this database (on any device), into this tree's and empties it."""
+        _ffi.check(_ffi.lib().pfq_abundance_absorb(self._h, other._h))
+
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
 
@@ -341,6 +368,14 @@ def _lca_flags(lca: Optional[str], want_hits: bool, want_scores: bool) -> int:
     if not (want_hits and want_scores):
         raise ValueError("lca='best' needs the hits and their scores (want_hits=True, want_scores=True)")
     return _ffi.WANT_LCA | _ffi.LCA_BEST
+
+
+def _abundance_flags(abundance: bool, want_hits: bool) -> int:
+    if not abundance:
+        return 0
+    if not want_hits:
+        raise ValueError("abundance=True needs the hits (want_hits=True): the log holds the rows of the call's hit lists")
+    return _ffi.WANT_ABUNDANCE
 
 
 def _pair_flags(paired: bool, pair_mode: str) -> int:
