@@ -76,6 +76,24 @@ struct DevBuf {
     }
     size_t bytes() const { return n * sizeof(T); }
 };
+// The page-locked host counterpart.  A buffer that grows takes a quarter more than asked plus 4 KiB and drops its contents;
+// what it held before (pointers handed to a caller) stays valid until then.
+template <typename T>
+struct HostBuf {
+    T *p = nullptr;
+    size_t cap = 0;  // bytes
+    ~HostBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t want) {
+        const size_t bytes = want * sizeof(T), grown = bytes + bytes / 4 + 4096;
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipHostMalloc((void **)&p, grown, hipHostMallocDefault);
+        if (e == hipSuccess) cap = grown;
+        return e;
+    }
+};
 
 // Tuning / test knobs.  Never needed for correct results.  The environment is read ONCE, when a tree is
 // created or opened; afterwards pfq_set_option changes a knob of that tree.  -1 / unset = the built-in choice.
@@ -135,6 +153,39 @@ namespace {
 std::atomic<long> g_open_trees{0};
 void release_communicators();  // (the kept RCCL communicators go when the last tree of the process is closed)
 }  // namespace
+
+// Slots of pfq_tree::d_cursors, 8 bytes each.  Every attempt of a query call clears all CUR_ALLOC of them; the kernels only
+// ever receive pointers to single slots.
+enum CursorSlot {
+    CUR_HIT = 0,             // hit pairs written (may exceed the hit buffer: the call then runs again)
+    CUR_PAIR = 1,            // deferred-pair slots reserved
+    CUR_TILE_ENTRIES = 2,    // tile entries the plan asks for
+    CUR_CHUNKS_FLAGGED = 3,  // lo: chunks, hi: flagged pairs
+    CUR_LONG = 4,            // lo: reads of >= 256 k-mers queued by a classify launch (thresholds < 1)
+    CUR_MISS_WORDS = 5,      // miss words handed out
+    CUR_DIRTY = 6,           // pairs with a k-mer missing
+    CUR_OPEN = 7,            // lo: open pairs after the tile passes (thresholds < 1)
+    CUR_GUARD = 8,           // guard-pair slots reserved
+    CUR_KMISS = 9,           // k-mer miss bytes handed out
+    CUR_TAIL_SHAPES = 10,    // lo: tail shapes that served a pair (pfq::TAIL_SHAPE_*)
+    CUR_TAIL_WORK = 11,      // lo: k_tail_records' work counter
+    CUR_N = 12,
+    CUR_ALLOC = 16,          // slots allocated and cleared
+};
+static_assert(CUR_N <= CUR_ALLOC, "an attempt clears CUR_ALLOC slots");
+static_assert(CUR_HIT == 0 && CUR_PAIR == 1, "read_hits reads slots 0 and 1 with one 16-byte copy");
+static_assert(CUR_TAIL_WORK == CUR_TAIL_SHAPES + 1, "k_tail_records finds its work counter at shapes[2]");
+// Slots of pfq_tree::h_pair_cursor, the pinned mirror a bucketed call leaves for the next call's sizing (HINT_N allocated).
+enum HintSlot {
+    HINT_PAIRS = 0,         // CUR_PAIR
+    HINT_TILE_ENTRIES = 1,  // CUR_TILE_ENTRIES
+    HINT_DIRTY = 2,         // CUR_DIRTY
+    HINT_SORTED = 3,        // lo: pairs sorted (the pair cursor also counts partly used reservations)
+    HINT_CANDIDATES = 4,    // ST_CANDIDATES
+    HINT_PLAN = 5,          // not a hint: block mode reads CUR_TILE_ENTRIES back here after the plan
+    HINT_N = 8,
+};
+static_assert(CUR_TILE_ENTRIES == CUR_PAIR + 1 && HINT_TILE_ENTRIES == HINT_PAIRS + 1, "one 16-byte copy fills both hints");
 
 struct pfq_tree {
     pfq_tree() { ++g_open_trees; }
@@ -217,7 +268,9 @@ struct pfq_tree {
     // reduced: the reductions over replicas / ranks add up counters - base, so that stored counts are not added once per replica
     DevBuf<unsigned long long> d_counts_base, d_counts_delta;
     // ---- query scratch
-    DevBuf<unsigned long long> d_stats, d_cursors;  // cursors: [0] hit, [1] pair, [2] tile entries, [3] lo: chunks, hi: flagged pairs, [4] long reads, [5] miss words, [6] dirty pairs, [7] lo: open pairs after the tile passes (thresholds < 1), [8] guard pairs, [9] k-mer miss bytes handed out, [10] tail shapes that served a pair (pfq::TAIL_SHAPE_*), [11] lo: k_tail_records' work counter
+    DevBuf<unsigned long long> d_stats, d_cursors;  // d_cursors: one slot per CursorSlot
+    unsigned int *cur_lo(CursorSlot s) const { return reinterpret_cast<unsigned int *>(d_cursors.p + s); }  // a slot's halves
+    unsigned int *cur_hi(CursorSlot s) const { return cur_lo(s) + 1; }
     DevBuf<uint32_t> d_entries, d_pair_chunk, d_leaf_chunk0, d_flag_list;  // LDS-tile certificates
     DevBuf<pfq::ChunkDesc> d_chunks;
     DevBuf<unsigned int> d_gfill, d_binq;
@@ -271,13 +324,11 @@ struct pfq_tree {
     // per-read hit lists of the last PFQ_WANT_HITS call: built on the device, copied into page-locked host memory
     DevBuf<uint32_t> d_hit_cnt, d_hit_leaves;
     DevBuf<unsigned long long> d_hit_sums, d_hit_off;
-    uint64_t *h_hit_off = nullptr;
-    uint32_t *h_hit_leaves = nullptr;
-    size_t h_hit_off_cap = 0, h_hit_leaves_cap = 0;
+    HostBuf<uint64_t> h_hit_off;
+    HostBuf<uint32_t> h_hit_leaves;
     // PFQ_WANT_SCORES: one score per entry of h_hit_leaves (pfq_last_hit_scores); valid only after a call that asked for them
     DevBuf<uint32_t> d_hit_scores;
-    uint32_t *h_hit_scores = nullptr;
-    size_t h_hit_scores_cap = 0;
+    HostBuf<uint32_t> h_hit_scores;
     bool scores_valid = false;
     uint64_t scores_n = 0;
     // PFQ_PAIRED: the mates' increments land in d_pair_sink (never read); the fragment CSR is built into d_frag_off /
@@ -996,7 +1047,7 @@ int abund_shard_refused() {
 
 int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
     HIP_TRY(t.d_stats.ensure(pfq::ST_N));
-    HIP_TRY(t.d_cursors.ensure(16));
+    HIP_TRY(t.d_cursors.ensure(CUR_ALLOC));
     // two hits per read, or 1.3 x what recent blocks reported (a block that overflows is run again, see query_device)
     const uint64_t cap = (uint64_t)(std::max(2.0, 1.3 * t.hits_per_read) * (double)n_reads) + 1024;
     if (want_hits) {
@@ -1011,18 +1062,18 @@ constexpr uint64_t CLASSIFY_MAX_BLOCKS = 4096;  // blocks of 4 waves; every wave
 // Scratch of the bucketed path.  false: not enough device memory, the caller stays on the direct kernel.
 bool ensure_bucket_scratch(pfq_tree &t, uint64_t n_reads, bool with_guards, uint64_t launch_waves) {
     if (!t.h_pair_cursor) {
-        if (hipHostMalloc((void **)&t.h_pair_cursor, 64, hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc((void **)&t.h_pair_cursor, HINT_N * 8, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             t.h_pair_cursor = nullptr;
             return false;
         }
-        for (int i = 0; i < 8; ++i) t.h_pair_cursor[i] = 0;
+        for (int i = 0; i < HINT_N; ++i) t.h_pair_cursor[i] = 0;
         if (hipEventCreateWithFlags(&t.hint_ev, hipEventDisableTiming) != hipSuccess) return false;
     } else if (t.hint_reads && hipEventQuery(t.hint_ev) == hipSuccess) {
-        t.pairs_per_read = std::max(t.pairs_per_read, (double)t.h_pair_cursor[0] / (double)t.hint_reads);
-        if (t.hint_entry_cap) t.passes_hint = std::max<uint64_t>(1, (t.h_pair_cursor[1] + t.hint_entry_cap - 1) / t.hint_entry_cap);
-        if (t.hint_counts) t.dirty_frac = (double)t.h_pair_cursor[2] / (double)std::max<unsigned long long>(1, t.h_pair_cursor[3] & 0xffffffffull);
-        t.cand_per_read = (double)t.h_pair_cursor[4] / (double)t.hint_reads;
+        t.pairs_per_read = std::max(t.pairs_per_read, (double)t.h_pair_cursor[HINT_PAIRS] / (double)t.hint_reads);
+        if (t.hint_entry_cap) t.passes_hint = std::max<uint64_t>(1, (t.h_pair_cursor[HINT_TILE_ENTRIES] + t.hint_entry_cap - 1) / t.hint_entry_cap);
+        if (t.hint_counts) t.dirty_frac = (double)t.h_pair_cursor[HINT_DIRTY] / (double)std::max<unsigned long long>(1, t.h_pair_cursor[HINT_SORTED] & 0xffffffffull);
+        t.cand_per_read = (double)t.h_pair_cursor[HINT_CANDIDATES] / (double)t.hint_reads;
         t.have_cand_hint = true;
         t.hint_reads = 0;
     }
@@ -1057,8 +1108,9 @@ constexpr uint64_t SLICE_TARGET_BYTES = 2560ull << 10;
 // the device has left and — block mode, on a tree without history — a screened sample of the block's own reads; attempt() is
 // one run of the kernels (a second one only when the hit buffer proved too small), stage by stage: frontier(), then on the
 // bucketed path setup_pairs() -> frontier(true) -> expand guards / tail records -> bucket_sort() -> setup_verify() ->
-// tile_stage() -> finish_blocks() or finish_pairs(); read_hits() brings the per-read hit lists back.  Everything is queued on
-// `st`; results never depend on which modes were chosen.
+// tile_stage() -> finish_blocks() or finish_pairs().  read_hits() then looks at the hit pairs: it asks for the second attempt,
+// or builds the reads' CSR (fragments: pair_hits()), which deliver_rows() hands to the caller with the scores, the LCAs and
+// the abundance log.  Everything is queued on `st`; results never depend on which modes were chosen.
 struct QueryRun {
     pfq_tree &t;
     const uint8_t *d_seq;
@@ -1071,6 +1123,8 @@ struct QueryRun {
     const Knobs &kn;
     // ---- the plan
     bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
+    bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
@@ -1163,6 +1217,8 @@ struct QueryRun {
         if (block_mode && !soft_ensure(t.d_T, n_blocks * t.n_words * 64)) block_mode = false;
         if (block_mode && !soft_ensure(t.d_failb, t.d_pairs.n * 8)) block_mode = false;
         if (block_mode) nc = n_blocks * 256;  // buckets by (block, candidate mask)
+        pair_miss = counts_mode && !block_mode;  // (block_mode is final here; neither flag depends on `bucketed`)
+        guard_pairs = with_guards && !block_mode;
         t.last_block_mode = 0;
         miss_cap = 0;
         nb = 0;
@@ -1172,7 +1228,7 @@ struct QueryRun {
             while (sub_log2 < 6 && (nc << sub_log2) < 1024) ++sub_log2;
             nb = nc << sub_log2;
             if (block_mode && !soft_ensure(t.d_bucket, 3 * nb + 2)) bucketed = false;  // (buckets by (block, mask) outnumber the columns of small trees)
-            if (counts_mode && !block_mode) {  // thresholds < 1: every deferred pair owns ceil(n/64) words of k-mer miss bits that the slices OR into
+            if (pair_miss) {  // thresholds < 1: every deferred pair owns ceil(n/64) words of k-mer miss bits that the slices OR into
                 const uint64_t avg_len = n_reads ? total_bytes / n_reads : 0;
                 miss_cap = std::min<uint64_t>((t.leaf_cap + t.guard_cap) * ((avg_len >> 6) + 2) + (launch_waves + 4 * 2048) * (uint64_t)pfq::MISS_RESERVE, 0xfffffff0ull);
                 if (!(soft_ensure(t.d_miss_words, miss_cap) && soft_ensure(t.d_miss_pos, t.d_pairs.n) && soft_ensure(t.d_bucket_w, 3 * nb + 2)))
@@ -1192,43 +1248,43 @@ struct QueryRun {
         return PFQ_OK;
     }
 
+    // what every classify launch of this call is told about the block, the threshold and the tree's layout; the callers add
+    // the number of reads and where the launch counts and lists hits
+    pfq::QueryArgs base_args() const {
+        pfq::QueryArgs q{};
+        q.hp = t.hp;
+        q.seq = d_seq;
+        q.off = d_off;
+        q.threshold = threshold;
+        q.S_all = t.d_S.p;
+        q.group_stride = t.group_stride;
+        q.group_log2 = t.group_log2;
+        q.ones_row = (uint32_t)(t.n_words * 64);
+        q.rw = t.rw;
+        q.rw_log2 = t.rw_log2;
+        q.n_cols = t.n_cols;
+        q.guard_off = t.d_guard_off.p;
+        q.guard_col = t.d_guard_col.p;
+        q.hit_cursor = t.d_cursors.p + CUR_HIT;
+        q.stats = t.d_stats.p;
+        if (counts_mode) {  // thresholds < 1: the queue of reads of >= 256 k-mers (d_long holds n_reads + 1 by now)
+            q.long_list = t.d_long.p;
+            q.n_long = t.cur_lo(CUR_LONG);
+        }
+        return q;
+    }
+
     // Candidates per read of the first reads of this block: the frontier only, nothing is certified or counted.
     int sample_candidates() {
         const uint64_t n_s = std::min<uint64_t>(n_reads, 16384);
         HIP_TRY(hipMemsetAsync(t.d_stats.p, 0, pfq::ST_N * 8, st));
-        HIP_TRY(hipMemsetAsync(t.d_cursors.p, 0, 128, st));
-        pfq::QueryArgs sa{};
-        sa.hp = t.hp;
-        sa.seq = d_seq;
-        sa.off = d_off;
+        HIP_TRY(hipMemsetAsync(t.d_cursors.p, 0, CUR_ALLOC * 8, st));
+        if (counts_mode) HIP_TRY(t.d_long.ensure(n_reads + 1));
+        pfq::QueryArgs sa = base_args();
         sa.n_reads = n_s;
-        sa.threshold = threshold;
-        sa.S_all = t.d_S.p;
-        sa.group_stride = t.group_stride;
-        sa.group_log2 = t.group_log2;
-        sa.ones_row = (uint32_t)(t.n_words * 64);
-        sa.rw = t.rw;
-        sa.rw_log2 = t.rw_log2;
-        sa.n_cols = t.n_cols;
-        sa.guard_off = t.d_guard_off.p;
-        sa.guard_col = t.d_guard_col.p;
         sa.counts = t.d_counts.p;
-        sa.hit_cursor = t.d_cursors.p;
-        sa.stats = t.d_stats.p;
         sa.screen_only = 1;
-        if (!(threshold >= 1.0f)) {
-            HIP_TRY(t.d_long.ensure(n_reads + 1));
-            sa.long_list = t.d_long.p;
-            sa.n_long = reinterpret_cast<unsigned int *>(t.d_cursors.p + 4);
-        }
-        for (uint32_t g = 0; g < leaf_groups; ++g) {
-            sa.S = t.d_S.p + (uint64_t)g * t.group_stride;
-            sa.col0 = g * group_cols;
-            sa.n_leaves = (uint32_t)std::min<size_t>(group_cols, nl - (size_t)g * group_cols);
-            sa.first_group = g == 0;
-            if (g && !(threshold >= 1.0f)) HIP_TRY(hipMemsetAsync(t.d_cursors.p + 4, 0, 8, st));
-            pfq::launch_classify(sa, false, !(threshold >= 1.0f), (int)std::min<uint64_t>((n_s + 3) / 4, CLASSIFY_MAX_BLOCKS), st);
-        }
+        PFQ_TRY(classify_groups(sa, false, (int)std::min<uint64_t>((n_s + 3) / 4, CLASSIFY_MAX_BLOCKS)));
         HIP_TRY(hipGetLastError());
         unsigned long long cand = 0;
         HIP_TRY(hipMemcpyAsync(&cand, t.d_stats.p + pfq::ST_CANDIDATES, 8, hipMemcpyDeviceToHost, st));
@@ -1317,17 +1373,21 @@ struct QueryRun {
             a.grid_groups = 0;
             if (counts_mode) {
                 a.long_list = t.d_long.p;
-                a.n_long = reinterpret_cast<unsigned int *>(t.d_cursors.p + 4);
+                a.n_long = t.cur_lo(CUR_LONG);
             }
             return PFQ_OK;
         }
+        return classify_groups(a, defer, blocks);
+    }
+    // one classify launch per column group that holds leaves, on all reads
+    int classify_groups(pfq::QueryArgs &q, bool defer, int n_blocks_launch) {
         for (uint32_t g = 0; g < leaf_groups; ++g) {
-            a.S = t.d_S.p + (uint64_t)g * t.group_stride;
-            a.col0 = g * group_cols;
-            a.n_leaves = (uint32_t)std::min<size_t>(group_cols, nl - (size_t)g * group_cols);
-            a.first_group = g == 0;
-            if (g && counts_mode) HIP_TRY(hipMemsetAsync(t.d_cursors.p + 4, 0, 8, st));  // the queue of long reads is per launch
-            pfq::launch_classify(a, defer, counts_mode, blocks, st);
+            q.S = t.d_S.p + (uint64_t)g * t.group_stride;
+            q.col0 = g * group_cols;
+            q.n_leaves = (uint32_t)std::min<size_t>(group_cols, nl - (size_t)g * group_cols);
+            q.first_group = g == 0;
+            if (g && counts_mode) HIP_TRY(hipMemsetAsync(t.d_cursors.p + CUR_LONG, 0, 8, st));  // the queue of long reads is per launch
+            pfq::launch_classify(q, defer, counts_mode, n_blocks_launch, st);
         }
         return PFQ_OK;
     }
@@ -1335,39 +1395,20 @@ struct QueryRun {
     int attempt(int attempt_no) {
         t.last_attempts = (uint32_t)attempt_no + 1;
         HIP_TRY(hipMemsetAsync(t.d_stats.p, 0, pfq::ST_N * 8, st));
-        HIP_TRY(hipMemsetAsync(t.d_cursors.p, 0, 128, st));
+        HIP_TRY(hipMemsetAsync(t.d_cursors.p, 0, CUR_ALLOC * 8, st));
         if (want_hits) {
             HIP_TRY(hipMemsetAsync(t.d_allhit.p, 0, n_reads + 1, st));
             if (attempt_no == 0 && nl)
                 HIP_TRY(hipMemcpyAsync(t.d_counts_snapshot.p, t.d_counts.p, nl * 8, hipMemcpyDeviceToDevice, st));
         }
         if (n_reads && nl) {
-            a = pfq::QueryArgs{};
-            a.hp = t.hp;
-            a.seq = d_seq;
-            a.off = d_off;
+            if (counts_mode) HIP_TRY(t.d_long.ensure(n_reads + 1));
+            a = base_args();
             a.n_reads = n_reads;
-            a.threshold = threshold;
-            a.S_all = t.d_S.p;
-            a.group_stride = t.group_stride;
-            a.group_log2 = t.group_log2;
-            a.ones_row = (uint32_t)(t.n_words * 64);
-            a.rw = t.rw;
-            a.rw_log2 = t.rw_log2;
-            a.n_cols = t.n_cols;
-            a.guard_off = t.d_guard_off.p;
-            a.guard_col = t.d_guard_col.p;
             a.counts = count_dst();
             a.hit_pairs = want_hits ? t.d_hit_pairs.p : nullptr;
             a.hit_cap = hit_cap;
-            a.hit_cursor = t.d_cursors.p;
             a.allhit_flag = want_hits ? t.d_allhit.p : nullptr;
-            a.stats = t.d_stats.p;
-            if (counts_mode) {
-                HIP_TRY(t.d_long.ensure(n_reads + 1));
-                a.long_list = t.d_long.p;
-                a.n_long = reinterpret_cast<unsigned int *>(t.d_cursors.p + 4);
-            }
             ev = nullptr;
             if (t.prof_used < t.prof_cap) {
                 ev = &t.prof_ev[PROF_EV * t.prof_used];
@@ -1391,11 +1432,11 @@ struct QueryRun {
             HIP_TRY(hipGetLastError());
         }
         if (bucketed) {  // how many pair slots this call used, for the next call's sizing
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor, t.d_cursors.p + 1, 16, hipMemcpyDeviceToHost, st));  // pair cursor, bucket cursor
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + 2, t.d_cursors.p + 6, 8, hipMemcpyDeviceToHost, st));  // pairs with a k-mer missing
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + 4, t.d_stats.p + pfq::ST_CANDIDATES, 8, hipMemcpyDeviceToHost, st));  // candidate leaves
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_PAIRS, t.d_cursors.p + CUR_PAIR, 16, hipMemcpyDeviceToHost, st));  // and HINT_TILE_ENTRIES
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_DIRTY, t.d_cursors.p + CUR_DIRTY, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_CANDIDATES, t.d_stats.p + pfq::ST_CANDIDATES, 8, hipMemcpyDeviceToHost, st));
             if (n_reads && nl)  // ... of how many sorted pairs (the pair cursor also counts partly used reservations)
-                HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + 3, t.d_bucket.p + 2 * (nc << t.last_sub_log2), 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_SORTED, t.d_bucket.p + 2 * (nc << t.last_sub_log2), 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(t.hint_ev, st));
             t.hint_reads = n_reads;
         }
@@ -1415,21 +1456,21 @@ struct QueryRun {
         a.pair_cap = t.leaf_cap;  // whole reservations only (PAIR_CHUNK = 32)
         if (kn.pair_slots >= 0) a.pair_cap = std::min<uint64_t>(a.pair_cap, (uint64_t)kn.pair_slots & ~(uint64_t)(pfq::PAIR_RESERVE - 1));
         t.last_pair_cap = a.pair_cap;
-        a.pair_cursor = t.d_cursors.p + 1;
+        a.pair_cursor = t.d_cursors.p + CUR_PAIR;
         a.bucket_cnt = cnt;
         a.sub_log2 = sub_log2;
         recs = recs_possible ? t.d_recs.p : nullptr;
         a.recs = recs;
         a.rec_cap = recs ? t.d_recs.n : 0;
         cntw = offw = curw = nullptr;
-        if (counts_mode && !block_mode) {
+        if (pair_miss) {
             cntw = t.d_bucket_w.p;
             offw = cntw + nb;
             curw = offw + nb + 1;
             HIP_TRY(hipMemsetAsync(t.d_miss_words.p, 0, miss_cap * 8, st));
             HIP_TRY(hipMemsetAsync(cntw, 0, nb * 4, st));
             a.bucket_words = cntw;
-            a.miss_cursor = t.d_cursors.p + 5;
+            a.miss_cursor = t.d_cursors.p + CUR_MISS_WORDS;
             a.miss_cap = miss_cap;
         }
         n_slices = 1;
@@ -1466,32 +1507,31 @@ struct QueryRun {
     // guard columns of the deferred pairs (pairs of their own), the probe records of the deferred reads
     int guards_and_tails() {
         ga = pfq::GuardArgs{};
-        if (with_guards && !block_mode) {  // every guard of a deferred pair's leaf becomes a pair of its own (second region of the buffer)
+        if (guard_pairs) {  // every guard of a deferred pair's leaf becomes a pair of its own (second region of the buffer)
             ga.pairs = t.d_pairs.p + t.leaf_cap;
             ga.cap = t.guard_cap;
             if (kn.guard_slots >= 0) ga.cap = std::min<uint64_t>(ga.cap, (uint64_t)kn.guard_slots);
             t.last_guard_cap = ga.cap;
-            ga.cursor = t.d_cursors.p + 8;
+            ga.cursor = t.d_cursors.p + CUR_GUARD;
             ga.slot0 = (uint32_t)t.leaf_cap;
             ga.owner = t.d_owner.p;
             ga.gfail = t.d_gfail.p;
             pfq::launch_expand_guards(a, ga, 2048, st);
         }
-        if (a.batch_tails || a.split_recs) pfq::launch_tail_records(a, reinterpret_cast<unsigned int *>(t.d_cursors.p + 10), 2048, st);
+        if (a.batch_tails || a.split_recs) pfq::launch_tail_records(a, t.cur_lo(CUR_TAIL_SHAPES), 2048, st);
         if (ev) HIP_TRY(hipEventRecord(ev[1], st));
         return PFQ_OK;
     }
     // counting sort of the pairs by column (block mode: by (block, candidate mask))
     int bucket_sort() {
         pfq::launch_bucket_scan(cnt, off, cur, (uint32_t)nb, st);
-        if (counts_mode && !block_mode) pfq::launch_bucket_scan(cntw, offw, curw, (uint32_t)nb, st);
-        t.last_sort = pfq::launch_bucket_scatter(t.d_pairs.p, t.d_cursors.p + 1, a.pair_cap, off, cur, (uint32_t)nb, sub_log2, t.d_sorted.p,
+        if (pair_miss) pfq::launch_bucket_scan(cntw, offw, curw, (uint32_t)nb, st);
+        t.last_sort = pfq::launch_bucket_scatter(t.d_pairs.p, t.d_cursors.p + CUR_PAIR, a.pair_cap, off, cur, (uint32_t)nb, sub_log2, t.d_sorted.p,
                                                  recs ? t.d_meta.p : nullptr, d_off, block_mode ? nullptr : t.d_col_row.p, offw, curw,
-                                                 (counts_mode && !block_mode) ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
-                                                 (with_guards && !block_mode) ? t.d_owner.p : nullptr,
-                                                 (with_guards && !block_mode) ? t.d_owner_sorted.p : nullptr,
+                                                 pair_miss ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
+                                                 guard_pairs ? t.d_owner.p : nullptr, guard_pairs ? t.d_owner_sorted.p : nullptr,
                                                  block_mode ? 2u : 0u, st);
-        if (with_guards && !block_mode)  // (the guard pairs reserve on the same cursors)
+        if (guard_pairs)  // (the guard pairs reserve on the same cursors)
             pfq::launch_bucket_scatter(ga.pairs, ga.cursor, ga.cap, off, cur, (uint32_t)nb, sub_log2, t.d_sorted.p,
                                        recs ? t.d_meta.p : nullptr, d_off, t.d_col_row.p, offw, curw,
                                        counts_mode ? t.d_miss_pos.p : nullptr, (uint32_t)t.kmer_size,
@@ -1511,8 +1551,8 @@ struct QueryRun {
         v.n_pairs_ptr = off + nb;
         v.fail = t.d_fail.p;
         v.recs = recs;
-        v.miss_words = (counts_mode && !block_mode) ? t.d_miss_words.p : nullptr;
-        v.miss_pos = (counts_mode && !block_mode) ? t.d_miss_pos.p : nullptr;
+        v.miss_words = pair_miss ? t.d_miss_words.p : nullptr;
+        v.miss_pos = pair_miss ? t.d_miss_pos.p : nullptr;
         v.meta = t.d_meta.p;
         v.n_slices = n_slices;
         uint64_t sb = (t.n_words * 64 + n_slices - 1) / n_slices;
@@ -1595,11 +1635,11 @@ struct QueryRun {
                 ta.max_chunks = (uint32_t)max_chunks;
                 ta.leaf_chunk0 = t.d_leaf_chunk0.p;
                 ta.pair_chunk = t.d_pair_chunk.p;
-                ta.n_chunks = reinterpret_cast<unsigned int *>(t.d_cursors.p + 3);
-                ta.n_flagged = reinterpret_cast<unsigned int *>(t.d_cursors.p + 3) + 1;
+                ta.n_chunks = t.cur_lo(CUR_CHUNKS_FLAGGED);
+                ta.n_flagged = t.cur_hi(CUR_CHUNKS_FLAGGED);
                 ta.flag_list = t.d_flag_list.p;
                 ta.flag_cap = (uint32_t)std::min<uint64_t>(t.d_flag_list.n, 0xffffffffu);
-                ta.entry_cursor = t.d_cursors.p + 2;
+                ta.entry_cursor = t.d_cursors.p + CUR_TILE_ENTRIES;
                 // (a multiple of 32 entries: buckets then start on 128-byte boundaries, k_tile_test reads them 16 bytes at a time)
                 ta.entry_cap = std::min<uint64_t>(want, t.d_entries.n) & ~31ull;  // (the buffer only grows; the budget of this call is `want`)
                 ta.entries = t.d_entries.p;
@@ -1612,7 +1652,7 @@ struct QueryRun {
                     ta.kmiss = t.d_kmiss.p;
                     ta.kmiss_cap = kmiss_cap;
                     t.last_kmiss_cap = kmiss_cap;
-                    ta.kmiss_used = t.d_cursors.p + 9;
+                    ta.kmiss_used = t.d_cursors.p + CUR_KMISS;
                     ta.round_k0 = t.d_round_k0.p;
                     ta.n_rounds = t.d_n_rounds.p;
                     ta.pair_kpos = t.d_pair_kpos.p;
@@ -1630,9 +1670,9 @@ struct QueryRun {
                 // passes (if any) are certified by the record kernel below — exact either way.
                 uint64_t n_passes = std::min<uint64_t>(std::max<uint64_t>(1, t.passes_hint), 256);  // (more: the record kernel takes the rest)
                 if (block_mode) {  // the fallback of block mode is slow: wait for the plan and launch every pass it needs
-                    HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + 5, t.d_cursors.p + 2, 8, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_PLAN, t.d_cursors.p + CUR_TILE_ENTRIES, 8, hipMemcpyDeviceToHost, st));
                     HIP_TRY(hipStreamSynchronize(st));
-                    n_passes = ta.entry_cap ? std::min<uint64_t>(std::max<uint64_t>(1, (t.h_pair_cursor[5] + ta.entry_cap - 1) / ta.entry_cap), 256) : 1;
+                    n_passes = ta.entry_cap ? std::min<uint64_t>(std::max<uint64_t>(1, (t.h_pair_cursor[HINT_PLAN] + ta.entry_cap - 1) / ta.entry_cap), 256) : 1;
                 }
                 for (uint64_t p = 0; p < n_passes; ++p) {
                     ta.pass = (uint32_t)p;
@@ -1643,19 +1683,15 @@ struct QueryRun {
                 }
                 v.pair_chunk = t.d_pair_chunk.p;
                 v.chunks = t.d_chunks.p;
-                v.entry_cursor = t.d_cursors.p + 2;
+                v.entry_cursor = t.d_cursors.p + CUR_TILE_ENTRIES;
                 v.entry_cap = ta.entry_cap;
                 v.launched_passes = (uint32_t)n_passes;
-                if (counts_mode && !block_mode) {  // binned pairs whose prefix of k-mers leaves them undecided go to the record kernel
+                if (pair_miss) {  // binned pairs whose prefix of k-mers leaves them undecided go to the record kernel
                     pfq::FinalizeArgs pf{};
                     pf.hp = t.hp;
                     pf.threshold = threshold;
                     pf.fail = t.d_fail.p;
-                    pf.kmiss = t.d_kmiss.p;
-                    pf.pair_kpos = t.d_pair_kpos.p;
-                    pf.pair_chunk = t.d_pair_chunk.p;
-                    pf.chunks = t.d_chunks.p;
-                    pf.launched_passes = (uint32_t)n_passes;
+                    binned_miss(pf, (uint32_t)n_passes);
                     pfq::launch_prefix_open(pf, t.d_meta.p, off + nb, t.d_fail.p, st);
                 }
                 t.hint_entry_cap = ta.entry_cap;
@@ -1674,6 +1710,30 @@ struct QueryRun {
         }
         return PFQ_OK;
     }
+    // thresholds < 1 after tile passes: the miss bits of the binned pairs are in their chunks' bitmaps
+    void binned_miss(pfq::FinalizeArgs &f, uint32_t launched_passes) const {
+        f.kmiss = t.d_kmiss.p;
+        f.pair_kpos = t.d_pair_kpos.p;
+        f.pair_chunk = t.d_pair_chunk.p;
+        f.chunks = t.d_chunks.p;
+        f.launched_passes = launched_passes;
+    }
+    // what k_finalize needs on either side: the sorted pairs, where hits and counts go
+    pfq::FinalizeArgs finalize_args() const {
+        pfq::FinalizeArgs f{};
+        f.hp = t.hp;
+        f.off = d_off;
+        f.sorted = t.d_sorted.p;
+        f.bucket_off = off;
+        f.sub_log2 = sub_log2;
+        f.threshold = threshold;
+        f.counts = count_dst();
+        f.hit_pairs = a.hit_pairs;
+        f.hit_cap = hit_cap;
+        f.hit_cursor = t.d_cursors.p + CUR_HIT;
+        f.stats = t.d_stats.p;
+        return f;
+    }
     int finish_blocks() {
         // what the passes did not bin (overflows, no room, or no passes at all) is certified leaf by leaf against S
         a.S = t.d_S.p;
@@ -1686,12 +1746,8 @@ struct QueryRun {
             cf.sorted = t.d_sorted.p;
             cf.threshold = threshold;
             cf.fail = t.d_fail.p;
-            cf.kmiss = t.d_kmiss.p;
             cf.kall = t.d_kall.p;
-            cf.pair_kpos = t.d_pair_kpos.p;
-            cf.pair_chunk = t.d_pair_chunk.p;
-            cf.chunks = t.d_chunks.p;
-            cf.launched_passes = v.launched_passes;
+            binned_miss(cf, v.launched_passes);
             pfq::launch_block_count(cf, off + nb, t.d_failb.p, st);
         }
         pfq::launch_block_fallback(a, t.d_sorted.p, off + nb, t.d_fail.p, t.d_failb.p, t.d_pair_chunk.p,
@@ -1701,18 +1757,7 @@ struct QueryRun {
         // that is still standing
         if (with_guards) pfq::launch_block_guards(a, t.d_sorted.p, off + nb, t.d_failb.p, st);
         if (ev) HIP_TRY(hipEventRecord(ev[5], st));
-        pfq::FinalizeArgs f{};
-        f.hp = t.hp;
-        f.off = d_off;
-        f.sorted = t.d_sorted.p;
-        f.bucket_off = off;
-        f.sub_log2 = sub_log2;
-        f.threshold = threshold;
-        f.counts = count_dst();
-        f.hit_pairs = a.hit_pairs;
-        f.hit_cap = hit_cap;
-        f.hit_cursor = t.d_cursors.p;
-        f.stats = t.d_stats.p;
+        pfq::FinalizeArgs f = finalize_args();
         f.failb = t.d_failb.p;
         f.c0 = 0;
         f.c1 = (uint32_t)nc;
@@ -1726,7 +1771,7 @@ struct QueryRun {
     int finish_pairs() {
         if (v.only_flagged == 1 && counts_mode) {
             // thresholds < 1: the list becomes every pair the tile passes left open (a k-mer missing, or not binned)
-            unsigned int *n_open = reinterpret_cast<unsigned int *>(t.d_cursors.p + 7);
+            unsigned int *n_open = t.cur_lo(CUR_OPEN);
             pfq::launch_collect_open(t.d_fail.p, off + nb, t.d_flag_list.p, v.flag_cap, n_open, st);
             v.n_flagged = n_open;
         }
@@ -1737,29 +1782,12 @@ struct QueryRun {
             pfq::launch_verify(v, vblocks, vthreads, st);
         }
         if (ev) HIP_TRY(hipEventRecord(ev[5], st));
-        pfq::FinalizeArgs f{};
-        f.hp = t.hp;
-        f.off = d_off;
-        f.sorted = t.d_sorted.p;
-        f.bucket_off = off;
-        f.sub_log2 = sub_log2;
+        pfq::FinalizeArgs f = finalize_args();
         f.fail = t.d_fail.p;
         f.miss_words = v.miss_words;
         f.miss_pos = v.miss_pos;
-        f.threshold = threshold;
-        f.counts = count_dst();
-        f.hit_pairs = a.hit_pairs;
-        f.hit_cap = hit_cap;
-        f.hit_cursor = t.d_cursors.p;
-        f.stats = t.d_stats.p;
-        f.n_dirty = t.d_cursors.p + 6;
-        if (counts_mode && t.last_tile_mode) {  // miss bits of the binned pairs: in their chunks' bitmaps
-            f.kmiss = t.d_kmiss.p;
-            f.pair_kpos = t.d_pair_kpos.p;
-            f.pair_chunk = t.d_pair_chunk.p;
-            f.chunks = t.d_chunks.p;
-            f.launched_passes = v.launched_passes;
-        }
+        f.n_dirty = t.d_cursors.p + CUR_DIRTY;
+        if (counts_mode && t.last_tile_mode) binned_miss(f, v.launched_passes);
         f.owner_sorted = with_guards ? t.d_owner_sorted.p : nullptr;
         f.gfail = with_guards ? t.d_gfail.p : nullptr;
         t.hint_counts = counts_mode;
@@ -1777,165 +1805,138 @@ struct QueryRun {
         return PFQ_OK;
     }
 
-    // PFQ_WANT_HITS: the per-read hit lists of this attempt; done = false: the hit buffer was too small, run again
+    // The hit pairs of this attempt, once the stream has drained.  done = false: the hit buffer was too small, run again.
+    // Otherwise the call's results: fragments (pair_hits), the LCAs alone, or the per-read CSR for deliver_rows().
     int read_hits(bool &done) {
         done = true;
         HIP_TRY(hipStreamSynchronize(st));
-        unsigned long long cursors[2] = {0, 0};
+        unsigned long long cursors[2] = {0, 0};  // CUR_HIT, CUR_PAIR
         HIP_TRY(hipMemcpy(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost));
-        if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)cursors[0] / (double)n_reads);
-        if (t.last_attempts == 1) t.last_hit_cursor0 = cursors[0];
-        if (cursors[0] <= hit_cap && paired) return pair_hits(cursors[0]);
-        if (cursors[0] <= hit_cap && !user_hits) {  // PFQ_WANT_LCA alone: the reads' spans straight from the hit pairs, nothing waited for
+        const uint64_t n_pairs = cursors[CUR_HIT];
+        if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)n_pairs / (double)n_reads);
+        if (t.last_attempts == 1) t.last_hit_cursor0 = n_pairs;
+        if (n_pairs > hit_cap) {
+            // restore the counters and run the block again with room for every hit (whatever PFQ_HIT_SLOTS says)
+            if (nl) HIP_TRY(hipMemcpy(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice));
+            HIP_TRY(t.d_hit_pairs.ensure(n_pairs + 1024));
+            hit_cap = t.d_hit_pairs.n;
+            done = false;
+            return PFQ_OK;
+        }
+        if (paired) return pair_hits(n_pairs);
+        if (!user_hits) {  // PFQ_WANT_LCA alone: the reads' spans straight from the hit pairs, nothing waited for
             if (n_reads && nl) {
                 HIP_TRY(t.d_lca_span.ensure(n_reads));
                 HIP_TRY(hipMemsetAsync(t.d_lca_span.p, 0xff, n_reads * sizeof(uint2), st));
-                pfq::launch_lca_pairs(t.d_hit_pairs.p, cursors[0], t.d_allhit.p, n_reads, t.d_lca_span.p, lca_tables(), t.d_lca.p, st);
+                pfq::launch_lca_pairs(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_lca_span.p, lca_tables(), t.d_lca.p, st);
                 HIP_TRY(hipGetLastError());
             }
             return PFQ_OK;
         }
-        if (cursors[0] <= hit_cap) {
-            // CSR read -> leaves (ascending; reads that pass every node list every leaf), built on the device from the
-            // unordered hit pairs and copied into page-locked host buffers
-            auto host_room = [&](void **p, size_t &cap, size_t want) -> int {
-                if (want <= cap) return PFQ_OK;
-                if (*p) (void)hipHostFree(*p);
-                *p = nullptr;
-                cap = 0;
-                const size_t grown = want + want / 4 + 4096;
-                HIP_TRY(hipHostMalloc(p, grown, hipHostMallocDefault));
-                cap = grown;
-                return PFQ_OK;
-            };
-            PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, ((size_t)n_reads + 1) * 8));
-            t.h_hit_off[0] = 0;
-            uint64_t total = 0;
-            if (n_reads) {
-                unsigned long long n_allhit = 0;
-                HIP_TRY(hipMemcpy(&n_allhit, t.d_stats.p + pfq::ST_ALLHIT, 8, hipMemcpyDeviceToHost));
-                HIP_TRY(t.d_hit_cnt.ensure(n_reads + 1));
-                HIP_TRY(t.d_hit_off.ensure(n_reads + 2));
-                HIP_TRY(t.d_hit_sums.ensure((n_reads + 4095) / 4096 + 2));
-                HIP_TRY(hipMemsetAsync(t.d_hit_cnt.p, 0, (n_reads + 1) * 4, st));
-                pfq::launch_hits_csr(t.d_hit_pairs.p, cursors[0], t.d_allhit.p, n_reads, (uint32_t)nl, n_allhit != 0, t.d_hit_cnt.p, t.d_hit_sums.p,
-                                     t.d_hit_off.p, st);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(t.h_hit_off, t.d_hit_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                total = t.h_hit_off[n_reads];
-                PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, (size_t)total * 4 + 4));
-                if (total) {
-                    HIP_TRY(t.d_hit_leaves.ensure(total));
-                    pfq::launch_hits_fill(t.d_hit_pairs.p, cursors[0], t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipMemcpyAsync(t.h_hit_leaves, t.d_hit_leaves.p, total * 4, hipMemcpyDeviceToHost, st));
-                    if (want_scores) {  // the hit set is final: score every (read, hit leaf) pair of the CSR
-                        HIP_TRY(t.d_hit_scores.ensure(total));
-                        PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
-                        pfq::launch_hit_scores(t.hp, d_seq, d_off, n_reads, threshold, t.d_hit_off.p, t.d_hit_leaves.p, t.d_col_row.p,
-                                               t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
-                        HIP_TRY(hipGetLastError());
-                        HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
-                    }
-                    if (want_lca) PFQ_TRY(lca_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, 0));  // (runs beside the copies)
-                    HIP_TRY(hipStreamSynchronize(st));
-                } else if (want_lca) PFQ_TRY(lca_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, 0));  // (every row is empty)
-            } else PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, 4));
-            if (want_scores) {
-                PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
-                t.scores_valid = true;
-                t.scores_n = total;
-            }
-            hits->n_reads = n_reads;
-            hits->offsets = t.h_hit_off;
-            hits->leaves = t.h_hit_leaves;
-            if (want_abund) return abund_append(t.d_hit_off.p, t.d_hit_leaves.p, n_reads);
-            return PFQ_OK;
+        if (!n_reads) return deliver_rows(nullptr, nullptr, 0, 0, 0);
+        // CSR read -> leaves (ascending; reads that pass every node list every leaf), built on the device from the unordered
+        // hit pairs.  All-hit reads list every leaf, so the total is only known from the offsets: they are read back first.
+        unsigned long long n_allhit = 0;
+        HIP_TRY(hipMemcpy(&n_allhit, t.d_stats.p + pfq::ST_ALLHIT, 8, hipMemcpyDeviceToHost));
+        PFQ_TRY(mate_csr(n_pairs, n_allhit != 0));
+        uint64_t total = 0;
+        PFQ_TRY(fetch_offsets(t.d_hit_off.p, n_reads, total));
+        if (total) {
+            HIP_TRY(t.d_hit_leaves.ensure(total));
+            pfq::launch_hits_fill(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
+            HIP_TRY(hipGetLastError());
         }
-        // hit buffer too small: restore the counters and run the block again with room for every hit (whatever PFQ_HIT_SLOTS says)
-        if (nl) HIP_TRY(hipMemcpy(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice));
-        HIP_TRY(t.d_hit_pairs.ensure(cursors[0] + 1024));
-        hit_cap = t.d_hit_pairs.n;
-        done = false;
+        return deliver_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, total, 0);
+    }
+
+    // Offsets of the mates' (reads') CSR from the hit pairs, into d_hit_off; launch_hits_fill then scatters the leaves with
+    // d_hit_cnt and leaves it zero.  any_allhit: all-hit reads list every leaf (else they stay flags in d_allhit).
+    int mate_csr(uint64_t n_pairs, bool any_allhit) {
+        HIP_TRY(t.d_hit_cnt.ensure(n_reads + 1));
+        HIP_TRY(t.d_hit_off.ensure(n_reads + 2));
+        HIP_TRY(t.d_hit_sums.ensure((n_reads + 4095) / 4096 + 2));
+        HIP_TRY(hipMemsetAsync(t.d_hit_cnt.p, 0, (n_reads + 1) * 4, st));
+        if (paired) HIP_TRY(hipMemsetAsync(t.d_pair_misc.p, 0, 16, st));  // (pair_hits' two words, cleared where they always were)
+        pfq::launch_hits_csr(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, (uint32_t)nl, any_allhit, t.d_hit_cnt.p, t.d_hit_sums.p, t.d_hit_off.p, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
+    }
+    // the offsets of a CSR into the caller's page-locked copy, waited for: total = its number of entries
+    int fetch_offsets(const unsigned long long *off, uint64_t n_units, uint64_t &total) {
+        HIP_TRY(t.h_hit_off.ensure(n_units + 1));
+        HIP_TRY(hipMemcpyAsync(t.h_hit_off.p, off, (n_units + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        total = t.h_hit_off.p[n_units];
         return PFQ_OK;
     }
 
     // PFQ_PAIRED, after the mates' hit pairs are complete: the mate CSR (all-hit mates as flags only), the fragment CSR
-    // (union / intersection per fragment), its histogram into the tree's counters and — PFQ_WANT_HITS — the lists and
-    // scores copied out.  Without PFQ_WANT_HITS nothing more is waited for: every all-leaf fragment is a count, the lists
-    // hold at most the mates' n_pairs entries.
+    // (union / intersection per fragment) and its histogram into the tree's counters; PFQ_WANT_HITS: deliver_rows().
+    // Without PFQ_WANT_HITS nothing more is waited for: every all-leaf fragment is a count, the lists hold at most the
+    // mates' n_pairs entries (a union holds at most both mates' entries).
     int pair_hits(uint64_t n_pairs) {
         const uint64_t n_frag = n_reads / 2;
-        auto host_room = [&](void **p, size_t &cap, size_t want) -> int {
-            if (want <= cap) return PFQ_OK;
-            if (*p) (void)hipHostFree(*p);
-            *p = nullptr;
-            cap = 0;
-            const size_t grown = want + want / 4 + 4096;
-            HIP_TRY(hipHostMalloc(p, grown, hipHostMallocDefault));
-            cap = grown;
-            return PFQ_OK;
-        };
+        const int pair_mode = pair_both ? 2 : 1;
+        if (!n_frag || !nl) return user_hits ? deliver_rows(nullptr, nullptr, n_frag, 0, pair_mode) : PFQ_OK;
+        HIP_TRY(t.d_hit_leaves.ensure(n_pairs + 1));
+        HIP_TRY(t.d_frag_off.ensure(n_frag + 2));
+        HIP_TRY(t.d_pair_long.ensure(n_frag + 1));
+        HIP_TRY(t.d_pair_misc.ensure(2));
+        PFQ_TRY(mate_csr(n_pairs, false));
+        pfq::launch_hits_fill(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
+        // (the scatter leaves d_hit_cnt zero: it holds the fragments' counts next)
+        pfq::launch_pair_combine(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, user_hits, t.d_hit_cnt.p,
+                                 t.d_pair_long.p, t.d_pair_misc.p, t.d_hit_sums.p, t.d_frag_off.p, st);
+        HIP_TRY(hipGetLastError());
         uint64_t total = 0;
-        if (n_frag && nl) {
-            HIP_TRY(t.d_hit_cnt.ensure(n_reads + 1));
-            HIP_TRY(t.d_hit_off.ensure(n_reads + 2));
-            HIP_TRY(t.d_hit_sums.ensure((n_reads + 4095) / 4096 + 2));
-            HIP_TRY(t.d_hit_leaves.ensure(n_pairs + 1));
-            HIP_TRY(t.d_frag_off.ensure(n_frag + 2));
-            HIP_TRY(t.d_pair_long.ensure(n_frag + 1));
-            HIP_TRY(t.d_pair_misc.ensure(2));
-            HIP_TRY(hipMemsetAsync(t.d_hit_cnt.p, 0, (n_reads + 1) * 4, st));
-            HIP_TRY(hipMemsetAsync(t.d_pair_misc.p, 0, 16, st));
-            pfq::launch_hits_csr(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, (uint32_t)nl, false, t.d_hit_cnt.p, t.d_hit_sums.p, t.d_hit_off.p, st);
-            pfq::launch_hits_fill(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
-            // (the scatter leaves d_hit_cnt zero: it holds the fragments' counts next)
-            pfq::launch_pair_combine(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, user_hits, t.d_hit_cnt.p,
-                                     t.d_pair_long.p, t.d_pair_misc.p, t.d_hit_sums.p, t.d_frag_off.p, st);
-            HIP_TRY(hipGetLastError());
-            uint64_t room = n_pairs;  // a union holds at most both mates' entries
-            if (user_hits) {
-                PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, (n_frag + 1) * 8));
-                HIP_TRY(hipMemcpyAsync(t.h_hit_off, t.d_frag_off.p, (n_frag + 1) * 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                total = room = t.h_hit_off[n_frag];
-            }
-            HIP_TRY(t.d_frag_leaves.ensure(room + 1));
-            pfq::launch_pair_fill(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, t.d_pair_long.p, t.d_pair_misc.p,
-                                  t.d_frag_off.p, t.d_frag_leaves.p, st);
-            pfq::launch_pair_leaf_counts(t.d_frag_leaves.p, t.d_frag_off.p + n_frag, t.d_pair_misc.p, (uint32_t)nl, room, t.d_counts.p, st);
-            HIP_TRY(hipGetLastError());
-            if (user_hits && total) {
-                PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, (size_t)total * 4 + 4));
-                HIP_TRY(hipMemcpyAsync(t.h_hit_leaves, t.d_frag_leaves.p, total * 4, hipMemcpyDeviceToHost, st));
-                if (want_scores) {
-                    HIP_TRY(t.d_hit_scores.ensure(total));
-                    PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
-                    pfq::launch_pair_scores(t.hp, d_seq, d_off, n_frag, threshold, pair_both, t.d_frag_off.p, t.d_frag_leaves.p, t.d_col_row.p,
-                                            t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipMemcpyAsync(t.h_hit_scores, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
-                }
-                if (want_lca) PFQ_TRY(lca_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, pair_both ? 2 : 1));
-                HIP_TRY(hipStreamSynchronize(st));
-            } else if (want_lca) PFQ_TRY(lca_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, pair_both ? 2 : 1));
-        } else if (user_hits) {  // no fragments, or no leaves: empty lists
-            PFQ_TRY(host_room((void **)&t.h_hit_off, t.h_hit_off_cap, (n_frag + 1) * 8));
-            for (uint64_t i = 0; i <= n_frag; ++i) t.h_hit_off[i] = 0;
+        if (user_hits) PFQ_TRY(fetch_offsets(t.d_frag_off.p, n_frag, total));
+        const uint64_t room = user_hits ? total : n_pairs;
+        HIP_TRY(t.d_frag_leaves.ensure(room + 1));
+        pfq::launch_pair_fill(t.d_hit_off.p, t.d_hit_leaves.p, t.d_allhit.p, n_frag, pair_both, (uint32_t)nl, t.d_pair_long.p, t.d_pair_misc.p,
+                              t.d_frag_off.p, t.d_frag_leaves.p, st);
+        pfq::launch_pair_leaf_counts(t.d_frag_leaves.p, t.d_frag_off.p + n_frag, t.d_pair_misc.p, (uint32_t)nl, room, t.d_counts.p, st);
+        HIP_TRY(hipGetLastError());
+        if (user_hits) return deliver_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, total, pair_mode);
+        if (want_lca) PFQ_TRY(lca_rows(t.d_frag_off.p, t.d_frag_leaves.p, n_frag, pair_mode));
+        return PFQ_OK;
+    }
+
+    // PFQ_WANT_HITS: the call's final CSR (off / leaves in device memory, `total` entries over n_units rows, the offsets
+    // already in h_hit_off; off == nullptr: no row was built, every list is empty) goes to the caller, with everything that
+    // is derived from it: scores (reads: pair_mode 0, fragments: 1 either / 2 both), LCAs, the abundance log.  The scores
+    // are queued before the LCAs (PFQ_LCA_BEST reads d_hit_scores), the LCAs run beside the copies, and the log is appended
+    // once the copies have been waited for.  Host waits of a call that builds hit pairs (PFQ_PAIRED, PFQ_WANT_LCA alone included):
+    //   every such call             1 wait and the 16-byte cursor read (read_hits)
+    //   reads, PFQ_WANT_HITS        + the 8-byte read of ST_ALLHIT, 1 wait for the offsets (fetch_offsets), 1 for the lists (here)
+    //   fragments, PFQ_WANT_HITS    + 1 wait for the fragment offsets (fetch_offsets), 1 for the lists (here)
+    //   fragments without it, PFQ_WANT_LCA alone: nothing more;  PFQ_WANT_ABUNDANCE: + 1, in abund_append
+    int deliver_rows(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units, uint64_t total, int pair_mode) {
+        if (!off) {  // offsets[0 .. n_units] are always written
+            HIP_TRY(t.h_hit_off.ensure(n_units + 1));
+            std::fill_n(t.h_hit_off.p, n_units + 1, 0);
         }
-        if (!user_hits) return PFQ_OK;
-        PFQ_TRY(host_room((void **)&t.h_hit_leaves, t.h_hit_leaves_cap, (size_t)total * 4 + 4));
+        HIP_TRY(t.h_hit_leaves.ensure(total + 1));  // (empty lists still get a buffer)
+        if (want_scores) HIP_TRY(t.h_hit_scores.ensure(total + 1));
+        if (total) {
+            HIP_TRY(hipMemcpyAsync(t.h_hit_leaves.p, leaves, total * 4, hipMemcpyDeviceToHost, st));
+            if (want_scores) {  // the hit set is final: score every (unit, listed leaf) pair of the CSR
+                HIP_TRY(t.d_hit_scores.ensure(total));
+                if (pair_mode) pfq::launch_pair_scores(t.hp, d_seq, d_off, n_units, threshold, pair_both, off, leaves, t.d_col_row.p, t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
+                else pfq::launch_hit_scores(t.hp, d_seq, d_off, n_units, threshold, off, leaves, t.d_col_row.p, t.d_bits.p, t.n_words, t.d_hit_scores.p, st);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(t.h_hit_scores.p, t.d_hit_scores.p, total * 4, hipMemcpyDeviceToHost, st));
+            }
+        }
+        if (want_lca && off) PFQ_TRY(lca_rows(off, leaves, n_units, pair_mode));
+        if (total) HIP_TRY(hipStreamSynchronize(st));
         if (want_scores) {
-            PFQ_TRY(host_room((void **)&t.h_hit_scores, t.h_hit_scores_cap, (size_t)total * 4 + 4));
             t.scores_valid = true;
             t.scores_n = total;
         }
-        hits->n_reads = n_frag;
-        hits->offsets = t.h_hit_off;
-        hits->leaves = t.h_hit_leaves;
-        if (want_abund) return abund_append(t.d_frag_off.p, t.d_frag_leaves.p, n_frag);
-        return PFQ_OK;
+        hits->n_reads = n_units;
+        hits->offsets = t.h_hit_off.p;
+        hits->leaves = t.h_hit_leaves.p;
+        return want_abund ? abund_append(off, leaves, n_units) : PFQ_OK;
     }
 
     // PFQ_WANT_ABUNDANCE: the rows of the call's final CSR (off / leaves, in device memory) go into the log, device to device.
@@ -2792,10 +2793,6 @@ void pfq_tree_close(pfq_tree *tree) {
         if (e) (void)hipEventDestroy(e);
     for (auto h : tree->h_gseq)
         if (h) (void)hipHostFree(h);
-    if (tree->h_hit_off) (void)hipHostFree(tree->h_hit_off);
-    if (tree->h_hit_leaves) (void)hipHostFree(tree->h_hit_leaves);
-    if (tree->h_hit_scores) (void)hipHostFree(tree->h_hit_scores);
-
     if (tree->h_pair_cursor) (void)hipHostFree(tree->h_pair_cursor);
     if (tree->hint_ev) (void)hipEventDestroy(tree->hint_ev);
     if (tree->last_done) (void)hipEventDestroy(tree->last_done);
@@ -2860,7 +2857,7 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
 int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits) {
     if (!tree || !scores || !n_hits) return fail(PFQ_ERR_ARG, "null argument");
     if (!tree->scores_valid) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for scores (PFQ_WANT_SCORES)");
-    *scores = tree->h_hit_scores;
+    *scores = tree->h_hit_scores.p;
     *n_hits = tree->scores_n;
     return PFQ_OK;
 }
@@ -3298,16 +3295,16 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
     out->tile_mode = t.last_tile_mode;
     out->tile_bin_build = t.last_tile_bin;
     if (t.d_cursors.p) {
-        unsigned long long c[11];
+        unsigned long long c[CUR_TAIL_SHAPES + 1];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
-        const uint32_t shapes = t.last_path ? (uint32_t)c[10] : 0u;  // pfq::TAIL_SHAPE_*
+        const uint32_t shapes = t.last_path ? (uint32_t)c[CUR_TAIL_SHAPES] : 0u;  // pfq::TAIL_SHAPE_*
         out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u);
-        out->n_chunks = (uint32_t)c[3];
-        out->n_fallback_pairs = (uint32_t)(c[3] >> 32);
-        out->tile_entries = c[2];
+        out->n_chunks = (uint32_t)c[CUR_CHUNKS_FLAGGED];
+        out->n_fallback_pairs = (uint32_t)(c[CUR_CHUNKS_FLAGGED] >> 32);
+        out->tile_entries = c[CUR_TILE_ENTRIES];
         if (t.last_tile_mode && t.hint_entry_cap) {
             out->tile_passes_launched = t.last_passes;
-            out->tile_passes_needed = (uint32_t)std::max<uint64_t>(1, (c[2] + t.hint_entry_cap - 1) / t.hint_entry_cap);
+            out->tile_passes_needed = (uint32_t)std::max<uint64_t>(1, (c[CUR_TILE_ENTRIES] + t.hint_entry_cap - 1) / t.hint_entry_cap);
         }
     }
     out->leaf_groups = t.last_leaf_groups;
@@ -3384,11 +3381,11 @@ int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n) {
     uint64_t v[PFQ_CAPACITY_N] = {};
     if (t.d_cursors.p) {
         PFQ_TRY(wait_last_call(t));
-        unsigned long long c[10];
+        unsigned long long c[CUR_KMISS + 1];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
         uint32_t sorted = 0;
         if (t.last_nb && t.d_bucket.n > 2 * t.last_nb) HIP_TRY(hipMemcpy(&sorted, t.d_bucket.p + 2 * t.last_nb, 4, hipMemcpyDeviceToHost));
-        const uint64_t w[PFQ_CAPACITY_N] = {c[1], t.last_pair_cap, c[8], t.last_guard_cap, c[5], t.last_miss_cap, c[9], t.last_kmiss_cap,
+        const uint64_t w[PFQ_CAPACITY_N] = {c[CUR_PAIR], t.last_pair_cap, c[CUR_GUARD], t.last_guard_cap, c[CUR_MISS_WORDS], t.last_miss_cap, c[CUR_KMISS], t.last_kmiss_cap,
                                             t.last_hit_cursor0, t.last_hit_cap0, t.last_attempts, sorted};
         if (t.last_path) memcpy(v, w, sizeof v);
         else v[8] = w[8], v[9] = w[9], v[10] = w[10];  // (the direct path has no pair buffers)
