@@ -87,6 +87,13 @@ typedef struct pfq_hits {
  * log: its other results (counts, hits, scores, LCAs) stand, the log keeps what it held and is incomplete until it is reset. */
 #define PFQ_WANT_ABUNDANCE 64u
 #define PFQ_ABUND_Q 16 /* pfq_abundance.mass counts units in steps of 2^-16 */
+/* Coverage: every unit of the call (a read; with PFQ_PAIRED a fragment) is also sketched on the device for pfq_coverage_get: per
+ * leaf of the row pfq_hits gives for it, the unit, its matched k-mers and a HyperLogLog sketch of them (see "coverage" below).
+ * Only together with PFQ_WANT_HITS (alone: PFQ_ERR_ARG); combines with every other flag and changes none of their results.  A
+ * block whose hit buffer overflowed and ran again is sketched once.  Subtree shards are accepted: a leaf's sketch depends only
+ * on the units that list that leaf, so a shard's sketch of its leaves is the whole tree's sketch of those leaves.  The sketch is
+ * allocated and zeroed by the first such call; if that fails the call returns PFQ_ERR_DEVICE and nothing of it is sketched. */
+#define PFQ_WANT_COVERAGE 128u
 
 /* ---- database ---- */
 
@@ -251,6 +258,45 @@ int pfq_abundance_reset(pfq_tree *tree);
  * through host memory: this runs once per job).  An incomplete log on either side: PFQ_ERR_STATE.  If dst's log cannot take
  * the rows (as for a query call): PFQ_ERR_UNSUPPORTED, and both logs stay as they were. */
 int pfq_abundance_absorb(pfq_tree *dst, pfq_tree *src);
+
+/* ---- coverage (PFQ_WANT_COVERAGE) ----
+ * Is a genome really in the sample, or do its reads pile onto one shared stretch?  Per leaf l the library keeps units[l],
+ * matched[l] and a HyperLogLog sketch R[l] of 2^p one-byte registers (p: the option PFQ_COVER_P, 4..16, default 12) of the
+ * distinct k-mers matched.  For every unit of a PFQ_WANT_COVERAGE call and every leaf l of its row: units[l] += 1, and every read x
+ * of the unit (a fragment: both mates, whichever mate caused the listing) gives every canonical k-mer c of get_kmers(x),
+ * duplicates included, whose num_hashes probed bits are all set in l's filter (the test PFQ_WANT_SCORES counts):
+ *   matched[l] += 1;  h = seeded_hash(seed1, c), the first of the two hashes the probe indices are made of;
+ *   u = mix(h), the splitmix64 finaliser: x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31;
+ *   j = u >> (64 - p);  w = u << p (mod 2^64);  rho = min(clz64(w), 64 - p) + 1 (w = 0: 64 - p + 1);  R[l][j] = max(R[l][j], rho).
+ * So a call's increase of matched[l] is the sum of its pfq_last_hit_scores over the rows that list l, and that of units[l] is the
+ * leaf counter's.  The state is a pure function of the multiset of (k-mer, leaf) pairs logged: it does not depend on the order
+ * of the calls, how the units were split over them, or any knob.
+ * pfq_coverage_get waits for the queued work and copies the state out; the derived values are computed on the host in double:
+ *   distinct[l]: classic HyperLogLog, m = 2^p, alpha = 0.7213 / (1 + 1.079 / m) (p = 4, 5, 6: 0.673, 0.697, 0.709),
+ *     E = alpha m^2 / sum_j 2^-R[l][j], V = registers that are 0; m ln(m / V) if E <= 2.5 m and V > 0, else E; an all-zero sketch
+ *     gives 0.  No large-range correction (the hash has 64 bits).  Standard error about 1.04 / sqrt(m): 1.6 % at p = 12.
+ *   filter_bits[l]: set bits of l's filter (computed once per tree, lazily);
+ *   genome_kmers[l] = -(nbits / num_hashes) log1p(-filter_bits / nbits), the distinct k-mers the genome put into the filter
+ *     (Swamidass-Baldi); a full filter gives 0.0, "not estimable".
+ * Breadth of coverage is distinct / genome_kmers (not clamped; 0 where genome_kmers is 0), duplication matched / distinct.
+ * Before any PFQ_WANT_COVERAGE call everything is 0 except filter_bits and genome_kmers.  Leaves are in pfq_leaf_counts order;
+ * the arrays are library-owned and valid until the next coverage call on the tree.
+ * The sketch takes (n_leaves << p) + 16 n_leaves bytes of device memory (pfq_info.device_bytes counts them) from the first
+ * flagged call until it is freed: by pfq_coverage_reset, pfq_leaf_counts_reset, pfq_tree_prune and pfq_tree_insert (the leaf
+ * columns change meaning).  It is not stored by pfq_tree_save.  pfq_set_option("PFQ_COVER_P") outside 4..16 is PFQ_ERR_ARG, and
+ * a change of p while the sketch holds units is PFQ_ERR_STATE.  The leaf counters are untouched by all of this. */
+typedef struct pfq_coverage {
+    uint64_t n_leaves, n_units; uint32_t precision;
+    const uint8_t *registers;      /* [n_leaves << precision] */
+    const uint64_t *units, *matched, *filter_bits;   /* [n_leaves] */
+    const double *distinct, *genome_kmers;           /* [n_leaves] */
+} pfq_coverage;                    /* library-owned, valid until the next coverage call on the tree */
+int pfq_coverage_get(pfq_tree *tree, pfq_coverage *out);    /* before any flagged call: zeros, filter_bits filled */
+int pfq_coverage_reset(pfq_tree *tree);
+/* registers: element-wise max; units / matched / n_units: sums; src is emptied.  The trees must hold the same leaves with the
+ * same hash parameters and precision (replicas, on any devices, or the same shard of one database), dst != src: else
+ * PFQ_ERR_ARG.  Staged through host memory: this runs once per job. */
+int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src);
 
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);

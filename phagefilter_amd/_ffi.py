@@ -16,6 +16,7 @@ SYMBOLS = [
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
+    "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
@@ -69,6 +70,13 @@ class Abundance(C.Structure):
                 ("iterations", C.c_uint32), ("converged", C.c_uint32)]
 
 
+class Coverage(C.Structure):
+    _fields_ = [("n_leaves", C.c_uint64), ("n_units", C.c_uint64), ("precision", C.c_uint32),
+                ("registers", C.POINTER(C.c_uint8)),
+                ("units", C.POINTER(C.c_uint64)), ("matched", C.POINTER(C.c_uint64)), ("filter_bits", C.POINTER(C.c_uint64)),
+                ("distinct", C.POINTER(C.c_double)), ("genome_kmers", C.POINTER(C.c_double))]
+
+
 WANT_HITS = 1
 WANT_SCORES = 2
 PAIRED = 4
@@ -77,6 +85,7 @@ WANT_LCA = 16
 LCA_BEST = 32
 WANT_ABUNDANCE = 64
 ABUND_Q = 16
+WANT_COVERAGE = 128
 NO_CLADE = 0xFFFFFFFF
 _lib = None
 
@@ -125,6 +134,9 @@ def lib() -> C.CDLL:
     L.pfq_abundance_estimate.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(Abundance)]
     L.pfq_abundance_reset.argtypes = [vp]
     L.pfq_abundance_absorb.argtypes = [vp, vp]
+    L.pfq_coverage_get.argtypes = [vp, C.POINTER(Coverage)]
+    L.pfq_coverage_reset.argtypes = [vp]
+    L.pfq_coverage_absorb.argtypes = [vp, vp]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

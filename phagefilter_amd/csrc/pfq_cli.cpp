@@ -1145,6 +1145,31 @@ struct ServedDb {
         }
         if (fclose(f) != 0) die("short write to " + tsv);
     }
+    // --coverage: the precision of every replica's (shard's) sketch, before the first call makes it
+    void set_coverage_precision(const std::string &p) {
+        for (pfq_tree *t : trees) check(pfq_set_option(t, "PFQ_COVER_P", p.c_str()));
+    }
+    // --coverage: COVERAGE.tsv, one line per leaf in leaf order.  Every replica sketched its own units: the sketches are merged
+    // into replica 0's (registers: maximum, counters: sums).  Shards hold disjoint leaf ranges in the whole tree's order and a
+    // leaf's sketch depends only on the units that list it, so their lines follow one another like CLASSIFICATION.csv's.
+    void save_coverage(const std::string &tsv) {
+        if (!sharded)
+            for (size_t i = 1; i < trees.size(); ++i) check(pfq_coverage_absorb(trees[0], trees[i]));
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+        fputs("#genome\tunits\tmatched_kmers\tdistinct_kmers\tgenome_kmers\tbreadth\tduplication\n", f);
+        for (size_t i = 0; i < (sharded ? trees.size() : 1); ++i) {
+            pfq_coverage cv{};
+            check(pfq_coverage_get(trees[i], &cv));
+            for (uint64_t l = 0; l < cv.n_leaves; ++l) {
+                const double distinct = cv.distinct[l], genome = cv.genome_kmers[l];
+                fprintf(f, "%s\t%llu\t%llu\t%.1f\t%.1f\t%.4f\t%.2f\n", leaf_names[leaf_base[i] + l].c_str(), (unsigned long long)cv.units[l],
+                        (unsigned long long)cv.matched[l], distinct, genome, genome > 0.0 ? distinct / genome : 0.0,
+                        distinct > 0.0 ? (double)cv.matched[l] / distinct : 0.0);
+            }
+        }
+        if (fclose(f) != 0) die("short write to " + tsv);
+    }
     void close() {
         for (pfq_tree *t : trees) pfq_tree_close(t);
     }
@@ -1371,7 +1396,8 @@ struct QueryLoop {
     const int lca = 0;             // --lca: 0 none, 1 all, 2 best (the library is asked for hits and scores)
     const bool lca_reads = false;  // --lca-reads: READ_LCA.tsv
     const bool abundance = false;  // --abundance: every call asks for the hits and logs their rows
-    uint32_t abundance_flags() const { return abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u; }
+    const bool coverage = false;   // --coverage: every call asks for the hits and sketches the listed genomes' matched k-mers
+    uint32_t abundance_flags() const { return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u); }
     uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
 
@@ -1870,7 +1896,7 @@ int cmd_query(int argc, char **argv) {
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
-                             {"abundance", 0, false}, {"abundance-iters", 0, true}};
+                             {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -1902,7 +1928,18 @@ int cmd_query(int argc, char **argv) {
     if (abundance && a.val.count("shard-depth"))
         die("error: '--abundance' cannot be used with '--shard-depth': a subtree shard sees only its own genomes, so the hit rows it "
             "would log are partial (not implemented)");
-    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance;  // the per-read hit lists are needed
+    // --coverage: every query call also sketches, per genome a read lists, the read's k-mers that genome's filter contains
+    // (PFQ_WANT_HITS | PFQ_WANT_COVERAGE); at the end COVERAGE.tsv says how many distinct k-mers every genome's reads matched
+    const bool coverage = a.flags.count("coverage") != 0;
+    if (a.val.count("coverage-precision") && !coverage) die("error: '--coverage-precision' needs '--coverage'");
+    const std::string coverage_p = opt(a, "coverage-precision", "12");
+    if (coverage) {
+        char *end = nullptr;
+        const long v = strtol(coverage_p.c_str(), &end, 10);
+        if (coverage_p.empty() || !isdigit((unsigned char)coverage_p[0]) || *end || v < 4 || v > 16)
+            die("error: invalid value '" + coverage_p + "' for '--coverage-precision': 4 to 16 (2^P registers per genome)");
+    }
+    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
@@ -1946,6 +1983,7 @@ int cmd_query(int argc, char **argv) {
         if (a.val.count("search-depth")) shard_depth = std::min(shard_depth, to_u64(a.val.at("search-depth"), "search-depth"));
     }
     ServedDb db(db_path, devices, sharded, shard_depth);
+    if (coverage) db.set_coverage_precision(coverage_p);
     printf("Querying reads...\n");
     printf("Filtering settings: positive=%s; negative=%s\n", pos ? "true" : "false", neg ? "true" : "false");
     if (a.val.count("search-depth")) {
@@ -1980,7 +2018,7 @@ int cmd_query(int argc, char **argv) {
     if (lca_reads) db.load_clade_names();
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage};
     if (block == 0) {
         // nothing to do: see above
     } else if (paired) {
@@ -2006,6 +2044,7 @@ int cmd_query(int argc, char **argv) {
     db.save_counts(out + "/CLASSIFICATION.csv");
     if (lca) db.save_clade_counts(out + "/CLADE_COUNTS.tsv");
     if (abundance) db.save_abundance(out + "/ABUNDANCE.tsv", (uint32_t)abundance_iters);
+    if (coverage) db.save_coverage(out + "/COVERAGE.tsv");
     db.close();
     printf("Finished.\n");
     return 0;
@@ -2228,6 +2267,17 @@ void usage() {
             "for the hit lists, the counts-only mode (no filter, no --scores) too, which so runs at the hit-list rate.  The other\n"
             "outputs stay as they are.  Not with --shard-depth: a shard sees only its own genomes.  With --devices the replicas'\n"
             "logs are merged before the estimate.  --abundance-iters <N> (needs --abundance): at most N EM iterations (default 200)\n"
+            "--coverage: also count, per genome, the distinct k-mers its reads (paired input: fragments, both mates) matched, and\n"
+            "write COVERAGE.tsv into --out: 5 000 reads piled onto one shared gene and 5 000 reads that tile a genome look the same\n"
+            "in CLASSIFICATION.csv; here the first shows few distinct k-mers under many reads.  \"#genome<TAB>units<TAB>matched_kmers\n"
+            "<TAB>distinct_kmers<TAB>genome_kmers<TAB>breadth<TAB>duplication\", one line per genome in CLASSIFICATION.csv's order, zeros\n"
+            "included: units = reads that list the genome, matched_kmers = their k-mers the genome's filter contains, distinct_kmers =\n"
+            "a HyperLogLog estimate of the distinct ones among them, genome_kmers = the genome's own distinct k-mers estimated from\n"
+            "its filter's fill (0.0: filter full, not estimable), breadth = distinct_kmers / genome_kmers (not clamped), duplication =\n"
+            "matched_kmers / distinct_kmers.  Every query call then asks the library for the hit lists, as with --abundance.  The other\n"
+            "outputs stay as they are.  Works with --shard-depth (the shards' lines follow one another) and with --devices (the\n"
+            "replicas' sketches are merged first).  --coverage-precision <P> (needs --coverage): 2^P one-byte registers per genome,\n"
+            "4 to 16 (default 12: 4 KiB per genome, standard error 1.6 %%)\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
 }
 

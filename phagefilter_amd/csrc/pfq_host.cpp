@@ -104,6 +104,7 @@ struct Knobs {
     long long coarse = -1, coarse_cols = -1, coarse_probes = -1, group_log2 = -1, screen_recs = -1, coarse_min_leaves = -1, greedy_host = -1;
     long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
     long long abund_slots = -1, abund_blocks = -1, abund_lds = -1;  // PFQ_WANT_ABUNDANCE: cap on the log's leaf entries; grid and LDS use of the EM step
+    long long cover_p = -1, cover_blocks = -1;  // PFQ_WANT_COVERAGE: registers per leaf = 2^cover_p (4..16, unset: 12); grid of the sketch kernel
 };
 struct KnobName {
     const char *name;
@@ -131,6 +132,7 @@ const KnobName KNOBS[] = {
     {"PFQ_HIT_SLOTS", &Knobs::hit_slots},
     {"PFQ_ABUND_SLOTS", &Knobs::abund_slots},   {"PFQ_ABUND_BLOCKS", &Knobs::abund_blocks},
     {"PFQ_ABUND_LDS", &Knobs::abund_lds},
+    {"PFQ_COVER_P", &Knobs::cover_p},           {"PFQ_COVER_BLOCKS", &Knobs::cover_blocks},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -356,6 +358,17 @@ struct pfq_tree {
     uint64_t ab_rows = 0, ab_entries = 0, ab_units = 0, ab_unhit = 0, ab_unique = 0, ab_all = 0;
     bool ab_incomplete = false;            // a call's rows did not fit: no estimate until the log is reset
     std::vector<uint64_t> out_mass, out_unique;
+    // PFQ_WANT_COVERAGE: d_cov_regs u8[n_leaves << cov_p] (HyperLogLog registers, [leaf << cov_p | j]), d_cov_cnt
+    // [2][n_leaves] (units, matched); made by the first flagged call, freed by cover_clear.  cov_units: units sketched.
+    // cov_bits: the leaves' filter popcounts, computed once per topology (cov_bits_valid).
+    DevBuf<uint8_t> d_cov_regs;
+    DevBuf<unsigned long long> d_cov_cnt;
+    uint32_t cov_p = 0;
+    uint64_t cov_units = 0;
+    bool cov_bits_valid = false;
+    std::vector<uint64_t> cov_bits, out_cov_units, out_cov_matched;
+    std::vector<uint8_t> out_cov_regs;
+    std::vector<double> out_cov_distinct, out_cov_genome;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -1045,6 +1058,64 @@ int abund_shard_refused() {
                                      "are partial");
 }
 
+// ---- PFQ_WANT_COVERAGE: the per-leaf sketches (pfq_tree::d_cov_*) ----
+// The precision a new sketch gets: the option PFQ_COVER_P where it is in range (pfq_set_option refuses other values; one from
+// the environment that is out of range counts as unset).
+uint32_t cover_precision(const Knobs &k) {
+    return k.cover_p >= (long long)pfq::COVER_P_MIN && k.cover_p <= (long long)pfq::COVER_P_MAX ? (uint32_t)k.cover_p : pfq::COVER_P_DEFAULT;
+}
+// Empties the sketch and gives its memory back (hipFree waits for the device).
+void cover_clear(pfq_tree &t) {
+    t.d_cov_regs.release();
+    t.d_cov_cnt.release();
+    t.cov_units = 0;
+}
+// The sketch of a tree of nl leaves, zeroed on `st` if it is made here.  Nothing of the call has run yet.
+int cover_ensure(pfq_tree &t, size_t nl, hipStream_t st) {
+    if (t.d_cov_regs.p || !nl) return PFQ_OK;
+    const uint32_t p = cover_precision(t.knobs);
+    if (t.d_cov_regs.ensure(nl << p) != hipSuccess || t.d_cov_cnt.ensure(2 * nl) != hipSuccess) {
+        (void)hipGetLastError();
+        cover_clear(t);
+        return fail(PFQ_ERR_DEVICE, "no device memory for the coverage sketch (" + std::to_string((nl << p) + 16 * nl) + " bytes: " + std::to_string(nl) +
+                                    " leaves, PFQ_COVER_P = " + std::to_string(p) + "); nothing of this call was sketched");
+    }
+    t.cov_p = p;
+    HIP_TRY(hipMemsetAsync(t.d_cov_regs.p, 0, nl << p, st));
+    HIP_TRY(hipMemsetAsync(t.d_cov_cnt.p, 0, 2 * nl * 8, st));
+    return PFQ_OK;
+}
+// Set bits of every leaf's filter, once per topology.
+int cover_filter_bits(pfq_tree &t) {
+    const size_t nl = t.leaves.size();
+    if (t.cov_bits_valid && t.cov_bits.size() == nl) return PFQ_OK;
+    t.cov_bits.assign(nl, 0);
+    if (nl) {
+        DevBuf<unsigned long long> d_pop;
+        HIP_TRY(d_pop.ensure(nl));
+        pfq::launch_row_popcount(t.d_bits.p, t.n_words, t.d_col_row.p, (uint32_t)nl, d_pop.p, nullptr);  // (the first nl columns are the leaves)
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(t.cov_bits.data(), d_pop.p, nl * 8, hipMemcpyDeviceToHost));
+    }
+    t.cov_bits_valid = true;
+    return PFQ_OK;
+}
+// Classic HyperLogLog over the m = 2^p registers of one leaf (pfq.h "coverage").
+double cover_estimate(const uint8_t *reg, uint32_t p) {
+    const size_t m = (size_t)1 << p;
+    double sum = 0.0;
+    size_t zeros = 0;
+    for (size_t j = 0; j < m; ++j) {
+        sum += std::ldexp(1.0, -(int)reg[j]);
+        zeros += reg[j] == 0;
+    }
+    if (zeros == m) return 0.0;
+    const double dm = (double)m;
+    const double alpha = p == 4 ? 0.673 : p == 5 ? 0.697 : p == 6 ? 0.709 : 0.7213 / (1.0 + 1.079 / dm);
+    const double e = alpha * dm * dm / sum;
+    return e <= 2.5 * dm && zeros > 0 ? dm * std::log(dm / (double)zeros) : e;
+}
+
 int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
     HIP_TRY(t.d_stats.ensure(pfq::ST_N));
     HIP_TRY(t.d_cursors.ensure(CUR_ALLOC));
@@ -1122,7 +1193,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
@@ -1155,6 +1226,7 @@ struct QueryRun {
         want_lca = (flags & PFQ_WANT_LCA) != 0;
         lca_best = (flags & PFQ_LCA_BEST) != 0;
         want_abund = (flags & PFQ_WANT_ABUNDANCE) != 0;
+        want_cover = (flags & PFQ_WANT_COVERAGE) != 0;
         if (want_lca) PFQ_TRY(ensure_lca(t));
         want_hits = user_hits || paired || want_lca;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
@@ -1166,6 +1238,7 @@ struct QueryRun {
         t.last_n_reads = n_reads;
         PFQ_TRY(ensure_scratch(t, n_reads, want_hits));
         nl = t.leaves.size();
+        if (want_cover) PFQ_TRY(cover_ensure(t, nl, st));  // (before anything of the call runs: a failure sketches nothing)
         if (paired) HIP_TRY(t.d_pair_sink.ensure(nl + 1));
         nc = t.n_cols;  // leaf + guard columns = buckets of the bucketed path (block mode: blocks of 8 leaf columns)
         with_guards = !t.guard_col.empty();
@@ -1928,6 +2001,7 @@ struct QueryRun {
             }
         }
         if (want_lca && off) PFQ_TRY(lca_rows(off, leaves, n_units, pair_mode));
+        if (want_cover) PFQ_TRY(cover_sketch(off, leaves, n_units, total, pair_mode));
         if (total) HIP_TRY(hipStreamSynchronize(st));
         if (want_scores) {
             t.scores_valid = true;
@@ -1937,6 +2011,19 @@ struct QueryRun {
         hits->offsets = t.h_hit_off.p;
         hits->leaves = t.h_hit_leaves.p;
         return want_abund ? abund_append(off, leaves, n_units) : PFQ_OK;
+    }
+
+    // PFQ_WANT_COVERAGE: the rows of the call's final CSR are sketched, once: deliver_rows() runs for the attempt that stands.
+    // Queued behind the scores and before deliver_rows' wait, which so covers the kernel's reads of d_seq (the caller's own
+    // buffer in pfq_query_batch_device).  Rows without entries add nothing to any leaf.
+    int cover_sketch(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units, uint64_t total, int pair_mode) {
+        t.cov_units += n_units;
+        if (!off || !total || !t.d_cov_regs.p) return PFQ_OK;
+        const pfq::CoverArgs cv{t.d_cov_regs.p, t.d_cov_cnt.p, t.d_cov_cnt.p + nl, (uint32_t)nl, t.cov_p};
+        const uint32_t blocks = kn.cover_blocks > 0 ? (uint32_t)std::min<long long>(kn.cover_blocks, 65535) : 0;
+        pfq::launch_cover_sketch(t.hp, d_seq, d_off, n_units, threshold, pair_mode, off, leaves, t.d_col_row.p, t.d_bits.p, t.n_words, cv, blocks, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
     }
 
     // PFQ_WANT_ABUNDANCE: the rows of the call's final CSR (off / leaves, in device memory) go into the log, device to device.
@@ -2466,6 +2553,8 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     t.layout_valid = false;
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
+    cover_clear(t);
+    t.cov_bits_valid = false;
     PFQ_TRY(reserve_rows(t, t.n_rows + 2));
     if (!t.greedy_blocks) {
         hipDeviceProp_t prop;
@@ -2758,7 +2847,8 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
     out->tree_leaves = t.is_shard ? t.tree_leaves : out->n_leaves;
     out->device_bytes = t.d_bits.bytes() + t.d_S.bytes() + t.d_pairs.bytes() + t.d_sorted.bytes() + t.d_fail.bytes() +
                         t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes() +
-                        t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes();  // (the abundance log)
+                        t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes() +  // (the abundance log)
+                        t.d_cov_regs.bytes() + t.d_cov_cnt.bytes();                                                   // (the coverage sketch)
     return PFQ_OK;
 }
 
@@ -2776,6 +2866,8 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
     t.layout_valid = false;
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
+    cover_clear(t);
+    t.cov_bits_valid = false;
     return PFQ_OK;
 }
 
@@ -2811,6 +2903,7 @@ static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     if ((flags & PFQ_WANT_SCORES) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SCORES needs PFQ_WANT_HITS");
     if ((flags & PFQ_WANT_ABUNDANCE) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_ABUNDANCE needs PFQ_WANT_HITS");
     if ((flags & PFQ_WANT_ABUNDANCE) && t.is_shard) return abund_shard_refused();
+    if ((flags & PFQ_WANT_COVERAGE) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_COVERAGE needs PFQ_WANT_HITS");
     if ((flags & PFQ_PAIRED) && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
     if ((flags & PFQ_PAIR_BOTH) && !(flags & PFQ_PAIRED)) return fail(PFQ_ERR_ARG, "PFQ_PAIR_BOTH needs PFQ_PAIRED");
     return PFQ_OK;
@@ -2908,6 +3001,96 @@ int pfq_abundance_reset(pfq_tree *tree) {
     PFQ_TRY(use_device(tree->device));
     HIP_TRY(hipDeviceSynchronize());
     abund_clear(*tree);
+    return PFQ_OK;
+}
+
+int pfq_coverage_reset(pfq_tree *tree) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    HIP_TRY(hipDeviceSynchronize());
+    cover_clear(*tree);
+    return PFQ_OK;
+}
+
+int pfq_coverage_get(pfq_tree *tree, pfq_coverage *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    HIP_TRY(hipDeviceSynchronize());  // the queued sketches
+    const size_t nl = t.leaves.size();
+    const bool held = t.d_cov_regs.p != nullptr;
+    const uint32_t p = held ? t.cov_p : cover_precision(t.knobs);
+    PFQ_TRY(cover_filter_bits(t));
+    t.out_cov_regs.assign((nl << p) + 1, 0);
+    t.out_cov_units.assign(nl + 1, 0);
+    t.out_cov_matched.assign(nl + 1, 0);
+    t.out_cov_distinct.assign(nl + 1, 0.0);
+    t.out_cov_genome.assign(nl + 1, 0.0);
+    if (held && nl) {
+        HIP_TRY(hipMemcpy(t.out_cov_regs.data(), t.d_cov_regs.p, nl << p, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.out_cov_units.data(), t.d_cov_cnt.p, nl * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.out_cov_matched.data(), t.d_cov_cnt.p + nl, nl * 8, hipMemcpyDeviceToHost));
+    }
+    const double d = (double)t.nbits;
+    for (size_t l = 0; l < nl; ++l) {
+        if (held) t.out_cov_distinct[l] = cover_estimate(t.out_cov_regs.data() + (l << p), p);
+        const uint64_t b = t.cov_bits[l];
+        t.out_cov_genome[l] = b >= t.nbits ? 0.0 : -(d / (double)t.hp.num_hashes) * std::log1p(-(double)b / d);
+    }
+    memset(out, 0, sizeof *out);
+    out->n_leaves = nl;
+    out->n_units = t.cov_units;
+    out->precision = p;
+    out->registers = t.out_cov_regs.data();
+    out->units = t.out_cov_units.data();
+    out->matched = t.out_cov_matched.data();
+    out->filter_bits = t.cov_bits.data();
+    out->distinct = t.out_cov_distinct.data();
+    out->genome_kmers = t.out_cov_genome.data();
+    return PFQ_OK;
+}
+
+int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src) {
+    if (!dst || !src) return fail(PFQ_ERR_ARG, "null argument");
+    if (dst == src) return fail(PFQ_ERR_ARG, "pfq_coverage_absorb: dst and src are one tree");
+    pfq_tree &d = *dst, &s = *src;
+    PFQ_TRY(use_device(s.device));
+    PFQ_TRY(build_layout(s));
+    HIP_TRY(hipDeviceSynchronize());
+    PFQ_TRY(use_device(d.device));
+    PFQ_TRY(build_layout(d));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t nl = d.leaves.size();
+    if (s.leaves.size() != nl || d.is_shard != s.is_shard || d.shard_first_leaf != s.shard_first_leaf)
+        return fail(PFQ_ERR_ARG, "pfq_coverage_absorb: the trees do not hold the same leaves (" + std::to_string(nl) + " and " +
+                                 std::to_string(s.leaves.size()) + ")");
+    if (d.hp.k != s.hp.k || d.hp.num_hashes != s.hp.num_hashes || d.hp.nbits != s.hp.nbits || d.hp.a1 != s.hp.a1 || d.hp.a2 != s.hp.a2)
+        return fail(PFQ_ERR_ARG, "pfq_coverage_absorb: the trees differ in their hash parameters");
+    const uint32_t pd = d.d_cov_regs.p ? d.cov_p : cover_precision(d.knobs), ps = s.d_cov_regs.p ? s.cov_p : cover_precision(s.knobs);
+    if (pd != ps)
+        return fail(PFQ_ERR_ARG, "pfq_coverage_absorb: the sketches differ in precision (" + std::to_string(pd) + " and " + std::to_string(ps) + ")");
+    if (s.d_cov_regs.p && nl) {
+        PFQ_TRY(cover_ensure(d, nl, nullptr));  // (nothing was absorbed if this fails)
+        // staged through host memory: the replicas may sit on different devices, and this runs once per job
+        const size_t nr = nl << pd;
+        std::vector<uint8_t> rs(nr), rd(nr);
+        std::vector<unsigned long long> cs(2 * nl), cd(2 * nl);
+        PFQ_TRY(use_device(s.device));
+        HIP_TRY(hipMemcpy(rs.data(), s.d_cov_regs.p, nr, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cs.data(), s.d_cov_cnt.p, 2 * nl * 8, hipMemcpyDeviceToHost));
+        PFQ_TRY(use_device(d.device));
+        HIP_TRY(hipMemcpy(rd.data(), d.d_cov_regs.p, nr, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cd.data(), d.d_cov_cnt.p, 2 * nl * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nr; ++i) rd[i] = std::max(rd[i], rs[i]);
+        for (size_t i = 0; i < 2 * nl; ++i) cd[i] += cs[i];
+        HIP_TRY(hipMemcpy(d.d_cov_regs.p, rd.data(), nr, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.d_cov_cnt.p, cd.data(), 2 * nl * 8, hipMemcpyHostToDevice));
+    }
+    d.cov_units += s.cov_units;
+    PFQ_TRY(use_device(s.device));
+    cover_clear(s);
+    PFQ_TRY(use_device(d.device));
     return PFQ_OK;
 }
 
@@ -3273,6 +3456,7 @@ int pfq_leaf_counts_reset(pfq_tree *tree) {
     }
     for (auto &nd : tree->nodes) nd.mapped_reads = nd.base_reads = 0;
     abund_clear(*tree);
+    cover_clear(*tree);
     return PFQ_OK;
 }
 
@@ -3357,6 +3541,20 @@ int pfq_profile_end(pfq_tree *tree, pfq_profile *out) {
 }
 int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
     if (!tree || !name) return fail(PFQ_ERR_ARG, "null argument");
+    if (!strcmp(name, "PFQ_COVER_P")) {  // the precision of the coverage sketch: in range, and not changed under a sketch that holds units
+        Knobs k = tree->knobs;
+        set_knob(k, name, value);
+        if (k.cover_p != -1 && (k.cover_p < (long long)pfq::COVER_P_MIN || k.cover_p > (long long)pfq::COVER_P_MAX))
+            return fail(PFQ_ERR_ARG, std::string("PFQ_COVER_P must be 4..16, not ") + value);
+        if (tree->d_cov_regs.p && cover_precision(k) != tree->cov_p) {
+            if (tree->cov_units)
+                return fail(PFQ_ERR_STATE, "PFQ_COVER_P cannot change while the coverage sketch holds units (precision " + std::to_string(tree->cov_p) +
+                                           "); pfq_coverage_reset empties it");
+            PFQ_TRY(use_device(tree->device));
+            HIP_TRY(hipDeviceSynchronize());
+            cover_clear(*tree);  // (made by a call without units: the next flagged call makes it anew)
+        }
+    }
     if (!set_knob(tree->knobs, name, value)) return fail(PFQ_ERR_ARG, std::string("unknown option ") + name);
     // knobs of the device layout (column groups, coarse level): the layout is rebuilt before the next use
     if (!strcmp(name, "PFQ_COARSE") || !strcmp(name, "PFQ_COARSE_COLS") || !strcmp(name, "PFQ_GROUP_LOG2") || !strcmp(name, "PFQ_COARSE_MIN_LEAVES")) {

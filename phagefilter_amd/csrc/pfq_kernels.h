@@ -433,6 +433,20 @@ void launch_abund_start(unsigned long long *d_a, unsigned long long *d_nxt, cons
 void launch_abund_step(const AbundStep &s, uint32_t blocks, bool lds, hipStream_t st);
 void launch_abund_delta(unsigned long long *d_a, const unsigned long long *d_nxt, const unsigned long long *d_unique, uint32_t n_leaves,
                         unsigned long long *d_delta, hipStream_t st);
+// PFQ_WANT_COVERAGE (pfq_cover.hip): per leaf a HyperLogLog sketch of the k-mers its units matched.  launch_cover_sketch: over
+// the rows of the call's final CSR d_row_off / d_row_leaves [n_units] (pair_mode 0: unit u is read u; 1 either / 2 both: unit f
+// is reads 2f, 2f + 1), per listed leaf l: units[l] += 1, matched[l] += the unit's k-mers whose probed bits are all set in l's
+// filter (row d_col_row[l] of d_bits; what launch_hit_scores / launch_pair_scores count), and each of those k-mers raises one
+// register of l: registers[l << precision | j] = max(.., rho).  blocks = 0: the built-in grid.
+struct CoverArgs {
+    uint8_t *registers;                   // [n_leaves << precision], 4-byte aligned
+    unsigned long long *units, *matched;  // [n_leaves]
+    uint32_t n_leaves, precision;         // precision: COVER_P_MIN .. COVER_P_MAX
+};
+constexpr uint32_t COVER_P_MIN = 4, COVER_P_MAX = 16, COVER_P_DEFAULT = 12;
+void launch_cover_sketch(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_units, float threshold, int pair_mode,
+                         const unsigned long long *d_row_off, const uint32_t *d_row_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
+                         uint64_t n_words, const CoverArgs &cv, uint32_t blocks, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -217,7 +217,7 @@ class BloomTree:
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
                      want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                     lca: Optional[str] = None, abundance: bool = False):
+                     lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
@@ -225,8 +225,9 @@ class BloomTree:
         `lca`: "all" also assigns every read / fragment to the lowest common ancestor of its hit leaves (last_lca(),
         clade_counts()), "best" to that of its best-scoring hits (needs want_hits and want_scores); the return value and
         every other result stay what they are without it.
-        `abundance`: the call's rows are also logged on the device for abundance() (needs want_hits)."""
-        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits)
+        `abundance`: the call's rows are also logged on the device for abundance() (needs want_hits).
+        `coverage`: every listed genome's matched k-mers are also sketched on the device for coverage() (needs want_hits)."""
+        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits)
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -260,13 +261,13 @@ class BloomTree:
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
                           want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                          lca: Optional[str] = None, abundance: bool = False):
+                          lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, as in query_packed."""
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) |
-                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True))
+                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True))
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -278,18 +279,20 @@ class BloomTree:
         return offs, leaves, self.last_hit_scores()
 
     def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
-                    mode: str = "either", lca: Optional[str] = None, abundance: bool = False) -> List[List[int]]:
+                    mode: str = "either", lca: Optional[str] = None, abundance: bool = False,
+                    coverage: bool = False) -> List[List[int]]:
         """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
         (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments.
         `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca().
-        `abundance`: the fragments' rows are also logged for abundance()."""
+        `abundance`: the fragments' rows are also logged for abundance(); `coverage`: both mates' matched k-mers are also
+        sketched for coverage(), per genome the fragment lists."""
         if lca not in (None, "all", "best"):
             raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
         if len(r1) != len(r2):
             raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
         seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
         offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best", paired=True,
-                                         pair_mode=mode, lca=lca, abundance=abundance)[:2]
+                                         pair_mode=mode, lca=lca, abundance=abundance, coverage=coverage)[:2]
         return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
 
     # ---- clades (lowest common ancestors)
@@ -343,6 +346,35 @@ class BloomTree:
         """Moves the abundance log of `other`, a replica of this database (on any device), into this tree's and empties it."""
         _ffi.check(_ffi.lib().pfq_abundance_absorb(self._h, other._h))
 
+    # ---- coverage (PFQ_WANT_COVERAGE)
+    def coverage(self) -> dict:
+        """Per-genome distinct k-mers and what goes with them, from the `coverage=True` calls so far (pfq_coverage_get), as
+        numpy arrays in the leaf order of get_leaf_counts: `registers` uint8 (n_leaves, 2**precision), the HyperLogLog
+        sketches; `units`, `matched`, `filter_bits` uint64; `distinct`, `genome_kmers` float64; and the ints `n_leaves`,
+        `n_units`, `precision`.  Breadth of coverage is distinct / genome_kmers, duplication matched / distinct.  Before
+        any such call everything but filter_bits and genome_kmers is 0.  The sketch is not consumed."""
+        c = _ffi.Coverage()
+        _ffi.check(_ffi.lib().pfq_coverage_get(self._h, C.byref(c)))
+        n, p = int(c.n_leaves), int(c.precision)
+
+        def arr(ptr, shape, dtype):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy() if n else np.zeros(shape, dtype=dtype)
+        out = {"n_leaves": n, "n_units": int(c.n_units), "precision": p, "registers": arr(c.registers, (n, 1 << p), np.uint8)}
+        for k in ("units", "matched", "filter_bits"):
+            out[k] = arr(getattr(c, k), (n,), np.uint64)
+        for k in ("distinct", "genome_kmers"):
+            out[k] = arr(getattr(c, k), (n,), np.float64)
+        return out
+
+    def coverage_reset(self) -> None:
+        """Empties the coverage sketch and frees it (reset_counts, prune_tree and insert do so as well)."""
+        _ffi.check(_ffi.lib().pfq_coverage_reset(self._h))
+
+    def coverage_absorb(self, other: "BloomTree") -> None:
+        """Merges the coverage sketch of `other`, a replica of this database (on any device) or the same shard of it, into
+        this tree's (registers: element-wise max, counters: sums) and empties it."""
+        _ffi.check(_ffi.lib().pfq_coverage_absorb(self._h, other._h))
+
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
 
@@ -376,6 +408,14 @@ def _abundance_flags(abundance: bool, want_hits: bool) -> int:
     if not want_hits:
         raise ValueError("abundance=True needs the hits (want_hits=True): the log holds the rows of the call's hit lists")
     return _ffi.WANT_ABUNDANCE
+
+
+def _coverage_flags(coverage: bool, want_hits: bool) -> int:
+    if not coverage:
+        return 0
+    if not want_hits:
+        raise ValueError("coverage=True needs the hits (want_hits=True): the genomes a read lists are the ones it is sketched for")
+    return _ffi.WANT_COVERAGE
 
 
 def _pair_flags(paired: bool, pair_mode: str) -> int:
