@@ -377,7 +377,8 @@ typedef struct pfq_stats {
                                  * its survivors and k_tail_records made all their probe records, 64 k-mers a pass
                                  * (theta = 1 with records unless PFQ_SPLIT_RECORDS=0).  Bits 4-6: the shapes of
                                  * last-window pass that served at least one pair — 0x10: sixteen reads x 4 k-mers,
-                                 * 0x20: four x 16, 0x40: two x 32 (none: no last window was left to the batched kernel) */
+                                 * 0x20: four x 16, 0x40: two x 32 (none: no last window was left to the batched kernel).
+                                 * Bit 3 (0x8): k_classify emitted at least one pair a pass at a time (theta = 1, leaf pairs — not in block mode — unless PFQ_BATCH_EMIT=0) */
 } pfq_stats;
 int pfq_last_stats(pfq_tree *tree, pfq_stats *out);
 /* Force a query path: -1 auto, 0 direct, 1 bucketed. */

@@ -100,7 +100,7 @@ struct HostBuf {
 struct Knobs {
     long long record_gb = -1, tile_gb = -1, tile_entries = -1, slice_kb = -1;
     long long verify_blocks = -1, verify_chunk = -1, verify_sub = -1, verify_threads = -1, bin_blocks = -1, test_blocks = -1;
-    long long tile = -1, tile_counts = -1, no_tail_batch = -1, split_records = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1;
+    long long tile = -1, tile_counts = -1, no_tail_batch = -1, split_records = -1, bin_narrow = -1, bin_wide = -1, bin_debug = -1, block = -1, batch_emit = -1;
     long long coarse = -1, coarse_cols = -1, coarse_probes = -1, group_log2 = -1, screen_recs = -1, coarse_min_leaves = -1, greedy_host = -1;
     long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
     long long abund_slots = -1, abund_blocks = -1, abund_lds = -1;  // PFQ_WANT_ABUNDANCE: cap on the log's leaf entries; grid and LDS use of the EM step
@@ -122,7 +122,7 @@ const KnobName KNOBS[] = {
 #ifdef PFQ_EXPERIMENTS  // (timing experiments with wrong results: not in the library as shipped)
     {"PFQ_BIN_DEBUG", &Knobs::bin_debug},
 #endif
-    {"PFQ_BLOCK", &Knobs::block},
+    {"PFQ_BLOCK", &Knobs::block},               {"PFQ_BATCH_EMIT", &Knobs::batch_emit},
     {"PFQ_COARSE", &Knobs::coarse},             {"PFQ_COARSE_COLS", &Knobs::coarse_cols},
     {"PFQ_COARSE_PROBES", &Knobs::coarse_probes}, {"PFQ_GROUP_LOG2", &Knobs::group_log2},
     {"PFQ_SCREEN_RECS", &Knobs::screen_recs},   {"PFQ_COARSE_MIN_LEAVES", &Knobs::coarse_min_leaves},
@@ -1567,6 +1567,7 @@ struct QueryRun {
         // (PFQ_SPLIT_RECORDS=0: k_classify hashes every window it does not leave to the batched tails)
         a.split_recs = (recs && !counts_mode && kn.split_records != 0) ? 1u : 0u;
         a.block_pairs = block_mode ? 1u : 0u;
+        a.batch_emit = kn.batch_emit != 0 ? 1u : 0u;  // (PFQ_BATCH_EMIT=0: the per-read loop for every survivor)
         a.screen_recs = kn.screen_recs >= 0 ? (uint32_t)(kn.screen_recs != 0) : 1u;
         if (block_mode) {
             if (!t.tables_valid) {  // (the leaf set changed, or first use)
@@ -3482,7 +3483,8 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
         unsigned long long c[CUR_TAIL_SHAPES + 1];
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
         const uint32_t shapes = t.last_path ? (uint32_t)c[CUR_TAIL_SHAPES] : 0u;  // pfq::TAIL_SHAPE_*
-        out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u);
+        out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u) |
+                          ((t.last_path && h[pfq::ST_BATCHED]) ? 8u : 0u);
         out->n_chunks = (uint32_t)c[CUR_CHUNKS_FLAGGED];
         out->n_fallback_pairs = (uint32_t)(c[CUR_CHUNKS_FLAGGED] >> 32);
         out->tile_entries = c[CUR_TILE_ENTRIES];

@@ -26,7 +26,7 @@ namespace pfq {
 #define PFQ_DEBUG_BITS(a) 0u
 #endif
 constexpr uint32_t PAIR_RESERVE = 32, MISS_RESERVE = 256;
-enum StatSlot { ST_CANDIDATES = 0, ST_HITS = 1, ST_ALLHIT = 2, ST_ALG_BYTES = 3, ST_DEFERRED = 4, ST_LISTED = 5 /* (read, leaf group) entries of a two-level frontier */, ST_N = 8 };
+enum StatSlot { ST_CANDIDATES = 0, ST_HITS = 1, ST_ALLHIT = 2, ST_ALG_BYTES = 3, ST_DEFERRED = 4, ST_LISTED = 5 /* (read, leaf group) entries of a two-level frontier */, ST_BATCHED = 6 /* pairs emitted a pass at a time */, ST_N = 8 };
 
 struct QueryArgs {
     HashParams hp;
@@ -75,6 +75,7 @@ struct QueryArgs {
     uint32_t batch_tails;        // theta == 1 with records: last windows of <= batch_tails k-mers (0: none, 16 or 32) are left to k_tail_records
     uint32_t split_recs;         // 1 (theta == 1 with records): k_classify only defers; k_tail_records makes every record of a deferred read
     uint32_t block_pairs;        // 1 (DEFER, theta == 1, no guard columns): defer (read, block of 8 leaves | candidate mask << 24)
+    uint32_t batch_emit;         // 1 (DEFER, theta == 1, leaf pairs): the survivors of a pass of the dense screen are emitted together (PFQ_BATCH_EMIT)
     uint32_t screen_recs;        // thresholds < 1: the dense counting screen writes the probe records of the k-mers it hashes
     uint32_t screen_only;        // (launches without deferral) count the frontier's candidate leaves, certify nothing, count no read
     // thresholds < 1: every deferred pair owns ceil(n/64) u64 words of k-mer miss bits.  k_classify only accounts for

@@ -703,8 +703,10 @@ __device__ __forceinline__ uint32_t queue_long_reads(const QueryArgs &a, uint32_
 // BLOCKS (DEFER, theta == 1, no guard columns): survivors are deferred per block of 8 leaf columns — (read, block | mask of
 // the candidate leaves << 24) — see TILE_LOG2_BLOCK.
 // LIST: the launch of a leaf group of a two-level frontier — its reads are the ones k_coarse listed for the group (read_list).
+// (the theta = 1 builds that defer leaf pairs are held to four waves per SIMD — 128 VGPRs: with the batched emission beside the
+// per-read path the allocator stops at 129 on its own, bounded it takes 124 without a spill.)
 template <bool DEFER, bool COUNTS, bool LONG = false, uint32_t LPR_LOG2 = 0, bool BLOCKS = false, bool LIST = false>
-__global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_LOG2 != 4) ? 3 : 1) k_classify(QueryArgs a) {
+__global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_LOG2 != 4) ? 3 : ((DEFER && !COUNTS && !BLOCKS) ? 4 : 1)) k_classify(QueryArgs a) {
     __shared__ BlockLds lds;
     __shared__ DenseLds<(DEFER && !LONG) || COUNTS> dlds;
     fill_complement(lds.comp);
@@ -863,6 +865,108 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
         }
     };
 
+    // Batched emission (theta == 1, leaf pairs, a.batch_emit): the survivors of a pass of the dense screen are regular reads
+    // (need == n, no miss tolerated), so all a wave has to do for them is turn the set bits of their frontier words — still in
+    // LDS, dlds.live[wave][read * rw + word], masked with the leaf columns — into pairs.  Lanes are (read = lane >> 2, quarter
+    // of the row = lane & 3) as in the screen's hashing: a lane counts the bits of its rw / 4 words, an exclusive prefix sum
+    // over the wave gives it the slot of its first pair — lane order is read-major and column-ascending, which keeps a
+    // read's pairs in consecutive slots (k_tail_records) — and every lane writes its own pairs.  Slots come from the wave's
+    // current reservation while it lasts and from ONE further reservation of whole chunks for the rest, whose unused end
+    // becomes the current reservation.  Returns the reads left to process_read: the ones whose records would not fit, and the
+    // reads whose pairs reach past the end of a full pair buffer (process_read certifies inline what finds no slot: results
+    // do not depend on capacities).
+    uint32_t st_bat = 0;  // pairs written here (ST_BATCHED)
+    const bool batch_emit = DEFER && !COUNTS && !BLOCKS && a.batch_emit && (!a.recs || a.split_recs);
+    const bool recs_fit = !a.recs || a.off[a.n_reads] <= a.rec_cap;  // (wave-uniform) every read's records fit
+    auto emit_pass = [&](uint32_t survive, uint32_t rid, uint64_t lane_len) -> uint32_t {
+        const uint32_t jj = lane >> 2, t = lane & 3u, qw = rw >> 2;
+        uint32_t take = survive;
+        if (!recs_fit) {
+            bool fits = true;
+            if (t == 0 && ((survive >> jj) & 1u)) fits = a.off[rid] + (lane_len - a.hp.k + 1) <= a.rec_cap;  // (regular: length >= k)
+            uint64_t nf = ballot64(!fits);
+            while (nf) {
+                take &= ~(1u << (((uint32_t)__ffsll((unsigned long long)nf) - 1u) >> 2));
+                nf &= nf - 1ull;
+            }
+            if (!take) return survive;
+        }
+        const bool mine = (take >> jj) & 1u;
+        const uint32_t *lw = dlds.live[wave] + jj * rw + t * qw;
+        uint32_t c = 0;
+        if (mine) {
+            if (qw >= 4u) {
+                for (uint32_t u = 0; u < qw; u += 4u) {
+                    const uint4 w4 = *reinterpret_cast<const uint4 *>(lw + u);
+                    c += (uint32_t)(__popc(w4.x) + __popc(w4.y) + __popc(w4.z) + __popc(w4.w));
+                }
+            } else {
+                for (uint32_t u = 0; u < qw; ++u) c += (uint32_t)__popc(lw[u]);
+            }
+        }
+        uint32_t incl;  // inclusive prefix sum of c over the lanes
+        if (ballot64(c > 1u) == 0) {  // (the common pass: a survivor has one candidate leaf) the lanes below mine that hold a pair
+            const uint64_t ones = ballot64(c != 0u);
+            incl = __builtin_amdgcn_mbcnt_hi((uint32_t)(ones >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ones, 0u)) + c;
+        } else {
+            incl = c;
+#pragma unroll
+            for (uint32_t d = 1; d < 64u; d <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+                if (lane >= d) incl += up;
+            }
+        }
+        uint32_t T = bcast_u32(incl, 63);  // pairs of the pass
+        const uint32_t left = PAIR_CHUNK - pair_used;
+        unsigned long long nbase = 0;
+        bool put = mine, full = false;
+        if (T > left) {  // (wave-uniform) one reservation of whole chunks for what the current one does not hold
+            const unsigned long long want = (unsigned long long)((T - left + PAIR_CHUNK - 1u) / PAIR_CHUNK) * PAIR_CHUNK;
+            if (lane == 0) nbase = atomicAdd(a.pair_cursor, want);
+            nbase = bcast_u64(nbase, 0);
+            if (nbase + want > a.pair_cap) {
+                // The pair buffer is full.  The reads whose pairs all lie below its end are still emitted here (they are the
+                // first of the pass), the slots behind them are voided and no reservation is kept; the other reads are left
+                // to process_read, which certifies inline what it finds no slot for.
+                full = true;
+                const uint32_t room = left + (nbase < a.pair_cap ? (uint32_t)(a.pair_cap - nbase) : 0u);
+                put = mine && (uint32_t)__shfl((int)incl, (int)(lane | 3u)) <= room;
+                const uint64_t pb = ballot64(put);
+                T = pb ? bcast_u32(incl, 63 - (int)__clzll((unsigned long long)pb)) : 0u;
+                take = 0;
+                for (uint32_t j = 0; j < DENSE_READS; ++j) take |= (uint32_t)((pb >> (4u * j)) & 1ull) << j;
+                for (unsigned long long i = nbase + (T > left ? T - left : 0u) + lane; i < a.pair_cap; i += 64) a.pairs[i] = make_uint2(0xffffffffu, 0xffffffffu);
+            }
+        }
+        if (put) {
+            uint32_t s = incl - c;
+            const uint32_t sub_mask = (1u << a.sub_log2) - 1u;
+            for (uint32_t u = 0; u < qw; ++u) {
+                uint32_t w = lw[u];
+                const uint32_t cbase = a.col0 + (t * qw + u) * 32u;
+                while (w) {
+                    const uint32_t col = cbase + (uint32_t)__ffs((int)w) - 1u;
+                    w &= w - 1u;
+                    a.pairs[s < left ? pair_base + pair_used + s : nbase + (s - left)] = make_uint2(rid, col);
+                    atomicAdd(&a.bucket_cnt[(col << a.sub_log2) | (rid & sub_mask)], 1u);
+                    ++s;
+                }
+            }
+            dense_bytes += lane_len;  // (on the read's first lane)
+        }
+        if (T <= left) {
+            pair_used += T;
+        } else {  // the new reservation's last chunk, if partly used, is the wave's current one (voided when the buffer is full)
+            const uint32_t over = T - left;
+            pair_base = nbase + (over & ~(PAIR_CHUNK - 1u));
+            pair_used = ((over & (PAIR_CHUNK - 1u)) && !full) ? (over & (PAIR_CHUNK - 1u)) : PAIR_CHUNK;
+        }
+        st_cand += T;
+        st_def += T;
+        st_bat += T;
+        return survive & ~take;
+    };
+
     // the reads of this launch: all of them, or (leaf group of a two-level frontier) the ones k_coarse listed for the group
     uint64_t n_work = a.n_reads;
     if (LIST) n_work = *a.n_list;
@@ -878,6 +982,7 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
             uint32_t survive = dense_screen<false>(dlds.mini[wave][0], dlds.mini[wave][1], lds.comp, dlds.live[wave], a, read_list, r0, cnt,
                                                    colmask, 2u, irregular, lane_len, rid);
             if (!(((survive | irregular) >> (lane >> 2)) & 1u)) dense_bytes += lane_len;  // reads finished here still count their bytes
+            if (!BLOCKS && batch_emit && survive) survive = emit_pass(survive, rid, lane_len);
             while (survive) {
                 const uint32_t jj = (uint32_t)__ffs((int)survive) - 1u;
                 survive &= survive - 1u;
@@ -964,6 +1069,7 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
         if (st_all) atomicAdd(&a.stats[ST_ALLHIT], st_all);
         if (st_bytes) atomicAdd(&a.stats[ST_ALG_BYTES], st_bytes);
         if (st_def) atomicAdd(&a.stats[ST_DEFERRED], st_def);
+        if (st_bat) atomicAdd(&a.stats[ST_BATCHED], (unsigned long long)st_bat);
     }
 }
 
