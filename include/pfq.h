@@ -298,6 +298,50 @@ int pfq_coverage_reset(pfq_tree *tree);
  * PFQ_ERR_ARG.  Staged through host memory: this runs once per job. */
 int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src);
 
+/* ---- frames and segments (pfq_query_frames) ----
+ * Where on a long sequence (an assembled contig, a long read) does a genome match?  Every sequence is cut into overlapping
+ * frames of `frame` = F bases every `step` = S bases, k <= F and 1 <= S <= F (else PFQ_ERR_ARG); each frame is classified exactly
+ * as pfq_query_batch classifies a read holding those bytes; runs of consecutive frames that hit a leaf become segments, and each
+ * segment is refined to k-mer resolution on that leaf's own filter.
+ * Frames of a sequence of L bases: L <= F: one frame, [0, L).  Otherwise n = ceil((L - F) / S) + 1 frames, frame j = [s_j, s_j + F)
+ *   with s_j = min(j * S, L - F): the last frame is flush with the end, no frame is a short tail.
+ * Frame hits: H_j = the ascending leaf set pfq_query_batch(.., threshold, PFQ_WANT_HITS) gives a read made of frame j's bytes:
+ *   its own n_kmers and need, guards and the coarse level as they are, any threshold (<= 0 and NaN included); a sequence shorter
+ *   than k is one frame without k-mers and passes every leaf, as such a read does.
+ * Segments: for a leaf l, a maximal run j0..j1 of consecutive frames with l in H_j:
+ *   first_frame = j0, n_frames = j1 - j0 + 1, begin = s_j0, end = s_j1 + len(frame j1) (0-based, half-open);
+ *   kmers = the k-mer positions p in [begin, end - k] (0 if end - begin < k);
+ *   matched = those whose canonical k-mer has all num_hashes probed bits set in l's own filter (the test PFQ_WANT_SCORES counts);
+ *   match_begin = the smallest such p, match_end = the largest such p plus k (matched == 0: both equal begin);
+ *   longest_run = the longest run of consecutive matching positions.
+ * Order: by sequence, then first_frame, then leaf; seg[offsets[i] .. offsets[i + 1]) are the segments of sequence i.
+ * Leaf counters: += 1 per (sequence, distinct leaf among its segments) — they count sequences, as mapped_reads counts reads.
+ *   With F >= the longest sequence of a call the counters and the per-sequence leaf sets equal those of
+ *   pfq_query_batch(.., PFQ_WANT_HITS) on the same input.  Results do not depend on how the sequences are cut into calls, on the
+ *   query path or on any knob.
+ * Limits, PFQ_ERR_UNSUPPORTED with a message that says which, nothing counted: a sequence of 2^32 bases or more; 2^32 - 1 frames
+ *   or more in one call (the classification takes a block of fewer than 2^31 - 1024: that is the limit in force); frame bytes
+ *   (about the input times F / S) that do not fit in device memory.
+ * Subtree shards are accepted: a leaf's segments depend only on that leaf's frame hits, so a shard's segments are the whole
+ *   tree's for its leaves, with leaf indices local to the shard.
+ * flags must be 0 (else PFQ_ERR_ARG): frames do not combine with pairs, LCA, abundance or coverage.  Both calls are synchronous.
+ * Afterwards pfq_last_hit_scores and pfq_last_lca answer PFQ_ERR_ARG, as after a call without their flags; pfq_last_stats and
+ * pfq_debug_last_capacity describe the inner classification, whose n_reads is the number of frames.  Sticky insert errors, the
+ * empty tree (PFQ_ERR_STATE) and the stream-ordering rules are those of pfq_query_batch_device; total_bytes as there (unused).
+ * The option PFQ_FRAME_PIECE (a positive multiple of 64, else PFQ_ERR_ARG) is how many k-mer positions one wave refines. */
+typedef struct pfq_segment {
+    uint32_t leaf, first_frame, n_frames, begin, end, match_begin, match_end, kmers, matched, longest_run;
+} pfq_segment;
+typedef struct pfq_segments {
+    uint64_t n_seqs, n_frames;
+    const uint64_t *offsets; /* [n_seqs + 1] */
+    const pfq_segment *seg;  /* [offsets[n_seqs]] */
+} pfq_segments;              /* library-owned until the next query call on the tree */
+int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets, uint64_t n_seqs, uint32_t frame, uint32_t step,
+                     float threshold, uint32_t flags, pfq_segments *out);
+int pfq_query_frames_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bytes,
+                            uint32_t frame, uint32_t step, float threshold, uint32_t flags, void *stream, pfq_segments *out);
+
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);
 /* save_leaf_counts (query.rs:173-183): "<tax_id>,<count>\n" for count > 0, no header. */

@@ -17,6 +17,7 @@ SYMBOLS = [
     "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
+    "pfq_query_frames", "pfq_query_frames_device",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
@@ -75,6 +76,15 @@ class Coverage(C.Structure):
                 ("registers", C.POINTER(C.c_uint8)),
                 ("units", C.POINTER(C.c_uint64)), ("matched", C.POINTER(C.c_uint64)), ("filter_bits", C.POINTER(C.c_uint64)),
                 ("distinct", C.POINTER(C.c_double)), ("genome_kmers", C.POINTER(C.c_double))]
+
+
+class Segment(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("leaf", "first_frame", "n_frames", "begin", "end", "match_begin", "match_end", "kmers",
+                                          "matched", "longest_run")]
+
+
+class Segments(C.Structure):
+    _fields_ = [("n_seqs", C.c_uint64), ("n_frames", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("seg", C.POINTER(Segment))]
 
 
 WANT_HITS = 1
@@ -137,6 +147,9 @@ def lib() -> C.CDLL:
     L.pfq_coverage_get.argtypes = [vp, C.POINTER(Coverage)]
     L.pfq_coverage_reset.argtypes = [vp]
     L.pfq_coverage_absorb.argtypes = [vp, vp]
+    L.pfq_query_frames.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(Segments)]
+    L.pfq_query_frames_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
+                                          C.POINTER(Segments)]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

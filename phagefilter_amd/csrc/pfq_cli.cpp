@@ -1474,6 +1474,70 @@ struct QueryLoop {
         if (!src.err.empty()) rq.pending_error = src.err;  // fatal later, after the outputs of the fragments before it
     }
 
+    // --frame: sequences batch by batch, whole sequences dealt to the replicas in contiguous shares (a sequence's segments and
+    // its count need all of its frames), each share one pfq_query_frames on the replica's own thread; then the batch's lines
+    // are written in input order.  A batch is cut by sequences (PFQ_CLI_BATCH_READS) and by bases, so that the frames' bytes of
+    // one call — its bases times frame / step — stay near 1 GiB and its frames far below the call's limit; a sequence larger
+    // than that is a call of its own.  The results do not depend on the cut.
+    void frames(uint32_t frame, uint32_t step, const std::string &tsv) {
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv);
+        fputs("sequence\tgenome\tbegin\tend\tmatch_begin\tmatch_end\tframes\tkmers\tmatched\tlongest_run\n", f);
+        const uint64_t batch_seqs = batch_size(1u << 16);
+        const uint64_t batch_bases = std::max<uint64_t>(1, (uint64_t)((double)(1ull << 30) * step / frame));
+        struct Part {
+            std::vector<uint64_t> off, call_off;
+            std::vector<pfq_segment> seg;
+        };
+        std::vector<Part> parts(n_trees());
+        Batch b;
+        std::string lines;
+        char num[128];
+        bool more = true;
+        while (more) {
+            b.clear();
+            more = rq.fill(b, batch_seqs, batch_bases);
+            const uint64_t n = b.n();
+            if (!n) continue;
+            b.seq.resize(b.seq.size() + 16);
+            const uint64_t tq0 = ReadQueue::now_ns();
+            fan_out(n_trees(), [&](size_t i) {
+                const size_t P = n_trees();
+                const uint64_t r0 = n * i / P, r1 = n * (i + 1) / P;
+                Part &p = parts[i];
+                p.off.assign(r1 - r0 + 1, 0);
+                p.seg.clear();
+                if (r1 == r0) return;
+                p.call_off.resize(r1 - r0 + 1);
+                for (uint64_t r = r0; r <= r1; ++r) p.call_off[r - r0] = b.off[r] - b.off[r0];
+                pfq_segments sg{};
+                if (pfq_query_frames(db.trees[i], b.seq.data() + b.off[r0], p.call_off.data(), r1 - r0, frame, step, threshold, 0, &sg) != PFQ_OK)
+                    fail_from_thread(pfq_last_error());
+                p.off.assign(sg.offsets, sg.offsets + (r1 - r0) + 1);
+                p.seg.assign(sg.seg, sg.seg + sg.offsets[r1 - r0]);
+            });
+            ns_gpu += ReadQueue::now_ns() - tq0;
+            n_total += n;
+            lines.clear();
+            for (size_t i = 0; i < n_trees(); ++i) {
+                const uint64_t r0 = n * i / n_trees();
+                const Part &p = parts[i];
+                for (uint64_t u = 0; u + 1 < p.off.size(); ++u)
+                    for (uint64_t j = p.off[u]; j < p.off[u + 1]; ++j) {
+                        const pfq_segment &s = p.seg[j];
+                        const std::string_view id = b.id(r0 + u);
+                        lines.append(id.data(), id.size());
+                        lines.push_back('\t');
+                        lines.append(db.leaf_names[s.leaf]);
+                        lines.append(num, (size_t)snprintf(num, sizeof num, "\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", s.begin, s.end, s.match_begin, s.match_end,
+                                                           s.n_frames, s.kmers, s.matched, s.longest_run));
+                    }
+            }
+            if (!lines.empty() && fwrite(lines.data(), 1, lines.size(), f) != lines.size()) die("short write to SEGMENTS.tsv");
+        }
+        if (fclose(f) != 0) die("short write to SEGMENTS.tsv");
+    }
+
     // Counts only: the next parsed segment in input order, padded for the device, or nullptr at the end of the input.
     // `end`: nothing follows it — malformed input ends the input (the reads before it are still classified).
     Segment *fetch_segment(bool &end) {
@@ -1896,7 +1960,8 @@ int cmd_query(int argc, char **argv) {
                              {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
-                             {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true}};
+                             {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
+                             {"frame", 0, true}, {"frame-step", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -1938,6 +2003,31 @@ int cmd_query(int argc, char **argv) {
         const long v = strtol(coverage_p.c_str(), &end, 10);
         if (coverage_p.empty() || !isdigit((unsigned char)coverage_p[0]) || *end || v < 4 || v > 16)
             die("error: invalid value '" + coverage_p + "' for '--coverage-precision': 4 to 16 (2^P registers per genome)");
+    }
+    // --frame F [--frame-step S]: every sequence (a contig, a long read) is classified in overlapping frames of F bases every S
+    // bases (pfq_query_frames) and SEGMENTS.tsv says where on it every genome matched; CLASSIFICATION.csv then counts sequences
+    const bool framed = a.val.count("frame") != 0;
+    if (a.val.count("frame-step") && !framed) die("error: '--frame-step' needs '--frame <F>'");
+    uint32_t frame = 0, frame_step = 0;
+    if (framed) {
+        auto positive = [&](const char *name) {
+            const std::string v = a.val.at(name);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long x = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || !isdigit((unsigned char)v[0]) || *end || errno || x == 0 || x > 0xffffffffull)
+                die("error: invalid value '" + v + "' for '--" + name + "': a positive number of bases");
+            return (uint32_t)x;
+        };
+        frame = positive("frame");
+        frame_step = a.val.count("frame-step") ? positive("frame-step") : std::max<uint32_t>(frame / 2, 1);
+        if (frame_step > frame)
+            die("error: '--frame-step " + std::to_string(frame_step) + "' is larger than '--frame " + std::to_string(frame) + "': frames would leave gaps");
+        for (const char *other : {"reads2", "shard-depth"})
+            if (a.val.count(other)) die(std::string("error: '--frame' cannot be used with '--") + other + "'");
+        for (const char *other : {"interleaved", "scores", "abundance", "coverage", "pos-filter", "neg-filter"})
+            if (a.flags.count(other)) die(std::string("error: '--frame' cannot be used with '--") + other + "'");
+        if (lca) die("error: '--frame' cannot be used with '--lca'");
     }
     const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
@@ -2000,7 +2090,7 @@ int cmd_query(int argc, char **argv) {
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    if (block != 0) rq.start(per_read || paired, threads);  // (paired: the mates' ids are compared)
+    if (block != 0) rq.start(per_read || paired || framed, threads);  // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences)
     if (block != 0 && rq2) rq2->start(true, threads);
 
     // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
@@ -2009,11 +2099,13 @@ int cmd_query(int argc, char **argv) {
     mkdir(out.c_str(), 0777);
     Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads);
     uint64_t kmer_size = 0;
-    if (scores) {
+    if (scores || framed) {
         pfq_info info{};
         check(pfq_tree_info(db.trees[0], &info));
         kmer_size = info.kmer_size;
     }
+    if (framed && frame < kmer_size)
+        die("error: '--frame " + std::to_string(frame) + "' is shorter than the database's k-mers (k = " + std::to_string(kmer_size) + "): a frame must hold one");
     db.load_leaf_names();
     if (lca_reads) db.load_clade_names();
 
@@ -2021,6 +2113,8 @@ int cmd_query(int argc, char **argv) {
     QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage};
     if (block == 0) {
         // nothing to do: see above
+    } else if (framed) {
+        q.frames(frame, frame_step, out + "/SEGMENTS.tsv");
     } else if (paired) {
         q.paired(rq2.get(), pair_mode == "both");
     } else if (!per_read) {
@@ -2278,6 +2372,16 @@ void usage() {
             "outputs stay as they are.  Works with --shard-depth (the shards' lines follow one another) and with --devices (the\n"
             "replicas' sketches are merged first).  --coverage-precision <P> (needs --coverage): 2^P one-byte registers per genome,\n"
             "4 to 16 (default 12: 4 KiB per genome, standard error 1.6 %%)\n"
+            "--frame <F> [--frame-step <S>]: for contigs and long reads.  Every sequence is cut into overlapping frames of F bases\n"
+            "every S bases (default S = max(F / 2, 1); the last frame is flush with the sequence's end), every frame is classified like a\n"
+            "read at -f, runs of consecutive frames that hit a genome become segments, and SEGMENTS.tsv in --out says where each lies:\n"
+            "\"sequence<TAB>genome<TAB>begin<TAB>end<TAB>match_begin<TAB>match_end<TAB>frames<TAB>kmers<TAB>matched<TAB>longest_run\", one line per\n"
+            "segment in input order, then by first frame and genome; coordinates are 0-based and half-open; kmers / matched: k-mer\n"
+            "positions of [begin, end) and those the genome's filter contains, match_begin / match_end: from the first to the end of the\n"
+            "last of them, longest_run: the longest stretch of consecutive ones.  Sequences without segments have no line.\n"
+            "CLASSIFICATION.csv then counts sequences, one per genome with a segment.  Works with --devices (whole sequences are dealt to\n"
+            "the replicas; the files do not depend on the device list, -t or the batch size).  Not with --reads2, --interleaved,\n"
+            "--scores, --lca, --abundance, --coverage, --shard-depth, --pos-filter or --neg-filter; F must be at least the database's k\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
 }
 

@@ -41,18 +41,6 @@ __device__ __forceinline__ void cover_raise(uint8_t *regs, uint64_t at, uint32_t
     }
 }
 
-// The kernel's cold pointers (used once per unit, chunk or read) are kept in vector registers: the probing loop below needs
-// nearly every scalar register there is, and a pointer that waits in one through it would push others out to spill lanes.
-// What is loaded through such a pointer is wave-uniform all the same, and is said to be (uniform64).
-template <typename T>
-__device__ __forceinline__ T *in_vgpr(T *ptr) {
-    asm("" : "+v"(ptr));
-    return ptr;
-}
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-
 // One read of a unit against the (up to 64) leaves of a chunk of its row: lane j holds leaf j (my_leaf, filter row my_row;
 // lanes j >= nh: none) and returns how many of the read's k-mers leaf j matched.  Window by window, every lane hashes its
 // k-mer once.  ALL: every k-mer of the read is contained in every listed leaf, so every valid lane raises a register of every

@@ -349,6 +349,19 @@ __device__ __forceinline__ uint64_t need_kmers(float threshold, uint64_t n) {
     return (uint64_t)c;
 }
 
+// ---- cold pointers of the probing post-stages (pfq_cover.hip, pfq_frames.hip) -------------------------------------------
+// A kernel's cold pointers (used once per unit, chunk or read) are kept in vector registers: its probing loop needs
+// nearly every scalar register there is, and a pointer that waits in one through it would push others out to spill lanes.
+// What is loaded through such a pointer is wave-uniform all the same, and is said to be (uniform64).
+template <typename T>
+__device__ __forceinline__ T *in_vgpr(T *ptr) {
+    asm("" : "+v"(ptr));
+    return ptr;
+}
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
 // ---- synthetic workload PRNG (mirrors oracle/pfq_oracle.c) --------------------------------------------
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;

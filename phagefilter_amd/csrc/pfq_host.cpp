@@ -105,6 +105,7 @@ struct Knobs {
     long long pair_slots = -1, guard_slots = -1, miss_words = -1, kmiss_bytes = -1, hit_slots = -1;  // tests: capacities below the built-in ones
     long long abund_slots = -1, abund_blocks = -1, abund_lds = -1;  // PFQ_WANT_ABUNDANCE: cap on the log's leaf entries; grid and LDS use of the EM step
     long long cover_p = -1, cover_blocks = -1;  // PFQ_WANT_COVERAGE: registers per leaf = 2^cover_p (4..16, unset: 12); grid of the sketch kernel
+    long long frame_piece = -1;                 // pfq_query_frames: k-mer positions per piece of the refinement (a positive multiple of 64)
 };
 struct KnobName {
     const char *name;
@@ -133,6 +134,7 @@ const KnobName KNOBS[] = {
     {"PFQ_ABUND_SLOTS", &Knobs::abund_slots},   {"PFQ_ABUND_BLOCKS", &Knobs::abund_blocks},
     {"PFQ_ABUND_LDS", &Knobs::abund_lds},
     {"PFQ_COVER_P", &Knobs::cover_p},           {"PFQ_COVER_BLOCKS", &Knobs::cover_blocks},
+    {"PFQ_FRAME_PIECE", &Knobs::frame_piece},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -369,6 +371,18 @@ struct pfq_tree {
     std::vector<uint64_t> cov_bits, out_cov_units, out_cov_matched;
     std::vector<uint8_t> out_cov_regs;
     std::vector<double> out_cov_distinct, out_cov_genome;
+    // pfq_query_frames: the frame table of the call (per sequence its first frame and the scan of the lone frames' deficits; per
+    // frame its sequence, start and byte offset), the frames' bytes — the block the inner classification reads, d_fr_bytes
+    // behind d_fr_foff — and what the post-stage makes of the frames' rows: per frame where its segments go, the segments,
+    // their sequences, the queue of long runs, the refinement's pieces.  d_fr_cnt / d_fr_sums: input and scratch of the scans.
+    DevBuf<uint32_t> d_fr_cnt, d_fr_def, d_fr_seq, d_fr_start, d_fr_segseq, d_fr_queue;
+    DevBuf<unsigned long long> d_fr_seq0, d_fr_defoff, d_fr_sums, d_fr_segpos, d_fr_seqseg, d_fr_pieceoff, d_fr_misc;
+    DevBuf<uint64_t> d_fr_foff;
+    DevBuf<uint8_t> d_fr_bytes;
+    DevBuf<pfq::Segment> d_fr_segs;
+    DevBuf<pfq::FramePart> d_fr_parts;
+    HostBuf<uint64_t> h_fr_off;
+    HostBuf<pfq_segment> h_fr_segs;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -1210,6 +1224,10 @@ struct QueryRun {
     pfq::GuardArgs ga{};
     pfq::VerifyArgs v{};
     int vblocks = 512, vthreads = 512;
+    // pfq_query_frames: the reads are a call's frames.  They count into the sink and their CSR stays on the device (d_hit_off /
+    // d_hit_leaves, rows_total entries) for the segment stage; nothing is handed to a caller.
+    bool frames = false;
+    uint64_t rows_total = 0;
 
     QueryRun(pfq_tree &t_, const uint8_t *seq_, const uint64_t *off_, uint64_t n_, uint64_t bytes_, float thr_, uint32_t flags_, hipStream_t st_,
              pfq_hits *hits_)
@@ -1239,7 +1257,7 @@ struct QueryRun {
         PFQ_TRY(ensure_scratch(t, n_reads, want_hits));
         nl = t.leaves.size();
         if (want_cover) PFQ_TRY(cover_ensure(t, nl, st));  // (before anything of the call runs: a failure sketches nothing)
-        if (paired) HIP_TRY(t.d_pair_sink.ensure(nl + 1));
+        if (paired || frames) HIP_TRY(t.d_pair_sink.ensure(nl + 1));
         nc = t.n_cols;  // leaf + guard columns = buckets of the bucketed path (block mode: blocks of 8 leaf columns)
         with_guards = !t.guard_col.empty();
         // bucketed path: threshold 1 (any certificate kernel), or 0 < threshold < 1 with probe records (per-pair k-mer miss bits)
@@ -1516,8 +1534,9 @@ struct QueryRun {
         return PFQ_OK;
     }
 
-    // where the classify / finalize kernels count: the tree's counters, or with PFQ_PAIRED a sink (fragments count afterwards)
-    unsigned long long *count_dst() const { return paired ? t.d_pair_sink.p : t.d_counts.p; }
+    // where the classify / finalize kernels count: the tree's counters, or with PFQ_PAIRED a sink (fragments count afterwards;
+    // the frames of pfq_query_frames likewise: sequences count afterwards)
+    unsigned long long *count_dst() const { return paired || frames ? t.d_pair_sink.p : t.d_counts.p; }
 
     // deferred-pair buffer, bucket histograms, probe records, miss words; block tables on first use
     int setup_pairs() {
@@ -1920,6 +1939,8 @@ struct QueryRun {
             pfq::launch_hits_fill(t.d_hit_pairs.p, n_pairs, t.d_allhit.p, n_reads, t.d_hit_off.p, t.d_hit_cnt.p, t.d_hit_leaves.p, st);
             HIP_TRY(hipGetLastError());
         }
+        rows_total = total;
+        if (frames) return PFQ_OK;
         return deliver_rows(t.d_hit_off.p, t.d_hit_leaves.p, n_reads, total, 0);
     }
 
@@ -2116,6 +2137,141 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
 // Waits for the last query call's work (its stream may since have been destroyed by the caller).
 int wait_last_call(pfq_tree &t) {
     if (t.last_done) HIP_TRY(hipEventSynchronize(t.last_done));
+    return PFQ_OK;
+}
+
+// ---- pfq_query_frames (pfq.h "frames and segments") ----
+static_assert(sizeof(pfq::Segment) == sizeof(pfq_segment) && sizeof(pfq_segment) == 40, "the kernels write pfq_segment");
+uint32_t frame_piece(const Knobs &k) {
+    return k.frame_piece > 0 && k.frame_piece % 64 == 0 && k.frame_piece <= (1ll << 30) ? (uint32_t)k.frame_piece : pfq::FRAME_PIECE_DEFAULT;
+}
+// a few words of the device read on the host, waited for
+int fetch_words(unsigned long long *dst, const unsigned long long *d_src, size_t n, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(dst, d_src, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PFQ_OK;
+}
+// One pfq_query_frames[_device] call, everything queued on `st` and waited for: the frame table and the frames' bytes; the
+// frames classified as a block of reads by QueryRun (hit lists, overflow retry) into the count sink; then, from the rows it
+// leaves on the device, the segments, the sequences' leaf counts — the only writes to the tree's counters — and the
+// refinement.  Host waits beyond QueryRun's: the number of frames, of segments, of pieces (they size buffers), the results.
+int query_frames_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_seqs, uint32_t F, uint32_t S, float threshold,
+                        hipStream_t st, pfq_segments *out) {
+    if (F < t.kmer_size || S < 1 || S > F)
+        return fail(PFQ_ERR_ARG, "pfq_query_frames: frame = " + std::to_string(F) + ", step = " + std::to_string(S) + " (need k = " +
+                                     std::to_string(t.kmer_size) + " <= frame and 1 <= step <= frame)");
+    if (t.root < 0) return fail(PFQ_ERR_STATE, "query on an empty tree");
+    PFQ_TRY(build_layout(t));
+    HIP_TRY(t.h_fr_off.ensure(n_seqs + 1));
+    HIP_TRY(t.h_fr_segs.ensure(1));
+    out->n_seqs = n_seqs;
+    out->n_frames = 0;
+    out->offsets = t.h_fr_off.p;
+    out->seg = t.h_fr_segs.p;
+    t.h_fr_off.p[0] = 0;
+    if (!n_seqs) return PFQ_OK;
+    // (the scratch is reused call after call: as in QueryRun::plan, a call on another stream waits for the last one)
+    if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
+    if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipEventSynchronize(t.last_done));
+    t.last_stream = st;
+    t.have_last_stream = true;
+    if (n_seqs >= 0xffffffffull) return fail(PFQ_ERR_UNSUPPORTED, "pfq_query_frames: 2^32 - 1 frames or more in one call (every sequence has a frame)");
+    const size_t nl = t.leaves.size();
+    // ---- frames per sequence, their scan, the table and the cut
+    HIP_TRY(t.d_fr_cnt.ensure(n_seqs + 1));
+    HIP_TRY(t.d_fr_def.ensure(n_seqs + 1));
+    HIP_TRY(t.d_fr_seq0.ensure(n_seqs + 2));
+    HIP_TRY(t.d_fr_defoff.ensure(n_seqs + 2));
+    HIP_TRY(t.d_fr_seqseg.ensure(n_seqs + 2));
+    HIP_TRY(t.d_fr_sums.ensure((n_seqs + 4095) / 4096 + 2));
+    HIP_TRY(t.d_fr_misc.ensure(4));  // [0] a sequence is too long, [1] segments queued for k_seg_walk, [2..3] totals on their way to the host
+    HIP_TRY(hipMemsetAsync(t.d_fr_misc.p, 0, 4 * 8, st));
+    pfq::launch_frame_count(d_off, n_seqs, F, S, t.d_fr_cnt.p, t.d_fr_def.p, t.d_fr_misc.p, st);
+    pfq::launch_scan_u32(t.d_fr_cnt.p, n_seqs, t.d_fr_sums.p, t.d_fr_seq0.p, st);
+    pfq::launch_scan_u32(t.d_fr_def.p, n_seqs, t.d_fr_sums.p, t.d_fr_defoff.p, st);
+    HIP_TRY(hipGetLastError());
+    unsigned long long w[2] = {0, 0}, too_long = 0;
+    HIP_TRY(hipMemcpyAsync(&w[0], t.d_fr_seq0.p + n_seqs, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&w[1], t.d_fr_defoff.p + n_seqs, 8, hipMemcpyDeviceToHost, st));
+    PFQ_TRY(fetch_words(&too_long, t.d_fr_misc.p, 1, st));
+    if (too_long) return fail(PFQ_ERR_UNSUPPORTED, "pfq_query_frames: a sequence of 2^32 bases or more (or offsets that do not ascend); nothing was counted");
+    const uint64_t n_frames = w[0], bytes = (uint64_t)F * n_frames - w[1];
+    // (QueryRun takes fewer than 2^31 - 1024 reads a block: that is the limit in force, below the 2^32 - 1 of the frame table)
+    if (n_frames >= (1ull << 31) - 1024)
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_query_frames: " + std::to_string(n_frames) + " frames in one call (the limit is 2^31 - 1024: a smaller step "
+                                         "or longer sequences need several calls); nothing was counted");
+    if (!(soft_ensure(t.d_fr_bytes, bytes + 64) && soft_ensure(t.d_fr_foff, n_frames + 2) && soft_ensure(t.d_fr_seq, n_frames + 1) &&
+          soft_ensure(t.d_fr_start, n_frames + 1) && soft_ensure(t.d_fr_segpos, n_frames + 2) && soft_ensure(t.d_fr_cnt, n_frames + 1) &&
+          soft_ensure(t.d_fr_sums, (n_frames + 4095) / 4096 + 2)))
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_query_frames: no device memory for the frame bytes (" + std::to_string(bytes) + " bytes in " +
+                                         std::to_string(n_frames) + " frames: the input times frame / step); nothing was counted");
+    out->n_frames = n_frames;
+    pfq::FrameArgs fa{d_off, n_seqs, n_frames, F, S, t.d_fr_seq0.p, t.d_fr_defoff.p, t.d_fr_seq.p, t.d_fr_start.p, t.d_fr_foff.p};
+    pfq::launch_frame_cut(fa, d_seq, t.d_fr_bytes.p, st);
+    HIP_TRY(hipGetLastError());
+    // ---- the frames, classified like reads
+    pfq_hits unused{};
+    QueryRun q(t, t.d_fr_bytes.p, t.d_fr_foff.p, n_frames, bytes, threshold, PFQ_WANT_HITS, st, &unused);
+    q.frames = true;
+    PFQ_TRY(q.plan());
+    PFQ_TRY(q.run());
+    // ---- segments from the ascending rows (t.d_hit_off / t.d_hit_leaves)
+    pfq::SegArgs sa{};
+    sa.row_off = t.d_hit_off.p;
+    sa.row_leaves = t.d_hit_leaves.p;
+    sa.n_frames = n_frames;
+    sa.n_leaves = (uint32_t)nl;
+    sa.frame_seq = t.d_fr_seq.p;
+    sa.frame_start = t.d_fr_start.p;
+    sa.frame_off = t.d_fr_foff.p;
+    sa.seq_frame0 = t.d_fr_seq0.p;
+    sa.open_cnt = t.d_fr_cnt.p;
+    sa.seg_pos = t.d_fr_segpos.p;
+    sa.n_queued = t.d_fr_misc.p + 1;
+    sa.counts = t.d_counts.p;
+    uint64_t n_segs = 0;
+    if (q.rows_total) {
+        pfq::launch_seg_count(sa, st);
+        pfq::launch_scan_u32(t.d_fr_cnt.p, n_frames, t.d_fr_sums.p, t.d_fr_segpos.p, st);
+        pfq::launch_seq_seg_off(t.d_fr_seq0.p, t.d_fr_segpos.p, n_seqs, t.d_fr_seqseg.p, st);
+        HIP_TRY(hipGetLastError());
+        unsigned long long ns = 0;
+        PFQ_TRY(fetch_words(&ns, t.d_fr_segpos.p + n_frames, 1, st));
+        n_segs = ns;
+    }
+    if (!n_segs) {
+        std::fill_n(t.h_fr_off.p, n_seqs + 1, 0);
+        return PFQ_OK;
+    }
+    if (n_segs >= 0xffffffffull) return fail(PFQ_ERR_UNSUPPORTED, "pfq_query_frames: 2^32 - 1 segments or more in one call; nothing was counted");
+    HIP_TRY(t.d_fr_segs.ensure(n_segs + 1));
+    HIP_TRY(t.d_fr_segseq.ensure(n_segs + 1));
+    HIP_TRY(t.d_fr_queue.ensure(n_segs + 1));
+    HIP_TRY(t.d_fr_cnt.ensure(std::max<uint64_t>(n_segs, n_frames) + 1));  // (may drop the open counts: they are scanned by now)
+    HIP_TRY(t.d_fr_pieceoff.ensure(n_segs + 2));
+    HIP_TRY(t.d_fr_sums.ensure((n_segs + 4095) / 4096 + 2));
+    HIP_TRY(t.h_fr_segs.ensure(n_segs));
+    sa.open_cnt = t.d_fr_cnt.p;
+    sa.seg = t.d_fr_segs.p;
+    sa.seg_seq = t.d_fr_segseq.p;
+    sa.queue = t.d_fr_queue.p;
+    pfq::launch_seg_fill(sa, t.d_fr_seqseg.p, n_seqs, n_segs, st);
+    // ---- refinement: pieces of the segments' k-mer positions, probed on the sequences themselves
+    const uint32_t piece = frame_piece(t.knobs);
+    pfq::launch_piece_count(t.d_fr_segs.p, n_segs, t.hp.k, piece, t.d_fr_cnt.p, st);
+    pfq::launch_scan_u32(t.d_fr_cnt.p, n_segs, t.d_fr_sums.p, t.d_fr_pieceoff.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(t.h_fr_off.p, t.d_fr_seqseg.p, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, st));
+    unsigned long long n_pieces = 0;
+    PFQ_TRY(fetch_words(&n_pieces, t.d_fr_pieceoff.p + n_segs, 1, st));
+    HIP_TRY(t.d_fr_parts.ensure(n_pieces + 1));
+    pfq::launch_seg_refine(t.hp, d_seq, d_off, t.d_fr_segs.p, t.d_fr_segseq.p, t.d_fr_pieceoff.p, n_segs, n_pieces, piece, t.d_col_row.p, t.d_bits.p,
+                           t.n_words, t.d_fr_parts.p, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(t.h_fr_segs.p, t.d_fr_segs.p, n_segs * sizeof(pfq_segment), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->offsets = t.h_fr_off.p;
+    out->seg = t.h_fr_segs.p;
     return PFQ_OK;
 }
 
@@ -2849,7 +3005,10 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
     out->device_bytes = t.d_bits.bytes() + t.d_S.bytes() + t.d_pairs.bytes() + t.d_sorted.bytes() + t.d_fail.bytes() +
                         t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes() +
                         t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes() +  // (the abundance log)
-                        t.d_cov_regs.bytes() + t.d_cov_cnt.bytes();                                                   // (the coverage sketch)
+                        t.d_cov_regs.bytes() + t.d_cov_cnt.bytes() +                                                  // (the coverage sketch)
+                        t.d_fr_bytes.bytes() + t.d_fr_foff.bytes() + t.d_fr_seq.bytes() + t.d_fr_start.bytes() + t.d_fr_segpos.bytes() +  // (pfq_query_frames)
+                        t.d_fr_cnt.bytes() + t.d_fr_def.bytes() + t.d_fr_seq0.bytes() + t.d_fr_defoff.bytes() + t.d_fr_seqseg.bytes() + t.d_fr_sums.bytes() +
+                        t.d_fr_segs.bytes() + t.d_fr_segseq.bytes() + t.d_fr_queue.bytes() + t.d_fr_pieceoff.bytes() + t.d_fr_parts.bytes() + t.d_fr_misc.bytes();
     return PFQ_OK;
 }
 
@@ -2892,6 +3051,28 @@ void pfq_tree_close(pfq_tree *tree) {
     delete tree;
 }
 
+// The host block of pfq_query_batch / pfq_query_frames into device memory.  Two input buffers and a copy stream of its own: the
+// copy of this block runs while the kernels of the previous block (which read the other buffer) are still at work.  A call
+// that wants no hits returns once its kernels are queued; counts are read by calls that synchronise (pfq_leaf_counts,
+// pfq_last_stats, pfq_tree_close).  slot: which pair (d_seq / d_off or d_seq2 / d_off2) holds the block; the caller records
+// in_free[slot] behind the kernels that read it.
+static int stage_input(pfq_tree &t, const uint8_t *seq, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int &slot) {
+    if (!t.copy_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
+        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    slot = (t.in_slot ^= 1);
+    if (t.in_used[slot]) HIP_TRY(hipEventSynchronize(t.in_free[slot]));  // the kernels that read this buffer are done
+    DevBuf<uint8_t> &ds = slot ? t.d_seq2 : t.d_seq;
+    DevBuf<uint64_t> &dof = slot ? t.d_off2 : t.d_off;
+    HIP_TRY(ds.ensure(total + 16));
+    HIP_TRY(dof.ensure(n_reads + 1));
+    if (total) HIP_TRY(hipMemcpyAsync(ds.p, seq, total, hipMemcpyHostToDevice, t.copy_stream));
+    if (n_reads) HIP_TRY(hipMemcpyAsync(dof.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, t.copy_stream));
+    HIP_TRY(hipStreamSynchronize(t.copy_stream));
+    return PFQ_OK;
+}
+
 // Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
 static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     t.scores_valid = false;
@@ -2925,26 +3106,48 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
     uint64_t total = n_reads ? offsets[n_reads] : 0;
-    // Two input buffers and a copy stream of its own: the copy of this block runs while the kernels of the previous
-    // block (which read the other buffer) are still at work.  A call that wants no hits returns once its kernels are
-    // queued; counts are read by calls that synchronise (pfq_leaf_counts, pfq_last_stats, pfq_tree_close).
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const int slot = (t.in_slot ^= 1);
-    if (t.in_used[slot]) HIP_TRY(hipEventSynchronize(t.in_free[slot]));  // the kernels that read this buffer are done
-    DevBuf<uint8_t> &ds = slot ? t.d_seq2 : t.d_seq;
-    DevBuf<uint64_t> &dof = slot ? t.d_off2 : t.d_off;
-    HIP_TRY(ds.ensure(total + 16));
-    HIP_TRY(dof.ensure(n_reads + 1));
-    if (total) HIP_TRY(hipMemcpyAsync(ds.p, seq, total, hipMemcpyHostToDevice, t.copy_stream));
-    if (n_reads) HIP_TRY(hipMemcpyAsync(dof.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, t.copy_stream));
-    HIP_TRY(hipStreamSynchronize(t.copy_stream));
-    PFQ_TRY(query_device(t, ds.p, dof.p, n_reads, total, threshold, flags, nullptr, hits));
+    int slot = 0;
+    PFQ_TRY(stage_input(t, seq, offsets, n_reads, total, slot));
+    PFQ_TRY(query_device(t, (slot ? t.d_seq2 : t.d_seq).p, (slot ? t.d_off2 : t.d_off).p, n_reads, total, threshold, flags, nullptr, hits));
     HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
     t.in_used[slot] = true;
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
+    return PFQ_OK;
+}
+
+// Flags and arguments of a frames call; like every query call it ends the validity of the previous call's scores and LCAs.
+static int check_frames(pfq_tree *tree, const void *seq, const void *offsets, uint64_t n_seqs, uint32_t flags, pfq_segments *out) {
+    if (!tree || !out || (n_seqs && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
+    tree->scores_valid = false;
+    tree->lca_last = false;
+    if (flags) return fail(PFQ_ERR_ARG, "pfq_query_frames: flags must be 0 (frames do not combine with pairs, LCA, abundance or coverage)");
+    return PFQ_OK;
+}
+static int frames_call(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_seqs, uint32_t frame, uint32_t step, float threshold,
+                       hipStream_t st, pfq_segments *out) {
+    const int rc = query_frames_device(t, d_seq, d_off, n_seqs, frame, step, threshold, st, out);
+    if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
+    return rc;
+}
+
+int pfq_query_frames_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bytes, uint32_t frame,
+                            uint32_t step, float threshold, uint32_t flags, void *stream, pfq_segments *out) {
+    (void)total_bytes;  // (the frames' own buffer is what the classification reads: its size is known)
+    PFQ_TRY(check_frames(tree, d_seq, d_offsets, n_seqs, flags, out));
+    PFQ_TRY(use_device(tree->device));
+    return frames_call(*tree, d_seq, d_offsets, n_seqs, frame, step, threshold, (hipStream_t)stream, out);
+}
+
+int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets, uint64_t n_seqs, uint32_t frame, uint32_t step, float threshold,
+                     uint32_t flags, pfq_segments *out) {
+    PFQ_TRY(check_frames(tree, seq, offsets, n_seqs, flags, out));
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    int slot = 0;
+    PFQ_TRY(stage_input(t, seq, offsets, n_seqs, n_seqs ? offsets[n_seqs] : 0, slot));
+    PFQ_TRY(frames_call(t, (slot ? t.d_seq2 : t.d_seq).p, (slot ? t.d_off2 : t.d_off).p, n_seqs, frame, step, threshold, nullptr, out));
+    HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
+    t.in_used[slot] = true;
     return PFQ_OK;
 }
 
@@ -3556,6 +3759,10 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
             HIP_TRY(hipDeviceSynchronize());
             cover_clear(*tree);  // (made by a call without units: the next flagged call makes it anew)
         }
+    }
+    if (!strcmp(name, "PFQ_FRAME_PIECE") && value && *value) {  // the windows of a piece are whole: a positive multiple of 64
+        const long long v = strtoll(value, nullptr, 10);
+        if (v <= 0 || v % 64 || v > (1ll << 30)) return fail(PFQ_ERR_ARG, std::string("PFQ_FRAME_PIECE must be a positive multiple of 64 up to 2^30, not ") + value);
     }
     if (!set_knob(tree->knobs, name, value)) return fail(PFQ_ERR_ARG, std::string("unknown option ") + name);
     // knobs of the device layout (column groups, coarse level): the layout is rebuilt before the next use

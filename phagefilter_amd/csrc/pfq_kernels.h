@@ -448,6 +448,65 @@ constexpr uint32_t COVER_P_MIN = 4, COVER_P_MAX = 16, COVER_P_DEFAULT = 12;
 void launch_cover_sketch(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_units, float threshold, int pair_mode,
                          const unsigned long long *d_row_off, const uint32_t *d_row_leaves, const uint32_t *d_col_row, const uint64_t *d_bits,
                          uint64_t n_words, const CoverArgs &cv, uint32_t blocks, hipStream_t st);
+// The exclusive scan behind launch_hits_csr on its own: d_off[i] = d_cnt[0] + .. + d_cnt[i - 1], i <= n (d_off[n]: the total);
+// d_sums: ceil(n / 4096) + 1 words of scratch.  n = 0: nothing is written.
+void launch_scan_u32(const uint32_t *d_cnt, uint64_t n, unsigned long long *d_sums, unsigned long long *d_off, hipStream_t st);
+// pfq_query_frames (pfq_frames.hip): sequences cut into overlapping frames, the frames classified like reads, runs of frames
+// that list a leaf merged into segments, every segment refined to k-mer resolution on the leaf's own filter.
+//   launch_frame_count: per sequence its frames (d_cnt) and, for a sequence of one frame, what that frame is shorter than
+//     `frame` (d_deficit); *d_err |= 1 if a sequence has 2^32 bases or more.  The caller scans both (launch_scan_u32).
+//   launch_frame_cut: the frame table (sequence, start, byte offset of every frame) and the frames' bytes gathered into d_out,
+//     a CSR buffer behind frame_off that the classify kernels read like any block of reads.
+//   launch_seg_count: open_cnt[f] = entries of frame f's row that open a segment; the caller scans them into seg_pos.
+//   launch_seq_seg_off: d_seq_seg_off[i] = first segment of sequence i, i <= n_seqs.
+//   launch_seg_fill: the segments' leaf, first_frame, n_frames, begin, end, in CSR order; seg_seq their sequences; the leaf
+//     counters += 1 per (sequence, distinct leaf among its segments).  queue [n_segs], *n_queued zeroed by the caller.
+//   launch_piece_count: d_cnt[p] = pieces of at most `piece` k-mer positions of segment p; the caller scans them.
+//   launch_seg_refine: one wave per piece probes the leaf's filter (row d_col_row[leaf] of d_bits) and leaves a FramePart;
+//     then the pieces of a segment are folded in order into kmers, matched, match_begin, match_end, longest_run.
+struct Segment {  // = pfq_segment (pfq.h)
+    uint32_t leaf, first_frame, n_frames, begin, end, match_begin, match_end, kmers, matched, longest_run;
+};
+struct FramePart {  // a stretch of k-mer positions reduced (see part_join)
+    uint32_t len, matched, first, last, pre, suf, best, pad_;
+};
+struct FrameArgs {
+    const uint64_t *seq_off;                 // [n_seqs + 1] the caller's offsets
+    uint64_t n_seqs, n_frames;
+    uint32_t frame, step;
+    const unsigned long long *seq_frame0;    // [n_seqs + 1] first frame of every sequence
+    const unsigned long long *seq_deficit;   // [n_seqs + 1] scan of d_deficit
+    uint32_t *frame_seq, *frame_start;       // [n_frames]
+    uint64_t *frame_off;                     // [n_frames + 1]
+};
+struct SegArgs {
+    const unsigned long long *row_off;       // [n_frames + 1] the frames' ascending CSR rows
+    const uint32_t *row_leaves;
+    uint64_t n_frames;
+    uint32_t n_leaves;
+    const uint32_t *frame_seq, *frame_start;
+    const uint64_t *frame_off;
+    const unsigned long long *seq_frame0;
+    uint32_t *open_cnt;                      // [n_frames]
+    const unsigned long long *seg_pos;       // [n_frames + 1]
+    Segment *seg;
+    uint32_t *seg_seq;                       // [n_segs]
+    uint32_t *queue;                         // [n_segs] segments still open after the opening lane's walk
+    unsigned long long *n_queued;
+    unsigned long long *counts;              // the tree's leaf counters
+};
+void launch_frame_count(const uint64_t *d_seq_off, uint64_t n_seqs, uint32_t frame, uint32_t step, uint32_t *d_cnt, uint32_t *d_deficit,
+                        unsigned long long *d_err, hipStream_t st);
+void launch_frame_cut(const FrameArgs &fa, const uint8_t *d_seq, uint8_t *d_out, hipStream_t st);
+void launch_seg_count(const SegArgs &sa, hipStream_t st);
+void launch_seq_seg_off(const unsigned long long *d_seq_frame0, const unsigned long long *d_seg_pos, uint64_t n_seqs, unsigned long long *d_seq_seg_off,
+                        hipStream_t st);
+void launch_seg_fill(const SegArgs &sa, const unsigned long long *d_seq_seg_off, uint64_t n_seqs, uint64_t n_segs, hipStream_t st);
+void launch_piece_count(const Segment *d_seg, uint64_t n_segs, uint32_t k, uint32_t piece, uint32_t *d_cnt, hipStream_t st);
+void launch_seg_refine(const HashParams &hp, const uint8_t *d_seq, const uint64_t *d_seq_off, Segment *d_seg, const uint32_t *d_seg_seq,
+                       const unsigned long long *d_piece_off, uint64_t n_segs, uint64_t n_pieces, uint32_t piece, const uint32_t *d_col_row,
+                       const uint64_t *d_bits, uint64_t n_words, FramePart *d_parts, hipStream_t st);
+constexpr uint32_t FRAME_PIECE_DEFAULT = 16384;  // k-mer positions per piece of the refinement (PFQ_FRAME_PIECE)
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -3613,12 +3613,16 @@ __global__ void __launch_bounds__(256) k_hit_sort(const unsigned long long *off,
 void launch_hits_csr(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_allhit, uint64_t n_reads, uint32_t n_leaves, bool any_allhit,
                      uint32_t *d_cnt, unsigned long long *d_sums, unsigned long long *d_off, hipStream_t st) {
     // d_cnt: [n_reads] zeroed by the caller; d_sums: [ceil(n_reads / SCAN_ITEMS) + 1]; d_off: [n_reads + 1]
-    const uint32_t n_blocks = (uint32_t)((n_reads + SCAN_ITEMS - 1) / SCAN_ITEMS);
     if (n_pairs) hipLaunchKernelGGL(k_hit_count, dim3(2048), dim3(256), 0, st, d_pairs, n_pairs, d_cnt);
     if (any_allhit) hipLaunchKernelGGL(k_hit_allhit, dim3(2048), dim3(256), 0, st, d_allhit, n_reads, d_cnt, n_leaves);
-    hipLaunchKernelGGL(k_scan_sums, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n_reads, d_sums);
+    launch_scan_u32(d_cnt, n_reads, d_sums, d_off, st);
+}
+void launch_scan_u32(const uint32_t *d_cnt, uint64_t n, unsigned long long *d_sums, unsigned long long *d_off, hipStream_t st) {
+    if (!n) return;
+    const uint32_t n_blocks = (uint32_t)((n + SCAN_ITEMS - 1) / SCAN_ITEMS);
+    hipLaunchKernelGGL(k_scan_sums, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n, d_sums);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, d_sums, n_blocks);
-    hipLaunchKernelGGL(k_scan_apply, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n_reads, d_sums, d_off);
+    hipLaunchKernelGGL(k_scan_apply, dim3(n_blocks), dim3(1024), 0, st, d_cnt, n, d_sums, d_off);
 }
 void launch_hits_fill(const uint2 *d_pairs, uint64_t n_pairs, const uint8_t *d_allhit, uint64_t n_reads, const unsigned long long *d_off,
                       uint32_t *d_cnt, uint32_t *d_leaves, hipStream_t st) {

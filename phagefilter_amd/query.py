@@ -33,6 +33,11 @@ class ResultMap:
         self.read_map.clear()
 
 
+# one pfq_segment (include/pfq.h)
+SEGMENT_DTYPE = np.dtype([(f, np.uint32) for f in ("leaf", "first_frame", "n_frames", "begin", "end", "match_begin", "match_end", "kmers",
+                                                   "matched", "longest_run")])
+
+
 def pack_reads(reads: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     off = np.zeros(len(reads) + 1, dtype=np.uint64)
     if reads:
@@ -47,6 +52,7 @@ class BloomTree:
     def __init__(self, handle: C.c_void_p, device: int):
         self._h = handle
         self.device = device
+        self.last_n_frames = 0  # frames the last query_frames call classified
 
     # ---- construction
     @classmethod
@@ -243,6 +249,37 @@ class BloomTree:
         if not want_scores:
             return offs, leaves
         return offs, leaves, self.last_hit_scores().copy()
+
+    def _segments(self, out: "_ffi.Segments"):
+        n = int(out.n_seqs)
+        offs = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy() if n else np.zeros(1, dtype=np.uint64)
+        total = int(offs[-1])
+        segs = np.zeros(total, dtype=SEGMENT_DTYPE)
+        if total:
+            C.memmove(segs.ctypes.data, out.seg, total * SEGMENT_DTYPE.itemsize)
+        self.last_n_frames = int(out.n_frames)
+        return offs, segs
+
+    def query_frames(self, seq: np.ndarray, off: np.ndarray, frame: int, step: int, threshold: float):
+        """Long sequences (contigs, long reads) from host memory, classified in overlapping frames of `frame` bases every
+        `step` bases (pfq_query_frames).  Returns (offsets uint64[n + 1], segments): segments[offsets[i]:offsets[i + 1]] are
+        those of sequence i, a structured array (SEGMENT_DTYPE) ordered by first_frame, then leaf; coordinates are 0-based and
+        half-open.  The leaf counters grow by one per (sequence, distinct leaf among its segments); last_n_frames is the
+        number of frames the call classified."""
+        n = len(off) - 1
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        out = _ffi.Segments()
+        _ffi.check(_ffi.lib().pfq_query_frames(self._h, seq.ctypes.data, off.ctypes.data, n, frame, step, threshold, 0, C.byref(out)))
+        return self._segments(out)
+
+    def query_frames_device(self, d_seq: int, d_off: int, n_seqs: int, total_bytes: int, frame: int, step: int, threshold: float,
+                            stream: int = 0):
+        """The same with the sequences already resident in HBM (raw device pointers), on `stream`; synchronous."""
+        out = _ffi.Segments()
+        _ffi.check(_ffi.lib().pfq_query_frames_device(self._h, d_seq, d_off, n_seqs, total_bytes, frame, step, threshold, 0, stream,
+                                                      C.byref(out)))
+        return self._segments(out)
 
     def last_hit_scores(self) -> np.ndarray:
         """Scores of the hits of the last query call, which must have asked for them (view of the library's buffer, valid
