@@ -342,6 +342,41 @@ int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets
 int pfq_query_frames_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bytes,
                             uint32_t frame, uint32_t step, float threshold, uint32_t flags, void *stream, pfq_segments *out);
 
+/* ---- genome similarity ----
+ * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one
+ * geometry and one seed pair; for two filters the set bits and the shared set bits estimate how many k-mers each genome has and
+ * how many they share.  The device computes, exactly, for the listed leaves of `a` and of `b`:
+ *   shared_bits[i * n_b + j] = popcount(filter of leaves_a[i] AND filter of leaves_b[j]),  bits_a[i], bits_b[j] = their set bits
+ * (bit indices below nbits only), and the host derives in double, with m = nbits, h = num_hashes,
+ *   n(x) = -(m / h) * log1p(-x / m) for x < m, and n(m) = 0.0: "not estimable", as genome_kmers of the coverage,
+ * and for a pair A = bits_a[i], B = bits_b[j], I = shared_bits, U = A + B - I (the set bits of the union of the two filters):
+ *   kmers_a = n(A), kmers_b = n(B);
+ *   shared_kmers = max(0, n(A) + n(B) - n(U)), and 0 if any of the three is not estimable;
+ *   jaccard = shared_kmers / n(U), and 0 where n(U) is 0.
+ * Two unrelated filters share about A * B / m bits by chance; the inclusion-exclusion cancels that in expectation.  A leaf against
+ * itself gives shared_bits = bits and jaccard = 1.0 exactly.  What a caller derives from these:
+ *   containment_a = shared_kmers / kmers_a, the share of a's k-mers that b has (0 where kmers_a is 0); containment_b likewise;
+ *   ani = 1 + ln(2 J / (1 + J)) / kmer_size for J = jaccard > 0, else 0: the Mash distance, turned round.
+ * leaves_a / leaves_b are leaf indices in pfq_leaf_counts order — the current leaves, after pfq_tree_prune or pfq_tree_insert; on a
+ * subtree shard they are local to the shard.  A NULL list means all leaves (its n is ignored); a list may be unordered and may
+ * repeat; an explicit empty list (n_a == 0 or n_b == 0) is PFQ_OK with an empty result.  b may be a, or NULL meaning a.
+ * PFQ_ERR_ARG: a or out NULL; the trees differ in kmer_size, nbits, num_hashes, seed1 or seed2 (the message names the field) or
+ * sit on different devices; a leaf index >= n_leaves.  PFQ_ERR_UNSUPPORTED: n_a * n_b > 2^26 (ask in panels).  PFQ_ERR_STATE: an
+ * empty tree.  A sticky insertion error of either tree is returned as by every other call.
+ * The call is synchronous: it waits for both trees' queued work, insertions included, and for its own.  It changes no counter,
+ * log, sketch or query scratch, so pfq_last_stats, pfq_last_hit_scores and pfq_last_lca still describe the last query.  Its
+ * device buffers (8 (n_a + n_b) + 4 n_a n_b bytes and the row lists) live only during the call.  The options PFQ_SIM_SLICES and
+ * PFQ_SIM_NAIVE of `a` choose how the device computes the same numbers (DESIGN.md "Similarity"). */
+typedef struct pfq_similarity {
+    uint64_t n_a, n_b;
+    const uint32_t *shared_bits;            /* [n_a * n_b], row-major */
+    const uint64_t *bits_a, *bits_b;        /* [n_a], [n_b] set bits of each listed leaf's filter */
+    const double *kmers_a, *kmers_b;        /* [n_a], [n_b] */
+    const double *shared_kmers, *jaccard;   /* [n_a * n_b] */
+} pfq_similarity;                           /* library-owned by `a`, valid until the next similarity call on `a` or its close */
+int pfq_tree_similarity(pfq_tree *a, const uint32_t *leaves_a, uint64_t n_a,
+                        pfq_tree *b, const uint32_t *leaves_b, uint64_t n_b, pfq_similarity *out);
+
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);
 /* save_leaf_counts (query.rs:173-183): "<tax_id>,<count>\n" for count > 0, no header. */
@@ -446,6 +481,11 @@ int pfq_profile_end(pfq_tree *tree, pfq_profile *out);
 /* K1 parity hook: the num_hashes bit indices of every canonical k-mer of `seq` (HOST buffers), exactly what
  * BloomFilter::contains probes (bloom_filter.rs:312-332 via hash_iter.rs:13-45): out_idx[(kmer * num_hashes) + i]. */
 int pfq_debug_kmer_indices(pfq_tree *tree, const uint8_t *seq, uint64_t len, uint64_t *out_idx, uint64_t *n_kmers);
+/* The last pfq_tree_similarity call on `a` that had pairs to compute: the slices it cut the filter words into (PFQ_SIM_NAIVE: 1)
+ * and, if the option PFQ_SIM_TIME was 1 during it, the device time of its intersection kernel alone in milliseconds, between two
+ * HIP events round the launch (no copy, no clearing, no host arithmetic); without the option no call makes events and the time
+ * is 0.  Either pointer may be NULL.  Before any such call: 0 and 0. */
+int pfq_debug_last_similarity(pfq_tree *a, double *kernel_ms, uint32_t *slices);
 /* Copy one node's filter words (Lsb0 u64, bloom_filter.rs:86) to the host; node = pre-order index. */
 int pfq_debug_node_filter(pfq_tree *tree, uint64_t node, uint64_t *out_words, uint64_t n_words);
 

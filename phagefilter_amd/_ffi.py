@@ -18,9 +18,10 @@ SYMBOLS = [
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
+    "pfq_tree_similarity",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
-    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity",
+    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity", "pfq_debug_last_similarity",
     "pfq_synth_genomes_device",
     "pfq_synth_reads_device", "pfq_host_alloc", "pfq_host_free", "pfq_last_error", "pfq_version",
 ]
@@ -87,6 +88,13 @@ class Segments(C.Structure):
     _fields_ = [("n_seqs", C.c_uint64), ("n_frames", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("seg", C.POINTER(Segment))]
 
 
+class Similarity(C.Structure):
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("shared_bits", C.POINTER(C.c_uint32)),
+                ("bits_a", C.POINTER(C.c_uint64)), ("bits_b", C.POINTER(C.c_uint64)),
+                ("kmers_a", C.POINTER(C.c_double)), ("kmers_b", C.POINTER(C.c_double)),
+                ("shared_kmers", C.POINTER(C.c_double)), ("jaccard", C.POINTER(C.c_double))]
+
+
 WANT_HITS = 1
 WANT_SCORES = 2
 PAIRED = 4
@@ -150,6 +158,8 @@ def lib() -> C.CDLL:
     L.pfq_query_frames.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(Segments)]
     L.pfq_query_frames_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
                                           C.POINTER(Segments)]
+    L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
+    L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

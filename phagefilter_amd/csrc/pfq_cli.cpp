@@ -2319,13 +2319,118 @@ int cmd_ingest_check(int argc, char **argv) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// compare: which genomes of a database (or of two) are related, from the leaf filters (pfq_tree_similarity); no reference
+// counterpart.  SIMILARITY.tsv in --out, one line per pair of leaves whose larger containment reaches --min-containment.
+// ---------------------------------------------------------------------------------------------------------------
+const char *const SIMILARITY_HEADER =
+    "#genome_a\tgenome_b\tbits_a\tbits_b\tshared_bits\tkmers_a\tkmers_b\tshared_kmers\tjaccard\tcontainment_a\tcontainment_b\tani\n";
+int cmd_compare(int argc, char **argv) {
+    std::vector<Opt> opts = {{"db-path", 'd', true}, {"out", 'o', true}, {"against", 0, true}, {"min-containment", 0, true}, {"device", 0, true}};
+    Args a = parse(argc, argv, 2, opts);
+    // every option is checked before a device is touched
+    const std::string db = req(a, "db-path"), out = req(a, "out");
+    const bool two = a.val.count("against") != 0;
+    const std::string mc = opt(a, "min-containment", "0.1");
+    char *end = nullptr;
+    const double min_c = strtod(mc.c_str(), &end);
+    if (mc.empty() || !end || *end || !(min_c >= 0.0 && min_c <= 1.0))
+        die("error: invalid value '" + mc + "' for '--min-containment': a number from 0 to 1 (0 writes every pair)");
+    const int device = a.val.count("device") ? (int)to_u64(a.val.at("device"), "device") : device_from_env();
+
+    const uint64_t t0 = ReadQueue::now_ns();
+    pfq_tree *ta = nullptr, *tb = nullptr;
+    check(pfq_tree_open(db.c_str(), device, &ta));
+    if (two) check(pfq_tree_open(a.val.at("against").c_str(), device, &tb));
+    pfq_tree *const other = two ? tb : ta;
+    pfq_info info{};
+    check(pfq_tree_info(ta, &info));
+    auto names_of = [](pfq_tree *t) {
+        const char *const *ids = nullptr;
+        const uint64_t *counts = nullptr;
+        uint64_t n = 0;
+        check(pfq_leaf_counts(t, &ids, &counts, &n));
+        return std::vector<std::string>(ids, ids + n);
+    };
+    const std::vector<std::string> names_a = names_of(ta), names_b = two ? names_of(tb) : names_a;
+    const uint64_t na = names_a.size(), nb = names_b.size();
+    {  // one pair first: two databases that cannot be compared are refused, in the library's words, before --out is touched
+        const uint32_t zero = 0;
+        pfq_similarity probe{};
+        check(pfq_tree_similarity(ta, &zero, 1, other, &zero, 1, &probe));
+    }
+    // the directory convention of query's --out (main.rs:380-391): an existing output directory is deleted
+    struct stat st;
+    if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
+    mkdir(out.c_str(), 0777);
+    const std::string tsv = out + "/SIMILARITY.tsv";
+    FILE *f = fopen(tsv.c_str(), "wb");
+    if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+    fputs(SIMILARITY_HEADER, f);
+    // Panels of at most 1024 leaves of a by as many of b as stay under the library's 2^26 pairs a call; one database against
+    // itself: only the panels on or above the diagonal, and of those the pairs a < b.  The file is ordered by a, then b: a panel
+    // that holds all of its rows' columns (every panel, up to 65 536 leaves of b) is written row by row as it comes; only where
+    // the columns are cut into several panels are a row's lines kept until its last panel is in.
+    constexpr uint64_t PANEL_A = 1024, MAX_PAIRS = 1ull << 26;
+    uint64_t compared = 0, written = 0;
+    std::vector<uint32_t> la, lb;
+    std::vector<std::string> rows;
+    char line[256];
+    for (uint64_t a0 = 0; a0 < na; a0 += PANEL_A) {
+        const uint64_t a1 = std::min(na, a0 + PANEL_A), pb = MAX_PAIRS / (a1 - a0);
+        la.resize(a1 - a0);
+        for (uint64_t i = a0; i < a1; ++i) la[i - a0] = (uint32_t)i;
+        const uint64_t b_first = two ? 0 : a0;
+        const bool direct = nb - b_first <= pb;  // one panel of columns
+        rows.assign(direct ? 1 : a1 - a0, std::string());
+        for (uint64_t b0 = b_first; b0 < nb; b0 += pb) {
+            const uint64_t b1 = std::min(nb, b0 + pb);
+            lb.resize(b1 - b0);
+            for (uint64_t j = b0; j < b1; ++j) lb[j - b0] = (uint32_t)j;
+            pfq_similarity sm{};
+            check(pfq_tree_similarity(ta, la.data(), la.size(), other, lb.data(), lb.size(), &sm));
+            for (uint64_t i = a0; i < a1; ++i) {
+                std::string &row = rows[direct ? 0 : i - a0];
+                for (uint64_t j = two ? b0 : std::max(b0, i + 1); j < b1; ++j) {
+                    const uint64_t at = (i - a0) * sm.n_b + (j - b0);
+                    const double ka = sm.kmers_a[i - a0], kb = sm.kmers_b[j - b0], sh = sm.shared_kmers[at], jac = sm.jaccard[at];
+                    const double ca = ka > 0.0 ? sh / ka : 0.0, cb = kb > 0.0 ? sh / kb : 0.0;
+                    ++compared;
+                    if (!(std::max(ca, cb) >= min_c)) continue;
+                    const double ani = jac > 0.0 ? 1.0 + std::log(2.0 * jac / (1.0 + jac)) / (double)info.kmer_size : 0.0;
+                    snprintf(line, sizeof line, "\t%llu\t%llu\t%u\t%.1f\t%.1f\t%.1f\t%.6f\t%.6f\t%.6f\t%.6f\n", (unsigned long long)sm.bits_a[i - a0],
+                             (unsigned long long)sm.bits_b[j - b0], sm.shared_bits[at], ka, kb, sh, jac, ca, cb, ani);
+                    row += names_a[i] + "\t" + names_b[j] + line;
+                    ++written;
+                }
+                if (direct) {
+                    fwrite(row.data(), 1, row.size(), f);
+                    row.clear();
+                }
+            }
+        }
+        if (!direct)
+            for (const std::string &r : rows) fwrite(r.data(), 1, r.size(), f);
+    }
+    if (fclose(f) != 0) die("short write to " + tsv);
+    if (tb) pfq_tree_close(tb);
+    pfq_tree_close(ta);
+    printf("Compared %llu x %llu genomes: %llu pairs compared, %llu written to %s, %.3f s\n", (unsigned long long)na, (unsigned long long)nb,
+           (unsigned long long)compared, (unsigned long long)written, tsv.c_str(), (ReadQueue::now_ns() - t0) * 1e-9);
+    return 0;
+}
+
 void usage() {
+    std::string header_cols(SIMILARITY_HEADER);  // the column line as the file has it, tabs spelt out
+    header_cols.pop_back();
+    for (size_t p = 0; (p = header_cols.find('\t', p)) != std::string::npos;) header_cols.replace(p, 1, "<TAB>");
     fprintf(stderr,
             "A fast, simple and memory efficient metagenomic filtering tool. (MI355X query path)\n\n"
             "Usage: phage_filter [-v...|-q...] <COMMAND>\n\nCommands:\n"
             "  query           Queries a set of reads. (ran after building the bloom tree)\n"
             "  build           Builds the BloomTree.\n"
             "  add             Adds genomes to an already built BloomFilter.\n"
+            "  compare         Says which genomes of a database are related, and how closely, from their Bloom filters\n"
             "  build-balanced  Builds a balanced synthetic BloomTree on the GPU (benchmark databases)\n"
             "  ingest-check    Parses reads like `query` and prints what was read (no GPU)\n\n"
             "query takes the reference's options, plus --devices <0,1,..|all>: one replica of the database per GPU, reads\n"
@@ -2382,7 +2487,18 @@ void usage() {
             "CLASSIFICATION.csv then counts sequences, one per genome with a segment.  Works with --devices (whole sequences are dealt to\n"
             "the replicas; the files do not depend on the device list, -t or the batch size).  Not with --reads2, --interleaved,\n"
             "--scores, --lca, --abundance, --coverage, --shard-depth, --pos-filter or --neg-filter; F must be at least the database's k\n"
-            "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n");
+            "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"
+            "compare -d <DB> -o <OUT> [--against <DB2>] [--min-containment <C>] [--device <N>]: a phage database is full of strains and\n"
+            "near-duplicates; this says which of its genomes are related.  For two genomes' filters the set bits and the shared set bits\n"
+            "(counted on the GPU, all pairs at once) estimate how many k-mers each genome has and how many they share.  SIMILARITY.tsv in\n"
+            "--out (an existing directory is replaced, as by query):\n\"%s\"\n"
+            "(<TAB> between the columns), one line per pair: without --against the pairs a < b of the database in CLASSIFICATION.csv's order,\n"
+            "with --against every (genome of DB, genome of DB2); the two databases must share k, filter size, hashes and seeds (build\n"
+            "--seed1 / --seed2).  bits: set bits of the filters; kmers: each genome's distinct k-mers estimated from its filter's fill;\n"
+            "shared_kmers: those both have; jaccard = shared / union; containment_a = shared_kmers / kmers_a, the share of a's k-mers that b\n"
+            "has; ani = 1 + ln(2 J / (1 + J)) / k, the Mash distance turned round (0 where jaccard is 0).  Only pairs whose larger containment\n"
+            "is at least C are written (default 0.1; --min-containment 0 writes all), ordered by a, then b\n",
+            header_cols.c_str());
 }
 
 }  // namespace
@@ -2405,6 +2521,7 @@ int main(int argc, char **argv) {
     if (cmd == "ingest-check") return cmd_ingest_check((int)av.size(), av.data());
     if (cmd == "build") return cmd_build((int)av.size(), av.data());
     if (cmd == "add") return cmd_add((int)av.size(), av.data());
+    if (cmd == "compare") return cmd_compare((int)av.size(), av.data());
     usage();
     return 2;
 }

@@ -106,6 +106,7 @@ struct Knobs {
     long long abund_slots = -1, abund_blocks = -1, abund_lds = -1;  // PFQ_WANT_ABUNDANCE: cap on the log's leaf entries; grid and LDS use of the EM step
     long long cover_p = -1, cover_blocks = -1;  // PFQ_WANT_COVERAGE: registers per leaf = 2^cover_p (4..16, unset: 12); grid of the sketch kernel
     long long frame_piece = -1;                 // pfq_query_frames: k-mer positions per piece of the refinement (a positive multiple of 64)
+    long long sim_slices = -1, sim_naive = -1, sim_time = -1;  // pfq_tree_similarity: slices of the filter words (0 / unset: built-in); 1: the one-block-per-pair kernel; 1: time the kernel
 };
 struct KnobName {
     const char *name;
@@ -135,6 +136,8 @@ const KnobName KNOBS[] = {
     {"PFQ_ABUND_LDS", &Knobs::abund_lds},
     {"PFQ_COVER_P", &Knobs::cover_p},           {"PFQ_COVER_BLOCKS", &Knobs::cover_blocks},
     {"PFQ_FRAME_PIECE", &Knobs::frame_piece},
+    {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
+    {"PFQ_SIM_TIME", &Knobs::sim_time},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -383,6 +386,12 @@ struct pfq_tree {
     DevBuf<pfq::FramePart> d_fr_parts;
     HostBuf<uint64_t> h_fr_off;
     HostBuf<pfq_segment> h_fr_segs;
+    // pfq_tree_similarity: the last call's result (its device buffers live only during the call)
+    std::vector<uint32_t> out_sim_shared;
+    std::vector<uint64_t> out_sim_bits_a, out_sim_bits_b;
+    std::vector<double> out_sim_kmers_a, out_sim_kmers_b, out_sim_shared_kmers, out_sim_jaccard;
+    float sim_kernel_ms = 0.0f;            // pfq_debug_last_similarity: device time of the last call's intersection kernel, its slices
+    uint32_t sim_slices = 0;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3295,6 +3304,150 @@ int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src) {
     PFQ_TRY(use_device(s.device));
     cover_clear(s);
     PFQ_TRY(use_device(d.device));
+    return PFQ_OK;
+}
+
+// ---- pfq_tree_similarity ----
+namespace {
+// Distinct k-mers behind x set bits of a filter of m bits and h hashes (Swamidass-Baldi, as pfq_coverage.genome_kmers); a full
+// filter is not estimable: 0.0.
+double sim_kmers(uint64_t x, uint64_t m, uint32_t h) {
+    return x >= m ? 0.0 : -((double)m / (double)h) * std::log1p(-(double)x / (double)m);
+}
+// The leaves a list names, as filter rows of the tree (NULL: every leaf, in order).
+int sim_rows(const pfq_tree &t, const char *which, const uint32_t *leaves, uint64_t n, std::vector<uint32_t> &rows) {
+    const size_t nl = t.leaves.size();
+    rows.clear();
+    if (!leaves) {
+        rows.assign(t.col_row.begin(), t.col_row.begin() + nl);  // (the first nl columns are the leaves)
+        return PFQ_OK;
+    }
+    rows.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (leaves[i] >= nl)
+            return fail(PFQ_ERR_ARG, std::string("pfq_tree_similarity: ") + which + "[" + std::to_string(i) + "] = " + std::to_string(leaves[i]) +
+                                         " is not a leaf index (the tree has " + std::to_string(nl) + " leaves)");
+        rows.push_back(t.col_row[leaves[i]]);
+    }
+    return PFQ_OK;
+}
+}  // namespace
+
+int pfq_tree_similarity(pfq_tree *a, const uint32_t *leaves_a, uint64_t n_a, pfq_tree *b, const uint32_t *leaves_b, uint64_t n_b, pfq_similarity *out) {
+    if (!a) return fail(PFQ_ERR_ARG, "pfq_tree_similarity: tree a is NULL");
+    if (!out) return fail(PFQ_ERR_ARG, "pfq_tree_similarity: out is NULL");
+    if (!b) b = a;
+    pfq_tree &ta = *a, &tb = *b;
+    // the queued work of both trees, pending insertions included (a sticky insertion error is returned here)
+    PFQ_TRY(use_device(tb.device));
+    PFQ_TRY(build_layout(tb));
+    HIP_TRY(hipDeviceSynchronize());
+    if (b != a) {
+        PFQ_TRY(use_device(ta.device));
+        PFQ_TRY(build_layout(ta));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    if (ta.leaves.empty() || tb.leaves.empty()) return fail(PFQ_ERR_STATE, "pfq_tree_similarity on an empty tree");
+    auto differ = [&](const char *field, uint64_t va, uint64_t vb) {
+        return fail(PFQ_ERR_ARG, std::string("pfq_tree_similarity: the trees differ in ") + field + " (" + std::to_string(va) + " and " + std::to_string(vb) +
+                                     "): their filters cannot be compared bit by bit");
+    };
+    if (ta.kmer_size != tb.kmer_size) return differ("kmer_size", ta.kmer_size, tb.kmer_size);
+    if (ta.nbits != tb.nbits) return differ("nbits", ta.nbits, tb.nbits);
+    if (ta.num_hashes != tb.num_hashes) return differ("num_hashes", ta.num_hashes, tb.num_hashes);
+    if (ta.seed1 != tb.seed1) return differ("seed1", ta.seed1, tb.seed1);
+    if (ta.seed2 != tb.seed2) return differ("seed2", ta.seed2, tb.seed2);
+    if (ta.device != tb.device)
+        return fail(PFQ_ERR_ARG, "pfq_tree_similarity: the trees sit on different devices (" + std::to_string(ta.device) + " and " + std::to_string(tb.device) + ")");
+    if (!leaves_a) n_a = ta.leaves.size();
+    if (!leaves_b) n_b = tb.leaves.size();
+    constexpr uint64_t MAX_PAIRS = 1ull << 26;
+    if (n_a && n_b > MAX_PAIRS / n_a)
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_tree_similarity: " + std::to_string(n_a) + " x " + std::to_string(n_b) +
+                                             " pairs are more than 2^26 in one call: ask in panels (sublists of the leaves)");
+    std::vector<uint32_t> rows_a, rows_b;
+    PFQ_TRY(sim_rows(ta, "leaves_a", leaves_a, n_a, rows_a));
+    PFQ_TRY(sim_rows(tb, "leaves_b", leaves_b, n_b, rows_b));
+    const size_t np = (size_t)(n_a * n_b);
+    ta.out_sim_shared.assign(np + 1, 0);
+    ta.out_sim_bits_a.assign(n_a + 1, 0);
+    ta.out_sim_bits_b.assign(n_b + 1, 0);
+    if (np) {
+        // scratch of this call only (freed on return: it never shows in pfq_info.device_bytes)
+        DevBuf<uint32_t> d_rows, d_out;
+        DevBuf<unsigned long long> d_pop;
+        if (d_rows.ensure(n_a + n_b) != hipSuccess || d_out.ensure(np) != hipSuccess || d_pop.ensure(n_a + n_b) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PFQ_ERR_DEVICE, "pfq_tree_similarity: no device memory for " + std::to_string(np) + " pairs");
+        }
+        HIP_TRY(hipMemcpy(d_rows.p, rows_a.data(), n_a * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rows.p + n_a, rows_b.data(), n_b * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_out.p, 0, np * 4, nullptr));  // (the slices of the tiled kernel add into it)
+        const uint32_t slices = ta.knobs.sim_slices > 0 ? (uint32_t)std::min<long long>(ta.knobs.sim_slices, 65535) : 0;
+        // PFQ_SIM_TIME=1 (tools/sim_bench.py): two HIP events round the intersection kernel alone; otherwise no call pays for them
+        const bool timed = ta.knobs.sim_time == 1;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        if (timed) {
+            HIP_TRY(hipEventCreate(&ev[0]));
+            if (hipEventCreate(&ev[1]) != hipSuccess) {
+                (void)hipGetLastError();
+                (void)hipEventDestroy(ev[0]);
+                return fail(PFQ_ERR_DEVICE, "pfq_tree_similarity: hipEventCreate failed");
+            }
+            (void)hipEventRecord(ev[0], nullptr);
+        }
+        ta.sim_slices = pfq::launch_filter_intersections(ta.d_bits.p, d_rows.p, (uint32_t)n_a, tb.d_bits.p, d_rows.p + n_a, (uint32_t)n_b, ta.n_words,
+                                                         ta.nbits, slices, ta.knobs.sim_naive == 1, d_out.p, nullptr);
+        ta.sim_kernel_ms = 0.0f;
+        if (timed) {
+            (void)hipEventRecord(ev[1], nullptr);
+            if (hipEventSynchronize(ev[1]) == hipSuccess) (void)hipEventElapsedTime(&ta.sim_kernel_ms, ev[0], ev[1]);
+            (void)hipEventDestroy(ev[0]);
+            (void)hipEventDestroy(ev[1]);
+        }
+        pfq::launch_filter_row_bits(ta.d_bits.p, d_rows.p, (uint32_t)n_a, ta.n_words, ta.nbits, d_pop.p, nullptr);
+        pfq::launch_filter_row_bits(tb.d_bits.p, d_rows.p + n_a, (uint32_t)n_b, tb.n_words, tb.nbits, d_pop.p + n_a, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(ta.out_sim_shared.data(), d_out.p, np * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ta.out_sim_bits_a.data(), d_pop.p, n_a * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ta.out_sim_bits_b.data(), d_pop.p + n_a, n_b * 8, hipMemcpyDeviceToHost));
+    }
+    // the derived values (pfq.h "genome similarity"): this is the one place that computes them
+    const uint64_t m = ta.nbits;
+    const uint32_t h = ta.num_hashes;
+    ta.out_sim_kmers_a.assign(n_a + 1, 0.0);
+    ta.out_sim_kmers_b.assign(n_b + 1, 0.0);
+    ta.out_sim_shared_kmers.assign(np + 1, 0.0);
+    ta.out_sim_jaccard.assign(np + 1, 0.0);
+    if (np) {
+        for (uint64_t i = 0; i < n_a; ++i) ta.out_sim_kmers_a[i] = sim_kmers(ta.out_sim_bits_a[i], m, h);
+        for (uint64_t j = 0; j < n_b; ++j) ta.out_sim_kmers_b[j] = sim_kmers(ta.out_sim_bits_b[j], m, h);
+        for (uint64_t i = 0; i < n_a; ++i)
+            for (uint64_t j = 0; j < n_b; ++j) {
+                const uint64_t A = ta.out_sim_bits_a[i], B = ta.out_sim_bits_b[j], U = A + B - ta.out_sim_shared[i * n_b + j];
+                if (A >= m || B >= m || U >= m) continue;  // not estimable: 0
+                const double nu = sim_kmers(U, m, h), sh = std::max(0.0, ta.out_sim_kmers_a[i] + ta.out_sim_kmers_b[j] - nu);
+                ta.out_sim_shared_kmers[i * n_b + j] = sh;
+                ta.out_sim_jaccard[i * n_b + j] = nu > 0.0 ? sh / nu : 0.0;
+            }
+    }
+    memset(out, 0, sizeof *out);
+    out->n_a = n_a;
+    out->n_b = n_b;
+    out->shared_bits = ta.out_sim_shared.data();
+    out->bits_a = ta.out_sim_bits_a.data();
+    out->bits_b = ta.out_sim_bits_b.data();
+    out->kmers_a = ta.out_sim_kmers_a.data();
+    out->kmers_b = ta.out_sim_kmers_b.data();
+    out->shared_kmers = ta.out_sim_shared_kmers.data();
+    out->jaccard = ta.out_sim_jaccard.data();
+    return PFQ_OK;
+}
+
+int pfq_debug_last_similarity(pfq_tree *a, double *kernel_ms, uint32_t *slices) {
+    if (!a) return fail(PFQ_ERR_ARG, "null argument");
+    if (kernel_ms) *kernel_ms = (double)a->sim_kernel_ms;
+    if (slices) *slices = a->sim_slices;
     return PFQ_OK;
 }
 

@@ -507,6 +507,16 @@ void launch_seg_refine(const HashParams &hp, const uint8_t *d_seq, const uint64_
                        const unsigned long long *d_piece_off, uint64_t n_segs, uint64_t n_pieces, uint32_t piece, const uint32_t *d_col_row,
                        const uint64_t *d_bits, uint64_t n_words, FramePart *d_parts, hipStream_t st);
 constexpr uint32_t FRAME_PIECE_DEFAULT = 16384;  // k-mer positions per piece of the refinement (PFQ_FRAME_PIECE)
+// pfq_tree_similarity (pfq_sim.hip): d_out[i * n_b + j] += the bits below nbits that filter row d_rows_a[i] of bits_a and filter
+// row d_rows_b[j] of bits_b (both of n_words words) have in common.  d_out [n_a * n_b] must be zero: the tiled kernel cuts the
+// words into `slices` ranges (0: the built-in choice; clamped to 1 .. chunks of 16 words) whose blocks add their partial counts
+// with u32 atomics — the sums are exact whatever the slices and the order.  naive: one block per pair, no tiling, no atomics
+// (the A/B baseline).  The rows may repeat and need no order; bits_a and bits_b may be one array.  Returns the slices launched
+// (naive: 1; nothing to do: 0).  launch_filter_row_bits: d_out[i] = the bits below nbits of filter row d_rows[i].
+uint32_t launch_filter_intersections(const uint64_t *bits_a, const uint32_t *d_rows_a, uint32_t n_a, const uint64_t *bits_b, const uint32_t *d_rows_b,
+                                     uint32_t n_b, uint64_t n_words, uint64_t nbits, uint32_t slices, bool naive, uint32_t *d_out, hipStream_t st);
+void launch_filter_row_bits(const uint64_t *bits, const uint32_t *d_rows, uint32_t n_rows, uint64_t n_words, uint64_t nbits, unsigned long long *d_out,
+                            hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -412,6 +412,47 @@ class BloomTree:
         this tree's (registers: element-wise max, counters: sums) and empties it."""
         _ffi.check(_ffi.lib().pfq_coverage_absorb(self._h, other._h))
 
+    # ---- genome similarity
+    def similarity(self, other: Optional["BloomTree"] = None, leaves_a: Optional[Sequence[int]] = None,
+                   leaves_b: Optional[Sequence[int]] = None) -> dict:
+        """How related are the genomes of this database, or of this one and `other` (pfq_tree_similarity)?  leaves_a / leaves_b
+        are leaf indices in the order of get_leaf_counts (None: all leaves; any order, repeats allowed; an empty list gives an
+        empty result), into this tree and into `other` (None: this tree).  Returns numpy copies: `shared_bits` uint32
+        (n_a, n_b), the set bits the two leaves' filters have in common; `bits_a`, `bits_b` uint64, each filter's set bits;
+        `kmers_a`, `kmers_b`, and per pair `shared_kmers`, `jaccard` float64, the estimates derived from them.  The trees must
+        share k, filter size, hashes and seeds.  Changes nothing a query left behind."""
+        def as_list(v):
+            if v is None:
+                return None, 0, None
+            a = np.ascontiguousarray(v, dtype=np.uint32).reshape(-1)
+            n = len(a)
+            if not n:
+                a = np.zeros(1, dtype=np.uint32)  # (an empty list is still a list: the pointer must not be NULL)
+            return a, n, a.ctypes.data
+        la, na, pa = as_list(leaves_a)
+        lb, nb, pb = as_list(leaves_b)
+        s = _ffi.Similarity()
+        _ffi.check(_ffi.lib().pfq_tree_similarity(self._h, pa, na, other._h if other is not None else None, pb, nb, C.byref(s)))
+        n_a, n_b = int(s.n_a), int(s.n_b)
+
+        def arr(ptr, shape, dtype):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy() if n_a and n_b else np.zeros(shape, dtype=dtype)
+        out = {"shared_bits": arr(s.shared_bits, (n_a, n_b), np.uint32)}
+        for k, n in (("bits_a", n_a), ("bits_b", n_b)):
+            out[k] = arr(getattr(s, k), (n,), np.uint64)
+        for k, n in (("kmers_a", n_a), ("kmers_b", n_b)):
+            out[k] = arr(getattr(s, k), (n,), np.float64)
+        for k in ("shared_kmers", "jaccard"):
+            out[k] = arr(getattr(s, k), (n_a, n_b), np.float64)
+        return out
+
+    def last_similarity(self) -> Tuple[float, int]:
+        """(device milliseconds of the intersection kernel, slices of the filter words) of the last similarity() call that had
+        pairs to compute (pfq_debug_last_similarity); the time is measured only under set_option("PFQ_SIM_TIME", "1"), else 0."""
+        ms, sl = C.c_double(), C.c_uint32()
+        _ffi.check(_ffi.lib().pfq_debug_last_similarity(self._h, C.byref(ms), C.byref(sl)))
+        return float(ms.value), int(sl.value)
+
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
 
