@@ -377,6 +377,46 @@ typedef struct pfq_similarity {
 int pfq_tree_similarity(pfq_tree *a, const uint32_t *leaves_a, uint64_t n_a,
                         pfq_tree *b, const uint32_t *leaves_b, uint64_t n_b, pfq_similarity *out);
 
+/* ---- re-clustering ----
+ * pfq_tree_build_balanced and pfq_tree_insert decide a tree's shape by the order the genomes arrive in.  pfq_tree_recluster
+ * makes a new tree over the same leaves whose shape follows from the leaf filters alone: average-linkage agglomerative
+ * clustering of the chance-corrected similarities, on the device, in integers.  The result is a pure function of the filters.
+ * Nodes: the L current leaves of `src`, in pfq_leaf_counts order, are nodes 0 .. L - 1; internal nodes are L, L + 1, .. in the
+ *   order they are made.
+ * Leaf pair: with m = nbits, A and B the set bits of the two filters, I their shared set bits (all three as pfq_tree_similarity
+ *   reports them: bit indices below nbits only) and U = A + B - I,
+ *     num = max(0, I m - A B),  den = U m - A B,  q = floor(num 2^20 / den), and q = 0 where den = 0:  0 <= q <= 2^20.
+ *   A B / m is what two unrelated filters share by chance.
+ * Clusters: S(X, Y) = the sum of q over the leaf pairs (x in X, y in Y), w(X, Y) = |X| |Y|; the score of the pair is S / w, and
+ *   after X and Y are merged into Z, S(Z, W) = S(X, W) + S(Y, W).
+ * Order: (X, Y1) is before (X, Y2) when S1 w2 > S2 w1, compared as 128-bit products; on equality the smaller node index.
+ * Rounds: every live node i finds best(i), the first of all other live nodes in that order; every pair with best(i) = j,
+ *   best(j) = i, i < j is merged; the pairs are taken in ascending i and get consecutive new indices, left child i, right
+ *   child j.  (Of the pairs with the highest score the one with the smallest (i, j) is always such a pair.)  Rounds repeat
+ *   until one node is left, the root.  L = 1: that leaf is the root.
+ * The new tree: 2 L - 1 nodes on src's device, with src's parameters and seeds.  A leaf keeps its tax_id, its .bf name and its
+ * filter words, padding bits included; an internal node's filter is the OR of its children's and its name "Internal_Node_<n>"
+ * with a running n that skips names in use, as pfq_tree_insert names with a NULL name; superset_verified is 1; every counter,
+ * log and sketch starts at zero.
+ * The call is synchronous: it waits for src's queued work, insertions included (a sticky insertion error is returned as by
+ * every other call), and changes nothing of src: counters, logs, sketches, query scratch and pfq_last_stats stay.  Its scratch
+ * (8 L^2 bytes of scores and a panel of shared bits) is freed before it returns.  src's options PFQ_SIM_SLICES and
+ * PFQ_SIM_NAIVE choose how the shared bits are computed, as for pfq_tree_similarity.
+ * PFQ_ERR_ARG: src or out NULL.  PFQ_ERR_STATE: an empty tree.  PFQ_ERR_UNSUPPORTED: a subtree shard; two leaves that share one
+ * .bf name (the new tree would save two files under it); more than 16384 leaves, or a score matrix that does not fit in device
+ * memory beside the two trees (the message says which). */
+int pfq_tree_recluster(pfq_tree *src, pfq_tree **out);
+/* The merge log of a tree made by pfq_tree_recluster, one entry per internal node in creation order: node = L + its position,
+ * left and right its children (indices as above), round the round that made it (from 0), n_leaves the leaves below it,
+ * score_sum = S(left, right) and pairs = w(left, right): the similarity the merge happened at is score_sum / (pairs 2^20).
+ * *rounds: the rounds run.  Library-owned by the tree until it is closed or its topology changes (pfq_tree_insert,
+ * pfq_tree_prune).  Any other tree: *n = 0, *rounds = 0. */
+typedef struct pfq_merge {
+    uint32_t node, left, right, round, n_leaves, pad_;
+    uint64_t score_sum, pairs;
+} pfq_merge;
+int pfq_tree_merges(pfq_tree *tree, const pfq_merge **merges, uint64_t *n, uint32_t *rounds);
+
 /* get_leaf_counts (query.rs:197-218): leaves left-to-right, zeros included.  Library-owned arrays. */
 int pfq_leaf_counts(pfq_tree *tree, const char *const **tax_ids, const uint64_t **counts, uint64_t *n_leaves);
 /* save_leaf_counts (query.rs:173-183): "<tax_id>,<count>\n" for count > 0, no header. */
@@ -486,6 +526,11 @@ int pfq_debug_kmer_indices(pfq_tree *tree, const uint8_t *seq, uint64_t len, uin
  * HIP events round the launch (no copy, no clearing, no host arithmetic); without the option no call makes events and the time
  * is 0.  Either pointer may be NULL.  Before any such call: 0 and 0. */
 int pfq_debug_last_similarity(pfq_tree *a, double *kernel_ms, uint32_t *slices);
+/* The last pfq_tree_recluster call on `src` that ran rounds: ms[0] the shared bits and scores of all leaf pairs, ms[1] all rounds
+ * (kernels, read-backs and the unions of the new filters), ms[2] the nearest-neighbour kernel alone over all rounds, in device
+ * milliseconds between HIP events — measured only if src's option PFQ_CLUSTER_TIME was 1 during the call, else 0;
+ * *nn_bytes: the score-matrix bytes the nearest-neighbour kernel read over all rounds; *rounds.  Any pointer may be NULL. */
+int pfq_debug_last_recluster(pfq_tree *src, double *ms, uint64_t *nn_bytes, uint32_t *rounds);
 /* Copy one node's filter words (Lsb0 u64, bloom_filter.rs:86) to the host; node = pre-order index. */
 int pfq_debug_node_filter(pfq_tree *tree, uint64_t node, uint64_t *out_words, uint64_t n_words);
 

@@ -18,10 +18,10 @@ SYMBOLS = [
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
-    "pfq_tree_similarity",
+    "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
-    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity", "pfq_debug_last_similarity",
+    "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity", "pfq_debug_last_similarity", "pfq_debug_last_recluster",
     "pfq_synth_genomes_device",
     "pfq_synth_reads_device", "pfq_host_alloc", "pfq_host_free", "pfq_last_error", "pfq_version",
 ]
@@ -95,6 +95,11 @@ class Similarity(C.Structure):
                 ("shared_kmers", C.POINTER(C.c_double)), ("jaccard", C.POINTER(C.c_double))]
 
 
+class Merge(C.Structure):
+    _fields_ = [("node", C.c_uint32), ("left", C.c_uint32), ("right", C.c_uint32), ("round", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("pad_", C.c_uint32), ("score_sum", C.c_uint64), ("pairs", C.c_uint64)]
+
+
 WANT_HITS = 1
 WANT_SCORES = 2
 PAIRED = 4
@@ -160,6 +165,9 @@ def lib() -> C.CDLL:
                                           C.POINTER(Segments)]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
     L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.pfq_tree_recluster.argtypes = [vp, C.POINTER(vp)]
+    L.pfq_tree_merges.argtypes = [vp, C.POINTER(C.POINTER(Merge)), u64p, C.POINTER(C.c_uint32)]
+    L.pfq_debug_last_recluster.argtypes = [vp, C.POINTER(C.c_double), u64p, C.POINTER(C.c_uint32)]
     L.pfq_leaf_counts.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(u64p), u64p]
     L.pfq_save_leaf_counts.argtypes = [vp, C.c_char_p]
     L.pfq_leaf_counts_export.argtypes = [vp, vp, vp]

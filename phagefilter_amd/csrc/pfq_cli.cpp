@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <climits>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -2216,10 +2217,99 @@ int insert_genomes(pfq_tree *tree, const std::string &genomes, FmtOverride ov, u
     }
     return (int)n;
 }
+// ---------------------------------------------------------------------------------------------------------------
+// recluster: the same leaves under a tree whose shape follows from the leaf filters (pfq_tree_recluster); no reference
+// counterpart.  `build --cluster` is build followed by it, without the database in between.
+// ---------------------------------------------------------------------------------------------------------------
+const char *const MERGES_HEADER = "#node\tleft\tright\tleaves\tround\tscore_sum\tpairs\tsimilarity\n";
+// The merge log of `made` = pfq_tree_recluster(src) as a dendrogram: one line per internal node in creation order.
+void write_merges(pfq_tree *src, pfq_tree *made, const std::string &path) {
+    const char *const *ids = nullptr;
+    const uint64_t *counts = nullptr;
+    uint64_t n_leaves = 0, n_merges = 0, n_clades = 0;
+    check(pfq_leaf_counts(src, &ids, &counts, &n_leaves));
+    std::vector<std::string> name(ids, ids + n_leaves);  // node -> name: src's leaves in order, then the new tree's internal nodes
+    const pfq_merge *mg = nullptr;
+    uint32_t rounds = 0;
+    check(pfq_tree_merges(made, &mg, &n_merges, &rounds));
+    // an internal node is the clade of the new tree with its leaf range: the new tree lists the leaves left subtree first
+    const pfq_clade *clades = nullptr;
+    check(pfq_tree_clades(made, &clades, &n_clades));
+    std::map<std::pair<uint32_t, uint32_t>, std::string> by_range;
+    for (uint64_t c = 0; c < n_clades; ++c)
+        if (clades[c].n_leaves > 1) by_range[{clades[c].first_leaf, clades[c].n_leaves}] = clades[c].name;
+    std::vector<uint32_t> first(n_leaves + n_merges, 0);
+    if (n_merges) {
+        uint32_t next_leaf = 0;
+        std::vector<uint32_t> st{(uint32_t)(n_leaves + n_merges - 1)};
+        while (!st.empty()) {  // pre-order: a node's first leaf is the next one to be numbered when the node is reached
+            const uint32_t v = st.back();
+            st.pop_back();
+            first[v] = next_leaf;
+            if (v < n_leaves) ++next_leaf;
+            else {
+                st.push_back(mg[v - n_leaves].right);
+                st.push_back(mg[v - n_leaves].left);
+            }
+        }
+    }
+    name.resize(n_leaves + n_merges);
+    for (uint64_t i = 0; i < n_merges; ++i) {
+        auto it = by_range.find({first[mg[i].node], mg[i].n_leaves});
+        if (it == by_range.end()) die("recluster: merge " + std::to_string(i) + " matches no node of the new tree");
+        name[mg[i].node] = it->second;
+    }
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) die("cannot create " + path + ": " + strerror(errno));
+    fputs(MERGES_HEADER, f);
+    for (uint64_t i = 0; i < n_merges; ++i) {
+        const pfq_merge &m = mg[i];
+        fprintf(f, "%s\t%s\t%s\t%u\t%u\t%llu\t%llu\t%.6f\n", name[m.node].c_str(), name[m.left].c_str(), name[m.right].c_str(), m.n_leaves, m.round,
+                (unsigned long long)m.score_sum, (unsigned long long)m.pairs, (double)m.score_sum / ((double)m.pairs * 1048576.0));
+    }
+    if (fclose(f) != 0) die("short write to " + path);
+}
+// a path as far as it can be resolved, without trailing slashes: two spellings of one directory compare equal
+std::string resolved(const std::string &p) {
+    char buf[PATH_MAX];
+    if (realpath(p.c_str(), buf)) return buf;
+    std::string s = p;
+    while (s.size() > 1 && s.back() == '/') s.pop_back();
+    return s;
+}
+int cmd_recluster(int argc, char **argv) {
+    std::vector<Opt> opts = {{"db-path", 'd', true}, {"out", 'o', true}, {"merges", 0, true}, {"device", 0, true}};
+    Args a = parse(argc, argv, 2, opts);
+    // every option is checked before a device is touched
+    const std::string db = req(a, "db-path"), out = req(a, "out");
+    if (out.empty()) die("error: invalid value '' for '--out': the directory of the new database");
+    if (resolved(db) == resolved(out))
+        die("error: invalid value '" + out + "' for '--out': the same directory as '--db-path' (the new database is written beside the old one, not over it)");
+    const bool want_merges = a.val.count("merges") != 0;
+    if (want_merges && a.val.at("merges").empty()) die("error: invalid value '' for '--merges': a file name");
+    const int device = a.val.count("device") ? (int)to_u64(a.val.at("device"), "device") : device_from_env();
+
+    const uint64_t t0 = ReadQueue::now_ns();
+    pfq_tree *src = nullptr, *made = nullptr;
+    check(pfq_tree_open(db.c_str(), device, &src));
+    check(pfq_tree_recluster(src, &made));
+    mkdir(out.c_str(), 0777);
+    check(pfq_tree_save(made, out.c_str()));
+    if (want_merges) write_merges(src, made, a.val.at("merges"));
+    const pfq_merge *mg = nullptr;
+    uint64_t n_merges = 0;
+    uint32_t rounds = 0;
+    check(pfq_tree_merges(made, &mg, &n_merges, &rounds));
+    pfq_tree_close(made);
+    pfq_tree_close(src);
+    printf("Reclustered %llu genomes in %u rounds into %s, %.3f s\n", (unsigned long long)(n_merges + 1), rounds, out.c_str(), (ReadQueue::now_ns() - t0) * 1e-9);
+    return 0;
+}
+
 int cmd_build(int argc, char **argv) {
     std::vector<Opt> opts = {{"genomes", 'g', true}, {"db-path", 'd', true}, {"threads", 't', true}, {"kmer-size", 'k', true},
                              {"cache-size", 'c', true}, {"false-pos-rate", 'f', true}, {"largest-genome", 'l', true},
-                             {"format", 'F', true}, {"seed1", 0, true}, {"seed2", 0, true}};
+                             {"format", 'F', true}, {"seed1", 0, true}, {"seed2", 0, true}, {"cluster", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string genomes = req(a, "genomes"), db = req(a, "db-path");
     const uint64_t k = to_u64(opt(a, "kmer-size", "20"), "kmer-size");
@@ -2235,6 +2325,12 @@ int cmd_build(int argc, char **argv) {
     pfq_tree *tree = nullptr;
     check(pfq_tree_create(k, fpr, largest, s1, s2, 0, device_from_env(), &tree));
     insert_genomes(tree, genomes, to_fmt(opt(a, "format", "auto")), threads);
+    if (a.flags.count("cluster")) {  // --cluster: what `recluster` would make of the database this build would have saved
+        pfq_tree *made = nullptr;
+        check(pfq_tree_recluster(tree, &made));
+        pfq_tree_close(tree);
+        tree = made;
+    }
     check(pfq_tree_save(tree, db.c_str()));
     pfq_tree_close(tree);
     printf("Finished.\n");
@@ -2424,6 +2520,9 @@ void usage() {
     std::string header_cols(SIMILARITY_HEADER);  // the column line as the file has it, tabs spelt out
     header_cols.pop_back();
     for (size_t p = 0; (p = header_cols.find('\t', p)) != std::string::npos;) header_cols.replace(p, 1, "<TAB>");
+    std::string merges_cols(MERGES_HEADER);
+    merges_cols.pop_back();
+    for (size_t p = 0; (p = merges_cols.find('\t', p)) != std::string::npos;) merges_cols.replace(p, 1, "<TAB>");
     fprintf(stderr,
             "A fast, simple and memory efficient metagenomic filtering tool. (MI355X query path)\n\n"
             "Usage: phage_filter [-v...|-q...] <COMMAND>\n\nCommands:\n"
@@ -2431,6 +2530,7 @@ void usage() {
             "  build           Builds the BloomTree.\n"
             "  add             Adds genomes to an already built BloomFilter.\n"
             "  compare         Says which genomes of a database are related, and how closely, from their Bloom filters\n"
+            "  recluster       Writes a database with the same genomes under a tree rebuilt by their similarity\n"
             "  build-balanced  Builds a balanced synthetic BloomTree on the GPU (benchmark databases)\n"
             "  ingest-check    Parses reads like `query` and prints what was read (no GPU)\n\n"
             "query takes the reference's options, plus --devices <0,1,..|all>: one replica of the database per GPU, reads\n"
@@ -2497,8 +2597,15 @@ void usage() {
             "--seed1 / --seed2).  bits: set bits of the filters; kmers: each genome's distinct k-mers estimated from its filter's fill;\n"
             "shared_kmers: those both have; jaccard = shared / union; containment_a = shared_kmers / kmers_a, the share of a's k-mers that b\n"
             "has; ani = 1 + ln(2 J / (1 + J)) / k, the Mash distance turned round (0 where jaccard is 0).  Only pairs whose larger containment\n"
-            "is at least C are written (default 0.1; --min-containment 0 writes all), ordered by a, then b\n",
-            header_cols.c_str());
+            "is at least C are written (default 0.1; --min-containment 0 writes all), ordered by a, then b\n"
+            "recluster -d <DB> -o <NEWDB> [--merges <FILE>] [--device <N>]: build and add place a genome by the order it arrives in, and\n"
+            "nothing ever moves.  This writes NEWDB (not DB itself) with the same genomes and the same filters under a tree rebuilt from\n"
+            "the filters alone: average-linkage clustering of the genomes' chance-corrected similarities, on the GPU, so that strains\n"
+            "sit under one node (--lca, --search-depth and large databases rely on that).  query gives the same genomes for every read\n"
+            "on both.  --merges writes the dendrogram, one line per internal node in the order they were made:\n\"%s\"\n"
+            "(<TAB> between the columns; similarity = score_sum / (pairs * 2^20), from 0 to 1: cut the tree where it drops).  Up to 16384\n"
+            "genomes.  build --cluster: build, then recluster, in one run; the database equals that of the two commands byte for byte\n",
+            header_cols.c_str(), merges_cols.c_str());
 }
 
 }  // namespace
@@ -2522,6 +2629,7 @@ int main(int argc, char **argv) {
     if (cmd == "build") return cmd_build((int)av.size(), av.data());
     if (cmd == "add") return cmd_add((int)av.size(), av.data());
     if (cmd == "compare") return cmd_compare((int)av.size(), av.data());
+    if (cmd == "recluster") return cmd_recluster((int)av.size(), av.data());
     usage();
     return 2;
 }

@@ -107,6 +107,7 @@ struct Knobs {
     long long cover_p = -1, cover_blocks = -1;  // PFQ_WANT_COVERAGE: registers per leaf = 2^cover_p (4..16, unset: 12); grid of the sketch kernel
     long long frame_piece = -1;                 // pfq_query_frames: k-mer positions per piece of the refinement (a positive multiple of 64)
     long long sim_slices = -1, sim_naive = -1, sim_time = -1;  // pfq_tree_similarity: slices of the filter words (0 / unset: built-in); 1: the one-block-per-pair kernel; 1: time the kernel
+    long long cluster_time = -1;                // pfq_tree_recluster: 1: time the stages with HIP events (pfq_debug_last_recluster)
 };
 struct KnobName {
     const char *name;
@@ -137,7 +138,7 @@ const KnobName KNOBS[] = {
     {"PFQ_COVER_P", &Knobs::cover_p},           {"PFQ_COVER_BLOCKS", &Knobs::cover_blocks},
     {"PFQ_FRAME_PIECE", &Knobs::frame_piece},
     {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
-    {"PFQ_SIM_TIME", &Knobs::sim_time},
+    {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -392,6 +393,13 @@ struct pfq_tree {
     std::vector<double> out_sim_kmers_a, out_sim_kmers_b, out_sim_shared_kmers, out_sim_jaccard;
     float sim_kernel_ms = 0.0f;            // pfq_debug_last_similarity: device time of the last call's intersection kernel, its slices
     uint32_t sim_slices = 0;
+    // pfq_tree_recluster: the merge log of the tree the call made (pfq_tree_merges), until its topology changes; on the source
+    // tree, what pfq_debug_last_recluster reports of the last call
+    std::vector<pfq_merge> merges;
+    uint32_t merge_rounds = 0;
+    float cluster_ms[3] = {0.0f, 0.0f, 0.0f};
+    uint64_t cluster_nn_bytes = 0;
+    uint32_t cluster_rounds = 0;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -2721,6 +2729,8 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
     t.cov_bits_valid = false;
+    t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
+    t.merge_rounds = 0;
     PFQ_TRY(reserve_rows(t, t.n_rows + 2));
     if (!t.greedy_blocks) {
         hipDeviceProp_t prop;
@@ -3037,6 +3047,8 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
     t.cov_bits_valid = false;
+    t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
+    t.merge_rounds = 0;
     return PFQ_OK;
 }
 
@@ -3448,6 +3460,227 @@ int pfq_debug_last_similarity(pfq_tree *a, double *kernel_ms, uint32_t *slices) 
     if (!a) return fail(PFQ_ERR_ARG, "null argument");
     if (kernel_ms) *kernel_ms = (double)a->sim_kernel_ms;
     if (slices) *slices = a->sim_slices;
+    return PFQ_OK;
+}
+
+// ---- pfq_tree_recluster ----
+namespace {
+// HIP events of a PFQ_CLUSTER_TIME=1 call: pairs (begin, end) per measured stretch, destroyed with the call
+struct ClusterTimer {
+    bool on = false;
+    std::vector<hipEvent_t> ev;
+    ~ClusterTimer() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    size_t mark() {  // records an event on the null stream; its index
+        if (!on) return 0;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) {
+            (void)hipGetLastError();
+            on = false;
+            return 0;
+        }
+        (void)hipEventRecord(e, nullptr);
+        ev.push_back(e);
+        return ev.size() - 1;
+    }
+    float between(size_t a, size_t b) const {
+        float ms = 0.0f;
+        if (on && a < ev.size() && b < ev.size() && hipEventSynchronize(ev[b]) == hipSuccess) (void)hipEventElapsedTime(&ms, ev[a], ev[b]);
+        return ms;
+    }
+};
+}  // namespace
+
+int pfq_tree_recluster(pfq_tree *src, pfq_tree **out) {
+    if (!src) return fail(PFQ_ERR_ARG, "pfq_tree_recluster: src is NULL");
+    if (!out) return fail(PFQ_ERR_ARG, "pfq_tree_recluster: out is NULL");
+    *out = nullptr;
+    pfq_tree &s = *src;
+    // src's queued work, pending insertions included (a sticky insertion error is returned here)
+    PFQ_TRY(use_device(s.device));
+    PFQ_TRY(build_layout(s));
+    HIP_TRY(hipDeviceSynchronize());
+    if (s.leaves.empty()) return fail(PFQ_ERR_STATE, "pfq_tree_recluster on an empty tree");
+    if (s.is_shard) return fail(PFQ_ERR_UNSUPPORTED, "pfq_tree_recluster: a subtree shard holds only part of the database's leaves");
+    const size_t L = s.leaves.size(), nw = (size_t)s.n_words;
+    if (L > pfq::CLUSTER_MAX_LEAVES)
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_tree_recluster: " + std::to_string(L) + " leaves are more than the " + std::to_string(pfq::CLUSTER_MAX_LEAVES) +
+                                             " whose score matrix is kept in device memory");
+    {
+        std::unordered_set<std::string> seen;
+        for (int32_t v : s.leaves)
+            if (!seen.insert(s.nodes[v].bf_path).second)
+                return fail(PFQ_ERR_UNSUPPORTED, "pfq_tree_recluster: two leaves share " + s.nodes[v].bf_path + ": the new tree would save two filters under one name");
+    }
+    std::unique_ptr<pfq_tree> t(new pfq_tree());
+    t->device = s.device;
+    t->kmer_size = s.kmer_size;
+    t->nbits = s.nbits;
+    t->num_hashes = s.num_hashes;
+    t->seed1 = s.seed1;
+    t->seed2 = s.seed2;
+    t->false_pos_rate = s.false_pos_rate;
+    t->largest_expected_genome = s.largest_expected_genome;
+    PFQ_TRY(setup_hash_params(*t));
+    const size_t n_nodes = 2 * L - 1;
+    if (t->d_bits.ensure(n_nodes * nw) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PFQ_ERR_DEVICE, "not enough device memory for " + std::to_string(n_nodes) + " filters of " + std::to_string(nw * 8) + " bytes");
+    }
+    t->n_rows = t->row_capacity = n_nodes;
+    // nodes in the numbering of the rule (pfq.h "re-clustering"), node n's filter in row n; finish_topology puts them in pre-order
+    t->nodes.resize(n_nodes);
+    t->filter_paths.resize(n_nodes);
+    std::unordered_set<std::string> names;
+    for (size_t i = 0; i < L; ++i) {
+        const Node &from = s.nodes[s.leaves[i]];
+        Node &nd = t->nodes[i];
+        nd.bf_path = from.bf_path;
+        nd.has_tax = from.has_tax;
+        nd.tax_id = from.tax_id;
+        nd.filter = (uint32_t)i;
+        t->filter_paths[i] = nd.bf_path;
+        names.insert(nd.bf_path);
+        HIP_TRY(hipMemcpyAsync(t->d_bits.p + i * nw, s.d_bits.p + (size_t)s.col_row[i] * nw, nw * 8, hipMemcpyDeviceToDevice, nullptr));
+    }
+    ClusterTimer timer;
+    timer.on = s.knobs.cluster_time == 1;
+    s.cluster_ms[0] = s.cluster_ms[1] = s.cluster_ms[2] = 0.0f;
+    s.cluster_nn_bytes = 0;
+    s.cluster_rounds = 0;
+    uint32_t round = 0;
+    if (L > 1) {
+        // scratch of this call only (freed on return: it never shows in pfq_info.device_bytes)
+        const size_t pitch = (L + 15) & ~(size_t)15;
+        constexpr uint64_t MAX_PANEL = 1ull << 26;  // pairs per launch of the intersection kernel
+        DevBuf<unsigned long long> d_S, d_pop, d_pos, d_sums;
+        DevBuf<uint32_t> d_rows, d_I, d_slot_of, d_best, d_flag, d_triples;
+        DevBuf<uint2> d_meta;
+        DevBuf<pfq::ClusterMerge> d_list;
+        if (d_S.ensure(L * pitch) != hipSuccess || d_I.ensure((size_t)std::min<uint64_t>((uint64_t)L * L, MAX_PANEL)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PFQ_ERR_UNSUPPORTED, "pfq_tree_recluster: the score matrix of " + std::to_string(L) + " leaves (" + std::to_string((L * pitch * 8) >> 20) +
+                                                 " MiB) and a panel of shared bits do not fit in device memory beside the two trees");
+        }
+        HIP_TRY(d_pop.ensure(L));
+        HIP_TRY(d_rows.ensure(L));
+        HIP_TRY(d_meta.ensure(pitch));
+        HIP_TRY(d_slot_of.ensure(n_nodes));
+        HIP_TRY(d_best.ensure(L));
+        HIP_TRY(d_flag.ensure(n_nodes));
+        HIP_TRY(d_pos.ensure(n_nodes + 1));
+        HIP_TRY(d_sums.ensure(n_nodes / 4096 + 2));
+        HIP_TRY(d_list.ensure(L / 2 + 1));
+        HIP_TRY(d_triples.ensure(3 * (L / 2 + 1)));
+        std::vector<uint2> meta(pitch, make_uint2(pfq::CLUSTER_NONE, 0u));
+        std::vector<uint32_t> slot_of(n_nodes, pfq::CLUSTER_NONE), size_of(n_nodes, 1);
+        for (size_t i = 0; i < L; ++i) {
+            meta[i] = make_uint2((uint32_t)i, 1u);
+            slot_of[i] = (uint32_t)i;
+        }
+        HIP_TRY(hipMemcpy(d_meta.p, meta.data(), pitch * sizeof(uint2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_slot_of.p, slot_of.data(), n_nodes * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rows.p, s.col_row.data(), L * 4, hipMemcpyHostToDevice));  // (the first L columns are the leaves)
+        HIP_TRY(hipMemsetAsync(d_S.p, 0, L * pitch * 8, nullptr));
+        // stage A: the shared bits of all leaf pairs on or above the diagonal, in panels of rows, and their scores
+        const size_t ev_a = timer.mark();
+        pfq::launch_filter_row_bits(s.d_bits.p, d_rows.p, (uint32_t)L, nw, s.nbits, d_pop.p, nullptr);
+        const uint32_t slices = s.knobs.sim_slices > 0 ? (uint32_t)std::min<long long>(s.knobs.sim_slices, 65535) : 0;
+        for (size_t r0 = 0; r0 < L;) {
+            const size_t nc = L - r0, nr = std::min<size_t>(nc, std::max<size_t>(1, (size_t)(MAX_PANEL / nc)));
+            HIP_TRY(hipMemsetAsync(d_I.p, 0, nr * nc * 4, nullptr));  // (the slices of the tiled kernel add into it)
+            pfq::launch_filter_intersections(s.d_bits.p, d_rows.p + r0, (uint32_t)nr, s.d_bits.p, d_rows.p + r0, (uint32_t)nc, nw, s.nbits, slices,
+                                             s.knobs.sim_naive == 1, d_I.p, nullptr);
+            pfq::launch_cluster_scores(d_I.p, d_pop.p, (uint32_t)r0, (uint32_t)nr, (uint32_t)nc, s.nbits, d_S.p, pitch, nullptr);
+            HIP_TRY(hipGetLastError());
+            r0 += nr;
+        }
+        const size_t ev_b = timer.mark();
+        // stage B: the rounds.  The host reads back a round's merges only: the topology lives here.
+        std::vector<pfq::ClusterMerge> list(L / 2 + 1);
+        std::vector<uint32_t> triples;
+        std::vector<std::pair<size_t, size_t>> nn_ev;
+        size_t made = L, live = L;
+        uint64_t counter = 0;
+        while (live > 1) {
+            const size_t e0 = timer.mark();
+            pfq::launch_cluster_nearest(d_S.p, pitch, d_meta.p, (uint32_t)L, d_best.p, nullptr);
+            nn_ev.emplace_back(e0, timer.mark());
+            s.cluster_nn_bytes += (uint64_t)live * pitch * 8;
+            pfq::launch_cluster_mutual(d_slot_of.p, (uint32_t)made, d_best.p, d_meta.p, d_flag.p, nullptr);
+            pfq::launch_scan_u32(d_flag.p, made, d_sums.p, d_pos.p, nullptr);
+            pfq::launch_cluster_list(d_slot_of.p, (uint32_t)made, d_best.p, d_meta.p, d_flag.p, d_pos.p, d_S.p, pitch, d_list.p, (uint32_t)(L / 2 + 1), nullptr);
+            HIP_TRY(hipGetLastError());
+            unsigned long long n_merges = 0;
+            HIP_TRY(hipMemcpy(&n_merges, d_pos.p + made, 8, hipMemcpyDeviceToHost));
+            if (n_merges == 0 || n_merges > live / 2)
+                return fail(PFQ_ERR_DEVICE, "pfq_tree_recluster: round " + std::to_string(round) + " found " + std::to_string(n_merges) + " mutual pairs among " +
+                                                std::to_string(live) + " clusters");
+            HIP_TRY(hipMemcpy(list.data(), d_list.p, (size_t)n_merges * sizeof(pfq::ClusterMerge), hipMemcpyDeviceToHost));
+            triples.clear();
+            for (size_t p = 0; p < n_merges; ++p) {
+                const pfq::ClusterMerge &mg = list[p];
+                const uint32_t node = (uint32_t)(made + p);
+                if (mg.node_a >= made || mg.node_b >= made || mg.node_a >= mg.node_b)
+                    return fail(PFQ_ERR_DEVICE, "pfq_tree_recluster: round " + std::to_string(round) + " lists a pair that is none");
+                size_of[node] = size_of[mg.node_a] + size_of[mg.node_b];
+                t->merges.push_back(pfq_merge{node, mg.node_a, mg.node_b, round, size_of[node], 0u, mg.score, (uint64_t)size_of[mg.node_a] * size_of[mg.node_b]});
+                std::string name;
+                do name = "Internal_Node_" + std::to_string(counter++);
+                while (names.count(name + ".bf"));
+                Node &nd = t->nodes[node];
+                nd.has_tax = true;
+                nd.tax_id = name;
+                nd.bf_path = name + ".bf";
+                nd.filter = node;
+                nd.left = (int32_t)mg.node_a;
+                nd.right = (int32_t)mg.node_b;
+                t->filter_paths[node] = nd.bf_path;
+                names.insert(nd.bf_path);
+                triples.insert(triples.end(), {node, mg.node_a, mg.node_b});
+            }
+            pfq::launch_cluster_merge(d_S.p, pitch, d_meta.p, d_slot_of.p, (uint32_t)L, d_list.p, (uint32_t)n_merges, (uint32_t)made, nullptr);
+            // the new nodes' filters: one launch per round, earlier rounds first (a later round reads their rows)
+            HIP_TRY(hipMemcpy(d_triples.p, triples.data(), triples.size() * 4, hipMemcpyHostToDevice));
+            pfq::launch_union(t->d_bits.p, nw, d_triples.p, (uint32_t)n_merges, nullptr);
+            HIP_TRY(hipGetLastError());
+            made += (size_t)n_merges;
+            live -= (size_t)n_merges;
+            ++round;
+        }
+        const size_t ev_c = timer.mark();
+        HIP_TRY(hipDeviceSynchronize());
+        s.cluster_ms[0] = timer.between(ev_a, ev_b);
+        s.cluster_ms[1] = timer.between(ev_b, ev_c);
+        for (const auto &e : nn_ev) s.cluster_ms[2] += timer.between(e.first, e.second);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    s.cluster_rounds = round;
+    t->internal_counter = t->merges.size();
+    t->merge_rounds = round;
+    t->root = (int32_t)(n_nodes - 1);
+    t->tree_leaves = L;
+    t->topology_dirty = true;  // renumbered into pre-order, parent ⊇ child verified on the device
+    PFQ_TRY(finish_topology(*t));
+    *out = t.release();
+    return PFQ_OK;
+}
+
+int pfq_tree_merges(pfq_tree *tree, const pfq_merge **merges, uint64_t *n, uint32_t *rounds) {
+    if (!tree || !merges || !n) return fail(PFQ_ERR_ARG, "null argument");
+    *merges = tree->merges.data();
+    *n = tree->merges.size();
+    if (rounds) *rounds = tree->merge_rounds;
+    return PFQ_OK;
+}
+
+int pfq_debug_last_recluster(pfq_tree *src, double *ms, uint64_t *nn_bytes, uint32_t *rounds) {
+    if (!src) return fail(PFQ_ERR_ARG, "null argument");
+    if (ms)
+        for (int i = 0; i < 3; ++i) ms[i] = (double)src->cluster_ms[i];
+    if (nn_bytes) *nn_bytes = src->cluster_nn_bytes;
+    if (rounds) *rounds = src->cluster_rounds;
     return PFQ_OK;
 }
 

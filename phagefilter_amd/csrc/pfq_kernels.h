@@ -517,6 +517,34 @@ uint32_t launch_filter_intersections(const uint64_t *bits_a, const uint32_t *d_r
                                      uint32_t n_b, uint64_t n_words, uint64_t nbits, uint32_t slices, bool naive, uint32_t *d_out, hipStream_t st);
 void launch_filter_row_bits(const uint64_t *bits, const uint32_t *d_rows, uint32_t n_rows, uint64_t n_words, uint64_t nbits, unsigned long long *d_out,
                             hipStream_t st);
+// pfq_tree_recluster (pfq_cluster.hip): average linkage over the chance-corrected scores of the leaf filters, in integers.
+// The score matrix d_S is u64 [n_slots][pitch] (pitch: a multiple of 16 columns, >= n_slots), a slot per cluster: the leaves
+// start in slots 0 .. L - 1, a merge leaves the new cluster in its left child's slot and retires the right child's.
+// d_meta [pitch]: (node index or CLUSTER_NONE, leaves of the cluster) per slot; d_slot_of [2 L - 1]: node -> slot or CLUSTER_NONE.
+//   launch_cluster_scores: a panel of launch_filter_intersections — leaves r0 .. r0 + n_r against leaves r0 .. r0 + n_c, d_shared
+//     [n_r][n_c] — turned into q (pfq.h "re-clustering") with d_pop = launch_filter_row_bits of all leaves; pairs above the
+//     diagonal are written to both halves of d_S (the caller zeroes d_S once).
+//   launch_cluster_nearest: d_best[slot] = the slot of the best other live cluster (score descending, node index ascending).
+//   launch_cluster_mutual: d_flag[n] = 1 for a live node n whose best chose it back and has the larger index, n < n_nodes; the
+//     caller scans the flags (launch_scan_u32) into d_pos.  launch_cluster_list: the flagged pairs at d_list[d_pos[n]].
+//   launch_cluster_merge: the rows and the columns of the right children are added to the left children's, the slots retired,
+//     merge p becomes node first_node + p.
+constexpr uint32_t CLUSTER_NONE = 0xffffffffu;
+constexpr uint32_t CLUSTER_MAX_LEAVES = 16384;
+constexpr uint32_t CLUSTER_Q = 20;  // a leaf pair's score is in units of 2^-20
+struct ClusterMerge {
+    uint32_t slot_a, slot_b, node_a, node_b;  // left child (the smaller node index) and right child
+    unsigned long long score;                 // S(left, right) before the merge
+};
+void launch_cluster_scores(const uint32_t *d_shared, const unsigned long long *d_pop, uint32_t r0, uint32_t n_r, uint32_t n_c, uint64_t nbits,
+                           unsigned long long *d_S, uint64_t pitch, hipStream_t st);
+void launch_cluster_nearest(const unsigned long long *d_S, uint64_t pitch, const uint2 *d_meta, uint32_t n_slots, uint32_t *d_best, hipStream_t st);
+void launch_cluster_mutual(const uint32_t *d_slot_of, uint32_t n_nodes, const uint32_t *d_best, const uint2 *d_meta, uint32_t *d_flag, hipStream_t st);
+void launch_cluster_list(const uint32_t *d_slot_of, uint32_t n_nodes, const uint32_t *d_best, const uint2 *d_meta, const uint32_t *d_flag,
+                         const unsigned long long *d_pos, const unsigned long long *d_S, uint64_t pitch, ClusterMerge *d_list, uint32_t list_cap,
+                         hipStream_t st);
+void launch_cluster_merge(unsigned long long *d_S, uint64_t pitch, uint2 *d_meta, uint32_t *d_slot_of, uint32_t n_slots, const ClusterMerge *d_list,
+                          uint32_t n_merges, uint32_t first_node, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -38,6 +38,11 @@ SEGMENT_DTYPE = np.dtype([(f, np.uint32) for f in ("leaf", "first_frame", "n_fra
                                                    "matched", "longest_run")])
 
 
+# one pfq_merge (include/pfq.h)
+MERGE_DTYPE = np.dtype([("node", np.uint32), ("left", np.uint32), ("right", np.uint32), ("round", np.uint32), ("n_leaves", np.uint32),
+                        ("pad_", np.uint32), ("score_sum", np.uint64), ("pairs", np.uint64)])
+
+
 def pack_reads(reads: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     off = np.zeros(len(reads) + 1, dtype=np.uint64)
     if reads:
@@ -452,6 +457,45 @@ class BloomTree:
         ms, sl = C.c_double(), C.c_uint32()
         _ffi.check(_ffi.lib().pfq_debug_last_similarity(self._h, C.byref(ms), C.byref(sl)))
         return float(ms.value), int(sl.value)
+
+    # ---- re-clustering
+    def recluster(self) -> "BloomTree":
+        """A new tree over this tree's leaves, on the same device, whose shape follows from the leaf filters alone
+        (pfq_tree_recluster): average-linkage clustering of their chance-corrected similarities.  The leaves keep their names and
+        filter words; this tree is left as it was.  merges() of the new tree is the dendrogram."""
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().pfq_tree_recluster(self._h, C.byref(h)))
+        return BloomTree(h, self.device)
+
+    def merges(self) -> np.ndarray:
+        """The merge log of a tree made by recluster() (pfq_tree_merges), one MERGE_DTYPE record per internal node in creation
+        order: `node`, `left`, `right` number the source tree's leaves 0 .. L - 1 in its get_leaf_counts order and the internal
+        nodes from L on; `round`, `n_leaves`, `score_sum`, `pairs`: the merge happened at similarity score_sum / (pairs * 2**20).
+        Empty for any other tree."""
+        p = C.POINTER(_ffi.Merge)()
+        n = C.c_uint64()
+        r = C.c_uint32()
+        _ffi.check(_ffi.lib().pfq_tree_merges(self._h, C.byref(p), C.byref(n), C.byref(r)))
+        if not n.value:
+            return np.zeros(0, dtype=MERGE_DTYPE)
+        return np.frombuffer(C.string_at(p, n.value * C.sizeof(_ffi.Merge)), dtype=MERGE_DTYPE).copy()
+
+    def merge_rounds(self) -> int:
+        """Rounds the clustering behind this tree ran (0 for a tree not made by recluster(), and for one leaf)."""
+        p = C.POINTER(_ffi.Merge)()
+        n = C.c_uint64()
+        r = C.c_uint32()
+        _ffi.check(_ffi.lib().pfq_tree_merges(self._h, C.byref(p), C.byref(n), C.byref(r)))
+        return int(r.value)
+
+    def last_recluster(self) -> dict:
+        """Of the last recluster() of this tree (pfq_debug_last_recluster): `scores_ms`, `rounds_ms`, `nearest_ms` — device
+        milliseconds, measured only under set_option("PFQ_CLUSTER_TIME", "1") — `nearest_bytes` and `rounds`."""
+        ms = (C.c_double * 3)()
+        b = C.c_uint64()
+        r = C.c_uint32()
+        _ffi.check(_ffi.lib().pfq_debug_last_recluster(self._h, ms, C.byref(b), C.byref(r)))
+        return {"scores_ms": ms[0], "rounds_ms": ms[1], "nearest_ms": ms[2], "nearest_bytes": int(b.value), "rounds": int(r.value)}
 
     def export_counts(self, d_dst: int, stream: int = 0) -> None:
         _ffi.check(_ffi.lib().pfq_leaf_counts_export(self._h, d_dst, stream))
