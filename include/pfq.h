@@ -342,6 +342,51 @@ int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets
 int pfq_query_frames_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t total_bytes,
                             uint32_t frame, uint32_t step, float threshold, uint32_t flags, void *stream, pfq_segments *out);
 
+/* ---- text (pfq_text_parse, pfq_text_query) ----
+ * Plain FASTA / FASTQ text parsed on the device into the block a query call takes, at the seam of the reference's readers
+ * (file_parser.rs:191-301): the host only hands over file bytes.  Two calls, so that a caller who guessed a record boundary can
+ * parse, check the guess and only then let the records reach the counters.
+ * pfq_text_parse: the caller claims that text[0] is the first byte of a record's header line; the result is defined relative to
+ * the sequential reader started there.  A line is a maximal run of bytes ended by '\n', without the '\n'; an unterminated last
+ * run counts as a line only with PFQ_TEXT_FINAL; trimmed = without trailing bytes of {' ', \t, \n, \v, \f, \r}.
+ * FASTQ: record r = lines 4r .. 4r + 3, beginning at b = the start of line 4r.  In this order: no byte is left: stop END; bytes are
+ *   left but no considered line: MORE; b >= limit: LIMIT; fewer than four considered lines are left: SLOW with PFQ_TEXT_FINAL, else
+ *   MORE; the record is not plain: SLOW; otherwise it is taken, its sequence is line 4r + 1 trimmed, and r + 1 follows.  Plain: line
+ *   4r begins with '@', line 4r + 1 does not begin with '+' (it may be empty), line 4r + 2 begins with '+', line 4r + 3 trimmed is
+ *   not empty.  A plain record is exactly what the sequential reader returns from b, and it goes on at line 4r + 4.
+ * FASTA: a header is a line whose first byte is '>'.  Text that does not begin with '>': nothing taken, consumed 0, SLOW.  A
+ *   record is complete when a later header is among the considered lines, or with PFQ_TEXT_FINAL.  In order: a record that begins
+ *   at or beyond limit: LIMIT; an incomplete record: MORE; otherwise it is taken, its sequence being its other lines, each
+ *   trimmed, joined.  All taken: consumed = len, END.
+ * Empty text: nothing, END.  consumed is always the begin of the first record not taken, or len: the records taken are a prefix
+ * of the sequential reader's, and it would read next at text + consumed.
+ * The call changes no counter, log, sketch or query result and may be used on a tree whose filters are never queried.  text is a
+ * host buffer (page-locked memory copies fastest) that may be reused when the call returns.  The copy and the parse kernels run
+ * on the tree's copy stream into one of two alternating CSR buffer sets, so they overlap the classification of the previous
+ * pfq_text_query; the call waits for its own work only, and for an earlier classification only if that one still reads the set
+ * about to be reused.  The CSR (sequence buffer padded by 16 bytes) lives until the next pfq_text_parse on the tree or its close;
+ * other query calls do not disturb it.  PFQ_ERR_ARG: tree or out NULL, text NULL with len > 0, an unknown format or flag;
+ * PFQ_ERR_UNSUPPORTED: len >= 2^31 (ask in pieces).  The option PFQ_TEXT_TILE (a power of two, 256 .. 8192) is the text a block
+ * scans.
+ * pfq_text_query: exactly pfq_query_batch_device(tree, csr_seq, csr_off, n_records, n_bases, threshold, flags, NULL, hits) on the
+ * block parsed last, ordered behind the parse by an event; every rule of that call applies.  It may be repeated (the counters
+ * grow each time).  Before any parse: PFQ_ERR_STATE. */
+#define PFQ_TEXT_FASTA 0
+#define PFQ_TEXT_FASTQ 1
+#define PFQ_TEXT_FINAL 1u         /* the text ends where the file ends */
+#define PFQ_TEXT_WANT_RECORDS 2u  /* fill rec_begin */
+enum { PFQ_TEXT_END = 0, PFQ_TEXT_LIMIT = 1, PFQ_TEXT_MORE = 2, PFQ_TEXT_SLOW = 3 };
+typedef struct pfq_text {
+    uint64_t n_records;        /* records taken */
+    uint64_t consumed;         /* the records taken are text[0, consumed); the next record starts at text + consumed */
+    uint64_t n_bases;          /* bases of the records taken (offsets[n_records] of the CSR) */
+    uint32_t stop;             /* why it stopped, PFQ_TEXT_* */
+    const uint64_t *rec_begin; /* [n_records + 1] byte offset of every taken record's header line, then consumed; NULL without PFQ_TEXT_WANT_RECORDS; library-owned */
+} pfq_text;
+int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t limit, int format, uint32_t flags, pfq_text *out);
+int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits);
+int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /* tests: the parsed CSR copied to the host */
+
 /* ---- genome similarity ----
  * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one
  * geometry and one seed pair; for two filters the set bits and the shared set bits estimate how many k-mers each genome has and

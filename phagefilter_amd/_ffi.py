@@ -18,6 +18,7 @@ SYMBOLS = [
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
+    "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
@@ -88,6 +89,11 @@ class Segments(C.Structure):
     _fields_ = [("n_seqs", C.c_uint64), ("n_frames", C.c_uint64), ("offsets", C.POINTER(C.c_uint64)), ("seg", C.POINTER(Segment))]
 
 
+class Text(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("consumed", C.c_uint64), ("n_bases", C.c_uint64), ("stop", C.c_uint32),
+                ("rec_begin", C.POINTER(C.c_uint64))]
+
+
 class Similarity(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("shared_bits", C.POINTER(C.c_uint32)),
                 ("bits_a", C.POINTER(C.c_uint64)), ("bits_b", C.POINTER(C.c_uint64)),
@@ -110,6 +116,9 @@ WANT_ABUNDANCE = 64
 ABUND_Q = 16
 WANT_COVERAGE = 128
 NO_CLADE = 0xFFFFFFFF
+TEXT_FASTA, TEXT_FASTQ = 0, 1
+TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
+TEXT_END, TEXT_LIMIT, TEXT_MORE, TEXT_SLOW = 0, 1, 2, 3
 _lib = None
 
 
@@ -163,6 +172,9 @@ def lib() -> C.CDLL:
     L.pfq_query_frames.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(Segments)]
     L.pfq_query_frames_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
                                           C.POINTER(Segments)]
+    L.pfq_text_parse.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(Text)]
+    L.pfq_text_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
+    L.pfq_debug_text_csr.argtypes = [vp, vp, vp]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
     L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.pfq_tree_recluster.argtypes = [vp, C.POINTER(vp)]

@@ -465,6 +465,28 @@ struct RecordParser {
 //   * a gzip file is inflated and parsed by one worker as a stream of segments; several files run concurrently.
 // Segments are consumed strictly in input order, so blocks, ids and outputs are those of a sequential reader.
 // ---------------------------------------------------------------------------------------------------------------
+// A page-locked buffer (pfq_host_alloc) that only grows; --device-parse reads file bytes into it for pfq_text_parse.
+struct PinnedBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    ~PinnedBuf() {
+        if (p) pfq_host_free(p);
+    }
+    char *ensure(size_t n) {
+        if (n > cap) {
+            if (p) pfq_host_free(p);
+            p = nullptr;
+            cap = 0;
+            void *q = nullptr;
+            if (pfq_host_alloc(n + n / 8, &q) != PFQ_OK) die(std::string("libpfq: ") + pfq_last_error());
+            p = (char *)q;
+            cap = n + n / 8;
+        }
+        return p;
+    }
+};
 struct Segment {
     Batch b;
     std::atomic<int> refs{0};             // the consumer + every batch that references the segment's ids / qualities
@@ -472,6 +494,10 @@ struct Segment {
     uint64_t start_pos = 0, end_pos = 0;  // plain chunks: first record start, start of the record after the last one
     std::string err;                      // malformed input met after the records in b
     bool last = true;                     // gzip streams: more segments of this task follow when false
+    // --device-parse: a plain chunk as bytes [text_lo, text_hi) of the file, not parsed; start_pos is the guessed record start
+    PinnedBuf text;
+    uint64_t text_lo = 0, text_hi = 0;
+    bool is_text = false;
 };
 struct MappedFile {  // (plain files are read with pread into reused buffers: first-touch page faults of a mapping
     uint64_t size = 0;   //  cost more than the copy, and serialise the workers)
@@ -501,6 +527,8 @@ struct ReadQueue {
     unsigned n_threads = 1;
     uint64_t chunk_bytes = 32ull << 20, seg_reads = 1u << 18;
     size_t lookahead = 8;
+    bool device_parse = false;        // --device-parse: the workers only read the plain chunks (read_raw), the consumer parses
+    std::unique_ptr<std::atomic<bool>[]> file_slow;  // ... until a file turned out not to be ordinary: its later chunks are parsed here
 
     std::mutex mu;
     std::condition_variable cv_work, cv_out;
@@ -572,6 +600,8 @@ struct ReadQueue {
                 }
             }
         }
+        file_slow.reset(new std::atomic<bool>[files.size() + 1]);
+        for (size_t i = 0; i < files.size(); ++i) file_slow[i] = false;
         started = true;
         for (unsigned i = 0; i < n_threads; ++i) workers.emplace_back([this] { work(); });
     }
@@ -634,12 +664,7 @@ struct ReadQueue {
         for (uint64_t extra = 1ull << 20;; extra *= 8) {
             const uint64_t r_hi = std::min(m.size, std::max(hi, want_lo) + extra);
             s.raw.resize((size_t)(r_hi - want_lo));
-            for (uint64_t got = 0; got < r_hi - want_lo;) {
-                ssize_t n = pread(m.fd, s.raw.data() + got, (size_t)(r_hi - want_lo - got), (off_t)(want_lo + got));
-                if (n < 0) die(std::string("read error: ") + strerror(errno));
-                if (n == 0) die("input file shrank while it was being read");
-                got += (uint64_t)n;
-            }
+            read_range(m, s.raw.data(), want_lo, r_hi);
             const FileView v{(const char *)((uintptr_t)s.raw.data() - (uintptr_t)want_lo), want_lo, r_hi};
             s.b.clear();
             s.err.clear();
@@ -650,6 +675,31 @@ struct ReadQueue {
             ns_find += t1 - t0;
             ns_parse += now_ns() - t1;
             if (!hit_end || r_hi == m.size) return;  // otherwise the last record may be cut: read further
+        }
+    }
+    // --device-parse: chunk [lo, hi) of a plain file as bytes [lo - 1, hi + 1 MiB) in page-locked memory and the guessed start
+    // of its first record; nothing is parsed.
+    void read_raw(const MappedFile &m, Fmt fmt, uint64_t lo, uint64_t hi, Segment &s) {
+        const uint64_t want_lo = lo ? lo - 1 : 0, r_hi = std::min<uint64_t>(m.size, hi + (1ull << 20));
+        char *buf = s.text.ensure((size_t)(r_hi - want_lo));
+        read_range(m, buf, want_lo, r_hi);
+        const FileView v{(const char *)((uintptr_t)buf - (uintptr_t)want_lo), want_lo, r_hi};
+        s.b.clear();
+        s.err.clear();
+        const uint64_t t0 = now_ns();
+        s.start_pos = find_record_start(v, fmt, lo);
+        ns_find += now_ns() - t0;
+        s.end_pos = s.start_pos;
+        s.text_lo = want_lo;
+        s.text_hi = r_hi;
+        s.is_text = true;
+    }
+    static void read_range(const MappedFile &m, char *buf, uint64_t lo, uint64_t hi) {
+        for (uint64_t got = 0; got < hi - lo;) {
+            ssize_t n = pread(m.fd, buf + got, (size_t)(hi - lo - got), (off_t)(lo + got));
+            if (n < 0) die(std::string("read error: ") + strerror(errno));
+            if (n == 0) die("input file shrank while it was being read");
+            got += (uint64_t)n;
         }
     }
     Segment *fresh_segment() {
@@ -666,6 +716,7 @@ struct ReadQueue {
         s->start_pos = s->end_pos = 0;
         s->err.clear();
         s->last = true;
+        s->is_text = false;
         return s;
     }
     // segments the pool takes back (filtering: batches in flight hold their segments)
@@ -709,7 +760,8 @@ struct ReadQueue {
             const Fmt fmt = fmts[t.file];
             if (!t.stream) {
                 Segment *s = fresh_segment();
-                parse_chunk(m, fmt, t.lo, t.hi, false, 0, *s);
+                if (device_parse && m.size && !file_slow[t.file]) read_raw(m, fmt, t.lo, t.hi, *s);
+                else parse_chunk(m, fmt, t.lo, t.hi, false, 0, *s);
                 push(t, s);
                 continue;
             }
@@ -739,6 +791,14 @@ struct ReadQueue {
     // ---- ordered consumption ----------------------------------------------------------------------------------
     // Next segment in input order (validated), or nullptr at the end of the input.
     Segment *next_segment() {
+        const Task *t = nullptr;
+        Segment *s = pop_segment(t);
+        if (s) validate(*t, *s);
+        return s;
+    }
+    // The two halves of next_segment: the next segment in input order as the workers left it, and the proof of a plain chunk's
+    // start.  --device-parse takes segments on several threads and proves them one after the other, in the order taken.
+    Segment *pop_segment(const Task *&task) {
         while (consume_task < tasks.size()) {
             Task &t = tasks[consume_task];
             Segment *s;
@@ -747,25 +807,24 @@ struct ReadQueue {
                 cv_out.wait(lk, [&] { return !t.out.empty(); });
                 s = t.out.front();
                 t.out.pop_front();
+                if (s->last) ++consume_task;
             }
             cv_work.notify_all();
-            const bool task_done = s->last;
-            if (!t.stream) {
-                const MappedFile &m = maps[t.file];
-                const uint64_t expect = t.lo == 0 ? 0 : proven_pos;
-                if (m.size && s->start_pos != expect) {  // guessed boundary was wrong (or a record spans chunks): redo
-                    parse_chunk(m, fmts[t.file], t.lo, t.hi, true, expect, *s);
-                }
-                proven_pos = s->end_pos;
-            }
-            if (task_done) {
-                std::lock_guard<std::mutex> lk(mu);
-                ++consume_task;
-            }
-            cv_work.notify_all();
+            task = &t;
             return s;
         }
         return nullptr;
+    }
+    uint64_t expected_start(const Task &t) const { return t.lo == 0 ? 0 : proven_pos; }
+    void validate(const Task &t, Segment &s) {
+        if (t.stream) return;
+        const MappedFile &m = maps[t.file];
+        const uint64_t expect = expected_start(t);
+        if (m.size && (s.is_text || s.start_pos != expect)) {  // guessed boundary was wrong (or a record spans chunks): redo
+            parse_chunk(m, fmts[t.file], t.lo, t.hi, true, expect, s);
+            s.is_text = false;
+        }
+        proven_pos = s.end_pos;
     }
     // Appends up to max_reads reads (and at most ~max_bytes bases); false when the input is exhausted.
     // by_ref (needs keep): ids and qualities are referenced, not copied — the batch holds the segments (release_held).
@@ -1633,6 +1692,110 @@ struct QueryLoop {
         });
     }
 
+    // --device-parse: counts only on replicas, the plain files parsed on the device.  A replica's thread takes the next segment
+    // in input order (a ticket) and, if it is a chunk's bytes, has its own tree parse them from the guessed record start
+    // (pfq_text_parse: speculative, no counter changes).  Then, ticket after ticket, the start is proven as next_segment proves
+    // it — it must be where the chunk before ended — and a wrong guess is parsed again from the proven position; the records
+    // taken are committed (proven_pos moves behind them) and classified after the turn is handed on (pfq_text_query).  Where the
+    // device stopped at text that is not ordinary (SLOW) or not complete within the chunk's slack (MORE), the sequential reader
+    // parses the rest of the chunk from exactly there, malformed input included; after a SLOW the file's later chunks go to
+    // the reader at once.  gzip streams arrive parsed, as ever.  Counting commutes, so only the proofs are ordered.
+    std::atomic<uint64_t> n_device_records{0}, n_host_records{0}, ns_text_parse{0}, n_text_bytes{0};
+    void counts_only_text() {
+        std::mutex take_mu, turn_mu;
+        std::condition_variable turn_cv;
+        uint64_t taken = 0, commit_next = 0;
+        std::atomic<bool> exhausted{false}, aborted{false};  // no segment is left; malformed input was met: later tickets are dropped
+        fan_out(n_trees(), [&](size_t d) {
+            pfq_tree *tree = db.trees[d];
+            Hits unused;
+            while (true) {
+                Segment *sg;
+                const Task *task = nullptr;
+                uint64_t ticket;
+                {
+                    std::lock_guard<std::mutex> lk(take_mu);
+                    if (exhausted || aborted) return;
+                    if (!(sg = rq.pop_segment(task))) {
+                        exhausted = true;
+                        return;
+                    }
+                    ticket = taken++;
+                }
+                const MappedFile &m = rq.maps[task->file];
+                const Fmt fmt = rq.fmts[task->file];
+                pfq_text res{};
+                uint64_t parsed_from = ~0ull;
+                auto parse_from = [&](uint64_t from) {  // the chunk's records from file offset `from` on
+                    parsed_from = from;
+                    res = pfq_text{};
+                    res.stop = PFQ_TEXT_LIMIT;
+                    if (from >= task->hi || from > sg->text_hi) return;  // (no record of this chunk begins there)
+                    const uint64_t t0 = ReadQueue::now_ns();
+                    if (pfq_text_parse(tree, (const uint8_t *)sg->text.p + (from - sg->text_lo), sg->text_hi - from, task->hi - from,
+                                       fmt == Fmt::Fastq ? PFQ_TEXT_FASTQ : PFQ_TEXT_FASTA, sg->text_hi == m.size ? PFQ_TEXT_FINAL : 0u, &res) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    ns_text_parse += ReadQueue::now_ns() - t0;
+                    n_text_bytes += sg->text_hi - from;
+                };
+                if (sg->is_text && !rq.file_slow[task->file]) parse_from(sg->start_pos);
+                {
+                    std::unique_lock<std::mutex> lk(turn_mu);
+                    turn_cv.wait(lk, [&] { return commit_next == ticket; });
+                }
+                // (the turn: one thread at a time, in the order the segments were taken)
+                const bool dropped = aborted;
+                uint64_t n_dev = 0;
+                if (!dropped && sg->is_text) {
+                    const uint64_t expect = rq.expected_start(*task);
+                    bool host_rest = rq.file_slow[task->file];
+                    uint64_t rest_from = expect;
+                    if (!host_rest) {
+                        if (parsed_from != expect) parse_from(expect);  // the guess was wrong (or a record spans chunks)
+                        n_dev = res.n_records;
+                        rest_from = expect + res.consumed;
+                        if (res.stop == PFQ_TEXT_SLOW) rq.file_slow[task->file] = host_rest = true;
+                        // (END short of the chunk's end in a window that is not the file's end: the window was used up, as with MORE)
+                        else if (res.stop == PFQ_TEXT_MORE || (res.stop == PFQ_TEXT_END && sg->text_hi != m.size && rest_from < task->hi)) host_rest = true;
+                    }
+                    if (host_rest) {
+                        rq.parse_chunk(m, fmt, task->lo, task->hi, true, rest_from, *sg);
+                        rq.proven_pos = sg->end_pos;
+                    } else rq.proven_pos = rest_from;
+                    sg->is_text = false;
+                } else if (!dropped) rq.validate(*task, *sg);
+                if (!dropped && !sg->err.empty()) {
+                    rq.pending_error = sg->err;  // (fatal later, after the reads before it)
+                    aborted = true;
+                }
+                {
+                    std::lock_guard<std::mutex> lk(turn_mu);
+                    ++commit_next;
+                }
+                turn_cv.notify_all();
+                if (!dropped && n_dev) {
+                    const uint64_t tq0 = ReadQueue::now_ns();
+                    if (pfq_text_query(tree, threshold, lca_flags(), nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    ns_gpu += ReadQueue::now_ns() - tq0;
+                    n_total += n_dev;
+                    n_device_records += n_dev;
+                }
+                if (!dropped && sg->b.n()) {
+                    sg->b.seq.resize(sg->b.seq.size() + 16);
+                    n_host_records += sg->b.n();
+                    count_segment(d, *sg, unused);
+                }
+                rq.recycle(sg);
+            }
+        });
+    }
+    void report_device_parse() const {
+        const double s = ns_text_parse.load() * 1e-9;
+        fprintf(stderr, "device parse: %llu records parsed on the device, %llu by the host reader; pfq_text_parse took %llu bytes in %.3f s (%.2f GB/s, copy and kernels, summed over devices)\n",
+                (unsigned long long)n_device_records.load(), (unsigned long long)n_host_records.load(), (unsigned long long)n_text_bytes.load(), s,
+                s > 0 ? n_text_bytes.load() / s * 1e-9 : 0.0);
+    }
+
     // Per read, with POS/NEG and/or READ_SCORES.  The device processes big batches; ResultMap semantics (ids merged per
     // reference block, cleared per block, main.rs:334-368) are applied per `block` consecutive reads so the outputs do not
     // depend on the batch size.  Three stages, each on its own thread(s), batches in flight between them: (1) the
@@ -1962,7 +2125,7 @@ int cmd_query(int argc, char **argv) {
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
-                             {"frame", 0, true}, {"frame-step", 0, true}};
+                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2030,6 +2193,16 @@ int cmd_query(int argc, char **argv) {
             if (a.flags.count(other)) die(std::string("error: '--frame' cannot be used with '--") + other + "'");
         if (lca) die("error: '--frame' cannot be used with '--lca'");
     }
+    // --device-parse: plain FASTA / FASTQ files are parsed on the device (pfq_text_parse); only where the run counts per genome
+    // (and per clade) on replicas — per-read outputs, pairs, frames and shards keep the host reader
+    const bool device_parse = a.flags.count("device-parse") != 0;
+    if (device_parse) {
+        for (const char *other : {"pos-filter", "neg-filter", "scores", "lca-reads", "interleaved", "abundance", "coverage"})
+            if (a.flags.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
+        for (const char *other : {"reads2", "frame", "shard-depth"})
+            if (a.val.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
+        if (lca == 2) die("error: '--device-parse' cannot be used with '--lca best': the best hits need every read's scores");
+    }
     const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
@@ -2091,6 +2264,7 @@ int cmd_query(int argc, char **argv) {
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
+    rq.device_parse = device_parse;
     if (block != 0) rq.start(per_read || paired || framed, threads);  // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences)
     if (block != 0 && rq2) rq2->start(true, threads);
 
@@ -2118,6 +2292,8 @@ int cmd_query(int argc, char **argv) {
         q.frames(frame, frame_step, out + "/SEGMENTS.tsv");
     } else if (paired) {
         q.paired(rq2.get(), pair_mode == "both");
+    } else if (device_parse) {
+        q.counts_only_text();
     } else if (!per_read) {
         q.counts_only();
     } else {
@@ -2129,6 +2305,7 @@ int cmd_query(int argc, char **argv) {
                 (unsigned long long)q.n_total.load(), wall, q.n_total.load() / wall * 1e-6, devices.size(), q.ns_gpu.load() * 1e-9,
                 q.ns_out.load() * 1e-9);
         rq.report_timing();
+        if (device_parse) q.report_device_parse();
         struct rusage ru;
         if (getrusage(RUSAGE_SELF, &ru) == 0)
             fprintf(stderr, "cpu: user %.2f s + system %.2f s so far (all threads) for %.2f s of query loop\n",
@@ -2587,6 +2764,12 @@ void usage() {
             "CLASSIFICATION.csv then counts sequences, one per genome with a segment.  Works with --devices (whole sequences are dealt to\n"
             "the replicas; the files do not depend on the device list, -t or the batch size).  Not with --reads2, --interleaved,\n"
             "--scores, --lca, --abundance, --coverage, --shard-depth, --pos-filter or --neg-filter; F must be at least the database's k\n"
+            "--device-parse: plain (not gzip) FASTA / FASTQ files are parsed on the GPU: the host threads only read file bytes, kernels\n"
+            "find the lines, check that the records are ordinary (FASTQ: four lines each) and gather the sequences.  Where the text is\n"
+            "anything else (multi-line FASTQ, malformed records) the host reader takes over from exactly that record, so every output and\n"
+            "every error is what the run without the option gives.  For runs that only count: with -f, -b, -t, --search-depth, --devices,\n"
+            "-F and --lca all.  Not with --pos-filter, --neg-filter, --scores, --lca best, --lca-reads, --reads2, --interleaved,\n"
+            "--abundance, --coverage, --frame or --shard-depth\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"
             "compare -d <DB> -o <OUT> [--against <DB2>] [--min-containment <C>] [--device <N>]: a phage database is full of strains and\n"
             "near-duplicates; this says which of its genomes are related.  For two genomes' filters the set bits and the shared set bits\n"

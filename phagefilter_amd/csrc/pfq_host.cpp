@@ -108,6 +108,7 @@ struct Knobs {
     long long frame_piece = -1;                 // pfq_query_frames: k-mer positions per piece of the refinement (a positive multiple of 64)
     long long sim_slices = -1, sim_naive = -1, sim_time = -1;  // pfq_tree_similarity: slices of the filter words (0 / unset: built-in); 1: the one-block-per-pair kernel; 1: time the kernel
     long long cluster_time = -1;                // pfq_tree_recluster: 1: time the stages with HIP events (pfq_debug_last_recluster)
+    long long text_tile = -1;                   // pfq_text_parse: bytes of text a block scans (a power of two, 256 .. the built-in 8192)
 };
 struct KnobName {
     const char *name;
@@ -139,6 +140,7 @@ const KnobName KNOBS[] = {
     {"PFQ_FRAME_PIECE", &Knobs::frame_piece},
     {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
+    {"PFQ_TEXT_TILE", &Knobs::text_tile},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -400,6 +402,19 @@ struct pfq_tree {
     float cluster_ms[3] = {0.0f, 0.0f, 0.0f};
     uint64_t cluster_nn_bytes = 0;
     uint32_t cluster_rounds = 0;
+    // pfq_text_parse: the text, what the parse kernels leave per tile and per line (scratch of one call: the call waits for its
+    // kernels), and two alternating CSR sets — the classification of pfq_text_query reads set tx_slot while the next parse fills
+    // the other.  tx_free[s]: recorded behind the classification that read set s; tx_parsed: behind the parse kernels.
+    DevBuf<uint8_t> d_tx_text, d_tx_seq[2];
+    DevBuf<uint64_t> d_tx_off[2], d_tx_rec_begin;
+    DevBuf<uint32_t> d_tx_blk, d_tx_line, d_tx_len, d_tx_hdr, d_tx_rec_line, d_tx_bad;
+    DevBuf<unsigned long long> d_tx_blk_off, d_tx_sums, d_tx_dst, d_tx_rec_idx, d_tx_res;
+    unsigned long long *h_tx_res = nullptr;  // page-locked: the result words, the newline count
+    hipEvent_t tx_free[2] = {nullptr, nullptr}, tx_parsed = nullptr;
+    bool tx_used[2] = {false, false}, tx_have = false;
+    int tx_slot = 0;
+    uint64_t tx_records = 0, tx_bases = 0;
+    std::vector<uint64_t> out_rec_begin;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3027,7 +3042,10 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_cov_regs.bytes() + t.d_cov_cnt.bytes() +                                                  // (the coverage sketch)
                         t.d_fr_bytes.bytes() + t.d_fr_foff.bytes() + t.d_fr_seq.bytes() + t.d_fr_start.bytes() + t.d_fr_segpos.bytes() +  // (pfq_query_frames)
                         t.d_fr_cnt.bytes() + t.d_fr_def.bytes() + t.d_fr_seq0.bytes() + t.d_fr_defoff.bytes() + t.d_fr_seqseg.bytes() + t.d_fr_sums.bytes() +
-                        t.d_fr_segs.bytes() + t.d_fr_segseq.bytes() + t.d_fr_queue.bytes() + t.d_fr_pieceoff.bytes() + t.d_fr_parts.bytes() + t.d_fr_misc.bytes();
+                        t.d_fr_segs.bytes() + t.d_fr_segseq.bytes() + t.d_fr_queue.bytes() + t.d_fr_pieceoff.bytes() + t.d_fr_parts.bytes() + t.d_fr_misc.bytes() +
+                        t.d_tx_text.bytes() + t.d_tx_seq[0].bytes() + t.d_tx_seq[1].bytes() + t.d_tx_off[0].bytes() + t.d_tx_off[1].bytes() +  // (pfq_text_parse)
+                        t.d_tx_rec_begin.bytes() + t.d_tx_blk.bytes() + t.d_tx_line.bytes() + t.d_tx_len.bytes() + t.d_tx_hdr.bytes() + t.d_tx_rec_line.bytes() +
+                        t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes();
     return PFQ_OK;
 }
 
@@ -3069,6 +3087,10 @@ void pfq_tree_close(pfq_tree *tree) {
     if (tree->h_pair_cursor) (void)hipHostFree(tree->h_pair_cursor);
     if (tree->hint_ev) (void)hipEventDestroy(tree->hint_ev);
     if (tree->last_done) (void)hipEventDestroy(tree->last_done);
+    for (auto e : tree->tx_free)
+        if (e) (void)hipEventDestroy(e);
+    if (tree->tx_parsed) (void)hipEventDestroy(tree->tx_parsed);
+    if (tree->h_tx_res) (void)hipHostFree(tree->h_tx_res);
     delete tree;
 }
 
@@ -3169,6 +3191,154 @@ int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets
     PFQ_TRY(frames_call(t, (slot ? t.d_seq2 : t.d_seq).p, (slot ? t.d_off2 : t.d_off).p, n_seqs, frame, step, threshold, nullptr, out));
     HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
     t.in_used[slot] = true;
+    return PFQ_OK;
+}
+
+// ---- text ---------------------------------------------------------------------------------------------------------------
+
+static uint32_t text_tile(const Knobs &k) {
+    const long long v = k.text_tile;  // (the environment is not checked when it is read: anything but a power of two in range is the built-in)
+    return (v >= (long long)pfq::TEXT_TILE_MIN && v <= (long long)pfq::TEXT_TILE_DEFAULT && !(v & (v - 1))) ? (uint32_t)v : pfq::TEXT_TILE_DEFAULT;
+}
+
+int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t limit, int format, uint32_t flags, pfq_text *out) {
+    if (!tree || !out || (len && !text)) return fail(PFQ_ERR_ARG, "null argument");
+    if (format != PFQ_TEXT_FASTA && format != PFQ_TEXT_FASTQ) return fail(PFQ_ERR_ARG, "pfq_text_parse: format must be PFQ_TEXT_FASTA or PFQ_TEXT_FASTQ");
+    if (flags & ~(PFQ_TEXT_FINAL | PFQ_TEXT_WANT_RECORDS)) return fail(PFQ_ERR_ARG, "pfq_text_parse: unknown flag bits");
+    if (len >> 31) return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_parse: 2^31 bytes of text or more in one call: ask in pieces");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    const bool fastq = format == PFQ_TEXT_FASTQ, final = (flags & PFQ_TEXT_FINAL) != 0, want_rec = (flags & PFQ_TEXT_WANT_RECORDS) != 0;
+    if (!t.copy_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
+        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (!t.tx_parsed) {
+        HIP_TRY(hipEventCreateWithFlags(&t.tx_parsed, hipEventDisableTiming));
+        for (auto &e : t.tx_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_tx_res), pfq::TEXT_RES_N * 8, hipHostMallocDefault));
+        HIP_TRY(t.d_tx_res.ensure(pfq::TEXT_RES_N));
+        HIP_TRY(t.d_tx_bad.ensure(1));
+    }
+    hipStream_t st = t.copy_stream;
+    const int slot = t.tx_slot ^ 1;
+    if (t.tx_used[slot]) HIP_TRY(hipEventSynchronize(t.tx_free[slot]));  // the classification that read this set is done
+    t.tx_have = false;  // (until this parse has succeeded there is no block to query)
+    const uint32_t n = (uint32_t)len;
+    HIP_TRY(t.d_tx_seq[slot].ensure((size_t)n + 16));
+    out->n_records = out->consumed = out->n_bases = 0;
+    out->stop = PFQ_TEXT_END;
+    out->rec_begin = nullptr;
+    uint32_t n_lines = 0;
+    bool unterminated = false;
+    if (n) {
+        HIP_TRY(t.d_tx_text.ensure(((size_t)n + 15) / 16 * 16 + 16));
+        HIP_TRY(hipMemcpyAsync(t.d_tx_text.p, text, n, hipMemcpyHostToDevice, st));
+        const uint32_t tile = text_tile(t.knobs), n_tiles = (n + tile - 1) / tile;
+        HIP_TRY(t.d_tx_blk.ensure(n_tiles));
+        HIP_TRY(t.d_tx_blk_off.ensure((size_t)n_tiles + 1));
+        HIP_TRY(t.d_tx_sums.ensure((size_t)n_tiles / 4096 + 2));
+        pfq::launch_text_count(t.d_tx_text.p, n, tile, t.d_tx_blk.p, st);
+        pfq::launch_scan_u32(t.d_tx_blk.p, n_tiles, t.d_tx_sums.p, t.d_tx_blk_off.p, st);
+        HIP_TRY(hipMemcpyAsync(t.h_tx_res, t.d_tx_blk_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffer is free from here; the line count sizes what follows)
+        unterminated = final && text[n - 1] != '\n';
+        n_lines = (uint32_t)t.h_tx_res[0] + (unterminated ? 1u : 0u);
+    }
+    // what needs no kernel: empty text; text without a considered line; FASTA that does not begin with a header
+    bool trivial = true;
+    if (!n) out->stop = PFQ_TEXT_END;
+    else if (!fastq && text[0] != '>') out->stop = PFQ_TEXT_SLOW;
+    else if (!n_lines) out->stop = (fastq || limit) ? PFQ_TEXT_MORE : PFQ_TEXT_LIMIT;
+    else trivial = false;
+    const uint64_t max_records = fastq ? n_lines / 4 : n_lines;
+    HIP_TRY(t.d_tx_off[slot].ensure(max_records + 1));
+    if (want_rec) HIP_TRY(t.d_tx_rec_begin.ensure(max_records + 1));
+    if (trivial) {
+        HIP_TRY(hipMemsetAsync(t.d_tx_off[slot].p, 0, 8, st));
+        if (want_rec) t.out_rec_begin.assign(1, 0);
+    } else {
+        HIP_TRY(t.d_tx_line.ensure((size_t)n_lines + 1));
+        HIP_TRY(t.d_tx_len.ensure(n_lines));
+        HIP_TRY(t.d_tx_dst.ensure((size_t)n_lines + 1));
+        HIP_TRY(t.d_tx_sums.ensure((size_t)n_lines / 4096 + 2));
+        pfq::TextArgs a{};
+        a.text = t.d_tx_text.p;
+        a.len = n;
+        a.n_lines = n_lines;
+        a.limit = limit;
+        a.fastq = fastq ? 1 : 0;
+        a.final = final ? 1 : 0;
+        a.line_start = t.d_tx_line.p;
+        a.line_len = t.d_tx_len.p;
+        a.dst = t.d_tx_dst.p;
+        a.first_bad = t.d_tx_bad.p;
+        a.result = t.d_tx_res.p;
+        const uint32_t tile = text_tile(t.knobs);
+        pfq::launch_text_lines(t.d_tx_text.p, n, tile, t.d_tx_blk_off.p, t.d_tx_line.p, n_lines, unterminated, st);
+        if (fastq) {
+            const uint32_t n_full = n_lines / 4;
+            t.h_tx_res[1] = n_full;  // (little-endian: its low word is what is copied; the result lands here only behind this copy)
+            HIP_TRY(hipMemcpyAsync(t.d_tx_bad.p, t.h_tx_res + 1, 4, hipMemcpyHostToDevice, st));
+        } else {
+            HIP_TRY(t.d_tx_hdr.ensure(n_lines));
+            HIP_TRY(t.d_tx_rec_idx.ensure((size_t)n_lines + 1));
+            HIP_TRY(t.d_tx_rec_line.ensure(n_lines));
+            a.rec_idx = t.d_tx_rec_idx.p;
+            a.rec_line = t.d_tx_rec_line.p;
+        }
+        pfq::launch_text_roles(a, t.d_tx_hdr.p, st);
+        pfq::launch_scan_u32(t.d_tx_len.p, n_lines, t.d_tx_sums.p, t.d_tx_dst.p, st);
+        if (!fastq) {
+            pfq::launch_scan_u32(t.d_tx_hdr.p, n_lines, t.d_tx_sums.p, t.d_tx_rec_idx.p, st);
+            pfq::launch_text_rec_lines(t.d_tx_hdr.p, t.d_tx_rec_idx.p, n_lines, t.d_tx_rec_line.p, st);
+        }
+        pfq::launch_text_finish(a, t.d_tx_seq[slot].p, t.d_tx_off[slot].p, want_rec ? t.d_tx_rec_begin.p : nullptr, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(t.h_tx_res, t.d_tx_res.p, pfq::TEXT_RES_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        out->n_records = t.h_tx_res[pfq::TEXT_RES_RECORDS];
+        out->consumed = t.h_tx_res[pfq::TEXT_RES_CONSUMED];
+        out->n_bases = t.h_tx_res[pfq::TEXT_RES_BASES];
+        out->stop = (uint32_t)t.h_tx_res[pfq::TEXT_RES_STOP];
+        if (want_rec) {
+            t.out_rec_begin.resize(out->n_records + 1);
+            HIP_TRY(hipMemcpyAsync(t.out_rec_begin.data(), t.d_tx_rec_begin.p, (out->n_records + 1) * 8, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_TRY(hipEventRecord(t.tx_parsed, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (want_rec) out->rec_begin = t.out_rec_begin.data();
+    t.tx_slot = slot;
+    t.tx_records = out->n_records;
+    t.tx_bases = out->n_bases;
+    t.tx_have = true;
+    return PFQ_OK;
+}
+
+int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(check_flags(*tree, flags, tree->tx_records));
+    if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_text_query before a pfq_text_parse on this tree");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    const int slot = t.tx_slot;
+    HIP_TRY(hipStreamWaitEvent(nullptr, t.tx_parsed, 0));  // (the classification is ordered behind the parse on the device)
+    const int rc = query_device(t, t.d_tx_seq[slot].p, t.d_tx_off[slot].p, t.tx_records, t.tx_bases, threshold, flags, nullptr, hits);
+    HIP_TRY(hipEventRecord(t.tx_free[slot], nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
+    t.tx_used[slot] = true;
+    PFQ_TRY(rc);
+    if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
+    return PFQ_OK;
+}
+
+int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
+    if (!tree || !off_out || (tree->tx_bases && !seq_out)) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_debug_text_csr before a pfq_text_parse on this tree");
+    PFQ_TRY(use_device(tree->device));
+    const pfq_tree &t = *tree;
+    if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_slot].p, t.tx_bases, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_slot].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
     return PFQ_OK;
 }
 
@@ -4145,6 +4315,11 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
             HIP_TRY(hipDeviceSynchronize());
             cover_clear(*tree);  // (made by a call without units: the next flagged call makes it anew)
         }
+    }
+    if (!strcmp(name, "PFQ_TEXT_TILE") && value && *value) {  // the text a block scans: a power of two, at most the built-in
+        const long long v = strtoll(value, nullptr, 10);
+        if (v < (long long)pfq::TEXT_TILE_MIN || v > (long long)pfq::TEXT_TILE_DEFAULT || (v & (v - 1)))
+            return fail(PFQ_ERR_ARG, std::string("PFQ_TEXT_TILE must be a power of two from 256 to 8192, not ") + value);
     }
     if (!strcmp(name, "PFQ_FRAME_PIECE") && value && *value) {  // the windows of a piece are whole: a positive multiple of 64
         const long long v = strtoll(value, nullptr, 10);

@@ -545,6 +545,39 @@ void launch_cluster_list(const uint32_t *d_slot_of, uint32_t n_nodes, const uint
                          hipStream_t st);
 void launch_cluster_merge(unsigned long long *d_S, uint64_t pitch, uint2 *d_meta, uint32_t *d_slot_of, uint32_t n_slots, const ClusterMerge *d_list,
                           uint32_t n_merges, uint32_t first_node, hipStream_t st);
+// pfq_text_parse (pfq_text.hip): plain FASTA / FASTQ text in device memory parsed into the CSR the classifier takes.  d_text is
+// 16-byte aligned and holds 16 bytes beyond len rounded up to 16; len < 2^31.
+//   launch_text_count: d_blk_cnt[b] = newlines of text[b * tile, (b + 1) * tile), b < ceil(len / tile); tile: a power of two from
+//     TEXT_TILE_MIN.  The caller scans them (launch_scan_u32) and reads the total back: the considered lines are the newlines,
+//     plus an unterminated last run with PFQ_TEXT_FINAL.
+//   launch_text_lines: line_start [n_lines + 1]: line i is text[line_start[i], line_start[i + 1] - 1).
+//   launch_text_roles: line_len[i] = the trimmed length of a sequence line, 0 of any other; FASTQ: *first_bad (set to n_lines / 4
+//     by the caller) = the first whole record that is not plain; FASTA: d_is_header[i].  The caller scans line_len into dst and,
+//     FASTA, d_is_header into rec_idx; launch_text_rec_lines then lists the header lines in rec_line.
+//   launch_text_finish: result[TEXT_RES_*] by the rules of pfq.h; d_csr_off[j], j <= records taken; d_rec_begin likewise unless
+//     NULL; the sequence lines of the records taken copied to d_csr_seq.  FASTA: line 0 must be a header.
+constexpr uint32_t TEXT_TILE_MIN = 256, TEXT_TILE_DEFAULT = 8192;
+constexpr uint32_t PFQ_TEXT_STOP_END = 0, PFQ_TEXT_STOP_LIMIT = 1, PFQ_TEXT_STOP_MORE = 2, PFQ_TEXT_STOP_SLOW = 3;  // = PFQ_TEXT_* of pfq.h
+enum TextResult { TEXT_RES_RECORDS = 0, TEXT_RES_CONSUMED = 1, TEXT_RES_BASES = 2, TEXT_RES_STOP = 3, TEXT_RES_LINES = 4, TEXT_RES_N = 8 };
+struct TextArgs {
+    const uint8_t *text;
+    uint32_t len, n_lines;
+    uint64_t limit;
+    int fastq, final;
+    const uint32_t *line_start;            // [n_lines + 1]
+    uint32_t *line_len;                    // [n_lines]
+    const unsigned long long *dst;         // [n_lines + 1] scan of line_len
+    uint32_t *first_bad;                   // FASTQ
+    const unsigned long long *rec_idx;     // FASTA: [n_lines + 1] scan of the header flags
+    const uint32_t *rec_line;              // FASTA: [headers]
+    unsigned long long *result;            // [TEXT_RES_N]
+};
+void launch_text_count(const uint8_t *d_text, uint32_t len, uint32_t tile, uint32_t *d_blk_cnt, hipStream_t st);
+void launch_text_lines(const uint8_t *d_text, uint32_t len, uint32_t tile, const unsigned long long *d_blk_off, uint32_t *d_line_start, uint32_t n_lines,
+                       bool unterminated, hipStream_t st);
+void launch_text_roles(const TextArgs &a, uint32_t *d_is_header, hipStream_t st);
+void launch_text_rec_lines(const uint32_t *d_is_header, const unsigned long long *d_rec_idx, uint32_t n_lines, uint32_t *d_rec_line, hipStream_t st);
+void launch_text_finish(const TextArgs &a, uint8_t *d_csr_seq, uint64_t *d_csr_off, uint64_t *d_rec_begin, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

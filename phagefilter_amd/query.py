@@ -245,6 +245,9 @@ class BloomTree:
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
         _ffi.check(_ffi.lib().pfq_query_batch(self._h, seq.ctypes.data, off.ctypes.data, n, threshold, flags, C.byref(hits)))
+        return self._hits_result(hits, want_hits, want_scores)
+
+    def _hits_result(self, hits: "_ffi.Hits", want_hits: bool, want_scores: bool):
         if not want_hits:
             return None
         n = int(hits.n_reads)
@@ -254,6 +257,44 @@ class BloomTree:
         if not want_scores:
             return offs, leaves
         return offs, leaves, self.last_hit_scores().copy()
+
+    # ---- text
+    def parse_text(self, data: bytes, fmt: str, limit: Optional[int] = None, final: bool = True, want_records: bool = False) -> dict:
+        """Plain FASTA / FASTQ text (`fmt` "fasta" or "fastq") parsed on the device into the block query_text() classifies
+        (pfq_text_parse): data[0] must begin a record's header line.  Records that begin at or beyond `limit` bytes are left
+        (None: no limit); `final`: the text ends where the file ends, so an unterminated last line counts.  Returns n_records,
+        consumed (where the first record not taken begins), n_bases, stop ("end", "limit", "more": the next record is not
+        complete, "slow": it is not an ordinary record, the sequential reader must take over at consumed) and, with
+        `want_records`, rec_begin: uint64[n_records + 1], every taken record's byte offset, then consumed.  No counter changes."""
+        if fmt not in ("fasta", "fastq"):
+            raise ValueError(f"fmt must be 'fasta' or 'fastq', not {fmt!r}")
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = _ffi.Text()
+        flags = (_ffi.TEXT_FINAL if final else 0) | (_ffi.TEXT_WANT_RECORDS if want_records else 0)
+        _ffi.check(_ffi.lib().pfq_text_parse(self._h, buf.ctypes.data if buf.size else None, buf.size, (1 << 64) - 1 if limit is None else limit,
+                                             _ffi.TEXT_FASTQ if fmt == "fastq" else _ffi.TEXT_FASTA, flags, C.byref(out)))
+        self._text_shape = (int(out.n_records), int(out.n_bases))
+        n = int(out.n_records)
+        return {"n_records": n, "consumed": int(out.consumed), "n_bases": int(out.n_bases),
+                "stop": ("end", "limit", "more", "slow")[out.stop],
+                "rec_begin": np.ctypeslib.as_array(out.rec_begin, shape=(n + 1,)).copy() if want_records else None}
+
+    def text_csr(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The block parsed last, copied to the host: (seq uint8[n_bases], off uint64[n_records + 1]) (pfq_debug_text_csr)."""
+        n, nb = getattr(self, "_text_shape", (0, 0))
+        seq, off = np.zeros(nb, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+        _ffi.check(_ffi.lib().pfq_debug_text_csr(self._h, seq.ctypes.data, off.ctypes.data))
+        return seq, off
+
+    def query_text(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
+                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
+        """Classifies the block parse_text() parsed last, exactly as query_packed() classifies the same reads from host memory
+        (pfq_text_query); same keywords, same return value.  May be repeated: the counters grow each time."""
+        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits)
+        hits = _ffi.Hits()
+        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
+        _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
+        return self._hits_result(hits, want_hits, want_scores)
 
     def _segments(self, out: "_ffi.Segments"):
         n = int(out.n_seqs)

@@ -4,6 +4,7 @@ synthetic 150 bp FASTQ (50 % positive) and times the CLI for several worker coun
 and from gzip.  Prints one JSON line per run.
 
     python tools/cli_bench.py [--reads 16000000] [--threads 1,4,16] [--threshold 1.0] [--block 100000] [--workdir /tmp/pfq_cli_bench]
+    python tools/cli_bench.py --device-parse --repeats 3 --only counts --threads 4,16     (A/B of query --device-parse)
 """
 import argparse
 import gzip
@@ -56,7 +57,10 @@ def main():
     ap.add_argument("--leaves", type=int, default=64)
     ap.add_argument("--threshold", default="1.0", help="-f of every query run")
     ap.add_argument("--block", default="100000", help="-b of every query run")
-    ap.add_argument("--only", default="", help="'posneg': only the run with both outputs (environment variables reach the CLI)")
+    ap.add_argument("--only", default="", help="'posneg': only the run with both outputs (environment variables reach the CLI); "
+                    "'counts': only the counts-only runs")
+    ap.add_argument("--device-parse", action="store_true", help="every counts-only run is followed by the same run with query --device-parse")
+    ap.add_argument("--repeats", type=int, default=1, help="how often the counts-only runs (alternating with --device-parse) are repeated")
     ap.add_argument("--devices", default="", help="comma-separated device lists to run as well, ';'-separated (e.g. '0,0' = two replicas on GPU 0)")
     ap.add_argument("--shard-depth", default="", help="the --devices runs split the database into the subtree shards of this depth "
                     "(query --shard-depth) instead of replicating it")
@@ -105,10 +109,11 @@ def main():
         ingest = [l for l in p.stderr.splitlines() if l.startswith("ingest:")]
         outl = [l for l in p.stderr.splitlines() if l.startswith("output:")]
         cpul = [l for l in p.stderr.splitlines() if l.startswith("cpu:")]
+        devl = [l for l in p.stderr.splitlines() if l.startswith("device parse:")]
         csv = open(os.path.join(out, "CLASSIFICATION.csv")).read().splitlines()
         print(json.dumps({"run": label, "threads": threads, "reads": n_reads, "whole_process_s": round(wall, 3),
                           "whole_process_reads_per_s": round(n_reads / wall), "query_loop": loop[0] if loop else None,
-                          "ingest": ingest[0] if ingest else None, "output": outl[0] if outl else None, "cpu": cpul[0] if cpul else None, "classified": sum(int(l.split(",")[1]) for l in csv)}), flush=True)
+                          "ingest": ingest[0] if ingest else None, "output": outl[0] if outl else None, "cpu": cpul[0] if cpul else None, "device_parse": devl[0] if devl else None, "classified": sum(int(l.split(",")[1]) for l in csv)}), flush=True)
 
     tmax = max(int(x) for x in a.threads.split(","))
     if a.only == "posneg":
@@ -117,7 +122,13 @@ def main():
         shutil.rmtree(a.workdir, ignore_errors=True)
         return
     for t in [int(x) for x in a.threads.split(",")]:
-        run("fastq counts-only", fq, a.reads, t)
+        for rep in range(a.repeats):
+            run("fastq counts-only", fq, a.reads, t)
+            if a.device_parse:
+                run("fastq counts-only --device-parse", fq, a.reads, t, ("--device-parse",))
+    if a.only == "counts":
+        shutil.rmtree(a.workdir, ignore_errors=True)
+        return
     run("fastq pos+neg output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter"))
     for devs in [d for d in a.devices.split(";") if d]:
         sh = ("--shard-depth", a.shard_depth) if a.shard_depth else ()
