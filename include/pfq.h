@@ -226,6 +226,93 @@ int pfq_clade_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **bel
  * of that chain.  Library-owned; valid until the next query call on the tree. */
 int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units);
 
+/* ---- taxonomy (PFQ_WANT_TAXA) ----
+ * The tree's topology is an index, not a classification: a taxonomy is a second tree over the same leaves, supplied by the user,
+ * and every node of it gets two exact counts — the units assigned to it, and the units that touch it at all.
+ * A taxonomy of a tree with L current leaves is given as n_taxa >= 1 taxa.
+ *   - Taxon 0 is the root, with parent PFQ_NO_CLADE.
+ *   - taxon_parent[i] < i for i > 0.
+ *   - Every taxon has a name.
+ *   - leaf_taxon[l] < n_taxa is the taxon that genome l sits directly under.
+ *   - l is a leaf index in pfq_leaf_counts order.
+ * The library derives the nodes:
+ *   - Every genome is a node of its own, under its taxon.
+ *   - A taxon with no genome anywhere below it is dropped.  The root is kept.
+ *   - Nodes are numbered in pre-order: first a taxon, then the genomes directly under it in ascending leaf index, then its
+ *     remaining child taxa in ascending input index, each with its subtree.
+ *   - rank[l] is the position of genome l among the genomes in that order (0 .. L - 1).  So every node covers a contiguous
+ *     range of ranks.
+ * pfq_tree_taxa returns, per node, a pfq_taxon: parent, depth, first_rank, n_leaves, leaf (the leaf index of a genome node,
+ * PFQ_NO_CLADE for a taxon), name (a genome node: the leaf's tax_id, as pfq_tree_clades names leaves).
+ * A unit is a read, or with PFQ_PAIRED a fragment.  Its hit set H is exactly the row pfq_hits gives for it in that call; nothing
+ * is decided again.  With PFQ_WANT_HITS an all-leaf unit's row lists all L leaves.  Per unit with H non-empty:
+ *   - taxon(unit) is the deepest node that is an ancestor-or-self of every genome of H.  With H empty it is PFQ_NO_CLADE.
+ *   - here[taxon(unit)] += 1.
+ *   - any[t] += 1 for every node t that is an ancestor-or-self of at least one genome of H, once per unit however many genomes
+ *     of H lie below t.
+ *   - below[t] is the sum of here over t's subtree, derived on the host at read-out as pfq_clade_counts does.
+ * Consequences: a call's increase of any[genome node of l] equals the increase of leaf counter l; any[root] = below[root] is the
+ * number of units that hit anything; any[t] >= below[t] for every t.
+ * All state is integer and is a pure function of the multiset of rows.  It does not depend on call split, replica split, path,
+ * or any knob.
+ *
+ * pfq_tree_set_taxonomy copies everything it needs, builds the node table and uploads the device tables (their bytes count in
+ * pfq_info.device_bytes); it replaces an earlier taxonomy and zeroes the taxon counters.  A violation of the rules above:
+ * PFQ_ERR_ARG; an empty tree: PFQ_ERR_STATE; a subtree shard: PFQ_ERR_UNSUPPORTED (its rows are partial, as for PFQ_WANT_LCA and
+ * PFQ_WANT_ABUNDANCE); a sticky insertion error is returned as by every other call.
+ * pfq_tree_taxa: the node table, library-owned until the taxonomy is set again or dropped; *n = 0 when no taxonomy is set.
+ * PFQ_WANT_TAXA: only together with PFQ_WANT_HITS (alone: PFQ_ERR_ARG — `any` needs whole rows, and the unordered hit pairs of a
+ * counts-only call do not give them); without a taxonomy set: PFQ_ERR_STATE; on a subtree shard: PFQ_ERR_UNSUPPORTED.  It
+ * combines with every other flag and changes none of their results (leaf counters, CSR, scores, LCAs, abundance log, coverage
+ * sketch, pfq_last_stats), and works through pfq_query_batch, pfq_query_batch_device and pfq_text_query; pfq_query_frames keeps
+ * flags == 0.  A block whose hit buffer overflowed and ran again is counted once.
+ * pfq_taxon_counts waits for the device; here, below, any are library-owned [n] and any of the three pointers may be NULL.
+ * pfq_last_taxa: one node index (or PFQ_NO_CLADE) per unit of the last query call on `tree`, which must have set PFQ_WANT_TAXA
+ * (else PFQ_ERR_ARG, as pfq_last_lca); library-owned, valid until the next query call on the tree.
+ * Lifetime: the counters are zeroed by pfq_leaf_counts_reset; pfq_tree_prune and pfq_tree_insert drop the taxonomy itself (the
+ * leaves are no longer the ones it described): afterwards pfq_tree_taxa gives n = 0 and a flagged call PFQ_ERR_STATE until it is
+ * set again.  Nothing of it is stored by pfq_tree_save. */
+#define PFQ_WANT_TAXA 256u
+typedef struct pfq_taxon {
+    uint32_t parent;     /* node index; PFQ_NO_CLADE for the root */
+    uint32_t depth;      /* edges from the root */
+    uint32_t first_rank; /* the node's genomes are ranks [first_rank, first_rank + n_leaves) */
+    uint32_t n_leaves;
+    uint32_t leaf;       /* a genome node: its leaf index in pfq_leaf_counts order; a taxon: PFQ_NO_CLADE */
+    const char *name;
+} pfq_taxon;
+int pfq_tree_set_taxonomy(pfq_tree *tree, uint64_t n_taxa, const uint32_t *taxon_parent, const char *const *taxon_names,
+                          const uint32_t *leaf_taxon);
+int pfq_tree_taxa(pfq_tree *tree, const pfq_taxon **nodes, uint64_t *n);
+int pfq_taxon_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **below, const uint64_t **any, uint64_t *n);
+int pfq_last_taxa(pfq_tree *tree, const uint32_t **node, uint64_t *n_units);
+/* The host side of the same, for tools that check a taxonomy before a device is used.  None of the three touches a device; what
+ * they return is owned by the library per calling thread and valid until that thread calls the same function again.
+ * pfq_db_leaf_ids: the tax_ids of <db_dir>'s leaves in pfq_leaf_counts order, from tree.bin alone (as pfq_db_shard_count reads
+ *   it; PFQ_ERR_IO, PFQ_ERR_FORMAT likewise; an empty tree: n = 0).
+ * pfq_taxonomy_read: a taxonomy file for the leaves named leaf_ids.  Lines end with '\n', a trailing '\r' is dropped; empty
+ *   lines and lines beginning with '#' are skipped.  A line is genome<TAB>lineage[<TAB>ignored...]; fewer than two fields is an
+ *   error.  lineage is a ';'-separated list of names from the top rank down, each trimmed of spaces; an empty lineage means
+ *   directly under the root, an empty name inside a non-empty lineage is an error.  A taxon is identified by its whole path: the
+ *   same name under two parents is two taxa.  Only lines whose genome equals a leaf id are considered (lines_considered; the
+ *   others: lines_other) and every leaf with that id gets the lineage; two considered lines for one genome with different
+ *   lineages is an error.  Taxon indices are assigned in order of first appearance over the considered lines, prefixes left to
+ *   right; the root is taxon 0, named "root".  Leaves without a line sit under the root (leaves_without_line).  An unreadable
+ *   file: PFQ_ERR_IO; an error in it: PFQ_ERR_FORMAT with a message that names the line.
+ * pfq_taxonomy_nodes: the node table pfq_tree_set_taxonomy would derive for leaves named leaf_ids (PFQ_ERR_ARG as there). */
+typedef struct pfq_taxonomy_file {
+    uint64_t n_taxa;
+    const uint32_t *taxon_parent;    /* [n_taxa] */
+    const char *const *taxon_names;  /* [n_taxa] */
+    uint64_t n_leaves;
+    const uint32_t *leaf_taxon;      /* [n_leaves] */
+    uint64_t lines_considered, lines_other, leaves_without_line;
+} pfq_taxonomy_file;
+int pfq_db_leaf_ids(const char *db_dir, const char *const **tax_ids, uint64_t *n_leaves);
+int pfq_taxonomy_read(const char *path, const char *const *leaf_ids, uint64_t n_leaves, pfq_taxonomy_file *out);
+int pfq_taxonomy_nodes(uint64_t n_leaves, const char *const *leaf_ids, uint64_t n_taxa, const uint32_t *taxon_parent,
+                       const char *const *taxon_names, const uint32_t *leaf_taxon, const pfq_taxon **nodes, uint64_t *n);
+
 /* ---- abundance (PFQ_WANT_ABUNDANCE) ----
  * The log holds, per unit of every PFQ_WANT_ABUNDANCE call since it was last cleared, the unit's row, by class (L = n_leaves):
  * empty: n_unhit; one leaf l: unique[l]; L > 1 and all L leaves (units without k-mers, threshold <= 0, all-leaf fragments — the

@@ -15,6 +15,7 @@ SYMBOLS = [
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
+    "pfq_tree_set_taxonomy", "pfq_tree_taxa", "pfq_taxon_counts", "pfq_last_taxa", "pfq_db_leaf_ids", "pfq_taxonomy_read", "pfq_taxonomy_nodes",
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
@@ -66,6 +67,17 @@ class Clade(C.Structure):
                 ("name", C.c_char_p)]
 
 
+class Taxon(C.Structure):
+    _fields_ = [("parent", C.c_uint32), ("depth", C.c_uint32), ("first_rank", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("leaf", C.c_uint32), ("name", C.c_char_p)]
+
+
+class TaxonomyFile(C.Structure):
+    _fields_ = [("n_taxa", C.c_uint64), ("taxon_parent", C.POINTER(C.c_uint32)), ("taxon_names", C.POINTER(C.c_char_p)),
+                ("n_leaves", C.c_uint64), ("leaf_taxon", C.POINTER(C.c_uint32)), ("lines_considered", C.c_uint64),
+                ("lines_other", C.c_uint64), ("leaves_without_line", C.c_uint64)]
+
+
 class Abundance(C.Structure):
     _fields_ = [("n_leaves", C.c_uint64), ("mass", C.POINTER(C.c_uint64)), ("unique", C.POINTER(C.c_uint64)),
                 ("n_units", C.c_uint64), ("n_unhit", C.c_uint64), ("n_unique", C.c_uint64), ("n_ambiguous", C.c_uint64),
@@ -115,6 +127,7 @@ LCA_BEST = 32
 WANT_ABUNDANCE = 64
 ABUND_Q = 16
 WANT_COVERAGE = 128
+WANT_TAXA = 256
 NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
@@ -163,6 +176,15 @@ def lib() -> C.CDLL:
     L.pfq_tree_clades.argtypes = [vp, C.POINTER(C.POINTER(Clade)), u64p]
     L.pfq_clade_counts.argtypes = [vp, C.POINTER(u64p), C.POINTER(u64p), u64p]
     L.pfq_last_lca.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), u64p]
+    u32p = C.POINTER(C.c_uint32)
+    L.pfq_tree_set_taxonomy.argtypes = [vp, C.c_uint64, vp, C.POINTER(C.c_char_p), vp]
+    L.pfq_tree_taxa.argtypes = [vp, C.POINTER(C.POINTER(Taxon)), u64p]
+    L.pfq_taxon_counts.argtypes = [vp, C.POINTER(u64p), C.POINTER(u64p), C.POINTER(u64p), u64p]
+    L.pfq_last_taxa.argtypes = [vp, C.POINTER(u32p), u64p]
+    L.pfq_db_leaf_ids.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_char_p)), u64p]
+    L.pfq_taxonomy_read.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(TaxonomyFile)]
+    L.pfq_taxonomy_nodes.argtypes = [C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, vp, C.POINTER(C.c_char_p), vp,
+                                     C.POINTER(C.POINTER(Taxon)), u64p]
     L.pfq_abundance_estimate.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(Abundance)]
     L.pfq_abundance_reset.argtypes = [vp]
     L.pfq_abundance_absorb.argtypes = [vp, vp]

@@ -1205,6 +1205,67 @@ struct ServedDb {
         }
         if (fclose(f) != 0) die("short write to " + tsv);
     }
+    // --taxonomy: the file read for the current leaves (after --search-depth pruned them) and laid over every replica; the node
+    // names (READ_TAXA.tsv) from replica 0.  The file's lines for other genomes and the leaves without a line go to stderr.
+    std::vector<std::string> taxon_names;
+    void set_taxonomy(const std::string &file) {
+        std::vector<const char *> ids;
+        for (const std::string &s : leaf_names) ids.push_back(s.c_str());
+        pfq_taxonomy_file tf{};
+        check(pfq_taxonomy_read(file.c_str(), ids.data(), ids.size(), &tf));
+        fprintf(stderr, "taxonomy: %llu taxa from %llu lines; %llu lines for genomes that are not in the database; %llu of %llu genomes without a line sit under the root\n",
+                (unsigned long long)tf.n_taxa, (unsigned long long)tf.lines_considered, (unsigned long long)tf.lines_other,
+                (unsigned long long)tf.leaves_without_line, (unsigned long long)tf.n_leaves);
+        for (pfq_tree *t : trees) check(pfq_tree_set_taxonomy(t, tf.n_taxa, tf.taxon_parent, tf.taxon_names, tf.leaf_taxon));
+        const pfq_taxon *tx = nullptr;
+        uint64_t n = 0;
+        check(pfq_tree_taxa(trees[0], &tx, &n));
+        for (uint64_t v = 0; v < n; ++v) taxon_names.push_back(tx[v].name);
+    }
+    // --taxonomy: TAXON_COUNTS.tsv.  Every replica counted its own reads: their `here` and `any` are summed on the host and `below`
+    // is the sum of `here` over each node's subtree (pre-order: children come after their parent).  with_abundance: one more column,
+    // the EM masses (replica 0's log, merged by save_abundance before) of the genomes below the node.
+    void save_taxon_counts(const std::string &tsv, bool with_abundance, uint32_t max_iters) {
+        const pfq_taxon *tx = nullptr;
+        uint64_t n = 0;
+        check(pfq_tree_taxa(trees[0], &tx, &n));
+        std::vector<uint64_t> here(n, 0), any(n, 0);
+        for (pfq_tree *t : trees) {
+            const uint64_t *h = nullptr, *a = nullptr;
+            uint64_t nh = 0;
+            check(pfq_taxon_counts(t, &h, nullptr, &a, &nh));
+            if (nh != n) die("--taxonomy: the replicas' node tables differ");
+            for (uint64_t v = 0; v < n; ++v) {
+                here[v] += h[v];
+                any[v] += a[v];
+            }
+        }
+        std::vector<uint64_t> below(here), mass(n, 0);
+        for (uint64_t v = n; v-- > 1;) below[tx[v].parent] += below[v];
+        if (with_abundance) {
+            pfq_abundance ab{};
+            check(pfq_abundance_estimate(trees[0], max_iters, 65, &ab));
+            for (uint64_t v = 0; v < n; ++v)
+                if (tx[v].leaf != PFQ_NO_CLADE) mass[v] = ab.mass[tx[v].leaf];
+            for (uint64_t v = n; v-- > 1;) mass[tx[v].parent] += mass[v];
+        }
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+        fprintf(f, "#node\tparent\tdepth\tkind\tgenomes\tname\treads_here\treads_below\treads_any%s\n", with_abundance ? "\testimated" : "");
+        for (uint64_t v = 0; v < n; ++v) {
+            if (!any[v]) continue;
+            const std::string parent = tx[v].parent == PFQ_NO_CLADE ? "-" : std::to_string(tx[v].parent);
+            fprintf(f, "%llu\t%s\t%u\t%s\t%u\t%s\t%llu\t%llu\t%llu", (unsigned long long)v, parent.c_str(), tx[v].depth,
+                    tx[v].leaf == PFQ_NO_CLADE ? "taxon" : "genome", tx[v].n_leaves, tx[v].name, (unsigned long long)here[v],
+                    (unsigned long long)below[v], (unsigned long long)any[v]);
+            if (with_abundance) {
+                const unsigned __int128 milli = ((unsigned __int128)mass[v] * 1000 + 32768) >> 16;
+                fprintf(f, "\t%llu.%03llu", (unsigned long long)(milli / 1000), (unsigned long long)(milli % 1000));
+            }
+            fputc('\n', f);
+        }
+        if (fclose(f) != 0) die("short write to " + tsv);
+    }
     // --coverage: the precision of every replica's (shard's) sketch, before the first call makes it
     void set_coverage_precision(const std::string &p) {
         for (pfq_tree *t : trees) check(pfq_set_option(t, "PFQ_COVER_P", p.c_str()));
@@ -1249,7 +1310,9 @@ struct Outputs {
     OutFile pos, neg, pos2, neg2;  // --reads2: the mates of R2 go to POS_FILTERING_2 / NEG_FILTERING_2, those of R1 to _1
     FILE *scores = nullptr;        // --scores: READ_SCORES.tsv
     FILE *lca = nullptr;           // --lca-reads: READ_LCA.tsv
-    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores, bool want_lca_reads) {
+    FILE *taxa = nullptr;          // --taxon-reads: READ_TAXA.tsv
+    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores, bool want_lca_reads,
+            bool want_taxon_reads = false) {
         auto create = [&](OutFile &f, const std::string &name, const char *suffix) {
             if ((f.fd = open((dir + "/" + name + suffix + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
                 die("cannot create " + name + " in " + dir);
@@ -1267,12 +1330,17 @@ struct Outputs {
             if (!(lca = fopen((dir + "/READ_LCA.tsv").c_str(), "wb"))) die("cannot create READ_LCA.tsv in " + dir);
             fputs("#read_id\thits\tclade\tname\n", lca);
         }
+        if (want_taxon_reads) {
+            if (!(taxa = fopen((dir + "/READ_TAXA.tsv").c_str(), "wb"))) die("cannot create READ_TAXA.tsv in " + dir);
+            fputs("#read_id\thits\tnode\tname\n", taxa);
+        }
     }
     void close() {
         for (OutFile *f : {&pos, &neg, &pos2, &neg2})
             if (f->fd >= 0) ::close(f->fd);
         if (scores && fclose(scores) != 0) die("short write to READ_SCORES.tsv");
         if (lca && fclose(lca) != 0) die("short write to READ_LCA.tsv");
+        if (taxa && fclose(taxa) != 0) die("short write to READ_TAXA.tsv");
     }
 };
 
@@ -1282,12 +1350,14 @@ struct Hits {
     std::vector<uint64_t> off;
     std::vector<uint32_t> leaves, scores;
     std::vector<uint32_t> lca;       // --lca-reads: the unit's clade (PFQ_NO_CLADE: no hit)
+    std::vector<uint32_t> taxa;      // --taxon-reads: the unit's node of the taxonomy (PFQ_NO_CLADE: no hit)
     std::vector<uint64_t> call_off;  // the call's read offsets, when its range does not start at the batch's first read
 };
 // Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
 // scores; keep_lca: the units' LCAs of a PFQ_WANT_LCA call) are copied out of the library's buffers, which the next call on
 // the tree reuses, into h.
-void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h, bool keep_lca = false) {
+void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h, bool keep_lca = false,
+              bool keep_taxa = false) {
     const bool want = (flags & PFQ_WANT_HITS) != 0;
     const uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
     if (want) {
@@ -1295,6 +1365,7 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         h.leaves.clear();
         h.scores.clear();
         h.lca.clear();
+        h.taxa.clear();
     }
     if (r1 == r0) return;
     const uint64_t *off = b.off.data();
@@ -1321,6 +1392,12 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         if (pfq_last_lca(tree, &lca, &n_lca) != PFQ_OK) fail_from_thread(pfq_last_error());
         h.lca.assign(lca, lca + n_lca);
     }
+    if (keep_taxa) {
+        const uint32_t *node = nullptr;
+        uint64_t n_node = 0;
+        if (pfq_last_taxa(tree, &node, &n_node) != PFQ_OK) fail_from_thread(pfq_last_error());
+        h.taxa.assign(node, node + n_node);
+    }
 }
 // The trees' hit lists of n units in the whole tree's leaf order.  Part i covers units [n i / P, n (i + 1) / P) for a
 // replica (the shares follow one another) and all of them for a shard (per unit, the shards' lists in shard order, each
@@ -1332,13 +1409,15 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
         return;
     }
     uint64_t total = 0;
-    bool with_scores = false, with_lca = false;
+    bool with_scores = false, with_lca = false, with_taxa = false;
     for (const Hits &h : parts) {
         total += h.leaves.size();
         with_scores |= !h.scores.empty();
         with_lca |= !h.lca.empty();
+        with_taxa |= !h.taxa.empty();
     }
     out.lca.assign(with_lca ? n : 0, PFQ_NO_CLADE);  // (replicas only: --lca does not serve shards)
+    out.taxa.assign(with_taxa ? n : 0, PFQ_NO_CLADE);  // (replicas only, likewise)
     out.off.assign(n + 1, 0);
     out.leaves.resize(total);
     out.scores.resize(with_scores ? total : 0);
@@ -1352,6 +1431,7 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
             const uint32_t base = db.sharded ? (uint32_t)db.leaf_base[i] : 0u;
             if (with_scores) std::copy(h.scores.begin() + j0, h.scores.begin() + j1, out.scores.begin() + at);
             if (with_lca) out.lca[u] = h.lca[u - u0];
+            if (with_taxa) out.taxa[u] = h.taxa[u - u0];
             for (uint64_t j = j0; j < j1; ++j) out.leaves[at++] = h.leaves[j] + base;
         }
         out.off[u + 1] = at;
@@ -1434,7 +1514,7 @@ void put_scores(std::string &o, std::string_view id, uint64_t kmers, const uint3
     }
 }
 
-// READ_LCA.tsv line of a record (or fragment) with hits: "id\thits\tclade\tname"
+// READ_LCA.tsv (READ_TAXA.tsv) line of a record (or fragment) with hits: "id\thits\tclade\tname" (the node of the taxonomy and its name)
 void put_lca(std::string &o, std::string_view id, uint64_t n_hits, uint32_t clade, const std::vector<std::string> &clade_names) {
     char num[64];
     o.append(id.data(), id.size());
@@ -1457,7 +1537,12 @@ struct QueryLoop {
     const bool lca_reads = false;  // --lca-reads: READ_LCA.tsv
     const bool abundance = false;  // --abundance: every call asks for the hits and logs their rows
     const bool coverage = false;   // --coverage: every call asks for the hits and sketches the listed genomes' matched k-mers
-    uint32_t abundance_flags() const { return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u); }
+    const bool taxonomy = false;   // --taxonomy: every call asks for the hits and counts its units on the taxonomy's nodes
+    const bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv
+    uint32_t abundance_flags() const {
+        return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
+               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u);
+    }
     uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
 
@@ -1473,7 +1558,7 @@ struct QueryLoop {
     // calls want counts only.
     void paired(ReadQueue *rq2, bool both) {
         const uint64_t batch_frags = batch_size(1u << 19);
-        const bool per_read = pos || neg || scores || lca_reads;
+        const bool per_read = pos || neg || scores || lca_reads || taxon_reads;
         const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags() |
                                abundance_flags();
         PairSource src{rq, rq2, {}, {}, 0, {}, false};
@@ -1481,7 +1566,7 @@ struct QueryLoop {
         std::vector<Hits> parts(n_trees());
         Hits f;  // the fragments' lists in the whole tree's leaf order
         OutBuf pos_out, neg_out, pos2_out, neg2_out;
-        std::string sc_out, lca_out;
+        std::string sc_out, lca_out, taxa_out;
         std::vector<uint64_t> order;
         bool more = true;
         while (more) {
@@ -1494,7 +1579,7 @@ struct QueryLoop {
             fan_out(n_trees(), [&](size_t i) {
                 const size_t P = n_trees();
                 const uint64_t f0 = db.sharded ? 0 : nf * i / P, f1 = db.sharded ? nf : nf * (i + 1) / P;
-                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads);
+                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads, taxon_reads);
             });
             ns_gpu += ReadQueue::now_ns() - tq0;
             n_total += n;
@@ -1525,6 +1610,12 @@ struct QueryLoop {
                 for (uint64_t fr = 0; fr < nf; ++fr)
                     if (f.off[fr] != f.off[fr + 1]) put_lca(lca_out, b.id(2 * fr), f.off[fr + 1] - f.off[fr], f.lca[fr], db.clade_names);
                 if (!lca_out.empty() && fwrite(lca_out.data(), 1, lca_out.size(), out.lca) != lca_out.size()) die("short write to READ_LCA.tsv");
+            }
+            if (taxon_reads) {
+                taxa_out.clear();
+                for (uint64_t fr = 0; fr < nf; ++fr)
+                    if (f.off[fr] != f.off[fr + 1]) put_lca(taxa_out, b.id(2 * fr), f.off[fr + 1] - f.off[fr], f.taxa[fr], db.taxon_names);
+                if (!taxa_out.empty() && fwrite(taxa_out.data(), 1, taxa_out.size(), out.taxa) != taxa_out.size()) die("short write to READ_TAXA.tsv");
             }
             out.pos.append(pos_out.p, pos_out.n);
             out.neg.append(neg_out.p, neg_out.n);
@@ -1861,7 +1952,7 @@ struct QueryLoop {
                     if (past_end(k)) return;
                 }
                 const uint64_t n = s->b.n(), tq0 = ReadQueue::now_ns();
-                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads);
+                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads, taxon_reads);
                 if (n) {
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     if (!db.sharded || i == 0) n_total += n;
@@ -2080,6 +2171,17 @@ struct QueryLoop {
                     for (const std::string &p : parts)
                         if (!p.empty() && fwrite(p.data(), 1, p.size(), out.lca) != p.size()) fail_from_thread("short write to READ_LCA.tsv");
                 }
+                if (taxon_reads) {
+                    // READ_TAXA.tsv: per record with hits, the size of its hit set and its node of the taxonomy
+                    std::vector<std::string> parts(nw);
+                    const uint32_t *h_taxa = s.hits.taxa.data();
+                    fan_out(nw, [&](size_t w) {
+                        for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r)
+                            if (h_off[r] != h_off[r + 1]) put_lca(parts[w], b.id(r), h_off[r + 1] - h_off[r], h_taxa[r], db.taxon_names);
+                    });
+                    for (const std::string &p : parts)
+                        if (!p.empty() && fwrite(p.data(), 1, p.size(), out.taxa) != p.size()) fail_from_thread("short write to READ_TAXA.tsv");
+                }
                 const uint64_t t1 = ReadQueue::now_ns();
                 ns_fmt += t1 - t0;
                 // the bytes: batches come in input order, so a part's place is the sum of what lies before it
@@ -2125,7 +2227,8 @@ int cmd_query(int argc, char **argv) {
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
-                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}};
+                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"taxonomy", 0, true},
+                             {"taxon-reads", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2203,7 +2306,26 @@ int cmd_query(int argc, char **argv) {
             if (a.val.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
         if (lca == 2) die("error: '--device-parse' cannot be used with '--lca best': the best hits need every read's scores");
     }
-    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage;  // the per-read hit lists are needed
+    // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
+    // (PFQ_WANT_HITS | PFQ_WANT_TAXA): TAXON_COUNTS.tsv; --taxon-reads: READ_TAXA.tsv, one line per record with hits.  The file is
+    // parsed and checked against tree.bin here, before any device is used.
+    const bool taxonomy = a.val.count("taxonomy") != 0;
+    const bool taxon_reads = a.flags.count("taxon-reads") != 0;
+    if (taxon_reads && !taxonomy) die("error: '--taxon-reads' needs '--taxonomy <FILE>'");
+    if (taxonomy) {
+        for (const char *other : {"shard-depth", "frame"})
+            if (a.val.count(other))
+                die(std::string("error: '--taxonomy' cannot be used with '--") + other + "'" +
+                    (other[0] == 's' ? ": a subtree shard sees only its own genomes, so the hit rows it would count are partial (not implemented)"
+                                     : ": frames do not combine with per-read post-stages"));
+        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--taxonomy': it serves runs that only count");
+        const char *const *ids = nullptr;
+        uint64_t n_ids = 0;
+        check(pfq_db_leaf_ids(db_path.c_str(), &ids, &n_ids));
+        pfq_taxonomy_file tf{};
+        check(pfq_taxonomy_read(a.val.at("taxonomy").c_str(), ids, n_ids, &tf));
+    }
+    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage || taxonomy;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
@@ -2272,7 +2394,7 @@ int cmd_query(int argc, char **argv) {
     struct stat st;
     if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
     mkdir(out.c_str(), 0777);
-    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads);
+    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads, taxon_reads);
     uint64_t kmer_size = 0;
     if (scores || framed) {
         pfq_info info{};
@@ -2283,9 +2405,10 @@ int cmd_query(int argc, char **argv) {
         die("error: '--frame " + std::to_string(frame) + "' is shorter than the database's k-mers (k = " + std::to_string(kmer_size) + "): a frame must hold one");
     db.load_leaf_names();
     if (lca_reads) db.load_clade_names();
+    if (taxonomy) db.set_taxonomy(a.val.at("taxonomy"));
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads};
     if (block == 0) {
         // nothing to do: see above
     } else if (framed) {
@@ -2317,6 +2440,7 @@ int cmd_query(int argc, char **argv) {
     if (lca) db.save_clade_counts(out + "/CLADE_COUNTS.tsv");
     if (abundance) db.save_abundance(out + "/ABUNDANCE.tsv", (uint32_t)abundance_iters);
     if (coverage) db.save_coverage(out + "/COVERAGE.tsv");
+    if (taxonomy) db.save_taxon_counts(out + "/TAXON_COUNTS.tsv", abundance, (uint32_t)abundance_iters);
     db.close();
     printf("Finished.\n");
     return 0;
@@ -2693,6 +2817,38 @@ int cmd_compare(int argc, char **argv) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// taxonomy: the node table a taxonomy file gives over a database's genomes (tree.bin and the file only: no device)
+// ---------------------------------------------------------------------------------------------------------------
+int cmd_taxonomy(int argc, char **argv) {
+    std::vector<Opt> opts = {{"db-path", 'd', true}, {"taxonomy", 0, true}, {"out", 'o', true}};
+    Args a = parse(argc, argv, 2, opts);
+    const std::string db_path = req(a, "db-path"), file = req(a, "taxonomy"), out = req(a, "out");
+    const char *const *ids = nullptr;
+    uint64_t n_ids = 0;
+    check(pfq_db_leaf_ids(db_path.c_str(), &ids, &n_ids));
+    pfq_taxonomy_file tf{};
+    check(pfq_taxonomy_read(file.c_str(), ids, n_ids, &tf));
+    fprintf(stderr, "taxonomy: %llu taxa from %llu lines; %llu lines for genomes that are not in the database; %llu of %llu genomes without a line sit under the root\n",
+            (unsigned long long)tf.n_taxa, (unsigned long long)tf.lines_considered, (unsigned long long)tf.lines_other,
+            (unsigned long long)tf.leaves_without_line, (unsigned long long)tf.n_leaves);
+    const pfq_taxon *tx = nullptr;
+    uint64_t n = 0;
+    check(pfq_taxonomy_nodes(n_ids, ids, tf.n_taxa, tf.taxon_parent, tf.taxon_names, tf.leaf_taxon, &tx, &n));
+    mkdir(out.c_str(), 0777);
+    const std::string tsv = out + "/TAXA.tsv";
+    FILE *f = fopen(tsv.c_str(), "wb");
+    if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+    fputs("#node\tparent\tdepth\tkind\tgenomes\tname\n", f);
+    for (uint64_t v = 0; v < n; ++v) {
+        const std::string parent = tx[v].parent == PFQ_NO_CLADE ? "-" : std::to_string(tx[v].parent);
+        fprintf(f, "%llu\t%s\t%u\t%s\t%u\t%s\n", (unsigned long long)v, parent.c_str(), tx[v].depth, tx[v].leaf == PFQ_NO_CLADE ? "taxon" : "genome",
+                tx[v].n_leaves, tx[v].name);
+    }
+    if (fclose(f) != 0) die("short write to " + tsv);
+    return 0;
+}
+
 void usage() {
     std::string header_cols(SIMILARITY_HEADER);  // the column line as the file has it, tabs spelt out
     header_cols.pop_back();
@@ -2708,6 +2864,7 @@ void usage() {
             "  add             Adds genomes to an already built BloomFilter.\n"
             "  compare         Says which genomes of a database are related, and how closely, from their Bloom filters\n"
             "  recluster       Writes a database with the same genomes under a tree rebuilt by their similarity\n"
+            "  taxonomy        Checks a taxonomy file against a database and writes the node table it gives (no GPU)\n"
             "  build-balanced  Builds a balanced synthetic BloomTree on the GPU (benchmark databases)\n"
             "  ingest-check    Parses reads like `query` and prints what was read (no GPU)\n\n"
             "query takes the reference's options, plus --devices <0,1,..|all>: one replica of the database per GPU, reads\n"
@@ -2770,6 +2927,23 @@ void usage() {
             "every error is what the run without the option gives.  For runs that only count: with -f, -b, -t, --search-depth, --devices,\n"
             "-F and --lca all.  Not with --pos-filter, --neg-filter, --scores, --lca best, --lca-reads, --reads2, --interleaved,\n"
             "--abundance, --coverage, --frame or --shard-depth\n"
+            "--taxonomy <FILE>: the tree's shape is an index, not a classification; this lays a taxonomy of your own over the database's\n"
+            "genomes and counts the reads (paired input: fragments) at every rank.  FILE has one line per genome, \"genome<TAB>lineage\",\n"
+            "the lineage a ';'-separated list of names from the top rank down (\"Caudoviricetes;Autographiviridae;Teseptimavirus\"; empty:\n"
+            "directly under the root; further columns are ignored, as are empty lines and lines that begin with #).  A taxon is its whole\n"
+            "path.  Lines for genomes that are not in the database are skipped and genomes without a line sit under the root; both are\n"
+            "counted on stderr.  The file is checked before any GPU is used; an error names its line.  TAXON_COUNTS.tsv in --out:\n"
+            "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name<TAB>reads_here<TAB>reads_below<TAB>reads_any\", one line per node with\n"
+            "reads_any > 0, nodes in pre-order, every genome a node (kind genome) under its taxon (kind taxon).  reads_here: reads whose\n"
+            "genomes all lie under this node and under no deeper one (Kraken's clade report); reads_below: the sum of that over the node's\n"
+            "subtree; reads_any: reads with at least one genome under the node, each counted once — what CLASSIFICATION.csv means, at every\n"
+            "rank (for a genome line it is that file's count).  With --abundance one more column, estimated: the sum of ABUNDANCE.tsv's\n"
+            "estimates over the genomes under the node.  Every query call then asks the library for the hit lists, as with --abundance.\n"
+            "The other outputs stay as they are.  With --devices the replicas' counts are summed.  Not with --shard-depth, --frame or\n"
+            "--device-parse.  --taxon-reads (needs --taxonomy): also write READ_TAXA.tsv, one line per record with hits in input order\n"
+            "(per fragment: R1's id): \"#read_id<TAB>hits<TAB>node<TAB>name\"\n"
+            "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
+            "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"
             "compare -d <DB> -o <OUT> [--against <DB2>] [--min-containment <C>] [--device <N>]: a phage database is full of strains and\n"
             "near-duplicates; this says which of its genomes are related.  For two genomes' filters the set bits and the shared set bits\n"
@@ -2813,6 +2987,7 @@ int main(int argc, char **argv) {
     if (cmd == "add") return cmd_add((int)av.size(), av.data());
     if (cmd == "compare") return cmd_compare((int)av.size(), av.data());
     if (cmd == "recluster") return cmd_recluster((int)av.size(), av.data());
+    if (cmd == "taxonomy") return cmd_taxonomy((int)av.size(), av.data());
     usage();
     return 2;
 }

@@ -24,6 +24,7 @@
 
 #include "../../include/pfq.h"
 #include "pfq_kernels.h"
+#include "pfq_taxonomy.h"
 
 namespace {
 
@@ -418,6 +419,18 @@ struct pfq_tree {
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
+    // PFQ_WANT_TAXA: the user's taxonomy over the current leaves (pfq_tree_set_taxonomy): the node table, its device tables
+    // (pfq_kernels.h TaxTables) and the counters d_tax_here / d_tax_any [n_nodes], d_tax_misc [TAX_MISC_N: units with a hit,
+    // all-leaf units — applied at read-out] and d_tax_cur [1: the queue cursor of a call's long rows].  Dropped by tax_clear.
+    bool tax_set = false;
+    pfq_taxonomy::NodeTable tax;
+    uint32_t tax_hot[pfq::TAX_HOT] = {PFQ_NO_CLADE, PFQ_NO_CLADE, PFQ_NO_CLADE, PFQ_NO_CLADE};
+    DevBuf<uint32_t> d_tax_rank, d_tax_leaf_node, d_tax_parent, d_tax_first, d_tax_gap_min, d_tax_node, d_tax_long;
+    DevBuf<unsigned long long> d_tax_here, d_tax_any, d_tax_misc, d_tax_cur;
+    std::vector<uint64_t> out_tax_here, out_tax_below, out_tax_any;
+    std::vector<uint32_t> out_tax_node;
+    bool taxa_last = false;                // the last query call set PFQ_WANT_TAXA
+    uint64_t taxa_units = 0;
 };
 
 namespace {
@@ -1104,6 +1117,23 @@ int abund_shard_refused() {
                                      "are partial");
 }
 
+// ---- PFQ_WANT_TAXA: the user's taxonomy (pfq_tree::tax, d_tax_*) ----
+// Drops the taxonomy and gives its tables back (hipFree waits for the device): the leaves are no longer the ones it described.
+void tax_clear(pfq_tree &t) {
+    for (DevBuf<uint32_t> *b : {&t.d_tax_rank, &t.d_tax_leaf_node, &t.d_tax_parent, &t.d_tax_first, &t.d_tax_gap_min}) b->release();
+    for (DevBuf<unsigned long long> *b : {&t.d_tax_here, &t.d_tax_any, &t.d_tax_misc}) b->release();
+    t.tax = pfq_taxonomy::NodeTable();
+    t.tax_set = false;
+}
+int tax_zero(pfq_tree &t) {
+    if (!t.tax_set) return PFQ_OK;
+    HIP_TRY(hipMemset(t.d_tax_here.p, 0, t.tax.nodes.size() * 8));
+    HIP_TRY(hipMemset(t.d_tax_any.p, 0, t.tax.nodes.size() * 8));
+    HIP_TRY(hipMemset(t.d_tax_misc.p, 0, pfq::TAX_MISC_N * 8));
+    return PFQ_OK;
+}
+static_assert(pfq::TAX_NO_NODE == PFQ_NO_CLADE, "pfq.h and pfq_kernels.h disagree about \"no node\"");
+
 // ---- PFQ_WANT_COVERAGE: the per-leaf sketches (pfq_tree::d_cov_*) ----
 // The precision a new sketch gets: the option PFQ_COVER_P where it is in range (pfq_set_option refuses other values; one from
 // the environment that is out of range counts as unset).
@@ -1239,7 +1269,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
@@ -1277,6 +1307,9 @@ struct QueryRun {
         lca_best = (flags & PFQ_LCA_BEST) != 0;
         want_abund = (flags & PFQ_WANT_ABUNDANCE) != 0;
         want_cover = (flags & PFQ_WANT_COVERAGE) != 0;
+        want_taxa = (flags & PFQ_WANT_TAXA) != 0;
+        if (want_taxa && (!t.tax_set || t.tax.rank.size() != t.leaves.size()))
+            return fail(PFQ_ERR_STATE, "PFQ_WANT_TAXA without a taxonomy: pfq_tree_set_taxonomy first (pfq_tree_prune and pfq_tree_insert drop it)");
         if (want_lca) PFQ_TRY(ensure_lca(t));
         want_hits = user_hits || paired || want_lca;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
@@ -2056,6 +2089,7 @@ struct QueryRun {
         }
         if (want_lca && off) PFQ_TRY(lca_rows(off, leaves, n_units, pair_mode));
         if (want_cover) PFQ_TRY(cover_sketch(off, leaves, n_units, total, pair_mode));
+        if (want_taxa && off) PFQ_TRY(tax_rows(off, leaves, n_units));
         if (total) HIP_TRY(hipStreamSynchronize(st));
         if (want_scores) {
             t.scores_valid = true;
@@ -2076,6 +2110,31 @@ struct QueryRun {
         const pfq::CoverArgs cv{t.d_cov_regs.p, t.d_cov_cnt.p, t.d_cov_cnt.p + nl, (uint32_t)nl, t.cov_p};
         const uint32_t blocks = kn.cover_blocks > 0 ? (uint32_t)std::min<long long>(kn.cover_blocks, 65535) : 0;
         pfq::launch_cover_sketch(t.hp, d_seq, d_off, n_units, threshold, pair_mode, off, leaves, t.d_col_row.p, t.d_bits.p, t.n_words, cv, blocks, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
+    }
+
+    // PFQ_WANT_TAXA: the rows of the call's final CSR are counted on the taxonomy's nodes, once: deliver_rows() runs for the attempt
+    // that stands.  Queued before deliver_rows' wait; rows without entries count nowhere (d_tax_node keeps PFQ_NO_CLADE).
+    int tax_rows(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units) {
+        if (!n_units) return PFQ_OK;
+        HIP_TRY(t.d_tax_long.ensure(n_units));
+        HIP_TRY(t.d_tax_cur.ensure(1));
+        HIP_TRY(hipMemsetAsync(t.d_tax_cur.p, 0, 8, st));
+        pfq::TaxTables tb{};
+        tb.n_leaves = (uint32_t)nl;
+        tb.n_nodes = (uint32_t)t.tax.nodes.size();
+        tb.top_node = t.tax.top;
+        for (uint32_t k = 0; k < pfq::TAX_HOT; ++k) tb.hot[k] = t.tax_hot[k];
+        tb.rank = t.d_tax_rank.p;
+        tb.leaf_node = t.d_tax_leaf_node.p;
+        tb.parent = t.d_tax_parent.p;
+        tb.first_rank = t.d_tax_first.p;
+        tb.gap_min = t.d_tax_gap_min.p;
+        tb.here = t.d_tax_here.p;
+        tb.any = t.d_tax_any.p;
+        tb.misc = t.d_tax_misc.p;
+        pfq::launch_tax_rows(off, leaves, n_units, tb, t.d_tax_node.p, t.d_tax_long.p, t.d_tax_cur.p, st);
         HIP_TRY(hipGetLastError());
         return PFQ_OK;
     }
@@ -2144,6 +2203,11 @@ struct QueryRun {
             HIP_TRY(t.d_lca.ensure(t.lca_units + 1));
             HIP_TRY(hipMemsetAsync(t.d_lca.p, 0xff, t.lca_units * 4, st));  // (an empty tree or call: no unit has a clade)
         }
+        if (want_taxa) {
+            t.taxa_units = paired ? n_reads / 2 : n_reads;
+            HIP_TRY(t.d_tax_node.ensure(t.taxa_units + 1));
+            HIP_TRY(hipMemsetAsync(t.d_tax_node.p, 0xff, t.taxa_units * 4, st));  // (a unit without a hit has no node)
+        }
         for (int attempt_no = 0; attempt_no < 2; ++attempt_no) {
             PFQ_TRY(attempt(attempt_no));
             if (!want_hits) return PFQ_OK;  // (PFQ_PAIRED always builds the mates' hit lists)
@@ -2159,10 +2223,12 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
                  float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
     t.scores_valid = false;
     t.lca_last = false;
+    t.taxa_last = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
     int rc = q.plan();
     if (rc == PFQ_OK) rc = q.run();
     t.lca_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_LCA);
+    t.taxa_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_TAXA);
     if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
     return rc;
 }
@@ -2743,6 +2809,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
+    tax_clear(t);         // (the taxonomy described the leaves as they were)
     t.cov_bits_valid = false;
     t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
     t.merge_rounds = 0;
@@ -3040,6 +3107,8 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes() +
                         t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes() +  // (the abundance log)
                         t.d_cov_regs.bytes() + t.d_cov_cnt.bytes() +                                                  // (the coverage sketch)
+                        t.d_tax_rank.bytes() + t.d_tax_leaf_node.bytes() + t.d_tax_parent.bytes() + t.d_tax_first.bytes() +   // (the taxonomy)
+                        t.d_tax_gap_min.bytes() + t.d_tax_here.bytes() + t.d_tax_any.bytes() + t.d_tax_misc.bytes() +
                         t.d_fr_bytes.bytes() + t.d_fr_foff.bytes() + t.d_fr_seq.bytes() + t.d_fr_start.bytes() + t.d_fr_segpos.bytes() +  // (pfq_query_frames)
                         t.d_fr_cnt.bytes() + t.d_fr_def.bytes() + t.d_fr_seq0.bytes() + t.d_fr_defoff.bytes() + t.d_fr_seqseg.bytes() + t.d_fr_sums.bytes() +
                         t.d_fr_segs.bytes() + t.d_fr_segseq.bytes() + t.d_fr_queue.bytes() + t.d_fr_pieceoff.bytes() + t.d_fr_parts.bytes() + t.d_fr_misc.bytes() +
@@ -3064,6 +3133,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
+    tax_clear(t);         // (the taxonomy described the leaves as they were)
     t.cov_bits_valid = false;
     t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
     t.merge_rounds = 0;
@@ -3120,6 +3190,10 @@ static int stage_input(pfq_tree &t, const uint8_t *seq, const uint64_t *offsets,
 static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     t.scores_valid = false;
     t.lca_last = false;
+    t.taxa_last = false;
+    if ((flags & PFQ_WANT_TAXA) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_TAXA needs PFQ_WANT_HITS");
+    if ((flags & PFQ_WANT_TAXA) && t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_TAXA on a subtree shard: a shard sees only its own leaves, so its rows are partial");
     if ((flags & PFQ_LCA_BEST) && (~flags & (PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES)))
         return fail(PFQ_ERR_ARG, "PFQ_LCA_BEST needs PFQ_WANT_LCA | PFQ_WANT_HITS | PFQ_WANT_SCORES");
     if ((flags & PFQ_WANT_LCA) && t.is_shard)
@@ -3163,6 +3237,7 @@ static int check_frames(pfq_tree *tree, const void *seq, const void *offsets, ui
     if (!tree || !out || (n_seqs && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
     tree->scores_valid = false;
     tree->lca_last = false;
+    tree->taxa_last = false;
     if (flags) return fail(PFQ_ERR_ARG, "pfq_query_frames: flags must be 0 (frames do not combine with pairs, LCA, abundance or coverage)");
     return PFQ_OK;
 }
@@ -3388,6 +3463,179 @@ int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units) {
     if (t.lca_units) HIP_TRY(hipMemcpy(t.out_lca.data(), t.d_lca.p, t.lca_units * 4, hipMemcpyDeviceToHost));
     *lca = t.out_lca.data();
     *n_units = t.lca_units;
+    return PFQ_OK;
+}
+
+// ---- taxonomy (pfq.h "taxonomy") ----
+namespace {
+thread_local pfq_taxonomy::File g_tax_file;
+thread_local std::vector<const char *> g_tax_file_names;
+thread_local pfq_taxonomy::NodeTable g_tax_nodes;
+thread_local std::vector<std::string> g_db_leaf_ids;
+thread_local std::vector<const char *> g_db_leaf_ptr;
+}  // namespace
+
+int pfq_db_leaf_ids(const char *db_dir, const char *const **tax_ids, uint64_t *n_leaves) {
+    if (!db_dir || !tax_ids || !n_leaves) return fail(PFQ_ERR_ARG, "null argument");
+    *n_leaves = 0;
+    pfq_tree t;  // the model only: no filter is read, no device is touched
+    PFQ_TRY(read_tree_bin(db_dir, t));
+    g_db_leaf_ids.clear();
+    for (int32_t v : leaves_dfs(t)) {
+        if (!t.nodes[v].has_tax) return fail(PFQ_ERR_FORMAT, "leaf node without tax_id (reference: unwrap panic, query.rs:146)");
+        g_db_leaf_ids.push_back(t.nodes[v].tax_id);
+    }
+    g_db_leaf_ptr.clear();
+    for (const std::string &s : g_db_leaf_ids) g_db_leaf_ptr.push_back(s.c_str());
+    g_db_leaf_ptr.push_back(nullptr);
+    *tax_ids = g_db_leaf_ptr.data();
+    *n_leaves = g_db_leaf_ids.size();
+    return PFQ_OK;
+}
+
+int pfq_taxonomy_read(const char *path, const char *const *leaf_ids, uint64_t n_leaves, pfq_taxonomy_file *out) {
+    if (!path || !out || (n_leaves && !leaf_ids)) return fail(PFQ_ERR_ARG, "null argument");
+    memset(out, 0, sizeof *out);
+    std::vector<std::string> ids;
+    for (uint64_t l = 0; l < n_leaves; ++l) {
+        if (!leaf_ids[l]) return fail(PFQ_ERR_ARG, "null leaf id");
+        ids.push_back(leaf_ids[l]);
+    }
+    bool io = false;
+    const std::string err = pfq_taxonomy::read_file(path, ids, g_tax_file, io);
+    if (!err.empty()) return fail(io ? PFQ_ERR_IO : PFQ_ERR_FORMAT, err);
+    g_tax_file_names.clear();
+    for (const std::string &s : g_tax_file.names) g_tax_file_names.push_back(s.c_str());
+    out->n_taxa = g_tax_file.parent.size();
+    out->taxon_parent = g_tax_file.parent.data();
+    out->taxon_names = g_tax_file_names.data();
+    out->n_leaves = n_leaves;
+    out->leaf_taxon = g_tax_file.leaf_taxon.data();
+    out->lines_considered = g_tax_file.lines_considered;
+    out->lines_other = g_tax_file.lines_other;
+    out->leaves_without_line = g_tax_file.leaves_without_line;
+    return PFQ_OK;
+}
+
+int pfq_taxonomy_nodes(uint64_t n_leaves, const char *const *leaf_ids, uint64_t n_taxa, const uint32_t *taxon_parent, const char *const *taxon_names,
+                       const uint32_t *leaf_taxon, const pfq_taxon **nodes, uint64_t *n) {
+    if (!nodes || !n) return fail(PFQ_ERR_ARG, "null argument");
+    *n = 0;
+    const std::string err = pfq_taxonomy::build_nodes(n_leaves, leaf_ids, n_taxa, taxon_parent, taxon_names, leaf_taxon, g_tax_nodes);
+    if (!err.empty()) return fail(PFQ_ERR_ARG, err);
+    *nodes = g_tax_nodes.nodes.data();
+    *n = g_tax_nodes.nodes.size();
+    return PFQ_OK;
+}
+
+int pfq_tree_set_taxonomy(pfq_tree *tree, uint64_t n_taxa, const uint32_t *taxon_parent, const char *const *taxon_names, const uint32_t *leaf_taxon) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(insertion_error(t));
+    if (t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "a taxonomy on a subtree shard: a shard sees only its own leaves, so the rows it would count are partial");
+    PFQ_TRY(finish_topology(t));
+    if (t.root < 0) return fail(PFQ_ERR_STATE, "a taxonomy on an empty tree");
+    PFQ_TRY(build_layout(t));
+    const size_t nl = t.leaves.size();
+    std::vector<const char *> ids;
+    for (int32_t v : t.leaves) ids.push_back(t.nodes[v].tax_id.c_str());
+    pfq_taxonomy::NodeTable nt;
+    const std::string err = pfq_taxonomy::build_nodes(nl, ids.data(), n_taxa, taxon_parent, taxon_names, leaf_taxon, nt);
+    if (!err.empty()) return fail(PFQ_ERR_ARG, err);
+    HIP_TRY(hipDeviceSynchronize());  // (queued calls may still count on the tables about to go)
+    tax_clear(t);
+    t.tax = std::move(nt);
+    for (size_t v = 0; v < t.tax.nodes.size(); ++v) t.tax.nodes[v].name = t.tax.names[v].c_str();  // (the strings may have moved)
+    const size_t nn = t.tax.nodes.size();
+    // the sparse table of range minima over the gaps' nodes, as ensure_lca builds the tree's own
+    uint32_t levels = 1;
+    while ((2ull << (levels - 1)) <= t.tax.gap.size()) ++levels;
+    std::vector<uint32_t> tab((size_t)levels * nl, PFQ_NO_CLADE);
+    std::copy(t.tax.gap.begin(), t.tax.gap.end(), tab.begin());
+    for (uint32_t j = 1; j < levels; ++j) {
+        const size_t half = (size_t)1 << (j - 1);
+        const uint32_t *prev = tab.data() + (size_t)(j - 1) * nl;
+        uint32_t *cur = tab.data() + (size_t)j * nl;
+        for (size_t i = 0; i + 2 * half <= t.tax.gap.size(); ++i) cur[i] = std::min(prev[i], prev[i + half]);
+    }
+    std::vector<uint32_t> parent(nn), first(nn), heaviest(nn, PFQ_NO_CLADE);
+    for (size_t v = 0; v < nn; ++v) {
+        parent[v] = t.tax.nodes[v].parent;
+        first[v] = t.tax.nodes[v].first_rank;
+        if (v && (heaviest[parent[v]] == PFQ_NO_CLADE || t.tax.nodes[v].n_leaves > t.tax.nodes[heaviest[parent[v]]].n_leaves)) heaviest[parent[v]] = (uint32_t)v;
+    }
+    // the hot nodes: from top down the heaviest child while it holds at least half of all leaves (phage taxonomies are top-heavy)
+    uint32_t cur = t.tax.top;
+    for (uint32_t k = 0; k < pfq::TAX_HOT; ++k) {
+        t.tax_hot[k] = PFQ_NO_CLADE;
+        if (cur == PFQ_NO_CLADE) continue;
+        const uint32_t h = heaviest[cur];
+        cur = (h != PFQ_NO_CLADE && 2ull * t.tax.nodes[h].n_leaves >= nl) ? h : PFQ_NO_CLADE;
+        t.tax_hot[k] = cur;
+    }
+    HIP_TRY(t.d_tax_rank.ensure(nl));
+    HIP_TRY(t.d_tax_leaf_node.ensure(nl));
+    HIP_TRY(t.d_tax_parent.ensure(nn));
+    HIP_TRY(t.d_tax_first.ensure(nn));
+    HIP_TRY(t.d_tax_gap_min.ensure(tab.size()));
+    HIP_TRY(t.d_tax_here.ensure(nn));
+    HIP_TRY(t.d_tax_any.ensure(nn));
+    HIP_TRY(t.d_tax_misc.ensure(pfq::TAX_MISC_N));
+    HIP_TRY(hipMemcpy(t.d_tax_rank.p, t.tax.rank.data(), nl * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.d_tax_leaf_node.p, t.tax.leaf_node.data(), nl * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.d_tax_parent.p, parent.data(), nn * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.d_tax_first.p, first.data(), nn * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.d_tax_gap_min.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    t.tax_set = true;
+    return tax_zero(t);
+}
+
+int pfq_tree_taxa(pfq_tree *tree, const pfq_taxon **nodes, uint64_t *n) {
+    if (!tree || !nodes || !n) return fail(PFQ_ERR_ARG, "null argument");
+    *nodes = tree->tax_set ? tree->tax.nodes.data() : nullptr;
+    *n = tree->tax_set ? tree->tax.nodes.size() : 0;
+    return PFQ_OK;
+}
+
+int pfq_taxon_counts(pfq_tree *tree, const uint64_t **here, const uint64_t **below, const uint64_t **any, uint64_t *n) {
+    if (!tree || !n) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    const size_t nn = t.tax_set ? t.tax.nodes.size() : 0;
+    t.out_tax_here.assign(nn, 0);
+    t.out_tax_any.assign(nn, 0);
+    if (nn) {
+        unsigned long long misc[pfq::TAX_MISC_N];
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(t.out_tax_here.data(), t.d_tax_here.p, nn * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t.out_tax_any.data(), t.d_tax_any.p, nn * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(misc, t.d_tax_misc.p, sizeof misc, hipMemcpyDeviceToHost));
+        // what the kernels count once instead of per node (pfq_kernels.h): the units with a hit touch every node down to top,
+        // an all-leaf unit sits on top and touches every node below it
+        t.out_tax_here[t.tax.top] += misc[pfq::TAX_MISC_ALL];
+        for (size_t v = 0; v < nn; ++v) t.out_tax_any[v] = v <= t.tax.top ? misc[pfq::TAX_MISC_HIT] : t.out_tax_any[v] + misc[pfq::TAX_MISC_ALL];
+    }
+    t.out_tax_below = t.out_tax_here;
+    for (size_t v = nn; v-- > 1;) t.out_tax_below[t.tax.nodes[v].parent] += t.out_tax_below[v];  // (pre-order: children after their parent)
+    if (here) *here = t.out_tax_here.data();
+    if (below) *below = t.out_tax_below.data();
+    if (any) *any = t.out_tax_any.data();
+    *n = nn;
+    return PFQ_OK;
+}
+
+int pfq_last_taxa(pfq_tree *tree, const uint32_t **node, uint64_t *n_units) {
+    if (!tree || !node || !n_units) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->taxa_last) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for the taxa (PFQ_WANT_TAXA)");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(wait_last_call(t));
+    t.out_tax_node.resize(t.taxa_units + 1);
+    if (t.taxa_units) HIP_TRY(hipMemcpy(t.out_tax_node.data(), t.d_tax_node.p, t.taxa_units * 4, hipMemcpyDeviceToHost));
+    *node = t.out_tax_node.data();
+    *n_units = t.taxa_units;
     return PFQ_OK;
 }
 
@@ -4213,6 +4461,7 @@ int pfq_leaf_counts_reset(pfq_tree *tree) {
         HIP_TRY(hipMemset(tree->d_counts.p, 0, tree->leaves.size() * 8));
         HIP_TRY(hipMemset(tree->d_counts_base.p, 0, tree->leaves.size() * 8));
         if (tree->lca_valid) HIP_TRY(hipMemset(tree->d_clade_here.p, 0, tree->clades.size() * 8));
+        PFQ_TRY(tax_zero(*tree));
     }
     for (auto &nd : tree->nodes) nd.mapped_reads = nd.base_reads = 0;
     abund_clear(*tree);

@@ -397,6 +397,31 @@ void launch_lca_rows(const unsigned long long *d_off, const uint32_t *d_leaves, 
                      const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
 void launch_lca_best(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint2 *d_span,
                      uint32_t *d_long, unsigned long long *d_n_long, const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
+// PFQ_WANT_TAXA (pfq_tax.hip): the units of the call's final ascending CSR d_off / d_leaves [n_units] counted on the nodes of the
+// user's taxonomy (pfq.h "taxonomy"): d_node[u] = the deepest node above every leaf of row u (TAX_NO_NODE: an empty row),
+// here[that node] += 1, any[t] += 1 for every node t above at least one leaf of the row.  The tables describe the current leaf
+// set: rank, leaf_node [n_leaves]; parent, first_rank [n_nodes]; gap_min [levels][n_leaves], level j entry i = the smallest node
+// index among the lowest common nodes of the adjacent ranks (i, i + 1) .. (i + 2^j - 1, i + 2^j) — nodes are in pre-order, so
+// that is their shallowest; top_node = the deepest node above every leaf (nodes 0 .. top_node are the root's one-child chain).
+// What the kernels leave out of here / any, exact and cheap to add at read-out: misc[TAX_MISC_HIT] += units with a hit, which is
+// any[t] of every t <= top_node (the walks stop below them); misc[TAX_MISC_ALL] += rows that list all n_leaves leaves, each a
+// unit of here[top_node] and of any[t] for every t > top_node (they walk nothing).  hot: up to TAX_HOT nodes below top_node that
+// a wave counts with ballots instead of one atomic per lane (unused slots: TAX_NO_NODE).  Up to TAX_HIST_LDS nodes a block
+// counts here and any in two u32 LDS histograms (dynamic LDS, 8 bytes per node: 64 KiB at the bound) and flushes once per node;
+// above, global atomics.
+// d_long [n_units]: queue of the rows of more than 64 entries, *d_n_long zeroed by the caller.
+constexpr uint32_t TAX_NO_NODE = 0xffffffffu;
+constexpr uint32_t TAX_HIST_LDS = 8192;
+constexpr uint32_t TAX_HOT = 4;
+enum { TAX_MISC_HIT = 0, TAX_MISC_ALL = 1, TAX_MISC_N = 2 };
+struct TaxTables {
+    uint32_t n_leaves, n_nodes, top_node;
+    uint32_t hot[TAX_HOT];
+    const uint32_t *rank, *leaf_node, *parent, *first_rank, *gap_min;
+    unsigned long long *here, *any, *misc;
+};
+void launch_tax_rows(const unsigned long long *d_off, const uint32_t *d_leaves, uint64_t n_units, const TaxTables &tb, uint32_t *d_node,
+                     uint32_t *d_long, unsigned long long *d_n_long, hipStream_t st);
 // PFQ_WANT_ABUNDANCE (pfq_abund.hip): the device log of the calls' ambiguous rows and the EM over it.
 //   launch_abund_count: d_cnt[ABUND_CNT_*] += what the CSR d_off [n_units] would add to the log, per class (a row's class
 //     follows from its length: 0 unhit, 1 unique, n_leaves > 1 all leaves, else ambiguous) and the ambiguous rows' entries.

@@ -228,7 +228,7 @@ class BloomTree:
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
                      want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                     lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
+                     lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
@@ -237,8 +237,11 @@ class BloomTree:
         clade_counts()), "best" to that of its best-scoring hits (needs want_hits and want_scores); the return value and
         every other result stay what they are without it.
         `abundance`: the call's rows are also logged on the device for abundance() (needs want_hits).
-        `coverage`: every listed genome's matched k-mers are also sketched on the device for coverage() (needs want_hits)."""
-        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits)
+        `coverage`: every listed genome's matched k-mers are also sketched on the device for coverage() (needs want_hits).
+        `taxa`: every read / fragment is also counted on the nodes of the taxonomy set_taxonomy() gave (needs want_hits):
+        last_taxa(), taxon_counts()."""
+        lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
+                     _taxa_flags(taxa, want_hits))
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -287,10 +290,11 @@ class BloomTree:
         return seq, off
 
     def query_text(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
-                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
+                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
         """Classifies the block parse_text() parsed last, exactly as query_packed() classifies the same reads from host memory
         (pfq_text_query); same keywords, same return value.  May be repeated: the counters grow each time."""
-        lca_flags = _lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits)
+        lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
+                     _taxa_flags(taxa, want_hits))
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
         _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
@@ -344,13 +348,13 @@ class BloomTree:
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
                           want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                          lca: Optional[str] = None, abundance: bool = False, coverage: bool = False):
+                          lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, `taxa`, as in query_packed."""
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) |
-                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True))
+                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True) | _taxa_flags(taxa, True))
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -363,19 +367,19 @@ class BloomTree:
 
     def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
                     mode: str = "either", lca: Optional[str] = None, abundance: bool = False,
-                    coverage: bool = False) -> List[List[int]]:
+                    coverage: bool = False, taxa: bool = False) -> List[List[int]]:
         """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
         (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments.
         `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca().
         `abundance`: the fragments' rows are also logged for abundance(); `coverage`: both mates' matched k-mers are also
-        sketched for coverage(), per genome the fragment lists."""
+        sketched for coverage(), per genome the fragment lists; `taxa`: the fragments are also counted on the taxonomy's nodes."""
         if lca not in (None, "all", "best"):
             raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
         if len(r1) != len(r2):
             raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
         seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
         offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best", paired=True,
-                                         pair_mode=mode, lca=lca, abundance=abundance, coverage=coverage)[:2]
+                                         pair_mode=mode, lca=lca, abundance=abundance, coverage=coverage, taxa=taxa)[:2]
         return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
 
     # ---- clades (lowest common ancestors)
@@ -403,6 +407,44 @@ class BloomTree:
         p = C.POINTER(C.c_uint32)()
         n = C.c_uint64()
         _ffi.check(_ffi.lib().pfq_last_lca(self._h, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
+
+    # ---- taxonomy (PFQ_WANT_TAXA)
+    def set_taxonomy(self, taxon_parent: Sequence[int], taxon_names: Sequence[str], leaf_taxon: Sequence[int]) -> None:
+        """Lays a taxonomy over the current leaves (pfq_tree_set_taxonomy): taxon 0 is the root (parent _ffi.NO_CLADE or -1),
+        taxon_parent[i] < i, leaf_taxon[l] is the taxon genome l of get_leaf_counts() sits directly under.  Replaces an earlier
+        one and zeroes the taxon counters; prune_tree and insert drop it."""
+        if len(taxon_parent) != len(taxon_names):
+            raise ValueError(f"{len(taxon_parent)} taxon parents but {len(taxon_names)} taxon names")
+        par = np.ascontiguousarray([_ffi.NO_CLADE if int(x) < 0 else int(x) for x in taxon_parent], dtype=np.uint32)
+        leaf = np.ascontiguousarray(np.asarray(leaf_taxon, dtype=np.int64), dtype=np.uint32)
+        names = (C.c_char_p * max(len(taxon_names), 1))(*[t.encode() for t in taxon_names])
+        _ffi.check(_ffi.lib().pfq_tree_set_taxonomy(self._h, len(par), par.ctypes.data if par.size else None, names,
+                                                    leaf.ctypes.data if leaf.size else None))
+
+    def taxa(self) -> List[Tuple[int, int, int, int, int, str]]:
+        """The nodes of the taxonomy: (parent, depth, first_rank, n_leaves, leaf, name) per node in pre-order; parent -1 for
+        the root, leaf -1 for a taxon (a genome node: its index in get_leaf_counts()).  Empty when no taxonomy is set."""
+        p = C.POINTER(_ffi.Taxon)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_tree_taxa(self._h, C.byref(p), C.byref(n)))
+        return _taxon_rows(p, n.value)
+
+    def taxon_counts(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(here, below, any) per node of the taxonomy: the reads / fragments assigned to it, the sum of that over its subtree,
+        and those that hit at least one genome below it."""
+        here, below, any_ = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_taxon_counts(self._h, C.byref(here), C.byref(below), C.byref(any_), C.byref(n)))
+        if not n.value:
+            return tuple(np.zeros(0, dtype=np.uint64) for _ in range(3))
+        return tuple(np.ctypeslib.as_array(x, shape=(n.value,)).copy() for x in (here, below, any_))
+
+    def last_taxa(self) -> np.ndarray:
+        """Node index per read / fragment of the last query call, which must have asked for it (_ffi.NO_CLADE: no hit)."""
+        p = C.POINTER(C.c_uint32)()
+        n = C.c_uint64()
+        _ffi.check(_ffi.lib().pfq_last_taxa(self._h, C.byref(p), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
 
     # ---- abundance (PFQ_WANT_ABUNDANCE)
@@ -571,6 +613,55 @@ def _abundance_flags(abundance: bool, want_hits: bool) -> int:
     if not want_hits:
         raise ValueError("abundance=True needs the hits (want_hits=True): the log holds the rows of the call's hit lists")
     return _ffi.WANT_ABUNDANCE
+
+
+def _taxa_flags(taxa: bool, want_hits: bool) -> int:
+    if not taxa:
+        return 0
+    if not want_hits:
+        raise ValueError("taxa=True needs the hits (want_hits=True): a node is touched by whole rows of the call's hit lists")
+    return _ffi.WANT_TAXA
+
+
+def _taxon_rows(p, n: int) -> List[Tuple[int, int, int, int, int, str]]:
+    def idx(x):
+        return -1 if x == _ffi.NO_CLADE else int(x)
+    return [(idx(p[i].parent), int(p[i].depth), int(p[i].first_rank), int(p[i].n_leaves), idx(p[i].leaf), p[i].name.decode()) for i in range(n)]
+
+
+def db_leaf_ids(directory: str) -> List[str]:
+    """The tax_ids of a database's leaves in get_leaf_counts order, from tree.bin alone (pfq_db_leaf_ids); needs no device."""
+    ids = C.POINTER(C.c_char_p)()
+    n = C.c_uint64()
+    _ffi.check(_ffi.lib().pfq_db_leaf_ids(directory.encode(), C.byref(ids), C.byref(n)))
+    return [ids[i].decode() for i in range(n.value)]
+
+
+def read_taxonomy(path: str, leaf_ids: Sequence[str]) -> Tuple[List[int], List[str], List[int]]:
+    """A taxonomy file (`genome<TAB>lineage` per line, the lineage a ';'-separated list of names from the top rank down; see
+    pfq_taxonomy_read in include/pfq.h) for the leaves named `leaf_ids`: (taxon_parent, taxon_names, leaf_taxon) as
+    BloomTree.set_taxonomy takes them (the root's parent is -1).  Needs no device.  A bad file raises PfqError."""
+    ids = (C.c_char_p * max(len(leaf_ids), 1))(*[t.encode() for t in leaf_ids])
+    out = _ffi.TaxonomyFile()
+    _ffi.check(_ffi.lib().pfq_taxonomy_read(path.encode(), ids, len(leaf_ids), C.byref(out)))
+    nt, nl = int(out.n_taxa), int(out.n_leaves)
+    parent = [-1 if out.taxon_parent[i] == _ffi.NO_CLADE else int(out.taxon_parent[i]) for i in range(nt)]
+    return parent, [out.taxon_names[i].decode() for i in range(nt)], [int(out.leaf_taxon[l]) for l in range(nl)]
+
+
+def taxonomy_nodes(leaf_ids: Sequence[str], taxon_parent: Sequence[int], taxon_names: Sequence[str],
+                   leaf_taxon: Sequence[int]) -> List[Tuple[int, int, int, int, int, str]]:
+    """The node table BloomTree.set_taxonomy would derive for leaves named `leaf_ids` (pfq_taxonomy_nodes), as BloomTree.taxa()
+    returns it.  Needs no device."""
+    ids = (C.c_char_p * max(len(leaf_ids), 1))(*[t.encode() for t in leaf_ids])
+    names = (C.c_char_p * max(len(taxon_names), 1))(*[t.encode() for t in taxon_names])
+    par = np.ascontiguousarray([_ffi.NO_CLADE if int(x) < 0 else int(x) for x in taxon_parent], dtype=np.uint32)
+    leaf = np.ascontiguousarray(np.asarray(leaf_taxon, dtype=np.int64), dtype=np.uint32)
+    p = C.POINTER(_ffi.Taxon)()
+    n = C.c_uint64()
+    _ffi.check(_ffi.lib().pfq_taxonomy_nodes(len(leaf_ids), ids, len(par), par.ctypes.data if par.size else None, names,
+                                             leaf.ctypes.data if leaf.size else None, C.byref(p), C.byref(n)))
+    return _taxon_rows(p, n.value)
 
 
 def _coverage_flags(coverage: bool, want_hits: bool) -> int:
