@@ -385,6 +385,39 @@ int pfq_coverage_reset(pfq_tree *tree);
  * PFQ_ERR_ARG.  Staged through host memory: this runs once per job. */
 int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src);
 
+/* ---- best rows (PFQ_ROWS_BEST) ----
+ * Below threshold 1 a read from one strain also passes that strain's relatives, and its row lists the whole family although the
+ * scores say which genome fits best.  With PFQ_ROWS_BEST the per-unit consumers take every unit's best-scoring genomes instead.
+ * A unit is a read, or with PFQ_PAIRED a fragment.  Its row H(u) and the scores s are exactly what pfq_hits and
+ * pfq_last_hit_scores give for the call.  The unit's best row is
+ *     B(u) = { H(u)[j] : s[j] == max over the row }
+ * in ascending leaf order; it is empty when H(u) is empty.  Ties stay.  Nothing is decided again: B is a pure function of (H, s).
+ * With the flag set, PFQ_WANT_TAXA, PFQ_WANT_ABUNDANCE and PFQ_WANT_COVERAGE consume B(u) wherever their text above says "the row
+ * pfq_hits gives for it".  Everything else of the call is bit for bit what it is without the flag: the leaf counters, the
+ * pfq_hits CSR and pfq_last_hit_scores, pfq_last_stats and pfq_debug_last_capacity, PFQ_WANT_LCA with or without PFQ_LCA_BEST
+ * (clade counters and pfq_last_lca), and the overflow retry: a block that ran again is reduced and consumed once.
+ * Consequences:
+ *   - Threshold 1: every listed leaf scores n_kmers, so B = H and the flag changes nothing.
+ *   - Units without k-mers: all scores are 0, so B = H = all leaves.
+ *   - Threshold <= 0 with k-mers: the row lists every leaf, and B is the top scorers only.
+ *   - Abundance: the classes follow from |B(u)|: 0 unhit, 1 unique, L all-leaves, else ambiguous.
+ *   - Coverage: units[l] counts the units whose best row lists l; a call's increase of matched[l] is the sum of its scores over the
+ *     best rows that list l.
+ *   - Taxonomy: any[genome node of l] grows by the units whose best row lists l, so it no longer equals the leaf counter's
+ *     increase; any[root] = below[root] is still the number of units that hit anything.
+ *   - All three states stay pure functions of the multiset of best rows: they do not depend on call split, replica split, query
+ *     path or any knob.
+ * Only together with PFQ_WANT_HITS | PFQ_WANT_SCORES, else PFQ_ERR_ARG.  Valid without any of the three consumers: then only
+ * pfq_last_best_rows shows it.  On a subtree shard: PFQ_ERR_UNSUPPORTED — the best of a partial row is not the row's best; this
+ * holds for PFQ_WANT_COVERAGE too, which otherwise accepts shards.  Works through pfq_query_batch, pfq_query_batch_device and
+ * pfq_text_query; pfq_query_frames keeps flags == 0.
+ * pfq_last_best_rows: the CSR of B for the last query call on `tree`, which must have set PFQ_ROWS_BEST (else PFQ_ERR_ARG, as
+ * pfq_last_lca); out->n_reads is the number of units.  The rows live in device memory and are copied to the host by this call,
+ * so a query call that is never asked pays nothing for the copy.  Library-owned; valid until the next query call on the tree.
+ * It is also right after a call that returned PFQ_ERR_UNSUPPORTED from the abundance log with its other results standing. */
+#define PFQ_ROWS_BEST 512u
+int pfq_last_best_rows(pfq_tree *tree, pfq_hits *out);
+
 /* ---- frames and segments (pfq_query_frames) ----
  * Where on a long sequence (an assembled contig, a long read) does a genome match?  Every sequence is cut into overlapping
  * frames of `frame` = F bases every `step` = S bases, k <= F and 1 <= S <= F (else PFQ_ERR_ARG); each frame is classified exactly

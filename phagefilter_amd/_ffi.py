@@ -15,7 +15,7 @@ SYMBOLS = [
     "pfq_tree_build_balanced_subtree_device", "pfq_trees_allreduce_counts", "pfq_last_allreduce_ranks", "pfq_device_count", "pfq_set_option", "pfq_tree_save", "pfq_tree_info",
     "pfq_tree_prune", "pfq_tree_close", "pfq_query_batch", "pfq_query_batch_device", "pfq_last_hit_scores", "pfq_leaf_counts",
     "pfq_tree_clades", "pfq_clade_counts", "pfq_last_lca",
-    "pfq_tree_set_taxonomy", "pfq_tree_taxa", "pfq_taxon_counts", "pfq_last_taxa", "pfq_db_leaf_ids", "pfq_taxonomy_read", "pfq_taxonomy_nodes",
+    "pfq_tree_set_taxonomy", "pfq_tree_taxa", "pfq_taxon_counts", "pfq_last_taxa", "pfq_last_best_rows", "pfq_db_leaf_ids", "pfq_taxonomy_read", "pfq_taxonomy_nodes",
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
@@ -128,6 +128,7 @@ WANT_ABUNDANCE = 64
 ABUND_Q = 16
 WANT_COVERAGE = 128
 WANT_TAXA = 256
+ROWS_BEST = 512
 NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
@@ -181,6 +182,7 @@ def lib() -> C.CDLL:
     L.pfq_tree_taxa.argtypes = [vp, C.POINTER(C.POINTER(Taxon)), u64p]
     L.pfq_taxon_counts.argtypes = [vp, C.POINTER(u64p), C.POINTER(u64p), C.POINTER(u64p), u64p]
     L.pfq_last_taxa.argtypes = [vp, C.POINTER(u32p), u64p]
+    L.pfq_last_best_rows.argtypes = [vp, C.POINTER(Hits)]
     L.pfq_db_leaf_ids.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_char_p)), u64p]
     L.pfq_taxonomy_read.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(TaxonomyFile)]
     L.pfq_taxonomy_nodes.argtypes = [C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, vp, C.POINTER(C.c_char_p), vp,

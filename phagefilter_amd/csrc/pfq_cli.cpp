@@ -1539,9 +1539,10 @@ struct QueryLoop {
     const bool coverage = false;   // --coverage: every call asks for the hits and sketches the listed genomes' matched k-mers
     const bool taxonomy = false;   // --taxonomy: every call asks for the hits and counts its units on the taxonomy's nodes
     const bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv
+    const bool best_hits = false;  // --best-hits: the three above take every unit's best-scoring genomes (the library is asked for hits and scores)
     uint32_t abundance_flags() const {
         return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
-               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u);
+               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u);
     }
     uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
@@ -2228,7 +2229,7 @@ int cmd_query(int argc, char **argv) {
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
                              {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"taxonomy", 0, true},
-                             {"taxon-reads", 0, false}};
+                             {"taxon-reads", 0, false}, {"best-hits", 0, false}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2239,6 +2240,19 @@ int cmd_query(int argc, char **argv) {
     const bool filtering = pos || neg;
     // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
     const bool scores = a.flags.count("scores") != 0;
+    // --best-hits: --taxonomy, --abundance and --coverage take every read's (fragment's) best-scoring genomes instead of its whole
+    // hit row (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST); every other output stays what it is.  Checked first, so that a
+    // refusal names this option whichever of the three it came with
+    const bool best_hits = a.flags.count("best-hits") != 0;
+    if (best_hits) {
+        if (!a.flags.count("abundance") && !a.flags.count("coverage") && !a.val.count("taxonomy"))
+            die("error: '--best-hits' needs at least one of '--taxonomy <FILE>', '--abundance', '--coverage': they are what it changes");
+        if (a.val.count("shard-depth"))
+            die("error: '--best-hits' cannot be used with '--shard-depth': a subtree shard sees only its own genomes, and the best of a "
+                "partial hit row is not the row's best");
+        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--best-hits': it serves runs that only count");
+        if (a.val.count("frame")) die("error: '--best-hits' cannot be used with '--frame': frames do not combine with per-read post-stages");
+    }
     // --lca all|best: every read (fragment) is also assigned to the lowest common ancestor of its hit genomes (best: of the
     // genomes with its highest score): CLADE_COUNTS.tsv; --lca-reads: READ_LCA.tsv, one line per record with hits
     const std::string lca_arg = opt(a, "lca", "");
@@ -2408,7 +2422,7 @@ int cmd_query(int argc, char **argv) {
     if (taxonomy) db.set_taxonomy(a.val.at("taxonomy"));
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits};
     if (block == 0) {
         // nothing to do: see above
     } else if (framed) {
@@ -2942,6 +2956,14 @@ void usage() {
             "The other outputs stay as they are.  With --devices the replicas' counts are summed.  Not with --shard-depth, --frame or\n"
             "--device-parse.  --taxon-reads (needs --taxonomy): also write READ_TAXA.tsv, one line per record with hits in input order\n"
             "(per fragment: R1's id): \"#read_id<TAB>hits<TAB>node<TAB>name\"\n"
+            "--best-hits (needs --taxonomy, --abundance or --coverage): below -f 1 a read from one strain also passes that strain's\n"
+            "relatives, although its scores say which genome fits best.  With this option TAXON_COUNTS.tsv, READ_TAXA.tsv, ABUNDANCE.tsv\n"
+            "(and the estimated column of TAXON_COUNTS.tsv) and COVERAGE.tsv are computed from every read's (fragment's) best-scoring\n"
+            "genomes: those of its hits that contain the most of its k-mers, ties kept.  The reduction runs on the GPU; every query call\n"
+            "then asks the library for hits and scores (READ_SCORES.tsv is still written with --scores only).  CLASSIFICATION.csv, POS / NEG,\n"
+            "READ_SCORES.tsv, CLADE_COUNTS.tsv, READ_LCA.tsv and the hits column of READ_TAXA.tsv (the size of the whole hit set) stay as\n"
+            "they are.  At -f 1 it changes nothing.  Works with --reads2 / --interleaved and --devices.  Not with --shard-depth, --frame or\n"
+            "--device-parse\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

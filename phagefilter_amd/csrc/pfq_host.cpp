@@ -431,6 +431,17 @@ struct pfq_tree {
     std::vector<uint32_t> out_tax_node;
     bool taxa_last = false;                // the last query call set PFQ_WANT_TAXA
     uint64_t taxa_units = 0;
+    // PFQ_ROWS_BEST: the last flagged call's best rows, a second CSR in device memory (d_best_off [best_units + 1],
+    // d_best_leaves) that the taxonomy, the abundance log and the coverage sketch read in place of the call's own; d_best_cnt /
+    // d_best_sums: input and scratch of the scan, d_best_long / d_best_cur: the queue of rows a wave takes and its cursor.
+    // Scratch like d_lca_span / d_tax_long: reused call after call, copied to the host only by pfq_last_best_rows.
+    DevBuf<uint32_t> d_best_cnt, d_best_long, d_best_leaves;
+    DevBuf<unsigned long long> d_best_sums, d_best_off, d_best_cur;
+    std::vector<uint64_t> out_best_off;
+    std::vector<uint32_t> out_best_leaves;
+    bool best_last = false;                // the last query call set PFQ_ROWS_BEST
+    bool best_built = false;               // ... and built rows (else: every best row is empty)
+    uint64_t best_units = 0;
 };
 
 namespace {
@@ -1269,7 +1280,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, rows_best = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
@@ -1308,6 +1319,7 @@ struct QueryRun {
         want_abund = (flags & PFQ_WANT_ABUNDANCE) != 0;
         want_cover = (flags & PFQ_WANT_COVERAGE) != 0;
         want_taxa = (flags & PFQ_WANT_TAXA) != 0;
+        rows_best = (flags & PFQ_ROWS_BEST) != 0;
         if (want_taxa && (!t.tax_set || t.tax.rank.size() != t.leaves.size()))
             return fail(PFQ_ERR_STATE, "PFQ_WANT_TAXA without a taxonomy: pfq_tree_set_taxonomy first (pfq_tree_prune and pfq_tree_insert drop it)");
         if (want_lca) PFQ_TRY(ensure_lca(t));
@@ -2088,8 +2100,18 @@ struct QueryRun {
             }
         }
         if (want_lca && off) PFQ_TRY(lca_rows(off, leaves, n_units, pair_mode));
-        if (want_cover) PFQ_TRY(cover_sketch(off, leaves, n_units, total, pair_mode));
-        if (want_taxa && off) PFQ_TRY(tax_rows(off, leaves, n_units));
+        // PFQ_ROWS_BEST: the three consumers below read the best rows; everything above and the caller's copies keep the call's own
+        const unsigned long long *use_off = off;
+        const uint32_t *use_leaves = leaves;
+        if (rows_best) {
+            PFQ_TRY(best_rows(off, leaves, n_units, total));
+            if (off) {
+                use_off = t.d_best_off.p;
+                use_leaves = t.d_best_leaves.p;
+            }
+        }
+        if (want_cover) PFQ_TRY(cover_sketch(use_off, use_leaves, n_units, total, pair_mode));
+        if (want_taxa && off) PFQ_TRY(tax_rows(use_off, use_leaves, n_units));
         if (total) HIP_TRY(hipStreamSynchronize(st));
         if (want_scores) {
             t.scores_valid = true;
@@ -2098,7 +2120,28 @@ struct QueryRun {
         hits->n_reads = n_units;
         hits->offsets = t.h_hit_off.p;
         hits->leaves = t.h_hit_leaves.p;
-        return want_abund ? abund_append(off, leaves, n_units) : PFQ_OK;
+        return want_abund ? abund_append(use_off, use_leaves, n_units) : PFQ_OK;
+    }
+
+    // PFQ_ROWS_BEST: the rows of the call's final CSR reduced to their best-scoring entries (pfq.h "best rows"), once:
+    // deliver_rows() runs for the attempt that stands.  Queued behind the score kernel (check_flags has made sure of the scores;
+    // fragments: launch_pair_scores' sums); `total` bounds what the reduction can keep, so nothing is read back.  No row built:
+    // every best row is empty and nothing runs.
+    int best_rows(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units, uint64_t total) {
+        t.best_units = n_units;
+        t.best_built = off != nullptr && n_units != 0;
+        if (!t.best_built) return PFQ_OK;
+        HIP_TRY(t.d_best_cnt.ensure(n_units));
+        HIP_TRY(t.d_best_sums.ensure((n_units + 4095) / 4096 + 2));
+        HIP_TRY(t.d_best_long.ensure(n_units));
+        HIP_TRY(t.d_best_cur.ensure(1));
+        HIP_TRY(t.d_best_off.ensure(n_units + 1));
+        HIP_TRY(t.d_best_leaves.ensure(total + 1));
+        HIP_TRY(hipMemsetAsync(t.d_best_cur.p, 0, 8, st));
+        pfq::launch_best_rows(off, leaves, t.d_hit_scores.p, n_units, t.d_best_cnt.p, t.d_best_sums.p, t.d_best_long.p, t.d_best_cur.p,
+                              t.d_best_off.p, t.d_best_leaves.p, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
     }
 
     // PFQ_WANT_COVERAGE: the rows of the call's final CSR are sketched, once: deliver_rows() runs for the attempt that stands.
@@ -2224,11 +2267,13 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
+    t.best_last = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
     int rc = q.plan();
     if (rc == PFQ_OK) rc = q.run();
     t.lca_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_LCA);
     t.taxa_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_TAXA);
+    t.best_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_ROWS_BEST);
     if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
     return rc;
 }
@@ -3191,6 +3236,12 @@ static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
+    t.best_last = false;
+    if ((flags & PFQ_ROWS_BEST) && (~flags & (PFQ_WANT_HITS | PFQ_WANT_SCORES)))
+        return fail(PFQ_ERR_ARG, "PFQ_ROWS_BEST needs PFQ_WANT_HITS | PFQ_WANT_SCORES");
+    if ((flags & PFQ_ROWS_BEST) && t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "PFQ_ROWS_BEST on a subtree shard: a shard sees only its own leaves, and the best of a partial row "
+                                         "is not the row's best");
     if ((flags & PFQ_WANT_TAXA) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_TAXA needs PFQ_WANT_HITS");
     if ((flags & PFQ_WANT_TAXA) && t.is_shard)
         return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_TAXA on a subtree shard: a shard sees only its own leaves, so its rows are partial");
@@ -3238,6 +3289,7 @@ static int check_frames(pfq_tree *tree, const void *seq, const void *offsets, ui
     tree->scores_valid = false;
     tree->lca_last = false;
     tree->taxa_last = false;
+    tree->best_last = false;
     if (flags) return fail(PFQ_ERR_ARG, "pfq_query_frames: flags must be 0 (frames do not combine with pairs, LCA, abundance or coverage)");
     return PFQ_OK;
 }
@@ -3463,6 +3515,26 @@ int pfq_last_lca(pfq_tree *tree, const uint32_t **lca, uint64_t *n_units) {
     if (t.lca_units) HIP_TRY(hipMemcpy(t.out_lca.data(), t.d_lca.p, t.lca_units * 4, hipMemcpyDeviceToHost));
     *lca = t.out_lca.data();
     *n_units = t.lca_units;
+    return PFQ_OK;
+}
+
+int pfq_last_best_rows(pfq_tree *tree, pfq_hits *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->best_last) return fail(PFQ_ERR_ARG, "the last query call on this tree did not ask for the best rows (PFQ_ROWS_BEST)");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(wait_last_call(t));
+    t.out_best_off.assign(t.best_units + 1, 0);
+    uint64_t total = 0;
+    if (t.best_built) {
+        HIP_TRY(hipMemcpy(t.out_best_off.data(), t.d_best_off.p, (t.best_units + 1) * 8, hipMemcpyDeviceToHost));
+        total = t.out_best_off[t.best_units];
+    }
+    t.out_best_leaves.resize(total + 1);
+    if (total) HIP_TRY(hipMemcpy(t.out_best_leaves.data(), t.d_best_leaves.p, total * 4, hipMemcpyDeviceToHost));
+    out->n_reads = t.best_units;
+    out->offsets = t.out_best_off.data();
+    out->leaves = t.out_best_leaves.data();
     return PFQ_OK;
 }
 

@@ -397,6 +397,14 @@ void launch_lca_rows(const unsigned long long *d_off, const uint32_t *d_leaves, 
                      const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
 void launch_lca_best(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint2 *d_span,
                      uint32_t *d_long, unsigned long long *d_n_long, const LcaTables &tb, uint32_t *d_lca, hipStream_t st);
+// PFQ_ROWS_BEST (pfq_best.hip): the rows of the ascending CSR d_off / d_leaves [n_units], scored by d_scores (one score per
+// entry), reduced to the entries at the row's highest score: d_best_off [n_units + 1], d_best_leaves [at most the rows'
+// entries], ascending within a row like the rows themselves; an empty row stays empty, a row whose scores are all equal is
+// kept whole.  Scratch: d_cnt [n_units], d_sums [ceil(n_units / 4096) + 1], d_long [n_units], d_n_long [1] zeroed by the caller.
+// n_units = 0: nothing is written.
+void launch_best_rows(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint32_t *d_cnt,
+                      unsigned long long *d_sums, uint32_t *d_long, unsigned long long *d_n_long, unsigned long long *d_best_off,
+                      uint32_t *d_best_leaves, hipStream_t st);
 // PFQ_WANT_TAXA (pfq_tax.hip): the units of the call's final ascending CSR d_off / d_leaves [n_units] counted on the nodes of the
 // user's taxonomy (pfq.h "taxonomy"): d_node[u] = the deepest node above every leaf of row u (TAX_NO_NODE: an empty row),
 // here[that node] += 1, any[t] += 1 for every node t above at least one leaf of the row.  The tables describe the current leaf

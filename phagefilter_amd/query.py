@@ -228,7 +228,8 @@ class BloomTree:
     # ---- query
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
                      want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                     lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
+                     lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
+                     best: bool = False):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
@@ -239,9 +240,11 @@ class BloomTree:
         `abundance`: the call's rows are also logged on the device for abundance() (needs want_hits).
         `coverage`: every listed genome's matched k-mers are also sketched on the device for coverage() (needs want_hits).
         `taxa`: every read / fragment is also counted on the nodes of the taxonomy set_taxonomy() gave (needs want_hits):
-        last_taxa(), taxon_counts()."""
+        last_taxa(), taxon_counts().
+        `best`: `abundance`, `coverage` and `taxa` take every read's / fragment's best-scoring genomes instead of its whole row
+        (PFQ_ROWS_BEST; needs want_hits and want_scores); last_best_rows() gives those rows.  Everything else stays what it is."""
         lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
-                     _taxa_flags(taxa, want_hits))
+                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores))
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -290,11 +293,12 @@ class BloomTree:
         return seq, off
 
     def query_text(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
-                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
+                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
+                   best: bool = False):
         """Classifies the block parse_text() parsed last, exactly as query_packed() classifies the same reads from host memory
         (pfq_text_query); same keywords, same return value.  May be repeated: the counters grow each time."""
         lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
-                     _taxa_flags(taxa, want_hits))
+                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores))
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
         _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
@@ -348,13 +352,15 @@ class BloomTree:
 
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
                           want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
-                          lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False):
+                          lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
+                          best: bool = False):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, `taxa`, as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, `taxa`, `best`, as in query_packed."""
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) |
-                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True) | _taxa_flags(taxa, True))
+                 _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True) | _taxa_flags(taxa, True) |
+                 _best_flags(best, True, want_scores))
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -367,19 +373,20 @@ class BloomTree:
 
     def query_pairs(self, r1: Sequence[bytes], r2: Sequence[bytes], threshold: float,
                     mode: str = "either", lca: Optional[str] = None, abundance: bool = False,
-                    coverage: bool = False, taxa: bool = False) -> List[List[int]]:
+                    coverage: bool = False, taxa: bool = False, best: bool = False) -> List[List[int]]:
         """Mates r1[i], r2[i] as fragment i: its leaves (ascending indices into get_leaf_counts' order), the union
         (mode "either") or the intersection ("both") of the mates' hit sets.  Leaf counters count fragments.
         `lca`: None, "all" or "best" (scores are then computed as well): the fragments' clades are in last_lca().
         `abundance`: the fragments' rows are also logged for abundance(); `coverage`: both mates' matched k-mers are also
-        sketched for coverage(), per genome the fragment lists; `taxa`: the fragments are also counted on the taxonomy's nodes."""
+        sketched for coverage(), per genome the fragment lists; `taxa`: the fragments are also counted on the taxonomy's nodes;
+        `best`: those three take every fragment's best-scoring genomes (scores are then computed as well; last_best_rows())."""
         if lca not in (None, "all", "best"):
             raise ValueError(f"lca must be None, 'all' or 'best', not {lca!r}")
         if len(r1) != len(r2):
             raise ValueError(f"{len(r1)} first mates but {len(r2)} second mates")
         seq, off = pack_reads([m for pair in zip(r1, r2) for m in pair])
-        offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best", paired=True,
-                                         pair_mode=mode, lca=lca, abundance=abundance, coverage=coverage, taxa=taxa)[:2]
+        offs, leaves = self.query_packed(seq, off, threshold, want_hits=True, want_scores=lca == "best" or best, paired=True,
+                                         pair_mode=mode, lca=lca, abundance=abundance, coverage=coverage, taxa=taxa, best=best)[:2]
         return [leaves[int(offs[i]):int(offs[i + 1])].tolist() for i in range(len(r1))]
 
     # ---- clades (lowest common ancestors)
@@ -408,6 +415,18 @@ class BloomTree:
         n = C.c_uint64()
         _ffi.check(_ffi.lib().pfq_last_lca(self._h, C.byref(p), C.byref(n)))
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, dtype=np.uint32)
+
+    # ---- best rows (PFQ_ROWS_BEST)
+    def last_best_rows(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(offsets, leaves): per read / fragment of the last query call, which must have set `best`, the genomes of its row
+        whose score is the row's highest, ascending (pfq_last_best_rows); copied from the device by this call."""
+        hits = _ffi.Hits()
+        _ffi.check(_ffi.lib().pfq_last_best_rows(self._h, C.byref(hits)))
+        n = int(hits.n_reads)
+        offs = np.ctypeslib.as_array(hits.offsets, shape=(n + 1,)).copy()
+        total = int(offs[-1])
+        leaves = np.ctypeslib.as_array(hits.leaves, shape=(total,)).copy() if total else np.zeros(0, dtype=np.uint32)
+        return offs, leaves
 
     # ---- taxonomy (PFQ_WANT_TAXA)
     def set_taxonomy(self, taxon_parent: Sequence[int], taxon_names: Sequence[str], leaf_taxon: Sequence[int]) -> None:
@@ -607,6 +626,14 @@ def _lca_flags(lca: Optional[str], want_hits: bool, want_scores: bool) -> int:
     return _ffi.WANT_LCA | _ffi.LCA_BEST
 
 
+def _best_flags(best: bool, want_hits: bool, want_scores: bool) -> int:
+    if not best:
+        return 0
+    if not (want_hits and want_scores):
+        raise ValueError("best=True needs the hits and their scores (want_hits=True, want_scores=True)")
+    return _ffi.ROWS_BEST
+
+
 def _abundance_flags(abundance: bool, want_hits: bool) -> int:
     if not abundance:
         return 0
@@ -681,13 +708,15 @@ def _pair_flags(paired: bool, pair_mode: str) -> int:
 
 
 def query_batch(bloom_tree: BloomTree, read_set: Sequence[bytes], threshold: float,
-                result_map: Optional[ResultMap] = None, read_ids: Optional[Sequence[str]] = None) -> BloomTree:
+                result_map: Optional[ResultMap] = None, read_ids: Optional[Sequence[str]] = None, best: bool = False) -> BloomTree:
     """query::query_batch (query.rs:66-82).  Leaf counts accumulate in the tree; when `result_map` is given
-    (the reference fills it when reads carry their sequence, query.rs:146-154) every (read id, tax id) hit is added."""
+    (the reference fills it when reads carry their sequence, query.rs:146-154) every (read id, tax id) hit is added.
+    `best`: the call also asks for hits and scores and reduces every read's row to its best-scoring genomes
+    (bloom_tree.last_best_rows()); the leaf counts and `result_map` stay those of the whole rows."""
     seq, off = pack_reads(read_set)
-    res = bloom_tree.query_packed(seq, off, threshold, want_hits=result_map is not None)
+    res = bloom_tree.query_packed(seq, off, threshold, want_hits=result_map is not None or best, want_scores=best, best=best)
     if result_map is not None:
-        offs, leaves = res
+        offs, leaves = res[:2]
         names = [t for t, _ in bloom_tree.get_leaf_counts()]
         for r in range(len(read_set)):
             rid = read_ids[r] if read_ids is not None else str(r)
