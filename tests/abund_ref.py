@@ -8,31 +8,33 @@ Q = 16
 ONE = 1 << Q
 
 
-def classify(rows, n_leaves):
+def classify(rows, n_leaves, mult=None):
     """The log the library keeps for these rows: class counters, unique[], and the ambiguous rows as a Counter of tuples
-    (identical rows add the same terms, so they are folded here; the library keeps them one by one)."""
+    (identical rows add the same terms, so they are folded here; the library keeps them one by one).  `mult`: per row, how
+    many units have it (one each without)."""
     log = {"n_leaves": n_leaves, "n_units": 0, "n_unhit": 0, "n_unique": 0, "n_ambiguous": 0, "n_all_leaves": 0, "n_entries": 0,
            "unique": [0] * n_leaves, "rows": Counter()}
-    add(log, rows)
+    add(log, rows, mult)
     return log
 
 
-def add(log, rows):
+def add(log, rows, mult=None):
     L = log["n_leaves"]
-    for r in rows:
+    for i, r in enumerate(rows):
         r = tuple(int(x) for x in r)
-        log["n_units"] += 1
+        m = 1 if mult is None else int(mult[i])
+        log["n_units"] += m
         if len(r) == 0:
-            log["n_unhit"] += 1
+            log["n_unhit"] += m
         elif len(r) == 1:                      # (so a tree of one leaf has no "all leaves" class)
-            log["n_unique"] += 1
-            log["unique"][r[0]] += 1
+            log["n_unique"] += m
+            log["unique"][r[0]] += m
         elif len(r) == L:
-            log["n_all_leaves"] += 1
+            log["n_all_leaves"] += m
         else:
-            log["n_ambiguous"] += 1
-            log["n_entries"] += len(r)
-            log["rows"][r] += 1
+            log["n_ambiguous"] += m
+            log["n_entries"] += m * len(r)
+            log["rows"][r] += m
     return log
 
 

@@ -38,10 +38,10 @@ class Sketch:
         self.units = [0] * n_leaves
         self.matched = [0] * n_leaves
 
-    def add_hash(self, leaf, h):
-        """One matched k-mer of `leaf` whose seeded hash is h."""
+    def add_hash(self, leaf, h, mult=1):
+        """One matched k-mer of `leaf` whose seeded hash is h (`mult`: met that many times; the maximum does not care)."""
         j, rho = slot(mix(h), self.p)
-        self.matched[leaf] += 1
+        self.matched[leaf] += mult
         if rho > self.registers[leaf][j]:
             self.registers[leaf][j] = rho
 
@@ -59,7 +59,7 @@ class Sketch:
 
 class TreeSketcher:
     """Sketches units against an oracle tree: `add(row, reads)` is one unit whose row (leaf columns) the query gave and whose
-    reads are one read, or the two mates of a fragment."""
+    reads are one read, or the two mates of a fragment; with `mult`, that many equal units."""
 
     def __init__(self, ot, p=P_DEFAULT, share=None):
         self.ot = ot
@@ -68,11 +68,11 @@ class TreeSketcher:
         # the oracle's answers per k-mer, kept (`share`: another sketcher of the same tree whose answers are reused)
         self._hash, self._in = (share._hash, share._in) if share is not None else ({}, {})
 
-    def add(self, row, reads):
+    def add(self, row, reads, mult=1):
         sk, ot = self.sk, self.ot
-        sk.n_units += 1
+        sk.n_units += mult
         for l in row:
-            sk.units[l] += 1
+            sk.units[l] += mult
             for x in reads:
                 for c in orc.get_kmers(x, ot.kmer_size):                     # canonical, duplicates included
                     key = (l, c)
@@ -81,17 +81,17 @@ class TreeSketcher:
                     if self._in[key]:
                         if c not in self._hash:
                             self._hash[c] = orc.seeded_hash(ot.seed1, c)
-                        sk.add_hash(l, self._hash[c])
+                        sk.add_hash(l, self._hash[c], mult)
         return self
 
-    def add_reads(self, rows, reads):
-        for row, x in zip(rows, reads):
-            self.add(row, [x])
+    def add_reads(self, rows, reads, mult=None):
+        for i, (row, x) in enumerate(zip(rows, reads)):
+            self.add(row, [x], 1 if mult is None else int(mult[i]))
         return self
 
-    def add_pairs(self, rows, pairs):
-        for row, (a, b) in zip(rows, pairs):
-            self.add(row, [a, b])
+    def add_pairs(self, rows, pairs, mult=None):
+        for i, (row, (a, b)) in enumerate(zip(rows, pairs)):
+            self.add(row, [a, b], 1 if mult is None else int(mult[i]))
         return self
 
     def filter_bits(self):
