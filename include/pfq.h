@@ -418,6 +418,69 @@ int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src);
 #define PFQ_ROWS_BEST 512u
 int pfq_last_best_rows(pfq_tree *tree, pfq_hits *out);
 
+/* ---- threshold sweep (PFQ_WANT_SWEEP) ----
+ * The filter threshold decides everything a query reports, and finding it costs one whole run per candidate.  With a sweep list
+ * set, one flagged call at a threshold no higher than the list's lowest also counts, per threshold of the list, what a call of
+ * its own at that threshold would count.
+ * A sweep list is T thresholds, 1 <= T <= PFQ_SWEEP_MAX, float, none NaN, strictly ascending.  Any finite values are allowed,
+ * values <= 0 and > 1 included.  A unit is a read (fragments are refused); its n = max(len - k + 1, 0) k-mers.
+ *     need_t = need_kmers(thr[t], n): the f32 product, ceilf, clamped, exactly what a call at thr[t] asks of the read.
+ * thr[s] <= thr[t] implies need_s <= need_t, so the thresholds an entry passes are a prefix of the list.  For an entry e = (u, l)
+ * of the call's final CSR with score s(e), exactly what pfq_hits and pfq_last_hit_scores give:
+ *     p(e) = #{t : s(e) >= need_t(u)}, from 0 to T.
+ * Per unit: top(u) = the maximum of p over its row (0 for an empty row); arg(u) = the leaf of the first entry that reaches it;
+ * second(u) = the second-largest p counted with multiplicity (two entries at the maximum: second = top; a one-entry row: 0).
+ * The unit's row at thr[t] is the entries with p > t.  That row is a single genome exactly for second <= t < top, and the genome
+ * is arg.  State, all u64, accumulated over the flagged calls like the leaf counters, L = n_leaves:
+ *     pass[(T + 1) x L]   pass[p][l] += 1 per entry
+ *     uniq[T x L]         uniq[t][arg(u)] += 1 for every t in [second(u), top(u))
+ *     tops[T + 1]         tops[top(u)] += 1 per unit
+ *     n_units
+ * Read-out (pfq_sweep_get), derived on the host in integers:
+ *     leaf_units[t][l]  = sum over p > t of pass[p][l]        leaf_unique[t][l] = uniq[t][l]
+ *     units_hit[t]      = sum over p > t of tops[p]           units_unique[t]   = sum over l of uniq[t][l]
+ *     entries[t]        = sum over l of leaf_units[t][l]      genomes_hit[t]    = #{l : leaf_units[t][l] > 0}
+ * Consequences:
+ *   - On a tree where every parent filter is a superset of its children's (pfq_info.superset_verified == 1), a read passes leaf l
+ *     at thr[t] exactly when l is in its row at any threshold <= thr[t] and that score reaches need_t.  So leaf_units[t] is the
+ *     leaf counters' increase of the same reads queried at thr[t], units_hit[t] the number of non-empty rows of that query and
+ *     units_unique[t] its one-entry rows.
+ *   - A unit without k-mers has need 0 everywhere: its row lists all L leaves and every entry has p = T.
+ *   - The state is a pure function of the multiset of (row, scores, n).  It does not depend on call split, replica split, query
+ *     path or any knob.
+ * pfq_tree_set_sweep copies the list, allocates and zeroes the device state ((2 T + 1) L + T + 1 words, counted in
+ * pfq_info.device_bytes) and replaces an earlier list with its counters; n == 0 drops the list and frees the state.  A bad list
+ * (n > PFQ_SWEEP_MAX, a NaN, not strictly ascending): PFQ_ERR_ARG.  An empty tree: PFQ_ERR_STATE.  PFQ_ERR_UNSUPPORTED, with a
+ * message that says why: superset_verified == 0 (the scores of a read's ancestors are not in its row, so a leaf that fails at
+ * thr[t] through an ancestor would be counted), and a subtree shard (units and unique rows would be partial).
+ * PFQ_WANT_SWEEP: only together with PFQ_WANT_HITS | PFQ_WANT_SCORES, else PFQ_ERR_ARG; with PFQ_PAIRED: PFQ_ERR_ARG (a
+ * fragment's score is the mates' sum, and its row is a union or intersection of per-mate decisions); without a list:
+ * PFQ_ERR_STATE; the call's threshold must satisfy threshold <= thr[0] as floats (a NaN fails the comparison), else
+ * PFQ_ERR_ARG.  It combines with every other flag and changes none of their results: leaf counters, CSR, scores, stats, LCA,
+ * taxonomy, abundance, coverage, best rows.  It reads the whole rows, whatever PFQ_ROWS_BEST says.  It works through
+ * pfq_query_batch, pfq_query_batch_device and pfq_text_query; pfq_query_frames keeps flags == 0.  A block whose hit buffer
+ * overflowed and ran again is counted once.
+ * The counters are zeroed by pfq_sweep_reset and pfq_leaf_counts_reset; pfq_tree_prune and pfq_tree_insert zero them and
+ * re-size them to the new leaf count, and the list stays: a pruned or grown superset tree is still one.  Nothing of the sweep is
+ * stored by pfq_tree_save.
+ * pfq_sweep_get waits for the queued work; before any flagged call it returns zeros, without a list n_thresholds = 0.  The arrays
+ * are library-owned until the next sweep call on the tree; leaf_units and leaf_unique are threshold-major.
+ * pfq_sweep_absorb sums src's counters into dst's and zeroes src's (replicas of one database): the same conditions as
+ * pfq_coverage_absorb, plus bit-identical lists; otherwise PFQ_ERR_ARG. */
+#define PFQ_WANT_SWEEP 1024u
+#define PFQ_SWEEP_MAX 16
+int pfq_tree_set_sweep(pfq_tree *tree, const float *thresholds, uint32_t n);
+typedef struct pfq_sweep {
+    uint32_t n_thresholds;
+    const float *thresholds;
+    uint64_t n_leaves, n_units;
+    const uint64_t *leaf_units, *leaf_unique;                         /* [n_thresholds * n_leaves], threshold-major */
+    const uint64_t *units_hit, *units_unique, *entries, *genomes_hit; /* [n_thresholds] */
+} pfq_sweep;
+int pfq_sweep_get(pfq_tree *tree, pfq_sweep *out);
+int pfq_sweep_reset(pfq_tree *tree);
+int pfq_sweep_absorb(pfq_tree *dst, pfq_tree *src);
+
 /* ---- frames and segments (pfq_query_frames) ----
  * Where on a long sequence (an assembled contig, a long read) does a genome match?  Every sequence is cut into overlapping
  * frames of `frame` = F bases every `step` = S bases, k <= F and 1 <= S <= F (else PFQ_ERR_ARG); each frame is classified exactly

@@ -18,6 +18,7 @@ SYMBOLS = [
     "pfq_tree_set_taxonomy", "pfq_tree_taxa", "pfq_taxon_counts", "pfq_last_taxa", "pfq_last_best_rows", "pfq_db_leaf_ids", "pfq_taxonomy_read", "pfq_taxonomy_nodes",
     "pfq_abundance_estimate", "pfq_abundance_reset", "pfq_abundance_absorb",
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
+    "pfq_tree_set_sweep", "pfq_sweep_get", "pfq_sweep_reset", "pfq_sweep_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
     "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
@@ -92,6 +93,13 @@ class Coverage(C.Structure):
                 ("distinct", C.POINTER(C.c_double)), ("genome_kmers", C.POINTER(C.c_double))]
 
 
+class Sweep(C.Structure):
+    _fields_ = [("n_thresholds", C.c_uint32), ("thresholds", C.POINTER(C.c_float)), ("n_leaves", C.c_uint64), ("n_units", C.c_uint64),
+                ("leaf_units", C.POINTER(C.c_uint64)), ("leaf_unique", C.POINTER(C.c_uint64)),
+                ("units_hit", C.POINTER(C.c_uint64)), ("units_unique", C.POINTER(C.c_uint64)), ("entries", C.POINTER(C.c_uint64)),
+                ("genomes_hit", C.POINTER(C.c_uint64))]
+
+
 class Segment(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("leaf", "first_frame", "n_frames", "begin", "end", "match_begin", "match_end", "kmers",
                                           "matched", "longest_run")]
@@ -129,6 +137,8 @@ ABUND_Q = 16
 WANT_COVERAGE = 128
 WANT_TAXA = 256
 ROWS_BEST = 512
+WANT_SWEEP = 1024
+SWEEP_MAX = 16
 NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
@@ -193,6 +203,10 @@ def lib() -> C.CDLL:
     L.pfq_coverage_get.argtypes = [vp, C.POINTER(Coverage)]
     L.pfq_coverage_reset.argtypes = [vp]
     L.pfq_coverage_absorb.argtypes = [vp, vp]
+    L.pfq_tree_set_sweep.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32]
+    L.pfq_sweep_get.argtypes = [vp, C.POINTER(Sweep)]
+    L.pfq_sweep_reset.argtypes = [vp]
+    L.pfq_sweep_absorb.argtypes = [vp, vp]
     L.pfq_query_frames.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(Segments)]
     L.pfq_query_frames_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
                                           C.POINTER(Segments)]

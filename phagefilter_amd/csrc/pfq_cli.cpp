@@ -1291,6 +1291,38 @@ struct ServedDb {
         }
         if (fclose(f) != 0) die("short write to " + tsv);
     }
+    // --sweep: the list for every replica, before the first call; the library refuses a database that is not superset-verified
+    void set_sweep(const std::vector<float> &thr) {
+        for (pfq_tree *t : trees) check(pfq_tree_set_sweep(t, thr.data(), (uint32_t)thr.size()));
+    }
+    // --sweep: THRESHOLDS.tsv, one line per threshold, and THRESHOLD_GENOMES.tsv, one line per (genome, threshold) with reads, the
+    // genomes in leaf order like CLASSIFICATION.csv.  Every replica counted its own reads: the counters are summed into replica
+    // 0's.  typed: the thresholds as the user wrote them.
+    void save_sweep(const std::string &dir, const std::vector<std::string> &typed) {
+        for (size_t i = 1; i < trees.size(); ++i) check(pfq_sweep_absorb(trees[0], trees[i]));
+        pfq_sweep sw{};
+        check(pfq_sweep_get(trees[0], &sw));
+        if (sw.n_thresholds != typed.size()) die("--sweep: the library holds another threshold list");
+        const std::string tsv = dir + "/THRESHOLDS.tsv", per_genome = dir + "/THRESHOLD_GENOMES.tsv";
+        FILE *f = fopen(tsv.c_str(), "wb");
+        if (!f) die("cannot create " + tsv + ": " + strerror(errno));
+        fputs("#threshold\treads\treads_hit\treads_unique\tassignments\tgenomes_hit\n", f);
+        for (uint32_t t = 0; t < sw.n_thresholds; ++t)
+            fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\n", typed[t].c_str(), (unsigned long long)sw.n_units, (unsigned long long)sw.units_hit[t],
+                    (unsigned long long)sw.units_unique[t], (unsigned long long)sw.entries[t], (unsigned long long)sw.genomes_hit[t]);
+        if (fclose(f) != 0) die("short write to " + tsv);
+        f = fopen(per_genome.c_str(), "wb");
+        if (!f) die("cannot create " + per_genome + ": " + strerror(errno));
+        fputs("#genome\tthreshold\treads\tunique_reads\n", f);
+        for (uint64_t l = 0; l < sw.n_leaves; ++l)
+            for (uint32_t t = 0; t < sw.n_thresholds; ++t) {
+                const uint64_t reads = sw.leaf_units[t * sw.n_leaves + l];
+                if (reads)
+                    fprintf(f, "%s\t%s\t%llu\t%llu\n", leaf_names[l].c_str(), typed[t].c_str(), (unsigned long long)reads,
+                            (unsigned long long)sw.leaf_unique[t * sw.n_leaves + l]);
+            }
+        if (fclose(f) != 0) die("short write to " + per_genome);
+    }
     void close() {
         for (pfq_tree *t : trees) pfq_tree_close(t);
     }
@@ -1540,9 +1572,11 @@ struct QueryLoop {
     const bool taxonomy = false;   // --taxonomy: every call asks for the hits and counts its units on the taxonomy's nodes
     const bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv
     const bool best_hits = false;  // --best-hits: the three above take every unit's best-scoring genomes (the library is asked for hits and scores)
+    const bool sweep = false;      // --sweep: every call also counts its rows and scores against the threshold list (hits and scores, as --best-hits)
     uint32_t abundance_flags() const {
         return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
-               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u);
+               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u) |
+               (sweep ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP) : 0u);
     }
     uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
@@ -2229,7 +2263,7 @@ int cmd_query(int argc, char **argv) {
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
                              {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"taxonomy", 0, true},
-                             {"taxon-reads", 0, false}, {"best-hits", 0, false}};
+                             {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2252,6 +2286,45 @@ int cmd_query(int argc, char **argv) {
                 "partial hit row is not the row's best");
         if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--best-hits': it serves runs that only count");
         if (a.val.count("frame")) die("error: '--best-hits' cannot be used with '--frame': frames do not combine with per-read post-stages");
+    }
+    // --sweep T1,T2,..: one pass at -f also counts, per listed threshold, what a run of its own at that threshold would report
+    // (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP): THRESHOLDS.tsv and THRESHOLD_GENOMES.tsv; every other output stays what it
+    // is.  The values are parsed as -f is and kept as typed for the files.
+    const bool sweep = a.val.count("sweep") != 0;
+    std::vector<float> sweep_thr;
+    std::vector<std::string> sweep_typed;
+    if (sweep) {
+        for (const char *other : {"reads2", "shard-depth", "frame"})
+            if (a.val.count(other))
+                die(std::string("error: '--sweep' cannot be used with '--") + other + "'" +
+                    (other[0] == 'r'   ? ": a fragment's score is its mates' sum, so its hits at other thresholds do not follow from it"
+                     : other[0] == 's' ? ": a subtree shard sees only its own genomes, so the reads it would count are partial"
+                                       : ": frames do not combine with per-read post-stages"));
+        if (a.flags.count("interleaved"))
+            die("error: '--sweep' cannot be used with '--interleaved': a fragment's score is its mates' sum, so its hits at other thresholds do "
+                "not follow from it");
+        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--sweep': it serves runs that only count");
+        const std::string spec = a.val.at("sweep");
+        for (size_t p0 = 0; p0 <= spec.size();) {
+            size_t p1 = spec.find(',', p0);
+            if (p1 == std::string::npos) p1 = spec.size();
+            const std::string item = spec.substr(p0, p1 - p0);
+            if (item.empty()) die("error: invalid value '" + spec + "' for '--sweep': an empty item in the list of thresholds");
+            const float v = to_f32(item, "sweep");
+            if (v != v) die("error: invalid value '" + item + "' for '--sweep': not a number");
+            if (!sweep_thr.empty() && !(sweep_thr.back() < v))
+                die("error: invalid value '" + spec + "' for '--sweep': the thresholds must be strictly ascending ('" + sweep_typed.back() +
+                    "' before '" + item + "')");
+            if (!(threshold <= v))
+                die("error: '--sweep " + item + "' is below '--filter-threshold " + opt(a, "filter-threshold", "1.0") +
+                    "' (-f): the one pass runs at -f and cannot answer a lower threshold; lower -f to the list's lowest value");
+            sweep_thr.push_back(v);
+            sweep_typed.push_back(item);
+            p0 = p1 + 1;
+        }
+        if (sweep_thr.size() > PFQ_SWEEP_MAX)
+            die("error: invalid value '" + spec + "' for '--sweep': " + std::to_string(sweep_thr.size()) + " thresholds, at most " +
+                std::to_string(PFQ_SWEEP_MAX));
     }
     // --lca all|best: every read (fragment) is also assigned to the lowest common ancestor of its hit genomes (best: of the
     // genomes with its highest score): CLADE_COUNTS.tsv; --lca-reads: READ_LCA.tsv, one line per record with hits
@@ -2339,7 +2412,7 @@ int cmd_query(int argc, char **argv) {
         pfq_taxonomy_file tf{};
         check(pfq_taxonomy_read(a.val.at("taxonomy").c_str(), ids, n_ids, &tf));
     }
-    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage || taxonomy;  // the per-read hit lists are needed
+    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage || taxonomy || sweep;  // the per-read hit lists are needed
     const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
@@ -2392,6 +2465,7 @@ int cmd_query(int argc, char **argv) {
         printf("Search depth settings: %llu\n", (unsigned long long)depth);
         db.prune(depth);
     }
+    if (sweep) db.set_sweep(sweep_thr);  // (before any read is classified: a database that is not superset-verified is refused here)
     ReadQueue rq(reads, ov);
     std::unique_ptr<ReadQueue> rq2;
     if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
@@ -2422,7 +2496,7 @@ int cmd_query(int argc, char **argv) {
     if (taxonomy) db.set_taxonomy(a.val.at("taxonomy"));
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits, sweep};
     if (block == 0) {
         // nothing to do: see above
     } else if (framed) {
@@ -2455,6 +2529,7 @@ int cmd_query(int argc, char **argv) {
     if (abundance) db.save_abundance(out + "/ABUNDANCE.tsv", (uint32_t)abundance_iters);
     if (coverage) db.save_coverage(out + "/COVERAGE.tsv");
     if (taxonomy) db.save_taxon_counts(out + "/TAXON_COUNTS.tsv", abundance, (uint32_t)abundance_iters);
+    if (sweep) db.save_sweep(out, sweep_typed);
     db.close();
     printf("Finished.\n");
     return 0;
@@ -2964,6 +3039,15 @@ void usage() {
             "READ_SCORES.tsv, CLADE_COUNTS.tsv, READ_LCA.tsv and the hits column of READ_TAXA.tsv (the size of the whole hit set) stay as\n"
             "they are.  At -f 1 it changes nothing.  Works with --reads2 / --interleaved and --devices.  Not with --shard-depth, --frame or\n"
             "--device-parse\n"
+            "--sweep <T1,T2,..> (1 to 16 thresholds, strictly ascending, none below -f): choosing -f otherwise costs one whole run per\n"
+            "candidate.  With this option the one pass at -f also counts, per listed threshold, what a run of its own at that threshold\n"
+            "would report, from the hits and scores the GPU already holds.  THRESHOLDS.tsv: \"#threshold<TAB>reads<TAB>reads_hit<TAB>\n"
+            "reads_unique<TAB>assignments<TAB>genomes_hit\", one line per threshold: the reads POS filtering would keep, those that name one\n"
+            "genome only, the (read, genome) pairs and the genomes with a read.  THRESHOLD_GENOMES.tsv: \"#genome<TAB>threshold<TAB>reads\n"
+            "<TAB>unique_reads\", one line per genome and threshold with reads, genomes in CLASSIFICATION.csv's order: reads is that run's\n"
+            "CLASSIFICATION.csv count.  Every other output stays as it is.  Works with --devices.  Needs a database whose parent filters\n"
+            "contain their children's (every database build, add and recluster make).  Not with --reads2, --interleaved, --shard-depth,\n"
+            "--frame or --device-parse\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

@@ -110,6 +110,7 @@ struct Knobs {
     long long sim_slices = -1, sim_naive = -1, sim_time = -1;  // pfq_tree_similarity: slices of the filter words (0 / unset: built-in); 1: the one-block-per-pair kernel; 1: time the kernel
     long long cluster_time = -1;                // pfq_tree_recluster: 1: time the stages with HIP events (pfq_debug_last_recluster)
     long long text_tile = -1;                   // pfq_text_parse: bytes of text a block scans (a power of two, 256 .. the built-in 8192)
+    long long sweep_lds = -1;                   // PFQ_WANT_SWEEP: 0: count `pass` with global atomics although its bins fit the block's LDS
 };
 struct KnobName {
     const char *name;
@@ -141,7 +142,7 @@ const KnobName KNOBS[] = {
     {"PFQ_FRAME_PIECE", &Knobs::frame_piece},
     {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
-    {"PFQ_TEXT_TILE", &Knobs::text_tile},
+    {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -442,6 +443,18 @@ struct pfq_tree {
     bool best_last = false;                // the last query call set PFQ_ROWS_BEST
     bool best_built = false;               // ... and built rows (else: every best row is empty)
     uint64_t best_units = 0;
+    // PFQ_WANT_SWEEP: the list (pfq_tree_set_sweep) and the counters of the flagged calls, one buffer of u64 sized for sw_nl
+    // leaves and T thresholds: pass [(T + 1) * sw_nl] | uniq [T * sw_nl] | tops [T + 1] (sweep_ensure makes it, zeroed;
+    // pfq_tree_prune and pfq_tree_insert drop it, and the next use makes it anew for the new leaves).  sw_units: units counted
+    // (those of calls that built no row are counted here only: they belong to tops[0], which no read-out uses).  d_sw_long /
+    // d_sw_cur: a call's queue of long rows.
+    std::vector<float> sw_thr;
+    DevBuf<unsigned long long> d_sw_state, d_sw_cur;
+    DevBuf<uint32_t> d_sw_long;
+    size_t sw_nl = 0;
+    uint64_t sw_units = 0;
+    std::vector<uint64_t> out_sw_leaf_units, out_sw_leaf_unique, out_sw_sums;
+    std::vector<float> out_sw_thr;
 };
 
 namespace {
@@ -1145,6 +1158,47 @@ int tax_zero(pfq_tree &t) {
 }
 static_assert(pfq::TAX_NO_NODE == PFQ_NO_CLADE, "pfq.h and pfq_kernels.h disagree about \"no node\"");
 
+// ---- PFQ_WANT_SWEEP: the counters of the threshold list (pfq_tree::d_sw_state) ----
+static_assert(pfq::SWEEP_MAX == PFQ_SWEEP_MAX, "pfq.h and pfq_kernels.h disagree about the longest sweep list");
+size_t sweep_words(size_t n_thr, size_t nl) { return (2 * n_thr + 1) * nl + n_thr + 1; }
+// Gives the counters' memory back (hipFree waits for the device); the list stays.
+void sweep_drop(pfq_tree &t) {
+    t.d_sw_state.release();
+    t.sw_nl = 0;
+    t.sw_units = 0;
+}
+// The counters of the list over nl leaves, zeroed on `st` if they are made here.  No list: nothing.
+int sweep_ensure(pfq_tree &t, size_t nl, hipStream_t st) {
+    if (t.sw_thr.empty() || (t.d_sw_state.p && t.sw_nl == nl)) return PFQ_OK;
+    sweep_drop(t);
+    const size_t words = sweep_words(t.sw_thr.size(), nl);
+    if ((t.sw_thr.size() + 1) * nl >= (1ull << 32) || t.d_sw_state.ensure(words) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PFQ_ERR_DEVICE, "no device memory for the threshold sweep's counters (" + std::to_string(words * 8) + " bytes: " + std::to_string(nl) +
+                                    " leaves, " + std::to_string(t.sw_thr.size()) + " thresholds)");
+    }
+    t.sw_nl = nl;
+    HIP_TRY(hipMemsetAsync(t.d_sw_state.p, 0, words * 8, st));
+    return PFQ_OK;
+}
+// Zeroes the counters; the device is idle.
+int sweep_zero(pfq_tree &t) {
+    if (t.d_sw_state.p) HIP_TRY(hipMemset(t.d_sw_state.p, 0, sweep_words(t.sw_thr.size(), t.sw_nl) * 8));
+    t.sw_units = 0;
+    return PFQ_OK;
+}
+// Why a tree cannot be swept (pfq.h "threshold sweep"); PFQ_OK: it can.
+int sweep_refused(const pfq_tree &t, const char *what) {
+    if (t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, std::string(what) + " on a subtree shard: a shard sees only its own leaves, so the units and the unique rows "
+                                         "it would count are partial");
+    if (!t.superset_all)
+        return fail(PFQ_ERR_UNSUPPORTED, std::string(what) + " on a tree that is not superset-verified (pfq_info.superset_verified == 0): a read can "
+                                         "fail a higher threshold at an ancestor whose score is not in its row, so the rows of the lowest "
+                                         "threshold do not answer the others");
+    return PFQ_OK;
+}
+
 // ---- PFQ_WANT_COVERAGE: the per-leaf sketches (pfq_tree::d_cov_*) ----
 // The precision a new sketch gets: the option PFQ_COVER_P where it is in range (pfq_set_option refuses other values; one from
 // the environment that is out of range counts as unset).
@@ -1280,7 +1334,7 @@ struct QueryRun {
     pfq_hits *hits;
     const Knobs &kn;
     // ---- the plan
-    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, rows_best = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
+    bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, rows_best = false, want_sweep = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
@@ -1320,6 +1374,8 @@ struct QueryRun {
         want_cover = (flags & PFQ_WANT_COVERAGE) != 0;
         want_taxa = (flags & PFQ_WANT_TAXA) != 0;
         rows_best = (flags & PFQ_ROWS_BEST) != 0;
+        want_sweep = (flags & PFQ_WANT_SWEEP) != 0;
+        if (want_sweep) PFQ_TRY(sweep_refused(t, "PFQ_WANT_SWEEP"));  // (the list was set on a tree that has changed since)
         if (want_taxa && (!t.tax_set || t.tax.rank.size() != t.leaves.size()))
             return fail(PFQ_ERR_STATE, "PFQ_WANT_TAXA without a taxonomy: pfq_tree_set_taxonomy first (pfq_tree_prune and pfq_tree_insert drop it)");
         if (want_lca) PFQ_TRY(ensure_lca(t));
@@ -1334,6 +1390,7 @@ struct QueryRun {
         PFQ_TRY(ensure_scratch(t, n_reads, want_hits));
         nl = t.leaves.size();
         if (want_cover) PFQ_TRY(cover_ensure(t, nl, st));  // (before anything of the call runs: a failure sketches nothing)
+        if (want_sweep) PFQ_TRY(sweep_ensure(t, nl, st));
         if (paired || frames) HIP_TRY(t.d_pair_sink.ensure(nl + 1));
         nc = t.n_cols;  // leaf + guard columns = buckets of the bucketed path (block mode: blocks of 8 leaf columns)
         with_guards = !t.guard_col.empty();
@@ -2110,6 +2167,7 @@ struct QueryRun {
                 use_leaves = t.d_best_leaves.p;
             }
         }
+        if (want_sweep) PFQ_TRY(sweep_rows(off, leaves, n_units));  // (the whole rows, whatever PFQ_ROWS_BEST says)
         if (want_cover) PFQ_TRY(cover_sketch(use_off, use_leaves, n_units, total, pair_mode));
         if (want_taxa && off) PFQ_TRY(tax_rows(use_off, use_leaves, n_units));
         if (total) HIP_TRY(hipStreamSynchronize(st));
@@ -2140,6 +2198,37 @@ struct QueryRun {
         HIP_TRY(hipMemsetAsync(t.d_best_cur.p, 0, 8, st));
         pfq::launch_best_rows(off, leaves, t.d_hit_scores.p, n_units, t.d_best_cnt.p, t.d_best_sums.p, t.d_best_long.p, t.d_best_cur.p,
                               t.d_best_off.p, t.d_best_leaves.p, st);
+        HIP_TRY(hipGetLastError());
+        return PFQ_OK;
+    }
+
+    // PFQ_WANT_SWEEP: the rows of the call's final CSR and their scores are counted against the tree's threshold list (pfq.h
+    // "threshold sweep"), once: deliver_rows() runs for the attempt that stands.  Queued behind the score kernel (check_flags has
+    // made sure of the scores and of reads, not fragments) and before deliver_rows' wait, which so covers the kernels' reads of
+    // d_off.  No row built: the units have empty rows and are counted in sw_units alone.
+    int sweep_rows(const unsigned long long *off, const uint32_t *leaves, uint64_t n_units) {
+        t.sw_units += n_units;
+        if (!off || !n_units) return PFQ_OK;
+        HIP_TRY(t.d_sw_long.ensure(n_units));
+        HIP_TRY(t.d_sw_cur.ensure(1));
+        HIP_TRY(hipMemsetAsync(t.d_sw_cur.p, 0, 8, st));
+        const size_t n_thr = t.sw_thr.size();
+        pfq::SweepArgs a{};
+        a.off = off;
+        a.leaves = leaves;
+        a.scores = t.d_hit_scores.p;
+        a.read_off = d_off;
+        a.n_units = n_units;
+        a.k = t.hp.k;
+        a.n_thr = (uint32_t)n_thr;
+        a.n_leaves = (uint32_t)nl;
+        std::copy(t.sw_thr.begin(), t.sw_thr.end(), a.thr);
+        a.pass = t.d_sw_state.p;
+        a.uniq = a.pass + (n_thr + 1) * nl;
+        a.tops = a.uniq + n_thr * nl;
+        a.long_list = t.d_sw_long.p;
+        a.n_long = t.d_sw_cur.p;
+        pfq::launch_sweep(a, kn.sweep_lds != 0, st);
         HIP_TRY(hipGetLastError());
         return PFQ_OK;
     }
@@ -2854,6 +2943,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
+    sweep_drop(t);        // (the list stays: the counters are made anew for the new leaves)
     tax_clear(t);         // (the taxonomy described the leaves as they were)
     t.cov_bits_valid = false;
     t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
@@ -3152,6 +3242,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_hit_pairs.bytes() + t.d_seq.bytes() + t.d_off.bytes() + t.d_recs.bytes() + t.d_entries.bytes() +
                         t.d_ab_start.bytes() + t.d_ab_len.bytes() + t.d_ab_entries.bytes() + t.d_ab_unique.bytes() +  // (the abundance log)
                         t.d_cov_regs.bytes() + t.d_cov_cnt.bytes() +                                                  // (the coverage sketch)
+                        t.d_sw_state.bytes() +                                                                        // (the threshold sweep)
                         t.d_tax_rank.bytes() + t.d_tax_leaf_node.bytes() + t.d_tax_parent.bytes() + t.d_tax_first.bytes() +   // (the taxonomy)
                         t.d_tax_gap_min.bytes() + t.d_tax_here.bytes() + t.d_tax_any.bytes() + t.d_tax_misc.bytes() +
                         t.d_fr_bytes.bytes() + t.d_fr_foff.bytes() + t.d_fr_seq.bytes() + t.d_fr_start.bytes() + t.d_fr_segpos.bytes() +  // (pfq_query_frames)
@@ -3178,6 +3269,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
+    sweep_drop(t);        // (the list stays: the counters are made anew for the new leaves)
     tax_clear(t);         // (the taxonomy described the leaves as they were)
     t.cov_bits_valid = false;
     t.merges.clear();     // (a re-clustered tree's merge log describes the shape it was given)
@@ -3232,7 +3324,7 @@ static int stage_input(pfq_tree &t, const uint8_t *seq, const uint64_t *offsets,
 }
 
 // Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
-static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
+static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads, float threshold) {
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
@@ -3242,6 +3334,16 @@ static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
     if ((flags & PFQ_ROWS_BEST) && t.is_shard)
         return fail(PFQ_ERR_UNSUPPORTED, "PFQ_ROWS_BEST on a subtree shard: a shard sees only its own leaves, and the best of a partial row "
                                          "is not the row's best");
+    if (flags & PFQ_WANT_SWEEP) {
+        if (~flags & (PFQ_WANT_HITS | PFQ_WANT_SCORES)) return fail(PFQ_ERR_ARG, "PFQ_WANT_SWEEP needs PFQ_WANT_HITS | PFQ_WANT_SCORES");
+        if (flags & PFQ_PAIRED)
+            return fail(PFQ_ERR_ARG, "PFQ_WANT_SWEEP with PFQ_PAIRED: a fragment's score is its mates' sum and its row a union or an intersection "
+                                     "of per-mate decisions, so its rows at other thresholds do not follow from them");
+        if (t.sw_thr.empty()) return fail(PFQ_ERR_STATE, "PFQ_WANT_SWEEP without a threshold list: pfq_tree_set_sweep first");
+        if (!(threshold <= t.sw_thr[0]))
+            return fail(PFQ_ERR_ARG, "PFQ_WANT_SWEEP: the call's threshold (" + std::to_string(threshold) + ") must not be above the list's lowest (" +
+                                     std::to_string(t.sw_thr[0]) + "): the rows of a higher threshold lack entries the lower ones have");
+    }
     if ((flags & PFQ_WANT_TAXA) && !(flags & PFQ_WANT_HITS)) return fail(PFQ_ERR_ARG, "PFQ_WANT_TAXA needs PFQ_WANT_HITS");
     if ((flags & PFQ_WANT_TAXA) && t.is_shard)
         return fail(PFQ_ERR_UNSUPPORTED, "PFQ_WANT_TAXA on a subtree shard: a shard sees only its own leaves, so its rows are partial");
@@ -3262,7 +3364,7 @@ static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads) {
 int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t *d_offsets, uint64_t n_reads,
                            uint64_t total_bytes, float threshold, uint32_t flags, void *stream, pfq_hits *hits) {
     if (!tree || (n_reads && (!d_seq || !d_offsets))) return fail(PFQ_ERR_ARG, "null argument");
-    PFQ_TRY(check_flags(*tree, flags, n_reads));
+    PFQ_TRY(check_flags(*tree, flags, n_reads, threshold));
     PFQ_TRY(use_device(tree->device));
     return query_device(*tree, d_seq, d_offsets, n_reads, total_bytes, threshold, flags, (hipStream_t)stream, hits);
 }
@@ -3270,7 +3372,7 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
 int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets, uint64_t n_reads, float threshold,
                     uint32_t flags, pfq_hits *hits) {
     if (!tree || (n_reads && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
-    PFQ_TRY(check_flags(*tree, flags, n_reads));
+    PFQ_TRY(check_flags(*tree, flags, n_reads, threshold));
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
     uint64_t total = n_reads ? offsets[n_reads] : 0;
@@ -3445,7 +3547,7 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
 
 int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits) {
     if (!tree) return fail(PFQ_ERR_ARG, "null argument");
-    PFQ_TRY(check_flags(*tree, flags, tree->tx_records));
+    PFQ_TRY(check_flags(*tree, flags, tree->tx_records, threshold));
     if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_text_query before a pfq_text_parse on this tree");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
@@ -3807,6 +3909,126 @@ int pfq_coverage_absorb(pfq_tree *dst, pfq_tree *src) {
     cover_clear(s);
     PFQ_TRY(use_device(d.device));
     return PFQ_OK;
+}
+
+// ---- threshold sweep (pfq.h "threshold sweep") ----
+int pfq_tree_set_sweep(pfq_tree *tree, const float *thresholds, uint32_t n) {
+    if (!tree || (n && !thresholds)) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    if (n == 0) {
+        PFQ_TRY(insertion_error(t));
+        HIP_TRY(hipDeviceSynchronize());
+        t.sw_thr.clear();
+        sweep_drop(t);
+        return PFQ_OK;
+    }
+    if (n > PFQ_SWEEP_MAX) return fail(PFQ_ERR_ARG, "pfq_tree_set_sweep: " + std::to_string(n) + " thresholds, at most " + std::to_string(PFQ_SWEEP_MAX));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (thresholds[i] != thresholds[i]) return fail(PFQ_ERR_ARG, "pfq_tree_set_sweep: threshold " + std::to_string(i) + " is not a number");
+        if (i && !(thresholds[i - 1] < thresholds[i]))
+            return fail(PFQ_ERR_ARG, "pfq_tree_set_sweep: the thresholds must be strictly ascending (" + std::to_string(thresholds[i - 1]) + " before " +
+                                     std::to_string(thresholds[i]) + ")");
+    }
+    PFQ_TRY(finish_topology(t));
+    if (t.root < 0) return fail(PFQ_ERR_STATE, "pfq_tree_set_sweep on an empty tree");
+    PFQ_TRY(sweep_refused(t, "pfq_tree_set_sweep"));
+    PFQ_TRY(build_layout(t));
+    HIP_TRY(hipDeviceSynchronize());
+    sweep_drop(t);
+    t.sw_thr.assign(thresholds, thresholds + n);
+    const int rc = sweep_ensure(t, t.leaves.size(), nullptr);
+    if (rc != PFQ_OK) t.sw_thr.clear();
+    PFQ_TRY(rc);
+    HIP_TRY(hipDeviceSynchronize());  // (the counters are zero before a call on any stream adds to them)
+    return PFQ_OK;
+}
+
+int pfq_sweep_reset(pfq_tree *tree) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    HIP_TRY(hipDeviceSynchronize());
+    return sweep_zero(*tree);
+}
+
+int pfq_sweep_get(pfq_tree *tree, pfq_sweep *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    HIP_TRY(hipDeviceSynchronize());  // the queued counts
+    const size_t nl = t.leaves.size(), n_thr = t.sw_thr.size();
+    std::vector<uint64_t> st(sweep_words(n_thr, nl), 0);
+    if (t.d_sw_state.p && t.sw_nl == nl) HIP_TRY(hipMemcpy(st.data(), t.d_sw_state.p, st.size() * 8, hipMemcpyDeviceToHost));
+    const uint64_t *pass = st.data(), *uniq = pass + (n_thr + 1) * nl, *tops = uniq + n_thr * nl;
+    t.out_sw_thr = t.sw_thr;
+    t.out_sw_thr.push_back(0.0f);
+    t.out_sw_leaf_units.assign(n_thr * nl + 1, 0);
+    t.out_sw_leaf_unique.assign(n_thr * nl + 1, 0);
+    t.out_sw_sums.assign(4 * n_thr + 1, 0);
+    uint64_t *hit = t.out_sw_sums.data(), *unique = hit + n_thr, *entries = unique + n_thr, *genomes = entries + n_thr;
+    for (size_t th = n_thr; th-- > 0;) {  // leaf_units[th] = leaf_units[th + 1] + pass[th + 1], from the top
+        uint64_t *row = t.out_sw_leaf_units.data() + th * nl;
+        for (size_t l = 0; l < nl; ++l) {
+            row[l] = pass[(th + 1) * nl + l] + (th + 1 < n_thr ? row[nl + l] : 0);
+            t.out_sw_leaf_unique[th * nl + l] = uniq[th * nl + l];
+            entries[th] += row[l];
+            genomes[th] += row[l] != 0;
+            unique[th] += uniq[th * nl + l];
+        }
+        hit[th] = tops[th + 1] + (th + 1 < n_thr ? hit[th + 1] : 0);
+    }
+    memset(out, 0, sizeof *out);
+    out->n_thresholds = (uint32_t)n_thr;
+    out->thresholds = t.out_sw_thr.data();
+    out->n_leaves = nl;
+    out->n_units = n_thr ? t.sw_units : 0;
+    out->leaf_units = t.out_sw_leaf_units.data();
+    out->leaf_unique = t.out_sw_leaf_unique.data();
+    out->units_hit = hit;
+    out->units_unique = unique;
+    out->entries = entries;
+    out->genomes_hit = genomes;
+    return PFQ_OK;
+}
+
+int pfq_sweep_absorb(pfq_tree *dst, pfq_tree *src) {
+    if (!dst || !src) return fail(PFQ_ERR_ARG, "null argument");
+    if (dst == src) return fail(PFQ_ERR_ARG, "pfq_sweep_absorb: dst and src are one tree");
+    pfq_tree &d = *dst, &s = *src;
+    PFQ_TRY(use_device(s.device));
+    PFQ_TRY(build_layout(s));
+    HIP_TRY(hipDeviceSynchronize());
+    PFQ_TRY(use_device(d.device));
+    PFQ_TRY(build_layout(d));
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t nl = d.leaves.size(), n_thr = d.sw_thr.size();
+    if (s.leaves.size() != nl || d.is_shard != s.is_shard || d.shard_first_leaf != s.shard_first_leaf)
+        return fail(PFQ_ERR_ARG, "pfq_sweep_absorb: the trees do not hold the same leaves (" + std::to_string(nl) + " and " +
+                                 std::to_string(s.leaves.size()) + ")");
+    if (d.hp.k != s.hp.k || d.hp.num_hashes != s.hp.num_hashes || d.hp.nbits != s.hp.nbits || d.hp.a1 != s.hp.a1 || d.hp.a2 != s.hp.a2)
+        return fail(PFQ_ERR_ARG, "pfq_sweep_absorb: the trees differ in their hash parameters");
+    if (s.sw_thr.size() != n_thr || (n_thr && memcmp(s.sw_thr.data(), d.sw_thr.data(), n_thr * sizeof(float))))
+        return fail(PFQ_ERR_ARG, "pfq_sweep_absorb: the trees' threshold lists differ");
+    if (!n_thr) return PFQ_OK;
+    if (s.d_sw_state.p && s.sw_nl == nl) {
+        PFQ_TRY(sweep_ensure(d, nl, nullptr));  // (nothing was absorbed if this fails)
+        // staged through host memory: the replicas may sit on different devices, and this runs once per job
+        const size_t words = sweep_words(n_thr, nl);
+        std::vector<unsigned long long> hs(words), hd(words);
+        PFQ_TRY(use_device(s.device));
+        HIP_TRY(hipMemcpy(hs.data(), s.d_sw_state.p, words * 8, hipMemcpyDeviceToHost));
+        PFQ_TRY(use_device(d.device));
+        HIP_TRY(hipDeviceSynchronize());  // (the zeroing of counters made just now)
+        HIP_TRY(hipMemcpy(hd.data(), d.d_sw_state.p, words * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < words; ++i) hd[i] += hs[i];
+        HIP_TRY(hipMemcpy(d.d_sw_state.p, hd.data(), words * 8, hipMemcpyHostToDevice));
+    }
+    d.sw_units += s.sw_units;
+    PFQ_TRY(use_device(s.device));
+    const int rc = sweep_zero(s);
+    PFQ_TRY(use_device(d.device));
+    return rc;
 }
 
 // ---- pfq_tree_similarity ----
@@ -4538,6 +4760,7 @@ int pfq_leaf_counts_reset(pfq_tree *tree) {
     for (auto &nd : tree->nodes) nd.mapped_reads = nd.base_reads = 0;
     abund_clear(*tree);
     cover_clear(*tree);
+    PFQ_TRY(sweep_zero(*tree));
     return PFQ_OK;
 }
 

@@ -405,6 +405,27 @@ void launch_lca_best(const unsigned long long *d_off, const uint32_t *d_leaves, 
 void launch_best_rows(const unsigned long long *d_off, const uint32_t *d_leaves, const uint32_t *d_scores, uint64_t n_units, uint32_t *d_cnt,
                       unsigned long long *d_sums, uint32_t *d_long, unsigned long long *d_n_long, unsigned long long *d_best_off,
                       uint32_t *d_best_leaves, hipStream_t st);
+// PFQ_WANT_SWEEP (pfq_sweep.hip): the rows of the ascending CSR off / leaves [n_units] of reads, scored by scores (one score per
+// entry), counted against the n_thr ascending thresholds thr (pfq.h "threshold sweep"): per entry pass[p * n_leaves + leaf] += 1
+// with p = the thresholds whose need_kmers(thr[t], the read's k-mers) the score reaches; per unit tops[max p] += 1 and
+// uniq[t * n_leaves + arg] += 1 for second <= t < max p.  read_off [n_units + 1]: the reads' offsets (for their lengths), k: the
+// k-mer size.  long_list [n_units] and n_long [1] zeroed by the caller: the queue of rows a wave takes.  lds: count `pass` in the
+// block's LDS where its (n_thr + 1) * n_leaves bins fit; needs (n_thr + 1) * n_leaves < 2^32.  n_units = 0: nothing runs.
+constexpr uint32_t SWEEP_MAX = 16;          // (PFQ_SWEEP_MAX)
+constexpr uint32_t SWEEP_GRID_ROWS = 1024;  // blocks of 256 threads of the thread-per-row kernel: units of one grid trip / 256
+constexpr uint32_t SWEEP_GRID_LONG = 1024;  // blocks of WAVES_PER_BLOCK waves of the wave-per-row kernel
+struct SweepArgs {
+    const unsigned long long *off;
+    const uint32_t *leaves, *scores;
+    const uint64_t *read_off;
+    uint64_t n_units;
+    uint32_t k, n_thr, n_leaves;
+    float thr[SWEEP_MAX];
+    unsigned long long *pass, *uniq, *tops;
+    uint32_t *long_list;
+    unsigned long long *n_long;
+};
+void launch_sweep(const SweepArgs &a, bool lds, hipStream_t st);
 // PFQ_WANT_TAXA (pfq_tax.hip): the units of the call's final ascending CSR d_off / d_leaves [n_units] counted on the nodes of the
 // user's taxonomy (pfq.h "taxonomy"): d_node[u] = the deepest node above every leaf of row u (TAX_NO_NODE: an empty row),
 // here[that node] += 1, any[t] += 1 for every node t above at least one leaf of the row.  The tables describe the current leaf

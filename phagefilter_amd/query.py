@@ -229,7 +229,7 @@ class BloomTree:
     def query_packed(self, seq: np.ndarray, off: np.ndarray, threshold: float, want_hits: bool = False,
                      want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
                      lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
-                     best: bool = False):
+                     best: bool = False, sweep: bool = False):
         """One block of reads from host memory.  Returns None, the (offsets, leaves) CSR, or with `want_scores`
         (offsets, leaves, scores): scores[j] = how many of the read's k-mers leaf leaves[j] contains (pfq_last_hit_scores).
         `paired`: reads 2i and 2i + 1 are mates (PFQ_PAIRED); rows, counts and scores are per fragment, whose set is the union
@@ -242,9 +242,11 @@ class BloomTree:
         `taxa`: every read / fragment is also counted on the nodes of the taxonomy set_taxonomy() gave (needs want_hits):
         last_taxa(), taxon_counts().
         `best`: `abundance`, `coverage` and `taxa` take every read's / fragment's best-scoring genomes instead of its whole row
-        (PFQ_ROWS_BEST; needs want_hits and want_scores); last_best_rows() gives those rows.  Everything else stays what it is."""
+        (PFQ_ROWS_BEST; needs want_hits and want_scores); last_best_rows() gives those rows.  Everything else stays what it is.
+        `sweep`: the rows and scores are also counted against the list set_sweep() gave (PFQ_WANT_SWEEP; needs want_hits and
+        want_scores, reads only, `threshold` at most the list's lowest): sweep()."""
         lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
-                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores))
+                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores) | _sweep_flags(sweep, want_hits, want_scores))
         n = len(off) - 1
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -294,11 +296,11 @@ class BloomTree:
 
     def query_text(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
                    pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
-                   best: bool = False):
+                   best: bool = False, sweep: bool = False):
         """Classifies the block parse_text() parsed last, exactly as query_packed() classifies the same reads from host memory
         (pfq_text_query); same keywords, same return value.  May be repeated: the counters grow each time."""
         lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
-                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores))
+                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores) | _sweep_flags(sweep, want_hits, want_scores))
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
         _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
@@ -353,14 +355,14 @@ class BloomTree:
     def query_device_hits(self, d_seq: int, d_off: int, n_reads: int, total_bytes: int, threshold: float, stream: int = 0,
                           want_scores: bool = False, paired: bool = False, pair_mode: str = "either",
                           lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
-                          best: bool = False):
+                          best: bool = False, sweep: bool = False):
         """The same block with PFQ_WANT_HITS: synchronous, returns the CSR (offsets, leaves) — with `want_scores`
         (offsets, leaves, scores) — as views of the library's buffers (valid until the next call on this tree).
-        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, `taxa`, `best`, as in query_packed."""
+        `paired`: one row per fragment (reads 2i, 2i + 1), `lca`: None, "all" or "best", `abundance`, `coverage`, `taxa`, `best`, `sweep`, as in query_packed."""
         hits = _ffi.Hits()
         flags = (_ffi.WANT_HITS | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) |
                  _lca_flags(lca, True, want_scores) | _abundance_flags(abundance, True) | _coverage_flags(coverage, True) | _taxa_flags(taxa, True) |
-                 _best_flags(best, True, want_scores))
+                 _best_flags(best, True, want_scores) | _sweep_flags(sweep, True, want_scores))
         _ffi.check(_ffi.lib().pfq_query_batch_device(self._h, d_seq, d_off, n_reads, total_bytes, threshold, flags,
                                                      stream, C.byref(hits)))
         n_reads = int(hits.n_reads)
@@ -519,6 +521,44 @@ class BloomTree:
         this tree's (registers: element-wise max, counters: sums) and empties it."""
         _ffi.check(_ffi.lib().pfq_coverage_absorb(self._h, other._h))
 
+    # ---- threshold sweep (PFQ_WANT_SWEEP)
+    def set_sweep(self, thresholds: Sequence[float]) -> None:
+        """Sets the list of thresholds (1 to _ffi.SWEEP_MAX floats, strictly ascending) the `sweep=True` calls count against
+        (pfq_tree_set_sweep) and zeroes the counters; an empty list drops it.  Refused on a tree that is not superset-verified
+        and on a subtree shard."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+        if thr.ndim != 1:
+            raise ValueError("thresholds must be a flat sequence of floats")
+        _ffi.check(_ffi.lib().pfq_tree_set_sweep(self._h, thr.ctypes.data_as(C.POINTER(C.c_float)), len(thr)))
+
+    def sweep(self) -> dict:
+        """Per threshold of the list what a query of its own at that threshold would have counted for the reads of the
+        `sweep=True` calls so far (pfq_sweep_get), as numpy arrays: `thresholds` float32 (T,); `leaf_units` (the leaf counters'
+        increase) and `leaf_unique` (reads that list that genome alone) uint64 (T, n_leaves) in the leaf order of
+        get_leaf_counts; `units_hit` (reads with a hit), `units_unique` (reads with one genome), `entries` (listed (read,
+        genome) pairs), `genomes_hit` uint64 (T,); and the ints `n_leaves`, `n_units`.  The counters are not consumed."""
+        c = _ffi.Sweep()
+        _ffi.check(_ffi.lib().pfq_sweep_get(self._h, C.byref(c)))
+        t, n = int(c.n_thresholds), int(c.n_leaves)
+
+        def arr(ptr, shape, dtype):
+            return np.ctypeslib.as_array(ptr, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dtype)
+        out = {"n_leaves": n, "n_units": int(c.n_units), "thresholds": arr(c.thresholds, (t,), np.float32)}
+        for k in ("leaf_units", "leaf_unique"):
+            out[k] = arr(getattr(c, k), (t, n), np.uint64)
+        for k in ("units_hit", "units_unique", "entries", "genomes_hit"):
+            out[k] = arr(getattr(c, k), (t,), np.uint64)
+        return out
+
+    def sweep_reset(self) -> None:
+        """Zeroes the sweep's counters and keeps the list (reset_counts does so as well)."""
+        _ffi.check(_ffi.lib().pfq_sweep_reset(self._h))
+
+    def sweep_absorb(self, other: "BloomTree") -> None:
+        """Adds the sweep counters of `other`, a replica of this database (on any device) with the same list, to this tree's
+        and zeroes them there."""
+        _ffi.check(_ffi.lib().pfq_sweep_absorb(self._h, other._h))
+
     # ---- genome similarity
     def similarity(self, other: Optional["BloomTree"] = None, leaves_a: Optional[Sequence[int]] = None,
                    leaves_b: Optional[Sequence[int]] = None) -> dict:
@@ -632,6 +672,14 @@ def _best_flags(best: bool, want_hits: bool, want_scores: bool) -> int:
     if not (want_hits and want_scores):
         raise ValueError("best=True needs the hits and their scores (want_hits=True, want_scores=True)")
     return _ffi.ROWS_BEST
+
+
+def _sweep_flags(sweep: bool, want_hits: bool, want_scores: bool) -> int:
+    if not sweep:
+        return 0
+    if not (want_hits and want_scores):
+        raise ValueError("sweep=True needs the hits and their scores (want_hits=True, want_scores=True)")
+    return _ffi.WANT_SWEEP
 
 
 def _abundance_flags(abundance: bool, want_hits: bool) -> int:
