@@ -570,6 +570,66 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
 int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits);
 int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /* tests: the parsed CSR copied to the host */
 
+/* ---- read preprocessing (pfq_prep_reads, pfq_prep_query) ----
+ * What a trimmer in front of a classifier does — low-quality and poly-X tails cut, reads that are too short, mostly N or of
+ * low complexity dropped — on the device, into the block a query call takes.  Integers only; the result for a read is a pure
+ * function of that read (for a fragment: of its two mates).
+ * Per read: bases s[0, L); optionally qualities q[0, L), Phred+33: p[j] = max(q[j] - 33, 0).  up(c) = c & 0xDF; a base is an N
+ * when up(c) is none of A C G T.  The steps, in this order, give a kept interval [b, e), starting from [0, L):
+ *   1. Quality (only if trim_quality = Q > 0 and the read has qualities).  Leading: b = min{ j : p[j] >= Q }; none: the interval
+ *      is empty.  Sliding window: w = min(trim_window, L - b); for i = b .. L - w, window i is bad iff p[i] + .. + p[i + w - 1] <
+ *      Q w; e = the first bad i, or L if no window is bad.  Trailing: e = 1 + max{ j in [b, e) : p[j] >= Q }; none: empty.
+ *   2. Poly-X tail (only if poly_x = P > 0 and the interval is not empty): r = the length of the longest suffix of [b, e) whose
+ *      bytes all equal up(s[e - 1]) under up; if r >= P then e -= r.  Applied once.
+ *   3. len = e - b; an empty interval is reported as begin = 0, len = 0.
+ *   4. The reason, the first that applies: PFQ_PREP_SHORT: len < min_length; PFQ_PREP_N: more than max_n N bases in [b, e)
+ *      (0xffffffff: off); PFQ_PREP_COMPLEXITY: min_complexity = C > 0 and 100 d < C max(len - 1, 0), d = the number of j in
+ *      [b, e - 1) with up(s[j]) != up(s[j + 1]); else 0: the read is kept (an empty read too).
+ *   5. With PFQ_PREP_PAIRED reads 2i and 2i + 1 are mates (an odd n_reads: PFQ_ERR_ARG); a fragment is kept only if both mates
+ *      are, and a mate that passed on its own while its partner was dropped gets PFQ_PREP_MATE.
+ * Parameters: trim_quality 0 (off) or 1 .. 93; trim_window 1 .. 1024; min_complexity 0 (off) or 1 .. 100; unknown flag bits, a
+ * NULL tree, params or out, NULL seq or offsets with n_reads > 0: PFQ_ERR_ARG.  qual shares offsets with seq, NULL: no read has
+ * qualities; has_qual is a byte per read, NULL: every read has (if qual is given).  PFQ_ERR_UNSUPPORTED: a read of 2^32 bases or
+ * more, 2^31 - 1024 reads or more.
+ * pfq_prep: the totals of the call — n_reason[0] = n_kept, n_trimmed = the kept reads with len < L, bases_kept over the kept reads
+ * — and, with PFQ_PREP_WANT_READS, library-owned host arrays begin, len, reason [n_reads] and kept [n_kept] (the kept reads'
+ * indices, ascending), valid until the next pfq_prep_reads on the tree; without the flag they are NULL and only the totals are
+ * copied back.
+ * The call changes no counter, log, sketch or query result.  seq, qual, offsets and has_qual are host buffers that may be reused
+ * when the call returns.  The copies and the kernels run on the tree's copy stream into one of two alternating CSR buffer sets,
+ * so they overlap the classification of the previous pfq_prep_query; the call waits for its own work only, and for an earlier
+ * classification only if that one still reads the set about to be reused.  The CSR (the kept intervals, the sequence buffer padded
+ * by 16 bytes; qualities are not gathered) lives until the next pfq_prep_reads on the tree or its close; other query calls do not
+ * disturb it.
+ * pfq_prep_query: exactly pfq_query_batch_device(tree, csr_seq, csr_off, n_kept, bases_kept, threshold, flags, NULL, hits) on the
+ * block prepared last, ordered behind the prep by an event; every flag and rule of that call applies.  The units are the kept
+ * reads, with PFQ_PAIRED the kept fragments (mates are dropped together, so they stay adjacent); PFQ_PAIRED on a block prepared
+ * without PFQ_PREP_PAIRED: PFQ_ERR_ARG.  It may be repeated (the counters grow each time).  Before any prep: PFQ_ERR_STATE. */
+#define PFQ_PREP_PAIRED 1u      /* reads 2i and 2i + 1 are mates */
+#define PFQ_PREP_WANT_READS 2u  /* fill begin, len, reason, kept */
+enum { PFQ_PREP_KEPT = 0, PFQ_PREP_SHORT = 1, PFQ_PREP_N = 2, PFQ_PREP_COMPLEXITY = 3, PFQ_PREP_MATE = 4 };
+typedef struct pfq_prep_params {
+    uint32_t trim_quality;   /* Q: 0 off, else 1 .. 93 */
+    uint32_t trim_window;    /* W: 1 .. 1024 */
+    uint32_t poly_x;         /* P: 0 off */
+    uint32_t min_length;
+    uint32_t max_n;          /* 0xffffffff: off */
+    uint32_t min_complexity; /* C, percent: 0 off, else 1 .. 100 */
+    uint32_t flags;          /* PFQ_PREP_* */
+} pfq_prep_params;
+typedef struct pfq_prep {
+    uint64_t n_reads, n_kept, bases_in, bases_kept, n_trimmed;
+    uint64_t n_reason[5];    /* reads per reason, PFQ_PREP_KEPT .. PFQ_PREP_MATE */
+    const uint32_t *begin, *len, *reason; /* [n_reads]; NULL without PFQ_PREP_WANT_READS; library-owned */
+    const uint32_t *kept;    /* [n_kept] likewise */
+} pfq_prep;
+int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, const uint64_t *offsets, const uint8_t *has_qual,
+                   uint64_t n_reads, const pfq_prep_params *params, pfq_prep *out);
+int pfq_prep_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits);
+int pfq_debug_prep_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /* tests: the prepared CSR copied to the host */
+/* measurements: device milliseconds of the last pfq_prep_reads with reads — ms[0] trim and mark, ms[1] the two scans, ms[2] offsets and gather */
+int pfq_debug_last_prep(pfq_tree *tree, double *ms);
+
 /* ---- genome similarity ----
  * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one
  * geometry and one seed pair; for two filters the set bits and the shared set bits estimate how many k-mers each genome has and

@@ -21,6 +21,7 @@ SYMBOLS = [
     "pfq_tree_set_sweep", "pfq_sweep_get", "pfq_sweep_reset", "pfq_sweep_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
     "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr",
+    "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
@@ -114,6 +115,17 @@ class Text(C.Structure):
                 ("rec_begin", C.POINTER(C.c_uint64))]
 
 
+class PrepParams(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("trim_quality", "trim_window", "poly_x", "min_length", "max_n", "min_complexity", "flags")]
+
+
+class Prep(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_kept", C.c_uint64), ("bases_in", C.c_uint64), ("bases_kept", C.c_uint64),
+                ("n_trimmed", C.c_uint64), ("n_reason", C.c_uint64 * 5),
+                ("begin", C.POINTER(C.c_uint32)), ("len", C.POINTER(C.c_uint32)), ("reason", C.POINTER(C.c_uint32)),
+                ("kept", C.POINTER(C.c_uint32))]
+
+
 class Similarity(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("shared_bits", C.POINTER(C.c_uint32)),
                 ("bits_a", C.POINTER(C.c_uint64)), ("bits_b", C.POINTER(C.c_uint64)),
@@ -143,6 +155,9 @@ NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
 TEXT_END, TEXT_LIMIT, TEXT_MORE, TEXT_SLOW = 0, 1, 2, 3
+PREP_PAIRED, PREP_WANT_READS = 1, 2
+PREP_KEPT, PREP_SHORT, PREP_N, PREP_COMPLEXITY, PREP_MATE = 0, 1, 2, 3, 4
+PREP_MAX_N_OFF = 0xFFFFFFFF
 _lib = None
 
 
@@ -213,6 +228,10 @@ def lib() -> C.CDLL:
     L.pfq_text_parse.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(Text)]
     L.pfq_text_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_text_csr.argtypes = [vp, vp, vp]
+    L.pfq_prep_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(PrepParams), C.POINTER(Prep)]
+    L.pfq_prep_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
+    L.pfq_debug_prep_csr.argtypes = [vp, vp, vp]
+    L.pfq_debug_last_prep.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
     L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.pfq_tree_recluster.argtypes = [vp, C.POINTER(vp)]

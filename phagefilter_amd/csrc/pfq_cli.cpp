@@ -1385,13 +1385,32 @@ struct Hits {
     std::vector<uint32_t> taxa;      // --taxon-reads: the unit's node of the taxonomy (PFQ_NO_CLADE: no hit)
     std::vector<uint64_t> call_off;  // the call's read offsets, when its range does not start at the batch's first read
 };
+// Read preprocessing (--trim-quality, --trim-window, --trim-poly-x, --min-length, --max-n, --min-complexity): the parameters in
+// force and the totals of all calls and replicas (PREPROCESS.tsv).
+struct PrepRun {
+    bool on = false;
+    pfq_prep_params params{0, 4, 0, 0, 0xffffffffu, 0, 0};
+    std::atomic<uint64_t> reads{0}, kept{0}, trimmed{0}, bases{0}, bases_kept{0};
+    std::atomic<uint64_t> reason[5] = {};
+};
+// What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending
+struct PrepKept {
+    std::vector<uint32_t> begin, len, kept;
+};
 // Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
 // scores; keep_lca: the units' LCAs of a PFQ_WANT_LCA call) are copied out of the library's buffers, which the next call on
-// the tree reuses, into h.
+// the tree reuses, into h.  With preprocessing on the reads go through pfq_prep_reads first — the qualities in a buffer aligned to
+// the bases; a read whose quality length differs from its sequence length, and every FASTA read, has none — and pfq_prep_query
+// classifies what it kept: the units are then the kept reads (fragments), which pk (if asked for) names.
 void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h, bool keep_lca = false,
-              bool keep_taxa = false) {
-    const bool want = (flags & PFQ_WANT_HITS) != 0;
-    const uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
+              bool keep_taxa = false, PrepRun *prep = nullptr, PrepKept *pk = nullptr) {
+    const bool want = (flags & PFQ_WANT_HITS) != 0, prep_on = prep && prep->on;
+    uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
+    if (pk) {
+        pk->begin.clear();
+        pk->len.clear();
+        pk->kept.clear();
+    }
     if (want) {
         h.off.assign(units + 1, 0);
         h.leaves.clear();
@@ -1407,8 +1426,44 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         off = h.call_off.data();
     }
     pfq_hits hits{};
-    if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, threshold, flags, want ? &hits : nullptr) != PFQ_OK)
+    if (prep_on) {
+        static thread_local std::vector<uint8_t> qual, has;
+        const uint64_t base = b.off[r0];
+        qual.assign(b.off[r1] - base, 0);
+        has.assign(r1 - r0, 0);
+        bool any_qual = false;
+        if (prep->params.trim_quality && !b.has_qual.empty())
+            for (uint64_t r = r0; r < r1; ++r) {
+                if (!b.has_qual[r]) continue;
+                const std::string_view q = b.quality(r);
+                if (q.size() != b.off[r + 1] - b.off[r]) continue;
+                if (!q.empty()) memcpy(qual.data() + (b.off[r] - base), q.data(), q.size());
+                has[r - r0] = 1;
+                any_qual = true;
+            }
+        pfq_prep_params par = prep->params;
+        par.flags = (flags & PFQ_PAIRED ? PFQ_PREP_PAIRED : 0u) | (pk ? PFQ_PREP_WANT_READS : 0u);
+        pfq_prep res{};
+        if (pfq_prep_reads(tree, b.seq.data() + base, any_qual ? qual.data() : nullptr, off, any_qual ? has.data() : nullptr, r1 - r0, &par, &res) != PFQ_OK)
+            fail_from_thread(pfq_last_error());
+        prep->reads += res.n_reads;
+        prep->kept += res.n_kept;
+        prep->trimmed += res.n_trimmed;
+        prep->bases += res.bases_in;
+        prep->bases_kept += res.bases_kept;
+        for (int c = 0; c < 5; ++c) prep->reason[c] += res.n_reason[c];
+        if (pk) {
+            pk->begin.assign(res.begin, res.begin + res.n_reads);
+            pk->len.assign(res.len, res.len + res.n_reads);
+            pk->kept.assign(res.kept, res.kept + res.n_kept);
+        }
+        units = flags & PFQ_PAIRED ? res.n_kept / 2 : res.n_kept;
+        if (want) h.off.assign(units + 1, 0);
+        if (!res.n_kept) return;
+        if (pfq_prep_query(tree, threshold, flags, want ? &hits : nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
+    } else if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, threshold, flags, want ? &hits : nullptr) != PFQ_OK) {
         fail_from_thread(pfq_last_error());
+    }
     if (!want) return;
     memcpy(h.off.data(), hits.offsets, (units + 1) * sizeof(uint64_t));
     h.leaves.assign(hits.leaves, hits.leaves + hits.offsets[units]);
@@ -1433,8 +1488,9 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
 }
 // The trees' hit lists of n units in the whole tree's leaf order.  Part i covers units [n i / P, n (i + 1) / P) for a
 // replica (the shares follow one another) and all of them for a shard (per unit, the shards' lists in shard order, each
-// offset by the shard's first leaf).  A single part is swapped into `out`.
-void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &out) {
+// offset by the shard's first leaf).  A single part is swapped into `out`.  cuts (replicas, preprocessing): part i covers units
+// [cuts[i], cuts[i + 1]) instead — what share i kept.
+void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &out, const std::vector<uint64_t> *cuts = nullptr) {
     const size_t P = parts.size();
     if (P == 1) {
         std::swap(out, parts[0]);
@@ -1456,7 +1512,7 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
     uint64_t at = 0;
     for (uint64_t u = 0; u < n; ++u) {
         for (size_t i = 0; i < P; ++i) {
-            const uint64_t u0 = db.sharded ? 0 : n * i / P, u1 = db.sharded ? n : n * (i + 1) / P;
+            const uint64_t u0 = db.sharded ? 0 : cuts ? (*cuts)[i] : n * i / P, u1 = db.sharded ? n : cuts ? (*cuts)[i + 1] : n * (i + 1) / P;
             if (u < u0 || u >= u1) continue;
             const Hits &h = parts[i];
             const uint64_t j0 = h.off[u - u0], j1 = h.off[u - u0 + 1];
@@ -1468,6 +1524,34 @@ void merge_hits(std::vector<Hits> &parts, uint64_t n, const ServedDb &db, Hits &
         }
         out.off[u + 1] = at;
     }
+}
+
+// Preprocessing with per-read outputs: the batch becomes what the parsers would have made of an input that holds only the kept
+// reads, each cut to [begin, begin + len) in bases and qualities, ids unchanged — everything behind the classification then
+// works as it does without the options.  Share i of the batch is reads [share[i], share[i + 1]) and pks[i] what its call kept;
+// returns the kept reads before every share (and their total).  A quality whose length differs from its sequence's stays whole.
+std::vector<uint64_t> keep_prepared(Batch &b, const std::vector<uint64_t> &share, const std::vector<PrepKept> &pks) {
+    Batch nb;
+    std::vector<uint64_t> cuts(pks.size() + 1, 0);
+    for (size_t i = 0; i < pks.size(); ++i) {
+        const PrepKept &pk = pks[i];
+        for (uint32_t j : pk.kept) {
+            const uint64_t r = share[i] + j, s0 = b.off[r] + pk.begin[j], len = pk.len[j];
+            nb.seq.insert(nb.seq.end(), b.seq.begin() + s0, b.seq.begin() + s0 + len);
+            nb.off.push_back(nb.seq.size());
+            const std::string_view id = b.id(r), q = b.quality(r);
+            nb.id_bytes.insert(nb.id_bytes.end(), id.begin(), id.end());
+            nb.id_off.push_back(nb.id_bytes.size());
+            if (q.size() == b.off[r + 1] - b.off[r]) nb.qual.insert(nb.qual.end(), q.begin() + pk.begin[j], q.begin() + pk.begin[j] + len);
+            else nb.qual.insert(nb.qual.end(), q.begin(), q.end());
+            nb.qual_off.push_back(nb.qual.size());
+            nb.has_qual.push_back(b.has_qual[r]);
+        }
+        cuts[i + 1] = nb.n();
+    }
+    nb.held = std::move(b.held);  // (the parsed segments go back to the parsers when the batch is released, as before)
+    b = std::move(nb);
+    return cuts;
 }
 
 // Output buffers of the formatters: grown with realloc (no zero fill), kept from batch to batch.
@@ -1573,6 +1657,8 @@ struct QueryLoop {
     const bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv
     const bool best_hits = false;  // --best-hits: the three above take every unit's best-scoring genomes (the library is asked for hits and scores)
     const bool sweep = false;      // --sweep: every call also counts its rows and scores against the threshold list (hits and scores, as --best-hits)
+    PrepRun *const prep = nullptr; // read preprocessing: every call trims and filters its reads on the device first
+    bool prep_on() const { return prep && prep->on; }
     uint32_t abundance_flags() const {
         return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
                (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u) |
@@ -1607,19 +1693,30 @@ struct QueryLoop {
         while (more) {
             b.clear();
             more = src.next(b, batch_frags);
-            const uint64_t n = b.n(), nf = n / 2;
+            const uint64_t n = b.n();
+            uint64_t nf = n / 2;
             if (!nf) continue;
             b.seq.resize(b.seq.size() + 16);
             const uint64_t tq0 = ReadQueue::now_ns();
+            const bool map_back = per_read && prep_on();  // (the rows of the kept fragments are mapped back through kept, begin and len)
+            std::vector<PrepKept> pks(map_back ? n_trees() : 0);
+            std::vector<uint64_t> share(n_trees() + 1, 0);
             fan_out(n_trees(), [&](size_t i) {
                 const size_t P = n_trees();
                 const uint64_t f0 = db.sharded ? 0 : nf * i / P, f1 = db.sharded ? nf : nf * (i + 1) / P;
-                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads, taxon_reads);
+                share[i] = 2 * f0;
+                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads, taxon_reads, prep, map_back ? &pks[i] : nullptr);
             });
             ns_gpu += ReadQueue::now_ns() - tq0;
             n_total += n;
             if (!per_read) continue;
-            merge_hits(parts, nf, db, f);
+            std::vector<uint64_t> cuts;
+            if (map_back) {
+                cuts = keep_prepared(b, share, pks);
+                for (uint64_t &c : cuts) c /= 2;
+                nf = cuts.back();
+            }
+            merge_hits(parts, nf, db, f, map_back ? &cuts : nullptr);
             // every mate with its own id and its fragment's genomes; a fragment with genomes goes to POS, both mates alike
             pos_out.n = neg_out.n = pos2_out.n = neg2_out.n = 0;
             sc_out.clear();
@@ -1738,7 +1835,7 @@ struct QueryLoop {
         const uint64_t n = sg.b.n();
         if (!n) return;
         const uint64_t tq0 = ReadQueue::now_ns();
-        classify(db.trees[i], sg.b, 0, n, threshold, lca_flags(), unused);
+        classify(db.trees[i], sg.b, 0, n, threshold, lca_flags(), unused, false, false, prep);
         ns_gpu += ReadQueue::now_ns() - tq0;
         if (!db.sharded || i == 0) n_total += n;
     }
@@ -1986,12 +2083,15 @@ struct QueryLoop {
                     cv.wait(lk, [&] { return (s->ready == 1 && s->seq == k) || past_end(k); });
                     if (past_end(k)) return;
                 }
-                const uint64_t n = s->b.n(), tq0 = ReadQueue::now_ns();
-                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads, taxon_reads);
+                uint64_t n = s->b.n();
+                const uint64_t tq0 = ReadQueue::now_ns();
+                std::vector<PrepKept> pks(prep_on() ? 1 : 0);
+                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads, taxon_reads, prep, prep_on() ? &pks[0] : nullptr);
                 if (n) {
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     if (!db.sharded || i == 0) n_total += n;
                 }
+                if (prep_on()) n = keep_prepared(s->b, {0, n}, pks).back();  // (replicas only: this thread alone holds the batch)
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     if (--s->trees_left != 0) continue;
@@ -2263,7 +2363,9 @@ int cmd_query(int argc, char **argv) {
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
                              {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"taxonomy", 0, true},
-                             {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}};
+                             {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
+                             {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
+                             {"min-complexity", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2393,6 +2495,35 @@ int cmd_query(int argc, char **argv) {
             if (a.val.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
         if (lca == 2) die("error: '--device-parse' cannot be used with '--lca best': the best hits need every read's scores");
     }
+    // --trim-quality Q, --trim-window W, --trim-poly-x P, --min-length L, --max-n N, --min-complexity C: any of them turns read
+    // preprocessing on: every call trims and filters its reads on the device (pfq_prep_reads) and classifies what is kept
+    // (pfq_prep_query); PREPROCESS.tsv holds the totals.  --min-length then defaults to the database's k.
+    static PrepRun prep_run;
+    const char *prep_first = nullptr;
+    for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity"})
+        if (a.val.count(name) && !prep_first) prep_first = name;
+    if (prep_first) {
+        prep_run.on = true;
+        const std::string why = ": preprocessing works on the batches the host reader parses and classifies every kept read on every replica";
+        if (a.flags.count("device-parse")) die(std::string("error: '--") + prep_first + "' cannot be used with '--device-parse'" + why);
+        for (const char *other : {"frame", "shard-depth"})
+            if (a.val.count(other)) die(std::string("error: '--") + prep_first + "' cannot be used with '--" + other + "'" + why);
+        auto number = [&](const char *name, const char *dflt, uint64_t lo, uint64_t hi, const char *what) {
+            const std::string v = opt(a, name, dflt);
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long x = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || !isdigit((unsigned char)v[0]) || *end || errno || x < lo || x > hi)
+                die("error: invalid value '" + v + "' for '--" + name + "': " + what);
+            return (uint32_t)x;
+        };
+        prep_run.params.trim_quality = number("trim-quality", "0", 0, 93, "a Phred quality from 0 (off) to 93");
+        prep_run.params.trim_window = number("trim-window", "4", 1, 1024, "a window of 1 to 1024 bases");
+        prep_run.params.poly_x = number("trim-poly-x", "0", 0, 0xffffffffull, "a number of bases (0: off)");
+        prep_run.params.min_length = a.val.count("min-length") ? number("min-length", "1", 1, 0xffffffffull, "at least 1 base (the default is the database's k)") : 0;
+        prep_run.params.max_n = a.val.count("max-n") ? number("max-n", "0", 0, 0xfffffffeull, "a number of N bases") : 0xffffffffu;
+        prep_run.params.min_complexity = number("min-complexity", "0", 0, 100, "a percentage from 0 (off) to 100");
+    }
     // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
     // (PFQ_WANT_HITS | PFQ_WANT_TAXA): TAXON_COUNTS.tsv; --taxon-reads: READ_TAXA.tsv, one line per record with hits.  The file is
     // parsed and checked against tree.bin here, before any device is used.
@@ -2475,7 +2606,8 @@ int cmd_query(int argc, char **argv) {
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
     rq.device_parse = device_parse;
-    if (block != 0) rq.start(per_read || paired || framed, threads);  // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences)
+    // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences; preprocessing: the qualities go to the device)
+    if (block != 0) rq.start(per_read || paired || framed || prep_run.on, threads);
     if (block != 0 && rq2) rq2->start(true, threads);
 
     // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
@@ -2484,11 +2616,12 @@ int cmd_query(int argc, char **argv) {
     mkdir(out.c_str(), 0777);
     Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads, taxon_reads);
     uint64_t kmer_size = 0;
-    if (scores || framed) {
+    if (scores || framed || prep_run.on) {
         pfq_info info{};
         check(pfq_tree_info(db.trees[0], &info));
         kmer_size = info.kmer_size;
     }
+    if (prep_run.on && !a.val.count("min-length")) prep_run.params.min_length = (uint32_t)kmer_size;
     if (framed && frame < kmer_size)
         die("error: '--frame " + std::to_string(frame) + "' is shorter than the database's k-mers (k = " + std::to_string(kmer_size) + "): a frame must hold one");
     db.load_leaf_names();
@@ -2496,7 +2629,7 @@ int cmd_query(int argc, char **argv) {
     if (taxonomy) db.set_taxonomy(a.val.at("taxonomy"));
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits, sweep};
+    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits, sweep, &prep_run};
     if (block == 0) {
         // nothing to do: see above
     } else if (framed) {
@@ -2530,6 +2663,28 @@ int cmd_query(int argc, char **argv) {
     if (coverage) db.save_coverage(out + "/COVERAGE.tsv");
     if (taxonomy) db.save_taxon_counts(out + "/TAXON_COUNTS.tsv", abundance, (uint32_t)abundance_iters);
     if (sweep) db.save_sweep(out, sweep_typed);
+    if (prep_run.on) {
+        // PREPROCESS.tsv: the totals over all calls and replicas, then the parameters in force
+        const PrepRun &pr = prep_run;
+        const std::string max_n = pr.params.max_n == 0xffffffffu ? "off" : std::to_string(pr.params.max_n);
+        const std::pair<const char *, std::string> rows[] = {
+            {"reads", std::to_string(pr.reads.load())}, {"reads_kept", std::to_string(pr.kept.load())}, {"reads_trimmed", std::to_string(pr.trimmed.load())},
+            {"dropped_short", std::to_string(pr.reason[PFQ_PREP_SHORT].load())}, {"dropped_n", std::to_string(pr.reason[PFQ_PREP_N].load())},
+            {"dropped_complexity", std::to_string(pr.reason[PFQ_PREP_COMPLEXITY].load())}, {"dropped_mate", std::to_string(pr.reason[PFQ_PREP_MATE].load())},
+            {"bases", std::to_string(pr.bases.load())}, {"bases_kept", std::to_string(pr.bases_kept.load())},
+            {"trim_quality", std::to_string(pr.params.trim_quality)}, {"trim_window", std::to_string(pr.params.trim_window)},
+            {"trim_poly_x", std::to_string(pr.params.poly_x)}, {"min_length", std::to_string(pr.params.min_length)}, {"max_n", max_n},
+            {"min_complexity", std::to_string(pr.params.min_complexity)}};
+        FILE *f = fopen((out + "/PREPROCESS.tsv").c_str(), "wb");
+        if (!f) die("cannot create PREPROCESS.tsv in " + out);
+        for (const auto &row : rows) fprintf(f, "%s\t%s\n", row.first, row.second.c_str());
+        if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
+        fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept\n",
+                (unsigned long long)pr.reads.load(), (unsigned long long)pr.kept.load(), (unsigned long long)pr.trimmed.load(),
+                (unsigned long long)pr.reason[PFQ_PREP_SHORT].load(), (unsigned long long)pr.reason[PFQ_PREP_N].load(),
+                (unsigned long long)pr.reason[PFQ_PREP_COMPLEXITY].load(), (unsigned long long)pr.reason[PFQ_PREP_MATE].load(),
+                (unsigned long long)pr.bases_kept.load(), (unsigned long long)pr.bases.load());
+    }
     db.close();
     printf("Finished.\n");
     return 0;
@@ -3048,6 +3203,17 @@ void usage() {
             "CLASSIFICATION.csv count.  Every other output stays as it is.  Works with --devices.  Needs a database whose parent filters\n"
             "contain their children's (every database build, add and recluster make).  Not with --reads2, --interleaved, --shard-depth,\n"
             "--frame or --device-parse\n"
+            "--trim-quality <Q> --trim-window <W> --trim-poly-x <P> --min-length <L> --max-n <N> --min-complexity <C>: nobody classifies raw\n"
+            "reads; any of these trims and filters every read on the GPU before it is classified, as a trimmer in front of the run would:\n"
+            "leading bases below Phred Q go, the read is cut at the first window of W bases (default 4) whose mean quality is below Q and\n"
+            "then back to its last base of at least Q; a tail of P or more equal bases (poly-G) goes; then a read shorter than L (default:\n"
+            "the database's k, so that no read without a k-mer counts at every genome; at least 1), with more than N bases other than A C G\n"
+            "T, or with fewer than C percent of its adjacent bases differing is dropped.  FASTA reads have no qualities: the other steps\n"
+            "apply.  With --reads2 / --interleaved a fragment is dropped when either mate is.  Every output is, byte for byte, that of the\n"
+            "same command without these options on an input that holds only the kept reads, each cut to what was kept, ids unchanged;\n"
+            "PREPROCESS.tsv in --out adds \"key<TAB>value\" lines: reads, reads_kept, reads_trimmed, dropped_short, dropped_n,\n"
+            "dropped_complexity, dropped_mate, bases, bases_kept, then the parameters in force; the totals are also printed on stderr.\n"
+            "Works with every other output, with pairs and with --devices.  Not with --device-parse, --frame or --shard-depth\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

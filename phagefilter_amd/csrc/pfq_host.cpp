@@ -417,6 +417,20 @@ struct pfq_tree {
     int tx_slot = 0;
     uint64_t tx_records = 0, tx_bases = 0;
     std::vector<uint64_t> out_rec_begin;
+    // pfq_prep_reads: the block as the caller gave it and what the kernels leave per read (scratch of one call: the call waits
+    // for its kernels), and two alternating CSR sets as above: pp_free[s] behind the classification that read set s, pp_ready
+    // behind the prep kernels.
+    DevBuf<uint8_t> d_pp_in, d_pp_qual, d_pp_hq, d_pp_seq[2];
+    DevBuf<uint64_t> d_pp_inoff, d_pp_off[2];
+    DevBuf<uint32_t> d_pp_begin, d_pp_len, d_pp_reason, d_pp_keep, d_pp_klen, d_pp_kept;
+    DevBuf<unsigned long long> d_pp_kpos, d_pp_koff, d_pp_sums, d_pp_tot;
+    unsigned long long *h_pp_tot = nullptr;  // page-locked: the totals, then the kept reads
+    hipEvent_t pp_free[2] = {nullptr, nullptr}, pp_ready = nullptr;
+    hipEvent_t pp_time[4] = {nullptr, nullptr, nullptr, nullptr};  // pfq_debug_last_prep: round trim + mark, the scans, offsets + gather
+    bool pp_used[2] = {false, false}, pp_have = false, pp_paired = false, pp_timed = false;
+    int pp_slot = 0;
+    uint64_t pp_kept = 0, pp_bases = 0;
+    std::vector<uint32_t> out_pp_begin, out_pp_len, out_pp_reason, out_pp_kept;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3250,7 +3264,10 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_fr_segs.bytes() + t.d_fr_segseq.bytes() + t.d_fr_queue.bytes() + t.d_fr_pieceoff.bytes() + t.d_fr_parts.bytes() + t.d_fr_misc.bytes() +
                         t.d_tx_text.bytes() + t.d_tx_seq[0].bytes() + t.d_tx_seq[1].bytes() + t.d_tx_off[0].bytes() + t.d_tx_off[1].bytes() +  // (pfq_text_parse)
                         t.d_tx_rec_begin.bytes() + t.d_tx_blk.bytes() + t.d_tx_line.bytes() + t.d_tx_len.bytes() + t.d_tx_hdr.bytes() + t.d_tx_rec_line.bytes() +
-                        t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes();
+                        t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes() +
+                        t.d_pp_in.bytes() + t.d_pp_qual.bytes() + t.d_pp_hq.bytes() + t.d_pp_seq[0].bytes() + t.d_pp_seq[1].bytes() + t.d_pp_inoff.bytes() +  // (pfq_prep_reads)
+                        t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
+                        t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes();
     return PFQ_OK;
 }
 
@@ -3298,6 +3315,12 @@ void pfq_tree_close(pfq_tree *tree) {
         if (e) (void)hipEventDestroy(e);
     if (tree->tx_parsed) (void)hipEventDestroy(tree->tx_parsed);
     if (tree->h_tx_res) (void)hipHostFree(tree->h_tx_res);
+    for (auto e : tree->pp_free)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->pp_time)
+        if (e) (void)hipEventDestroy(e);
+    if (tree->pp_ready) (void)hipEventDestroy(tree->pp_ready);
+    if (tree->h_pp_tot) (void)hipHostFree(tree->h_pp_tot);
     delete tree;
 }
 
@@ -3568,6 +3591,173 @@ int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
     const pfq_tree &t = *tree;
     if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_slot].p, t.tx_bases, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_slot].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+// ---- read preprocessing ----------------------------------------------------------------------------------------------------
+
+int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, const uint64_t *offsets, const uint8_t *has_qual, uint64_t n_reads,
+                   const pfq_prep_params *params, pfq_prep *out) {
+    if (!tree || !params || !out || (n_reads && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
+    const pfq_prep_params &pr = *params;
+    if (pr.flags & ~(PFQ_PREP_PAIRED | PFQ_PREP_WANT_READS)) return fail(PFQ_ERR_ARG, "pfq_prep_reads: unknown flag bits");
+    if (pr.trim_quality > 93) return fail(PFQ_ERR_ARG, "pfq_prep_reads: trim_quality must be 0 (off) or 1 .. 93, not " + std::to_string(pr.trim_quality));
+    if (pr.trim_window < 1 || pr.trim_window > 1024) return fail(PFQ_ERR_ARG, "pfq_prep_reads: trim_window must be 1 .. 1024, not " + std::to_string(pr.trim_window));
+    if (pr.min_complexity > 100) return fail(PFQ_ERR_ARG, "pfq_prep_reads: min_complexity must be 0 (off) or 1 .. 100, not " + std::to_string(pr.min_complexity));
+    const bool paired = (pr.flags & PFQ_PREP_PAIRED) != 0, want_reads = (pr.flags & PFQ_PREP_WANT_READS) != 0;
+    if (paired && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PREP_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
+    if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: 2^31 - 1024 reads or more in one block: ask in pieces");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    if (!t.copy_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
+        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (!t.pp_ready) {
+        HIP_TRY(hipEventCreateWithFlags(&t.pp_ready, hipEventDisableTiming));
+        for (auto &e : t.pp_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto &e : t.pp_time) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1) * 8, hipHostMallocDefault));
+        HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
+    }
+    hipStream_t st = t.copy_stream;
+    const int slot = t.pp_slot ^ 1;
+    if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));  // the classification that read this set is done
+    t.pp_have = false;  // (until this prep has succeeded there is no block to query)
+    const uint64_t total = n_reads ? offsets[n_reads] : 0;
+    *out = pfq_prep{};
+    out->n_reads = n_reads;
+    HIP_TRY(t.d_pp_seq[slot].ensure(total + 16));
+    HIP_TRY(t.d_pp_off[slot].ensure(n_reads + 1));
+    uint64_t n_kept = 0;
+    if (!n_reads) {
+        HIP_TRY(hipMemsetAsync(t.d_pp_off[slot].p, 0, 8, st));
+    } else {
+        HIP_TRY(t.d_pp_in.ensure(total + 16));
+        HIP_TRY(t.d_pp_inoff.ensure(n_reads + 1));
+        if (qual) HIP_TRY(t.d_pp_qual.ensure(total + 16));
+        if (qual && has_qual) HIP_TRY(t.d_pp_hq.ensure(n_reads));
+        for (DevBuf<uint32_t> *b : {&t.d_pp_begin, &t.d_pp_len, &t.d_pp_reason, &t.d_pp_keep, &t.d_pp_klen, &t.d_pp_kept}) HIP_TRY(b->ensure(n_reads));
+        HIP_TRY(t.d_pp_kpos.ensure(n_reads + 1));
+        HIP_TRY(t.d_pp_koff.ensure(n_reads + 1));
+        HIP_TRY(t.d_pp_sums.ensure(n_reads / 4096 + 2));
+        if (total) HIP_TRY(hipMemcpyAsync(t.d_pp_in.p, seq, total, hipMemcpyHostToDevice, st));
+        if (total && qual) HIP_TRY(hipMemcpyAsync(t.d_pp_qual.p, qual, total, hipMemcpyHostToDevice, st));
+        if (qual && has_qual) HIP_TRY(hipMemcpyAsync(t.d_pp_hq.p, has_qual, n_reads, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_pp_inoff.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(t.d_pp_tot.p, 0, pfq::PREP_TOT_N * 8, st));
+        pfq::PrepArgs a{};
+        a.seq = t.d_pp_in.p;
+        a.qual = qual ? t.d_pp_qual.p : nullptr;
+        a.off = t.d_pp_inoff.p;
+        a.has_qual = (qual && has_qual) ? t.d_pp_hq.p : nullptr;
+        a.n_reads = n_reads;
+        a.trim_quality = pr.trim_quality;
+        a.trim_window = pr.trim_window;
+        a.poly_x = pr.poly_x;
+        a.min_length = pr.min_length;
+        a.max_n = pr.max_n;
+        a.min_complexity = pr.min_complexity;
+        a.paired = paired ? 1u : 0u;
+        a.begin = t.d_pp_begin.p;
+        a.len = t.d_pp_len.p;
+        a.reason = t.d_pp_reason.p;
+        a.keep = t.d_pp_keep.p;
+        a.klen = t.d_pp_klen.p;
+        a.totals = t.d_pp_tot.p;
+        a.kpos = t.d_pp_kpos.p;
+        a.koff = t.d_pp_koff.p;
+        a.kept = t.d_pp_kept.p;
+        a.csr_off = t.d_pp_off[slot].p;
+        a.out = t.d_pp_seq[slot].p;
+        HIP_TRY(hipEventRecord(t.pp_time[0], st));
+        pfq::launch_prep_trim(a, st);
+        pfq::launch_prep_mark(a, st);
+        HIP_TRY(hipEventRecord(t.pp_time[1], st));
+        pfq::launch_scan_u32(t.d_pp_keep.p, n_reads, t.d_pp_sums.p, t.d_pp_kpos.p, st);
+        pfq::launch_scan_u32(t.d_pp_klen.p, n_reads, t.d_pp_sums.p, t.d_pp_koff.p, st);
+        HIP_TRY(hipEventRecord(t.pp_time[2], st));
+        pfq::launch_prep_gather(a, st);
+        HIP_TRY(hipEventRecord(t.pp_time[3], st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(t.h_pp_tot, t.d_pp_tot.p, pfq::PREP_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffers are free from here)
+        t.pp_timed = true;
+        if (t.h_pp_tot[pfq::PREP_TOT_ERR])
+            return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: a read of 2^32 bases or more (or offsets that do not ascend)");
+        n_kept = t.h_pp_tot[pfq::PREP_TOT_N];
+        for (int c = 0; c < 5; ++c) out->n_reason[c] = t.h_pp_tot[pfq::PREP_TOT_REASON + c];
+        out->bases_in = t.h_pp_tot[pfq::PREP_TOT_BASES_IN];
+        out->bases_kept = t.h_pp_tot[pfq::PREP_TOT_BASES_KEPT];
+        out->n_trimmed = t.h_pp_tot[pfq::PREP_TOT_TRIMMED];
+    }
+    out->n_kept = n_kept;
+    if (want_reads) {
+        t.out_pp_begin.resize(std::max<uint64_t>(n_reads, 1));  // (never NULL with the flag)
+        t.out_pp_len.resize(std::max<uint64_t>(n_reads, 1));
+        t.out_pp_reason.resize(std::max<uint64_t>(n_reads, 1));
+        t.out_pp_kept.resize(std::max<uint64_t>(n_kept, 1));
+        if (n_reads) {
+            HIP_TRY(hipMemcpyAsync(t.out_pp_begin.data(), t.d_pp_begin.p, n_reads * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.out_pp_len.data(), t.d_pp_len.p, n_reads * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.out_pp_reason.data(), t.d_pp_reason.p, n_reads * 4, hipMemcpyDeviceToHost, st));
+        }
+        if (n_kept) HIP_TRY(hipMemcpyAsync(t.out_pp_kept.data(), t.d_pp_kept.p, n_kept * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipEventRecord(t.pp_ready, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (want_reads) {
+        out->begin = t.out_pp_begin.data();
+        out->len = t.out_pp_len.data();
+        out->reason = t.out_pp_reason.data();
+        out->kept = t.out_pp_kept.data();
+    }
+    t.pp_slot = slot;
+    t.pp_kept = n_kept;
+    t.pp_bases = out->bases_kept;
+    t.pp_paired = paired;
+    t.pp_have = true;
+    return PFQ_OK;
+}
+
+int pfq_prep_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(check_flags(*tree, flags, tree->pp_kept, threshold));
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_prep_query before a pfq_prep_reads on this tree");
+    if ((flags & PFQ_PAIRED) && !tree->pp_paired)
+        return fail(PFQ_ERR_ARG, "pfq_prep_query: PFQ_PAIRED on a block prepared without PFQ_PREP_PAIRED (its kept reads are not whole fragments)");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    const int slot = t.pp_slot;
+    HIP_TRY(hipStreamWaitEvent(nullptr, t.pp_ready, 0));  // (the classification is ordered behind the prep on the device)
+    const int rc = query_device(t, t.d_pp_seq[slot].p, t.d_pp_off[slot].p, t.pp_kept, t.pp_bases, threshold, flags, nullptr, hits);
+    HIP_TRY(hipEventRecord(t.pp_free[slot], nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
+    t.pp_used[slot] = true;
+    PFQ_TRY(rc);
+    if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
+    return PFQ_OK;
+}
+
+int pfq_debug_prep_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
+    if (!tree || !off_out || (tree->pp_bases && !seq_out)) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_debug_prep_csr before a pfq_prep_reads on this tree");
+    PFQ_TRY(use_device(tree->device));
+    const pfq_tree &t = *tree;
+    if (t.pp_bases) HIP_TRY(hipMemcpy(seq_out, t.d_pp_seq[t.pp_slot].p, t.pp_bases, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off_out, t.d_pp_off[t.pp_slot].p, (t.pp_kept + 1) * 8, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+int pfq_debug_last_prep(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_prep before a pfq_prep_reads with reads on this tree");
+    PFQ_TRY(use_device(tree->device));
+    for (int i = 0; i < 3; ++i) {
+        float v = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&v, tree->pp_time[i], tree->pp_time[i + 1]));
+        ms[i] = v;
+    }
     return PFQ_OK;
 }
 

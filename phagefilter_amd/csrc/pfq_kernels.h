@@ -632,6 +632,37 @@ void launch_text_lines(const uint8_t *d_text, uint32_t len, uint32_t tile, const
 void launch_text_roles(const TextArgs &a, uint32_t *d_is_header, hipStream_t st);
 void launch_text_rec_lines(const uint32_t *d_is_header, const unsigned long long *d_rec_idx, uint32_t n_lines, uint32_t *d_rec_line, hipStream_t st);
 void launch_text_finish(const TextArgs &a, uint8_t *d_csr_seq, uint64_t *d_csr_off, uint64_t *d_rec_begin, hipStream_t st);
+// pfq_prep_reads (pfq_prep.hip): reads trimmed and filtered by the rules of pfq.h "read preprocessing", the kept intervals
+// gathered into the CSR the classifier takes.  seq and qual are 16-byte aligned and hold 16 bytes beyond off[n_reads]; qual
+// shares off with seq (nullptr: no read has qualities), has_qual is a byte per read (nullptr: all have).
+//   launch_prep_trim: begin, len, reason [n_reads] before the mate rule; totals[PREP_TOT_ERR] |= 1 if a read has 2^32 bases or
+//     more (or the offsets descend).  Three builds of one kernel share the reads by length: groups of 16 lanes up to
+//     PREP_SHORT_MAX bases, a wave up to PREP_WAVE_MAX, a block beyond; a group takes 16 bytes a lane and piece.
+//   launch_prep_mark: the mate rule (paired: reads 2i, 2i + 1; n_reads even), keep and klen [n_reads], totals[0 .. PREP_TOT_ERR)
+//     += the call's (zeroed by the caller).  The caller scans keep into kpos and klen into koff (launch_scan_u32).
+//   launch_prep_gather: kept [n_kept], csr_off [n_kept + 1], the kept intervals copied to out (16 bytes beyond the kept bases).
+// n_reads = 0: nothing runs.
+constexpr uint32_t PREP_SHORT = 1, PREP_N = 2, PREP_COMPLEXITY = 3, PREP_MATE = 4;  // = PFQ_PREP_* of pfq.h
+constexpr uint32_t PREP_SHORT_MAX = 512, PREP_WAVE_MAX = 4096;
+constexpr uint32_t PREP_GRID = 1024;  // blocks of every kernel: reads of one grid trip / 256 (the 16-lane trim build: / its block size)
+enum PrepTotal { PREP_TOT_REASON = 0 /* .. 4 */, PREP_TOT_BASES_IN = 5, PREP_TOT_BASES_KEPT = 6, PREP_TOT_TRIMMED = 7, PREP_TOT_ERR = 8, PREP_TOT_N = 9 };
+struct PrepArgs {
+    const uint8_t *seq, *qual;
+    const uint64_t *off;                     // [n_reads + 1]
+    const uint8_t *has_qual;
+    uint64_t n_reads;
+    uint32_t trim_quality, trim_window, poly_x, min_length, max_n, min_complexity, paired;
+    uint32_t *begin, *len, *reason;          // [n_reads]
+    uint32_t *keep, *klen;                   // [n_reads]
+    unsigned long long *totals;              // [PREP_TOT_N]
+    const unsigned long long *kpos, *koff;   // [n_reads + 1] scans of keep and klen
+    uint32_t *kept;                          // [n_kept]
+    uint64_t *csr_off;                       // [n_kept + 1]
+    uint8_t *out;
+};
+void launch_prep_trim(const PrepArgs &a, hipStream_t st);
+void launch_prep_mark(const PrepArgs &a, hipStream_t st);
+void launch_prep_gather(const PrepArgs &a, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

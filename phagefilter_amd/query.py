@@ -306,6 +306,71 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
         return self._hits_result(hits, want_hits, want_scores)
 
+    # ---- read preprocessing
+    PREP_REASONS = ("kept", "short", "n", "complexity", "mate")
+
+    def prep_reads(self, seq: np.ndarray, off: np.ndarray, qual: Optional[np.ndarray] = None, has_qual: Optional[np.ndarray] = None, *,
+                   trim_quality: int = 0, trim_window: int = 4, poly_x: int = 0, min_length: int = 0, max_n: Optional[int] = None,
+                   min_complexity: int = 0, paired: bool = False, want_reads: bool = False) -> dict:
+        """One block of reads from host memory trimmed and filtered on the device into the block query_prep() classifies
+        (pfq_prep_reads; the rules are pfq.h "read preprocessing").  `qual`: Phred+33 bytes that share `off` with `seq` (None: no
+        read has qualities); `has_qual`: a byte per read (None: all have).  `max_n` None: off.  `paired`: reads 2i and 2i + 1
+        are mates and are dropped together.  Returns the totals n_reads, n_kept, bases_in, bases_kept, n_trimmed and n_reason
+        (a dict by PREP_REASONS) and, with `want_reads`, begin, len, reason uint32[n_reads] and kept uint32[n_kept] (else None).
+        No counter changes."""
+        n = len(off) - 1
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
+        has_qual = None if has_qual is None else np.ascontiguousarray(has_qual, dtype=np.uint8)
+        total = int(off[-1]) if n >= 0 and off.size else 0
+        if seq.size < total or (qual is not None and qual.size < total):
+            raise ValueError("seq and qual must hold off[-1] bytes each: qual shares off with seq, one quality byte per base")
+        if has_qual is not None and has_qual.size != n:
+            raise ValueError("has_qual must hold one byte per read")
+        par = _ffi.PrepParams(trim_quality, trim_window, poly_x, min_length, _ffi.PREP_MAX_N_OFF if max_n is None else max_n, min_complexity,
+                              (_ffi.PREP_PAIRED if paired else 0) | (_ffi.PREP_WANT_READS if want_reads else 0))
+        out = _ffi.Prep()
+        _ffi.check(_ffi.lib().pfq_prep_reads(self._h, seq.ctypes.data if seq.size else None, None if qual is None or not qual.size else qual.ctypes.data,
+                                             off.ctypes.data, None if has_qual is None or not n else has_qual.ctypes.data, n, C.byref(par),
+                                             C.byref(out)))
+        nk = int(out.n_kept)
+        self._prep_shape = (nk, int(out.bases_kept))
+
+        def arr(p, m):
+            if not want_reads:
+                return None
+            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=np.uint32)
+        return {"n_reads": int(out.n_reads), "n_kept": nk, "bases_in": int(out.bases_in), "bases_kept": int(out.bases_kept),
+                "n_trimmed": int(out.n_trimmed), "n_reason": {k: int(out.n_reason[i]) for i, k in enumerate(self.PREP_REASONS)},
+                "begin": arr(out.begin, n), "len": arr(out.len, n), "reason": arr(out.reason, n), "kept": arr(out.kept, nk)}
+
+    def prep_csr(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The block prepared last, copied to the host: (seq uint8[bases_kept], off uint64[n_kept + 1]) (pfq_debug_prep_csr)."""
+        n, nb = getattr(self, "_prep_shape", (0, 0))
+        seq, off = np.zeros(nb, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+        _ffi.check(_ffi.lib().pfq_debug_prep_csr(self._h, seq.ctypes.data, off.ctypes.data))
+        return seq, off
+
+    def last_prep_ms(self) -> Tuple[float, float, float]:
+        """Device milliseconds of the last prep_reads(): (trim and mark, the scans, offsets and gather) (pfq_debug_last_prep)."""
+        ms = (C.c_double * 3)()
+        _ffi.check(_ffi.lib().pfq_debug_last_prep(self._h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def query_prep(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
+                   pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
+                   best: bool = False, sweep: bool = False):
+        """Classifies the block prep_reads() prepared last, exactly as query_packed() classifies the kept, trimmed reads from host
+        memory (pfq_prep_query); same keywords, same return value; `paired` needs a block prepared with paired=True.  May be
+        repeated: the counters grow each time."""
+        lca_flags = (_lca_flags(lca, want_hits, want_scores) | _abundance_flags(abundance, want_hits) | _coverage_flags(coverage, want_hits) |
+                     _taxa_flags(taxa, want_hits) | _best_flags(best, want_hits, want_scores) | _sweep_flags(sweep, want_hits, want_scores))
+        hits = _ffi.Hits()
+        flags = (_ffi.WANT_HITS if want_hits else 0) | (_ffi.WANT_SCORES if want_scores else 0) | _pair_flags(paired, pair_mode) | lca_flags
+        _ffi.check(_ffi.lib().pfq_prep_query(self._h, threshold, flags, C.byref(hits)))
+        return self._hits_result(hits, want_hits, want_scores)
+
     def _segments(self, out: "_ffi.Segments"):
         n = int(out.n_seqs)
         offs = np.ctypeslib.as_array(out.offsets, shape=(n + 1,)).copy() if n else np.zeros(1, dtype=np.uint64)
