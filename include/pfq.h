@@ -756,6 +756,16 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value);
 #define PFQ_CAPACITY_N 12
 int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n);
 
+/* Position slots: every leaf or guard column whose filter has at most 8192 set bits in each 2^20-bit tile
+ * keeps the tile-relative positions of those bits, 8192 u32 per tile, and the LDS-tile certificates at theta = 1 rebuild such
+ * a tile from its slot instead of loading its 128 KiB.  Made with the device layout (builds it if need be); option
+ * PFQ_TILE_LISTS=0: none.  out[0] columns with slots, [1] bytes the slots hold, [2] tiles the last query call built from
+ * slots, [3] tiles it loaded dense (both 0 unless its certificates ran as k_tile_test<0>; waits for that call). */
+int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]);
+/* Copy min(n, 8192) entries of the slot of (column, tile) to the host: positions < 2^20 in any order, unused entries
+ * 0xffffffff.  A column without slots: PFQ_ERR_STATE. */
+int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n);
+
 
 /* Per-call statistics of the last pfq_query_batch[_device] (valid after the stream is synchronised). */
 typedef struct pfq_stats {

@@ -111,6 +111,7 @@ struct Knobs {
     long long cluster_time = -1;                // pfq_tree_recluster: 1: time the stages with HIP events (pfq_debug_last_recluster)
     long long text_tile = -1;                   // pfq_text_parse: bytes of text a block scans (a power of two, 256 .. the built-in 8192)
     long long sweep_lds = -1;                   // PFQ_WANT_SWEEP: 0: count `pass` with global atomics although its bins fit the block's LDS
+    long long tile_lists = -1;                  // 0: no position slots, k_tile_test loads every tile dense (unset: slots for every sparse column)
 };
 struct KnobName {
     const char *name;
@@ -143,6 +144,7 @@ const KnobName KNOBS[] = {
     {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
     {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
+    {"PFQ_TILE_LISTS", &Knobs::tile_lists},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -181,12 +183,15 @@ enum CursorSlot {
     CUR_KMISS = 9,           // k-mer miss bytes handed out
     CUR_TAIL_SHAPES = 10,    // lo: tail shapes that served a pair (pfq::TAIL_SHAPE_*)
     CUR_TAIL_WORK = 11,      // lo: k_tail_records' work counter
-    CUR_N = 12,
+    CUR_TILE_LIST = 12,      // k_tile_test<0>: tiles built from position slots
+    CUR_TILE_DENSE = 13,     //                 tiles loaded dense
+    CUR_N = 14,
     CUR_ALLOC = 16,          // slots allocated and cleared
 };
 static_assert(CUR_N <= CUR_ALLOC, "an attempt clears CUR_ALLOC slots");
 static_assert(CUR_HIT == 0 && CUR_PAIR == 1, "read_hits reads slots 0 and 1 with one 16-byte copy");
 static_assert(CUR_TAIL_WORK == CUR_TAIL_SHAPES + 1, "k_tail_records finds its work counter at shapes[2]");
+static_assert(CUR_TILE_DENSE == CUR_TILE_LIST + 1, "k_tile_test finds its dense counter at tile_list_stats[1]");
 // Slots of pfq_tree::h_pair_cursor, the pinned mirror a bucketed call leaves for the next call's sizing (HINT_N allocated).
 enum HintSlot {
     HINT_PAIRS = 0,         // CUR_PAIR
@@ -274,6 +279,14 @@ struct pfq_tree {
     DevBuf<unsigned int> d_gcur;
     uint32_t last_coarse_cols = 0, last_coarse_probes = 0, last_leaf_groups = 0;
     DevBuf<uint32_t> d_S, d_col_row, d_guard_off, d_guard_col;
+    // position slots of the sparse columns (pfq_tilelist.hip): made with the layout, gone with it; none is never an error
+    DevBuf<uint32_t> d_tile_list_row, d_tile_lists;  // [n_cols] row of slots or TILE_LIST_NONE; [rows][tiles][TILE_LIST_CAP]
+    uint32_t tile_list_cols = 0;     // columns with slots (0: d_tile_lists is not in use)
+    void drop_tile_lists() {
+        d_tile_list_row.release();
+        d_tile_lists.release();
+        tile_list_cols = 0;
+    }
     DevBuf<uint32_t> d_owner, d_owner_sorted, d_gfail;  // trees with guard columns, bucketed path: leaf pair of every pair slot
     DevBuf<unsigned long long> d_counts;
     // what the counters held when the tree was opened (BloomNode::mapped_reads stored in tree.bin), last reset, imported or
@@ -898,9 +911,45 @@ int build_coarse(pfq_tree &t, const CoarsePlan &plan) {
     return PFQ_OK;
 }
 
+// Position slots for k_tile_test<0>: every column whose filter has at most TILE_LIST_CAP set bits in each 2^TILE_LOG2-bit tile
+// gets a row of slots.  Two launches and the read-back of one count per column; whatever goes wrong with memory here leaves
+// the tree without slots (every tile is then loaded dense), never with an error.
+int build_tile_lists(pfq_tree &t) {
+    t.drop_tile_lists();
+    const uint64_t n_tiles = (t.n_words * 64 + (1ull << pfq::TILE_LOG2) - 1) >> pfq::TILE_LOG2;
+    if (t.knobs.tile_lists == 0 || t.n_cols == 0 || n_tiles == 0 || n_tiles >= 256) return PFQ_OK;  // (256 tiles and more: no tile mode)
+    auto give_up = [&]() {
+        (void)hipGetLastError();
+        t.drop_tile_lists();
+        return PFQ_OK;
+    };
+    DevBuf<uint32_t> d_max, d_cols;
+    if (d_max.ensure(t.n_cols) != hipSuccess || t.d_tile_list_row.ensure(t.n_cols) != hipSuccess) return give_up();
+    HIP_TRY(hipMemsetAsync(d_max.p, 0, (size_t)t.n_cols * 4, nullptr));
+    pfq::launch_tile_list_count(t.d_bits.p, t.n_words, t.d_col_row.p, t.n_cols, (uint32_t)n_tiles, d_max.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> col_max(t.n_cols), row(t.n_cols, pfq::TILE_LIST_NONE), cols;
+    HIP_TRY(hipMemcpy(col_max.data(), d_max.p, (size_t)t.n_cols * 4, hipMemcpyDeviceToHost));
+    for (uint32_t c = 0; c < t.n_cols; ++c)
+        if (col_max[c] <= pfq::TILE_LIST_CAP) {
+            row[c] = (uint32_t)cols.size();
+            cols.push_back(c);
+        }
+    if (cols.empty()) return give_up();
+    if (d_cols.ensure(cols.size()) != hipSuccess || t.d_tile_lists.ensure(cols.size() * n_tiles * pfq::TILE_LIST_CAP) != hipSuccess) return give_up();
+    HIP_TRY(hipMemcpy(d_cols.p, cols.data(), cols.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.d_tile_list_row.p, row.data(), row.size() * 4, hipMemcpyHostToDevice));
+    pfq::launch_tile_list_fill(t.d_bits.p, t.n_words, t.d_col_row.p, d_cols.p, (uint32_t)cols.size(), (uint32_t)n_tiles, t.d_tile_lists.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());  // (d_cols goes out of scope)
+    t.tile_list_cols = (uint32_t)cols.size();
+    return PFQ_OK;
+}
+
 int build_layout(pfq_tree &t) {
     PFQ_TRY(insertion_error(t));
     if (t.layout_valid) return PFQ_OK;
+    t.drop_tile_lists();
     PFQ_TRY(finish_topology(t));
     t.leaves = leaves_dfs(t);
     const size_t nl = t.leaves.size();
@@ -998,6 +1047,7 @@ int build_layout(pfq_tree &t) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     if (want_coarse) PFQ_TRY(build_coarse(t, plan));
+    PFQ_TRY(build_tile_lists(t));
     t.have_cand_hint = false;
     t.tables_valid = false;
     t.layout_valid = true;
@@ -1887,6 +1937,13 @@ struct QueryRun {
                 ta.gfill = t.d_gfill.p;
                 ta.fail = t.d_fail.p;
                 ta.n_pairs_ptr = off + nb;
+                if (!counts_mode && !block_mode) {  // k_tile_test<0>: sparse columns' tiles come from their position slots
+                    ta.tile_list_stats = t.d_cursors.p + CUR_TILE_LIST;
+                    if (t.tile_list_cols && kn.tile_lists != 0) {
+                        ta.tile_list_row = t.d_tile_list_row.p;
+                        ta.tile_lists = t.d_tile_lists.p;
+                    }
+                }
                 if (counts_mode) {
                     ta.counts = 1;
                     ta.threshold = threshold;
@@ -2954,6 +3011,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
         return fail(PFQ_ERR_ARG, std::string("a node named ") + internal_name + " exists already: two nodes would share " + internal_name + ".bf");
     PFQ_TRY(sync_counts_to_nodes(t));
     t.layout_valid = false;
+    t.drop_tile_lists();  // (made again with the layout)
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
@@ -3283,6 +3341,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
         if (nd.depth >= search_depth) nd.left = nd.right = -1;  // bloom_tree.rs:322-325
     // nodes below the cut are unreachable now; they keep their slots (and filters) but never appear as leaves
     t.layout_valid = false;
+    t.drop_tile_lists();  // (made again with the layout)
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
     cover_clear(t);
@@ -5061,11 +5120,13 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
     }
     if (!set_knob(tree->knobs, name, value)) return fail(PFQ_ERR_ARG, std::string("unknown option ") + name);
     // knobs of the device layout (column groups, coarse level): the layout is rebuilt before the next use
-    if (!strcmp(name, "PFQ_COARSE") || !strcmp(name, "PFQ_COARSE_COLS") || !strcmp(name, "PFQ_GROUP_LOG2") || !strcmp(name, "PFQ_COARSE_MIN_LEAVES")) {
+    if (!strcmp(name, "PFQ_COARSE") || !strcmp(name, "PFQ_COARSE_COLS") || !strcmp(name, "PFQ_GROUP_LOG2") || !strcmp(name, "PFQ_COARSE_MIN_LEAVES") ||
+        !strcmp(name, "PFQ_TILE_LISTS")) {  // (the position slots are made with the layout)
         if (tree->layout_valid) {
             PFQ_TRY(use_device(tree->device));
             PFQ_TRY(sync_counts_to_nodes(*tree));
             tree->layout_valid = false;
+            tree->drop_tile_lists();
         }
     }
     return PFQ_OK;
@@ -5093,6 +5154,37 @@ int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n) {
         else v[8] = w[8], v[9] = w[9], v[10] = w[10];  // (the direct path has no pair buffers)
     }
     for (uint64_t i = 0; i < n && i < PFQ_CAPACITY_N; ++i) out[i] = v[i];
+    return PFQ_OK;
+}
+
+int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    out[0] = t.tile_list_cols;
+    out[1] = t.tile_list_cols ? t.d_tile_lists.bytes() : 0;
+    out[2] = out[3] = 0;
+    if (t.d_cursors.p) {
+        PFQ_TRY(wait_last_call(t));
+        unsigned long long c[2];
+        HIP_TRY(hipMemcpy(c, t.d_cursors.p + CUR_TILE_LIST, sizeof c, hipMemcpyDeviceToHost));
+        out[2] = c[0];
+        out[3] = c[1];
+    }
+    return PFQ_OK;
+}
+int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n) {
+    if (!tree || (n && !out)) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    const uint64_t n_tiles = (t.n_words * 64 + (1ull << pfq::TILE_LOG2) - 1) >> pfq::TILE_LOG2;
+    if (col >= t.n_cols || tile >= n_tiles) return fail(PFQ_ERR_ARG, "column / tile out of range");
+    uint32_t row = pfq::TILE_LIST_NONE;
+    if (t.tile_list_cols) HIP_TRY(hipMemcpy(&row, t.d_tile_list_row.p + col, 4, hipMemcpyDeviceToHost));
+    if (row == pfq::TILE_LIST_NONE) return fail(PFQ_ERR_STATE, "column " + std::to_string(col) + " has no position slots (its tiles are loaded dense)");
+    HIP_TRY(hipMemcpy(out, t.d_tile_lists.p + (row * n_tiles + tile) * pfq::TILE_LIST_CAP, std::min<uint64_t>(n, pfq::TILE_LIST_CAP) * 4, hipMemcpyDeviceToHost));
     return PFQ_OK;
 }
 

@@ -263,7 +263,22 @@ struct TileArgs {
     uint32_t *round_k0;          // [max_chunks][MAX_ROUNDS] position (in the chunk) of the first k-mer of every round
     uint32_t *n_rounds;          // [max_chunks]
     uint32_t *pair_kpos;         // [sorted pair] position of the pair's first k-mer in its chunk
+    // position slots of sparse columns (k_tile_test<0> only; both null: every tile is loaded dense)
+    const uint32_t *tile_list_row;  // [n_leaves] the column's row of slots, TILE_LIST_NONE: dense
+    const uint32_t *tile_lists;     // [row][n_tiles][TILE_LIST_CAP]
+    unsigned long long *tile_list_stats;  // [0] += tiles built from slots, [1] += tiles loaded dense (k_tile_test<0>)
 };
+// Position slots (pfq_tilelist.hip): a column whose filter has at most TILE_LIST_CAP set bits in every 2^TILE_LOG2-bit tile
+// keeps, per tile, the tile-relative positions of the set bits in any order, the unused entries TILE_LIST_NONE — 32 KiB
+// in the place of the tile's 128 KiB.  The cap is what 1024 threads hold as two 16-byte loads each.
+constexpr uint32_t TILE_LIST_CAP = 8192;
+constexpr uint32_t TILE_LIST_NONE = 0xffffffffu;
+// col_max[col] = max over the column's tiles of the tile's set bits (the caller zeroes col_max)
+void launch_tile_list_count(const uint64_t *bits, uint64_t n_words, const uint32_t *col_row, uint32_t n_cols, uint32_t n_tiles, uint32_t *col_max,
+                            hipStream_t st);
+// row r of `lists` = the slots of column list_cols[r]
+void launch_tile_list_fill(const uint64_t *bits, uint64_t n_words, const uint32_t *col_row, const uint32_t *list_cols, uint32_t n_list_cols, uint32_t n_tiles,
+                           uint32_t *lists, hipStream_t st);
 void launch_tile_plan(const TileArgs &a, hipStream_t st);
 // returns the build it launched: BIN_WAVES << 16 | BIN_CAP of k_tile_bin (chosen from n_tiles by its LDS need, and bin_shape)
 uint32_t launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st);

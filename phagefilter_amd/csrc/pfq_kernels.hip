@@ -2627,6 +2627,47 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         if (!COUNTS)
             for (uint32_t i = threadIdx.x; i < N_FAILED; i += blockDim.x) s_failed[i] = 0;
     };
+    // MODE 0, a column with position slots (TILE_LIST_CAP, pfq_tilelist.hip): the tile is rebuilt in LDS from the 32 KiB slot
+    // of its set bits instead of loaded.  A thread's 8 entries arrive as two 16-byte loads, in the registers that hold a
+    // dense tile's first loads; pl keeps the entries of the tile that is in LDS, so that the next slot's tile is made by
+    // un-setting those and setting the new ones — after a dense tile (and at the block's first task) zeros are stored once.
+    // All of it is block-uniform: the choice comes with the column.
+    constexpr bool LISTS = MODE == 0;
+    const bool lists_on = LISTS && a.tile_list_row != nullptr && a.tile_lists != nullptr;
+    auto list_row = [&](uint32_t leaf) { return lists_on ? a.tile_list_row[leaf] : TILE_LIST_NONE; };
+    auto list_loads = [&](uint32_t lrow, uint32_t t, uint2 (&v)[TV]) {
+        const uint4 *slot = reinterpret_cast<const uint4 *>(a.tile_lists + ((uint64_t)lrow * a.n_tiles + t) * TILE_LIST_CAP);
+        const uint4 l0 = slot[threadIdx.x], l1 = slot[TILE_LIST_CAP / 8u + threadIdx.x];
+        v[0] = make_uint2(l0.x, l0.y);
+        v[1] = make_uint2(l0.z, l0.w);
+        v[2] = make_uint2(l1.x, l1.y);
+        v[3] = make_uint2(l1.z, l1.w);
+    };
+    uint32_t pl[8] = {TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE, TILE_LIST_NONE};
+    bool cur_list = false;           // the LDS tile holds exactly the bits the threads' pl name
+    uint32_t n_list = 0, n_dense = 0;  // tiles this block took from slots / loaded
+    auto list_store = [&](const uint2 (&v)[TV]) {
+        if (cur_list) {
+#pragma unroll
+            for (uint32_t j = 0; j < 8; ++j)
+                if (pl[j] < (1u << TL)) atomicAnd(&s_tile[pl[j] >> 5], ~(1u << (pl[j] & 31u)));
+        } else {
+#pragma unroll
+            for (uint32_t u = 0; u < TV; ++u) *reinterpret_cast<uint2 *>(s_tile + threadIdx.x * 2 + u * 2048u) = make_uint2(0, 0);
+        }
+        for (uint32_t i = threadIdx.x; i < N_FAILED; i += blockDim.x) s_failed[i] = 0;
+        __syncthreads();  // a bit may be in both slots: every un-set comes before any set
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            pl[2 * j] = v[j].x;
+            pl[2 * j + 1] = v[j].y;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j)
+            if (pl[j] < (1u << TL)) atomicOr(&s_tile[pl[j] >> 5], 1u << (pl[j] & 31u));  // (unused entries are TILE_LIST_NONE)
+        cur_list = true;
+        ++n_list;
+    };
     // COUNTS: the round_k0 rows of the 32 chunks from g0 on: 32 threads per chunk, 8 rounds per thread (rounds the chunk
     // did not have — and chunks of other columns — are never looked up)
     constexpr uint32_t RK_TPC = 1024u / TG, RK_V = TG / 16u;  // threads per chunk; 16-byte loads per thread (4 rounds each)
@@ -2754,12 +2795,18 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
     uint32_t buf = 0, g0 = a.leaf_chunk0[col_of((uint32_t)(task / a.n_tiles))];
     {
         const uint32_t leaf = col_of((uint32_t)(task / a.n_tiles)), t = (uint32_t)(task % a.n_tiles);
+        const uint32_t lrow = list_row(leaf);
         uint2 v[TV];
         uint4 rk[2];
-        tile_loads(leaf, t, v);
+        if (LISTS && lrow != TILE_LIST_NONE) list_loads(lrow, t, v);
+        else tile_loads(leaf, t, v);
         rk_loads(g0, rk);
         if (threadIdx.x < 64) describe(0, leaf, t, g0);
-        tile_store(v);
+        if (LISTS && lrow != TILE_LIST_NONE) list_store(v);
+        else {
+            tile_store(v);
+            ++n_dense;
+        }
         rk_store(rk);
         __syncthreads();
     }
@@ -2770,22 +2817,33 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         const bool have_n = ntask < n_tasks;
         const uint32_t nleaf = have_n ? col_of((uint32_t)(ntask / a.n_tiles)) : 0u, nt = have_n ? (uint32_t)(ntask % a.n_tiles) : 0u;
         const uint32_t ng0 = more ? g0 + TG : (have_n ? a.leaf_chunk0[nleaf] : 0u);
+        const bool nlist = LISTS && have_n && !more && list_row(nleaf) != TILE_LIST_NONE;  // (block-uniform)
         uint2 vn[TV];
         uint4 rkn[2];
-        if (have_n && !more) tile_loads(nleaf, nt, vn);  // in flight while this unit's entries stream
+        // in flight while this unit's entries stream
+        if (nlist) list_loads(a.tile_list_row[nleaf], nt, vn);
+        else if (have_n && !more) tile_loads(nleaf, nt, vn);
         if (have_n) rk_loads(ng0, rkn);
         if (have_n && threadIdx.x < 64) describe(buf ^ 1u, nleaf, nt, ng0);
         stream(buf);
         __syncthreads();  // everybody is done with this unit's tile, descriptors and tables; the next unit's descriptors are written
         if (!have_n) break;
-        if (!more) tile_store(vn);  // (clears the bitmap of reported failures)
-        else if (!COUNTS)
+        if (nlist) list_store(vn);  // (both clear the bitmap of reported failures)
+        else if (!more) {
+            tile_store(vn);
+            cur_list = false;
+            ++n_dense;
+        } else if (!COUNTS)
             for (uint32_t i = threadIdx.x; i < N_FAILED; i += blockDim.x) s_failed[i] = 0;
         rk_store(rkn);
         __syncthreads();
         task = ntask;
         g0 = ng0;
         buf ^= 1u;
+    }
+    if (LISTS && a.tile_list_stats && threadIdx.x == 0) {
+        if (n_list) atomicAdd(&a.tile_list_stats[0], (unsigned long long)n_list);
+        if (n_dense) atomicAdd(&a.tile_list_stats[1], (unsigned long long)n_dense);
     }
 }
 void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st) {

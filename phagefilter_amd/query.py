@@ -202,6 +202,23 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_last_capacity(self._h, out.ctypes.data, out.size))
         return {k: int(v) for k, v in zip(self.CAPACITY_FIELDS, out)}
 
+    TILE_LIST_CAP = 8192
+    TILE_LIST_NONE = 0xFFFFFFFF
+
+    def tile_lists_info(self) -> dict:
+        """Position slots of the sparse columns (pfq_tile_lists_info): `columns` that have them, the `bytes` they hold, and
+        how many tiles k_tile_test<0> of the last query call built from slots (`list_tiles`) and loaded (`dense_tiles`)."""
+        out = np.zeros(4, dtype=np.uint64)
+        _ffi.check(_ffi.lib().pfq_tile_lists_info(self._h, out.ctypes.data))
+        return {k: int(v) for k, v in zip(("columns", "bytes", "list_tiles", "dense_tiles"), out)}
+
+    def tile_list(self, col: int, tile: int) -> np.ndarray:
+        """One slot (pfq_debug_tile_list): TILE_LIST_CAP u32, the tile-relative positions of the tile's set bits in any order,
+        then TILE_LIST_NONE.  Raises PfqError for a column without slots."""
+        out = np.zeros(self.TILE_LIST_CAP, dtype=np.uint32)
+        _ffi.check(_ffi.lib().pfq_debug_tile_list(self._h, col, tile, out.ctypes.data, out.size))
+        return out
+
     def profile_begin(self, max_calls: int) -> None:
         _ffi.check(_ffi.lib().pfq_profile_begin(self._h, max_calls))
 

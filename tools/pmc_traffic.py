@@ -50,7 +50,7 @@ def main() -> None:
         per[name] += int(v.get("TCC_EA0_RDREQ_sum", 0) * 128 + v.get("TCC_EA0_WRREQ_sum", 0) * 64)
     js = {"reads_per_step": reads, "leaves": leaves, "threshold": thr, "source_stamp": source_stamp(),
           "hbm_bytes_per_launch": dict(per),
-          "source": "rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum (own pass, --kernel-trace only) of bench.py; "
+          "source": "rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum (a pass of its own, no tracing beside --pmc) of bench.py; "
                     "bytes = RDREQ*128 B + WRREQ*64 B summed over the kernel's dispatches of the last step; "
                     "Infinity-Cache hits are included in the EA counters"}
     json.dump(js, open(out, "w"), indent=1)
