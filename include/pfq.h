@@ -795,7 +795,9 @@ typedef struct pfq_stats {
                                  * (theta = 1 with records unless PFQ_SPLIT_RECORDS=0).  Bits 4-6: the shapes of
                                  * last-window pass that served at least one pair — 0x10: sixteen reads x 4 k-mers,
                                  * 0x20: four x 16, 0x40: two x 32 (none: no last window was left to the batched kernel).
-                                 * Bit 3 (0x8): k_classify emitted at least one pair a pass at a time (theta = 1, leaf pairs — not in block mode — unless PFQ_BATCH_EMIT=0) */
+                                 * Bit 3 (0x8): k_classify emitted at least one pair a pass at a time (theta = 1, leaf pairs — not in block mode — unless PFQ_BATCH_EMIT=0).
+                                 * Bit 7 (0x80): at least one pass ran the slots-only build of k_tile_test<0> (theta = 1, not in block
+                                 * mode, every column of the tree has position slots, unless PFQ_TILE_STREAM=0) */
 } pfq_stats;
 int pfq_last_stats(pfq_tree *tree, pfq_stats *out);
 /* Force a query path: -1 auto, 0 direct, 1 bucketed. */

@@ -112,6 +112,7 @@ struct Knobs {
     long long text_tile = -1;                   // pfq_text_parse: bytes of text a block scans (a power of two, 256 .. the built-in 8192)
     long long sweep_lds = -1;                   // PFQ_WANT_SWEEP: 0: count `pass` with global atomics although its bins fit the block's LDS
     long long tile_lists = -1;                  // 0: no position slots, k_tile_test loads every tile dense (unset: slots for every sparse column)
+    long long tile_stream = -1;                 // 0: the generic k_tile_test<0> even where every column has slots (unset: the slots-only build there)
 };
 struct KnobName {
     const char *name;
@@ -144,7 +145,7 @@ const KnobName KNOBS[] = {
     {"PFQ_SIM_SLICES", &Knobs::sim_slices},     {"PFQ_SIM_NAIVE", &Knobs::sim_naive},
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
     {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
-    {"PFQ_TILE_LISTS", &Knobs::tile_lists},
+    {"PFQ_TILE_LISTS", &Knobs::tile_lists},     {"PFQ_TILE_STREAM", &Knobs::tile_stream},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -309,6 +310,7 @@ struct pfq_tree {
     DevBuf<uint32_t> d_round_k0, d_n_rounds, d_pair_kpos;  // thresholds < 1: LDS-tile passes with k-mer entries
     uint32_t last_tile_mode = 0, last_passes = 1;
     uint32_t last_sort = 0;            // kernel the last call sorted its pairs with (pfq::SORT_SLICED / SORT_PER_PAIR); 0: direct path
+    bool last_tile_stream = false;     // the last call's passes ran the slots-only build of k_tile_test<0>
     uint32_t last_tile_bin = 0;        // build of k_tile_bin the last call launched (waves << 16 | bin capacity); 0: no pass
     DevBuf<uint2> d_hit_pairs, d_pairs, d_sorted;
     DevBuf<uint32_t> d_bucket, d_fail;  // bucket: cnt[n], off[n+1], cur[n]
@@ -1879,6 +1881,7 @@ struct QueryRun {
         if (kn.tile_gb >= 0) tile_budget = (uint64_t)kn.tile_gb << 30;
         t.last_tile_mode = 0;
         t.last_tile_bin = 0;
+        t.last_tile_stream = false;
         if (tile_mode) {
             // every read may survive with one candidate: (bases - (k-1) per read) * hashes * 1.125 + slack per bucket
             const uint64_t max_chunks = nc + ((t.leaf_cap + t.guard_cap) >> chunk_log2) + 2;
@@ -1942,6 +1945,8 @@ struct QueryRun {
                     if (t.tile_list_cols && kn.tile_lists != 0) {
                         ta.tile_list_row = t.d_tile_list_row.p;
                         ta.tile_lists = t.d_tile_lists.p;
+                        // the tree decides the build, once, with its layout: slots-only where no column has a dense tile
+                        ta.tile_stream = t.tile_list_cols == t.n_cols && kn.tile_stream != 0;
                     }
                 }
                 if (counts_mode) {
@@ -1978,6 +1983,7 @@ struct QueryRun {
                     t.last_tile_bin = pfq::launch_tile_bin(ta, bin_blocks, st);
                     if (p == 0 && ev) HIP_TRY(hipEventRecord(ev[3], st));
                     pfq::launch_tile_test(ta, test_blocks, st);
+                    t.last_tile_stream = ta.tile_stream != 0;
                 }
                 v.pair_chunk = t.d_pair_chunk.p;
                 v.chunks = t.d_chunks.p;
@@ -5036,7 +5042,7 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
         HIP_TRY(hipMemcpy(c, t.d_cursors.p, sizeof c, hipMemcpyDeviceToHost));
         const uint32_t shapes = t.last_path ? (uint32_t)c[CUR_TAIL_SHAPES] : 0u;  // pfq::TAIL_SHAPE_*
         out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u) |
-                          ((t.last_path && h[pfq::ST_BATCHED]) ? 8u : 0u);
+                          ((t.last_path && h[pfq::ST_BATCHED]) ? 8u : 0u) | ((t.last_path && t.last_tile_mode && t.last_tile_stream) ? 0x80u : 0u);
         out->n_chunks = (uint32_t)c[CUR_CHUNKS_FLAGGED];
         out->n_fallback_pairs = (uint32_t)(c[CUR_CHUNKS_FLAGGED] >> 32);
         out->tile_entries = c[CUR_TILE_ENTRIES];

@@ -267,6 +267,7 @@ struct TileArgs {
     const uint32_t *tile_list_row;  // [n_leaves] the column's row of slots, TILE_LIST_NONE: dense
     const uint32_t *tile_lists;     // [row][n_tiles][TILE_LIST_CAP]
     unsigned long long *tile_list_stats;  // [0] += tiles built from slots, [1] += tiles loaded dense (k_tile_test<0>)
+    uint32_t tile_stream;           // 1: EVERY column has slots (tile_list_row[c] == c for all columns): the slots-only build runs
 };
 // Position slots (pfq_tilelist.hip): a column whose filter has at most TILE_LIST_CAP set bits in every 2^TILE_LOG2-bit tile
 // keeps, per tile, the tile-relative positions of the set bits in any order, the unused entries TILE_LIST_NONE — 32 KiB

@@ -2552,10 +2552,16 @@ constexpr uint32_t TEST_GROUP = 32;  // chunks of a leaf whose buckets are strea
 // MODE 2 (block mode): the tile is 2^17 BYTES of the block's table, bit j of a byte = that Bloom bit of leaf 8b + j; an entry
 // carries the mask of the pair's candidate leaves; a candidate whose bit is 0 gets its failure byte set (plain stores: one
 // byte per (pair, leaf)), reported once per block and task through the LDS bitmap.
-template <uint32_t MODE>
+// DEPTH > 0 (MODE 0 only): the slots-only build, launched when every column of the tree has position slots.  No dense tile
+// exists in it, and the registers that would hold one carry a rotating pipeline of DEPTH entry steps per thread instead
+// (see the end of the kernel).  CARRY: the pipeline stays filled across the switch from one unit to the next.
+template <uint32_t MODE, uint32_t DEPTH = 0, bool CARRY = false>
 __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
     // MODE 3 (block mode at thresholds < 1): k-mer entries against the block's byte table; the candidate mask comes with the
     // chunk (buckets are keyed by (block, mask)); a candidate whose bit is 0 gets the k-mer's miss byte of that leaf set.
+    constexpr bool SLOTS = DEPTH != 0;
+    static_assert(!SLOTS || MODE == 0, "the slots-only build is a build of MODE 0");
+    constexpr uint32_t NSET = SLOTS ? 3 : 2;  // descriptor sets (the slots-only build describes two units ahead)
     constexpr bool COUNTS = MODE == 1 || MODE == 3, BLK = MODE == 2, BLKC = MODE == 3;
     constexpr uint32_t TL = MODE == 1 ? TILE_LOG2_COUNTS : (MODE >= 2 ? TILE_LOG2_BLOCK : TILE_LOG2);
     constexpr uint32_t TILE_BYTES = MODE >= 2 ? (1u << TL) : (1u << (TL - 3));
@@ -2566,21 +2572,27 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
     constexpr uint32_t TG = (BLK || BLKC) ? 16 : TEST_GROUP;
     constexpr uint32_t RK = COUNTS ? MAX_ROUNDS : 1u;
     extern __shared__ uint32_t s_tile[];  // 2^TL bits
-    __shared__ uint32_t s_pref[2][TG + 1], s_first[2][TG], s_misc[2][2], s_kbase[2][TG], s_mask[2][TG];
+    __shared__ uint32_t s_pref[NSET][TG + 1], s_first[NSET][TG], s_misc[NSET][2], s_kbase[2][TG], s_mask[2][TG];
     const uint32_t n_cols = a.n_leaves;
     auto col_of = [&](uint32_t li) { return li; };
     // failures this block already reported: a bit per pair of the group (MODE 0), per (pair, leaf of the block) (MODE 2)
     __shared__ uint32_t s_failed[COUNTS ? 1 : (BLK ? (TG << (CL - 2)) : (TG << (CL - 5)))];
     constexpr uint32_t N_FAILED = COUNTS ? 0 : (BLK ? (TG << (CL - 2)) : (TG << (CL - 5)));
     __shared__ uint32_t s_rk0[COUNTS ? TG : 1][RK];                               // round_k0 rows of the group's chunks
-    __shared__ unsigned long long s_base[2][TG];
+    __shared__ unsigned long long s_base[NSET][TG];
     const uint32_t tile_words = TILE_BYTES / 4u;
     const uint64_t n_words32 = a.n_words * 2;  // (block mode: n_words = bytes / 8 of one block's table)
     const uint64_t n_tasks = (uint64_t)n_cols * a.n_tiles;
     const uint32_t n_chunks = *a.n_chunks < a.max_chunks ? *a.n_chunks : a.max_chunks;
     // next task of this block at or after `task` whose column has pairs at all (block-uniform)
+    // (the slots-only build reads the table as constant memory — the plan wrote it before this kernel: scalar loads, which
+    // do not queue behind the entry loads in flight; after the kernel's first store a plain load would be a vector one)
+    auto chunk0_of = [&](uint32_t col) {
+        if constexpr (SLOTS) return ((const __attribute__((address_space(4))) uint32_t *)a.leaf_chunk0)[col];
+        else return a.leaf_chunk0[col_of(col)];
+    };
     auto valid_task = [&](uint64_t task) {
-        while (task < n_tasks && a.leaf_chunk0[col_of((uint32_t)(task / a.n_tiles))] == 0xffffffffu) task += gridDim.x;
+        while (task < n_tasks && chunk0_of((uint32_t)(task / a.n_tiles)) == 0xffffffffu) task += gridDim.x;
         return task;
     };
     // The buckets (this tile's) of up to 32 chunks of the column starting at chunk g0, described in LDS: they are streamed
@@ -2786,6 +2798,174 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         }
     };
 
+    if constexpr (SLOTS) {
+        // The slots-only build.  A step is four 16-byte loads a thread (16 k entries a block), as above; a thread keeps
+        // DEPTH steps in flight in rotating registers: step i + DEPTH is issued right after step i is tested, and a test
+        // waits for its own step only.  Every step issues its four loads unconditionally — a lane past the unit's end loads
+        // entry 0 and ignores it — so that the waits are counted ones (a load under a branch makes the compiler wait for
+        // everything at the next use).  What travels with a step is one word: per load the bucket (5 bits) and a valid bit;
+        // `first` is looked up from the bucket where a pair fails.
+        // CARRY: the last round of a unit issues the first DEPTH steps of the NEXT unit, so the queues stay filled across
+        // the barriers and list_store; they are tested once the new tile stands in LDS.  For that the next unit's
+        // descriptors are visible a unit earlier: three sets, unit n + 2 is described while unit n streams — wave 0 issues
+        // the descriptor loads before the stream and takes the prefix sum after it, so no wave waits for them.
+        constexpr uint32_t STEP = 1024u * 4u * TEST_LOADS;  // entries of a step
+        uint4 en[DEPTH][TEST_LOADS];
+        uint32_t pk[DEPTH];
+        uint32_t ci = 0;  // bucket of the thread's position in the unit whose steps are being issued (positions only grow)
+#pragma unroll
+        for (uint32_t j = 0; j < DEPTH; ++j) {
+            pk[j] = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < TEST_LOADS; ++u) en[j][u] = make_uint4(ENTRY_PAD, ENTRY_PAD, ENTRY_PAD, ENTRY_PAD);
+        }
+        auto issue = [&](uint32_t j, uint32_t set, uint32_t step, uint32_t total) {
+            uint32_t word = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < TEST_LOADS; ++u) {
+                const uint32_t v = step * STEP + u * 4096u + threadIdx.x * 4u;
+                const bool have = v < total;
+                if (have)
+                    while (v >= s_pref[set][ci + 1]) ++ci;
+                const uint64_t at = have ? s_base[set][ci] + (v - s_pref[set][ci]) : 0ull;
+                en[j][u] = *reinterpret_cast<const uint4 *>(a.entries + at);
+                word |= (have ? 0x80u | ci : 0u) << (8u * u);
+            }
+            pk[j] = word;
+        };
+        auto test = [&](uint32_t j, uint32_t set) {
+#pragma unroll
+            for (uint32_t u = 0; u < TEST_LOADS; ++u) {
+                const uint32_t w = pk[j] >> (8u * u);
+                if (!(w & 0x80u)) continue;
+                const uint32_t ev[4] = {en[j][u].x, en[j][u].y, en[j][u].z, en[j][u].w};
+#pragma unroll
+                for (uint32_t c = 0; c < 4; ++c) {
+                    const uint32_t off = ev[c] & ((1u << TL) - 1u);
+                    if (ev[c] != ENTRY_PAD && !((s_tile[off >> 5] >> (off & 31u)) & 1u)) {  // (as in stream())
+                        const uint32_t b = w & 31u, lp = ev[c] >> TL, fb = (b << CL) + lp;
+                        if (!(atomicOr(&s_failed[fb >> 5], 1u << (fb & 31u)) & (1u << (fb & 31u)))) atomicOr(&a.fail[s_first[set][b] + lp], 1u);
+                    }
+                }
+            }
+        };
+        static_assert(TEST_GROUP <= 32, "a step's word has 5 bits per bucket");
+        // describe(), split: the loads and, a unit's stream later, the prefix sum and the stores (threads 0..63).  Every
+        // thread issues the loads, without a branch around them — the others load the group's first chunk, one line a wave:
+        // a branch would end in copies of the loaded registers, and those wait for the loads where they were issued.
+        struct Described {
+            // the ChunkDesc's fields as 32-bit words, base in two halves that are never used as one 64-bit value: its loads
+            // merge with cap's into three words, the pair lands in odd registers, and a 64-bit use makes the compiler copy it
+            // to an even pair right behind the load — with a wait for the load and everything issued before it
+            uint32_t first, cap, base_lo, base_hi, leaf, pass;
+            uint32_t fill;
+            bool in;
+        };
+        static_assert(sizeof(ChunkDesc) == 48 && offsetof(ChunkDesc, first) == 4 && offsetof(ChunkDesc, cap) == 12 && offsetof(ChunkDesc, base) == 16 &&
+                          offsetof(ChunkDesc, leaf) == 24 && offsetof(ChunkDesc, pass) == 28,
+                      "describe_loads reads a ChunkDesc as 32-bit words");
+        auto describe_loads = [&](uint32_t t, uint32_t g) {
+            Described d{};
+            const uint32_t i = threadIdx.x < TG ? threadIdx.x : 0u;
+            d.in = threadIdx.x < TG && g + i < n_chunks;
+            const uint32_t c = g + i < n_chunks ? g + i : n_chunks - 1u;  // (a block with a task has a chunk)
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(a.chunks + c);
+            d.first = w[1], d.cap = w[3], d.base_lo = w[4], d.base_hi = w[5], d.leaf = w[6], d.pass = w[7];
+            d.fill = a.gfill[(uint64_t)c * a.n_tiles + t];
+            return d;
+        };
+        auto describe_put = [&](uint32_t set, uint32_t leaf, uint32_t t, const Described &d) {
+            const uint32_t i = threadIdx.x;
+            const bool mine = d.in && d.leaf == leaf;
+            const bool usable = mine && d.cap != 0 && d.pass == a.pass;
+            uint32_t fill = usable ? d.fill : 0u;
+            if (fill > d.cap) fill = d.cap;
+            uint32_t incl = fill;
+            for (uint32_t sft = 1; sft < TG; sft <<= 1) {
+                const uint32_t o = (uint32_t)__shfl_up((int)incl, (int)sft);
+                if (i >= sft) incl += o;
+            }
+            if (i < TG) {
+                s_pref[set][i + 1] = incl;
+                s_first[set][i] = d.first;
+                // base + t * cap, in halves
+                const uint32_t lo = d.base_lo + t * d.cap, hi = d.base_hi + __umulhi(t, d.cap) + (lo < d.base_lo ? 1u : 0u);
+                uint32_t *dst = reinterpret_cast<uint32_t *>(&s_base[set][i]);
+                dst[0] = lo;
+                dst[1] = hi;
+            }
+            const uint64_t mm = ballot64(mine);
+            if (i == 0) {
+                s_pref[set][0] = 0;
+                s_misc[set][0] = (uint32_t)__popcll(mm);
+            }
+        };
+        // the unit after (task, g): the column's next group if this one was full, else the first group of the block's next task
+        auto unit_after = [&](uint64_t task, uint32_t g, bool more, uint64_t &ntask, uint32_t &ng) {
+            ntask = more ? task : valid_task(task + gridDim.x);
+            if (ntask >= n_tasks) return false;
+            ng = more ? g + TG : chunk0_of((uint32_t)(ntask / a.n_tiles));
+            return true;
+        };
+        auto leaf_of = [&](uint64_t task) { return (uint32_t)(task / a.n_tiles); };
+        auto tile_of = [&](uint64_t task) { return (uint32_t)(task % a.n_tiles); };
+        // units 0, 1, 2 = current, next, the one after; their descriptor sets rotate
+        uint64_t task0 = valid_task(blockIdx.x), task1 = 0, task2 = 0;
+        if (task0 >= n_tasks) return;
+        uint32_t g0 = chunk0_of(leaf_of(task0)), g1 = 0, g2 = 0, d0 = 0, d1 = 1, d2 = 2;
+        bool have1;
+        {
+            uint2 v[TV];
+            list_loads(leaf_of(task0), tile_of(task0), v);  // (every column has slots: a column's row of slots is its own number)
+            const Described d = describe_loads(tile_of(task0), g0);
+            if (threadIdx.x < 64) describe_put(d0, leaf_of(task0), tile_of(task0), d);
+            list_store(v);  // (the block's first task: zeros are stored, once)
+            __syncthreads();
+            have1 = unit_after(task0, g0, s_misc[d0][0] == TG, task1, g1);
+            const Described d1st = describe_loads(have1 ? tile_of(task1) : 0u, have1 ? g1 : 0u);
+            if (have1 && threadIdx.x < 64) describe_put(d1, leaf_of(task1), tile_of(task1), d1st);
+            __syncthreads();
+        }
+        uint32_t total0 = s_pref[d0][TG];
+#pragma unroll
+        for (uint32_t j = 0; j < DEPTH; ++j) issue(j, d0, j, total0);
+        while (true) {
+            const bool have2 = have1 && unit_after(task1, g1, s_misc[d1][0] == TG, task2, g2);
+            const bool tile1 = have1 && task1 != task0;  // the next unit brings another tile
+            uint2 vn[TV];
+            if (tile1) list_loads(leaf_of(task1), tile_of(task1), vn);  // in flight while this unit streams
+            const Described dn = describe_loads(have2 ? tile_of(task2) : 0u, have2 ? g2 : 0u);
+            const uint32_t total1 = (CARRY && have1) ? s_pref[d1][TG] : 0u;
+            const uint32_t steps0 = (total0 + STEP - 1u) / STEP;
+            for (uint32_t s = 0; s < steps0 || s == 0; s += DEPTH) {
+                const bool last = s + DEPTH >= steps0;  // (block-uniform)
+                if (last) ci = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < DEPTH; ++j) {
+                    test(j, d0);
+                    issue(j, last ? d1 : d0, last ? j : s + DEPTH + j, last ? total1 : total0);
+                }
+            }
+            if (have2 && threadIdx.x < 64) describe_put(d2, leaf_of(task2), tile_of(task2), dn);
+            __syncthreads();  // everybody is done with this unit's tile and descriptors; those of the unit after the next are written
+            if (!have1) break;
+            if (tile1) list_store(vn);  // (clears the bitmap of reported failures)
+            else
+                for (uint32_t i = threadIdx.x; i < N_FAILED; i += blockDim.x) s_failed[i] = 0;
+            __syncthreads();
+            task0 = task1, g0 = g1, task1 = task2, g1 = g2, have1 = have2;
+            const uint32_t d = d0;
+            d0 = d1, d1 = d2, d2 = d;
+            total0 = s_pref[d0][TG];
+            if (!CARRY) {
+                ci = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < DEPTH; ++j) issue(j, d0, j, total0);
+            }
+        }
+        if (a.tile_list_stats && threadIdx.x == 0 && n_list) atomicAdd(&a.tile_list_stats[0], (unsigned long long)n_list);
+        return;
+    }
     // The unit of the pipeline is (task, group of TG chunks of the task's column): while a unit's entries stream, the
     // next unit's bucket descriptors (and round tables) are fetched into the other half of the descriptor arrays, and — when
     // the next unit belongs to another task — its tile into registers.  (A column of a family workload has hundreds of
@@ -2846,10 +3026,22 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         if (n_dense) atomicAdd(&a.tile_list_stats[1], (unsigned long long)n_dense);
     }
 }
+// The slots-only build of MODE 0: steps in flight per thread, and whether they are carried across the unit switch (both
+// can be set at build time for an A/B; DESIGN.md §7: depth 3 is no faster at 1024 leaves, 3.88 against 3.87 ms, and slower
+// at 4096, 6.55 against 5.74 ms, where a task has little more than one step and the third step of a round is an idle one;
+// without the carry 4.25 against 3.89 ms).
+#ifndef PFQ_STREAM_DEPTH
+#define PFQ_STREAM_DEPTH 2
+#endif
+#ifndef PFQ_STREAM_CARRY
+#define PFQ_STREAM_CARRY 1
+#endif
 void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st) {
     static std::atomic<uint64_t> attr_done{0};
+    const auto k_stream = k_tile_test<0, PFQ_STREAM_DEPTH, PFQ_STREAM_CARRY != 0>;
     if (first_on_device(attr_done)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stream), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         // (static LDS of the k-mer-entry build: the 32 KiB of round_k0 rows; static + dynamic must stay within the CU's 160 KiB)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << (TILE_LOG2_COUNTS - 3));
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << TILE_LOG2_BLOCK);
@@ -2859,6 +3051,7 @@ void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st) {
     if (a.counts && a.blocks) hipLaunchKernelGGL(k_tile_test<3>, g, b, (size_t)(1u << TILE_LOG2_BLOCK), st, a);
     else if (a.counts) hipLaunchKernelGGL(k_tile_test<1>, g, b, (size_t)(1u << (TILE_LOG2_COUNTS - 3)), st, a);
     else if (a.blocks) hipLaunchKernelGGL(k_tile_test<2>, g, b, (size_t)(1u << TILE_LOG2_BLOCK), st, a);
+    else if (a.tile_stream && a.tile_list_row && a.tile_lists) hipLaunchKernelGGL(k_stream, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
     else hipLaunchKernelGGL(k_tile_test<0>, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
 }
 
