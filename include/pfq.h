@@ -765,6 +765,18 @@ int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]);
 /* Copy min(n, 8192) entries of the slot of (column, tile) to the host: positions < 2^20 in any order, unused entries
  * 0xffffffff.  A column without slots: PFQ_ERR_STATE. */
 int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n);
+/* tests: one probe bucket of the last query call's LDS-tile passes at theta = 1 (not block mode), copied to the host after the
+ * call (waits for it).  The buckets are reused pass after pass: a chunk's bucket holds its entries only if no later pass took
+ * its place.  out, of cap >= PFQ_TILE_BUCKET_WORDS u32: [0] fill mark in 32-bit words (may exceed the capacity: what did not
+ * fit took the fallback), [1] the words of the bucket the format uses (packed: 4/5 of its capacity, room for as many entries), [2] first sorted pair of the chunk, [3] its pairs, [4] its column, [5] its
+ * pass, [6] 1: packed entries, [7] chunks of the call (written even when `chunk` is out of range), [8] rounds the chunk was
+ * binned in, [16 .. 272) the first pair of every round (both only with packed entries), [272 .. 1296) the read of each of the
+ * chunk's pairs, then min(fill, capacity, cap - PFQ_TILE_BUCKET_WORDS) words of the bucket.
+ * Packed entries: a 16-byte vector is five 24-bit entries [pair of the round : 4][offset in tile : 20], entry j in bits
+ * 24 j .. 24 j + 23, and the round's number in bits 120 .. 127; a run (one round's entries) is padded to a whole vector with
+ * copies of its last entry. */
+#define PFQ_TILE_BUCKET_WORDS 1296
+int pfq_debug_tile_bucket(pfq_tree *tree, uint64_t chunk, uint64_t tile, uint32_t *out, uint64_t cap);
 
 
 /* Per-call statistics of the last pfq_query_batch[_device] (valid after the stream is synchronised). */
@@ -798,6 +810,10 @@ typedef struct pfq_stats {
                                  * Bit 3 (0x8): k_classify emitted at least one pair a pass at a time (theta = 1, leaf pairs — not in block mode — unless PFQ_BATCH_EMIT=0).
                                  * Bit 7 (0x80): at least one pass ran the slots-only build of k_tile_test<0> (theta = 1, not in block
                                  * mode, every column of the tree has position slots, unless PFQ_TILE_STREAM=0) */
+    uint32_t entry_pack;        /* 1: the LDS-tile passes wrote and read packed entries, five 24-bit entries and a round number per
+                                 * 16 bytes (theta = 1, not in block mode; option PFQ_ENTRY_PACK: 0 never, 1 / unset where the call's
+                                 * mean read length makes the format's 16 pairs a round free, 2 always).  (A field of its own, in the
+                                 * padding behind pair_stage: the bits of pair_stage above 3 are the tail shapes and bit 7.) */
 } pfq_stats;
 int pfq_last_stats(pfq_tree *tree, pfq_stats *out);
 /* Force a query path: -1 auto, 0 direct, 1 bucketed. */

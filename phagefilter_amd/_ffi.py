@@ -26,7 +26,7 @@ SYMBOLS = [
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity", "pfq_debug_last_similarity", "pfq_debug_last_recluster",
-    "pfq_tile_lists_info", "pfq_debug_tile_list",
+    "pfq_tile_lists_info", "pfq_debug_tile_list", "pfq_debug_tile_bucket",
     "pfq_synth_genomes_device",
     "pfq_synth_reads_device", "pfq_host_alloc", "pfq_host_free", "pfq_last_error", "pfq_version",
 ]
@@ -57,7 +57,7 @@ class Stats(C.Structure):
                 ("n_chunks", C.c_uint64), ("tile_entries", C.c_uint64), ("tile_passes_launched", C.c_uint32),
                 ("tile_passes_needed", C.c_uint32), ("leaf_groups", C.c_uint32), ("coarse_cols", C.c_uint32),
                 ("coarse_probes", C.c_uint32), ("tile_bin_build", C.c_uint32), ("group_reads", C.c_uint64),
-                ("pair_stage", C.c_uint32)]
+                ("pair_stage", C.c_uint32), ("entry_pack", C.c_uint32)]
 
 
 class Profile(C.Structure):
@@ -255,6 +255,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "pfq_tile_lists_info"):  # (an older build chosen through PFQ_LIBPFQ for an A/B has no position slots)
         L.pfq_tile_lists_info.argtypes = [vp, vp]
         L.pfq_debug_tile_list.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
+    if hasattr(L, "pfq_debug_tile_bucket"):  # (likewise: an older build has no bucket read-back)
+        L.pfq_debug_tile_bucket.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     L.pfq_synth_genomes_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]
     L.pfq_synth_reads_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64,
                                          C.c_uint64, vp]

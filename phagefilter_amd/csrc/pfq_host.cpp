@@ -113,6 +113,7 @@ struct Knobs {
     long long sweep_lds = -1;                   // PFQ_WANT_SWEEP: 0: count `pass` with global atomics although its bins fit the block's LDS
     long long tile_lists = -1;                  // 0: no position slots, k_tile_test loads every tile dense (unset: slots for every sparse column)
     long long tile_stream = -1;                 // 0: the generic k_tile_test<0> even where every column has slots (unset: the slots-only build there)
+    long long entry_pack = -1;                  // packed tile entries at threshold 1: 0 never, 1 / unset chosen per call from its read lengths, 2 always
 };
 struct KnobName {
     const char *name;
@@ -146,6 +147,7 @@ const KnobName KNOBS[] = {
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
     {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
     {"PFQ_TILE_LISTS", &Knobs::tile_lists},     {"PFQ_TILE_STREAM", &Knobs::tile_stream},
+    {"PFQ_ENTRY_PACK", &Knobs::entry_pack},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -308,6 +310,10 @@ struct pfq_tree {
     bool have_cand_hint = false;       // cand_per_read describes this tree's workload (else a sample of the block is screened first)
     uint32_t last_block_mode = 0;
     DevBuf<uint32_t> d_round_k0, d_n_rounds, d_pair_kpos;  // thresholds < 1: LDS-tile passes with k-mer entries
+    DevBuf<uint32_t> d_round_p0;       // threshold 1, packed entries: first pair of every round of every chunk (and d_n_rounds)
+    DevBuf<uint8_t> d_round_fail;      //                              a failure byte per (chunk, round, pair of the round)
+    bool last_entry_pack = false;      // the last call's passes wrote and read packed entries
+    uint32_t last_n_tiles = 0;         // tiles per filter of the last call's passes (pfq_debug_tile_bucket)
     uint32_t last_tile_mode = 0, last_passes = 1;
     uint32_t last_sort = 0;            // kernel the last call sorted its pairs with (pfq::SORT_SLICED / SORT_PER_PAIR); 0: direct path
     bool last_tile_stream = false;     // the last call's passes ran the slots-only build of k_tile_test<0>
@@ -1882,6 +1888,7 @@ struct QueryRun {
         t.last_tile_mode = 0;
         t.last_tile_bin = 0;
         t.last_tile_stream = false;
+        t.last_entry_pack = false;
         if (tile_mode) {
             // every read may survive with one candidate: (bases - (k-1) per read) * hashes * 1.125 + slack per bucket
             const uint64_t max_chunks = nc + ((t.leaf_cap + t.guard_cap) >> chunk_log2) + 2;
@@ -1901,6 +1908,25 @@ struct QueryRun {
                 ok = soft_ensure(t.d_kmiss, kmiss_cap) && soft_ensure(t.d_round_k0, max_chunks * pfq::MAX_ROUNDS) &&
                      soft_ensure(t.d_n_rounds, max_chunks) && soft_ensure(t.d_pair_kpos, t.d_pairs.n);
             if (ok && counts_mode && block_mode) ok = soft_ensure(t.d_kall, (kmiss_cap >> 3) + 64);
+            // Threshold 1 outside block mode: packed entries (pfq::PACK_PAIRS) where the format's limits cost nothing.  A round
+            // of k_tile_bin takes KB k-mers; 16 pairs a round are no cap when a read has at least KB / 16 of them, and a chunk
+            // of 1024 pairs stays under 256 rounds — a round is more than half full where reads are shorter than KB / 2 — when
+            // 2 * 1024 * mean / KB + 2 <= 256.  (Beyond either bound results stay exact: shorter rounds, or the fallback.)
+            bool pack = false;
+            const uint32_t bin_shape = kn.bin_narrow > 0 ? (uint32_t)kn.bin_narrow : (kn.bin_wide > 0 ? 2u : 0u);
+            if (ok && !counts_mode && !block_mode && kn.entry_pack != 0) {
+                pfq::TileArgs shape{};
+                shape.n_tiles = n_tiles;
+                shape.bin_shape = bin_shape;
+                const uint32_t build = pfq::tile_bin_build(shape);
+                const uint64_t KB = pfq::tile_bin_kmer_budget(build >> 16, build & 0xffffu, n_tiles, t.num_hashes, false);
+                const uint64_t kmers = total_bytes > n_reads * (t.kmer_size - 1) ? total_bytes - n_reads * (t.kmer_size - 1) : 0;
+                pack = kn.entry_pack == 2 || (n_reads && kmers * pfq::PACK_PAIRS >= KB * n_reads &&
+                                              (2ull << chunk_log2) * kmers + 2 * KB * n_reads <= pfq::PACK_ROUNDS * KB * n_reads);
+                if (pack)
+                    pack = soft_ensure(t.d_round_p0, max_chunks * pfq::PACK_ROUNDS) && soft_ensure(t.d_n_rounds, max_chunks) &&
+                           soft_ensure(t.d_round_fail, max_chunks * pfq::PACK_ROUNDS * pfq::PACK_PAIRS);
+            }
             if (!ok) {
                 tile_mode = false;  // not enough HBM for the probe buckets: stay with the record kernel
             } else {
@@ -1948,6 +1974,14 @@ struct QueryRun {
                         // the tree decides the build, once, with its layout: slots-only where no column has a dense tile
                         ta.tile_stream = t.tile_list_cols == t.n_cols && kn.tile_stream != 0;
                     }
+                    if (pack) {
+                        ta.entry_pack = 1;
+                        ta.round_p0 = t.d_round_p0.p;
+                        ta.round_fail = t.d_round_fail.p;
+                        ta.n_rounds = t.d_n_rounds.p;
+                        // (k_pack_fail walks the rounds of every chunk: none for a chunk that no launched pass binned)
+                        HIP_TRY(hipMemsetAsync(t.d_n_rounds.p, 0, max_chunks * 4, st));
+                    }
                 }
                 if (counts_mode) {
                     ta.counts = 1;
@@ -1964,7 +1998,7 @@ struct QueryRun {
                 int bin_blocks = 512, test_blocks = 512;
                 if (kn.bin_blocks >= 0) bin_blocks = std::max(1, (int)kn.bin_blocks);
                 if (kn.test_blocks >= 0) test_blocks = std::max(1, (int)kn.test_blocks);
-                ta.bin_shape = kn.bin_narrow > 0 ? (uint32_t)kn.bin_narrow : (kn.bin_wide > 0 ? 2u : 0u);
+                ta.bin_shape = bin_shape;
                 ta.debug = kn.bin_debug > 0 ? (uint32_t)kn.bin_debug : 0u;
                 pfq::launch_tile_plan(ta, st);
                 // The probe buckets of all pairs may exceed the buffer (reads that pass many leaves): the plan
@@ -1985,6 +2019,9 @@ struct QueryRun {
                     pfq::launch_tile_test(ta, test_blocks, st);
                     t.last_tile_stream = ta.tile_stream != 0;
                 }
+                pfq::launch_pack_fail(ta, st);  // (packed entries: the failures of all passes become fail words)
+                t.last_entry_pack = ta.entry_pack != 0;
+                t.last_n_tiles = n_tiles;
                 v.pair_chunk = t.d_pair_chunk.p;
                 v.chunks = t.d_chunks.p;
                 v.entry_cursor = t.d_cursors.p + CUR_TILE_ENTRIES;
@@ -5043,6 +5080,7 @@ int pfq_last_stats(pfq_tree *tree, pfq_stats *out) {
         const uint32_t shapes = t.last_path ? (uint32_t)c[CUR_TAIL_SHAPES] : 0u;  // pfq::TAIL_SHAPE_*
         out->pair_stage = t.last_sort | ((shapes & 7u) << 4) | ((shapes & pfq::TAIL_SHAPE_FULL) ? 4u : 0u) |
                           ((t.last_path && h[pfq::ST_BATCHED]) ? 8u : 0u) | ((t.last_path && t.last_tile_mode && t.last_tile_stream) ? 0x80u : 0u);
+        out->entry_pack = (t.last_path && t.last_tile_mode && t.last_entry_pack) ? 1u : 0u;
         out->n_chunks = (uint32_t)c[CUR_CHUNKS_FLAGGED];
         out->n_fallback_pairs = (uint32_t)(c[CUR_CHUNKS_FLAGGED] >> 32);
         out->tile_entries = c[CUR_TILE_ENTRIES];
@@ -5191,6 +5229,42 @@ int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *o
     if (t.tile_list_cols) HIP_TRY(hipMemcpy(&row, t.d_tile_list_row.p + col, 4, hipMemcpyDeviceToHost));
     if (row == pfq::TILE_LIST_NONE) return fail(PFQ_ERR_STATE, "column " + std::to_string(col) + " has no position slots (its tiles are loaded dense)");
     HIP_TRY(hipMemcpy(out, t.d_tile_lists.p + (row * n_tiles + tile) * pfq::TILE_LIST_CAP, std::min<uint64_t>(n, pfq::TILE_LIST_CAP) * 4, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+int pfq_debug_tile_bucket(pfq_tree *tree, uint64_t chunk, uint64_t tile, uint32_t *out, uint64_t cap) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    if (!t.d_cursors.p || !t.last_tile_mode || t.last_block_mode || !t.last_n_tiles) return fail(PFQ_ERR_STATE, "the last call ran no LDS-tile pass at threshold 1");
+    if (cap < PFQ_TILE_BUCKET_WORDS) return fail(PFQ_ERR_ARG, "the buffer holds less than the header and the tables");
+    PFQ_TRY(wait_last_call(t));
+    unsigned long long n_chunks = 0;
+    HIP_TRY(hipMemcpy(&n_chunks, t.d_cursors.p + CUR_CHUNKS_FLAGGED, 8, hipMemcpyDeviceToHost));
+    n_chunks = std::min<uint64_t>(n_chunks & 0xffffffffu, t.d_chunks.n);
+    memset(out, 0, PFQ_TILE_BUCKET_WORDS * 4);
+    out[7] = (uint32_t)n_chunks;
+    if (chunk >= n_chunks || tile >= t.last_n_tiles) return fail(PFQ_ERR_ARG, "chunk / tile out of range");
+    pfq::ChunkDesc dsc;
+    HIP_TRY(hipMemcpy(&dsc, t.d_chunks.p + chunk, sizeof dsc, hipMemcpyDeviceToHost));
+    uint32_t fill = 0;
+    HIP_TRY(hipMemcpy(&fill, t.d_gfill.p + chunk * t.last_n_tiles + tile, 4, hipMemcpyDeviceToHost));
+    out[0] = fill;
+    out[1] = t.last_entry_pack ? pfq::pack_bucket_words(dsc.cap) : dsc.cap;
+    out[2] = dsc.first;
+    out[3] = dsc.n;
+    out[4] = dsc.leaf;
+    out[5] = dsc.pass;
+    out[6] = t.last_entry_pack ? 1u : 0u;
+    if (t.last_entry_pack) {
+        HIP_TRY(hipMemcpy(out + 8, t.d_n_rounds.p + chunk, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out + 16, t.d_round_p0.p + chunk * pfq::PACK_ROUNDS, pfq::PACK_ROUNDS * 4, hipMemcpyDeviceToHost));
+    }
+    std::vector<uint2> pairs(dsc.n);
+    if (dsc.n) HIP_TRY(hipMemcpy(pairs.data(), t.d_sorted.p + dsc.first, dsc.n * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < dsc.n && i < (1u << pfq::CHUNK_PAIRS_LOG2); ++i) out[16 + pfq::PACK_ROUNDS + i] = pairs[i].x;
+    const uint64_t words = std::min<uint64_t>(std::min(fill, out[1]), cap - PFQ_TILE_BUCKET_WORDS);
+    if (words) HIP_TRY(hipMemcpy(out + PFQ_TILE_BUCKET_WORDS, t.d_entries.p + dsc.base + tile * dsc.cap, words * 4, hipMemcpyDeviceToHost));
     return PFQ_OK;
 }
 

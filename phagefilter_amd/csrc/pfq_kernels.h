@@ -197,6 +197,31 @@ constexpr uint32_t MAX_TILES = 1024;               // tiles per filter the passe
 constexpr uint32_t TILE_LOG2_COUNTS = 19;          // 64 KiB tiles (twice the tiles, 128-entry deeper bins than needed)
 constexpr uint32_t ROUND_KMERS_LOG2 = 11;          // flattened k-mers per round of k_tile_bin (= 2 windows x 16 waves)
 constexpr uint32_t MAX_ROUNDS = 256;               // rounds per chunk the tags can name; later pairs take the fallback
+// Threshold 1, packed entries (TileArgs::entry_pack): a 16-byte vector of a bucket holds FIVE 24-bit entries [pair of the
+// round : 4][offset in tile : 20], entry j in bits 24 j .. 24 j + 23, and in bits 120..127 the number of the k_tile_bin round
+// the run belongs to.  round_p0[chunk][round] is the round's first pair (in the chunk); a run — the entries of one (round,
+// tile) — is padded to a whole vector with copies of its last entry.  Fill marks and capacities stay in 32-bit words.
+constexpr uint32_t PACK_PAIRS = 16;                // pairs per round the 4-bit id can name
+constexpr uint32_t PACK_ROUNDS = 256;              // rounds per chunk the tag can name; later pairs take the fallback
+// 32-bit words of a bucket of `cap` words that packed entries use: room for `cap` entries, as with 32-bit entries — the same
+// probes overflow into the fallback in either format, and the plan's capacities can shrink by the spare fifth later.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t pack_bucket_words(uint32_t cap) { return cap / 5u * 4u; }
+// k-mers a round of k_tile_bin<waves, cap> takes: the bins fill to 3/4 on average (shallow bins of many tiles — block mode —
+// to 1/2: an overflow costs the round's pairs the fallback, and 30 +- 5.5 entries must stay below 60), and at most
+// TILE_BIN_WPI windows of 64 k-mers a wave.  (The host chooses the entry format of a call from it.)
+constexpr uint32_t TILE_BIN_WPI = 2;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t tile_bin_kmer_budget(uint32_t waves, uint32_t cap, uint32_t n_tiles, uint32_t num_hashes, bool counts) {
+    uint32_t kb = (uint32_t)(((uint64_t)(cap < 128 ? cap / 2 : cap - cap / 4) * n_tiles) / (num_hashes ? num_hashes : 1u));
+    if (kb > TILE_BIN_WPI * waves * 64u) kb = TILE_BIN_WPI * waves * 64u;
+    if (counts && kb > (1u << ROUND_KMERS_LOG2)) kb = 1u << ROUND_KMERS_LOG2;
+    return kb ? kb : 1u;
+}
 // Reads that pass several related leaves (a phage database is full of strains): BLOCK MODE.  A pair is (read, block of 8
 // consecutive leaf columns, mask of the candidate leaves in it); the block's "filter" is a byte per Bloom bit index — bit j =
 // that bit of leaf 8b + j — so ONE entry tests a probe for all candidate leaves of the block: a read that passes 8 strains
@@ -268,7 +293,16 @@ struct TileArgs {
     const uint32_t *tile_lists;     // [row][n_tiles][TILE_LIST_CAP]
     unsigned long long *tile_list_stats;  // [0] += tiles built from slots, [1] += tiles loaded dense (k_tile_test<0>)
     uint32_t tile_stream;           // 1: EVERY column has slots (tile_list_row[c] == c for all columns): the slots-only build runs
+    // packed entries (threshold 1 outside block mode, see PACK_PAIRS)
+    uint32_t entry_pack;            // 1: five 24-bit entries and the round's number per 16-byte vector; n_rounds is written too
+    uint32_t *round_p0;             // [max_chunks][PACK_ROUNDS] first pair (in the chunk) of every round
+    uint8_t *round_fail;            // [max_chunks][PACK_ROUNDS][PACK_PAIRS] 1: a probed bit of that pair of the round was 0 (cleared
+                                    // by k_tile_bin with the round, set by k_tile_test with plain stores, read by k_pack_fail)
 };
+// after the last pass of a call with packed entries: the failures k_tile_test left in round_fail become fail words
+void launch_pack_fail(const TileArgs &a, hipStream_t st);
+// the build of k_tile_bin that launch_tile_bin launches for these arguments: BIN_WAVES << 16 | BIN_CAP
+uint32_t tile_bin_build(const TileArgs &a);
 // Position slots (pfq_tilelist.hip): a column whose filter has at most TILE_LIST_CAP set bits in every 2^TILE_LOG2-bit tile
 // keeps, per tile, the tile-relative positions of the set bits in any order, the unused entries TILE_LIST_NONE — 32 KiB
 // in the place of the tile's 128 KiB.  The cap is what 1024 threads hold as two 16-byte loads each.

@@ -2221,8 +2221,13 @@ __device__ __forceinline__ void flag_fallback(const TileArgs &a, uint32_t e) {
 // MODE 0: (pair, offset) entries, 128 KiB tiles.  MODE 1 (thresholds < 1): k-mer entries.  MODE 2 (block mode): entries
 // [pair:10][byte offset:17] against the byte-per-index table of a block of 8 leaves (the candidate mask comes with the chunk).
 // MODE 3 (block mode at thresholds < 1): k-mer entries against that table.
-template <uint32_t BIN_WAVES, uint32_t BIN_CAP, uint32_t MODE>
+// PACK (MODE 0 only): the flush writes five 24-bit entries [pair of the round:4][offset:20] and the round's number (8 bits)
+// per 16-byte vector instead of four 32-bit entries; a round then takes at most PACK_PAIRS pairs, round_p0[chunk][round] keeps
+// its first pair, and runs are padded to a whole vector with copies of their last entry.  The LDS bins keep 32-bit entries;
+// fill marks and capacities stay in 32-bit words (a run of cc entries takes 4 * ceil(cc / 5) of them).
+template <uint32_t BIN_WAVES, uint32_t BIN_CAP, uint32_t MODE, bool PACK = false>
 __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
+    static_assert(!PACK || MODE == 0, "packed entries are a format of MODE 0");
     constexpr bool COUNTS = MODE == 1 || MODE == 3, BLK = MODE == 2;  // (MODE 3: k-mer entries against block tables, no prefix)
     // COUNTS (thresholds < 1): an entry is [round tag:2][flattened k-mer of the round:11][offset in a 64 KiB tile:19]; the
     // tags are ORed in at flush time (position in the 16-byte vector -> two bits of the round's number), runs are padded
@@ -2241,10 +2246,8 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
     const uint32_t n_chunks = *a.n_chunks < a.max_chunks ? *a.n_chunks : a.max_chunks;
     // k-mers per round: the bins fill to 3/4 on average (shallow bins of many tiles — block mode — to 1/2: an overflow costs
     // the round's pairs the fallback, and 30 +- 5.5 entries must stay below 60)
-    uint32_t KB = (uint32_t)(((uint64_t)(BIN_CAP < 128 ? BIN_CAP / 2 : BIN_CAP - BIN_CAP / 4) * a.n_tiles) / nh);
-    if (KB > WPI * BIN_WAVES * WIN_KMERS) KB = WPI * BIN_WAVES * WIN_KMERS;
-    if (COUNTS && KB > (1u << ROUND_KMERS_LOG2)) KB = 1u << ROUND_KMERS_LOG2;
-    if (KB == 0) KB = 1;
+    const uint32_t KB = tile_bin_kmer_budget(BIN_WAVES, BIN_CAP, a.n_tiles, nh, COUNTS);
+    static_assert(WPI == TILE_BIN_WPI, "tile_bin_kmer_budget counts WPI windows a wave");
     for (uint32_t t = threadIdx.x; t < NT + 64; t += blockDim.x) cnt[t] = 0;
     while (true) {
         __syncthreads();  // everybody is done with the previous chunk
@@ -2277,7 +2280,7 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
             Round r;
             r.p = p;
             r.koff = koff;
-            const bool cand = lane < ROUND_PAIRS && p + lane < dsc.n;
+            const bool cand = lane < (PACK ? PACK_PAIRS : ROUND_PAIRS) && p + lane < dsc.n;
             // (k-mer entries: only the prefix of the read's k-mers that decides nearly every pair, see prefix_kmers)
             const uint32_t n_all = cand ? m.z - k + 1u : 0u, n_bin = (MODE == 1 && cand) ? prefix_kmers(a.threshold, n_all, k) : n_all;
             const unsigned long long n64 = cand ? (unsigned long long)n_bin - (lane == 0 ? koff : 0ull) : 0ull;
@@ -2366,6 +2369,17 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
                 // (a pair binned over several rounds keeps the position of its first piece; the pieces are contiguous)
                 if (wave == 0 && lane < cur.P && (lane > 0 || cur.koff == 0)) a.pair_kpos[dsc.first + cur.p + lane] = k0 + (cur.partial ? 0u : cur.start);
             }
+            if (PACK) {
+                if (rho >= PACK_ROUNDS) {  // the tag cannot name more rounds: what is left of the chunk takes the fallback
+                    for (uint32_t i = cur.p + threadIdx.x; i < dsc.n; i += blockDim.x) flag_fallback(a, dsc.first + i);
+                    break;
+                }
+                if (threadIdx.x == 0) {  // the round's first pair; its pairs' failure bytes cleared (k_tile_test sets them)
+                    a.round_p0[(uint64_t)c * PACK_ROUNDS + rho] = cur.p;
+                    static_assert(PACK_PAIRS == 16, "a round's failure bytes are one 16-byte store");
+                    *reinterpret_cast<uint4 *>(a.round_fail + ((uint64_t)c * PACK_ROUNDS + rho) * PACK_PAIRS) = make_uint4(0, 0, 0, 0);
+                }
+            }
             const uint32_t p1 = cur.partial ? cur.p : cur.p + cur.P;
             const Round nxt = compose(p1, cur.partial ? cur.koff + KBc : 0ull, m_nxt);
             uint4 rec_n[WPI];
@@ -2441,41 +2455,84 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
                 const uint32_t t = t0 + lane / LPT, sl = lane % LPT;
                 const bool have = t < a.n_tiles;
                 const uint32_t cn = have ? cnt[t] : 0u, pos = have ? fillp[t] : 0u;
-                const uint32_t cc = cn < BIN_CAP ? cn : BIN_CAP, c4 = (cc + 3u) & ~3u;
+                const uint32_t cc = cn < BIN_CAP ? cn : BIN_CAP;
                 uint32_t *row = bins + t * BIN_STRIDE;
-                if (sl < c4 - cc) row[cc + sl] = COUNTS ? row[cc - 1u] : ENTRY_PAD;  // (c4 > cc only when cc >= 1)
-                __builtin_amdgcn_wave_barrier();
-                // what fits is written (k_tile_test reads min(fill, cap) entries: every slot below cap must hold an entry
-                // or padding); the pairs whose probes are dropped — bucket full — take the fallback
-                const uint32_t room = pos < dsc.cap ? dsc.cap - pos : 0u, wr = c4 < room ? c4 : room;
-                uint32_t *dst = bucket0 + (uint64_t)(have ? t : 0u) * dsc.cap + pos;
-                constexpr uint32_t FB = BIN_CAP < 128 ? 2 : 5;  // 16-byte reads in flight per lane: two batches cover a full bin (516 entries / 64)
-                const uint32_t wr_eff = (PFQ_DEBUG_BITS(a) & 1u) ? 0u : wr;
-                for (uint32_t i0 = sl * 4u; i0 < wr; i0 += STEP * FB) {
-                    uint4 v[FB];
+                // words of the run in its bucket: four entries to a vector, five with PACK
+                const uint32_t c4 = PACK ? ((cc + 4u) / 5u) * 4u : (cc + 3u) & ~3u;
+                if constexpr (PACK) {
+                    const uint32_t nv = c4 >> 2;
+                    if (sl < nv * 5u - cc) row[cc + sl] = row[cc - 1u];  // (at most 4 <= LPT copies, and only when cc >= 1)
+                    __builtin_amdgcn_wave_barrier();
+                    // (a bucket takes the entries it took as 32-bit words: what overflows does not depend on the format)
+                    const uint32_t capw = pack_bucket_words(dsc.cap);
+                    const uint32_t room = pos < capw ? capw - pos : 0u, wr = c4 < room ? c4 : room;  // (words: multiples of 4)
+                    const uint32_t wrv = wr >> 2, wr_ent = wrv * 5u < cc ? wrv * 5u : cc;  // vectors written, entries in them
+                    uint32_t *dst = bucket0 + (uint64_t)(have ? t : 0u) * dsc.cap + pos;
+                    constexpr uint32_t FB = BIN_CAP < 128 ? 2 : 5;       // vectors in flight per lane
+                    constexpr uint32_t VMAX = (BIN_STRIDE - 5u) / 5u;  // last vector whose five entries lie inside the row
+                    static_assert(BIN_STRIDE >= 5u * ((BIN_CAP + 4u) / 5u), "the padding of a full bin fits its row");
+                    const uint32_t wrv_eff = (PFQ_DEBUG_BITS(a) & 1u) ? 0u : wrv;
+                    const uint32_t sub = flush_p << TL, tag = (rho & (PACK_ROUNDS - 1u)) << 24;
+                    for (uint32_t v0 = sl; v0 < wrv; v0 += LPT * FB) {
+                        uint32_t e[FB][5];
 #pragma unroll
-                    for (uint32_t u = 0; u < FB; ++u)  // (unconditional, clamped into the row: nothing waits for a branch)
-                        v[u] = *reinterpret_cast<const uint4 *>(row + min(i0 + u * STEP, BIN_STRIDE - 4u));
+                        for (uint32_t u = 0; u < FB; ++u) {  // (unconditional, clamped into the row: nothing waits for a branch)
+                            const uint32_t *src = row + 5u * min(v0 + u * LPT, VMAX);
 #pragma unroll
-                    for (uint32_t u = 0; u < FB; ++u)  // (keeps the compiler from sinking every read next to its store)
-                        asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w));
-                    if (COUNTS) {  // the round's number, two bits per entry of a vector
+                            for (uint32_t j = 0; j < 5; ++j) e[u][j] = src[j];
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < FB; ++u)  // (keeps the compiler from sinking every read next to its store)
+                            asm volatile("" : "+v"(e[u][0]), "+v"(e[u][1]), "+v"(e[u][2]), "+v"(e[u][3]), "+v"(e[u][4]));
 #pragma unroll
                         for (uint32_t u = 0; u < FB; ++u) {
-                            v[u].x |= (rho & 3u) << 30;
-                            v[u].y |= ((rho >> 2) & 3u) << 30;
-                            v[u].z |= ((rho >> 4) & 3u) << 30;
-                            v[u].w |= ((rho >> 6) & 3u) << 30;
+                            if (v0 + u * LPT >= wrv_eff) continue;
+                            // the pair becomes its number in the round (0 for the one pair of a partial round): 24 bits
+                            const uint32_t e0 = (e[u][0] - sub) & 0xffffffu, e1 = (e[u][1] - sub) & 0xffffffu, e2 = (e[u][2] - sub) & 0xffffffu,
+                                           e3 = (e[u][3] - sub) & 0xffffffu, e4 = (e[u][4] - sub) & 0xffffffu;
+                            *reinterpret_cast<uint4 *>(dst + 4u * (v0 + u * LPT)) =
+                                make_uint4(e0 | (e1 << 24), (e1 >> 8) | (e2 << 16), (e2 >> 16) | (e3 << 8), e4 | tag);
                         }
                     }
+                    if (!(PFQ_DEBUG_BITS(a) & 16u))
+                        for (uint32_t i = wr_ent + sl; i < cc; i += LPT) flag_fallback(a, dsc.first + (row[i] >> TL));
+                    if (cn > BIN_CAP)  // the LDS bin overflowed: whose probes were lost is unknown
+                        for (uint32_t i = sl; i < flush_P; i += LPT) flag_fallback(a, dsc.first + flush_p + i);
+                } else {
+                    if (sl < c4 - cc) row[cc + sl] = COUNTS ? row[cc - 1u] : ENTRY_PAD;  // (c4 > cc only when cc >= 1)
+                    __builtin_amdgcn_wave_barrier();
+                    // what fits is written (k_tile_test reads min(fill, cap) entries: every slot below cap must hold an entry
+                    // or padding); the pairs whose probes are dropped — bucket full — take the fallback
+                    const uint32_t room = pos < dsc.cap ? dsc.cap - pos : 0u, wr = c4 < room ? c4 : room;
+                    uint32_t *dst = bucket0 + (uint64_t)(have ? t : 0u) * dsc.cap + pos;
+                    constexpr uint32_t FB = BIN_CAP < 128 ? 2 : 5;  // 16-byte reads in flight per lane: two batches cover a full bin (516 entries / 64)
+                    const uint32_t wr_eff = (PFQ_DEBUG_BITS(a) & 1u) ? 0u : wr;
+                    for (uint32_t i0 = sl * 4u; i0 < wr; i0 += STEP * FB) {
+                        uint4 v[FB];
 #pragma unroll
-                    for (uint32_t u = 0; u < FB; ++u)
-                        if (i0 + u * STEP < wr_eff) *reinterpret_cast<uint4 *>(dst + i0 + u * STEP) = v[u];
-                }
-                if (!COUNTS && !(PFQ_DEBUG_BITS(a) & 16u))
-                    for (uint32_t i = wr + sl; i < cc; i += LPT) flag_fallback(a, dsc.first + (row[i] >> TL));
-                if (!BLK && (cn > BIN_CAP || (COUNTS && wr < cc))) {  // the LDS bin (or, with k-mer entries, the bucket) overflowed: whose probes were lost is unknown
-                    for (uint32_t i = sl; i < flush_P; i += LPT) flag_fallback(a, dsc.first + flush_p + i);
+                        for (uint32_t u = 0; u < FB; ++u)  // (unconditional, clamped into the row: nothing waits for a branch)
+                            v[u] = *reinterpret_cast<const uint4 *>(row + min(i0 + u * STEP, BIN_STRIDE - 4u));
+#pragma unroll
+                        for (uint32_t u = 0; u < FB; ++u)  // (keeps the compiler from sinking every read next to its store)
+                            asm volatile("" : "+v"(v[u].x), "+v"(v[u].y), "+v"(v[u].z), "+v"(v[u].w));
+                        if (COUNTS) {  // the round's number, two bits per entry of a vector
+#pragma unroll
+                            for (uint32_t u = 0; u < FB; ++u) {
+                                v[u].x |= (rho & 3u) << 30;
+                                v[u].y |= ((rho >> 2) & 3u) << 30;
+                                v[u].z |= ((rho >> 4) & 3u) << 30;
+                                v[u].w |= ((rho >> 6) & 3u) << 30;
+                            }
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < FB; ++u)
+                            if (i0 + u * STEP < wr_eff) *reinterpret_cast<uint4 *>(dst + i0 + u * STEP) = v[u];
+                    }
+                    if (!COUNTS && !(PFQ_DEBUG_BITS(a) & 16u))
+                        for (uint32_t i = wr + sl; i < cc; i += LPT) flag_fallback(a, dsc.first + (row[i] >> TL));
+                    if (!BLK && (cn > BIN_CAP || (COUNTS && wr < cc))) {  // the LDS bin (or, with k-mer entries, the bucket) overflowed: whose probes were lost is unknown
+                        for (uint32_t i = sl; i < flush_P; i += LPT) flag_fallback(a, dsc.first + flush_p + i);
+                    }
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (have && sl == 0 && cn) {
@@ -2487,7 +2544,7 @@ __global__ void __launch_bounds__(BIN_WAVES * 64) k_tile_bin(TileArgs a) {
             k0 += flush_K;
             ++rho;
         }
-        if (COUNTS && threadIdx.x == 0) a.n_rounds[c] = rho;
+        if ((COUNTS || PACK) && threadIdx.x == 0) a.n_rounds[c] = rho;
         for (uint32_t t = threadIdx.x; t < a.n_tiles; t += blockDim.x) a.gfill[(uint64_t)c * a.n_tiles + t] = fillp[t];
     }
 }
@@ -2506,37 +2563,41 @@ static void launch_tile_bin_shape(const TileArgs &a, int blocks, size_t lds, hip
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_bin<W, CAP, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_bin<W, CAP, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_bin<W, CAP, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_bin<W, CAP, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     }
     if (a.counts && a.blocks) hipLaunchKernelGGL((k_tile_bin<W, CAP, 3>), dim3(blocks), dim3(W * 64), lds, st, a);
     else if (a.counts) hipLaunchKernelGGL((k_tile_bin<W, CAP, 1>), dim3(blocks), dim3(W * 64), lds, st, a);
     else if (a.blocks) hipLaunchKernelGGL((k_tile_bin<W, CAP, 2>), dim3(blocks), dim3(W * 64), lds, st, a);
+    else if (a.entry_pack) hipLaunchKernelGGL((k_tile_bin<W, CAP, 0, true>), dim3(blocks), dim3(W * 64), lds, st, a);
     else hipLaunchKernelGGL((k_tile_bin<W, CAP, 0>), dim3(blocks), dim3(W * 64), lds, st, a);
 }
-uint32_t launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st) {
+static size_t tile_bin_lds(const TileArgs &a, size_t cap) {
     const size_t nt = (a.n_tiles + 63u) & ~63u;
-    auto lds_of = [&](size_t cap) { return (2 * nt + 64 + (size_t)a.n_tiles * (cap + 4)) * 4; };
-    if (a.bin_shape == 3 && lds_of(256) <= 74 * 1024) {  // experiment: two 8-wave blocks per CU
-        launch_tile_bin_shape<8, 256>(a, blocks, lds_of(256), st);
-        return 8u << 16 | 256u;
-    } else if (lds_of(2048) <= 148 * 1024 && a.bin_shape == 0) {  // few tiles (small filters): deeper bins, longer rounds
-        launch_tile_bin_shape<16, 2048>(a, (blocks + 1) / 2, lds_of(2048), st);
-        return 16u << 16 | 2048u;
-    } else if (lds_of(1024) <= 148 * 1024 && a.bin_shape == 0) {
-        launch_tile_bin_shape<16, 1024>(a, (blocks + 1) / 2, lds_of(1024), st);
-        return 16u << 16 | 1024u;
-    } else if (lds_of(512) <= 148 * 1024 && a.bin_shape == 0) {
-        launch_tile_bin_shape<16, 512>(a, (blocks + 1) / 2, lds_of(512), st);
-        return 16u << 16 | 512u;
-    } else if (lds_of(256) <= 148 * 1024 && a.bin_shape != 1) {
-        launch_tile_bin_shape<16, 256>(a, (blocks + 1) / 2, lds_of(256), st);
-        return 16u << 16 | 256u;
-    } else if (lds_of(128) <= 148 * 1024) {
-        launch_tile_bin_shape<8, 128>(a, blocks, lds_of(128), st);
-        return 8u << 16 | 128u;
-    } else {  // several hundred tiles (block mode of large filters): shallow bins
-        launch_tile_bin_shape<16, 60>(a, (blocks + 1) / 2, lds_of(60), st);
-        return 16u << 16 | 60u;
+    return (2 * nt + 64 + (size_t)a.n_tiles * (cap + 4)) * 4;
+}
+uint32_t tile_bin_build(const TileArgs &a) {
+    auto lds_of = [&](size_t cap) { return tile_bin_lds(a, cap); };
+    if (a.bin_shape == 3 && lds_of(256) <= 74 * 1024) return 8u << 16 | 256u;   // experiment: two 8-wave blocks per CU
+    if (lds_of(2048) <= 148 * 1024 && a.bin_shape == 0) return 16u << 16 | 2048u;  // few tiles (small filters): deeper bins, longer rounds
+    if (lds_of(1024) <= 148 * 1024 && a.bin_shape == 0) return 16u << 16 | 1024u;
+    if (lds_of(512) <= 148 * 1024 && a.bin_shape == 0) return 16u << 16 | 512u;
+    if (lds_of(256) <= 148 * 1024 && a.bin_shape != 1) return 16u << 16 | 256u;
+    if (lds_of(128) <= 148 * 1024) return 8u << 16 | 128u;
+    return 16u << 16 | 60u;  // several hundred tiles (block mode of large filters): shallow bins
+}
+uint32_t launch_tile_bin(const TileArgs &a, int blocks, hipStream_t st) {
+    const uint32_t build = tile_bin_build(a);
+    const size_t lds = tile_bin_lds(a, build & 0xffffu);
+    switch (build) {
+    case 8u << 16 | 256u: launch_tile_bin_shape<8, 256>(a, blocks, lds, st); break;
+    case 16u << 16 | 2048u: launch_tile_bin_shape<16, 2048>(a, (blocks + 1) / 2, lds, st); break;
+    case 16u << 16 | 1024u: launch_tile_bin_shape<16, 1024>(a, (blocks + 1) / 2, lds, st); break;
+    case 16u << 16 | 512u: launch_tile_bin_shape<16, 512>(a, (blocks + 1) / 2, lds, st); break;
+    case 16u << 16 | 256u: launch_tile_bin_shape<16, 256>(a, (blocks + 1) / 2, lds, st); break;
+    case 8u << 16 | 128u: launch_tile_bin_shape<8, 128>(a, blocks, lds, st); break;
+    default: launch_tile_bin_shape<16, 60>(a, (blocks + 1) / 2, lds, st); break;
     }
+    return build;
 }
 
 constexpr uint32_t TEST_LOADS = 4;   // 16-byte entry loads in flight per thread (8 measured slower: 6.1 vs 5.9 ms)
@@ -2555,8 +2616,13 @@ constexpr uint32_t TEST_GROUP = 32;  // chunks of a leaf whose buckets are strea
 // DEPTH > 0 (MODE 0 only): the slots-only build, launched when every column of the tree has position slots.  No dense tile
 // exists in it, and the registers that would hold one carry a rotating pipeline of DEPTH entry steps per thread instead
 // (see the end of the kernel).  CARRY: the pipeline stays filled across the switch from one unit to the next.
-template <uint32_t MODE, uint32_t DEPTH = 0, bool CARRY = false>
+// PACK (MODE 0 only): the buckets hold packed entries (PACK_PAIRS, pfq_kernels.h): five bit tests per 16-byte load.  An entry
+// names its pair only within its round, so the bitmap of reported failures is keyed by (bucket, round, pair of the round) —
+// repeats are dropped without knowing the pair — and the first failure of a key sets the byte round_fail[chunk][round][id]
+// with a plain store; k_pack_fail turns those bytes into fail words after the passes.
+template <uint32_t MODE, uint32_t DEPTH = 0, bool CARRY = false, bool PACK = false>
 __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
+    static_assert(!PACK || MODE == 0, "packed entries are a format of MODE 0");
     // MODE 3 (block mode at thresholds < 1): k-mer entries against the block's byte table; the candidate mask comes with the
     // chunk (buckets are keyed by (block, mask)); a candidate whose bit is 0 gets the k-mer's miss byte of that leaf set.
     constexpr bool SLOTS = DEPTH != 0;
@@ -2576,8 +2642,21 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
     const uint32_t n_cols = a.n_leaves;
     auto col_of = [&](uint32_t li) { return li; };
     // failures this block already reported: a bit per pair of the group (MODE 0), per (pair, leaf of the block) (MODE 2)
-    __shared__ uint32_t s_failed[COUNTS ? 1 : (BLK ? (TG << (CL - 2)) : (TG << (CL - 5)))];
-    constexpr uint32_t N_FAILED = COUNTS ? 0 : (BLK ? (TG << (CL - 2)) : (TG << (CL - 5)));
+    // (PACK: a bit per (bucket, round, pair of the round): TG x 256 x 16 bits = 16 KiB)
+    constexpr uint32_t PACK_KEY_LOG2 = 12;
+    static_assert(PACK_ROUNDS * PACK_PAIRS == 1u << PACK_KEY_LOG2, "a key of the packed build is (round : 8, pair of the round : 4)");
+    constexpr uint32_t N_FAILED = COUNTS ? 0 : (BLK ? (TG << (CL - 2)) : (PACK ? (TG << (PACK_KEY_LOG2 - 5)) : (TG << (CL - 5))));
+    __shared__ uint32_t s_failed[COUNTS ? 1 : N_FAILED];
+    // PACK: a probed bit of entry `e` (24 bits) of a vector with tag `rho` in bucket b of descriptor set `set` was 0
+    auto report_packed = [&](uint32_t set, uint32_t b, uint32_t rho, uint32_t e) {
+        const uint32_t id = e >> TL, fb = (b << PACK_KEY_LOG2) | (rho << 4) | id;
+        // A plain byte store, idempotent, nothing comes back.  (Tried first: a load of round_p0 here and the atomicOr on the
+        // pair's fail word — the loaded value is its address, so every first failure waited vmcnt(0), for the thread's entry
+        // loads in flight too: 1 % read errors 4.9 -> 8.1 ms; then an atomicOr of a bit per id into the round's word: the
+        // sixteen pairs of a round and all tiles meet in one word, 12.9 ms.)
+        if (!(atomicOr(&s_failed[fb >> 5], 1u << (fb & 31u)) & (1u << (fb & 31u))))
+            a.round_fail[((uint64_t)(s_misc[set][1] + b) * PACK_ROUNDS + rho) * PACK_PAIRS + id] = 1;
+    };
     __shared__ uint32_t s_rk0[COUNTS ? TG : 1][RK];                               // round_k0 rows of the group's chunks
     __shared__ unsigned long long s_base[NSET][TG];
     const uint32_t tile_words = TILE_BYTES / 4u;
@@ -2603,7 +2682,8 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         const bool mine = i < TG && c < n_chunks && (dsc = a.chunks[c], dsc.leaf == leaf);
         const bool usable = mine && dsc.cap != 0 && dsc.pass == a.pass;
         uint32_t fill = usable ? a.gfill[(uint64_t)c * a.n_tiles + t] : 0u;
-        if (fill > dsc.cap) fill = dsc.cap;
+        const uint32_t capw = PACK ? pack_bucket_words(dsc.cap) : dsc.cap;
+        if (fill > capw) fill = capw;
         uint32_t incl = fill;
         for (uint32_t sft = 1; sft < TG; sft <<= 1) {
             const uint32_t o = (uint32_t)__shfl_up((int)incl, (int)sft);
@@ -2620,6 +2700,7 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
         if (i == 0) {
             s_pref[buf][0] = 0;
             s_misc[buf][0] = (uint32_t)__popcll(mm);  // chunks of the column in this group
+            s_misc[buf][1] = g0;                      // chunk of the group's first bucket
         }
     };
     // the column's tile: words [t * tile_words, ...) of its filter row (zero beyond the filter's end); filter rows are only
@@ -2782,6 +2863,15 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
                             }
                         }
                     }
+                } else if (PACK) {
+                    if (!have[u]) continue;
+                    const uint32_t e5[5] = {ev[0] & 0xffffffu, (ev[0] >> 24) | ((ev[1] & 0xffffu) << 8), (ev[1] >> 16) | ((ev[2] & 0xffu) << 16), ev[2] >> 8,
+                                            ev[3] & 0xffffffu};
+#pragma unroll
+                    for (uint32_t c = 0; c < 5; ++c) {
+                        const uint32_t off = e5[c] & ((1u << TL) - 1u);
+                        if (!((s_tile[off >> 5] >> (off & 31u)) & 1u)) report_packed(buf, cidx[u] >> CL, ev[3] >> 24, e5[c]);
+                    }
                 } else {
 #pragma unroll
                     for (uint32_t c = 0; c < 4; ++c) {
@@ -2839,6 +2929,16 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
                 const uint32_t w = pk[j] >> (8u * u);
                 if (!(w & 0x80u)) continue;
                 const uint32_t ev[4] = {en[j][u].x, en[j][u].y, en[j][u].z, en[j][u].w};
+                if constexpr (PACK) {
+                    const uint32_t e5[5] = {ev[0] & 0xffffffu, (ev[0] >> 24) | ((ev[1] & 0xffffu) << 8), (ev[1] >> 16) | ((ev[2] & 0xffu) << 16), ev[2] >> 8,
+                                            ev[3] & 0xffffffu};
+#pragma unroll
+                    for (uint32_t c = 0; c < 5; ++c) {
+                        const uint32_t off = e5[c] & ((1u << TL) - 1u);
+                        if (!((s_tile[off >> 5] >> (off & 31u)) & 1u)) report_packed(set, w & 31u, ev[3] >> 24, e5[c]);  // (as in stream())
+                    }
+                    continue;
+                }
 #pragma unroll
                 for (uint32_t c = 0; c < 4; ++c) {
                     const uint32_t off = ev[c] & ((1u << TL) - 1u);
@@ -2874,12 +2974,13 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
             d.fill = a.gfill[(uint64_t)c * a.n_tiles + t];
             return d;
         };
-        auto describe_put = [&](uint32_t set, uint32_t leaf, uint32_t t, const Described &d) {
+        auto describe_put = [&](uint32_t set, uint32_t leaf, uint32_t t, uint32_t g, const Described &d) {
             const uint32_t i = threadIdx.x;
             const bool mine = d.in && d.leaf == leaf;
             const bool usable = mine && d.cap != 0 && d.pass == a.pass;
             uint32_t fill = usable ? d.fill : 0u;
-            if (fill > d.cap) fill = d.cap;
+            const uint32_t capw = PACK ? pack_bucket_words(d.cap) : d.cap;
+            if (fill > capw) fill = capw;
             uint32_t incl = fill;
             for (uint32_t sft = 1; sft < TG; sft <<= 1) {
                 const uint32_t o = (uint32_t)__shfl_up((int)incl, (int)sft);
@@ -2898,6 +2999,7 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
             if (i == 0) {
                 s_pref[set][0] = 0;
                 s_misc[set][0] = (uint32_t)__popcll(mm);
+                s_misc[set][1] = g;
             }
         };
         // the unit after (task, g): the column's next group if this one was full, else the first group of the block's next task
@@ -2918,12 +3020,12 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
             uint2 v[TV];
             list_loads(leaf_of(task0), tile_of(task0), v);  // (every column has slots: a column's row of slots is its own number)
             const Described d = describe_loads(tile_of(task0), g0);
-            if (threadIdx.x < 64) describe_put(d0, leaf_of(task0), tile_of(task0), d);
+            if (threadIdx.x < 64) describe_put(d0, leaf_of(task0), tile_of(task0), g0, d);
             list_store(v);  // (the block's first task: zeros are stored, once)
             __syncthreads();
             have1 = unit_after(task0, g0, s_misc[d0][0] == TG, task1, g1);
             const Described d1st = describe_loads(have1 ? tile_of(task1) : 0u, have1 ? g1 : 0u);
-            if (have1 && threadIdx.x < 64) describe_put(d1, leaf_of(task1), tile_of(task1), d1st);
+            if (have1 && threadIdx.x < 64) describe_put(d1, leaf_of(task1), tile_of(task1), g1, d1st);
             __syncthreads();
         }
         uint32_t total0 = s_pref[d0][TG];
@@ -2946,7 +3048,7 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
                     issue(j, last ? d1 : d0, last ? j : s + DEPTH + j, last ? total1 : total0);
                 }
             }
-            if (have2 && threadIdx.x < 64) describe_put(d2, leaf_of(task2), tile_of(task2), dn);
+            if (have2 && threadIdx.x < 64) describe_put(d2, leaf_of(task2), tile_of(task2), g2, dn);
             __syncthreads();  // everybody is done with this unit's tile and descriptors; those of the unit after the next are written
             if (!have1) break;
             if (tile1) list_store(vn);  // (clears the bitmap of reported failures)
@@ -3039,9 +3141,13 @@ __global__ void __launch_bounds__(1024) k_tile_test(TileArgs a) {
 void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st) {
     static std::atomic<uint64_t> attr_done{0};
     const auto k_stream = k_tile_test<0, PFQ_STREAM_DEPTH, PFQ_STREAM_CARRY != 0>;
+    const auto k_packed = k_tile_test<0, 0, false, true>, k_stream_packed = k_tile_test<0, PFQ_STREAM_DEPTH, PFQ_STREAM_CARRY != 0, true>;
     if (first_on_device(attr_done)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stream), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        // (static LDS of the packed builds: 16 KiB of reported-failure bits and the descriptor sets, beside the 128 KiB tile)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_packed), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << (TILE_LOG2 - 3));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stream_packed), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << (TILE_LOG2 - 3));
         // (static LDS of the k-mer-entry build: the 32 KiB of round_k0 rows; static + dynamic must stay within the CU's 160 KiB)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << (TILE_LOG2_COUNTS - 3));
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tile_test<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << TILE_LOG2_BLOCK);
@@ -3051,8 +3157,29 @@ void launch_tile_test(const TileArgs &a, int blocks, hipStream_t st) {
     if (a.counts && a.blocks) hipLaunchKernelGGL(k_tile_test<3>, g, b, (size_t)(1u << TILE_LOG2_BLOCK), st, a);
     else if (a.counts) hipLaunchKernelGGL(k_tile_test<1>, g, b, (size_t)(1u << (TILE_LOG2_COUNTS - 3)), st, a);
     else if (a.blocks) hipLaunchKernelGGL(k_tile_test<2>, g, b, (size_t)(1u << TILE_LOG2_BLOCK), st, a);
-    else if (a.tile_stream && a.tile_list_row && a.tile_lists) hipLaunchKernelGGL(k_stream, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
+    else if (a.tile_stream && a.tile_list_row && a.tile_lists)
+        hipLaunchKernelGGL(a.entry_pack ? k_stream_packed : k_stream, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
+    else if (a.entry_pack) hipLaunchKernelGGL(k_packed, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
     else hipLaunchKernelGGL(k_tile_test<0>, g, b, (size_t)(1u << (TILE_LOG2 - 3)), st, a);
+}
+
+// Packed entries, after the passes: k_tile_test left the failures of a round as bytes round_fail[chunk][round][pair of the
+// round]; here they become bit 0 of the pairs' fail words.  A thread per round, a block per chunk (n_rounds is cleared with
+// the call: a chunk no launched pass binned has none).
+__global__ void __launch_bounds__(PACK_ROUNDS) k_pack_fail(TileArgs a) {
+    const uint32_t n_chunks = *a.n_chunks < a.max_chunks ? *a.n_chunks : a.max_chunks;
+    for (uint32_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        if (threadIdx.x >= a.n_rounds[c]) continue;  // (n_rounds <= PACK_ROUNDS = the block's threads)
+        const uint64_t r = (uint64_t)c * PACK_ROUNDS + threadIdx.x;
+        const uint4 f = *reinterpret_cast<const uint4 *>(a.round_fail + r * PACK_PAIRS);
+        if (!(f.x | f.y | f.z | f.w)) continue;
+        const uint32_t at = a.chunks[c].first + a.round_p0[r], w[4] = {f.x, f.y, f.z, f.w};
+        for (uint32_t id = 0; id < PACK_PAIRS; ++id)  // (a pair binned over several rounds is reported by each of them: atomics)
+            if ((w[id >> 2] >> (8u * (id & 3u))) & 0xffu) atomicOr(&a.fail[at + id], 1u);
+    }
+}
+void launch_pack_fail(const TileArgs &a, hipStream_t st) {
+    if (a.entry_pack) hipLaunchKernelGGL(k_pack_fail, dim3(1024), dim3(PACK_ROUNDS), 0, st, a);
 }
 
 // Thresholds < 1 after the tile passes: the compact list of the pairs whose fail word is non-zero (a probe found 0, or the

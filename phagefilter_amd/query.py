@@ -219,6 +219,20 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_tile_list(self._h, col, tile, out.ctypes.data, out.size))
         return out
 
+    TILE_BUCKET_WORDS = 1296
+
+    def tile_bucket(self, chunk: int, tile: int, max_words: int = 1 << 20) -> dict:
+        """One probe bucket of the last call's LDS-tile passes at theta = 1 (pfq_debug_tile_bucket): the fill mark and
+        capacity in 32-bit words, the chunk's `first` pair, pair count `n`, column `leaf` and `pass`, whether the entries are
+        `packed`, the call's `n_chunks`, with packed entries the chunk's `n_rounds` and the first pair of each (`round_p0`),
+        the read of each of the chunk's pairs (`reads`) and the bucket's `words`."""
+        out = np.zeros(self.TILE_BUCKET_WORDS + max_words, dtype=np.uint32)
+        _ffi.check(_ffi.lib().pfq_debug_tile_bucket(self._h, chunk, tile, out.ctypes.data, out.size))
+        fill, cap, first, n, leaf, pas, packed, n_chunks, n_rounds = (int(v) for v in out[:9])
+        return dict(fill=fill, cap=cap, first=first, n=n, leaf=leaf, **{"pass": pas}, packed=bool(packed), n_chunks=n_chunks, n_rounds=n_rounds,
+                    round_p0=out[16:16 + n_rounds].astype(np.int64), reads=out[272:272 + n].astype(np.int64),
+                    words=out[self.TILE_BUCKET_WORDS:self.TILE_BUCKET_WORDS + min(fill, cap, max_words)].copy())
+
     def profile_begin(self, max_calls: int) -> None:
         _ffi.check(_ffi.lib().pfq_profile_begin(self._h, max_calls))
 
