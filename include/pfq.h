@@ -570,6 +570,57 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
 int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits);
 int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /* tests: the parsed CSR copied to the host */
 
+/* ---- text output (pfq_text_format) ----
+ * The POS / NEG records of a device-parsed block formatted on the device, at the seam of the reference's writer
+ * (main.rs:345-361,394-404): the bytes `query --pos-filter / --neg-filter` writes, made from the text, the gathered sequences
+ * and the hit rows where pfq_text_parse and pfq_text_query left them.
+ * Inputs: the block of n records is the one the last pfq_text_parse on the tree took; row H(r) is what the last pfq_text_query of
+ * that block gave for record r (the final CSR, after any overflow retry).  Record r has the global index first_index + r and
+ * lies in result block (first_index + r) / block.
+ * The reference decides POS / NEG per result block, through a map id -> genomes (result_map.rs:20-45): two records of a block
+ * with the same id merge their genomes, and a record without a hit is still mapped if its id is in the map.  In a block whose
+ * ids are pairwise different neither can happen, so the device formats exactly those blocks and leaves the rest to the caller:
+ * Ids and blocks: id(r) = the bytes of the record's header line, trimmed as the parser trims, from index 1 up to the first
+ *   separator or the trimmed end — the separator is ' ' in FASTQ and any of {' ', \t, \n, \v, \f, \r} in FASTA; the id may be
+ *   empty.  A result block is whole when all `block` records of it are among the n records.  The records before the first block
+ *   boundary inside the call are left as one run PFQ_LEFT_HEAD, those behind the last boundary as one run PFQ_LEFT_TAIL; a call
+ *   that contains no whole block leaves everything as one run PFQ_LEFT_HEAD (n = 0: no run).  A whole block is plain when the
+ *   ids of its records are pairwise different as byte strings (compared exactly: equal hashes are settled by the bytes); a
+ *   whole block that is not plain is left as one run PFQ_LEFT_REPEATED_ID.
+ * Bytes of one record: a record of a whole plain block is mapped when H(r) is not empty.  With PFQ_FMT_POS a mapped record goes
+ *   to the pos stream, with PFQ_FMT_NEG an unmapped one to neg, in ascending r.  Its bytes: '@' (FASTA: '>'), id(r); for a
+ *   mapped record " |" and the tax_ids (those of pfq_leaf_counts) of H(r) in row order joined by ','; '\n'; the record's
+ *   sequence of the parsed CSR with only 'a' .. 'z' lowered by 32 (bytes >= 0x80 and everything else stay); '\n'; FASTQ only:
+ *   "+\n", line 4r + 3 trimmed, '\n'.
+ * Left runs: left[i] covers records first .. first + count - 1 (r, relative to the parsed block); pos_at / neg_at are the offsets
+ *   in the two streams where the run's bytes belong.  The streams with the caller's own bytes for the left runs spliced in at
+ *   these offsets are the whole block's output in record order.
+ * PFQ_ERR_STATE: no parse yet; the last query call on the tree was not a successful pfq_text_query of this block with
+ * PFQ_WANT_HITS and without PFQ_PAIRED (another query call or another parse in between counts as this case).  PFQ_ERR_ARG: tree or
+ * out NULL, block 0 or above PFQ_FMT_BLOCK_MAX, neither PFQ_FMT_POS nor PFQ_FMT_NEG, unknown flag bits.  PFQ_ERR_UNSUPPORTED: a
+ * subtree shard (its rows are partial); a record whose output would be 2^32 bytes or more.  A sticky insertion error is returned
+ * as everywhere else.
+ * The call changes no counter, log, sketch or query result, may be repeated and then gives the same result, runs on the tree's
+ * copy stream and waits only for its own work.  pos, neg and left are valid until the next pfq_text_format or pfq_text_parse on
+ * the tree; pfq_info.device_bytes counts its buffers.  Options (results never depend on them): PFQ_FMT_GRID caps every grid, so
+ * that tiny inputs take several grid-stride trips; PFQ_FMT_HASH_BITS (1 .. 64) keeps only that many bits of the id hash, so that
+ * different ids collide and the byte comparison runs (a block's keys hold at most 51 of them); PFQ_FMT_TIME=1 makes the HIP
+ * events behind pfq_debug_last_format (PFQ_ERR_STATE without a timed call of at least one record). */
+#define PFQ_FMT_POS 1u
+#define PFQ_FMT_NEG 2u
+#define PFQ_FMT_BLOCK_MAX 8192
+enum { PFQ_LEFT_HEAD = 1, PFQ_LEFT_TAIL = 2, PFQ_LEFT_REPEATED_ID = 3 };
+typedef struct pfq_text_left { uint64_t first, count, pos_at, neg_at; uint32_t why, pad_; } pfq_text_left;
+typedef struct pfq_text_records {
+    uint64_t n_records;                                       /* records of the parsed block */
+    uint64_t pos_records, neg_records, pos_bytes, neg_bytes;  /* what the two streams hold */
+    const uint8_t *pos, *neg;                                 /* library-owned page-locked host memory */
+    uint64_t n_left;
+    const pfq_text_left *left;                                /* ascending, disjoint; library-owned */
+} pfq_text_records;
+int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out);
+int pfq_debug_last_format(pfq_tree *tree, double *ms /* [3]: ids + blocks, sizes + scans, emit; HIP events */);
+
 /* ---- read preprocessing (pfq_prep_reads, pfq_prep_query) ----
  * What a trimmer in front of a classifier does — low-quality and poly-X tails cut, reads that are too short, mostly N or of
  * low complexity dropped — on the device, into the block a query call takes.  Integers only; the result for a read is a pure

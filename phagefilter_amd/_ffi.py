@@ -20,7 +20,7 @@ SYMBOLS = [
     "pfq_coverage_get", "pfq_coverage_reset", "pfq_coverage_absorb",
     "pfq_tree_set_sweep", "pfq_sweep_get", "pfq_sweep_reset", "pfq_sweep_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
-    "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr",
+    "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr", "pfq_text_format", "pfq_debug_last_format",
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
@@ -116,6 +116,17 @@ class Text(C.Structure):
                 ("rec_begin", C.POINTER(C.c_uint64))]
 
 
+class TextLeft(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("pos_at", C.c_uint64), ("neg_at", C.c_uint64),
+                ("why", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class TextRecords(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("pos_records", C.c_uint64), ("neg_records", C.c_uint64),
+                ("pos_bytes", C.c_uint64), ("neg_bytes", C.c_uint64), ("pos", C.POINTER(C.c_uint8)), ("neg", C.POINTER(C.c_uint8)),
+                ("n_left", C.c_uint64), ("left", C.POINTER(TextLeft))]
+
+
 class PrepParams(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("trim_quality", "trim_window", "poly_x", "min_length", "max_n", "min_complexity", "flags")]
 
@@ -156,6 +167,8 @@ NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
 TEXT_END, TEXT_LIMIT, TEXT_MORE, TEXT_SLOW = 0, 1, 2, 3
+FMT_POS, FMT_NEG, FMT_BLOCK_MAX = 1, 2, 8192
+LEFT_HEAD, LEFT_TAIL, LEFT_REPEATED_ID = 1, 2, 3
 PREP_PAIRED, PREP_WANT_READS = 1, 2
 PREP_KEPT, PREP_SHORT, PREP_N, PREP_COMPLEXITY, PREP_MATE = 0, 1, 2, 3, 4
 PREP_MAX_N_OFF = 0xFFFFFFFF
@@ -229,6 +242,8 @@ def lib() -> C.CDLL:
     L.pfq_text_parse.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(Text)]
     L.pfq_text_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_text_csr.argtypes = [vp, vp, vp]
+    L.pfq_text_format.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(TextRecords)]
+    L.pfq_debug_last_format.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_prep_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(PrepParams), C.POINTER(Prep)]
     L.pfq_prep_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_prep_csr.argtypes = [vp, vp, vp]

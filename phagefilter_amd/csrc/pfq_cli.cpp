@@ -1639,6 +1639,114 @@ void put_lca(std::string &o, std::string_view id, uint64_t n_hits, uint32_t clad
     o.push_back('\n');
 }
 
+// ResultMap of one block (result_map.rs:20-45) without allocations: an open-addressing table over the ids of the reads that
+// hit.  An id that hits twice in a block (the same read id in two records) merges its genomes.
+struct BlockGroup {
+    std::string_view id;
+    uint64_t first_read;  // the (first) read with this id that hit
+    int32_t merged;       // index into the block's merged sets once a second read with the id has hit
+};
+inline uint64_t hash_id(std::string_view v) {
+    uint64_t h = 0x9E3779B97F4A7C15ull ^ v.size();
+    size_t i = 0;
+    for (; i + 8 <= v.size(); i += 8) {
+        uint64_t x;
+        memcpy(&x, v.data() + i, 8);
+        h = (h ^ x) * 0xff51afd7ed558ccdull;
+        h ^= h >> 32;
+    }
+    uint64_t x = 0;
+    if (i < v.size()) memcpy(&x, v.data() + i, v.size() - i);
+    h = (h ^ x) * 0xc4ceb9fe1a85ec53ull;
+    return h ^ (h >> 29);
+}
+// slots of the table of a block in which n_hit reads hit (a power of two; 0: the block has no hit and needs no table)
+inline uint64_t block_table_slots(uint64_t n_hit) {
+    if (!n_hit) return 0;
+    uint64_t want = 16;
+    while (want < 2 * n_hit) want <<= 1;
+    return want;
+}
+// The map of block [b0, b1) of batch b with the hit rows (h_off, h_leaves): grp [reads of the block that hit], tab [tab_slots,
+// zeroed], the genome sets of the ids that hit more than once in `merged`; then for EVERY read of the block its group in
+// grp_of[r] (read_mapped: the id is in the block's map, also for reads that did not hit themselves), -1: not mapped.
+void map_block(const Batch &b, uint64_t b0, uint64_t b1, const uint64_t *h_off, const uint32_t *h_leaves, BlockGroup *grp, uint32_t *tab,
+               size_t tab_slots, std::vector<std::vector<uint32_t>> &merged, int32_t *grp_of) {
+    const size_t mask = tab_slots - 1;  // (no table: the block has no hit)
+    const bool any = tab_slots != 0;
+    merged.clear();
+    uint32_t n_grp = 0;
+    auto find = [&](std::string_view id, bool insert, uint64_t r) -> int32_t {
+        for (size_t i = (size_t)hash_id(id) & mask;; i = (i + 1) & mask) {
+            const uint32_t g = tab[i];
+            if (!g) {
+                if (!insert) return -1;
+                grp[n_grp] = BlockGroup{id, r, -1};
+                tab[i] = ++n_grp;
+                return (int32_t)n_grp - 1;
+            }
+            if (grp[g - 1].id == id) return (int32_t)g - 1;
+        }
+    };
+    if (any)
+        for (uint64_t r = b0; r < b1; ++r) {
+            if (h_off[r] == h_off[r + 1]) continue;
+            const int32_t g = find(b.id(r), true, r);
+            grp_of[r] = g;
+            BlockGroup &gr = grp[g];
+            if (gr.first_read == r) continue;        // new id
+            if (gr.merged < 0) {                      // second read with this id: the sets merge
+                gr.merged = (int32_t)merged.size();
+                merged.emplace_back(h_leaves + h_off[gr.first_read], h_leaves + h_off[gr.first_read + 1]);
+            }
+            merged[gr.merged].insert(merged[gr.merged].end(), h_leaves + h_off[r], h_leaves + h_off[r + 1]);
+        }
+    for (auto &v : merged) {  // a set of genomes per id; printed in leaf order
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    }
+    for (uint64_t r = b0; r < b1; ++r)
+        if (h_off[r] == h_off[r + 1]) grp_of[r] = any ? find(b.id(r), false, 0) : -1;
+}
+// Read r of a mapped block (group g of grp, -1: not mapped) into the POS or the NEG buffer, if that stream is wanted.
+inline void put_block_record(OutBuf &pb, OutBuf &nb, const Batch &b, uint64_t r, int32_t g, const BlockGroup *grp,
+                             const std::vector<std::vector<uint32_t>> &merged, const uint64_t *h_off, const uint32_t *h_leaves, bool pos, bool neg,
+                             const std::vector<std::string> &names) {
+    const bool mapped = g >= 0;
+    if (mapped ? !pos : !neg) return;
+    const uint32_t *l0 = nullptr, *l1 = nullptr;
+    if (mapped) {
+        const BlockGroup &gr = grp[g];
+        if (gr.merged >= 0) {
+            l0 = merged[gr.merged].data();
+            l1 = l0 + merged[gr.merged].size();
+        } else {
+            l0 = h_leaves + h_off[gr.first_read];   // (ascending within a read, no duplicates)
+            l1 = h_leaves + h_off[gr.first_read + 1];
+        }
+    }
+    put_record(mapped ? pb : nb, b, r, l0, l1, names);
+}
+// One block on its own: reads [0, n) of b through the block's map, appended to pb / nb (--device-output: the blocks the device
+// leaves to the host).
+struct BlockFormatter {
+    std::vector<BlockGroup> grp;
+    std::vector<uint32_t> tab;
+    std::vector<int32_t> grp_of;
+    std::vector<std::vector<uint32_t>> merged;
+    void run(const Batch &b, const uint64_t *h_off, const uint32_t *h_leaves, bool pos, bool neg, const std::vector<std::string> &names, OutBuf &pb,
+             OutBuf &nb) {
+        const uint64_t n = b.n();
+        uint64_t n_hit = 0;
+        for (uint64_t r = 0; r < n; ++r) n_hit += h_off[r] != h_off[r + 1];
+        grp.resize(n_hit);
+        tab.assign(block_table_slots(n_hit), 0);
+        grp_of.resize(n);
+        map_block(b, 0, n, h_off, h_leaves, grp.data(), tab.data(), tab.size(), merged, grp_of.data());
+        for (uint64_t r = 0; r < n; ++r) put_block_record(pb, nb, b, r, grp_of[r], grp.data(), merged, h_off, h_leaves, pos, neg, names);
+    }
+};
+
 // The three query loops over an open database, the reader and the outputs.
 struct QueryLoop {
     ServedDb &db;
@@ -2019,6 +2127,209 @@ struct QueryLoop {
                 s > 0 ? n_text_bytes.load() / s * 1e-9 : 0.0);
     }
 
+    // --device-output: POS / NEG on replicas with the plain files parsed AND formatted on the device.  Tickets as in
+    // counts_only_text: a replica's thread parses its chunk (with the records' begins), proves the start in its turn — which also
+    // gives the chunk's first global record index — then classifies with hit lists (pfq_text_query) and formats
+    // (pfq_text_format: the whole result blocks whose ids are pairwise different).  A second ordered turn is the output stage:
+    // the device streams are written as they are; a block with a repeated id is parsed on the host from the chunk's own bytes
+    // and goes through the block map with the hits the query call already returned; the records at the chunk's edges (HEAD,
+    // TAIL) and everything the host reader parsed (gzip, the rest of a chunk after SLOW / MORE, malformed tails: classify())
+    // go into a carry that becomes a block when it holds `block` records, or at the end of the input.
+    std::atomic<uint64_t> n_fmt_device{0}, n_fmt_host{0}, ns_text_format{0}, n_fmt_bytes{0};
+    void device_output() {
+        std::mutex take_mu, turn_mu;
+        std::condition_variable turn_cv;
+        uint64_t taken = 0, commit_next = 0, write_next = 0, next_index = 0;
+        std::atomic<bool> exhausted{false}, aborted{false};
+        const uint32_t fmt_flags = (pos ? PFQ_FMT_POS : 0u) | (neg ? PFQ_FMT_NEG : 0u);
+        const uint32_t query_flags = PFQ_WANT_HITS | lca_flags();
+        // the output stage's state: touched only inside the output turn (and after the threads have joined)
+        Batch carry;
+        std::vector<uint64_t> carry_off{0};
+        std::vector<uint32_t> carry_leaves;
+        BlockFormatter bf;
+        OutBuf pb, nb;
+        auto write_block = [&](const Batch &b, const uint64_t *h_off, const uint32_t *h_leaves) {
+            pb.n = nb.n = 0;
+            bf.run(b, h_off, h_leaves, pos, neg, db.leaf_names, pb, nb);
+            out.pos.append(pb.p, pb.n);
+            out.neg.append(nb.p, nb.n);
+            n_fmt_host += b.n();
+        };
+        auto flush_carry = [&] {
+            if (!carry.n()) return;
+            write_block(carry, carry_off.data(), carry_leaves.data());
+            carry.clear();
+            carry_off.assign(1, 0);
+            carry_leaves.clear();
+        };
+        // records [r0, r1) of src with their rows (h_off relative to h_leaves) join the carry; it is written whenever it is a block
+        auto carry_add = [&](const Batch &src, uint64_t r0, uint64_t r1, const uint64_t *h_off, const uint32_t *h_leaves) {
+            while (r0 < r1) {
+                const uint64_t take = std::min<uint64_t>(r1 - r0, block - carry.n());
+                carry.append(src, r0, r0 + take, true);
+                carry_leaves.insert(carry_leaves.end(), h_leaves + h_off[r0], h_leaves + h_off[r0 + take]);
+                for (uint64_t r = r0 + 1; r <= r0 + take; ++r) carry_off.push_back(carry_off.back() + (h_off[r] - h_off[r - 1]));
+                r0 += take;
+                if (carry.n() == block) flush_carry();
+            }
+        };
+        fan_out(n_trees(), [&](size_t d) {
+            pfq_tree *tree = db.trees[d];
+            Hits host_hits;
+            Batch run_b;                       // a left run parsed on the host
+            std::vector<uint64_t> left_off;    // the rows of the left runs, copied before the tree's next query call
+            std::vector<uint32_t> left_leaves;
+            while (true) {
+                Segment *sg;
+                const Task *task = nullptr;
+                uint64_t ticket;
+                {
+                    std::lock_guard<std::mutex> lk(take_mu);
+                    if (exhausted || aborted) return;
+                    if (!(sg = rq.pop_segment(task))) {
+                        exhausted = true;
+                        return;
+                    }
+                    ticket = taken++;
+                }
+                const MappedFile &m = rq.maps[task->file];
+                const Fmt fmt = rq.fmts[task->file];
+                pfq_text res{};
+                uint64_t parsed_from = ~0ull;
+                auto parse_from = [&](uint64_t from) {  // the chunk's records from file offset `from` on
+                    parsed_from = from;
+                    res = pfq_text{};
+                    res.stop = PFQ_TEXT_LIMIT;
+                    if (from >= task->hi || from > sg->text_hi) return;  // (no record of this chunk begins there)
+                    const uint64_t t0 = ReadQueue::now_ns();
+                    if (pfq_text_parse(tree, (const uint8_t *)sg->text.p + (from - sg->text_lo), sg->text_hi - from, task->hi - from,
+                                       fmt == Fmt::Fastq ? PFQ_TEXT_FASTQ : PFQ_TEXT_FASTA,
+                                       (sg->text_hi == m.size ? PFQ_TEXT_FINAL : 0u) | PFQ_TEXT_WANT_RECORDS, &res) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    ns_text_parse += ReadQueue::now_ns() - t0;
+                    n_text_bytes += sg->text_hi - from;
+                };
+                if (sg->is_text && !rq.file_slow[task->file]) parse_from(sg->start_pos);
+                {
+                    std::unique_lock<std::mutex> lk(turn_mu);
+                    turn_cv.wait(lk, [&] { return commit_next == ticket; });
+                }
+                // (the proof turn: one thread at a time, in the order the segments were taken)
+                const bool dropped = aborted;
+                const bool was_text = sg->is_text;
+                uint64_t n_dev = 0, first_index = 0;
+                if (!dropped && was_text) {
+                    const uint64_t expect = rq.expected_start(*task);
+                    bool host_rest = rq.file_slow[task->file];
+                    uint64_t rest_from = expect;
+                    if (!host_rest) {
+                        if (parsed_from != expect) parse_from(expect);  // the guess was wrong (or a record spans chunks)
+                        n_dev = res.n_records;
+                        rest_from = expect + res.consumed;
+                        if (res.stop == PFQ_TEXT_SLOW) rq.file_slow[task->file] = host_rest = true;
+                        else if (res.stop == PFQ_TEXT_MORE || (res.stop == PFQ_TEXT_END && sg->text_hi != m.size && rest_from < task->hi)) host_rest = true;
+                    }
+                    if (host_rest) {
+                        rq.parse_chunk(m, fmt, task->lo, task->hi, true, rest_from, *sg);
+                        rq.proven_pos = sg->end_pos;
+                    } else rq.proven_pos = rest_from;
+                    sg->is_text = false;
+                } else if (!dropped) rq.validate(*task, *sg);
+                if (!dropped) {
+                    first_index = next_index;
+                    next_index += n_dev + sg->b.n();
+                    if (!sg->err.empty()) {
+                        rq.pending_error = sg->err;  // (fatal later, after the reads before it)
+                        aborted = true;
+                    }
+                }
+                {
+                    std::lock_guard<std::mutex> lk(turn_mu);
+                    ++commit_next;
+                }
+                turn_cv.notify_all();
+                // ---- outside the turns: classify and format the device's records, classify the host's
+                pfq_text_records recs{};
+                if (!dropped && n_dev) {
+                    const uint64_t tq0 = ReadQueue::now_ns();
+                    pfq_hits hits{};
+                    if (pfq_text_query(tree, threshold, query_flags, &hits) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    const uint64_t tq1 = ReadQueue::now_ns();
+                    if (pfq_text_format(tree, first_index, (uint32_t)block, fmt_flags, &recs) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    ns_text_format += ReadQueue::now_ns() - tq1;
+                    ns_gpu += tq1 - tq0;
+                    n_fmt_bytes += recs.pos_bytes + recs.neg_bytes;
+                    n_total += n_dev;
+                    n_device_records += n_dev;
+                    left_off.assign(1, 0);
+                    left_leaves.clear();
+                    for (uint64_t i = 0; i < recs.n_left; ++i) {  // (the library's hit lists live until the tree's next query call)
+                        const pfq_text_left &l = recs.left[i];
+                        left_leaves.insert(left_leaves.end(), hits.leaves + hits.offsets[l.first], hits.leaves + hits.offsets[l.first + l.count]);
+                        for (uint64_t r = l.first + 1; r <= l.first + l.count; ++r) left_off.push_back(left_off.back() + (hits.offsets[r] - hits.offsets[r - 1]));
+                    }
+                }
+                const uint64_t n_host = dropped ? 0 : sg->b.n();
+                if (n_host) {
+                    sg->b.seq.resize(sg->b.seq.size() + 16);
+                    const uint64_t tq0 = ReadQueue::now_ns();
+                    classify(tree, sg->b, 0, n_host, threshold, query_flags, host_hits);
+                    ns_gpu += ReadQueue::now_ns() - tq0;
+                    n_total += n_host;
+                    n_host_records += n_host;
+                }
+                {
+                    std::unique_lock<std::mutex> lk(turn_mu);
+                    turn_cv.wait(lk, [&] { return write_next == ticket; });
+                }
+                // (the output turn: one thread at a time, in input order)
+                const uint64_t t_out0 = ReadQueue::now_ns();
+                if (!dropped && n_dev) {
+                    const char *text = sg->text.p - sg->text_lo;  // (the address byte 0 of the file would have)
+                    uint64_t pc = 0, qc = 0, left_rows = 0, n_left_records = 0;
+                    for (uint64_t i = 0; i < recs.n_left; ++i) {
+                        const pfq_text_left &l = recs.left[i];
+                        out.pos.append((const char *)recs.pos + pc, l.pos_at - pc);
+                        out.neg.append((const char *)recs.neg + qc, l.neg_at - qc);
+                        pc = l.pos_at;
+                        qc = l.neg_at;
+                        run_b.clear();
+                        MemLines ml(text, parsed_from + res.rec_begin[l.first], parsed_from + res.rec_begin[l.first + l.count]);
+                        RecordParser<MemLines> rp(ml, fmt);
+                        while (run_b.n() < l.count && rp.next(run_b, true) == 1) {}
+                        if (run_b.n() != l.count) fail_from_thread("internal error: the host reader and the device disagree about a chunk's records");
+                        const uint64_t *off = left_off.data() + left_rows;  // (rows of this run; relative to off[0])
+                        std::vector<uint64_t> rel(l.count + 1);
+                        for (uint64_t r = 0; r <= l.count; ++r) rel[r] = off[r] - off[0];
+                        if (l.why == PFQ_LEFT_REPEATED_ID) write_block(run_b, rel.data(), left_leaves.data() + off[0]);
+                        else carry_add(run_b, 0, l.count, rel.data(), left_leaves.data() + off[0]);
+                        left_rows += l.count;
+                        n_left_records += l.count;
+                    }
+                    out.pos.append((const char *)recs.pos + pc, recs.pos_bytes - pc);
+                    out.neg.append((const char *)recs.neg + qc, recs.neg_bytes - qc);
+                    n_fmt_device += n_dev - n_left_records;
+                }
+                if (n_host) carry_add(sg->b, 0, n_host, host_hits.off.data(), host_hits.leaves.data());
+                ns_out += ReadQueue::now_ns() - t_out0;
+                {
+                    std::lock_guard<std::mutex> lk(turn_mu);
+                    ++write_next;
+                }
+                turn_cv.notify_all();
+                rq.recycle(sg);
+            }
+        });
+        flush_carry();  // the last block of the input is a partial one
+    }
+    void report_device_output() const {
+        const double s = ns_text_format.load() * 1e-9;
+        fprintf(stderr, "device output: %llu records formatted on the device, %llu by the host formatter; pfq_text_format made %llu bytes in %.3f s (%.2f GB/s, kernels and copy, summed over devices)\n",
+                (unsigned long long)n_fmt_device.load(), (unsigned long long)n_fmt_host.load(), (unsigned long long)n_fmt_bytes.load(), s,
+                s > 0 ? n_fmt_bytes.load() / s * 1e-9 : 0.0);
+    }
+
     // Per read, with POS/NEG and/or READ_SCORES.  The device processes big batches; ResultMap semantics (ids merged per
     // reference block, cleared per block, main.rs:334-368) are applied per `block` consecutive reads so the outputs do not
     // depend on the batch size.  Three stages, each on its own thread(s), batches in flight between them: (1) the
@@ -2146,35 +2457,15 @@ struct QueryLoop {
             }
         });
         std::thread output([&] {
-            // ResultMap of one block (result_map.rs:20-45) without allocations: an open-addressing table over the ids of the
-            // reads that hit.  An id that hits twice in a block (the same read id in two records) merges its genomes.
-            // Two phases per batch: (1) workers take whole blocks: table of the block's hit ids, then for EVERY read of the
-            // block its group (read_mapped: the id is in the block's map) — all hashing happens here; (2) workers take equal
-            // ranges of reads and only format (a block of 100 000 reads is formatted by several workers).
-            struct Group {
-                std::string_view id;
-                uint64_t first_read;          // the (first) read with this id that hit
-                int32_t merged;               // index into the block's merged sets once a second read with the id has hit
-            };
-            std::vector<Group> groups;                            // [hit reads of the batch], a slice per block
+            // The blocks' ResultMaps (map_block).  Two phases per batch: (1) workers take whole blocks: table of the block's hit
+            // ids, then for EVERY read of the block its group (read_mapped: the id is in the block's map) — all hashing happens
+            // here; (2) workers take equal ranges of reads and only format (a block of 100 000 reads is formatted by several
+            // workers).
+            std::vector<BlockGroup> groups;                       // [hit reads of the batch], a slice per block
             std::vector<uint32_t> table;                          // open-addressing tables of all blocks, a slice (power of two) per block
             std::vector<uint64_t> grp0, tab0;                     // [blocks + 1] first group / first table slot of every block
             std::vector<int32_t> grp_of;                          // [reads] group of the read within its block, -1: not mapped
             std::vector<std::vector<std::vector<uint32_t>>> merged_of;  // [blocks] merged genome sets (ids that hit more than once)
-            auto hash_id = [](std::string_view v) {
-                uint64_t h = 0x9E3779B97F4A7C15ull ^ v.size();
-                size_t i = 0;
-                for (; i + 8 <= v.size(); i += 8) {
-                    uint64_t x;
-                    memcpy(&x, v.data() + i, 8);
-                    h = (h ^ x) * 0xff51afd7ed558ccdull;
-                    h ^= h >> 32;
-                }
-                uint64_t x = 0;
-                if (i < v.size()) memcpy(&x, v.data() + i, v.size() - i);
-                h = (h ^ x) * 0xc4ceb9fe1a85ec53ull;
-                return h ^ (h >> 29);
-            };
             for (uint64_t k = 0;; ++k) {
                 Slot &s = slots[k % NB];
                 {
@@ -2200,13 +2491,8 @@ struct QueryLoop {
                     const uint64_t b0 = blk * block, b1 = std::min(n, b0 + block);
                     uint64_t n_hit = 0;
                     for (uint64_t r = b0; r < b1; ++r) n_hit += h_off[r] != h_off[r + 1];
-                    uint64_t want = 0;
-                    if (n_hit) {
-                        want = 16;
-                        while (want < 2 * n_hit) want <<= 1;
-                    }
                     grp0[blk + 1] = grp0[blk] + n_hit;
-                    tab0[blk + 1] = tab0[blk] + want;
+                    tab0[blk + 1] = tab0[blk] + block_table_slots(n_hit);
                 }
                 if (groups.size() < grp0[n_blocks]) groups.resize(grp0[n_blocks]);
                 table.assign(tab0[n_blocks], 0);
@@ -2216,44 +2502,8 @@ struct QueryLoop {
                 fan_out(nw1, [&](size_t w) {
                     for (uint64_t blk = n_blocks * w / nw1; blk < n_blocks * (w + 1) / nw1; ++blk) {
                         const uint64_t b0 = blk * block, b1 = std::min(n, b0 + block);
-                        Group *grp = groups.data() + grp0[blk];
-                        uint32_t *tab = table.data() + tab0[blk];
-                        const size_t mask = (size_t)(tab0[blk + 1] - tab0[blk]) - 1;   // (no table: the block has no hit)
-                        const bool any = tab0[blk + 1] != tab0[blk];
-                        auto &merged = merged_of[blk];
-                        merged.clear();
-                        uint32_t n_grp = 0;
-                        auto find = [&](std::string_view id, bool insert, uint64_t r) -> int32_t {
-                            for (size_t i = (size_t)hash_id(id) & mask;; i = (i + 1) & mask) {
-                                const uint32_t g = tab[i];
-                                if (!g) {
-                                    if (!insert) return -1;
-                                    grp[n_grp] = Group{id, r, -1};
-                                    tab[i] = ++n_grp;
-                                    return (int32_t)n_grp - 1;
-                                }
-                                if (grp[g - 1].id == id) return (int32_t)g - 1;
-                            }
-                        };
-                        if (any)
-                            for (uint64_t r = b0; r < b1; ++r) {
-                                if (h_off[r] == h_off[r + 1]) continue;
-                                const int32_t g = find(b.id(r), true, r);
-                                grp_of[r] = g;
-                                Group &gr = grp[g];
-                                if (gr.first_read == r) continue;        // new id
-                                if (gr.merged < 0) {                      // second read with this id: the sets merge
-                                    gr.merged = (int32_t)merged.size();
-                                    merged.emplace_back(h_leaves + h_off[gr.first_read], h_leaves + h_off[gr.first_read + 1]);
-                                }
-                                merged[gr.merged].insert(merged[gr.merged].end(), h_leaves + h_off[r], h_leaves + h_off[r + 1]);
-                            }
-                        for (auto &v : merged) {  // a set of genomes per id; printed in leaf order
-                            std::sort(v.begin(), v.end());
-                            v.erase(std::unique(v.begin(), v.end()), v.end());
-                        }
-                        for (uint64_t r = b0; r < b1; ++r)   // read_mapped: the id is in the block's map (also for reads that did not hit themselves)
-                            if (h_off[r] == h_off[r + 1]) grp_of[r] = any ? find(b.id(r), false, 0) : -1;
+                        map_block(b, b0, b1, h_off, h_leaves, groups.data() + grp0[blk], table.data() + tab0[blk], (size_t)(tab0[blk + 1] - tab0[blk]),
+                                  merged_of[blk], grp_of.data());
                     }
                 });
                 // ---- phase 2: the records
@@ -2262,22 +2512,8 @@ struct QueryLoop {
                     OutBuf &pb = pos_buf[w], &nb = neg_buf[w];
                     pb.n = nb.n = 0;
                     for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r) {
-                        const int32_t g = grp_of[r];
-                        const bool mapped = g >= 0;
-                        if (mapped ? !pos : !neg) continue;
-                        const uint32_t *l0 = nullptr, *l1 = nullptr;
-                        if (mapped) {
-                            const uint64_t blk = r / block;
-                            const Group &gr = groups[grp0[blk] + (uint64_t)g];
-                            if (gr.merged >= 0) {
-                                l0 = merged_of[blk][gr.merged].data();
-                                l1 = l0 + merged_of[blk][gr.merged].size();
-                            } else {
-                                l0 = h_leaves + h_off[gr.first_read];   // (ascending within a read, no duplicates)
-                                l1 = h_leaves + h_off[gr.first_read + 1];
-                            }
-                        }
-                        put_record(mapped ? pb : nb, b, r, l0, l1, db.leaf_names);
+                        const uint64_t blk = r / block;
+                        put_block_record(pb, nb, b, r, grp_of[r], groups.data() + grp0[blk], merged_of[blk], h_off, h_leaves, pos, neg, db.leaf_names);
                     }
                 });
                 for (unsigned w = nw; w < fmt_workers; ++w) pos_buf[w].n = neg_buf[w].n = 0;
@@ -2362,7 +2598,7 @@ int cmd_query(int argc, char **argv) {
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
-                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"taxonomy", 0, true},
+                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true},
                              {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
                              {"min-complexity", 0, true}};
@@ -2459,6 +2695,26 @@ int cmd_query(int argc, char **argv) {
         const long v = strtol(coverage_p.c_str(), &end, 10);
         if (coverage_p.empty() || !isdigit((unsigned char)coverage_p[0]) || *end || v < 4 || v > 16)
             die("error: invalid value '" + coverage_p + "' for '--coverage-precision': 4 to 16 (2^P registers per genome)");
+    }
+    // --device-output: the POS / NEG records of plain FASTA / FASTQ files are parsed, classified and formatted on the device
+    // (pfq_text_parse, pfq_text_query, pfq_text_format).  Everything --device-parse refuses but the two filters is refused here
+    // too, before the other options' own checks, so that the refusal names this option
+    const bool device_output = a.flags.count("device-output") != 0;
+    if (device_output) {
+        const std::string why = ": it formats the POS / NEG records of single reads, and nothing else, on the device";
+        if (a.flags.count("device-parse"))
+            die("error: '--device-output' cannot be used with '--device-parse': that option serves runs that only count, this one parses the text itself");
+        for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits"})
+            if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
+        for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
+                                  "min-complexity"})
+            if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
+        if (lca == 2) die("error: '--device-output' cannot be used with '--lca best': the best hits need every read's scores");
+        if (!filtering) die("error: '--device-output' needs '--pos-filter' or '--neg-filter' (or both): they are the outputs it makes");
+        if (block == 0) die("error: '--device-output' cannot be used with '--block-size-reads 0': no read would be classified");
+        if (block > PFQ_FMT_BLOCK_MAX)
+            die("error: '--device-output' cannot be used with '--block-size-reads " + std::to_string(block) + "': the device decides POS / NEG per block of at most " +
+                std::to_string(PFQ_FMT_BLOCK_MAX) + " reads");
     }
     // --frame F [--frame-step S]: every sequence (a contig, a long read) is classified in overlapping frames of F bases every S
     // bases (pfq_query_frames) and SEGMENTS.tsv says where on it every genome matched; CLASSIFICATION.csv then counts sequences
@@ -2605,7 +2861,7 @@ int cmd_query(int argc, char **argv) {
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    rq.device_parse = device_parse;
+    rq.device_parse = device_parse || device_output;
     // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences; preprocessing: the qualities go to the device)
     if (block != 0) rq.start(per_read || paired || framed || prep_run.on, threads);
     if (block != 0 && rq2) rq2->start(true, threads);
@@ -2638,6 +2894,8 @@ int cmd_query(int argc, char **argv) {
         q.paired(rq2.get(), pair_mode == "both");
     } else if (device_parse) {
         q.counts_only_text();
+    } else if (device_output) {
+        q.device_output();
     } else if (!per_read) {
         q.counts_only();
     } else {
@@ -2649,7 +2907,8 @@ int cmd_query(int argc, char **argv) {
                 (unsigned long long)q.n_total.load(), wall, q.n_total.load() / wall * 1e-6, devices.size(), q.ns_gpu.load() * 1e-9,
                 q.ns_out.load() * 1e-9);
         rq.report_timing();
-        if (device_parse) q.report_device_parse();
+        if (device_parse || device_output) q.report_device_parse();
+        if (device_output) q.report_device_output();
         struct rusage ru;
         if (getrusage(RUSAGE_SELF, &ru) == 0)
             fprintf(stderr, "cpu: user %.2f s + system %.2f s so far (all threads) for %.2f s of query loop\n",
@@ -3171,6 +3430,12 @@ void usage() {
             "every error is what the run without the option gives.  For runs that only count: with -f, -b, -t, --search-depth, --devices,\n"
             "-F and --lca all.  Not with --pos-filter, --neg-filter, --scores, --lca best, --lca-reads, --reads2, --interleaved,\n"
             "--abundance, --coverage, --frame or --shard-depth\n"
+            "--device-output (needs --pos-filter and / or --neg-filter): the POS / NEG records of plain (not gzip) FASTA / FASTQ files are\n"
+            "parsed, classified and formatted on the GPU: the host threads only read file bytes and write the output streams.  The\n"
+            "device writes the blocks of -b reads whose ids are all different; blocks with a repeated id, the reads at the edges of a\n"
+            "chunk, gzip files and everything the host reader takes over go through the host formatter, so every output and every\n"
+            "error is what the run without the option gives.  -b at most 8192.  With -f, -b, -t, --search-depth, --devices, -F and\n"
+            "--lca all.  Not with --device-parse, and not with anything --device-parse refuses other than the two filters\n"
             "--taxonomy <FILE>: the tree's shape is an index, not a classification; this lays a taxonomy of your own over the database's\n"
             "genomes and counts the reads (paired input: fragments) at every rank.  FILE has one line per genome, \"genome<TAB>lineage\",\n"
             "the lineage a ';'-separated list of names from the top rank down (\"Caudoviricetes;Autographiviridae;Teseptimavirus\"; empty:\n"

@@ -114,6 +114,7 @@ struct Knobs {
     long long tile_lists = -1;                  // 0: no position slots, k_tile_test loads every tile dense (unset: slots for every sparse column)
     long long tile_stream = -1;                 // 0: the generic k_tile_test<0> even where every column has slots (unset: the slots-only build there)
     long long entry_pack = -1;                  // packed tile entries at threshold 1: 0 never, 1 / unset chosen per call from its read lengths, 2 always
+    long long fmt_grid = -1, fmt_hash_bits = -1, fmt_time = -1;  // pfq_text_format: a cap on every grid; bits of the id hash that are kept (1 .. 64); 1: time the stages with HIP events
 };
 struct KnobName {
     const char *name;
@@ -148,6 +149,8 @@ const KnobName KNOBS[] = {
     {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
     {"PFQ_TILE_LISTS", &Knobs::tile_lists},     {"PFQ_TILE_STREAM", &Knobs::tile_stream},
     {"PFQ_ENTRY_PACK", &Knobs::entry_pack},
+    {"PFQ_FMT_GRID", &Knobs::fmt_grid},         {"PFQ_FMT_HASH_BITS", &Knobs::fmt_hash_bits},
+    {"PFQ_FMT_TIME", &Knobs::fmt_time},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -438,6 +441,24 @@ struct pfq_tree {
     int tx_slot = 0;
     uint64_t tx_records = 0, tx_bases = 0;
     std::vector<uint64_t> out_rec_begin;
+    int tx_fastq = 0;
+    // pfq_text_format: what the kernels leave per record (ids, hashes, lengths and their scans), the small words that go back to
+    // the host in one copy (d_fm_small: FMT_RES_N result words | the streams' offsets at the block boundaries | the block states),
+    // the leaves' names (uploaded when they differ from fm_names), the two streams and their page-locked copies, which only
+    // grow.  fm_rows: the last query call was a successful pfq_text_query of the parsed block with PFQ_WANT_HITS and without
+    // PFQ_PAIRED, so d_hit_off / d_hit_leaves hold its rows, of a tree of fm_rows_leaves leaves.
+    DevBuf<uint32_t> d_fm_idb, d_fm_idl, d_fm_len[2], d_fm_long, d_fm_name_off;
+    DevBuf<uint64_t> d_fm_hash;
+    DevBuf<unsigned long long> d_fm_dst[2], d_fm_sums, d_fm_small;
+    DevBuf<uint8_t> d_fm_names, d_fm_out[2];
+    HostBuf<uint8_t> h_fm_out[2];
+    HostBuf<unsigned long long> h_fm_small;
+    std::vector<uint8_t> fm_names;
+    std::vector<uint32_t> fm_name_off;
+    std::vector<pfq_text_left> out_fm_left;
+    bool fm_rows = false, fm_timed = false;
+    uint64_t fm_rows_leaves = 0;
+    hipEvent_t fm_time[4] = {nullptr, nullptr, nullptr, nullptr};  // pfq_debug_last_format: ids + blocks, sizes + scans, emit
     // pfq_prep_reads: the block as the caller gave it and what the kernels leave per read (scratch of one call: the call waits
     // for its kernels), and two alternating CSR sets as above: pp_free[s] behind the classification that read set s, pp_ready
     // behind the prep kernels.
@@ -2467,6 +2488,7 @@ struct QueryRun {
 
 int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, uint64_t total_bytes,
                  float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
+    t.fm_rows = false;
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
@@ -3054,6 +3076,7 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
         return fail(PFQ_ERR_ARG, std::string("a node named ") + internal_name + " exists already: two nodes would share " + internal_name + ".bf");
     PFQ_TRY(sync_counts_to_nodes(t));
     t.layout_valid = false;
+    t.fm_rows = false;    // (the rows of the last pfq_text_query name the leaves as they were)
     t.drop_tile_lists();  // (made again with the layout)
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
@@ -3368,7 +3391,10 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes() +
                         t.d_pp_in.bytes() + t.d_pp_qual.bytes() + t.d_pp_hq.bytes() + t.d_pp_seq[0].bytes() + t.d_pp_seq[1].bytes() + t.d_pp_inoff.bytes() +  // (pfq_prep_reads)
                         t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
-                        t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes();
+                        t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
+                        t.d_fm_idb.bytes() + t.d_fm_idl.bytes() + t.d_fm_len[0].bytes() + t.d_fm_len[1].bytes() + t.d_fm_long.bytes() +  // (pfq_text_format)
+                        t.d_fm_name_off.bytes() + t.d_fm_hash.bytes() + t.d_fm_dst[0].bytes() + t.d_fm_dst[1].bytes() + t.d_fm_sums.bytes() +
+                        t.d_fm_small.bytes() + t.d_fm_names.bytes() + t.d_fm_out[0].bytes() + t.d_fm_out[1].bytes();
     return PFQ_OK;
 }
 
@@ -3384,6 +3410,7 @@ int pfq_tree_prune(pfq_tree *tree, uint64_t search_depth) {
         if (nd.depth >= search_depth) nd.left = nd.right = -1;  // bloom_tree.rs:322-325
     // nodes below the cut are unreachable now; they keep their slots (and filters) but never appear as leaves
     t.layout_valid = false;
+    t.fm_rows = false;    // (the rows of the last pfq_text_query name the leaves as they were)
     t.drop_tile_lists();  // (made again with the layout)
     t.lca_valid = false;  // (the clade numbering changes: tables and counters start again)
     abund_clear(t);       // (the leaf columns change meaning)
@@ -3421,6 +3448,8 @@ void pfq_tree_close(pfq_tree *tree) {
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->pp_time)
         if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->fm_time)
+        if (e) (void)hipEventDestroy(e);
     if (tree->pp_ready) (void)hipEventDestroy(tree->pp_ready);
     if (tree->h_pp_tot) (void)hipHostFree(tree->h_pp_tot);
     delete tree;
@@ -3450,6 +3479,7 @@ static int stage_input(pfq_tree &t, const uint8_t *seq, const uint64_t *offsets,
 
 // Flags of a query call; every query call ends the validity of the previous call's scores, a refused one included.
 static int check_flags(pfq_tree &t, uint32_t flags, uint64_t n_reads, float threshold) {
+    t.fm_rows = false;
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
@@ -3513,6 +3543,7 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
 // Flags and arguments of a frames call; like every query call it ends the validity of the previous call's scores and LCAs.
 static int check_frames(pfq_tree *tree, const void *seq, const void *offsets, uint64_t n_seqs, uint32_t flags, pfq_segments *out) {
     if (!tree || !out || (n_seqs && (!seq || !offsets))) return fail(PFQ_ERR_ARG, "null argument");
+    tree->fm_rows = false;
     tree->scores_valid = false;
     tree->lca_last = false;
     tree->taxa_last = false;
@@ -3578,6 +3609,7 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
     const int slot = t.tx_slot ^ 1;
     if (t.tx_used[slot]) HIP_TRY(hipEventSynchronize(t.tx_free[slot]));  // the classification that read this set is done
     t.tx_have = false;  // (until this parse has succeeded there is no block to query)
+    t.fm_rows = false;
     const uint32_t n = (uint32_t)len;
     HIP_TRY(t.d_tx_seq[slot].ensure((size_t)n + 16));
     out->n_records = out->consumed = out->n_bases = 0;
@@ -3666,6 +3698,7 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
     t.tx_slot = slot;
     t.tx_records = out->n_records;
     t.tx_bases = out->n_bases;
+    t.tx_fastq = fastq ? 1 : 0;
     t.tx_have = true;
     return PFQ_OK;
 }
@@ -3683,6 +3716,8 @@ int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hi
     t.tx_used[slot] = true;
     PFQ_TRY(rc);
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
+    t.fm_rows = (flags & PFQ_WANT_HITS) && !(flags & PFQ_PAIRED);  // (pfq_text_format reads these rows)
+    t.fm_rows_leaves = t.leaves.size();
     return PFQ_OK;
 }
 
@@ -3693,6 +3728,160 @@ int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
     const pfq_tree &t = *tree;
     if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_slot].p, t.tx_bases, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_slot].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+// ---- text output ----------------------------------------------------------------------------------------------------------
+
+int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (block < 1 || block > PFQ_FMT_BLOCK_MAX)
+        return fail(PFQ_ERR_ARG, "pfq_text_format: block must be 1 .. " + std::to_string(PFQ_FMT_BLOCK_MAX) + ", not " + std::to_string(block));
+    if (!(flags & (PFQ_FMT_POS | PFQ_FMT_NEG)) || (flags & ~(PFQ_FMT_POS | PFQ_FMT_NEG)))
+        return fail(PFQ_ERR_ARG, "pfq_text_format: flags must be PFQ_FMT_POS, PFQ_FMT_NEG or both");
+    pfq_tree &t = *tree;
+    PFQ_TRY(insertion_error(t));
+    if (t.is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_format on a subtree shard: a shard sees only its own leaves, so the rows it would print are partial");
+    if (!t.tx_have) return fail(PFQ_ERR_STATE, "pfq_text_format before a pfq_text_parse on this tree");
+    if (!t.fm_rows || t.fm_rows_leaves != t.leaves.size())
+        return fail(PFQ_ERR_STATE, "pfq_text_format: the last query call on this tree was not a successful pfq_text_query of the parsed block with "
+                                   "PFQ_WANT_HITS and without PFQ_PAIRED");
+    PFQ_TRY(use_device(t.device));
+    hipStream_t st = t.copy_stream;
+    const uint32_t n = (uint32_t)t.tx_records;
+    const size_t nl = t.leaves.size();
+    // the whole result blocks of the call: records head .. head + n_whole * block - 1
+    uint32_t head = (uint32_t)((block - first_index % block) % block);
+    const uint32_t n_whole = head < n ? (n - head) / block : 0;
+    if (!n_whole) head = n;
+    for (auto &h : t.h_fm_out) HIP_TRY(h.ensure(1));
+    *out = pfq_text_records{};
+    out->n_records = n;
+    out->pos = t.h_fm_out[0].p;
+    out->neg = t.h_fm_out[1].p;
+    t.out_fm_left.clear();
+    out->left = t.out_fm_left.data();
+    t.fm_timed = false;
+    if (!n) return PFQ_OK;
+    const bool timed = t.knobs.fmt_time == 1;
+    if (timed)
+        for (auto &e : t.fm_time)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+    {  // the leaves' names, uploaded when they are not the ones on the device
+        std::vector<uint8_t> names;
+        std::vector<uint32_t> name_off(1, 0);
+        for (int32_t v : t.leaves) {
+            const std::string &s = t.nodes[v].tax_id;
+            names.insert(names.end(), s.begin(), s.end());
+            name_off.push_back((uint32_t)names.size());
+        }
+        if (names.size() >> 31) return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_format: 2^31 bytes of leaf names or more");
+        if (!t.d_fm_name_off.p || names != t.fm_names || name_off != t.fm_name_off) {
+            HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(t.d_fm_names.ensure(names.size() + 16));
+            HIP_TRY(t.d_fm_name_off.ensure(name_off.size()));
+            if (!names.empty()) HIP_TRY(hipMemcpy(t.d_fm_names.p, names.data(), names.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(t.d_fm_name_off.p, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice));
+            t.fm_names.swap(names);
+            t.fm_name_off.swap(name_off);
+        }
+    }
+    HIP_TRY(t.d_fm_idb.ensure(n));
+    HIP_TRY(t.d_fm_idl.ensure(n));
+    HIP_TRY(t.d_fm_hash.ensure(n));
+    HIP_TRY(t.d_fm_long.ensure(n));
+    HIP_TRY(t.d_fm_sums.ensure((size_t)n / 4096 + 2));
+    for (int s = 0; s < 2; ++s) {
+        HIP_TRY(t.d_fm_len[s].ensure(n));
+        HIP_TRY(t.d_fm_dst[s].ensure((size_t)n + 1));
+    }
+    const size_t n_bounds = 2 * ((size_t)n_whole + 2), n_small = pfq::FMT_RES_N + n_bounds + ((size_t)n_whole + 1) / 2;
+    HIP_TRY(t.d_fm_small.ensure(n_small));
+    HIP_TRY(t.h_fm_small.ensure(n_small));
+    HIP_TRY(hipMemsetAsync(t.d_fm_small.p, 0, n_small * 8, st));
+    pfq::FmtArgs a{};
+    a.text = t.d_tx_text.p;
+    a.line_start = t.d_tx_line.p;
+    a.rec_line = t.d_tx_rec_line.p;
+    a.fastq = t.tx_fastq;
+    a.n = n;
+    a.head = head;
+    a.block = block;
+    a.n_whole = n_whole;
+    a.flags = flags;
+    a.hash_bits = t.knobs.fmt_hash_bits >= 1 && t.knobs.fmt_hash_bits <= 64 ? (uint32_t)t.knobs.fmt_hash_bits : 64u;
+    a.grid = t.knobs.fmt_grid >= 1 && t.knobs.fmt_grid <= 65535 ? (uint32_t)t.knobs.fmt_grid : 0u;
+    a.seq = t.d_tx_seq[t.tx_slot].p;
+    a.seq_off = t.d_tx_off[t.tx_slot].p;
+    a.row_off = t.d_hit_off.p;
+    a.row_leaves = t.d_hit_leaves.p;
+    a.names = t.d_fm_names.p;
+    a.name_off = t.d_fm_name_off.p;
+    a.id_beg = t.d_fm_idb.p;
+    a.id_len = t.d_fm_idl.p;
+    a.hash = t.d_fm_hash.p;
+    a.res = t.d_fm_small.p;
+    a.bounds = a.res + pfq::FMT_RES_N;
+    a.state = reinterpret_cast<uint32_t *>(a.bounds + n_bounds);
+    a.long_list = t.d_fm_long.p;
+    for (int s = 0; s < 2; ++s) {
+        a.len[s] = t.d_fm_len[s].p;
+        a.dst[s] = t.d_fm_dst[s].p;
+    }
+    if (timed) HIP_TRY(hipEventRecord(t.fm_time[0], st));
+    pfq::launch_fmt_ids(a, st);
+    if (timed) HIP_TRY(hipEventRecord(t.fm_time[1], st));
+    pfq::launch_fmt_sizes(a, nl > 64, st);
+    for (int s = 0; s < 2; ++s) pfq::launch_scan_u32(a.len[s], n, t.d_fm_sums.p, t.d_fm_dst[s].p, st);
+    pfq::launch_fmt_bounds(a, st);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(t.fm_time[2], st));
+    HIP_TRY(hipMemcpyAsync(t.h_fm_small.p, t.d_fm_small.p, n_small * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the totals size the streams)
+    const unsigned long long *res = t.h_fm_small.p, *bounds = res + pfq::FMT_RES_N;
+    const uint32_t *state = reinterpret_cast<const uint32_t *>(bounds + n_bounds);
+    if (res[pfq::FMT_RES_ERR]) return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_format: a record whose output would be 2^32 bytes or more");
+    const uint64_t total[2] = {bounds[2 * ((size_t)n_whole + 1)], bounds[2 * ((size_t)n_whole + 1) + 1]};
+    for (int s = 0; s < 2; ++s) {
+        HIP_TRY(t.d_fm_out[s].ensure(total[s] + 16));
+        HIP_TRY(t.h_fm_out[s].ensure(total[s] + 1));
+        a.out[s] = t.d_fm_out[s].p;
+    }
+    pfq::launch_fmt_emit(a, st);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(t.fm_time[3], st));
+    for (int s = 0; s < 2; ++s)
+        if (total[s]) HIP_TRY(hipMemcpyAsync(t.h_fm_out[s].p, t.d_fm_out[s].p, total[s], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    t.fm_timed = timed;
+    // the left runs, from the block states
+    if (head) t.out_fm_left.push_back(pfq_text_left{0, head, 0, 0, PFQ_LEFT_HEAD, 0});
+    for (uint32_t b = 0; b < n_whole; ++b)
+        if (state[b])
+            t.out_fm_left.push_back(pfq_text_left{head + (uint64_t)b * block, block, bounds[2 * (size_t)b], bounds[2 * (size_t)b + 1], PFQ_LEFT_REPEATED_ID, 0});
+    const uint64_t tail = head + (uint64_t)n_whole * block;
+    if (tail < n) t.out_fm_left.push_back(pfq_text_left{tail, n - tail, bounds[2 * (size_t)n_whole], bounds[2 * (size_t)n_whole + 1], PFQ_LEFT_TAIL, 0});
+    out->pos_records = res[pfq::FMT_RES_POS_RECORDS];
+    out->neg_records = res[pfq::FMT_RES_NEG_RECORDS];
+    out->pos_bytes = total[0];
+    out->neg_bytes = total[1];
+    out->pos = t.h_fm_out[0].p;
+    out->neg = t.h_fm_out[1].p;
+    out->n_left = t.out_fm_left.size();
+    out->left = t.out_fm_left.data();
+    return PFQ_OK;
+}
+
+int pfq_debug_last_format(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->fm_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_format before a pfq_text_format with records and PFQ_FMT_TIME=1 on this tree");
+    PFQ_TRY(use_device(tree->device));
+    for (int i = 0; i < 3; ++i) {
+        float v = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&v, tree->fm_time[i], tree->fm_time[i + 1]));
+        ms[i] = v;
+    }
     return PFQ_OK;
 }
 
@@ -5157,6 +5346,14 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
         const long long v = strtoll(value, nullptr, 10);
         if (v < (long long)pfq::TEXT_TILE_MIN || v > (long long)pfq::TEXT_TILE_DEFAULT || (v & (v - 1)))
             return fail(PFQ_ERR_ARG, std::string("PFQ_TEXT_TILE must be a power of two from 256 to 8192, not ") + value);
+    }
+    if (!strcmp(name, "PFQ_FMT_HASH_BITS") && value && *value) {  // bits of the id hash pfq_text_format keeps
+        const long long v = strtoll(value, nullptr, 10);
+        if (v < 1 || v > 64) return fail(PFQ_ERR_ARG, std::string("PFQ_FMT_HASH_BITS must be 1 .. 64, not ") + value);
+    }
+    if (!strcmp(name, "PFQ_FMT_GRID") && value && *value) {  // a cap on the grids of pfq_text_format
+        const long long v = strtoll(value, nullptr, 10);
+        if (v < 1 || v > 65535) return fail(PFQ_ERR_ARG, std::string("PFQ_FMT_GRID must be 1 .. 65535, not ") + value);
     }
     if (!strcmp(name, "PFQ_FRAME_PIECE") && value && *value) {  // the windows of a piece are whole: a positive multiple of 64
         const long long v = strtoll(value, nullptr, 10);

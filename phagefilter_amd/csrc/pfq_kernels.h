@@ -682,6 +682,45 @@ void launch_text_lines(const uint8_t *d_text, uint32_t len, uint32_t tile, const
 void launch_text_roles(const TextArgs &a, uint32_t *d_is_header, hipStream_t st);
 void launch_text_rec_lines(const uint32_t *d_is_header, const unsigned long long *d_rec_idx, uint32_t n_lines, uint32_t *d_rec_line, hipStream_t st);
 void launch_text_finish(const TextArgs &a, uint8_t *d_csr_seq, uint64_t *d_csr_off, uint64_t *d_rec_begin, hipStream_t st);
+// pfq_text_format (pfq_emit.hip): the POS / NEG records of the block pfq_text_parse took, formatted by the rules of pfq.h "text
+// output" from what the parse left (text, line_start, FASTA: rec_line), the CSR it gathered (seq, seq_off) and the final hit
+// rows of pfq_text_query (row_off, row_leaves).  Records head .. head + n_whole * block - 1 are the whole result blocks.
+//   launch_fmt_ids: id_beg, id_len, hash [n] (the hash cut to hash_bits bits); then state [n_whole] (zeroed by the caller) = 1
+//     for a block in which two records have the same id, exactly: equal hashes are settled by the bytes.
+//   launch_fmt_sizes: len[0] / len[1] [n] = the bytes a record adds to the POS / NEG stream, 0 for a record that is not emitted;
+//     res[FMT_RES_POS_RECORDS / NEG_RECORDS] += the records emitted, res[FMT_RES_ERR] |= 1 for a record of 2^32 bytes or more;
+//     long_rows: rows of more than 64 names may occur (res[FMT_RES_LONG] counts long_list [n]).  res is zeroed by the caller,
+//     who scans len[s] into dst[s] (launch_scan_u32).
+//   launch_fmt_bounds: bounds[2 i + s] = dst[s][head + i * block], i <= n_whole; bounds[2 (n_whole + 1) + s] = dst[s][n].
+//   launch_fmt_emit: the records written to out[s] + dst[s][r].  names: the leaves' tax_ids back to back, name_off [n_leaves + 1].
+// grid: 0, or a cap on every grid (PFQ_FMT_GRID).  n = 0: nothing runs.
+constexpr uint32_t FMT_POS = 1, FMT_NEG = 2, FMT_BLOCK_MAX = 8192;  // = PFQ_FMT_* of pfq.h
+enum FmtResult { FMT_RES_LONG = 0, FMT_RES_ERR = 1, FMT_RES_POS_RECORDS = 2, FMT_RES_NEG_RECORDS = 3, FMT_RES_N = 4 };
+struct FmtArgs {
+    const uint8_t *text;
+    const uint32_t *line_start, *rec_line;
+    int fastq;
+    uint32_t n, head, block, n_whole, flags, hash_bits, grid;
+    const uint8_t *seq;
+    const uint64_t *seq_off;                 // [n + 1]
+    const unsigned long long *row_off;       // [n + 1]
+    const uint32_t *row_leaves;
+    const uint8_t *names;
+    const uint32_t *name_off;
+    uint32_t *id_beg, *id_len;               // [n]
+    uint64_t *hash;                          // [n]
+    uint32_t *state;                         // [n_whole]
+    uint32_t *len[2];                        // [n]
+    const unsigned long long *dst[2];        // [n + 1]
+    uint32_t *long_list;                     // [n]
+    unsigned long long *res;                 // [FMT_RES_N]
+    unsigned long long *bounds;              // [2 (n_whole + 2)]
+    uint8_t *out[2];
+};
+void launch_fmt_ids(const FmtArgs &a, hipStream_t st);
+void launch_fmt_sizes(const FmtArgs &a, bool long_rows, hipStream_t st);
+void launch_fmt_bounds(const FmtArgs &a, hipStream_t st);
+void launch_fmt_emit(const FmtArgs &a, hipStream_t st);
 // pfq_prep_reads (pfq_prep.hip): reads trimmed and filtered by the rules of pfq.h "read preprocessing", the kept intervals
 // gathered into the CSR the classifier takes.  seq and qual are 16-byte aligned and hold 16 bytes beyond off[n_reads]; qual
 // shares off with seq (nullptr: no read has qualities), has_qual is a byte per read (nullptr: all have).

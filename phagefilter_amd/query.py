@@ -337,6 +337,29 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_text_query(self._h, threshold, flags, C.byref(hits)))
         return self._hits_result(hits, want_hits, want_scores)
 
+    LEFT_REASONS = {_ffi.LEFT_HEAD: "head", _ffi.LEFT_TAIL: "tail", _ffi.LEFT_REPEATED_ID: "repeated_id"}
+
+    def format_text(self, first_index: int = 0, block: int = 100, pos: bool = True, neg: bool = True) -> dict:
+        """The POS / NEG records of the block parse_text() parsed and query_text(want_hits=True) classified last, formatted on the
+        device (pfq_text_format; the rules are pfq.h "text output").  Record r has the global index first_index + r and lies in
+        result block (first_index + r) // block; only whole blocks whose ids are pairwise different are formatted.  Returns
+        n_records, pos, neg (bytes), pos_records, neg_records and left: a list of (first, count, pos_at, neg_at, why) — the runs
+        of records left to the caller, the offsets in the two streams where their bytes belong, and why ("head", "tail",
+        "repeated_id").  No counter changes."""
+        out = _ffi.TextRecords()
+        flags = (_ffi.FMT_POS if pos else 0) | (_ffi.FMT_NEG if neg else 0)
+        _ffi.check(_ffi.lib().pfq_text_format(self._h, first_index, block, flags, C.byref(out)))
+        left = [(int(x.first), int(x.count), int(x.pos_at), int(x.neg_at), self.LEFT_REASONS[x.why]) for x in out.left[:int(out.n_left)]]
+        return {"n_records": int(out.n_records), "pos": C.string_at(out.pos, int(out.pos_bytes)), "neg": C.string_at(out.neg, int(out.neg_bytes)),
+                "pos_records": int(out.pos_records), "neg_records": int(out.neg_records), "left": left}
+
+    def last_format_ms(self) -> Tuple[float, float, float]:
+        """Device milliseconds of the last format_text() under PFQ_FMT_TIME=1: (ids and blocks, sizes and scans, emit)
+        (pfq_debug_last_format)."""
+        ms = (C.c_double * 3)()
+        _ffi.check(_ffi.lib().pfq_debug_last_format(self._h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     # ---- read preprocessing
     PREP_REASONS = ("kept", "short", "n", "complexity", "mate")
 

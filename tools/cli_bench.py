@@ -5,6 +5,7 @@ and from gzip.  Prints one JSON line per run.
 
     python tools/cli_bench.py [--reads 16000000] [--threads 1,4,16] [--threshold 1.0] [--block 100000] [--workdir /tmp/pfq_cli_bench]
     python tools/cli_bench.py --device-parse --repeats 3 --only counts --threads 4,16     (A/B of query --device-parse)
+    python tools/cli_bench.py --device-output --repeats 3 --only posneg --threads 16 --block 1000     (A/B of query --device-output)
 """
 import argparse
 import gzip
@@ -60,6 +61,8 @@ def main():
     ap.add_argument("--only", default="", help="'posneg': only the run with both outputs (environment variables reach the CLI); "
                     "'counts': only the counts-only runs")
     ap.add_argument("--device-parse", action="store_true", help="every counts-only run is followed by the same run with query --device-parse")
+    ap.add_argument("--device-output", action="store_true", help="--only posneg: every run is followed by the same run with query --device-output "
+                    "(needs --block of at most 8192)")
     ap.add_argument("--repeats", type=int, default=1, help="how often the counts-only runs (alternating with --device-parse) are repeated")
     ap.add_argument("--devices", default="", help="comma-separated device lists to run as well, ';'-separated (e.g. '0,0' = two replicas on GPU 0)")
     ap.add_argument("--shard-depth", default="", help="the --devices runs split the database into the subtree shards of this depth "
@@ -109,7 +112,7 @@ def main():
         ingest = [l for l in p.stderr.splitlines() if l.startswith("ingest:")]
         outl = [l for l in p.stderr.splitlines() if l.startswith("output:")]
         cpul = [l for l in p.stderr.splitlines() if l.startswith("cpu:")]
-        devl = [l for l in p.stderr.splitlines() if l.startswith("device parse:")]
+        devl = [l for l in p.stderr.splitlines() if l.startswith("device parse:") or l.startswith("device output:")]
         csv = open(os.path.join(out, "CLASSIFICATION.csv")).read().splitlines()
         print(json.dumps({"run": label, "threads": threads, "reads": n_reads, "whole_process_s": round(wall, 3),
                           "whole_process_reads_per_s": round(n_reads / wall), "query_loop": loop[0] if loop else None,
@@ -117,8 +120,10 @@ def main():
 
     tmax = max(int(x) for x in a.threads.split(","))
     if a.only == "posneg":
-        for rep in range(2):
+        for rep in range(max(2, a.repeats)):
             run("fastq pos+neg output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter"))
+            if a.device_output:
+                run("fastq pos+neg output --device-output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter", "--device-output"))
         shutil.rmtree(a.workdir, ignore_errors=True)
         return
     for t in [int(x) for x in a.threads.split(",")]:
