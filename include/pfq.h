@@ -681,6 +681,42 @@ int pfq_debug_prep_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /*
 /* measurements: device milliseconds of the last pfq_prep_reads with reads — ms[0] trim and mark, ms[1] the two scans, ms[2] offsets and gather */
 int pfq_debug_last_prep(pfq_tree *tree, double *ms);
 
+/* ---- adapters (pfq_tree_set_adapters, pfq_prep_last_adapters) ----
+ * A library whose inserts are shorter than the read length reads through into the 3' adapter; what follows the insert matches no
+ * genome.  While adapters are set on a tree, every pfq_prep_reads on it first cuts each read at the leftmost place an adapter
+ * matches.  Integers only; no indels.
+ * For a read s[0, L) and an adapter A[0, m), with min_overlap = O and max_error_percent = E:
+ *   at position p < L the overlap is o = min(m, L - p);
+ *   mm = the number of i < o with up(s[p + i]) != A[i], up(c) = c & 0xDF (a read base outside ACGT therefore always mismatches);
+ *   p matches iff o >= O and 100 mm <= E o;
+ *   cut = the smallest p that matches any adapter of the read's set, or L if none does;
+ *   which = the lowest index in the set of an adapter that matches at cut, or 0xff if none does.
+ * Steps 1 - 5 of "read preprocessing" then run exactly as written on the read cut to s[0, cut), q[0, cut): step 1's L in
+ * w = min(trim_window, L - b) is cut, and a read cut to nothing is an empty read.  begin and len stay relative to the original
+ * read; bases_in and the L of n_trimmed (kept reads with len < L) stay the original length, so an adapter-cut read that is kept
+ * counts as trimmed.  Hence, with adapters set, begin, len, reason, kept and the prepared CSR of a block equal those of the same
+ * call without adapters on the reads cut at cut.
+ * pfq_tree_set_adapters: set1 serves unpaired reads and first mates; set2 serves second mates (the odd reads of a call with
+ * PFQ_PREP_PAIRED), with n2 == 0 they use set1.  Letters ACGTacgt only (stored in upper case), every length m with O <= m <=
+ * PFQ_ADAPTER_LEN_MAX, at most PFQ_ADAPTER_MAX a set, O 1 .. 64, E 0 .. 50, n1 > 0 if n2 > 0; else PFQ_ERR_ARG, the message
+ * names the adapter.  n1 == 0 and n2 == 0 drops the state.  The state does not depend on the leaves: pfq_tree_prune and
+ * pfq_tree_insert keep it; pfq_tree_save stores nothing of it.  A sticky insertion error is returned as everywhere else.
+ * pfq_prep_last_adapters: what the adapter step of the last pfq_prep_reads found, before the mate rule; PFQ_ERR_STATE if there
+ * has been no prep yet or the last one ran without adapters.  pfq_prep_params, pfq_prep and the three values of
+ * pfq_debug_last_prep keep their meaning: ms[0] does not include the adapter kernels, which pfq_debug_last_adapters reports. */
+#define PFQ_ADAPTER_MAX 8        /* per set */
+#define PFQ_ADAPTER_LEN_MAX 64
+int pfq_tree_set_adapters(pfq_tree *tree, const char *const *set1, uint32_t n1, const char *const *set2, uint32_t n2,
+                          uint32_t min_overlap /* O: 1 .. 64 */, uint32_t max_error_percent /* E: 0 .. 50 */);
+typedef struct pfq_prep_adapters {
+    uint64_t n_reads, n_found, bases_cut;         /* of the last pfq_prep_reads: reads with cut < L, sum of L - cut; before the mate rule */
+    uint64_t found[2 * PFQ_ADAPTER_MAX];          /* reads per `which`: set1 at [0, 8), set2 at [8, 16) */
+    const uint32_t *cut; const uint8_t *which;    /* [n_reads], only after a call with PFQ_PREP_WANT_READS, else NULL; library-owned */
+} pfq_prep_adapters;
+int pfq_prep_last_adapters(pfq_tree *tree, pfq_prep_adapters *out);
+/* measurements: device milliseconds of the adapter kernels of the last pfq_prep_reads with reads (HIP events) */
+int pfq_debug_last_adapters(pfq_tree *tree, double *ms);
+
 /* ---- genome similarity ----
  * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one
  * geometry and one seed pair; for two filters the set bits and the shared set bits estimate how many k-mers each genome has and

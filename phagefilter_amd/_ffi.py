@@ -22,6 +22,7 @@ SYMBOLS = [
     "pfq_query_frames", "pfq_query_frames_device",
     "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr", "pfq_text_format", "pfq_debug_last_format",
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
+    "pfq_tree_set_adapters", "pfq_prep_last_adapters", "pfq_debug_last_adapters",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
@@ -138,6 +139,14 @@ class Prep(C.Structure):
                 ("kept", C.POINTER(C.c_uint32))]
 
 
+ADAPTER_MAX, ADAPTER_LEN_MAX, ADAPTER_NONE = 8, 64, 0xFF
+
+
+class PrepAdapters(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_found", C.c_uint64), ("bases_cut", C.c_uint64), ("found", C.c_uint64 * (2 * ADAPTER_MAX)),
+                ("cut", C.POINTER(C.c_uint32)), ("which", C.POINTER(C.c_uint8))]
+
+
 class Similarity(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("shared_bits", C.POINTER(C.c_uint32)),
                 ("bits_a", C.POINTER(C.c_uint64)), ("bits_b", C.POINTER(C.c_uint64)),
@@ -248,6 +257,9 @@ def lib() -> C.CDLL:
     L.pfq_prep_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_prep_csr.argtypes = [vp, vp, vp]
     L.pfq_debug_last_prep.argtypes = [vp, C.POINTER(C.c_double)]
+    L.pfq_tree_set_adapters.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]
+    L.pfq_prep_last_adapters.argtypes = [vp, C.POINTER(PrepAdapters)]
+    L.pfq_debug_last_adapters.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
     L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.pfq_tree_recluster.argtypes = [vp, C.POINTER(vp)]

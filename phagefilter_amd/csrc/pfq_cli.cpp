@@ -952,6 +952,7 @@ struct Opt {
     const char *lng;
     char shrt;
     bool takes_value;
+    bool repeatable = false;  // given again, the values are joined with ','
 };
 Args parse(int argc, char **argv, int start, const std::vector<Opt> &opts) {
     Args a;
@@ -985,7 +986,8 @@ Args parse(int argc, char **argv, int start, const std::vector<Opt> &opts) {
                 if (i + 1 >= argc) die("error: a value is required for '--" + name + "'");
                 v = argv[++i];
             }
-            a.val[o->lng] = v;
+            if (o->repeatable && a.val.count(o->lng)) a.val[o->lng] += "," + v;
+            else a.val[o->lng] = v;
         } else if (s.size() >= 2 && s[0] == '-') {
             for (size_t j = 1; j < s.size(); ++j) {
                 char c = s[j];
@@ -1392,6 +1394,12 @@ struct PrepRun {
     pfq_prep_params params{0, 4, 0, 0, 0xffffffffu, 0, 0};
     std::atomic<uint64_t> reads{0}, kept{0}, trimmed{0}, bases{0}, bases_kept{0};
     std::atomic<uint64_t> reason[5] = {};
+    // --adapter / --adapter2: the sets every replica's tree carries (pfq_tree_set_adapters) and what the adapter step found
+    std::vector<std::string> adapters[2];
+    uint32_t adapter_overlap = 5, adapter_errors = 10;
+    std::atomic<uint64_t> adapter_reads{0}, adapter_bases{0};
+    std::atomic<uint64_t> adapter_found[2 * PFQ_ADAPTER_MAX] = {};
+    bool adapters_on() const { return !adapters[0].empty(); }
 };
 // What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending
 struct PrepKept {
@@ -1452,6 +1460,13 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         prep->bases += res.bases_in;
         prep->bases_kept += res.bases_kept;
         for (int c = 0; c < 5; ++c) prep->reason[c] += res.n_reason[c];
+        if (prep->adapters_on()) {
+            pfq_prep_adapters ad{};
+            if (pfq_prep_last_adapters(tree, &ad) != PFQ_OK) fail_from_thread(pfq_last_error());
+            prep->adapter_reads += ad.n_found;
+            prep->adapter_bases += ad.bases_cut;
+            for (int c = 0; c < 2 * PFQ_ADAPTER_MAX; ++c) prep->adapter_found[c] += ad.found[c];
+        }
         if (pk) {
             pk->begin.assign(res.begin, res.begin + res.n_reads);
             pk->len.assign(res.len, res.len + res.n_reads);
@@ -2601,7 +2616,8 @@ int cmd_query(int argc, char **argv) {
                              {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true},
                              {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
-                             {"min-complexity", 0, true}};
+                             {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
+                             {"adapter-errors", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2707,7 +2723,7 @@ int cmd_query(int argc, char **argv) {
         for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits"})
             if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
-                                  "min-complexity"})
+                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors"})
             if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         if (lca == 2) die("error: '--device-output' cannot be used with '--lca best': the best hits need every read's scores");
         if (!filtering) die("error: '--device-output' needs '--pos-filter' or '--neg-filter' (or both): they are the outputs it makes");
@@ -2756,7 +2772,8 @@ int cmd_query(int argc, char **argv) {
     // (pfq_prep_query); PREPROCESS.tsv holds the totals.  --min-length then defaults to the database's k.
     static PrepRun prep_run;
     const char *prep_first = nullptr;
-    for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity"})
+    for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2", "adapter-overlap",
+                             "adapter-errors"})
         if (a.val.count(name) && !prep_first) prep_first = name;
     if (prep_first) {
         prep_run.on = true;
@@ -2779,6 +2796,37 @@ int cmd_query(int argc, char **argv) {
         prep_run.params.min_length = a.val.count("min-length") ? number("min-length", "1", 1, 0xffffffffull, "at least 1 base (the default is the database's k)") : 0;
         prep_run.params.max_n = a.val.count("max-n") ? number("max-n", "0", 0, 0xfffffffeull, "a number of N bases") : 0xffffffffu;
         prep_run.params.min_complexity = number("min-complexity", "0", 0, 100, "a percentage from 0 (off) to 100");
+        // --adapter SEQ[,SEQ..] (reads and first mates), --adapter2 SEQ[,..] (second mates; without it they use --adapter's),
+        // --adapter-overlap O, --adapter-errors E: every read is cut at the leftmost place an adapter matches (pfq.h "adapters")
+        // before the steps above.  A SEQ is a sequence over ACGT or the name of a preset.
+        for (const char *name : {"adapter-overlap", "adapter-errors", "adapter2"})
+            if (a.val.count(name) && !a.val.count("adapter")) die(std::string("error: '--") + name + "' needs '--adapter <SEQ>'");
+        if (a.val.count("adapter2") && !a.val.count("reads2") && !a.flags.count("interleaved"))
+            die("error: '--adapter2' needs '--reads2 <FILE>' or '--interleaved': it serves the second mates");
+        prep_run.adapter_overlap = number("adapter-overlap", "5", 1, PFQ_ADAPTER_LEN_MAX, "an overlap of 1 to 64 bases");
+        prep_run.adapter_errors = number("adapter-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
+        static const std::pair<const char *, const char *> presets[] = {
+            {"illumina", "AGATCGGAAGAGC"}, {"nextera", "CTGTCTCTTATACACATCT"}, {"smallrna", "TGGAATTCTCGGGTGCCAAGG"}};
+        for (int set = 0; set < 2; ++set) {
+            const char *name = set ? "adapter2" : "adapter";
+            if (!a.val.count(name)) continue;
+            const std::string list = a.val.at(name) + ",";
+            for (size_t at = 0, end; (end = list.find(',', at)) != std::string::npos; at = end + 1) {
+                std::string seq = list.substr(at, end - at);
+                for (const auto &p : presets)
+                    if (seq == p.first) seq = p.second;
+                const std::string bad = "error: invalid value '" + list.substr(at, end - at) + "' for '--" + name + "': ";
+                for (char &ch : seq) {
+                    const char u = (char)(ch & 0xDF);
+                    if (u != 'A' && u != 'C' && u != 'G' && u != 'T') die(bad + "a sequence over ACGT or one of illumina, nextera, smallrna");
+                    ch = u;
+                }
+                if (seq.size() < prep_run.adapter_overlap || seq.size() > PFQ_ADAPTER_LEN_MAX)
+                    die(bad + "an adapter has from --adapter-overlap (" + std::to_string(prep_run.adapter_overlap) + ") to " + std::to_string(PFQ_ADAPTER_LEN_MAX) + " bases");
+                if (prep_run.adapters[set].size() == PFQ_ADAPTER_MAX) die(bad + "at most " + std::to_string(PFQ_ADAPTER_MAX) + " adapters per option");
+                prep_run.adapters[set].push_back(seq);
+            }
+        }
     }
     // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
     // (PFQ_WANT_HITS | PFQ_WANT_TAXA): TAXON_COUNTS.tsv; --taxon-reads: READ_TAXA.tsv, one line per record with hits.  The file is
@@ -2853,6 +2901,14 @@ int cmd_query(int argc, char **argv) {
         db.prune(depth);
     }
     if (sweep) db.set_sweep(sweep_thr);  // (before any read is classified: a database that is not superset-verified is refused here)
+    if (prep_run.adapters_on()) {  // every replica cuts the reads of its own calls
+        std::vector<const char *> sets[2];
+        for (int set = 0; set < 2; ++set)
+            for (const std::string &s : prep_run.adapters[set]) sets[set].push_back(s.c_str());
+        for (pfq_tree *tree : db.trees)
+            check(pfq_tree_set_adapters(tree, sets[0].data(), (uint32_t)sets[0].size(), sets[1].data(), (uint32_t)sets[1].size(), prep_run.adapter_overlap,
+                                        prep_run.adapter_errors));
+    }
     ReadQueue rq(reads, ov);
     std::unique_ptr<ReadQueue> rq2;
     if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
@@ -2937,12 +2993,22 @@ int cmd_query(int argc, char **argv) {
         FILE *f = fopen((out + "/PREPROCESS.tsv").c_str(), "wb");
         if (!f) die("cannot create PREPROCESS.tsv in " + out);
         for (const auto &row : rows) fprintf(f, "%s\t%s\n", row.first, row.second.c_str());
+        if (pr.adapters_on()) {  // behind the rows above: what the adapter step found, its parameters, the reads per adapter
+            fprintf(f, "adapter_reads\t%llu\nadapter_bases\t%llu\nadapter_overlap\t%u\nadapter_errors\t%u\n", (unsigned long long)pr.adapter_reads.load(),
+                    (unsigned long long)pr.adapter_bases.load(), pr.adapter_overlap, pr.adapter_errors);
+            for (int set = 0; set < 2; ++set)
+                for (size_t i = 0; i < pr.adapters[set].size(); ++i)
+                    fprintf(f, "adapter%d.%s\t%llu\n", set + 1, pr.adapters[set][i].c_str(), (unsigned long long)pr.adapter_found[set * PFQ_ADAPTER_MAX + i].load());
+        }
         if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
-        fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept\n",
+        fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept",
                 (unsigned long long)pr.reads.load(), (unsigned long long)pr.kept.load(), (unsigned long long)pr.trimmed.load(),
                 (unsigned long long)pr.reason[PFQ_PREP_SHORT].load(), (unsigned long long)pr.reason[PFQ_PREP_N].load(),
                 (unsigned long long)pr.reason[PFQ_PREP_COMPLEXITY].load(), (unsigned long long)pr.reason[PFQ_PREP_MATE].load(),
                 (unsigned long long)pr.bases_kept.load(), (unsigned long long)pr.bases.load());
+        if (pr.adapters_on())
+            fprintf(stderr, "; adapters cut from %llu reads (%llu bases)", (unsigned long long)pr.adapter_reads.load(), (unsigned long long)pr.adapter_bases.load());
+        fprintf(stderr, "\n");
     }
     db.close();
     printf("Finished.\n");
@@ -3479,6 +3545,16 @@ void usage() {
             "PREPROCESS.tsv in --out adds \"key<TAB>value\" lines: reads, reads_kept, reads_trimmed, dropped_short, dropped_n,\n"
             "dropped_complexity, dropped_mate, bases, bases_kept, then the parameters in force; the totals are also printed on stderr.\n"
             "Works with every other output, with pairs and with --devices.  Not with --device-parse, --frame or --shard-depth\n"
+            "--adapter <SEQ[,SEQ..]> [--adapter2 <SEQ[,SEQ..]>] [--adapter-overlap <O>] [--adapter-errors <E>]: a library whose inserts are\n"
+            "shorter than its reads reads through into the 3' adapter, and such a read matches no genome; these cut every read, on the GPU\n"
+            "and before the steps above, at the leftmost place where an adapter matches over at least O bases (default 5; at the read's\n"
+            "end a part of the adapter is enough) with at most E percent mismatches (default 10; no insertions or deletions).  --adapter\n"
+            "serves reads and first mates, --adapter2 second mates (needs --reads2 or --interleaved; without it they use --adapter's); both\n"
+            "may be repeated, up to 8 adapters of O to 64 bases each.  A SEQ is a sequence over ACGT or a name: illumina\n"
+            "(AGATCGGAAGAGC), nextera (CTGTCTCTTATACACATCT), smallrna (TGGAATTCTCGGGTGCCAAGG).  They turn the preprocessing above on\n"
+            "(--min-length defaults to k) and are refused where it is, and with --device-output.  PREPROCESS.tsv then also holds\n"
+            "adapter_reads, adapter_bases, adapter_overlap, adapter_errors and one adapter1.<SEQ> / adapter2.<SEQ> line with the reads cut\n"
+            "by each adapter; a read cut by an adapter and kept counts in reads_trimmed\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

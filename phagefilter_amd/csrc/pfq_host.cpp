@@ -473,6 +473,18 @@ struct pfq_tree {
     int pp_slot = 0;
     uint64_t pp_kept = 0, pp_bases = 0;
     std::vector<uint32_t> out_pp_begin, out_pp_len, out_pp_reason, out_pp_kept;
+    // pfq_tree_set_adapters: the sets as the kernel takes them (ad_on: any is set) and what the adapter step of the last
+    // pfq_prep_reads left: cut and which per read (scratch of one call, as d_pp_begin), the totals (h_pp_tot behind the kept
+    // reads), the host copies of a PFQ_PREP_WANT_READS call.  ad_last: the last prep ran with adapters.
+    bool ad_on = false, ad_last = false, ad_last_reads = false, ad_timed = false;
+    pfq::AdaptSet ad_set{};
+    DevBuf<uint32_t> d_pp_cut;
+    DevBuf<uint8_t> d_pp_which;
+    DevBuf<unsigned long long> d_pp_atot;
+    hipEvent_t ad_time[2] = {nullptr, nullptr};  // pfq_debug_last_adapters
+    pfq_prep_adapters ad_out{};
+    std::vector<uint32_t> out_pp_cut;
+    std::vector<uint8_t> out_pp_which;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3392,6 +3404,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_pp_in.bytes() + t.d_pp_qual.bytes() + t.d_pp_hq.bytes() + t.d_pp_seq[0].bytes() + t.d_pp_seq[1].bytes() + t.d_pp_inoff.bytes() +  // (pfq_prep_reads)
                         t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
+                        t.d_pp_cut.bytes() + t.d_pp_which.bytes() + t.d_pp_atot.bytes() +  // (the adapter step)
                         t.d_fm_idb.bytes() + t.d_fm_idl.bytes() + t.d_fm_len[0].bytes() + t.d_fm_len[1].bytes() + t.d_fm_long.bytes() +  // (pfq_text_format)
                         t.d_fm_name_off.bytes() + t.d_fm_hash.bytes() + t.d_fm_dst[0].bytes() + t.d_fm_dst[1].bytes() + t.d_fm_sums.bytes() +
                         t.d_fm_small.bytes() + t.d_fm_names.bytes() + t.d_fm_out[0].bytes() + t.d_fm_out[1].bytes();
@@ -3447,6 +3460,8 @@ void pfq_tree_close(pfq_tree *tree) {
     for (auto e : tree->pp_free)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->pp_time)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->ad_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->fm_time)
         if (e) (void)hipEventDestroy(e);
@@ -3908,9 +3923,12 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         HIP_TRY(hipEventCreateWithFlags(&t.pp_ready, hipEventDisableTiming));
         for (auto &e : t.pp_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         for (auto &e : t.pp_time) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1) * 8, hipHostMallocDefault));
+        for (auto &e : t.ad_time) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N) * 8, hipHostMallocDefault));
         HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
     }
+    const bool adapters = t.ad_on;
+    t.ad_last = false;
     hipStream_t st = t.copy_stream;
     const int slot = t.pp_slot ^ 1;
     if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));  // the classification that read this set is done
@@ -3961,6 +3979,25 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         a.kept = t.d_pp_kept.p;
         a.csr_off = t.d_pp_off[slot].p;
         a.out = t.d_pp_seq[slot].p;
+        if (adapters) {  // cut[] first: the steps below then see every read cut there
+            HIP_TRY(t.d_pp_cut.ensure(n_reads));
+            HIP_TRY(t.d_pp_which.ensure(n_reads));
+            HIP_TRY(t.d_pp_atot.ensure(pfq::ADAPT_TOT_N));
+            HIP_TRY(hipMemsetAsync(t.d_pp_atot.p, 0, pfq::ADAPT_TOT_N * 8, st));
+            pfq::AdaptArgs ad{};
+            ad.seq = a.seq;
+            ad.off = a.off;
+            ad.n_reads = n_reads;
+            ad.paired = a.paired;
+            ad.cut = t.d_pp_cut.p;
+            ad.which = t.d_pp_which.p;
+            ad.totals = t.d_pp_atot.p;
+            ad.set = t.ad_set;
+            HIP_TRY(hipEventRecord(t.ad_time[0], st));
+            pfq::launch_prep_adapter(ad, st);
+            HIP_TRY(hipEventRecord(t.ad_time[1], st));
+            a.cut = t.d_pp_cut.p;
+        }
         HIP_TRY(hipEventRecord(t.pp_time[0], st));
         pfq::launch_prep_trim(a, st);
         pfq::launch_prep_mark(a, st);
@@ -3973,8 +4010,10 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(t.h_pp_tot, t.d_pp_tot.p, pfq::PREP_TOT_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        if (adapters) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1, t.d_pp_atot.p, pfq::ADAPT_TOT_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffers are free from here)
         t.pp_timed = true;
+        t.ad_timed = adapters;
         if (t.h_pp_tot[pfq::PREP_TOT_ERR])
             return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: a read of 2^32 bases or more (or offsets that do not ascend)");
         n_kept = t.h_pp_tot[pfq::PREP_TOT_N];
@@ -3995,6 +4034,24 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             HIP_TRY(hipMemcpyAsync(t.out_pp_reason.data(), t.d_pp_reason.p, n_reads * 4, hipMemcpyDeviceToHost, st));
         }
         if (n_kept) HIP_TRY(hipMemcpyAsync(t.out_pp_kept.data(), t.d_pp_kept.p, n_kept * 4, hipMemcpyDeviceToHost, st));
+        if (adapters) {
+            t.out_pp_cut.resize(std::max<uint64_t>(n_reads, 1));
+            t.out_pp_which.resize(std::max<uint64_t>(n_reads, 1));
+            if (n_reads) {
+                HIP_TRY(hipMemcpyAsync(t.out_pp_cut.data(), t.d_pp_cut.p, n_reads * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(t.out_pp_which.data(), t.d_pp_which.p, n_reads, hipMemcpyDeviceToHost, st));
+            }
+        }
+    }
+    if (adapters) {
+        t.ad_out = pfq_prep_adapters{};
+        t.ad_out.n_reads = n_reads;
+        if (n_reads) {
+            const unsigned long long *at = t.h_pp_tot + pfq::PREP_TOT_N + 1;
+            t.ad_out.n_found = at[pfq::ADAPT_TOT_FOUND];
+            t.ad_out.bases_cut = at[pfq::ADAPT_TOT_BASES];
+            for (uint32_t i = 0; i < 2 * PFQ_ADAPTER_MAX; ++i) t.ad_out.found[i] = at[pfq::ADAPT_TOT_WHICH + i];
+        }
     }
     HIP_TRY(hipEventRecord(t.pp_ready, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4009,6 +4066,80 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     t.pp_bases = out->bases_kept;
     t.pp_paired = paired;
     t.pp_have = true;
+    t.ad_last = adapters;
+    t.ad_last_reads = adapters && want_reads;
+    return PFQ_OK;
+}
+
+// ---- adapters ----------------------------------------------------------------------------------------------------------------
+
+int pfq_tree_set_adapters(pfq_tree *tree, const char *const *set1, uint32_t n1, const char *const *set2, uint32_t n2, uint32_t min_overlap,
+                          uint32_t max_error_percent) {
+    if (!tree || (n1 && !set1) || (n2 && !set2)) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(insertion_error(*tree));
+    pfq_tree &t = *tree;
+    if (n1 == 0 && n2 == 0) {
+        t.ad_on = false;
+        t.ad_set = pfq::AdaptSet{};
+        return PFQ_OK;
+    }
+    if (n1 == 0) return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: set 2 has " + std::to_string(n2) + " adapters but set 1 is empty (second mates fall back to set 1, not the reverse)");
+    if (min_overlap < 1 || min_overlap > PFQ_ADAPTER_LEN_MAX)
+        return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: min_overlap must be 1 .. " + std::to_string(PFQ_ADAPTER_LEN_MAX) + ", not " + std::to_string(min_overlap));
+    if (max_error_percent > 50) return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: max_error_percent must be 0 .. 50, not " + std::to_string(max_error_percent));
+    pfq::AdaptSet s{};
+    s.min_overlap = min_overlap;
+    s.max_error_percent = max_error_percent;
+    const char *const *sets[2] = {set1, set2};
+    const uint32_t ns[2] = {n1, n2};
+    for (uint32_t k = 0; k < 2; ++k) {
+        const std::string set_name = "set " + std::to_string(k + 1);
+        if (ns[k] > PFQ_ADAPTER_MAX)
+            return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: " + set_name + " has " + std::to_string(ns[k]) + " adapters, at most " + std::to_string(PFQ_ADAPTER_MAX));
+        s.n[k] = ns[k];
+        for (uint32_t i = 0; i < ns[k]; ++i) {
+            const std::string name = "adapter " + std::to_string(i) + " of " + set_name;
+            const char *seq = sets[k][i];
+            if (!seq) return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: " + name + " is NULL");
+            const size_t m = strnlen(seq, PFQ_ADAPTER_LEN_MAX + 1);
+            const std::string shown = " '" + std::string(seq, std::min<size_t>(m, PFQ_ADAPTER_LEN_MAX)) + (m > PFQ_ADAPTER_LEN_MAX ? "..." : "") + "'";
+            if (m < min_overlap || m > PFQ_ADAPTER_LEN_MAX)
+                return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: " + name + shown + " must have min_overlap = " + std::to_string(min_overlap) + " .. " +
+                                             std::to_string(PFQ_ADAPTER_LEN_MAX) + " bases");
+            const uint32_t at = k * pfq::ADAPT_MAX + i;
+            s.len[at] = (uint8_t)m;
+            for (size_t j = 0; j < m; ++j) {
+                const uint32_t u = (uint8_t)seq[j] & 0xDFu;
+                if (u != 'A' && u != 'C' && u != 'G' && u != 'T')
+                    return fail(PFQ_ERR_ARG, "pfq_tree_set_adapters: " + name + shown + " has a letter other than ACGT at position " + std::to_string(j));
+                s.code[at][j >> 4] |= ((u >> 1) & 3u) << (2u * (j & 15u));
+            }
+        }
+    }
+    t.ad_set = s;
+    t.ad_on = true;
+    return PFQ_OK;
+}
+
+int pfq_prep_last_adapters(pfq_tree *tree, pfq_prep_adapters *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_prep_last_adapters before a pfq_prep_reads on this tree");
+    if (!tree->ad_last) return fail(PFQ_ERR_STATE, "pfq_prep_last_adapters: the last pfq_prep_reads on this tree ran without adapters (pfq_tree_set_adapters)");
+    *out = tree->ad_out;
+    if (tree->ad_last_reads) {
+        out->cut = tree->out_pp_cut.data();
+        out->which = tree->out_pp_which.data();
+    }
+    return PFQ_OK;
+}
+
+int pfq_debug_last_adapters(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_timed || !tree->ad_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_adapters: the last pfq_prep_reads with reads on this tree ran without adapters");
+    PFQ_TRY(use_device(tree->device));
+    float v = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&v, tree->ad_time[0], tree->ad_time[1]));
+    *ms = v;
     return PFQ_OK;
 }
 

@@ -748,7 +748,29 @@ struct PrepArgs {
     uint32_t *kept;                          // [n_kept]
     uint64_t *csr_off;                       // [n_kept + 1]
     uint8_t *out;
+    const uint32_t *cut;                     // [n_reads] of launch_prep_adapter: read r is s[0, min(L, cut[r])); nullptr: no adapters
 };
+// The adapter step (pfq_adapt.hip; the rule is pfq.h "adapters"): cut and which [n_reads], totals[0 .. ADAPT_TOT_N) += the
+// call's (zeroed by the caller).  An adapter is 4 words of 2-bit codes, base i at bits 2i, 2i + 1 of word i / 16, code
+// (letter >> 1) & 3; set 1 at [0, ADAPT_MAX), set 2 (odd reads of a paired call, if it has any) at [ADAPT_MAX, 2 ADAPT_MAX).
+constexpr uint32_t ADAPT_MAX = 8, ADAPT_LEN_MAX = 64;  // = PFQ_ADAPTER_* of pfq.h
+enum AdaptTotal { ADAPT_TOT_FOUND = 0, ADAPT_TOT_BASES = 1, ADAPT_TOT_WHICH = 2 /* .. 17 */, ADAPT_TOT_N = 18 };
+struct AdaptSet {
+    uint32_t n[2], min_overlap, max_error_percent;
+    uint8_t len[2 * ADAPT_MAX];
+    uint32_t code[2 * ADAPT_MAX][4];
+};
+struct AdaptArgs {
+    const uint8_t *seq;                      // as PrepArgs
+    const uint64_t *off;
+    uint64_t n_reads;
+    uint32_t paired;
+    uint32_t *cut;                           // [n_reads]
+    uint8_t *which;                          // [n_reads]
+    unsigned long long *totals;              // [ADAPT_TOT_N]
+    AdaptSet set;
+};
+void launch_prep_adapter(const AdaptArgs &a, hipStream_t st);
 void launch_prep_trim(const PrepArgs &a, hipStream_t st);
 void launch_prep_mark(const PrepArgs &a, hipStream_t st);
 void launch_prep_gather(const PrepArgs &a, hipStream_t st);

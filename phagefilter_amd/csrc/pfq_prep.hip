@@ -20,102 +20,11 @@
 // The later passes look again at bytes the quality pass has just read and take the L2 hit (see DESIGN: a 150-base read is one
 // piece of one group, so what is re-read is a line or two that another lane of the same wave loaded microseconds ago; keeping
 // the pieces in LDS would cost 16 bytes a lane of LDS per buffer for every length, to save those hits).
-#include "pfq_kernels.h"
-
-#include <algorithm>
+// Grp<G>, load_chunk and for_lengths are in pfq_prep_groups.h, shared with the adapter step (pfq_adapt.hip), which runs first
+// when adapters are set and leaves cut[]: the read is then s[0, cut).
+#include "pfq_prep_groups.h"
 
 namespace pfq {
-
-constexpr uint32_t NONE = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t up(uint32_t c) { return c & 0xDFu; }
-__device__ __forceinline__ bool is_n(uint32_t u) { return !(u == 'A' || u == 'C' || u == 'G' || u == 'T'); }
-
-// A group of G lanes: 16 or 64 (part of a wave: shuffles of width G) or 256 (the block: wave shuffles, four words of LDS and
-// two barriers; every thread of the block must then arrive).
-template <int G>
-struct Grp {
-    static constexpr uint32_t PIECE = G * 16u;
-    __device__ static __forceinline__ uint32_t rank() { return G == 256 ? threadIdx.x : (threadIdx.x & (uint32_t)(G - 1)); }
-    template <typename Op>
-    __device__ static __forceinline__ uint32_t reduce(uint32_t v, uint32_t *s_x, Op op) {
-        constexpr int W = G < 64 ? G : 64;
-#pragma unroll
-        for (int d = W / 2; d > 0; d >>= 1) v = op(v, (uint32_t)__shfl_xor((int)v, d, W));
-        if (G == 256) {
-            if (lane_id() == 0) s_x[threadIdx.x >> 6] = v;
-            __syncthreads();
-            v = op(op(s_x[0], s_x[1]), op(s_x[2], s_x[3]));
-            __syncthreads();
-        }
-        return v;
-    }
-    __device__ static __forceinline__ uint32_t gmin(uint32_t v, uint32_t *s_x) { return reduce(v, s_x, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
-    __device__ static __forceinline__ uint32_t gmax(uint32_t v, uint32_t *s_x) { return reduce(v, s_x, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); }
-    __device__ static __forceinline__ uint32_t gsum(uint32_t v, uint32_t *s_x) { return reduce(v, s_x, [](uint32_t a, uint32_t b) { return a + b; }); }
-    // inclusive scan over the group's lanes; total = the group's sum
-    __device__ static __forceinline__ uint32_t scan(uint32_t v, uint32_t &total, uint32_t *s_x) {
-        constexpr int W = G < 64 ? G : 64;
-        const uint32_t l = threadIdx.x & (uint32_t)(W - 1);
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < W; d <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, W);
-            if ((int)l >= d) incl += o;
-        }
-        total = (uint32_t)__shfl((int)incl, W - 1, W);
-        if (G == 256) {
-            const uint32_t wave = threadIdx.x >> 6;
-            if (lane_id() == 63) s_x[wave] = incl;
-            __syncthreads();
-            uint32_t before = 0, all = 0;
-            for (uint32_t w = 0; w < 4; ++w) {
-                if (w < wave) before += s_x[w];
-                all += s_x[w];
-            }
-            __syncthreads();
-            incl += before;
-            total = all;
-        }
-        return incl;
-    }
-    // between the group's stores to its ring and its loads from it (and back): the lanes of a wave run in step and LDS serves
-    // a wave in order, so inside a wave only the compiler has to keep the order
-    __device__ static __forceinline__ void ring_sync() {
-        if (G == 256) {
-            __syncthreads();
-        } else {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-    }
-};
-
-// The 16 aligned bytes at abase + x that belong to this lane (zero beyond the span: nothing is loaded there), and which of them
-// are bases of the read: byte k is base jb + k for lo <= k < hi.  abase is 16-byte aligned, sh = the read's first byte in it.
-struct Chunk {
-    uint32_t w[4];
-    uint32_t lo, hi;
-    int64_t jb;
-    __device__ __forceinline__ uint32_t byte(uint32_t k) const { return (w[k >> 2] >> (8u * (k & 3u))) & 0xffu; }
-    __device__ __forceinline__ uint32_t pos(uint32_t k) const { return (uint32_t)(jb + (int64_t)k); }
-};
-__device__ __forceinline__ Chunk load_chunk(const uint8_t *__restrict__ abase, uint64_t x, uint32_t sh, uint32_t L) {
-    Chunk c;
-    c.jb = (int64_t)x - (int64_t)sh;
-    const int64_t left = (int64_t)L - c.jb;  // bases at or behind byte 0
-    c.lo = c.jb < 0 ? (uint32_t)(-c.jb) : 0u;
-    c.hi = left <= 0 ? 0u : left >= 16 ? 16u : (uint32_t)left;
-    if (c.lo >= c.hi) {
-        c.lo = c.hi = 0;
-        c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
-    } else {
-        const uint4 v = *reinterpret_cast<const uint4 *>(abase + x);
-        c.w[0] = v.x, c.w[1] = v.y, c.w[2] = v.z, c.w[3] = v.w;
-    }
-    return c;
-}
 
 // One read, by the group: rank 0 leaves (begin, len, reason before the mate rule).  ring: the group's ring_mask + 1 words of LDS.
 template <int G>
@@ -261,55 +170,16 @@ __device__ __forceinline__ void prep_one(const PrepArgs &a, uint64_t r, uint64_t
     }
 }
 
-// f(i, off[i], length) by a whole group for every i < n whose length off[i + 1] - off[i] is in [lo, hi].  A block looks at
-// blockDim.x entries a trip, a thread each; the groups of a wave share the wave's 64 (G = 256: the block's 256).  Lengths of
-// 2^32 or more (or offsets that descend) belong to nobody; the build with lo == 0 reports them in *err.
-template <int G, typename F>
-__device__ __forceinline__ void for_lengths(const uint64_t *__restrict__ off, uint64_t n, uint32_t lo, uint32_t hi, unsigned long long *err, F f) {
-    __shared__ uint64_t s_mask[4];
-    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {  // (uniform in the block)
-        const uint64_t i = base + threadIdx.x;
-        bool mine = false;
-        if (i < n) {
-            const uint64_t len = off[i + 1] - off[i];
-            if (len >> 32) {
-                if (lo == 0 && err) atomicOr(err, 1ull);
-            } else {
-                mine = (uint32_t)len >= lo && (uint32_t)len <= hi;
-            }
-        }
-        uint64_t mask = ballot64(mine);
-        if (G == 256) {
-            if (lane_id() == 0) s_mask[threadIdx.x >> 6] = mask;
-            __syncthreads();
-            for (uint32_t w = 0; w < 4; ++w) {
-                uint64_t m = s_mask[w];
-                while (m) {
-                    const uint64_t j = base + w * 64u + (uint32_t)(__ffsll((unsigned long long)m) - 1);
-                    m &= m - 1;
-                    f(j, off[j], (uint32_t)(off[j + 1] - off[j]));
-                }
-            }
-            __syncthreads();
-        } else {
-            const uint64_t wave_base = base + (threadIdx.x & ~63u);
-            for (uint32_t bit = lane_id() / G; bit < 64u; bit += 64u / G) {
-                if (!((mask >> bit) & 1ull)) continue;
-                const uint64_t j = wave_base + bit;
-                f(j, off[j], (uint32_t)(off[j + 1] - off[j]));
-            }
-        }
-    }
-}
-
 extern __shared__ uint32_t s_prep_rings[];  // a ring per group of the block
 
-template <int G>
+// CUT: the adapter step ran first and read r is s[0, min(L, cut[r])).  A build of its own, chosen on the host, so that the
+// kernel without adapters stays the one it was.
+template <int G, bool CUT>
 __global__ void __launch_bounds__(256) k_prep_trim(PrepArgs a, uint32_t len_lo, uint32_t len_hi, uint32_t ring_words) {
     __shared__ uint32_t s_x[4];
     uint32_t *ring = s_prep_rings + (G == 256 ? 0u : (threadIdx.x / G) * ring_words);
     for_lengths<G>(a.off, a.n_reads, len_lo, len_hi, a.totals + PREP_TOT_ERR,
-                   [&](uint64_t r, uint64_t start, uint32_t L) { prep_one<G>(a, r, start, L, ring, ring_words - 1u, s_x); });
+                   [&](uint64_t r, uint64_t start, uint32_t L) { prep_one<G>(a, r, start, CUT ? min(L, a.cut[r]) : L, ring, ring_words - 1u, s_x); });
 }
 
 // A thread per unit (a read; PFQ_PREP_PAIRED: a fragment): the mate rule, keep and klen per read, the totals.
@@ -402,7 +272,6 @@ __global__ void __launch_bounds__(256) k_prep_gather(PrepArgs a, uint32_t len_lo
     });
 }
 
-static uint32_t prep_grid(uint64_t n, uint32_t per_block) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(PREP_GRID, (n + per_block - 1) / per_block)); }
 static uint32_t pow2_at_least(uint32_t v) {
     uint32_t p = 1;
     while (p < v) p <<= 1;
@@ -417,9 +286,15 @@ void launch_prep_trim(const PrepArgs &a, hipStream_t st) {
                    ring256 = pow2_at_least(256u * 16u + a.trim_window + 1u);
     const uint32_t t16 = std::max(64u, std::min(256u, (32768u / (ring16 * 4u)) * 16u / 64u * 64u)),
                    t64 = ring64 > 2048u ? 128u : 256u;
-    hipLaunchKernelGGL(k_prep_trim<16>, dim3(prep_grid(a.n_reads, t16)), dim3(t16), (t16 / 16u) * ring16 * 4u, st, a, 0u, PREP_SHORT_MAX, ring16);
-    hipLaunchKernelGGL(k_prep_trim<64>, dim3(prep_grid(a.n_reads, t64)), dim3(t64), (t64 / 64u) * ring64 * 4u, st, a, PREP_SHORT_MAX + 1u, PREP_WAVE_MAX, ring64);
-    hipLaunchKernelGGL(k_prep_trim<256>, dim3(prep_grid(a.n_reads, 256)), dim3(256), ring256 * 4u, st, a, PREP_WAVE_MAX + 1u, 0xffffffffu, ring256);
+    if (a.cut) {
+        hipLaunchKernelGGL((k_prep_trim<16, true>), dim3(prep_grid(a.n_reads, t16)), dim3(t16), (t16 / 16u) * ring16 * 4u, st, a, 0u, PREP_SHORT_MAX, ring16);
+        hipLaunchKernelGGL((k_prep_trim<64, true>), dim3(prep_grid(a.n_reads, t64)), dim3(t64), (t64 / 64u) * ring64 * 4u, st, a, PREP_SHORT_MAX + 1u, PREP_WAVE_MAX, ring64);
+        hipLaunchKernelGGL((k_prep_trim<256, true>), dim3(prep_grid(a.n_reads, 256)), dim3(256), ring256 * 4u, st, a, PREP_WAVE_MAX + 1u, 0xffffffffu, ring256);
+        return;
+    }
+    hipLaunchKernelGGL((k_prep_trim<16, false>), dim3(prep_grid(a.n_reads, t16)), dim3(t16), (t16 / 16u) * ring16 * 4u, st, a, 0u, PREP_SHORT_MAX, ring16);
+    hipLaunchKernelGGL((k_prep_trim<64, false>), dim3(prep_grid(a.n_reads, t64)), dim3(t64), (t64 / 64u) * ring64 * 4u, st, a, PREP_SHORT_MAX + 1u, PREP_WAVE_MAX, ring64);
+    hipLaunchKernelGGL((k_prep_trim<256, false>), dim3(prep_grid(a.n_reads, 256)), dim3(256), ring256 * 4u, st, a, PREP_WAVE_MAX + 1u, 0xffffffffu, ring256);
 }
 void launch_prep_mark(const PrepArgs &a, hipStream_t st) {
     if (!a.n_reads) return;

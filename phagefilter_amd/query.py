@@ -412,6 +412,42 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_last_prep(self._h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    def set_adapters(self, set1, set2=None, min_overlap: int = 5, max_error_percent: int = 10) -> None:
+        """3' adapters that every later prep_reads() cuts before its other steps (pfq_tree_set_adapters; the rule is pfq.h
+        "adapters"): each read ends at the leftmost position where an adapter of its set matches over at least `min_overlap`
+        bases with at most `max_error_percent` percent mismatches.  `set1`: sequences (str or bytes, ACGT) for unpaired reads and
+        first mates; `set2`: for second mates of a paired call (None or empty: they use `set1`).  An empty `set1`: no adapters."""
+        def strings(seqs):
+            seqs = list(seqs or ())
+            arr = (C.c_char_p * max(len(seqs), 1))()
+            for i, s in enumerate(seqs):
+                arr[i] = s.encode() if isinstance(s, str) else (None if s is None else bytes(s))
+            return arr, len(seqs)
+        a1, n1 = strings(set1)
+        a2, n2 = strings(set2)
+        _ffi.check(_ffi.lib().pfq_tree_set_adapters(self._h, a1, n1, a2, n2, min_overlap, max_error_percent))
+
+    def last_adapters(self) -> dict:
+        """What the adapter step of the last prep_reads() found, before the mate rule (pfq_prep_last_adapters): n_reads, n_found
+        (reads with cut < L), bases_cut, found (reads per adapter: set1 at [0, 8), set2 at [8, 16)) and, if that call had
+        want_reads, cut uint32[n_reads] and which uint8[n_reads] (0xff: no adapter), else None for both."""
+        out = _ffi.PrepAdapters()
+        _ffi.check(_ffi.lib().pfq_prep_last_adapters(self._h, C.byref(out)))
+        n = int(out.n_reads)
+
+        def arr(p, dtype):
+            if not p:
+                return None
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=dtype)
+        return {"n_reads": n, "n_found": int(out.n_found), "bases_cut": int(out.bases_cut), "found": [int(v) for v in out.found],
+                "cut": arr(out.cut, np.uint32), "which": arr(out.which, np.uint8)}
+
+    def last_adapters_ms(self) -> float:
+        """Device milliseconds of the adapter kernels of the last prep_reads() (pfq_debug_last_adapters)."""
+        ms = C.c_double()
+        _ffi.check(_ffi.lib().pfq_debug_last_adapters(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def query_prep(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
                    pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
                    best: bool = False, sweep: bool = False):
