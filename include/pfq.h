@@ -717,6 +717,50 @@ int pfq_prep_last_adapters(pfq_tree *tree, pfq_prep_adapters *out);
 /* measurements: device milliseconds of the adapter kernels of the last pfq_prep_reads with reads (HIP events) */
 int pfq_debug_last_adapters(pfq_tree *tree, double *ms);
 
+/* ---- mate overlap (pfq_tree_set_mate_overlap, pfq_prep_last_overlap) ----
+ * When the insert of a paired-end fragment is shorter than its reads, the two mates are reverse complements of each other over
+ * the whole insert, and everything behind the insert is adapter, whatever its sequence.  While the overlap is set on a tree,
+ * every pfq_prep_reads with PFQ_PREP_PAIRED on it finds each fragment's insert length from its mates and cuts both mates there.
+ * Integers only; no indels.
+ * A fragment is reads 2i (mate 1, a[0, L1)) and 2i + 1 (mate 2, b[0, L2)).  up(c) = c & 0xDF; comp maps A <-> T and C <-> G on
+ * upper-cased letters; a base outside ACGT on either side always mismatches.  min_overlap = O, max_error_percent = E.
+ * The hypothesis "the insert has I bases" compares the pairs (i, j = I - 1 - i) with 0 <= i < L1 and 0 <= j < L2, that is i in
+ * [max(0, I - L2), min(I, L1)):
+ *   o(I) = the number of such pairs;
+ *   mm(I) = the pairs with up(a[i]) != comp(up(b[j])), or with either base outside ACGT;
+ *   I matches iff o(I) >= O and 100 mm(I) <= E o(I);
+ *   insert = the LARGEST matching I in [O, L1 + L2 - O], or PFQ_NO_INSERT if none matches; mismatches = mm(insert) (0 if none).
+ * The largest I cuts least: poly-A mates or a tandem repeat, which match at many I, get the longest insert and lose nothing.
+ * With an insert found, ocut(mate 1) = min(L1, insert) and ocut(mate 2) = min(L2, insert); otherwise ocut = L1 and L2.  An insert
+ * at or above max(L1, L2) is reported and cuts nothing.
+ * A fragment with a mate longer than PFQ_OVERLAP_LEN_MAX is not analysed: it counts as n_skipped and gets no insert and no cut.
+ * With adapters set too, both steps look at the original reads, independently, and steps 1 - 5 of "read preprocessing" run on
+ * s[0, min(cut, ocut)), cut being the adapter step's; pfq_prep_last_adapters reports exactly what it reports without the overlap.
+ * begin, len, bases_in and n_trimmed keep the conventions of "adapters": relative to the original read, and a read that is cut and
+ * kept counts as trimmed.  Hence, with the overlap set, begin, len, reason, kept and the prepared CSR of a block equal those of
+ * the same call without it on the reads cut at min(cut, ocut).
+ * pfq_tree_set_mate_overlap: O 1 .. PFQ_OVERLAP_LEN_MAX (0 drops the state, E is then ignored), E 0 .. 50; else PFQ_ERR_ARG, the
+ * message names the parameter.  The state does not depend on the leaves: pfq_tree_prune and pfq_tree_insert keep it;
+ * pfq_tree_save stores nothing of it.  A sticky insertion error is returned as everywhere else.
+ * A pfq_prep_reads without PFQ_PREP_PAIRED does not run the step.
+ * pfq_prep_last_overlap: what the step of the last pfq_prep_reads found, before the mate rule; PFQ_ERR_STATE if there has been no
+ * prep yet or the last one ran without the step.  n_fragments = n_analysed + n_skipped; n_readthrough: insert < max(L1, L2);
+ * reads_cut and bases_cut: the reads with ocut < L and the sum of L - ocut, by ocut alone; hist[I] = the fragments of this call
+ * with insert I.  ms[0] of pfq_debug_last_prep does not include the overlap kernel, which pfq_debug_last_overlap reports. */
+#define PFQ_OVERLAP_LEN_MAX 512
+#define PFQ_OVERLAP_INSERT_MAX 1024
+#define PFQ_NO_INSERT 0xffffffffu
+int pfq_tree_set_mate_overlap(pfq_tree *tree, uint32_t min_overlap /* O: 0 off, else 1 .. 512 */, uint32_t max_error_percent /* E: 0 .. 50 */);
+typedef struct pfq_prep_overlap {
+    uint64_t n_fragments, n_analysed, n_skipped, n_overlapped /* insert found */, n_readthrough /* insert < max(L1, L2) */;
+    uint64_t reads_cut, bases_cut;            /* by ocut alone, before the mate rule */
+    const uint64_t *hist;                     /* [PFQ_OVERLAP_INSERT_MAX + 1] fragments per insert, of this call; library-owned */
+    const uint32_t *insert, *mismatches;      /* [n_fragments], only after a call with PFQ_PREP_WANT_READS, else NULL; library-owned */
+} pfq_prep_overlap;
+int pfq_prep_last_overlap(pfq_tree *tree, pfq_prep_overlap *out);
+/* measurements: device milliseconds of the overlap kernel of the last pfq_prep_reads with reads (HIP events) */
+int pfq_debug_last_overlap(pfq_tree *tree, double *ms);
+
 /* ---- genome similarity ----
  * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one
  * geometry and one seed pair; for two filters the set bits and the shared set bits estimate how many k-mers each genome has and

@@ -12,35 +12,6 @@
 
 namespace pfq {
 
-__device__ __forceinline__ void planes_of(const Chunk &c, uint32_t &code, uint32_t &nmask) {
-    code = nmask = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {  // four bases a step: bits 1, 2 of every byte, then the four pairs brought together
-        uint32_t t = (c.w[i] >> 1) & 0x03030303u;
-        t |= t >> 6;
-        code |= ((t & 0xfu) | ((t >> 12) & 0xf0u)) << (8u * i);
-    }
-    // not A C G T: v = up(c) ^ 'A' is 0, 2, 6 or 21 for the four letters; a byte of x is v's low five bits, and 32 more if
-    // v has bit 6 or 7 (bit 5 never: up() cleared it), so a table of 32 bits and x >> 5 decide
-    constexpr uint32_t NOT_LETTER = ~((1u << 0) | (1u << 2) | (1u << 6) | (1u << 21));
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t v = (c.w[i] & 0xDFDFDFDFu) ^ 0x41414141u;
-        const uint32_t x = (v & 0x1F1F1F1Fu) | ((((v | (v >> 1)) & 0x40404040u)) >> 1);
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t idx = (x >> (8u * j)) & 0x3fu;
-            nmask |= (((NOT_LETTER >> (idx & 31u)) | (idx >> 5)) & 1u) << (2u * (4u * i + j));
-        }
-    }
-}
-
-// The even bits of word w (bases 16 w .. 16 w + 15) that lie inside an overlap of o bases.
-__device__ __forceinline__ uint32_t overlap_mask(uint32_t o, uint32_t w) {
-    const uint32_t cnt = o > 16u * w ? min(o - 16u * w, 16u) : 0u;
-    return cnt >= 16u ? 0x55555555u : (0x55555555u & ((1u << (2u * cnt)) - 1u));
-}
-
 // One read, by the group: rank 0 leaves cut and which and adds to the block's totals.  p_code, p_n: the group's G + 4 words each.
 template <int G>
 __device__ __forceinline__ void adapt_one(const AdaptArgs &a, uint64_t r, uint64_t start, uint32_t L, uint32_t *p_code, uint32_t *p_n, uint32_t *s_x,

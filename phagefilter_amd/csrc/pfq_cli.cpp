@@ -1400,6 +1400,11 @@ struct PrepRun {
     std::atomic<uint64_t> adapter_reads{0}, adapter_bases{0};
     std::atomic<uint64_t> adapter_found[2 * PFQ_ADAPTER_MAX] = {};
     bool adapters_on() const { return !adapters[0].empty(); }
+    // --mate-overlap / --mate-overlap-errors: what every replica's tree is set to (pfq_tree_set_mate_overlap; 0: off), what the
+    // overlap step found and the fragments per insert length (INSERT_SIZES.tsv)
+    uint32_t mate_overlap = 0, mate_overlap_errors = 10;
+    std::atomic<uint64_t> overlap_fragments{0}, overlap_skipped{0}, overlap_found{0}, overlap_readthrough{0}, overlap_reads{0}, overlap_bases{0};
+    std::atomic<uint64_t> insert_hist[PFQ_OVERLAP_INSERT_MAX + 1] = {};
 };
 // What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending
 struct PrepKept {
@@ -1466,6 +1471,18 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
             prep->adapter_reads += ad.n_found;
             prep->adapter_bases += ad.bases_cut;
             for (int c = 0; c < 2 * PFQ_ADAPTER_MAX; ++c) prep->adapter_found[c] += ad.found[c];
+        }
+        if (prep->mate_overlap && (par.flags & PFQ_PREP_PAIRED)) {
+            pfq_prep_overlap ov{};
+            if (pfq_prep_last_overlap(tree, &ov) != PFQ_OK) fail_from_thread(pfq_last_error());
+            prep->overlap_fragments += ov.n_analysed;
+            prep->overlap_skipped += ov.n_skipped;
+            prep->overlap_found += ov.n_overlapped;
+            prep->overlap_readthrough += ov.n_readthrough;
+            prep->overlap_reads += ov.reads_cut;
+            prep->overlap_bases += ov.bases_cut;
+            for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
+                if (ov.hist[i]) prep->insert_hist[i] += ov.hist[i];
         }
         if (pk) {
             pk->begin.assign(res.begin, res.begin + res.n_reads);
@@ -2617,7 +2634,7 @@ int cmd_query(int argc, char **argv) {
                              {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
                              {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
-                             {"adapter-errors", 0, true}};
+                             {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2723,7 +2740,7 @@ int cmd_query(int argc, char **argv) {
         for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits"})
             if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
-                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors"})
+                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors"})
             if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         if (lca == 2) die("error: '--device-output' cannot be used with '--lca best': the best hits need every read's scores");
         if (!filtering) die("error: '--device-output' needs '--pos-filter' or '--neg-filter' (or both): they are the outputs it makes");
@@ -2773,7 +2790,7 @@ int cmd_query(int argc, char **argv) {
     static PrepRun prep_run;
     const char *prep_first = nullptr;
     for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2", "adapter-overlap",
-                             "adapter-errors"})
+                             "adapter-errors", "mate-overlap", "mate-overlap-errors"})
         if (a.val.count(name) && !prep_first) prep_first = name;
     if (prep_first) {
         prep_run.on = true;
@@ -2826,6 +2843,15 @@ int cmd_query(int argc, char **argv) {
                 if (prep_run.adapters[set].size() == PFQ_ADAPTER_MAX) die(bad + "at most " + std::to_string(PFQ_ADAPTER_MAX) + " adapters per option");
                 prep_run.adapters[set].push_back(seq);
             }
+        }
+        // --mate-overlap O [--mate-overlap-errors E]: both mates of a fragment are cut at the insert length that the overlap of
+        // the mates gives (pfq.h "mate overlap"), whatever the adapter's sequence; INSERT_SIZES.tsv counts the fragments per length
+        if (a.val.count("mate-overlap-errors") && !a.val.count("mate-overlap")) die("error: '--mate-overlap-errors' needs '--mate-overlap <O>'");
+        if (a.val.count("mate-overlap")) {
+            if (!a.val.count("reads2") && !a.flags.count("interleaved"))
+                die("error: '--mate-overlap' needs '--reads2 <FILE>' or '--interleaved': it compares the two mates of a fragment");
+            prep_run.mate_overlap = number("mate-overlap", "30", 1, PFQ_OVERLAP_LEN_MAX, "an overlap of 1 to 512 bases");
+            prep_run.mate_overlap_errors = number("mate-overlap-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
         }
     }
     // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
@@ -2909,6 +2935,8 @@ int cmd_query(int argc, char **argv) {
             check(pfq_tree_set_adapters(tree, sets[0].data(), (uint32_t)sets[0].size(), sets[1].data(), (uint32_t)sets[1].size(), prep_run.adapter_overlap,
                                         prep_run.adapter_errors));
     }
+    if (prep_run.mate_overlap)
+        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_overlap(tree, prep_run.mate_overlap, prep_run.mate_overlap_errors));
     ReadQueue rq(reads, ov);
     std::unique_ptr<ReadQueue> rq2;
     if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
@@ -3000,7 +3028,22 @@ int cmd_query(int argc, char **argv) {
                 for (size_t i = 0; i < pr.adapters[set].size(); ++i)
                     fprintf(f, "adapter%d.%s\t%llu\n", set + 1, pr.adapters[set][i].c_str(), (unsigned long long)pr.adapter_found[set * PFQ_ADAPTER_MAX + i].load());
         }
+        if (pr.mate_overlap) {  // behind the adapter rows: what the overlap step found and its parameters
+            fprintf(f, "overlap_fragments\t%llu\noverlap_skipped\t%llu\noverlap_found\t%llu\noverlap_readthrough\t%llu\noverlap_reads\t%llu\noverlap_bases\t%llu\n",
+                    (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_skipped.load(), (unsigned long long)pr.overlap_found.load(),
+                    (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(), (unsigned long long)pr.overlap_bases.load());
+            fprintf(f, "mate_overlap\t%u\nmate_overlap_errors\t%u\n", pr.mate_overlap, pr.mate_overlap_errors);
+        }
         if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
+        if (pr.mate_overlap) {
+            // INSERT_SIZES.tsv: the fragments per insert length, summed over all calls and replicas
+            FILE *g = fopen((out + "/INSERT_SIZES.tsv").c_str(), "wb");
+            if (!g) die("cannot create INSERT_SIZES.tsv in " + out);
+            fprintf(g, "insert\tfragments\n");
+            for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
+                if (pr.insert_hist[i].load()) fprintf(g, "%d\t%llu\n", i, (unsigned long long)pr.insert_hist[i].load());
+            if (fclose(g) != 0) die("short write to INSERT_SIZES.tsv");
+        }
         fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept",
                 (unsigned long long)pr.reads.load(), (unsigned long long)pr.kept.load(), (unsigned long long)pr.trimmed.load(),
                 (unsigned long long)pr.reason[PFQ_PREP_SHORT].load(), (unsigned long long)pr.reason[PFQ_PREP_N].load(),
@@ -3008,6 +3051,10 @@ int cmd_query(int argc, char **argv) {
                 (unsigned long long)pr.bases_kept.load(), (unsigned long long)pr.bases.load());
         if (pr.adapters_on())
             fprintf(stderr, "; adapters cut from %llu reads (%llu bases)", (unsigned long long)pr.adapter_reads.load(), (unsigned long long)pr.adapter_bases.load());
+        if (pr.mate_overlap)
+            fprintf(stderr, "; mates overlap in %llu of %llu fragments, %llu with read-through: %llu reads cut (%llu bases)", (unsigned long long)pr.overlap_found.load(),
+                    (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(),
+                    (unsigned long long)pr.overlap_bases.load());
         fprintf(stderr, "\n");
     }
     db.close();
@@ -3555,6 +3602,16 @@ void usage() {
             "(--min-length defaults to k) and are refused where it is, and with --device-output.  PREPROCESS.tsv then also holds\n"
             "adapter_reads, adapter_bases, adapter_overlap, adapter_errors and one adapter1.<SEQ> / adapter2.<SEQ> line with the reads cut\n"
             "by each adapter; a read cut by an adapter and kept counts in reads_trimmed\n"
+            "--mate-overlap <O> [--mate-overlap-errors <E>]: paired reads say where their adapters begin themselves: when the insert is\n"
+            "shorter than the reads, the mates are reverse complements of each other over the whole insert, and what follows is adapter,\n"
+            "whatever its sequence.  On the GPU and before the steps above, the insert of every fragment is the largest length at which the\n"
+            "mates overlap over at least O bases (1 to 512) with at most E percent mismatches (default 10; no insertions or deletions), and\n"
+            "both mates are cut there; a fragment with a mate of more than 512 bases is left alone.  Needs --reads2 or --interleaved.\n"
+            "Works with --adapter: each read is cut where the first of the two says.  Turns the preprocessing above on (--min-length\n"
+            "defaults to k) and is refused where it is, and with --device-output.  PREPROCESS.tsv then also holds overlap_fragments (the\n"
+            "fragments looked at), overlap_skipped, overlap_found, overlap_readthrough (insert shorter than a mate), overlap_reads,\n"
+            "overlap_bases (reads and bases cut), mate_overlap and mate_overlap_errors, and INSERT_SIZES.tsv in --out holds\n"
+            "\"insert<TAB>fragments\", one line per insert length found, ascending\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

@@ -485,6 +485,17 @@ struct pfq_tree {
     pfq_prep_adapters ad_out{};
     std::vector<uint32_t> out_pp_cut;
     std::vector<uint8_t> out_pp_which;
+    // pfq_tree_set_mate_overlap (ov_on) and what the overlap step of the last paired pfq_prep_reads left: insert and mismatches
+    // per fragment, the merged cut per read that the trim kernel takes (d_pp_ecut = min(adapter cut, ocut)), the totals and
+    // the histogram (h_pp_tot behind the adapter totals).  ov_last: the last prep ran the step.
+    bool ov_on = false, ov_last = false, ov_last_reads = false, ov_timed = false;
+    uint32_t ov_min_overlap = 0, ov_max_error_percent = 0;
+    DevBuf<uint32_t> d_pp_oins, d_pp_omm, d_pp_ecut;
+    DevBuf<unsigned long long> d_pp_otot;
+    hipEvent_t ov_time[2] = {nullptr, nullptr};  // pfq_debug_last_overlap
+    pfq_prep_overlap ov_out{};
+    std::vector<uint64_t> out_ov_hist;
+    std::vector<uint32_t> out_ov_insert, out_ov_mm;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3405,6 +3416,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
                         t.d_pp_cut.bytes() + t.d_pp_which.bytes() + t.d_pp_atot.bytes() +  // (the adapter step)
+                        t.d_pp_oins.bytes() + t.d_pp_omm.bytes() + t.d_pp_ecut.bytes() + t.d_pp_otot.bytes() +  // (the mate overlap step)
                         t.d_fm_idb.bytes() + t.d_fm_idl.bytes() + t.d_fm_len[0].bytes() + t.d_fm_len[1].bytes() + t.d_fm_long.bytes() +  // (pfq_text_format)
                         t.d_fm_name_off.bytes() + t.d_fm_hash.bytes() + t.d_fm_dst[0].bytes() + t.d_fm_dst[1].bytes() + t.d_fm_sums.bytes() +
                         t.d_fm_small.bytes() + t.d_fm_names.bytes() + t.d_fm_out[0].bytes() + t.d_fm_out[1].bytes();
@@ -3462,6 +3474,8 @@ void pfq_tree_close(pfq_tree *tree) {
     for (auto e : tree->pp_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->ad_time)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->ov_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->fm_time)
         if (e) (void)hipEventDestroy(e);
@@ -3912,6 +3926,8 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     if (pr.min_complexity > 100) return fail(PFQ_ERR_ARG, "pfq_prep_reads: min_complexity must be 0 (off) or 1 .. 100, not " + std::to_string(pr.min_complexity));
     const bool paired = (pr.flags & PFQ_PREP_PAIRED) != 0, want_reads = (pr.flags & PFQ_PREP_WANT_READS) != 0;
     if (paired && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PREP_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
+    const bool overlap = paired && tree->ov_on;  // (the mate overlap step needs mates)
+    constexpr size_t n_otot = pfq::OVL_TOT_N + pfq::OVL_HIST;
     if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: 2^31 - 1024 reads or more in one block: ask in pieces");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
@@ -3924,11 +3940,13 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         for (auto &e : t.pp_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         for (auto &e : t.pp_time) HIP_TRY(hipEventCreate(&e));
         for (auto &e : t.ad_time) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N) * 8, hipHostMallocDefault));
+        for (auto &e : t.ov_time) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N + pfq::OVL_TOT_N + pfq::OVL_HIST) * 8, hipHostMallocDefault));
         HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
     }
     const bool adapters = t.ad_on;
     t.ad_last = false;
+    t.ov_last = false;
     hipStream_t st = t.copy_stream;
     const int slot = t.pp_slot ^ 1;
     if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));  // the classification that read this set is done
@@ -3998,6 +4016,28 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             HIP_TRY(hipEventRecord(t.ad_time[1], st));
             a.cut = t.d_pp_cut.p;
         }
+        if (overlap) {  // behind the adapter step: the cut the steps below see is the smaller of the two
+            HIP_TRY(t.d_pp_oins.ensure(n_reads / 2));
+            HIP_TRY(t.d_pp_omm.ensure(n_reads / 2));
+            HIP_TRY(t.d_pp_ecut.ensure(n_reads));
+            HIP_TRY(t.d_pp_otot.ensure(n_otot));
+            HIP_TRY(hipMemsetAsync(t.d_pp_otot.p, 0, n_otot * 8, st));
+            pfq::OverlapArgs ov{};
+            ov.seq = a.seq;
+            ov.off = a.off;
+            ov.n_reads = n_reads;
+            ov.min_overlap = t.ov_min_overlap;
+            ov.max_error_percent = t.ov_max_error_percent;
+            ov.adapter_cut = adapters ? t.d_pp_cut.p : nullptr;
+            ov.insert = t.d_pp_oins.p;
+            ov.mismatches = t.d_pp_omm.p;
+            ov.cut = t.d_pp_ecut.p;
+            ov.totals = t.d_pp_otot.p;
+            HIP_TRY(hipEventRecord(t.ov_time[0], st));
+            pfq::launch_prep_overlap(ov, st);
+            HIP_TRY(hipEventRecord(t.ov_time[1], st));
+            a.cut = t.d_pp_ecut.p;
+        }
         HIP_TRY(hipEventRecord(t.pp_time[0], st));
         pfq::launch_prep_trim(a, st);
         pfq::launch_prep_mark(a, st);
@@ -4011,9 +4051,11 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         HIP_TRY(hipMemcpyAsync(t.h_pp_tot, t.d_pp_tot.p, pfq::PREP_TOT_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
         if (adapters) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1, t.d_pp_atot.p, pfq::ADAPT_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        if (overlap) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N, t.d_pp_otot.p, n_otot * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffers are free from here)
         t.pp_timed = true;
         t.ad_timed = adapters;
+        t.ov_timed = overlap;
         if (t.h_pp_tot[pfq::PREP_TOT_ERR])
             return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: a read of 2^32 bases or more (or offsets that do not ascend)");
         n_kept = t.h_pp_tot[pfq::PREP_TOT_N];
@@ -4043,6 +4085,29 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             }
         }
     }
+    if (overlap) {
+        if (want_reads) {
+            t.out_ov_insert.resize(std::max<uint64_t>(n_reads / 2, 1));
+            t.out_ov_mm.resize(std::max<uint64_t>(n_reads / 2, 1));
+            if (n_reads) {
+                HIP_TRY(hipMemcpyAsync(t.out_ov_insert.data(), t.d_pp_oins.p, n_reads / 2 * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(t.out_ov_mm.data(), t.d_pp_omm.p, n_reads / 2 * 4, hipMemcpyDeviceToHost, st));
+            }
+        }
+        t.ov_out = pfq_prep_overlap{};
+        t.ov_out.n_fragments = n_reads / 2;
+        t.out_ov_hist.assign(pfq::OVL_HIST, 0);
+        if (n_reads) {
+            const unsigned long long *ot = t.h_pp_tot + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N;
+            t.ov_out.n_analysed = ot[pfq::OVL_TOT_ANALYSED];
+            t.ov_out.n_skipped = ot[pfq::OVL_TOT_SKIPPED];
+            t.ov_out.n_overlapped = ot[pfq::OVL_TOT_FOUND];
+            t.ov_out.n_readthrough = ot[pfq::OVL_TOT_THROUGH];
+            t.ov_out.reads_cut = ot[pfq::OVL_TOT_READS];
+            t.ov_out.bases_cut = ot[pfq::OVL_TOT_BASES];
+            for (uint32_t i = 0; i < pfq::OVL_HIST; ++i) t.out_ov_hist[i] = ot[pfq::OVL_TOT_N + i];
+        }
+    }
     if (adapters) {
         t.ad_out = pfq_prep_adapters{};
         t.ad_out.n_reads = n_reads;
@@ -4068,6 +4133,8 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     t.pp_have = true;
     t.ad_last = adapters;
     t.ad_last_reads = adapters && want_reads;
+    t.ov_last = overlap;
+    t.ov_last_reads = overlap && want_reads;
     return PFQ_OK;
 }
 
@@ -4139,6 +4206,50 @@ int pfq_debug_last_adapters(pfq_tree *tree, double *ms) {
     PFQ_TRY(use_device(tree->device));
     float v = 0.0f;
     HIP_TRY(hipEventElapsedTime(&v, tree->ad_time[0], tree->ad_time[1]));
+    *ms = v;
+    return PFQ_OK;
+}
+
+// ---- mate overlap ------------------------------------------------------------------------------------------------------------
+
+int pfq_tree_set_mate_overlap(pfq_tree *tree, uint32_t min_overlap, uint32_t max_error_percent) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(insertion_error(*tree));
+    pfq_tree &t = *tree;
+    if (min_overlap == 0) {
+        t.ov_on = false;
+        t.ov_min_overlap = t.ov_max_error_percent = 0;
+        return PFQ_OK;
+    }
+    if (min_overlap > PFQ_OVERLAP_LEN_MAX)
+        return fail(PFQ_ERR_ARG, "pfq_tree_set_mate_overlap: min_overlap must be 0 (off) or 1 .. " + std::to_string(PFQ_OVERLAP_LEN_MAX) + ", not " + std::to_string(min_overlap));
+    if (max_error_percent > 50) return fail(PFQ_ERR_ARG, "pfq_tree_set_mate_overlap: max_error_percent must be 0 .. 50, not " + std::to_string(max_error_percent));
+    t.ov_min_overlap = min_overlap;
+    t.ov_max_error_percent = max_error_percent;
+    t.ov_on = true;
+    return PFQ_OK;
+}
+
+int pfq_prep_last_overlap(pfq_tree *tree, pfq_prep_overlap *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_prep_last_overlap before a pfq_prep_reads on this tree");
+    if (!tree->ov_last)
+        return fail(PFQ_ERR_STATE, "pfq_prep_last_overlap: the last pfq_prep_reads on this tree ran without the mate overlap (pfq_tree_set_mate_overlap and PFQ_PREP_PAIRED)");
+    *out = tree->ov_out;
+    out->hist = tree->out_ov_hist.data();
+    if (tree->ov_last_reads) {
+        out->insert = tree->out_ov_insert.data();
+        out->mismatches = tree->out_ov_mm.data();
+    }
+    return PFQ_OK;
+}
+
+int pfq_debug_last_overlap(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_timed || !tree->ov_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_overlap: the last pfq_prep_reads with reads on this tree ran without the mate overlap");
+    PFQ_TRY(use_device(tree->device));
+    float v = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&v, tree->ov_time[0], tree->ov_time[1]));
     *ms = v;
     return PFQ_OK;
 }

@@ -748,7 +748,7 @@ struct PrepArgs {
     uint32_t *kept;                          // [n_kept]
     uint64_t *csr_off;                       // [n_kept + 1]
     uint8_t *out;
-    const uint32_t *cut;                     // [n_reads] of launch_prep_adapter: read r is s[0, min(L, cut[r])); nullptr: no adapters
+    const uint32_t *cut;                     // [n_reads] of launch_prep_adapter or launch_prep_overlap: read r is s[0, min(L, cut[r])); nullptr: neither ran
 };
 // The adapter step (pfq_adapt.hip; the rule is pfq.h "adapters"): cut and which [n_reads], totals[0 .. ADAPT_TOT_N) += the
 // call's (zeroed by the caller).  An adapter is 4 words of 2-bit codes, base i at bits 2i, 2i + 1 of word i / 16, code
@@ -770,7 +770,24 @@ struct AdaptArgs {
     unsigned long long *totals;              // [ADAPT_TOT_N]
     AdaptSet set;
 };
+// The mate overlap step (pfq_overlap.hip; the rule is pfq.h "mate overlap"): a wave per fragment (reads 2f, 2f + 1).  insert and
+// mismatches [n_reads / 2]; cut [n_reads] = min(ocut, adapter_cut[r]) (adapter_cut nullptr: ocut), which launch_prep_trim then
+// takes as PrepArgs::cut; totals[0 .. OVL_TOT_N + OVL_HIST) += the call's (zeroed by the caller), the histogram of the inserts
+// behind the counters.  A fragment with a mate of more than OVL_LEN_MAX bases is skipped: no insert, cut = the adapter's or L.
+constexpr uint32_t OVL_LEN_MAX = 512, OVL_HIST = 2 * OVL_LEN_MAX + 1;  // = PFQ_OVERLAP_LEN_MAX, PFQ_OVERLAP_INSERT_MAX + 1 of pfq.h
+enum OvlTotal { OVL_TOT_ANALYSED = 0, OVL_TOT_SKIPPED = 1, OVL_TOT_FOUND = 2, OVL_TOT_THROUGH = 3, OVL_TOT_READS = 4, OVL_TOT_BASES = 5, OVL_TOT_N = 6 };
+struct OverlapArgs {
+    const uint8_t *seq;                      // as PrepArgs
+    const uint64_t *off;
+    uint64_t n_reads;                        // even
+    uint32_t min_overlap, max_error_percent;
+    const uint32_t *adapter_cut;             // [n_reads] of launch_prep_adapter, or nullptr
+    uint32_t *insert, *mismatches;           // [n_reads / 2]
+    uint32_t *cut;                           // [n_reads]
+    unsigned long long *totals;              // [OVL_TOT_N + OVL_HIST]
+};
 void launch_prep_adapter(const AdaptArgs &a, hipStream_t st);
+void launch_prep_overlap(const OverlapArgs &a, hipStream_t st);
 void launch_prep_trim(const PrepArgs &a, hipStream_t st);
 void launch_prep_mark(const PrepArgs &a, hipStream_t st);
 void launch_prep_gather(const PrepArgs &a, hipStream_t st);

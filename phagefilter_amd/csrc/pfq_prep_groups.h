@@ -1,4 +1,4 @@
-// pfq_prep_groups.h — what the per-read kernels of pfq_prep_reads share (pfq_prep.hip, pfq_adapt.hip): a group of G lanes that
+// pfq_prep_groups.h — what the per-read kernels of pfq_prep_reads share (pfq_prep.hip, pfq_adapt.hip, pfq_overlap.hip): a group of G lanes that
 // takes a read in pieces of 16 G bytes, 16 aligned bytes a lane, and the loop that hands the reads of a length range to groups.
 #pragma once
 #include "pfq_kernels.h"
@@ -96,6 +96,37 @@ __device__ __forceinline__ Chunk load_chunk(const uint8_t *__restrict__ abase, u
         c.w[0] = v.x, c.w[1] = v.y, c.w[2] = v.z, c.w[3] = v.w;
     }
     return c;
+}
+
+// The 2-bit planes of a lane's 16 bytes (pfq_adapt.hip, pfq_overlap.hip): code has (u >> 1) & 3 of the upper-cased byte k at bits
+// 2k, 2k + 1; nmask has bit 2k set where byte k is none of A C G T.
+__device__ __forceinline__ void planes_of(const Chunk &c, uint32_t &code, uint32_t &nmask) {
+    code = nmask = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {  // four bases a step: bits 1, 2 of every byte, then the four pairs brought together
+        uint32_t t = (c.w[i] >> 1) & 0x03030303u;
+        t |= t >> 6;
+        code |= ((t & 0xfu) | ((t >> 12) & 0xf0u)) << (8u * i);
+    }
+    // not A C G T: v = up(c) ^ 'A' is 0, 2, 6 or 21 for the four letters; a byte of x is v's low five bits, and 32 more if
+    // v has bit 6 or 7 (bit 5 never: up() cleared it), so a table of 32 bits and x >> 5 decide
+    constexpr uint32_t NOT_LETTER = ~((1u << 0) | (1u << 2) | (1u << 6) | (1u << 21));
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t v = (c.w[i] & 0xDFDFDFDFu) ^ 0x41414141u;
+        const uint32_t x = (v & 0x1F1F1F1Fu) | ((((v | (v >> 1)) & 0x40404040u)) >> 1);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t idx = (x >> (8u * j)) & 0x3fu;
+            nmask |= (((NOT_LETTER >> (idx & 31u)) | (idx >> 5)) & 1u) << (2u * (4u * i + j));
+        }
+    }
+}
+
+// The even bits of word w (bases 16 w .. 16 w + 15) that lie inside an overlap of o bases.
+__device__ __forceinline__ uint32_t overlap_mask(uint32_t o, uint32_t w) {
+    const uint32_t cnt = o > 16u * w ? min(o - 16u * w, 16u) : 0u;
+    return cnt >= 16u ? 0x55555555u : (0x55555555u & ((1u << (2u * cnt)) - 1u));
 }
 
 // f(i, off[i], length) by a whole group for every i < n whose length off[i + 1] - off[i] is in [lo, hi].  A block looks at

@@ -448,6 +448,37 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_last_adapters(self._h, C.byref(ms)))
         return float(ms.value)
 
+    OVERLAP_TOTALS = ("n_fragments", "n_analysed", "n_skipped", "n_overlapped", "n_readthrough", "reads_cut", "bases_cut")
+
+    def set_mate_overlap(self, min_overlap: int = 30, max_error_percent: int = 10) -> None:
+        """Every later prep_reads(paired=True) finds each fragment's insert length from the overlap of its mates and cuts both
+        mates there (pfq_tree_set_mate_overlap; the rule is pfq.h "mate overlap"): the largest insert at which the mates are
+        reverse complements over at least `min_overlap` bases with at most `max_error_percent` percent mismatches.
+        `min_overlap` 0 drops it."""
+        _ffi.check(_ffi.lib().pfq_tree_set_mate_overlap(self._h, min_overlap, max_error_percent))
+
+    def last_overlap(self) -> dict:
+        """What the mate overlap step of the last prep_reads() found, before the mate rule (pfq_prep_last_overlap): the totals
+        OVERLAP_TOTALS, hist uint64[1025] (fragments per insert length) and, if that call had want_reads, insert and mismatches
+        uint32[n_fragments] (insert 0xffffffff: none), else None for both."""
+        out = _ffi.PrepOverlap()
+        _ffi.check(_ffi.lib().pfq_prep_last_overlap(self._h, C.byref(out)))
+        n = int(out.n_fragments)
+
+        def arr(p):
+            if not p:
+                return None
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32)
+        res = {k: int(getattr(out, k)) for k in self.OVERLAP_TOTALS}
+        res.update(hist=np.ctypeslib.as_array(out.hist, shape=(_ffi.OVERLAP_INSERT_MAX + 1,)).copy(), insert=arr(out.insert), mismatches=arr(out.mismatches))
+        return res
+
+    def last_overlap_ms(self) -> float:
+        """Device milliseconds of the overlap kernel of the last prep_reads() (pfq_debug_last_overlap)."""
+        ms = C.c_double()
+        _ffi.check(_ffi.lib().pfq_debug_last_overlap(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def query_prep(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
                    pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
                    best: bool = False, sweep: bool = False):
