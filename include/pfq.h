@@ -199,7 +199,17 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
  * hit leaf l) is num_matches of query_passes (query.rs:38-49) on l's filter: how many of get_kmers(r) (canonical k-mers,
  * duplicates counted, file_parser.rs:114-148) have all num_hashes probed bits set (bloom_filter.rs:312-332), between
  * ceil(threshold * n_kmers) and n_kmers = max(len - k + 1, 0).  The hits themselves are those of the same call without
- * PFQ_WANT_SCORES.  Library-owned; valid until the next query call on the tree. */
+ * PFQ_WANT_SCORES.  Library-owned; valid until the next query call on the tree.
+ * "A query call", here and for pfq_last_lca, pfq_last_taxa, pfq_last_best_rows and pfq_text_format: every call of pfq_query_batch,
+ * pfq_query_batch_device, pfq_text_query, pfq_prep_query, pfq_query_frames and pfq_query_frames_device whose tree (for the frames
+ * calls also out, and for a non-empty block its buffers) is not NULL.  Such a call ends the validity of what the one before it
+ * left even when it is then refused: PFQ_ERR_ARG for a combination of flags, an odd PFQ_PAIRED block, PFQ_WANT_SWEEP above the
+ * list's lowest threshold or with PFQ_PAIRED, PFQ_PAIRED on a block prepared unpaired, frames flags other than 0; PFQ_ERR_STATE for
+ * PFQ_WANT_TAXA without a taxonomy, PFQ_WANT_SWEEP without a list, pfq_text_query before a parse, pfq_prep_query before a prep;
+ * PFQ_ERR_UNSUPPORTED for a flag a subtree shard refuses or an abundance log that is full.  No refused call changes a counter, log
+ * or sketch, except the one whose rows do not fit the abundance log: its other results stand (PFQ_WANT_ABUNDANCE).  Not query calls: pfq_text_parse, pfq_prep_reads,
+ * pfq_text_format, the resets, the settings, pfq_tree_insert and pfq_tree_prune; they leave these results readable as the call
+ * left them (clade and node indices then still number the tree and the taxonomy of that call). */
 int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits);
 
 /* ---- clades (PFQ_WANT_LCA) ----
@@ -553,7 +563,10 @@ int pfq_query_frames_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t
  * scans.
  * pfq_text_query: exactly pfq_query_batch_device(tree, csr_seq, csr_off, n_records, n_bases, threshold, flags, NULL, hits) on the
  * block parsed last, ordered behind the parse by an event; every rule of that call applies.  It may be repeated (the counters
- * grow each time).  Before any parse: PFQ_ERR_STATE. */
+ * grow each time).  Before any parse: PFQ_ERR_STATE.  The parsed block is sequence data and does not depend on the leaves: a
+ * block parsed before pfq_tree_insert or pfq_tree_prune may still be queried after it, and is then classified against the leaves
+ * as they are at the query, like the same reads given to pfq_query_batch; pfq_text_format needs a pfq_text_query after the
+ * change. */
 #define PFQ_TEXT_FASTA 0
 #define PFQ_TEXT_FASTQ 1
 #define PFQ_TEXT_FINAL 1u         /* the text ends where the file ends */
@@ -655,7 +668,9 @@ int pfq_debug_last_format(pfq_tree *tree, double *ms /* [3]: ids + blocks, sizes
  * pfq_prep_query: exactly pfq_query_batch_device(tree, csr_seq, csr_off, n_kept, bases_kept, threshold, flags, NULL, hits) on the
  * block prepared last, ordered behind the prep by an event; every flag and rule of that call applies.  The units are the kept
  * reads, with PFQ_PAIRED the kept fragments (mates are dropped together, so they stay adjacent); PFQ_PAIRED on a block prepared
- * without PFQ_PREP_PAIRED: PFQ_ERR_ARG.  It may be repeated (the counters grow each time).  Before any prep: PFQ_ERR_STATE. */
+ * without PFQ_PREP_PAIRED: PFQ_ERR_ARG.  It may be repeated (the counters grow each time).  Before any prep: PFQ_ERR_STATE.  Like
+ * a parsed block, a block prepared before pfq_tree_insert or pfq_tree_prune may still be queried after it, against the leaves as
+ * they are at the query. */
 #define PFQ_PREP_PAIRED 1u      /* reads 2i and 2i + 1 are mates */
 #define PFQ_PREP_WANT_READS 2u  /* fill begin, len, reason, kept */
 enum { PFQ_PREP_KEPT = 0, PFQ_PREP_SHORT = 1, PFQ_PREP_N = 2, PFQ_PREP_COMPLEXITY = 3, PFQ_PREP_MATE = 4 };

@@ -1,0 +1,393 @@
+"""One long-lived tree through every entry point, checked per call.  The features that came after tests/test_gpu_call_sequences.py
+— text parse / query / format, read preprocessing with adapters and mate overlap, frames, the sweep, best rows, taxonomy,
+abundance, coverage, similarity and recluster — share one pfq_tree: the copy stream, the hit rows, the hand-kept validity flags,
+two double-buffered CSR pipelines, the workload hints and the accumulators.  Here a seeded deck (tests/mixed_model.py: every
+operation at least twice, every adjacent pair of mixed_model.PAIRS) drives one tree through all of them, and every call, every
+accumulator, every result of the last call and the validity of format_text are held against the model, whose expectations come
+from the oracle and the *_ref modules and whose lifetime rules are those of include/pfq.h.  PFQ_SEQUENCE_SEEDS sets the number
+of seeds (default 2)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import abund_ref
+import mixed_model as mm
+import prep_ref
+import sweep_ref
+from hipbuf import stream_synchronize
+from mixed_model import (PFQ_ERR_STATE, PFQ_ERR_UNSUPPORTED, Play, TreeModel, check_accumulators, check_format, check_last, raises,
+                         rows_of)
+from phagefilter_amd import BloomTree, _ffi, pack_reads
+from phagefilter_amd.query import allreduce_counts
+from test_gpu_call_sequences import K, Model, Runner, check_counts
+from test_gpu_parity import gpu_tree
+from test_gpu_tax import random_taxonomy
+from test_gpu_text import wrap_fastq
+
+pytestmark = pytest.mark.gpu
+
+SEEDS = int(os.environ.get("PFQ_SEQUENCE_SEEDS", "2"))
+SWEEP = (0.3, 0.7, 1.0)
+ALL_ON = dict(hits=True, scores=True, lca="best", taxa=True, abundance=True, coverage=True, best=True, sweep=True)
+
+
+def kw_of(f, paired=None):
+    """The keywords of query_packed / query_text / query_prep for the model's flags."""
+    out = {k: f.get(k, False) for k in ("abundance", "coverage", "taxa", "best", "sweep")}
+    out.update(want_hits=f.get("hits", False), want_scores=f.get("scores", False), lca=f.get("lca"), paired=paired is not None, pair_mode=paired or "either")
+    return out
+
+
+@pytest.fixture(scope="module")
+def balanced(gpu):
+    return mm.balanced_case()
+
+
+def greedy_tree(genomes, ids):
+    gt = BloomTree.new(K, 0.001, 5000, 5, 10)
+    for g, i in zip(genomes, ids):
+        gt.insert(g, i)
+    return gt
+
+
+def play_deck(gt, model, world, seed, d, extra=()):
+    runner = Runner(gt)
+    try:
+        play = Play(model, world, seed, gt, runner, extra)
+        play.run(d)                                                  # (ends with a full read-out of every accumulator)
+        assert play.most_unsynced >= 2
+    finally:
+        runner.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 1, 2. the decks
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", range(SEEDS))
+def test_balanced_tree_mixed_sequence(balanced, seed):
+    genomes, ids, ot, world = balanced
+    gt = gpu_tree(genomes, ids, K, 131071, 7)
+    try:
+        play_deck(gt, TreeModel(ot), world, mm.BALANCED_SEED + seed, mm.deck(mm.BALANCED_SEED + seed))
+    finally:
+        gt.close()
+
+
+@pytest.mark.parametrize("seed", range(SEEDS))
+def test_greedy_tree_mixed_sequence_with_inserts_and_prune(gpu, seed):
+    genomes, ids, ot, world, extra = mm.greedy_case(seed)
+    gt = greedy_tree(genomes, ids)
+    try:
+        play_deck(gt, TreeModel(ot), world, mm.GREEDY_SEED + seed, mm.deck(mm.GREEDY_SEED + seed, greedy=True), extra)
+    finally:
+        gt.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 3. the pipelines
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ahead", [False, True], ids=["in order", "two blocks ahead"])
+def test_pipelines_without_a_synchronising_read(balanced, ahead):
+    """Parse A, query_text, prep B, query_prep, host query C, all counts-only, over block sizes that make each CSR set grow while the
+    other may still be read; no result is read until the end, then every counter against the oracle.  `ahead`: every parse and
+    prep is issued twice in a row, so the block that is classified lies in the set the one before it did not take, and a set is
+    written again only behind its own event."""
+    genomes, ids, ot, world = balanced
+    gt = gpu_tree(genomes, ids, K, 131071, 7)
+    model = Model(ot)
+    params = mm.PREP_PARAMS[1]
+    try:
+        for i, n in enumerate((200, 3000, 100, 3000, 50, 1500)):
+            thr = (1.0, 0.7)[i % 2]
+            for _ in range(2 if ahead else 1):
+                a = world.varied(n, longs=())
+                gt.parse_text(wrap_fastq(a), "fastq")
+            model.query(a, thr)
+            gt.query_text(thr)
+            for _ in range(2 if ahead else 1):
+                b, quals = world.prep_reads(n, True)
+                seq, off, qual, hq = mm.pack_quals(b, quals)
+                gt.prep_reads(seq, off, qual, hq, **params)
+            model.query(prep_ref.prep_block(b, quals, **params)["kept_reads"], thr)
+            gt.query_prep(thr)
+            c = world.varied(n, longs=())
+            model.query(c, thr)
+            gt.query_packed(*pack_reads(c), thr)
+        check_counts(gt, model)
+        assert sum(model.total.values()) > 0
+    finally:
+        gt.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 4. what each call invalidates
+# ---------------------------------------------------------------------------------------------------------------
+def establish(gt, m, play):
+    """A valid format_text state with scores, LCA, taxa and best rows of the last call all valid, and checked."""
+    if m.nodes is None:
+        play.op_set_taxonomy(None)
+    reads = play.w.reads(play.rng, True)
+    data = mm.fc.fastq(reads[:len(reads) - len(reads) % 2])           # (an even block: it can also be queried as fragments)
+    m.parse(data, True, None)
+    gt.parse_text(data, "fastq")
+    f = dict(hits=True, scores=True, lca="best", taxa=True, best=True)
+    exp = m.classify(m.text["reads"], 0.7, **f)
+    res = gt.query_text(0.7, **kw_of(f))
+    assert np.array_equal(res[0], exp["offs"]) and np.array_equal(res[1], exp["leaves"])
+    m.fmt_valid, m.fmt_rows = True, rows_of(exp["sets"])
+    assert all(m.last[k] is not None for k in ("lca", "taxa", "best", "scores"))
+    check_last(gt, m, "established")
+    assert check_format(gt, m, 3, 7, "established") is not None
+
+
+def test_what_each_call_invalidates(gpu):
+    genomes, ids, ot, world, extra = mm.greedy_case(7)
+    gt = greedy_tree(genomes, ids)
+    m = TreeModel(ot)
+    runner = Runner(gt)
+    play = Play(m, world, 8400, gt, runner, extra)
+    reads = world.reads(play.rng, True)
+    seq, off = pack_reads(reads)
+
+    def host():
+        m.classify(reads, 1.0)
+        gt.query_packed(seq, off, 1.0)
+
+    def device():
+        m.classify(reads, 1.0)
+        d_seq, d_off, total = runner.device(seq, off, "streams")
+        runner.last_stream = runner.streams[0]
+        gt.query_device(d_seq, d_off, len(reads), total, 1.0, stream=runner.streams[0])
+        stream_synchronize(runner.streams[0])
+
+    def paired_text():
+        assert len(m.text["reads"]) % 2 == 0 and len(m.text["reads"]) >= 2
+        exp = m.classify(m.text["reads"], 0.7, paired="either", hits=True)   # a successful query_text with hits, and yet no format_text
+        offs, leaves = gt.query_text(0.7, want_hits=True, paired=True)
+        assert np.array_equal(offs, exp["offs"]) and np.array_equal(leaves, exp["leaves"]) and len(leaves) > 0
+
+    def text_without_hits():
+        m.classify(m.text["reads"], 1.0)
+        gt.query_text(1.0)
+
+    def prep_query():
+        play.op_prep(None)
+        check_format(gt, m, 3, 7, "prep_reads alone")                  # (the prep itself changes nothing)
+        m.classify(m.prep["reads"], 1.0)
+        gt.query_prep(1.0)
+
+    def reset_counts():
+        gt.reset_counts()
+        m.reset()
+
+    def knob(name, value):
+        gt.set_option(name, value)
+        try:
+            check_format(gt, m, 3, 7, (name, value))
+        finally:
+            gt.set_option(name, None)
+
+    # (kind, the call, whether what the last call left stays readable, whether format_text stays valid), by pfq.h: a query call
+    # ends both ("valid until the next query call on the tree", "text output"); a parse, an insertion and a prune end format_text
+    # alone; everything else changes nothing
+    kinds = [("host query", host, False, False), ("device query", device, False, False), ("paired text query", paired_text, False, False),
+             ("text query without hits", text_without_hits, False, False), ("parse_text", lambda: play.op_parse(None), True, False),
+             ("prep_reads", lambda: play.op_prep(None), True, True), ("paired prep_reads", lambda: play.op_prep_paired(None), True, True),
+             ("query_prep", prep_query, False, False), ("query_frames", lambda: play.op_frames(None), False, False),
+             ("query_frames_device", lambda: play.op_frames_dev(None), False, False), ("reset_counts", reset_counts, True, True),
+             ("insert", lambda: play.op_insert(None), True, False), ("insert again", lambda: play.op_insert(None), True, False),
+             ("prune_tree", lambda: play.op_prune(None), True, False),
+             # adapters and mate overlap do not depend on the leaves: insert and prune kept them
+             ("prep_reads after insert and prune", lambda: play.op_prep(None), True, True),
+             ("paired prep_reads after insert and prune", lambda: play.op_prep_paired(None), True, True),
+             ("format_text", lambda: play.op_format(None), True, True), ("similarity", lambda: play.op_similarity(None), True, True),
+             ("recluster", lambda: play.op_recluster(None), True, True), ("read-outs", lambda: play.op_readout(None), True, True),
+             ("delta", lambda: play.op_delta(None), True, True)]
+    kinds += [(f"{name}={value}", lambda name=name, value=value: knob(name, value), True, True) for name, value in mm.KNOBS]
+    try:
+        play.op_set_adapters("on")
+        play.op_set_mate_overlap("on")
+        for kind, call, last_stays, format_stays in kinds:
+            establish(gt, m, play)
+            before = dict(m.last)
+            call()
+            assert all((m.last[k] is before[k]) if last_stays else (m.last[k] is None) for k in before), kind
+            assert m.fmt_valid == format_stays, kind
+            runner.sync()
+            check_last(gt, m, kind)
+            check_format(gt, m, 3, 7, kind)
+            check_accumulators(gt, m, kind)
+        assert m.adapters is not None and m.overlap is not None and m.seen.get("adapter found") and m.seen.get("insert found")
+    finally:
+        runner.close()
+        gt.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 5. the accumulators across entry points and replicas
+# ---------------------------------------------------------------------------------------------------------------
+def feed(gt, runner, entry, part, thr, f, paired=None):
+    """One part through one entry point with the flags f."""
+    if entry == "host":
+        return gt.query_packed(*pack_reads(part), thr, **kw_of(f, paired))
+    if entry == "streams":
+        seq, off = pack_reads(part)
+        d_seq, d_off, total = runner.device(seq, off, "streams")
+        kw = kw_of(f, paired)
+        kw.pop("want_hits")
+        return gt.query_device_hits(d_seq, d_off, len(part), total, thr, stream=runner.streams[1], **kw)
+    if entry == "text":
+        gt.parse_text(wrap_fastq(part), "fastq")
+        return gt.query_text(thr, **kw_of(f, paired))
+    seq, off = pack_reads(part)
+    kept = gt.prep_reads(seq, off, paired=paired is not None)
+    assert kept["n_kept"] == len(part)                                 # (untrimmed parameters: every read is kept whole)
+    return gt.query_prep(thr, **kw_of(f, paired))
+
+
+def test_accumulators_across_entry_points_and_replicas(balanced, tmp_path):
+    """One read set in five parts through the host, device-stream, text, prep and paired-prep entry points of one tree, and in one
+    call per kind of unit through a second tree loaded from the saved database: every read-out is the same and the references'.
+    (The fragments of the paired part make a call of their own there, and go without the sweep, which refuses fragments.)  Then the
+    parts dealt over the two trees: absorbing and reducing gives the one-tree result."""
+    genomes, ids, ot, world = balanced
+    a = gpu_tree(genomes, ids, K, 131071, 7)
+    db = str(tmp_path / "db")
+    a.save(db)
+    b = BloomTree.load(db)
+    runner = Runner(a)
+    rng = np.random.default_rng(8500)
+    parts = [world.reads(rng, True)[:50] for _ in range(4)] + [world.pairs(20)]
+    entries = ("host", "streams", "text", "prep", "prep")
+    tax = random_taxonomy(8501, len(ids))
+    thr = 0.3
+    pf = dict(ALL_ON, sweep=False)
+    try:
+        m = TreeModel(ot)
+        for gt in (a, b):
+            gt.set_taxonomy(*tax)
+            gt.set_sweep(SWEEP)
+        m.set_taxonomy(tax)
+        m.set_sweep(SWEEP)
+        for i, (entry, part) in enumerate(zip(entries, parts)):
+            paired = "either" if i == 4 else None
+            exp = m.classify(part, thr, paired=paired, **(pf if paired else ALL_ON))
+            res = feed(a, runner, entry, part, thr, pf if paired else ALL_ON, paired)
+            assert np.array_equal(res[0], exp["offs"]) and np.array_equal(res[1], exp["leaves"]) and np.array_equal(np.asarray(res[2]).astype(np.int64), exp["scores"]), entry
+            check_last(a, m, entry)
+        whole = [r for part in parts[:4] for r in part]
+        b.query_packed(*pack_reads(whole), thr, **kw_of(ALL_ON))
+        b.query_packed(*pack_reads(parts[4]), thr, **kw_of(pf, "either"))
+        check_accumulators(a, m, "five entry points")
+        check_accumulators(b, m, "one call per kind of unit")
+        assert m.log["n_ambiguous"] > 0 and m.sw["n_units"] == len(whole) and m.sketcher.sk.n_units == len(whole) + len(parts[4]) // 2
+        # the parts dealt over two replicas
+        for gt in (a, b):
+            gt.reset_counts()
+        m.reset()
+        for i, (entry, part) in enumerate(zip(entries, parts)):
+            paired = "either" if i == 4 else None
+            m.classify(part, thr, paired=paired, **(pf if paired else ALL_ON))
+            feed(b if i % 2 else a, runner, "host" if i % 2 else entry, part, thr, pf if paired else ALL_ON, paired)
+        a.abundance_absorb(b)
+        a.coverage_absorb(b)
+        a.sweep_absorb(b)
+        allreduce_counts([a, b])
+        check_counts(a, m)
+        check_counts(b, m)
+        mm.same_abundance(a.abundance(200, 0), abund_ref.estimate(m.log, 200, 0), "absorbed")
+        mm.same_coverage(a.coverage(), m.sketcher, "absorbed")
+        sweep_ref.same(a.sweep(), m.sweep_state(), "absorbed")
+        assert b.abundance()["n_units"] == 0 and b.coverage()["n_units"] == 0 and b.sweep()["n_units"] == 0   # (moved, not copied)
+    finally:
+        runner.close()
+        a.close()
+        b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 6. refused calls
+# ---------------------------------------------------------------------------------------------------------------
+def test_refused_calls_change_no_accumulator_and_end_what_the_last_call_left(balanced):
+    """The documented refusals of well-formed inputs, one after another, on a tree with every accumulator non-zero: query_text,
+    query_prep and format_text before any parse / prep; taxa without a taxonomy; the sweep without a list, above the list's lowest
+    threshold and of fragments; a paired query of a block prepared unpaired; scores without hits; rows that exceed PFQ_ABUND_SLOTS.
+    The code is the documented one and every accumulator is what it was.  Each of them but format_text is a query call that was
+    refused, and pfq.h ("a query call") counts it as the next query call: what the call before it left and format_text are no
+    longer valid.  The next good call is right."""
+    genomes, ids, ot, world = balanced
+    fresh = gpu_tree(genomes, ids, K, 131071, 7)
+    try:                                                               # before any parse / prep on a fresh tree
+        raises(PFQ_ERR_STATE, fresh.query_text, 1.0)
+        raises(PFQ_ERR_STATE, fresh.query_prep, 1.0)
+        raises(PFQ_ERR_STATE, fresh.format_text)
+        assert not any(c for _, c in fresh.get_leaf_counts())
+    finally:
+        fresh.close()
+    gt = gpu_tree(genomes, ids, K, 131071, 7)
+    m = TreeModel(ot)
+    runner = Runner(gt)
+    play = Play(m, world, 8600, gt, runner)
+    try:
+        gt.set_sweep(SWEEP)
+        m.set_sweep(SWEEP)
+        reads = world.reads(play.rng, True)
+        m.classify(reads, 0.3, **dict(ALL_ON, taxa=False))
+        gt.query_packed(*pack_reads(reads), 0.3, **kw_of(dict(ALL_ON, taxa=False)))
+        done = set()
+
+        def refuse_all():
+            for name, code, call in play.refusals():
+                if name in done:
+                    continue
+                done.add(name)
+                establish(gt, m, play) if m.nodes is not None else None
+                m.refused_query()
+                raises(code, call, gt)
+                runner.sync()
+                check_accumulators(gt, m, name)
+                check_last(gt, m, name)
+                check_format(gt, m, 0, 7, name)
+        refuse_all()                                                   # without a taxonomy
+        assert "taxa without a taxonomy" in done
+        play.op_set_taxonomy(None)
+        m.classify(reads, 0.3, **ALL_ON)
+        gt.query_packed(*pack_reads(reads), 0.3, **kw_of(ALL_ON))
+        assert m.tax_here.any() and m.clade_here.any() and m.log["n_units"] and m.sketcher.sk.n_units and m.sw["n_units"] and sum(m.total.values())
+        play.op_prep(None)
+        refuse_all()                                                   # the rest, an unpaired prepared block among them
+        gt.set_sweep([])
+        m.set_sweep(None)
+        refuse_all()                                                   # without a list
+        assert done >= {"sweep without a list", "sweep above the list's lowest", "sweep of fragments", "paired query of an unpaired block", "scores without hits"}
+        # a call whose rows exceed PFQ_ABUND_SLOTS: every other result of the call stands, the log is incomplete until it is reset
+        establish(gt, m, play)
+        held = abund_ref.estimate(m.log, 200, 0)
+        fam = [world.fam[0][i:i + 150] for i in range(0, 1500, 50)]
+        seq, off = pack_reads(fam)
+        exp = m.classify(fam, 0.7, hits=True, lca="all", abundance=True, log_fits=False)
+        assert abund_ref.classify(rows_of(exp["sets"]), m.n_leaves)["n_entries"] > 1
+        hits = _ffi.Hits()
+        gt.set_option("PFQ_ABUND_SLOTS", 1)
+        try:
+            rc = _ffi.lib().pfq_query_batch(gt._h, seq.ctypes.data, off.ctypes.data, len(fam), 0.7,
+                                            _ffi.WANT_HITS | _ffi.WANT_LCA | _ffi.WANT_ABUNDANCE, C.byref(hits))
+            assert rc == PFQ_ERR_UNSUPPORTED and b"abundance log" in _ffi.lib().pfq_last_error()
+            assert np.array_equal(np.ctypeslib.as_array(hits.offsets, shape=(len(fam) + 1,)), exp["offs"])
+            assert np.array_equal(np.ctypeslib.as_array(hits.leaves, shape=(int(exp["offs"][-1]),)), exp["leaves"])
+        finally:
+            gt.set_option("PFQ_ABUND_SLOTS", None)
+        m.log_ok = False
+        check_last(gt, m, "abundance log full")
+        check_accumulators(gt, m, "abundance log full")               # (the estimate is refused: PFQ_ERR_STATE)
+        gt.abundance_reset()
+        m.abundance_reset()
+        assert held["n_units"] > 0
+        check_accumulators(gt, m, "log reset")
+        play.classify("host", reads, "hits")                           # the next good call is right
+        play.op_readout(None)
+    finally:
+        runner.close()
+        gt.close()
