@@ -202,7 +202,7 @@ int pfq_query_batch_device(pfq_tree *tree, const uint8_t *d_seq, const uint64_t 
  * PFQ_WANT_SCORES.  Library-owned; valid until the next query call on the tree.
  * "A query call", here and for pfq_last_lca, pfq_last_taxa, pfq_last_best_rows and pfq_text_format: every call of pfq_query_batch,
  * pfq_query_batch_device, pfq_text_query, pfq_prep_query, pfq_query_frames and pfq_query_frames_device whose tree (for the frames
- * calls also out, and for a non-empty block its buffers) is not NULL.  Such a call ends the validity of what the one before it
+ * calls also out, and for a non-empty block its buffers) is not NULL, and for the screen of a pfq_prep_deplete that is not refused.  Such a call ends the validity of what the one before it
  * left even when it is then refused: PFQ_ERR_ARG for a combination of flags, an odd PFQ_PAIRED block, PFQ_WANT_SWEEP above the
  * list's lowest threshold or with PFQ_PAIRED, PFQ_PAIRED on a block prepared unpaired, frames flags other than 0; PFQ_ERR_STATE for
  * PFQ_WANT_TAXA without a taxonomy, PFQ_WANT_SWEEP without a list, pfq_text_query before a parse, pfq_prep_query before a prep;
@@ -775,6 +775,45 @@ typedef struct pfq_prep_overlap {
 int pfq_prep_last_overlap(pfq_tree *tree, pfq_prep_overlap *out);
 /* measurements: device milliseconds of the overlap kernel of the last pfq_prep_reads with reads (HIP events) */
 int pfq_debug_last_overlap(pfq_tree *tree, double *ms);
+
+/* ---- depletion (pfq_prep_deplete) ----
+ * Host and contaminant screening between the trimmer and the classifier: the units of the block prepared last on `tree` that hit a
+ * second tree, the screen, on the same device leave the block before pfq_prep_query sees it.
+ * What the call does.  The units (the kept reads; with PFQ_PAIRED the kept fragments) are classified against `screen` exactly as
+ * pfq_query_batch_device(screen, csr_seq, csr_off, n_kept, bases_kept, threshold, flags, ..) would classify the prepared CSR, with
+ * the screen's own k, hashes, seeds and topology.  flags: 0, PFQ_PAIRED or PFQ_PAIRED | PFQ_PAIR_BOTH, anything else PFQ_ERR_ARG.
+ * It is a query call on `screen` in the sense of pfq_last_hit_scores: the screen's leaf counters grow by exactly what that call
+ * would add, and what the screen's previous query call left becomes invalid.  A unit is removed iff its row on the screen is not
+ * empty.  The classifier's rule for a read shorter than the screen's k holds: it has no k-mer, passes every leaf, and is removed;
+ * with PFQ_PAIR_BOTH a fragment with such a mate gets the other mate's set, so it is removed iff the other mate hits.  That is
+ * what query --neg-filter against the screen followed by a run on NEG_FILTERING does.
+ * What is left.  The prepared block of `tree` is the remaining units in their order, mates together, the CSR padded by 16 bytes as
+ * before; pfq_prep_query, pfq_debug_prep_csr and a further pfq_prep_deplete see that block, so screens compose (host, then PhiX),
+ * and a second call with the same screen removes nothing.
+ * What is not touched.  No counter, log, sketch or query result of `tree`; the arrays pfq_prep_reads handed out (begin, len,
+ * reason, kept), which stay as that call left them; pfq_prep_last_adapters and pfq_prep_last_overlap.
+ * pfq_prep_depleted: the totals of the call and of the block afterwards and, only if the block was prepared with
+ * PFQ_PREP_WANT_READS (else NULL), library-owned host arrays valid until the next pfq_prep_deplete or pfq_prep_reads on the tree:
+ * kept [n_kept], the remaining reads' indices into the block given to pfq_prep_reads, ascending, and reason [n_reads], the prep's
+ * reasons with PFQ_PREP_DEPLETED written over the removed reads (pfq_prep.n_reason keeps its five entries and their meaning).
+ * Errors.  PFQ_ERR_ARG: a NULL tree, screen or out, screen == tree, trees on different devices, PFQ_PAIRED on a block prepared
+ * without PFQ_PREP_PAIRED; PFQ_ERR_STATE: before any pfq_prep_reads on `tree`, an empty screen; PFQ_ERR_UNSUPPORTED: the screen
+ * is a subtree shard (its rows are partial); a sticky insertion error of either tree is returned as everywhere else.  A refused
+ * call changes nothing on either tree.  A block with n_kept == 0 is a no-op that returns zeros.
+ * Overlap.  The call returns totals, so it waits for its own work: the screen's classification, the mark, the scans and the
+ * compaction, all on the stream of the prep.  It neither waits for nor disturbs the classification of the previous block that
+ * pfq_prep_query has queued on `tree` (which reads the other CSR set); a pfq_prep_query of this very block is waited for. */
+#define PFQ_PREP_DEPLETED 5   /* reason of a read whose unit hit the screen */
+typedef struct pfq_prep_depleted {
+    uint64_t n_units, units_removed, reads_removed, bases_removed;   /* of this call */
+    uint64_t n_kept, bases_kept;                                     /* the prepared block afterwards */
+    const uint32_t *kept;    /* [n_kept] indices into the block given to pfq_prep_reads, ascending */
+    const uint32_t *reason;  /* [n_reads] the prep's reasons with PFQ_PREP_DEPLETED written over the removed reads */
+} pfq_prep_depleted;
+int pfq_prep_deplete(pfq_tree *tree, pfq_tree *screen, float threshold, uint32_t flags, pfq_prep_depleted *out);
+/* measurements: device milliseconds of the last pfq_prep_deplete with units — ms[0] the screen's classification (host waits
+ * between its stages included), ms[1] mark, the two scans, offsets and gather (HIP events) */
+int pfq_debug_last_deplete(pfq_tree *tree, double *ms);
 
 /* ---- genome similarity ----
  * Which genomes of a database are related, and how closely?  Every leaf's Bloom filter is in device memory, all built with one

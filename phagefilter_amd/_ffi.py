@@ -24,6 +24,7 @@ SYMBOLS = [
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_set_adapters", "pfq_prep_last_adapters", "pfq_debug_last_adapters",
     "pfq_tree_set_mate_overlap", "pfq_prep_last_overlap", "pfq_debug_last_overlap",
+    "pfq_prep_deplete", "pfq_debug_last_deplete",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
@@ -156,6 +157,14 @@ class PrepOverlap(C.Structure):
                 ("hist", C.POINTER(C.c_uint64)), ("insert", C.POINTER(C.c_uint32)), ("mismatches", C.POINTER(C.c_uint32))]
 
 
+PREP_DEPLETED = 5
+
+
+class PrepDepleted(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_units", "units_removed", "reads_removed", "bases_removed", "n_kept", "bases_kept")] + [
+                ("kept", C.POINTER(C.c_uint32)), ("reason", C.POINTER(C.c_uint32))]
+
+
 class Similarity(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("shared_bits", C.POINTER(C.c_uint32)),
                 ("bits_a", C.POINTER(C.c_uint64)), ("bits_b", C.POINTER(C.c_uint64)),
@@ -272,6 +281,8 @@ def lib() -> C.CDLL:
     L.pfq_tree_set_mate_overlap.argtypes = [vp, C.c_uint32, C.c_uint32]
     L.pfq_prep_last_overlap.argtypes = [vp, C.POINTER(PrepOverlap)]
     L.pfq_debug_last_overlap.argtypes = [vp, C.POINTER(C.c_double)]
+    L.pfq_prep_deplete.argtypes = [vp, vp, C.c_float, C.c_uint32, C.POINTER(PrepDepleted)]
+    L.pfq_debug_last_deplete.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]
     L.pfq_debug_last_similarity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.pfq_tree_recluster.argtypes = [vp, C.POINTER(vp)]

@@ -1405,6 +1405,14 @@ struct PrepRun {
     uint32_t mate_overlap = 0, mate_overlap_errors = 10;
     std::atomic<uint64_t> overlap_fragments{0}, overlap_skipped{0}, overlap_found{0}, overlap_readthrough{0}, overlap_reads{0}, overlap_bases{0};
     std::atomic<uint64_t> insert_hist[PFQ_OVERLAP_INSERT_MAX + 1] = {};
+    // --deplete DIR [..] / --deplete-threshold T: the screens in the order given, every replica's own copies of them on its device
+    // (screens_of: by the replica's tree; filled before the loop starts, only read afterwards) and what every screen removed
+    static constexpr size_t DEPLETE_MAX = 4;
+    std::vector<std::string> deplete_dirs;
+    float deplete_threshold = 1.0f;
+    std::string deplete_threshold_typed;
+    std::map<pfq_tree *, std::vector<pfq_tree *>> screens_of;
+    std::atomic<uint64_t> depleted_units[DEPLETE_MAX] = {}, depleted_reads[DEPLETE_MAX] = {}, depleted_bases[DEPLETE_MAX] = {};
 };
 // What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending
 struct PrepKept {
@@ -1484,14 +1492,30 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
             for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
                 if (ov.hist[i]) prep->insert_hist[i] += ov.hist[i];
         }
+        // --deplete: the screens take their units out of the prepared block, one after the other; a fragment leaves when either
+        // mate hits.  What is mapped back is what the last screen left.
+        uint64_t n_kept = res.n_kept;
+        const uint32_t *kept = res.kept;
+        if (!prep->deplete_dirs.empty()) {
+            const std::vector<pfq_tree *> &screens = prep->screens_of.at(tree);
+            for (size_t i = 0; i < screens.size(); ++i) {
+                pfq_prep_depleted d{};
+                if (pfq_prep_deplete(tree, screens[i], prep->deplete_threshold, flags & PFQ_PAIRED ? PFQ_PAIRED : 0u, &d) != PFQ_OK) fail_from_thread(pfq_last_error());
+                prep->depleted_units[i] += d.units_removed;
+                prep->depleted_reads[i] += d.reads_removed;
+                prep->depleted_bases[i] += d.bases_removed;
+                n_kept = d.n_kept;
+                if (pk) kept = d.kept;
+            }
+        }
         if (pk) {
             pk->begin.assign(res.begin, res.begin + res.n_reads);
             pk->len.assign(res.len, res.len + res.n_reads);
-            pk->kept.assign(res.kept, res.kept + res.n_kept);
+            pk->kept.assign(kept, kept + n_kept);
         }
-        units = flags & PFQ_PAIRED ? res.n_kept / 2 : res.n_kept;
+        units = flags & PFQ_PAIRED ? n_kept / 2 : n_kept;
         if (want) h.off.assign(units + 1, 0);
-        if (!res.n_kept) return;
+        if (!n_kept) return;
         if (pfq_prep_query(tree, threshold, flags, want ? &hits : nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
     } else if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, threshold, flags, want ? &hits : nullptr) != PFQ_OK) {
         fail_from_thread(pfq_last_error());
@@ -2634,7 +2658,8 @@ int cmd_query(int argc, char **argv) {
                              {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
                              {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
-                             {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}};
+                             {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}, {"deplete", 0, true, true},
+                             {"deplete-threshold", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2739,6 +2764,8 @@ int cmd_query(int argc, char **argv) {
             die("error: '--device-output' cannot be used with '--device-parse': that option serves runs that only count, this one parses the text itself");
         for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits"})
             if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
+        for (const char *other : {"deplete", "deplete-threshold"})  // (first: whatever else turns preprocessing on, the refusal names this one)
+            if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
                                   "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors"})
             if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
@@ -2792,6 +2819,11 @@ int cmd_query(int argc, char **argv) {
     for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2", "adapter-overlap",
                              "adapter-errors", "mate-overlap", "mate-overlap-errors"})
         if (a.val.count(name) && !prep_first) prep_first = name;
+    // --deplete DIR [--deplete DIR2 ..] [--deplete-threshold T]: after the steps above every unit that hits one of the screens, a
+    // database each, at T (default: -f) is taken out before the classification (pfq.h "depletion").  It turns preprocessing on
+    // as the options above do, and its refusals name it.
+    if (a.val.count("deplete-threshold") && !a.val.count("deplete")) die("error: '--deplete-threshold' needs '--deplete <DIR>'");
+    if (a.val.count("deplete")) prep_first = "deplete";
     if (prep_first) {
         prep_run.on = true;
         const std::string why = ": preprocessing works on the batches the host reader parses and classifies every kept read on every replica";
@@ -2852,6 +2884,20 @@ int cmd_query(int argc, char **argv) {
                 die("error: '--mate-overlap' needs '--reads2 <FILE>' or '--interleaved': it compares the two mates of a fragment");
             prep_run.mate_overlap = number("mate-overlap", "30", 1, PFQ_OVERLAP_LEN_MAX, "an overlap of 1 to 512 bases");
             prep_run.mate_overlap_errors = number("mate-overlap-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
+        }
+        if (a.val.count("deplete")) {
+            const std::string list = a.val.at("deplete") + ",";  // (the parser joins a repeated option's values with ',')
+            for (size_t at = 0, end; (end = list.find(',', at)) != std::string::npos; at = end + 1) prep_run.deplete_dirs.push_back(list.substr(at, end - at));
+            if (prep_run.deplete_dirs.size() > PrepRun::DEPLETE_MAX)
+                die("error: '--deplete' given " + std::to_string(prep_run.deplete_dirs.size()) + " times, at most " + std::to_string(PrepRun::DEPLETE_MAX) +
+                    " screens (a directory name must not hold a ',')");
+            prep_run.deplete_threshold_typed = opt(a, "deplete-threshold", opt(a, "filter-threshold", "1.0"));
+            prep_run.deplete_threshold = a.val.count("deplete-threshold") ? to_f32(a.val.at("deplete-threshold"), "deplete-threshold") : threshold;
+            for (const std::string &dir : prep_run.deplete_dirs) {  // before any read is parsed, and before any device is used
+                FILE *f = fopen((dir + "/tree.bin").c_str(), "rb");
+                if (!f) die("error: invalid value '" + dir + "' for '--deplete': cannot read " + dir + "/tree.bin: " + strerror(errno));
+                fclose(f);
+            }
         }
     }
     // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
@@ -2937,6 +2983,12 @@ int cmd_query(int argc, char **argv) {
     }
     if (prep_run.mate_overlap)
         for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_overlap(tree, prep_run.mate_overlap, prep_run.mate_overlap_errors));
+    // --deplete: every replica gets its own copy of every screen on its device (the screens' memory once per replica)
+    std::vector<std::unique_ptr<ServedDb>> screens;
+    for (const std::string &dir : prep_run.deplete_dirs) {
+        screens.emplace_back(new ServedDb(dir, devices, false, 0));
+        for (size_t i = 0; i < db.trees.size(); ++i) prep_run.screens_of[db.trees[i]].push_back(screens.back()->trees[i]);
+    }
     ReadQueue rq(reads, ov);
     std::unique_ptr<ReadQueue> rq2;
     if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
@@ -3034,7 +3086,15 @@ int cmd_query(int argc, char **argv) {
                     (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(), (unsigned long long)pr.overlap_bases.load());
             fprintf(f, "mate_overlap\t%u\nmate_overlap_errors\t%u\n", pr.mate_overlap, pr.mate_overlap_errors);
         }
+        for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)  // behind the overlap rows: per screen, in the order given
+            fprintf(f, "deplete_db\t%s\ndeplete_threshold\t%s\ndepleted_units\t%llu\ndepleted_reads\t%llu\ndepleted_bases\t%llu\n", pr.deplete_dirs[i].c_str(),
+                    pr.deplete_threshold_typed.c_str(), (unsigned long long)pr.depleted_units[i].load(), (unsigned long long)pr.depleted_reads[i].load(),
+                    (unsigned long long)pr.depleted_bases[i].load());
         if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
+        // DEPLETION.csv (several screens: DEPLETION_1.csv ..): what CLASSIFICATION.csv of a run of the block screen i saw against
+        // that screen would hold; the replicas' counters are summed as the main database's are
+        for (size_t i = 0; i < screens.size(); ++i)
+            screens[i]->save_counts(out + (screens.size() == 1 ? std::string("/DEPLETION.csv") : "/DEPLETION_" + std::to_string(i + 1) + ".csv"));
         if (pr.mate_overlap) {
             // INSERT_SIZES.tsv: the fragments per insert length, summed over all calls and replicas
             FILE *g = fopen((out + "/INSERT_SIZES.tsv").c_str(), "wb");
@@ -3055,6 +3115,9 @@ int cmd_query(int argc, char **argv) {
             fprintf(stderr, "; mates overlap in %llu of %llu fragments, %llu with read-through: %llu reads cut (%llu bases)", (unsigned long long)pr.overlap_found.load(),
                     (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(),
                     (unsigned long long)pr.overlap_bases.load());
+        for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)
+            fprintf(stderr, "; screen %s took %llu reads (%llu bases)", pr.deplete_dirs[i].c_str(), (unsigned long long)pr.depleted_reads[i].load(),
+                    (unsigned long long)pr.depleted_bases[i].load());
         fprintf(stderr, "\n");
     }
     db.close();
@@ -3612,6 +3675,18 @@ void usage() {
             "fragments looked at), overlap_skipped, overlap_found, overlap_readthrough (insert shorter than a mate), overlap_reads,\n"
             "overlap_bases (reads and bases cut), mate_overlap and mate_overlap_errors, and INSERT_SIZES.tsv in --out holds\n"
             "\"insert<TAB>fragments\", one line per insert length found, ascending\n"
+            "--deplete <DIR> [--deplete <DIR2> ..] [--deplete-threshold <T>]: reads of the host, of PhiX and of the lab's usual\n"
+            "contaminants are thrown away before anything is counted: every DIR is a database (a screen), and behind the steps above every\n"
+            "read that hits a genome of a screen at T (default: the run's -f) is taken out on the GPU before the classification, which so\n"
+            "sees what query -d DIR --neg-filter would have left, without writing and parsing it.  Up to 4 screens, applied in the order\n"
+            "given (a DIR must not hold a ','); a screen has its own k, filter size and seeds; a read shorter than a screen's k hits all of\n"
+            "its genomes, as everywhere, and goes.  With --reads2 / --interleaved a fragment goes when either mate hits.  Every replica\n"
+            "(--devices) opens its own copy of every screen next to the database: the screens' memory is spent once per replica.  Turns the\n"
+            "preprocessing above on (--min-length defaults to the database's k), combines with every option of it, and is refused where\n"
+            "it is, and with --device-output.  Every output is, byte for byte, that of the same command without the option on an input\n"
+            "that holds only the remaining records, each cut to what preprocessing kept.  PREPROCESS.tsv then also holds, per screen in\n"
+            "order, deplete_db, deplete_threshold, depleted_units, depleted_reads and depleted_bases, and DEPLETION.csv in --out (several\n"
+            "screens: DEPLETION_1.csv, DEPLETION_2.csv ..) is the CLASSIFICATION.csv of the reads a screen saw against that screen\n"
             "taxonomy -d <DB> --taxonomy <FILE> -o <OUT>: checks FILE against DB's tree.bin without a GPU and writes OUT/TAXA.tsv,\n"
             "\"#node<TAB>parent<TAB>depth<TAB>kind<TAB>genomes<TAB>name\", every node of the table query --taxonomy would count on\n"
             "ingest-check takes --reads2 / --interleaved too and prints the fragments' records, mates adjacent\n"

@@ -473,6 +473,18 @@ struct pfq_tree {
     int pp_slot = 0;
     uint64_t pp_kept = 0, pp_bases = 0;
     std::vector<uint32_t> out_pp_begin, out_pp_len, out_pp_reason, out_pp_kept;
+    // pfq_prep_deplete on this tree's prepared block: pp_reads / pp_want_reads of the prep that made it (d_pp_keep, d_pp_klen,
+    // d_pp_kept, d_pp_reason, d_pp_begin and the raw block stay on the device until the next prep, and the call compacts from
+    // them), the per-unit hit flags of a screen's call on reads, the totals and their page-locked copy (behind them the kept
+    // reads and bases of the new scans), the host copies of kept and reason after the last call (dp_have: there has been one
+    // since the prep; out_pp_* stay the prep's).
+    uint64_t pp_reads = 0;
+    bool pp_want_reads = false, dp_have = false, dp_timed = false;
+    DevBuf<uint32_t> d_dp_hit;
+    DevBuf<unsigned long long> d_dp_tot;
+    unsigned long long *h_dp_tot = nullptr;
+    hipEvent_t dp_time[3] = {nullptr, nullptr, nullptr};  // pfq_debug_last_deplete: the screen's classification, mark + scans + compaction
+    std::vector<uint32_t> out_dp_kept, out_dp_reason;
     // pfq_tree_set_adapters: the sets as the kernel takes them (ad_on: any is set) and what the adapter step of the last
     // pfq_prep_reads left: cut and which per read (scratch of one call, as d_pp_begin), the totals (h_pp_tot behind the kept
     // reads), the host copies of a PFQ_PREP_WANT_READS call.  ad_last: the last prep ran with adapters.
@@ -1471,6 +1483,12 @@ struct QueryRun {
     // d_hit_leaves, rows_total entries) for the segment stage; nothing is handed to a caller.
     bool frames = false;
     uint64_t rows_total = 0;
+    // pfq_prep_deplete: the call is a screen's, on a block of another tree.  It builds the hit pairs (with their overflow retry)
+    // like PFQ_WANT_LCA alone and hands nothing to a caller: reads leave a flag per read with a hit pair in deplete_hit (zeroed
+    // by the caller), fragments their final CSR offsets in d_frag_off; the all-hit bytes stay in d_allhit.  Its small reads go
+    // through `st`, not the null stream, so that nothing of the call waits for what another tree has queued there.
+    bool deplete = false;
+    uint32_t *deplete_hit = nullptr;
 
     QueryRun(pfq_tree &t_, const uint8_t *seq_, const uint64_t *off_, uint64_t n_, uint64_t bytes_, float thr_, uint32_t flags_, hipStream_t st_,
              pfq_hits *hits_)
@@ -1495,7 +1513,7 @@ struct QueryRun {
         if (want_taxa && (!t.tax_set || t.tax.rank.size() != t.leaves.size()))
             return fail(PFQ_ERR_STATE, "PFQ_WANT_TAXA without a taxonomy: pfq_tree_set_taxonomy first (pfq_tree_prune and pfq_tree_insert drop it)");
         if (want_lca) PFQ_TRY(ensure_lca(t));
-        want_hits = user_hits || paired || want_lca;  // (fragments and LCAs are combined from the reads' hit lists)
+        want_hits = user_hits || paired || want_lca || deplete;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
         if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
@@ -2196,19 +2214,30 @@ struct QueryRun {
         done = true;
         HIP_TRY(hipStreamSynchronize(st));
         unsigned long long cursors[2] = {0, 0};  // CUR_HIT, CUR_PAIR
-        HIP_TRY(hipMemcpy(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost));
+        if (deplete) {
+            HIP_TRY(hipMemcpyAsync(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        } else HIP_TRY(hipMemcpy(cursors, t.d_cursors.p, 16, hipMemcpyDeviceToHost));
         const uint64_t n_pairs = cursors[CUR_HIT];
         if (n_reads) t.hits_per_read = std::max(t.hits_per_read, (double)n_pairs / (double)n_reads);
         if (t.last_attempts == 1) t.last_hit_cursor0 = n_pairs;
         if (n_pairs > hit_cap) {
             // restore the counters and run the block again with room for every hit (whatever PFQ_HIT_SLOTS says)
-            if (nl) HIP_TRY(hipMemcpy(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice));
+            if (nl && deplete) {
+                HIP_TRY(hipMemcpyAsync(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            } else if (nl) HIP_TRY(hipMemcpy(t.d_counts.p, t.d_counts_snapshot.p, nl * 8, hipMemcpyDeviceToDevice));
             HIP_TRY(t.d_hit_pairs.ensure(n_pairs + 1024));
             hit_cap = t.d_hit_pairs.n;
             done = false;
             return PFQ_OK;
         }
         if (paired) return pair_hits(n_pairs);
+        if (deplete) {  // reads: the flags straight from the hit pairs, nothing waited for
+            pfq::launch_deplete_pairs(t.d_hit_pairs.p, n_pairs, n_reads, deplete_hit, st);
+            HIP_TRY(hipGetLastError());
+            return PFQ_OK;
+        }
         if (!user_hits) {  // PFQ_WANT_LCA alone: the reads' spans straight from the hit pairs, nothing waited for
             if (n_reads && nl) {
                 HIP_TRY(t.d_lca_span.ensure(n_reads));
@@ -2510,13 +2539,15 @@ struct QueryRun {
 };
 
 int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, uint64_t total_bytes,
-                 float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits) {
+                 float threshold, uint32_t flags, hipStream_t st, pfq_hits *hits, bool deplete = false, uint32_t *deplete_hit = nullptr) {
     t.fm_rows = false;
     t.scores_valid = false;
     t.lca_last = false;
     t.taxa_last = false;
     t.best_last = false;
     QueryRun q(t, d_seq, d_off, n_reads, total_bytes, threshold, flags, st, hits);
+    q.deplete = deplete;
+    q.deplete_hit = deplete_hit;
     int rc = q.plan();
     if (rc == PFQ_OK) rc = q.run();
     t.lca_last = (rc == PFQ_OK || q.results_stand) && (flags & PFQ_WANT_LCA);
@@ -3417,6 +3448,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
                         t.d_pp_cut.bytes() + t.d_pp_which.bytes() + t.d_pp_atot.bytes() +  // (the adapter step)
                         t.d_pp_oins.bytes() + t.d_pp_omm.bytes() + t.d_pp_ecut.bytes() + t.d_pp_otot.bytes() +  // (the mate overlap step)
+                        t.d_dp_hit.bytes() + t.d_dp_tot.bytes() +  // (pfq_prep_deplete)
                         t.d_fm_idb.bytes() + t.d_fm_idl.bytes() + t.d_fm_len[0].bytes() + t.d_fm_len[1].bytes() + t.d_fm_long.bytes() +  // (pfq_text_format)
                         t.d_fm_name_off.bytes() + t.d_fm_hash.bytes() + t.d_fm_dst[0].bytes() + t.d_fm_dst[1].bytes() + t.d_fm_sums.bytes() +
                         t.d_fm_small.bytes() + t.d_fm_names.bytes() + t.d_fm_out[0].bytes() + t.d_fm_out[1].bytes();
@@ -3481,6 +3513,9 @@ void pfq_tree_close(pfq_tree *tree) {
         if (e) (void)hipEventDestroy(e);
     if (tree->pp_ready) (void)hipEventDestroy(tree->pp_ready);
     if (tree->h_pp_tot) (void)hipHostFree(tree->h_pp_tot);
+    for (auto e : tree->dp_time)
+        if (e) (void)hipEventDestroy(e);
+    if (tree->h_dp_tot) (void)hipHostFree(tree->h_dp_tot);
     delete tree;
 }
 
@@ -4131,6 +4166,9 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     t.pp_bases = out->bases_kept;
     t.pp_paired = paired;
     t.pp_have = true;
+    t.pp_reads = n_reads;
+    t.pp_want_reads = want_reads;
+    t.dp_have = false;
     t.ad_last = adapters;
     t.ad_last_reads = adapters && want_reads;
     t.ov_last = overlap;
@@ -4289,6 +4327,136 @@ int pfq_debug_last_prep(pfq_tree *tree, double *ms) {
     for (int i = 0; i < 3; ++i) {
         float v = 0.0f;
         HIP_TRY(hipEventElapsedTime(&v, tree->pp_time[i], tree->pp_time[i + 1]));
+        ms[i] = v;
+    }
+    return PFQ_OK;
+}
+
+// ---- depletion ---------------------------------------------------------------------------------------------------------------
+
+// Everything runs on tree's copy stream, which the prep used: the screen's classification of the prepared slot, then the mark,
+// the two scans, the offsets and the gather from the raw block into the same slot, so the stream orders the rewrite of the
+// slot behind its last reader.  The null stream, where pfq_prep_query queued the previous block's classification (it reads the
+// other slot), is neither waited for nor given work.
+int pfq_prep_deplete(pfq_tree *tree, pfq_tree *screen, float threshold, uint32_t flags, pfq_prep_depleted *out) {
+    if (!tree || !screen || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (screen == tree) return fail(PFQ_ERR_ARG, "pfq_prep_deplete: the screen is the tree whose block it would deplete");
+    if (flags != 0 && flags != PFQ_PAIRED && flags != (PFQ_PAIRED | PFQ_PAIR_BOTH))
+        return fail(PFQ_ERR_ARG, "pfq_prep_deplete: flags must be 0, PFQ_PAIRED or PFQ_PAIRED | PFQ_PAIR_BOTH");
+    if (screen->device != tree->device)
+        return fail(PFQ_ERR_ARG, "pfq_prep_deplete: the screen is on device " + std::to_string(screen->device) + ", the prepared block on device " +
+                                     std::to_string(tree->device));
+    PFQ_TRY(insertion_error(*tree));
+    PFQ_TRY(insertion_error(*screen));
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_prep_deplete before a pfq_prep_reads on this tree");
+    if ((flags & PFQ_PAIRED) && !tree->pp_paired)
+        return fail(PFQ_ERR_ARG, "pfq_prep_deplete: PFQ_PAIRED on a block prepared without PFQ_PREP_PAIRED (its kept reads are not whole fragments)");
+    if (screen->root < 0) return fail(PFQ_ERR_STATE, "pfq_prep_deplete: the screen is an empty tree");
+    if (screen->is_shard)
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_deplete: the screen is a subtree shard: it sees only its own leaves, so an empty row does not "
+                                         "say that the unit misses the database");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree, &s = *screen;
+    const bool paired = (flags & PFQ_PAIRED) != 0;
+    const uint32_t per = paired ? 2u : 1u;
+    const uint64_t n_reads = t.pp_reads, n_before = t.pp_kept, n_units = n_before / per;
+    const int slot = t.pp_slot;
+    hipStream_t st = t.copy_stream;
+    if (!t.h_dp_tot) {
+        for (auto &e : t.dp_time) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_dp_tot), (pfq::DEPL_TOT_N + 2) * 8, hipHostMallocDefault));
+        HIP_TRY(t.d_dp_tot.ensure(pfq::DEPL_TOT_N));
+    }
+    *out = pfq_prep_depleted{};
+    out->n_units = n_units;
+    uint64_t n_kept = n_before, bases_kept = t.pp_bases;
+    if (n_units) {
+        // (a classification of this block that pfq_prep_query has queued still reads the slot the gather below rewrites)
+        if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));
+        if (!paired) {
+            HIP_TRY(t.d_dp_hit.ensure(n_units));
+            HIP_TRY(hipMemsetAsync(t.d_dp_hit.p, 0, n_units * 4, st));
+        }
+        HIP_TRY(hipMemsetAsync(t.d_dp_tot.p, 0, pfq::DEPL_TOT_N * 8, st));
+        HIP_TRY(hipEventRecord(t.dp_time[0], st));
+        t.dp_timed = false;
+        PFQ_TRY(query_device(s, t.d_pp_seq[slot].p, t.d_pp_off[slot].p, n_before, t.pp_bases, threshold, flags, st, nullptr, true, t.d_dp_hit.p));
+        HIP_TRY(hipEventRecord(t.dp_time[1], st));
+        pfq::DepleteArgs d{};
+        d.hit = t.d_dp_hit.p;
+        d.allhit = s.d_allhit.p;
+        d.frag_off = paired ? s.d_frag_off.p : nullptr;
+        d.pair_mode = paired ? ((flags & PFQ_PAIR_BOTH) ? 2 : 1) : 0;
+        d.n_units = n_units;
+        d.n_reads = n_reads;
+        d.kept = t.d_pp_kept.p;
+        d.keep = t.d_pp_keep.p;
+        d.klen = t.d_pp_klen.p;
+        d.reason = t.d_pp_reason.p;
+        d.totals = t.d_dp_tot.p;
+        pfq::launch_deplete_mark(d, st);
+        pfq::launch_scan_u32(t.d_pp_keep.p, n_reads, t.d_pp_sums.p, t.d_pp_kpos.p, st);
+        pfq::launch_scan_u32(t.d_pp_klen.p, n_reads, t.d_pp_sums.p, t.d_pp_koff.p, st);
+        pfq::PrepArgs a{};
+        a.seq = t.d_pp_in.p;
+        a.off = t.d_pp_inoff.p;
+        a.n_reads = n_reads;
+        a.paired = t.pp_paired ? 1u : 0u;
+        a.begin = t.d_pp_begin.p;
+        a.len = t.d_pp_len.p;
+        a.reason = t.d_pp_reason.p;
+        a.keep = t.d_pp_keep.p;
+        a.klen = t.d_pp_klen.p;
+        a.totals = t.d_pp_tot.p;
+        a.kpos = t.d_pp_kpos.p;
+        a.koff = t.d_pp_koff.p;
+        a.kept = t.d_pp_kept.p;
+        a.csr_off = t.d_pp_off[slot].p;
+        a.out = t.d_pp_seq[slot].p;
+        pfq::launch_prep_gather(a, st);
+        HIP_TRY(hipEventRecord(t.dp_time[2], st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot, t.d_dp_tot.p, pfq::DEPL_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot + pfq::DEPL_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot + pfq::DEPL_TOT_N + 1, t.d_pp_koff.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(t.pp_ready, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t.dp_timed = true;
+        out->units_removed = t.h_dp_tot[pfq::DEPL_TOT_UNITS];
+        out->reads_removed = t.h_dp_tot[pfq::DEPL_TOT_READS];
+        out->bases_removed = t.h_dp_tot[pfq::DEPL_TOT_BASES];
+        n_kept = t.h_dp_tot[pfq::DEPL_TOT_N];
+        bases_kept = t.h_dp_tot[pfq::DEPL_TOT_N + 1];
+        t.pp_kept = n_kept;
+        t.pp_bases = bases_kept;
+    }
+    out->n_kept = n_kept;
+    out->bases_kept = bases_kept;
+    if (t.pp_want_reads) {
+        if (!t.dp_have) {  // the first call since the prep starts from what the prep handed out
+            t.out_dp_kept = t.out_pp_kept;
+            t.out_dp_reason = t.out_pp_reason;
+        }
+        if (out->units_removed) {
+            t.out_dp_kept.resize(std::max<uint64_t>(n_kept, 1));
+            if (n_kept) HIP_TRY(hipMemcpyAsync(t.out_dp_kept.data(), t.d_pp_kept.p, n_kept * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.out_dp_reason.data(), t.d_pp_reason.p, n_reads * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        out->kept = t.out_dp_kept.data();
+        out->reason = t.out_dp_reason.data();
+    }
+    t.dp_have = true;
+    return PFQ_OK;
+}
+
+int pfq_debug_last_deplete(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->dp_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_deplete before a pfq_prep_deplete with units on this tree");
+    PFQ_TRY(use_device(tree->device));
+    for (int i = 0; i < 2; ++i) {
+        float v = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&v, tree->dp_time[i], tree->dp_time[i + 1]));
         ms[i] = v;
     }
     return PFQ_OK;

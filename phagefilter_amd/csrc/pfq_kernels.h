@@ -791,6 +791,27 @@ void launch_prep_overlap(const OverlapArgs &a, hipStream_t st);
 void launch_prep_trim(const PrepArgs &a, hipStream_t st);
 void launch_prep_mark(const PrepArgs &a, hipStream_t st);
 void launch_prep_gather(const PrepArgs &a, hipStream_t st);
+// pfq_prep_deplete (pfq_deplete.hip; the rule is pfq.h "depletion"): the verdict of the screen's classification of the prepared
+// block, turned into the prep's keep flags.  The caller then scans keep and klen again and runs launch_prep_gather.
+//   launch_deplete_pairs: hit[r] = 1 for every hit pair (r, leaf) of the screen's call on reads (hit zeroed by the caller).
+//   launch_deplete_mark: a unit (pair_mode 0: kept read u = read kept[u] of the block; 1 either / 2 both: kept fragment u = reads
+//     kept[2u], kept[2u + 1]) is removed iff its row on the screen is not empty — reads: hit[u] or allhit[u]; fragments: row u
+//     of frag_off (nullptr: no row was built) or the all-hit bytes of its mates, as launch_lca_rows reads them.  The reads of a
+//     removed unit get keep = klen = 0 and reason = PREP_DEPLETED; totals[0 .. DEPL_TOT_N) += the call's (zeroed by the caller).
+constexpr uint32_t PREP_DEPLETED = 5;  // = PFQ_PREP_DEPLETED of pfq.h
+enum DepleteTotal { DEPL_TOT_UNITS = 0, DEPL_TOT_READS = 1, DEPL_TOT_BASES = 2, DEPL_TOT_N = 3 };
+struct DepleteArgs {
+    const uint32_t *hit;                     // [n_units] (reads)
+    const uint8_t *allhit;                   // [n_units] (reads), [2 n_units] (fragments): of the screen's call
+    const unsigned long long *frag_off;      // [n_units + 1] (fragments): the screen's final CSR offsets, or nullptr
+    int pair_mode;
+    uint64_t n_units, n_reads;               // n_reads: of the block given to pfq_prep_reads
+    const uint32_t *kept;                    // [n_units or 2 n_units]
+    uint32_t *keep, *klen, *reason;          // [n_reads]
+    unsigned long long *totals;              // [DEPL_TOT_N]
+};
+void launch_deplete_pairs(const uint2 *d_pairs, uint64_t n_pairs, uint64_t n_units, uint32_t *d_hit, hipStream_t st);
+void launch_deplete_mark(const DepleteArgs &a, hipStream_t st);
 void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t len, uint64_t *d_out, hipStream_t st);
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,

@@ -390,6 +390,7 @@ class BloomTree:
                                              C.byref(out)))
         nk = int(out.n_kept)
         self._prep_shape = (nk, int(out.bases_kept))
+        self._prep_reads = n
 
         def arr(p, m):
             if not want_reads:
@@ -478,6 +479,35 @@ class BloomTree:
         ms = C.c_double()
         _ffi.check(_ffi.lib().pfq_debug_last_overlap(self._h, C.byref(ms)))
         return float(ms.value)
+
+    DEPLETE_TOTALS = ("n_units", "units_removed", "reads_removed", "bases_removed", "n_kept", "bases_kept")
+
+    def prep_deplete(self, screen: "BloomTree", threshold: float, paired: bool = False, pair_mode: str = "either") -> dict:
+        """Removes from the block prep_reads() prepared last the units (kept reads; `paired`: kept fragments) that hit `screen`, a
+        second tree on the same device, at `threshold` (pfq_prep_deplete; the rule is pfq.h "depletion").  prep_csr(),
+        query_prep() and a further prep_deplete() then see the remaining units.  `screen`'s counters grow as by a query of the
+        block; this tree's do not change.  Returns the totals DEPLETE_TOTALS and, if the block was prepared with want_reads,
+        kept uint32[n_kept] (indices into the block given to prep_reads) and reason uint32[n_reads] (5 = depleted), else None."""
+        out = _ffi.PrepDepleted()
+        n_reads = getattr(self, "_prep_reads", 0)
+        _ffi.check(_ffi.lib().pfq_prep_deplete(self._h, screen._h, threshold, _pair_flags(paired, pair_mode), C.byref(out)))
+        nk = int(out.n_kept)
+        self._prep_shape = (nk, int(out.bases_kept))
+
+        def arr(p, m):
+            if not p:
+                return None
+            return np.ctypeslib.as_array(p, shape=(m,)).copy() if m else np.zeros(0, dtype=np.uint32)
+        res = {k: int(getattr(out, k)) for k in self.DEPLETE_TOTALS}
+        res.update(kept=arr(out.kept, nk), reason=arr(out.reason, n_reads))
+        return res
+
+    def last_deplete_ms(self) -> Tuple[float, float]:
+        """Device milliseconds of the last prep_deplete(): (the screen's classification, mark + scans + compaction)
+        (pfq_debug_last_deplete)."""
+        ms = (C.c_double * 2)()
+        _ffi.check(_ffi.lib().pfq_debug_last_deplete(self._h, ms))
+        return float(ms[0]), float(ms[1])
 
     def query_prep(self, threshold: float, want_hits: bool = False, want_scores: bool = False, paired: bool = False,
                    pair_mode: str = "either", lca: Optional[str] = None, abundance: bool = False, coverage: bool = False, taxa: bool = False,
