@@ -776,6 +776,59 @@ int pfq_prep_last_overlap(pfq_tree *tree, pfq_prep_overlap *out);
 /* measurements: device milliseconds of the overlap kernel of the last pfq_prep_reads with reads (HIP events) */
 int pfq_debug_last_overlap(pfq_tree *tree, double *ms);
 
+/* ---- mate correction (pfq_tree_set_mate_correct, pfq_prep_last_corrections) ----
+ * Where the mates of a fragment overlap, every base was read twice.  Where the two calls disagree and one has a high quality and the
+ * other a low one, the low one is a sequencing error and the mate says what the base was.  While the correction is set on a tree,
+ * the mate overlap step of every pfq_prep_reads on it rewrites such bases and their qualities on the device, before steps 1 - 5 of
+ * "read preprocessing" and before the gather.  Integers only; a fragment's correction is a pure function of that fragment.
+ * With a[0, L1), b[0, L2), up, comp, O, E, insert, mm as in "mate overlap", qualities q1, q2 (Phred+33), high = H and low = W < H:
+ * Which fragments.  A fragment is corrected only if it was analysed and an insert I was found (below max(L1, L2) or not),
+ * mm(I) > 0, and both mates have qualities (qual given, and has_qual NULL or set for both).  A fragment with an insert and
+ * mm(I) > 0 that lacks qualities counts in n_no_quality.
+ * Which pairs.  For every pair (i, j = I - 1 - i) of the hypothesis I that mm(I) counts, with p1 = max(q1[i] - 33, 0) and
+ * p2 = max(q2[j] - 33, 0):
+ *   if up(a[i]) is one of ACGT, p1 >= H and p2 <= W:  b[j] = comp(up(a[i])), an upper-case letter, and q2[j] = q1[i], the raw byte;
+ *   else if up(b[j]) is one of ACGT, p2 >= H and p1 <= W:  a[i] = comp(up(b[j])) and q1[i] = q2[j];
+ *   else the pair is unresolved and nothing changes.
+ * A low side outside ACGT (an N with quality '#') is therefore repaired; a high side outside ACGT never corrects anything.  Each
+ * base lies in exactly one pair of I, so the order of the pairs does not matter.
+ * What the other steps see.  The adapter step and the overlap step look at the original reads: insert, mismatches, ocut, every
+ * total, the histogram and pfq_prep_last_adapters are unchanged by the correction.  Steps 1 - 5 and the gather see the corrected
+ * bases and qualities, cut at min(cut, ocut) as before.  Hence begin, len, reason, kept, the totals and the prepared CSR equal those
+ * of the same call without the correction on the corrected mates.  A corrected position behind the cut is harmless and is still
+ * reported.
+ * pfq_tree_set_mate_correct: high 0 (off, low is then ignored) or 1 .. 93, low < high; else PFQ_ERR_ARG, the message names the
+ * parameter.  The step needs the mate overlap: with the correction set but no overlap set, or in a pfq_prep_reads without
+ * PFQ_PREP_PAIRED, it does not run.  The state does not depend on the leaves: pfq_tree_prune and pfq_tree_insert keep it;
+ * pfq_tree_save stores nothing of it.  A sticky insertion error is returned as everywhere else.
+ * pfq_prep_last_corrections: the totals of the last pfq_prep_reads — the fragments with a corrected base, the corrected bases per
+ * mate, n_unresolved: the mismatching pairs, in fragments whose mates both have qualities, that were left as they were,
+ * n_no_quality — and, only after a call with PFQ_PREP_WANT_READS (else NULL and n_patches 0), the library-owned patch list,
+ * ascending by (read, pos): read is an index into the block given to pfq_prep_reads, pos is relative to the original read, base and
+ * qual are what the position holds now, old_base and old_qual what it held.  A caller that holds the original records applies the
+ * list to get the corrected ones.  The list has exactly n_bases[0] + n_bases[1] entries, whatever their number, and is valid until
+ * the next pfq_prep_reads on the tree.  PFQ_ERR_STATE if there has been no prep yet or the last one ran without the step.
+ * A call without PFQ_PREP_WANT_READS corrects in the overlap kernel, in place, with no list and no further wait of the host; a
+ * call with it waits once more, for the length of the list.  pfq_debug_last_overlap reports the overlap kernel, the correction
+ * or its counting included; pfq_debug_last_corrections the scan and the patch kernel of a call with PFQ_PREP_WANT_READS. */
+#define PFQ_MATE_CORRECT_HIGH 30   /* the defaults of the CLI and the Python binding */
+#define PFQ_MATE_CORRECT_LOW 14
+int pfq_tree_set_mate_correct(pfq_tree *tree, uint32_t high /* H: 0 off, else 1 .. 93 */, uint32_t low /* W < H */);
+typedef struct pfq_prep_patch {
+    uint32_t read, pos;
+    uint8_t base, qual, old_base, old_qual;
+} pfq_prep_patch;
+typedef struct pfq_prep_corrections {
+    uint64_t n_fragments_corrected;
+    uint64_t n_bases[2];                      /* corrected bases of first and of second mates */
+    uint64_t n_unresolved, n_no_quality;
+    uint64_t n_patches;                       /* n_bases[0] + n_bases[1] after a call with PFQ_PREP_WANT_READS, else 0 */
+    const pfq_prep_patch *patches;            /* [n_patches], only after a call with PFQ_PREP_WANT_READS, else NULL; library-owned */
+} pfq_prep_corrections;
+int pfq_prep_last_corrections(pfq_tree *tree, pfq_prep_corrections *out);
+/* measurements: device milliseconds of the scan and the patch kernel of the last pfq_prep_reads with reads (HIP events) */
+int pfq_debug_last_corrections(pfq_tree *tree, double *ms);
+
 /* ---- depletion (pfq_prep_deplete) ----
  * Host and contaminant screening between the trimmer and the classifier: the units of the block prepared last on `tree` that hit a
  * second tree, the screen, on the same device leave the block before pfq_prep_query sees it.

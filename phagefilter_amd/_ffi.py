@@ -24,6 +24,7 @@ SYMBOLS = [
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_set_adapters", "pfq_prep_last_adapters", "pfq_debug_last_adapters",
     "pfq_tree_set_mate_overlap", "pfq_prep_last_overlap", "pfq_debug_last_overlap",
+    "pfq_tree_set_mate_correct", "pfq_prep_last_corrections", "pfq_debug_last_corrections",
     "pfq_prep_deplete", "pfq_debug_last_deplete",
     "pfq_tree_similarity", "pfq_tree_recluster", "pfq_tree_merges",
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
@@ -157,6 +158,18 @@ class PrepOverlap(C.Structure):
                 ("hist", C.POINTER(C.c_uint64)), ("insert", C.POINTER(C.c_uint32)), ("mismatches", C.POINTER(C.c_uint32))]
 
 
+MATE_CORRECT_HIGH, MATE_CORRECT_LOW = 30, 14
+
+
+class PrepPatch(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("pos", C.c_uint32), ("base", C.c_uint8), ("qual", C.c_uint8), ("old_base", C.c_uint8), ("old_qual", C.c_uint8)]
+
+
+class PrepCorrections(C.Structure):
+    _fields_ = [("n_fragments_corrected", C.c_uint64), ("n_bases", C.c_uint64 * 2), ("n_unresolved", C.c_uint64), ("n_no_quality", C.c_uint64),
+                ("n_patches", C.c_uint64), ("patches", C.POINTER(PrepPatch))]
+
+
 PREP_DEPLETED = 5
 
 
@@ -281,6 +294,10 @@ def lib() -> C.CDLL:
     L.pfq_tree_set_mate_overlap.argtypes = [vp, C.c_uint32, C.c_uint32]
     L.pfq_prep_last_overlap.argtypes = [vp, C.POINTER(PrepOverlap)]
     L.pfq_debug_last_overlap.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "pfq_tree_set_mate_correct"):  # (an older build chosen through PFQ_LIBPFQ for an A/B has no mate correction)
+        L.pfq_tree_set_mate_correct.argtypes = [vp, C.c_uint32, C.c_uint32]
+        L.pfq_prep_last_corrections.argtypes = [vp, C.POINTER(PrepCorrections)]
+        L.pfq_debug_last_corrections.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_prep_deplete.argtypes = [vp, vp, C.c_float, C.c_uint32, C.POINTER(PrepDepleted)]
     L.pfq_debug_last_deplete.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_tree_similarity.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(Similarity)]

@@ -1405,6 +1405,10 @@ struct PrepRun {
     uint32_t mate_overlap = 0, mate_overlap_errors = 10;
     std::atomic<uint64_t> overlap_fragments{0}, overlap_skipped{0}, overlap_found{0}, overlap_readthrough{0}, overlap_reads{0}, overlap_bases{0};
     std::atomic<uint64_t> insert_hist[PFQ_OVERLAP_INSERT_MAX + 1] = {};
+    // --mate-correct / --mate-correct-quality: what every replica's tree is set to (pfq_tree_set_mate_correct; high 0: off) and
+    // what the correction did
+    uint32_t mate_correct_high = 0, mate_correct_low = 0;
+    std::atomic<uint64_t> corrected_fragments{0}, corrected_bases{0}, correct_unresolved{0}, correct_no_quality{0};
     // --deplete DIR [..] / --deplete-threshold T: the screens in the order given, every replica's own copies of them on its device
     // (screens_of: by the replica's tree; filled before the loop starts, only read afterwards) and what every screen removed
     static constexpr size_t DEPLETE_MAX = 4;
@@ -1414,9 +1418,11 @@ struct PrepRun {
     std::map<pfq_tree *, std::vector<pfq_tree *>> screens_of;
     std::atomic<uint64_t> depleted_units[DEPLETE_MAX] = {}, depleted_reads[DEPLETE_MAX] = {}, depleted_bases[DEPLETE_MAX] = {};
 };
-// What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending
+// What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending; with
+// --mate-correct the call's patch list (read relative to r0), ascending by (read, pos)
 struct PrepKept {
     std::vector<uint32_t> begin, len, kept;
+    std::vector<pfq_prep_patch> patches;
 };
 // Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
 // scores; keep_lca: the units' LCAs of a PFQ_WANT_LCA call) are copied out of the library's buffers, which the next call on
@@ -1431,6 +1437,7 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         pk->begin.clear();
         pk->len.clear();
         pk->kept.clear();
+        pk->patches.clear();
     }
     if (want) {
         h.off.assign(units + 1, 0);
@@ -1453,7 +1460,7 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         qual.assign(b.off[r1] - base, 0);
         has.assign(r1 - r0, 0);
         bool any_qual = false;
-        if (prep->params.trim_quality && !b.has_qual.empty())
+        if ((prep->params.trim_quality || prep->mate_correct_high) && !b.has_qual.empty())  // (the two steps that look at qualities)
             for (uint64_t r = r0; r < r1; ++r) {
                 if (!b.has_qual[r]) continue;
                 const std::string_view q = b.quality(r);
@@ -1491,6 +1498,15 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
             prep->overlap_bases += ov.bases_cut;
             for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
                 if (ov.hist[i]) prep->insert_hist[i] += ov.hist[i];
+            if (prep->mate_correct_high) {
+                pfq_prep_corrections co{};
+                if (pfq_prep_last_corrections(tree, &co) != PFQ_OK) fail_from_thread(pfq_last_error());
+                prep->corrected_fragments += co.n_fragments_corrected;
+                prep->corrected_bases += co.n_bases[0] + co.n_bases[1];
+                prep->correct_unresolved += co.n_unresolved;
+                prep->correct_no_quality += co.n_no_quality;
+                if (pk) pk->patches.assign(co.patches, co.patches + co.n_patches);
+            }
         }
         // --deplete: the screens take their units out of the prepared block, one after the other; a fragment leaves when either
         // mate hits.  What is mapped back is what the last screen left.
@@ -1591,8 +1607,10 @@ std::vector<uint64_t> keep_prepared(Batch &b, const std::vector<uint64_t> &share
     std::vector<uint64_t> cuts(pks.size() + 1, 0);
     for (size_t i = 0; i < pks.size(); ++i) {
         const PrepKept &pk = pks[i];
+        size_t pi = 0;  // (--mate-correct: the patches and the kept reads both ascend)
         for (uint32_t j : pk.kept) {
             const uint64_t r = share[i] + j, s0 = b.off[r] + pk.begin[j], len = pk.len[j];
+            const uint64_t at = nb.seq.size(), qat = nb.qual.size();
             nb.seq.insert(nb.seq.end(), b.seq.begin() + s0, b.seq.begin() + s0 + len);
             nb.off.push_back(nb.seq.size());
             const std::string_view id = b.id(r), q = b.quality(r);
@@ -1600,6 +1618,14 @@ std::vector<uint64_t> keep_prepared(Batch &b, const std::vector<uint64_t> &share
             nb.id_off.push_back(nb.id_bytes.size());
             if (q.size() == b.off[r + 1] - b.off[r]) nb.qual.insert(nb.qual.end(), q.begin() + pk.begin[j], q.begin() + pk.begin[j] + len);
             else nb.qual.insert(nb.qual.end(), q.begin(), q.end());
+            // the corrections that lie in what is kept of the read (a corrected read has qualities as long as its bases)
+            while (pi < pk.patches.size() && pk.patches[pi].read < j) ++pi;
+            for (; pi < pk.patches.size() && pk.patches[pi].read == j; ++pi) {
+                const pfq_prep_patch &pt = pk.patches[pi];
+                if (pt.pos < pk.begin[j] || pt.pos >= pk.begin[j] + len) continue;
+                nb.seq[at + (pt.pos - pk.begin[j])] = pt.base;
+                nb.qual[qat + (pt.pos - pk.begin[j])] = (char)pt.qual;
+            }
             nb.qual_off.push_back(nb.qual.size());
             nb.has_qual.push_back(b.has_qual[r]);
         }
@@ -2659,7 +2685,7 @@ int cmd_query(int argc, char **argv) {
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
                              {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
                              {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}, {"deplete", 0, true, true},
-                             {"deplete-threshold", 0, true}};
+                             {"deplete-threshold", 0, true}, {"mate-correct", 0, false}, {"mate-correct-quality", 0, true}};
     Args a = parse(argc, argv, 2, opts);
     const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
     const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
@@ -2762,12 +2788,12 @@ int cmd_query(int argc, char **argv) {
         const std::string why = ": it formats the POS / NEG records of single reads, and nothing else, on the device";
         if (a.flags.count("device-parse"))
             die("error: '--device-output' cannot be used with '--device-parse': that option serves runs that only count, this one parses the text itself");
-        for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits"})
+        for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits", "mate-correct"})
             if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         for (const char *other : {"deplete", "deplete-threshold"})  // (first: whatever else turns preprocessing on, the refusal names this one)
             if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
-                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors"})
+                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors", "mate-correct-quality"})
             if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
         if (lca == 2) die("error: '--device-output' cannot be used with '--lca best': the best hits need every read's scores");
         if (!filtering) die("error: '--device-output' needs '--pos-filter' or '--neg-filter' (or both): they are the outputs it makes");
@@ -2814,6 +2840,12 @@ int cmd_query(int argc, char **argv) {
     // --trim-quality Q, --trim-window W, --trim-poly-x P, --min-length L, --max-n N, --min-complexity C: any of them turns read
     // preprocessing on: every call trims and filters its reads on the device (pfq_prep_reads) and classifies what is kept
     // (pfq_prep_query); PREPROCESS.tsv holds the totals.  --min-length then defaults to the database's k.
+    // --mate-correct [--mate-correct-quality HI[,LO]]: part of the mate overlap step, so it needs --mate-overlap and is refused
+    // wherever that is
+    const bool mate_correct = a.flags.count("mate-correct") != 0;
+    if (a.val.count("mate-correct-quality") && !mate_correct) die("error: '--mate-correct-quality' needs '--mate-correct'");
+    if (mate_correct && !a.val.count("mate-overlap"))
+        die("error: '--mate-correct' needs '--mate-overlap <O>': it corrects the bases on which the overlapping mates of a fragment disagree");
     static PrepRun prep_run;
     const char *prep_first = nullptr;
     for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2", "adapter-overlap",
@@ -2884,6 +2916,25 @@ int cmd_query(int argc, char **argv) {
                 die("error: '--mate-overlap' needs '--reads2 <FILE>' or '--interleaved': it compares the two mates of a fragment");
             prep_run.mate_overlap = number("mate-overlap", "30", 1, PFQ_OVERLAP_LEN_MAX, "an overlap of 1 to 512 bases");
             prep_run.mate_overlap_errors = number("mate-overlap-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
+        }
+        // --mate-correct [--mate-correct-quality HI[,LO]]: where the mates disagree inside their overlap, a base of quality LO or less
+        // takes what the mate says if that one's quality is HI or more (pfq.h "mate correction"), before the steps above
+        if (mate_correct) {
+            const std::string v = opt(a, "mate-correct-quality", "30,14");
+            const std::string bad = "error: invalid value '" + v + "' for '--mate-correct-quality': HI[,LO], Phred qualities with 1 <= HI <= 93 and LO < HI (default 30,14)";
+            const size_t comma = v.find(',');
+            const std::string part[2] = {v.substr(0, comma), comma == std::string::npos ? std::string("14") : v.substr(comma + 1)};
+            uint32_t val[2] = {0, 0};
+            for (int i = 0; i < 2; ++i) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long x = strtoull(part[i].c_str(), &end, 10);
+                if (part[i].empty() || !isdigit((unsigned char)part[i][0]) || *end || errno || x > 93) die(bad);
+                val[i] = (uint32_t)x;
+            }
+            if (val[0] < 1 || val[1] >= val[0]) die(bad);
+            prep_run.mate_correct_high = val[0];
+            prep_run.mate_correct_low = val[1];
         }
         if (a.val.count("deplete")) {
             const std::string list = a.val.at("deplete") + ",";  // (the parser joins a repeated option's values with ',')
@@ -2983,6 +3034,8 @@ int cmd_query(int argc, char **argv) {
     }
     if (prep_run.mate_overlap)
         for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_overlap(tree, prep_run.mate_overlap, prep_run.mate_overlap_errors));
+    if (prep_run.mate_correct_high)
+        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_correct(tree, prep_run.mate_correct_high, prep_run.mate_correct_low));
     // --deplete: every replica gets its own copy of every screen on its device (the screens' memory once per replica)
     std::vector<std::unique_ptr<ServedDb>> screens;
     for (const std::string &dir : prep_run.deplete_dirs) {
@@ -3086,6 +3139,10 @@ int cmd_query(int argc, char **argv) {
                     (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(), (unsigned long long)pr.overlap_bases.load());
             fprintf(f, "mate_overlap\t%u\nmate_overlap_errors\t%u\n", pr.mate_overlap, pr.mate_overlap_errors);
         }
+        if (pr.mate_correct_high)  // behind the overlap rows: what the correction did and its parameters
+            fprintf(f, "corrected_fragments\t%llu\ncorrected_bases\t%llu\ncorrect_unresolved\t%llu\ncorrect_no_quality\t%llu\nmate_correct_quality\t%u\nmate_correct_low\t%u\n",
+                    (unsigned long long)pr.corrected_fragments.load(), (unsigned long long)pr.corrected_bases.load(), (unsigned long long)pr.correct_unresolved.load(),
+                    (unsigned long long)pr.correct_no_quality.load(), pr.mate_correct_high, pr.mate_correct_low);
         for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)  // behind the overlap rows: per screen, in the order given
             fprintf(f, "deplete_db\t%s\ndeplete_threshold\t%s\ndepleted_units\t%llu\ndepleted_reads\t%llu\ndepleted_bases\t%llu\n", pr.deplete_dirs[i].c_str(),
                     pr.deplete_threshold_typed.c_str(), (unsigned long long)pr.depleted_units[i].load(), (unsigned long long)pr.depleted_reads[i].load(),
@@ -3115,6 +3172,10 @@ int cmd_query(int argc, char **argv) {
             fprintf(stderr, "; mates overlap in %llu of %llu fragments, %llu with read-through: %llu reads cut (%llu bases)", (unsigned long long)pr.overlap_found.load(),
                     (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(),
                     (unsigned long long)pr.overlap_bases.load());
+        if (pr.mate_correct_high)
+            fprintf(stderr, "; %llu bases corrected in %llu fragments (%llu mismatches unresolved, %llu fragments without qualities)",
+                    (unsigned long long)pr.corrected_bases.load(), (unsigned long long)pr.corrected_fragments.load(), (unsigned long long)pr.correct_unresolved.load(),
+                    (unsigned long long)pr.correct_no_quality.load());
         for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)
             fprintf(stderr, "; screen %s took %llu reads (%llu bases)", pr.deplete_dirs[i].c_str(), (unsigned long long)pr.depleted_reads[i].load(),
                     (unsigned long long)pr.depleted_bases[i].load());
@@ -3675,6 +3736,15 @@ void usage() {
             "fragments looked at), overlap_skipped, overlap_found, overlap_readthrough (insert shorter than a mate), overlap_reads,\n"
             "overlap_bases (reads and bases cut), mate_overlap and mate_overlap_errors, and INSERT_SIZES.tsv in --out holds\n"
             "\"insert<TAB>fragments\", one line per insert length found, ascending\n"
+            "--mate-correct [--mate-correct-quality <HI[,LO]>]: inside the overlap every base was read twice.  Where the mates disagree\n"
+            "there, a base with Phred quality LO or less (default 14; an N too) takes what its mate says, and the mate's quality, if\n"
+            "that one is ACGT with quality HI or more (default 30); other disagreements stay as they are.  On the GPU, as part of the\n"
+            "--mate-overlap step, which it needs, and before trimming: at -f 1.0 one wrong base hides a read from every genome, and the 3'\n"
+            "end of the second mate is where they are.  The insert and the cuts are found on the reads as they came; trimming, --deplete,\n"
+            "the classification, --scores, POS and NEG records see the corrected bases and qualities.  A read without qualities (FASTA, or\n"
+            "a quality line of another length) is never corrected.  Refused where --mate-overlap is.  PREPROCESS.tsv then also holds\n"
+            "corrected_fragments, corrected_bases, correct_unresolved (disagreements left), correct_no_quality (fragments with\n"
+            "disagreements but without qualities), mate_correct_quality and mate_correct_low\n"
             "--deplete <DIR> [--deplete <DIR2> ..] [--deplete-threshold <T>]: reads of the host, of PhiX and of the lab's usual\n"
             "contaminants are thrown away before anything is counted: every DIR is a database (a screen), and behind the steps above every\n"
             "read that hits a genome of a screen at T (default: the run's -f) is taken out on the GPU before the classification, which so\n"

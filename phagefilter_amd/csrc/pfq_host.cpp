@@ -508,6 +508,17 @@ struct pfq_tree {
     pfq_prep_overlap ov_out{};
     std::vector<uint64_t> out_ov_hist;
     std::vector<uint32_t> out_ov_insert, out_ov_mm;
+    // pfq_tree_set_mate_correct (mc_high > 0: on) and what the correction of the last paired pfq_prep_reads left: the totals
+    // (h_pp_tot behind the overlap's, then the length of the patch list) and, for a PFQ_PREP_WANT_READS call only, the
+    // corrections per fragment, their scan and the patch list.  mc_last: the last prep ran the correction.
+    uint32_t mc_high = 0, mc_low = 0;
+    bool mc_last = false, mc_last_reads = false, mc_timed = false;
+    DevBuf<unsigned long long> d_pp_ctot, d_pp_cat;
+    DevBuf<uint32_t> d_pp_ccnt;
+    DevBuf<pfq::CorPatch> d_pp_patch;
+    hipEvent_t mc_time[2] = {nullptr, nullptr};  // pfq_debug_last_corrections: the scan and the patch kernel
+    pfq_prep_corrections mc_out{};
+    std::vector<pfq_prep_patch> out_mc_patch;
     std::vector<uint32_t> out_lca;
     bool lca_last = false;                 // the last query call set PFQ_WANT_LCA
     uint64_t lca_units = 0;
@@ -3448,6 +3459,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
                         t.d_pp_cut.bytes() + t.d_pp_which.bytes() + t.d_pp_atot.bytes() +  // (the adapter step)
                         t.d_pp_oins.bytes() + t.d_pp_omm.bytes() + t.d_pp_ecut.bytes() + t.d_pp_otot.bytes() +  // (the mate overlap step)
+                        t.d_pp_ctot.bytes() + t.d_pp_cat.bytes() + t.d_pp_ccnt.bytes() + t.d_pp_patch.bytes() +  // (the mate correction)
                         t.d_dp_hit.bytes() + t.d_dp_tot.bytes() +  // (pfq_prep_deplete)
                         t.d_fm_idb.bytes() + t.d_fm_idl.bytes() + t.d_fm_len[0].bytes() + t.d_fm_len[1].bytes() + t.d_fm_long.bytes() +  // (pfq_text_format)
                         t.d_fm_name_off.bytes() + t.d_fm_hash.bytes() + t.d_fm_dst[0].bytes() + t.d_fm_dst[1].bytes() + t.d_fm_sums.bytes() +
@@ -3508,6 +3520,8 @@ void pfq_tree_close(pfq_tree *tree) {
     for (auto e : tree->ad_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->ov_time)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->mc_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->fm_time)
         if (e) (void)hipEventDestroy(e);
@@ -3962,6 +3976,8 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     const bool paired = (pr.flags & PFQ_PREP_PAIRED) != 0, want_reads = (pr.flags & PFQ_PREP_WANT_READS) != 0;
     if (paired && (n_reads & 1)) return fail(PFQ_ERR_ARG, "PFQ_PREP_PAIRED needs an even number of reads (mates 2i, 2i + 1)");
     const bool overlap = paired && tree->ov_on;  // (the mate overlap step needs mates)
+    const bool correct = overlap && tree->mc_high > 0;  // (the correction is part of that step)
+    constexpr size_t at_ctot = pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N + pfq::OVL_TOT_N + pfq::OVL_HIST;  // in h_pp_tot; the patches' number behind
     constexpr size_t n_otot = pfq::OVL_TOT_N + pfq::OVL_HIST;
     if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: 2^31 - 1024 reads or more in one block: ask in pieces");
     PFQ_TRY(use_device(tree->device));
@@ -3976,12 +3992,15 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         for (auto &e : t.pp_time) HIP_TRY(hipEventCreate(&e));
         for (auto &e : t.ad_time) HIP_TRY(hipEventCreate(&e));
         for (auto &e : t.ov_time) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N + pfq::OVL_TOT_N + pfq::OVL_HIST) * 8, hipHostMallocDefault));
+        for (auto &e : t.mc_time) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (at_ctot + pfq::COR_TOT_N + 1) * 8, hipHostMallocDefault));
         HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
     }
     const bool adapters = t.ad_on;
     t.ad_last = false;
     t.ov_last = false;
+    t.mc_last = false;
+    uint64_t n_patches = 0;
     hipStream_t st = t.copy_stream;
     const int slot = t.pp_slot ^ 1;
     if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));  // the classification that read this set is done
@@ -4068,9 +4087,40 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             ov.mismatches = t.d_pp_omm.p;
             ov.cut = t.d_pp_ecut.p;
             ov.totals = t.d_pp_otot.p;
+            if (correct) {  // (the adapter kernel, launched above, has read the reads as they came)
+                HIP_TRY(t.d_pp_ctot.ensure(pfq::COR_TOT_N));
+                HIP_TRY(hipMemsetAsync(t.d_pp_ctot.p, 0, pfq::COR_TOT_N * 8, st));
+                ov.cor_high = t.mc_high;
+                ov.cor_low = t.mc_low;
+                ov.cor_seq = t.d_pp_in.p;
+                ov.cor_qual = qual ? t.d_pp_qual.p : nullptr;
+                ov.has_qual = a.has_qual;
+                ov.cor_totals = t.d_pp_ctot.p;
+                if (want_reads) {  // the kernel counts, launch_prep_patches below lists and corrects
+                    HIP_TRY(t.d_pp_ccnt.ensure(n_reads / 2));
+                    HIP_TRY(t.d_pp_cat.ensure(n_reads / 2 + 1));
+                    HIP_TRY(hipMemsetAsync(t.d_pp_ccnt.p, 0, n_reads / 2 * 4, st));
+                    ov.cor_count = t.d_pp_ccnt.p;
+                }
+            }
             HIP_TRY(hipEventRecord(t.ov_time[0], st));
             pfq::launch_prep_overlap(ov, st);
             HIP_TRY(hipEventRecord(t.ov_time[1], st));
+            if (correct && want_reads) {
+                // the list's length decides its buffer, so the host waits for it here: once more than a call without the list
+                HIP_TRY(hipEventRecord(t.mc_time[0], st));
+                pfq::launch_scan_u32(t.d_pp_ccnt.p, n_reads / 2, t.d_pp_sums.p, t.d_pp_cat.p, st);
+                HIP_TRY(hipMemcpyAsync(t.h_pp_tot + at_ctot + pfq::COR_TOT_N, t.d_pp_cat.p + n_reads / 2, 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                n_patches = t.h_pp_tot[at_ctot + pfq::COR_TOT_N];
+                if (n_patches) {
+                    HIP_TRY(t.d_pp_patch.ensure(n_patches));
+                    ov.cor_at = t.d_pp_cat.p;
+                    ov.patches = t.d_pp_patch.p;
+                    pfq::launch_prep_patches(ov, st);
+                }
+                HIP_TRY(hipEventRecord(t.mc_time[1], st));
+            }
             a.cut = t.d_pp_ecut.p;
         }
         HIP_TRY(hipEventRecord(t.pp_time[0], st));
@@ -4087,10 +4137,12 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
         if (adapters) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1, t.d_pp_atot.p, pfq::ADAPT_TOT_N * 8, hipMemcpyDeviceToHost, st));
         if (overlap) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N, t.d_pp_otot.p, n_otot * 8, hipMemcpyDeviceToHost, st));
+        if (correct) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + at_ctot, t.d_pp_ctot.p, pfq::COR_TOT_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffers are free from here)
         t.pp_timed = true;
         t.ad_timed = adapters;
         t.ov_timed = overlap;
+        t.mc_timed = correct && want_reads;
         if (t.h_pp_tot[pfq::PREP_TOT_ERR])
             return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: a read of 2^32 bases or more (or offsets that do not ascend)");
         n_kept = t.h_pp_tot[pfq::PREP_TOT_N];
@@ -4143,6 +4195,22 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             for (uint32_t i = 0; i < pfq::OVL_HIST; ++i) t.out_ov_hist[i] = ot[pfq::OVL_TOT_N + i];
         }
     }
+    if (correct) {
+        t.mc_out = pfq_prep_corrections{};
+        if (want_reads) {
+            t.out_mc_patch.resize(std::max<uint64_t>(n_patches, 1));  // (never NULL with the flag)
+            if (n_patches) HIP_TRY(hipMemcpyAsync(t.out_mc_patch.data(), t.d_pp_patch.p, n_patches * sizeof(pfq_prep_patch), hipMemcpyDeviceToHost, st));
+            t.mc_out.n_patches = n_patches;
+        }
+        if (n_reads) {
+            const unsigned long long *ct = t.h_pp_tot + at_ctot;
+            t.mc_out.n_fragments_corrected = ct[pfq::COR_TOT_FRAGMENTS];
+            t.mc_out.n_bases[0] = ct[pfq::COR_TOT_BASES];
+            t.mc_out.n_bases[1] = ct[pfq::COR_TOT_BASES + 1];
+            t.mc_out.n_unresolved = ct[pfq::COR_TOT_UNRESOLVED];
+            t.mc_out.n_no_quality = ct[pfq::COR_TOT_NO_QUALITY];
+        }
+    }
     if (adapters) {
         t.ad_out = pfq_prep_adapters{};
         t.ad_out.n_reads = n_reads;
@@ -4173,6 +4241,8 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     t.ad_last_reads = adapters && want_reads;
     t.ov_last = overlap;
     t.ov_last_reads = overlap && want_reads;
+    t.mc_last = correct;
+    t.mc_last_reads = correct && want_reads;
     return PFQ_OK;
 }
 
@@ -4288,6 +4358,46 @@ int pfq_debug_last_overlap(pfq_tree *tree, double *ms) {
     PFQ_TRY(use_device(tree->device));
     float v = 0.0f;
     HIP_TRY(hipEventElapsedTime(&v, tree->ov_time[0], tree->ov_time[1]));
+    *ms = v;
+    return PFQ_OK;
+}
+
+// ---- mate correction ---------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(pfq_prep_patch) == sizeof(pfq::CorPatch) && sizeof(pfq_prep_patch) == 12, "the kernel writes pfq_prep_patch");
+
+int pfq_tree_set_mate_correct(pfq_tree *tree, uint32_t high, uint32_t low) {
+    if (!tree) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(insertion_error(*tree));
+    pfq_tree &t = *tree;
+    if (high == 0) {
+        t.mc_high = t.mc_low = 0;
+        return PFQ_OK;
+    }
+    if (high > 93) return fail(PFQ_ERR_ARG, "pfq_tree_set_mate_correct: high must be 0 (off) or 1 .. 93, not " + std::to_string(high));
+    if (low >= high) return fail(PFQ_ERR_ARG, "pfq_tree_set_mate_correct: low must be below high = " + std::to_string(high) + ", not " + std::to_string(low));
+    t.mc_high = high;
+    t.mc_low = low;
+    return PFQ_OK;
+}
+
+int pfq_prep_last_corrections(pfq_tree *tree, pfq_prep_corrections *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_prep_last_corrections before a pfq_prep_reads on this tree");
+    if (!tree->mc_last)
+        return fail(PFQ_ERR_STATE, "pfq_prep_last_corrections: the last pfq_prep_reads on this tree ran without the mate correction (pfq_tree_set_mate_correct, pfq_tree_set_mate_overlap and PFQ_PREP_PAIRED)");
+    *out = tree->mc_out;
+    if (tree->mc_last_reads) out->patches = tree->out_mc_patch.data();
+    return PFQ_OK;
+}
+
+int pfq_debug_last_corrections(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->pp_timed || !tree->mc_timed)
+        return fail(PFQ_ERR_STATE, "pfq_debug_last_corrections: the last pfq_prep_reads with reads on this tree wrote no patch list (the mate correction and PFQ_PREP_WANT_READS)");
+    PFQ_TRY(use_device(tree->device));
+    float v = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&v, tree->mc_time[0], tree->mc_time[1]));
     *ms = v;
     return PFQ_OK;
 }

@@ -776,6 +776,11 @@ struct AdaptArgs {
 // behind the counters.  A fragment with a mate of more than OVL_LEN_MAX bases is skipped: no insert, cut = the adapter's or L.
 constexpr uint32_t OVL_LEN_MAX = 512, OVL_HIST = 2 * OVL_LEN_MAX + 1;  // = PFQ_OVERLAP_LEN_MAX, PFQ_OVERLAP_INSERT_MAX + 1 of pfq.h
 enum OvlTotal { OVL_TOT_ANALYSED = 0, OVL_TOT_SKIPPED = 1, OVL_TOT_FOUND = 2, OVL_TOT_THROUGH = 3, OVL_TOT_READS = 4, OVL_TOT_BASES = 5, OVL_TOT_N = 6 };
+enum CorTotal { COR_TOT_FRAGMENTS = 0, COR_TOT_BASES = 1 /* , 2: per mate */, COR_TOT_UNRESOLVED = 3, COR_TOT_NO_QUALITY = 4, COR_TOT_N = 5 };
+struct CorPatch {                            // = pfq_prep_patch of pfq.h
+    uint32_t read, pos;
+    uint8_t base, qual, old_base, old_qual;
+};
 struct OverlapArgs {
     const uint8_t *seq;                      // as PrepArgs
     const uint64_t *off;
@@ -785,9 +790,22 @@ struct OverlapArgs {
     uint32_t *insert, *mismatches;           // [n_reads / 2]
     uint32_t *cut;                           // [n_reads]
     unsigned long long *totals;              // [OVL_TOT_N + OVL_HIST]
+    // mate correction (the rule is pfq.h "mate correction"): cor_high == 0: off, and nothing below is looked at
+    uint32_t cor_high, cor_low;
+    uint8_t *cor_seq, *cor_qual;             // seq and the qualities that share off with it, writable; cor_qual nullptr: no read has qualities
+    const uint8_t *has_qual;                 // [n_reads] or nullptr: every read has
+    unsigned long long *cor_totals;          // [COR_TOT_N], zeroed by the caller
+    uint32_t *cor_count;                     // [n_reads / 2] zeroed by the caller: the overlap kernel leaves the reads as they are and writes
+                                             // the corrections of a fragment that has any, for launch_prep_patches; nullptr: it corrects in place
+    const unsigned long long *cor_at;        // [n_reads / 2 + 1] the exclusive scan of cor_count (launch_prep_patches)
+    CorPatch *patches;                       // [cor_at[n_reads / 2]] (launch_prep_patches)
 };
 void launch_prep_adapter(const AdaptArgs &a, hipStream_t st);
+// cor_high == 0: the kernel without the correction; else the build with it
 void launch_prep_overlap(const OverlapArgs &a, hipStream_t st);
+// behind launch_prep_overlap with cor_count and the scan of it: a wave per fragment with corrections writes its patches at
+// cor_at[f], ascending by (read, pos), from the reads as they came, and then corrects them
+void launch_prep_patches(const OverlapArgs &a, hipStream_t st);
 void launch_prep_trim(const PrepArgs &a, hipStream_t st);
 void launch_prep_mark(const PrepArgs &a, hipStream_t st);
 void launch_prep_gather(const PrepArgs &a, hipStream_t st);

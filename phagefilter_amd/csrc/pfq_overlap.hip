@@ -11,6 +11,14 @@
 //
 // Nothing per candidate touches global memory.  The totals and the histogram of the inserts gather in LDS and leave the block
 // as one atomic per counter that is not zero.
+//
+// Mate correction (pfq.h "mate correction", DESIGN.md "Mate correction") is a second build of the kernel, chosen on the host:
+// a fragment whose insert has mismatches recomputes the mismatch word of that one hypothesis from the planes still in LDS, and
+// the lane of a word takes its set bits one by one: two quality bytes from global memory, the rule, a byte store each for the
+// base and its quality.  Byte stores only: the bytes beside a mate are another wave's.
+//   k_prep_patches   for calls that want the patch list: the overlap kernel then only counts a fragment's corrections, a scan
+//                    gives every fragment its place in the list, and this kernel, a wave per fragment that has any, writes the
+//                    patches from the reads as they came, ascending by (read, pos), and then corrects them.
 #include "pfq_prep_groups.h"
 
 namespace pfq {
@@ -130,13 +138,40 @@ __device__ __forceinline__ uint32_t overlap_one(const Fragment &x, uint32_t O, u
     return NONE;
 }
 
+// The mismatching pairs of the hypothesis I, which overlap_one found: lane w gets the word bad & overlap_mask(o, w) of the
+// candidate loop, read from the planes overlap_one left in p.  Bit 2 t of lane w is pair m = 16 w + t: (i, j) = (i0 + m, j0 - m).
+__device__ __forceinline__ uint32_t mismatch_word(const Fragment &x, uint32_t I, const uint32_t *p, uint32_t &i0, uint32_t &j0) {
+    const uint32_t w = Wave::rank(), L1 = x.L1, L2 = x.L2;
+    const int32_t d = (int32_t)I - (int32_t)L2;
+    const uint32_t s = (uint32_t)(d >= 0 ? d : -d), px = d >= 0 ? OVL_A : OVL_R, py = d >= 0 ? OVL_R : OVL_A;
+    const uint32_t o = min(d >= 0 ? L2 : L1, (d >= 0 ? L1 : L2) - s);
+    i0 = d >= 0 ? s : 0u;
+    j0 = L2 - 1u - (d >= 0 ? 0u : s);
+    const uint32_t k = s >> 4, by = 2u * (s & 15u), nw = (o + 15u) >> 4;
+    if (w >= nw) return 0;
+    const uint32_t v = __builtin_amdgcn_alignbit(p[px + k + w + 1u], p[px + k + w], by) ^ p[py + w];
+    const uint32_t bad = v | (v >> 1) | __builtin_amdgcn_alignbit(p[px + OVL_PLANE + k + w + 1u], p[px + OVL_PLANE + k + w], by) | p[py + OVL_PLANE + w];
+    return bad & overlap_mask(o, w);
+}
+
+__device__ __forceinline__ uint32_t comp_of(uint32_t u) { return u == 'A' ? 'T' : u == 'T' ? 'A' : u == 'C' ? 'G' : 'C'; }
+
+// A mismatching pair by the rule: 1: mate 2's base becomes comp(up(ca)) with qa, 2: mate 1's becomes comp(up(cb)) with qb, 0: unresolved.
+__device__ __forceinline__ uint32_t correct_pair(uint32_t ca, uint32_t cb, uint32_t qa, uint32_t qb, uint32_t high, uint32_t low) {
+    const uint32_t pa = qa > 33u ? qa - 33u : 0u, pb = qb > 33u ? qb - 33u : 0u;
+    if (!is_n(up(ca)) && pa >= high && pb <= low) return 1;
+    if (!is_n(up(cb)) && pb >= high && pa <= low) return 2;
+    return 0;
+}
+
 // (eight waves a SIMD: 64 VGPRs)
+template <bool CORRECT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) k_prep_overlap(OverlapArgs a) {
     __shared__ uint32_t s_planes[4 * OVL_GROUP];
     __shared__ uint32_t s_hist[OVL_HIST];
-    __shared__ unsigned long long s_tot[OVL_TOT_N];
+    __shared__ unsigned long long s_tot[OVL_TOT_N + (CORRECT ? COR_TOT_N : 0u)];  // (the correction's behind the step's own)
     for (uint32_t i = threadIdx.x; i < OVL_HIST; i += 256u) s_hist[i] = 0;
-    if (threadIdx.x < OVL_TOT_N) s_tot[threadIdx.x] = 0;
+    if (threadIdx.x < OVL_TOT_N + (CORRECT ? COR_TOT_N : 0u)) s_tot[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t g = threadIdx.x >> 6;
     const uint64_t n_frag = a.n_reads / 2u;
@@ -149,6 +184,43 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
         const bool skipped = x.skipped();
         uint32_t insert = NONE, mm = 0;
         if (!skipped) insert = overlap_one(x, a.min_overlap, a.max_error_percent, s_planes + g * OVL_GROUP, mm);
+        if (CORRECT && mm) {  // (uniform in the wave; mm > 0: an insert was found)
+            const bool has = a.cor_qual && (!a.has_qual || (a.has_qual[2u * f] && a.has_qual[2u * f + 1u]));
+            uint32_t n1 = 0, n2 = 0, nu = 0;
+            if (has) {
+                uint32_t i0, j0;
+                uint32_t word = mismatch_word(x, insert, s_planes + g * OVL_GROUP, i0, j0);
+                const uint64_t at1 = a.off[2u * f] + i0 + 16u * Wave::rank(), at2 = a.off[2u * f + 1u] + j0 - 16u * Wave::rank();
+                while (word) {  // (rare: a few bits a fragment)
+                    const uint32_t t = (uint32_t)(__ffs((int)word) - 1) >> 1;
+                    word &= word - 1u;
+                    const uint64_t ia = at1 + t, jb = at2 - t;
+                    const uint32_t ca = a.cor_seq[ia], cb = a.cor_seq[jb], qa = a.cor_qual[ia], qb = a.cor_qual[jb];
+                    const uint32_t r = correct_pair(ca, cb, qa, qb, a.cor_high, a.cor_low);
+                    if (r == 1) {
+                        if (!a.cor_count) a.cor_seq[jb] = (uint8_t)comp_of(up(ca)), a.cor_qual[jb] = (uint8_t)qa;
+                        ++n2;
+                    } else if (r == 2) {
+                        if (!a.cor_count) a.cor_seq[ia] = (uint8_t)comp_of(up(cb)), a.cor_qual[ia] = (uint8_t)qb;
+                        ++n1;
+                    } else {
+                        ++nu;
+                    }
+                }
+                const uint32_t all = Wave::gsum(n1 | (n2 << 10) | (nu << 20), nullptr);  // (each at most 512)
+                n1 = all & 1023u, n2 = (all >> 10) & 1023u, nu = all >> 20;
+            }
+            if (Wave::rank() == 0) {
+                if (!has) atomicAdd(s_tot + OVL_TOT_N + COR_TOT_NO_QUALITY, 1ull);
+                if (n1 + n2) {
+                    atomicAdd(s_tot + OVL_TOT_N + COR_TOT_FRAGMENTS, 1ull);
+                    if (n1) atomicAdd(s_tot + OVL_TOT_N + COR_TOT_BASES, (unsigned long long)n1);
+                    if (n2) atomicAdd(s_tot + OVL_TOT_N + COR_TOT_BASES + 1u, (unsigned long long)n2);
+                    if (a.cor_count) a.cor_count[f] = n1 + n2;
+                }
+                if (nu) atomicAdd(s_tot + OVL_TOT_N + COR_TOT_UNRESOLVED, (unsigned long long)nu);
+            }
+        }
         if (Wave::rank() == 0) {
             const uint32_t L1 = x.L1, L2 = x.L2;
             const uint32_t c1 = min(L1, insert), c2 = min(L2, insert);
@@ -173,6 +245,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
     if (threadIdx.x < OVL_TOT_N) {  // one atomic per block and counter
         const unsigned long long v = s_tot[threadIdx.x];
         if (v) atomicAdd(a.totals + threadIdx.x, v);
+    } else if (CORRECT && threadIdx.x < OVL_TOT_N + COR_TOT_N) {
+        const unsigned long long v = s_tot[threadIdx.x];
+        if (v) atomicAdd(a.cor_totals + (threadIdx.x - OVL_TOT_N), v);
     }
     for (uint32_t i = threadIdx.x; i < OVL_HIST; i += 256u) {
         const uint32_t v = s_hist[i];
@@ -184,7 +259,74 @@ void launch_prep_overlap(const OverlapArgs &a, hipStream_t st) {
     if (a.n_reads < 2) return;
     // eight blocks a CU: what a wave does for a fragment is a chain of short steps, and it is the other waves that fill its gaps
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2u * PREP_GRID, (a.n_reads / 2u + 3u) / 4u));
-    hipLaunchKernelGGL(k_prep_overlap, dim3(grid), dim3(256), 0, st, a);
+    if (a.cor_high)
+        hipLaunchKernelGGL(k_prep_overlap<true>, dim3(grid), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(k_prep_overlap<false>, dim3(grid), dim3(256), 0, st, a);
+}
+
+// One fragment with corrections, by the wave: the pairs of its insert once for mate 1's corrections, ascending in i, and once for
+// mate 2's, ascending in j.  A pass corrects what it lists; the pairs it touches are not the other pass's (a pair corrects one side).
+__device__ __forceinline__ void patch_one(const OverlapArgs &a, uint64_t f) {
+    const uint32_t rk = Wave::rank();
+    const uint64_t s1 = a.off[2u * f], s2 = a.off[2u * f + 1u];
+    const uint32_t L1 = (uint32_t)(s2 - s1), L2 = (uint32_t)(a.off[2u * f + 2u] - s2), I = a.insert[f];
+    const uint32_t lo = I > L2 ? I - L2 : 0u, hi = min(I, L1);
+    unsigned long long at = a.cor_at[f];
+    const unsigned long long end = a.cor_at[f + 1u];
+    for (uint32_t side = 2; side >= 1; --side) {  // (2: mate 1 is corrected, then 1: mate 2)
+        const uint32_t first = side == 2 ? lo : I - hi, last = side == 2 ? hi : I - lo;
+        for (uint32_t base = first; base < last; base += 64u) {  // (uniform in the wave)
+            const uint32_t z = base + rk, i = side == 2 ? z : I - 1u - z, j = I - 1u - i;
+            bool fix = false;
+            uint32_t ca = 0, cb = 0, qa = 0, qb = 0;
+            if (z < last) {
+                ca = a.cor_seq[s1 + i], cb = a.cor_seq[s2 + j];
+                const uint32_t ua = up(ca), ub = up(cb);
+                if (is_n(ua) || is_n(ub) || ua != comp_of(ub)) {
+                    qa = a.cor_qual[s1 + i], qb = a.cor_qual[s2 + j];
+                    fix = correct_pair(ca, cb, qa, qb, a.cor_high, a.cor_low) == side;
+                }
+            }
+            const uint64_t m = ballot64(fix);
+            if (fix) {
+                CorPatch pt;
+                pt.read = (uint32_t)(2u * f) + (side == 2 ? 0u : 1u);
+                pt.pos = z;
+                pt.base = (uint8_t)comp_of(up(side == 2 ? cb : ca));
+                pt.qual = (uint8_t)(side == 2 ? qb : qa);
+                pt.old_base = (uint8_t)(side == 2 ? ca : cb);
+                pt.old_qual = (uint8_t)(side == 2 ? qa : qb);
+                const unsigned long long slot = at + (uint32_t)__popcll(m & ((1ull << rk) - 1ull));
+                if (slot < end) a.patches[slot] = pt;  // (always: the overlap kernel counted these very pairs)
+                const uint64_t where = side == 2 ? s1 + i : s2 + j;
+                a.cor_seq[where] = pt.base;
+                a.cor_qual[where] = pt.qual;
+            }
+            at += (uint32_t)__popcll(m);
+        }
+        __threadfence_block();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_prep_patches(OverlapArgs a) {
+    const uint64_t n_frag = a.n_reads / 2u;
+    for (uint64_t base = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; base < n_frag; base += (uint64_t)gridDim.x * 256u) {  // (uniform in the wave)
+        const uint64_t f = base + Wave::rank();
+        uint64_t m = ballot64(f < n_frag && a.cor_count[f] != 0);
+        while (m) {
+            const uint32_t bit = (uint32_t)(__ffsll((unsigned long long)m) - 1);
+            m &= m - 1;
+            patch_one(a, base + bit);
+        }
+    }
+}
+
+void launch_prep_patches(const OverlapArgs &a, hipStream_t st) {
+    if (a.n_reads < 2) return;
+    // a block a CU: most waves only look through their 64 counts a trip and find nothing
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(PREP_GRID / 4u, (a.n_reads / 2u + 255u) / 256u));
+    hipLaunchKernelGGL(k_prep_patches, dim3(grid), dim3(256), 0, st, a);
 }
 
 }  // namespace pfq

@@ -480,6 +480,35 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_last_overlap(self._h, C.byref(ms)))
         return float(ms.value)
 
+    CORRECT_TOTALS = ("n_fragments_corrected", "n_bases", "n_unresolved", "n_no_quality")
+    PATCH_DTYPE = np.dtype([("read", np.uint32), ("pos", np.uint32), ("base", np.uint8), ("qual", np.uint8), ("old_base", np.uint8), ("old_qual", np.uint8)])
+
+    def set_mate_correct(self, high: int = _ffi.MATE_CORRECT_HIGH, low: int = _ffi.MATE_CORRECT_LOW) -> None:
+        """Every later prep_reads(paired=True) with the mate overlap set corrects, where the mates of a fragment disagree inside
+        their overlap, the base whose quality is at most `low` by the mate's if that one's is at least `high`, before trimming
+        and the gather (pfq_tree_set_mate_correct; the rule is pfq.h "mate correction").  `high` 0 drops it."""
+        _ffi.check(_ffi.lib().pfq_tree_set_mate_correct(self._h, high, low))
+
+    def last_corrections(self) -> dict:
+        """What the mate correction of the last prep_reads() did (pfq_prep_last_corrections): n_fragments_corrected, n_bases (a
+        list: first mates, second mates), n_unresolved, n_no_quality and, if that call had want_reads, patches: a structured
+        array PATCH_DTYPE (read, pos, base, qual, old_base, old_qual), ascending by (read, pos); else None."""
+        out = _ffi.PrepCorrections()
+        _ffi.check(_ffi.lib().pfq_prep_last_corrections(self._h, C.byref(out)))
+        n = int(out.n_patches)
+        patches = None
+        if out.patches:
+            patches = np.frombuffer(C.string_at(out.patches, n * self.PATCH_DTYPE.itemsize), dtype=self.PATCH_DTYPE).copy() if n else np.zeros(0, dtype=self.PATCH_DTYPE)
+        return {"n_fragments_corrected": int(out.n_fragments_corrected), "n_bases": [int(out.n_bases[0]), int(out.n_bases[1])],
+                "n_unresolved": int(out.n_unresolved), "n_no_quality": int(out.n_no_quality), "patches": patches}
+
+    def last_corrections_ms(self) -> float:
+        """Device milliseconds of the scan and the patch kernel of the last prep_reads(want_reads=True) with the mate correction
+        (pfq_debug_last_corrections); last_overlap_ms() has the overlap kernel, the correction or its counting included."""
+        ms = C.c_double()
+        _ffi.check(_ffi.lib().pfq_debug_last_corrections(self._h, C.byref(ms)))
+        return float(ms.value)
+
     DEPLETE_TOTALS = ("n_units", "units_removed", "reads_removed", "bases_removed", "n_kept", "bases_kept")
 
     def prep_deplete(self, screen: "BloomTree", threshold: float, paired: bool = False, pair_mode: str = "either") -> dict:
