@@ -6,6 +6,10 @@ whether each is still valid, the block parsed last and the block prepared last, 
 settings that live on the tree.  Every expectation comes from the oracle and the *_ref modules; the lifetime rules are those of
 include/pfq.h, applied literally.
 
+Since the depletion (pfq_prep_deplete) involves two trees, a Play runs two: the main tree and beside it, for the whole deck, the
+screen — a second TreeModel with its own k, hashes, size and seeds — which prepared blocks are depleted against and which is
+queried, parsed for and grown on its own.  A depletion that is not refused is a query call on the screen and on the screen alone.
+
 deck() is the schedule: per seed a shuffled deck that holds every operation at least twice, patched so that every pair of
 PAIRS occurs.  Play runs a deck: the model side always, the device side when it is given one, compared call by call.
 tests/test_mixed_model_cpu.py runs it without a device."""
@@ -16,7 +20,9 @@ import numpy as np
 import abund_ref
 import adapter_ref
 import cluster_ref
+import correct_ref
 import cover_ref
+import deplete_ref
 import format_cases as fc
 import format_ref
 import frames_ref
@@ -46,6 +52,12 @@ AD33 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 AD2 = b"CTGTCTCTTATACACATCT"
 ADAPTER_SETS = (((AD33,), (), 5, 10), ((AD33, AD2), (AD2,), 8, 20), None)
 OVERLAPS = ((30, 10), (12, 50), None)
+CORRECTS = ((30, 14), (35, 5), None)         # (high, low) of the mate correction
+Q_HIGH, Q_LOW = 40 + 33, 2 + 33              # planted qualities: at least every `high`, at most every `low` of CORRECTS
+# the screen of each deck: its own k (above the main tree's, so a read the trimmer keeps can still lie under it), hashes, size, seeds
+SCREEN_BALANCED = dict(k=25, nbits=100003, h=3, seeds=(0x1111222233334444, 0x9999AAAABBBBCCCC))
+SCREEN_GREEDY = dict(k=23, fpr=0.001, largest=5000, seeds=(11, 13))
+UNDER_K = 22                                 # K <= UNDER_K < both screens' k
 SWEEP_LISTS = ((0.3, 0.7, 1.0), (0.7, 0.9), None)
 PREP_PARAMS = ({}, dict(trim_quality=20, trim_window=4, poly_x=10, min_length=K),
                dict(trim_quality=20, trim_window=4, poly_x=10, min_length=K, max_n=3, min_complexity=30))
@@ -59,8 +71,10 @@ KNOBS = (("PFQ_TILE_LISTS", "0"), ("PFQ_ENTRY_PACK", "0"), ("PFQ_ENTRY_PACK", "2
 QUERY_OPS = ("host", "dev", "text", "prepq", "frames", "frames_dev")
 BLOCK_OPS = ("parse", "prep", "prep_paired")
 NOTHING_OPS = ("format", "readout", "similarity", "recluster", "option", "delta")
-STATE_OPS = ("reset_counts", "abundance_reset", "coverage_reset", "sweep_reset", "set_sweep", "set_taxonomy", "set_adapters", "set_mate_overlap")
-OPS = QUERY_OPS + BLOCK_OPS + NOTHING_OPS + STATE_OPS + ("refuse",)
+STATE_OPS = ("reset_counts", "abundance_reset", "coverage_reset", "sweep_reset", "set_sweep", "set_taxonomy", "set_adapters", "set_mate_overlap",
+             "set_mate_correct")
+SCREEN_OPS = ("deplete", "screen_query")     # the two calls that involve the second tree
+OPS = QUERY_OPS + BLOCK_OPS + NOTHING_OPS + STATE_OPS + SCREEN_OPS + ("refuse",)
 # adjacent operations every deck must hold; an entry is (operation, forced result mode or None)
 PAIRS = {
     "query -> format": [("text", "hits"), ("format", None)],
@@ -70,12 +84,33 @@ PAIRS = {
     "prep -> prep -> query": [("prep", None), ("prep", None), ("prepq", None)],
     "counts-only -> non-query -> counts-only": [("host", "counts"), ("parse", None), ("dev", "counts")],
     "host query -> text parse -> host query": [("host", None), ("parse", None), ("host", None)],
+    # the depletion (pfq_prep_deplete).  A deplete "again" repeats the call before it, which then removes nothing; "first", "either"
+    # and "both" draw a threshold above 0 (at 0 every unit goes), the latter two force the pair mode; prep_paired "quals": with qualities
+    "prep -> deplete -> prepq": [("prep", None), ("deplete", None), ("prepq", None)],
+    "prep_paired -> deplete -> prepq": [("prep_paired", None), ("deplete", "both"), ("prepq", None)],
+    "prep -> deplete -> deplete -> prepq": [("prep", None), ("deplete", "first"), ("deplete", "again"), ("prepq", None)],
+    # the depleted block's own classification is still queued (the wait for pp_free[slot])
+    "prep -> prepq(counts) -> deplete -> prepq(hits)": [("prep", None), ("prepq", "counts"), ("deplete", None), ("prepq", "hits")],
+    # the previous block's classification is queued on the other CSR set
+    "prep -> prepq(counts) -> prep -> deplete -> prepq(counts)": [("prep", None), ("prepq", "counts"), ("prep", None), ("deplete", None), ("prepq", "counts")],
+    "screen_query(hits) -> deplete": [("screen_query", "hits"), ("deplete", None)],
+    "text(hits) -> prep -> deplete -> format": [("text", "hits"), ("prep", None), ("deplete", None), ("format", None)],
+    "overlap, adapters, correction -> prep_paired -> deplete -> prepq": [("set_mate_overlap", "on"), ("set_adapters", "on"), ("set_mate_correct", "on"),
+                                                                         ("prep_paired", "quals"), ("deplete", "either"), ("prepq", None)],
+    # once per deck the screen's own parse_text / query_text / format_text, valid when the depletion comes
+    "screen text -> prep -> deplete": [("screen_query", "text"), ("prep", None), ("deplete", None)],
 }
+DEPLETE_RUNS = [name for name in PAIRS if "deplete" in name]
 
 
 # on the greedy tree: a block parsed and a block prepared before the topology changes, queried after it against the new leaves
 STALE_INSERT = [("parse", None), ("prep", None), ("insert", None), ("text", "hits"), ("prepq", "hits")]
 STALE_PRUNE = [("parse", None), ("prep", None), ("prune", None), ("text", "hits"), ("prepq", "hits")]
+# ... and a prepared block depleted when it is older than the main tree's leaves, or than the screen's
+DEPLETE_INSERT = [("prep", None), ("insert", None), ("deplete", None), ("prepq", "hits")]
+DEPLETE_PRUNE = [("prep", None), ("prune", None), ("deplete", None), ("prepq", "hits")]
+DEPLETE_SCREEN_INSERT = [("prep", None), ("screen_insert", None), ("deplete", None), ("prepq", "hits")]
+GREEDY_RUNS = (STALE_INSERT, STALE_PRUNE, DEPLETE_INSERT, DEPLETE_PRUNE, DEPLETE_SCREEN_INSERT)
 
 
 def has_run(deck, run):
@@ -87,8 +122,10 @@ def has_run(deck, run):
 
 def deck(seed, greedy=False, repeats=2):
     """The schedule of one seed: every operation `repeats` times (the queries of a parsed or prepared block come once more behind
-    their block and once more on their own, which repeats the query), shuffled, then every run of PAIRS that the shuffle did not
-    produce appended.  On the greedy tree two insertions lie in the middle and a prune near the end."""
+    their block and once more on their own, which repeats the query) and the depletion runs of PAIRS as units of their own,
+    shuffled, then every run of PAIRS that the shuffle did not produce appended.  On the greedy tree two insertions lie in the
+    middle and two prunes near the end, each followed once by queries of the older blocks and once by a depletion of the older
+    prepared block, and the screen takes its spare genome between a prep and its depletion."""
     rng = np.random.default_rng(seed)
     units = []
     for op in OPS:
@@ -98,10 +135,15 @@ def deck(seed, greedy=False, repeats=2):
     units += [[("host", "counts"), ("dev", "counts"), ("dev", "counts")], [("set_sweep", "on"), ("host", "scores")], [("set_taxonomy", None), ("dev", "hits")]]
     units += [[("set_mate_overlap", "on"), ("set_adapters", "on"), ("prep_paired", None), ("prepq", None)]]
     units += [[("parse", "even"), ("text", "paired"), ("format", None)]]      # (fragments: a successful query_text that leaves format_text invalid)
+    units += [list(PAIRS[name]) for name in DEPLETE_RUNS]
+    if greedy:                                      # the screen grows by a leaf between a prep and its depletion, once
+        units += [list(DEPLETE_SCREEN_INSERT)]
     units = [units[i] for i in rng.permutation(len(units))]
     if greedy:                                      # (whole units: no run that belongs together is split)
         mid = len(units) // 2
-        units = units[:mid] + [STALE_INSERT + [("readout", None)] + STALE_INSERT] + units[mid:-3] + [STALE_PRUNE + [("readout", None)]] + units[-3:]
+        after = [("readout", None), ("parse", None)]
+        units = (units[:mid] + [STALE_INSERT + after + DEPLETE_INSERT + [("text", "hits")]] + units[mid:-3] +
+                 [STALE_PRUNE + after + [("prep", None), ("prune", "deeper")] + DEPLETE_PRUNE[2:] + [("text", "hits"), ("readout", None)]] + units[-3:])
     out = [e for u in units for e in u]
     for run in PAIRS.values():
         if not has_run(out, run):
@@ -127,6 +169,7 @@ class TreeModel(Model):
         super().__init__(ot)
         self.adapters = None        # (set1, set2, O, E)
         self.overlap = None         # (O, E)
+        self.correct = None         # (high, low)
         self.sweep_list = None
         self.text = None            # the block parsed last: dict(recs, reads, fastq, scan)
         self.prep = None            # the block prepared last: dict(want, paired)
@@ -229,9 +272,17 @@ class TreeModel(Model):
         return self.text
 
     def prepare(self, reads, quals, paired, params):
-        ad, ov = self.adapters, self.overlap
+        ad, ov, co = self.adapters, self.overlap, self.correct
+        cor = None
+        if paired and ov and co:
+            want = correct_ref.prep_block(reads, quals, ov[0], ov[1], co[0], co[1], *(ad or ((), (), 5, 10)), **params)
+            ad_want, cor = want["adapters"], want["corrections"]
+            self.note("base corrected in mate 1", cor["n_bases"][0] > 0)
+            self.note("base corrected in mate 2", cor["n_bases"][1] > 0)
+            self.note("unresolved pair", cor["n_unresolved"] > 0)
+            self.note("fragment without qualities", cor["n_no_quality"] > 0)
         if paired and ov:
-            want = overlap_ref.prep_block(reads, quals, ov[0], ov[1], *(ad or ((), (), 5, 10)), **params)
+            want = want if co else overlap_ref.prep_block(reads, quals, ov[0], ov[1], *(ad or ((), (), 5, 10)), **params)
             ad_want = want["adapters"]
             self.note("insert found", want["n_overlapped"] > 0)
             self.note("fragment skipped above 512 bases", want["n_skipped"] > 0)
@@ -243,8 +294,35 @@ class TreeModel(Model):
         self.note("read trimmed", want["n_trimmed"] > 0)
         self.note("read dropped", want["n_kept"] < want["n_reads"])
         self.note("read kept whole", any(want["len"][i] == len(reads[i]) > 0 for i in want["kept"]))
-        self.prep = dict(stale=False, want=want, paired=paired, reads=want["kept_reads"], adapters=ad_want, overlap=want if paired and ov else None)
+        self.prep = dict(stale=False, want=want, paired=paired, reads=want["kept_reads"], adapters=ad_want, overlap=want if paired and ov else None,
+                         corrections=cor, kept=list(want["kept"]), reason=list(want["reason"]), last_deplete=None)
         return self.prep
+
+    def deplete(self, screen, thr, pair_mode):
+        """pfq_prep_deplete of the block prepared last against the TreeModel `screen` (pair_mode None, "either" or "both"): the
+        reference's result.  The block becomes the survivors; the screen's leaf totals grow and what its last query call left ends,
+        as after any query call on it; nothing else of this model changes.  A block without units is a no-op (pfq.h) on both."""
+        p = self.prep
+        ref = deplete_ref.deplete(p["reads"], screen.ot, thr, paired=pair_mode is not None, both=pair_mode == "both", kept=p["kept"], reason=p["reason"])
+        hits_main = oracle_sets(self.ot, ref["survivors"], 1.0) if ref["survivors"] else []
+        self.note("unit removed", ref["units_removed"] > 0)
+        self.note("survivor that hits the main tree", any(hits_main))
+        self.note("read under the screen's k removed", any(len(r) < screen.ot.kmer_size and ref["removed"][i // (2 if pair_mode else 1)]
+                                                          for i, r in enumerate(p["reads"])))
+        if pair_mode == "both":
+            either = deplete_ref.deplete(p["reads"], screen.ot, thr, paired=True, kept=p["kept"], reason=p["reason"])
+            self.note("fragment removed in mode both", ref["units_removed"] > 0)
+            self.note("fragment kept in both that either would remove", any(e and not b for e, b in zip(either["removed"], ref["removed"])))
+        self.note("corrected block depleted", p["corrections"] is not None and sum(p["corrections"]["n_bases"]) > 0 and ref["n_units"] > 0)
+        self.note("screen result invalidated by a depletion", ref["n_units"] > 0 and (screen.fmt_valid or any(v is not None for v in screen.last.values())))
+        self.note("depletion while format_text is valid", self.fmt_valid and ref["n_units"] > 0)
+        p.update(reads=ref["survivors"], kept=ref["kept"], reason=ref["reason"], last_deplete=(thr, pair_mode))
+        if ref["n_units"]:
+            names = screen.names()
+            for c, n in enumerate(ref["leaf_counts"]):
+                screen.total[names[c]] += n
+            screen.refused_query()
+        return ref
 
     # ---- query calls
     def refused_query(self):
@@ -344,14 +422,25 @@ class TreeModel(Model):
 class World:
     """The genomes of a tree and the reads drawn from them (tests/test_gpu_parity.RNG, as the workloads of the call sequences)."""
 
-    def __init__(self, genomes, fam, singles):
-        self.genomes, self.fam, self.singles = list(genomes), list(fam), list(singles)
+    def __init__(self, genomes, fam, singles, screen=()):
+        self.genomes, self.fam, self.singles, self.screen = list(genomes), list(fam), list(singles), list(screen)
 
-    def piece(self, L):
-        g = self.genomes[int(RNG.integers(0, len(self.genomes)))]
+    def piece(self, L, of=None):
+        of = self.genomes if of is None else of
+        g = of[int(RNG.integers(0, len(of)))]
         L = min(L, len(g))
         o = int(RNG.integers(0, len(g) - L + 1))
         return g[o:o + L]
+
+    def screen_piece(self, L):
+        """A piece of one of the screen's genomes (of the main tree's where the world has no screen)."""
+        return self.piece(L, self.screen or None)
+
+    def screen_reads(self, n):
+        """n reads for a query of the screen: of its genomes, of the main tree's, random ones, and the lengths round its k."""
+        out = [self.screen_piece(int(RNG.integers(0, 301))) if i % 3 == 0 else self.piece(int(RNG.integers(0, 301))) if i % 3 == 1 else
+               rand_dna(int(RNG.integers(0, 301))) for i in range(n)]
+        return out + [self.screen_piece(L) for L in (UNDER_K, UNDER_K + 1, UNDER_K + 3, 600)]
 
     def long_read(self, L):
         out = b""
@@ -372,26 +461,55 @@ class World:
         n = int(rng.choice([64, 150, 400, 1400]))
         return workload(kind, self.genomes, self.fam, self.singles, n * 3 // 4) + self.varied(n // 4)
 
-    def pairs(self, n):
-        """n fragments as mates 2i, 2i + 1: inserts of 25 .. 400 bases from the genomes read from both ends (read-through below
-        the mate length: the adapter follows), unrelated mates, and one fragment with a mate above 512 bases."""
-        out = []
+    def pairs(self, n, quals=False):
+        """n fragments as mates 2i, 2i + 1: inserts of 25 .. 400 bases from the genomes, every fourth from the screen's, read from
+        both ends (read-through below the mate length: the adapter follows), unrelated mates, one fragment with a mate above 512
+        bases, and the fragments whose fate differs between the pair modes of a depletion: a mate under the screen's k beside a
+        screen mate and beside a random one, a screen mate beside a main one.  With `quals` (reads, qualities): a low-quality eighth
+        at every 3' end, and in overlaps of 40 pairs or more two planted disagreements (the idea of test_gpu_correct.planted_q) —
+        by turns a wrong base of low quality in mate 2 against a high one, the same in mate 1, a wrong base with both qualities
+        high (unresolved), an N of low quality in mate 1; every twelfth fragment has a second mate without qualities."""
+        out, qs = [], []
+        tail = lambda L: bytearray(b"I" * (L - L // 8) + b"#" * (L // 8))
+        other = lambda c: b"ACGT"[(b"ACGT".find(bytes([c])) + 1 + int(RNG.integers(0, 3))) % 4]
         for i in range(n):
             L1, L2 = int(RNG.integers(60, 200)), int(RNG.integers(60, 200))
             if i % 4 == 3:
-                out += [self.piece(L1), rand_dna(L2)]
+                out += [self.screen_piece(L1) if i % 8 == 7 else self.piece(L1), rand_dna(L2)]
+                qs += [bytes(tail(len(out[-2]))), bytes(tail(L2))]
                 continue
-            ins = self.piece(int(RNG.integers(25, 400)))
-            out += [(ins + AD33 + rand_dna(L1))[:L1], (orc.revcomp(ins) + AD2 + rand_dna(L2))[:L2]]
-        return out + [self.long_read(600), self.piece(150), b"", self.piece(100)]
+            ins = self.screen_piece(int(RNG.integers(25, 400))) if i % 4 == 1 else self.piece(int(RNG.integers(25, 400)))
+            a, b = bytearray((ins + AD33 + rand_dna(L1))[:L1]), bytearray((orc.revcomp(ins) + AD2 + rand_dna(L2))[:L2])
+            q1, q2 = tail(L1), tail(L2)
+            I = len(ins)
+            lo, hi = max(0, I - L2), min(I, L1)
+            if hi - lo >= 40:                        # 2 of 40 or more: inside every tolerance of OVERLAPS
+                for t, at in enumerate((lo + (hi - lo) // 3, lo + 2 * (hi - lo) // 3)):
+                    j, kind = I - 1 - at, (i // 4 + t) % 4
+                    if kind == 0:
+                        b[j], q1[at], q2[j] = other(b[j]), Q_HIGH, Q_LOW
+                    elif kind == 1:
+                        a[at], q1[at], q2[j] = other(a[at]), Q_LOW, Q_HIGH
+                    elif kind == 2:
+                        a[at], q1[at], q2[j] = other(a[at]), Q_HIGH, Q_HIGH
+                    else:
+                        a[at], q1[at], q2[j] = ord("N"), Q_LOW, Q_HIGH
+            out += [bytes(a), bytes(b)]
+            qs += [bytes(q1), None if i % 12 == 5 else bytes(q2)]
+        more = [self.long_read(600), self.piece(150), b"", self.piece(100), self.piece(UNDER_K), self.screen_piece(100), self.piece(UNDER_K), rand_dna(100),
+                self.screen_piece(120), self.piece(120)]
+        out += more
+        qs += [bytes(tail(len(r))) if len(r) > 2 * UNDER_K else b"I" * len(r) for r in more]
+        return (out, qs) if quals else out
 
     def prep_reads(self, n, with_quals):
         """Reads for the trimmer: plain ones, low-quality and poly-G tails, adapter read-through, random, short, N-rich and
-        homopolymer reads, 0 .. 300 bases, and three long ones that carry an adapter."""
+        homopolymer reads, 0 .. 300 bases, every third from the screen's genomes, three long ones that carry an adapter, and two
+        of UNDER_K bases: min_length = K keeps them, and the screen, whose k is larger, finds no k-mer in them."""
         reads, quals = [], []
         for i in range(n):
             L = int(RNG.integers(0, 301))
-            s, q = bytearray(self.piece(L)), bytearray(b"I" * L)
+            s, q = bytearray(self.screen_piece(L) if i % 3 == 1 else self.piece(L)), bytearray(b"I" * L)     # (every kind from both trees' genomes)
             kind = i % 8
             if kind == 1 and L > 50:
                 t = int(RNG.integers(5, 40))
@@ -419,6 +537,9 @@ class World:
             p = L - int(RNG.integers(40, 200))
             reads.append((x[:p] + AD33 + rand_dna(L))[:L])
             quals.append(b"I" * (L - 20) + b"#" * 20)
+        for x in (self.piece(UNDER_K), self.screen_piece(UNDER_K)):     # kept by min_length = K, under the screen's k
+            reads.append(x)
+            quals.append(b"I" * len(x))
         return reads, (quals if with_quals else None)
 
     def sequences(self, F, S, negative):
@@ -438,7 +559,21 @@ def balanced_case():
     fam = close_families(3)
     singles = [rand_dna(3000) for _ in range(6)]
     ot, ids = oracle_tree(fam + singles, K, 131071, 7)
-    return fam + singles, ids, ot, World(fam + singles, fam, singles)
+    return fam + singles, ids, ot, World(fam + singles, fam, singles, screen=[rand_dna(3000) for _ in range(3)])
+
+
+def balanced_screen(world):
+    """The screen that lives beside the balanced tree, over world.screen: (ids, a new oracle tree)."""
+    s = SCREEN_BALANCED
+    ids = [f"S{i:02d}" for i in range(len(world.screen))]
+    return ids, orc.build_balanced_tree(world.screen, ids, s["k"], s["nbits"], s["h"], *s["seeds"])
+
+
+def greedy_screen(world, seed):
+    """The screen beside the greedy tree: (ids, a new greedy oracle tree, the one genome it still takes)."""
+    s = SCREEN_GREEDY
+    ids = [f"S{seed}_{i}" for i in range(len(world.screen))]
+    return ids, orc.build_greedy_tree(world.screen, ids, s["k"], s["fpr"], s["largest"], *s["seeds"]), [(world.screen_spare, f"S{seed}_x")]
 
 
 def greedy_case(seed):
@@ -450,14 +585,20 @@ def greedy_case(seed):
     ids = [f"M{seed}_{i}" for i in range(len(genomes))]
     ot = orc.build_greedy_tree(genomes, ids, K, 0.001, 5000, 5, 10)
     extra = [(mutate(base, 3), f"M{seed}_x0"), (rand_dna(3000), f"M{seed}_x1")]
-    return genomes, ids, ot, World(genomes, fam, singles), extra
+    world = World(genomes, fam, singles, screen=[rand_dna(3000) for _ in range(3)])
+    world.screen_spare = rand_dna(3000)
+    return genomes, ids, ot, world, extra
 
 
 BALANCED_SEED, GREEDY_SEED = 8100, 8300
 # what one sequence's expectations must hold, from the references alone (TreeModel.seen)
 NOT_VACUOUS = ("non-empty row", "empty row", "ambiguous abundance row", "read trimmed", "read dropped", "read kept whole", "adapter found", "insert found",
                "fragment skipped above 512 bases", "valid format with both streams", "HEAD or TAIL run", "whole block", "frames call with a segment",
-               "frames call without a segment", "sweep counts differ between thresholds", "best row shorter than its row", "paired text query with hits")
+               "frames call without a segment", "sweep counts differ between thresholds", "best row shorter than its row", "paired text query with hits",
+               # the depletion and the mate correction
+               "unit removed", "survivor that hits the main tree", "fragment removed in mode both", "fragment kept in both that either would remove",
+               "read under the screen's k removed", "second call removes nothing", "base corrected in mate 1", "base corrected in mate 2", "unresolved pair",
+               "fragment without qualities", "corrected block depleted", "screen result invalidated by a depletion", "depletion while format_text is valid")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -530,7 +671,8 @@ def check_last(gt, m, tag):
 
 
 def check_prep_reports(gt, m, tag):
-    """last_adapters / last_overlap of the block prepared last (PFQ_ERR_STATE when that prep did not run the step)."""
+    """last_adapters / last_overlap / last_corrections of the block prepared last (PFQ_ERR_STATE when that prep did not run the
+    step): the totals and, since every prep of a deck asks for the reads, the arrays and the patch list, exact and in order."""
     p = m.prep
     if p is None or p["adapters"] is None:
         raises(PFQ_ERR_STATE, gt.last_adapters)
@@ -546,6 +688,21 @@ def check_prep_reports(gt, m, tag):
         for k in overlap_ref.TOTALS:
             assert ov[k] == p["overlap"][k], (tag, k, ov[k], p["overlap"][k])
         assert ov["hist"].tolist() == p["overlap"]["hist"] and ov["insert"].tolist() == p["overlap"]["insert"], tag
+    if p is None or p["corrections"] is None:
+        raises(PFQ_ERR_STATE, gt.last_corrections)
+    else:
+        cor, want = gt.last_corrections(), p["corrections"]
+        for k in correct_ref.TOTALS:
+            assert cor[k] == want[k], (tag, k, cor[k], want[k])
+        got = list(zip(*(cor["patches"][k].tolist() for k in ("read", "pos", "base", "qual", "old_base", "old_qual"))))
+        assert got == want["patches"], (tag, "patches", got[:4], want["patches"][:4])     # (every prep of a deck asks for the reads)
+
+
+def check_prep_csr(gt, reads, tag):
+    """The prepared CSR on the device, byte for byte, against the reads the model holds."""
+    cseq, coff = gt.prep_csr()
+    assert coff.tolist() == np.concatenate([[0], np.cumsum([len(r) for r in reads], dtype=np.int64)]).tolist(), (tag, "csr offsets")
+    assert cseq.tobytes() == b"".join(reads), (tag, "csr bytes")
 
 
 def check_format(gt, m, first, block, tag):
@@ -571,29 +728,41 @@ def check_format(gt, m, first, block, tag):
 # ---------------------------------------------------------------------------------------------------------------
 # one deck on one tree
 # ---------------------------------------------------------------------------------------------------------------
+class Side:
+    """One of the two trees of a Play: its model and, on a device, the tree and its Runner."""
+
+    def __init__(self, m, gt=None, runner=None, extra=()):
+        self.m, self.gt, self.runner = m, gt, runner
+        self.extra = list(extra)        # genomes a greedy tree still takes: (genome, name)
+
+
 class Play:
     """Runs a deck on a TreeModel and, with `gt` and `runner` (the Runner of tests/test_gpu_call_sequences.py), on the tree itself,
-    every call checked as it returns.  Everything is drawn from `rng` on the model's side, so a deck runs the same way with and
-    without a device."""
+    every call checked as it returns; `screen` is the Side of the second tree, the one prepared blocks are depleted against, which
+    lives beside the first for the whole deck.  Everything is drawn from `rng` on the model's side, so a deck runs the same way
+    with and without a device."""
 
-    def __init__(self, model, world, seed, gt=None, runner=None, extra=()):
+    def __init__(self, model, world, seed, gt=None, runner=None, extra=(), screen=None):
         self.m, self.w, self.rng, self.gt, self.runner = model, world, np.random.default_rng(seed), gt, runner
-        self.extra = list(extra)        # genomes the greedy tree still takes: (genome, name)
+        self.main = Side(model, gt, runner, extra)
+        self.extra = self.main.extra
+        self.screen = screen
         self.n_frames = self.n_unsynced = self.most_unsynced = 0
         self.step = 0
         self.read_steps = set()         # the steps whose query call was followed by a read of its results or of the counters
 
     # ---- drawing
-    def threshold(self, sweep_wanted):
+    def threshold(self, sweep_wanted, m=None):
+        m = m or self.m
         thr = THRESHOLDS[int(self.rng.integers(0, 4))]
-        if sweep_wanted and self.m.sweep_list:
-            low = [t for t in THRESHOLDS if np.float32(t) <= np.float32(self.m.sweep_list[0])]
+        if sweep_wanted and m.sweep_list:
+            low = [t for t in THRESHOLDS if np.float32(t) <= np.float32(m.sweep_list[0])]
             thr = low[int(self.rng.integers(0, len(low)))]
         return thr
 
-    def flags(self, mode, n_units, thr, paired):
+    def flags(self, mode, n_units, thr, paired, m=None):
         """The flags of a query call: the result mode and independently any legal subset of the post-stages."""
-        rng, m = self.rng, self.m
+        rng, m = self.rng, m or self.m
         small, forced = n_units <= SMALL, mode
         if mode is None:
             mode = ("counts", "counts", "hits", "scores")[int(rng.integers(0, 4))]
@@ -613,8 +782,9 @@ class Play:
         return f
 
     # ---- the device side of a query call
-    def query(self, entry, reads, thr, f, paired):
-        gt, runner = self.gt, self.runner
+    def query(self, entry, reads, thr, f, paired, side=None):
+        side = side or self.main
+        gt, runner = side.gt, side.runner
         kw = dict(paired=paired is not None, pair_mode=paired or "either")
         post = {k: f[k] for k in ("lca", "abundance", "coverage", "taxa", "best", "sweep")}
         runner.last_stream = 0
@@ -636,21 +806,22 @@ class Play:
         gt.query_device(d_seq, d_off, len(reads), total, thr, stream=stream, lca=f["lca"], **kw)
         return None
 
-    def classify(self, entry, reads, mode, paired=None, thr=None):
+    def classify(self, entry, reads, mode, paired=None, thr=None, side=None):
         """One query call through `entry`: the model's expectation, the call, and the checks that belong to it."""
-        m, rng = self.m, self.rng
+        side = side or self.main
+        m, gt, rng = side.m, side.gt, self.rng
         n_units = len(reads) // 2 if paired else len(reads)
         if thr is None:
-            thr = self.threshold(sweep_wanted=not paired and n_units <= SMALL and mode in (None, "scores"))
-        f = self.flags(mode, n_units, thr, paired)
+            thr = self.threshold(not paired and n_units <= SMALL and mode in (None, "scores"), m)
+        f = self.flags(mode, n_units, thr, paired, m)
         exp = m.classify(reads, thr, paired=paired, **f)
-        tag = (self.step, entry, thr, paired, {k: v for k, v in f.items() if v})
+        tag = (self.step, entry, thr, paired, {k: v for k, v in f.items() if v}) + (("screen",) if side is self.screen else ())
         read_now = f["hits"] or (rng.random() < 0.25 and mode != "counts")     # (a forced counts-only call is never read: PAIRS)
         if read_now:
             self.read_steps.add(self.step)
-        if self.gt is not None:
-            self.gt.set_path(int(rng.choice([-1, 1])))
-            res = self.query(entry, reads, thr, f, paired)
+        if gt is not None:
+            gt.set_path(int(rng.choice([-1, 1])))
+            res = self.query(entry, reads, thr, f, paired, side)
             if f["hits"]:
                 assert np.array_equal(res[0], exp["offs"]) and np.array_equal(res[1], exp["leaves"]), tag
                 if f["scores"]:
@@ -658,8 +829,8 @@ class Play:
             else:
                 assert res is None, tag
             if read_now:
-                check_last(self.gt, m, tag)
-                check_counts(self.gt, m)
+                check_last(gt, m, tag)
+                check_counts(gt, m)
         else:
             rng.choice([-1, 1])
         if read_now:                                    # (most counts-only calls are followed by another call unsynchronised)
@@ -719,13 +890,13 @@ class Play:
         m.fmt_valid = f["hits"] and not paired          # pfq.h "text output": a successful pfq_text_query with PFQ_WANT_HITS, without PFQ_PAIRED
         m.fmt_rows = rows_of(exp["sets"])
 
-    def prepare(self, paired):
+    def prepare(self, paired, mode=None):
         rng, m = self.rng, self.m
         params = PREP_PARAMS[int(rng.integers(0, len(PREP_PARAMS)))]
-        with_quals = rng.random() < 0.7
+        with_quals = rng.random() < 0.7 or mode == "quals"
         if paired:
-            reads = self.w.pairs(int(rng.choice([20, 34])))
-            quals = [b"I" * (len(r) - len(r) // 8) + b"#" * (len(r) // 8) for r in reads] if with_quals else None
+            reads, quals = self.w.pairs(int(rng.choice([20, 34])), quals=True)
+            quals = quals if with_quals else None
         else:
             reads, quals = self.w.prep_reads(int(rng.choice([64, 200, 600])), with_quals)
         p = m.prepare(reads, quals, paired, params)
@@ -740,20 +911,92 @@ class Play:
                 assert got[k] == want[k], (self.step, k, got[k], want[k])
             for k in ("begin", "len", "reason", "kept"):
                 assert np.array_equal(got[k], np.array(want[k], dtype=np.uint32)), (self.step, k)
+            check_prep_csr(self.gt, p["reads"], (self.step, "prep"))
+            check_prep_reports(self.gt, m, (self.step, "prep"))
 
     def op_prep(self, mode):
         self.prepare(False)
 
     def op_prep_paired(self, mode):
-        self.prepare(True)
+        self.prepare(True, mode)
 
     def op_prepq(self, mode):
         m = self.m
         if m.prep is None:
             self.prepare(False)
-        paired = (("either", "both")[int(self.rng.integers(0, 2))]) if m.prep["paired"] else None
+        paired = (("either", "both")[int(self.rng.integers(0, 2))]) if self.whole_fragments() else None
         m.note("prepared block queried after the leaves changed", m.prep["stale"])
         self.classify("prepq", m.prep["reads"], mode, paired)
+
+    def whole_fragments(self):
+        """Whether the block prepared last still consists of fragments: prepared paired and never depleted read by read."""
+        return self.m.prep["paired"] and not self.m.prep.get("split")
+
+    # ---- the second tree
+    def op_deplete(self, mode):
+        """pfq_prep_deplete of the block prepared last against the screen ("again": the call before it repeated, which removes
+        nothing), and after it everything the call may and may not have touched, on both trees."""
+        m, rng, scr = self.m, self.rng, self.screen
+        if m.prep is None:
+            self.prepare(False)
+        p = m.prep
+        if mode == "again" and p["last_deplete"] is not None:
+            thr, pair_mode = p["last_deplete"]
+        else:
+            thr = THRESHOLDS[int(rng.integers(0, 4 if mode is None else 3))]
+            pair_mode = (None, "either", "both")[int(rng.integers(0, 3))] if self.whole_fragments() else None
+            if mode in ("either", "both") and self.whole_fragments():
+                pair_mode = mode
+        before = dict(m.last), m.fmt_valid, dict(m.total)
+        ref = m.deplete(scr.m, thr, pair_mode)
+        if mode == "again":
+            assert ref["units_removed"] == 0 and ref["n_units"] * (2 if pair_mode else 1) == ref["n_kept"], (self.step, ref["units_removed"])
+            m.note("second call removes nothing", ref["n_units"] > 0)
+        if p["paired"] and pair_mode is None and ref["units_removed"]:
+            p["split"] = True                        # (mates were judged one by one: the survivors are reads)
+        assert all(m.last[k] is before[0][k] for k in m.last) and m.fmt_valid == before[1] and m.total == before[2]
+        self.n_unsynced = 0
+        if self.gt is None:
+            return
+        tag = (self.step, "deplete", thr, pair_mode)
+        got = self.gt.prep_deplete(scr.gt, thr, paired=pair_mode is not None, pair_mode=pair_mode or "either")
+        for k in deplete_ref.TOTALS:
+            assert got[k] == ref[k], (tag, k, got[k], ref[k])
+        for k in ("kept", "reason"):
+            assert np.array_equal(got[k], np.array(ref[k], dtype=np.uint32)), (tag, k)
+        check_prep_csr(self.gt, ref["survivors"], tag)
+        check_prep_reports(self.gt, m, tag)
+        self.check_both(tag)
+
+    def op_screen_query(self, mode):
+        """A query of the screen, so that a depletion has something to invalidate: through the host or a device stream; "text": its
+        own parse_text, query_text with hits and format_text."""
+        scr, rng = self.screen, self.rng
+        reads = self.w.screen_reads(40)
+        if mode == "text":
+            data = fc.fastq(reads)
+            text = scr.m.parse(data, True, None)
+            if scr.gt is not None:
+                got = scr.gt.parse_text(data, "fastq")
+                assert (got["n_records"], got["consumed"], got["n_bases"]) == (len(text["recs"]), text["consumed"], text["n_bases"]), (self.step, got)
+            exp, f = self.classify("text", text["reads"], "hits", None, 0.7, side=scr)
+            scr.m.fmt_valid, scr.m.fmt_rows = True, rows_of(exp["sets"])
+            if scr.gt is not None:
+                assert check_format(scr.gt, scr.m, 0, 7, (self.step, "screen format")) is not None
+            return
+        paired = (None, None, "either", "both")[int(rng.integers(0, 4))]
+        reads = reads[:len(reads) - len(reads) % 2]
+        entry = ("host", "streams", "dev0")[int(rng.integers(0, 3))]
+        self.classify(entry, reads, mode, paired, side=scr)
+
+    def op_screen_insert(self, mode):
+        scr = self.screen
+        genome, name = scr.extra.pop(0)
+        if scr.gt is not None:
+            scr.runner.sync()
+            scr.gt.insert(genome, name)
+        scr.m.insert(genome, name)
+        self.w.screen.append(genome)
 
     def frames(self, device):
         m, rng = self.m, self.rng
@@ -799,15 +1042,18 @@ class Play:
         self.n_unsynced = 0
         if self.gt is None:
             return
-        gt, m, tag = self.gt, self.m, (self.step, "readout")
-        self.runner.sync()
-        check_accumulators(gt, m, tag)
-        check_last(gt, m, tag)
-        check_prep_reports(gt, m, tag)
-        info = gt.info()
-        assert (int(info.n_leaves), int(info.kmer_size)) == (m.n_leaves, K), tag
-        gt.last_stats()
-        assert gt.clades() == m.cm.table, tag
+        for side in (self.main, self.screen):
+            if side is None:
+                continue
+            gt, m, tag = side.gt, side.m, (self.step, "readout", "screen" if side is self.screen else "main")
+            side.runner.sync()
+            check_accumulators(gt, m, tag)
+            check_last(gt, m, tag)
+            check_prep_reports(gt, m, tag)
+            info = gt.info()
+            assert (int(info.n_leaves), int(info.kmer_size)) == (m.n_leaves, m.ot.kmer_size), tag
+            gt.last_stats()
+            assert gt.clades() == m.cm.table, tag
 
     def op_similarity(self, mode):
         if self.gt is not None:
@@ -897,6 +1143,13 @@ class Play:
             self.gt.set_mate_overlap(*(ov or (0, 10)))
         self.m.overlap = ov
 
+    def op_set_mate_correct(self, mode):
+        choice = [c for c in CORRECTS if c != self.m.correct and (c or mode != "on")]
+        co = choice[int(self.rng.integers(0, len(choice)))]
+        if self.gt is not None:
+            self.gt.set_mate_correct(*(co or (0, 0)))
+        self.m.correct = co
+
     def op_insert(self, mode):
         genome, name = self.extra.pop(0)
         if self.gt is not None:
@@ -906,10 +1159,11 @@ class Play:
         self.w.genomes.append(genome)
 
     def op_prune(self, mode):
+        depth = 2 if mode == "deeper" else 3
         if self.gt is not None:
             self.runner.sync()
-            self.gt.prune_tree(3)
-        self.m.prune(3)
+            self.gt.prune_tree(depth)
+        self.m.prune(depth)
 
     # ---- refused calls
     def refusals(self):
@@ -938,17 +1192,43 @@ class Play:
         out.append(("scores without hits", PFQ_ERR_ARG, scores_alone))
         return out
 
+    def deplete_refusals(self):
+        """[(name, documented code, the call on (tree, screen))] of the refused depletions that apply now.  They are a kind of their
+        own: a refused pfq_prep_deplete is no query call on either tree and changes nothing on either (pfq.h "depletion")."""
+        out = []
+        if self.m.prep is None:
+            out.append(("depletion before any prep", PFQ_ERR_STATE, lambda gt, sgt: gt.prep_deplete(sgt, 0.7)))
+        elif not self.m.prep["paired"]:
+            out.append(("paired depletion of an unpaired block", PFQ_ERR_ARG, lambda gt, sgt: gt.prep_deplete(sgt, 0.7, paired=True)))
+        out.append(("the screen is the tree itself", PFQ_ERR_ARG, lambda gt, sgt: gt.prep_deplete(gt, 0.7)))
+
+        def other_flag(gt, sgt):
+            res = _ffi.PrepDepleted()
+            _ffi.check(_ffi.lib().pfq_prep_deplete(gt._h, sgt._h, 0.7, _ffi.WANT_HITS, C.byref(res)))
+        out.append(("a depletion flag other than the three allowed", PFQ_ERR_ARG, other_flag))
+        return out
+
+    def check_both(self, tag):
+        """Every accumulator, what the last call left and format_text, on both trees against their models."""
+        for side in (self.main, self.screen):
+            side.runner.sync()
+            check_accumulators(side.gt, side.m, tag)
+            check_last(side.gt, side.m, tag)
+            check_format(side.gt, side.m, 0, 7, tag)
+
     def op_refuse(self, mode):
-        cases = self.refusals()
-        name, code, call = cases[int(self.rng.integers(0, len(cases)))]
-        self.m.refused_query()
+        cases = [("query",) + c for c in self.refusals()] + [("deplete",) + c for c in self.deplete_refusals()]
+        kind, name, code, call = cases[int(self.rng.integers(0, len(cases)))]
+        if kind == "query":
+            self.m.refused_query()
         if self.gt is not None:
             self.runner.last_stream = 0
-            raises(code, call, self.gt)
-            self.runner.sync()
-            check_accumulators(self.gt, self.m, (self.step, "refused", name))
-            check_last(self.gt, self.m, (self.step, "refused", name))
-            check_format(self.gt, self.m, 0, 7, (self.step, "refused", name))
+            if kind == "query":
+                raises(code, call, self.gt)
+            else:
+                raises(code, call, self.gt, self.screen.gt)
+                check_prep_reports(self.gt, self.m, (self.step, "refused", name))
+            self.check_both((self.step, "refused", name))
         self.n_unsynced = 0
 
     # ---- the deck

@@ -2,17 +2,22 @@
 classifier): every total, kept, reason and the prepared CSR after the call, the screen's leaf counters, the main tree's counters
 untouched; then the classification of the depleted block against query_packed of the survivors, blocks of more units than one
 scan block and one grid trip, pairs in both modes, screens in sequence with the previous block's classification still queued,
-the edges, the all-hit path and every refusal."""
+the edges, the all-hit path and every refusal; then the call behind the adapter, mate-overlap and mate-correction steps of the
+prep, whose results it must leave alone, and the overflow retry on a screen that has counters to lose and a call in flight."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import correct_ref
 import deplete_ref
+import overlap_ref
 import prep_ref
+from hipbuf import DeviceBuffer, stream_create, stream_destroy, stream_synchronize
 from oracle import pfq_oracle as orc
 from phagefilter_amd import BloomTree, PfqError, _ffi, pack_reads
 from test_gpu_build import SEEDS, _dna, _one_child_db
+from test_gpu_overlap import AD33, other_base
 from test_gpu_prep import (H, K, LONG_LENGTHS, NBITS, PFQ_ERR_ARG, PFQ_ERR_STATE, PFQ_ERR_UNSUPPORTED, SCAN_ITEMS, SHORT_LENGTHS, TRIP_READS,
                            counts_of, pack_quals)
 
@@ -366,3 +371,159 @@ def test_refusals(case, tmp_path):
     want = case.deplete(prep_ref.prep_block(case.reads[:60], case.quals[:60], **TRIM), case.a_o, THR)
     case.check(main.prep_deplete(a, THR), want, "after the refusals")
     fresh(main, a)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# behind the other prep steps
+# ---------------------------------------------------------------------------------------------------------------
+STEPS = dict(O=30, E=10, high=30, low=14, par=dict(trim_quality=20, trim_window=4, min_length=K))
+
+
+def worked_fragments(case):
+    """150 fragments of 60 .. 200 bases as tests/test_gpu_correct.py builds them for test_with_adapters_and_quality_trimming, but
+    with inserts of the screen's genomes and of the main tree's by turns: adapter read-through, a low-quality tail on some second
+    mates, and in three of four overlaps one wrong base per mate, of quality 2 against 40 — at threshold 1 either hides its mate
+    from the tree the insert comes from until it is corrected.  Returns reads, quals."""
+    rng = np.random.default_rng(4800)
+    background = np.frombuffer(b"5?IJ", dtype=np.uint8)
+    reads, quals = [], []
+    for n in range(150):
+        L1, L2 = (int(v) for v in rng.integers(60, 200, 2))
+        I = int(rng.integers(40, 230))
+        g = case.a_g[n % 4] if n % 2 else case.main_g[n % 16]
+        ins = piece(rng, g, I)
+        a = bytearray((ins + (AD33 if n % 3 == 0 else b"") + _dna(rng, L1))[:L1])
+        b = bytearray((orc.revcomp(ins) + _dna(rng, L2))[:L2])
+        q1, q2 = (bytearray(rng.choice(background, L).astype(np.uint8)) for L in (L1, L2))
+        lo, hi = max(0, I - L2), min(I, L1)
+        if n % 4 and hi - lo >= 30:
+            i1, i2 = sorted(rng.choice(hi - lo, 2, replace=False).tolist())
+            a[lo + i1], q1[lo + i1], q2[I - 1 - lo - i1] = other_base(rng, a[lo + i1]), 2 + 33, 40 + 33
+            b[I - 1 - lo - i2], q2[I - 1 - lo - i2], q1[lo + i2] = other_base(rng, b[I - 1 - lo - i2]), 2 + 33, 40 + 33
+        if n % 7 == 2 and I > 14:
+            q2[I - 6:] = b"#" * len(q2[I - 6:])
+        reads += [bytes(a), bytes(b)]
+        quals += [None if n % 13 == 12 else bytes(q1), bytes(q2)]
+    return reads, quals
+
+
+@pytest.fixture(scope="module")
+def worked(case):
+    """The fragments and, from the references alone, the prepared block with and without the correction."""
+    reads, quals = worked_fragments(case)
+    s = STEPS
+    with_c = correct_ref.prep_block(reads, quals, s["O"], s["E"], s["high"], s["low"], [AD33], **s["par"])
+    without = overlap_ref.prep_block(reads, quals, s["O"], s["E"], [AD33], **s["par"])
+    cor = with_c["corrections"]
+    assert min(cor["n_bases"]) > 40 and with_c["adapters"]["n_found"] >= 15 and with_c["n_overlapped"] > 100 and with_c["n_trimmed"] > 100
+    return reads, quals, with_c, without
+
+
+def same_report(got, want, tag):
+    """Two read-outs of pfq_prep_last_adapters / _overlap / _corrections, field by field."""
+    assert got.keys() == want.keys(), tag
+    for k, v in want.items():
+        if isinstance(v, np.ndarray):
+            assert got[k].dtype == v.dtype and np.array_equal(got[k], v), (tag, k)
+        else:
+            assert got[k] == v, (tag, k, got[k], v)
+
+
+@pytest.mark.parametrize("mode", [None, "either", "both"], ids=["unpaired", "either", "both"])
+@pytest.mark.parametrize("want_reads", [False, True], ids=["corrected in the overlap kernel", "corrected by the patch kernel"])
+def test_behind_adapters_overlap_and_correction(case, worked, want_reads, mode):
+    """The depletion re-gathers from the raw block the correction changed in place (in the overlap kernel, or with want_reads in
+    the patch kernel), by begin / len that hold min(adapter cut, overlap cut): expected is deplete_ref on correct_ref's kept
+    reads.  What the three steps reported and the arrays the prep handed out are after the call what they were before it."""
+    main, a, L = case.main, case.a, _ffi.lib()
+    reads, quals, with_c, without = worked
+    kw = dict(paired=mode is not None, both=mode == "both")
+    want = case.deplete(with_c, case.a_o, 1.0, **kw)
+    plain = case.deplete(without, case.a_o, 1.0, **kw)
+    gone = lambda prep, ref: {prep["kept"][i] // 2 for i in range(len(prep["kept"])) if ref["removed"][i // (2 if mode else 1)]}
+    by_correction = gone(with_c, want) - gone(without, plain)
+    assert len(by_correction) >= 10, len(by_correction)              # removed only because a correction restored a k-mer of the screen
+    main_hits = lambda ref: sum(map(bool, deplete_ref.leaf_sets(case.main_o, ref["survivors"], 1.0)))
+    assert main_hits(want) >= main_hits(plain) + 10                   # ... and survivors the main tree sees only corrected
+    assert 0 < want["units_removed"] < want["n_units"]
+    fresh(main, a)
+    seq, off, qual, hq = pack_quals(reads, quals)
+    s = STEPS
+    par = _ffi.PrepParams(s["par"]["trim_quality"], s["par"]["trim_window"], 0, s["par"]["min_length"], _ffi.PREP_MAX_N_OFF, 0,
+                          _ffi.PREP_PAIRED | (_ffi.PREP_WANT_READS if want_reads else 0))
+    out = _ffi.Prep()
+    n = len(reads)
+    try:
+        main.set_adapters([AD33])
+        main.set_mate_overlap(s["O"], s["E"])
+        main.set_mate_correct(s["high"], s["low"])
+        # (the C call, so that the library-owned arrays it hands out can be read again after the depletion)
+        _ffi.check(L.pfq_prep_reads(main._h, seq.ctypes.data, qual.ctypes.data, off.ctypes.data, hq.ctypes.data, n, C.byref(par), C.byref(out)))
+        main._prep_shape, main._prep_reads = (int(out.n_kept), int(out.bases_kept)), n
+        assert int(out.n_kept) == with_c["n_kept"]
+        handed = lambda: {k: np.ctypeslib.as_array(getattr(out, k), shape=(m,)).copy() for k, m in
+                          (("begin", n), ("len", n), ("reason", n), ("kept", with_c["n_kept"]))} if want_reads else {}
+        for k, v in handed().items():
+            assert v.tolist() == with_c[k], k
+        reports = (main.last_adapters, main.last_overlap, main.last_corrections)
+        before = [call() for call in reports]
+        assert before[2]["n_bases"] == with_c["corrections"]["n_bases"] and (before[2]["patches"] is not None) == want_reads
+        got = main.prep_deplete(a, 1.0, paired=mode is not None, pair_mode=mode or "either")
+        case.check(got, want, (want_reads, mode), arrays=want_reads)
+        assert counts_of(a).tolist() == want["leaf_counts"] and counts_of(main).sum() == 0
+        for call, was in zip(reports, before):
+            same_report(call(), was, call.__name__)
+        for k, v in handed().items():
+            assert v.tolist() == with_c[k], (k, "changed by the depletion")
+        qkw = dict(want_hits=True, paired=mode is not None, pair_mode=mode or "either")
+        want_off, want_leaves = main.query_packed(*pack_reads(want["survivors"]), 1.0, **qkw)
+        want_counts = counts_of(main)
+        assert want_counts.sum() > 0
+        fresh(main)
+        off_, leaves = main.query_prep(1.0, **qkw)
+        assert off_.tolist() == want_off.tolist() and leaves.tolist() == want_leaves.tolist()
+        assert counts_of(main).tolist() == want_counts.tolist()
+    finally:
+        main.set_adapters([])
+        main.set_mate_correct(0)
+        main.set_mate_overlap(0)
+        fresh(main, a)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the retry with something to lose
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("paired", [False, True])
+def test_the_retry_restores_counters_that_are_not_zero(case, paired):
+    """As test_a_full_hit_buffer_is_retried, but the screen's counters hold an earlier, synchronised query and a counts-only
+    query_device of the screen was issued on a user stream and not waited for: afterwards they are the earlier call's plus the
+    one in flight plus the depletion's, counted exactly once."""
+    main, a = case.main, case.a
+    reads = fragments(case) if paired else case.prep["kept_reads"]
+    prep = prep_ref.prep_block(reads, None, paired=paired, min_length=5)
+    want = case.deplete(prep, case.a_o, THR, paired=paired)
+    assert want["units_removed"] > 0
+    earlier, flying = case.reads[:60], case.reads[60:] * 4
+    c_earlier, c_flying = oracle_counts(case.a_o, earlier, THR), oracle_counts(case.a_o, flying, THR)
+    assert sum(c_earlier) > 0 and sum(c_flying) > 0
+    fresh(a)
+    a.query_packed(*pack_reads(earlier), THR)
+    assert counts_of(a).tolist() == c_earlier
+    seq, off = pack_reads(flying)
+    d_seq, d_off, stream = DeviceBuffer.from_numpy(seq), DeviceBuffer.from_numpy(off), stream_create()
+    try:
+        case.prepare(reads, None, paired=paired, min_length=5)
+        a.query_device(d_seq.ptr, d_off.ptr, len(flying), int(off[-1]), THR, stream=stream)       # not waited for
+        a.set_option("PFQ_HIT_SLOTS", "0")
+        try:
+            case.check(main.prep_deplete(a, THR, paired=paired), want, ("retry with counters", paired))
+            c = a.last_capacity()
+            assert c["attempts"] == 2 and c["hit_cap"] == 0 < c["hit_cursor"], c
+        finally:
+            a.set_option("PFQ_HIT_SLOTS", None)
+        stream_synchronize(stream)
+        assert counts_of(a).tolist() == (np.array(c_earlier) + np.array(c_flying) + np.array(want["leaf_counts"])).tolist()
+    finally:
+        stream_synchronize(stream)
+        stream_destroy(stream)
+        fresh(a)
