@@ -1000,6 +1000,15 @@ int pfq_debug_last_capacity(pfq_tree *tree, uint64_t *out, uint64_t n);
  * PFQ_TILE_LISTS=0: none.  out[0] columns with slots, [1] bytes the slots hold, [2] tiles the last query call built from
  * slots, [3] tiles it loaded dense (both 0 unless its certificates ran as k_tile_test<0>; waits for that call). */
 int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]);
+/* The dense screen of k_classify at theta = 1: 4 k-mers of 16 reads a pass, or — the lean build — 2 k-mers of 32
+ * reads where four rows a read keep false candidates rare: E = sum over the leaves of (set bits / nbits)^4 <= 2^-10, rows of
+ * at most 32 words, one leaf group, not block mode (option PFQ_SCREEN_KMERS: 0 / unset this rule, 2 wherever the rows allow,
+ * 4 never).  Results do not depend on the build; n_candidates may.  out[0] k-mers a read the screen of the last query call
+ * took (2: the lean build ran, 4, 0: the call had no such screen — direct path, thresholds below 1), [1] E of the tree as it
+ * is (builds the device layout and counts the leaves' bits if need be, once per topology), [2] words of a row, [3] column
+ * groups.  (A call of its own and not a bit of pfq_stats.pair_stage: callers compare the bits of pair_stage above 3 with the
+ * tail shapes.) */
+int pfq_screen_info(pfq_tree *tree, double out[4]);
 /* Copy min(n, 8192) entries of the slot of (column, tile) to the host: positions < 2^20 in any order, unused entries
  * 0xffffffff.  A column without slots: PFQ_ERR_STATE. */
 int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n);

@@ -193,13 +193,20 @@ __device__ __forceinline__ void kmer_hashes(const BlockLds &lds, uint32_t wave, 
 // ---- dense pre-screen staging: the first DENSE_KMERS k-mers of DENSE_READS reads per wave ------------------------------
 constexpr uint32_t DENSE_READS = 16, DENSE_KMERS = 4;               // 16 x 4 = 64 lanes
 constexpr uint32_t MINI_BYTES = 84;                                  // >= WIN_PAD + (KMAX + DENSE_KMERS - 1) + WIN_PAD, dword multiple
-template <bool ENABLED>
+// The lean screen (theta = 1 on sparse trees, pfq_host.cpp plan()): the first LEAN_KMERS k-mers of LEAN_READS reads per wave.
+// A read's window is its k + 1 bytes and nothing else: the windows lie back to back (the dword over-reads of a k-mer's ends
+// fall into the neighbours, whose bytes are shifted out again) and only the buffer has a pad at either end, so 32 reads take
+// 2192 bytes where 32 windows of MINI_BYTES would take 2688.
+constexpr uint32_t LEAN_READS = 32, LEAN_KMERS = 2;                  // 32 x 2 = 64 lanes
+constexpr uint32_t LEAN_MINI_BYTES = 68;                             // >= KMAX + LEAN_KMERS - 1, dword multiple
+constexpr uint32_t LEAN_BUF_BYTES = LEAN_READS * LEAN_MINI_BYTES + 2u * WIN_PAD;
+template <bool ENABLED, bool LEAN = false>
 struct alignas(16) DenseLds {
-    uint32_t mini[WAVES_PER_BLOCK][2][DENSE_READS * MINI_BYTES / 4];
-    uint32_t live[WAVES_PER_BLOCK][DENSE_READS * 64];  // frontier words of the reads of a group, [read][row word]
+    uint32_t mini[WAVES_PER_BLOCK][2][(LEAN ? LEAN_BUF_BYTES : DENSE_READS * MINI_BYTES) / 4];
+    uint32_t live[WAVES_PER_BLOCK][DENSE_READS * 64];  // frontier words of the reads of a group, [read][row word] (lean: 32 reads of rw <= 32 words)
 };
-template <>
-struct DenseLds<false> {
+template <bool LEAN>
+struct DenseLds<false, LEAN> {
     uint32_t mini[1][2][1];
     uint32_t live[1][1];
 };

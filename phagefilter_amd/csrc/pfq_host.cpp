@@ -113,6 +113,7 @@ struct Knobs {
     long long sweep_lds = -1;                   // PFQ_WANT_SWEEP: 0: count `pass` with global atomics although its bins fit the block's LDS
     long long tile_lists = -1;                  // 0: no position slots, k_tile_test loads every tile dense (unset: slots for every sparse column)
     long long tile_stream = -1;                 // 0: the generic k_tile_test<0> even where every column has slots (unset: the slots-only build there)
+    long long screen_kmers = -1;                // k-mers a read of the dense screen at threshold 1: 0 / unset chosen per tree from its leaves' fill, 2 wherever rows have <= 32 words, 4 always
     long long entry_pack = -1;                  // packed tile entries at threshold 1: 0 never, 1 / unset chosen per call from its read lengths, 2 always
     long long fmt_grid = -1, fmt_hash_bits = -1, fmt_time = -1;  // pfq_text_format: a cap on every grid; bits of the id hash that are kept (1 .. 64); 1: time the stages with HIP events
 };
@@ -148,7 +149,7 @@ const KnobName KNOBS[] = {
     {"PFQ_SIM_TIME", &Knobs::sim_time},         {"PFQ_CLUSTER_TIME", &Knobs::cluster_time},
     {"PFQ_TEXT_TILE", &Knobs::text_tile},       {"PFQ_SWEEP_LDS", &Knobs::sweep_lds},
     {"PFQ_TILE_LISTS", &Knobs::tile_lists},     {"PFQ_TILE_STREAM", &Knobs::tile_stream},
-    {"PFQ_ENTRY_PACK", &Knobs::entry_pack},
+    {"PFQ_ENTRY_PACK", &Knobs::entry_pack},     {"PFQ_SCREEN_KMERS", &Knobs::screen_kmers},
     {"PFQ_FMT_GRID", &Knobs::fmt_grid},         {"PFQ_FMT_HASH_BITS", &Knobs::fmt_hash_bits},
     {"PFQ_FMT_TIME", &Knobs::fmt_time},
 };
@@ -401,6 +402,10 @@ struct pfq_tree {
     uint64_t cov_units = 0;
     bool cov_bits_valid = false;
     std::vector<uint64_t> cov_bits, out_cov_units, out_cov_matched;
+    // The lean dense screen (QueryRun::plan): screen_E = sum over the leaves of (popcount / nbits)^4, made with cov_bits;
+    // last_screen_kmers: k-mers a read the dense screen of the last call's deferring launch took (2: the lean build, 4, 0: none ran).
+    double screen_E = 0.0;
+    uint32_t last_screen_kmers = 0;
     std::vector<uint8_t> out_cov_regs;
     std::vector<double> out_cov_distinct, out_cov_genome;
     // pfq_query_frames: the frame table of the call (per sequence its first frame and the scan of the lone frames' deficits; per
@@ -1377,6 +1382,11 @@ int cover_filter_bits(pfq_tree &t) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(t.cov_bits.data(), d_pop.p, nl * 8, hipMemcpyDeviceToHost));
     }
+    t.screen_E = 0.0;
+    for (size_t l = 0; l < nl; ++l) {
+        const double f = (double)t.cov_bits[l] / (double)t.nbits;
+        t.screen_E += f * f * f * f;
+    }
     t.cov_bits_valid = true;
     return PFQ_OK;
 }
@@ -1476,7 +1486,7 @@ struct QueryRun {
     bool want_hits = false, want_scores = false, paired = false, pair_both = false, user_hits = false, want_lca = false, lca_best = false, want_abund = false, want_cover = false, want_taxa = false, rows_best = false, want_sweep = false, results_stand = false, with_guards = false, thr_one = false, thr_frac = false, counts_mode = false;
     bool pair_miss = false;    // counts_mode outside block mode: every deferred pair owns words of k-mer miss bits
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
-    bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false;
+    bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false, lean_screen = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
     uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
     int blocks = 0, blocks_group = 0;
@@ -1606,6 +1616,25 @@ struct QueryRun {
             }
         }
         if (bucketed && kn.miss_words >= 0) miss_cap = std::min<uint64_t>(miss_cap, (uint64_t)kn.miss_words);
+        // The lean dense screen: 2 k-mers of 32 reads a pass instead of 4 of 16 — half the row gathers, the passes and the
+        // hashing of k_classify.  The screen is a necessary condition only (every pair it lets through is certified probe by
+        // probe), so fewer rows change no result; they let more foreign reads through.  A random read keeps a leaf whose filter
+        // has the fraction f of its bits set with probability f^4 after four rows, so E = sum over the leaves of
+        // (popcount / nbits)^4 is the expected number of false pairs a read.  A false pair costs what a true one costs behind
+        // the screen, about 3 ns of bin + test + records (13.4 ms for 4.2 M pairs); the lean screen saves about
+        // 0.1 ns a read: break-even at E = 0.03.  The rule asks for E <= 2^-10, a factor of thirty below.  The popcounts are
+        // the coverage report's (cover_filter_bits: once per topology).  Only the pair pipeline at threshold 1 on all reads
+        // has the build: not block mode, not the leaf groups of a two-level frontier, and rows of at most 32 words (the
+        // frontier words of 32 reads fill the wave's 1024 words of LDS).  PFQ_SCREEN_KMERS=2 / 4 forces / forbids it.
+        lean_screen = false;
+        if (bucketed && thr_one && !block_mode && leaf_groups == 1 && t.rw <= 32 && kn.screen_kmers != 4) {
+            if (kn.screen_kmers == 2) lean_screen = true;
+            else {
+                PFQ_TRY(cover_filter_bits(t));
+                lean_screen = t.screen_E <= 1.0 / 1024.0;
+            }
+        }
+        t.last_screen_kmers = 0;
         t.last_path = bucketed ? 1 : 0;
         t.last_sort = 0;
         if (!bucketed) t.last_tile_mode = t.last_tile_bin = 0;  // (the direct path runs no tile pass)
@@ -1866,6 +1895,8 @@ struct QueryRun {
         a.split_recs = (recs && !counts_mode && kn.split_records != 0) ? 1u : 0u;
         a.block_pairs = block_mode ? 1u : 0u;
         a.batch_emit = kn.batch_emit != 0 ? 1u : 0u;  // (PFQ_BATCH_EMIT=0: the per-read loop for every survivor)
+        a.lean_screen = lean_screen ? 1u : 0u;
+        t.last_screen_kmers = counts_mode ? 0u : (lean_screen ? 2u : 4u);  // (thresholds < 1 have the counting screen)
         a.screen_recs = kn.screen_recs >= 0 ? (uint32_t)(kn.screen_recs != 0) : 1u;
         if (block_mode) {
             if (!t.tables_valid) {  // (the leaf set changed, or first use)
@@ -5933,6 +5964,18 @@ int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]) {
         out[2] = c[0];
         out[3] = c[1];
     }
+    return PFQ_OK;
+}
+int pfq_screen_info(pfq_tree *tree, double out[4]) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    PFQ_TRY(build_layout(t));
+    PFQ_TRY(cover_filter_bits(t));
+    out[0] = t.last_path ? (double)t.last_screen_kmers : 0.0;
+    out[1] = t.screen_E;
+    out[2] = (double)t.rw;
+    out[3] = (double)t.n_groups;
     return PFQ_OK;
 }
 int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n) {

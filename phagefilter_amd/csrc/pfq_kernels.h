@@ -78,6 +78,7 @@ struct QueryArgs {
     uint32_t batch_emit;         // 1 (DEFER, theta == 1, leaf pairs): the survivors of a pass of the dense screen are emitted together (PFQ_BATCH_EMIT)
     uint32_t screen_recs;        // thresholds < 1: the dense counting screen writes the probe records of the k-mers it hashes
     uint32_t screen_only;        // (launches without deferral) count the frontier's candidate leaves, certify nothing, count no read
+    uint32_t lean_screen;        // 1 (DEFER, theta == 1, leaf pairs, all reads, rw <= 32): the build whose dense screen takes 2 k-mers of 32 reads a pass (PFQ_SCREEN_KMERS)
     // thresholds < 1: every deferred pair owns ceil(n/64) u64 words of k-mer miss bits.  k_classify only accounts for
     // them (per bucket, and against the buffer's capacity through per-wave reservations); k_bucket_scatter places them.
     uint32_t *bucket_words;            // [n_leaves << sub_log2] miss words per bucket, or nullptr (threshold 1)

@@ -214,12 +214,18 @@ constexpr uint64_t SHORT_KMERS = 256;
 // The group is reads r0 .. r0 + n_in_group - 1, or list[r0 ..] when a list is given (entries 0xffffffff are no reads);
 // `rid` returns the lane's read.  MULTI (the coarse level of a two-level frontier, whose filters are fuller): n_probes
 // probes per k-mer (2 .. COARSE_MAX_PROBES) instead of two.
-template <bool MULTI>
+// KMERS = LEAN_KMERS (the lean screen of k_classify<..., LEAN>, chosen by the host where the leaves' fill lets four rows empty
+// the frontier of a foreign read): lane = (read lane >> 1, k-mer lane & 1), 32 reads per pass, k + 1 bytes staged and four
+// rows ANDed per read; `survive` and `irregular` hold 32 reads, live_out 32 x rw words (rw <= 32).  The screen is a
+// necessary condition only — every pair is certified probe by probe afterwards — so fewer rows change no result.
+template <bool MULTI, uint32_t KMERS = DENSE_KMERS>
 __device__ __forceinline__ uint32_t dense_screen(uint32_t *fw, uint32_t *rw_, const uint8_t *comp, uint32_t *live_out,
                                                  const QueryArgs &a, const uint32_t *list, uint64_t r0, uint32_t n_in_group,
                                                  uint32_t colmask, uint32_t n_probes, uint32_t &irregular, uint64_t &lane_len,
                                                  uint32_t &rid) {
-    const uint32_t lane = lane_id(), j = lane >> 2, t = lane & 3u, k = a.hp.k;
+    static_assert(KMERS == DENSE_KMERS || (KMERS == LEAN_KMERS && !MULTI), "16 reads x 4 k-mers, or the lean screen: 32 x 2");
+    constexpr uint32_t READS = 64u / KMERS, MINI = KMERS == DENSE_KMERS ? MINI_BYTES : LEAN_MINI_BYTES;  // reads per pass; bytes between two reads' windows
+    const uint32_t lane = lane_id(), j = lane / KMERS, t = lane & (KMERS - 1u), k = a.hp.k;
     const uint32_t rw = a.rw;
     uint64_t o0 = 0, L = 0;
     rid = (uint32_t)(r0 + j);
@@ -235,21 +241,22 @@ __device__ __forceinline__ uint32_t dense_screen(uint32_t *fw, uint32_t *rw_, co
     lane_len = (t == 0) ? L : 0;  // read length, on the first lane of each read
     const uint64_t n = (L >= k) ? (L - k + 1) : 0;
     const bool regular = present && n >= 1 && need_kmers(a.threshold, n) == n;
-    const uint32_t nk = regular ? (uint32_t)(n < DENSE_KMERS ? n : DENSE_KMERS) : 0u;
+    const uint32_t nk = regular ? (uint32_t)(n < KMERS ? n : KMERS) : 0u;
     const uint32_t W = nk ? nk + k - 1 : 0u;  // bytes of this read that are staged
     uint8_t *fwd = reinterpret_cast<uint8_t *>(fw), *rcb = reinterpret_cast<uint8_t *>(rw_);
-    const uint32_t mb = j * MINI_BYTES + WIN_PAD;
+    const uint32_t mb = j * MINI + WIN_PAD;
     __builtin_amdgcn_wave_barrier();
-    for (uint32_t i0 = 0; i0 < k + DENSE_KMERS - 1; i0 += 24) {  // six bytes per lane and batch, loads before uses
-        uint8_t b[6];
+    constexpr uint32_t NB = 24u / KMERS;  // bytes per lane and batch
+    for (uint32_t i0 = 0; i0 < k + KMERS - 1; i0 += 24) {  // six bytes per lane and batch (lean: twelve), loads before uses
+        uint8_t b[NB];
 #pragma unroll
-        for (uint32_t u = 0; u < 6; ++u) {
-            const uint32_t idx = i0 + 4u * u + t;
+        for (uint32_t u = 0; u < NB; ++u) {
+            const uint32_t idx = i0 + KMERS * u + t;
             b[u] = idx < W ? a.seq[o0 + idx] : (uint8_t)0;
         }
 #pragma unroll
-        for (uint32_t u = 0; u < 6; ++u) {
-            const uint32_t idx = i0 + 4u * u + t;
+        for (uint32_t u = 0; u < NB; ++u) {
+            const uint32_t idx = i0 + KMERS * u + t;
             if (idx < W) {
                 fwd[mb + idx] = b[u];
                 rcb[mb + (W - 1 - idx)] = comp[b[u]];
@@ -281,7 +288,7 @@ __device__ __forceinline__ uint32_t dense_screen(uint32_t *fw, uint32_t *rw_, co
     uint32_t survive = 0;
     irregular = 0;
 #ifdef PFQ_DENSE_V1
-    if constexpr (MULTI) {
+    if constexpr (MULTI || KMERS != DENSE_KMERS) {
 #else
     {
 #endif
@@ -290,7 +297,7 @@ __device__ __forceinline__ uint32_t dense_screen(uint32_t *fw, uint32_t *rw_, co
         // row of their read, 64 / (rw / 4) reads per sub-pass, eight 16-byte gathers in flight per lane.  (Lanes as (row, part)
         // with the indices picked by ds_bpermute and the AND finished by shuffles cost ~490 LDS-pipe instructions per pass of
         // 16 reads against ~20 here: k_coarse at theta = 1 was bound by them.)
-        const uint32_t lpr_log2 = a.rw_log2 - 2u, lpr = 1u << lpr_log2, part = lane & (lpr - 1u), rows = DENSE_KMERS * ppk;
+        const uint32_t lpr_log2 = a.rw_log2 - 2u, lpr = 1u << lpr_log2, part = lane & (lpr - 1u), rows = KMERS * ppk;
         uint32_t cm[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -310,6 +317,59 @@ __device__ __forceinline__ uint32_t dense_screen(uint32_t *fw, uint32_t *rw_, co
         __builtin_amdgcn_wave_barrier();
         const uint64_t irr_b = ballot64(present && t == 0 && nk == 0);  // (no screening possible: the per-read path)
         const uint32_t rps = 64u >> lpr_log2;  // reads per sub-pass
+        if constexpr (KMERS == LEAN_KMERS) {
+            // Four rows a read (2 k-mers x 2 probes): one 16-byte LDS load holds a read's indices, and the gathers of two
+            // sub-passes are issued together, so that a lane still has eight 16-byte gathers in flight before the first AND.
+            const uint32_t sub = lane >> lpr_log2;
+            const uint64_t lmask = lpr >= 64u ? ~0ull : ((1ull << lpr) - 1ull);
+            auto screened = [&](uint32_t jj) { return jj < READS && ((present_b >> (jj * KMERS)) & 1ull) && !((irr_b >> (jj * KMERS)) & 1ull); };
+            auto finish = [&](uint4 acc, bool rd, uint32_t jj, uint32_t jbase) {
+                acc.x &= cm[0]; acc.y &= cm[1]; acc.z &= cm[2]; acc.w &= cm[3];
+                const uint64_t bal = ballot64(rd && (acc.x | acc.y | acc.z | acc.w) != 0u);
+                const uint64_t mine_b = (bal >> (sub << lpr_log2)) & lmask;
+                if (rd && mine_b) *reinterpret_cast<uint4 *>(live_out + jj * rw + part * 4u) = acc;
+                for (uint32_t r = 0; r < rps && jbase + r < READS; ++r)
+                    if ((bal >> (r << lpr_log2)) & lmask) survive |= 1u << (jbase + r);
+            };
+            for (uint32_t j0 = 0; j0 < READS; j0 += 2u * rps) {
+                const bool second = j0 + rps < READS;  // (wave-uniform: rows of 4 or 8 words screen all 32 reads in one sub-pass)
+                const uint32_t ja = j0 + sub, jb = j0 + rps + sub;
+                const bool rda = screened(ja), rdb = second && screened(jb);
+                const uint4 xa = *reinterpret_cast<const uint4 *>(idx + (rda ? ja : 0u) * 4u);
+                uint4 acc_a = make_uint4(~0u, ~0u, ~0u, ~0u), acc_b = acc_a;
+                if (second) {
+                    const uint4 xb = *reinterpret_cast<const uint4 *>(idx + (rdb ? jb : 0u) * 4u);
+                    const uint32_t xs[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+                    uint4 m[8];
+#pragma unroll
+                    for (uint32_t u = 0; u < 8; ++u) {
+                        const uint32_t x = (u < 4 ? rda : rdb) ? xs[u] : a.ones_row;
+                        m[u] = *reinterpret_cast<const uint4 *>(a.S + (uint64_t)x * rw + part * 4u);
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < 4; ++u) {
+                        acc_a.x &= m[u].x; acc_a.y &= m[u].y; acc_a.z &= m[u].z; acc_a.w &= m[u].w;
+                        acc_b.x &= m[u + 4].x; acc_b.y &= m[u + 4].y; acc_b.z &= m[u + 4].z; acc_b.w &= m[u + 4].w;
+                    }
+                } else {
+                    const uint32_t xs[4] = {xa.x, xa.y, xa.z, xa.w};
+                    uint4 m[4];
+#pragma unroll
+                    for (uint32_t u = 0; u < 4; ++u) m[u] = *reinterpret_cast<const uint4 *>(a.S + (uint64_t)(rda ? xs[u] : a.ones_row) * rw + part * 4u);
+#pragma unroll
+                    for (uint32_t u = 0; u < 4; ++u) {
+                        acc_a.x &= m[u].x; acc_a.y &= m[u].y; acc_a.z &= m[u].z; acc_a.w &= m[u].w;
+                    }
+                }
+                finish(acc_a, rda, ja, j0);
+                if (second) finish(acc_b, rdb, jb, j0 + rps);
+            }
+            if (irr_b)
+                for (uint32_t jj = 0; jj < READS; ++jj)
+                    if ((irr_b >> (jj * KMERS)) & 1ull) irregular |= 1u << jj;
+            __builtin_amdgcn_wave_barrier();
+            return survive;
+        }
         for (uint32_t j0 = 0; j0 < DENSE_READS; j0 += rps) {
             const uint32_t jj = j0 + (lane >> lpr_log2);
             const bool rd = jj < DENSE_READS && ((present_b >> (jj * 4u)) & 1ull) && !((irr_b >> (jj * 4u)) & 1ull);
@@ -705,10 +765,15 @@ __device__ __forceinline__ uint32_t queue_long_reads(const QueryArgs &a, uint32_
 // LIST: the launch of a leaf group of a two-level frontier — its reads are the ones k_coarse listed for the group (read_list).
 // (the theta = 1 builds that defer leaf pairs are held to four waves per SIMD — 128 VGPRs: with the batched emission beside the
 // per-read path the allocator stops at 129 on its own, bounded it takes 124 without a spill.)
-template <bool DEFER, bool COUNTS, bool LONG = false, uint32_t LPR_LOG2 = 0, bool BLOCKS = false, bool LIST = false>
+// LEAN (the theta = 1 build that defers leaf pairs of all reads — DEFER, not COUNTS, BLOCKS or LIST): the dense screen takes
+// LEAN_KMERS k-mers of LEAN_READS reads a pass (dense_screen<false, LEAN_KMERS>); the group loop and the batched emission take
+// their reads per pass and lanes per read from it.  The host launches it where the tree's fill allows (plan()).
+template <bool DEFER, bool COUNTS, bool LONG = false, uint32_t LPR_LOG2 = 0, bool BLOCKS = false, bool LIST = false, bool LEAN = false>
 __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_LOG2 != 4) ? 3 : ((DEFER && !COUNTS && !BLOCKS) ? 4 : 1)) k_classify(QueryArgs a) {
+    static_assert(!LEAN || (DEFER && !COUNTS && !LONG && !BLOCKS && !LIST), "the lean screen serves the pair pipeline at theta = 1 only");
+    constexpr uint32_t SCR_KMERS = LEAN ? LEAN_KMERS : DENSE_KMERS, SCR_READS = 64u / SCR_KMERS;  // lanes per read, reads per pass of the dense screen
     __shared__ BlockLds lds;
-    __shared__ DenseLds<(DEFER && !LONG) || COUNTS> dlds;
+    __shared__ DenseLds<(DEFER && !LONG) || COUNTS, LEAN> dlds;
     fill_complement(lds.comp);
     __syncthreads();
     if ((LIST || LONG) && a.grid_groups) {  // (block-uniform) one launch for all leaf groups of a two-level frontier: mine is blockIdx.y
@@ -868,7 +933,8 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     // Batched emission (theta == 1, leaf pairs, a.batch_emit): the survivors of a pass of the dense screen are regular reads
     // (need == n, no miss tolerated), so all a wave has to do for them is turn the set bits of their frontier words — still in
     // LDS, dlds.live[wave][read * rw + word], masked with the leaf columns — into pairs.  Lanes are (read = lane >> 2, quarter
-    // of the row = lane & 3) as in the screen's hashing: a lane counts the bits of its rw / 4 words, an exclusive prefix sum
+    // of the row = lane & 3) as in the screen's hashing (LEAN: read = lane >> 1, half of the row = lane & 1, 32 reads a pass):
+    // a lane counts the bits of its rw / 4 (rw / 2) words, an exclusive prefix sum
     // over the wave gives it the slot of its first pair — lane order is read-major and column-ascending, which keeps a
     // read's pairs in consecutive slots (k_tail_records) — and every lane writes its own pairs.  Slots come from the wave's
     // current reservation while it lasts and from ONE further reservation of whole chunks for the rest, whose unused end
@@ -879,14 +945,14 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     const bool batch_emit = DEFER && !COUNTS && !BLOCKS && a.batch_emit && (!a.recs || a.split_recs);
     const bool recs_fit = !a.recs || a.off[a.n_reads] <= a.rec_cap;  // (wave-uniform) every read's records fit
     auto emit_pass = [&](uint32_t survive, uint32_t rid, uint64_t lane_len) -> uint32_t {
-        const uint32_t jj = lane >> 2, t = lane & 3u, qw = rw >> 2;
+        const uint32_t jj = lane / SCR_KMERS, t = lane & (SCR_KMERS - 1u), qw = rw / SCR_KMERS;
         uint32_t take = survive;
         if (!recs_fit) {
             bool fits = true;
             if (t == 0 && ((survive >> jj) & 1u)) fits = a.off[rid] + (lane_len - a.hp.k + 1) <= a.rec_cap;  // (regular: length >= k)
             uint64_t nf = ballot64(!fits);
             while (nf) {
-                take &= ~(1u << (((uint32_t)__ffsll((unsigned long long)nf) - 1u) >> 2));
+                take &= ~(1u << (((uint32_t)__ffsll((unsigned long long)nf) - 1u) / SCR_KMERS));
                 nf &= nf - 1ull;
             }
             if (!take) return survive;
@@ -930,11 +996,11 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
                 // to process_read, which certifies inline what it finds no slot for.
                 full = true;
                 const uint32_t room = left + (nbase < a.pair_cap ? (uint32_t)(a.pair_cap - nbase) : 0u);
-                put = mine && (uint32_t)__shfl((int)incl, (int)(lane | 3u)) <= room;
+                put = mine && (uint32_t)__shfl((int)incl, (int)(lane | (SCR_KMERS - 1u))) <= room;
                 const uint64_t pb = ballot64(put);
                 T = pb ? bcast_u32(incl, 63 - (int)__clzll((unsigned long long)pb)) : 0u;
                 take = 0;
-                for (uint32_t j = 0; j < DENSE_READS; ++j) take |= (uint32_t)((pb >> (4u * j)) & 1ull) << j;
+                for (uint32_t j = 0; j < SCR_READS; ++j) take |= (uint32_t)((pb >> (SCR_KMERS * j)) & 1ull) << j;
                 for (unsigned long long i = nbase + (T > left ? T - left : 0u) + lane; i < a.pair_cap; i += 64) a.pairs[i] = make_uint2(0xffffffffu, 0xffffffffu);
             }
         }
@@ -972,26 +1038,26 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     if (LIST) n_work = *a.n_list;
     const uint32_t *const read_list = LIST ? a.read_list : nullptr;
     if (DEFER && !COUNTS && a.rw >= 4u) {
-        // groups of DENSE_READS consecutive reads: dense pre-screen, then the per-read path for the survivors
-        const uint64_t n_groups = (n_work + DENSE_READS - 1) / DENSE_READS;
+        // groups of SCR_READS consecutive reads: dense pre-screen, then the per-read path for the survivors
+        const uint64_t n_groups = (n_work + SCR_READS - 1) / SCR_READS;
         for (uint64_t g = gw; g < n_groups; g += nw) {
-            const uint64_t r0 = g * DENSE_READS;
-            const uint32_t cnt = (uint32_t)(n_work - r0 < DENSE_READS ? n_work - r0 : DENSE_READS);
+            const uint64_t r0 = g * SCR_READS;
+            const uint32_t cnt = (uint32_t)(n_work - r0 < SCR_READS ? n_work - r0 : SCR_READS);
             uint64_t lane_len;
             uint32_t irregular, rid;
-            uint32_t survive = dense_screen<false>(dlds.mini[wave][0], dlds.mini[wave][1], lds.comp, dlds.live[wave], a, read_list, r0, cnt,
-                                                   colmask, 2u, irregular, lane_len, rid);
-            if (!(((survive | irregular) >> (lane >> 2)) & 1u)) dense_bytes += lane_len;  // reads finished here still count their bytes
+            uint32_t survive = dense_screen<false, SCR_KMERS>(dlds.mini[wave][0], dlds.mini[wave][1], lds.comp, dlds.live[wave], a, read_list, r0, cnt,
+                                                              colmask, 2u, irregular, lane_len, rid);
+            if (!(((survive | irregular) >> (lane / SCR_KMERS)) & 1u)) dense_bytes += lane_len;  // reads finished here still count their bytes
             if (!BLOCKS && batch_emit && survive) survive = emit_pass(survive, rid, lane_len);
             while (survive) {
                 const uint32_t jj = (uint32_t)__ffs((int)survive) - 1u;
                 survive &= survive - 1u;
-                process_read(LIST ? (uint64_t)bcast_u32(rid, (int)(jj * 4u)) : r0 + jj, dlds.live[wave] + jj * rw);
+                process_read(LIST ? (uint64_t)bcast_u32(rid, (int)(jj * SCR_KMERS)) : r0 + jj, dlds.live[wave] + jj * rw);
             }
             while (irregular) {
                 const uint32_t jj = (uint32_t)__ffs((int)irregular) - 1u;
                 irregular &= irregular - 1u;
-                process_read(LIST ? (uint64_t)bcast_u32(rid, (int)(jj * 4u)) : r0 + jj, nullptr);
+                process_read(LIST ? (uint64_t)bcast_u32(rid, (int)(jj * SCR_KMERS)) : r0 + jj, nullptr);
             }
         }
     } else if constexpr (COUNTS && !LONG && LPR_LOG2 >= 2u) {
@@ -1087,6 +1153,7 @@ template <bool LIST>
 static void launch_classify_l(const QueryArgs &a, bool defer, bool counts_mode, dim3 g, dim3 b, hipStream_t st) {
     if (!counts_mode) {
         if (defer && a.block_pairs) hipLaunchKernelGGL((k_classify<true, false, false, 0, true, LIST>), g, b, 0, st, a);
+        else if (defer && !LIST && a.lean_screen) hipLaunchKernelGGL((k_classify<true, false, false, 0, false, false, true>), g, b, 0, st, a);
         else if (defer) hipLaunchKernelGGL((k_classify<true, false, false, 0, false, LIST>), g, b, 0, st, a);
         else hipLaunchKernelGGL((k_classify<false, false, false, 0, false, LIST>), g, b, 0, st, a);
         return;

@@ -212,6 +212,13 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_tile_lists_info(self._h, out.ctypes.data))
         return {k: int(v) for k, v in zip(("columns", "bytes", "list_tiles", "dense_tiles"), out)}
 
+    def screen_info(self) -> dict:
+        """The dense screen at theta = 1 (pfq_screen_info): `kmers` a read the last query call's screen took (2: the lean build,
+        4, 0: no such screen), the tree's `E` (expected false candidates a random read after four rows), `rw` and `groups`."""
+        out = np.zeros(4, dtype=np.float64)
+        _ffi.check(_ffi.lib().pfq_screen_info(self._h, out.ctypes.data))
+        return {"kmers": int(out[0]), "E": float(out[1]), "rw": int(out[2]), "groups": int(out[3])}
+
     def tile_list(self, col: int, tile: int) -> np.ndarray:
         """One slot (pfq_debug_tile_list): TILE_LIST_CAP u32, the tile-relative positions of the tile's set bits in any order,
         then TILE_LIST_NONE.  Raises PfqError for a column without slots."""
