@@ -1009,6 +1009,17 @@ int pfq_tile_lists_info(pfq_tree *tree, uint64_t out[4]);
  * groups.  (A call of its own and not a bit of pfq_stats.pair_stage: callers compare the bits of pair_stage above 3 with the
  * tail shapes.) */
 int pfq_screen_info(pfq_tree *tree, double out[4]);
+/* The pair slots of k_classify at theta = 1: a wave appends its deferred pairs to ranges of the pair buffer
+ * that it reserves in whole chunks of 32 slots with one atomic on the buffer's cursor.  A batched emission that has to reserve
+ * asks, beyond what its pass needs, for min(A x 32, pairs of the pass x groups of reads the wave still has to screen) slots,
+ * rounded up to 32, so that the next passes find their slots reserved; what a wave leaves unused is voided (at most
+ * (A + 1) x 32 slots a wave).  Option PFQ_PAIR_AHEAD: A = 0 .. 16, unset 8; 0: every pass reserves what it needs and no more.
+ * Option PFQ_CLASSIFY_BLOCKS (tests): a cap on the grid of the classify launches — without it every wave of a small input has
+ * one group of reads and never reserves ahead.  Results do not depend on either.  out[1] A of the last query call's classify
+ * launches (0: it deferred no leaf pairs a pass at a time — direct path, thresholds below 1, block mode, PFQ_BATCH_EMIT=0),
+ * [2] reservations those launches made (waits for the call); [0] and [3] are 0: they are kept for the bucket histogram made
+ * from the pair buffer by a kernel of its own, which was measured and not built. */
+int pfq_pair_info(pfq_tree *tree, uint64_t out[4]);
 /* Copy min(n, 8192) entries of the slot of (column, tile) to the host: positions < 2^20 in any order, unused entries
  * 0xffffffff.  A column without slots: PFQ_ERR_STATE. */
 int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n);

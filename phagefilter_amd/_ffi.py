@@ -30,7 +30,7 @@ SYMBOLS = [
     "pfq_save_leaf_counts", "pfq_leaf_counts_export", "pfq_leaf_counts_import", "pfq_leaf_counts_reset",
     "pfq_leaf_counts_export_delta", "pfq_leaf_counts_import_delta",
     "pfq_last_stats", "pfq_set_path", "pfq_profile_begin", "pfq_profile_end", "pfq_debug_kmer_indices", "pfq_debug_node_filter", "pfq_debug_last_capacity", "pfq_debug_last_similarity", "pfq_debug_last_recluster",
-    "pfq_tile_lists_info", "pfq_debug_tile_list", "pfq_debug_tile_bucket", "pfq_screen_info",
+    "pfq_tile_lists_info", "pfq_debug_tile_list", "pfq_debug_tile_bucket", "pfq_screen_info", "pfq_pair_info",
     "pfq_synth_genomes_device",
     "pfq_synth_reads_device", "pfq_host_alloc", "pfq_host_free", "pfq_last_error", "pfq_version",
 ]
@@ -326,6 +326,8 @@ def lib() -> C.CDLL:
         L.pfq_debug_tile_bucket.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
     if hasattr(L, "pfq_screen_info"):  # (likewise: an older build has one dense screen)
         L.pfq_screen_info.argtypes = [vp, vp]
+    if hasattr(L, "pfq_pair_info"):  # (likewise: an older build reserves pair slots one pass at a time)
+        L.pfq_pair_info.argtypes = [vp, vp]
     L.pfq_synth_genomes_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]
     L.pfq_synth_reads_device.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64,
                                          C.c_uint64, vp]

@@ -115,6 +115,8 @@ struct Knobs {
     long long tile_stream = -1;                 // 0: the generic k_tile_test<0> even where every column has slots (unset: the slots-only build there)
     long long screen_kmers = -1;                // k-mers a read of the dense screen at threshold 1: 0 / unset chosen per tree from its leaves' fill, 2 wherever rows have <= 32 words, 4 always
     long long entry_pack = -1;                  // packed tile entries at threshold 1: 0 never, 1 / unset chosen per call from its read lengths, 2 always
+    long long pair_ahead = -1;                  // reservations of 32 pair slots a batched emission of k_classify asks for beyond what its pass needs: 0 .. 16, unset: 8
+    long long classify_blocks = -1;             // tests: a cap on the grid of the classify launches (a wave then screens several groups of a small input)
     long long fmt_grid = -1, fmt_hash_bits = -1, fmt_time = -1;  // pfq_text_format: a cap on every grid; bits of the id hash that are kept (1 .. 64); 1: time the stages with HIP events
 };
 struct KnobName {
@@ -152,6 +154,7 @@ const KnobName KNOBS[] = {
     {"PFQ_ENTRY_PACK", &Knobs::entry_pack},     {"PFQ_SCREEN_KMERS", &Knobs::screen_kmers},
     {"PFQ_FMT_GRID", &Knobs::fmt_grid},         {"PFQ_FMT_HASH_BITS", &Knobs::fmt_hash_bits},
     {"PFQ_FMT_TIME", &Knobs::fmt_time},
+    {"PFQ_PAIR_AHEAD", &Knobs::pair_ahead},     {"PFQ_CLASSIFY_BLOCKS", &Knobs::classify_blocks},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -406,6 +409,7 @@ struct pfq_tree {
     // last_screen_kmers: k-mers a read the dense screen of the last call's deferring launch took (2: the lean build, 4, 0: none ran).
     double screen_E = 0.0;
     uint32_t last_screen_kmers = 0;
+    uint32_t last_pair_ahead = 0;  // QueryArgs::pair_ahead of the last call's classify launches (pfq_pair_info); 0: none deferred
     std::vector<uint8_t> out_cov_regs;
     std::vector<double> out_cov_distinct, out_cov_genome;
     // pfq_query_frames: the frame table of the call (per sequence its first frame and the scan of the lone frames' deficits; per
@@ -1421,7 +1425,7 @@ int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
 constexpr uint64_t CLASSIFY_MAX_BLOCKS = 4096;  // blocks of 4 waves; every wave may leave one reservation partly used
 
 // Scratch of the bucketed path.  false: not enough device memory, the caller stays on the direct kernel.
-bool ensure_bucket_scratch(pfq_tree &t, uint64_t n_reads, bool with_guards, uint64_t launch_waves) {
+bool ensure_bucket_scratch(pfq_tree &t, uint64_t n_reads, bool with_guards, uint64_t launch_waves, uint32_t pair_ahead) {
     if (!t.h_pair_cursor) {
         if (hipHostMalloc((void **)&t.h_pair_cursor, HINT_N * 8, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
@@ -1440,9 +1444,10 @@ bool ensure_bucket_scratch(pfq_tree &t, uint64_t n_reads, bool with_guards, uint
     }
     (void)hipGetLastError();  // hipEventQuery reports "not ready" through the error state
     // room for two candidates per read, or for 1.3 x what recent calls deferred (at most 24 per read: 40 B per slot);
-    // + one partially used reservation per wave.  Pairs that do not fit are certified inline (exact, slow).
+    // + one partially used reservation per wave and the pair_ahead it may hold beyond.  Pairs that do not fit are certified
+    // inline (exact, slow).
     const double per_read = std::min(24.0, std::max(2.0, 1.3 * t.pairs_per_read));
-    uint64_t cap = ((uint64_t)(per_read * (double)n_reads) + pfq::PAIR_RESERVE * launch_waves + 1024 + 31) & ~31ull;
+    uint64_t cap = ((uint64_t)(per_read * (double)n_reads) + (1 + (uint64_t)pair_ahead) * pfq::PAIR_RESERVE * launch_waves + 1024 + 31) & ~31ull;
     // pairs deferred by k_classify: slots [0, leaf_cap); guard pairs (k_expand_guards): [leaf_cap, leaf_cap + guard_cap),
     // sized by the tree's guards per leaf (what does not fit is certified inline there)
     if (t.d_pairs.n && t.leaf_cap >= cap) cap = t.leaf_cap;  // (the buffers only grow)
@@ -1488,7 +1493,7 @@ struct QueryRun {
     bool guard_pairs = false;  // guard columns outside block mode: the guards are pairs of their own, in a region of their own
     bool recs_possible = false, bucketed = false, block_mode = false, want_two_level = false, lean_screen = false;
     size_t nl = 0, nc = 0, guarded = 0, nb = 0, mem_free = 0, mem_total = 0;
-    uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0;
+    uint32_t group_cols = 0, leaf_groups = 1, n_tiles_block = 0, sub_log2 = 0, pair_ahead = 0;
     int blocks = 0, blocks_group = 0;
     uint64_t launch_waves = 0, n_blocks = 0, miss_cap = 0, hit_cap = 0;
     // ---- one attempt
@@ -1569,10 +1574,13 @@ struct QueryRun {
         group_cols = 1u << t.group_log2;
         leaf_groups = (uint32_t)std::max<size_t>(1, (nl + group_cols - 1) / group_cols);
         blocks = (int)std::min<uint64_t>((n_reads + 3) / 4, CLASSIFY_MAX_BLOCKS);  // (2048: 10.1 ms, 4096: 9.9 ms per step)
+        if (kn.classify_blocks > 0) blocks = (int)std::min<long long>(blocks, kn.classify_blocks);
+        // threshold 1: a wave's batched emission reserves pair slots for its next passes too (k_classify, emit_pass)
+        pair_ahead = threshold >= 1.0f ? (uint32_t)(kn.pair_ahead >= 0 ? std::min<long long>(kn.pair_ahead, 16) : 8) : 0u;
         want_two_level = t.coarse_valid && leaf_groups > 1 && (kn.coarse > 0 || threshold >= 1.0f || t.coarse_fill <= 0.70);
         blocks_group = want_two_level ? std::min(blocks, 1024) : blocks;  // (a list holds a fraction of the reads)
         launch_waves = 4ull * (uint64_t)blocks_group * leaf_groups * (threshold >= 1.0f ? 1 : 2);
-        if (bucketed && !ensure_bucket_scratch(t, n_reads, with_guards, launch_waves)) bucketed = false;
+        if (bucketed && !ensure_bucket_scratch(t, n_reads, with_guards, launch_waves, pair_ahead)) bucketed = false;
         if (bucketed && recs_possible && !soft_ensure(t.d_meta, t.d_pairs.n)) recs_possible = false;
         if (bucketed && thr_frac && !recs_possible) bucketed = false;
         counts_mode = !(threshold >= 1.0f);  // theta >= 1: need >= n for every read with k-mers
@@ -1635,6 +1643,7 @@ struct QueryRun {
             }
         }
         t.last_screen_kmers = 0;
+        t.last_pair_ahead = 0;
         t.last_path = bucketed ? 1 : 0;
         t.last_sort = 0;
         if (!bucketed) t.last_tile_mode = t.last_tile_bin = 0;  // (the direct path runs no tile pass)
@@ -1896,6 +1905,8 @@ struct QueryRun {
         a.block_pairs = block_mode ? 1u : 0u;
         a.batch_emit = kn.batch_emit != 0 ? 1u : 0u;  // (PFQ_BATCH_EMIT=0: the per-read loop for every survivor)
         a.lean_screen = lean_screen ? 1u : 0u;
+        a.pair_ahead = (!counts_mode && !block_mode && a.batch_emit) ? pair_ahead : 0u;  // (only the batched emission reserves ahead)
+        t.last_pair_ahead = a.pair_ahead;
         t.last_screen_kmers = counts_mode ? 0u : (lean_screen ? 2u : 4u);  // (thresholds < 1 have the counting screen)
         a.screen_recs = kn.screen_recs >= 0 ? (uint32_t)(kn.screen_recs != 0) : 1u;
         if (block_mode) {
@@ -5976,6 +5987,20 @@ int pfq_screen_info(pfq_tree *tree, double out[4]) {
     out[1] = t.screen_E;
     out[2] = (double)t.rw;
     out[3] = (double)t.n_groups;
+    return PFQ_OK;
+}
+int pfq_pair_info(pfq_tree *tree, uint64_t out[4]) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (t.last_path && t.d_stats.p) {
+        PFQ_TRY(wait_last_call(t));
+        unsigned long long r = 0;
+        HIP_TRY(hipMemcpy(&r, t.d_stats.p + pfq::ST_PAIR_RESERVATIONS, sizeof r, hipMemcpyDeviceToHost));
+        out[1] = t.last_pair_ahead;
+        out[2] = r;
+    }
     return PFQ_OK;
 }
 int pfq_debug_tile_list(pfq_tree *tree, uint64_t col, uint64_t tile, uint32_t *out, uint64_t n) {

@@ -26,7 +26,7 @@ namespace pfq {
 #define PFQ_DEBUG_BITS(a) 0u
 #endif
 constexpr uint32_t PAIR_RESERVE = 32, MISS_RESERVE = 256;
-enum StatSlot { ST_CANDIDATES = 0, ST_HITS = 1, ST_ALLHIT = 2, ST_ALG_BYTES = 3, ST_DEFERRED = 4, ST_LISTED = 5 /* (read, leaf group) entries of a two-level frontier */, ST_BATCHED = 6 /* pairs emitted a pass at a time */, ST_N = 8 };
+enum StatSlot { ST_CANDIDATES = 0, ST_HITS = 1, ST_ALLHIT = 2, ST_ALG_BYTES = 3, ST_DEFERRED = 4, ST_LISTED = 5 /* (read, leaf group) entries of a two-level frontier */, ST_BATCHED = 6 /* pairs emitted a pass at a time */, ST_PAIR_RESERVATIONS = 7 /* reservations the classify launches made in the pair buffer */, ST_N = 8 };
 
 struct QueryArgs {
     HashParams hp;
@@ -68,6 +68,8 @@ struct QueryArgs {
     unsigned long long *pair_cursor;
     uint32_t *bucket_cnt;        // [n_leaves << sub_log2]: bucket = (leaf << sub_log2) | (read & (subs-1))
     uint32_t sub_log2;           // sub-buckets per leaf (so that no counter is a hot spot when leaves are few)
+    uint32_t pair_ahead;         // A: a batched emission that has to reserve asks for up to A further reservations of PAIR_RESERVE slots
+                                 // for the wave's next passes (PFQ_PAIR_AHEAD; 0: what the pass needs and no more)
     uint4 *recs;                 // probe records, indexed by (read byte offset + k-mer position), or nullptr
     uint64_t rec_cap;            // entries in recs (reads whose records would not fit are certified inline)
     uint32_t *long_list;         // thresholds < 1: reads of >= 256 k-mers, classified by a second launch (wider counters)

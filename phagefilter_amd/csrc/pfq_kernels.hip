@@ -796,10 +796,14 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     if (word * 32u < a.n_leaves) colmask = (a.n_leaves - word * 32u >= 32u) ? ~0u : ((1u << (a.n_leaves - word * 32u)) - 1u);
     unsigned long long st_cand = 0, st_hits = 0, st_all = 0, st_bytes = 0, st_def = 0;
     unsigned long long dense_bytes = 0;  // per lane
-    // deferred pairs are appended through per-wave reservations of PAIR_CHUNK slots: one atomic on the shared
-    // cursor per chunk (a single hot address saturates at ~88 atomics/us); unused slots are voided at the end
-    unsigned long long pair_base = 0;
-    uint32_t pair_used = PAIR_CHUNK;
+    // deferred pairs are appended through per-wave reservations of whole PAIR_CHUNKs of slots: one atomic on the shared
+    // cursor per reservation (a single hot address saturates at ~88 atomics/us: 131 k reservations of a flagship step were
+    // 0.46 ms of this kernel; the batched emission therefore reserves ahead, see emit_pass).  The wave's current range is
+    // [pair_pos, pair_pos + pair_left), wave-uniform; what is left of it at the end is voided.
+    unsigned long long pair_pos = 0;
+    uint32_t pair_left = 0;
+    uint32_t groups_left = 0;  // (wave-uniform) groups of reads the wave still has to screen after the current one
+    uint32_t st_resv = 0;      // reservations made (ST_PAIR_RESERVATIONS)
     uint32_t miss_left = 0;  // thresholds < 1: miss words this wave may still hand out (reserved MISS_RESERVE at a time)
 
     // pre: frontier words from the dense screen; n_done: k-mers (from the first on) whose probe records the screen wrote
@@ -861,27 +865,29 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
                 if (got + want <= a.miss_cap) miss_left = want;  // else: no room, this pair is certified inline
             }
             if (DEFER && (!a.recs || o0 + rc.n <= a.rec_cap) && miss_left >= miss_need) {
-                if (pair_used == PAIR_CHUNK) {  // wave-uniform
+                if (pair_left == 0) {  // wave-uniform
                     unsigned long long base = 0;
                     if (lane == 0) base = atomicAdd(a.pair_cursor, (unsigned long long)PAIR_CHUNK);
                     base = ((unsigned long long)bcast_u32((uint32_t)(base >> 32), 0) << 32) | bcast_u32((uint32_t)base, 0);
+                    ++st_resv;
                     if (base + PAIR_CHUNK <= a.pair_cap) {
-                        pair_base = base;
-                        pair_used = 0;
+                        pair_pos = base;
+                        pair_left = PAIR_CHUNK;
                     }
                 }
-                if (pair_used < PAIR_CHUNK) {
+                if (pair_left != 0) {
                     if (lane == 0) {
                         // (block mode: buckets by (block, mask) — the pairs of a chunk share their mask)
                         const uint32_t blk = col >> BLOCK_LEAVES_LOG2;
                         const uint32_t key = BLOCKS ? ((blk << 8) | mask8) : col;
                         const uint32_t bkt = (key << a.sub_log2) | ((uint32_t)r & ((1u << a.sub_log2) - 1u));
-                        a.pairs[pair_base + pair_used] = make_uint2((uint32_t)r, BLOCKS ? (blk | (mask8 << 24)) : col);
+                        a.pairs[pair_pos] = make_uint2((uint32_t)r, BLOCKS ? (blk | (mask8 << 24)) : col);
                         atomicAdd(&a.bucket_cnt[bkt], 1u);
                         if (COUNTS && a.bucket_words) atomicAdd(&a.bucket_words[bkt], miss_need);
                     }
                     miss_left -= miss_need;
-                    ++pair_used;
+                    ++pair_pos;
+                    --pair_left;
                     ++st_def;
                     // (a.split_recs: the pair is all this kernel leaves behind — k_tail_records hashes the read, 7 waves per SIMD
                     // there against 4 here and no frontier between two windows)
@@ -937,8 +943,8 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     // a lane counts the bits of its rw / 4 (rw / 2) words, an exclusive prefix sum
     // over the wave gives it the slot of its first pair — lane order is read-major and column-ascending, which keeps a
     // read's pairs in consecutive slots (k_tail_records) — and every lane writes its own pairs.  Slots come from the wave's
-    // current reservation while it lasts and from ONE further reservation of whole chunks for the rest, whose unused end
-    // becomes the current reservation.  Returns the reads left to process_read: the ones whose records would not fit, and the
+    // current range while it lasts and from ONE further reservation of whole chunks for the rest — and, a.pair_ahead, for the
+    // wave's next passes — whose unused end becomes the current range.  Returns the reads left to process_read: the ones whose records would not fit, and the
     // reads whose pairs reach past the end of a full pair buffer (process_read certifies inline what finds no slot: results
     // do not depend on capacities).
     uint32_t st_bat = 0;  // pairs written here (ST_BATCHED)
@@ -983,13 +989,23 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
             }
         }
         uint32_t T = bcast_u32(incl, 63);  // pairs of the pass
-        const uint32_t left = PAIR_CHUNK - pair_used;
+        const uint32_t left = pair_left;
         unsigned long long nbase = 0;
+        uint32_t want = 0;
         bool put = mine, full = false;
-        if (T > left) {  // (wave-uniform) one reservation of whole chunks for what the current one does not hold
-            const unsigned long long want = (unsigned long long)((T - left + PAIR_CHUNK - 1u) / PAIR_CHUNK) * PAIR_CHUNK;
-            if (lane == 0) nbase = atomicAdd(a.pair_cursor, want);
+        if (T > left) {  // (wave-uniform) one reservation of whole chunks for what the current one does not hold ...
+            want = (T - left + PAIR_CHUNK - 1u) & ~(PAIR_CHUNK - 1u);
+            // ... and for the wave's next passes: up to pair_ahead chunks, but no more than passes like this one would fill
+            // in the groups the wave still has to screen (the last pass of a wave asks for nothing extra: a call whose
+            // waves have one group each reserves what it needs and no more)
+            if (a.pair_ahead && groups_left) {
+                const uint32_t cap_ahead = a.pair_ahead * PAIR_CHUNK;
+                const uint32_t ahead = (groups_left >= cap_ahead || T >= cap_ahead) ? cap_ahead : (T * groups_left < cap_ahead ? T * groups_left : cap_ahead);
+                want += (ahead + PAIR_CHUNK - 1u) & ~(PAIR_CHUNK - 1u);
+            }
+            if (lane == 0) nbase = atomicAdd(a.pair_cursor, (unsigned long long)want);
             nbase = bcast_u64(nbase, 0);
+            ++st_resv;
             if (nbase + want > a.pair_cap) {
                 // The pair buffer is full.  The reads whose pairs all lie below its end are still emitted here (they are the
                 // first of the pass), the slots behind them are voided and no reservation is kept; the other reads are left
@@ -1013,7 +1029,7 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
                 while (w) {
                     const uint32_t col = cbase + (uint32_t)__ffs((int)w) - 1u;
                     w &= w - 1u;
-                    a.pairs[s < left ? pair_base + pair_used + s : nbase + (s - left)] = make_uint2(rid, col);
+                    a.pairs[s < left ? pair_pos + s : nbase + (s - left)] = make_uint2(rid, col);
                     atomicAdd(&a.bucket_cnt[(col << a.sub_log2) | (rid & sub_mask)], 1u);
                     ++s;
                 }
@@ -1021,11 +1037,12 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
             dense_bytes += lane_len;  // (on the read's first lane)
         }
         if (T <= left) {
-            pair_used += T;
-        } else {  // the new reservation's last chunk, if partly used, is the wave's current one (voided when the buffer is full)
+            pair_pos += T;
+            pair_left -= T;
+        } else {  // what the pass leaves of the new reservation is the wave's current range (nothing when the buffer is full: voided above)
             const uint32_t over = T - left;
-            pair_base = nbase + (over & ~(PAIR_CHUNK - 1u));
-            pair_used = ((over & (PAIR_CHUNK - 1u)) && !full) ? (over & (PAIR_CHUNK - 1u)) : PAIR_CHUNK;
+            pair_pos = nbase + over;
+            pair_left = full ? 0u : want - over;
         }
         st_cand += T;
         st_def += T;
@@ -1040,7 +1057,9 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     if (DEFER && !COUNTS && a.rw >= 4u) {
         // groups of SCR_READS consecutive reads: dense pre-screen, then the per-read path for the survivors
         const uint64_t n_groups = (n_work + SCR_READS - 1) / SCR_READS;
+        if (gw < n_groups) groups_left = (uint32_t)(n_groups - 1 - gw) / (uint32_t)nw + 1u;  // (reads < 2^31, waves <= 2^22)
         for (uint64_t g = gw; g < n_groups; g += nw) {
+            --groups_left;
             const uint64_t r0 = g * SCR_READS;
             const uint32_t cnt = (uint32_t)(n_work - r0 < SCR_READS ? n_work - r0 : SCR_READS);
             uint64_t lane_len;
@@ -1121,8 +1140,8 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
     } else {
         for (uint64_t r = gw; r < a.n_reads; r += nw) process_read(r, nullptr);
     }
-    if (DEFER && pair_used < PAIR_CHUNK)
-        for (uint32_t i = pair_used + lane; i < PAIR_CHUNK; i += 64) a.pairs[pair_base + i] = make_uint2(0xffffffffu, 0xffffffffu);
+    if (DEFER)
+        for (uint32_t i = lane; i < pair_left; i += 64) a.pairs[pair_pos + i] = make_uint2(0xffffffffu, 0xffffffffu);
     // reads that pass every node (need == 0) count at every leaf (query.rs:143 reached through every path)
     if (st_all && !(!DEFER && a.screen_only))
         for (uint32_t c = lane; c < a.n_leaves; c += 64) atomicAdd(&a.counts[a.col0 + c], st_all);
@@ -1136,6 +1155,7 @@ __global__ void __launch_bounds__(256, (COUNTS && !LONG && LPR_LOG2 != 0 && LPR_
         if (st_bytes) atomicAdd(&a.stats[ST_ALG_BYTES], st_bytes);
         if (st_def) atomicAdd(&a.stats[ST_DEFERRED], st_def);
         if (st_bat) atomicAdd(&a.stats[ST_BATCHED], (unsigned long long)st_bat);
+        if (st_resv) atomicAdd(&a.stats[ST_PAIR_RESERVATIONS], (unsigned long long)st_resv);
     }
 }
 

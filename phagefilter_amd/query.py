@@ -219,6 +219,14 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_screen_info(self._h, out.ctypes.data))
         return {"kmers": int(out[0]), "E": float(out[1]), "rw": int(out[2]), "groups": int(out[3])}
 
+    def pair_info(self) -> tuple:
+        """The pair slots of the last query call's classify launches (pfq_pair_info): [1] the reservations a batched emission
+        asks for beyond its pass (PFQ_PAIR_AHEAD as used; 0: no such emission ran), [2] the reservations the launches made;
+        [0] and [3] are 0 (no kernel counts the buckets from the pair buffer)."""
+        out = np.zeros(4, dtype=np.uint64)
+        _ffi.check(_ffi.lib().pfq_pair_info(self._h, out.ctypes.data))
+        return tuple(int(v) for v in out)
+
     def tile_list(self, col: int, tile: int) -> np.ndarray:
         """One slot (pfq_debug_tile_list): TILE_LIST_CAP u32, the tile-relative positions of the tile's set bits in any order,
         then TILE_LIST_NONE.  Raises PfqError for a column without slots."""
