@@ -583,6 +583,65 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
 int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits);
 int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out);  /* tests: the parsed CSR copied to the host */
 
+/* ---- blocked gzip (pfq_gz_scan, pfq_text_inflate, pfq_text_parse_inflated, pfq_text_read) ----
+ * A general gzip stream is one deflate stream and has no independent pieces; blocked gzip (BGZF: what bgzip and the sequencers'
+ * converters write and every htslib tool reads) is a sequence of independent gzip members of at most 64 KiB of text each, every
+ * member's compressed size in its header and its text size and CRC-32 in its trailer.  So the host finds every member and every
+ * output offset by walking headers, without inflating a byte, and the device inflates all members at once.
+ * pfq_gz_scan (no device): the members of gz[0, len) from gz[0] on.  The member at p is taken when all of these hold: bytes 1f 8b
+ *   08; FLG has FEXTRA and bits 5 - 7 clear; the extra field parses as subfields (SI1 SI2 SLEN data) that fill XLEN exactly, one of
+ *   them 'B' 'C' with SLEN 2 (the first such counts; others may precede or follow): its value is BSIZE and the member is BSIZE + 1
+ *   bytes; FNAME, FCOMMENT and FHCRC, if flagged, end inside the member; the deflate payload [header end, p + BSIZE + 1 - 8) has at
+ *   least one byte; ISIZE <= PFQ_GZ_MEMBER_TEXT_MAX; p + BSIZE + 1 <= len.  Stops, in this order: no byte left: END; fewer bytes
+ *   left than the fixed header with XLEN (12), the extra field or the member needs: MORE, with PFQ_TEXT_FINAL FOREIGN (a truncated
+ *   file: the host reader will say so); not such a member: FOREIGN; taking it would pass max_text, or 2^31 - 1 bytes of text:
+ *   LIMIT.  max_text 0: no limit of the caller's; 0 < max_text < PFQ_GZ_MEMBER_TEXT_MAX: PFQ_ERR_ARG, as are gz NULL with len > 0,
+ *   out NULL and flags other than PFQ_TEXT_FINAL.  Boundaries are found only by walking headers, never by searching for magic
+ *   bytes; a member of ISIZE 0 (the 28-byte end marker) is an ordinary member.  The tables are library-owned per calling thread
+ *   and valid until that thread's next pfq_gz_scan.
+ * pfq_text_inflate: scans as pfq_gz_scan does for the same arguments, copies gz[0, consumed) to the device on the tree's copy
+ *   stream, inflates every member there (one wave a member; the grid is min(members, PFQ_INFLATE_BLOCKS), unset: two workgroups a
+ *   compute unit) into a staging buffer of the tree (counted in pfq_info.device_bytes) and reads the statuses and CRCs back.  The
+ *   input is untrusted: a member the device does not follow to the letter is a status, never an error: 0 ok, 1 malformed deflate
+ *   (RFC 1951: a reserved block type, LEN != ~NLEN, HLIT > 286, HDIST > 30, a repeat with nothing before it or across the total, an
+ *   over-subscribed or incomplete code set - but for no distance code at all or exactly one of length 1 -, no end-of-block code,
+ *   symbols 286 / 287, distances 30 / 31, a distance beyond the member's own text, input that ends early), 2 length mismatch (text
+ *   beyond or short of ISIZE, payload bytes left over), 3 the text's CRC-32 differs from the trailer's.  When in doubt the device
+ *   rejects; the caller then lets zlib decide.  n_good: the leading members with status 0; good_text: their text bytes.  The call
+ *   changes no counter, no query result and not the parsed block; it waits for its own work.  The tables and statuses are owned
+ *   by the tree and valid until its next pfq_text_inflate.  gz may be reused when the call returns.  PFQ_ERR_ARG as pfq_gz_scan,
+ *   and for a NULL tree.
+ * pfq_text_parse_inflated: exactly pfq_text_parse(tree, carry ++ staged[0, good_text), carry_len + good_text, limit, format, flags,
+ *   out), staged being the text the last pfq_text_inflate on the tree left: the same fields, stops, rec_begin, alternating CSR sets
+ *   and follow-up calls (pfq_text_query, pfq_text_format, pfq_debug_text_csr, pfq_text_read see that text, offsets relative to the
+ *   carry's first byte).  The text is assembled on the device: the carry's upload, then a device-to-device copy of the staged text
+ *   behind it (the parse kernels want the text 16-byte aligned).  It may be repeated after one inflate.  Before an inflate on the
+ *   tree: PFQ_ERR_STATE; carry_len + good_text >= 2^31: PFQ_ERR_UNSUPPORTED; carry NULL with carry_len > 0: PFQ_ERR_ARG.
+ * pfq_text_read: bytes [from, from + n) of the text parsed last by either parse call, copied to dst (what a caller keeps as the
+ *   next carry).  Before a parse: PFQ_ERR_STATE; from + n beyond that text, dst NULL with n > 0: PFQ_ERR_ARG.
+ * pfq_debug_last_inflate: device milliseconds of the last pfq_text_inflate that had members, by HIP events: ms[0] the copies to
+ *   the device, ms[1] the kernel.  PFQ_ERR_STATE without one. */
+#define PFQ_GZ_MEMBER_TEXT_MAX 65536
+enum { PFQ_GZ_END = 0, PFQ_GZ_LIMIT = 1, PFQ_GZ_MORE = 2, PFQ_GZ_FOREIGN = 3 };
+enum { PFQ_GZ_OK = 0, PFQ_GZ_MALFORMED = 1, PFQ_GZ_LENGTH = 2, PFQ_GZ_CRC = 3 };  /* a member's status */
+typedef struct pfq_gz_members {
+    uint64_t n_members, consumed, text_bytes; /* whole members taken: gz[0, consumed), the sum of their ISIZE */
+    uint32_t stop;                            /* PFQ_GZ_* */
+    const uint64_t *begin;                    /* [n_members + 1] byte offset of every member, then consumed */
+    const uint64_t *text_begin;               /* [n_members + 1] prefix sums of ISIZE */
+} pfq_gz_members;
+typedef struct pfq_text_inflated {
+    pfq_gz_members members; /* what pfq_gz_scan gives for the same arguments (tree-owned here) */
+    uint64_t n_good;        /* leading members with status 0 */
+    uint64_t good_text;     /* members.text_begin[n_good]: the text pfq_text_parse_inflated will see */
+    const uint8_t *status;  /* [members.n_members], tree-owned */
+} pfq_text_inflated;
+int pfq_gz_scan(const uint8_t *gz, uint64_t len, uint64_t max_text, uint32_t flags, pfq_gz_members *out);
+int pfq_text_inflate(pfq_tree *tree, const uint8_t *gz, uint64_t len, uint64_t max_text, uint32_t flags, pfq_text_inflated *out);
+int pfq_text_parse_inflated(pfq_tree *tree, const uint8_t *carry, uint64_t carry_len, uint64_t limit, int format, uint32_t flags, pfq_text *out);
+int pfq_text_read(pfq_tree *tree, uint64_t from, uint64_t n, uint8_t *dst);
+int pfq_debug_last_inflate(pfq_tree *tree, double *ms);
+
 /* ---- text output (pfq_text_format) ----
  * The POS / NEG records of a device-parsed block formatted on the device, at the seam of the reference's writer
  * (main.rs:345-361,394-404): the bytes `query --pos-filter / --neg-filter` writes, made from the text, the gathered sequences

@@ -21,6 +21,7 @@ SYMBOLS = [
     "pfq_tree_set_sweep", "pfq_sweep_get", "pfq_sweep_reset", "pfq_sweep_absorb",
     "pfq_query_frames", "pfq_query_frames_device",
     "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr", "pfq_text_format", "pfq_debug_last_format",
+    "pfq_gz_scan", "pfq_text_inflate", "pfq_text_parse_inflated", "pfq_text_read", "pfq_debug_last_inflate",
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_set_adapters", "pfq_prep_last_adapters", "pfq_debug_last_adapters",
     "pfq_tree_set_mate_overlap", "pfq_prep_last_overlap", "pfq_debug_last_overlap",
@@ -120,6 +121,15 @@ class Text(C.Structure):
                 ("rec_begin", C.POINTER(C.c_uint64))]
 
 
+class GzMembers(C.Structure):
+    _fields_ = [("n_members", C.c_uint64), ("consumed", C.c_uint64), ("text_bytes", C.c_uint64), ("stop", C.c_uint32),
+                ("begin", C.POINTER(C.c_uint64)), ("text_begin", C.POINTER(C.c_uint64))]
+
+
+class TextInflated(C.Structure):
+    _fields_ = [("members", GzMembers), ("n_good", C.c_uint64), ("good_text", C.c_uint64), ("status", C.POINTER(C.c_uint8))]
+
+
 class TextLeft(C.Structure):
     _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("pos_at", C.c_uint64), ("neg_at", C.c_uint64),
                 ("why", C.c_uint32), ("pad_", C.c_uint32)]
@@ -207,6 +217,9 @@ NO_CLADE = 0xFFFFFFFF
 TEXT_FASTA, TEXT_FASTQ = 0, 1
 TEXT_FINAL, TEXT_WANT_RECORDS = 1, 2
 TEXT_END, TEXT_LIMIT, TEXT_MORE, TEXT_SLOW = 0, 1, 2, 3
+GZ_MEMBER_TEXT_MAX = 65536
+GZ_END, GZ_LIMIT, GZ_MORE, GZ_FOREIGN = 0, 1, 2, 3
+GZ_OK, GZ_MALFORMED, GZ_LENGTH, GZ_CRC = 0, 1, 2, 3
 FMT_POS, FMT_NEG, FMT_BLOCK_MAX = 1, 2, 8192
 LEFT_HEAD, LEFT_TAIL, LEFT_REPEATED_ID = 1, 2, 3
 PREP_PAIRED, PREP_WANT_READS = 1, 2
@@ -284,6 +297,11 @@ def lib() -> C.CDLL:
     L.pfq_debug_text_csr.argtypes = [vp, vp, vp]
     L.pfq_text_format.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(TextRecords)]
     L.pfq_debug_last_format.argtypes = [vp, C.POINTER(C.c_double)]
+    L.pfq_gz_scan.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(GzMembers)]
+    L.pfq_text_inflate.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(TextInflated)]
+    L.pfq_text_parse_inflated.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(Text)]
+    L.pfq_text_read.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    L.pfq_debug_last_inflate.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_prep_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(PrepParams), C.POINTER(Prep)]
     L.pfq_prep_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_prep_csr.argtypes = [vp, vp, vp]

@@ -67,7 +67,17 @@ void fan_out(size_t n, const F &fn) {
     for (auto &t : th) t.join();
 }
 
+// die() off the main thread, and die_in_flight() anywhere, end the process WITHOUT exit(): exit() would run the atexit handlers
+// and static destructors (the HIP runtime's among them) while the other threads are still inside HIP calls, which has ended
+// such a run with a segmentation fault instead of the message's status.  Same message, same status.
+const std::thread::id g_main_thread = std::this_thread::get_id();
+[[noreturn]] void die_in_flight(const std::string &msg) {
+    fprintf(stderr, "phage_filter: %s\n", msg.c_str());
+    fflush(stderr);
+    _exit(101);
+}
 [[noreturn]] void die(const std::string &msg) {  // the reference panics: message on stderr, exit code 101
+    if (std::this_thread::get_id() != g_main_thread) die_in_flight(msg);
     fprintf(stderr, "phage_filter: %s\n", msg.c_str());
     exit(101);
 }
@@ -160,6 +170,18 @@ struct GzLines {
         if (!f) die("Failed to open '" + path + "': " + strerror(errno));
         gzbuffer(f, 1 << 20);
     }
+    // The stream that begins at byte `offset` of the file (the begin of a gzip member), without its first `discard` bytes of text.
+    GzLines(const std::string &path, uint64_t offset, uint64_t discard) : buf(4 << 20) {
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0 || lseek(fd, (off_t)offset, SEEK_SET) < 0 || !(f = gzdopen(fd, "rb"))) die("Failed to open '" + path + "': " + strerror(errno));
+        gzbuffer(f, 1 << 20);
+        while (discard) {
+            const int got = gzread(f, buf.data(), (unsigned)std::min<uint64_t>(discard, buf.size()));
+            if (got < 0) die_in_flight("read error (corrupt gzip?)");
+            if (got == 0) break;
+            discard -= (uint64_t)got;
+        }
+    }
     GzLines(const GzLines &) = delete;
     ~GzLines() {
         if (f) gzclose(f);
@@ -174,7 +196,7 @@ struct GzLines {
                     return false;
                 }
                 int got = gzread(f, buf.data(), (unsigned)buf.size());
-                if (got < 0) die("read error (corrupt gzip?)");
+                if (got < 0) die_in_flight("read error (corrupt gzip?)");
                 if (got == 0) { eof = true; continue; }
                 pos = 0;
                 len = (size_t)got;
@@ -462,7 +484,9 @@ struct RecordParser {
 //     well-formed records) and then PROVEN by the consumer: chunk i+1 is accepted only if it starts exactly where
 //     chunk i ended, which by induction from offset 0 makes every accepted start a true one.  A chunk that fails the
 //     check is re-parsed from the proven position, so the result never depends on the guess;
-//   * a gzip file is inflated and parsed by one worker as a stream of segments; several files run concurrently.
+//   * a gzip file is inflated and parsed by one worker as a stream of segments; several files run concurrently;
+//   * --device-inflate: a blocked gzip file is cut into chunks of whole members by a walk over the members' headers
+//     (bgzf_tasks); the workers only read them, the device inflates and parses (Query::counts_only_text).
 // Segments are consumed strictly in input order, so blocks, ids and outputs are those of a sequential reader.
 // ---------------------------------------------------------------------------------------------------------------
 // A page-locked buffer (pfq_host_alloc) that only grows; --device-parse reads file bytes into it for pfq_text_parse.
@@ -498,6 +522,8 @@ struct Segment {
     PinnedBuf text;
     uint64_t text_lo = 0, text_hi = 0;
     bool is_text = false;
+    // --device-inflate: a chunk of whole blocked-gzip members as bytes [text_lo, text_hi) of the file, not inflated
+    bool is_gz = false;
 };
 struct MappedFile {  // (plain files are read with pread into reused buffers: first-touch page faults of a mapping
     uint64_t size = 0;   //  cost more than the copy, and serialise the workers)
@@ -513,6 +539,9 @@ struct Task {
     int file = 0;
     uint64_t lo = 0, hi = 0;  // nominal byte range of a plain chunk
     bool stream = false;      // gzip file: one streaming task
+    bool bgzf = false;        // --device-inflate: whole members [lo, hi) of a blocked gzip file
+    bool bgzf_tail = false;   // ... the header walk ended at lo short of the file's end: what follows is for the host reader
+    bool last_of_file = false;
     std::deque<Segment *> out;
     bool taken = false;
 };
@@ -529,6 +558,8 @@ struct ReadQueue {
     size_t lookahead = 8;
     bool device_parse = false;        // --device-parse: the workers only read the plain chunks (read_raw), the consumer parses
     std::unique_ptr<std::atomic<bool>[]> file_slow;  // ... until a file turned out not to be ordinary: its later chunks are parsed here
+    bool device_inflate = false;      // --device-inflate: blocked gzip files are cut into chunks of whole members, which the workers only read
+    std::vector<uint64_t> bgzf_members;  // per file: the members the header walk found (0: not read as chunks)
 
     std::mutex mu;
     std::condition_variable cv_work, cv_out;
@@ -585,6 +616,8 @@ struct ReadQueue {
             m.gz = pread(m.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
             if (!m.gz) posix_fadvise(m.fd, 0, 0, POSIX_FADV_SEQUENTIAL);
             maps.push_back(m);
+            bgzf_members.push_back(0);
+            if (m.gz && device_inflate && bgzf_tasks(i, m)) continue;
             if (m.gz) {
                 Task t;
                 t.file = (int)i;
@@ -605,6 +638,81 @@ struct ReadQueue {
         started = true;
         for (unsigned i = 0; i < n_threads; ++i) workers.emplace_back([this] { work(); });
     }
+
+    // --device-inflate: the size of the blocked-gzip member whose header begins at byte p, from its 'BC' extra subfield, or 0 if
+    // the bytes there are no such header or the member would pass the file's end.  Only the header is read.
+    static uint64_t bgzf_member_size(const MappedFile &m, uint64_t p, std::vector<unsigned char> &extra) {
+        unsigned char h[12];
+        if (p + 12 > m.size || pread(m.fd, h, 12, (off_t)p) != 12) return 0;
+        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4) || (h[3] & 0xe0)) return 0;
+        const size_t xlen = (size_t)h[10] | (size_t)h[11] << 8;
+        extra.resize(xlen + 1);
+        if (p + 12 + xlen > m.size || pread(m.fd, extra.data(), xlen, (off_t)(p + 12)) != (ssize_t)xlen) return 0;
+        for (size_t at = 0; at + 4 <= xlen;) {
+            const size_t slen = (size_t)extra[at + 2] | (size_t)extra[at + 3] << 8;
+            if (at + 4 + slen > xlen) return 0;
+            if (extra[at] == 'B' && extra[at + 1] == 'C' && slen == 2) {
+                const uint64_t size = ((uint64_t)extra[at + 4] | (uint64_t)extra[at + 5] << 8) + 1;
+                return (size >= 12 + xlen + 9 && p + size <= m.size) ? size : 0;
+            }
+            at += 4 + slen;
+        }
+        return 0;
+    }
+    // The chunk tasks of a blocked gzip file: whole members, at least chunk_bytes of compressed bytes each, cut by a walk over
+    // the headers; false if the file's first member is not one pfq_gz_scan takes (the file then keeps its streaming task).
+    bool bgzf_tasks(size_t file, const MappedFile &m) {
+        std::vector<unsigned char> head((size_t)std::min<uint64_t>(m.size, 65536));
+        if (pread(m.fd, head.data(), head.size(), 0) != (ssize_t)head.size()) return false;
+        pfq_gz_members first{};
+        if (pfq_gz_scan(head.data(), head.size(), 0, head.size() == m.size ? PFQ_TEXT_FINAL : 0u, &first) != PFQ_OK || !first.n_members) return false;
+        const uint64_t cut = std::min<uint64_t>(chunk_bytes, 1ull << 28);  // (a chunk's text must stay below 2^31 bytes)
+        std::vector<unsigned char> extra;
+        uint64_t lo = 0, p = 0, n = 0;
+        while (p < m.size) {
+            const uint64_t size = bgzf_member_size(m, p, extra);
+            if (!size) break;
+            p += size;
+            ++n;
+            if (p - lo >= cut || p == m.size) {
+                Task t;
+                t.file = (int)file;
+                t.lo = lo;
+                t.hi = p;
+                t.bgzf = true;
+                t.last_of_file = p == m.size;
+                tasks.push_back(std::move(t));
+                lo = p;
+            }
+        }
+        if (p < m.size) {  // the walk ended early: the members up to here, then a task that only hands the rest to the host reader
+            Task t;
+            t.file = (int)file;
+            t.bgzf = true;
+            if (p > lo) {
+                t.lo = lo;
+                t.hi = p;
+                tasks.push_back(t);
+            }
+            t.lo = t.hi = p;
+            t.bgzf_tail = t.last_of_file = true;
+            tasks.push_back(std::move(t));
+        }
+        bgzf_members[file] = n;
+        posix_fadvise(m.fd, 0, 0, POSIX_FADV_SEQUENTIAL);
+        return true;
+    }
+    // A chunk of whole members as it is in the file, in page-locked memory; nothing is inflated.
+    void read_gz(const MappedFile &m, uint64_t lo, uint64_t hi, Segment &s) {
+        s.b.clear();
+        s.err.clear();
+        s.text_lo = s.text_hi = lo;
+        s.is_gz = true;
+        if (hi == lo || file_slow_of(m)) return;
+        read_range(m, s.text.ensure((size_t)(hi - lo)), lo, hi);
+        s.text_hi = hi;
+    }
+    bool file_slow_of(const MappedFile &m) const { return file_slow[&m - maps.data()]; }
 
     // ---- chunk parsing ----------------------------------------------------------------------------------------
     // First record start at or after `from` (a line start) inside the view, or v.hi when there is none.
@@ -717,6 +825,7 @@ struct ReadQueue {
         s->err.clear();
         s->last = true;
         s->is_text = false;
+        s->is_gz = false;
         return s;
     }
     // segments the pool takes back (filtering: batches in flight hold their segments)
@@ -760,7 +869,8 @@ struct ReadQueue {
             const Fmt fmt = fmts[t.file];
             if (!t.stream) {
                 Segment *s = fresh_segment();
-                if (device_parse && m.size && !file_slow[t.file]) read_raw(m, fmt, t.lo, t.hi, *s);
+                if (t.bgzf) read_gz(m, t.lo, t.hi, *s);
+                else if (device_parse && m.size && !file_slow[t.file]) read_raw(m, fmt, t.lo, t.hi, *s);
                 else parse_chunk(m, fmt, t.lo, t.hi, false, 0, *s);
                 push(t, s);
                 continue;
@@ -2114,7 +2224,86 @@ struct QueryLoop {
     // parses the rest of the chunk from exactly there, malformed input included; after a SLOW the file's later chunks go to
     // the reader at once.  gzip streams arrive parsed, as ever.  Counting commutes, so only the proofs are ordered.
     std::atomic<uint64_t> n_device_records{0}, n_host_records{0}, ns_text_parse{0}, n_text_bytes{0};
+    // --device-inflate: blocked gzip files arrive as chunks of whole members (ReadQueue::bgzf_tasks).  A replica's thread has its
+    // tree inflate the chunk it took (pfq_text_inflate: outside the turn, this is the parallel part); inside its turn the text is
+    // parsed behind the carry the file's previous chunk left (pfq_text_parse_inflated), the bytes behind the last record taken
+    // become the next carry (pfq_text_read), and the records are classified after the turn, as those of a plain chunk are.  Where
+    // the device declines — bytes that are no member, a member it rejects, text that is not ordinary (SLOW), a carry above the
+    // cap, a file that ends inside a record — the file's streaming reader takes over for the rest of the file, inside the turn:
+    // it opens the file at the begin of a chunk whose first member the scan took (never at foreign bytes, which zlib would copy
+    // through at the start of a stream but ignores behind a member) and discards the text up to the first record not taken.
+    struct GzFile {
+        std::vector<uint8_t> carry;  // the text behind the last record taken
+        uint64_t text_done = 0;      // where in the file's text the carry begins: the first record not taken
+        std::vector<std::pair<uint64_t, uint64_t>> chunks;  // (file offset, text offset) of the chunks whose first member the scan took
+        uint64_t members_used = 0;
+    };
+    static constexpr uint64_t GZ_CARRY_MAX = 1ull << 20;
+    std::vector<GzFile> gz_files;
+    std::atomic<uint64_t> n_gz_members{0}, n_gz_host{0}, ns_inflate{0}, n_gz_bytes{0}, n_gz_text{0};
+    void gz_takeover(size_t d, const Task &task, GzFile &g, uint64_t at, Fmt fmt, std::atomic<bool> &aborted) {
+        rq.file_slow[task.file] = true;
+        n_gz_host += rq.bgzf_members[task.file] - g.members_used;
+        size_t j = g.chunks.size();
+        while (j && g.chunks[j - 1].second > at) --j;
+        if (!j) die("'" + rq.files[task.file] + "' changed while it was being read");
+        GzLines gl(rq.files[task.file], g.chunks[j - 1].first, at - g.chunks[j - 1].second);
+        RecordParser<GzLines> rp(gl, fmt);
+        Hits unused;
+        Segment seg;
+        for (int rc = 1; rc == 1;) {
+            seg.b.clear();
+            while (seg.b.n() < rq.seg_reads && (rc = rp.next(seg.b, false)) == 1) {}
+            if (seg.b.n()) {
+                seg.b.seq.resize(seg.b.seq.size() + 16);
+                n_host_records += seg.b.n();
+                count_segment(d, seg, unused);
+            }
+            if (rc < 0) {
+                rq.pending_error = rp.err;  // (fatal later, after the reads before it)
+                aborted = true;
+            }
+        }
+    }
+    // The turn of a chunk of members; returns the records the device parsed, which the caller classifies after the turn.
+    uint64_t gz_turn(size_t d, pfq_tree *tree, const Task &task, const pfq_text_inflated *inf, Fmt fmt, std::atomic<bool> &aborted) {
+        GzFile &g = gz_files[task.file];
+        const uint64_t text0 = g.text_done + g.carry.size();  // where in the file's text this chunk's first member begins
+        if (inf && inf->members.n_members) g.chunks.push_back({task.lo, text0});
+        bool decline = task.bgzf_tail || !inf || inf->members.stop != PFQ_GZ_END || inf->members.consumed != task.hi - task.lo ||
+                       inf->n_good < inf->members.n_members || ((g.carry.size() + inf->good_text) >> 31);
+        uint64_t n_dev = 0, takeover_at = g.text_done;
+        if (!decline) {
+            pfq_text res{};
+            const uint64_t t0 = ReadQueue::now_ns();
+            if (pfq_text_parse_inflated(tree, g.carry.data(), g.carry.size(), ~0ull, fmt == Fmt::Fastq ? PFQ_TEXT_FASTQ : PFQ_TEXT_FASTA,
+                                        task.last_of_file ? PFQ_TEXT_FINAL : 0u, &res) != PFQ_OK)
+                fail_from_thread(pfq_last_error());
+            ns_text_parse += ReadQueue::now_ns() - t0;
+            const uint64_t len = g.carry.size() + inf->good_text, rest = len - res.consumed;
+            n_text_bytes += len;
+            n_dev = res.n_records;
+            takeover_at = g.text_done + res.consumed;
+            if (res.stop == PFQ_TEXT_SLOW || rest > GZ_CARRY_MAX || (task.last_of_file && rest)) decline = true;
+            else {
+                g.carry.resize(rest);
+                if (rest && pfq_text_read(tree, res.consumed, rest, g.carry.data()) != PFQ_OK) fail_from_thread(pfq_last_error());
+                g.text_done = takeover_at;
+                g.members_used += inf->members.n_members;
+                n_gz_members += inf->members.n_members;
+            }
+        }
+        if (decline) gz_takeover(d, task, g, takeover_at, fmt, aborted);
+        return n_dev;
+    }
+    void report_device_inflate() const {
+        const double s = ns_inflate.load() * 1e-9;
+        fprintf(stderr, "device inflate: %llu members inflated on the device, %llu handed to the host reader; pfq_text_inflate took %llu compressed bytes (%llu bytes of text) in %.3f s (%.2f GB/s of text, copy and kernel, summed over devices)\n",
+                (unsigned long long)n_gz_members.load(), (unsigned long long)n_gz_host.load(), (unsigned long long)n_gz_bytes.load(),
+                (unsigned long long)n_gz_text.load(), s, s > 0 ? n_gz_text.load() / s * 1e-9 : 0.0);
+    }
     void counts_only_text() {
+        gz_files.resize(rq.files.size());
         std::mutex take_mu, turn_mu;
         std::condition_variable turn_cv;
         uint64_t taken = 0, commit_next = 0;
@@ -2152,6 +2341,17 @@ struct QueryLoop {
                     n_text_bytes += sg->text_hi - from;
                 };
                 if (sg->is_text && !rq.file_slow[task->file]) parse_from(sg->start_pos);
+                pfq_text_inflated inf{};
+                bool inflated = false;
+                if (sg->is_gz && sg->text_hi > sg->text_lo && !rq.file_slow[task->file] && !aborted) {
+                    const uint64_t t0 = ReadQueue::now_ns();
+                    if (pfq_text_inflate(tree, (const uint8_t *)sg->text.p, sg->text_hi - sg->text_lo, 0, task->last_of_file ? PFQ_TEXT_FINAL : 0u, &inf) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    ns_inflate += ReadQueue::now_ns() - t0;
+                    n_gz_bytes += inf.members.consumed;
+                    n_gz_text += inf.members.text_bytes;
+                    inflated = true;
+                }
                 {
                     std::unique_lock<std::mutex> lk(turn_mu);
                     turn_cv.wait(lk, [&] { return commit_next == ticket; });
@@ -2159,7 +2359,9 @@ struct QueryLoop {
                 // (the turn: one thread at a time, in the order the segments were taken)
                 const bool dropped = aborted;
                 uint64_t n_dev = 0;
-                if (!dropped && sg->is_text) {
+                if (!dropped && sg->is_gz) {
+                    if (!rq.file_slow[task->file]) n_dev = gz_turn(d, tree, *task, inflated ? &inf : nullptr, fmt, aborted);
+                } else if (!dropped && sg->is_text) {
                     const uint64_t expect = rq.expected_start(*task);
                     bool host_rest = rq.file_slow[task->file];
                     uint64_t rest_from = expect;
@@ -2680,7 +2882,7 @@ int cmd_query(int argc, char **argv) {
                              {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
                              {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
                              {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
-                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true},
+                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"device-inflate", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true},
                              {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
                              {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
                              {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
@@ -2829,7 +3031,10 @@ int cmd_query(int argc, char **argv) {
     }
     // --device-parse: plain FASTA / FASTQ files are parsed on the device (pfq_text_parse); only where the run counts per genome
     // (and per clade) on replicas — per-read outputs, pairs, frames and shards keep the host reader
-    const bool device_parse = a.flags.count("device-parse") != 0;
+    // --device-inflate: blocked gzip (BGZF) files are inflated on the device as well (pfq_text_inflate); it rides on --device-parse
+    const bool device_parse = a.flags.count("device-parse") != 0, device_inflate = a.flags.count("device-inflate") != 0;
+    if (device_inflate && !device_parse)
+        die("error: '--device-inflate' needs '--device-parse': the text it inflates on the device is parsed there");
     if (device_parse) {
         for (const char *other : {"pos-filter", "neg-filter", "scores", "lca-reads", "interleaved", "abundance", "coverage"})
             if (a.flags.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
@@ -3051,6 +3256,7 @@ int cmd_query(int argc, char **argv) {
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
     rq.device_parse = device_parse || device_output;
+    rq.device_inflate = device_inflate;
     // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences; preprocessing: the qualities go to the device)
     if (block != 0) rq.start(per_read || paired || framed || prep_run.on, threads);
     if (block != 0 && rq2) rq2->start(true, threads);
@@ -3097,6 +3303,7 @@ int cmd_query(int argc, char **argv) {
                 q.ns_out.load() * 1e-9);
         rq.report_timing();
         if (device_parse || device_output) q.report_device_parse();
+        if (device_inflate) q.report_device_inflate();
         if (device_output) q.report_device_output();
         struct rusage ru;
         if (getrusage(RUSAGE_SELF, &ru) == 0)
@@ -3589,6 +3796,71 @@ int cmd_taxonomy(int argc, char **argv) {
     return 0;
 }
 
+// bgzf: a plain or gzip file rewritten as blocked gzip (BGZF) with zlib: members of 65 280 text bytes, each with its compressed
+// size in a 'BC' extra subfield, then the 28-byte end marker.  What pfq_gz_scan takes and every htslib tool reads.
+int cmd_bgzf(int argc, char **argv) {
+    std::vector<Opt> opts = {{"in", 'i', true}, {"out", 'o', true}, {"level", 0, true}};
+    Args a = parse(argc, argv, 2, opts);
+    const std::string in = req(a, "in"), out = req(a, "out");
+    int level = 6;
+    if (a.val.count("level")) {
+        char *end = nullptr;
+        const long v = strtol(a.val["level"].c_str(), &end, 10);
+        if (!*a.val["level"].c_str() || *end || v < 0 || v > 9) die("error: '--level' must be 0 .. 9, not '" + a.val["level"] + "'");
+        level = (int)v;
+    }
+    constexpr size_t BLOCK = 65280;
+    gzFile f = gzopen(in.c_str(), "rb");  // (transparent for plain files)
+    if (!f) die("Failed to open '" + in + "': " + strerror(errno));
+    gzbuffer(f, 1 << 20);
+    FILE *o = fopen(out.c_str(), "wb");
+    if (!o) die("cannot create " + out + ": " + strerror(errno));
+    std::vector<unsigned char> text(BLOCK), member(18 + compressBound(BLOCK) + 64 + 8);
+    uint64_t n_members = 0, n_text = 0, n_out = 0;
+    auto put_member = [&](size_t n) {
+        z_stream z{};
+        // (the empty member at a level above 0 is the marker every reader knows, byte for byte)
+        if (deflateInit2(&z, n ? level : 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) die("zlib: deflateInit2 failed");
+        z.next_in = text.data();
+        z.avail_in = (uInt)n;
+        z.next_out = member.data() + 18;
+        z.avail_out = (uInt)(member.size() - 18 - 8);
+        if (deflate(&z, Z_FINISH) != Z_STREAM_END) die("zlib: deflate did not finish a member");
+        const size_t pay = z.total_out, size = 18 + pay + 8;
+        deflateEnd(&z);
+        if (size > 65536) die("bgzf: a member of more than 64 KiB");  // (cannot happen: 65 280 bytes stored are 65 290)
+        const unsigned char head[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (unsigned char)((size - 1) & 0xff), (unsigned char)((size - 1) >> 8)};
+        memcpy(member.data(), head, 18);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), text.data(), (uInt)n), isize = (uint32_t)n;
+        for (int i = 0; i < 4; ++i) {
+            member[18 + pay + i] = (unsigned char)(crc >> (8 * i));
+            member[18 + pay + 4 + i] = (unsigned char)(isize >> (8 * i));
+        }
+        if (fwrite(member.data(), 1, size, o) != size) die("short write to " + out);
+        ++n_members;
+        n_text += n;
+        n_out += size;
+    };
+    while (true) {
+        size_t have = 0;
+        while (have < BLOCK) {
+            const int got = gzread(f, text.data() + have, (unsigned)(BLOCK - have));
+            if (got < 0) die("read error (corrupt gzip?)");
+            if (got == 0) break;
+            have += (size_t)got;
+        }
+        if (!have) break;
+        put_member(have);
+        if (have < BLOCK) break;
+    }
+    put_member(0);  // the end marker
+    gzclose(f);
+    if (fclose(o) != 0) die("short write to " + out);
+    fprintf(stderr, "bgzf: %llu bytes of text in %llu members and the end marker, %llu bytes written\n", (unsigned long long)n_text,
+            (unsigned long long)(n_members - 1), (unsigned long long)n_out);
+    return 0;
+}
+
 void usage() {
     std::string header_cols(SIMILARITY_HEADER);  // the column line as the file has it, tabs spelt out
     header_cols.pop_back();
@@ -3605,6 +3877,7 @@ void usage() {
             "  compare         Says which genomes of a database are related, and how closely, from their Bloom filters\n"
             "  recluster       Writes a database with the same genomes under a tree rebuilt by their similarity\n"
             "  taxonomy        Checks a taxonomy file against a database and writes the node table it gives (no GPU)\n"
+            "  bgzf            Rewrites a plain or gzip file as blocked gzip: bgzf -i IN -o OUT [--level 0..9] (no GPU)\n"
             "  build-balanced  Builds a balanced synthetic BloomTree on the GPU (benchmark databases)\n"
             "  ingest-check    Parses reads like `query` and prints what was read (no GPU)\n\n"
             "query takes the reference's options, plus --devices <0,1,..|all>: one replica of the database per GPU, reads\n"
@@ -3667,6 +3940,12 @@ void usage() {
             "every error is what the run without the option gives.  For runs that only count: with -f, -b, -t, --search-depth, --devices,\n"
             "-F and --lca all.  Not with --pos-filter, --neg-filter, --scores, --lca best, --lca-reads, --reads2, --interleaved,\n"
             "--abundance, --coverage, --frame or --shard-depth\n"
+            "--device-inflate (needs --device-parse): blocked gzip files (BGZF: what bgzip, the sequencers' converters and\n"
+            "`phage_filter bgzf` write) are inflated on the GPU too: the host threads read chunks of whole members, found by walking the\n"
+            "members' headers, and every member is inflated by a wave of its own.  Where the file has anything else (bytes that are no\n"
+            "member, a member the device does not follow to the letter, records that are not ordinary, a file that ends inside a\n"
+            "record) the streaming host reader takes over from exactly the first record not taken, so every output and every error is\n"
+            "what the run without the option gives.  Other gzip files keep the host reader, as they do under --device-output\n"
             "--device-output (needs --pos-filter and / or --neg-filter): the POS / NEG records of plain (not gzip) FASTA / FASTQ files are\n"
             "parsed, classified and formatted on the GPU: the host threads only read file bytes and write the output streams.  The\n"
             "device writes the blocks of -b reads whose ids are all different; blocks with a repeated id, the reads at the edges of a\n"
@@ -3803,6 +4082,7 @@ int main(int argc, char **argv) {
     if (cmd == "compare") return cmd_compare((int)av.size(), av.data());
     if (cmd == "recluster") return cmd_recluster((int)av.size(), av.data());
     if (cmd == "taxonomy") return cmd_taxonomy((int)av.size(), av.data());
+    if (cmd == "bgzf") return cmd_bgzf((int)av.size(), av.data());
     usage();
     return 2;
 }

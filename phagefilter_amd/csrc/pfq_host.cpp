@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/pfq.h"
+#include "pfq_inflate_core.h"
 #include "pfq_kernels.h"
 #include "pfq_taxonomy.h"
 
@@ -118,6 +119,7 @@ struct Knobs {
     long long pair_ahead = -1;                  // reservations of 32 pair slots a batched emission of k_classify asks for beyond what its pass needs: 0 .. 16, unset: 8
     long long classify_blocks = -1;             // tests: a cap on the grid of the classify launches (a wave then screens several groups of a small input)
     long long fmt_grid = -1, fmt_hash_bits = -1, fmt_time = -1;  // pfq_text_format: a cap on every grid; bits of the id hash that are kept (1 .. 64); 1: time the stages with HIP events
+    long long inflate_blocks = -1;              // pfq_text_inflate: a cap on the grid of k_gz_inflate (1 .. 65535; unset: two workgroups a CU, what their LDS admits)
 };
 struct KnobName {
     const char *name;
@@ -155,6 +157,7 @@ const KnobName KNOBS[] = {
     {"PFQ_FMT_GRID", &Knobs::fmt_grid},         {"PFQ_FMT_HASH_BITS", &Knobs::fmt_hash_bits},
     {"PFQ_FMT_TIME", &Knobs::fmt_time},
     {"PFQ_PAIR_AHEAD", &Knobs::pair_ahead},     {"PFQ_CLASSIFY_BLOCKS", &Knobs::classify_blocks},
+    {"PFQ_INFLATE_BLOCKS", &Knobs::inflate_blocks},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -451,6 +454,20 @@ struct pfq_tree {
     uint64_t tx_records = 0, tx_bases = 0;
     std::vector<uint64_t> out_rec_begin;
     int tx_fastq = 0;
+    uint64_t tx_len = 0;  // bytes of the text parsed last (pfq_text_read)
+    // pfq_text_inflate: the compressed chunk, the members the host's header walk found, the texts back to back (what
+    // pfq_text_parse_inflated copies behind the carry), per member its status and CRC; the walk's tables and the statuses as
+    // the caller sees them.  gz_time: before the copy, behind it, behind the kernel.
+    DevBuf<uint8_t> d_gz, d_gz_text;
+    DevBuf<pfq::GzMember> d_gz_mem;
+    DevBuf<uint32_t> d_gz_res;
+    std::vector<uint64_t> gz_begin, gz_text_begin;
+    std::vector<pfq::GzMember> gz_mem;
+    std::vector<uint32_t> gz_res;
+    std::vector<uint8_t> gz_status;
+    bool gz_have = false, gz_timed = false;
+    uint64_t gz_good_text = 0;
+    hipEvent_t gz_time[3] = {nullptr, nullptr, nullptr};
     // pfq_text_format: what the kernels leave per record (ids, hashes, lengths and their scans), the small words that go back to
     // the host in one copy (d_fm_small: FMT_RES_N result words | the streams' offsets at the block boundaries | the block states),
     // the leaves' names (uploaded when they differ from fm_names), the two streams and their page-locked copies, which only
@@ -3496,6 +3513,7 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_tx_text.bytes() + t.d_tx_seq[0].bytes() + t.d_tx_seq[1].bytes() + t.d_tx_off[0].bytes() + t.d_tx_off[1].bytes() +  // (pfq_text_parse)
                         t.d_tx_rec_begin.bytes() + t.d_tx_blk.bytes() + t.d_tx_line.bytes() + t.d_tx_len.bytes() + t.d_tx_hdr.bytes() + t.d_tx_rec_line.bytes() +
                         t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes() +
+                        t.d_gz.bytes() + t.d_gz_text.bytes() + t.d_gz_mem.bytes() + t.d_gz_res.bytes() +  // (pfq_text_inflate)
                         t.d_pp_in.bytes() + t.d_pp_qual.bytes() + t.d_pp_hq.bytes() + t.d_pp_seq[0].bytes() + t.d_pp_seq[1].bytes() + t.d_pp_inoff.bytes() +  // (pfq_prep_reads)
                         t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
@@ -3555,6 +3573,8 @@ void pfq_tree_close(pfq_tree *tree) {
         if (e) (void)hipEventDestroy(e);
     if (tree->tx_parsed) (void)hipEventDestroy(tree->tx_parsed);
     if (tree->h_tx_res) (void)hipHostFree(tree->h_tx_res);
+    for (auto e : tree->gz_time)
+        if (e) (void)hipEventDestroy(e);
     for (auto e : tree->pp_free)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->pp_time)
@@ -3706,14 +3726,10 @@ static uint32_t text_tile(const Knobs &k) {
     return (v >= (long long)pfq::TEXT_TILE_MIN && v <= (long long)pfq::TEXT_TILE_DEFAULT && !(v & (v - 1))) ? (uint32_t)v : pfq::TEXT_TILE_DEFAULT;
 }
 
-int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t limit, int format, uint32_t flags, pfq_text *out) {
-    if (!tree || !out || (len && !text)) return fail(PFQ_ERR_ARG, "null argument");
-    if (format != PFQ_TEXT_FASTA && format != PFQ_TEXT_FASTQ) return fail(PFQ_ERR_ARG, "pfq_text_parse: format must be PFQ_TEXT_FASTA or PFQ_TEXT_FASTQ");
-    if (flags & ~(PFQ_TEXT_FINAL | PFQ_TEXT_WANT_RECORDS)) return fail(PFQ_ERR_ARG, "pfq_text_parse: unknown flag bits");
-    if (len >> 31) return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_parse: 2^31 bytes of text or more in one call: ask in pieces");
-    PFQ_TRY(use_device(tree->device));
-    pfq_tree &t = *tree;
-    const bool fastq = format == PFQ_TEXT_FASTQ, final = (flags & PFQ_TEXT_FINAL) != 0, want_rec = (flags & PFQ_TEXT_WANT_RECORDS) != 0;
+// What both parse calls do first: the copy stream and the events, the CSR set the coming parse fills (waiting for the
+// classification that read it), room for n bytes of text in d_tx_text.  From here there is no block to query until the parse
+// has succeeded.
+static int text_parse_begin(pfq_tree &t, uint32_t n, int *slot_out) {
     if (!t.copy_stream) {
         HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
         for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -3725,21 +3741,26 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
         HIP_TRY(t.d_tx_res.ensure(pfq::TEXT_RES_N));
         HIP_TRY(t.d_tx_bad.ensure(1));
     }
-    hipStream_t st = t.copy_stream;
     const int slot = t.tx_slot ^ 1;
     if (t.tx_used[slot]) HIP_TRY(hipEventSynchronize(t.tx_free[slot]));  // the classification that read this set is done
     t.tx_have = false;  // (until this parse has succeeded there is no block to query)
     t.fm_rows = false;
-    const uint32_t n = (uint32_t)len;
     HIP_TRY(t.d_tx_seq[slot].ensure((size_t)n + 16));
+    if (n) HIP_TRY(t.d_tx_text.ensure(((size_t)n + 15) / 16 * 16 + 16));
+    *slot_out = slot;
+    return PFQ_OK;
+}
+
+// The parse of d_tx_text[0, n), which the caller has queued on the copy stream; first and last: text[0] and text[n - 1].
+static int text_parse_staged(pfq_tree &t, int slot, uint32_t n, uint8_t first, uint8_t last, uint64_t limit, bool fastq, bool final, bool want_rec,
+                             pfq_text *out) {
+    hipStream_t st = t.copy_stream;
     out->n_records = out->consumed = out->n_bases = 0;
     out->stop = PFQ_TEXT_END;
     out->rec_begin = nullptr;
     uint32_t n_lines = 0;
     bool unterminated = false;
     if (n) {
-        HIP_TRY(t.d_tx_text.ensure(((size_t)n + 15) / 16 * 16 + 16));
-        HIP_TRY(hipMemcpyAsync(t.d_tx_text.p, text, n, hipMemcpyHostToDevice, st));
         const uint32_t tile = text_tile(t.knobs), n_tiles = (n + tile - 1) / tile;
         HIP_TRY(t.d_tx_blk.ensure(n_tiles));
         HIP_TRY(t.d_tx_blk_off.ensure((size_t)n_tiles + 1));
@@ -3748,13 +3769,13 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
         pfq::launch_scan_u32(t.d_tx_blk.p, n_tiles, t.d_tx_sums.p, t.d_tx_blk_off.p, st);
         HIP_TRY(hipMemcpyAsync(t.h_tx_res, t.d_tx_blk_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffer is free from here; the line count sizes what follows)
-        unterminated = final && text[n - 1] != '\n';
+        unterminated = final && last != '\n';
         n_lines = (uint32_t)t.h_tx_res[0] + (unterminated ? 1u : 0u);
     }
     // what needs no kernel: empty text; text without a considered line; FASTA that does not begin with a header
     bool trivial = true;
     if (!n) out->stop = PFQ_TEXT_END;
-    else if (!fastq && text[0] != '>') out->stop = PFQ_TEXT_SLOW;
+    else if (!fastq && first != '>') out->stop = PFQ_TEXT_SLOW;
     else if (!n_lines) out->stop = (fastq || limit) ? PFQ_TEXT_MORE : PFQ_TEXT_LIMIT;
     else trivial = false;
     const uint64_t max_records = fastq ? n_lines / 4 : n_lines;
@@ -3819,9 +3840,26 @@ int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t l
     t.tx_records = out->n_records;
     t.tx_bases = out->n_bases;
     t.tx_fastq = fastq ? 1 : 0;
+    t.tx_len = n;
     t.tx_have = true;
     return PFQ_OK;
 }
+
+int pfq_text_parse(pfq_tree *tree, const uint8_t *text, uint64_t len, uint64_t limit, int format, uint32_t flags, pfq_text *out) {
+    if (!tree || !out || (len && !text)) return fail(PFQ_ERR_ARG, "null argument");
+    if (format != PFQ_TEXT_FASTA && format != PFQ_TEXT_FASTQ) return fail(PFQ_ERR_ARG, "pfq_text_parse: format must be PFQ_TEXT_FASTA or PFQ_TEXT_FASTQ");
+    if (flags & ~(PFQ_TEXT_FINAL | PFQ_TEXT_WANT_RECORDS)) return fail(PFQ_ERR_ARG, "pfq_text_parse: unknown flag bits");
+    if (len >> 31) return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_parse: 2^31 bytes of text or more in one call: ask in pieces");
+    PFQ_TRY(use_device(tree->device));
+    pfq_tree &t = *tree;
+    const uint32_t n = (uint32_t)len;
+    int slot = 0;
+    PFQ_TRY(text_parse_begin(t, n, &slot));
+    if (n) HIP_TRY(hipMemcpyAsync(t.d_tx_text.p, text, n, hipMemcpyHostToDevice, t.copy_stream));
+    return text_parse_staged(t, slot, n, n ? text[0] : 0, n ? text[n - 1] : 0, limit, format == PFQ_TEXT_FASTQ, (flags & PFQ_TEXT_FINAL) != 0,
+                             (flags & PFQ_TEXT_WANT_RECORDS) != 0, out);
+}
+
 
 int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits) {
     if (!tree) return fail(PFQ_ERR_ARG, "null argument");
@@ -3848,6 +3886,174 @@ int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
     const pfq_tree &t = *tree;
     if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_slot].p, t.tx_bases, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_slot].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+// ---- blocked gzip ---------------------------------------------------------------------------------------------------------
+
+// The header walk of pfq_gz_scan: begin and text_begin [n + 1]; for pfq_text_inflate also what the kernel needs per member and
+// the trailers' CRCs.
+static int gz_walk(const char *who, const uint8_t *gz, uint64_t len, uint64_t max_text, uint32_t flags, std::vector<uint64_t> &begin,
+                   std::vector<uint64_t> &text_begin, std::vector<pfq::GzMember> *mem, std::vector<uint32_t> *crc, pfq_gz_members *out) {
+    if (!out || (len && !gz)) return fail(PFQ_ERR_ARG, "null argument");
+    if (flags & ~PFQ_TEXT_FINAL) return fail(PFQ_ERR_ARG, std::string(who) + ": unknown flag bits");
+    if (max_text && max_text < PFQ_GZ_MEMBER_TEXT_MAX)
+        return fail(PFQ_ERR_ARG, std::string(who) + ": max_text must be 0 or at least " + std::to_string(PFQ_GZ_MEMBER_TEXT_MAX) + ", not " + std::to_string(max_text));
+    begin.assign(1, 0);
+    text_begin.assign(1, 0);
+    if (mem) mem->clear();
+    if (crc) crc->clear();
+    uint64_t p = 0, text = 0;
+    uint32_t stop = PFQ_GZ_END;
+    while (p < len) {
+        pfq_inflate::Member m{};
+        const pfq_inflate::Walk w = pfq_inflate::walk_member(gz + p, len - p, &m);
+        if (w == pfq_inflate::WALK_SHORT) {
+            stop = (flags & PFQ_TEXT_FINAL) ? PFQ_GZ_FOREIGN : PFQ_GZ_MORE;
+            break;
+        }
+        if (w == pfq_inflate::WALK_FOREIGN) {
+            stop = PFQ_GZ_FOREIGN;
+            break;
+        }
+        if ((max_text && text + m.isize > max_text) || text + m.isize > 0x7fffffffull) {
+            stop = PFQ_GZ_LIMIT;
+            break;
+        }
+        if (mem) mem->push_back(pfq::GzMember{p + m.header, text, m.size - 8 - m.header, m.isize});
+        if (crc) crc->push_back(m.crc);
+        p += m.size;
+        text += m.isize;
+        begin.push_back(p);
+        text_begin.push_back(text);
+    }
+    out->n_members = begin.size() - 1;
+    out->consumed = p;
+    out->text_bytes = text;
+    out->stop = stop;
+    out->begin = begin.data();
+    out->text_begin = text_begin.data();
+    return PFQ_OK;
+}
+
+thread_local std::vector<uint64_t> g_gz_begin, g_gz_text_begin;
+
+int pfq_gz_scan(const uint8_t *gz, uint64_t len, uint64_t max_text, uint32_t flags, pfq_gz_members *out) {
+    return gz_walk("pfq_gz_scan", gz, len, max_text, flags, g_gz_begin, g_gz_text_begin, nullptr, nullptr, out);
+}
+
+int pfq_text_inflate(pfq_tree *tree, const uint8_t *gz, uint64_t len, uint64_t max_text, uint32_t flags, pfq_text_inflated *out) {
+    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+    pfq_tree &t = *tree;
+    t.gz_have = false;
+    std::vector<uint32_t> trailer_crc;
+    PFQ_TRY(gz_walk("pfq_text_inflate", gz, len, max_text, flags, t.gz_begin, t.gz_text_begin, &t.gz_mem, &trailer_crc, &out->members));
+    PFQ_TRY(use_device(t.device));
+    if (!t.copy_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
+        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    for (auto &e : t.gz_time)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    hipStream_t st = t.copy_stream;
+    const uint64_t n = out->members.n_members, consumed = out->members.consumed;
+    t.gz_res.assign(2 * n, 0);
+    t.gz_timed = false;
+    if (n) {
+        // (the kernel stages whole pieces of GZ_STAGE bytes: the allocation reaches beyond the last one it can touch)
+        HIP_TRY(t.d_gz.ensure((consumed + pfq::GZ_STAGE - 1) / pfq::GZ_STAGE * pfq::GZ_STAGE + pfq::GZ_STAGE));
+        HIP_TRY(t.d_gz_text.ensure(out->members.text_bytes + 16));
+        HIP_TRY(t.d_gz_mem.ensure(n));
+        HIP_TRY(t.d_gz_res.ensure(2 * n));
+        long long blocks = t.knobs.inflate_blocks;
+        if (blocks < 1 || blocks > 65535) {
+            int cus = 0;
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t.device));
+            blocks = 2 * std::max(cus, 1);
+        }
+        HIP_TRY(hipEventRecord(t.gz_time[0], st));
+        HIP_TRY(hipMemcpyAsync(t.d_gz.p, gz, consumed, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_gz_mem.p, t.gz_mem.data(), n * sizeof(pfq::GzMember), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(t.gz_time[1], st));
+        pfq::launch_gz_inflate(t.d_gz.p, t.d_gz_mem.p, n, t.d_gz_text.p, t.d_gz_res.p, (uint32_t)blocks, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t.gz_time[2], st));
+        HIP_TRY(hipMemcpyAsync(t.gz_res.data(), t.d_gz_res.p, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t.gz_timed = true;
+    }
+    t.gz_status.resize(n);
+    uint64_t good = n;
+    for (uint64_t m = 0; m < n; m++) {
+        uint32_t s = t.gz_res[2 * m];
+        if (s > PFQ_GZ_LENGTH) s = PFQ_GZ_MALFORMED;  // (not a word the kernel writes)
+        if (s == PFQ_GZ_OK && t.gz_res[2 * m + 1] != trailer_crc[m]) s = PFQ_GZ_CRC;
+        t.gz_status[m] = (uint8_t)s;
+        if (s != PFQ_GZ_OK && m < good) good = m;
+    }
+    out->n_good = good;
+    out->good_text = t.gz_text_begin[good];
+    out->status = t.gz_status.data();
+    t.gz_good_text = out->good_text;
+    t.gz_have = true;
+    return PFQ_OK;
+}
+
+int pfq_text_parse_inflated(pfq_tree *tree, const uint8_t *carry, uint64_t carry_len, uint64_t limit, int format, uint32_t flags, pfq_text *out) {
+    if (!tree || !out || (carry_len && !carry)) return fail(PFQ_ERR_ARG, "null argument");
+    if (format != PFQ_TEXT_FASTA && format != PFQ_TEXT_FASTQ)
+        return fail(PFQ_ERR_ARG, "pfq_text_parse_inflated: format must be PFQ_TEXT_FASTA or PFQ_TEXT_FASTQ");
+    if (flags & ~(PFQ_TEXT_FINAL | PFQ_TEXT_WANT_RECORDS)) return fail(PFQ_ERR_ARG, "pfq_text_parse_inflated: unknown flag bits");
+    if (!tree->gz_have) return fail(PFQ_ERR_STATE, "pfq_text_parse_inflated before a pfq_text_inflate on this tree");
+    pfq_tree &t = *tree;
+    if ((carry_len >> 31) || ((carry_len + t.gz_good_text) >> 31))
+        return fail(PFQ_ERR_UNSUPPORTED, "pfq_text_parse_inflated: 2^31 bytes of text or more in one call (carry " + std::to_string(carry_len) +
+                                             " + inflated " + std::to_string(t.gz_good_text) + "): inflate smaller chunks");
+    PFQ_TRY(use_device(t.device));
+    const uint32_t n = (uint32_t)(carry_len + t.gz_good_text), n_carry = (uint32_t)carry_len;
+    int slot = 0;
+    PFQ_TRY(text_parse_begin(t, n, &slot));
+    hipStream_t st = t.copy_stream;
+    uint8_t ends[2] = {0, 0};  // the text's first and last byte
+    if (n) {
+        if (n_carry) HIP_TRY(hipMemcpyAsync(t.d_tx_text.p, carry, n_carry, hipMemcpyHostToDevice, st));
+        if (t.gz_good_text) HIP_TRY(hipMemcpyAsync(t.d_tx_text.p + n_carry, t.d_gz_text.p, t.gz_good_text, hipMemcpyDeviceToDevice, st));
+        if (n_carry) {
+            ends[0] = carry[0];
+        } else {
+            HIP_TRY(hipMemcpyAsync(&ends[0], t.d_gz_text.p, 1, hipMemcpyDeviceToHost, st));
+        }
+        if (t.gz_good_text) {
+            HIP_TRY(hipMemcpyAsync(&ends[1], t.d_gz_text.p + t.gz_good_text - 1, 1, hipMemcpyDeviceToHost, st));
+        } else {
+            ends[1] = carry[n_carry - 1];
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return text_parse_staged(t, slot, n, ends[0], ends[1], limit, format == PFQ_TEXT_FASTQ, (flags & PFQ_TEXT_FINAL) != 0,
+                             (flags & PFQ_TEXT_WANT_RECORDS) != 0, out);
+}
+
+int pfq_text_read(pfq_tree *tree, uint64_t from, uint64_t n, uint8_t *dst) {
+    if (!tree || (n && !dst)) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_text_read before a pfq_text_parse or pfq_text_parse_inflated on this tree");
+    if (from > tree->tx_len || n > tree->tx_len - from)
+        return fail(PFQ_ERR_ARG, "pfq_text_read: bytes [" + std::to_string(from) + ", " + std::to_string(from) + " + " + std::to_string(n) +
+                                     ") of a text of " + std::to_string(tree->tx_len) + " bytes");
+    PFQ_TRY(use_device(tree->device));
+    if (n) HIP_TRY(hipMemcpy(dst, tree->d_tx_text.p + from, n, hipMemcpyDeviceToHost));
+    return PFQ_OK;
+}
+
+int pfq_debug_last_inflate(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->gz_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_inflate before a pfq_text_inflate with members on this tree");
+    PFQ_TRY(use_device(tree->device));
+    for (int i = 0; i < 2; i++) {
+        float f = 0;
+        HIP_TRY(hipEventElapsedTime(&f, tree->gz_time[i], tree->gz_time[i + 1]));
+        ms[i] = f;
+    }
     return PFQ_OK;
 }
 
@@ -5916,6 +6122,10 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
     if (!strcmp(name, "PFQ_FMT_GRID") && value && *value) {  // a cap on the grids of pfq_text_format
         const long long v = strtoll(value, nullptr, 10);
         if (v < 1 || v > 65535) return fail(PFQ_ERR_ARG, std::string("PFQ_FMT_GRID must be 1 .. 65535, not ") + value);
+    }
+    if (!strcmp(name, "PFQ_INFLATE_BLOCKS") && value && *value) {  // a cap on the grid of k_gz_inflate
+        const long long v = strtoll(value, nullptr, 10);
+        if (v < 1 || v > 65535) return fail(PFQ_ERR_ARG, std::string("PFQ_INFLATE_BLOCKS must be 1 .. 65535, not ") + value);
     }
     if (!strcmp(name, "PFQ_FRAME_PIECE") && value && *value) {  // the windows of a piece are whole: a positive multiple of 64
         const long long v = strtoll(value, nullptr, 10);

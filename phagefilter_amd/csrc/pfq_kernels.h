@@ -837,5 +837,17 @@ void launch_debug_indices(const HashParams &hp, const uint8_t *d_seq, uint64_t l
 void launch_synth_genomes(uint8_t *d_out, uint64_t n_genomes, uint64_t genome_len, uint64_t seed_base, hipStream_t st);
 void launch_synth_reads(uint8_t *d_out, uint64_t first, uint64_t n_reads, uint64_t read_len, const uint8_t *d_genomes,
                         uint64_t genome_len, uint64_t n_genomes, uint64_t seed, hipStream_t st);
+// pfq_text_inflate (pfq_inflate.hip): the members of a blocked gzip chunk inflated, one wave a member, a grid-stride loop over
+// the members.  d_gz: the chunk, 16-byte aligned, allocated (not necessarily filled) up to a multiple of GZ_STAGE beyond its last
+// payload byte; members: what the host's header walk found (nothing in them comes from the device's reading of the bytes);
+// d_text: the texts back to back, text_begin + isize <= its size.  d_result [2 n_members]: per member its status
+// (pfq_inflate::Status, never ST_CRC: the host compares) and the CRC-32 of the text it produced (0 unless the status is 0).
+constexpr uint32_t GZ_STAGE = 2048;  // compressed bytes a wave stages into LDS at a time
+struct GzMember {
+    uint64_t pay_begin, text_begin;  // of the deflate payload in d_gz, of the text in d_text
+    uint32_t pay_len, isize;
+};
+void launch_gz_inflate(const uint8_t *d_gz, const GzMember *d_members, uint64_t n_members, uint8_t *d_text, uint32_t *d_result, uint32_t blocks,
+                       hipStream_t st);
 
 }  // namespace pfq

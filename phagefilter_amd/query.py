@@ -333,6 +333,49 @@ class BloomTree:
                 "stop": ("end", "limit", "more", "slow")[out.stop],
                 "rec_begin": np.ctypeslib.as_array(out.rec_begin, shape=(n + 1,)).copy() if want_records else None}
 
+    def inflate_text(self, data: bytes, max_text: int = 0, final: bool = True) -> dict:
+        """The members of blocked gzip (BGZF) bytes inflated on the device into the text parse_inflated() parses
+        (pfq_text_inflate).  Returns what gz_scan() returns for the same arguments and status: uint8[n_members] (0 ok, 1
+        malformed deflate, 2 length mismatch, 3 CRC mismatch), n_good: the leading members with status 0, good_text: their text
+        bytes.  No counter changes, the block parsed last stays."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = _ffi.TextInflated()
+        _ffi.check(_ffi.lib().pfq_text_inflate(self._h, buf.ctypes.data if buf.size else None, buf.size, max_text, _ffi.TEXT_FINAL if final else 0,
+                                               C.byref(out)))
+        res = _gz_members(out.members)
+        n = res["n_members"]
+        res.update(n_good=int(out.n_good), good_text=int(out.good_text),
+                   status=np.ctypeslib.as_array(out.status, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint8))
+        return res
+
+    def parse_inflated(self, fmt: str, carry: bytes = b"", limit: Optional[int] = None, final: bool = True, want_records: bool = False) -> dict:
+        """parse_text() of `carry` followed by the good text inflate_text() left on the device (pfq_text_parse_inflated): same
+        result, and query_text(), format_text(), text_csr() and read_text() see that text."""
+        if fmt not in ("fasta", "fastq"):
+            raise ValueError(f"fmt must be 'fasta' or 'fastq', not {fmt!r}")
+        buf = np.frombuffer(bytes(carry), dtype=np.uint8)
+        out = _ffi.Text()
+        flags = (_ffi.TEXT_FINAL if final else 0) | (_ffi.TEXT_WANT_RECORDS if want_records else 0)
+        _ffi.check(_ffi.lib().pfq_text_parse_inflated(self._h, buf.ctypes.data if buf.size else None, buf.size, (1 << 64) - 1 if limit is None else limit,
+                                                      _ffi.TEXT_FASTQ if fmt == "fastq" else _ffi.TEXT_FASTA, flags, C.byref(out)))
+        self._text_shape = (int(out.n_records), int(out.n_bases))
+        n = int(out.n_records)
+        return {"n_records": n, "consumed": int(out.consumed), "n_bases": int(out.n_bases),
+                "stop": ("end", "limit", "more", "slow")[out.stop],
+                "rec_begin": np.ctypeslib.as_array(out.rec_begin, shape=(n + 1,)).copy() if want_records else None}
+
+    def read_text(self, begin: int, n: int) -> bytes:
+        """Bytes [begin, begin + n) of the text parsed last by parse_text() or parse_inflated() (pfq_text_read)."""
+        dst = np.zeros(n, dtype=np.uint8)
+        _ffi.check(_ffi.lib().pfq_text_read(self._h, begin, n, dst.ctypes.data if n else None))
+        return dst.tobytes()
+
+    def last_inflate_ms(self) -> Tuple[float, float]:
+        """Device milliseconds of the last inflate_text() with members: (copies to the device, kernel) (pfq_debug_last_inflate)."""
+        ms = (C.c_double * 2)()
+        _ffi.check(_ffi.lib().pfq_debug_last_inflate(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     def text_csr(self) -> Tuple[np.ndarray, np.ndarray]:
         """The block parsed last, copied to the host: (seq uint8[n_bases], off uint64[n_records + 1]) (pfq_debug_text_csr)."""
         n, nb = getattr(self, "_text_shape", (0, 0))
@@ -970,6 +1013,26 @@ def db_leaf_ids(directory: str) -> List[str]:
     n = C.c_uint64()
     _ffi.check(_ffi.lib().pfq_db_leaf_ids(directory.encode(), C.byref(ids), C.byref(n)))
     return [ids[i].decode() for i in range(n.value)]
+
+
+GZ_STOPS = ("end", "limit", "more", "foreign")
+
+
+def _gz_members(m: "_ffi.GzMembers") -> dict:
+    n = int(m.n_members)
+    return {"n_members": n, "consumed": int(m.consumed), "text_bytes": int(m.text_bytes), "stop": GZ_STOPS[m.stop],
+            "begin": np.ctypeslib.as_array(m.begin, shape=(n + 1,)).copy(), "text_begin": np.ctypeslib.as_array(m.text_begin, shape=(n + 1,)).copy()}
+
+
+def gz_scan(data: bytes, max_text: int = 0, final: bool = True) -> dict:
+    """The members of blocked gzip (BGZF) bytes found by walking their headers (pfq_gz_scan; the rules are pfq.h "blocked gzip");
+    needs no device.  Members are taken from data[0] while they are BGZF members and their text stays within `max_text` (0: no
+    limit).  Returns n_members, consumed, text_bytes, stop ("end", "limit", "more": the next member is not all there, "foreign":
+    what follows is no BGZF member, or with `final` a truncated one), begin and text_begin: uint64[n_members + 1]."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = _ffi.GzMembers()
+    _ffi.check(_ffi.lib().pfq_gz_scan(buf.ctypes.data if buf.size else None, buf.size, max_text, _ffi.TEXT_FINAL if final else 0, C.byref(out)))
+    return _gz_members(out)
 
 
 def read_taxonomy(path: str, leaf_ids: Sequence[str]) -> Tuple[List[int], List[str], List[int]]:
