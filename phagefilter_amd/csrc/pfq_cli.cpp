@@ -1440,6 +1440,51 @@ struct ServedDb {
     }
 };
 
+// Everything the command line of `query` says, as parse_query_options() leaves it: plain data, read by everything below.
+struct QueryOptions {
+    std::string reads, reads2, out, db_path;
+    unsigned threads = 4;                     // rayon pool size in the reference; here: parser workers
+    uint64_t block = 100;                     // --block-size-reads
+    float threshold = 1.0f;
+    FmtOverride format = FmtOverride::Auto;
+    bool pos = false, neg = false;  // --pos-filter, --neg-filter
+    bool scores = false;            // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
+    int lca = 0;                    // --lca: 0 none, 1 all, 2 best: CLADE_COUNTS.tsv
+    bool lca_reads = false;         // --lca-reads: READ_LCA.tsv, one line per record with hits
+    bool abundance = false;         // --abundance [--abundance-iters N]: ABUNDANCE.tsv, an EM over the logged hit rows
+    bool coverage = false;          // --coverage [--coverage-precision P]: COVERAGE.tsv, the distinct k-mers every genome's reads matched
+    bool taxonomy = false;          // --taxonomy FILE: TAXON_COUNTS.tsv
+    uint64_t abundance_iters = 200;
+    std::string coverage_precision = "12", taxonomy_file;
+    bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv, one line per record with hits
+    bool best_hits = false;    // --best-hits: --taxonomy, --abundance and --coverage take every unit's best-scoring genomes
+    bool sweep = false;        // --sweep T1,T2,..: THRESHOLDS.tsv and THRESHOLD_GENOMES.tsv; the values as numbers and as typed
+    std::vector<float> sweep_thr;
+    std::vector<std::string> sweep_typed;
+    uint32_t frame = 0, frame_step = 0;  // --frame F [--frame-step S] (frame 0: whole sequences): SEGMENTS.tsv
+    bool device_parse = false, device_inflate = false, device_output = false;
+    bool has_reads2 = false, interleaved = false, pair_both = false;  // --reads2, --interleaved, --pair-mode both
+    std::vector<int> devices;                     // --devices or PFQ_DEVICES, else the one of PFQ_DEVICE
+    bool sharded = false, pruned = false;         // --shard-depth D, already lowered to the search depth; --search-depth, as typed: it is
+    uint64_t shard_depth = 0;                     // read after the database is open
+    std::string search_depth;
+    // read preprocessing: any trimming, adapter or mate option or --deplete turns it on
+    bool prep = false;
+    pfq_prep_params params{0, 4, 0, 0, 0xffffffffu, 0, 0};  // (min_length 0: not given, the database's k)
+    std::vector<std::string> adapters[2];                   // --adapter / --adapter2: upper case, presets replaced
+    uint32_t adapter_overlap = 5, adapter_errors = 10;
+    uint32_t mate_overlap = 0, mate_overlap_errors = 10;    // (0: off)
+    uint32_t mate_correct_high = 0, mate_correct_low = 0;  // (high 0: off)
+    std::vector<std::string> deplete_dirs;                  // --deplete DIR [..], in the order given
+    float deplete_threshold = 1.0f;                         // --deplete-threshold T (default: -f), and as typed
+    std::string deplete_threshold_typed;
+    bool adapters_on() const { return !adapters[0].empty(); }
+    bool paired() const { return interleaved || has_reads2; }
+    bool per_read() const {  // the per-read hit lists are needed
+        return pos || neg || scores || lca == 2 || lca_reads || abundance || coverage || taxonomy || sweep;
+    }
+};
+
 // A POS/NEG file and the bytes written to it so far (the formatters' parts are written at computed offsets)
 struct OutFile {
     int fd = -1;
@@ -1455,26 +1500,27 @@ struct Outputs {
     FILE *scores = nullptr;        // --scores: READ_SCORES.tsv
     FILE *lca = nullptr;           // --lca-reads: READ_LCA.tsv
     FILE *taxa = nullptr;          // --taxon-reads: READ_TAXA.tsv
-    Outputs(const std::string &dir, const char *ext, bool want_pos, bool want_neg, bool has_reads2, bool want_scores, bool want_lca_reads,
-            bool want_taxon_reads = false) {
+    Outputs(const QueryOptions &o, const char *ext) {
+        const std::string &dir = o.out;
+        const bool has_reads2 = o.has_reads2;
         auto create = [&](OutFile &f, const std::string &name, const char *suffix) {
             if ((f.fd = open((dir + "/" + name + suffix + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
                 die("cannot create " + name + " in " + dir);
         };
         const char *mate1 = has_reads2 ? "_1." : ".";
-        if (want_pos) create(pos, "POS_FILTERING", mate1);
-        if (want_neg) create(neg, "NEG_FILTERING", mate1);
-        if (has_reads2 && want_pos) create(pos2, "POS_FILTERING_2", ".");
-        if (has_reads2 && want_neg) create(neg2, "NEG_FILTERING_2", ".");
-        if (want_scores) {
+        if (o.pos) create(pos, "POS_FILTERING", mate1);
+        if (o.neg) create(neg, "NEG_FILTERING", mate1);
+        if (has_reads2 && o.pos) create(pos2, "POS_FILTERING_2", ".");
+        if (has_reads2 && o.neg) create(neg2, "NEG_FILTERING_2", ".");
+        if (o.scores) {
             if (!(scores = fopen((dir + "/READ_SCORES.tsv").c_str(), "wb"))) die("cannot create READ_SCORES.tsv in " + dir);
             fputs("#read_id\tkmers\tgenome\tmatched_kmers\n", scores);
         }
-        if (want_lca_reads) {
+        if (o.lca_reads) {
             if (!(lca = fopen((dir + "/READ_LCA.tsv").c_str(), "wb"))) die("cannot create READ_LCA.tsv in " + dir);
             fputs("#read_id\thits\tclade\tname\n", lca);
         }
-        if (want_taxon_reads) {
+        if (o.taxon_reads) {
             if (!(taxa = fopen((dir + "/READ_TAXA.tsv").c_str(), "wb"))) die("cannot create READ_TAXA.tsv in " + dir);
             fputs("#read_id\thits\tnode\tname\n", taxa);
         }
@@ -1497,36 +1543,19 @@ struct Hits {
     std::vector<uint32_t> taxa;      // --taxon-reads: the unit's node of the taxonomy (PFQ_NO_CLADE: no hit)
     std::vector<uint64_t> call_off;  // the call's read offsets, when its range does not start at the batch's first read
 };
-// Read preprocessing (--trim-quality, --trim-window, --trim-poly-x, --min-length, --max-n, --min-complexity): the parameters in
-// force and the totals of all calls and replicas (PREPROCESS.tsv).
+// Read preprocessing: the totals of all calls and replicas (PREPROCESS.tsv, INSERT_SIZES.tsv) and every replica's own copies of
+// the screens of --deplete on its device (screens_of: by the replica's tree; filled before the loop starts, only read afterwards)
 struct PrepRun {
-    bool on = false;
-    pfq_prep_params params{0, 4, 0, 0, 0xffffffffu, 0, 0};
+    static constexpr size_t DEPLETE_MAX = 4;
     std::atomic<uint64_t> reads{0}, kept{0}, trimmed{0}, bases{0}, bases_kept{0};
     std::atomic<uint64_t> reason[5] = {};
-    // --adapter / --adapter2: the sets every replica's tree carries (pfq_tree_set_adapters) and what the adapter step found
-    std::vector<std::string> adapters[2];
-    uint32_t adapter_overlap = 5, adapter_errors = 10;
     std::atomic<uint64_t> adapter_reads{0}, adapter_bases{0};
     std::atomic<uint64_t> adapter_found[2 * PFQ_ADAPTER_MAX] = {};
-    bool adapters_on() const { return !adapters[0].empty(); }
-    // --mate-overlap / --mate-overlap-errors: what every replica's tree is set to (pfq_tree_set_mate_overlap; 0: off), what the
-    // overlap step found and the fragments per insert length (INSERT_SIZES.tsv)
-    uint32_t mate_overlap = 0, mate_overlap_errors = 10;
     std::atomic<uint64_t> overlap_fragments{0}, overlap_skipped{0}, overlap_found{0}, overlap_readthrough{0}, overlap_reads{0}, overlap_bases{0};
     std::atomic<uint64_t> insert_hist[PFQ_OVERLAP_INSERT_MAX + 1] = {};
-    // --mate-correct / --mate-correct-quality: what every replica's tree is set to (pfq_tree_set_mate_correct; high 0: off) and
-    // what the correction did
-    uint32_t mate_correct_high = 0, mate_correct_low = 0;
     std::atomic<uint64_t> corrected_fragments{0}, corrected_bases{0}, correct_unresolved{0}, correct_no_quality{0};
-    // --deplete DIR [..] / --deplete-threshold T: the screens in the order given, every replica's own copies of them on its device
-    // (screens_of: by the replica's tree; filled before the loop starts, only read afterwards) and what every screen removed
-    static constexpr size_t DEPLETE_MAX = 4;
-    std::vector<std::string> deplete_dirs;
-    float deplete_threshold = 1.0f;
-    std::string deplete_threshold_typed;
-    std::map<pfq_tree *, std::vector<pfq_tree *>> screens_of;
     std::atomic<uint64_t> depleted_units[DEPLETE_MAX] = {}, depleted_reads[DEPLETE_MAX] = {}, depleted_bases[DEPLETE_MAX] = {};
+    std::map<pfq_tree *, std::vector<pfq_tree *>> screens_of;
 };
 // What a call kept of its reads [r0, r1): begin and len of every read, the kept reads' indices (relative to r0), ascending; with
 // --mate-correct the call's patch list (read relative to r0), ascending by (read, pos)
@@ -1534,14 +1563,14 @@ struct PrepKept {
     std::vector<uint32_t> begin, len, kept;
     std::vector<pfq_prep_patch> patches;
 };
-// Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch.  With PFQ_WANT_HITS the hit lists (and
-// scores; keep_lca: the units' LCAs of a PFQ_WANT_LCA call) are copied out of the library's buffers, which the next call on
+// Reads [r0, r1) of the padded batch b through `tree` in one pfq_query_batch at o.threshold.  With PFQ_WANT_HITS the hit lists (and
+// scores; --lca-reads, --taxon-reads: the units' LCAs and nodes) are copied out of the library's buffers, which the next call on
 // the tree reuses, into h.  With preprocessing on the reads go through pfq_prep_reads first — the qualities in a buffer aligned to
 // the bases; a read whose quality length differs from its sequence length, and every FASTA read, has none — and pfq_prep_query
-// classifies what it kept: the units are then the kept reads (fragments), which pk (if asked for) names.
-void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float threshold, uint32_t flags, Hits &h, bool keep_lca = false,
-              bool keep_taxa = false, PrepRun *prep = nullptr, PrepKept *pk = nullptr) {
-    const bool want = (flags & PFQ_WANT_HITS) != 0, prep_on = prep && prep->on;
+// classifies what it kept: the units are then the kept reads (fragments), which pk (if asked for) names.  The parameters of
+// preprocessing are the options', what it did is added to `prep`.
+void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, const QueryOptions &o, uint32_t flags, Hits &h, PrepRun &prep, PrepKept *pk = nullptr) {
+    const bool want = (flags & PFQ_WANT_HITS) != 0;
     uint64_t units = flags & PFQ_PAIRED ? (r1 - r0) / 2 : r1 - r0;
     if (pk) {
         pk->begin.clear();
@@ -1564,13 +1593,13 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         off = h.call_off.data();
     }
     pfq_hits hits{};
-    if (prep_on) {
+    if (o.prep) {
         static thread_local std::vector<uint8_t> qual, has;
         const uint64_t base = b.off[r0];
         qual.assign(b.off[r1] - base, 0);
         has.assign(r1 - r0, 0);
         bool any_qual = false;
-        if ((prep->params.trim_quality || prep->mate_correct_high) && !b.has_qual.empty())  // (the two steps that look at qualities)
+        if ((o.params.trim_quality || o.mate_correct_high) && !b.has_qual.empty())  // (the two steps that look at qualities)
             for (uint64_t r = r0; r < r1; ++r) {
                 if (!b.has_qual[r]) continue;
                 const std::string_view q = b.quality(r);
@@ -1579,42 +1608,42 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
                 has[r - r0] = 1;
                 any_qual = true;
             }
-        pfq_prep_params par = prep->params;
+        pfq_prep_params par = o.params;
         par.flags = (flags & PFQ_PAIRED ? PFQ_PREP_PAIRED : 0u) | (pk ? PFQ_PREP_WANT_READS : 0u);
         pfq_prep res{};
         if (pfq_prep_reads(tree, b.seq.data() + base, any_qual ? qual.data() : nullptr, off, any_qual ? has.data() : nullptr, r1 - r0, &par, &res) != PFQ_OK)
             fail_from_thread(pfq_last_error());
-        prep->reads += res.n_reads;
-        prep->kept += res.n_kept;
-        prep->trimmed += res.n_trimmed;
-        prep->bases += res.bases_in;
-        prep->bases_kept += res.bases_kept;
-        for (int c = 0; c < 5; ++c) prep->reason[c] += res.n_reason[c];
-        if (prep->adapters_on()) {
+        prep.reads += res.n_reads;
+        prep.kept += res.n_kept;
+        prep.trimmed += res.n_trimmed;
+        prep.bases += res.bases_in;
+        prep.bases_kept += res.bases_kept;
+        for (int c = 0; c < 5; ++c) prep.reason[c] += res.n_reason[c];
+        if (o.adapters_on()) {
             pfq_prep_adapters ad{};
             if (pfq_prep_last_adapters(tree, &ad) != PFQ_OK) fail_from_thread(pfq_last_error());
-            prep->adapter_reads += ad.n_found;
-            prep->adapter_bases += ad.bases_cut;
-            for (int c = 0; c < 2 * PFQ_ADAPTER_MAX; ++c) prep->adapter_found[c] += ad.found[c];
+            prep.adapter_reads += ad.n_found;
+            prep.adapter_bases += ad.bases_cut;
+            for (int c = 0; c < 2 * PFQ_ADAPTER_MAX; ++c) prep.adapter_found[c] += ad.found[c];
         }
-        if (prep->mate_overlap && (par.flags & PFQ_PREP_PAIRED)) {
+        if (o.mate_overlap && (par.flags & PFQ_PREP_PAIRED)) {
             pfq_prep_overlap ov{};
             if (pfq_prep_last_overlap(tree, &ov) != PFQ_OK) fail_from_thread(pfq_last_error());
-            prep->overlap_fragments += ov.n_analysed;
-            prep->overlap_skipped += ov.n_skipped;
-            prep->overlap_found += ov.n_overlapped;
-            prep->overlap_readthrough += ov.n_readthrough;
-            prep->overlap_reads += ov.reads_cut;
-            prep->overlap_bases += ov.bases_cut;
+            prep.overlap_fragments += ov.n_analysed;
+            prep.overlap_skipped += ov.n_skipped;
+            prep.overlap_found += ov.n_overlapped;
+            prep.overlap_readthrough += ov.n_readthrough;
+            prep.overlap_reads += ov.reads_cut;
+            prep.overlap_bases += ov.bases_cut;
             for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
-                if (ov.hist[i]) prep->insert_hist[i] += ov.hist[i];
-            if (prep->mate_correct_high) {
+                if (ov.hist[i]) prep.insert_hist[i] += ov.hist[i];
+            if (o.mate_correct_high) {
                 pfq_prep_corrections co{};
                 if (pfq_prep_last_corrections(tree, &co) != PFQ_OK) fail_from_thread(pfq_last_error());
-                prep->corrected_fragments += co.n_fragments_corrected;
-                prep->corrected_bases += co.n_bases[0] + co.n_bases[1];
-                prep->correct_unresolved += co.n_unresolved;
-                prep->correct_no_quality += co.n_no_quality;
+                prep.corrected_fragments += co.n_fragments_corrected;
+                prep.corrected_bases += co.n_bases[0] + co.n_bases[1];
+                prep.correct_unresolved += co.n_unresolved;
+                prep.correct_no_quality += co.n_no_quality;
                 if (pk) pk->patches.assign(co.patches, co.patches + co.n_patches);
             }
         }
@@ -1622,14 +1651,14 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         // mate hits.  What is mapped back is what the last screen left.
         uint64_t n_kept = res.n_kept;
         const uint32_t *kept = res.kept;
-        if (!prep->deplete_dirs.empty()) {
-            const std::vector<pfq_tree *> &screens = prep->screens_of.at(tree);
+        if (!o.deplete_dirs.empty()) {
+            const std::vector<pfq_tree *> &screens = prep.screens_of.at(tree);
             for (size_t i = 0; i < screens.size(); ++i) {
                 pfq_prep_depleted d{};
-                if (pfq_prep_deplete(tree, screens[i], prep->deplete_threshold, flags & PFQ_PAIRED ? PFQ_PAIRED : 0u, &d) != PFQ_OK) fail_from_thread(pfq_last_error());
-                prep->depleted_units[i] += d.units_removed;
-                prep->depleted_reads[i] += d.reads_removed;
-                prep->depleted_bases[i] += d.bases_removed;
+                if (pfq_prep_deplete(tree, screens[i], o.deplete_threshold, flags & PFQ_PAIRED ? PFQ_PAIRED : 0u, &d) != PFQ_OK) fail_from_thread(pfq_last_error());
+                prep.depleted_units[i] += d.units_removed;
+                prep.depleted_reads[i] += d.reads_removed;
+                prep.depleted_bases[i] += d.bases_removed;
                 n_kept = d.n_kept;
                 if (pk) kept = d.kept;
             }
@@ -1642,8 +1671,8 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         units = flags & PFQ_PAIRED ? n_kept / 2 : n_kept;
         if (want) h.off.assign(units + 1, 0);
         if (!n_kept) return;
-        if (pfq_prep_query(tree, threshold, flags, want ? &hits : nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
-    } else if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, threshold, flags, want ? &hits : nullptr) != PFQ_OK) {
+        if (pfq_prep_query(tree, o.threshold, flags, want ? &hits : nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
+    } else if (pfq_query_batch(tree, b.seq.data() + b.off[r0], off, r1 - r0, o.threshold, flags, want ? &hits : nullptr) != PFQ_OK) {
         fail_from_thread(pfq_last_error());
     }
     if (!want) return;
@@ -1655,13 +1684,13 @@ void classify(pfq_tree *tree, const Batch &b, uint64_t r0, uint64_t r1, float th
         if (pfq_last_hit_scores(tree, &sc, &n_sc) != PFQ_OK) fail_from_thread(pfq_last_error());
         h.scores.assign(sc, sc + n_sc);
     }
-    if (keep_lca) {
+    if (o.lca_reads) {
         const uint32_t *lca = nullptr;
         uint64_t n_lca = 0;
         if (pfq_last_lca(tree, &lca, &n_lca) != PFQ_OK) fail_from_thread(pfq_last_error());
         h.lca.assign(lca, lca + n_lca);
     }
-    if (keep_taxa) {
+    if (o.taxon_reads) {
         const uint32_t *node = nullptr;
         uint64_t n_node = 0;
         if (pfq_last_taxa(tree, &node, &n_node) != PFQ_OK) fail_from_thread(pfq_last_error());
@@ -1944,33 +1973,24 @@ struct QueryLoop {
     ServedDb &db;
     ReadQueue &rq;
     Outputs &out;
-    const float threshold;
-    const uint64_t block;
-    const bool pos, neg, scores;
-    const unsigned threads;
+    const QueryOptions &o;
+    PrepRun &prep;  // read preprocessing (o.prep): every call trims and filters its reads on the device first and adds to these totals
     const uint64_t kmer_size;
-    const int lca = 0;             // --lca: 0 none, 1 all, 2 best (the library is asked for hits and scores)
-    const bool lca_reads = false;  // --lca-reads: READ_LCA.tsv
-    const bool abundance = false;  // --abundance: every call asks for the hits and logs their rows
-    const bool coverage = false;   // --coverage: every call asks for the hits and sketches the listed genomes' matched k-mers
-    const bool taxonomy = false;   // --taxonomy: every call asks for the hits and counts its units on the taxonomy's nodes
-    const bool taxon_reads = false;  // --taxon-reads: READ_TAXA.tsv
-    const bool best_hits = false;  // --best-hits: the three above take every unit's best-scoring genomes (the library is asked for hits and scores)
-    const bool sweep = false;      // --sweep: every call also counts its rows and scores against the threshold list (hits and scores, as --best-hits)
-    PrepRun *const prep = nullptr; // read preprocessing: every call trims and filters its reads on the device first
-    bool prep_on() const { return prep && prep->on; }
+    // what the post-stages ask of every call: --abundance logs the hit rows, --coverage sketches the listed genomes' matched k-mers,
+    // --taxonomy counts the units on the taxonomy's nodes, --best-hits gives the three every unit's best-scoring genomes, --sweep
+    // counts rows and scores against the threshold list (the last two: the library is asked for hits and scores)
     uint32_t abundance_flags() const {
-        return (abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
-               (taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u) |
-               (sweep ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP) : 0u);
+        return (o.abundance ? (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE) : 0u) | (o.coverage ? (PFQ_WANT_HITS | PFQ_WANT_COVERAGE) : 0u) |
+               (o.taxonomy ? (PFQ_WANT_HITS | PFQ_WANT_TAXA) : 0u) | (o.best_hits ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST) : 0u) |
+               (o.sweep ? (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP) : 0u);
     }
-    uint32_t lca_flags() const { return lca == 0 ? 0u : lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
+    uint32_t lca_flags() const { return o.lca == 0 ? 0u : o.lca == 1 ? PFQ_WANT_LCA : (PFQ_WANT_LCA | PFQ_LCA_BEST | PFQ_WANT_HITS | PFQ_WANT_SCORES); }
     std::atomic<uint64_t> ns_gpu{0}, ns_out{0}, n_total{0};
 
     size_t n_trees() const { return db.trees.size(); }
     uint64_t batch_size(uint64_t target) const {  // a whole number of reference blocks
         if (const char *e = getenv("PFQ_CLI_BATCH_READS")) target = std::max<uint64_t>(1, strtoull(e, nullptr, 10));  // (tests: several batches)
-        return std::max<uint64_t>(block, target) / block * block;
+        return std::max<uint64_t>(o.block, target) / o.block * o.block;
     }
 
     // Fragments, batch by batch: the parsers fill a batch of whole fragments (mates adjacent, -b counts fragments); every
@@ -1979,8 +1999,8 @@ struct QueryLoop {
     // calls want counts only.
     void paired(ReadQueue *rq2, bool both) {
         const uint64_t batch_frags = batch_size(1u << 19);
-        const bool per_read = pos || neg || scores || lca_reads || taxon_reads;
-        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags() |
+        const bool per_read = o.pos || o.neg || o.scores || o.lca_reads || o.taxon_reads;
+        const uint32_t flags = PFQ_PAIRED | (both ? PFQ_PAIR_BOTH : 0u) | (per_read ? PFQ_WANT_HITS : 0u) | (o.scores ? PFQ_WANT_SCORES : 0u) | lca_flags() |
                                abundance_flags();
         PairSource src{rq, rq2, {}, {}, 0, {}, false};
         Batch b;
@@ -1998,14 +2018,14 @@ struct QueryLoop {
             if (!nf) continue;
             b.seq.resize(b.seq.size() + 16);
             const uint64_t tq0 = ReadQueue::now_ns();
-            const bool map_back = per_read && prep_on();  // (the rows of the kept fragments are mapped back through kept, begin and len)
+            const bool map_back = per_read && o.prep;  // (the rows of the kept fragments are mapped back through kept, begin and len)
             std::vector<PrepKept> pks(map_back ? n_trees() : 0);
             std::vector<uint64_t> share(n_trees() + 1, 0);
             fan_out(n_trees(), [&](size_t i) {
                 const size_t P = n_trees();
                 const uint64_t f0 = db.sharded ? 0 : nf * i / P, f1 = db.sharded ? nf : nf * (i + 1) / P;
                 share[i] = 2 * f0;
-                classify(db.trees[i], b, 2 * f0, 2 * f1, threshold, flags, parts[i], lca_reads, taxon_reads, prep, map_back ? &pks[i] : nullptr);
+                classify(db.trees[i], b, 2 * f0, 2 * f1, o, flags, parts[i], prep, map_back ? &pks[i] : nullptr);
             });
             ns_gpu += ReadQueue::now_ns() - tq0;
             n_total += n;
@@ -2023,11 +2043,11 @@ struct QueryLoop {
             for (uint64_t fr = 0; fr < nf; ++fr) {
                 const uint32_t *l0 = f.leaves.data() + f.off[fr], *l1 = f.leaves.data() + f.off[fr + 1];
                 const bool mapped = l0 != l1;
-                if (mapped ? !pos : !neg) continue;
+                if (mapped ? !o.pos : !o.neg) continue;
                 for (uint64_t r = 2 * fr; r < 2 * fr + 2; ++r)
                     put_record((r & 1) && rq2 ? (mapped ? pos2_out : neg2_out) : (mapped ? pos_out : neg_out), b, r, l0, l1, db.leaf_names);
             }
-            if (scores) {
+            if (o.scores) {
                 // READ_SCORES.tsv: per fragment with hits (R1's id), both mates' k-mers and matched k-mers per genome
                 for (uint64_t fr = 0; fr < nf; ++fr) {
                     if (f.off[fr] == f.off[fr + 1]) continue;
@@ -2037,13 +2057,13 @@ struct QueryLoop {
                 }
                 if (!sc_out.empty() && fwrite(sc_out.data(), 1, sc_out.size(), out.scores) != sc_out.size()) die("short write to READ_SCORES.tsv");
             }
-            if (lca_reads) {
+            if (o.lca_reads) {
                 lca_out.clear();
                 for (uint64_t fr = 0; fr < nf; ++fr)
                     if (f.off[fr] != f.off[fr + 1]) put_lca(lca_out, b.id(2 * fr), f.off[fr + 1] - f.off[fr], f.lca[fr], db.clade_names);
                 if (!lca_out.empty() && fwrite(lca_out.data(), 1, lca_out.size(), out.lca) != lca_out.size()) die("short write to READ_LCA.tsv");
             }
-            if (taxon_reads) {
+            if (o.taxon_reads) {
                 taxa_out.clear();
                 for (uint64_t fr = 0; fr < nf; ++fr)
                     if (f.off[fr] != f.off[fr + 1]) put_lca(taxa_out, b.id(2 * fr), f.off[fr + 1] - f.off[fr], f.taxa[fr], db.taxon_names);
@@ -2094,7 +2114,7 @@ struct QueryLoop {
                 p.call_off.resize(r1 - r0 + 1);
                 for (uint64_t r = r0; r <= r1; ++r) p.call_off[r - r0] = b.off[r] - b.off[r0];
                 pfq_segments sg{};
-                if (pfq_query_frames(db.trees[i], b.seq.data() + b.off[r0], p.call_off.data(), r1 - r0, frame, step, threshold, 0, &sg) != PFQ_OK)
+                if (pfq_query_frames(db.trees[i], b.seq.data() + b.off[r0], p.call_off.data(), r1 - r0, frame, step, o.threshold, 0, &sg) != PFQ_OK)
                     fail_from_thread(pfq_last_error());
                 p.off.assign(sg.offsets, sg.offsets + (r1 - r0) + 1);
                 p.seg.assign(sg.seg, sg.seg + sg.offsets[r1 - r0]);
@@ -2135,7 +2155,7 @@ struct QueryLoop {
         const uint64_t n = sg.b.n();
         if (!n) return;
         const uint64_t tq0 = ReadQueue::now_ns();
-        classify(db.trees[i], sg.b, 0, n, threshold, lca_flags(), unused, false, false, prep);
+        classify(db.trees[i], sg.b, 0, n, o, lca_flags(), unused, prep);
         ns_gpu += ReadQueue::now_ns() - tq0;
         if (!db.sharded || i == 0) n_total += n;
     }
@@ -2390,7 +2410,7 @@ struct QueryLoop {
                 turn_cv.notify_all();
                 if (!dropped && n_dev) {
                     const uint64_t tq0 = ReadQueue::now_ns();
-                    if (pfq_text_query(tree, threshold, lca_flags(), nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    if (pfq_text_query(tree, o.threshold, lca_flags(), nullptr) != PFQ_OK) fail_from_thread(pfq_last_error());
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     n_total += n_dev;
                     n_device_records += n_dev;
@@ -2425,7 +2445,7 @@ struct QueryLoop {
         std::condition_variable turn_cv;
         uint64_t taken = 0, commit_next = 0, write_next = 0, next_index = 0;
         std::atomic<bool> exhausted{false}, aborted{false};
-        const uint32_t fmt_flags = (pos ? PFQ_FMT_POS : 0u) | (neg ? PFQ_FMT_NEG : 0u);
+        const uint32_t fmt_flags = (o.pos ? PFQ_FMT_POS : 0u) | (o.neg ? PFQ_FMT_NEG : 0u);
         const uint32_t query_flags = PFQ_WANT_HITS | lca_flags();
         // the output stage's state: touched only inside the output turn (and after the threads have joined)
         Batch carry;
@@ -2435,7 +2455,7 @@ struct QueryLoop {
         OutBuf pb, nb;
         auto write_block = [&](const Batch &b, const uint64_t *h_off, const uint32_t *h_leaves) {
             pb.n = nb.n = 0;
-            bf.run(b, h_off, h_leaves, pos, neg, db.leaf_names, pb, nb);
+            bf.run(b, h_off, h_leaves, o.pos, o.neg, db.leaf_names, pb, nb);
             out.pos.append(pb.p, pb.n);
             out.neg.append(nb.p, nb.n);
             n_fmt_host += b.n();
@@ -2450,12 +2470,12 @@ struct QueryLoop {
         // records [r0, r1) of src with their rows (h_off relative to h_leaves) join the carry; it is written whenever it is a block
         auto carry_add = [&](const Batch &src, uint64_t r0, uint64_t r1, const uint64_t *h_off, const uint32_t *h_leaves) {
             while (r0 < r1) {
-                const uint64_t take = std::min<uint64_t>(r1 - r0, block - carry.n());
+                const uint64_t take = std::min<uint64_t>(r1 - r0, o.block - carry.n());
                 carry.append(src, r0, r0 + take, true);
                 carry_leaves.insert(carry_leaves.end(), h_leaves + h_off[r0], h_leaves + h_off[r0 + take]);
                 for (uint64_t r = r0 + 1; r <= r0 + take; ++r) carry_off.push_back(carry_off.back() + (h_off[r] - h_off[r - 1]));
                 r0 += take;
-                if (carry.n() == block) flush_carry();
+                if (carry.n() == o.block) flush_carry();
             }
         };
         fan_out(n_trees(), [&](size_t d) {
@@ -2538,9 +2558,9 @@ struct QueryLoop {
                 if (!dropped && n_dev) {
                     const uint64_t tq0 = ReadQueue::now_ns();
                     pfq_hits hits{};
-                    if (pfq_text_query(tree, threshold, query_flags, &hits) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    if (pfq_text_query(tree, o.threshold, query_flags, &hits) != PFQ_OK) fail_from_thread(pfq_last_error());
                     const uint64_t tq1 = ReadQueue::now_ns();
-                    if (pfq_text_format(tree, first_index, (uint32_t)block, fmt_flags, &recs) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    if (pfq_text_format(tree, first_index, (uint32_t)o.block, fmt_flags, &recs) != PFQ_OK) fail_from_thread(pfq_last_error());
                     ns_text_format += ReadQueue::now_ns() - tq1;
                     ns_gpu += tq1 - tq0;
                     n_fmt_bytes += recs.pos_bytes + recs.neg_bytes;
@@ -2558,7 +2578,7 @@ struct QueryLoop {
                 if (n_host) {
                     sg->b.seq.resize(sg->b.seq.size() + 16);
                     const uint64_t tq0 = ReadQueue::now_ns();
-                    classify(tree, sg->b, 0, n_host, threshold, query_flags, host_hits);
+                    classify(tree, sg->b, 0, n_host, o, query_flags, host_hits, prep);
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     n_total += n_host;
                     n_host_records += n_host;
@@ -2635,7 +2655,7 @@ struct QueryLoop {
         std::vector<Slot> slots(db.devices.size() + 3);
         const size_t NB = slots.size();
         for (Slot &s : slots) s.parts.resize(db.sharded ? n_trees() : 1);
-        const uint32_t query_flags = PFQ_WANT_HITS | (scores ? PFQ_WANT_SCORES : 0u) | lca_flags() | abundance_flags();
+        const uint32_t query_flags = PFQ_WANT_HITS | (o.scores ? PFQ_WANT_SCORES : 0u) | lca_flags() | abundance_flags();
         std::mutex mu;
         std::condition_variable cv;
         long long last_seq = -1;                 // sequence number of the last batch, once the assembler knows it
@@ -2680,13 +2700,13 @@ struct QueryLoop {
                 }
                 uint64_t n = s->b.n();
                 const uint64_t tq0 = ReadQueue::now_ns();
-                std::vector<PrepKept> pks(prep_on() ? 1 : 0);
-                classify(db.trees[i], s->b, 0, n, threshold, query_flags, s->parts[db.sharded ? i : 0], lca_reads, taxon_reads, prep, prep_on() ? &pks[0] : nullptr);
+                std::vector<PrepKept> pks(o.prep ? 1 : 0);
+                classify(db.trees[i], s->b, 0, n, o, query_flags, s->parts[db.sharded ? i : 0], prep, o.prep ? &pks[0] : nullptr);
                 if (n) {
                     ns_gpu += ReadQueue::now_ns() - tq0;
                     if (!db.sharded || i == 0) n_total += n;
                 }
-                if (prep_on()) n = keep_prepared(s->b, {0, n}, pks).back();  // (replicas only: this thread alone holds the batch)
+                if (o.prep) n = keep_prepared(s->b, {0, n}, pks).back();  // (replicas only: this thread alone holds the batch)
                 {
                     std::lock_guard<std::mutex> lk(mu);
                     if (--s->trees_left != 0) continue;
@@ -2702,9 +2722,9 @@ struct QueryLoop {
         // (formatters and writers share the cores with the parser workers and the assembler; measured on 16 cores with
         // -t 16: 16 formatters / 16 writers 18.6 - 19.2 M reads/s, 12 / 8: 19.5 - 19.7, 8 / 4: 16.8 - 17.1.  PFQ_CLI_FMT_WORKERS /
         // PFQ_CLI_WRITERS override the split.)
-        unsigned fmt_workers = std::max(1u, threads * 3u / 4u);
+        unsigned fmt_workers = std::max(1u, o.threads * 3u / 4u);
         if (const char *e = getenv("PFQ_CLI_FMT_WORKERS")) fmt_workers = std::max(1u, (unsigned)atoi(e));
-        unsigned max_writers = std::max(1u, threads / 2u);
+        unsigned max_writers = std::max(1u, o.threads / 2u);
         if (const char *e = getenv("PFQ_CLI_WRITERS")) max_writers = std::max(1u, (unsigned)atoi(e));
         // two sets of output buffers: while the writer thread puts set s into the files, the formatters fill the other one
         std::vector<OutBuf> pos_sets[2] = {std::vector<OutBuf>(fmt_workers), std::vector<OutBuf>(fmt_workers)};
@@ -2767,12 +2787,12 @@ struct QueryLoop {
                 }
                 std::vector<OutBuf> &pos_buf = pos_sets[k & 1], &neg_buf = neg_sets[k & 1];
                 const uint64_t t0 = ReadQueue::now_ns();
-                const uint64_t n_blocks = n ? (n + block - 1) / block : 0;
+                const uint64_t n_blocks = n ? (n + o.block - 1) / o.block : 0;
                 // ---- phase 1: the blocks' maps
                 grp0.assign(n_blocks + 1, 0);
                 tab0.assign(n_blocks + 1, 0);
                 for (uint64_t blk = 0; blk < n_blocks; ++blk) {
-                    const uint64_t b0 = blk * block, b1 = std::min(n, b0 + block);
+                    const uint64_t b0 = blk * o.block, b1 = std::min(n, b0 + o.block);
                     uint64_t n_hit = 0;
                     for (uint64_t r = b0; r < b1; ++r) n_hit += h_off[r] != h_off[r + 1];
                     grp0[blk + 1] = grp0[blk] + n_hit;
@@ -2785,7 +2805,7 @@ struct QueryLoop {
                 const unsigned nw1 = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(fmt_workers, n_blocks));
                 fan_out(nw1, [&](size_t w) {
                     for (uint64_t blk = n_blocks * w / nw1; blk < n_blocks * (w + 1) / nw1; ++blk) {
-                        const uint64_t b0 = blk * block, b1 = std::min(n, b0 + block);
+                        const uint64_t b0 = blk * o.block, b1 = std::min(n, b0 + o.block);
                         map_block(b, b0, b1, h_off, h_leaves, groups.data() + grp0[blk], table.data() + tab0[blk], (size_t)(tab0[blk + 1] - tab0[blk]),
                                   merged_of[blk], grp_of.data());
                     }
@@ -2796,12 +2816,12 @@ struct QueryLoop {
                     OutBuf &pb = pos_buf[w], &nb = neg_buf[w];
                     pb.n = nb.n = 0;
                     for (uint64_t r = n * w / nw; r < n * (w + 1) / nw; ++r) {
-                        const uint64_t blk = r / block;
-                        put_block_record(pb, nb, b, r, grp_of[r], groups.data() + grp0[blk], merged_of[blk], h_off, h_leaves, pos, neg, db.leaf_names);
+                        const uint64_t blk = r / o.block;
+                        put_block_record(pb, nb, b, r, grp_of[r], groups.data() + grp0[blk], merged_of[blk], h_off, h_leaves, o.pos, o.neg, db.leaf_names);
                     }
                 });
                 for (unsigned w = nw; w < fmt_workers; ++w) pos_buf[w].n = neg_buf[w].n = 0;
-                if (scores) {
+                if (o.scores) {
                     // READ_SCORES.tsv: per record with hits, its genomes by matched k-mers
                     std::vector<std::string> parts(nw);
                     const uint32_t *h_sc = s.hits.scores.data();
@@ -2815,7 +2835,7 @@ struct QueryLoop {
                     for (const std::string &p : parts)
                         if (!p.empty() && fwrite(p.data(), 1, p.size(), out.scores) != p.size()) fail_from_thread("short write to READ_SCORES.tsv");
                 }
-                if (lca_reads) {
+                if (o.lca_reads) {
                     // READ_LCA.tsv: per record with hits, the size of its hit set and its clade
                     std::vector<std::string> parts(nw);
                     const uint32_t *h_lca = s.hits.lca.data();
@@ -2826,7 +2846,7 @@ struct QueryLoop {
                     for (const std::string &p : parts)
                         if (!p.empty() && fwrite(p.data(), 1, p.size(), out.lca) != p.size()) fail_from_thread("short write to READ_LCA.tsv");
                 }
-                if (taxon_reads) {
+                if (o.taxon_reads) {
                     // READ_TAXA.tsv: per record with hits, the size of its hit set and its node of the taxonomy
                     std::vector<std::string> parts(nw);
                     const uint32_t *h_taxa = s.hits.taxa.data();
@@ -2875,423 +2895,472 @@ struct QueryLoop {
     }
 };
 
-int cmd_query(int argc, char **argv) {
-    std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true},
-                             {"block-size-reads", 'b', true}, {"filter-threshold", 'f', true}, {"cache-size", 'c', true},
-                             {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false}, {"format", 'F', true},
-                             {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true},
-                             {"interleaved", 0, false}, {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false},
-                             {"abundance", 0, false}, {"abundance-iters", 0, true}, {"coverage", 0, false}, {"coverage-precision", 0, true},
-                             {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false}, {"device-inflate", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true},
-                             {"taxon-reads", 0, false}, {"best-hits", 0, false}, {"sweep", 0, true}, {"trim-quality", 0, true},
-                             {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true}, {"max-n", 0, true},
-                             {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
-                             {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}, {"deplete", 0, true, true},
-                             {"deplete-threshold", 0, true}, {"mate-correct", 0, false}, {"mate-correct-quality", 0, true}};
-    Args a = parse(argc, argv, 2, opts);
-    const std::string reads = req(a, "reads"), out = req(a, "out"), db_path = req(a, "db-path");
-    const unsigned threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);  // rayon pool size in the reference; here: parser workers
-    (void)to_u64(opt(a, "cache-size", "10"), "cache-size");  // LRU of .bf files: the whole tree is resident in HBM
-    const uint64_t block = to_u64(opt(a, "block-size-reads", "100"), "block-size-reads");
-    const float threshold = to_f32(opt(a, "filter-threshold", "1.0"), "filter-threshold");
-    const bool pos = a.flags.count("pos-filter") != 0, neg = a.flags.count("neg-filter") != 0;
-    const bool filtering = pos || neg;
-    // --scores: READ_SCORES.tsv, one line per (read record, hit genome) with how many of the read's k-mers the genome contains
-    const bool scores = a.flags.count("scores") != 0;
-    // --best-hits: --taxonomy, --abundance and --coverage take every read's (fragment's) best-scoring genomes instead of its whole
-    // hit row (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_ROWS_BEST); every other output stays what it is.  Checked first, so that a
-    // refusal names this option whichever of the three it came with
-    const bool best_hits = a.flags.count("best-hits") != 0;
-    if (best_hits) {
-        if (!a.flags.count("abundance") && !a.flags.count("coverage") && !a.val.count("taxonomy"))
-            die("error: '--best-hits' needs at least one of '--taxonomy <FILE>', '--abundance', '--coverage': they are what it changes");
-        if (a.val.count("shard-depth"))
-            die("error: '--best-hits' cannot be used with '--shard-depth': a subtree shard sees only its own genomes, and the best of a "
-                "partial hit row is not the row's best");
-        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--best-hits': it serves runs that only count");
-        if (a.val.count("frame")) die("error: '--best-hits' cannot be used with '--frame': frames do not combine with per-read post-stages");
+// --- the options of `query`: values ---
+[[noreturn]] void invalid(const std::string &name, const std::string &value, const std::string &what) {
+    die("error: invalid value '" + value + "' for '--" + name + "': " + what);
+}
+// The strict rule for a number: it starts with a digit, nothing follows the digits, it fits and lies in [lo, hi].  (to_u64 is the
+// lenient one, with the shorter message: it takes "+5" and " 5".)
+bool strict_uint(const std::string &text, uint64_t lo, uint64_t hi, uint64_t &x) {
+    char *end = nullptr;
+    errno = 0;
+    x = strtoull(text.c_str(), &end, 10);
+    return !text.empty() && isdigit((unsigned char)text[0]) && !*end && !errno && x >= lo && x <= hi;
+}
+uint64_t parse_uint(const char *name, const std::string &text, uint64_t lo, uint64_t hi, const char *what) {
+    uint64_t x = 0;
+    if (!strict_uint(text, lo, hi, x)) invalid(name, text, what);
+    return x;
+}
+std::vector<std::string> split_list(const std::string &text) {  // at every ',': empty items are kept, "" is one empty item
+    std::vector<std::string> items;
+    for (size_t at = 0, end = 0; end != std::string::npos; at = end + 1) {
+        end = text.find(',', at);
+        items.push_back(text.substr(at, end == std::string::npos ? end : end - at));
     }
-    // --sweep T1,T2,..: one pass at -f also counts, per listed threshold, what a run of its own at that threshold would report
-    // (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP): THRESHOLDS.tsv and THRESHOLD_GENOMES.tsv; every other output stays what it
-    // is.  The values are parsed as -f is and kept as typed for the files.
-    const bool sweep = a.val.count("sweep") != 0;
-    std::vector<float> sweep_thr;
-    std::vector<std::string> sweep_typed;
-    if (sweep) {
-        for (const char *other : {"reads2", "shard-depth", "frame"})
-            if (a.val.count(other))
-                die(std::string("error: '--sweep' cannot be used with '--") + other + "'" +
-                    (other[0] == 'r'   ? ": a fragment's score is its mates' sum, so its hits at other thresholds do not follow from it"
-                     : other[0] == 's' ? ": a subtree shard sees only its own genomes, so the reads it would count are partial"
-                                       : ": frames do not combine with per-read post-stages"));
-        if (a.flags.count("interleaved"))
-            die("error: '--sweep' cannot be used with '--interleaved': a fragment's score is its mates' sum, so its hits at other thresholds do "
-                "not follow from it");
-        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--sweep': it serves runs that only count");
-        const std::string spec = a.val.at("sweep");
-        for (size_t p0 = 0; p0 <= spec.size();) {
-            size_t p1 = spec.find(',', p0);
-            if (p1 == std::string::npos) p1 = spec.size();
-            const std::string item = spec.substr(p0, p1 - p0);
-            if (item.empty()) die("error: invalid value '" + spec + "' for '--sweep': an empty item in the list of thresholds");
-            const float v = to_f32(item, "sweep");
-            if (v != v) die("error: invalid value '" + item + "' for '--sweep': not a number");
-            if (!sweep_thr.empty() && !(sweep_thr.back() < v))
-                die("error: invalid value '" + spec + "' for '--sweep': the thresholds must be strictly ascending ('" + sweep_typed.back() +
-                    "' before '" + item + "')");
-            if (!(threshold <= v))
-                die("error: '--sweep " + item + "' is below '--filter-threshold " + opt(a, "filter-threshold", "1.0") +
-                    "' (-f): the one pass runs at -f and cannot answer a lower threshold; lower -f to the list's lowest value");
-            sweep_thr.push_back(v);
-            sweep_typed.push_back(item);
-            p0 = p1 + 1;
+    return items;
+}
+
+// --- the options of `query`: which go together ---
+// REFUSALS, read from top to bottom, is THE order in which a command line is refused: parse_query_options() walks it stage by
+// stage, each named in the call, and does between two stages the checks that are no pairs (values, lists, files), which the
+// comment at that place names.  A row says: WITH: `option` cannot be used with any of `others` (the first one given is named);
+// NEEDS: `option` needs one of `others`, and `reason` is what the message says it needs; ARGUMENT: as WITH, in the words of the
+// reference's parser.  An entry is an option's name, or "name value" (given with just that value), or "any-prep": the first of
+// PREP_OPTIONS given, but --deplete before all of them.  Where a row sits decides which option a refusal names when several rows
+// apply, so a new option's rows go where its priority demands, not at the end.
+enum class Stage { FIRST, LCA, COVERAGE, DEVICE_OUTPUT, FRAME_STEP, MODES, ADAPTERS, MATES, TAXONOMY, PAIRS, PAIR_MODE };
+struct Refusal {
+    Stage stage;
+    enum Rule { WITH, NEEDS, ARGUMENT } rule;
+    const char *option, *others, *reason;
+};
+const char *const PREP_OPTIONS[] = {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2",
+                                    "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors"};
+const char ONLY_COUNTS[] = ": it serves runs that only count", FRAMES[] = ": frames do not combine with per-read post-stages",
+           FRAGMENTS[] = ": a fragment's score is its mates' sum, so its hits at other thresholds do not follow from it",
+           BEST_SCORES[] = ": the best hits need every read's scores",
+           DEVICE_OUTPUT[] = ": it formats the POS / NEG records of single reads, and nothing else, on the device";
+const Refusal REFUSALS[] = {
+    // --best-hits first, so that a refusal names it whichever of --taxonomy, --abundance, --coverage it came with
+    {Stage::FIRST, Refusal::NEEDS, "best-hits", "taxonomy,abundance,coverage", "at least one of '--taxonomy <FILE>', '--abundance', '--coverage': they are what it changes"},
+    {Stage::FIRST, Refusal::WITH, "best-hits", "shard-depth", ": a subtree shard sees only its own genomes, and the best of a partial hit row is not the row's best"},
+    {Stage::FIRST, Refusal::WITH, "device-parse", "best-hits", ONLY_COUNTS},
+    {Stage::FIRST, Refusal::WITH, "best-hits", "frame", FRAMES},
+    {Stage::FIRST, Refusal::WITH, "sweep", "reads2", FRAGMENTS},
+    {Stage::FIRST, Refusal::WITH, "sweep", "shard-depth", ": a subtree shard sees only its own genomes, so the reads it would count are partial"},
+    {Stage::FIRST, Refusal::WITH, "sweep", "frame", FRAMES},
+    {Stage::FIRST, Refusal::WITH, "sweep", "interleaved", FRAGMENTS},
+    {Stage::FIRST, Refusal::WITH, "device-parse", "sweep", ONLY_COUNTS},
+    // then: the list of --sweep, each value against -f; the value of --lca
+    {Stage::LCA, Refusal::NEEDS, "lca-reads", "lca", "'--lca <all|best>'"},
+    {Stage::LCA, Refusal::WITH, "lca", "shard-depth", ": a subtree shard holds only its own part of the tree, and combining the shards' lowest common ancestors needs the whole tree's clades (not implemented)"},
+    {Stage::LCA, Refusal::NEEDS, "abundance-iters", "abundance", "'--abundance'"},
+    // then: the value of --abundance-iters
+    {Stage::COVERAGE, Refusal::WITH, "abundance", "shard-depth", ": a subtree shard sees only its own genomes, so the hit rows it would log are partial (not implemented)"},
+    {Stage::COVERAGE, Refusal::NEEDS, "coverage-precision", "coverage", "'--coverage'"},
+    // then: the value of --coverage-precision
+    // --device-output refuses everything --device-parse refuses but the two filters, before the other options' own checks, so that the
+    // refusal names it; --deplete before the other options that turn preprocessing on
+    {Stage::DEVICE_OUTPUT, Refusal::WITH, "device-output", "device-parse", ": that option serves runs that only count, this one parses the text itself"},
+    {Stage::DEVICE_OUTPUT, Refusal::WITH, "device-output", "scores,lca-reads,interleaved,abundance,coverage,taxon-reads,best-hits,mate-correct,deplete,deplete-threshold", DEVICE_OUTPUT},
+    {Stage::DEVICE_OUTPUT, Refusal::WITH, "device-output", "reads2,frame,shard-depth,taxonomy,sweep,trim-quality,trim-window,trim-poly-x,min-length,max-n,min-complexity,adapter,adapter2",
+     DEVICE_OUTPUT},
+    {Stage::DEVICE_OUTPUT, Refusal::WITH, "device-output", "adapter-overlap,adapter-errors,mate-overlap,mate-overlap-errors,mate-correct-quality", DEVICE_OUTPUT},
+    {Stage::DEVICE_OUTPUT, Refusal::WITH, "device-output", "lca best", BEST_SCORES},
+    {Stage::DEVICE_OUTPUT, Refusal::NEEDS, "device-output", "pos-filter,neg-filter", "'--pos-filter' or '--neg-filter' (or both): they are the outputs it makes"},
+    // then: --device-output against the value of --block-size-reads
+    {Stage::FRAME_STEP, Refusal::NEEDS, "frame-step", "frame", "'--frame <F>'"},
+    // then: the values of --frame and --frame-step, the step against the frame
+    {Stage::MODES, Refusal::WITH, "frame", "reads2,shard-depth,interleaved,scores,abundance,coverage,pos-filter,neg-filter,lca", ""},
+    {Stage::MODES, Refusal::NEEDS, "device-inflate", "device-parse", "'--device-parse': the text it inflates on the device is parsed there"},
+    {Stage::MODES, Refusal::WITH, "device-parse", "pos-filter,neg-filter,scores,lca-reads,interleaved,abundance,coverage,reads2,frame,shard-depth", ONLY_COUNTS},
+    {Stage::MODES, Refusal::WITH, "device-parse", "lca best", BEST_SCORES},
+    // --mate-correct is part of the mate overlap step, so it needs --mate-overlap and is refused wherever that is
+    {Stage::MODES, Refusal::NEEDS, "mate-correct-quality", "mate-correct", "'--mate-correct'"},
+    {Stage::MODES, Refusal::NEEDS, "mate-correct", "mate-overlap", "'--mate-overlap <O>': it corrects the bases on which the overlapping mates of a fragment disagree"},
+    {Stage::MODES, Refusal::NEEDS, "deplete-threshold", "deplete", "'--deplete <DIR>'"},
+    {Stage::MODES, Refusal::WITH, "any-prep", "device-parse,frame,shard-depth", ": preprocessing works on the batches the host reader parses and classifies every kept read on every replica"},
+    // then: the values of the trimming options
+    {Stage::ADAPTERS, Refusal::NEEDS, "adapter-overlap", "adapter", "'--adapter <SEQ>'"},
+    {Stage::ADAPTERS, Refusal::NEEDS, "adapter-errors", "adapter", "'--adapter <SEQ>'"},
+    {Stage::ADAPTERS, Refusal::NEEDS, "adapter2", "adapter", "'--adapter <SEQ>'"},
+    {Stage::ADAPTERS, Refusal::NEEDS, "adapter2", "reads2,interleaved", "'--reads2 <FILE>' or '--interleaved': it serves the second mates"},
+    // then: the values of --adapter-overlap and --adapter-errors, the adapters, each one's length against --adapter-overlap
+    {Stage::MATES, Refusal::NEEDS, "mate-overlap-errors", "mate-overlap", "'--mate-overlap <O>'"},
+    {Stage::MATES, Refusal::NEEDS, "mate-overlap", "reads2,interleaved", "'--reads2 <FILE>' or '--interleaved': it compares the two mates of a fragment"},
+    // then: the values of the mate options; the screens of --deplete, each one's tree.bin
+    {Stage::TAXONOMY, Refusal::NEEDS, "taxon-reads", "taxonomy", "'--taxonomy <FILE>'"},
+    {Stage::TAXONOMY, Refusal::WITH, "taxonomy", "shard-depth", ": a subtree shard sees only its own genomes, so the hit rows it would count are partial (not implemented)"},
+    {Stage::TAXONOMY, Refusal::WITH, "taxonomy", "frame", FRAMES},
+    {Stage::TAXONOMY, Refusal::WITH, "device-parse", "taxonomy", ONLY_COUNTS},
+    // then: the taxonomy's file against tree.bin; the value of --format
+    {Stage::PAIRS, Refusal::ARGUMENT, "reads2", "interleaved", ""},
+    // then: the value of --pair-mode
+    {Stage::PAIR_MODE, Refusal::NEEDS, "pair-mode", "reads2,interleaved", "'--reads2' or '--interleaved'"}};
+// What the command line has of a table entry (see REFUSALS), as a message names it; empty: nothing
+std::string given(const Args &a, const std::string &entry) {
+    if (entry == "any-prep") {
+        if (a.val.count("deplete")) return "deplete";
+        for (const char *name : PREP_OPTIONS)
+            if (a.val.count(name)) return name;
+        return "";
+    }
+    const size_t space = entry.find(' ');
+    const auto it = a.val.find(entry.substr(0, space));
+    if (space != std::string::npos) return it != a.val.end() && it->second == entry.substr(space + 1) ? entry : "";
+    return it != a.val.end() || a.flags.count(entry) ? entry : "";
+}
+[[noreturn]] void refuse_with(const std::string &option, const std::string &other, const std::string &reason, bool argument = false) {
+    std::string upper = option;
+    for (char &c : upper) c = (char)toupper((unsigned char)c);
+    die("error: " + (argument ? "the argument '--" + option + " <" + upper + ">'" : "'--" + option + "'") + " cannot be used with '--" + other + "'" + reason);
+}
+// Refuses the command line by the first row of the stage that applies
+void refuse_by_table(const Args &a, Stage stage) {
+    for (const Refusal &row : REFUSALS) {
+        const std::string option = row.stage == stage ? given(a, row.option) : "";
+        if (option.empty()) continue;
+        bool any = false;
+        for (const std::string &entry : split_list(row.others)) {
+            const std::string other = given(a, entry);
+            if (other.empty()) continue;
+            if (row.rule != Refusal::NEEDS) refuse_with(option, other, row.reason, row.rule == Refusal::ARGUMENT);
+            any = true;
         }
-        if (sweep_thr.size() > PFQ_SWEEP_MAX)
-            die("error: invalid value '" + spec + "' for '--sweep': " + std::to_string(sweep_thr.size()) + " thresholds, at most " +
-                std::to_string(PFQ_SWEEP_MAX));
+        if (row.rule == Refusal::NEEDS && !any) die("error: '--" + option + "' needs " + row.reason);
     }
-    // --lca all|best: every read (fragment) is also assigned to the lowest common ancestor of its hit genomes (best: of the
-    // genomes with its highest score): CLADE_COUNTS.tsv; --lca-reads: READ_LCA.tsv, one line per record with hits
-    const std::string lca_arg = opt(a, "lca", "");
-    if (a.val.count("lca") && lca_arg != "all" && lca_arg != "best")
-        die("error: invalid value '" + lca_arg + "' for '--lca' [possible values: all, best]");
-    const int lca = lca_arg == "all" ? 1 : lca_arg == "best" ? 2 : 0;
-    const bool lca_reads = a.flags.count("lca-reads") != 0;
-    if (lca_reads && !lca) die("error: '--lca-reads' needs '--lca <all|best>'");
-    if (lca && a.val.count("shard-depth"))
-        die("error: '--lca' cannot be used with '--shard-depth': a subtree shard holds only its own part of the tree, and combining "
-            "the shards' lowest common ancestors needs the whole tree's clades (not implemented)");
-    // --abundance: every query call also logs its units' hit rows on the device (PFQ_WANT_HITS | PFQ_WANT_ABUNDANCE); at the end
-    // an EM over the log estimates how many units every genome produced: ABUNDANCE.tsv
-    const bool abundance = a.flags.count("abundance") != 0;
-    if (a.val.count("abundance-iters") && !abundance) die("error: '--abundance-iters' needs '--abundance'");
-    const uint64_t abundance_iters = to_u64(opt(a, "abundance-iters", "200"), "abundance-iters");
-    if (abundance && (abundance_iters == 0 || abundance_iters > 0xffffffffull))
-        die("error: invalid value '" + opt(a, "abundance-iters", "") + "' for '--abundance-iters': at least 1 iteration");
-    if (abundance && a.val.count("shard-depth"))
-        die("error: '--abundance' cannot be used with '--shard-depth': a subtree shard sees only its own genomes, so the hit rows it "
-            "would log are partial (not implemented)");
-    // --coverage: every query call also sketches, per genome a read lists, the read's k-mers that genome's filter contains
-    // (PFQ_WANT_HITS | PFQ_WANT_COVERAGE); at the end COVERAGE.tsv says how many distinct k-mers every genome's reads matched
-    const bool coverage = a.flags.count("coverage") != 0;
-    if (a.val.count("coverage-precision") && !coverage) die("error: '--coverage-precision' needs '--coverage'");
-    const std::string coverage_p = opt(a, "coverage-precision", "12");
-    if (coverage) {
-        char *end = nullptr;
-        const long v = strtol(coverage_p.c_str(), &end, 10);
-        if (coverage_p.empty() || !isdigit((unsigned char)coverage_p[0]) || *end || v < 4 || v > 16)
-            die("error: invalid value '" + coverage_p + "' for '--coverage-precision': 4 to 16 (2^P registers per genome)");
+}
+
+// Reads and checks the command line of `query`.  Everything here happens before any device is used and before the output directory
+// is touched; the only files looked at are the screens' tree.bin (--deplete) and the database's leaf ids and the taxonomy (--taxonomy).
+QueryOptions parse_query_options(const Args &a) {
+    QueryOptions o;
+    const auto has = [&](const char *name) { return a.flags.count(name) != 0 || a.val.count(name) != 0; };
+    const auto number = [&](const char *name, const char *dflt, uint64_t lo, uint64_t hi, const char *what) { return (uint32_t)parse_uint(name, opt(a, name, dflt), lo, hi, what); };
+    o.reads = req(a, "reads"), o.out = req(a, "out"), o.db_path = req(a, "db-path");
+    o.threads = (unsigned)std::min<uint64_t>(to_u64(opt(a, "threads", "4"), "threads"), 256);
+    (void)to_u64(opt(a, "cache-size", "10"), "cache-size");  // LRU of .bf files: the whole tree is resident in HBM
+    o.block = to_u64(opt(a, "block-size-reads", "100"), "block-size-reads");
+    const std::string threshold_typed = opt(a, "filter-threshold", "1.0");
+    o.threshold = to_f32(threshold_typed, "filter-threshold");
+    o.pos = has("pos-filter"), o.neg = has("neg-filter"), o.scores = has("scores"), o.best_hits = has("best-hits");
+    refuse_by_table(a, Stage::FIRST);
+    // --sweep T1,T2,..: one pass at -f also counts, per listed threshold, what a run of its own at that threshold would report
+    // (PFQ_WANT_HITS | PFQ_WANT_SCORES | PFQ_WANT_SWEEP).  The values are parsed as -f is and kept as typed for the files.
+    if ((o.sweep = has("sweep"))) {
+        const std::string &spec = a.val.at("sweep");
+        for (const std::string &item : split_list(spec)) {
+            if (item.empty()) invalid("sweep", spec, "an empty item in the list of thresholds");
+            const float v = to_f32(item, "sweep");
+            if (v != v) invalid("sweep", item, "not a number");
+            if (!o.sweep_thr.empty() && !(o.sweep_thr.back() < v))
+                invalid("sweep", spec, "the thresholds must be strictly ascending ('" + o.sweep_typed.back() + "' before '" + item + "')");
+            if (!(o.threshold <= v))
+                die("error: '--sweep " + item + "' is below '--filter-threshold " + threshold_typed +
+                    "' (-f): the one pass runs at -f and cannot answer a lower threshold; lower -f to the list's lowest value");
+            o.sweep_thr.push_back(v), o.sweep_typed.push_back(item);
+        }
+        if (o.sweep_thr.size() > PFQ_SWEEP_MAX)
+            invalid("sweep", spec, std::to_string(o.sweep_thr.size()) + " thresholds, at most " + std::to_string(PFQ_SWEEP_MAX));
     }
+    // --lca all|best: every read (fragment) is also assigned to the lowest common ancestor of its hit genomes (best: of its best-scoring ones)
+    const std::string lca = opt(a, "lca", "");
+    if (has("lca") && lca != "all" && lca != "best") die("error: invalid value '" + lca + "' for '--lca' [possible values: all, best]");
+    o.lca = lca == "all" ? 1 : lca == "best" ? 2 : 0, o.lca_reads = has("lca-reads");
+    refuse_by_table(a, Stage::LCA);
+    // --abundance: every call also logs its units' hit rows on the device; at the end an EM over the log estimates every genome's units
+    o.abundance = has("abundance"), o.abundance_iters = to_u64(opt(a, "abundance-iters", "200"), "abundance-iters");
+    if (o.abundance && (o.abundance_iters == 0 || o.abundance_iters > 0xffffffffull)) invalid("abundance-iters", opt(a, "abundance-iters", ""), "at least 1 iteration");
+    refuse_by_table(a, Stage::COVERAGE);
+    // --coverage: every call also sketches, per genome a read lists, the read's k-mers that genome's filter contains
+    o.coverage = has("coverage"), o.coverage_precision = opt(a, "coverage-precision", "12");
+    if (o.coverage) parse_uint("coverage-precision", o.coverage_precision, 4, 16, "4 to 16 (2^P registers per genome)");
+    refuse_by_table(a, Stage::DEVICE_OUTPUT);
     // --device-output: the POS / NEG records of plain FASTA / FASTQ files are parsed, classified and formatted on the device
-    // (pfq_text_parse, pfq_text_query, pfq_text_format).  Everything --device-parse refuses but the two filters is refused here
-    // too, before the other options' own checks, so that the refusal names this option
-    const bool device_output = a.flags.count("device-output") != 0;
-    if (device_output) {
-        const std::string why = ": it formats the POS / NEG records of single reads, and nothing else, on the device";
-        if (a.flags.count("device-parse"))
-            die("error: '--device-output' cannot be used with '--device-parse': that option serves runs that only count, this one parses the text itself");
-        for (const char *other : {"scores", "lca-reads", "interleaved", "abundance", "coverage", "taxon-reads", "best-hits", "mate-correct"})
-            if (a.flags.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
-        for (const char *other : {"deplete", "deplete-threshold"})  // (first: whatever else turns preprocessing on, the refusal names this one)
-            if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
-        for (const char *other : {"reads2", "frame", "shard-depth", "taxonomy", "sweep", "trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n",
-                                  "min-complexity", "adapter", "adapter2", "adapter-overlap", "adapter-errors", "mate-overlap", "mate-overlap-errors", "mate-correct-quality"})
-            if (a.val.count(other)) die(std::string("error: '--device-output' cannot be used with '--") + other + "'" + why);
-        if (lca == 2) die("error: '--device-output' cannot be used with '--lca best': the best hits need every read's scores");
-        if (!filtering) die("error: '--device-output' needs '--pos-filter' or '--neg-filter' (or both): they are the outputs it makes");
-        if (block == 0) die("error: '--device-output' cannot be used with '--block-size-reads 0': no read would be classified");
-        if (block > PFQ_FMT_BLOCK_MAX)
-            die("error: '--device-output' cannot be used with '--block-size-reads " + std::to_string(block) + "': the device decides POS / NEG per block of at most " +
-                std::to_string(PFQ_FMT_BLOCK_MAX) + " reads");
+    if ((o.device_output = has("device-output"))) {
+        if (o.block == 0) refuse_with("device-output", "block-size-reads 0", ": no read would be classified");
+        if (o.block > PFQ_FMT_BLOCK_MAX)
+            refuse_with("device-output", "block-size-reads " + std::to_string(o.block), ": the device decides POS / NEG per block of at most " + std::to_string(PFQ_FMT_BLOCK_MAX) + " reads");
     }
+    refuse_by_table(a, Stage::FRAME_STEP);
     // --frame F [--frame-step S]: every sequence (a contig, a long read) is classified in overlapping frames of F bases every S
     // bases (pfq_query_frames) and SEGMENTS.tsv says where on it every genome matched; CLASSIFICATION.csv then counts sequences
-    const bool framed = a.val.count("frame") != 0;
-    if (a.val.count("frame-step") && !framed) die("error: '--frame-step' needs '--frame <F>'");
-    uint32_t frame = 0, frame_step = 0;
-    if (framed) {
-        auto positive = [&](const char *name) {
-            const std::string v = a.val.at(name);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long x = strtoull(v.c_str(), &end, 10);
-            if (v.empty() || !isdigit((unsigned char)v[0]) || *end || errno || x == 0 || x > 0xffffffffull)
-                die("error: invalid value '" + v + "' for '--" + name + "': a positive number of bases");
-            return (uint32_t)x;
-        };
-        frame = positive("frame");
-        frame_step = a.val.count("frame-step") ? positive("frame-step") : std::max<uint32_t>(frame / 2, 1);
-        if (frame_step > frame)
-            die("error: '--frame-step " + std::to_string(frame_step) + "' is larger than '--frame " + std::to_string(frame) + "': frames would leave gaps");
-        for (const char *other : {"reads2", "shard-depth"})
-            if (a.val.count(other)) die(std::string("error: '--frame' cannot be used with '--") + other + "'");
-        for (const char *other : {"interleaved", "scores", "abundance", "coverage", "pos-filter", "neg-filter"})
-            if (a.flags.count(other)) die(std::string("error: '--frame' cannot be used with '--") + other + "'");
-        if (lca) die("error: '--frame' cannot be used with '--lca'");
+    if (has("frame")) {
+        o.frame = number("frame", "", 1, 0xffffffffull, "a positive number of bases");
+        o.frame_step = has("frame-step") ? number("frame-step", "", 1, 0xffffffffull, "a positive number of bases") : std::max<uint32_t>(o.frame / 2, 1);
+        if (o.frame_step > o.frame)
+            die("error: '--frame-step " + std::to_string(o.frame_step) + "' is larger than '--frame " + std::to_string(o.frame) + "': frames would leave gaps");
     }
     // --device-parse: plain FASTA / FASTQ files are parsed on the device (pfq_text_parse); only where the run counts per genome
     // (and per clade) on replicas — per-read outputs, pairs, frames and shards keep the host reader
     // --device-inflate: blocked gzip (BGZF) files are inflated on the device as well (pfq_text_inflate); it rides on --device-parse
-    const bool device_parse = a.flags.count("device-parse") != 0, device_inflate = a.flags.count("device-inflate") != 0;
-    if (device_inflate && !device_parse)
-        die("error: '--device-inflate' needs '--device-parse': the text it inflates on the device is parsed there");
-    if (device_parse) {
-        for (const char *other : {"pos-filter", "neg-filter", "scores", "lca-reads", "interleaved", "abundance", "coverage"})
-            if (a.flags.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
-        for (const char *other : {"reads2", "frame", "shard-depth"})
-            if (a.val.count(other)) die(std::string("error: '--device-parse' cannot be used with '--") + other + "': it serves runs that only count");
-        if (lca == 2) die("error: '--device-parse' cannot be used with '--lca best': the best hits need every read's scores");
+    o.device_parse = has("device-parse"), o.device_inflate = has("device-inflate");
+    refuse_by_table(a, Stage::MODES);
+    // --trim-quality Q, --trim-window W, --trim-poly-x P, --min-length L, --max-n N, --min-complexity C, the adapter and mate options
+    // and --deplete: any of them turns read preprocessing on: every call trims and filters its reads on the device (pfq_prep_reads)
+    // and classifies what is kept (pfq_prep_query).  --min-length then defaults to the database's k.
+    if ((o.prep = !given(a, "any-prep").empty())) {
+        o.params.trim_quality = number("trim-quality", "0", 0, 93, "a Phred quality from 0 (off) to 93");
+        o.params.trim_window = number("trim-window", "4", 1, 1024, "a window of 1 to 1024 bases");
+        o.params.poly_x = number("trim-poly-x", "0", 0, 0xffffffffull, "a number of bases (0: off)");
+        o.params.min_length = has("min-length") ? number("min-length", "1", 1, 0xffffffffull, "at least 1 base (the default is the database's k)") : 0;
+        o.params.max_n = has("max-n") ? number("max-n", "0", 0, 0xfffffffeull, "a number of N bases") : 0xffffffffu;
+        o.params.min_complexity = number("min-complexity", "0", 0, 100, "a percentage from 0 (off) to 100");
     }
-    // --trim-quality Q, --trim-window W, --trim-poly-x P, --min-length L, --max-n N, --min-complexity C: any of them turns read
-    // preprocessing on: every call trims and filters its reads on the device (pfq_prep_reads) and classifies what is kept
-    // (pfq_prep_query); PREPROCESS.tsv holds the totals.  --min-length then defaults to the database's k.
-    // --mate-correct [--mate-correct-quality HI[,LO]]: part of the mate overlap step, so it needs --mate-overlap and is refused
-    // wherever that is
-    const bool mate_correct = a.flags.count("mate-correct") != 0;
-    if (a.val.count("mate-correct-quality") && !mate_correct) die("error: '--mate-correct-quality' needs '--mate-correct'");
-    if (mate_correct && !a.val.count("mate-overlap"))
-        die("error: '--mate-correct' needs '--mate-overlap <O>': it corrects the bases on which the overlapping mates of a fragment disagree");
-    static PrepRun prep_run;
-    const char *prep_first = nullptr;
-    for (const char *name : {"trim-quality", "trim-window", "trim-poly-x", "min-length", "max-n", "min-complexity", "adapter", "adapter2", "adapter-overlap",
-                             "adapter-errors", "mate-overlap", "mate-overlap-errors"})
-        if (a.val.count(name) && !prep_first) prep_first = name;
-    // --deplete DIR [--deplete DIR2 ..] [--deplete-threshold T]: after the steps above every unit that hits one of the screens, a
-    // database each, at T (default: -f) is taken out before the classification (pfq.h "depletion").  It turns preprocessing on
-    // as the options above do, and its refusals name it.
-    if (a.val.count("deplete-threshold") && !a.val.count("deplete")) die("error: '--deplete-threshold' needs '--deplete <DIR>'");
-    if (a.val.count("deplete")) prep_first = "deplete";
-    if (prep_first) {
-        prep_run.on = true;
-        const std::string why = ": preprocessing works on the batches the host reader parses and classifies every kept read on every replica";
-        if (a.flags.count("device-parse")) die(std::string("error: '--") + prep_first + "' cannot be used with '--device-parse'" + why);
-        for (const char *other : {"frame", "shard-depth"})
-            if (a.val.count(other)) die(std::string("error: '--") + prep_first + "' cannot be used with '--" + other + "'" + why);
-        auto number = [&](const char *name, const char *dflt, uint64_t lo, uint64_t hi, const char *what) {
-            const std::string v = opt(a, name, dflt);
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long x = strtoull(v.c_str(), &end, 10);
-            if (v.empty() || !isdigit((unsigned char)v[0]) || *end || errno || x < lo || x > hi)
-                die("error: invalid value '" + v + "' for '--" + name + "': " + what);
-            return (uint32_t)x;
-        };
-        prep_run.params.trim_quality = number("trim-quality", "0", 0, 93, "a Phred quality from 0 (off) to 93");
-        prep_run.params.trim_window = number("trim-window", "4", 1, 1024, "a window of 1 to 1024 bases");
-        prep_run.params.poly_x = number("trim-poly-x", "0", 0, 0xffffffffull, "a number of bases (0: off)");
-        prep_run.params.min_length = a.val.count("min-length") ? number("min-length", "1", 1, 0xffffffffull, "at least 1 base (the default is the database's k)") : 0;
-        prep_run.params.max_n = a.val.count("max-n") ? number("max-n", "0", 0, 0xfffffffeull, "a number of N bases") : 0xffffffffu;
-        prep_run.params.min_complexity = number("min-complexity", "0", 0, 100, "a percentage from 0 (off) to 100");
-        // --adapter SEQ[,SEQ..] (reads and first mates), --adapter2 SEQ[,..] (second mates; without it they use --adapter's),
-        // --adapter-overlap O, --adapter-errors E: every read is cut at the leftmost place an adapter matches (pfq.h "adapters")
-        // before the steps above.  A SEQ is a sequence over ACGT or the name of a preset.
-        for (const char *name : {"adapter-overlap", "adapter-errors", "adapter2"})
-            if (a.val.count(name) && !a.val.count("adapter")) die(std::string("error: '--") + name + "' needs '--adapter <SEQ>'");
-        if (a.val.count("adapter2") && !a.val.count("reads2") && !a.flags.count("interleaved"))
-            die("error: '--adapter2' needs '--reads2 <FILE>' or '--interleaved': it serves the second mates");
-        prep_run.adapter_overlap = number("adapter-overlap", "5", 1, PFQ_ADAPTER_LEN_MAX, "an overlap of 1 to 64 bases");
-        prep_run.adapter_errors = number("adapter-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
+    refuse_by_table(a, Stage::ADAPTERS);
+    // --adapter SEQ[,SEQ..] (reads and first mates), --adapter2 SEQ[,..] (second mates; without it they use --adapter's),
+    // --adapter-overlap O, --adapter-errors E: every read is cut at the leftmost place an adapter matches (pfq.h "adapters")
+    // before the steps above.  A SEQ is a sequence over ACGT or the name of a preset.
+    if (has("adapter")) {
+        o.adapter_overlap = number("adapter-overlap", "5", 1, PFQ_ADAPTER_LEN_MAX, "an overlap of 1 to 64 bases");
+        o.adapter_errors = number("adapter-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
         static const std::pair<const char *, const char *> presets[] = {
             {"illumina", "AGATCGGAAGAGC"}, {"nextera", "CTGTCTCTTATACACATCT"}, {"smallrna", "TGGAATTCTCGGGTGCCAAGG"}};
         for (int set = 0; set < 2; ++set) {
             const char *name = set ? "adapter2" : "adapter";
-            if (!a.val.count(name)) continue;
-            const std::string list = a.val.at(name) + ",";
-            for (size_t at = 0, end; (end = list.find(',', at)) != std::string::npos; at = end + 1) {
-                std::string seq = list.substr(at, end - at);
+            if (!has(name)) continue;
+            for (const std::string &item : split_list(a.val.at(name))) {  // (the parser joins a repeated option's values with ',')
+                std::string seq = item;
                 for (const auto &p : presets)
                     if (seq == p.first) seq = p.second;
-                const std::string bad = "error: invalid value '" + list.substr(at, end - at) + "' for '--" + name + "': ";
                 for (char &ch : seq) {
-                    const char u = (char)(ch & 0xDF);
-                    if (u != 'A' && u != 'C' && u != 'G' && u != 'T') die(bad + "a sequence over ACGT or one of illumina, nextera, smallrna");
-                    ch = u;
+                    ch = (char)(ch & 0xDF);
+                    if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') invalid(name, item, "a sequence over ACGT or one of illumina, nextera, smallrna");
                 }
-                if (seq.size() < prep_run.adapter_overlap || seq.size() > PFQ_ADAPTER_LEN_MAX)
-                    die(bad + "an adapter has from --adapter-overlap (" + std::to_string(prep_run.adapter_overlap) + ") to " + std::to_string(PFQ_ADAPTER_LEN_MAX) + " bases");
-                if (prep_run.adapters[set].size() == PFQ_ADAPTER_MAX) die(bad + "at most " + std::to_string(PFQ_ADAPTER_MAX) + " adapters per option");
-                prep_run.adapters[set].push_back(seq);
+                if (seq.size() < o.adapter_overlap || seq.size() > PFQ_ADAPTER_LEN_MAX)
+                    invalid(name, item, "an adapter has from --adapter-overlap (" + std::to_string(o.adapter_overlap) + ") to " + std::to_string(PFQ_ADAPTER_LEN_MAX) + " bases");
+                if (o.adapters[set].size() == PFQ_ADAPTER_MAX) invalid(name, item, "at most " + std::to_string(PFQ_ADAPTER_MAX) + " adapters per option");
+                o.adapters[set].push_back(seq);
             }
         }
-        // --mate-overlap O [--mate-overlap-errors E]: both mates of a fragment are cut at the insert length that the overlap of
-        // the mates gives (pfq.h "mate overlap"), whatever the adapter's sequence; INSERT_SIZES.tsv counts the fragments per length
-        if (a.val.count("mate-overlap-errors") && !a.val.count("mate-overlap")) die("error: '--mate-overlap-errors' needs '--mate-overlap <O>'");
-        if (a.val.count("mate-overlap")) {
-            if (!a.val.count("reads2") && !a.flags.count("interleaved"))
-                die("error: '--mate-overlap' needs '--reads2 <FILE>' or '--interleaved': it compares the two mates of a fragment");
-            prep_run.mate_overlap = number("mate-overlap", "30", 1, PFQ_OVERLAP_LEN_MAX, "an overlap of 1 to 512 bases");
-            prep_run.mate_overlap_errors = number("mate-overlap-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
-        }
-        // --mate-correct [--mate-correct-quality HI[,LO]]: where the mates disagree inside their overlap, a base of quality LO or less
-        // takes what the mate says if that one's quality is HI or more (pfq.h "mate correction"), before the steps above
-        if (mate_correct) {
-            const std::string v = opt(a, "mate-correct-quality", "30,14");
-            const std::string bad = "error: invalid value '" + v + "' for '--mate-correct-quality': HI[,LO], Phred qualities with 1 <= HI <= 93 and LO < HI (default 30,14)";
-            const size_t comma = v.find(',');
-            const std::string part[2] = {v.substr(0, comma), comma == std::string::npos ? std::string("14") : v.substr(comma + 1)};
-            uint32_t val[2] = {0, 0};
-            for (int i = 0; i < 2; ++i) {
-                char *end = nullptr;
-                errno = 0;
-                const unsigned long long x = strtoull(part[i].c_str(), &end, 10);
-                if (part[i].empty() || !isdigit((unsigned char)part[i][0]) || *end || errno || x > 93) die(bad);
-                val[i] = (uint32_t)x;
-            }
-            if (val[0] < 1 || val[1] >= val[0]) die(bad);
-            prep_run.mate_correct_high = val[0];
-            prep_run.mate_correct_low = val[1];
-        }
-        if (a.val.count("deplete")) {
-            const std::string list = a.val.at("deplete") + ",";  // (the parser joins a repeated option's values with ',')
-            for (size_t at = 0, end; (end = list.find(',', at)) != std::string::npos; at = end + 1) prep_run.deplete_dirs.push_back(list.substr(at, end - at));
-            if (prep_run.deplete_dirs.size() > PrepRun::DEPLETE_MAX)
-                die("error: '--deplete' given " + std::to_string(prep_run.deplete_dirs.size()) + " times, at most " + std::to_string(PrepRun::DEPLETE_MAX) +
-                    " screens (a directory name must not hold a ',')");
-            prep_run.deplete_threshold_typed = opt(a, "deplete-threshold", opt(a, "filter-threshold", "1.0"));
-            prep_run.deplete_threshold = a.val.count("deplete-threshold") ? to_f32(a.val.at("deplete-threshold"), "deplete-threshold") : threshold;
-            for (const std::string &dir : prep_run.deplete_dirs) {  // before any read is parsed, and before any device is used
-                FILE *f = fopen((dir + "/tree.bin").c_str(), "rb");
-                if (!f) die("error: invalid value '" + dir + "' for '--deplete': cannot read " + dir + "/tree.bin: " + strerror(errno));
-                fclose(f);
-            }
+    }
+    refuse_by_table(a, Stage::MATES);
+    // --mate-overlap O [--mate-overlap-errors E]: both mates of a fragment are cut at the insert length that the overlap of
+    // the mates gives (pfq.h "mate overlap"), whatever the adapter's sequence; INSERT_SIZES.tsv counts the fragments per length
+    if (has("mate-overlap")) {
+        o.mate_overlap = number("mate-overlap", "30", 1, PFQ_OVERLAP_LEN_MAX, "an overlap of 1 to 512 bases");
+        o.mate_overlap_errors = number("mate-overlap-errors", "10", 0, 50, "a percentage of mismatches from 0 to 50");
+    }
+    // --mate-correct [--mate-correct-quality HI[,LO]]: where the mates disagree inside their overlap, a base of quality LO or less
+    // takes what the mate says if that one's quality is HI or more (pfq.h "mate correction"), before the steps above
+    if (has("mate-correct")) {
+        const std::string v = opt(a, "mate-correct-quality", "30,14");
+        const size_t comma = v.find(',');
+        uint64_t high = 0, low = 14;
+        if (!strict_uint(v.substr(0, comma), 0, 93, high) || (comma != std::string::npos && !strict_uint(v.substr(comma + 1), 0, 93, low)) || high < 1 || low >= high)
+            invalid("mate-correct-quality", v, "HI[,LO], Phred qualities with 1 <= HI <= 93 and LO < HI (default 30,14)");
+        o.mate_correct_high = (uint32_t)high, o.mate_correct_low = (uint32_t)low;
+    }
+    // --deplete DIR [--deplete DIR2 ..] [--deplete-threshold T]: after the steps above every unit that hits one of the screens, a
+    // database each, at T (default: -f) is taken out before the classification (pfq.h "depletion")
+    if (has("deplete")) {
+        o.deplete_dirs = split_list(a.val.at("deplete"));  // (the parser joins a repeated option's values with ',')
+        if (o.deplete_dirs.size() > PrepRun::DEPLETE_MAX)
+            die("error: '--deplete' given " + std::to_string(o.deplete_dirs.size()) + " times, at most " + std::to_string(PrepRun::DEPLETE_MAX) +
+                " screens (a directory name must not hold a ',')");
+        o.deplete_threshold_typed = opt(a, "deplete-threshold", threshold_typed);
+        o.deplete_threshold = has("deplete-threshold") ? to_f32(a.val.at("deplete-threshold"), "deplete-threshold") : o.threshold;
+        for (const std::string &dir : o.deplete_dirs) {
+            FILE *f = fopen((dir + "/tree.bin").c_str(), "rb");
+            if (!f) invalid("deplete", dir, "cannot read " + dir + "/tree.bin: " + strerror(errno));
+            fclose(f);
         }
     }
     // --taxonomy FILE: every read (fragment) is also counted on the nodes of the user's taxonomy over the database's genomes
-    // (PFQ_WANT_HITS | PFQ_WANT_TAXA): TAXON_COUNTS.tsv; --taxon-reads: READ_TAXA.tsv, one line per record with hits.  The file is
-    // parsed and checked against tree.bin here, before any device is used.
-    const bool taxonomy = a.val.count("taxonomy") != 0;
-    const bool taxon_reads = a.flags.count("taxon-reads") != 0;
-    if (taxon_reads && !taxonomy) die("error: '--taxon-reads' needs '--taxonomy <FILE>'");
-    if (taxonomy) {
-        for (const char *other : {"shard-depth", "frame"})
-            if (a.val.count(other))
-                die(std::string("error: '--taxonomy' cannot be used with '--") + other + "'" +
-                    (other[0] == 's' ? ": a subtree shard sees only its own genomes, so the hit rows it would count are partial (not implemented)"
-                                     : ": frames do not combine with per-read post-stages"));
-        if (a.flags.count("device-parse")) die("error: '--device-parse' cannot be used with '--taxonomy': it serves runs that only count");
+    // (PFQ_WANT_HITS | PFQ_WANT_TAXA).  The file is parsed and checked against tree.bin here.
+    o.taxonomy = has("taxonomy"), o.taxon_reads = has("taxon-reads");
+    refuse_by_table(a, Stage::TAXONOMY);
+    if (o.taxonomy) {
+        o.taxonomy_file = a.val.at("taxonomy");
         const char *const *ids = nullptr;
         uint64_t n_ids = 0;
-        check(pfq_db_leaf_ids(db_path.c_str(), &ids, &n_ids));
+        check(pfq_db_leaf_ids(o.db_path.c_str(), &ids, &n_ids));
         pfq_taxonomy_file tf{};
-        check(pfq_taxonomy_read(a.val.at("taxonomy").c_str(), ids, n_ids, &tf));
+        check(pfq_taxonomy_read(o.taxonomy_file.c_str(), ids, n_ids, &tf));
     }
-    const bool per_read = filtering || scores || lca == 2 || lca_reads || abundance || coverage || taxonomy || sweep;  // the per-read hit lists are needed
-    const FmtOverride ov = to_fmt(opt(a, "format", "auto"));
+    o.format = to_fmt(opt(a, "format", "auto"));
     // paired-end reads: --reads2 (mates by record index across the two streams) or --interleaved (adjacent records); every
     // fragment is classified with PFQ_PAIRED, its set the union (--pair-mode either) or intersection (both) of its mates'
-    const bool interleaved = a.flags.count("interleaved") != 0, has_reads2 = a.val.count("reads2") != 0;
-    if (interleaved && has_reads2) die("error: the argument '--reads2 <READS2>' cannot be used with '--interleaved'");
-    const bool paired = interleaved || has_reads2;
+    o.interleaved = has("interleaved"), o.has_reads2 = has("reads2"), o.reads2 = opt(a, "reads2", "");
+    refuse_by_table(a, Stage::PAIRS);
     const std::string pair_mode = opt(a, "pair-mode", "either");
-    if (pair_mode != "either" && pair_mode != "both")
-        die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
-    if (a.val.count("pair-mode") && !paired) die("error: '--pair-mode' needs '--reads2' or '--interleaved'");
-
+    if (pair_mode != "either" && pair_mode != "both") die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
+    o.pair_both = pair_mode == "both";
+    refuse_by_table(a, Stage::PAIR_MODE);
     // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
     // the per-genome counts are combined by one RCCL all-reduce at the end.  The reference has one rayon pool instead
     // (main.rs:269-272); results do not depend on how the reads are dealt.
-    std::vector<int> devices;
-    {
-        std::string spec = opt(a, "devices", getenv("PFQ_DEVICES") ? getenv("PFQ_DEVICES") : "");
-        if (spec == "all") {
-            int n = 0;
-            check(pfq_device_count(&n));
-            for (int i = 0; i < n; ++i) devices.push_back(i);
-        } else if (!spec.empty()) {
-            size_t p0 = 0;
-            while (p0 <= spec.size()) {
-                size_t p1 = spec.find(',', p0);
-                if (p1 == std::string::npos) p1 = spec.size();
-                devices.push_back((int)to_u64(spec.substr(p0, p1 - p0), "devices"));
-                p0 = p1 + 1;
-            }
-        }
-        if (devices.empty()) devices.push_back(device_from_env());
+    const std::string devices = opt(a, "devices", getenv("PFQ_DEVICES") ? getenv("PFQ_DEVICES") : "");
+    if (devices == "all") {
+        int n = 0;
+        check(pfq_device_count(&n));
+        for (int i = 0; i < n; ++i) o.devices.push_back(i);
+    } else if (!devices.empty()) {
+        for (const std::string &item : split_list(devices)) o.devices.push_back((int)to_u64(item, "devices"));
     }
+    if (o.devices.empty()) o.devices.push_back(device_from_env());
     // --shard-depth D: the database is split into the subtree shards of its depth-E frontier (pfq_tree_open_subtree), E = D,
     // or the search depth when that is smaller (a shard cut below the pruning depth would put one pruned leaf into several
     // shards).  Shard i classifies EVERY read, on its own host thread; the shards' hits and counts are concatenated in
     // shard order.
-    const bool sharded = a.val.count("shard-depth") != 0;
-    uint64_t shard_depth = 0;
-    if (sharded) {
-        shard_depth = to_u64(a.val.at("shard-depth"), "shard-depth");
-        if (a.val.count("search-depth")) shard_depth = std::min(shard_depth, to_u64(a.val.at("search-depth"), "search-depth"));
+    o.pruned = has("search-depth"), o.search_depth = opt(a, "search-depth", "");
+    if ((o.sharded = has("shard-depth"))) {
+        o.shard_depth = to_u64(a.val.at("shard-depth"), "shard-depth");
+        if (o.pruned) o.shard_depth = std::min(o.shard_depth, to_u64(o.search_depth, "search-depth"));
     }
-    ServedDb db(db_path, devices, sharded, shard_depth);
-    if (coverage) db.set_coverage_precision(coverage_p);
+    return o;
+}
+
+// What preprocessing did and with which parameters: PREPROCESS.tsv, DEPLETION*.csv, INSERT_SIZES.tsv and one line on stderr
+void write_prep_report(const QueryOptions &o, const PrepRun &pr, const std::vector<std::unique_ptr<ServedDb>> &screens) {
+    const auto n = [](const std::atomic<uint64_t> &x) { return (unsigned long long)x.load(); };
+    // PREPROCESS.tsv: the totals over all calls and replicas, then the parameters in force
+    const std::string max_n = o.params.max_n == 0xffffffffu ? "off" : std::to_string(o.params.max_n);
+    const std::pair<const char *, std::string> rows[] = {
+        {"reads", std::to_string(n(pr.reads))}, {"reads_kept", std::to_string(n(pr.kept))}, {"reads_trimmed", std::to_string(n(pr.trimmed))},
+        {"dropped_short", std::to_string(n(pr.reason[PFQ_PREP_SHORT]))}, {"dropped_n", std::to_string(n(pr.reason[PFQ_PREP_N]))},
+        {"dropped_complexity", std::to_string(n(pr.reason[PFQ_PREP_COMPLEXITY]))}, {"dropped_mate", std::to_string(n(pr.reason[PFQ_PREP_MATE]))},
+        {"bases", std::to_string(n(pr.bases))}, {"bases_kept", std::to_string(n(pr.bases_kept))},
+        {"trim_quality", std::to_string(o.params.trim_quality)}, {"trim_window", std::to_string(o.params.trim_window)},
+        {"trim_poly_x", std::to_string(o.params.poly_x)}, {"min_length", std::to_string(o.params.min_length)}, {"max_n", max_n},
+        {"min_complexity", std::to_string(o.params.min_complexity)}};
+    FILE *f = fopen((o.out + "/PREPROCESS.tsv").c_str(), "wb");
+    if (!f) die("cannot create PREPROCESS.tsv in " + o.out);
+    for (const auto &row : rows) fprintf(f, "%s\t%s\n", row.first, row.second.c_str());
+    if (o.adapters_on()) {  // behind the rows above: what the adapter step found, its parameters, the reads per adapter
+        fprintf(f, "adapter_reads\t%llu\nadapter_bases\t%llu\nadapter_overlap\t%u\nadapter_errors\t%u\n", n(pr.adapter_reads), n(pr.adapter_bases), o.adapter_overlap,
+                o.adapter_errors);
+        for (int set = 0; set < 2; ++set)
+            for (size_t i = 0; i < o.adapters[set].size(); ++i)
+                fprintf(f, "adapter%d.%s\t%llu\n", set + 1, o.adapters[set][i].c_str(), n(pr.adapter_found[set * PFQ_ADAPTER_MAX + i]));
+    }
+    if (o.mate_overlap) {  // behind the adapter rows: what the overlap step found and its parameters
+        fprintf(f, "overlap_fragments\t%llu\noverlap_skipped\t%llu\noverlap_found\t%llu\noverlap_readthrough\t%llu\noverlap_reads\t%llu\noverlap_bases\t%llu\n",
+                n(pr.overlap_fragments), n(pr.overlap_skipped), n(pr.overlap_found), n(pr.overlap_readthrough), n(pr.overlap_reads), n(pr.overlap_bases));
+        fprintf(f, "mate_overlap\t%u\nmate_overlap_errors\t%u\n", o.mate_overlap, o.mate_overlap_errors);
+    }
+    if (o.mate_correct_high)  // behind the overlap rows: what the correction did and its parameters
+        fprintf(f, "corrected_fragments\t%llu\ncorrected_bases\t%llu\ncorrect_unresolved\t%llu\ncorrect_no_quality\t%llu\nmate_correct_quality\t%u\nmate_correct_low\t%u\n",
+                n(pr.corrected_fragments), n(pr.corrected_bases), n(pr.correct_unresolved), n(pr.correct_no_quality), o.mate_correct_high, o.mate_correct_low);
+    for (size_t i = 0; i < o.deplete_dirs.size(); ++i)  // behind the overlap rows: per screen, in the order given
+        fprintf(f, "deplete_db\t%s\ndeplete_threshold\t%s\ndepleted_units\t%llu\ndepleted_reads\t%llu\ndepleted_bases\t%llu\n", o.deplete_dirs[i].c_str(),
+                o.deplete_threshold_typed.c_str(), n(pr.depleted_units[i]), n(pr.depleted_reads[i]), n(pr.depleted_bases[i]));
+    if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
+    // DEPLETION.csv (several screens: DEPLETION_1.csv ..): what CLASSIFICATION.csv of a run of the block screen i saw against
+    // that screen would hold; the replicas' counters are summed as the main database's are
+    for (size_t i = 0; i < screens.size(); ++i)
+        screens[i]->save_counts(o.out + (screens.size() == 1 ? std::string("/DEPLETION.csv") : "/DEPLETION_" + std::to_string(i + 1) + ".csv"));
+    if (o.mate_overlap) {
+        // INSERT_SIZES.tsv: the fragments per insert length, summed over all calls and replicas
+        FILE *g = fopen((o.out + "/INSERT_SIZES.tsv").c_str(), "wb");
+        if (!g) die("cannot create INSERT_SIZES.tsv in " + o.out);
+        fprintf(g, "insert\tfragments\n");
+        for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
+            if (n(pr.insert_hist[i])) fprintf(g, "%d\t%llu\n", i, n(pr.insert_hist[i]));
+        if (fclose(g) != 0) die("short write to INSERT_SIZES.tsv");
+    }
+    fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept",
+            n(pr.reads), n(pr.kept), n(pr.trimmed), n(pr.reason[PFQ_PREP_SHORT]), n(pr.reason[PFQ_PREP_N]), n(pr.reason[PFQ_PREP_COMPLEXITY]),
+            n(pr.reason[PFQ_PREP_MATE]), n(pr.bases_kept), n(pr.bases));
+    if (o.adapters_on()) fprintf(stderr, "; adapters cut from %llu reads (%llu bases)", n(pr.adapter_reads), n(pr.adapter_bases));
+    if (o.mate_overlap)
+        fprintf(stderr, "; mates overlap in %llu of %llu fragments, %llu with read-through: %llu reads cut (%llu bases)", n(pr.overlap_found), n(pr.overlap_fragments),
+                n(pr.overlap_readthrough), n(pr.overlap_reads), n(pr.overlap_bases));
+    if (o.mate_correct_high)
+        fprintf(stderr, "; %llu bases corrected in %llu fragments (%llu mismatches unresolved, %llu fragments without qualities)", n(pr.corrected_bases),
+                n(pr.corrected_fragments), n(pr.correct_unresolved), n(pr.correct_no_quality));
+    for (size_t i = 0; i < o.deplete_dirs.size(); ++i)
+        fprintf(stderr, "; screen %s took %llu reads (%llu bases)", o.deplete_dirs[i].c_str(), n(pr.depleted_reads[i]), n(pr.depleted_bases[i]));
+    fprintf(stderr, "\n");
+}
+
+int cmd_query(int argc, char **argv) {
+    std::vector<Opt> opts = {{"reads", 'r', true}, {"out", 'o', true}, {"db-path", 'd', true}, {"threads", 't', true}, {"block-size-reads", 'b', true},
+                             {"filter-threshold", 'f', true}, {"cache-size", 'c', true}, {"search-depth", 0, true}, {"pos-filter", 0, false}, {"neg-filter", 0, false},
+                             {"format", 'F', true}, {"devices", 0, true}, {"shard-depth", 0, true}, {"scores", 0, false}, {"reads2", 0, true}, {"interleaved", 0, false},
+                             {"pair-mode", 0, true}, {"lca", 0, true}, {"lca-reads", 0, false}, {"abundance", 0, false}, {"abundance-iters", 0, true},
+                             {"coverage", 0, false}, {"coverage-precision", 0, true}, {"frame", 0, true}, {"frame-step", 0, true}, {"device-parse", 0, false},
+                             {"device-inflate", 0, false}, {"device-output", 0, false}, {"taxonomy", 0, true}, {"taxon-reads", 0, false}, {"best-hits", 0, false},
+                             {"sweep", 0, true}, {"trim-quality", 0, true}, {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true},
+                             {"max-n", 0, true}, {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
+                             {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}, {"deplete", 0, true, true},
+                             {"deplete-threshold", 0, true}, {"mate-correct", 0, false}, {"mate-correct-quality", 0, true}};
+    QueryOptions o = parse_query_options(parse(argc, argv, 2, opts));
+    ServedDb db(o.db_path, o.devices, o.sharded, o.shard_depth);
+    if (o.coverage) db.set_coverage_precision(o.coverage_precision);
     printf("Querying reads...\n");
-    printf("Filtering settings: positive=%s; negative=%s\n", pos ? "true" : "false", neg ? "true" : "false");
-    if (a.val.count("search-depth")) {
-        uint64_t depth = to_u64(a.val.at("search-depth"), "search-depth");
-        if (!filtering) printf("If using a search depth, use a filtering flag (--pos-filter or --neg-filter, or both!)\n");
+    printf("Filtering settings: positive=%s; negative=%s\n", o.pos ? "true" : "false", o.neg ? "true" : "false");
+    if (o.pruned) {
+        uint64_t depth = to_u64(o.search_depth, "search-depth");
+        if (!o.pos && !o.neg) printf("If using a search depth, use a filtering flag (--pos-filter or --neg-filter, or both!)\n");
         printf("Search depth settings: %llu\n", (unsigned long long)depth);
         db.prune(depth);
     }
-    if (sweep) db.set_sweep(sweep_thr);  // (before any read is classified: a database that is not superset-verified is refused here)
-    if (prep_run.adapters_on()) {  // every replica cuts the reads of its own calls
+    if (o.sweep) db.set_sweep(o.sweep_thr);  // (before any read is classified: a database that is not superset-verified is refused here)
+    if (o.adapters_on()) {                   // every replica cuts the reads of its own calls
         std::vector<const char *> sets[2];
         for (int set = 0; set < 2; ++set)
-            for (const std::string &s : prep_run.adapters[set]) sets[set].push_back(s.c_str());
+            for (const std::string &s : o.adapters[set]) sets[set].push_back(s.c_str());
         for (pfq_tree *tree : db.trees)
-            check(pfq_tree_set_adapters(tree, sets[0].data(), (uint32_t)sets[0].size(), sets[1].data(), (uint32_t)sets[1].size(), prep_run.adapter_overlap,
-                                        prep_run.adapter_errors));
+            check(pfq_tree_set_adapters(tree, sets[0].data(), (uint32_t)sets[0].size(), sets[1].data(), (uint32_t)sets[1].size(), o.adapter_overlap, o.adapter_errors));
     }
-    if (prep_run.mate_overlap)
-        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_overlap(tree, prep_run.mate_overlap, prep_run.mate_overlap_errors));
-    if (prep_run.mate_correct_high)
-        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_correct(tree, prep_run.mate_correct_high, prep_run.mate_correct_low));
+    if (o.mate_overlap)
+        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_overlap(tree, o.mate_overlap, o.mate_overlap_errors));
+    if (o.mate_correct_high)
+        for (pfq_tree *tree : db.trees) check(pfq_tree_set_mate_correct(tree, o.mate_correct_high, o.mate_correct_low));
     // --deplete: every replica gets its own copy of every screen on its device (the screens' memory once per replica)
+    PrepRun prep;
     std::vector<std::unique_ptr<ServedDb>> screens;
-    for (const std::string &dir : prep_run.deplete_dirs) {
-        screens.emplace_back(new ServedDb(dir, devices, false, 0));
-        for (size_t i = 0; i < db.trees.size(); ++i) prep_run.screens_of[db.trees[i]].push_back(screens.back()->trees[i]);
+    for (const std::string &dir : o.deplete_dirs) {
+        screens.emplace_back(new ServedDb(dir, o.devices, false, 0));
+        for (size_t i = 0; i < db.trees.size(); ++i) prep.screens_of[db.trees[i]].push_back(screens.back()->trees[i]);
     }
-    ReadQueue rq(reads, ov);
+    ReadQueue rq(o.reads, o.format);
     std::unique_ptr<ReadQueue> rq2;
-    if (has_reads2) rq2.reset(new ReadQueue(a.val.at("reads2"), ov));
+    if (o.has_reads2) rq2.reset(new ReadQueue(o.reads2, o.format));
     // Page-locking costs ~1.7 s per GB here (hipHostMalloc), the pageable copy ~0.1 s per GB: pinned buffers only
     // pay off once every pooled buffer has been reused a few dozen times (inputs of >~ 10^9 reads).  Opt-in.
     g_pinned = getenv("PFQ_PINNED") && atoi(getenv("PFQ_PINNED")) != 0;
+    rq.device_parse = o.device_parse || o.device_output;
+    rq.device_inflate = o.device_inflate;
     // --block-size-reads 0: the reference's first block is empty (file_parser.rs:252-270: `0 > read_block.len()` is false),
     // so its loop (main.rs:334-368) never runs: no read is parsed or classified, the outputs are created empty
-    rq.device_parse = device_parse || device_output;
-    rq.device_inflate = device_inflate;
     // (paired: the mates' ids are compared; framed: SEGMENTS.tsv names the sequences; preprocessing: the qualities go to the device)
-    if (block != 0) rq.start(per_read || paired || framed || prep_run.on, threads);
-    if (block != 0 && rq2) rq2->start(true, threads);
+    if (o.block != 0) rq.start(o.per_read() || o.paired() || o.frame || o.prep, o.threads);
+    if (o.block != 0 && rq2) rq2->start(true, o.threads);
 
     // create_and_overwrite_directory (main.rs:380-391): an existing output directory is deleted
     struct stat st;
-    if (stat(out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(out);
-    mkdir(out.c_str(), 0777);
-    Outputs outs(out, rq.peek_format() == Fmt::Fastq ? "fq" : "fa", pos, neg, has_reads2, scores, lca_reads, taxon_reads);
+    if (stat(o.out.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) rm_rf(o.out);
+    mkdir(o.out.c_str(), 0777);
+    Outputs outs(o, rq.peek_format() == Fmt::Fastq ? "fq" : "fa");
     uint64_t kmer_size = 0;
-    if (scores || framed || prep_run.on) {
+    if (o.scores || o.frame || o.prep) {
         pfq_info info{};
         check(pfq_tree_info(db.trees[0], &info));
         kmer_size = info.kmer_size;
     }
-    if (prep_run.on && !a.val.count("min-length")) prep_run.params.min_length = (uint32_t)kmer_size;
-    if (framed && frame < kmer_size)
-        die("error: '--frame " + std::to_string(frame) + "' is shorter than the database's k-mers (k = " + std::to_string(kmer_size) + "): a frame must hold one");
+    if (o.prep && !o.params.min_length) o.params.min_length = (uint32_t)kmer_size;
+    if (o.frame && o.frame < kmer_size)
+        die("error: '--frame " + std::to_string(o.frame) + "' is shorter than the database's k-mers (k = " + std::to_string(kmer_size) + "): a frame must hold one");
     db.load_leaf_names();
-    if (lca_reads) db.load_clade_names();
-    if (taxonomy) db.set_taxonomy(a.val.at("taxonomy"));
+    if (o.lca_reads) db.load_clade_names();
+    if (o.taxonomy) db.set_taxonomy(o.taxonomy_file);
 
     const uint64_t t_loop0 = ReadQueue::now_ns();
-    QueryLoop q{db, rq, outs, threshold, block, pos, neg, scores, threads, kmer_size, lca, lca_reads, abundance, coverage, taxonomy, taxon_reads, best_hits, sweep, &prep_run};
-    if (block == 0) {
+    QueryLoop q{db, rq, outs, o, prep, kmer_size};
+    if (o.block == 0) {
         // nothing to do: see above
-    } else if (framed) {
-        q.frames(frame, frame_step, out + "/SEGMENTS.tsv");
-    } else if (paired) {
-        q.paired(rq2.get(), pair_mode == "both");
-    } else if (device_parse) {
+    } else if (o.frame) {
+        q.frames(o.frame, o.frame_step, o.out + "/SEGMENTS.tsv");
+    } else if (o.paired()) {
+        q.paired(rq2.get(), o.pair_both);
+    } else if (o.device_parse) {
         q.counts_only_text();
-    } else if (device_output) {
+    } else if (o.device_output) {
         q.device_output();
-    } else if (!per_read) {
+    } else if (!o.per_read()) {
         q.counts_only();
     } else {
         q.per_read();
@@ -3299,12 +3368,12 @@ int cmd_query(int argc, char **argv) {
     if (getenv("PFQ_INGEST_TIMING")) {
         const double wall = (ReadQueue::now_ns() - t_loop0) * 1e-9;
         fprintf(stderr, "query loop: %llu reads in %.3f s = %.2f M reads/s on %zu device(s) (pfq_query_batch %.3f s, output %.3f s)\n",
-                (unsigned long long)q.n_total.load(), wall, q.n_total.load() / wall * 1e-6, devices.size(), q.ns_gpu.load() * 1e-9,
+                (unsigned long long)q.n_total.load(), wall, q.n_total.load() / wall * 1e-6, o.devices.size(), q.ns_gpu.load() * 1e-9,
                 q.ns_out.load() * 1e-9);
         rq.report_timing();
-        if (device_parse || device_output) q.report_device_parse();
-        if (device_inflate) q.report_device_inflate();
-        if (device_output) q.report_device_output();
+        if (o.device_parse || o.device_output) q.report_device_parse();
+        if (o.device_inflate) q.report_device_inflate();
+        if (o.device_output) q.report_device_output();
         struct rusage ru;
         if (getrusage(RUSAGE_SELF, &ru) == 0)
             fprintf(stderr, "cpu: user %.2f s + system %.2f s so far (all threads) for %.2f s of query loop\n",
@@ -3312,82 +3381,13 @@ int cmd_query(int argc, char **argv) {
     }
     outs.close();
     if (!rq.pending_error.empty()) die(rq.pending_error);  // the reads before the malformed record were processed
-    db.save_counts(out + "/CLASSIFICATION.csv");
-    if (lca) db.save_clade_counts(out + "/CLADE_COUNTS.tsv");
-    if (abundance) db.save_abundance(out + "/ABUNDANCE.tsv", (uint32_t)abundance_iters);
-    if (coverage) db.save_coverage(out + "/COVERAGE.tsv");
-    if (taxonomy) db.save_taxon_counts(out + "/TAXON_COUNTS.tsv", abundance, (uint32_t)abundance_iters);
-    if (sweep) db.save_sweep(out, sweep_typed);
-    if (prep_run.on) {
-        // PREPROCESS.tsv: the totals over all calls and replicas, then the parameters in force
-        const PrepRun &pr = prep_run;
-        const std::string max_n = pr.params.max_n == 0xffffffffu ? "off" : std::to_string(pr.params.max_n);
-        const std::pair<const char *, std::string> rows[] = {
-            {"reads", std::to_string(pr.reads.load())}, {"reads_kept", std::to_string(pr.kept.load())}, {"reads_trimmed", std::to_string(pr.trimmed.load())},
-            {"dropped_short", std::to_string(pr.reason[PFQ_PREP_SHORT].load())}, {"dropped_n", std::to_string(pr.reason[PFQ_PREP_N].load())},
-            {"dropped_complexity", std::to_string(pr.reason[PFQ_PREP_COMPLEXITY].load())}, {"dropped_mate", std::to_string(pr.reason[PFQ_PREP_MATE].load())},
-            {"bases", std::to_string(pr.bases.load())}, {"bases_kept", std::to_string(pr.bases_kept.load())},
-            {"trim_quality", std::to_string(pr.params.trim_quality)}, {"trim_window", std::to_string(pr.params.trim_window)},
-            {"trim_poly_x", std::to_string(pr.params.poly_x)}, {"min_length", std::to_string(pr.params.min_length)}, {"max_n", max_n},
-            {"min_complexity", std::to_string(pr.params.min_complexity)}};
-        FILE *f = fopen((out + "/PREPROCESS.tsv").c_str(), "wb");
-        if (!f) die("cannot create PREPROCESS.tsv in " + out);
-        for (const auto &row : rows) fprintf(f, "%s\t%s\n", row.first, row.second.c_str());
-        if (pr.adapters_on()) {  // behind the rows above: what the adapter step found, its parameters, the reads per adapter
-            fprintf(f, "adapter_reads\t%llu\nadapter_bases\t%llu\nadapter_overlap\t%u\nadapter_errors\t%u\n", (unsigned long long)pr.adapter_reads.load(),
-                    (unsigned long long)pr.adapter_bases.load(), pr.adapter_overlap, pr.adapter_errors);
-            for (int set = 0; set < 2; ++set)
-                for (size_t i = 0; i < pr.adapters[set].size(); ++i)
-                    fprintf(f, "adapter%d.%s\t%llu\n", set + 1, pr.adapters[set][i].c_str(), (unsigned long long)pr.adapter_found[set * PFQ_ADAPTER_MAX + i].load());
-        }
-        if (pr.mate_overlap) {  // behind the adapter rows: what the overlap step found and its parameters
-            fprintf(f, "overlap_fragments\t%llu\noverlap_skipped\t%llu\noverlap_found\t%llu\noverlap_readthrough\t%llu\noverlap_reads\t%llu\noverlap_bases\t%llu\n",
-                    (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_skipped.load(), (unsigned long long)pr.overlap_found.load(),
-                    (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(), (unsigned long long)pr.overlap_bases.load());
-            fprintf(f, "mate_overlap\t%u\nmate_overlap_errors\t%u\n", pr.mate_overlap, pr.mate_overlap_errors);
-        }
-        if (pr.mate_correct_high)  // behind the overlap rows: what the correction did and its parameters
-            fprintf(f, "corrected_fragments\t%llu\ncorrected_bases\t%llu\ncorrect_unresolved\t%llu\ncorrect_no_quality\t%llu\nmate_correct_quality\t%u\nmate_correct_low\t%u\n",
-                    (unsigned long long)pr.corrected_fragments.load(), (unsigned long long)pr.corrected_bases.load(), (unsigned long long)pr.correct_unresolved.load(),
-                    (unsigned long long)pr.correct_no_quality.load(), pr.mate_correct_high, pr.mate_correct_low);
-        for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)  // behind the overlap rows: per screen, in the order given
-            fprintf(f, "deplete_db\t%s\ndeplete_threshold\t%s\ndepleted_units\t%llu\ndepleted_reads\t%llu\ndepleted_bases\t%llu\n", pr.deplete_dirs[i].c_str(),
-                    pr.deplete_threshold_typed.c_str(), (unsigned long long)pr.depleted_units[i].load(), (unsigned long long)pr.depleted_reads[i].load(),
-                    (unsigned long long)pr.depleted_bases[i].load());
-        if (fclose(f) != 0) die("short write to PREPROCESS.tsv");
-        // DEPLETION.csv (several screens: DEPLETION_1.csv ..): what CLASSIFICATION.csv of a run of the block screen i saw against
-        // that screen would hold; the replicas' counters are summed as the main database's are
-        for (size_t i = 0; i < screens.size(); ++i)
-            screens[i]->save_counts(out + (screens.size() == 1 ? std::string("/DEPLETION.csv") : "/DEPLETION_" + std::to_string(i + 1) + ".csv"));
-        if (pr.mate_overlap) {
-            // INSERT_SIZES.tsv: the fragments per insert length, summed over all calls and replicas
-            FILE *g = fopen((out + "/INSERT_SIZES.tsv").c_str(), "wb");
-            if (!g) die("cannot create INSERT_SIZES.tsv in " + out);
-            fprintf(g, "insert\tfragments\n");
-            for (int i = 0; i <= PFQ_OVERLAP_INSERT_MAX; ++i)
-                if (pr.insert_hist[i].load()) fprintf(g, "%d\t%llu\n", i, (unsigned long long)pr.insert_hist[i].load());
-            if (fclose(g) != 0) die("short write to INSERT_SIZES.tsv");
-        }
-        fprintf(stderr, "preprocessing: %llu reads, %llu kept (%llu trimmed), dropped: %llu short, %llu N, %llu low complexity, %llu mate; %llu of %llu bases kept",
-                (unsigned long long)pr.reads.load(), (unsigned long long)pr.kept.load(), (unsigned long long)pr.trimmed.load(),
-                (unsigned long long)pr.reason[PFQ_PREP_SHORT].load(), (unsigned long long)pr.reason[PFQ_PREP_N].load(),
-                (unsigned long long)pr.reason[PFQ_PREP_COMPLEXITY].load(), (unsigned long long)pr.reason[PFQ_PREP_MATE].load(),
-                (unsigned long long)pr.bases_kept.load(), (unsigned long long)pr.bases.load());
-        if (pr.adapters_on())
-            fprintf(stderr, "; adapters cut from %llu reads (%llu bases)", (unsigned long long)pr.adapter_reads.load(), (unsigned long long)pr.adapter_bases.load());
-        if (pr.mate_overlap)
-            fprintf(stderr, "; mates overlap in %llu of %llu fragments, %llu with read-through: %llu reads cut (%llu bases)", (unsigned long long)pr.overlap_found.load(),
-                    (unsigned long long)pr.overlap_fragments.load(), (unsigned long long)pr.overlap_readthrough.load(), (unsigned long long)pr.overlap_reads.load(),
-                    (unsigned long long)pr.overlap_bases.load());
-        if (pr.mate_correct_high)
-            fprintf(stderr, "; %llu bases corrected in %llu fragments (%llu mismatches unresolved, %llu fragments without qualities)",
-                    (unsigned long long)pr.corrected_bases.load(), (unsigned long long)pr.corrected_fragments.load(), (unsigned long long)pr.correct_unresolved.load(),
-                    (unsigned long long)pr.correct_no_quality.load());
-        for (size_t i = 0; i < pr.deplete_dirs.size(); ++i)
-            fprintf(stderr, "; screen %s took %llu reads (%llu bases)", pr.deplete_dirs[i].c_str(), (unsigned long long)pr.depleted_reads[i].load(),
-                    (unsigned long long)pr.depleted_bases[i].load());
-        fprintf(stderr, "\n");
-    }
+    db.save_counts(o.out + "/CLASSIFICATION.csv");
+    if (o.lca) db.save_clade_counts(o.out + "/CLADE_COUNTS.tsv");
+    if (o.abundance) db.save_abundance(o.out + "/ABUNDANCE.tsv", (uint32_t)o.abundance_iters);
+    if (o.coverage) db.save_coverage(o.out + "/COVERAGE.tsv");
+    if (o.taxonomy) db.save_taxon_counts(o.out + "/TAXON_COUNTS.tsv", o.abundance, (uint32_t)o.abundance_iters);
+    if (o.sweep) db.save_sweep(o.out, o.sweep_typed);
+    if (o.prep) write_prep_report(o, prep, screens);
     db.close();
     printf("Finished.\n");
     return 0;
