@@ -693,6 +693,43 @@ typedef struct pfq_text_records {
 int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out);
 int pfq_debug_last_format(pfq_tree *tree, double *ms /* [3]: ids + blocks, sizes + scans, emit; HIP events */);
 
+/* ---- blocked gzip written on the device (pfq_bgzf_deflate, pfq_text_format_gz) ----
+ * Text deflated where it lies, into members of blocked gzip that every gzip reader, every htslib tool and pfq_text_inflate take.
+ * Cutting (a pure function of len and the cuts): a stream of len bytes with n_cuts ascending offsets 0 <= cuts[0] <= .. <=
+ *   cuts[n_cuts - 1] <= len has the n_cuts + 1 pieces [0, cuts[0]), [cuts[0], cuts[1]), .., [cuts[n_cuts - 1], len).  Every piece is
+ *   cut from its first byte into members of PFQ_BGZF_MEMBER_TEXT text bytes, the last one shorter; an empty piece has no member.
+ *   The 28-byte end marker is never written: it belongs to the end of a file, which only the caller knows.
+ * Bytes of a member: a pure function of the member's text, stated rule by rule at the head of phagefilter_amd/csrc/
+ *   pfq_deflate_core.h (tiles of 256 positions, a hash of 4 bytes into 2^13 entries plus the distance-1 candidate, a greedy
+ *   parse, one dynamic block from the member's own counts limited to 15 bits, or one stored block where that is not smaller), so
+ *   the device's bytes are those of the stand-alone host program tools/deflate_host.cpp, whatever the grid.  A member is at most
+ *   its text + 31 bytes.  There are no levels.
+ * pfq_bgzf_deflate: text[0, len) goes to the device on the tree's copy stream, is cut, deflated (one workgroup a member; the grid
+ *   is min(members, PFQ_DEFLATE_BLOCKS), unset: one workgroup a compute unit, what their LDS admits) and gathered, and the members
+ *   come back, piece after piece, in gz.  piece_begin [n_pieces + 1] and member_begin [n_members + 1] are offsets into gz.
+ *   PFQ_ERR_ARG: tree or out NULL, text NULL with len > 0, cuts NULL with n_cuts > 0, cuts not ascending or beyond len;
+ *   PFQ_ERR_UNSUPPORTED: len >= 2^31.
+ * pfq_text_format_gz: exactly pfq_text_format for the same arguments — the same preconditions, errors, counts and left runs —
+ *   except that the two plain streams stay on the device: out->pos and out->neg are NULL, and each stream that flags asks for is
+ *   deflated where it lies, cut at left[0].pos_at, .., left[n_left - 1].pos_at (neg_at for the other): piece j of pos_gz is what the
+ *   caller writes between its own bytes for left run j - 1 and for left run j, n_left + 1 pieces in all, empty ones without a member.
+ *   A later pfq_text_format gives what it would have given.
+ * Both change no counter, result or parsed block, wait for their own work, and leave results (library-owned, gz page-locked) that
+ * are valid until the tree's next call of either; pfq_info.device_bytes counts the buffers.
+ * pfq_debug_last_deflate: device milliseconds of the tree's last deflate that had members (of pfq_text_format_gz: its last
+ *   stream), by HIP events: ms[0] the copy to the device (pfq_text_format_gz: none), ms[1] the deflate kernel, ms[2] scan, gather
+ *   and the copy back.  PFQ_ERR_STATE without one. */
+#define PFQ_BGZF_MEMBER_TEXT 65280
+typedef struct pfq_bgzf {
+    const uint8_t *gz;            /* the members back to back */
+    uint64_t gz_bytes, n_members, n_pieces;
+    const uint64_t *piece_begin;  /* [n_pieces + 1] */
+    const uint64_t *member_begin; /* [n_members + 1] */
+} pfq_bgzf;
+int pfq_bgzf_deflate(pfq_tree *tree, const uint8_t *text, uint64_t len, const uint64_t *cuts, uint64_t n_cuts, pfq_bgzf *out);
+int pfq_text_format_gz(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out, pfq_bgzf *pos_gz, pfq_bgzf *neg_gz);
+int pfq_debug_last_deflate(pfq_tree *tree, double *ms /* [3] */);
+
 /* ---- read preprocessing (pfq_prep_reads, pfq_prep_query) ----
  * What a trimmer in front of a classifier does — low-quality and poly-X tails cut, reads that are too short, mostly N or of
  * low complexity dropped — on the device, into the block a query call takes.  Integers only; the result for a read is a pure

@@ -22,6 +22,7 @@ SYMBOLS = [
     "pfq_query_frames", "pfq_query_frames_device",
     "pfq_text_parse", "pfq_text_query", "pfq_debug_text_csr", "pfq_text_format", "pfq_debug_last_format",
     "pfq_gz_scan", "pfq_text_inflate", "pfq_text_parse_inflated", "pfq_text_read", "pfq_debug_last_inflate",
+    "pfq_bgzf_deflate", "pfq_text_format_gz", "pfq_debug_last_deflate",
     "pfq_prep_reads", "pfq_prep_query", "pfq_debug_prep_csr", "pfq_debug_last_prep",
     "pfq_tree_set_adapters", "pfq_prep_last_adapters", "pfq_debug_last_adapters",
     "pfq_tree_set_mate_overlap", "pfq_prep_last_overlap", "pfq_debug_last_overlap",
@@ -139,6 +140,11 @@ class TextRecords(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("pos_records", C.c_uint64), ("neg_records", C.c_uint64),
                 ("pos_bytes", C.c_uint64), ("neg_bytes", C.c_uint64), ("pos", C.POINTER(C.c_uint8)), ("neg", C.POINTER(C.c_uint8)),
                 ("n_left", C.c_uint64), ("left", C.POINTER(TextLeft))]
+
+
+class Bgzf(C.Structure):
+    _fields_ = [("gz", C.POINTER(C.c_uint8)), ("gz_bytes", C.c_uint64), ("n_members", C.c_uint64), ("n_pieces", C.c_uint64),
+                ("piece_begin", C.POINTER(C.c_uint64)), ("member_begin", C.POINTER(C.c_uint64))]
 
 
 class PrepParams(C.Structure):
@@ -302,6 +308,9 @@ def lib() -> C.CDLL:
     L.pfq_text_parse_inflated.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(Text)]
     L.pfq_text_read.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
     L.pfq_debug_last_inflate.argtypes = [vp, C.POINTER(C.c_double)]
+    L.pfq_bgzf_deflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(Bgzf)]
+    L.pfq_text_format_gz.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(TextRecords), C.POINTER(Bgzf), C.POINTER(Bgzf)]
+    L.pfq_debug_last_deflate.argtypes = [vp, C.POINTER(C.c_double)]
     L.pfq_prep_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(PrepParams), C.POINTER(Prep)]
     L.pfq_prep_query.argtypes = [vp, C.c_float, C.c_uint32, C.POINTER(Hits)]
     L.pfq_debug_prep_csr.argtypes = [vp, vp, vp]

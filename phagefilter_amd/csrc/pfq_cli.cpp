@@ -1463,6 +1463,8 @@ struct QueryOptions {
     std::vector<std::string> sweep_typed;
     uint32_t frame = 0, frame_step = 0;  // --frame F [--frame-step S] (frame 0: whole sequences): SEGMENTS.tsv
     bool device_parse = false, device_inflate = false, device_output = false;
+    bool gzip_output = false;  // --gzip-output [--gzip-level L]: the POS / NEG files are blocked gzip (BGZF)
+    int gzip_level = 6;        // zlib's, for the members the host makes
     bool has_reads2 = false, interleaved = false, pair_both = false;  // --reads2, --interleaved, --pair-mode both
     std::vector<int> devices;                     // --devices or PFQ_DEVICES, else the one of PFQ_DEVICE
     bool sharded = false, pruned = false;         // --shard-depth D, already lowered to the search depth; --search-depth, as typed: it is
@@ -1485,14 +1487,56 @@ struct QueryOptions {
     }
 };
 
-// A POS/NEG file and the bytes written to it so far (the formatters' parts are written at computed offsets)
+// One member of blocked gzip (BGZF) made with zlib: text[0, n), n <= BGZF_TEXT, into member (BGZF_ROOM bytes); returns its size.
+// The empty text at a level above 0 is the 28-byte end marker every reader knows, byte for byte.
+constexpr size_t BGZF_TEXT = 65280, BGZF_ROOM = 65536 + 1024;
+size_t bgzf_member(const unsigned char *text, size_t n, int level, unsigned char *member) {
+    z_stream z{};
+    if (deflateInit2(&z, n ? level : 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) die("zlib: deflateInit2 failed");
+    z.next_in = const_cast<unsigned char *>(text);
+    z.avail_in = (uInt)n;
+    z.next_out = member + 18;
+    z.avail_out = (uInt)(BGZF_ROOM - 18 - 8);
+    if (deflate(&z, Z_FINISH) != Z_STREAM_END) die("zlib: deflate did not finish a member");
+    const size_t pay = z.total_out, size = 18 + pay + 8;
+    deflateEnd(&z);
+    if (size > 65536) die("bgzf: a member of more than 64 KiB");  // (cannot happen: 65 280 bytes stored are 65 290)
+    const unsigned char head[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (unsigned char)((size - 1) & 0xff), (unsigned char)((size - 1) >> 8)};
+    memcpy(member, head, 18);
+    const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), text, (uInt)n), isize = (uint32_t)n;
+    for (int i = 0; i < 4; ++i) {
+        member[18 + pay + i] = (unsigned char)(crc >> (8 * i));
+        member[18 + pay + 4 + i] = (unsigned char)(isize >> (8 * i));
+    }
+    return size;
+}
+// text[0, n) as members of at most BGZF_TEXT text bytes, appended to gz
+void bgzf_pack(const char *text, size_t n, int level, std::vector<unsigned char> &gz) {
+    for (size_t at = 0; at < n; at += BGZF_TEXT) {
+        const size_t have = gz.size();
+        gz.resize(have + BGZF_ROOM);
+        gz.resize(have + bgzf_member((const unsigned char *)text + at, std::min(BGZF_TEXT, n - at), level, gz.data() + have));
+    }
+}
+
+// A POS/NEG file and the bytes written to it so far (the formatters' parts are written at computed offsets).  --gzip-output
+// (gz_level >= 0): what append() is given is text and is written as members zlib makes of it; append_raw() takes members.
 struct OutFile {
     int fd = -1;
     uint64_t size = 0;
-    void append(const char *p, size_t len) {
+    int gz_level = -1;
+    std::vector<unsigned char> gz;
+    void append_raw(const char *p, size_t len) {
         if (fd < 0 || !len) return;
         write_at(fd, p, len, size);
         size += len;
+    }
+    void append(const char *p, size_t len) {
+        if (fd < 0 || !len) return;
+        if (gz_level < 0) return append_raw(p, len);
+        gz.clear();
+        bgzf_pack(p, len, gz_level, gz);
+        append_raw((const char *)gz.data(), gz.size());
     }
 };
 struct Outputs {
@@ -1504,8 +1548,9 @@ struct Outputs {
         const std::string &dir = o.out;
         const bool has_reads2 = o.has_reads2;
         auto create = [&](OutFile &f, const std::string &name, const char *suffix) {
-            if ((f.fd = open((dir + "/" + name + suffix + ext).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+            if ((f.fd = open((dir + "/" + name + suffix + ext + (o.gzip_output ? ".gz" : "")).c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
                 die("cannot create " + name + " in " + dir);
+            if (o.gzip_output) f.gz_level = o.gzip_level;
         };
         const char *mate1 = has_reads2 ? "_1." : ".";
         if (o.pos) create(pos, "POS_FILTERING", mate1);
@@ -1526,8 +1571,13 @@ struct Outputs {
         }
     }
     void close() {
-        for (OutFile *f : {&pos, &neg, &pos2, &neg2})
+        for (OutFile *f : {&pos, &neg, &pos2, &neg2}) {
+            if (f->fd >= 0 && f->gz_level >= 0) {  // the end marker, also of a file without a record
+                unsigned char marker[BGZF_ROOM];
+                f->append_raw((const char *)marker, bgzf_member(marker, 0, 6, marker));
+            }
             if (f->fd >= 0) ::close(f->fd);
+        }
         if (scores && fclose(scores) != 0) die("short write to READ_SCORES.tsv");
         if (lca && fclose(lca) != 0) die("short write to READ_LCA.tsv");
         if (taxa && fclose(taxa) != 0) die("short write to READ_TAXA.tsv");
@@ -2439,7 +2489,8 @@ struct QueryLoop {
     // and goes through the block map with the hits the query call already returned; the records at the chunk's edges (HEAD,
     // TAIL) and everything the host reader parsed (gzip, the rest of a chunk after SLOW / MORE, malformed tails: classify())
     // go into a carry that becomes a block when it holds `block` records, or at the end of the input.
-    std::atomic<uint64_t> n_fmt_device{0}, n_fmt_host{0}, ns_text_format{0}, n_fmt_bytes{0};
+    std::atomic<uint64_t> n_fmt_device{0}, n_fmt_host{0}, ns_text_format{0}, n_fmt_bytes{0}, n_fmt_gz_bytes{0};
+    double ms_deflate = 0.0;  // --gzip-output: the deflate kernels (pfq_debug_last_deflate), summed in the output turns
     void device_output() {
         std::mutex take_mu, turn_mu;
         std::condition_variable turn_cv;
@@ -2555,12 +2606,18 @@ struct QueryLoop {
                 turn_cv.notify_all();
                 // ---- outside the turns: classify and format the device's records, classify the host's
                 pfq_text_records recs{};
+                pfq_bgzf pos_gz{}, neg_gz{};  // --gzip-output: the streams as the device deflated them, a piece between two left runs
+                double deflate_ms[3] = {0.0, 0.0, 0.0};
                 if (!dropped && n_dev) {
                     const uint64_t tq0 = ReadQueue::now_ns();
                     pfq_hits hits{};
                     if (pfq_text_query(tree, o.threshold, query_flags, &hits) != PFQ_OK) fail_from_thread(pfq_last_error());
                     const uint64_t tq1 = ReadQueue::now_ns();
-                    if (pfq_text_format(tree, first_index, (uint32_t)o.block, fmt_flags, &recs) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    if ((o.gzip_output ? pfq_text_format_gz(tree, first_index, (uint32_t)o.block, fmt_flags, &recs, &pos_gz, &neg_gz)
+                                       : pfq_text_format(tree, first_index, (uint32_t)o.block, fmt_flags, &recs)) != PFQ_OK)
+                        fail_from_thread(pfq_last_error());
+                    if (o.gzip_output && pos_gz.n_members + neg_gz.n_members && pfq_debug_last_deflate(tree, deflate_ms) != PFQ_OK) fail_from_thread(pfq_last_error());
+                    n_fmt_gz_bytes += pos_gz.gz_bytes + neg_gz.gz_bytes;
                     ns_text_format += ReadQueue::now_ns() - tq1;
                     ns_gpu += tq1 - tq0;
                     n_fmt_bytes += recs.pos_bytes + recs.neg_bytes;
@@ -2589,13 +2646,23 @@ struct QueryLoop {
                 }
                 // (the output turn: one thread at a time, in input order)
                 const uint64_t t_out0 = ReadQueue::now_ns();
+                // the device's bytes between left run i - 1 and left run i (i = n_left: behind the last)
+                auto device_bytes = [&](uint64_t i, uint64_t pc, uint64_t qc, uint64_t p_end, uint64_t q_end) {
+                    if (o.gzip_output) {
+                        out.pos.append_raw((const char *)pos_gz.gz + pos_gz.piece_begin[i], pos_gz.piece_begin[i + 1] - pos_gz.piece_begin[i]);
+                        out.neg.append_raw((const char *)neg_gz.gz + neg_gz.piece_begin[i], neg_gz.piece_begin[i + 1] - neg_gz.piece_begin[i]);
+                    } else {
+                        out.pos.append((const char *)recs.pos + pc, p_end - pc);
+                        out.neg.append((const char *)recs.neg + qc, q_end - qc);
+                    }
+                };
                 if (!dropped && n_dev) {
                     const char *text = sg->text.p - sg->text_lo;  // (the address byte 0 of the file would have)
                     uint64_t pc = 0, qc = 0, left_rows = 0, n_left_records = 0;
+                    ms_deflate += deflate_ms[1];
                     for (uint64_t i = 0; i < recs.n_left; ++i) {
                         const pfq_text_left &l = recs.left[i];
-                        out.pos.append((const char *)recs.pos + pc, l.pos_at - pc);
-                        out.neg.append((const char *)recs.neg + qc, l.neg_at - qc);
+                        device_bytes(i, pc, qc, l.pos_at, l.neg_at);
                         pc = l.pos_at;
                         qc = l.neg_at;
                         run_b.clear();
@@ -2611,8 +2678,7 @@ struct QueryLoop {
                         left_rows += l.count;
                         n_left_records += l.count;
                     }
-                    out.pos.append((const char *)recs.pos + pc, recs.pos_bytes - pc);
-                    out.neg.append((const char *)recs.neg + qc, recs.neg_bytes - qc);
+                    device_bytes(recs.n_left, pc, qc, recs.pos_bytes, recs.neg_bytes);
                     n_fmt_device += n_dev - n_left_records;
                 }
                 if (n_host) carry_add(sg->b, 0, n_host, host_hits.off.data(), host_hits.leaves.data());
@@ -2629,9 +2695,13 @@ struct QueryLoop {
     }
     void report_device_output() const {
         const double s = ns_text_format.load() * 1e-9;
-        fprintf(stderr, "device output: %llu records formatted on the device, %llu by the host formatter; pfq_text_format made %llu bytes in %.3f s (%.2f GB/s, kernels and copy, summed over devices)\n",
+        fprintf(stderr, "device output: %llu records formatted on the device, %llu by the host formatter; pfq_text_format made %llu bytes in %.3f s (%.2f GB/s, kernels and copy, summed over devices)",
                 (unsigned long long)n_fmt_device.load(), (unsigned long long)n_fmt_host.load(), (unsigned long long)n_fmt_bytes.load(), s,
                 s > 0 ? n_fmt_bytes.load() / s * 1e-9 : 0.0);
+        if (o.gzip_output)
+            fprintf(stderr, "; deflated on the device to %llu bytes, %.3f s in the deflate kernels (of each call's last stream)", (unsigned long long)n_fmt_gz_bytes.load(),
+                    ms_deflate * 1e-3);
+        fprintf(stderr, "\n");
     }
 
     // Per read, with POS/NEG and/or READ_SCORES.  The device processes big batches; ResultMap semantics (ids merged per
@@ -2729,6 +2799,7 @@ struct QueryLoop {
         // two sets of output buffers: while the writer thread puts set s into the files, the formatters fill the other one
         std::vector<OutBuf> pos_sets[2] = {std::vector<OutBuf>(fmt_workers), std::vector<OutBuf>(fmt_workers)};
         std::vector<OutBuf> neg_sets[2] = {std::vector<OutBuf>(fmt_workers), std::vector<OutBuf>(fmt_workers)};
+        std::vector<std::vector<unsigned char>> gz_parts(fmt_workers);  // --gzip-output: a worker's members before they replace its text
         struct WriteJob {
             int state = 0;  // 0 free, 1 to be written
             unsigned nw = 0;
@@ -2819,6 +2890,14 @@ struct QueryLoop {
                         const uint64_t blk = r / o.block;
                         put_block_record(pb, nb, b, r, grp_of[r], groups.data() + grp0[blk], merged_of[blk], h_off, h_leaves, o.pos, o.neg, db.leaf_names);
                     }
+                    if (o.gzip_output)  // the worker deflates its own part; the parts' places then follow from the compressed sizes
+                        for (OutBuf *part : {&pb, &nb}) {
+                            std::vector<unsigned char> &gz = gz_parts[w];
+                            gz.clear();
+                            bgzf_pack(part->p, part->n, o.gzip_level, gz);
+                            part->n = 0;
+                            part->put((const char *)gz.data(), gz.size());
+                        }
                 });
                 for (unsigned w = nw; w < fmt_workers; ++w) pos_buf[w].n = neg_buf[w].n = 0;
                 if (o.scores) {
@@ -2929,7 +3008,7 @@ std::vector<std::string> split_list(const std::string &text) {  // at every ',':
 // reference's parser.  An entry is an option's name, or "name value" (given with just that value), or "any-prep": the first of
 // PREP_OPTIONS given, but --deplete before all of them.  Where a row sits decides which option a refusal names when several rows
 // apply, so a new option's rows go where its priority demands, not at the end.
-enum class Stage { FIRST, LCA, COVERAGE, DEVICE_OUTPUT, FRAME_STEP, MODES, ADAPTERS, MATES, TAXONOMY, PAIRS, PAIR_MODE };
+enum class Stage { FIRST, LCA, COVERAGE, DEVICE_OUTPUT, FRAME_STEP, MODES, ADAPTERS, MATES, TAXONOMY, PAIRS, PAIR_MODE, GZIP };
 struct Refusal {
     Stage stage;
     enum Rule { WITH, NEEDS, ARGUMENT } rule;
@@ -2997,7 +3076,11 @@ const Refusal REFUSALS[] = {
     // then: the taxonomy's file against tree.bin; the value of --format
     {Stage::PAIRS, Refusal::ARGUMENT, "reads2", "interleaved", ""},
     // then: the value of --pair-mode
-    {Stage::PAIR_MODE, Refusal::NEEDS, "pair-mode", "reads2,interleaved", "'--reads2' or '--interleaved'"}};
+    {Stage::PAIR_MODE, Refusal::NEEDS, "pair-mode", "reads2,interleaved", "'--reads2' or '--interleaved'"},
+    // --gzip-output last of all: it changes how two files are written and nothing else, so every other refusal comes first
+    {Stage::GZIP, Refusal::NEEDS, "gzip-output", "pos-filter,neg-filter", "'--pos-filter' or '--neg-filter' (or both): theirs are the files it compresses"},
+    {Stage::GZIP, Refusal::NEEDS, "gzip-level", "gzip-output", "'--gzip-output'"}};
+    // then: the value of --gzip-level
 // What the command line has of a table entry (see REFUSALS), as a message names it; empty: nothing
 std::string given(const Args &a, const std::string &entry) {
     if (entry == "any-prep") {
@@ -3188,6 +3271,10 @@ QueryOptions parse_query_options(const Args &a) {
     if (pair_mode != "either" && pair_mode != "both") die("error: invalid value '" + pair_mode + "' for '--pair-mode' [possible values: either, both]");
     o.pair_both = pair_mode == "both";
     refuse_by_table(a, Stage::PAIR_MODE);
+    // --gzip-output [--gzip-level L]: POS / NEG as blocked gzip; L is zlib's level for the members the host makes
+    refuse_by_table(a, Stage::GZIP);
+    o.gzip_output = has("gzip-output");
+    if (has("gzip-level")) o.gzip_level = (int)number("gzip-level", "6", 1, 9, "a zlib level from 1 to 9");
     // --devices 0,1,..|all (or PFQ_DEVICES): one replica of the database per listed GPU, each fed by its own host thread;
     // the per-genome counts are combined by one RCCL all-reduce at the end.  The reference has one rayon pool instead
     // (main.rs:269-272); results do not depend on how the reads are dealt.
@@ -3285,7 +3372,8 @@ int cmd_query(int argc, char **argv) {
                              {"sweep", 0, true}, {"trim-quality", 0, true}, {"trim-window", 0, true}, {"trim-poly-x", 0, true}, {"min-length", 0, true},
                              {"max-n", 0, true}, {"min-complexity", 0, true}, {"adapter", 0, true, true}, {"adapter2", 0, true, true}, {"adapter-overlap", 0, true},
                              {"adapter-errors", 0, true}, {"mate-overlap", 0, true}, {"mate-overlap-errors", 0, true}, {"deplete", 0, true, true},
-                             {"deplete-threshold", 0, true}, {"mate-correct", 0, false}, {"mate-correct-quality", 0, true}};
+                             {"deplete-threshold", 0, true}, {"mate-correct", 0, false}, {"mate-correct-quality", 0, true}, {"gzip-output", 0, false},
+                             {"gzip-level", 0, true}};
     QueryOptions o = parse_query_options(parse(argc, argv, 2, opts));
     ServedDb db(o.db_path, o.devices, o.sharded, o.shard_depth);
     if (o.coverage) db.set_coverage_precision(o.coverage_precision);
@@ -3809,33 +3897,16 @@ int cmd_bgzf(int argc, char **argv) {
         if (!*a.val["level"].c_str() || *end || v < 0 || v > 9) die("error: '--level' must be 0 .. 9, not '" + a.val["level"] + "'");
         level = (int)v;
     }
-    constexpr size_t BLOCK = 65280;
+    constexpr size_t BLOCK = BGZF_TEXT;
     gzFile f = gzopen(in.c_str(), "rb");  // (transparent for plain files)
     if (!f) die("Failed to open '" + in + "': " + strerror(errno));
     gzbuffer(f, 1 << 20);
     FILE *o = fopen(out.c_str(), "wb");
     if (!o) die("cannot create " + out + ": " + strerror(errno));
-    std::vector<unsigned char> text(BLOCK), member(18 + compressBound(BLOCK) + 64 + 8);
+    std::vector<unsigned char> text(BLOCK), member(BGZF_ROOM);
     uint64_t n_members = 0, n_text = 0, n_out = 0;
     auto put_member = [&](size_t n) {
-        z_stream z{};
-        // (the empty member at a level above 0 is the marker every reader knows, byte for byte)
-        if (deflateInit2(&z, n ? level : 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) die("zlib: deflateInit2 failed");
-        z.next_in = text.data();
-        z.avail_in = (uInt)n;
-        z.next_out = member.data() + 18;
-        z.avail_out = (uInt)(member.size() - 18 - 8);
-        if (deflate(&z, Z_FINISH) != Z_STREAM_END) die("zlib: deflate did not finish a member");
-        const size_t pay = z.total_out, size = 18 + pay + 8;
-        deflateEnd(&z);
-        if (size > 65536) die("bgzf: a member of more than 64 KiB");  // (cannot happen: 65 280 bytes stored are 65 290)
-        const unsigned char head[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (unsigned char)((size - 1) & 0xff), (unsigned char)((size - 1) >> 8)};
-        memcpy(member.data(), head, 18);
-        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), text.data(), (uInt)n), isize = (uint32_t)n;
-        for (int i = 0; i < 4; ++i) {
-            member[18 + pay + i] = (unsigned char)(crc >> (8 * i));
-            member[18 + pay + 4 + i] = (unsigned char)(isize >> (8 * i));
-        }
+        const size_t size = bgzf_member(text.data(), n, level, member.data());
         if (fwrite(member.data(), 1, size, o) != size) die("short write to " + out);
         ++n_members;
         n_text += n;
@@ -3861,7 +3932,9 @@ int cmd_bgzf(int argc, char **argv) {
     return 0;
 }
 
-void usage() {
+// asked: --help / -h was given, and the text ends with the options that came after the wording of the bare usage message was
+// recorded (tests/golden/cli_query_refusals.json holds that message byte for byte)
+void usage(bool asked = false) {
     std::string header_cols(SIMILARITY_HEADER);  // the column line as the file has it, tabs spelt out
     header_cols.pop_back();
     for (size_t p = 0; (p = header_cols.find('\t', p)) != std::string::npos;) header_cols.replace(p, 1, "<TAB>");
@@ -4057,6 +4130,14 @@ void usage() {
             "(<TAB> between the columns; similarity = score_sum / (pairs * 2^20), from 0 to 1: cut the tree where it drops).  Up to 16384\n"
             "genomes.  build --cluster: build, then recluster, in one run; the database equals that of the two commands byte for byte\n",
             header_cols.c_str(), merges_cols.c_str());
+    if (asked)
+        fprintf(stderr,
+            "--gzip-output (needs --pos-filter and / or --neg-filter): the POS / NEG files are written as blocked gzip (BGZF, what bgzip\n"
+            "writes): POS_FILTERING.fq.gz and so on, each ending with the 28-byte end marker.  zcat of each file is, byte for byte, the file\n"
+            "the same command writes without the option; every other output is unchanged.  Under --device-output the GPU deflates the\n"
+            "records it formats, where they lie; everything else is deflated by the host threads with zlib.  Where the members begin\n"
+            "may depend on -t, -b and --devices; the text does not.  --gzip-level <1..9> (default 6) is zlib's level for the members the\n"
+            "host makes: the GPU's deflate has no levels.  --device-parse --device-inflate reads such files back on the GPU\n");
 }
 
 }  // namespace
@@ -4083,6 +4164,6 @@ int main(int argc, char **argv) {
     if (cmd == "recluster") return cmd_recluster((int)av.size(), av.data());
     if (cmd == "taxonomy") return cmd_taxonomy((int)av.size(), av.data());
     if (cmd == "bgzf") return cmd_bgzf((int)av.size(), av.data());
-    usage();
+    usage(cmd == "--help" || cmd == "-h");
     return 2;
 }

@@ -120,6 +120,7 @@ struct Knobs {
     long long classify_blocks = -1;             // tests: a cap on the grid of the classify launches (a wave then screens several groups of a small input)
     long long fmt_grid = -1, fmt_hash_bits = -1, fmt_time = -1;  // pfq_text_format: a cap on every grid; bits of the id hash that are kept (1 .. 64); 1: time the stages with HIP events
     long long inflate_blocks = -1;              // pfq_text_inflate: a cap on the grid of k_gz_inflate (1 .. 65535; unset: two workgroups a CU, what their LDS admits)
+    long long deflate_blocks = -1;              // pfq_bgzf_deflate, pfq_text_format_gz: a cap on the grid of k_bgzf_deflate (1 .. 65535; unset: one workgroup a CU)
 };
 struct KnobName {
     const char *name;
@@ -158,6 +159,7 @@ const KnobName KNOBS[] = {
     {"PFQ_FMT_TIME", &Knobs::fmt_time},
     {"PFQ_PAIR_AHEAD", &Knobs::pair_ahead},     {"PFQ_CLASSIFY_BLOCKS", &Knobs::classify_blocks},
     {"PFQ_INFLATE_BLOCKS", &Knobs::inflate_blocks},
+    {"PFQ_DEFLATE_BLOCKS", &Knobs::deflate_blocks},
 };
 bool set_knob(Knobs &k, const char *name, const char *value) {
     for (const KnobName &kn : KNOBS)
@@ -468,6 +470,20 @@ struct pfq_tree {
     bool gz_have = false, gz_timed = false;
     uint64_t gz_good_text = 0;
     hipEvent_t gz_time[3] = {nullptr, nullptr, nullptr};
+    // pfq_bgzf_deflate / pfq_text_format_gz: the text of a host caller, the members as the host cut them, a slab of tokens for
+    // every workgroup, a slot for every member and their sizes with the scan (scratch of one call: the call waits for its
+    // kernels); per stream (0: pfq_bgzf_deflate and pos, 1: neg) the gathered members, their page-locked copy and the tables the
+    // caller sees.  df_time: before the copy in, behind it, behind the kernel, behind the copy out.
+    DevBuf<uint8_t> d_df_text, d_df_slots, d_df_gz[2];
+    DevBuf<pfq::BgzfMember> d_df_mem;
+    DevBuf<uint32_t> d_df_tokens, d_df_sizes;
+    DevBuf<unsigned long long> d_df_off, d_df_sums;
+    HostBuf<uint8_t> h_df_gz[2];
+    HostBuf<unsigned long long> h_df_off;
+    std::vector<pfq::BgzfMember> df_mem;
+    std::vector<uint64_t> df_piece_begin[2], df_member_begin[2];
+    bool df_timed = false;
+    hipEvent_t df_time[4] = {nullptr, nullptr, nullptr, nullptr};
     // pfq_text_format: what the kernels leave per record (ids, hashes, lengths and their scans), the small words that go back to
     // the host in one copy (d_fm_small: FMT_RES_N result words | the streams' offsets at the block boundaries | the block states),
     // the leaves' names (uploaded when they differ from fm_names), the two streams and their page-locked copies, which only
@@ -3514,6 +3530,8 @@ int pfq_tree_info(const pfq_tree *tree, pfq_info *out) {
                         t.d_tx_rec_begin.bytes() + t.d_tx_blk.bytes() + t.d_tx_line.bytes() + t.d_tx_len.bytes() + t.d_tx_hdr.bytes() + t.d_tx_rec_line.bytes() +
                         t.d_tx_bad.bytes() + t.d_tx_blk_off.bytes() + t.d_tx_sums.bytes() + t.d_tx_dst.bytes() + t.d_tx_rec_idx.bytes() + t.d_tx_res.bytes() +
                         t.d_gz.bytes() + t.d_gz_text.bytes() + t.d_gz_mem.bytes() + t.d_gz_res.bytes() +  // (pfq_text_inflate)
+                        t.d_df_text.bytes() + t.d_df_slots.bytes() + t.d_df_gz[0].bytes() + t.d_df_gz[1].bytes() + t.d_df_mem.bytes() +  // (pfq_bgzf_deflate)
+                        t.d_df_tokens.bytes() + t.d_df_sizes.bytes() + t.d_df_off.bytes() + t.d_df_sums.bytes() +
                         t.d_pp_in.bytes() + t.d_pp_qual.bytes() + t.d_pp_hq.bytes() + t.d_pp_seq[0].bytes() + t.d_pp_seq[1].bytes() + t.d_pp_inoff.bytes() +  // (pfq_prep_reads)
                         t.d_pp_off[0].bytes() + t.d_pp_off[1].bytes() + t.d_pp_begin.bytes() + t.d_pp_len.bytes() + t.d_pp_reason.bytes() + t.d_pp_keep.bytes() +
                         t.d_pp_klen.bytes() + t.d_pp_kept.bytes() + t.d_pp_kpos.bytes() + t.d_pp_koff.bytes() + t.d_pp_sums.bytes() + t.d_pp_tot.bytes() +
@@ -3574,6 +3592,8 @@ void pfq_tree_close(pfq_tree *tree) {
     if (tree->tx_parsed) (void)hipEventDestroy(tree->tx_parsed);
     if (tree->h_tx_res) (void)hipHostFree(tree->h_tx_res);
     for (auto e : tree->gz_time)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : tree->df_time)
         if (e) (void)hipEventDestroy(e);
     for (auto e : tree->pp_free)
         if (e) (void)hipEventDestroy(e);
@@ -4059,8 +4079,12 @@ int pfq_debug_last_inflate(pfq_tree *tree, double *ms) {
 
 // ---- text output ----------------------------------------------------------------------------------------------------------
 
-int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out) {
-    if (!tree || !out) return fail(PFQ_ERR_ARG, "null argument");
+static int deflate_device(pfq_tree &t, const uint8_t *d_text, const uint8_t *h_text, uint64_t len, const uint64_t *cuts, uint64_t n_cuts, int s,
+                          pfq_bgzf *out);
+
+// pfq_text_format, and pfq_text_format_gz where gz is given: the streams then stay on the device and are deflated there.
+static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out, pfq_bgzf *const *gz) {
+    if (!tree || !out || (gz && (!gz[0] || !gz[1]))) return fail(PFQ_ERR_ARG, "null argument");
     if (block < 1 || block > PFQ_FMT_BLOCK_MAX)
         return fail(PFQ_ERR_ARG, "pfq_text_format: block must be 1 .. " + std::to_string(PFQ_FMT_BLOCK_MAX) + ", not " + std::to_string(block));
     if (!(flags & (PFQ_FMT_POS | PFQ_FMT_NEG)) || (flags & ~(PFQ_FMT_POS | PFQ_FMT_NEG)))
@@ -4084,12 +4108,16 @@ int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32
     for (auto &h : t.h_fm_out) HIP_TRY(h.ensure(1));
     *out = pfq_text_records{};
     out->n_records = n;
-    out->pos = t.h_fm_out[0].p;
-    out->neg = t.h_fm_out[1].p;
+    out->pos = gz ? nullptr : t.h_fm_out[0].p;
+    out->neg = gz ? nullptr : t.h_fm_out[1].p;
     t.out_fm_left.clear();
     out->left = t.out_fm_left.data();
     t.fm_timed = false;
-    if (!n) return PFQ_OK;
+    if (!n) {
+        if (gz)
+            for (int s = 0; s < 2; ++s) PFQ_TRY(deflate_device(t, nullptr, nullptr, 0, nullptr, 0, s, gz[s]));
+        return PFQ_OK;
+    }
     const bool timed = t.knobs.fmt_time == 1;
     if (timed)
         for (auto &e : t.fm_time)
@@ -4171,14 +4199,14 @@ int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32
     const uint64_t total[2] = {bounds[2 * ((size_t)n_whole + 1)], bounds[2 * ((size_t)n_whole + 1) + 1]};
     for (int s = 0; s < 2; ++s) {
         HIP_TRY(t.d_fm_out[s].ensure(total[s] + 16));
-        HIP_TRY(t.h_fm_out[s].ensure(total[s] + 1));
+        if (!gz) HIP_TRY(t.h_fm_out[s].ensure(total[s] + 1));
         a.out[s] = t.d_fm_out[s].p;
     }
     pfq::launch_fmt_emit(a, st);
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(t.fm_time[3], st));
     for (int s = 0; s < 2; ++s)
-        if (total[s]) HIP_TRY(hipMemcpyAsync(t.h_fm_out[s].p, t.d_fm_out[s].p, total[s], hipMemcpyDeviceToHost, st));
+        if (total[s] && !gz) HIP_TRY(hipMemcpyAsync(t.h_fm_out[s].p, t.d_fm_out[s].p, total[s], hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     t.fm_timed = timed;
     // the left runs, from the block states
@@ -4192,10 +4220,127 @@ int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32
     out->neg_records = res[pfq::FMT_RES_NEG_RECORDS];
     out->pos_bytes = total[0];
     out->neg_bytes = total[1];
-    out->pos = t.h_fm_out[0].p;
-    out->neg = t.h_fm_out[1].p;
+    out->pos = gz ? nullptr : t.h_fm_out[0].p;
+    out->neg = gz ? nullptr : t.h_fm_out[1].p;
     out->n_left = t.out_fm_left.size();
     out->left = t.out_fm_left.data();
+    if (gz) {  // each stream cut where the caller's own bytes for the left runs belong
+        std::vector<uint64_t> cuts(t.out_fm_left.size());
+        for (int s = 0; s < 2; ++s) {
+            for (size_t i = 0; i < cuts.size(); ++i) cuts[i] = s ? t.out_fm_left[i].neg_at : t.out_fm_left[i].pos_at;
+            PFQ_TRY(deflate_device(t, t.d_fm_out[s].p, nullptr, total[s], cuts.data(), cuts.size(), s, gz[s]));
+        }
+    }
+    return PFQ_OK;
+}
+
+int pfq_text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out) {
+    return text_format(tree, first_index, block, flags, out, nullptr);
+}
+
+// ---- blocked gzip written on the device ---------------------------------------------------------------------------------------
+
+// text[0, len) on the device (h_text: copied there first) cut, deflated and gathered into stream s's buffers.
+static int deflate_device(pfq_tree &t, const uint8_t *d_text, const uint8_t *h_text, uint64_t len, const uint64_t *cuts, uint64_t n_cuts, int s,
+                          pfq_bgzf *out) {
+    std::vector<uint64_t> &piece_begin = t.df_piece_begin[s], &member_begin = t.df_member_begin[s];
+    t.df_mem.clear();
+    piece_begin.assign(n_cuts + 2, 0);  // first as the first member of every piece, below as its offset
+    for (uint64_t piece = 0; piece <= n_cuts; ++piece) {
+        const uint64_t from = piece ? cuts[piece - 1] : 0, to = piece < n_cuts ? cuts[piece] : len;
+        piece_begin[piece] = t.df_mem.size();
+        for (uint64_t at = from; at < to; at += PFQ_BGZF_MEMBER_TEXT)
+            t.df_mem.push_back(pfq::BgzfMember{at, (uint32_t)std::min<uint64_t>(PFQ_BGZF_MEMBER_TEXT, to - at), (uint32_t)piece});
+    }
+    const uint64_t n = t.df_mem.size();
+    piece_begin[n_cuts + 1] = n;
+    member_begin.assign(n + 1, 0);
+    HIP_TRY(t.h_df_gz[s].ensure(1));
+    *out = pfq_bgzf{};
+    out->n_members = n;
+    out->n_pieces = n_cuts + 1;
+    if (n) {
+        if (!t.copy_stream) {
+            HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
+            for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        for (auto &e : t.df_time)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        hipStream_t st = t.copy_stream;
+        long long blocks = t.knobs.deflate_blocks;
+        if (blocks < 1 || blocks > 65535) {
+            int cus = 0;
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t.device));
+            blocks = std::max(cus, 1);
+        }
+        const uint64_t grid = std::min<uint64_t>(n, (uint64_t)blocks);
+        if (h_text) {
+            HIP_TRY(t.d_df_text.ensure(len + 32));
+            d_text = t.d_df_text.p;
+        }
+        HIP_TRY(t.d_df_mem.ensure(n));
+        HIP_TRY(t.d_df_tokens.ensure(grid * pfq::BGZF_TOKENS));
+        HIP_TRY(t.d_df_slots.ensure(n * pfq::BGZF_SLOT));
+        HIP_TRY(t.d_df_sizes.ensure(n));
+        HIP_TRY(t.d_df_off.ensure(n + 1));
+        HIP_TRY(t.d_df_sums.ensure(n / 4096 + 2));
+        HIP_TRY(t.d_df_gz[s].ensure(len + 31 * n + 16));
+        HIP_TRY(t.h_df_off.ensure(n + 1));
+        t.df_timed = false;
+        HIP_TRY(hipEventRecord(t.df_time[0], st));
+        if (h_text) HIP_TRY(hipMemcpyAsync(t.d_df_text.p, h_text, len, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_df_mem.p, t.df_mem.data(), n * sizeof(pfq::BgzfMember), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(t.df_time[1], st));
+        pfq::launch_bgzf_deflate(d_text, t.d_df_mem.p, n, t.d_df_tokens.p, t.d_df_slots.p, t.d_df_sizes.p, (uint32_t)blocks, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t.df_time[2], st));
+        pfq::launch_scan_u32(t.d_df_sizes.p, n, t.d_df_sums.p, t.d_df_off.p, st);
+        pfq::launch_bgzf_gather(t.d_df_slots.p, t.d_df_off.p, n, t.d_df_gz[s].p, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(t.h_df_off.p, t.d_df_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // (the total sizes the copy)
+        const uint64_t total = t.h_df_off.p[n];
+        if (total > len + 31 * n) return fail(PFQ_ERR_DEVICE, "deflate: members of " + std::to_string(total) + " bytes for " + std::to_string(len) + " of text");
+        HIP_TRY(t.h_df_gz[s].ensure(total + 1));
+        HIP_TRY(hipMemcpyAsync(t.h_df_gz[s].p, t.d_df_gz[s].p, total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(t.df_time[3], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t.df_timed = true;
+        for (uint64_t m = 0; m <= n; ++m) member_begin[m] = t.h_df_off.p[m];
+        out->gz_bytes = total;
+    }
+    for (uint64_t piece = 0; piece <= n_cuts + 1; ++piece) piece_begin[piece] = member_begin[piece_begin[piece]];
+    out->gz = t.h_df_gz[s].p;
+    out->piece_begin = piece_begin.data();
+    out->member_begin = member_begin.data();
+    return PFQ_OK;
+}
+
+int pfq_bgzf_deflate(pfq_tree *tree, const uint8_t *text, uint64_t len, const uint64_t *cuts, uint64_t n_cuts, pfq_bgzf *out) {
+    if (!tree || !out || (len && !text) || (n_cuts && !cuts)) return fail(PFQ_ERR_ARG, "null argument");
+    for (uint64_t i = 0; i < n_cuts; ++i)
+        if (cuts[i] > len || (i && cuts[i] < cuts[i - 1]))
+            return fail(PFQ_ERR_ARG, "pfq_bgzf_deflate: cut " + std::to_string(i) + " (" + std::to_string(cuts[i]) + ") is not ascending or lies beyond the text's " +
+                                         std::to_string(len) + " bytes");
+    if (len >> 31) return fail(PFQ_ERR_UNSUPPORTED, "pfq_bgzf_deflate: 2^31 bytes of text or more in one call: deflate smaller chunks");
+    PFQ_TRY(use_device(tree->device));
+    return deflate_device(*tree, nullptr, text, len, cuts, n_cuts, 0, out);
+}
+
+int pfq_text_format_gz(pfq_tree *tree, uint64_t first_index, uint32_t block, uint32_t flags, pfq_text_records *out, pfq_bgzf *pos_gz, pfq_bgzf *neg_gz) {
+    pfq_bgzf *const gz[2] = {pos_gz, neg_gz};
+    return text_format(tree, first_index, block, flags, out, gz);
+}
+
+int pfq_debug_last_deflate(pfq_tree *tree, double *ms) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!tree->df_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_deflate before a deflate call with members on this tree");
+    PFQ_TRY(use_device(tree->device));
+    for (int i = 0; i < 3; i++) {
+        float f = 0;
+        HIP_TRY(hipEventElapsedTime(&f, tree->df_time[i], tree->df_time[i + 1]));
+        ms[i] = f;
+    }
     return PFQ_OK;
 }
 
@@ -6126,6 +6271,10 @@ int pfq_set_option(pfq_tree *tree, const char *name, const char *value) {
     if (!strcmp(name, "PFQ_INFLATE_BLOCKS") && value && *value) {  // a cap on the grid of k_gz_inflate
         const long long v = strtoll(value, nullptr, 10);
         if (v < 1 || v > 65535) return fail(PFQ_ERR_ARG, std::string("PFQ_INFLATE_BLOCKS must be 1 .. 65535, not ") + value);
+    }
+    if (!strcmp(name, "PFQ_DEFLATE_BLOCKS") && value && *value) {  // a cap on the grid of k_bgzf_deflate
+        const long long v = strtoll(value, nullptr, 10);
+        if (v < 1 || v > 65535) return fail(PFQ_ERR_ARG, std::string("PFQ_DEFLATE_BLOCKS must be 1 .. 65535, not ") + value);
     }
     if (!strcmp(name, "PFQ_FRAME_PIECE") && value && *value) {  // the windows of a piece are whole: a positive multiple of 64
         const long long v = strtoll(value, nullptr, 10);

@@ -849,5 +849,18 @@ struct GzMember {
 };
 void launch_gz_inflate(const uint8_t *d_gz, const GzMember *d_members, uint64_t n_members, uint8_t *d_text, uint32_t *d_result, uint32_t blocks,
                        hipStream_t st);
+// pfq_bgzf_deflate / pfq_text_format_gz (pfq_deflate.hip): text deflated into members of blocked gzip, one workgroup a member, a
+// grid-stride loop over the members.  d_text: 16-byte aligned and allocated 16 bytes beyond the last member's text; members: the
+// host's cutting (text_len <= BGZF_TOKENS).  d_tokens: BGZF_TOKENS words for every workgroup of the grid min(n_members, blocks);
+// member m is written to d_slots + m * BGZF_SLOT and its bytes to d_sizes[m].  The caller scans the sizes (launch_scan_u32) into
+// d_off, and launch_bgzf_gather moves the members to d_gz + d_off[m] (d_gz: 4-byte aligned).
+constexpr uint32_t BGZF_SLOT = 65536, BGZF_TOKENS = 65280;
+struct BgzfMember {
+    uint64_t text_begin;  // in d_text
+    uint32_t text_len, piece;
+};
+void launch_bgzf_deflate(const uint8_t *d_text, const BgzfMember *d_members, uint64_t n_members, uint32_t *d_tokens, uint8_t *d_slots, uint32_t *d_sizes,
+                         uint32_t blocks, hipStream_t st);
+void launch_bgzf_gather(const uint8_t *d_slots, const unsigned long long *d_off, uint64_t n_members, uint8_t *d_gz, hipStream_t st);
 
 }  // namespace pfq

@@ -418,6 +418,46 @@ class BloomTree:
         _ffi.check(_ffi.lib().pfq_debug_last_format(self._h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
+    # ---- blocked gzip written on the device
+    @staticmethod
+    def _bgzf(out) -> dict:
+        n, k = int(out.n_members), int(out.n_pieces)
+        return {"gz": C.string_at(out.gz, int(out.gz_bytes)), "n_members": n,
+                "piece_begin": np.ctypeslib.as_array(out.piece_begin, shape=(k + 1,)).copy(),
+                "member_begin": np.ctypeslib.as_array(out.member_begin, shape=(n + 1,)).copy()}
+
+    def deflate_bytes(self, data: bytes, cuts: Sequence[int] = ()) -> dict:
+        """`data`, cut at the ascending offsets `cuts` into len(cuts) + 1 pieces and every piece into members of 65280 text bytes,
+        deflated on the device into blocked gzip (pfq_bgzf_deflate; the rules are pfq.h "blocked gzip written on the device").
+        Returns gz (the members back to back, no end marker), n_members, piece_begin uint64[pieces + 1] and member_begin
+        uint64[n_members + 1], offsets into gz.  No counter changes."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        c = np.asarray(list(cuts), dtype=np.uint64)
+        out = _ffi.Bgzf()
+        _ffi.check(_ffi.lib().pfq_bgzf_deflate(self._h, buf.ctypes.data if buf.size else None, buf.size, c.ctypes.data if c.size else None, c.size,
+                                               C.byref(out)))
+        return self._bgzf(out)
+
+    def format_text_gz(self, first_index: int = 0, block: int = 100, pos: bool = True, neg: bool = True) -> dict:
+        """format_text() for the same arguments with the two streams deflated on the device instead of copied
+        (pfq_text_format_gz): pos_gz and neg_gz replace pos and neg, and pos_piece_begin / neg_piece_begin uint64[len(left) + 2]
+        say where the pieces lie: piece j of a stream is what belongs between the caller's bytes for left run j - 1 and j."""
+        out, pg, ng = _ffi.TextRecords(), _ffi.Bgzf(), _ffi.Bgzf()
+        flags = (_ffi.FMT_POS if pos else 0) | (_ffi.FMT_NEG if neg else 0)
+        _ffi.check(_ffi.lib().pfq_text_format_gz(self._h, first_index, block, flags, C.byref(out), C.byref(pg), C.byref(ng)))
+        left = [(int(x.first), int(x.count), int(x.pos_at), int(x.neg_at), self.LEFT_REASONS[x.why]) for x in out.left[:int(out.n_left)]]
+        p, q = self._bgzf(pg), self._bgzf(ng)
+        return {"n_records": int(out.n_records), "pos_gz": p["gz"], "neg_gz": q["gz"], "pos_piece_begin": p["piece_begin"],
+                "neg_piece_begin": q["piece_begin"], "pos_bytes": int(out.pos_bytes), "neg_bytes": int(out.neg_bytes),
+                "pos_records": int(out.pos_records), "neg_records": int(out.neg_records), "left": left}
+
+    def last_deflate_ms(self) -> Tuple[float, float, float]:
+        """Device milliseconds of the last deflate_bytes() or format_text_gz() stream with members: (copy in, deflate kernel,
+        scan + gather + copy out) (pfq_debug_last_deflate)."""
+        ms = (C.c_double * 3)()
+        _ffi.check(_ffi.lib().pfq_debug_last_deflate(self._h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     # ---- read preprocessing
     PREP_REASONS = ("kept", "short", "n", "complexity", "mate")
 

@@ -6,6 +6,8 @@ and from gzip.  Prints one JSON line per run.
     python tools/cli_bench.py [--reads 16000000] [--threads 1,4,16] [--threshold 1.0] [--block 100000] [--workdir /tmp/pfq_cli_bench]
     python tools/cli_bench.py --device-parse --repeats 3 --only counts --threads 4,16     (A/B of query --device-parse)
     python tools/cli_bench.py --device-output --repeats 3 --only posneg --threads 16 --block 1000     (A/B of query --device-output)
+    python tools/cli_bench.py --device-output --gzip-output --repeats 3 --only posneg --threads 16 --block 1000 --reads 8000000
+        (query --device-output, the same with --gzip-output, and --device-output followed by `phage_filter bgzf` of both files)
 """
 import argparse
 import gzip
@@ -63,6 +65,8 @@ def main():
     ap.add_argument("--device-parse", action="store_true", help="every counts-only run is followed by the same run with query --device-parse")
     ap.add_argument("--device-output", action="store_true", help="--only posneg: every run is followed by the same run with query --device-output "
                     "(needs --block of at most 8192)")
+    ap.add_argument("--gzip-output", action="store_true", help="--only posneg --device-output: each round also runs --device-output --gzip-output, and "
+                    "--device-output followed by `phage_filter bgzf` of POS and NEG (the two steps the option fuses)")
     ap.add_argument("--repeats", type=int, default=1, help="how often the counts-only runs (alternating with --device-parse) are repeated")
     ap.add_argument("--devices", default="", help="comma-separated device lists to run as well, ';'-separated (e.g. '0,0' = two replicas on GPU 0)")
     ap.add_argument("--shard-depth", default="", help="the --devices runs split the database into the subtree shards of this depth "
@@ -113,10 +117,19 @@ def main():
         outl = [l for l in p.stderr.splitlines() if l.startswith("output:")]
         cpul = [l for l in p.stderr.splitlines() if l.startswith("cpu:")]
         devl = [l for l in p.stderr.splitlines() if l.startswith("device parse:") or l.startswith("device output:")]
+        written = {f: os.path.getsize(os.path.join(out, f)) for f in sorted(os.listdir(out)) if f.startswith(("POS", "NEG"))}
+        then = None
+        if "then-bgzf" in label:  # the second step: both files through `phage_filter bgzf`, one after the other
+            t1 = time.time()
+            for f in list(written):
+                subprocess.run([CLI, "bgzf", "-i", os.path.join(out, f), "-o", os.path.join(out, f + ".gz"), "--level", "1"], check=True, capture_output=True)
+                written[f + ".gz"] = os.path.getsize(os.path.join(out, f + ".gz"))
+            then = round(time.time() - t1, 3)
+            wall = time.time() - t0
         csv = open(os.path.join(out, "CLASSIFICATION.csv")).read().splitlines()
         print(json.dumps({"run": label, "threads": threads, "reads": n_reads, "whole_process_s": round(wall, 3),
                           "whole_process_reads_per_s": round(n_reads / wall), "query_loop": loop[0] if loop else None,
-                          "ingest": ingest[0] if ingest else None, "output": outl[0] if outl else None, "cpu": cpul[0] if cpul else None, "device_parse": devl[0] if devl else None, "classified": sum(int(l.split(",")[1]) for l in csv)}), flush=True)
+                          "ingest": ingest[0] if ingest else None, "output": outl[0] if outl else None, "cpu": cpul[0] if cpul else None, "device_parse": devl[0] if devl else None, "written": written, "bgzf_step_s": then, "classified": sum(int(l.split(",")[1]) for l in csv)}), flush=True)
 
     tmax = max(int(x) for x in a.threads.split(","))
     if a.only == "posneg":
@@ -124,6 +137,9 @@ def main():
             run("fastq pos+neg output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter"))
             if a.device_output:
                 run("fastq pos+neg output --device-output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter", "--device-output"))
+            if a.device_output and a.gzip_output:
+                run("fastq pos+neg output --device-output --gzip-output", fq, a.reads, tmax, ("--pos-filter", "--neg-filter", "--device-output", "--gzip-output"))
+                run("fastq pos+neg output --device-output then-bgzf (level 1, one thread a file)", fq, a.reads, tmax, ("--pos-filter", "--neg-filter", "--device-output"))
         shutil.rmtree(a.workdir, ignore_errors=True)
         return
     for t in [int(x) for x in a.threads.split(",")]:
