@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -94,6 +95,75 @@ struct HostBuf {
         hipError_t e = hipHostMalloc((void **)&p, grown, hipHostMallocDefault);
         if (e == hipSuccess) cap = grown;
         return e;
+    }
+};
+// One HIP event, made by the first ensure() and destroyed with its owner.  ensure() of an event that exists does nothing, so a
+// set-up that failed part of the way is completed by the next call that runs it.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t ensure(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_constructible<Event>::value,
+              "an event has one owner; std::vector<Event> moves it");
+// A stream of the library's own, likewise.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t ensure(unsigned flags) { return s ? hipSuccess : hipStreamCreateWithFlags(&s, flags); }
+    operator hipStream_t() const { return s; }
+};
+// N timing events round the N - 1 stages of a call.  valid: the last call that marks them has recorded all of them and has
+// been waited for, so read() may ask for the intervals.
+template <int N>
+struct StageTimes {
+    Event ev[N];
+    bool valid = false;
+    hipError_t ensure() {
+        for (Event &e : ev)
+            if (hipError_t r = e.ensure(); r != hipSuccess) return r;
+        return hipSuccess;
+    }
+    hipError_t mark(int i, hipStream_t st) { return hipEventRecord(ev[i], st); }
+    hipError_t read(double *ms) const {
+        for (int i = 0; i + 1 < N; ++i) {
+            float f = 0.0f;
+            if (hipError_t r = hipEventElapsedTime(&f, ev[i], ev[i + 1]); r != hipSuccess) return r;
+            ms[i] = f;
+        }
+        return hipSuccess;
+    }
+};
+// Two alternating sets of buffers that one call fills while the kernels of another still read the other set.  free[s] is
+// recorded behind the last reader of set s (used[s]: there has been one); cur is the set that holds the current block.  When
+// cur moves is the call site's business: a set that is being filled becomes current only where its filling cannot fail any more.
+struct TwoSets {
+    Event free[2];
+    bool used[2] = {false, false};
+    int cur = 0;
+    hipError_t ensure() {
+        for (Event &e : free)
+            if (hipError_t r = e.ensure(hipEventDisableTiming); r != hipSuccess) return r;
+        return hipSuccess;
+    }
+    int other() const { return cur ^ 1; }
+    hipError_t wait(int s) const { return used[s] ? hipEventSynchronize(free[s]) : hipSuccess; }  // the last reader of set s is done
+    hipError_t read_by(int s, hipStream_t st) {  // what `st` holds so far reads set s
+        const hipError_t r = hipEventRecord(free[s], st);
+        if (r == hipSuccess) used[s] = true;
+        return r;
     }
 };
 
@@ -242,8 +312,8 @@ struct pfq_tree {
     bool is_shard = false;
     // deferred pairs per read seen by recent calls (related genomes: a read passes several leaves): sizes the pair
     // buffer and the probe buckets of the next call.  The cursor of a call lands in pinned memory asynchronously.
-    unsigned long long *h_pair_cursor = nullptr;
-    hipEvent_t hint_ev = nullptr;
+    HostBuf<unsigned long long> h_pair_cursor;
+    Event hint_ev;
     uint64_t hint_reads = 0, hint_entry_cap = 0, passes_hint = 1;
     double pairs_per_read = 1.0, hits_per_read = 1.0;
     double dirty_frac = 1.0;           // thresholds < 1: share of the last call's deferred pairs with a k-mer missing (1: unknown)
@@ -261,10 +331,8 @@ struct pfq_tree {
     bool topo_on_device = false;       // d_topo / d_walk mirror the host's nodes
     bool topo_pending = false;         // insertions ran since the host last read the shape back
     DevBuf<uint8_t> d_gseq[4];         // genomes of the insertions in flight (ring)
-    hipEvent_t gseq_free[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t gseq_copied[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint8_t *h_gseq[4] = {nullptr, nullptr, nullptr, nullptr};  // page-locked staging of the same ring (the caller's buffer is free when pfq_tree_insert returns)
-    size_t h_gseq_n[4] = {0, 0, 0, 0};
+    Event gseq_free[4], gseq_copied[4];
+    HostBuf<uint8_t> h_gseq[4];        // page-locked staging of the same ring (the caller's buffer is free when pfq_tree_insert returns)
     uint32_t gseq_next = 0;
     int greedy_blocks = 0;
     uint32_t walk_seq = 0;             // launches of the device walk since d_walk was written (parity: where the root is read / left)
@@ -335,10 +403,8 @@ struct pfq_tree {
     DevBuf<unsigned int> d_queue;
     DevBuf<uint8_t> d_allhit, d_seq, d_seq2;  // d_seq / d_seq2, d_off / d_off2: input buffers of pfq_query_batch, alternating
     DevBuf<uint64_t> d_off2;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t in_free[2] = {nullptr, nullptr};
-    bool in_used[2] = {false, false};
-    int in_slot = 0;
+    Stream copy_stream;                // made by ensure_copy_stream
+    TwoSets in_sets;                   // d_seq / d_off and d_seq2 / d_off2 (stage_input)
     DevBuf<unsigned long long> d_miss_words;  // thresholds < 1: k-mer miss bits of every deferred pair
     DevBuf<uint32_t> d_miss_pos, d_bucket_w;  // first word per sorted pair; per-bucket word counts / offsets / cursors
     DevBuf<uint32_t> d_long;
@@ -350,10 +416,10 @@ struct pfq_tree {
     // waits for that call is last_done, recorded on it after the call's work
     hipStream_t last_stream = nullptr;
     bool have_last_stream = false;
-    hipEvent_t last_done = nullptr;
+    Event last_done;
     int force_path = -1;
     // ---- profiling (HIP events on the launch stream)
-    std::vector<hipEvent_t> prof_ev;  // PROF_EV events per recorded call
+    std::vector<Event> prof_ev;  // PROF_EV events per recorded call
     size_t prof_cap = 0, prof_used = 0;
     std::vector<uint8_t> prof_bucketed;
     uint32_t last_path = 0, last_slices = 1;
@@ -444,15 +510,15 @@ struct pfq_tree {
     uint32_t cluster_rounds = 0;
     // pfq_text_parse: the text, what the parse kernels leave per tile and per line (scratch of one call: the call waits for its
     // kernels), and two alternating CSR sets — the classification of pfq_text_query reads set tx_slot while the next parse fills
-    // the other.  tx_free[s]: recorded behind the classification that read set s; tx_parsed: behind the parse kernels.
+    // the other.  tx_sets: set s is read by the classification; tx_parsed: behind the parse kernels.
     DevBuf<uint8_t> d_tx_text, d_tx_seq[2];
     DevBuf<uint64_t> d_tx_off[2], d_tx_rec_begin;
     DevBuf<uint32_t> d_tx_blk, d_tx_line, d_tx_len, d_tx_hdr, d_tx_rec_line, d_tx_bad;
     DevBuf<unsigned long long> d_tx_blk_off, d_tx_sums, d_tx_dst, d_tx_rec_idx, d_tx_res;
-    unsigned long long *h_tx_res = nullptr;  // page-locked: the result words, the newline count
-    hipEvent_t tx_free[2] = {nullptr, nullptr}, tx_parsed = nullptr;
-    bool tx_used[2] = {false, false}, tx_have = false;
-    int tx_slot = 0;
+    HostBuf<unsigned long long> h_tx_res;  // page-locked: the result words, the newline count
+    TwoSets tx_sets;
+    Event tx_parsed;
+    bool tx_have = false;
     uint64_t tx_records = 0, tx_bases = 0;
     std::vector<uint64_t> out_rec_begin;
     int tx_fastq = 0;
@@ -467,9 +533,9 @@ struct pfq_tree {
     std::vector<pfq::GzMember> gz_mem;
     std::vector<uint32_t> gz_res;
     std::vector<uint8_t> gz_status;
-    bool gz_have = false, gz_timed = false;
+    bool gz_have = false;
     uint64_t gz_good_text = 0;
-    hipEvent_t gz_time[3] = {nullptr, nullptr, nullptr};
+    StageTimes<3> gz_time;
     // pfq_bgzf_deflate / pfq_text_format_gz: the text of a host caller, the members as the host cut them, a slab of tokens for
     // every workgroup, a slot for every member and their sizes with the scan (scratch of one call: the call waits for its
     // kernels); per stream (0: pfq_bgzf_deflate and pos, 1: neg) the gathered members, their page-locked copy and the tables the
@@ -482,8 +548,7 @@ struct pfq_tree {
     HostBuf<unsigned long long> h_df_off;
     std::vector<pfq::BgzfMember> df_mem;
     std::vector<uint64_t> df_piece_begin[2], df_member_begin[2];
-    bool df_timed = false;
-    hipEvent_t df_time[4] = {nullptr, nullptr, nullptr, nullptr};
+    StageTimes<4> df_time;
     // pfq_text_format: what the kernels leave per record (ids, hashes, lengths and their scans), the small words that go back to
     // the host in one copy (d_fm_small: FMT_RES_N result words | the streams' offsets at the block boundaries | the block states),
     // the leaves' names (uploaded when they differ from fm_names), the two streams and their page-locked copies, which only
@@ -498,21 +563,20 @@ struct pfq_tree {
     std::vector<uint8_t> fm_names;
     std::vector<uint32_t> fm_name_off;
     std::vector<pfq_text_left> out_fm_left;
-    bool fm_rows = false, fm_timed = false;
+    bool fm_rows = false;
     uint64_t fm_rows_leaves = 0;
-    hipEvent_t fm_time[4] = {nullptr, nullptr, nullptr, nullptr};  // pfq_debug_last_format: ids + blocks, sizes + scans, emit
+    StageTimes<4> fm_time;  // pfq_debug_last_format: ids + blocks, sizes + scans, emit
     // pfq_prep_reads: the block as the caller gave it and what the kernels leave per read (scratch of one call: the call waits
-    // for its kernels), and two alternating CSR sets as above: pp_free[s] behind the classification that read set s, pp_ready
-    // behind the prep kernels.
+    // for its kernels), and two alternating CSR sets as above (pp_sets); pp_ready: behind the prep kernels.
     DevBuf<uint8_t> d_pp_in, d_pp_qual, d_pp_hq, d_pp_seq[2];
     DevBuf<uint64_t> d_pp_inoff, d_pp_off[2];
     DevBuf<uint32_t> d_pp_begin, d_pp_len, d_pp_reason, d_pp_keep, d_pp_klen, d_pp_kept;
     DevBuf<unsigned long long> d_pp_kpos, d_pp_koff, d_pp_sums, d_pp_tot;
-    unsigned long long *h_pp_tot = nullptr;  // page-locked: the totals, then the kept reads
-    hipEvent_t pp_free[2] = {nullptr, nullptr}, pp_ready = nullptr;
-    hipEvent_t pp_time[4] = {nullptr, nullptr, nullptr, nullptr};  // pfq_debug_last_prep: round trim + mark, the scans, offsets + gather
-    bool pp_used[2] = {false, false}, pp_have = false, pp_paired = false, pp_timed = false;
-    int pp_slot = 0;
+    HostBuf<unsigned long long> h_pp_tot;  // page-locked: the totals, then the kept reads
+    TwoSets pp_sets;
+    Event pp_ready;
+    StageTimes<4> pp_time;  // pfq_debug_last_prep: round trim + mark, the scans, offsets + gather
+    bool pp_have = false, pp_paired = false;
     uint64_t pp_kept = 0, pp_bases = 0;
     std::vector<uint32_t> out_pp_begin, out_pp_len, out_pp_reason, out_pp_kept;
     // pfq_prep_deplete on this tree's prepared block: pp_reads / pp_want_reads of the prep that made it (d_pp_keep, d_pp_klen,
@@ -521,32 +585,32 @@ struct pfq_tree {
     // reads and bases of the new scans), the host copies of kept and reason after the last call (dp_have: there has been one
     // since the prep; out_pp_* stay the prep's).
     uint64_t pp_reads = 0;
-    bool pp_want_reads = false, dp_have = false, dp_timed = false;
+    bool pp_want_reads = false, dp_have = false;
     DevBuf<uint32_t> d_dp_hit;
     DevBuf<unsigned long long> d_dp_tot;
-    unsigned long long *h_dp_tot = nullptr;
-    hipEvent_t dp_time[3] = {nullptr, nullptr, nullptr};  // pfq_debug_last_deplete: the screen's classification, mark + scans + compaction
+    HostBuf<unsigned long long> h_dp_tot;
+    StageTimes<3> dp_time;  // pfq_debug_last_deplete: the screen's classification, mark + scans + compaction
     std::vector<uint32_t> out_dp_kept, out_dp_reason;
     // pfq_tree_set_adapters: the sets as the kernel takes them (ad_on: any is set) and what the adapter step of the last
     // pfq_prep_reads left: cut and which per read (scratch of one call, as d_pp_begin), the totals (h_pp_tot behind the kept
     // reads), the host copies of a PFQ_PREP_WANT_READS call.  ad_last: the last prep ran with adapters.
-    bool ad_on = false, ad_last = false, ad_last_reads = false, ad_timed = false;
+    bool ad_on = false, ad_last = false, ad_last_reads = false;
     pfq::AdaptSet ad_set{};
     DevBuf<uint32_t> d_pp_cut;
     DevBuf<uint8_t> d_pp_which;
     DevBuf<unsigned long long> d_pp_atot;
-    hipEvent_t ad_time[2] = {nullptr, nullptr};  // pfq_debug_last_adapters
+    StageTimes<2> ad_time;  // pfq_debug_last_adapters
     pfq_prep_adapters ad_out{};
     std::vector<uint32_t> out_pp_cut;
     std::vector<uint8_t> out_pp_which;
     // pfq_tree_set_mate_overlap (ov_on) and what the overlap step of the last paired pfq_prep_reads left: insert and mismatches
     // per fragment, the merged cut per read that the trim kernel takes (d_pp_ecut = min(adapter cut, ocut)), the totals and
     // the histogram (h_pp_tot behind the adapter totals).  ov_last: the last prep ran the step.
-    bool ov_on = false, ov_last = false, ov_last_reads = false, ov_timed = false;
+    bool ov_on = false, ov_last = false, ov_last_reads = false;
     uint32_t ov_min_overlap = 0, ov_max_error_percent = 0;
     DevBuf<uint32_t> d_pp_oins, d_pp_omm, d_pp_ecut;
     DevBuf<unsigned long long> d_pp_otot;
-    hipEvent_t ov_time[2] = {nullptr, nullptr};  // pfq_debug_last_overlap
+    StageTimes<2> ov_time;  // pfq_debug_last_overlap
     pfq_prep_overlap ov_out{};
     std::vector<uint64_t> out_ov_hist;
     std::vector<uint32_t> out_ov_insert, out_ov_mm;
@@ -554,11 +618,11 @@ struct pfq_tree {
     // (h_pp_tot behind the overlap's, then the length of the patch list) and, for a PFQ_PREP_WANT_READS call only, the
     // corrections per fragment, their scan and the patch list.  mc_last: the last prep ran the correction.
     uint32_t mc_high = 0, mc_low = 0;
-    bool mc_last = false, mc_last_reads = false, mc_timed = false;
+    bool mc_last = false, mc_last_reads = false;
     DevBuf<unsigned long long> d_pp_ctot, d_pp_cat;
     DevBuf<uint32_t> d_pp_ccnt;
     DevBuf<pfq::CorPatch> d_pp_patch;
-    hipEvent_t mc_time[2] = {nullptr, nullptr};  // pfq_debug_last_corrections: the scan and the patch kernel
+    StageTimes<2> mc_time;  // pfq_debug_last_corrections: the scan and the patch kernel
     pfq_prep_corrections mc_out{};
     std::vector<pfq_prep_patch> out_mc_patch;
     std::vector<uint32_t> out_lca;
@@ -1443,6 +1507,12 @@ double cover_estimate(const uint8_t *reg, uint32_t p) {
     return e <= 2.5 * dm && zeros > 0 ? dm * std::log(dm / (double)zeros) : e;
 }
 
+// The tree's own stream, for the uploads and stages that run beside the null stream's kernels; made by the first call that needs it.
+int ensure_copy_stream(pfq_tree &t) {
+    HIP_TRY(t.copy_stream.ensure(hipStreamNonBlocking));
+    return PFQ_OK;
+}
+
 int ensure_scratch(pfq_tree &t, uint64_t n_reads, bool want_hits) {
     HIP_TRY(t.d_stats.ensure(pfq::ST_N));
     HIP_TRY(t.d_cursors.ensure(CUR_ALLOC));
@@ -1459,19 +1529,17 @@ constexpr uint64_t CLASSIFY_MAX_BLOCKS = 4096;  // blocks of 4 waves; every wave
 
 // Scratch of the bucketed path.  false: not enough device memory, the caller stays on the direct kernel.
 bool ensure_bucket_scratch(pfq_tree &t, uint64_t n_reads, bool with_guards, uint64_t launch_waves, uint32_t pair_ahead) {
-    if (!t.h_pair_cursor) {
-        if (hipHostMalloc((void **)&t.h_pair_cursor, HINT_N * 8, hipHostMallocDefault) != hipSuccess) {
+    if (!t.h_pair_cursor.p) {  // (made last: where it exists, so does the event)
+        if (t.hint_ev.ensure(hipEventDisableTiming) != hipSuccess || t.h_pair_cursor.ensure(HINT_N) != hipSuccess) {
             (void)hipGetLastError();
-            t.h_pair_cursor = nullptr;
             return false;
         }
-        for (int i = 0; i < HINT_N; ++i) t.h_pair_cursor[i] = 0;
-        if (hipEventCreateWithFlags(&t.hint_ev, hipEventDisableTiming) != hipSuccess) return false;
+        for (int i = 0; i < HINT_N; ++i) t.h_pair_cursor.p[i] = 0;
     } else if (t.hint_reads && hipEventQuery(t.hint_ev) == hipSuccess) {
-        t.pairs_per_read = std::max(t.pairs_per_read, (double)t.h_pair_cursor[HINT_PAIRS] / (double)t.hint_reads);
-        if (t.hint_entry_cap) t.passes_hint = std::max<uint64_t>(1, (t.h_pair_cursor[HINT_TILE_ENTRIES] + t.hint_entry_cap - 1) / t.hint_entry_cap);
-        if (t.hint_counts) t.dirty_frac = (double)t.h_pair_cursor[HINT_DIRTY] / (double)std::max<unsigned long long>(1, t.h_pair_cursor[HINT_SORTED] & 0xffffffffull);
-        t.cand_per_read = (double)t.h_pair_cursor[HINT_CANDIDATES] / (double)t.hint_reads;
+        t.pairs_per_read = std::max(t.pairs_per_read, (double)t.h_pair_cursor.p[HINT_PAIRS] / (double)t.hint_reads);
+        if (t.hint_entry_cap) t.passes_hint = std::max<uint64_t>(1, (t.h_pair_cursor.p[HINT_TILE_ENTRIES] + t.hint_entry_cap - 1) / t.hint_entry_cap);
+        if (t.hint_counts) t.dirty_frac = (double)t.h_pair_cursor.p[HINT_DIRTY] / (double)std::max<unsigned long long>(1, t.h_pair_cursor.p[HINT_SORTED] & 0xffffffffull);
+        t.cand_per_read = (double)t.h_pair_cursor.p[HINT_CANDIDATES] / (double)t.hint_reads;
         t.have_cand_hint = true;
         t.hint_reads = 0;
     }
@@ -1531,7 +1599,7 @@ struct QueryRun {
     uint64_t launch_waves = 0, n_blocks = 0, miss_cap = 0, hit_cap = 0;
     // ---- one attempt
     pfq::QueryArgs a{};
-    hipEvent_t *ev = nullptr;
+    Event *ev = nullptr;
     uint32_t *cnt = nullptr, *off = nullptr, *cur = nullptr, *cntw = nullptr, *offw = nullptr, *curw = nullptr;  // bucket histograms / offsets / cursors
     uint4 *recs = nullptr;
     uint32_t n_slices = 1;
@@ -1575,7 +1643,7 @@ struct QueryRun {
         want_hits = user_hits || paired || want_lca || deplete;  // (fragments and LCAs are combined from the reads' hit lists)
         if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_ARG, "more than 2^31 reads in one block");
         // the scratch buffers are reused call after call: calls on one stream are ordered by it, a change of stream waits
-        if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
+        HIP_TRY(t.last_done.ensure(hipEventDisableTiming));
         if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipEventSynchronize(t.last_done));
         t.last_stream = st;
         t.have_last_stream = true;
@@ -1873,11 +1941,11 @@ struct QueryRun {
             HIP_TRY(hipGetLastError());
         }
         if (bucketed) {  // how many pair slots this call used, for the next call's sizing
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_PAIRS, t.d_cursors.p + CUR_PAIR, 16, hipMemcpyDeviceToHost, st));  // and HINT_TILE_ENTRIES
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_DIRTY, t.d_cursors.p + CUR_DIRTY, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_CANDIDATES, t.d_stats.p + pfq::ST_CANDIDATES, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor.p + HINT_PAIRS, t.d_cursors.p + CUR_PAIR, 16, hipMemcpyDeviceToHost, st));  // and HINT_TILE_ENTRIES
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor.p + HINT_DIRTY, t.d_cursors.p + CUR_DIRTY, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(t.h_pair_cursor.p + HINT_CANDIDATES, t.d_stats.p + pfq::ST_CANDIDATES, 8, hipMemcpyDeviceToHost, st));
             if (n_reads && nl)  // ... of how many sorted pairs (the pair cursor also counts partly used reservations)
-                HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_SORTED, t.d_bucket.p + 2 * (nc << t.last_sub_log2), 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(t.h_pair_cursor.p + HINT_SORTED, t.d_bucket.p + 2 * (nc << t.last_sub_log2), 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(t.hint_ev, st));
             t.hint_reads = n_reads;
         }
@@ -2155,9 +2223,9 @@ struct QueryRun {
                 // passes (if any) are certified by the record kernel below — exact either way.
                 uint64_t n_passes = std::min<uint64_t>(std::max<uint64_t>(1, t.passes_hint), 256);  // (more: the record kernel takes the rest)
                 if (block_mode) {  // the fallback of block mode is slow: wait for the plan and launch every pass it needs
-                    HIP_TRY(hipMemcpyAsync(t.h_pair_cursor + HINT_PLAN, t.d_cursors.p + CUR_TILE_ENTRIES, 8, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipMemcpyAsync(t.h_pair_cursor.p + HINT_PLAN, t.d_cursors.p + CUR_TILE_ENTRIES, 8, hipMemcpyDeviceToHost, st));
                     HIP_TRY(hipStreamSynchronize(st));
-                    n_passes = ta.entry_cap ? std::min<uint64_t>(std::max<uint64_t>(1, (t.h_pair_cursor[HINT_PLAN] + ta.entry_cap - 1) / ta.entry_cap), 256) : 1;
+                    n_passes = ta.entry_cap ? std::min<uint64_t>(std::max<uint64_t>(1, (t.h_pair_cursor.p[HINT_PLAN] + ta.entry_cap - 1) / ta.entry_cap), 256) : 1;
                 }
                 for (uint64_t p = 0; p < n_passes; ++p) {
                     ta.pass = (uint32_t)p;
@@ -2642,6 +2710,17 @@ int query_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off, uint6
     if (t.last_done && t.have_last_stream && t.last_stream == st) HIP_TRY(hipEventRecord(t.last_done, st));  // (what waits for this call)
     return rc;
 }
+// What every pfq_debug_last_*_ms does: the intervals between a timer's events, where the call that recorded them has stood
+// (`also`: what else the getter asks of the tree); else PFQ_ERR_STATE with `refusal`.
+template <int N>
+int last_stage_ms(pfq_tree *tree, double *ms, StageTimes<N> pfq_tree::*timer, bool also, const char *refusal) {
+    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
+    if (!also || !(tree->*timer).valid) return fail(PFQ_ERR_STATE, refusal);
+    PFQ_TRY(use_device(tree->device));
+    HIP_TRY((tree->*timer).read(ms));
+    return PFQ_OK;
+}
+
 // Waits for the last query call's work (its stream may since have been destroyed by the caller).
 int wait_last_call(pfq_tree &t) {
     if (t.last_done) HIP_TRY(hipEventSynchronize(t.last_done));
@@ -2679,7 +2758,7 @@ int query_frames_device(pfq_tree &t, const uint8_t *d_seq, const uint64_t *d_off
     t.h_fr_off.p[0] = 0;
     if (!n_seqs) return PFQ_OK;
     // (the scratch is reused call after call: as in QueryRun::plan, a call on another stream waits for the last one)
-    if (!t.last_done) HIP_TRY(hipEventCreateWithFlags(&t.last_done, hipEventDisableTiming));
+    HIP_TRY(t.last_done.ensure(hipEventDisableTiming));
     if (t.have_last_stream && t.last_stream != st) HIP_TRY(hipEventSynchronize(t.last_done));
     t.last_stream = st;
     t.have_last_stream = true;
@@ -3265,30 +3344,19 @@ int pfq_tree_insert(pfq_tree *tree, const uint8_t *seq, uint64_t len, const char
     // kernels of genome i), its k-mers are inserted into a cleared row
     const uint32_t new_row = (uint32_t)t.n_rows++, int_row = (uint32_t)t.n_rows++;  // (the internal node's row stays unused by the first leaf of a tree)
     const uint32_t slot = t.gseq_next++ & 3u;
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (!t.gseq_free[slot]) {
-        HIP_TRY(hipEventCreateWithFlags(&t.gseq_free[slot], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&t.gseq_copied[slot], hipEventDisableTiming));
-    } else HIP_TRY(hipEventSynchronize(t.gseq_free[slot]));   // the insertion that used these buffers four calls ago has read them
+    PFQ_TRY(ensure_copy_stream(t));
+    HIP_TRY(t.gseq_copied[slot].ensure(hipEventDisableTiming));
+    if (t.gseq_free[slot]) HIP_TRY(hipEventSynchronize(t.gseq_free[slot]));  // the insertion that used these buffers four calls ago has read them
+    HIP_TRY(t.gseq_free[slot].ensure(hipEventDisableTiming));
     if (t.d_gseq[slot].n < len + 16) {
         HIP_TRY(t.d_gseq[slot].ensure(std::max<size_t>(len + 16, 2 * t.d_gseq[slot].n)));
     }
-    if (t.h_gseq_n[slot] < len + 16) {
-        if (t.h_gseq[slot]) HIP_TRY(hipHostFree(t.h_gseq[slot]));
-        t.h_gseq[slot] = nullptr;
-        t.h_gseq_n[slot] = 0;
-        const size_t want = std::max<size_t>(len + 16, 2 * t.h_gseq_n[slot]);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_gseq[slot]), want, hipHostMallocDefault));
-        t.h_gseq_n[slot] = want;
-    }
+    HIP_TRY(t.h_gseq[slot].ensure(len + 16));
     // (through page-locked staging on a stream of its own: the copy neither waits for the kernels of the insertions before
     // nor holds the caller — the kernels wait for it by event)
     if (len) {
-        memcpy(t.h_gseq[slot], seq, len);
-        HIP_TRY(hipMemcpyAsync(t.d_gseq[slot].p, t.h_gseq[slot], len, hipMemcpyHostToDevice, t.copy_stream));
+        memcpy(t.h_gseq[slot].p, seq, len);
+        HIP_TRY(hipMemcpyAsync(t.d_gseq[slot].p, t.h_gseq[slot].p, len, hipMemcpyHostToDevice, t.copy_stream));
     }
     HIP_TRY(hipEventRecord(t.gseq_copied[slot], t.copy_stream));
     HIP_TRY(hipStreamWaitEvent(nullptr, t.gseq_copied[slot], 0));
@@ -3574,44 +3642,6 @@ void pfq_tree_close(pfq_tree *tree) {
     if (!tree) return;
     (void)hipSetDevice(tree->device);
     (void)hipDeviceSynchronize();
-    if (tree->copy_stream) {
-        (void)hipStreamDestroy(tree->copy_stream);
-        for (auto e : tree->in_free) (void)hipEventDestroy(e);
-    }
-    for (auto e : tree->gseq_free)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->gseq_copied)
-        if (e) (void)hipEventDestroy(e);
-    for (auto h : tree->h_gseq)
-        if (h) (void)hipHostFree(h);
-    if (tree->h_pair_cursor) (void)hipHostFree(tree->h_pair_cursor);
-    if (tree->hint_ev) (void)hipEventDestroy(tree->hint_ev);
-    if (tree->last_done) (void)hipEventDestroy(tree->last_done);
-    for (auto e : tree->tx_free)
-        if (e) (void)hipEventDestroy(e);
-    if (tree->tx_parsed) (void)hipEventDestroy(tree->tx_parsed);
-    if (tree->h_tx_res) (void)hipHostFree(tree->h_tx_res);
-    for (auto e : tree->gz_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->df_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->pp_free)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->pp_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->ad_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->ov_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->mc_time)
-        if (e) (void)hipEventDestroy(e);
-    for (auto e : tree->fm_time)
-        if (e) (void)hipEventDestroy(e);
-    if (tree->pp_ready) (void)hipEventDestroy(tree->pp_ready);
-    if (tree->h_pp_tot) (void)hipHostFree(tree->h_pp_tot);
-    for (auto e : tree->dp_time)
-        if (e) (void)hipEventDestroy(e);
-    if (tree->h_dp_tot) (void)hipHostFree(tree->h_dp_tot);
     delete tree;
 }
 
@@ -3619,14 +3649,12 @@ void pfq_tree_close(pfq_tree *tree) {
 // copy of this block runs while the kernels of the previous block (which read the other buffer) are still at work.  A call
 // that wants no hits returns once its kernels are queued; counts are read by calls that synchronise (pfq_leaf_counts,
 // pfq_last_stats, pfq_tree_close).  slot: which pair (d_seq / d_off or d_seq2 / d_off2) holds the block; the caller records
-// in_free[slot] behind the kernels that read it.
+// the set as read (in_sets.read_by) behind the kernels that read it.
 static int stage_input(pfq_tree &t, const uint8_t *seq, const uint64_t *offsets, uint64_t n_reads, uint64_t total, int &slot) {
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    slot = (t.in_slot ^= 1);
-    if (t.in_used[slot]) HIP_TRY(hipEventSynchronize(t.in_free[slot]));  // the kernels that read this buffer are done
+    PFQ_TRY(ensure_copy_stream(t));
+    HIP_TRY(t.in_sets.ensure());
+    slot = t.in_sets.cur = t.in_sets.other();
+    HIP_TRY(t.in_sets.wait(slot));  // the kernels that read this buffer are done
     DevBuf<uint8_t> &ds = slot ? t.d_seq2 : t.d_seq;
     DevBuf<uint64_t> &dof = slot ? t.d_off2 : t.d_off;
     HIP_TRY(ds.ensure(total + 16));
@@ -3694,8 +3722,7 @@ int pfq_query_batch(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets,
     int slot = 0;
     PFQ_TRY(stage_input(t, seq, offsets, n_reads, total, slot));
     PFQ_TRY(query_device(t, (slot ? t.d_seq2 : t.d_seq).p, (slot ? t.d_off2 : t.d_off).p, n_reads, total, threshold, flags, nullptr, hits));
-    HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
-    t.in_used[slot] = true;
+    HIP_TRY(t.in_sets.read_by(slot, nullptr));
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
     return PFQ_OK;
 }
@@ -3734,8 +3761,7 @@ int pfq_query_frames(pfq_tree *tree, const uint8_t *seq, const uint64_t *offsets
     int slot = 0;
     PFQ_TRY(stage_input(t, seq, offsets, n_seqs, n_seqs ? offsets[n_seqs] : 0, slot));
     PFQ_TRY(frames_call(t, (slot ? t.d_seq2 : t.d_seq).p, (slot ? t.d_off2 : t.d_off).p, n_seqs, frame, step, threshold, nullptr, out));
-    HIP_TRY(hipEventRecord(t.in_free[slot], nullptr));
-    t.in_used[slot] = true;
+    HIP_TRY(t.in_sets.read_by(slot, nullptr));
     return PFQ_OK;
 }
 
@@ -3750,19 +3776,14 @@ static uint32_t text_tile(const Knobs &k) {
 // classification that read it), room for n bytes of text in d_tx_text.  From here there is no block to query until the parse
 // has succeeded.
 static int text_parse_begin(pfq_tree &t, uint32_t n, int *slot_out) {
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (!t.tx_parsed) {
-        HIP_TRY(hipEventCreateWithFlags(&t.tx_parsed, hipEventDisableTiming));
-        for (auto &e : t.tx_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_tx_res), pfq::TEXT_RES_N * 8, hipHostMallocDefault));
-        HIP_TRY(t.d_tx_res.ensure(pfq::TEXT_RES_N));
-        HIP_TRY(t.d_tx_bad.ensure(1));
-    }
-    const int slot = t.tx_slot ^ 1;
-    if (t.tx_used[slot]) HIP_TRY(hipEventSynchronize(t.tx_free[slot]));  // the classification that read this set is done
+    PFQ_TRY(ensure_copy_stream(t));
+    HIP_TRY(t.tx_parsed.ensure(hipEventDisableTiming));
+    HIP_TRY(t.tx_sets.ensure());
+    HIP_TRY(t.h_tx_res.ensure(pfq::TEXT_RES_N));
+    HIP_TRY(t.d_tx_res.ensure(pfq::TEXT_RES_N));
+    HIP_TRY(t.d_tx_bad.ensure(1));
+    const int slot = t.tx_sets.other();
+    HIP_TRY(t.tx_sets.wait(slot));  // the classification that read this set is done
     t.tx_have = false;  // (until this parse has succeeded there is no block to query)
     t.fm_rows = false;
     HIP_TRY(t.d_tx_seq[slot].ensure((size_t)n + 16));
@@ -3787,10 +3808,10 @@ static int text_parse_staged(pfq_tree &t, int slot, uint32_t n, uint8_t first, u
         HIP_TRY(t.d_tx_sums.ensure((size_t)n_tiles / 4096 + 2));
         pfq::launch_text_count(t.d_tx_text.p, n, tile, t.d_tx_blk.p, st);
         pfq::launch_scan_u32(t.d_tx_blk.p, n_tiles, t.d_tx_sums.p, t.d_tx_blk_off.p, st);
-        HIP_TRY(hipMemcpyAsync(t.h_tx_res, t.d_tx_blk_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_tx_res.p, t.d_tx_blk_off.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffer is free from here; the line count sizes what follows)
         unterminated = final && last != '\n';
-        n_lines = (uint32_t)t.h_tx_res[0] + (unterminated ? 1u : 0u);
+        n_lines = (uint32_t)t.h_tx_res.p[0] + (unterminated ? 1u : 0u);
     }
     // what needs no kernel: empty text; text without a considered line; FASTA that does not begin with a header
     bool trivial = true;
@@ -3825,8 +3846,8 @@ static int text_parse_staged(pfq_tree &t, int slot, uint32_t n, uint8_t first, u
         pfq::launch_text_lines(t.d_tx_text.p, n, tile, t.d_tx_blk_off.p, t.d_tx_line.p, n_lines, unterminated, st);
         if (fastq) {
             const uint32_t n_full = n_lines / 4;
-            t.h_tx_res[1] = n_full;  // (little-endian: its low word is what is copied; the result lands here only behind this copy)
-            HIP_TRY(hipMemcpyAsync(t.d_tx_bad.p, t.h_tx_res + 1, 4, hipMemcpyHostToDevice, st));
+            t.h_tx_res.p[1] = n_full;  // (little-endian: its low word is what is copied; the result lands here only behind this copy)
+            HIP_TRY(hipMemcpyAsync(t.d_tx_bad.p, t.h_tx_res.p + 1, 4, hipMemcpyHostToDevice, st));
         } else {
             HIP_TRY(t.d_tx_hdr.ensure(n_lines));
             HIP_TRY(t.d_tx_rec_idx.ensure((size_t)n_lines + 1));
@@ -3842,12 +3863,12 @@ static int text_parse_staged(pfq_tree &t, int slot, uint32_t n, uint8_t first, u
         }
         pfq::launch_text_finish(a, t.d_tx_seq[slot].p, t.d_tx_off[slot].p, want_rec ? t.d_tx_rec_begin.p : nullptr, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(t.h_tx_res, t.d_tx_res.p, pfq::TEXT_RES_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_tx_res.p, t.d_tx_res.p, pfq::TEXT_RES_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        out->n_records = t.h_tx_res[pfq::TEXT_RES_RECORDS];
-        out->consumed = t.h_tx_res[pfq::TEXT_RES_CONSUMED];
-        out->n_bases = t.h_tx_res[pfq::TEXT_RES_BASES];
-        out->stop = (uint32_t)t.h_tx_res[pfq::TEXT_RES_STOP];
+        out->n_records = t.h_tx_res.p[pfq::TEXT_RES_RECORDS];
+        out->consumed = t.h_tx_res.p[pfq::TEXT_RES_CONSUMED];
+        out->n_bases = t.h_tx_res.p[pfq::TEXT_RES_BASES];
+        out->stop = (uint32_t)t.h_tx_res.p[pfq::TEXT_RES_STOP];
         if (want_rec) {
             t.out_rec_begin.resize(out->n_records + 1);
             HIP_TRY(hipMemcpyAsync(t.out_rec_begin.data(), t.d_tx_rec_begin.p, (out->n_records + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -3856,7 +3877,7 @@ static int text_parse_staged(pfq_tree &t, int slot, uint32_t n, uint8_t first, u
     HIP_TRY(hipEventRecord(t.tx_parsed, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (want_rec) out->rec_begin = t.out_rec_begin.data();
-    t.tx_slot = slot;
+    t.tx_sets.cur = slot;
     t.tx_records = out->n_records;
     t.tx_bases = out->n_bases;
     t.tx_fastq = fastq ? 1 : 0;
@@ -3887,11 +3908,10 @@ int pfq_text_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hi
     if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_text_query before a pfq_text_parse on this tree");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
-    const int slot = t.tx_slot;
+    const int slot = t.tx_sets.cur;
     HIP_TRY(hipStreamWaitEvent(nullptr, t.tx_parsed, 0));  // (the classification is ordered behind the parse on the device)
     const int rc = query_device(t, t.d_tx_seq[slot].p, t.d_tx_off[slot].p, t.tx_records, t.tx_bases, threshold, flags, nullptr, hits);
-    HIP_TRY(hipEventRecord(t.tx_free[slot], nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
-    t.tx_used[slot] = true;
+    HIP_TRY(t.tx_sets.read_by(slot, nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
     PFQ_TRY(rc);
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
     t.fm_rows = (flags & PFQ_WANT_HITS) && !(flags & PFQ_PAIRED);  // (pfq_text_format reads these rows)
@@ -3904,8 +3924,8 @@ int pfq_debug_text_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
     if (!tree->tx_have) return fail(PFQ_ERR_STATE, "pfq_debug_text_csr before a pfq_text_parse on this tree");
     PFQ_TRY(use_device(tree->device));
     const pfq_tree &t = *tree;
-    if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_slot].p, t.tx_bases, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_slot].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
+    if (t.tx_bases) HIP_TRY(hipMemcpy(seq_out, t.d_tx_seq[t.tx_sets.cur].p, t.tx_bases, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off_out, t.d_tx_off[t.tx_sets.cur].p, (t.tx_records + 1) * 8, hipMemcpyDeviceToHost));
     return PFQ_OK;
 }
 
@@ -3969,16 +3989,12 @@ int pfq_text_inflate(pfq_tree *tree, const uint8_t *gz, uint64_t len, uint64_t m
     std::vector<uint32_t> trailer_crc;
     PFQ_TRY(gz_walk("pfq_text_inflate", gz, len, max_text, flags, t.gz_begin, t.gz_text_begin, &t.gz_mem, &trailer_crc, &out->members));
     PFQ_TRY(use_device(t.device));
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    for (auto &e : t.gz_time)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    PFQ_TRY(ensure_copy_stream(t));
+    HIP_TRY(t.gz_time.ensure());
     hipStream_t st = t.copy_stream;
     const uint64_t n = out->members.n_members, consumed = out->members.consumed;
     t.gz_res.assign(2 * n, 0);
-    t.gz_timed = false;
+    t.gz_time.valid = false;
     if (n) {
         // (the kernel stages whole pieces of GZ_STAGE bytes: the allocation reaches beyond the last one it can touch)
         HIP_TRY(t.d_gz.ensure((consumed + pfq::GZ_STAGE - 1) / pfq::GZ_STAGE * pfq::GZ_STAGE + pfq::GZ_STAGE));
@@ -3991,16 +4007,16 @@ int pfq_text_inflate(pfq_tree *tree, const uint8_t *gz, uint64_t len, uint64_t m
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t.device));
             blocks = 2 * std::max(cus, 1);
         }
-        HIP_TRY(hipEventRecord(t.gz_time[0], st));
+        HIP_TRY(t.gz_time.mark(0, st));
         HIP_TRY(hipMemcpyAsync(t.d_gz.p, gz, consumed, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(t.d_gz_mem.p, t.gz_mem.data(), n * sizeof(pfq::GzMember), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(t.gz_time[1], st));
+        HIP_TRY(t.gz_time.mark(1, st));
         pfq::launch_gz_inflate(t.d_gz.p, t.d_gz_mem.p, n, t.d_gz_text.p, t.d_gz_res.p, (uint32_t)blocks, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(t.gz_time[2], st));
+        HIP_TRY(t.gz_time.mark(2, st));
         HIP_TRY(hipMemcpyAsync(t.gz_res.data(), t.d_gz_res.p, 2 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        t.gz_timed = true;
+        t.gz_time.valid = true;
     }
     t.gz_status.resize(n);
     uint64_t good = n;
@@ -4066,15 +4082,8 @@ int pfq_text_read(pfq_tree *tree, uint64_t from, uint64_t n, uint8_t *dst) {
 }
 
 int pfq_debug_last_inflate(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->gz_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_inflate before a pfq_text_inflate with members on this tree");
-    PFQ_TRY(use_device(tree->device));
-    for (int i = 0; i < 2; i++) {
-        float f = 0;
-        HIP_TRY(hipEventElapsedTime(&f, tree->gz_time[i], tree->gz_time[i + 1]));
-        ms[i] = f;
-    }
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::gz_time, true,
+                         "pfq_debug_last_inflate before a pfq_text_inflate with members on this tree");
 }
 
 // ---- text output ----------------------------------------------------------------------------------------------------------
@@ -4112,7 +4121,7 @@ static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
     out->neg = gz ? nullptr : t.h_fm_out[1].p;
     t.out_fm_left.clear();
     out->left = t.out_fm_left.data();
-    t.fm_timed = false;
+    t.fm_time.valid = false;
     if (!n) {
         if (gz)
             for (int s = 0; s < 2; ++s) PFQ_TRY(deflate_device(t, nullptr, nullptr, 0, nullptr, 0, s, gz[s]));
@@ -4120,8 +4129,7 @@ static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
     }
     const bool timed = t.knobs.fmt_time == 1;
     if (timed)
-        for (auto &e : t.fm_time)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(t.fm_time.ensure());
     {  // the leaves' names, uploaded when they are not the ones on the device
         std::vector<uint8_t> names;
         std::vector<uint32_t> name_off(1, 0);
@@ -4166,8 +4174,8 @@ static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
     a.flags = flags;
     a.hash_bits = t.knobs.fmt_hash_bits >= 1 && t.knobs.fmt_hash_bits <= 64 ? (uint32_t)t.knobs.fmt_hash_bits : 64u;
     a.grid = t.knobs.fmt_grid >= 1 && t.knobs.fmt_grid <= 65535 ? (uint32_t)t.knobs.fmt_grid : 0u;
-    a.seq = t.d_tx_seq[t.tx_slot].p;
-    a.seq_off = t.d_tx_off[t.tx_slot].p;
+    a.seq = t.d_tx_seq[t.tx_sets.cur].p;
+    a.seq_off = t.d_tx_off[t.tx_sets.cur].p;
     a.row_off = t.d_hit_off.p;
     a.row_leaves = t.d_hit_leaves.p;
     a.names = t.d_fm_names.p;
@@ -4183,14 +4191,14 @@ static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
         a.len[s] = t.d_fm_len[s].p;
         a.dst[s] = t.d_fm_dst[s].p;
     }
-    if (timed) HIP_TRY(hipEventRecord(t.fm_time[0], st));
+    if (timed) HIP_TRY(t.fm_time.mark(0, st));
     pfq::launch_fmt_ids(a, st);
-    if (timed) HIP_TRY(hipEventRecord(t.fm_time[1], st));
+    if (timed) HIP_TRY(t.fm_time.mark(1, st));
     pfq::launch_fmt_sizes(a, nl > 64, st);
     for (int s = 0; s < 2; ++s) pfq::launch_scan_u32(a.len[s], n, t.d_fm_sums.p, t.d_fm_dst[s].p, st);
     pfq::launch_fmt_bounds(a, st);
     HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(t.fm_time[2], st));
+    if (timed) HIP_TRY(t.fm_time.mark(2, st));
     HIP_TRY(hipMemcpyAsync(t.h_fm_small.p, t.d_fm_small.p, n_small * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));  // (the totals size the streams)
     const unsigned long long *res = t.h_fm_small.p, *bounds = res + pfq::FMT_RES_N;
@@ -4204,11 +4212,11 @@ static int text_format(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
     }
     pfq::launch_fmt_emit(a, st);
     HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(t.fm_time[3], st));
+    if (timed) HIP_TRY(t.fm_time.mark(3, st));
     for (int s = 0; s < 2; ++s)
         if (total[s] && !gz) HIP_TRY(hipMemcpyAsync(t.h_fm_out[s].p, t.d_fm_out[s].p, total[s], hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    t.fm_timed = timed;
+    t.fm_time.valid = timed;
     // the left runs, from the block states
     if (head) t.out_fm_left.push_back(pfq_text_left{0, head, 0, 0, PFQ_LEFT_HEAD, 0});
     for (uint32_t b = 0; b < n_whole; ++b)
@@ -4260,12 +4268,8 @@ static int deflate_device(pfq_tree &t, const uint8_t *d_text, const uint8_t *h_t
     out->n_members = n;
     out->n_pieces = n_cuts + 1;
     if (n) {
-        if (!t.copy_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-            for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        for (auto &e : t.df_time)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+        PFQ_TRY(ensure_copy_stream(t));
+        HIP_TRY(t.df_time.ensure());
         hipStream_t st = t.copy_stream;
         long long blocks = t.knobs.deflate_blocks;
         if (blocks < 1 || blocks > 65535) {
@@ -4286,14 +4290,14 @@ static int deflate_device(pfq_tree &t, const uint8_t *d_text, const uint8_t *h_t
         HIP_TRY(t.d_df_sums.ensure(n / 4096 + 2));
         HIP_TRY(t.d_df_gz[s].ensure(len + 31 * n + 16));
         HIP_TRY(t.h_df_off.ensure(n + 1));
-        t.df_timed = false;
-        HIP_TRY(hipEventRecord(t.df_time[0], st));
+        t.df_time.valid = false;
+        HIP_TRY(t.df_time.mark(0, st));
         if (h_text) HIP_TRY(hipMemcpyAsync(t.d_df_text.p, h_text, len, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(t.d_df_mem.p, t.df_mem.data(), n * sizeof(pfq::BgzfMember), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(t.df_time[1], st));
+        HIP_TRY(t.df_time.mark(1, st));
         pfq::launch_bgzf_deflate(d_text, t.d_df_mem.p, n, t.d_df_tokens.p, t.d_df_slots.p, t.d_df_sizes.p, (uint32_t)blocks, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(t.df_time[2], st));
+        HIP_TRY(t.df_time.mark(2, st));
         pfq::launch_scan_u32(t.d_df_sizes.p, n, t.d_df_sums.p, t.d_df_off.p, st);
         pfq::launch_bgzf_gather(t.d_df_slots.p, t.d_df_off.p, n, t.d_df_gz[s].p, st);
         HIP_TRY(hipGetLastError());
@@ -4303,9 +4307,9 @@ static int deflate_device(pfq_tree &t, const uint8_t *d_text, const uint8_t *h_t
         if (total > len + 31 * n) return fail(PFQ_ERR_DEVICE, "deflate: members of " + std::to_string(total) + " bytes for " + std::to_string(len) + " of text");
         HIP_TRY(t.h_df_gz[s].ensure(total + 1));
         HIP_TRY(hipMemcpyAsync(t.h_df_gz[s].p, t.d_df_gz[s].p, total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(t.df_time[3], st));
+        HIP_TRY(t.df_time.mark(3, st));
         HIP_TRY(hipStreamSynchronize(st));
-        t.df_timed = true;
+        t.df_time.valid = true;
         for (uint64_t m = 0; m <= n; ++m) member_begin[m] = t.h_df_off.p[m];
         out->gz_bytes = total;
     }
@@ -4333,27 +4337,13 @@ int pfq_text_format_gz(pfq_tree *tree, uint64_t first_index, uint32_t block, uin
 }
 
 int pfq_debug_last_deflate(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->df_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_deflate before a deflate call with members on this tree");
-    PFQ_TRY(use_device(tree->device));
-    for (int i = 0; i < 3; i++) {
-        float f = 0;
-        HIP_TRY(hipEventElapsedTime(&f, tree->df_time[i], tree->df_time[i + 1]));
-        ms[i] = f;
-    }
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::df_time, true,
+                         "pfq_debug_last_deflate before a deflate call with members on this tree");
 }
 
 int pfq_debug_last_format(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->fm_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_format before a pfq_text_format with records and PFQ_FMT_TIME=1 on this tree");
-    PFQ_TRY(use_device(tree->device));
-    for (int i = 0; i < 3; ++i) {
-        float v = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&v, tree->fm_time[i], tree->fm_time[i + 1]));
-        ms[i] = v;
-    }
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::fm_time, true,
+                         "pfq_debug_last_format before a pfq_text_format with records and PFQ_FMT_TIME=1 on this tree");
 }
 
 // ---- read preprocessing ----------------------------------------------------------------------------------------------------
@@ -4375,28 +4365,23 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
     if (n_reads >= (1ull << 31) - 1024) return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: 2^31 - 1024 reads or more in one block: ask in pieces");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
-    if (!t.copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&t.copy_stream, hipStreamNonBlocking));
-        for (auto &e : t.in_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (!t.pp_ready) {
-        HIP_TRY(hipEventCreateWithFlags(&t.pp_ready, hipEventDisableTiming));
-        for (auto &e : t.pp_free) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : t.pp_time) HIP_TRY(hipEventCreate(&e));
-        for (auto &e : t.ad_time) HIP_TRY(hipEventCreate(&e));
-        for (auto &e : t.ov_time) HIP_TRY(hipEventCreate(&e));
-        for (auto &e : t.mc_time) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_pp_tot), (at_ctot + pfq::COR_TOT_N + 1) * 8, hipHostMallocDefault));
-        HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
-    }
+    PFQ_TRY(ensure_copy_stream(t));
+    HIP_TRY(t.pp_ready.ensure(hipEventDisableTiming));
+    HIP_TRY(t.pp_sets.ensure());
+    HIP_TRY(t.pp_time.ensure());
+    HIP_TRY(t.ad_time.ensure());
+    HIP_TRY(t.ov_time.ensure());
+    HIP_TRY(t.mc_time.ensure());
+    HIP_TRY(t.h_pp_tot.ensure(at_ctot + pfq::COR_TOT_N + 1));
+    HIP_TRY(t.d_pp_tot.ensure(pfq::PREP_TOT_N));
     const bool adapters = t.ad_on;
     t.ad_last = false;
     t.ov_last = false;
     t.mc_last = false;
     uint64_t n_patches = 0;
     hipStream_t st = t.copy_stream;
-    const int slot = t.pp_slot ^ 1;
-    if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));  // the classification that read this set is done
+    const int slot = t.pp_sets.other();
+    HIP_TRY(t.pp_sets.wait(slot));  // the classification that read this set is done
     t.pp_have = false;  // (until this prep has succeeded there is no block to query)
     const uint64_t total = n_reads ? offsets[n_reads] : 0;
     *out = pfq_prep{};
@@ -4458,9 +4443,9 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             ad.which = t.d_pp_which.p;
             ad.totals = t.d_pp_atot.p;
             ad.set = t.ad_set;
-            HIP_TRY(hipEventRecord(t.ad_time[0], st));
+            HIP_TRY(t.ad_time.mark(0, st));
             pfq::launch_prep_adapter(ad, st);
-            HIP_TRY(hipEventRecord(t.ad_time[1], st));
+            HIP_TRY(t.ad_time.mark(1, st));
             a.cut = t.d_pp_cut.p;
         }
         if (overlap) {  // behind the adapter step: the cut the steps below see is the smaller of the two
@@ -4496,53 +4481,53 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
                     ov.cor_count = t.d_pp_ccnt.p;
                 }
             }
-            HIP_TRY(hipEventRecord(t.ov_time[0], st));
+            HIP_TRY(t.ov_time.mark(0, st));
             pfq::launch_prep_overlap(ov, st);
-            HIP_TRY(hipEventRecord(t.ov_time[1], st));
+            HIP_TRY(t.ov_time.mark(1, st));
             if (correct && want_reads) {
                 // the list's length decides its buffer, so the host waits for it here: once more than a call without the list
-                HIP_TRY(hipEventRecord(t.mc_time[0], st));
+                HIP_TRY(t.mc_time.mark(0, st));
                 pfq::launch_scan_u32(t.d_pp_ccnt.p, n_reads / 2, t.d_pp_sums.p, t.d_pp_cat.p, st);
-                HIP_TRY(hipMemcpyAsync(t.h_pp_tot + at_ctot + pfq::COR_TOT_N, t.d_pp_cat.p + n_reads / 2, 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p + at_ctot + pfq::COR_TOT_N, t.d_pp_cat.p + n_reads / 2, 8, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
-                n_patches = t.h_pp_tot[at_ctot + pfq::COR_TOT_N];
+                n_patches = t.h_pp_tot.p[at_ctot + pfq::COR_TOT_N];
                 if (n_patches) {
                     HIP_TRY(t.d_pp_patch.ensure(n_patches));
                     ov.cor_at = t.d_pp_cat.p;
                     ov.patches = t.d_pp_patch.p;
                     pfq::launch_prep_patches(ov, st);
                 }
-                HIP_TRY(hipEventRecord(t.mc_time[1], st));
+                HIP_TRY(t.mc_time.mark(1, st));
             }
             a.cut = t.d_pp_ecut.p;
         }
-        HIP_TRY(hipEventRecord(t.pp_time[0], st));
+        HIP_TRY(t.pp_time.mark(0, st));
         pfq::launch_prep_trim(a, st);
         pfq::launch_prep_mark(a, st);
-        HIP_TRY(hipEventRecord(t.pp_time[1], st));
+        HIP_TRY(t.pp_time.mark(1, st));
         pfq::launch_scan_u32(t.d_pp_keep.p, n_reads, t.d_pp_sums.p, t.d_pp_kpos.p, st);
         pfq::launch_scan_u32(t.d_pp_klen.p, n_reads, t.d_pp_sums.p, t.d_pp_koff.p, st);
-        HIP_TRY(hipEventRecord(t.pp_time[2], st));
+        HIP_TRY(t.pp_time.mark(2, st));
         pfq::launch_prep_gather(a, st);
-        HIP_TRY(hipEventRecord(t.pp_time[3], st));
+        HIP_TRY(t.pp_time.mark(3, st));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(t.h_pp_tot, t.d_pp_tot.p, pfq::PREP_TOT_N * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
-        if (adapters) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1, t.d_pp_atot.p, pfq::ADAPT_TOT_N * 8, hipMemcpyDeviceToHost, st));
-        if (overlap) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N, t.d_pp_otot.p, n_otot * 8, hipMemcpyDeviceToHost, st));
-        if (correct) HIP_TRY(hipMemcpyAsync(t.h_pp_tot + at_ctot, t.d_pp_ctot.p, pfq::COR_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p, t.d_pp_tot.p, pfq::PREP_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p + pfq::PREP_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        if (adapters) HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p + pfq::PREP_TOT_N + 1, t.d_pp_atot.p, pfq::ADAPT_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        if (overlap) HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N, t.d_pp_otot.p, n_otot * 8, hipMemcpyDeviceToHost, st));
+        if (correct) HIP_TRY(hipMemcpyAsync(t.h_pp_tot.p + at_ctot, t.d_pp_ctot.p, pfq::COR_TOT_N * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));  // (the caller's buffers are free from here)
-        t.pp_timed = true;
-        t.ad_timed = adapters;
-        t.ov_timed = overlap;
-        t.mc_timed = correct && want_reads;
-        if (t.h_pp_tot[pfq::PREP_TOT_ERR])
+        t.pp_time.valid = true;
+        t.ad_time.valid = adapters;
+        t.ov_time.valid = overlap;
+        t.mc_time.valid = correct && want_reads;
+        if (t.h_pp_tot.p[pfq::PREP_TOT_ERR])
             return fail(PFQ_ERR_UNSUPPORTED, "pfq_prep_reads: a read of 2^32 bases or more (or offsets that do not ascend)");
-        n_kept = t.h_pp_tot[pfq::PREP_TOT_N];
-        for (int c = 0; c < 5; ++c) out->n_reason[c] = t.h_pp_tot[pfq::PREP_TOT_REASON + c];
-        out->bases_in = t.h_pp_tot[pfq::PREP_TOT_BASES_IN];
-        out->bases_kept = t.h_pp_tot[pfq::PREP_TOT_BASES_KEPT];
-        out->n_trimmed = t.h_pp_tot[pfq::PREP_TOT_TRIMMED];
+        n_kept = t.h_pp_tot.p[pfq::PREP_TOT_N];
+        for (int c = 0; c < 5; ++c) out->n_reason[c] = t.h_pp_tot.p[pfq::PREP_TOT_REASON + c];
+        out->bases_in = t.h_pp_tot.p[pfq::PREP_TOT_BASES_IN];
+        out->bases_kept = t.h_pp_tot.p[pfq::PREP_TOT_BASES_KEPT];
+        out->n_trimmed = t.h_pp_tot.p[pfq::PREP_TOT_TRIMMED];
     }
     out->n_kept = n_kept;
     if (want_reads) {
@@ -4578,7 +4563,7 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         t.ov_out.n_fragments = n_reads / 2;
         t.out_ov_hist.assign(pfq::OVL_HIST, 0);
         if (n_reads) {
-            const unsigned long long *ot = t.h_pp_tot + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N;
+            const unsigned long long *ot = t.h_pp_tot.p + pfq::PREP_TOT_N + 1 + pfq::ADAPT_TOT_N;
             t.ov_out.n_analysed = ot[pfq::OVL_TOT_ANALYSED];
             t.ov_out.n_skipped = ot[pfq::OVL_TOT_SKIPPED];
             t.ov_out.n_overlapped = ot[pfq::OVL_TOT_FOUND];
@@ -4596,7 +4581,7 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
             t.mc_out.n_patches = n_patches;
         }
         if (n_reads) {
-            const unsigned long long *ct = t.h_pp_tot + at_ctot;
+            const unsigned long long *ct = t.h_pp_tot.p + at_ctot;
             t.mc_out.n_fragments_corrected = ct[pfq::COR_TOT_FRAGMENTS];
             t.mc_out.n_bases[0] = ct[pfq::COR_TOT_BASES];
             t.mc_out.n_bases[1] = ct[pfq::COR_TOT_BASES + 1];
@@ -4608,7 +4593,7 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         t.ad_out = pfq_prep_adapters{};
         t.ad_out.n_reads = n_reads;
         if (n_reads) {
-            const unsigned long long *at = t.h_pp_tot + pfq::PREP_TOT_N + 1;
+            const unsigned long long *at = t.h_pp_tot.p + pfq::PREP_TOT_N + 1;
             t.ad_out.n_found = at[pfq::ADAPT_TOT_FOUND];
             t.ad_out.bases_cut = at[pfq::ADAPT_TOT_BASES];
             for (uint32_t i = 0; i < 2 * PFQ_ADAPTER_MAX; ++i) t.ad_out.found[i] = at[pfq::ADAPT_TOT_WHICH + i];
@@ -4622,7 +4607,7 @@ int pfq_prep_reads(pfq_tree *tree, const uint8_t *seq, const uint8_t *qual, cons
         out->reason = t.out_pp_reason.data();
         out->kept = t.out_pp_kept.data();
     }
-    t.pp_slot = slot;
+    t.pp_sets.cur = slot;
     t.pp_kept = n_kept;
     t.pp_bases = out->bases_kept;
     t.pp_paired = paired;
@@ -4702,13 +4687,8 @@ int pfq_prep_last_adapters(pfq_tree *tree, pfq_prep_adapters *out) {
 }
 
 int pfq_debug_last_adapters(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->pp_timed || !tree->ad_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_adapters: the last pfq_prep_reads with reads on this tree ran without adapters");
-    PFQ_TRY(use_device(tree->device));
-    float v = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&v, tree->ad_time[0], tree->ad_time[1]));
-    *ms = v;
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::ad_time, tree && tree->pp_time.valid,
+                         "pfq_debug_last_adapters: the last pfq_prep_reads with reads on this tree ran without adapters");
 }
 
 // ---- mate overlap ------------------------------------------------------------------------------------------------------------
@@ -4746,13 +4726,8 @@ int pfq_prep_last_overlap(pfq_tree *tree, pfq_prep_overlap *out) {
 }
 
 int pfq_debug_last_overlap(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->pp_timed || !tree->ov_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_overlap: the last pfq_prep_reads with reads on this tree ran without the mate overlap");
-    PFQ_TRY(use_device(tree->device));
-    float v = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&v, tree->ov_time[0], tree->ov_time[1]));
-    *ms = v;
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::ov_time, tree && tree->pp_time.valid,
+                         "pfq_debug_last_overlap: the last pfq_prep_reads with reads on this tree ran without the mate overlap");
 }
 
 // ---- mate correction ---------------------------------------------------------------------------------------------------------
@@ -4785,14 +4760,8 @@ int pfq_prep_last_corrections(pfq_tree *tree, pfq_prep_corrections *out) {
 }
 
 int pfq_debug_last_corrections(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->pp_timed || !tree->mc_timed)
-        return fail(PFQ_ERR_STATE, "pfq_debug_last_corrections: the last pfq_prep_reads with reads on this tree wrote no patch list (the mate correction and PFQ_PREP_WANT_READS)");
-    PFQ_TRY(use_device(tree->device));
-    float v = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&v, tree->mc_time[0], tree->mc_time[1]));
-    *ms = v;
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::mc_time, tree && tree->pp_time.valid,
+                         "pfq_debug_last_corrections: the last pfq_prep_reads with reads on this tree wrote no patch list (the mate correction and PFQ_PREP_WANT_READS)");
 }
 
 int pfq_prep_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hits) {
@@ -4803,11 +4772,10 @@ int pfq_prep_query(pfq_tree *tree, float threshold, uint32_t flags, pfq_hits *hi
         return fail(PFQ_ERR_ARG, "pfq_prep_query: PFQ_PAIRED on a block prepared without PFQ_PREP_PAIRED (its kept reads are not whole fragments)");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
-    const int slot = t.pp_slot;
+    const int slot = t.pp_sets.cur;
     HIP_TRY(hipStreamWaitEvent(nullptr, t.pp_ready, 0));  // (the classification is ordered behind the prep on the device)
     const int rc = query_device(t, t.d_pp_seq[slot].p, t.d_pp_off[slot].p, t.pp_kept, t.pp_bases, threshold, flags, nullptr, hits);
-    HIP_TRY(hipEventRecord(t.pp_free[slot], nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
-    t.pp_used[slot] = true;
+    HIP_TRY(t.pp_sets.read_by(slot, nullptr));  // (also behind a call that failed half-way: what it queued may read the set)
     PFQ_TRY(rc);
     if (flags & PFQ_WANT_HITS) HIP_TRY(hipStreamSynchronize(nullptr));
     return PFQ_OK;
@@ -4818,21 +4786,14 @@ int pfq_debug_prep_csr(pfq_tree *tree, uint8_t *seq_out, uint64_t *off_out) {
     if (!tree->pp_have) return fail(PFQ_ERR_STATE, "pfq_debug_prep_csr before a pfq_prep_reads on this tree");
     PFQ_TRY(use_device(tree->device));
     const pfq_tree &t = *tree;
-    if (t.pp_bases) HIP_TRY(hipMemcpy(seq_out, t.d_pp_seq[t.pp_slot].p, t.pp_bases, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(off_out, t.d_pp_off[t.pp_slot].p, (t.pp_kept + 1) * 8, hipMemcpyDeviceToHost));
+    if (t.pp_bases) HIP_TRY(hipMemcpy(seq_out, t.d_pp_seq[t.pp_sets.cur].p, t.pp_bases, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(off_out, t.d_pp_off[t.pp_sets.cur].p, (t.pp_kept + 1) * 8, hipMemcpyDeviceToHost));
     return PFQ_OK;
 }
 
 int pfq_debug_last_prep(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->pp_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_prep before a pfq_prep_reads with reads on this tree");
-    PFQ_TRY(use_device(tree->device));
-    for (int i = 0; i < 3; ++i) {
-        float v = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&v, tree->pp_time[i], tree->pp_time[i + 1]));
-        ms[i] = v;
-    }
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::pp_time, true,
+                         "pfq_debug_last_prep before a pfq_prep_reads with reads on this tree");
 }
 
 // ---- depletion ---------------------------------------------------------------------------------------------------------------
@@ -4863,28 +4824,26 @@ int pfq_prep_deplete(pfq_tree *tree, pfq_tree *screen, float threshold, uint32_t
     const bool paired = (flags & PFQ_PAIRED) != 0;
     const uint32_t per = paired ? 2u : 1u;
     const uint64_t n_reads = t.pp_reads, n_before = t.pp_kept, n_units = n_before / per;
-    const int slot = t.pp_slot;
+    const int slot = t.pp_sets.cur;
     hipStream_t st = t.copy_stream;
-    if (!t.h_dp_tot) {
-        for (auto &e : t.dp_time) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&t.h_dp_tot), (pfq::DEPL_TOT_N + 2) * 8, hipHostMallocDefault));
-        HIP_TRY(t.d_dp_tot.ensure(pfq::DEPL_TOT_N));
-    }
+    HIP_TRY(t.dp_time.ensure());
+    HIP_TRY(t.h_dp_tot.ensure(pfq::DEPL_TOT_N + 2));
+    HIP_TRY(t.d_dp_tot.ensure(pfq::DEPL_TOT_N));
     *out = pfq_prep_depleted{};
     out->n_units = n_units;
     uint64_t n_kept = n_before, bases_kept = t.pp_bases;
     if (n_units) {
         // (a classification of this block that pfq_prep_query has queued still reads the slot the gather below rewrites)
-        if (t.pp_used[slot]) HIP_TRY(hipEventSynchronize(t.pp_free[slot]));
+        HIP_TRY(t.pp_sets.wait(slot));
         if (!paired) {
             HIP_TRY(t.d_dp_hit.ensure(n_units));
             HIP_TRY(hipMemsetAsync(t.d_dp_hit.p, 0, n_units * 4, st));
         }
         HIP_TRY(hipMemsetAsync(t.d_dp_tot.p, 0, pfq::DEPL_TOT_N * 8, st));
-        HIP_TRY(hipEventRecord(t.dp_time[0], st));
-        t.dp_timed = false;
+        HIP_TRY(t.dp_time.mark(0, st));
+        t.dp_time.valid = false;
         PFQ_TRY(query_device(s, t.d_pp_seq[slot].p, t.d_pp_off[slot].p, n_before, t.pp_bases, threshold, flags, st, nullptr, true, t.d_dp_hit.p));
-        HIP_TRY(hipEventRecord(t.dp_time[1], st));
+        HIP_TRY(t.dp_time.mark(1, st));
         pfq::DepleteArgs d{};
         d.hit = t.d_dp_hit.p;
         d.allhit = s.d_allhit.p;
@@ -4917,19 +4876,19 @@ int pfq_prep_deplete(pfq_tree *tree, pfq_tree *screen, float threshold, uint32_t
         a.csr_off = t.d_pp_off[slot].p;
         a.out = t.d_pp_seq[slot].p;
         pfq::launch_prep_gather(a, st);
-        HIP_TRY(hipEventRecord(t.dp_time[2], st));
+        HIP_TRY(t.dp_time.mark(2, st));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(t.h_dp_tot, t.d_dp_tot.p, pfq::DEPL_TOT_N * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(t.h_dp_tot + pfq::DEPL_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(t.h_dp_tot + pfq::DEPL_TOT_N + 1, t.d_pp_koff.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot.p, t.d_dp_tot.p, pfq::DEPL_TOT_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot.p + pfq::DEPL_TOT_N, t.d_pp_kpos.p + n_reads, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(t.h_dp_tot.p + pfq::DEPL_TOT_N + 1, t.d_pp_koff.p + n_reads, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(t.pp_ready, st));
         HIP_TRY(hipStreamSynchronize(st));
-        t.dp_timed = true;
-        out->units_removed = t.h_dp_tot[pfq::DEPL_TOT_UNITS];
-        out->reads_removed = t.h_dp_tot[pfq::DEPL_TOT_READS];
-        out->bases_removed = t.h_dp_tot[pfq::DEPL_TOT_BASES];
-        n_kept = t.h_dp_tot[pfq::DEPL_TOT_N];
-        bases_kept = t.h_dp_tot[pfq::DEPL_TOT_N + 1];
+        t.dp_time.valid = true;
+        out->units_removed = t.h_dp_tot.p[pfq::DEPL_TOT_UNITS];
+        out->reads_removed = t.h_dp_tot.p[pfq::DEPL_TOT_READS];
+        out->bases_removed = t.h_dp_tot.p[pfq::DEPL_TOT_BASES];
+        n_kept = t.h_dp_tot.p[pfq::DEPL_TOT_N];
+        bases_kept = t.h_dp_tot.p[pfq::DEPL_TOT_N + 1];
         t.pp_kept = n_kept;
         t.pp_bases = bases_kept;
     }
@@ -4954,15 +4913,8 @@ int pfq_prep_deplete(pfq_tree *tree, pfq_tree *screen, float threshold, uint32_t
 }
 
 int pfq_debug_last_deplete(pfq_tree *tree, double *ms) {
-    if (!tree || !ms) return fail(PFQ_ERR_ARG, "null argument");
-    if (!tree->dp_timed) return fail(PFQ_ERR_STATE, "pfq_debug_last_deplete before a pfq_prep_deplete with units on this tree");
-    PFQ_TRY(use_device(tree->device));
-    for (int i = 0; i < 2; ++i) {
-        float v = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&v, tree->dp_time[i], tree->dp_time[i + 1]));
-        ms[i] = v;
-    }
-    return PFQ_OK;
+    return last_stage_ms(tree, ms, &pfq_tree::dp_time, true,
+                         "pfq_debug_last_deplete before a pfq_prep_deplete with units on this tree");
 }
 
 int pfq_last_hit_scores(pfq_tree *tree, const uint32_t **scores, uint64_t *n_hits) {
@@ -5504,12 +5456,11 @@ int pfq_tree_similarity(pfq_tree *a, const uint32_t *leaves_a, uint64_t n_a, pfq
         const uint32_t slices = ta.knobs.sim_slices > 0 ? (uint32_t)std::min<long long>(ta.knobs.sim_slices, 65535) : 0;
         // PFQ_SIM_TIME=1 (tools/sim_bench.py): two HIP events round the intersection kernel alone; otherwise no call pays for them
         const bool timed = ta.knobs.sim_time == 1;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        Event ev[2];
         if (timed) {
-            HIP_TRY(hipEventCreate(&ev[0]));
-            if (hipEventCreate(&ev[1]) != hipSuccess) {
+            HIP_TRY(ev[0].ensure());
+            if (ev[1].ensure() != hipSuccess) {
                 (void)hipGetLastError();
-                (void)hipEventDestroy(ev[0]);
                 return fail(PFQ_ERR_DEVICE, "pfq_tree_similarity: hipEventCreate failed");
             }
             (void)hipEventRecord(ev[0], nullptr);
@@ -5520,8 +5471,6 @@ int pfq_tree_similarity(pfq_tree *a, const uint32_t *leaves_a, uint64_t n_a, pfq
         if (timed) {
             (void)hipEventRecord(ev[1], nullptr);
             if (hipEventSynchronize(ev[1]) == hipSuccess) (void)hipEventElapsedTime(&ta.sim_kernel_ms, ev[0], ev[1]);
-            (void)hipEventDestroy(ev[0]);
-            (void)hipEventDestroy(ev[1]);
         }
         pfq::launch_filter_row_bits(ta.d_bits.p, d_rows.p, (uint32_t)n_a, ta.n_words, ta.nbits, d_pop.p, nullptr);
         pfq::launch_filter_row_bits(tb.d_bits.p, d_rows.p + n_a, (uint32_t)n_b, tb.n_words, tb.nbits, d_pop.p + n_a, nullptr);
@@ -5574,20 +5523,17 @@ namespace {
 // HIP events of a PFQ_CLUSTER_TIME=1 call: pairs (begin, end) per measured stretch, destroyed with the call
 struct ClusterTimer {
     bool on = false;
-    std::vector<hipEvent_t> ev;
-    ~ClusterTimer() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    std::vector<Event> ev;
     size_t mark() {  // records an event on the null stream; its index
         if (!on) return 0;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) {
+        Event e;
+        if (e.ensure() != hipSuccess) {
             (void)hipGetLastError();
             on = false;
             return 0;
         }
         (void)hipEventRecord(e, nullptr);
-        ev.push_back(e);
+        ev.push_back(std::move(e));
         return ev.size() - 1;
     }
     float between(size_t a, size_t b) const {
@@ -6201,11 +6147,8 @@ int pfq_profile_begin(pfq_tree *tree, uint32_t max_calls) {
     if (!tree) return fail(PFQ_ERR_ARG, "null argument");
     PFQ_TRY(use_device(tree->device));
     pfq_tree &t = *tree;
-    while (t.prof_ev.size() < PROF_EV * (size_t)max_calls) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        t.prof_ev.push_back(e);
-    }
+    if (t.prof_ev.size() < PROF_EV * (size_t)max_calls) t.prof_ev.resize(PROF_EV * (size_t)max_calls);
+    for (Event &e : t.prof_ev) HIP_TRY(e.ensure());
     t.prof_cap = max_calls;
     t.prof_used = 0;
     t.prof_bucketed.assign(max_calls, 0);
@@ -6218,7 +6161,7 @@ int pfq_profile_end(pfq_tree *tree, pfq_profile *out) {
     memset(out, 0, sizeof *out);
     PFQ_TRY(wait_last_call(t));
     for (size_t c = 0; c < t.prof_used; ++c) {
-        hipEvent_t *ev = &t.prof_ev[PROF_EV * c];
+        const Event *ev = &t.prof_ev[PROF_EV * c];
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
         out->classify_ms += ms;
